@@ -6,9 +6,11 @@ Workload (BASELINE.json metric / configs[2]): 2-D 5-point Poisson 4096 x 4096
 2 sweeps pre + 2 post on every level, 16-level hierarchy (coarsest 511 dofs),
 fp64.  One "step" = one vcycle() (multigrid.hpp:263-305), rss excluded.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-N = 1: one process, one GPU.  N > 1: launched by torch.distributed.run, one rank
+N = 1: one process, one GPU.  A plain run sets up, warms up, times the K steps and prints the
+headline; --full adds the convergence check, the roofline figures, the plain-CSR layout run and
+the CPU baseline.  N > 1: launched by torch.distributed.run, one rank
 per GPU, row-block sharded hierarchy with RCCL halo exchange (see
 algebraic-multigrid_amd/dist_vcycle.py); fixed global problem => strong scaling.
 Rank 0 prints ONE JSON line.
@@ -123,6 +125,22 @@ def cpu_baseline(args):
     }
 
 
+DUMP_MAX_VALUES = 1 << 22   # 32 MiB of fp64 per dumped array
+
+
+def dump_outputs(mg, out_dir):
+    """Writes what a caller of the timed vcycle() receives: the fine-grid solution u (get_soln),
+    fp64, as out_dir/u.npy.  Above DUMP_MAX_VALUES entries a fixed sample of that many, at
+    sorted indices drawn with seed 0, so that runs with the same --grid / --dim compare entry
+    for entry."""
+    import numpy as np
+    u = mg.get_soln(0)
+    if u.size > DUMP_MAX_VALUES:
+        u = u[np.sort(np.random.default_rng(0).choice(u.size, DUMP_MAX_VALUES, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "u.npy"), u)
+
+
 def run_single(args):
     import amg_ctypes as amg
     if amg.device_count() < 1:
@@ -155,20 +173,17 @@ def run_single(args):
     setup_s = time.time() - t0
     mg.vcycle(args.warmup)
     mg.sync()
-    rss0 = mg.rss()   # after the warm-up cycles (the first cycle from u=0 raises rss)
+    if args.full:
+        rss0 = mg.rss()   # after the warm-up cycles (the first cycle from u=0 raises rss)
     t1 = time.perf_counter()
     mg.vcycle(args.steps)
     mg.sync()
     dt = time.perf_counter() - t1
-    cyc_bytes, sweep_bytes = mg.cycle_bytes()
-    rss = mg.rss()
-    # every configuration must reduce rss over the timed cycles; the ratio is recorded
-    if args.warmup >= 1 and not (rss < rss0):
-        raise SystemExit(f"V-cycle iteration is not converging (rss {rss0:.3e} -> {rss:.3e})")
+    if args.dump_outputs:
+        dump_outputs(mg, args.dump_outputs)
     sizes = [mg.get_n_dofs(l) for l in range(L)]
     lay, mat_bytes = mg.level_layout(0)
     lay_name = {amg.LAYOUT_CSR: "csr", amg.LAYOUT_SELL: "sell", amg.LAYOUT_DICT: "dict"}[lay]
-    must = mg.cycle_must_move()
     problem = (f"2D 5-point Poisson {args.n}x{args.n} (Grid::laplacian/rhs)" if dim == 2 else
                f"3D 7-point Poisson {args.n}^3 (the 7-point analogue of Grid::laplacian/rhs)")
     out = {
@@ -193,16 +208,27 @@ def run_single(args):
             "n": args.n, "dim": dim, "levels": L, "smoother": args.smoother, "omega": args.omega,
             "sweeps": args.sweeps, "graph": not args.no_graph, "coarse_solve": mg.coarse_solve_kind(),
             "layout": lay_name, "setup_seconds": setup_s,
-            "rss_after_warmup": rss0, "rss_after_steps": rss,
-            "rss_ratio_per_cycle": (rss / rss0) ** (1.0 / args.steps) if rss0 > 0 else None,
-            "csr_formula_cycle_bytes": cyc_bytes,
-            # the whole cycle against the HBM roof: bytes every launch of the cycle has to move in the
-            # layout it streams (amg_hip_cycle_must_move) / measured time per cycle
-            "whole_cycle": {"must_move_bytes": must, "GBps": must / (dt / args.steps) / 1e9,
-                            "frac_of_hbm_peak": must / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
         },
-        "roofline": fine_sweep_roofline(amg, mg, args, lay_name, mat_bytes, sizes[0], sweep_bytes),
     }
+    if not args.full:
+        mg.close()
+        return out
+    cyc_bytes, sweep_bytes = mg.cycle_bytes()
+    rss = mg.rss()
+    # every configuration must reduce rss over the timed cycles; the ratio is recorded
+    if args.warmup >= 1 and not (rss < rss0):
+        raise SystemExit(f"V-cycle iteration is not converging (rss {rss0:.3e} -> {rss:.3e})")
+    must = mg.cycle_must_move()
+    out["config"].update({
+        "rss_after_warmup": rss0, "rss_after_steps": rss,
+        "rss_ratio_per_cycle": (rss / rss0) ** (1.0 / args.steps) if rss0 > 0 else None,
+        "csr_formula_cycle_bytes": cyc_bytes,
+        # the whole cycle against the HBM roof: bytes every launch of the cycle has to move in the
+        # layout it streams (amg_hip_cycle_must_move) / measured time per cycle
+        "whole_cycle": {"must_move_bytes": must, "GBps": must / (dt / args.steps) / 1e9,
+                        "frac_of_hbm_peak": must / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
+    })
+    out["roofline"] = fine_sweep_roofline(amg, mg, args, lay_name, mat_bytes, sizes[0], sweep_bytes)
     mg.close()
     # the same workload with the level matrices as plain CSR panels (SELL-64): the layout
     # SURVEY 8(d)'s CSR-formula bytes describe; a second, shorter measurement in the same run
@@ -317,6 +343,13 @@ def main():
                     help="partitioned (parallel) coarse solve; then fewer levels pay off (--levels 13)")
     ap.add_argument("--host-setup", action="store_true",
                     help="build the hierarchy from host arrays (amg_hip_create) instead of on the device")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: also the rss convergence check, the whole-cycle and fine-sweep "
+                         "roofline figures, the plain-CSR (SELL-64) measurement and the CPU baseline "
+                         "(a multi-GPU run always reports all it measures)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: after the timed steps write the fine-grid solution as DIR/u.npy "
+                         "(fp64; a seeded sample of 2^22 entries on larger grids)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-csr-ref", action="store_true",
                     help="skip the second measurement with the plain-CSR (SELL-64) layout")
@@ -359,6 +392,8 @@ def main():
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 or world > 1:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: one-GPU runs only")
         import dist_vcycle
         out = dist_vcycle.bench(args)
         if out is not None:

@@ -71,3 +71,30 @@ def test_multi_gpu_default_is_the_safe_transport_set():
         sys.argv = argv
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'choices=["safe", "auto", "p2p", "slab", "window", "library", "ipc", "graph"], default="safe"' in src
+
+
+def test_dump_outputs_writes_the_whole_solution_or_a_fixed_sample(tmp_path):
+    import numpy as np
+    import bench
+
+    class FakeSolver:
+        def __init__(self, n):
+            self.u = np.arange(n, dtype=np.float64) * 0.5
+
+        def get_soln(self, level=0):
+            assert level == 0
+            return self.u.copy()
+
+    small = FakeSolver(1000)
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    u = np.load(tmp_path / "small" / "u.npy")
+    assert u.dtype == np.float64 and np.array_equal(u, small.u)
+
+    big = FakeSolver(bench.DUMP_MAX_VALUES * 2 + 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    a, b = np.load(tmp_path / "a" / "u.npy"), np.load(tmp_path / "b" / "u.npy")
+    assert a.dtype == np.float64 and a.size == bench.DUMP_MAX_VALUES and a.nbytes <= 64 * 2 ** 20
+    assert np.array_equal(a, b)                                  # the same sample every run
+    idx = (a * 2).astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[-1] < big.u.size   # distinct entries, in order
