@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libamg_hip.so")
 
 OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED, ECOMM = 0, 1, 2, 3, 4, 5
-SM_SPGS, SM_REF_JACOBI, SM_SOR, SM_JACOBI, SM_MULTICOLOR_GS = 0, 1, 2, 3, 4
+SM_SPGS, SM_REF_JACOBI, SM_SOR, SM_JACOBI, SM_MULTICOLOR_GS, SM_CHEBYSHEV = 0, 1, 2, 3, 4, 5
 LAYOUT_AUTO, LAYOUT_CSR, LAYOUT_SELL, LAYOUT_DICT = 0, 1, 2, 3
 
 _i32p = C.POINTER(C.c_int32)
@@ -39,7 +39,8 @@ class Options(C.Structure):
                 ("fast_coarse_solve", C.c_int32), ("host_galerkin", C.c_int32),
                 ("keep_residual", C.c_int32), ("exact_coarse_solve", C.c_int32),
                 ("exact_gs", C.c_int32),
-                ("stream", C.c_void_p), ("window", C.c_int32), ("reserved0", C.c_int32)]
+                ("stream", C.c_void_p), ("window", C.c_int32), ("cheb_degree", C.c_int32),
+                ("cheb_lower", C.c_double), ("cheb_upper", C.c_double)]
 
 
 SLAB_MAX_LEVELS = 8
@@ -154,6 +155,9 @@ _SIGS = {
     "amg_hip_level_layout": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "amg_hip_get_colors": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i32p]),
     "amg_hip_level_op": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "amg_hip_cheb_bounds": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f64p]),
+    "amg_hip_smooth_chebyshev": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int32,
+                                           C.c_double, C.c_double, C.c_int64]),
     "amg_hip_cycle_bytes": (C.c_int, [C.c_void_p, _f64p, _f64p]),
     "amg_hip_cycle_must_move": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
     "amg_hip_profile_fine_sweep": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f64p]),
@@ -267,6 +271,10 @@ def set_default_layout(layout):
 
 def set_index16(on):
     lib().amg_hip_set_index16(int(on))
+
+
+def set_nontemporal(on):
+    lib().amg_hip_set_nontemporal(int(on))
 
 
 def set_dict_rows(rows_per_lane):
@@ -385,7 +393,7 @@ class Multigrid:
                  transfers=None, layout=None, host_only=False, keep_structural_zeros=False,
                  no_fusion=False, fuse_prolong=False, stream=None, fast_coarse_solve=False,
                  host_galerkin=False, keep_residual=False, exact_coarse_solve=False,
-                 exact_gs=False):
+                 exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0):
         # multigrid.hpp:165-178 (same checks, same order)
         if compute_error_every_n_iters > n_iters:
             raise ValueError("`compute_error_every_n_iters` must be leq to `n_iters`, got "
@@ -400,7 +408,8 @@ class Multigrid:
         self.n_iters = n_iters
         o = self._options(smoother, smoother_iters, omega, device, use_graph, stencil_transfers, layout,
                           host_only, keep_structural_zeros, no_fusion, fuse_prolong, stream,
-                          fast_coarse_solve, host_galerkin, keep_residual, exact_coarse_solve, exact_gs)
+                          fast_coarse_solve, host_galerkin, keep_residual, exact_coarse_solve, exact_gs,
+                          cheb_degree, cheb_lower, cheb_upper)
         h = C.c_void_p()
         if transfers is None:
             st = lib().amg_hip_create(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b),
@@ -434,7 +443,8 @@ class Multigrid:
     @staticmethod
     def _options(smoother, smoother_iters, omega, device, use_graph, stencil_transfers, layout,
                  host_only, keep_structural_zeros, no_fusion, fuse_prolong, stream,
-                 fast_coarse_solve, host_galerkin, keep_residual, exact_coarse_solve, exact_gs):
+                 fast_coarse_solve, host_galerkin, keep_residual, exact_coarse_solve, exact_gs,
+                 cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0):
         o = Options()
         lib().amg_hip_default_options(C.byref(o))
         o.smoother, o.smoother_iters, o.omega = smoother, smoother_iters, omega
@@ -450,6 +460,7 @@ class Multigrid:
         o.keep_residual = int(keep_residual)
         o.exact_coarse_solve = int(exact_coarse_solve)
         o.exact_gs = int(exact_gs)
+        o.cheb_degree, o.cheb_lower, o.cheb_upper = int(cheb_degree), float(cheb_lower), float(cheb_upper)
         if stream:
             o.stream = C.c_void_p(stream)
         return o
@@ -459,7 +470,7 @@ class Multigrid:
                      smoother=SM_SPGS, smoother_iters=1, omega=1.0, tolerance=1e-9,
                      compute_error_every_n_iters=10, n_iters=100, device=-1, use_graph=True, layout=None,
                      host_only=False, stream=None, host_galerkin=False, exact_coarse_solve=False,
-                     exact_gs=False):
+                     exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0):
         """AMG::Multigrid on a strength-based C/F hierarchy (amg_hip_create_rs): same V-cycle,
         coarsening by the classical Ruge-Stueben first pass with direct interpolation.
         `self.n_levels` tells how many levels were built."""
@@ -472,7 +483,7 @@ class Multigrid:
         self.tolerance, self.every, self.n_iters = tolerance, compute_error_every_n_iters, n_iters
         o = cls._options(smoother, smoother_iters, omega, device, use_graph, True, layout, host_only,
                          False, False, False, stream, False, host_galerkin, False, exact_coarse_solve,
-                         exact_gs)
+                         exact_gs, cheb_degree, cheb_lower, cheb_upper)
         h = C.c_void_p()
         st = lib().amg_hip_create_rs(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), int(max_levels),
                                      float(theta), int(min_coarse), C.byref(o), C.byref(h))
@@ -487,7 +498,7 @@ class Multigrid:
                 compute_error_every_n_iters=10, n_iters=100, device=-1, use_graph=True,
                 stencil_transfers=True, layout=None, keep_structural_zeros=False, no_fusion=False,
                 stream=None, fast_coarse_solve=False, keep_residual=False, exact_coarse_solve=False,
-                exact_gs=False):
+                exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0):
         """AMG::Multigrid on A = Grid::laplacian(n), b = Grid::rhs(n) with the setup on the device
         end to end (amg_hip_create_poisson): no host matrices."""
         if compute_error_every_n_iters > n_iters:
@@ -497,7 +508,8 @@ class Multigrid:
         self.tolerance, self.every, self.n_iters = tolerance, compute_error_every_n_iters, n_iters
         o = cls._options(smoother, smoother_iters, omega, device, use_graph, stencil_transfers, layout,
                          False, keep_structural_zeros, no_fusion, False, stream, fast_coarse_solve,
-                         False, keep_residual, exact_coarse_solve, exact_gs)
+                         False, keep_residual, exact_coarse_solve, exact_gs, cheb_degree, cheb_lower,
+                         cheb_upper)
         h = C.c_void_p()
         st = lib().amg_hip_create_poisson(dim, n, n_levels, C.byref(o), C.byref(h))
         if st == EINVAL:
@@ -653,6 +665,15 @@ class Multigrid:
         _chk(lib().amg_hip_fine_sweep_info(self._h, name, 256, C.byref(k), C.byref(nb)))
         return name.value.decode(), k.value, nb.value
 
+    def cheb_bounds(self, level):
+        """(lo, hi): the interval the Chebyshev smoother uses on `level` (amg_hip_cheb_bounds)."""
+        lo, hi = C.c_double(0), C.c_double(0)
+        st = lib().amg_hip_cheb_bounds(self._h, int(level), C.byref(lo), C.byref(hi))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return lo.value, hi.value
+
     def coarse_solve_kind(self):
         return {0: "band (one wave, sequential, bit-exact)", 1: "spike (partitioned, parallel)",
                 2: "band-wide (blocked sequential, any half-bandwidth, bit-exact)",
@@ -719,6 +740,18 @@ def smooth(kind, colptr, rowind, val, u, b, n_iters=1, omega=1.0, tol=1e-9, ever
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)
     return u, it.value, bool(conv.value)
+
+
+def smooth_chebyshev(colptr, rowind, val, u, b, degree=2, lower=0.3, upper=1.0, n_iters=1):
+    """amg_hip_smooth_chebyshev: n_iters applications of the Chebyshev polynomial; returns the new u."""
+    colptr, rowind, val, b = _a32(colptr), _a32(rowind), _a64(val), _a64(b)
+    u = np.array(u, dtype=np.float64, copy=True)
+    st = lib().amg_hip_smooth_chebyshev(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), _p64(u),
+                                        _p64(b), int(degree), float(lower), float(upper), int(n_iters))
+    if st == EINVAL:
+        raise ValueError(lib().amg_hip_last_error().decode())
+    _chk(st)
+    return u
 
 
 def spgs_sweep(direction, colptr, rowind, val, u, b):

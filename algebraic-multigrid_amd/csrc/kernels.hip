@@ -57,6 +57,23 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// Chebyshev steps (kernels.hpp: CSR_CHEB, cheb_kernel_mode): template MODE 16 + first + 2 last.  The
+// row walk is CSR_JACOBI's unchanged (same products, same order, same division); only the epilogue
+// differs, so the results are bit-identical across layouts as the Jacobi sweeps are.
+constexpr bool mode_cheb(int m) { return (m & ~3) == 16; }
+constexpr bool mode_jac(int m) { return m == CSR_JACOBI || mode_cheb(m); }
+constexpr bool cheb_first(int m) { return (m & 1) != 0; }
+constexpr bool cheb_last(int m) { return (m & 2) != 0; }
+// t = the Jacobi quotient t_i; z = t - x, d = alpha d + beta z (first step: beta z, d not read),
+// out = x + d.  A first step is CSR_JACOBI's x + omega (t - x) with omega = beta, operation for operation.
+template <int MODE>
+__device__ __forceinline__ double cheb_update(double t, double xi, double di, double alpha, double beta,
+                                              double& dn) {
+  const double z = t - xi;
+  dn = cheb_first(MODE) ? beta * z : alpha * di + beta * z;
+  return xi + dn;
+}
+
 // ------------------------------------------------------------------ K-CSR ----
 constexpr int CSR_BLOCK = 256;
 
@@ -65,7 +82,7 @@ __global__ __launch_bounds__(CSR_BLOCK) void csr_stage_kernel(
     int64_t n, int64_t nnz, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const double* __restrict__ val,
     const double* __restrict__ x, const double* f,  // f may be out (CSR_SPMV_ADD in place)
-    double* out, double omega, int64_t diag_shift) {
+    double* out, double omega, int64_t diag_shift, double* dvec, double alpha) {
   constexpr int CAP = CSR_BLOCK * K;  // entries staged per chunk
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* lds_val = reinterpret_cast<double*>(smem);                    // CAP + 4
@@ -79,12 +96,13 @@ __global__ __launch_bounds__(CSR_BLOCK) void csr_stage_kernel(
   const int64_t p0 = rowptr[r0];
   const int64_t p1 = rowptr[rlast];
   int64_t rs = 0, re = 0;
-  double fi = 0.0, xi = 0.0;
+  double fi = 0.0, xi = 0.0, di = 0.0;
   if (live) {
     rs = rowptr[row];
     re = rowptr[row + 1];
     if (MODE != CSR_SPMV) fi = f[row];
-    if (MODE == CSR_JACOBI) xi = x[row + diag_shift];
+    if (mode_jac(MODE)) xi = x[row + diag_shift];
+    if (mode_cheb(MODE) && !cheb_first(MODE)) di = dvec[row];
   }
   double acc = (MODE == CSR_RESID) ? fi : 0.0;
   double diag = 0.0;
@@ -139,7 +157,7 @@ __global__ __launch_bounds__(CSR_BLOCK) void csr_stage_kernel(
         if (p + u < pe) {
           if (MODE == CSR_RESID) {
             acc -= v[u] * xx[u];
-          } else if (MODE == CSR_JACOBI) {
+          } else if (mode_jac(MODE)) {
             if ((int64_t)c[u] == drow) diag = v[u];
             else acc += v[u] * xx[u];
           } else {
@@ -158,6 +176,10 @@ __global__ __launch_bounds__(CSR_BLOCK) void csr_stage_kernel(
       out[row] = fi + acc;  // t = P u_H summed from 0, then u_h + t: the reference's two statements
     } else if (MODE == CSR_JACOBI) {
       out[row] = (diag == 0.0) ? xi : xi + omega * ((fi - acc) / diag - xi);
+    } else if (mode_cheb(MODE)) {
+      double dn;
+      out[row] = cheb_update<MODE>((diag == 0.0) ? xi : (fi - acc) / diag, xi, di, alpha, omega, dn);
+      if (!cheb_last(MODE)) dvec[row] = dn;
     } else {  // CSR_RSSQ: (b - bhat)^2, common.hpp:24
       const double d = fi - acc;
       out[row] = d * d;
@@ -169,12 +191,13 @@ template <int MODE, int K, int U>
 static hipError_t launch_csr_ku(int64_t n, int64_t nnz, const int32_t* rowptr,
                                 const int32_t* col, const double* val,
                                 const double* x, const double* f, double* out,
-                                double omega, int64_t diag_shift, hipStream_t st) {
+                                double omega, int64_t diag_shift, hipStream_t st,
+                                double* dvec = nullptr, double alpha = 0.0) {
   if (n <= 0) return hipSuccess;
   const size_t lds = (size_t)(CSR_BLOCK * K + 4) * 12;
   const unsigned grid = (unsigned)((n + CSR_BLOCK - 1) / CSR_BLOCK);
   hipLaunchKernelGGL((csr_stage_kernel<MODE, K, U>), dim3(grid), dim3(CSR_BLOCK), lds,
-                     st, n, nnz, rowptr, col, val, x, f, out, omega, diag_shift);
+                     st, n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, dvec, alpha);
   return hipGetLastError();
 }
 
@@ -183,21 +206,27 @@ static hipError_t launch_csr_mode(int64_t n, int64_t nnz, int max_block_nnz,
                                   int max_row_nnz, const int32_t* rowptr,
                                   const int32_t* col, const double* val,
                                   const double* x, const double* f, double* out,
-                                  double omega, int64_t diag_shift, hipStream_t st) {
+                                  double omega, int64_t diag_shift, hipStream_t st,
+                                  double* dvec = nullptr, double alpha = 0.0) {
   // +3: the chunk start is rounded down to a multiple of 4 entries.  U (gathers
   // issued per pass of a lane over its row) is matched to the longest row: a
   // 5-point row walked with U = 8 wastes 3 LDS reads + 3 gathers (measured
   // 4.9 -> 5.6 TB/s on the 4096^2 fine level, tools/kbench.hip).
   const int need = max_block_nnz + 3;
   if (need <= CSR_BLOCK * 4 && max_row_nnz <= 3)
-    return launch_csr_ku<MODE, 4, 3>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st);
+    return launch_csr_ku<MODE, 4, 3>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st, dvec,
+                                      alpha);
   if (need <= CSR_BLOCK * 6 && max_row_nnz <= 5)
-    return launch_csr_ku<MODE, 6, 5>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st);
+    return launch_csr_ku<MODE, 6, 5>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st, dvec,
+                                      alpha);
   if (need <= CSR_BLOCK * 8 && max_row_nnz <= 7)
-    return launch_csr_ku<MODE, 8, 7>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st);
+    return launch_csr_ku<MODE, 8, 7>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st, dvec,
+                                      alpha);
   if (need <= CSR_BLOCK * 10 && max_row_nnz <= 9)
-    return launch_csr_ku<MODE, 10, 9>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st);
-  return launch_csr_ku<MODE, 16, 8>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st);
+    return launch_csr_ku<MODE, 10, 9>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st, dvec,
+                                      alpha);
+  return launch_csr_ku<MODE, 16, 8>(n, nnz, rowptr, col, val, x, f, out, omega, diag_shift, st, dvec,
+                                      alpha);
 }
 
 hipError_t launch_csr(int mode, int64_t n, int64_t nnz, int max_block_nnz,
@@ -222,6 +251,62 @@ hipError_t launch_csr(int mode, int64_t n, int64_t nnz, int max_block_nnz,
                                            val, x, f, out, omega, diag_shift, st);
   }
   return hipErrorInvalidValue;
+}
+hipError_t launch_csr_cheb(int64_t n, int64_t nnz, int max_block_nnz, int max_row_nnz, const int32_t* rowptr,
+                           const int32_t* col, const double* val, const double* x, const double* f, double* out,
+                           const ChebStep& c, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!c.d || x == out) return hipErrorInvalidValue;
+#define AMG_CSR_CHEB(FI, LA)                                                                            \
+  return launch_csr_mode<cheb_kernel_mode(FI, LA)>(n, nnz, max_block_nnz, max_row_nnz, rowptr, col, val, x, f, \
+                                                   out, c.beta, 0, st, c.d, c.alpha)
+  if (c.first && c.last) AMG_CSR_CHEB(true, true);
+  if (c.first) AMG_CSR_CHEB(true, false);
+  if (c.last) AMG_CSR_CHEB(false, true);
+  AMG_CSR_CHEB(false, false);
+#undef AMG_CSR_CHEB
+}
+
+// Gershgorin bound (kernels.hpp: launch_gershgorin): one lane per row, ascending column order as
+// the host sums; the max is order-independent, so the bound has the host's bits.  Non-negative
+// doubles order like their bit patterns: the block maximum goes out as one 64-bit atomic max.
+__global__ __launch_bounds__(256) void gershgorin_kernel(int64_t n, const int32_t* __restrict__ rowptr,
+                                                         const int32_t* __restrict__ col,
+                                                         const double* __restrict__ val,
+                                                         unsigned long long* out) {
+  __shared__ double red[256];
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double g = 0.0;
+  if (row < n) {
+    double sum = 0.0, dg = 0.0;
+    for (int32_t p = rowptr[row]; p < rowptr[row + 1]; ++p) {
+      const double v = val[p];
+      sum += fabs(v);
+      if ((int64_t)col[p] == row) dg = v;
+    }
+    if (dg == 0.0) atomicMin(out + 1, (unsigned long long)row);
+    else g = sum / fabs(dg);
+    if (!(g >= 0.0)) g = 0.0;  // NaN rows do not bound anything
+  }
+  red[threadIdx.x] = g;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicMax(out, (unsigned long long)__double_as_longlong(red[0]));
+}
+__global__ void gershgorin_init_kernel(unsigned long long* out) {
+  if (threadIdx.x < 2) out[threadIdx.x] = threadIdx.x == 0 ? 0ull : ~0ull;
+}
+hipError_t launch_gershgorin(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
+                             uint64_t* out, hipStream_t st) {
+  hipLaunchKernelGGL(gershgorin_init_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned long long*>(out));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || n <= 0) return e;
+  hipLaunchKernelGGL(gershgorin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, rowptr, col, val,
+                     reinterpret_cast<unsigned long long*>(out));
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------- K-SELL -----
@@ -252,7 +337,7 @@ __global__ __launch_bounds__(256) void sell_kernel(
     int n, const int64_t* __restrict__ soff, const void* __restrict__ scol_v,
     const double* __restrict__ sval, const double* x, const double* __restrict__ f,
     double* out, double omega, const int32_t* __restrict__ rowid, int row0,
-    const double* __restrict__ uH, int nH, int dshift) {
+    const double* __restrict__ uH, int nH, int dshift, double* dvec, double alpha) {
   // CSR_JACOBI_P: x is not the smoother's input yet -- the input is x + P uH
   // (LinearInterpolator prolongation, interpolator.hpp:106-129), formed on the
   // fly per gathered entry in the same order as K-ProlongAdd:
@@ -288,11 +373,12 @@ __global__ __launch_bounds__(256) void sell_kernel(
   // column of row's diagonal: row itself, or row + dshift when x is a rank's
   // halo-extended vector and the columns are numbered in it (multi-GPU shards)
   const int drow = row + dshift;
-  double fi = 0.0, xi = 0.0;
+  double fi = 0.0, xi = 0.0, di = 0.0;
   if (live) {
     if (MODE != CSR_SPMV) fi = NT ? __builtin_nontemporal_load(f + row) : f[row];
-    if (MODE == CSR_JACOBI || MODE == CSR_GS) xi = x[drow];
+    if (mode_jac(MODE) || MODE == CSR_GS) xi = x[drow];
     if (MODE == CSR_JACOBI_P) xi = corrected(row);
+    if (mode_cheb(MODE) && !cheb_first(MODE)) di = NT ? __builtin_nontemporal_load(dvec + row) : dvec[row];
   }
   double acc = (MODE == CSR_RESID) ? fi : 0.0;
   double diag = 0.0;
@@ -323,7 +409,7 @@ __global__ __launch_bounds__(256) void sell_kernel(
       if (j0 + u < w && c[u] >= 0) {
         if (MODE == CSR_RESID) {
           acc -= v[u] * xx[u];
-        } else if (MODE == CSR_JACOBI || MODE == CSR_GS || MODE == CSR_JACOBI_P) {
+        } else if (mode_jac(MODE) || MODE == CSR_GS || MODE == CSR_JACOBI_P) {
           if (c[u] == drow) diag = v[u];
           else acc += v[u] * xx[u];
         } else {
@@ -347,6 +433,13 @@ __global__ __launch_bounds__(256) void sell_kernel(
       res = acc;
     } else if (MODE == CSR_JACOBI || MODE == CSR_JACOBI_P) {
       res = (diag == 0.0) ? xi : xi + omega * ((fi - acc) / diag - xi);
+    } else if (mode_cheb(MODE)) {
+      double dn;
+      res = cheb_update<MODE>((diag == 0.0) ? xi : (fi - acc) / diag, xi, di, alpha, omega, dn);
+      if (!cheb_last(MODE)) {
+        if (NT) __builtin_nontemporal_store(dn, dvec + row);
+        else dvec[row] = dn;
+      }
     } else if (MODE == CSR_GS) {
       res = (fi - acc) / diag;  // smoother.hpp:136
       store = diag != 0.0;
@@ -367,12 +460,12 @@ static hipError_t launch_sell_mode(int64_t n, int idx16, const int64_t* soff,
                                    const double* f, double* out, double omega,
                                    const int32_t* rowid, int64_t row0, int64_t count,
                                    const double* uH, int64_t nH, hipStream_t st,
-                                   int64_t diag_shift = 0) {
+                                   int64_t diag_shift = 0, double* dvec = nullptr, double alpha = 0.0) {
   const unsigned grid = (unsigned)((count + 255) / 256);
   // idx16: bit 0 = 16-bit relative columns, bit 1 = non-temporal matrix stream
 #define AMG_SELL_LAUNCH(I16, NTF)                                                              \
   hipLaunchKernelGGL((sell_kernel<MODE, I16, NTF>), dim3(grid), dim3(256), 0, st, (int)n, soff, \
-                     scol, sval, x, f, out, omega, rowid, (int)row0, uH, (int)nH, (int)diag_shift)
+                     scol, sval, x, f, out, omega, rowid, (int)row0, uH, (int)nH, (int)diag_shift, dvec, alpha)
   switch (idx16 & 3) {
     case 0: AMG_SELL_LAUNCH(false, false); break;
     case 1: AMG_SELL_LAUNCH(true, false); break;
@@ -395,6 +488,20 @@ hipError_t launch_sell(int mode, int64_t n, int idx16, const int64_t* soff,
     case CSR_RSSQ: return launch_sell_mode<CSR_RSSQ>(n, idx16, soff, scol, sval, x, f, out, omega, nullptr, 0, n, nullptr, 0, st, diag_shift);
   }
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_sell_cheb(int64_t n, int idx16, const int64_t* soff, const void* scol, const double* sval,
+                            const double* x, const double* f, double* out, const ChebStep& c, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (n >= ((int64_t)1 << 31) - 256 || !c.d || x == out) return hipErrorInvalidValue;
+#define AMG_SELL_CHEB(FI, LA)                                                                                \
+  return launch_sell_mode<cheb_kernel_mode(FI, LA)>(n, idx16, soff, scol, sval, x, f, out, c.beta, nullptr, 0, n, \
+                                                    nullptr, 0, st, 0, c.d, c.alpha)
+  if (c.first && c.last) AMG_SELL_CHEB(true, true);
+  if (c.first) AMG_SELL_CHEB(true, false);
+  if (c.last) AMG_SELL_CHEB(false, true);
+  AMG_SELL_CHEB(false, false);
+#undef AMG_SELL_CHEB
 }
 
 hipError_t launch_sell_jacobi_prolong(int64_t n, int idx16, const int64_t* soff,
@@ -445,6 +552,7 @@ struct DictStream {  // streamed operands of R rows of one lane
   uint64_t cw[R][2];
   uint32_t ty;  // row types, byte r = row r
   double fi[R], xi[R];
+  double di[R];  // Chebyshev steps after the first: d_i
   bool live[R];
 };
 template <int MODE, int WORDS, bool NT, int R>
@@ -452,14 +560,15 @@ __device__ __forceinline__ void dict_fetch(DictStream<WORDS, R>& s, int row0, in
                                            const uint64_t* __restrict__ codes,
                                            const uint8_t* __restrict__ rtype,
                                            const double* __restrict__ f, const double* x,
-                                           int dshift) {
+                                           int dshift, const double* __restrict__ dvec = nullptr) {
   typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
   typedef double f64x2 __attribute__((ext_vector_type(2)));
+  constexpr bool read_d = mode_cheb(MODE) && !cheb_first(MODE);
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     s.live[r] = row0 + r < n;
     s.cw[r][0] = s.cw[r][1] = ~(uint64_t)0;
-    s.fi[r] = s.xi[r] = 0.0;
+    s.fi[r] = s.xi[r] = s.di[r] = 0.0;
   }
   s.ty = 0xFFFFu;  // both rows empty; unpacked in dict_expand, after the other loads are out
   if (R == 2 && s.live[R - 1]) {
@@ -480,7 +589,12 @@ __device__ __forceinline__ void dict_fetch(DictStream<WORDS, R>& s, int row0, in
       const f64x2 t = NT ? __builtin_nontemporal_load(fp) : *fp;
       s.fi[0] = t.x; s.fi[R - 1] = t.y;
     }
-    if (MODE == CSR_JACOBI) { s.xi[0] = x[row0 + dshift]; s.xi[R - 1] = x[row0 + 1 + dshift]; }
+    if (mode_jac(MODE)) { s.xi[0] = x[row0 + dshift]; s.xi[R - 1] = x[row0 + 1 + dshift]; }
+    if (read_d) {
+      const f64x2* dp = reinterpret_cast<const f64x2*>(dvec + row0);
+      const f64x2 t = NT ? __builtin_nontemporal_load(dp) : *dp;
+      s.di[0] = t.x; s.di[R - 1] = t.y;
+    }
   } else if (s.live[0]) {
     if (rtype) {
       s.ty = 0xFF00u | rtype[row0];
@@ -495,7 +609,8 @@ __device__ __forceinline__ void dict_fetch(DictStream<WORDS, R>& s, int row0, in
       }
     }
     if (MODE != CSR_SPMV) s.fi[0] = NT ? __builtin_nontemporal_load(f + row0) : f[row0];
-    if (MODE == CSR_JACOBI) s.xi[0] = x[row0 + dshift];
+    if (mode_jac(MODE)) s.xi[0] = x[row0 + dshift];
+    if (read_d) s.di[0] = NT ? __builtin_nontemporal_load(dvec + row0) : dvec[row0];
   }
 }
 // word table of the row types: 256 entries of WORDS words, entry 255 = all 0xFF (host pads)
@@ -529,7 +644,7 @@ __device__ __forceinline__ void dict_stage_table(DictEntry* tab, const int32_t* 
   const double v = t < ntab ? dval[t] : 0.0;
   const int32_t o = t < ntab ? doff[t] : 0;
   DictEntry e;
-  constexpr bool split = MODE == CSR_JACOBI || MODE == CSR_GS;
+  constexpr bool split = mode_jac(MODE) || MODE == CSR_GS;
   e.a = (split && o == 0) ? 0.0 : v;
   e.d = (split && o == 0 && t < ntab) ? v : 0.0;
   e.off8 = o * 8;
@@ -567,7 +682,7 @@ __device__ __forceinline__ void dict_rows(const DictStream<WORDS, R>& s, int row
       ok[r][u] = code != 0xFFu;
       c8[r][u] = drow8 + (uint32_t)tab[code].off8;
       v[r][u] = tab[code].a;
-      vd[r][u] = (MODE == CSR_JACOBI || MODE == CSR_GS) ? tab[code].d : 0.0;
+      vd[r][u] = (mode_jac(MODE) || MODE == CSR_GS) ? tab[code].d : 0.0;
     }
   }
 #pragma unroll
@@ -582,7 +697,7 @@ __device__ __forceinline__ void dict_rows(const DictStream<WORDS, R>& s, int row
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       double t = v[r][u] * xx[r][u];
-      if (MODE == CSR_JACOBI || MODE == CSR_GS) {
+      if (mode_jac(MODE) || MODE == CSR_GS) {
         acc += t;
         diag += vd[r][u];
       } else {
@@ -596,7 +711,7 @@ __device__ __forceinline__ void dict_rows(const DictStream<WORDS, R>& s, int row
     }
     if (MODE == CSR_RESID || MODE == CSR_SPMV) {
       res[r] = acc;
-    } else if (MODE == CSR_JACOBI || MODE == CSR_GS) {
+    } else if (mode_jac(MODE) || MODE == CSR_GS) {
       // The division runs for every row (a missing diagonal divides by 1 and is then
       // discarded): with it inside `diag != 0` clang puts the whole row walk, gathers and
       // their waits included, into that branch and the rows of a lane run one after
@@ -604,7 +719,7 @@ __device__ __forceinline__ void dict_rows(const DictStream<WORDS, R>& s, int row
       const bool nod = diag == 0.0;
       double q = (s.fi[r] - acc) / (nod ? 1.0 : diag);  // smoother.hpp:136
       asm volatile("" : "+v"(q));
-      if (MODE == CSR_GS) res[r] = nod ? s.xi[r] : q;
+      if (MODE == CSR_GS || mode_cheb(MODE)) res[r] = nod ? s.xi[r] : q;  // Chebyshev: t_i (cheb_update)
       else res[r] = nod ? s.xi[r] : s.xi[r] + omega * (q - s.xi[r]);
     } else {
       const double d = s.fi[r] - acc;
@@ -643,7 +758,7 @@ __device__ __forceinline__ void dict_rows_stencil(uint32_t ty, const double (&fi
                                                   const double* __restrict__ utd,
                                                   const int32_t* __restrict__ uti, const double* x,
                                                   double omega, double (&res)[2]) {
-  static_assert(MODE == CSR_JACOBI || MODE == CSR_RESID, "fast path of the two hot modes");
+  static_assert(mode_jac(MODE) || MODE == CSR_RESID, "fast path of the hot modes");
   static_assert(UN == 7 || UN == 16, "7-point rows / 15-point rows");
   typedef double f64x2 __attribute__((ext_vector_type(2)));
   constexpr int PAT = UN == 7 ? 7 : 15;
@@ -680,7 +795,7 @@ __device__ __forceinline__ void dict_rows_stencil(uint32_t ty, const double (&fi
 #pragma unroll
     for (int u = 0; u < PAT; ++u) {
       const double t = td[u] * xx[r][u];
-      if (MODE == CSR_JACOBI) acc += t;   // td[u] = +0.0 for the diagonal slot (dict_stage_table<CSR_JACOBI>)
+      if (mode_jac(MODE)) acc += t;       // td[u] = +0.0 for the diagonal slot (dict_stage_table<CSR_JACOBI>)
       else acc -= t;                      // every slot of the pattern is in use
     }
     if (MODE == CSR_RESID) {
@@ -689,7 +804,8 @@ __device__ __forceinline__ void dict_rows_stencil(uint32_t ty, const double (&fi
       const double diag = td[32];
       const bool nod = diag == 0.0;
       const double q = (fi[r] - acc) / (nod ? 1.0 : diag);  // smoother.hpp:136
-      res[r] = nod ? xi[r] : xi[r] + omega * (q - xi[r]);
+      if (mode_cheb(MODE)) res[r] = nod ? xi[r] : q;  // t_i (cheb_update)
+      else res[r] = nod ? xi[r] : xi[r] + omega * (q - xi[r]);
     }
   }
 }
@@ -736,24 +852,30 @@ __global__ __launch_bounds__(256) void dict_kernel(
     const uint64_t* __restrict__ rwords, const int32_t* __restrict__ doff,
     const double* __restrict__ dval, int ntab, const double* x, const double* __restrict__ f,
     double* out, double omega, int dshift, int xcd_map, const double* __restrict__ utd,
-    const int32_t* __restrict__ uti) {
+    const int32_t* __restrict__ uti, double* dvec, double alpha) {
   __shared__ DictEntry tab[256];
   __shared__ uint64_t wtab[256 * WORDS];
   const int row0 = (xcd_tile(blockIdx.x, gridDim.x, xcd_map) * 256 + (int)threadIdx.x) * R;
   DictStream<WORDS, R> s;
-  dict_fetch<MODE, WORDS, NT, R>(s, row0, n, codes, rtype, f, x, dshift);  // in flight while the tables are staged
+  dict_fetch<MODE, WORDS, NT, R>(s, row0, n, codes, rtype, f, x, dshift, dvec);  // in flight while the tables are staged
   dict_stage_table<MODE>(tab, doff, dval, ntab);
   if (rtype) dict_stage_words<WORDS>(wtab, rwords);
   __syncthreads();
   double res[R];
   bool fast = false;
-  if constexpr ((MODE == CSR_JACOBI || MODE == CSR_RESID) && R == 2 && (UN == 7 || UN == 16)) {
+  if constexpr ((mode_jac(MODE) || MODE == CSR_RESID) && R == 2 && (UN == 7 || UN == 16)) {
     if (utd) fast = dict_stencil_can<UN>(s.ty, s.live, uti);
     if (fast) dict_rows_stencil<MODE, UN>(s.ty, s.fi, s.xi, row0, utd, uti, x, omega, res);
   }
   if (!fast) {
     if (rtype) dict_expand<WORDS, R>(s, wtab);
     dict_rows<MODE, WORDS, UN, R>(s, row0, tab, x, omega, dshift, res);
+  }
+  if constexpr (mode_cheb(MODE)) {  // res = t_i
+    double dn[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) res[r] = cheb_update<MODE>(res[r], s.xi[r], s.di[r], alpha, omega, dn[r]);
+    if (!cheb_last(MODE)) dict_store<WORDS, NT, R>(s, row0, dn, dvec);
   }
   dict_store<WORDS, NT, R>(s, row0, res, out);
 }
@@ -2462,7 +2584,8 @@ void set_dict_rows_per_lane(int r) { g_dict_rows_per_lane = r == 1 ? 1 : 2; }
 void set_dict_stencil(int on) { g_dict_stencil = on ? 1 : 0; }
 template <int MODE>
 static hipError_t launch_dict_mode(int64_t n, const DictRef& D, const double* x, const double* f,
-                                   double* out, double omega, int64_t dshift, hipStream_t st) {
+                                   double* out, double omega, int64_t dshift, hipStream_t st,
+                                   double* dvec = nullptr, double alpha = 0.0) {
   const bool two = dict_two_rows(n, D, f, out);
   const unsigned tiles = (unsigned)((n + 256 * (two ? 2 : 1) - 1) / (256 * (two ? 2 : 1)));
   return dict_dispatch(D.words, D.wmax, D.nt != 0, two, [&](auto W, auto U, auto NTF, auto RR) {
@@ -2470,8 +2593,23 @@ static hipError_t launch_dict_mode(int64_t n, const DictRef& D, const double* x,
                                     decltype(NTF)::value, decltype(RR)::value>),
                        dim3(tiles), dim3(256), 0, st, (int)n, D.codes, D.rtype, D.rwords, D.doff,
                        D.dval, D.ntab, x, f, out, omega, (int)dshift, dict_xcd_map(D, 256 * (two ? 2 : 1)),
-                       dshift == 0 ? dict_stencil_tab(D, x) : nullptr, D.uti);
+                       dshift == 0 ? dict_stencil_tab(D, x) : nullptr, D.uti, dvec, alpha);
   });
+}
+hipError_t launch_dict_cheb(int64_t n, const DictRef& D, const double* x, const double* f, double* out,
+                            const ChebStep& c, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  // d moves as 16-byte pairs when the rows do (dict_two_rows)
+  if (!dict_args_ok(n, D.words, D.wmax, D.ntab) || !c.d || x == out ||
+      (reinterpret_cast<uintptr_t>(c.d) & 15) != 0)
+    return hipErrorInvalidValue;
+#define AMG_DICT_CHEB(FI, LA) \
+  return launch_dict_mode<cheb_kernel_mode(FI, LA)>(n, D, x, f, out, c.beta, 0, st, c.d, c.alpha)
+  if (c.first && c.last) AMG_DICT_CHEB(true, true);
+  if (c.first) AMG_DICT_CHEB(true, false);
+  if (c.last) AMG_DICT_CHEB(false, true);
+  AMG_DICT_CHEB(false, false);
+#undef AMG_DICT_CHEB
 }
 // the name rocprofv3 prints for the launch launch_dict(mode, ...) makes
 void dict_kernel_name(int mode, int64_t n, const DictRef& D, const void* f, const void* out,

@@ -13,8 +13,18 @@ enum CsrMode {
   CSR_RSSQ = 3,    // out_i = (f_i - (A x)_i)^2
   CSR_GS = 4,      // in-place Gauss-Seidel update of one colour
   CSR_JACOBI_P = 5,// Jacobi sweep whose input is x + P*uH (linear P), K-SELL only
-  CSR_SPMV_ADD = 6 // out = f + A x (f may be out: the prolongation-and-add u_h = u_h + P u_H of a
+  CSR_SPMV_ADD = 6,// out = f + A x (f may be out: the prolongation-and-add u_h = u_h + P u_H of a
                    // custom interpolator, multigrid.hpp:294-296, in one launch), K-CSR only
+  CSR_CHEB = 7     // one Chebyshev step (launch_mat_cheb): t_i as CSR_JACOBI computes it, then
+                   //   d_i = alpha d_i + beta (t_i - x_i)  (first step: beta (t_i - x_i), d not read)
+                   //   out_i = x_i + d_i                    (last step: d not written)
+};
+// Template MODE of the kernel a Chebyshev step launches (what rocprofv3 prints): 16 + first + 2 last
+constexpr int cheb_kernel_mode(bool first, bool last) { return 16 + (first ? 1 : 0) + (last ? 2 : 0); }
+struct ChebStep {
+  double* d = nullptr;  // n doubles, 16-byte aligned
+  double alpha = 0.0, beta = 0.0;
+  bool first = true, last = true;
 };
 
 // one workgroup runs the whole symmetric pass over all colours (small levels); starts_dev:
@@ -28,6 +38,18 @@ hipError_t launch_csr(int mode, int64_t n, int64_t nnz, int max_block_nnz,
                       int max_row_nnz, const int32_t* rowptr, const int32_t* col,
                       const double* val, const double* x, const double* f,
                       double* out, double omega, int64_t diag_shift, hipStream_t st);
+// CSR_CHEB on the three layouts: same row walk and division as CSR_JACOBI (bit-identical results
+// across layouts); a first step is bit for bit the CSR_JACOBI sweep with omega = beta.
+hipError_t launch_csr_cheb(int64_t n, int64_t nnz, int max_block_nnz, int max_row_nnz, const int32_t* rowptr,
+                           const int32_t* col, const double* val, const double* x, const double* f, double* out,
+                           const ChebStep& c, hipStream_t st);
+hipError_t launch_sell_cheb(int64_t n, int idx16, const int64_t* soff, const void* scol, const double* sval,
+                            const double* x, const double* f, double* out, const ChebStep& c, hipStream_t st);
+// Gershgorin bound of D^-1 A on a device CSR matrix: out[0] = bits of max_i (sum_j |a_ij|) / |a_ii|
+// (row sums in ascending column order, the host's order), out[1] = smallest row whose diagonal is
+// zero or absent.  out: 2 words, set by the launcher (stream-ordered) to {0, ~0}.
+hipError_t launch_gershgorin(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
+                             uint64_t* out, hipStream_t st);
 // Same operations on a SELL-64 matrix (64-row panels, lane-interleaved):
 // soff[n/64 + 1] panel offsets, scol/sval padded with col = -1.
 // idx16 bit 0: scol holds int16 offsets from the diagonal column (pad -32768);
@@ -60,6 +82,9 @@ void set_dict_rows_per_lane(int r);  // 1 or 2 (default), tuning / test switch
 void set_dict_stencil(int on);       // paired-load path for wave-uniform 7- / 15-point rows (default on)
 hipError_t launch_dict(int mode, int64_t n, const DictRef& D, const double* x, const double* f,
                        double* out, double omega, int64_t diag_shift, hipStream_t st);
+hipError_t launch_dict_cheb(int64_t n, const DictRef& D, const double* x, const double* f, double* out,
+                            const ChebStep& c, hipStream_t st);
+// mode: a CsrMode, or cheb_kernel_mode(...) for a Chebyshev step
 void dict_kernel_name(int mode, int64_t n, const DictRef& D, const void* f, const void* out,
                       char* buf, size_t cap);
 // one colour of the multicolour GS sweep on a dictionary-coded colour-permuted copy

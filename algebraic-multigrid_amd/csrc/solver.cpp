@@ -688,6 +688,70 @@ hipError_t launch_mat(int mode, const DevMat& A, const double* x, const double* 
                     C.v(), x, f, out, omega, diag_shift, st);
 }
 
+// one Chebyshev step (kernels.hpp: CSR_CHEB) on a level matrix in its device layout
+hipError_t launch_mat_cheb(const DevMat& A, const double* x, const double* f, double* out, const ChebStep& c,
+                           hipStream_t st) {
+  if (A.dict) {
+    if (A.dict_shift != 0) return hipErrorInvalidValue;
+    return launch_dict_cheb(A.n_rows, A.dict_ref(), x, f, out, c, st);
+  }
+  if (A.sell)
+    return launch_sell_cheb(A.n_rows, A.idx16, A.soff.as<int64_t>(), A.scol.p, A.sval.as<double>(), x, f, out, c,
+                            st);
+  const DevCsr& C = A.csr;
+  return launch_csr_cheb(C.n_rows, C.nnz, C.max_block_nnz, C.max_row_nnz, C.rowptr(), C.col(), C.v(), x, f, out,
+                         c, st);
+}
+
+// Chebyshev smoother: "" when the options are valid
+std::string cheb_options_error(int32_t degree, double lower, double upper) {
+  if (degree < 1) return "`cheb_degree` must be at least 1, got " + std::to_string(degree);
+  if (!(lower > 0.0)) return "`cheb_lower` must be > 0, got " + std::to_string(lower);
+  if (!(lower < upper))
+    return "`cheb_lower` must be < `cheb_upper`, got " + std::to_string(lower) + " and " + std::to_string(upper);
+  return "";
+}
+// Gershgorin bound of D^-1 A from CSR rows: max_i (sum_j |a_ij|) / |a_ii|, each row summed in
+// ascending column order (the device kernel's order: launch_gershgorin).  *zero_row: first row
+// whose diagonal is zero or absent, else -1.
+double gershgorin_host(const Sparse& Ar, int64_t* zero_row) {
+  double G = 0.0;
+  *zero_row = -1;
+  for (int64_t i = 0; i < Ar.n_outer; ++i) {
+    double sum = 0.0, dg = 0.0;
+    for (int32_t p = Ar.ptr[i]; p < Ar.ptr[i + 1]; ++p) {
+      sum += std::fabs(Ar.val[p]);
+      if (Ar.idx[p] == i) dg = Ar.val[p];
+    }
+    if (dg == 0.0) {
+      if (*zero_row < 0) *zero_row = i;
+      continue;
+    }
+    const double g = sum / std::fabs(dg);
+    if (g > G) G = g;
+  }
+  return G;
+}
+std::string cheb_zero_diag(int l, int64_t row) {
+  return "Chebyshev smoother: level " + std::to_string(l) + " row " + std::to_string(row) +
+         " has a zero diagonal (D^-1 A does not exist)";
+}
+// the step coefficients of one application, in double, in this order (include/amg_hip.h: cheb_lower)
+void cheb_coefs(double lo, double hi, int k, std::vector<double>* alpha, std::vector<double>* beta) {
+  const double theta = (hi + lo) / 2, delta = (hi - lo) / 2;
+  const double sigma = theta / delta;
+  double rho = 1.0 / sigma;
+  alpha->assign((size_t)k, 0.0);
+  beta->assign((size_t)k, 0.0);
+  (*beta)[0] = 1.0 / theta;
+  for (int i = 1; i < k; ++i) {
+    const double rn = 1.0 / (2.0 * sigma - rho);
+    (*alpha)[(size_t)i] = rn * rho;
+    (*beta)[(size_t)i] = 2.0 * rn / delta;
+    rho = rn;
+  }
+}
+
 struct SpikeOnDev {  // device copy of a SpikeFactor + scratch
   SpikeArgs a{};
   DevMem sf, sb, d, V, W, Vt, Wh, G, Z, T, H;
@@ -881,6 +945,8 @@ struct Level {
   const DevMat& A_cols() const { return symmetric ? A_rows : A_cols_own; }
   DevMem u, f, r, tmp;
   DevMem diag;             // a_ii (true-Jacobi smoother only)
+  double cheb_lo = 0.0, cheb_hi = 0.0;  // Chebyshev smoother: interval of D^-1 A's spectrum
+  DevMem cheb_d;           //   and its update vector d (r stays the residual: keep_residual)
   // transfers to level+1 (absent on the coarsest level)
   // host copies; for the built-in LinearInterpolator they are only materialised when a
   // getter, the CSR transfer kernels or the host Galerkin product ask for them
@@ -1296,6 +1362,37 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
         if (r != AMG_HIP_OK) return r;
       }
       return AMG_HIP_OK;
+    case AMG_HIP_SM_CHEBYSHEV: {
+      // iters applications of the degree-k polynomial, each k steps from step 0 (phases 1 / 2 have
+      // no shortcut here: u is read as it is).  The level vector ping-pongs u -> tmp -> u ...
+      const DevMat& A = L.A_rows;
+      const int k = s->opt.cheb_degree;
+      std::vector<double> alpha, beta;
+      cheb_coefs(L.cheb_lo, L.cheb_hi, k, &alpha, &beta);
+      double* a = L.u.as<double>();
+      double* b = L.tmp.as<double>();
+      int64_t passes = 0;
+      for (int it = 0; it < iters; ++it) {
+        for (int j = 0; j < k; ++j) {
+          ChebStep c;
+          c.d = L.cheb_d.as<double>();
+          c.alpha = alpha[(size_t)j];
+          c.beta = beta[(size_t)j];
+          c.first = j == 0;
+          c.last = j == k - 1;
+          HIP_TRY(launch_mat_cheb(A, a, L.f.as<double>(), b, c, st));
+          // matrix, f, x, out; d written (not on the last step) and read (not on the first)
+          s->acct(mat_bytes(A) + 24.0 * L.n + (c.first ? 0.0 : 8.0 * L.n) + (c.last ? 0.0 : 8.0 * L.n));
+          std::swap(a, b);
+          ++passes;
+        }
+      }
+      if (passes & 1) {  // result sits in tmp: bring it home (keeps the graph static)
+        HIP_TRY(hipMemcpyAsync(L.u.p, L.tmp.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, st));
+        s->acct(16.0 * L.n);
+      }
+      return AMG_HIP_OK;
+    }
   }
   return fail(AMG_HIP_EINVAL, "unknown smoother kind");
 }
@@ -1790,6 +1887,7 @@ void compute_bytes(amg_hip_solver* s) {
   int sweeps_per_smooth = iters;
   if (s->opt.smoother == AMG_HIP_SM_SPGS || s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS)
     sweeps_per_smooth = 2 * iters;
+  if (s->opt.smoother == AMG_HIP_SM_CHEBYSHEV) sweeps_per_smooth = iters * s->opt.cheb_degree;
   for (int l = 0; l < nl; ++l) {
     const Level& L = s->lv[l];
     const double sweep = 12.0 * (double)L.nnz_struct + 28.0 * (double)L.n;
@@ -1826,9 +1924,15 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
   if (opts) s->opt = *opts;
   else amg_hip_default_options(&s->opt);
-  if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_MULTICOLOR_GS)
+  if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_CHEBYSHEV)
     return fail(AMG_HIP_EINVAL, "unknown smoother kind");
   if (s->opt.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
+  const bool cheb = s->opt.smoother == AMG_HIP_SM_CHEBYSHEV;
+  if (cheb) {
+    const std::string e = cheb_options_error(s->opt.cheb_degree, s->opt.cheb_lower, s->opt.cheb_upper);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+    if (s->opt.window) return fail(AMG_HIP_EUNSUPPORTED, "the Chebyshev smoother is not available in a window solver");
+  }
   if (s->opt.layout < AMG_HIP_LAYOUT_AUTO || s->opt.layout > AMG_HIP_LAYOUT_DICT)
     return fail(AMG_HIP_EINVAL, "unknown matrix layout");
   if (s->opt.smoother == AMG_HIP_SM_SOR && (s->opt.omega > 2 || s->opt.omega < 0))
@@ -1895,6 +1999,13 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     Level& L = s->lv[l];
     L.symmetric = same_arrays(A_r, L.A_csc);
     L.nnz_struct = L.A_csc.nnz();
+    if (cheb) {  // bound of D^-1 A from the rows of A_l (CSR(A_l) = A_r)
+      int64_t zr = -1;
+      const double G = gershgorin_host(A_r, &zr);
+      if (zr >= 0) return fail(AMG_HIP_EINVAL, cheb_zero_diag(l, zr));
+      L.cheb_lo = s->opt.cheb_lower * G;
+      L.cheb_hi = s->opt.cheb_upper * G;
+    }
     if (dev) {
     const bool prune = !s->opt.keep_structural_zeros;
     // Symmetric levels headed for the dictionary layout are encoded ON THE DEVICE from CSR(A_l)
@@ -1921,7 +2032,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     }
     if (!encoded) {
       HIP_TRY(upload_mat_pruned(A_r, s->opt.layout, prune, &L.A_rows));
-      if (!L.symmetric && s->opt.smoother >= AMG_HIP_SM_JACOBI)
+      if (!L.symmetric && s->opt.smoother >= AMG_HIP_SM_JACOBI && !cheb)  // Chebyshev: rows of A
         HIP_TRY(upload_mat_pruned(L.A_csc, s->opt.layout, prune, &L.A_cols_own));
     }
     if (s->opt.smoother == AMG_HIP_SM_JACOBI && !L.diag.p) {  // diagonal of the column-as-row walk
@@ -1938,6 +2049,10 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     HIP_TRY(hipMemset(L.u.p, 0, sizeof(double) * L.n));
     HIP_TRY(hipMemset(L.f.p, 0, sizeof(double) * L.n));
     HIP_TRY(hipMemset(L.r.p, 0, sizeof(double) * L.n));
+    if (cheb) {
+      HIP_TRY(L.cheb_d.alloc(sizeof(double) * L.n));
+      HIP_TRY(hipMemset(L.cheb_d.p, 0, sizeof(double) * L.n));
+    }
     timer.lap(T_ENC);
     // smoother-specific structures
     // Lexicographic sweeps at size: the line-scan form, unless opt.exact_gs or a small
@@ -2309,8 +2424,15 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       o.smoother == AMG_HIP_SM_MULTICOLOR_GS || (lex && (o.exact_gs || N <= GS_SCAN_MIN_ROWS)) ||
       n_levels < 2 || N >= ((int64_t)1 << 28))
     return AMG_HIP_OK;
-  if (o.smoother_iters < 0 || (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0)))
+  if (o.smoother_iters < 0 || (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0)) ||
+      o.smoother < 0 || o.smoother > AMG_HIP_SM_CHEBYSHEV)
     return AMG_HIP_OK;  // the host path words the argument error
+  const bool cheb = o.smoother == AMG_HIP_SM_CHEBYSHEV;
+  if (cheb) {
+    const std::string e = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+    if (o.window) return fail(AMG_HIP_EUNSUPPORTED, "the Chebyshev smoother is not available in a window solver");
+  }
   std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
   s->opt = o;
   int ndev = 0;
@@ -2369,13 +2491,24 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
   }
   lap("generator");
   s->lv.resize(n_levels);
-  DevMem stats;
+  DevMem stats, gbound;
   HIP_TRY(stats.alloc(sizeof(int32_t) * 2));
+  if (cheb) HIP_TRY(gbound.alloc(sizeof(uint64_t) * 2));
   const bool prune = !o.keep_structural_zeros;
   for (int l = 0; l < n_levels; ++l) {
     Level& L = s->lv[l];
     L.n = cur.n_rows;
     L.nnz_struct = cur.nnz;
+    if (cheb) {  // Gershgorin bound of D^-1 A on the device CSR (K-Setup: gershgorin_kernel)
+      HIP_TRY(launch_gershgorin(L.n, cur.rowptr(), cur.col(), cur.v(), gbound.as<uint64_t>(), nullptr));
+      uint64_t g[2];
+      HIP_TRY(hipMemcpy(g, gbound.p, sizeof(g), hipMemcpyDeviceToHost));
+      if (g[1] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, cheb_zero_diag(l, (int64_t)g[1]));
+      double G;
+      std::memcpy(&G, &g[0], sizeof(G));
+      L.cheb_lo = o.cheb_lower * G;
+      L.cheb_hi = o.cheb_upper * G;
+    }
     HIP_TRY(L.diag.alloc(sizeof(double) * L.n));
     HIP_TRY(hipMemset(stats.p, 0, sizeof(int32_t) * 2));
     HIP_TRY(launch_csr_inspect(L.n, cur.rowptr(), cur.col(), cur.v(), prune, stats.as<int32_t>(),
@@ -2433,6 +2566,10 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
     HIP_TRY(hipMemset(L.u.p, 0, sizeof(double) * L.n));
     HIP_TRY(hipMemset(L.f.p, 0, sizeof(double) * L.n));
     HIP_TRY(hipMemset(L.r.p, 0, sizeof(double) * L.n));
+    if (cheb) {
+      HIP_TRY(L.cheb_d.alloc(sizeof(double) * L.n));
+      HIP_TRY(hipMemset(L.cheb_d.p, 0, sizeof(double) * L.n));
+    }
     if (lex && (l + 1 < n_levels || o.keep_residual)) {  // K-GS-scan on every smoothed level, or the host path
       const DevMat& A = L.A_rows;
       int ring = 128;
@@ -2548,7 +2685,9 @@ void amg_hip_default_options(amg_hip_options* o) {
   o->fast_coarse_solve = 0;
   o->stream = nullptr;
   o->window = 0;
-  o->reserved0 = 0;
+  o->cheb_degree = 2;
+  o->cheb_lower = 0.3;
+  o->cheb_upper = 1.0;
 }
 
 void amg_hip_set_index16(int32_t on) { g_index16 = on ? 1 : 0; }
@@ -2632,6 +2771,8 @@ amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t uni
   amg_hip_options o;
   if (opts) o = *opts;
   else amg_hip_default_options(&o);
+  if (o.smoother == AMG_HIP_SM_CHEBYSHEV)
+    return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_window: the Chebyshev smoother is not sharded");
   o.window = 1;
   bool unsupported = true;
   amg_hip_status r = build_poisson_device(dim, n, n_levels, &o, out, &unsupported, unit_begin, unit_end);
@@ -2735,6 +2876,8 @@ amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world
   if (!s || !info || world < 1 || rank < 0 || rank >= world)
     return fail(AMG_HIP_EINVAL, "amg_hip_slab_setup: bad argument");
   if (s->opt.window) return fail(AMG_HIP_EINVAL, "amg_hip_slab_setup: a window solver is cut already (amg_hip_window_setup)");
+  if (s->opt.smoother == AMG_HIP_SM_CHEBYSHEV)
+    return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_slab_setup: the Chebyshev smoother is not sharded");
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
   int k = 0;
@@ -2963,6 +3106,16 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       return AMG_HIP_OK;
   }
   return fail(AMG_HIP_EINVAL, "unknown level operation");
+}
+
+amg_hip_status amg_hip_cheb_bounds(const amg_hip_solver* s, int32_t level, double* lo, double* hi) {
+  if (!s || !lo || !hi) return fail(AMG_HIP_EINVAL, "null argument");
+  if (s->opt.smoother != AMG_HIP_SM_CHEBYSHEV)
+    return fail(AMG_HIP_EINVAL, "amg_hip_cheb_bounds: the solver's smoother is not AMG_HIP_SM_CHEBYSHEV");
+  if (level < 0 || level >= (int)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
+  *lo = s->lv[level].cheb_lo;
+  *hi = s->lv[level].cheb_hi;
+  return AMG_HIP_OK;
 }
 
 amg_hip_status amg_hip_rss(amg_hip_solver* s, double* out) {
@@ -3228,14 +3381,59 @@ amg_hip_status amg_hip_cycle_bytes(const amg_hip_solver* s, double* cycle_bytes,
   return AMG_HIP_OK;
 }
 
+namespace {
+// the Chebyshev step the level-0 measurement hooks run: step 1 (a middle step) when the degree has
+// one (>= 3), else step 0
+void cheb_profiled_step(const amg_hip_solver* s, ChebStep* out) {
+  const Level& L = s->lv[0];
+  const int k = s->opt.cheb_degree;
+  std::vector<double> alpha, beta;
+  cheb_coefs(L.cheb_lo, L.cheb_hi, k, &alpha, &beta);
+  const int j = k >= 3 ? 1 : 0;
+  ChebStep c;
+  c.d = L.cheb_d.as<double>();
+  c.alpha = alpha[(size_t)j];
+  c.beta = beta[(size_t)j];
+  c.first = j == 0;
+  c.last = j == k - 1;
+  *out = c;
+}
+}  // namespace
+
 amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
                                           double* avg_ms, double* min_ms) {
   if (!s || n_launches < 1) return fail(AMG_HIP_EINVAL, "bad argument");
-  if (s->opt.smoother != AMG_HIP_SM_JACOBI && s->opt.smoother != AMG_HIP_SM_MULTICOLOR_GS)
-    return fail(AMG_HIP_EUNSUPPORTED, "profile_fine_sweep: only for the Jacobi and multicolour smoothers");
+  if (s->opt.smoother != AMG_HIP_SM_JACOBI && s->opt.smoother != AMG_HIP_SM_MULTICOLOR_GS &&
+      s->opt.smoother != AMG_HIP_SM_CHEBYSHEV)
+    return fail(AMG_HIP_EUNSUPPORTED, "profile_fine_sweep: only for the Jacobi, multicolour and Chebyshev smoothers");
+  if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no device matrices");
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
   Level& L = s->lv[0];
+  if (s->opt.smoother == AMG_HIP_SM_CHEBYSHEV) {
+    // one middle step (u -> tmp, d read and written; u is not written), else step 0
+    ChebStep c;
+    cheb_profiled_step(s, &c);
+    std::vector<hipEvent_t> ev(2 * (size_t)n_launches);
+    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    for (int i = 0; i < n_launches; ++i) {
+      HIP_TRY(hipEventRecord(ev[2 * i], s->stream));
+      HIP_TRY(launch_mat_cheb(L.A_rows, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(), c, s->stream));
+      HIP_TRY(hipEventRecord(ev[2 * i + 1], s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    double sum = 0, mn = 1e30;
+    for (int i = 0; i < n_launches; ++i) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
+      sum += ms;
+      mn = std::min<double>(mn, ms);
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    if (avg_ms) *avg_ms = sum / n_launches;
+    if (min_ms) *min_ms = mn;
+    return AMG_HIP_OK;
+  }
   const DevMat& A = L.A_cols();
   const bool mc = s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS;
   const bool mc_patch = mc && mc_patch_ok(s, 0);
@@ -3330,7 +3528,23 @@ amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int3
   int sweeps = 1;
   // bytes one launch has to move: what it reads and writes once, not a layout it does not stream
   double bytes = 12.0 * (double)L.nnz_struct + 28.0 * (double)L.n;  // SELL / CSR: SURVEY 8(d)
-  if (s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS) {
+  if (s->opt.smoother == AMG_HIP_SM_CHEBYSHEV) {
+    // the step amg_hip_profile_fine_sweep runs: matrix in its layout, f, x, out, d read / written
+    ChebStep c;
+    cheb_profiled_step(s, &c);
+    const int mode = cheb_kernel_mode(c.first, c.last);
+    const DevMat& R = L.A_rows;
+    layout_of(R, &lay, &mat);
+    if (R.dict) {
+      dict_kernel_name(mode, R.n_rows, R.dict_ref(), L.f.p, L.tmp.p, name, (size_t)name_cap);
+    } else if (R.sell) {
+      std::snprintf(name, (size_t)name_cap, "sell_kernel<%d, %s, %s>", mode, (R.idx16 & 1) ? "true" : "false",
+                    (R.idx16 & 2) ? "true" : "false");
+    } else {
+      std::snprintf(name, (size_t)name_cap, "csr_stage_kernel<%d>", mode);
+    }
+    bytes = (double)mat + 24.0 * (double)L.n + (c.first ? 0.0 : 8.0 * L.n) + (c.last ? 0.0 : 8.0 * L.n);
+  } else if (s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS) {
     // one launch of the symmetric pass: two colour stages over the level (patch form), or one
     // colour of one direction (colour kernels: half the rows)
     if (mc_patch_ok(s, 0)) {
@@ -3601,6 +3815,49 @@ amg_hip_status amg_hip_smooth(int32_t kind, int64_t n, const int32_t* colptr,
   HIP_TRY(hipMemcpy(u, cur, sizeof(double) * n, hipMemcpyDeviceToHost));
   if (iters) *iters = iter;
   if (converged) *converged = error <= tol;
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_smooth_chebyshev(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                        const double* val, double* u, const double* b, int32_t degree,
+                                        double lower, double upper, int64_t n_iters) {
+  if (n <= 0 || !colptr || !rowind || !val || !u || !b) return fail(AMG_HIP_EINVAL, "bad argument");
+  std::string v = cheb_options_error(degree, lower, upper);
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
+  if (n_iters < 0) return fail(AMG_HIP_EINVAL, "`n_iters` must be >= 0");
+  Sparse A = from_raw(n, n, colptr, rowind, val);
+  v = validate(A, "A");
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
+  Sparse Ar = transpose(A);  // the polynomial is in D^-1 A: rows of A
+  int64_t zr = -1;
+  const double G = gershgorin_host(Ar, &zr);
+  if (zr >= 0) return fail(AMG_HIP_EINVAL, cheb_zero_diag(0, zr));
+  amg_hip_status st = need_device();
+  if (st != AMG_HIP_OK) return st;
+  std::vector<double> alpha, beta;
+  cheb_coefs(lower * G, upper * G, degree, &alpha, &beta);
+  DevMat D;
+  HIP_TRY(upload_mat(Ar, g_default_layout, &D));
+  DevMem du, db, dt, dd;
+  HIP_TRY(upload(du, u, (size_t)n));
+  HIP_TRY(upload(db, b, (size_t)n));
+  HIP_TRY(dt.alloc(sizeof(double) * n));
+  HIP_TRY(dd.alloc(sizeof(double) * n));
+  double* cur = du.as<double>();
+  double* alt = dt.as<double>();
+  for (int64_t it = 0; it < n_iters; ++it)
+    for (int j = 0; j < degree; ++j) {
+      ChebStep c;
+      c.d = dd.as<double>();
+      c.alpha = alpha[(size_t)j];
+      c.beta = beta[(size_t)j];
+      c.first = j == 0;
+      c.last = j == degree - 1;
+      HIP_TRY(launch_mat_cheb(D, cur, db.as<double>(), alt, c, nullptr));
+      std::swap(cur, alt);
+    }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(u, cur, sizeof(double) * n, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
 }
 

@@ -101,6 +101,11 @@ class Multigrid {
     } else if (auto* tj = dynamic_cast<TrueJacobi<EleType>*>(smoother)) {
       opt.smoother = AMG_HIP_SM_JACOBI;
       opt.omega = tj->get_omega();
+    } else if (auto* ch = dynamic_cast<Chebyshev<EleType>*>(smoother)) {
+      opt.smoother = AMG_HIP_SM_CHEBYSHEV;
+      opt.cheb_degree = ch->get_degree();
+      opt.cheb_lower = ch->get_lower();
+      opt.cheb_upper = ch->get_upper();
     } else {
       // user-defined SmootherBase: its smooth() runs on the host, everything else of the
       // V-cycle on the device; the device-side smoother is never used
@@ -111,7 +116,7 @@ class Multigrid {
     // convergence line on EVERY smooth() call (smoother.hpp:195-212).  The fused device
     // V-cycle runs a fixed number of sweeps and prints nothing, so such a smoother goes
     // through its own smooth() level by level: same sweep counts, same lines.
-    if (!custom_smoother && opt.smoother != AMG_HIP_SM_JACOBI &&
+    if (!custom_smoother && opt.smoother != AMG_HIP_SM_JACOBI && opt.smoother != AMG_HIP_SM_CHEBYSHEV &&
         smoother->compute_error_every_n_iters != 0)
       custom_smoother = true;
     if (custom_smoother) {

@@ -2,6 +2,7 @@
 // public fields; smooth() runs on the GPU through amg_hip.h.
 #pragma once
 #include <iostream>
+#include <stdexcept>
 #include <string>
 
 #include <amg/common.hpp>
@@ -124,6 +125,37 @@ class TrueJacobi : public SmootherBase<EleType> {
   void smooth(const Eigen::SparseMatrix<EleType>& A, Eigen::Matrix<EleType, -1, 1>& u,
               const Eigen::Matrix<EleType, -1, 1>& b) override {
     detail::device_smooth(AMG_HIP_SM_JACOBI, A, u, b, omega, 0.0, 0, this->n_iters, nullptr, nullptr);
+  }
+};
+
+// Build-side addition (no reference counterpart): Chebyshev polynomial smoother in D^-1 A of degree
+// `degree` on [lower G, upper G], G = max_i (sum_j |a_ij|) / |a_ii| (Gershgorin); `n_iters`
+// applications per smooth(), each `degree` fully parallel Jacobi-shaped passes.  A polynomial in
+// D^-1 A: the same pre- and post-smoother keep the V-cycle symmetric (AMG::PCG).  No colouring, no
+// omega to tune (amg_hip.h: AMG_HIP_SM_CHEBYSHEV).
+template <class EleType>
+class Chebyshev : public SmootherBase<EleType> {
+  int degree{2};
+  double lower{0.3}, upper{1.0};
+
+ public:
+  Chebyshev(int degree_ = 2, double lower_ = 0.3, double upper_ = 1.0, size_t n_iters_ = 1)
+      : degree(degree_), lower(lower_), upper(upper_) {
+    this->n_iters = n_iters_;
+    this->compute_error_every_n_iters = 0;
+    if (degree < 1) throw std::invalid_argument("`degree` must be at least 1");
+    if (!(lower > 0.0) || !(lower < upper))
+      throw std::invalid_argument("the interval must satisfy 0 < lower < upper");
+  }
+  int get_degree() const { return degree; }
+  double get_lower() const { return lower; }
+  double get_upper() const { return upper; }
+  void smooth(const Eigen::SparseMatrix<EleType>& A, Eigen::Matrix<EleType, -1, 1>& u,
+              const Eigen::Matrix<EleType, -1, 1>& b) override {
+    static_assert(sizeof(EleType) == sizeof(double), "the MI355X path is fp64 only");
+    const Eigen::SparseMatrix<EleType> C = detail::compressed(A);
+    detail::check(amg_hip_smooth_chebyshev(C.rows(), C.outerIndexPtr(), C.innerIndexPtr(), C.valuePtr(),
+                                           u.data(), b.data(), degree, lower, upper, (int64_t)this->n_iters));
   }
 };
 

@@ -43,7 +43,7 @@ typedef enum {
 } amg_hip_status;
 
 /* Smoother plug-ins (smoother.hpp).  0-2 are the reference's three classes;
- * 3-4 are build-side additions the reference does not contain.   */
+ * 3-5 are build-side additions the reference does not contain.   */
 typedef enum {
   AMG_HIP_SM_SPGS = 0,          /* AMG::SparseGaussSeidel smoother.hpp:86-216:
                                    n_iters x (forward + backward lexicographic
@@ -52,7 +52,12 @@ typedef enum {
                                    forward Gauss-Seidel, row addressed)         */
   AMG_HIP_SM_SOR = 2,           /* AMG::SuccessiveOverRelaxation :271-373       */
   AMG_HIP_SM_JACOBI = 3,        /* true two-buffer weighted Jacobi              */
-  AMG_HIP_SM_MULTICOLOR_GS = 4  /* symmetric multicolour Gauss-Seidel           */
+  AMG_HIP_SM_MULTICOLOR_GS = 4, /* symmetric multicolour Gauss-Seidel           */
+  AMG_HIP_SM_CHEBYSHEV = 5      /* Chebyshev polynomial in D^-1 A of degree
+                                   cheb_degree on [cheb_lower G, cheb_upper G],
+                                   G = Gershgorin bound of D^-1 A per level (rows
+                                   of A); smoother_iters applications per leg,
+                                   each cheb_degree Jacobi-shaped passes        */
 } amg_hip_smoother;
 
 /* Device layout of the level matrices (results are bit-identical in all).    */
@@ -133,7 +138,18 @@ typedef struct {
                               the ranks all-gather, so it is neither factored nor solved
                               here; amg_hip_vcycle / solve / apply / pcg are refused and
                               the cycle runs by parts (amg_hip_window_run).  Default 0. */
-  int32_t reserved0;       /* 0 */
+  int32_t cheb_degree;     /* AMG_HIP_SM_CHEBYSHEV: degree k >= 1 of the polynomial, i.e. matrix
+                              passes per application (default 2)                       */
+  double cheb_lower;       /* AMG_HIP_SM_CHEBYSHEV: the interval [lo, hi] = [cheb_lower G,
+                              cheb_upper G], G = max_i (sum_j |a_ij|) / |a_ii| of each
+                              level; 0 < cheb_lower < cheb_upper (defaults 0.3, 1.0).
+                              Step 0: d = (t - x) / theta, step s >= 1: rho_s = 1 /
+                              (2 sigma - rho_{s-1}), d = rho_s rho_{s-1} d + 2 rho_s / delta
+                              (t - x); x += d, with t the Jacobi quotient (f_i - sum_{j!=i}
+                              a_ij x_j) / a_ii, theta = (hi + lo) / 2, delta = (hi - lo) / 2,
+                              sigma = theta / delta, rho_0 = 1 / sigma.  A zero diagonal is
+                              refused at setup (AMG_HIP_EINVAL).                        */
+  double cheb_upper;       /* AMG_HIP_SM_CHEBYSHEV: upper end factor (default 1.0)    */
 } amg_hip_options;
 
 typedef struct amg_hip_solver amg_hip_solver; /* opaque; owns device memory    */
@@ -295,7 +311,8 @@ typedef struct amg_hip_slab_info {
 /* AMG_HIP_EUNSUPPORTED when a rank would own fewer lines than the halo depth. */
 amg_hip_status amg_hip_slab_plan(int64_t lines, int32_t rank, int32_t world, int32_t levels,
                                  amg_hip_slab_info* out);
-/* max_levels < 0: every K-Patch level.  AMG_HIP_EUNSUPPORTED when the solver has none.     */
+/* max_levels < 0: every K-Patch level.  AMG_HIP_EUNSUPPORTED when the solver has none, and for
+ * the Chebyshev smoother (not sharded).                                                    */
 amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world,
                                   int32_t max_levels, amg_hip_slab_info* info);
 /* part 1: down-legs of the slab levels; 2: the replicated rest of the cycle (from the gathered
@@ -327,7 +344,8 @@ amg_hip_status amg_hip_slab_run(amg_hip_solver* s, int32_t part);
  * Per-row arithmetic is the single-GPU kernels', so the owned units of the result equal the
  * single-GPU cycle bit for bit (tests/test_window_gloo.py, tests/test_gpu_window.py).
  * amg_hip_create_poisson_window: options as amg_hip_create_poisson; `n_levels` = k + 1 (level k
- * is only a container for f_k / u_k: opts->window is forced to 1).                         */
+ * is only a container for f_k / u_k: opts->window is forced to 1).  AMG_HIP_EUNSUPPORTED for
+ * the Chebyshev smoother (not sharded).                                                    */
 amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t unit_begin,
                                              int64_t unit_end, int32_t n_levels,
                                              const amg_hip_options* opts, amg_hip_solver** out);
@@ -483,6 +501,11 @@ amg_hip_status amg_hip_get_colors(const amg_hip_solver* s, int32_t level,
  *   4 coarsest solve u_L = A_L^-1 f_L (level must be L-1)   (:287-288)        */
 amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op);
 
+/* AMG_HIP_SM_CHEBYSHEV: the interval [*lo, *hi] the smoother of `level` uses (cheb_lower and
+ * cheb_upper times the level's Gershgorin bound of D^-1 A).  Also on host_only solvers (the
+ * host setup computes the bounds without a device).  AMG_HIP_EINVAL for other smoothers.   */
+amg_hip_status amg_hip_cheb_bounds(const amg_hip_solver* s, int32_t level, double* lo, double* hi);
+
 /* Sum over levels of the algorithmic HBM bytes of one V-cycle (SURVEY 8(d)
  * formulae) and the per-sweep bytes of level 0; used by bench.py.             */
 amg_hip_status amg_hip_cycle_bytes(const amg_hip_solver* s, double* cycle_bytes,
@@ -501,6 +524,8 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
  * solver's own stream, each launch bracketed by a pair of HIP events on that
  * stream, and returns the average / minimum launch duration in milliseconds.
  * AMG_HIP_SM_JACOBI: one launch = one sweep over level 0 (K-Patch: the level's down-leg);
+ * AMG_HIP_SM_CHEBYSHEV: one middle step of the polynomial over level 0 (u -> tmp, d read and
+ * written), or step 0 when the degree has no middle step (1 or 2);
  * AMG_HIP_SM_MULTICOLOR_GS: the first launch of the symmetric pass (K-Patch form: two colour
  * stages over the level; colour kernels: colour 0).  The level-0 solution is restored
  * afterwards.                                                                  */
@@ -525,6 +550,14 @@ amg_hip_status amg_hip_smooth(int32_t kind, int64_t n, const int32_t* colptr,
                               double* u, const double* b, double omega,
                               double tol, int64_t every, int64_t n_iters,
                               int64_t* iters, int32_t* converged);
+/* The Chebyshev smoother (AMG_HIP_SM_CHEBYSHEV) on host arrays: n_iters applications of the
+ * degree-`degree` polynomial on [lower G, upper G], G the Gershgorin bound of D^-1 A computed
+ * from the rows of A.  u is updated in place.  AMG_HIP_EINVAL: degree < 1, lower <= 0,
+ * lower >= upper, n_iters < 0, or a zero diagonal.                                          */
+amg_hip_status amg_hip_smooth_chebyshev(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                        const double* val, double* u, const double* b,
+                                        int32_t degree, double lower, double upper,
+                                        int64_t n_iters);
 /* One lexicographic sweep, dir=+1 forward (smoother.hpp:148-157) or -1 backward
  * (:167-174). */
 amg_hip_status amg_hip_spgs_sweep(int32_t dir, int64_t n, const int32_t* colptr,

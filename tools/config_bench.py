@@ -3,7 +3,8 @@
 headline) and records the convergence factor next to every rate.
 usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configuration
        config_bench.py all                                         the README table
-smoother: spgs | jacobi | multicolor.  Setup runs on the device (amg_hip_create_poisson);
+       config_bench.py cheb                                        the Chebyshev rows
+smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1).  Setup runs on the device (amg_hip_create_poisson);
 smoothers that need host structures fall back to the host path inside it."""
 import os
 import sys
@@ -16,7 +17,9 @@ import amg_ctypes as amg  # noqa: E402
 KW = {"spgs": dict(smoother=amg.SM_SPGS, smoother_iters=1),
       "jacobi": dict(smoother=amg.SM_JACOBI, smoother_iters=2, omega=0.6),
       "jacobi1": dict(smoother=amg.SM_JACOBI, smoother_iters=1, omega=0.6),
-      "multicolor": dict(smoother=amg.SM_MULTICOLOR_GS, smoother_iters=1)}
+      "multicolor": dict(smoother=amg.SM_MULTICOLOR_GS, smoother_iters=1),
+      "cheb": dict(smoother=amg.SM_CHEBYSHEV, smoother_iters=1, cheb_degree=2),
+      "cheb3": dict(smoother=amg.SM_CHEBYSHEV, smoother_iters=1, cheb_degree=3)}
 
 
 def run(dim, n, L, sm, cycles=10, warm=6, **extra):
@@ -76,7 +79,15 @@ def run_rs(n, sm, cycles=10, theta=0.25, min_coarse=500, dim=2):
     mg.close()
 
 
-if len(sys.argv) > 1 and sys.argv[1] == "rs":
+if len(sys.argv) > 1 and sys.argv[1] == "cheb":
+    run(2, 4096, 16, "cheb", 20)                       # the bench.py problem, Chebyshev(2) 1+1
+    run(2, 4096, 16, "jacobi", 20)                     # ... next to true Jacobi 2+2
+    run_rs(1024, "cheb")                               # RS 1024^2: rate, 1e-8, PCG to 1e-8
+    run_rs(1024, "cheb3")
+    run_rs(1024, "jacobi")
+    run(3, 256, 17, "cheb", 10)                        # 256^3 3-D
+    run(3, 256, 17, "jacobi", 10)
+elif len(sys.argv) > 1 and sys.argv[1] == "rs":
     for n in (512, 1024, 2048):
         run_rs(n, "multicolor")
         run_rs(n, "jacobi")
