@@ -2422,6 +2422,28 @@ hipError_t launch_march(MarchRef A, hipStream_t st) {
   hipLaunchKernelGGL(march_kernel, dim3((unsigned)(tiles * chunks)), dim3(MARCH_NT), 0, st, A);
   return hipGetLastError();
 }
+// Setup: does the row-type map describe an m x lines x planes box?  The march loads every cell
+// outside [0, m) x [0, lines) as 0, so a row on a column-0 / column-(m-1) / line-0 / line-(lines-1)
+// position must not hold the coupling that leaves its line or plane (bits 1 / 2 / 4 / 8 of
+// forbid[type]: it holds -1 / +1 / -m / +m); an empty row (type 255) is not a march row either.
+__global__ __launch_bounds__(256) void march_box_check_kernel(int64_t n, int m, int lines, MarchForbid F,
+                                                              const uint8_t* __restrict__ rtype,
+                                                              int32_t* __restrict__ bad) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const uint32_t t = rtype[r];
+  const int i = (int)(r % m), j = (int)((r / m) % lines);
+  const uint32_t at = (i == 0 ? 1u : 0u) | (i == m - 1 ? 2u : 0u) | (j == 0 ? 4u : 0u) | (j == lines - 1 ? 8u : 0u);
+  if (t >= (uint32_t)F.ntypes || (F.bits[t] & at) != 0) *bad = 1;
+}
+hipError_t launch_march_box_check(int64_t n, int m, int lines, const MarchForbid& F, const uint8_t* rtype,
+                                  int32_t* bad, hipStream_t st) {
+  if (m < 1 || lines < 1 || F.ntypes < 1 || F.ntypes > MARCH_TYPES || !rtype || !bad)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(march_box_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, m, lines,
+                     F, rtype, bad);
+  return hipGetLastError();
+}
 
 // ---- K-Strip: the multicolour smoother's whole leg of a NARROW level in one launch ----------
 // Below the K-Patch levels (pitch < 128) the symmetric pass of a 4-colour level is 7 colour

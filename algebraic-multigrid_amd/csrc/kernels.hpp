@@ -220,6 +220,14 @@ struct MarchRef {
 };
 bool march_ok(const MarchRef& A);
 hipError_t launch_march(MarchRef A, hipStream_t st);
+// setup: *bad = 1 when a row of type t sits on a box face that forbid.bits[t] rules out
+// (1: column 0, 2: column m-1, 4: line 0, 8: line lines-1) or its type is >= ntypes
+struct MarchForbid {
+  int ntypes = 0;
+  uint8_t bits[64] = {};
+};
+hipError_t launch_march_box_check(int64_t n, int m, int lines, const MarchForbid& F, const uint8_t* rtype,
+                                  int32_t* bad, hipStream_t st);
 // K-Strip (kernels.hip): the colour stages of a narrow level's whole leg in one launch over strips
 // of T rows (+ halo), any colouring (colour byte per row, < 16 colours); stages: 4 bits per stage.
 // prolong: the input is x + P uH; tail: followed by the residual (r_out optional), the restriction

@@ -527,6 +527,23 @@ hipError_t finish_dict(const DictMat& T, int64_t n, int64_t diag_shift, DevMat* 
         }
         wt[(size_t)t * 8 + 6] = diag;
       }
+      if (ok) {  // the offsets alone do not make a box: no row may couple across a line or plane edge
+        MarchForbid F;
+        F.ntypes = last + 1;
+        for (int t = 0; t <= last; ++t)
+          for (const auto& e : rows[(size_t)t])
+            F.bits[t] |= (uint8_t)((e.first == -1 ? 1 : 0) | (e.first == 1 ? 2 : 0) | (e.first == -pm ? 4 : 0) |
+                                   (e.first == pm ? 8 : 0));
+        DevMem dbad;
+        int32_t bad = 0;
+        if ((e = dbad.alloc(sizeof(int32_t))) != hipSuccess) return e;
+        if ((e = hipMemset(dbad.p, 0, sizeof(int32_t))) != hipSuccess) return e;
+        if ((e = launch_march_box_check(n, (int)pm, (int)(pM / pm), F, D->drtype.as<uint8_t>(),
+                                        dbad.as<int32_t>(), nullptr)) != hipSuccess)
+          return e;
+        if ((e = hipMemcpy(&bad, dbad.p, sizeof(int32_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+        ok = bad == 0;
+      }
       if (ok) {
         if ((e = upload(D->dmarch, wt.data(), wt.size())) != hipSuccess) return e;
         D->march_m = (int)pm;
@@ -944,6 +961,7 @@ struct Level {
   bool symmetric = false;  //   smoother.hpp:101-117); aliases A_rows when bitwise equal
   const DevMat& A_cols() const { return symmetric ? A_rows : A_cols_own; }
   DevMem u, f, r, tmp;
+  bool march_odd = false;  // K-March traded u and tmp an odd number of times in the cycle being enqueued
   DevMem diag;             // a_ii (true-Jacobi smoother only)
   double cheb_lo = 0.0, cheb_hi = 0.0;  // Chebyshev smoother: interval of D^-1 A's spectrum
   DevMem cheb_d;           //   and its update vector d (r stays the residual: keep_residual)
@@ -1236,8 +1254,10 @@ int tail_from(const amg_hip_solver* s) {
 }
 
 // K-March: the two plain Jacobi sweeps u -> tmp -> u of a 3-D 7-point level as ONE launch u -> tmp
-// (kernels.hip: march_kernel); the level's two vectors then trade places (a level is swept twice
-// per cycle this way -- down-leg and up-leg --, so every cycle ends with them where it found them).
+// (kernels.hip: march_kernel); the level's two vectors then trade places.  A level swept this way
+// on both legs ends the cycle with them where it found them; enqueue_vcycle brings back one that was
+// swept on one leg only.  Eligibility (finish_dict): the 7-point offsets of one interior type, n a
+// multiple of the plane, and no row on a line / plane edge coupling across it.
 static bool march_fill(const amg_hip_solver* s, int l, MarchRef* R) {
   const Level& L = s->lv[l];
   const DevMat& A = L.A_cols();
@@ -1333,6 +1353,7 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
           HIP_TRY(launch_march(R, st));
           s->acct(mat_bytes(A) + 24.0 * L.n);
           std::swap(L.u, L.tmp);
+          L.march_odd = !L.march_odd;
           return AMG_HIP_OK;
         }
       }
@@ -1525,7 +1546,19 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part);
 amg_hip_status enqueue_vcycle(amg_hip_solver* s, int part = CYCLE_ALL) {
   s->must_move[part] = 0;
   s->acct_part = part;
-  const amg_hip_status r = enqueue_vcycle_body(s, part);
+  amg_hip_status r = enqueue_vcycle_body(s, part);
+  // a level K-March swept on one leg only (the coarsest one: it has no up-leg) ends the cycle with
+  // u and tmp traded: its solution goes home so that the next cycle, or the next replay of the
+  // captured graph, finds every level where this one did
+  for (Level& L : s->lv) {
+    if (!L.march_odd) continue;
+    L.march_odd = false;
+    const hipError_t e =
+        hipMemcpyAsync(L.tmp.p, L.u.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream);
+    if (e != hipSuccess && r == AMG_HIP_OK) r = fail(AMG_HIP_EHIP, std::string("K-March copy: ") + hipGetErrorString(e));
+    s->acct(16.0 * L.n);
+    std::swap(L.u, L.tmp);
+  }
   s->acct_part = -1;
   return r;
 }

@@ -238,13 +238,40 @@ def patch_everywhere(amg):
     amg.set_patch_min_rows(amg.PATCH_MIN_ROWS_DEFAULT)
 
 
-@pytest.mark.parametrize("n,L,keep", [(128, 4, False), (256, 6, True), (512, 7, False), (192, 5, True)])
+def box2d(oracle, nx, ny):
+    """Symmetric anisotropic 5-point operator on an nx x ny box (dof = j*nx + i): the x coupling
+    alternates with the column parity and the y coupling with the line parity (four distinct
+    neighbour weights, A = A^T), the diagonal is 0.125 larger on odd lines."""
+    n = nx * ny
+    r = np.arange(n, dtype=np.int64)
+    i, j = r % nx, r // nx
+    wx = np.where(i % 2 == 0, -1.0, -0.75)      # coupling of (i, i+1) by the parity of i
+    wy = np.where(j % 2 == 0, -0.375, -0.5)     # coupling of (j, j+1) by the parity of j
+    ox, oy = i < nx - 1, j < ny - 1
+    rows = np.concatenate([r[ox], r[ox] + 1, r[oy], r[oy] + nx, r])
+    cols = np.concatenate([r[ox] + 1, r[ox], r[oy] + nx, r[oy], r])
+    vals = np.concatenate([wx[ox], wx[ox], wy[oy], wy[oy], 4.0 + 0.125 * (j % 2)])
+    order = np.lexsort((rows, cols))
+    colptr = np.zeros(n + 1, np.int32)
+    np.cumsum(np.bincount(cols, minlength=n), out=colptr[1:])
+    return oracle.CSC(n, n, colptr, rows[order].astype(np.int32), vals[order].astype(np.float64))
+
+
+@pytest.mark.parametrize("n,L,keep", [(128, 4, False), (256, 6, True), (512, 7, False), (192, 5, True),
+                                      ((128, 43), 4, False), ((128, 43), 4, True), ((192, 85), 5, False),
+                                      ((192, 85), 5, True), ((1024, 300), 9, False), ((1024, 300), 9, True)])
 def test_patch_kernels_bit_exact_against_oracle(amg, oracle, patch_everywhere, n, L, keep):
     """K-Patch: a level's down-leg (2 sweeps + residual + restriction + first coarse sweep)
     and up-leg (prolongation + 2 sweeps) in one launch each.  Same row arithmetic and
     transfer expressions as the separate kernels: every level vector equals the oracle's
-    bit for bit over whole cycles (multigrid.hpp:263-305 with the true-Jacobi twin)."""
-    A, b = oracle.laplacian(n), oracle.rhs(n)
+    bit for bit over whole cycles (multigrid.hpp:263-305 with the true-Jacobi twin).
+    n = (nx, ny): an anisotropic box (box2d) with lines that are no multiple of the 42-line
+    patch height and coarse levels with ragged last lines."""
+    if isinstance(n, tuple):
+        A = box2d(oracle, *n)
+        b = np.sin(0.001 * np.arange(A.rows)) + 1.5
+    else:
+        A, b = oracle.laplacian(n), oracle.rhs(n)
     ref = oracle.Multigrid(A, b, L, smoother=oracle.SM_TRUE_JACOBI, smoother_iters=2, omega=0.6)
     mg = amg.Multigrid(*csc(A), b, L, smoother=amg.SM_JACOBI, smoother_iters=2, omega=0.6,
                        keep_residual=keep, exact_coarse_solve=True)
