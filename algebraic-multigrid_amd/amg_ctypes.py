@@ -114,6 +114,11 @@ _SIGS = {
     "amg_hip_rss": (C.c_int, [C.c_void_p, _f64p]),
     "amg_hip_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "amg_hip_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, _i64p, _f64p]),
+    "amg_hip_block_vcycles": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    "amg_hip_block_rss": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _f64p]),
+    "amg_hip_block_pcg": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int64,
+                                    _i64p, _f64p]),
+    "amg_hip_block_must_move": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
     "amg_hip_n_levels": (C.c_int32, [C.c_void_p]),
     "amg_hip_get_n_dofs": (C.c_int64, [C.c_void_p, C.c_int32]),
     "amg_hip_get_level_nnz": (C.c_int64, [C.c_void_p, C.c_int32]),
@@ -439,6 +444,7 @@ class Multigrid:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)
         self._h = h
+        self._device = device
 
     @staticmethod
     def _options(smoother, smoother_iters, omega, device, use_graph, stencil_transfers, layout,
@@ -491,6 +497,7 @@ class Multigrid:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)
         self._h = h
+        self._device = device
         return self
 
     @classmethod
@@ -516,6 +523,7 @@ class Multigrid:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)
         self._h = h
+        self._device = device
         return self
 
     @classmethod
@@ -537,6 +545,7 @@ class Multigrid:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)
         self._h = h
+        self._device = device
         return self
 
     def window_setup(self, down_lo=None, down_hi=None, up_lo=None, up_hi=None):
@@ -714,6 +723,85 @@ class Multigrid:
         it, rel = C.c_int64(0), C.c_double(0)
         _chk(lib().amg_hip_pcg(self._h, rtol, max_iters, C.byref(it), C.byref(rel)))
         return self.get_soln(0), it.value, rel.value
+
+    # ---- block (multi-right-hand-side) cycles: amg_hip_block_* ---------------------------
+    def _block_check(self, name, t, k=None):
+        """ValueError unless t is a contiguous float64 tensor of shape (n_0, k), 1 <= k <= 16;
+        returns k.  No block call reaches C when a check fails."""
+        import torch
+        n0 = self.get_n_dofs(0)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch tensor, got {type(t).__name__}")
+        if t.dim() != 2 or t.shape[0] != n0 or not 1 <= t.shape[1] <= 16 or (k is not None and t.shape[1] != k):
+            want = f"({n0}, {k})" if k is not None else f"({n0}, k) with 1 <= k <= 16"
+            raise ValueError(f"{name}: expected shape {want}, got {tuple(t.shape)}")
+        if t.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype torch.float64, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous (row-major) tensor")
+        return int(t.shape[1])
+
+    def _block_device(self, **tensors):
+        dev = getattr(self, "_device", -1)
+        for name, t in tensors.items():
+            if not t.is_cuda or (dev is not None and dev >= 0 and t.device.index != dev):
+                raise ValueError(f"{name}: expected a tensor on the solver's device, got {t.device}")
+
+    def _block_call(self, device, fn):
+        """fn() on the solver's stream, ordered after torch's current stream, and torch's current
+        stream ordered after it (the tensors are torch's, the work is the solver's)."""
+        import torch
+        sp = C.c_void_p()
+        _chk(lib().amg_hip_get_stream(self._h, C.byref(sp)))
+        cur = torch.cuda.current_stream(device)
+        ext = torch.cuda.ExternalStream(sp.value or 0, device=device)
+        ext.wait_stream(cur)
+        try:
+            return fn()
+        finally:
+            cur.wait_stream(ext)
+
+    def block_vcycles(self, U, F, n=1):
+        """n V-cycles on every column of U (n_0 x k, in place) with right-hand sides F: column j
+        ends with the bits of vcycle(n) on column j (amg_hip_block_vcycles).  Returns U."""
+        k = self._block_check("U", U)
+        self._block_check("F", F, k)
+        self._block_device(U=U, F=F)
+        self._block_call(U.device, lambda: _chk(lib().amg_hip_block_vcycles(
+            self._h, k, C.c_void_p(F.data_ptr()), C.c_void_p(U.data_ptr()), int(n))))
+        return U
+
+    def block_rss(self, U, F):
+        """rss() of every column (amg_hip_block_rss): a numpy array of k values."""
+        k = self._block_check("U", U)
+        self._block_check("F", F, k)
+        self._block_device(U=U, F=F)
+        out = np.zeros(k, np.float64)
+        self._block_call(U.device, lambda: _chk(lib().amg_hip_block_rss(
+            self._h, k, C.c_void_p(F.data_ptr()), C.c_void_p(U.data_ptr()), _p64(out))))
+        return out
+
+    def block_pcg(self, B, X=None, rtol=1e-10, max_iters=100):
+        """pcg() on every column of B from X (zero when None), sharing the SpMVs and V-cycles
+        (amg_hip_block_pcg).  Returns (X, iters, relres); X is updated in place when given."""
+        import torch
+        k = self._block_check("B", B)
+        if X is None:
+            X = torch.zeros_like(B)
+        self._block_check("X", X, k)
+        self._block_device(B=B, X=X)
+        it = np.zeros(k, np.int64)
+        rel = np.zeros(k, np.float64)
+        self._block_call(B.device, lambda: _chk(lib().amg_hip_block_pcg(
+            self._h, k, C.c_void_p(B.data_ptr()), C.c_void_p(X.data_ptr()), float(rtol), int(max_iters),
+            it.ctypes.data_as(_i64p), _p64(rel))))
+        return X, it, rel
+
+    def block_must_move(self, k):
+        """bytes one block cycle on k columns has to move (amg_hip_block_must_move)"""
+        b = C.c_double(0)
+        _chk(lib().amg_hip_block_must_move(self._h, int(k), C.byref(b)))
+        return b.value
 
     def solve(self):
         """multigrid.hpp:311-337.  Returns (u, iters, converged, last_rss) and

@@ -3928,8 +3928,12 @@ template <int M>
 __global__ __launch_bounds__(64) void band_solve_kernel(
     int64_t n, const double* __restrict__ sched_f, const double* __restrict__ sched_b,
     const double* __restrict__ dg, const double* __restrict__ f, double* __restrict__ y,
-    double* __restrict__ x) {
+    double* __restrict__ x, int64_t cstride) {
   const int lane = threadIdx.x;
+  const int64_t co = (int64_t)blockIdx.x * cstride;  // one workgroup per right-hand side (block cycle)
+  f += co;
+  y += co;
+  x += co;
   band_pass<M, true>(n, lane, sched_f, f, y);           // L y = f
   __threadfence_block();
   for (int64_t i = lane; i < n; i += 64) y[i] = y[i] / dg[i];  // z = y / D
@@ -4054,8 +4058,10 @@ template <int W>
 __global__ __launch_bounds__(64) void band_chain_kernel(
     int n, const double* __restrict__ cf, const double* __restrict__ cb,
     const double* __restrict__ dg, const double* __restrict__ f, double* __restrict__ x, int n_h,
-    const double* uh_in, double* uh_out, int pre) {
+    const double* uh_in, double* uh_out, int pre, int64_t cstride) {
   extern __shared__ double chain_lds[];
+  f += (int64_t)blockIdx.x * cstride;  // one workgroup per right-hand side (block cycle)
+  x += (int64_t)blockIdx.x * cstride;
   const int np = band_chain_pad(n);
   double* ops = chain_lds;           // np x W: forward operands
   double* v = chain_lds + np * W;    // np: right-hand side in step order, then the result
@@ -4131,15 +4137,16 @@ __global__ __launch_bounds__(64) void band_chain_kernel(
 bool band_chain_ok(int64_t n, int64_t w) { return w >= 1 && w <= 3 && n >= 1 && n <= 2048; }
 hipError_t launch_band_chain(int64_t n, int w, const double* cf, const double* cb, const double* dg,
                              const double* f, double* x, hipStream_t st, int64_t n_h, const double* uh_in,
-                             double* uh_out) {
+                             double* uh_out, int cols, int64_t cstride) {
   if (!band_chain_ok(n, w) || (uh_out && (!uh_in || n_h < 1 || n_h > 2 * n + 2))) return hipErrorInvalidValue;
+  if (cols < 1 || (uh_out && cols != 1)) return hipErrorInvalidValue;
   const size_t np = (size_t)band_chain_pad((int)n);
   const int pre = sizeof(double) * np * (size_t)(2 * w + 1) <= (size_t)48 * 1024 ? 1 : 0;
   const size_t lds = sizeof(double) * np * (size_t)(pre ? 2 * w + 1 : w + 1);
   switch (w) {
-    case 1: hipLaunchKernelGGL(band_chain_kernel<1>, dim3(1), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre); break;
-    case 2: hipLaunchKernelGGL(band_chain_kernel<2>, dim3(1), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre); break;
-    default: hipLaunchKernelGGL(band_chain_kernel<3>, dim3(1), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre); break;
+    case 1: hipLaunchKernelGGL(band_chain_kernel<1>, dim3(cols), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
+    case 2: hipLaunchKernelGGL(band_chain_kernel<2>, dim3(cols), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
+    default: hipLaunchKernelGGL(band_chain_kernel<3>, dim3(cols), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
   }
   return hipGetLastError();
 }
@@ -4431,8 +4438,12 @@ __device__ __forceinline__ void band_wide_pass(int64_t n, int w, int ringmask, d
 __global__ __launch_bounds__(64) void band_wide_kernel(
     int64_t n, int w, int ringmask, const double* __restrict__ sched_f,
     const double* __restrict__ sched_b, const double* __restrict__ dg, const double* f, double* y,
-    double* x) {
+    double* x, int64_t cstride) {
   extern __shared__ double ring[];
+  const int64_t co = (int64_t)blockIdx.x * cstride;  // one workgroup per right-hand side (block cycle)
+  f += co;
+  y += co;
+  x += co;
   band_wide_pass<true>(n, w, ringmask, ring, sched_f, f, y);   // L y = f
   __threadfence_block();
   for (int64_t i = threadIdx.x; i < n; i += 64) y[i] = y[i] / dg[i];  // z = y / D
@@ -4442,13 +4453,14 @@ __global__ __launch_bounds__(64) void band_wide_kernel(
 }
 hipError_t launch_band_wide(int64_t n, int64_t w, const double* sched_f, const double* sched_b,
                             const double* dg, const double* f, double* y, double* x,
-                            hipStream_t st) {
+                            hipStream_t st, int cols, int64_t cstride) {
   if (n <= 0) return hipSuccess;
+  if (cols < 1) return hipErrorInvalidValue;
   int64_t R = 128;
   while (R < w + 64) R *= 2;
   if (R * 8 > 65536 || w < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(band_wide_kernel, dim3(1), dim3(64), (size_t)R * 8, st, n, (int)w, (int)(R - 1),
-                     sched_f, sched_b, dg, f, y, x);
+  hipLaunchKernelGGL(band_wide_kernel, dim3(cols), dim3(64), (size_t)R * 8, st, n, (int)w, (int)(R - 1),
+                     sched_f, sched_b, dg, f, y, x, cstride);
   return hipGetLastError();
 }
 
@@ -4550,14 +4562,15 @@ hipError_t launch_spike_solve(const SpikeArgs& a, hipStream_t st) {
 
 hipError_t launch_band_solve(int64_t n, int m, const double* sched_f, const double* sched_b,
                              const double* dg, const double* f, double* y, double* x,
-                             hipStream_t st) {
+                             hipStream_t st, int cols, int64_t cstride) {
   if (n <= 0) return hipSuccess;
+  if (cols < 1) return hipErrorInvalidValue;
   switch (m) {
-    case 4: hipLaunchKernelGGL(band_solve_kernel<4>, dim3(1), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x); break;
-    case 8: hipLaunchKernelGGL(band_solve_kernel<8>, dim3(1), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x); break;
-    case 16: hipLaunchKernelGGL(band_solve_kernel<16>, dim3(1), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x); break;
-    case 32: hipLaunchKernelGGL(band_solve_kernel<32>, dim3(1), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x); break;
-    case 64: hipLaunchKernelGGL(band_solve_kernel<64>, dim3(1), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x); break;
+    case 4: hipLaunchKernelGGL(band_solve_kernel<4>, dim3(cols), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x, cstride); break;
+    case 8: hipLaunchKernelGGL(band_solve_kernel<8>, dim3(cols), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x, cstride); break;
+    case 16: hipLaunchKernelGGL(band_solve_kernel<16>, dim3(cols), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x, cstride); break;
+    case 32: hipLaunchKernelGGL(band_solve_kernel<32>, dim3(cols), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x, cstride); break;
+    case 64: hipLaunchKernelGGL(band_solve_kernel<64>, dim3(cols), dim3(64), 0, st, n, sched_f, sched_b, dg, f, y, x, cstride); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -5002,6 +5015,305 @@ hipError_t launch_dict_types(int64_t n, const uint64_t* codes, int words, const 
   if (ntypes > 255 || (words != 1 && words != 2)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(dict_type_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, codes,
                      words, rwords, ntypes, rtype, fail);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ K-Block ----
+// Multi-right-hand-side (block) forms of the V-cycle's row kernels (solver.cpp: "block cycle").
+// Vectors are ROW-major panels of n x KP doubles (entry (i, j) at i * KP + j), KP a power of two
+// <= 16.  Lane = (row, column): KP consecutive lanes share one row, load the same col / val (the
+// same-address loads are served once) and each gathers x[c * KP + j]: a row group reads one
+// contiguous 8 KP-byte segment and stores out[row * KP + j] coalesced.  Per (row, column) the
+// operations and their order are csr_stage_kernel's (ascending column order, the diagonal picked
+// out of the walk for the Jacobi / Chebyshev quotient, the residual's sum started at f), so column
+// j has the bits of the single-vector kernel on column j.  KP = 1 is plain thread-per-row CSR.
+template <int MODE, int KP>
+__global__ __launch_bounds__(256) void block_csr_kernel(
+    int64_t n, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+    const double* __restrict__ val, const double* __restrict__ x, const double* f,  // f may be out
+    double* out, double omega, double* dvec, double alpha) {
+  constexpr int RPB = 256 / KP;  // rows per workgroup
+  const int tid = threadIdx.x;
+  const int64_t row = (int64_t)blockIdx.x * RPB + tid / KP;
+  const int j = tid % KP;
+  if (row >= n) return;
+  const int64_t o = row * KP + j;
+  const int32_t rs = rowptr[row], re = rowptr[row + 1];
+  double fi = 0.0, xi = 0.0, di = 0.0;
+  if (MODE != CSR_SPMV) fi = f[o];
+  if (mode_jac(MODE)) xi = x[o];
+  if (mode_cheb(MODE) && !cheb_first(MODE)) di = dvec[o];
+  double acc = (MODE == CSR_RESID) ? fi : 0.0;
+  double diag = 0.0;
+  constexpr int U = 4;  // gathers issued together; the sum itself stays in row order
+  for (int32_t p = rs; p < re; p += U) {
+    int32_t c[U];
+    double v[U], xx[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int32_t q = p + u < re ? p + u : p;
+      c[u] = col[q];
+      v[u] = val[q];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) xx[u] = x[(int64_t)c[u] * KP + j];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (p + u < re) {
+        if (MODE == CSR_RESID) {
+          acc -= v[u] * xx[u];
+        } else if (mode_jac(MODE)) {
+          if ((int64_t)c[u] == row) diag = v[u];
+          else acc += v[u] * xx[u];
+        } else {
+          acc += v[u] * xx[u];
+        }
+      }
+    }
+  }
+  if (MODE == CSR_RESID || MODE == CSR_SPMV) {
+    out[o] = acc;
+  } else if (MODE == CSR_SPMV_ADD) {
+    out[o] = fi + acc;
+  } else if (MODE == CSR_JACOBI) {
+    out[o] = (diag == 0.0) ? xi : xi + omega * ((fi - acc) / diag - xi);
+  } else if (mode_cheb(MODE)) {
+    double dn;
+    out[o] = cheb_update<MODE>((diag == 0.0) ? xi : (fi - acc) / diag, xi, di, alpha, omega, dn);
+    if (!cheb_last(MODE)) dvec[o] = dn;
+  } else {  // CSR_RSSQ
+    const double d = fi - acc;
+    out[o] = d * d;
+  }
+}
+
+template <int MODE>
+static hipError_t launch_block_csr_m(int kp, int64_t n, const int32_t* rowptr, const int32_t* col,
+                                     const double* val, const double* x, const double* f, double* out,
+                                     double omega, double* dvec, double alpha, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int64_t rpb = 256 / kp;
+  const dim3 grid((unsigned)((n + rpb - 1) / rpb));
+#define AMG_BLOCK_CSR(KP)                                                                                \
+  hipLaunchKernelGGL((block_csr_kernel<MODE, KP>), grid, dim3(256), 0, st, n, rowptr, col, val, x, f, out, \
+                     omega, dvec, alpha)
+  switch (kp) {
+    case 1: AMG_BLOCK_CSR(1); break;
+    case 2: AMG_BLOCK_CSR(2); break;
+    case 4: AMG_BLOCK_CSR(4); break;
+    case 8: AMG_BLOCK_CSR(8); break;
+    case 16: AMG_BLOCK_CSR(16); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef AMG_BLOCK_CSR
+  return hipGetLastError();
+}
+hipError_t launch_block_csr(int mode, int kp, int64_t n, const int32_t* rowptr, const int32_t* col,
+                            const double* val, const double* x, const double* f, double* out, double omega,
+                            hipStream_t st) {
+  switch (mode) {
+    case CSR_RESID: return launch_block_csr_m<CSR_RESID>(kp, n, rowptr, col, val, x, f, out, omega, nullptr, 0.0, st);
+    case CSR_JACOBI: return launch_block_csr_m<CSR_JACOBI>(kp, n, rowptr, col, val, x, f, out, omega, nullptr, 0.0, st);
+    case CSR_SPMV: return launch_block_csr_m<CSR_SPMV>(kp, n, rowptr, col, val, x, f, out, omega, nullptr, 0.0, st);
+    case CSR_RSSQ: return launch_block_csr_m<CSR_RSSQ>(kp, n, rowptr, col, val, x, f, out, omega, nullptr, 0.0, st);
+    case CSR_SPMV_ADD:
+      return launch_block_csr_m<CSR_SPMV_ADD>(kp, n, rowptr, col, val, x, f, out, omega, nullptr, 0.0, st);
+  }
+  return hipErrorInvalidValue;
+}
+hipError_t launch_block_csr_cheb(int kp, int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
+                                 const double* x, const double* f, double* out, const ChebStep& c, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!c.d || x == out) return hipErrorInvalidValue;
+#define AMG_BLOCK_CHEB(FI, LA)                                                                                 \
+  return launch_block_csr_m<cheb_kernel_mode(FI, LA)>(kp, n, rowptr, col, val, x, f, out, c.beta, c.d, c.alpha, \
+                                                      st)
+  if (c.first && c.last) AMG_BLOCK_CHEB(true, true);
+  if (c.first) AMG_BLOCK_CHEB(true, false);
+  if (c.last) AMG_BLOCK_CHEB(false, true);
+  AMG_BLOCK_CHEB(false, false);
+#undef AMG_BLOCK_CHEB
+}
+
+// Element-wise block kernels: one lane per panel entry e = i * kp + j (kp = 1 << ks).
+static inline dim3 block_grid(int64_t count) { return dim3((unsigned)((count + 255) / 256)); }
+
+// linear_restrict_kernel per column: f_H = ((0 + 0.5 r[2i]) + 1.0 r[2i+1]) + 0.5 r[2i+2]; uH zeroed
+__global__ __launch_bounds__(256) void block_restrict_kernel(int64_t n_h, int64_t n_H, int ks,
+                                                             const double* __restrict__ r,
+                                                             double* __restrict__ fH, double* __restrict__ uH) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (n_H << ks)) return;
+  const int64_t jr = e >> ks, c = e & ((1 << ks) - 1);
+  if (uH) uH[e] = 0.0;
+  const int64_t i = 2 * jr;
+  double s = 0.0;
+  if (i < n_h) s += 0.5 * r[(i << ks) + c];
+  if (i + 1 < n_h) s += 1.0 * r[((i + 1) << ks) + c];
+  if (i + 2 < n_h) s += 0.5 * r[((i + 2) << ks) + c];
+  fH[e] = s;
+}
+hipError_t launch_block_restrict(int kp, int64_t n_h, int64_t n_H, const double* r, double* fH, double* uH_zero,
+                                 hipStream_t st) {
+  if (n_H <= 0) return hipSuccess;
+  const int ks = __builtin_ctz((unsigned)kp);
+  hipLaunchKernelGGL(block_restrict_kernel, block_grid(n_H * kp), dim3(256), 0, st, n_h, n_H, ks, r, fH, uH_zero);
+  return hipGetLastError();
+}
+// linear_prolong_add2_kernel per column: u_h = u_h + t, t = P u_H (t[2j+1] = 0 + 1.0 u_H[j],
+// t[2j] = (0 + 0.5 u_H[j-1]) + 0.5 u_H[j])
+__global__ __launch_bounds__(256) void block_prolong_add_kernel(int64_t n_h, int64_t n_H, int ks,
+                                                                const double* __restrict__ uH, double* uh) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (n_h << ks)) return;
+  const int64_t i = e >> ks, c = e & ((1 << ks) - 1);
+  const int64_t j = i >> 1;
+  double t = 0.0;
+  if (i & 1) {
+    if (j < n_H) t += 1.0 * uH[(j << ks) + c];
+  } else {
+    if (j >= 1 && j - 1 < n_H) t += 0.5 * uH[((j - 1) << ks) + c];
+    if (j < n_H) t += 0.5 * uH[(j << ks) + c];
+  }
+  uh[e] = uh[e] + t;
+}
+hipError_t launch_block_prolong_add(int kp, int64_t n_h, int64_t n_H, const double* uH, double* uh,
+                                    hipStream_t st) {
+  if (n_h <= 0) return hipSuccess;
+  const int ks = __builtin_ctz((unsigned)kp);
+  hipLaunchKernelGGL(block_prolong_add_kernel, block_grid(n_h * kp), dim3(256), 0, st, n_h, n_H, ks, uH, uh);
+  return hipGetLastError();
+}
+
+// user pitch k <-> internal pitch kp: to_panel pads columns k .. kp-1 with zeros
+__global__ __launch_bounds__(256) void block_pitch_kernel(int64_t n, int k, int ks, const double* __restrict__ src,
+                                                          double* __restrict__ dst, int to_panel) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (to_panel) {
+    if (e >= (n << ks)) return;
+    const int64_t i = e >> ks;
+    const int c = (int)(e & ((1 << ks) - 1));
+    dst[e] = c < k ? src[i * k + c] : 0.0;
+  } else {
+    if (e >= n * k) return;
+    const int64_t i = e / k;
+    const int c = (int)(e - i * k);
+    dst[e] = src[(i << ks) + c];
+  }
+}
+hipError_t launch_block_pitch(int64_t n, int k, int kp, const double* src, double* dst, bool to_panel,
+                              hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int ks = __builtin_ctz((unsigned)kp);
+  hipLaunchKernelGGL(block_pitch_kernel, block_grid(to_panel ? n * kp : n * k), dim3(256), 0, st, n, k, ks, src,
+                     dst, to_panel ? 1 : 0);
+  return hipGetLastError();
+}
+// panel (n x kp, row-major) <-> kp contiguous columns of n (the coarse solve's operands)
+__global__ __launch_bounds__(256) void block_columns_kernel(int64_t n, int ks, const double* __restrict__ src,
+                                                            double* __restrict__ dst, int to_columns) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (n << ks)) return;
+  const int64_t i = e >> ks, c = e & ((1 << ks) - 1);
+  if (to_columns) dst[c * n + i] = src[e];
+  else dst[e] = src[c * n + i];
+}
+hipError_t launch_block_columns(int kp, int64_t n, const double* src, double* dst, bool to_columns,
+                                hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int ks = __builtin_ctz((unsigned)kp);
+  hipLaunchKernelGGL(block_columns_kernel, block_grid(n * kp), dim3(256), 0, st, n, ks, src, dst,
+                     to_columns ? 1 : 0);
+  return hipGetLastError();
+}
+
+// K-SumSq per column: the thread owning rows i, i + G, ... (G = grid x 256) keeps one partial per
+// column (s += x, or s += x * y), reading each row's KP contiguous values once; then per column
+// the same wave_sum and four-wave combine as sum_kernel / dot_kernel.  Launched with one workgroup
+// over the (blocks x KP) partials it is the second stage: sum_kernel's on every column.
+template <int KP>
+__global__ __launch_bounds__(256) void block_sum_kernel(int64_t n, const double* __restrict__ x,
+                                                        const double* __restrict__ y, double* __restrict__ out) {
+  __shared__ double part[4][KP];
+  double s[KP];
+#pragma unroll
+  for (int j = 0; j < KP; ++j) s[j] = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+      const double v = x[i * KP + j];
+      s[j] += y ? v * y[i * KP + j] : v;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KP; ++j) {
+    const double w = wave_sum(s[j]);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][j] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < KP) {
+    const int j = threadIdx.x;
+    out[(int64_t)blockIdx.x * KP + j] = ((part[0][j] + part[1][j]) + part[2][j]) + part[3][j];
+  }
+}
+// out[j] = sum_i x[i, j] (y == null) or sum_i x[i, j] y[i, j]; scratch: 1024 x kp doubles
+hipError_t launch_block_sum(int kp, int64_t n, const double* x, const double* y, double* out, double* scratch,
+                            hipStream_t st) {
+  int64_t g = (n + 255) / 256;
+  if (g > 1024) g = 1024;
+  if (g < 1) g = 1;
+#define AMG_BLOCK_SUM(KP)                                                                                    \
+  hipLaunchKernelGGL(block_sum_kernel<KP>, dim3((unsigned)g), dim3(256), 0, st, n, x, y, scratch);          \
+  hipLaunchKernelGGL(block_sum_kernel<KP>, dim3(1), dim3(256), 0, st, g, scratch, (const double*)nullptr, out)
+  switch (kp) {
+    case 1: AMG_BLOCK_SUM(1); break;
+    case 2: AMG_BLOCK_SUM(2); break;
+    case 4: AMG_BLOCK_SUM(4); break;
+    case 8: AMG_BLOCK_SUM(8); break;
+    case 16: AMG_BLOCK_SUM(16); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef AMG_BLOCK_SUM
+  return hipGetLastError();
+}
+
+// K-PCG per column with a mask: columns whose act[j] is 0 are frozen (x, r, p untouched)
+__global__ __launch_bounds__(256) void block_pcg_xr_kernel(int64_t n, int ks, const double* __restrict__ num,
+                                                           const double* __restrict__ den,
+                                                           const int32_t* __restrict__ act, double* x, double* r,
+                                                           const double* __restrict__ p,
+                                                           const double* __restrict__ q) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (n << ks)) return;
+  const int c = (int)(e & ((1 << ks) - 1));
+  if (!act[c]) return;
+  const double alpha = num[c] / den[c];
+  x[e] = x[e] + alpha * p[e];
+  r[e] = r[e] - alpha * q[e];
+}
+__global__ __launch_bounds__(256) void block_pcg_p_kernel(int64_t n, int ks, const double* __restrict__ num,
+                                                          const double* __restrict__ den,
+                                                          const int32_t* __restrict__ act, double* p,
+                                                          const double* __restrict__ z) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (n << ks)) return;
+  const int c = (int)(e & ((1 << ks) - 1));
+  if (!act[c]) return;
+  const double beta = num[c] / den[c];
+  p[e] = z[e] + beta * p[e];
+}
+hipError_t launch_block_pcg_update_xr(int kp, int64_t n, const double* num, const double* den, const int32_t* act,
+                                      double* x, double* r, const double* p, const double* q, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int ks = __builtin_ctz((unsigned)kp);
+  hipLaunchKernelGGL(block_pcg_xr_kernel, block_grid(n * kp), dim3(256), 0, st, n, ks, num, den, act, x, r, p, q);
+  return hipGetLastError();
+}
+hipError_t launch_block_pcg_update_p(int kp, int64_t n, const double* num, const double* den, const int32_t* act,
+                                     double* p, const double* z, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int ks = __builtin_ctz((unsigned)kp);
+  hipLaunchKernelGGL(block_pcg_p_kernel, block_grid(n * kp), dim3(256), 0, st, n, ks, num, den, act, p, z);
   return hipGetLastError();
 }
 

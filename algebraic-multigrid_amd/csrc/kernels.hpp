@@ -345,20 +345,24 @@ hipError_t launch_gs_scan(int64_t n, const DictRef& D, const double* b, double* 
 // per-(step, lane) L operands (host_setup: band_schedule); y: scratch, n doubles
 hipError_t launch_band_solve(int64_t n, int m, const double* sched_f, const double* sched_b,
                              const double* dg, const double* f, double* y, double* x,
-                             hipStream_t st);
+                             hipStream_t st, int cols = 1, int64_t cstride = 0);
+// cols > 1 (the block cycle): one workgroup per right-hand side in the same launch, column c's
+// f / y / x at c * cstride; cols = 1 is the single-vector launch (the same for K-BandChain and
+// K-BandWide below)
 
 // K-BandChain: narrow band (w <= 3), small n (<= 2048), everything in LDS; same bits as K-Band.
 // cf / cb: n x w operands per step (host_setup.hpp: band_chain_schedule)
 bool band_chain_ok(int64_t n, int64_t w);
 hipError_t launch_band_chain(int64_t n, int w, const double* cf, const double* cb, const double* dg,
                              const double* f, double* x, hipStream_t st, int64_t n_h = 0,
-                             const double* uh_in = nullptr, double* uh_out = nullptr);
+                             const double* uh_in = nullptr, double* uh_out = nullptr, int cols = 1,
+                             int64_t cstride = 0);
 // Any half-bandwidth (K-BandWide): rows in blocks of 64; sched_f/sched_b hold per block a
 // [w][64] panel of the operands that reach into earlier blocks followed by the block's own
 // [64][64] triangle (host_setup: band_wide_schedule).  w + 64 <= 8192 (LDS ring).
 hipError_t launch_band_wide(int64_t n, int64_t w, const double* sched_f, const double* sched_b,
                             const double* dg, const double* f, double* y, double* x,
-                            hipStream_t st);
+                            hipStream_t st, int cols = 1, int64_t cstride = 0);
 
 // Partitioned coarse solve (K-Spike); arrays as in host_setup.hpp: SpikeFactor.
 struct SpikeArgs {
@@ -405,5 +409,35 @@ hipError_t launch_dict_encode(int64_t n, const int32_t* rowptr, const int32_t* c
                               uint64_t* codes, int32_t* fail, hipStream_t st);
 hipError_t launch_dict_types(int64_t n, const uint64_t* codes, int words, const uint64_t* rwords,
                              int ntypes, uint8_t* rtype, int32_t* fail, hipStream_t st);
+
+// K-Block (kernels.hip): multi-right-hand-side forms for the block cycle.  Vectors are row-major
+// panels of n x kp doubles (entry (i, j) at i * kp + j), kp in {1, 2, 4, 8, 16}; per column the
+// operations of the single-vector kernels in the same order (same bits).  Plain CSR, lane = (row,
+// column); modes CSR_RESID, CSR_JACOBI, CSR_SPMV, CSR_SPMV_ADD (f may be out), CSR_RSSQ.
+hipError_t launch_block_csr(int mode, int kp, int64_t n, const int32_t* rowptr, const int32_t* col,
+                            const double* val, const double* x, const double* f, double* out, double omega,
+                            hipStream_t st);
+hipError_t launch_block_csr_cheb(int kp, int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
+                                 const double* x, const double* f, double* out, const ChebStep& c, hipStream_t st);
+// linear_restrict / linear_prolong_add per column (uH_zero optional: zero-filled in the same pass)
+hipError_t launch_block_restrict(int kp, int64_t n_h, int64_t n_H, const double* r, double* fH, double* uH_zero,
+                                 hipStream_t st);
+hipError_t launch_block_prolong_add(int kp, int64_t n_h, int64_t n_H, const double* uH, double* uh,
+                                    hipStream_t st);
+// to_panel: dst (n x kp) = src (n x k), columns k .. kp-1 zero; else dst (n x k) = the first k columns
+hipError_t launch_block_pitch(int64_t n, int k, int kp, const double* src, double* dst, bool to_panel,
+                              hipStream_t st);
+// to_columns: dst[j * n + i] = src[i * kp + j]; else the inverse
+hipError_t launch_block_columns(int kp, int64_t n, const double* src, double* dst, bool to_columns,
+                                hipStream_t st);
+// out[j] = sum_i x[i, j] (y null) or sum_i x[i, j] y[i, j], K-SumSq's tree per column; scratch: 1024 kp
+hipError_t launch_block_sum(int kp, int64_t n, const double* x, const double* y, double* out, double* scratch,
+                            hipStream_t st);
+// K-PCG updates per column j with act[j] != 0: alpha = num[j] / den[j], x += alpha p, r -= alpha q;
+// beta = num[j] / den[j], p = z + beta p
+hipError_t launch_block_pcg_update_xr(int kp, int64_t n, const double* num, const double* den, const int32_t* act,
+                                      double* x, double* r, const double* p, const double* q, hipStream_t st);
+hipError_t launch_block_pcg_update_p(int kp, int64_t n, const double* num, const double* den, const int32_t* act,
+                                     double* p, const double* z, hipStream_t st);
 
 }  // namespace amg_hip

@@ -1028,6 +1028,35 @@ struct Slab {
   }
 };
 
+// Block (multi-right-hand-side) cycle: per-level panels of n_l x kp doubles (row-major, entry (i, j)
+// at i * kp + j; kp = k rounded up to a power of two <= 16, padded columns zero) and the plain CSR
+// copies the block kernels walk.  Made at the first block call; the panels grow with kp.
+struct BlockLevel {
+  DevCsr rows_own, cols_own;       // CSR copies of levels whose single-vector layout is not CSR
+  const DevCsr* rows = nullptr;    // rows of A (residual, Chebyshev, rss, PCG)
+  const DevCsr* cols = nullptr;    // columns of A walked as rows (Jacobi); = rows when symmetric
+  DevMem U, F, R, T, D;            // solution, right-hand side, residual, ping-pong, Chebyshev d
+};
+constexpr int BLOCK_K_MAX = 16;
+struct Block {
+  bool mats = false;               // the CSR copies exist
+  int kp_alloc = 0;                // panel pitch the buffers were allocated for
+  std::vector<BlockLevel> lv;
+  DevMem cf, cy, cx;               // coarsest level as kp contiguous columns: f, scratch, x
+  DevMem px, pp, pq, pb;           // PCG panels (level-0 size)
+  DevMem part, dots, act;          // 1024 x 16 partials; 6 x 16 device scalars; 16 column flags
+  hipGraph_t graph[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // per log2(kp)
+  hipGraphExec_t exec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  void reset_graphs() {
+    for (int i = 0; i < 5; ++i) {
+      if (exec[i]) (void)hipGraphExecDestroy(exec[i]);
+      if (graph[i]) (void)hipGraphDestroy(graph[i]);
+      exec[i] = nullptr;
+      graph[i] = nullptr;
+    }
+  }
+};
+
 // amg_hip_set_tail_fusion / AMG_HIP_TAIL_FUSION=1: K-Tail (deepest levels + coarsest solve in one
 // launch).  Off by default: bit-identical, and measured 0.5 % SLOWER than one launch per step on the
 // 4096^2 cycle (1282 / 1291 / 1293 against 1299 / 1301 / 1294 V-cycles/s, alternating runs).
@@ -1062,8 +1091,19 @@ struct amg_hip_solver {
   int acct_part = -1;  // -1: not inside enqueue_vcycle
   void acct(double bytes) { if (acct_part >= 0) must_move[acct_part] += bytes; }
   Slab slab;
+  Block blk;
+  // block cycle bytes, counted while it is enqueued: matrix bytes (once per launch) and bytes per
+  // row-column pair; one block cycle on k columns has to move block_mm[0] + k * block_mm[1]
+  bool block_acct = false;
+  double block_mm[2] = {0, 0};
+  void bacct(double mat, double per_col) {
+    if (!block_acct) return;
+    block_mm[0] += mat;
+    block_mm[1] += per_col;
+  }
 
   ~amg_hip_solver() {
+    blk.reset_graphs();
     slab.reset_graphs();
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     if (graph) (void)hipGraphDestroy(graph);
@@ -2690,6 +2730,288 @@ amg_hip_status need_device() {
   return AMG_HIP_OK;
 }
 
+// ---- block (multi-right-hand-side) cycle ---------------------------------------
+// The same V-cycle as enqueue_vcycle_body on kp columns at once, with plain launches of the K-Block
+// kernels on CSR: per (row, column) every kernel does the operations of the single-vector path's
+// unfused form in the same order, and the fusions of that path are bit-neutral, so column j ends
+// with the bits of vcycle() on column j ("Block cycle").
+const char* block_smoother_name(int32_t sm) {
+  switch (sm) {
+    case AMG_HIP_SM_SPGS: return "SparseGaussSeidel (AMG_HIP_SM_SPGS)";
+    case AMG_HIP_SM_REF_JACOBI: return "AMG::Jacobi (AMG_HIP_SM_REF_JACOBI)";
+    case AMG_HIP_SM_SOR: return "SOR (AMG_HIP_SM_SOR)";
+    case AMG_HIP_SM_MULTICOLOR_GS: return "multicolour Gauss-Seidel (AMG_HIP_SM_MULTICOLOR_GS)";
+  }
+  return "unknown";
+}
+bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+int block_kp(int32_t k) {
+  int kp = 1;
+  while (kp < k) kp *= 2;
+  return kp;
+}
+// steps 2 and 3 of the argument checks (include/amg_hip.h: amg_hip_block_vcycles)
+amg_hip_status block_supported(amg_hip_solver* s) {
+  if (s->opt.window)
+    return fail(AMG_HIP_EUNSUPPORTED, "block cycles: a window solver (opt.window) is not supported");
+  if (s->opt.smoother != AMG_HIP_SM_JACOBI && s->opt.smoother != AMG_HIP_SM_CHEBYSHEV)
+    return fail(AMG_HIP_EUNSUPPORTED, std::string("block cycles: the smoother ") +
+                                          block_smoother_name(s->opt.smoother) +
+                                          " is not supported (true Jacobi and Chebyshev are)");
+  return set_device(s);
+}
+bool has_exact_zero(const Sparse& M) {
+  for (double v : M.val)
+    if (v == 0.0) return true;
+  return false;
+}
+double csr_bytes(const DevCsr& M) { return 12.0 * (double)M.nnz + 4.0 * (double)(M.n_rows + 1); }
+
+// the CSR copies (once) and the panels for pitch kp (again only when kp grows)
+amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
+  Block& B = s->blk;
+  const int nl = (int)s->lv.size();
+  const bool prune = !s->opt.keep_structural_zeros;
+  if (!B.mats) {
+    B.lv.clear();
+    B.lv.resize((size_t)nl);
+    for (int l = 0; l < nl; ++l) {
+      Level& L = s->lv[l];
+      BlockLevel& Q = B.lv[(size_t)l];
+      if (l + 1 == nl && l > 0) continue;  // the coarsest level only takes the direct solve
+      // the entry set of the device matrices: exact zeros dropped unless keep_structural_zeros,
+      // ascending column order (A_rows is plain CSR already when its layout is)
+      if (!L.A_rows.dict && !L.A_rows.sell) {
+        Q.rows = &L.A_rows.csr;
+      } else {
+        HIP_TRY(L.ensure_host_matrix());
+        const Sparse rows = L.symmetric ? L.A_csc : transpose(L.A_csc);  // CSR(A)
+        HIP_TRY(upload_csr(prune && has_exact_zero(rows) ? without_exact_zeros(rows) : rows, &Q.rows_own));
+        Q.rows = &Q.rows_own;
+      }
+      Q.cols = Q.rows;
+      if (!L.symmetric && s->opt.smoother == AMG_HIP_SM_JACOBI) {
+        const DevMat& Ac = L.A_cols();
+        if (!Ac.dict && !Ac.sell) {
+          Q.cols = &Ac.csr;
+        } else {
+          HIP_TRY(L.ensure_host_matrix());
+          HIP_TRY(upload_csr(prune && has_exact_zero(L.A_csc) ? without_exact_zeros(L.A_csc) : L.A_csc, &Q.cols_own));
+          Q.cols = &Q.cols_own;
+        }
+      }
+    }
+    B.mats = true;
+  }
+  if (kp <= B.kp_alloc) return AMG_HIP_OK;
+  B.reset_graphs();  // their pointers are about to change
+  const bool cheb = s->opt.smoother == AMG_HIP_SM_CHEBYSHEV;
+  for (int l = 0; l < nl; ++l) {
+    const size_t bytes = sizeof(double) * (size_t)s->lv[l].n * (size_t)kp;
+    BlockLevel& Q = B.lv[(size_t)l];
+    HIP_TRY(Q.U.alloc(bytes));
+    HIP_TRY(Q.F.alloc(bytes));
+    if (l + 1 < nl || l == 0) {
+      HIP_TRY(Q.R.alloc(bytes));
+      HIP_TRY(Q.T.alloc(bytes));
+      if (cheb) HIP_TRY(Q.D.alloc(bytes));
+    }
+  }
+  const size_t cb = sizeof(double) * (size_t)s->lv[nl - 1].n * (size_t)kp;
+  HIP_TRY(B.cf.alloc(cb));
+  HIP_TRY(B.cy.alloc(cb));
+  HIP_TRY(B.cx.alloc(cb));
+  B.px.release();  // PCG panels: allocated at the first block_pcg for this pitch
+  B.pp.release();
+  B.pq.release();
+  B.pb.release();
+  if (!B.part.p) {
+    HIP_TRY(B.part.alloc(sizeof(double) * 1024 * BLOCK_K_MAX));
+    HIP_TRY(B.dots.alloc(sizeof(double) * 6 * BLOCK_K_MAX));
+    HIP_TRY(B.act.alloc(sizeof(int32_t) * BLOCK_K_MAX));
+  }
+  B.kp_alloc = kp;
+  return AMG_HIP_OK;
+}
+
+// dry: count the bytes, launch nothing (amg_hip_block_must_move)
+#define BLK(expr)                 \
+  do {                            \
+    if (!dry) HIP_TRY(expr);      \
+  } while (0)
+
+// the smoothing of one level (enqueue_smooth's plain launches): U -> T -> U ..., home after an odd count
+amg_hip_status enqueue_block_smooth(amg_hip_solver* s, int l, int kp, bool dry) {
+  Level& L = s->lv[l];
+  BlockLevel& Q = s->blk.lv[(size_t)l];
+  hipStream_t st = s->stream;
+  const double n = (double)L.n;
+  double* a = Q.U.as<double>();
+  double* b = Q.T.as<double>();
+  int64_t passes = 0;
+  if (s->opt.smoother == AMG_HIP_SM_JACOBI) {
+    const DevCsr& A = *Q.cols;
+    for (int it = 0; it < s->opt.smoother_iters; ++it) {
+      BLK(launch_block_csr(CSR_JACOBI, kp, L.n, A.rowptr(), A.col(), A.v(), a, Q.F.as<double>(), b, s->opt.omega,
+                           st));
+      s->bacct(csr_bytes(A), 24.0 * n);  // matrix; x, f, out
+      std::swap(a, b);
+      ++passes;
+    }
+  } else {
+    const DevCsr& A = *Q.rows;
+    const int k = s->opt.cheb_degree;
+    std::vector<double> alpha, beta;
+    cheb_coefs(L.cheb_lo, L.cheb_hi, k, &alpha, &beta);
+    for (int it = 0; it < s->opt.smoother_iters; ++it) {
+      for (int j = 0; j < k; ++j) {
+        ChebStep c;
+        c.d = Q.D.as<double>();
+        c.alpha = alpha[(size_t)j];
+        c.beta = beta[(size_t)j];
+        c.first = j == 0;
+        c.last = j == k - 1;
+        BLK(launch_block_csr_cheb(kp, L.n, A.rowptr(), A.col(), A.v(), a, Q.F.as<double>(), b, c, st));
+        s->bacct(csr_bytes(A), 24.0 * n + (c.first ? 0.0 : 8.0 * n) + (c.last ? 0.0 : 8.0 * n));
+        std::swap(a, b);
+        ++passes;
+      }
+    }
+  }
+  if (passes & 1) {
+    BLK(hipMemcpyAsync(Q.U.p, Q.T.p, sizeof(double) * (size_t)L.n * (size_t)kp, hipMemcpyDeviceToDevice, st));
+    s->bacct(0.0, 16.0 * n);
+  }
+  return AMG_HIP_OK;
+}
+
+// multigrid.hpp:263-305 on the block panels (enqueue_vcycle_body's order: down-legs, coarsest
+// solve, up-legs), one plain launch per step, a single stream
+amg_hip_status enqueue_block_vcycle(amg_hip_solver* s, int kp, bool dry) {
+  const int nl = (int)s->lv.size();
+  hipStream_t st = s->stream;
+  Block& B = s->blk;
+  amg_hip_status r;
+  for (int l = 0; l + 1 < nl; ++l) {
+    Level& L = s->lv[l];
+    Level& C = s->lv[l + 1];
+    BlockLevel& Q = B.lv[(size_t)l];
+    BlockLevel& QC = B.lv[(size_t)l + 1];
+    if ((r = enqueue_block_smooth(s, l, kp, dry)) != AMG_HIP_OK) return r;  // :268
+    const DevCsr& A = *Q.rows;                                               // :272-274
+    BLK(launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
+                         Q.R.as<double>(), 1.0, st));
+    s->bacct(csr_bytes(A), 24.0 * (double)L.n);
+    if (L.linear && s->opt.stencil_transfers) {                              // :278 + :281-282
+      BLK(launch_block_restrict(kp, L.n, C.n, Q.R.as<double>(), QC.F.as<double>(), QC.U.as<double>(), st));
+      s->bacct(0.0, 8.0 * (double)L.n + 16.0 * (double)C.n);
+    } else {
+      BLK(hipMemsetAsync(QC.U.p, 0, sizeof(double) * (size_t)C.n * (size_t)kp, st));
+      const DevCsr& R = L.R_rows;
+      BLK(launch_block_csr(CSR_SPMV, kp, R.n_rows, R.rowptr(), R.col(), R.v(), Q.R.as<double>(), nullptr,
+                           QC.F.as<double>(), 1.0, st));
+      s->bacct(csr_bytes(R), 8.0 * (double)L.n + 16.0 * (double)C.n);
+    }
+  }
+  {  // :287-288, every column in one launch of the one-wave kinds (one workgroup per column)
+    Level& C = s->lv[(size_t)nl - 1];
+    BlockLevel& QC = B.lv[(size_t)nl - 1];
+    const CoarseOnDev& K = s->coarse;
+    double* cf = B.cf.as<double>();
+    double* cy = B.cy.as<double>();
+    double* cx = B.cx.as<double>();
+    BLK(launch_block_columns(kp, C.n, QC.F.as<double>(), cf, true, st));
+    const double factor = 16.0 * (double)C.n * (double)std::max<int64_t>(K.w, 1);
+    switch (K.kind) {
+      case COARSE_SPIKE:
+        for (int j = 0; j < kp; ++j) {
+          SpikeArgs a = K.spike->a;
+          a.f = cf + (size_t)j * (size_t)C.n;
+          a.x = cx + (size_t)j * (size_t)C.n;
+          BLK(launch_spike_solve(a, st));
+        }
+        s->bacct(0.0, factor);
+        break;
+      case COARSE_WIDE:
+        BLK(launch_band_wide(K.n, K.w, K.sf.as<double>(), K.sb.as<double>(), K.d.as<double>(), cf, cy, cx, st, kp,
+                             C.n));
+        s->bacct(factor, 0.0);
+        break;
+      case COARSE_CHAIN:
+        BLK(launch_band_chain(K.n, (int)K.w, K.sf.as<double>(), K.sb.as<double>(), K.d.as<double>(), cf, cx, st, 0,
+                              nullptr, nullptr, kp, C.n));
+        s->bacct(factor, 0.0);
+        break;
+      default:
+        BLK(launch_band_solve(K.n, K.m, K.sf.as<double>(), K.sb.as<double>(), K.d.as<double>(), cf, cy, cx, st, kp,
+                              C.n));
+        s->bacct(factor, 0.0);
+        break;
+    }
+    BLK(launch_block_columns(kp, C.n, cx, QC.U.as<double>(), false, st));
+    // f and u of the solve; the two reorderings read and write each once
+    s->bacct(0.0, 24.0 * (double)C.n + 32.0 * (double)C.n);
+  }
+  for (int l = nl - 2; l >= 0; --l) {                                        // :291
+    Level& L = s->lv[l];
+    Level& C = s->lv[l + 1];
+    BlockLevel& Q = B.lv[(size_t)l];
+    BlockLevel& QC = B.lv[(size_t)l + 1];
+    if (L.linear && s->opt.stencil_transfers) {                              // :294-296
+      BLK(launch_block_prolong_add(kp, L.n, C.n, QC.U.as<double>(), Q.U.as<double>(), st));
+      s->bacct(0.0, 8.0 * (double)C.n + 16.0 * (double)L.n);
+    } else {
+      const DevCsr& P = L.P_rows;
+      BLK(launch_block_csr(CSR_SPMV_ADD, kp, P.n_rows, P.rowptr(), P.col(), P.v(), QC.U.as<double>(),
+                           Q.U.as<double>(), Q.U.as<double>(), 1.0, st));
+      s->bacct(csr_bytes(P), 8.0 * (double)C.n + 16.0 * (double)L.n);
+    }
+    if ((r = enqueue_block_smooth(s, l, kp, dry)) != AMG_HIP_OK) return r;  // :300
+  }
+  return AMG_HIP_OK;
+}
+#undef BLK
+
+int log2i(int kp) { return __builtin_ctz((unsigned)kp); }
+
+// n block cycles on the panels of level 0 (their pitch is kp): the captured graph of this kp, or
+// the same enqueue eagerly (use_graph = 0)
+amg_hip_status run_block_cycles(amg_hip_solver* s, int kp, int32_t n) {
+  Block& B = s->blk;
+  if (!s->opt.use_graph) {
+    for (int i = 0; i < n; ++i) {
+      amg_hip_status r = enqueue_block_vcycle(s, kp, false);
+      if (r != AMG_HIP_OK) return r;
+    }
+    return AMG_HIP_OK;
+  }
+  const int g = log2i(kp);
+  if (!B.exec[g]) {
+    HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+    amg_hip_status r = enqueue_block_vcycle(s, kp, false);
+    hipGraph_t gr = nullptr;
+    hipError_t e = hipStreamEndCapture(s->stream, &gr);
+    if (r != AMG_HIP_OK) {
+      if (gr) (void)hipGraphDestroy(gr);
+      return r;
+    }
+    if (e != hipSuccess) return fail(AMG_HIP_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+    B.graph[g] = gr;
+    HIP_TRY(hipGraphInstantiate(&B.exec[g], B.graph[g], nullptr, nullptr, 0));
+  }
+  for (int i = 0; i < n; ++i) HIP_TRY(hipGraphLaunch(B.exec[g], s->stream));
+  return AMG_HIP_OK;
+}
+
+// out[j] (host, j < kp) = sum_i x[i, j] (y null) or x[i, j] y[i, j] over level 0's rows
+amg_hip_status block_sums_to_host(amg_hip_solver* s, int kp, const double* x, const double* y, double* out) {
+  double* d = s->blk.dots.as<double>() + 3 * BLOCK_K_MAX;  // past block_pcg's rz, pq, rz_new
+  HIP_TRY(launch_block_sum(kp, s->lv[0].n, x, y, d, s->blk.part.as<double>(), s->stream));
+  HIP_TRY(hipMemcpyAsync(out, d, sizeof(double) * (size_t)kp, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return AMG_HIP_OK;
+}
+
 }  // namespace
 
 namespace amg_hip {
@@ -4274,6 +4596,154 @@ amg_hip_status amg_hip_dev_sumsq(int64_t n, const double* r, double* out, double
                                  void* stream) {
   if (n < 0 || !r || !out || !scratch) return fail(AMG_HIP_EINVAL, "bad argument");
   HIP_TRY(launch_sum(n, r, out, scratch, 1, (hipStream_t)stream));
+  return AMG_HIP_OK;
+}
+
+// ---- block (multi-right-hand-side) cycles ------------------------------------------
+amg_hip_status amg_hip_block_vcycles(amg_hip_solver* s, int32_t k, const double* F, double* U, int32_t n_cycles) {
+  if (!s || !F || !U) return fail(AMG_HIP_EINVAL, "null argument");
+  if (k < 1 || k > BLOCK_K_MAX) return fail(AMG_HIP_EINVAL, "k must be in 1 .. 16, got " + std::to_string(k));
+  if (n_cycles < 0) return fail(AMG_HIP_EINVAL, "n_cycles must be >= 0");
+  if (misaligned(F) || misaligned(U)) return fail(AMG_HIP_EINVAL, "F and U must be 16-byte aligned");
+  amg_hip_status r = block_supported(s);
+  if (r != AMG_HIP_OK) return r;
+  if (n_cycles == 0) return AMG_HIP_OK;
+  const int kp = block_kp(k);
+  if ((r = ensure_block(s, kp)) != AMG_HIP_OK) return r;
+  BlockLevel& Q = s->blk.lv[0];
+  const int64_t n = s->lv[0].n;
+  HIP_TRY(launch_block_pitch(n, k, kp, F, Q.F.as<double>(), true, s->stream));
+  HIP_TRY(launch_block_pitch(n, k, kp, U, Q.U.as<double>(), true, s->stream));
+  if ((r = run_block_cycles(s, kp, n_cycles)) != AMG_HIP_OK) return r;
+  HIP_TRY(launch_block_pitch(n, k, kp, Q.U.as<double>(), U, false, s->stream));
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_block_rss(amg_hip_solver* s, int32_t k, const double* F, const double* U, double* out) {
+  if (!s || !F || !U || !out) return fail(AMG_HIP_EINVAL, "null argument");
+  if (k < 1 || k > BLOCK_K_MAX) return fail(AMG_HIP_EINVAL, "k must be in 1 .. 16, got " + std::to_string(k));
+  if (misaligned(F) || misaligned(U)) return fail(AMG_HIP_EINVAL, "F and U must be 16-byte aligned");
+  amg_hip_status r = block_supported(s);
+  if (r != AMG_HIP_OK) return r;
+  const int kp = block_kp(k);
+  if ((r = ensure_block(s, kp)) != AMG_HIP_OK) return r;
+  BlockLevel& Q = s->blk.lv[0];
+  const int64_t n = s->lv[0].n;
+  const DevCsr& A = *Q.rows;
+  HIP_TRY(launch_block_pitch(n, k, kp, F, Q.F.as<double>(), true, s->stream));
+  HIP_TRY(launch_block_pitch(n, k, kp, U, Q.U.as<double>(), true, s->stream));
+  HIP_TRY(launch_block_csr(CSR_RSSQ, kp, n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
+                           Q.T.as<double>(), 1.0, s->stream));
+  double h[BLOCK_K_MAX];
+  if ((r = block_sums_to_host(s, kp, Q.T.as<double>(), nullptr, h)) != AMG_HIP_OK) return r;
+  for (int j = 0; j < k; ++j) out[j] = h[j];
+  return AMG_HIP_OK;
+}
+
+// k independent PCG recurrences (amg_hip_pcg's, step for step) sharing every SpMV and block cycle.
+// The block cycle's level-0 panels are the operands of M^-1: F holds r, U receives z.
+amg_hip_status amg_hip_block_pcg(amg_hip_solver* s, int32_t k, const double* Bv, double* X, double rtol,
+                                 int64_t max_iters, int64_t* iters, double* relres) {
+  if (!s || !Bv || !X) return fail(AMG_HIP_EINVAL, "null argument");
+  if (k < 1 || k > BLOCK_K_MAX) return fail(AMG_HIP_EINVAL, "k must be in 1 .. 16, got " + std::to_string(k));
+  if (misaligned(Bv) || misaligned(X)) return fail(AMG_HIP_EINVAL, "B and X must be 16-byte aligned");
+  if (!(rtol >= 0) || max_iters < 0) return fail(AMG_HIP_EINVAL, "bad tolerance / iteration limit");
+  amg_hip_status rc = block_supported(s);
+  if (rc != AMG_HIP_OK) return rc;
+  const int kp = block_kp(k);
+  if ((rc = ensure_block(s, kp)) != AMG_HIP_OK) return rc;
+  Block& B = s->blk;
+  BlockLevel& Q = B.lv[0];
+  const int64_t n = s->lv[0].n;
+  const size_t bytes = sizeof(double) * (size_t)n * (size_t)kp;
+  hipStream_t st = s->stream;
+  if (!B.px.p) {  // at the panels' pitch: a later call with a smaller k reuses them
+    const size_t pbytes = sizeof(double) * (size_t)n * (size_t)B.kp_alloc;
+    HIP_TRY(B.px.alloc(pbytes));
+    HIP_TRY(B.pp.alloc(pbytes));
+    HIP_TRY(B.pq.alloc(pbytes));
+    HIP_TRY(B.pb.alloc(pbytes));
+  }
+  const DevCsr& A = *Q.rows;
+  double* x = B.px.as<double>();
+  double* p = B.pp.as<double>();
+  double* q = B.pq.as<double>();
+  double* b = B.pb.as<double>();
+  double* r = Q.F.as<double>();
+  double* z = Q.U.as<double>();
+  double* d = B.dots.as<double>();
+  double* d_rz = d;
+  double* d_pq = d + BLOCK_K_MAX;
+  double* d_rzn = d + 2 * BLOCK_K_MAX;
+  double* part = B.part.as<double>();
+  int32_t* act = B.act.as<int32_t>();
+  double h[BLOCK_K_MAX], bnorm[BLOCK_K_MAX], rel[BLOCK_K_MAX];
+  int64_t it[BLOCK_K_MAX];
+  int32_t on[BLOCK_K_MAX];
+  HIP_TRY(launch_block_pitch(n, k, kp, Bv, b, true, st));
+  HIP_TRY(launch_block_pitch(n, k, kp, X, x, true, st));
+  if ((rc = block_sums_to_host(s, kp, b, b, h)) != AMG_HIP_OK) return rc;  // b . b
+  for (int j = 0; j < kp; ++j) bnorm[j] = std::sqrt(h[j]);
+  HIP_TRY(launch_block_csr(CSR_RESID, kp, n, A.rowptr(), A.col(), A.v(), x, b, r, 1.0, st));  // r = b - A x
+  if ((rc = block_sums_to_host(s, kp, r, r, h)) != AMG_HIP_OK) return rc;
+  int live = 0;
+  for (int j = 0; j < kp; ++j) {
+    it[j] = 0;
+    rel[j] = bnorm[j] > 0 ? std::sqrt(h[j]) / bnorm[j] : std::sqrt(h[j]);
+    on[j] = (j < k && !(rel[j] <= rtol || max_iters == 0)) ? 1 : 0;
+    live += on[j];
+  }
+  if (live > 0) {
+    HIP_TRY(hipMemcpy(act, on, sizeof(int32_t) * (size_t)kp, hipMemcpyHostToDevice));
+    // z = M^-1 r; p = z; rz = r . z
+    HIP_TRY(hipMemsetAsync(z, 0, bytes, st));
+    if ((rc = run_block_cycles(s, kp, 1)) != AMG_HIP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(launch_block_sum(kp, n, r, z, d_rz, part, st));
+  }
+  while (live > 0) {
+    HIP_TRY(launch_block_csr(CSR_SPMV, kp, n, A.rowptr(), A.col(), A.v(), p, nullptr, q, 1.0, st));  // q = A p
+    HIP_TRY(launch_block_sum(kp, n, p, q, d_pq, part, st));
+    HIP_TRY(launch_block_pcg_update_xr(kp, n, d_rz, d_pq, act, x, r, p, q, st));  // alpha = rz / pq
+    if ((rc = block_sums_to_host(s, kp, r, r, h)) != AMG_HIP_OK) return rc;
+    live = 0;
+    for (int j = 0; j < kp; ++j) {
+      if (!on[j]) continue;
+      it[j] += 1;
+      rel[j] = bnorm[j] > 0 ? std::sqrt(h[j]) / bnorm[j] : std::sqrt(h[j]);
+      if (!(rel[j] > rtol) || it[j] >= max_iters) on[j] = 0;  // NaN stops too
+      live += on[j];
+    }
+    if (live == 0) break;
+    HIP_TRY(hipMemcpy(act, on, sizeof(int32_t) * (size_t)kp, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(z, 0, bytes, st));
+    if ((rc = run_block_cycles(s, kp, 1)) != AMG_HIP_OK) return rc;  // z = M^-1 r
+    HIP_TRY(launch_block_sum(kp, n, r, z, d_rzn, part, st));
+    HIP_TRY(launch_block_pcg_update_p(kp, n, d_rzn, d_rz, act, p, z, st));  // beta = rz_new / rz
+    HIP_TRY(hipMemcpyAsync(d_rz, d_rzn, sizeof(double) * (size_t)kp, hipMemcpyDeviceToDevice, st));
+  }
+  HIP_TRY(launch_block_pitch(n, k, kp, x, X, false, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int j = 0; j < k; ++j) {
+    if (iters) iters[j] = it[j];
+    if (relres) relres[j] = rel[j];
+  }
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_block_must_move(amg_hip_solver* s, int32_t k, double* bytes) {
+  if (!s || !bytes) return fail(AMG_HIP_EINVAL, "null argument");
+  if (k < 1 || k > BLOCK_K_MAX) return fail(AMG_HIP_EINVAL, "k must be in 1 .. 16, got " + std::to_string(k));
+  amg_hip_status r = block_supported(s);
+  if (r != AMG_HIP_OK) return r;
+  const int kp = block_kp(k);
+  if ((r = ensure_block(s, kp)) != AMG_HIP_OK) return r;
+  s->block_mm[0] = s->block_mm[1] = 0.0;
+  s->block_acct = true;
+  r = enqueue_block_vcycle(s, kp, true);
+  s->block_acct = false;
+  if (r != AMG_HIP_OK) return r;
+  *bytes = s->block_mm[0] + (double)k * s->block_mm[1];
   return AMG_HIP_OK;
 }
 

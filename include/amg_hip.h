@@ -439,6 +439,31 @@ amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, in
  * the sequential sum to ~1e-15 relative). */
 amg_hip_status amg_hip_rss(amg_hip_solver* s, double* out);
 
+/* ---- block (multi-right-hand-side) cycles on the solver's hierarchy ---------------------
+ * F, U, B, X: DEVICE arrays of n_dofs(0) x k doubles, ROW-major (entry (i, j) at [i*k + j], i.e.
+ * a contiguous torch tensor of shape (n_0, k)), 16-byte aligned, 1 <= k <= 16.  Work is enqueued
+ * on the solver's stream.  Column j of every result has the bits of the single-vector entry point
+ * on column j (vcycle() after set_vec(0, u / f, column j); rss(); pcg()).  The solver's own level
+ * vectors are not touched.  Argument checks, in this order: null pointers, k outside 1..16,
+ * n_cycles < 0, a misaligned pointer, bad rtol / max_iters -> AMG_HIP_EINVAL; a window solver or a
+ * smoother other than AMG_HIP_SM_JACOBI / AMG_HIP_SM_CHEBYSHEV -> AMG_HIP_EUNSUPPORTED; then the
+ * device (a host_only solver fails there).  The first call builds plain CSR copies of the level
+ * matrices that are not CSR already and n_l x kp panels per level (kp = k rounded up to a power
+ * of two); with use_graph one captured graph per kp.                                          */
+amg_hip_status amg_hip_block_vcycles(amg_hip_solver* s, int32_t k, const double* F, double* U,
+                                     int32_t n_cycles);           /* U in/out: n_cycles V-cycles */
+amg_hip_status amg_hip_block_rss(amg_hip_solver* s, int32_t k, const double* F, const double* U,
+                                 double* out /* host, k */);      /* amg_hip_rss per column     */
+/* k independent PCG recurrences (amg_hip_pcg's, step for step, from X) that share every SpMV and
+ * every block V-cycle; a column that has stopped is frozen.  X receives the result; iters[j] and
+ * relres[j] (host arrays of k, may be null) are amg_hip_pcg's per column.                     */
+amg_hip_status amg_hip_block_pcg(amg_hip_solver* s, int32_t k, const double* B, double* X,
+                                 double rtol, int64_t max_iters,
+                                 int64_t* iters /* host, k */, double* relres /* host, k */);
+/* Bytes one block cycle's launches have to move on k columns: every matrix once per launch (CSR:
+ * 12 B per entry + 4 B per row), every vector 8 k bytes per row (padded columns not counted). */
+amg_hip_status amg_hip_block_must_move(amg_hip_solver* s, int32_t k, double* bytes);
+
 /* Getters, multigrid.hpp:339-354. */
 int32_t amg_hip_n_levels(const amg_hip_solver* s);
 int64_t amg_hip_get_n_dofs(const amg_hip_solver* s, int32_t level);

@@ -4,6 +4,8 @@ headline) and records the convergence factor next to every rate.
 usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configuration
        config_bench.py all                                         the README table
        config_bench.py cheb                                        the Chebyshev rows
+       config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
+       config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1).  Setup runs on the device (amg_hip_create_poisson);
 smoothers that need host structures fall back to the host path inside it."""
 import os
@@ -79,7 +81,85 @@ def run_rs(n, sm, cycles=10, theta=0.25, min_coarse=500, dim=2):
     mg.close()
 
 
-if len(sys.argv) > 1 and sys.argv[1] == "cheb":
+def block_memory(mg, kp, cheb):
+    """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
+    U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
+    levels whose single-vector layout is not CSR (bounded by the structural nnz)"""
+    L = mg.n_levels
+    panels = 0
+    csr = 0
+    for l in range(L):
+        n = mg.get_n_dofs(l)
+        coarsest = l == L - 1 and l > 0
+        panels += 8 * n * kp * (2 if coarsest else (5 if cheb else 4))
+        if not coarsest and mg.level_layout(l)[0] != amg.LAYOUT_CSR:
+            csr += 12 * amg.lib().amg_hip_get_level_nnz(mg._h, l) + 4 * (n + 1)
+    panels += 3 * 8 * mg.get_n_dofs(L - 1) * kp
+    return panels, csr
+
+
+def run_block(label, mk, cycles=10, reps=3, ks=(1, 2, 4, 8, 16)):
+    """ms per block cycle and right-hand-side cycles per second for k = 1..16, next to the single
+    path's rate measured in the same run, alternating with it; the block cycle's must-move bytes
+    per second as a fraction of 8 TB/s."""
+    import numpy as np
+    import torch
+    mg = mk()
+    mg.sync()
+    n0 = mg.get_n_dofs(0)
+    rng = np.random.default_rng(1)
+    cheb = "cheb" in label
+    print(f"{label}: {mg.n_levels} levels, {n0} dofs, coarse solve {mg.coarse_solve_kind().split(' ')[0]}",
+          flush=True)
+    for k in ks:
+        U = torch.from_numpy(rng.standard_normal((n0, k))).cuda()
+        F = torch.from_numpy(rng.standard_normal((n0, k))).cuda()
+        mg.block_vcycles(U, F, n=2)   # CSR copies, panels, captured graph
+        mg.vcycle(2)
+        torch.cuda.synchronize()
+        tb, ts = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            mg.block_vcycles(U, F, n=cycles)
+            torch.cuda.synchronize()
+            tb.append((time.perf_counter() - t0) / cycles)
+            t0 = time.perf_counter()
+            mg.vcycle(cycles)
+            mg.sync()
+            ts.append((time.perf_counter() - t0) / cycles)
+        b, sgl = min(tb), min(ts)
+        mm = mg.block_must_move(k)
+        kp = 1 << (k - 1).bit_length()
+        panels, csr = block_memory(mg, kp, cheb)
+        print(f"  k={k:2d}: {b*1e3:8.3f} ms/block cycle = {k/b:9.1f} RHS-cycles/s | single {sgl*1e3:8.3f} ms = "
+              f"{1/sgl:8.1f} cycles/s | block/single {(k/b)*sgl:5.2f}x | must-move {mm/1e6:9.1f} MB = "
+              f"{mm/b/8e12*100:5.1f} % of 8 TB/s | block memory {panels/2**30:.2f} GiB panels + "
+              f"{csr/2**30:.2f} GiB CSR copies", flush=True)
+        del U, F
+    mg.close()
+
+
+if len(sys.argv) > 1 and sys.argv[1].startswith("block"):
+    import torch  # noqa: F401  (before the library: torch needs its own HIP runtime, INTEGRATION.md section 2)
+if len(sys.argv) > 1 and sys.argv[1] == "block":
+    def rs(sm):
+        cp, ri, v = amg.laplacian(1024)
+        return lambda: amg.Multigrid.ruge_stueben(cp, ri, v, amg.rhs(1024), 25, 0.25, 500, **KW[sm])
+    run_block("RS 1024^2 jacobi 2+2", rs("jacobi"))
+    run_block("RS 1024^2 cheb(2) 1+1", rs("cheb"))
+    run_block("poisson(1024, 6) jacobi 2+2", lambda: amg.Multigrid.poisson(1024, 6, **KW["jacobi"]))
+    run_block("poisson(4096, 16) jacobi 2+2", lambda: amg.Multigrid.poisson(4096, 16, **KW["jacobi"]), cycles=4)
+    run_block("poisson(256, 17, dim=3) jacobi 2+2",
+              lambda: amg.Multigrid.poisson(256, 17, dim=3, **KW["jacobi"]), cycles=4)
+elif len(sys.argv) > 2 and sys.argv[1] == "block8":   # one workload at k = 8 (kernel traces): rs | p4096
+    if sys.argv[2] == "rs":
+        cp, ri, v = amg.laplacian(1024)
+        run_block("RS 1024^2 jacobi 2+2", lambda: amg.Multigrid.ruge_stueben(cp, ri, v, amg.rhs(1024), 25, 0.25, 500,
+                                                                          **KW["jacobi"]), reps=1, ks=(8,))
+    else:
+        run_block("poisson(4096, 16) jacobi 2+2", lambda: amg.Multigrid.poisson(4096, 16, **KW["jacobi"]), cycles=4,
+                  reps=1, ks=(8,))
+elif len(sys.argv) > 1 and sys.argv[1] == "cheb":
     run(2, 4096, 16, "cheb", 20)                       # the bench.py problem, Chebyshev(2) 1+1
     run(2, 4096, 16, "jacobi", 20)                     # ... next to true Jacobi 2+2
     run_rs(1024, "cheb")                               # RS 1024^2: rate, 1e-8, PCG to 1e-8
