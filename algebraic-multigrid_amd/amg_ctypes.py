@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libamg_hip.so")
 
 OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED, ECOMM = 0, 1, 2, 3, 4, 5
-SM_SPGS, SM_REF_JACOBI, SM_SOR, SM_JACOBI, SM_MULTICOLOR_GS, SM_CHEBYSHEV = 0, 1, 2, 3, 4, 5
+SM_SPGS, SM_REF_JACOBI, SM_SOR, SM_JACOBI, SM_MULTICOLOR_GS, SM_CHEBYSHEV, SM_LINE_JACOBI = 0, 1, 2, 3, 4, 5, 6
 LAYOUT_AUTO, LAYOUT_CSR, LAYOUT_SELL, LAYOUT_DICT = 0, 1, 2, 3
 
 _i32p = C.POINTER(C.c_int32)
@@ -161,6 +161,9 @@ _SIGS = {
     "amg_hip_get_colors": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i32p]),
     "amg_hip_level_op": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "amg_hip_cheb_bounds": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f64p]),
+    "amg_hip_line_stride": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    "amg_hip_smooth_line": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, C.c_int64, C.c_double, C.c_int64,
+                                      _f64p, _f64p]),
     "amg_hip_smooth_chebyshev": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int32,
                                            C.c_double, C.c_double, C.c_int64]),
     "amg_hip_cycle_bytes": (C.c_int, [C.c_void_p, _f64p, _f64p]),
@@ -683,6 +686,15 @@ class Multigrid:
         _chk(st)
         return lo.value, hi.value
 
+    def line_stride(self, level):
+        """The stride s of the line smoother's lines on `level` (amg_hip_line_stride)."""
+        s = C.c_int64(0)
+        st = lib().amg_hip_line_stride(self._h, int(level), C.byref(s))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return s.value
+
     def coarse_solve_kind(self):
         return {0: "band (one wave, sequential, bit-exact)", 1: "spike (partitioned, parallel)",
                 2: "band-wide (blocked sequential, any half-bandwidth, bit-exact)",
@@ -836,6 +848,19 @@ def smooth_chebyshev(colptr, rowind, val, u, b, degree=2, lower=0.3, upper=1.0, 
     u = np.array(u, dtype=np.float64, copy=True)
     st = lib().amg_hip_smooth_chebyshev(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), _p64(u),
                                         _p64(b), int(degree), float(lower), float(upper), int(n_iters))
+    if st == EINVAL:
+        raise ValueError(lib().amg_hip_last_error().decode())
+    _chk(st)
+    return u
+
+
+def smooth_line(colptr, rowind, val, u, f, stride=0, omega=0.7, iters=1):
+    """amg_hip_smooth_line: `iters` sweeps u <- u + omega T^-1 (f - A u) of the line smoother with the
+    lines at distance `stride` (0: the automatic rule); returns the new u."""
+    colptr, rowind, val, f = _a32(colptr), _a32(rowind), _a64(val), _a64(f)
+    u = np.array(u, dtype=np.float64, copy=True)
+    st = lib().amg_hip_smooth_line(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), int(stride),
+                                   float(omega), int(iters), _p64(u), _p64(f))
     if st == EINVAL:
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)

@@ -44,6 +44,9 @@
 #include <cstdio>
 #include <type_traits>
 #include <utility>
+#include <vector>
+#include <algorithm>
+#include <cmath>
 
 #include "kernels.hpp"
 
@@ -5314,6 +5317,444 @@ hipError_t launch_block_pcg_update_p(int kp, int64_t n, const double* num, const
   if (n <= 0) return hipSuccess;
   const int ks = __builtin_ctz((unsigned)kp);
   hipLaunchKernelGGL(block_pcg_p_kernel, block_grid(n * kp), dim3(256), 0, st, n, ks, num, den, act, p, z);
+  return hipGetLastError();
+}
+
+// ---- K-Line: line-relaxation smoother (kernels.hpp: LineRef) -----------------------------------
+// T = the entries of A at column offsets 0, +s, -s.  Row i sits on chain c = i % s at position
+// p = i / s.  Every chain is cut with period LINE_SEG: positions 32 g .. 32 g + 30 are the interior
+// rows of segment g, position 32 g + 31 is a separator.  With the separators removed the segments
+// are independent tridiagonal blocks B_g; the Schur complement S on the separators of one chain is
+// tridiagonal again.  Setup factors every B_g and S (Thomas, no pivoting) and stores
+// v = B_g^-1 (dl_first e_first), w = B_g^-1 (du_last e_last).  One solve is
+//   line_seg_kernel     y_g = B_g^-1 r_g                                  lane per (segment, chain)
+//   line_sep_*_kernel   S x_s = r_s - dl_s y_(s-1) - du_s y_(s+1)         lane or workgroup per chain
+//   line_update_kernel  x = y - v x_(sep before) - w x_(sep after); u += omega x   lane per row
+// so the dependent depth is 2 * 31 + 2 * (chain length / 32) steps instead of 2 * chain length.
+// Arrays (n doubles each), interior row | separator row:
+//   dl: a_(i,i-s) | a_(i,i-s)     ip: 1 / pivot of B_g | 1 / pivot of S     cp: upper / pivot, both
+//   v:  v | lower entry of S      w:  w | a_(i,i+s)
+namespace {
+constexpr int LINE_INT = LINE_SEG - 1;  // interior rows of a full segment
+
+__host__ __device__ inline bool line_bad_pivot(double p) { return !(p == p) || p == 0.0 || p - p != 0.0; }
+
+// rows of T from CSR(A): dl -> L.dl, diagonal -> L.ip, du -> L.w
+__host__ __device__ inline void line_extract_row(int64_t i, int64_t n, int64_t s, const int32_t* rowptr,
+                                                 const int32_t* col, const double* val, double* dl, double* dd,
+                                                 double* du) {
+  double a = 0.0, b = 0.0, c = 0.0;
+  for (int32_t p = rowptr[i]; p < rowptr[i + 1]; ++p) {
+    const int64_t j = col[p];
+    if (j == i) b = val[p];
+    else if (j == i - s) a = val[p];
+    else if (j == i + s) c = val[p];
+  }
+  dl[i] = a;
+  dd[i] = b;
+  du[i] = c;
+}
+// factor B_g of chain c in place; returns the first row with a bad pivot, or -1
+__host__ __device__ inline int64_t line_factor_segment(const LineRef& L, int64_t g, int64_t c) {
+  const int64_t n = L.n, s = L.s;
+  const int64_t i0 = (g * LINE_SEG) * s + c;
+  int64_t bad = -1;
+  double cprev = 0.0, vprev = 0.0, wl = 0.0;
+  int len = 0;
+  for (int k = 0; k < LINE_INT; ++k) {
+    const int64_t i = i0 + (int64_t)k * s;
+    if (i >= n) break;
+    const bool last = k == LINE_INT - 1 || i + s >= n;
+    const double dl = L.dl[i], dd = L.ip[i], du = L.w[i];
+    const double piv = k > 0 ? dd - dl * cprev : dd;
+    if (bad < 0 && line_bad_pivot(piv)) bad = i;
+    const double ip = 1.0 / piv;
+    cprev = last ? 0.0 : du * ip;
+    vprev = k > 0 ? (0.0 - dl * vprev) * ip : dl * ip;
+    if (last) wl = du * ip;
+    L.ip[i] = ip;
+    L.cp[i] = cprev;
+    L.v[i] = vprev;
+    len = k + 1;
+  }
+  double vn = 0.0, wn = 0.0;
+  for (int k = len - 1; k >= 0; --k) {
+    const int64_t i = i0 + (int64_t)k * s;
+    const double cp = L.cp[i];
+    vn = L.v[i] - cp * vn;
+    wn = k == len - 1 ? wl : 0.0 - cp * wn;
+    L.v[i] = vn;
+    L.w[i] = wn;
+  }
+  return bad;
+}
+// Schur complement on the separators of chain c and its factors; after line_factor_segment of all
+__host__ __device__ inline int64_t line_factor_chain(const LineRef& L, int64_t c) {
+  const int64_t n = L.n, s = L.s;
+  int64_t bad = -1;
+  double cprev = 0.0;
+  for (int64_t g = 0;; ++g) {
+    const int64_t i = (g * LINE_SEG + LINE_INT) * s + c;
+    if (i >= n) break;
+    const bool next = i + s < n;
+    const double dl = L.dl[i], dd = L.ip[i], du = next ? L.w[i] : 0.0;
+    const double vl = L.v[i - s], wl = L.w[i - s];
+    const double vf = next ? L.v[i + s] : 0.0, wf = next ? L.w[i + s] : 0.0;
+    const double lo = 0.0 - dl * vl;
+    const double dg = (dd - dl * wl) - du * vf;
+    const double up = 0.0 - du * wf;
+    const double piv = g > 0 ? dg - lo * cprev : dg;
+    if (bad < 0 && line_bad_pivot(piv)) bad = i;
+    const double ip = 1.0 / piv;
+    cprev = up * ip;
+    L.v[i] = lo;
+    L.ip[i] = ip;
+    L.cp[i] = cprev;
+  }
+  return bad;
+}
+__host__ __device__ inline int64_t line_chains(int64_t n, int64_t s) { return s < n ? s : n; }
+__host__ __device__ inline int64_t line_segments(int64_t n, int64_t s) {  // of the longest chain (chain 0)
+  const int64_t m = (n + s - 1) / s;
+  return (m + LINE_SEG - 1) / LINE_SEG;
+}
+
+__global__ __launch_bounds__(256) void line_extract_kernel(LineRef L, const int32_t* __restrict__ rowptr,
+                                                           const int32_t* __restrict__ col,
+                                                           const double* __restrict__ val) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < L.n) line_extract_row(i, L.n, L.s, rowptr, col, val, L.dl, L.ip, L.w);
+}
+__global__ __launch_bounds__(256) void line_factor_seg_kernel(LineRef L, int64_t nch, int64_t nseg,
+                                                              unsigned long long* bad) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nch * nseg) return;
+  const int64_t b = line_factor_segment(L, t / nch, t % nch);
+  if (b >= 0) atomicMin(bad, (unsigned long long)b);
+}
+__global__ __launch_bounds__(256) void line_factor_chain_kernel(LineRef L, int64_t nch, unsigned long long* bad) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nch) return;
+  const int64_t b = line_factor_chain(L, c);
+  if (b >= 0) atomicMin(bad, (unsigned long long)b);
+}
+
+// y_g = B_g^-1 r_g: the forward values stay in registers (the loops are fully unrolled), so the
+// dependent chain is arithmetic only and the loads of r and of the factors run ahead of it
+__global__ __launch_bounds__(256) void line_seg_kernel(int64_t n, int64_t s, int64_t nch, int64_t nseg,
+                                                       const double* __restrict__ r,
+                                                       const double* __restrict__ dl,
+                                                       const double* __restrict__ ip,
+                                                       const double* __restrict__ cp, double* __restrict__ y) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nch * nseg) return;
+  const int64_t g = t / nch, c = t - g * nch;
+  const int64_t i0 = (g * LINE_SEG) * s + c;
+  double yv[LINE_INT];
+  double prev = 0.0;
+#pragma unroll
+  for (int k = 0; k < LINE_INT; ++k) {
+    const int64_t i = i0 + (int64_t)k * s;
+    if (i < n) prev = k > 0 ? (r[i] - dl[i] * prev) * ip[i] : r[i] * ip[i];
+    else prev = 0.0;
+    yv[k] = prev;
+  }
+  double nxt = 0.0;
+#pragma unroll
+  for (int k = LINE_INT - 1; k >= 0; --k) {
+    const int64_t i = i0 + (int64_t)k * s;
+    if (i < n) {
+      nxt = yv[k] - cp[i] * nxt;
+      y[i] = nxt;
+    }
+  }
+}
+
+// right-hand side of the reduced system at separator row i
+__device__ inline double line_sep_rhs(int64_t i, int64_t n, int64_t s, const double* r, const double* dl,
+                                      const double* w, const double* y) {
+  double b = r[i] - dl[i] * y[i - s];
+  if (i + s < n) b = b - w[i] * y[i + s];
+  return b;
+}
+// many chains: one lane per chain, neighbouring lanes neighbouring addresses.  Each batch of
+// LINE_BATCH separators is loaded before its dependent steps run, so a chain of m / 32 separators
+// costs m / (32 LINE_BATCH) memory latencies per direction.
+constexpr int LINE_BATCH = 8;
+__global__ __launch_bounds__(64) void line_sep_many_kernel(int64_t n, int64_t s, int64_t nch, const double* r,
+                                                           const double* dl, const double* ip, const double* cp,
+                                                           const double* v, const double* w, double* y) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nch) return;
+  const int64_t step = (int64_t)LINE_SEG * s;
+  const int64_t first = (int64_t)LINE_INT * s + c;
+  if (first >= n) return;
+  const int64_t nsep = (n - 1 - first) / step + 1;
+  double t = 0.0;
+  for (int64_t g0 = 0; g0 < nsep; g0 += LINE_BATCH) {
+    double b[LINE_BATCH], lo[LINE_BATCH], pv[LINE_BATCH];
+#pragma unroll
+    for (int j = 0; j < LINE_BATCH; ++j) {
+      const int64_t i = first + (g0 + j) * step;
+      const bool on = g0 + j < nsep;
+      b[j] = on ? line_sep_rhs(i, n, s, r, dl, w, y) : 0.0;
+      lo[j] = on ? v[i] : 0.0;
+      pv[j] = on ? ip[i] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < LINE_BATCH; ++j) {
+      if (g0 + j < nsep) {
+        t = (b[j] - lo[j] * t) * pv[j];
+        y[first + (g0 + j) * step] = t;
+      }
+    }
+  }
+  double x = 0.0;
+  for (int64_t g1 = nsep; g1 > 0; g1 -= LINE_BATCH) {  // separators g1-1, g1-2, ...
+    double tt[LINE_BATCH], cc[LINE_BATCH];
+#pragma unroll
+    for (int j = 0; j < LINE_BATCH; ++j) {
+      const int64_t g = g1 - 1 - j;
+      const int64_t i = first + g * step;
+      tt[j] = g >= 0 ? y[i] : 0.0;
+      cc[j] = g >= 0 ? cp[i] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < LINE_BATCH; ++j) {
+      const int64_t g = g1 - 1 - j;
+      if (g >= 0) {
+        x = tt[j] - cc[j] * x;
+        y[first + g * step] = x;
+      }
+    }
+  }
+}
+// few long chains: one workgroup per chain.  All lanes stage a chunk of the reduced system in LDS,
+// lane 0 walks it there (an LDS round trip per step instead of a memory one) and carries the
+// recurrence into the next chunk, all lanes write the chunk back.  Same arithmetic in the same
+// order as line_sep_many_kernel.
+constexpr int LINE_FEW_CHUNK = 1024;  // 3 arrays of doubles: 24 KB of LDS
+__global__ __launch_bounds__(256) void line_sep_few_kernel(int64_t n, int64_t s, const double* r, const double* dl,
+                                                           const double* ip, const double* cp, const double* v,
+                                                           const double* w, double* y) {
+  __shared__ double b[LINE_FEW_CHUNK], lo[LINE_FEW_CHUNK], pv[LINE_FEW_CHUNK];
+  __shared__ double carry;
+  const int64_t c = blockIdx.x;
+  const int64_t step = (int64_t)LINE_SEG * s;
+  const int64_t first = (int64_t)LINE_INT * s + c;
+  if (first >= n) return;  // the whole workgroup
+  const int64_t nsep = (n - 1 - first) / step + 1;
+  if (threadIdx.x == 0) carry = 0.0;
+  __syncthreads();
+  for (int64_t g0 = 0; g0 < nsep; g0 += LINE_FEW_CHUNK) {
+    const int m = (int)(nsep - g0 < LINE_FEW_CHUNK ? nsep - g0 : LINE_FEW_CHUNK);
+    for (int g = threadIdx.x; g < m; g += blockDim.x) {
+      const int64_t i = first + (g0 + g) * step;
+      b[g] = line_sep_rhs(i, n, s, r, dl, w, y);
+      lo[g] = v[i];
+      pv[g] = ip[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double t = carry;
+      for (int g = 0; g < m; ++g) {
+        t = (b[g] - lo[g] * t) * pv[g];
+        b[g] = t;
+      }
+      carry = t;
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < m; g += blockDim.x) y[first + (g0 + g) * step] = b[g];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) carry = 0.0;
+  __syncthreads();
+  for (int64_t g1 = nsep; g1 > 0; g1 -= LINE_FEW_CHUNK) {  // separators [g1 - m, g1)
+    const int m = (int)(g1 < LINE_FEW_CHUNK ? g1 : LINE_FEW_CHUNK);
+    const int64_t gb = g1 - m;
+    for (int g = threadIdx.x; g < m; g += blockDim.x) {
+      const int64_t i = first + (gb + g) * step;
+      b[g] = y[i];
+      lo[g] = cp[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double x = carry;
+      for (int g = m - 1; g >= 0; --g) {
+        x = b[g] - lo[g] * x;
+        b[g] = x;
+      }
+      carry = x;
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < m; g += blockDim.x) y[first + (gb + g) * step] = b[g];
+    __syncthreads();
+  }
+}
+
+// x_i = y_i - v_i x_(separator before) - w_i x_(separator after); u_i += omega x_i
+__global__ __launch_bounds__(256) void line_update_kernel(int64_t n, uint32_t s, const double* __restrict__ y,
+                                                          const double* __restrict__ v,
+                                                          const double* __restrict__ w, double omega,
+                                                          double* __restrict__ u) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = (uint32_t)i / s;
+  const uint32_t k = p % LINE_SEG;
+  double x = y[i];
+  if (k != LINE_INT) {
+    const int64_t before = i - ((int64_t)k + 1) * s;
+    const int64_t after = i + (int64_t)(LINE_INT - k) * s;
+    if (before >= 0) x = x - v[i] * y[before];
+    if (after < n) x = x - w[i] * y[after];
+  }
+  u[i] = u[i] + omega * x;
+}
+
+// ---- stride rule: w(d) = sum of |a_ij| over |j - i| = d >= 1 -----------------------------------
+// Level matrices have a handful of distinct distances, so every workgroup first sums into a small
+// LDS table keyed by distance and flushes one atomic per used slot; a full table falls through to
+// the global atomic.
+constexpr int LINE_DSLOTS = 32;
+__global__ __launch_bounds__(256) void line_dist_kernel(int64_t n, const int32_t* __restrict__ rowptr,
+                                                        const int32_t* __restrict__ col,
+                                                        const double* __restrict__ val, double* wd) {
+  __shared__ int key[LINE_DSLOTS];
+  __shared__ double sum[LINE_DSLOTS];
+  if (threadIdx.x < LINE_DSLOTS) {
+    key[threadIdx.x] = 0;
+    sum[threadIdx.x] = 0.0;
+  }
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    for (int32_t p = rowptr[i]; p < rowptr[i + 1]; ++p) {
+      const int64_t dj = (int64_t)col[p] - i;
+      const int d = (int)(dj < 0 ? -dj : dj);
+      if (d == 0) continue;
+      const double a = fabs(val[p]);
+      int slot = d % LINE_DSLOTS;
+      bool done = false;
+      for (int probe = 0; probe < LINE_DSLOTS && !done; ++probe) {
+        const int old = atomicCAS(&key[slot], 0, d);
+        if (old == 0 || old == d) {
+          atomicAdd(&sum[slot], a);
+          done = true;
+        }
+        slot = (slot + 1) % LINE_DSLOTS;
+      }
+      if (!done) atomicAdd(&wd[d], a);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < LINE_DSLOTS && key[threadIdx.x] != 0) atomicAdd(&wd[key[threadIdx.x]], sum[threadIdx.x]);
+}
+// out[0] = bits of max_d w(d) (non-negative doubles order like their bit patterns)
+__global__ __launch_bounds__(256) void line_wmax_kernel(int64_t n, const double* __restrict__ wd,
+                                                        unsigned long long* out) {
+  const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
+  if (d < n && wd[d] > 0.0) atomicMax(&out[0], (unsigned long long)__double_as_longlong(wd[d]));
+}
+// out[1] = the largest d with w(d) >= (1 - 1e-9) max w
+__global__ __launch_bounds__(256) void line_pick_kernel(int64_t n, const double* __restrict__ wd,
+                                                        unsigned long long* out) {
+  const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
+  if (d >= n) return;
+  const double mx = __longlong_as_double((long long)out[0]);
+  if (mx > 0.0 && wd[d] >= (1.0 - 1e-9) * mx) atomicMax(&out[1], (unsigned long long)d);
+}
+__global__ void line_init2_kernel(unsigned long long* out, unsigned long long a, unsigned long long b) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    out[0] = a;
+    out[1] = b;
+  }
+}
+inline dim3 line_grid(int64_t threads, int block = 256) { return dim3((unsigned)((threads + block - 1) / block)); }
+}  // namespace
+
+hipError_t launch_line_stride(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val, double* wd,
+                              uint64_t* out, hipStream_t st) {
+  auto* o = reinterpret_cast<unsigned long long*>(out);
+  hipLaunchKernelGGL(line_init2_kernel, dim3(1), dim3(64), 0, st, o, 0ull, 1ull);
+  hipError_t e = hipMemsetAsync(wd, 0, sizeof(double) * (size_t)n, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(line_dist_kernel, line_grid(n), dim3(256), 0, st, n, rowptr, col, val, wd);
+  if (n > 1) {
+    hipLaunchKernelGGL(line_wmax_kernel, line_grid(n - 1), dim3(256), 0, st, n, wd, o);
+    hipLaunchKernelGGL(line_pick_kernel, line_grid(n - 1), dim3(256), 0, st, n, wd, o);
+  }
+  return hipGetLastError();
+}
+int64_t line_stride_host(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val) {
+  std::vector<double> wd((size_t)n, 0.0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int32_t p = rowptr[i]; p < rowptr[i + 1]; ++p) {
+      const int64_t d = col[p] < i ? i - col[p] : col[p] - i;
+      if (d > 0) wd[(size_t)d] += std::fabs(val[p]);
+    }
+  double mx = 0.0;
+  for (int64_t d = 1; d < n; ++d) mx = std::max(mx, wd[(size_t)d]);
+  int64_t s = 1;
+  if (mx > 0.0)
+    for (int64_t d = 1; d < n; ++d)
+      if (wd[(size_t)d] >= (1.0 - 1e-9) * mx) s = d;
+  return s;
+}
+
+hipError_t launch_line_setup(const LineRef& L, const int32_t* rowptr, const int32_t* col, const double* val,
+                             uint64_t* bad, hipStream_t st) {
+  // s <= n < 2^31 bounds every index product of the kernels (at most 64 s + n) well inside int64
+  if (L.n <= 0 || L.s < 1 || L.s > L.n || L.n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+  auto* o = reinterpret_cast<unsigned long long*>(bad);
+  const int64_t nch = line_chains(L.n, L.s), nseg = line_segments(L.n, L.s);
+  hipLaunchKernelGGL(line_init2_kernel, dim3(1), dim3(64), 0, st, o, ~0ull, 0ull);
+  hipLaunchKernelGGL(line_extract_kernel, line_grid(L.n), dim3(256), 0, st, L, rowptr, col, val);
+  hipLaunchKernelGGL(line_factor_seg_kernel, line_grid(nch * nseg), dim3(256), 0, st, L, nch, nseg, o);
+  hipLaunchKernelGGL(line_factor_chain_kernel, line_grid(nch), dim3(256), 0, st, L, nch, o);
+  return hipGetLastError();
+}
+int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32_t* col, const double* val) {
+  std::vector<double> a[5];
+  for (auto& x : a) x.assign((size_t)n, 0.0);
+  LineRef L;
+  L.n = n;
+  L.s = s < n ? s : n;  // every stride >= n: each row its own chain
+  L.dl = a[0].data();
+  L.ip = a[1].data();
+  L.cp = a[2].data();
+  L.v = a[3].data();
+  L.w = a[4].data();
+  for (int64_t i = 0; i < n; ++i) line_extract_row(i, n, s, rowptr, col, val, L.dl, L.ip, L.w);
+  const int64_t nch = line_chains(n, L.s), nseg = line_segments(n, L.s);
+  int64_t bad = -1;
+  auto note = [&](int64_t b) {
+    if (b >= 0 && (bad < 0 || b < bad)) bad = b;
+  };
+  for (int64_t g = 0; g < nseg; ++g)
+    for (int64_t c = 0; c < nch; ++c) note(line_factor_segment(L, g, c));
+  for (int64_t c = 0; c < nch; ++c) note(line_factor_chain(L, c));
+  return bad;
+}
+
+bool line_few_chains(int64_t s) { return s < 64; }
+hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
+                             hipStream_t st) {
+  if (L.n <= 0 || L.s < 1 || L.s > L.n || L.n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+  const int64_t n = L.n, s = L.s;
+  const int64_t nch = line_chains(n, s), nseg = line_segments(n, s);
+  hipLaunchKernelGGL(line_seg_kernel, line_grid(nch * nseg), dim3(256), 0, st, n, s, nch, nseg, r, L.dl, L.ip, L.cp,
+                     y);
+  if ((int64_t)LINE_INT * s < n) {  // the level has separators
+    if (line_few_chains(s)) {
+      hipLaunchKernelGGL(line_sep_few_kernel, dim3((unsigned)nch), dim3(256), 0, st, n, s, r, L.dl, L.ip, L.cp, L.v,
+                         L.w, y);
+    } else {
+      hipLaunchKernelGGL(line_sep_many_kernel, line_grid(nch, 64), dim3(64), 0, st, n, s, nch, r, L.dl, L.ip, L.cp,
+                         L.v, L.w, y);
+    }
+  }
+  hipLaunchKernelGGL(line_update_kernel, line_grid(n), dim3(256), 0, st, n, (uint32_t)s, y,
+                     L.v, L.w, omega, u);
   return hipGetLastError();
 }
 

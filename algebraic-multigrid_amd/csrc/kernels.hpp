@@ -50,6 +50,34 @@ hipError_t launch_sell_cheb(int64_t n, int idx16, const int64_t* soff, const voi
 // zero or absent.  out: 2 words, set by the launcher (stream-ordered) to {0, ~0}.
 hipError_t launch_gershgorin(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
                              uint64_t* out, hipStream_t st);
+// K-Line, the line-relaxation smoother (AMG_HIP_SM_LINE_JACOBI): T = the entries of A at column
+// offsets 0, +s, -s, a tridiagonal matrix on each of the min(s, n) chains of rows c, c + s, ...
+// Every chain is cut with period LINE_SEG (31 interior rows, one separator); the arrays hold the
+// factors of the interior blocks, of the separators' Schur complement, and the two spike vectors
+// (kernels.hip: K-Line).  n doubles each, 1 <= s <= n < 2^31 (the launchers refuse anything else; s = n
+// stands for every stride >= n: each row its own chain).
+constexpr int LINE_SEG = 32;
+struct LineRef {
+  int64_t n = 0, s = 1;
+  double *dl = nullptr, *ip = nullptr, *cp = nullptr, *v = nullptr, *w = nullptr;
+};
+// stride rule on a device CSR matrix: out[1] = the largest distance d = |j - i| >= 1 whose weight
+// w(d) = sum |a_ij| reaches (1 - 1e-9) max w, or 1 without off-diagonal entries; out[0] = bits of
+// max w.  wd: n doubles of scratch.  line_stride_host: the same rule on host arrays.
+hipError_t launch_line_stride(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val, double* wd,
+                              uint64_t* out, hipStream_t st);
+int64_t line_stride_host(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val);
+// extract T from CSR(A) and factor it into L's arrays; bad[0] = smallest row whose pivot is zero or
+// not finite, else ~0 (bad: 2 words).  line_setup_host: the same elimination on the host, factors
+// discarded; returns that row or -1.
+hipError_t launch_line_setup(const LineRef& L, const int32_t* rowptr, const int32_t* col, const double* val,
+                             uint64_t* bad, hipStream_t st);
+int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32_t* col, const double* val);
+// u += omega T^-1 r.  y: n doubles of scratch, r is not written.  Three launches (two on a level
+// without separators): line_seg_kernel, line_sep_few_kernel or line_sep_many_kernel, line_update_kernel.
+hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
+                             hipStream_t st);
+bool line_few_chains(int64_t s);  // the reduced systems run as one workgroup per chain
 // Same operations on a SELL-64 matrix (64-row panels, lane-interleaved):
 // soff[n/64 + 1] panel offsets, scol/sval padded with col = -1.
 // idx16 bit 0: scol holds int16 offsets from the diagonal column (pad -32768);

@@ -769,6 +769,76 @@ void cheb_coefs(double lo, double hi, int k, std::vector<double>* alpha, std::ve
   }
 }
 
+// ---- line smoother (AMG_HIP_SM_LINE_JACOBI; kernels.hip: K-Line) ----
+std::string line_options_error(double omega) {
+  if (!(omega > 0.0 && omega < 2.0))
+    return "line smoother: `omega` must lie in (0, 2), got " + std::to_string(omega);
+  return "";
+}
+std::string line_bad_pivot(int l, int64_t row) {
+  return "line smoother: level " + std::to_string(l) + " row " + std::to_string(row) +
+         " has a zero or non-finite pivot in the elimination of its line (the smoother needs a diagonally "
+         "dominant operator)";
+}
+struct LineOnDev {  // factors of T (n doubles each) and the scratch vector y
+  int64_t n = 0, s = 0;
+  DevMem dl, ip, cp, v, w, y;
+  LineRef ref() const {
+    LineRef R;
+    R.n = n;
+    R.s = s;
+    R.dl = dl.as<double>();
+    R.ip = ip.as<double>();
+    R.cp = cp.as<double>();
+    R.v = v.as<double>();
+    R.w = w.as<double>();
+    return R;
+  }
+  // rows on a separator position (p % LINE_SEG == LINE_SEG - 1 on their chain)
+  int64_t separators() const {
+    int64_t k = 0;
+    if (s < 1 || s > n) return 0;  // line_setup_dev clamps the stride to n
+    for (int64_t p = LINE_SEG - 1; p * s < n; p += LINE_SEG) k += std::min<int64_t>(s, n - p * s);
+    return k;
+  }
+  // bytes one u += omega T^-1 r has to move: interior rows r, dl, ip, cp in and y out, then y, v, w, u
+  // in and u out (80 B); separator rows r, dl, w, v, ip, cp, both neighbours' y in and y out, then
+  // y, u in and u out (96 B)
+  double solve_bytes() const {
+    const int64_t sep = separators();
+    return 80.0 * (double)(n - sep) + 96.0 * (double)sep;
+  }
+};
+// stride (0: the automatic rule, on the device) and factors of one level from its device CSR rows
+amg_hip_status line_setup_dev(int l, int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
+                              int64_t stride, LineOnDev* out) {
+  LineOnDev& D = *out;
+  D.n = n;
+  for (DevMem* m : {&D.dl, &D.ip, &D.cp, &D.v, &D.w, &D.y}) HIP_TRY(m->alloc(sizeof(double) * (size_t)n));
+  DevMem flag;
+  HIP_TRY(flag.alloc(sizeof(uint64_t) * 2));
+  uint64_t h[2];
+  if (stride < 1) {
+    HIP_TRY(launch_line_stride(n, rowptr, col, val, D.y.as<double>(), flag.as<uint64_t>(), nullptr));
+    HIP_TRY(hipMemcpy(h, flag.p, sizeof(h), hipMemcpyDeviceToHost));
+    stride = (int64_t)h[1];
+  }
+  // s >= n: every row is its own chain, whatever s is; n stands for all of them, so that the index
+  // arithmetic of the kernels (positions times s) stays far from overflow
+  D.s = std::min<int64_t>(stride, n);
+  HIP_TRY(launch_line_setup(D.ref(), rowptr, col, val, flag.as<uint64_t>(), nullptr));
+  HIP_TRY(hipMemcpy(h, flag.p, sizeof(h), hipMemcpyDeviceToHost));
+  if (h[0] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, (int64_t)h[0]));
+  return AMG_HIP_OK;
+}
+// n_iters sweeps u <- u + omega T^-1 (f - A u); r: n doubles of scratch for the residual
+hipError_t launch_line_sweep(const DevMat& A, const LineOnDev& D, double* u, const double* f, double* r,
+                             double omega, hipStream_t st) {
+  hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
+  if (e != hipSuccess) return e;
+  return launch_line_solve(D.ref(), r, D.y.as<double>(), u, omega, st);
+}
+
 struct SpikeOnDev {  // device copy of a SpikeFactor + scratch
   SpikeArgs a{};
   DevMem sf, sb, d, V, W, Vt, Wh, G, Z, T, H;
@@ -965,6 +1035,7 @@ struct Level {
   DevMem diag;             // a_ii (true-Jacobi smoother only)
   double cheb_lo = 0.0, cheb_hi = 0.0;  // Chebyshev smoother: interval of D^-1 A's spectrum
   DevMem cheb_d;           //   and its update vector d (r stays the residual: keep_residual)
+  LineOnDev line;          // line smoother: stride, factors of T and scratch (host_only: stride only)
   // transfers to level+1 (absent on the coarsest level)
   // host copies; for the built-in LinearInterpolator they are only materialised when a
   // getter, the CSR transfer kernels or the host Galerkin product ask for them
@@ -1451,6 +1522,17 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
       if (passes & 1) {  // result sits in tmp: bring it home (keeps the graph static)
         HIP_TRY(hipMemcpyAsync(L.u.p, L.tmp.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, st));
         s->acct(16.0 * L.n);
+      }
+      return AMG_HIP_OK;
+    }
+    case AMG_HIP_SM_LINE_JACOBI: {
+      // residual of the old u into tmp, then K-Line adds omega T^-1 tmp to u in place (phases 1 / 2
+      // have no shortcut: u is read as it is); plain launches, r stays the cycle's residual
+      const DevMat& A = L.A_rows;
+      for (int it = 0; it < iters; ++it) {
+        HIP_TRY(launch_line_sweep(A, L.line, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
+                                  s->opt.omega, st));
+        s->acct(mat_bytes(A) + 24.0 * L.n + L.line.solve_bytes());  // matrix, f, u, r; K-Line
       }
       return AMG_HIP_OK;
     }
@@ -1965,10 +2047,12 @@ void compute_bytes(amg_hip_solver* s) {
     const Level& L = s->lv[l];
     const double sweep = 12.0 * (double)L.nnz_struct + 28.0 * (double)L.n;
     if (l == 0) s->fine_sweep_bytes = sweep;
+    // line smoother: every sweep is a residual plus the K-Line solve (80 B per row)
+    const double extra = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI ? 80.0 * (double)L.n * sweeps_per_smooth : 0.0;
     // pre-smooth + residual on every level; post-smooth on all but the coarsest
-    total += sweep * (sweeps_per_smooth + 1);
+    total += sweep * (sweeps_per_smooth + 1) + extra;
     if (l + 1 != nl) {
-      total += sweep * sweeps_per_smooth;
+      total += sweep * sweeps_per_smooth + extra;
       const double nH = (double)s->lv[l + 1].n, nh = (double)L.n;
       total += 8.0 * nH;                                   // zero
       total += 12.0 * 3 * nH + 4 * nH + 8 * nh + 8 * nH;   // restrict (CSR R)
@@ -1997,7 +2081,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
   if (opts) s->opt = *opts;
   else amg_hip_default_options(&s->opt);
-  if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_CHEBYSHEV)
+  if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_LINE_JACOBI)
     return fail(AMG_HIP_EINVAL, "unknown smoother kind");
   if (s->opt.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
   const bool cheb = s->opt.smoother == AMG_HIP_SM_CHEBYSHEV;
@@ -2005,6 +2089,12 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     const std::string e = cheb_options_error(s->opt.cheb_degree, s->opt.cheb_lower, s->opt.cheb_upper);
     if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
     if (s->opt.window) return fail(AMG_HIP_EUNSUPPORTED, "the Chebyshev smoother is not available in a window solver");
+  }
+  const bool line = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI;
+  if (line) {
+    const std::string e = line_options_error(s->opt.omega);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+    if (s->opt.window) return fail(AMG_HIP_EUNSUPPORTED, "the line smoother is not available in a window solver");
   }
   if (s->opt.layout < AMG_HIP_LAYOUT_AUTO || s->opt.layout > AMG_HIP_LAYOUT_DICT)
     return fail(AMG_HIP_EINVAL, "unknown matrix layout");
@@ -2079,6 +2169,20 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       L.cheb_lo = s->opt.cheb_lower * G;
       L.cheb_hi = s->opt.cheb_upper * G;
     }
+    if (line && !dev) {  // host_only: the stride and the pivot check on the host
+      if (L.n >= ((int64_t)1 << 31)) return fail(AMG_HIP_EUNSUPPORTED, "line smoother: levels of 2^31 rows or more");
+      L.line.n = L.n;
+      L.line.s = line_stride_host(L.n, A_r.ptr.data(), A_r.idx.data(), A_r.val.data());
+      const int64_t bad = line_setup_host(L.n, L.line.s, A_r.ptr.data(), A_r.idx.data(), A_r.val.data());
+      if (bad >= 0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, bad));
+    }
+    if (line && dev) {  // the same device setup as amg_hip_create_poisson, from a CSR copy of the rows
+      if (L.n >= ((int64_t)1 << 31)) return fail(AMG_HIP_EUNSUPPORTED, "line smoother: levels of 2^31 rows or more");
+      DevCsr rows;
+      HIP_TRY(upload_csr(A_r, &rows));
+      const amg_hip_status lr = line_setup_dev(l, L.n, rows.rowptr(), rows.col(), rows.v(), 0, &L.line);
+      if (lr != AMG_HIP_OK) return lr;
+    }
     if (dev) {
     const bool prune = !s->opt.keep_structural_zeros;
     // Symmetric levels headed for the dictionary layout are encoded ON THE DEVICE from CSR(A_l)
@@ -2105,7 +2209,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     }
     if (!encoded) {
       HIP_TRY(upload_mat_pruned(A_r, s->opt.layout, prune, &L.A_rows));
-      if (!L.symmetric && s->opt.smoother >= AMG_HIP_SM_JACOBI && !cheb)  // Chebyshev: rows of A
+      if (!L.symmetric && s->opt.smoother >= AMG_HIP_SM_JACOBI && !cheb && !line)  // Chebyshev, line: rows of A
         HIP_TRY(upload_mat_pruned(L.A_csc, s->opt.layout, prune, &L.A_cols_own));
     }
     if (s->opt.smoother == AMG_HIP_SM_JACOBI && !L.diag.p) {  // diagonal of the column-as-row walk
@@ -2498,13 +2602,19 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       n_levels < 2 || N >= ((int64_t)1 << 28))
     return AMG_HIP_OK;
   if (o.smoother_iters < 0 || (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0)) ||
-      o.smoother < 0 || o.smoother > AMG_HIP_SM_CHEBYSHEV)
+      o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_JACOBI)
     return AMG_HIP_OK;  // the host path words the argument error
   const bool cheb = o.smoother == AMG_HIP_SM_CHEBYSHEV;
   if (cheb) {
     const std::string e = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
     if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
     if (o.window) return fail(AMG_HIP_EUNSUPPORTED, "the Chebyshev smoother is not available in a window solver");
+  }
+  const bool line = o.smoother == AMG_HIP_SM_LINE_JACOBI;
+  if (line) {
+    const std::string e = line_options_error(o.omega);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+    if (o.window) return fail(AMG_HIP_EUNSUPPORTED, "the line smoother is not available in a window solver");
   }
   std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
   s->opt = o;
@@ -2581,6 +2691,10 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       std::memcpy(&G, &g[0], sizeof(G));
       L.cheb_lo = o.cheb_lower * G;
       L.cheb_hi = o.cheb_upper * G;
+    }
+    if (line) {  // stride rule and factors of T on the device CSR (K-Line setup)
+      const amg_hip_status lr = line_setup_dev(l, L.n, cur.rowptr(), cur.col(), cur.v(), 0, &L.line);
+      if (lr != AMG_HIP_OK) return lr;
     }
     HIP_TRY(L.diag.alloc(sizeof(double) * L.n));
     HIP_TRY(hipMemset(stats.p, 0, sizeof(int32_t) * 2));
@@ -2741,6 +2855,7 @@ const char* block_smoother_name(int32_t sm) {
     case AMG_HIP_SM_REF_JACOBI: return "AMG::Jacobi (AMG_HIP_SM_REF_JACOBI)";
     case AMG_HIP_SM_SOR: return "SOR (AMG_HIP_SM_SOR)";
     case AMG_HIP_SM_MULTICOLOR_GS: return "multicolour Gauss-Seidel (AMG_HIP_SM_MULTICOLOR_GS)";
+    case AMG_HIP_SM_LINE_JACOBI: return "line Jacobi (AMG_HIP_SM_LINE_JACOBI)";
   }
   return "unknown";
 }
@@ -3128,6 +3243,8 @@ amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t uni
   else amg_hip_default_options(&o);
   if (o.smoother == AMG_HIP_SM_CHEBYSHEV)
     return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_window: the Chebyshev smoother is not sharded");
+  if (o.smoother == AMG_HIP_SM_LINE_JACOBI)
+    return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_window: the line smoother is not sharded");
   o.window = 1;
   bool unsupported = true;
   amg_hip_status r = build_poisson_device(dim, n, n_levels, &o, out, &unsupported, unit_begin, unit_end);
@@ -3233,6 +3350,8 @@ amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world
   if (s->opt.window) return fail(AMG_HIP_EINVAL, "amg_hip_slab_setup: a window solver is cut already (amg_hip_window_setup)");
   if (s->opt.smoother == AMG_HIP_SM_CHEBYSHEV)
     return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_slab_setup: the Chebyshev smoother is not sharded");
+  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI)
+    return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_slab_setup: the line smoother is not sharded");
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
   int k = 0;
@@ -3470,6 +3589,15 @@ amg_hip_status amg_hip_cheb_bounds(const amg_hip_solver* s, int32_t level, doubl
   if (level < 0 || level >= (int)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
   *lo = s->lv[level].cheb_lo;
   *hi = s->lv[level].cheb_hi;
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_line_stride(const amg_hip_solver* s, int32_t level, int64_t* stride) {
+  if (!s || !stride) return fail(AMG_HIP_EINVAL, "null argument");
+  if (s->opt.smoother != AMG_HIP_SM_LINE_JACOBI)
+    return fail(AMG_HIP_EINVAL, "amg_hip_line_stride: the solver's smoother is not AMG_HIP_SM_LINE_JACOBI");
+  if (level < 0 || level >= (int)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
+  *stride = s->lv[level].line.s;
   return AMG_HIP_OK;
 }
 
@@ -3874,6 +4002,8 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
 amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int32_t name_cap,
                                        int32_t* sweeps_per_launch, double* bytes_per_launch) {
   if (!s || !name || name_cap < 32) return fail(AMG_HIP_EINVAL, "bad argument");
+  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI)
+    return fail(AMG_HIP_EUNSUPPORTED, "fine_sweep_info: a line-smoother sweep is not one launch");
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no device matrices");
   const Level& L = s->lv[0];
   const DevMat& A = L.A_cols();
@@ -4213,6 +4343,38 @@ amg_hip_status amg_hip_smooth_chebyshev(int64_t n, const int32_t* colptr, const 
     }
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(u, cur, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_smooth_line(int64_t n, const int32_t* colptr, const int32_t* rowind, const double* val,
+                                   int64_t stride, double omega, int64_t iters, double* u, const double* f) {
+  if (n <= 0 || !colptr || !rowind || !val || !u || !f) return fail(AMG_HIP_EINVAL, "bad argument");
+  if (stride < 0) return fail(AMG_HIP_EINVAL, "`stride` must be >= 0 (0: the automatic rule)");
+  if (iters < 0) return fail(AMG_HIP_EINVAL, "`iters` must be >= 0");
+  std::string v = line_options_error(omega);
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
+  Sparse A = from_raw(n, n, colptr, rowind, val);
+  v = validate(A, "A");
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
+  if (n >= ((int64_t)1 << 31)) return fail(AMG_HIP_EUNSUPPORTED, "line smoother: 2^31 rows or more");
+  Sparse Ar = transpose(A);  // T and the residual are taken from the rows of A
+  amg_hip_status st = need_device();
+  if (st != AMG_HIP_OK) return st;
+  DevCsr rows;
+  HIP_TRY(upload_csr(Ar, &rows));
+  LineOnDev D;
+  st = line_setup_dev(0, n, rows.rowptr(), rows.col(), rows.v(), stride, &D);
+  if (st != AMG_HIP_OK) return st;
+  DevMat M;
+  HIP_TRY(upload_mat(Ar, g_default_layout, &M));
+  DevMem du, df, dr;
+  HIP_TRY(upload(du, u, (size_t)n));
+  HIP_TRY(upload(df, f, (size_t)n));
+  HIP_TRY(dr.alloc(sizeof(double) * n));
+  for (int64_t it = 0; it < iters; ++it)
+    HIP_TRY(launch_line_sweep(M, D, du.as<double>(), df.as<double>(), dr.as<double>(), omega, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(u, du.p, sizeof(double) * n, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
 }
 

@@ -106,6 +106,9 @@ class Multigrid {
       opt.cheb_degree = ch->get_degree();
       opt.cheb_lower = ch->get_lower();
       opt.cheb_upper = ch->get_upper();
+    } else if (auto* lj = dynamic_cast<LineJacobi<EleType>*>(smoother)) {
+      opt.smoother = AMG_HIP_SM_LINE_JACOBI;
+      opt.omega = lj->get_omega();
     } else {
       // user-defined SmootherBase: its smooth() runs on the host, everything else of the
       // V-cycle on the device; the device-side smoother is never used

@@ -159,4 +159,29 @@ class Chebyshev : public SmootherBase<EleType> {
   }
 };
 
+// Build-side addition (no reference counterpart): line relaxation, Jacobi between the lines
+// (amg_hip.h: AMG_HIP_SM_LINE_JACOBI).  One sweep is u <- u + omega T^-1 (b - A u), T the
+// tridiagonal part of A along the lines the level's stride rule picks; `n_iters` sweeps per smooth().
+// On the hierarchies that halve the flat index it relaxes the lines of the direction that is not
+// coarsened.  omega in (0, 2); 0.7 is the recommended value (1.0 converges poorly).
+template <class EleType>
+class LineJacobi : public SmootherBase<EleType> {
+  double omega{0.7};
+
+ public:
+  LineJacobi(double omega_ = 0.7, size_t n_iters_ = 1) : omega(omega_) {
+    this->n_iters = n_iters_;
+    this->compute_error_every_n_iters = 0;
+    if (!(omega > 0.0 && omega < 2.0)) throw std::invalid_argument("`omega` must lie in (0, 2)");
+  }
+  double get_omega() const { return omega; }
+  void smooth(const Eigen::SparseMatrix<EleType>& A, Eigen::Matrix<EleType, -1, 1>& u,
+              const Eigen::Matrix<EleType, -1, 1>& b) override {
+    static_assert(sizeof(EleType) == sizeof(double), "the MI355X path is fp64 only");
+    const Eigen::SparseMatrix<EleType> C = detail::compressed(A);
+    detail::check(amg_hip_smooth_line(C.rows(), C.outerIndexPtr(), C.innerIndexPtr(), C.valuePtr(), 0, omega,
+                                      (int64_t)this->n_iters, u.data(), b.data()));
+  }
+};
+
 }  // namespace AMG

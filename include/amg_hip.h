@@ -43,7 +43,7 @@ typedef enum {
 } amg_hip_status;
 
 /* Smoother plug-ins (smoother.hpp).  0-2 are the reference's three classes;
- * 3-5 are build-side additions the reference does not contain.   */
+ * 3-6 are build-side additions the reference does not contain.   */
 typedef enum {
   AMG_HIP_SM_SPGS = 0,          /* AMG::SparseGaussSeidel smoother.hpp:86-216:
                                    n_iters x (forward + backward lexicographic
@@ -53,11 +53,35 @@ typedef enum {
   AMG_HIP_SM_SOR = 2,           /* AMG::SuccessiveOverRelaxation :271-373       */
   AMG_HIP_SM_JACOBI = 3,        /* true two-buffer weighted Jacobi              */
   AMG_HIP_SM_MULTICOLOR_GS = 4, /* symmetric multicolour Gauss-Seidel           */
-  AMG_HIP_SM_CHEBYSHEV = 5      /* Chebyshev polynomial in D^-1 A of degree
+  AMG_HIP_SM_CHEBYSHEV = 5,     /* Chebyshev polynomial in D^-1 A of degree
                                    cheb_degree on [cheb_lower G, cheb_upper G],
                                    G = Gershgorin bound of D^-1 A per level (rows
                                    of A); smoother_iters applications per leg,
                                    each cheb_degree Jacobi-shaped passes        */
+  AMG_HIP_SM_LINE_JACOBI = 6    /* line relaxation, Jacobi between the lines: with T
+                                   = the entries of A at column offsets 0, +s and -s
+                                   (tridiagonal on each of the min(s, n) chains of
+                                   rows c, c + s, c + 2s, ...), one sweep is
+                                   u <- u + omega T^-1 (f - A u), the residual taken
+                                   from the old u throughout; smoother_iters sweeps
+                                   per leg.  The stride s of a level comes from its
+                                   matrix alone: with w(d) the sum of |a_ij| over
+                                   the entries at distance d = |j - i| >= 1, s is
+                                   the LARGEST d with w(d) >= (1 - 1e-9) max w (s = 1
+                                   without off-diagonal entries; see
+                                   amg_hip_line_stride).  On the hierarchies made by
+                                   halving the flat index it relaxes the lines of
+                                   the direction that is not coarsened.  omega must
+                                   lie in (0, 2); the default 1.0 is a poor choice
+                                   here, 0.7 is recommended (INTEGRATION.md has the
+                                   table).  Meant for diagonally dominant operators:
+                                   T is eliminated without pivoting, and setup
+                                   refuses with AMG_HIP_EINVAL (level and row in the
+                                   message) a pivot that is zero or not finite.
+                                   T is symmetric when A is, so the V-cycle stays a
+                                   valid PCG preconditioner.  Window solvers, slab
+                                   sharding and the block entry points refuse it
+                                   (AMG_HIP_EUNSUPPORTED).                       */
 } amg_hip_smoother;
 
 /* Device layout of the level matrices (results are bit-identical in all).    */
@@ -312,7 +336,7 @@ typedef struct amg_hip_slab_info {
 amg_hip_status amg_hip_slab_plan(int64_t lines, int32_t rank, int32_t world, int32_t levels,
                                  amg_hip_slab_info* out);
 /* max_levels < 0: every K-Patch level.  AMG_HIP_EUNSUPPORTED when the solver has none, and for
- * the Chebyshev smoother (not sharded).                                                    */
+ * the Chebyshev and line smoothers (not sharded).                                          */
 amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world,
                                   int32_t max_levels, amg_hip_slab_info* info);
 /* part 1: down-legs of the slab levels; 2: the replicated rest of the cycle (from the gathered
@@ -345,7 +369,7 @@ amg_hip_status amg_hip_slab_run(amg_hip_solver* s, int32_t part);
  * single-GPU cycle bit for bit (tests/test_window_gloo.py, tests/test_gpu_window.py).
  * amg_hip_create_poisson_window: options as amg_hip_create_poisson; `n_levels` = k + 1 (level k
  * is only a container for f_k / u_k: opts->window is forced to 1).  AMG_HIP_EUNSUPPORTED for
- * the Chebyshev smoother (not sharded).                                                    */
+ * the Chebyshev and line smoothers (not sharded).                                          */
 amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t unit_begin,
                                              int64_t unit_end, int32_t n_levels,
                                              const amg_hip_options* opts, amg_hip_solver** out);
@@ -531,6 +555,11 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op);
  * host setup computes the bounds without a device).  AMG_HIP_EINVAL for other smoothers.   */
 amg_hip_status amg_hip_cheb_bounds(const amg_hip_solver* s, int32_t level, double* lo, double* hi);
 
+/* AMG_HIP_SM_LINE_JACOBI: the stride s of `level` (the rule in the enum's comment).  Also on
+ * host_only solvers, where the host computes it; the device rule gives the same integer.
+ * AMG_HIP_EINVAL for other smoothers.                                                      */
+amg_hip_status amg_hip_line_stride(const amg_hip_solver* s, int32_t level, int64_t* stride);
+
 /* Sum over levels of the algorithmic HBM bytes of one V-cycle (SURVEY 8(d)
  * formulae) and the per-sweep bytes of level 0; used by bench.py.             */
 amg_hip_status amg_hip_cycle_bytes(const amg_hip_solver* s, double* cycle_bytes,
@@ -551,6 +580,7 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
  * AMG_HIP_SM_JACOBI: one launch = one sweep over level 0 (K-Patch: the level's down-leg);
  * AMG_HIP_SM_CHEBYSHEV: one middle step of the polynomial over level 0 (u -> tmp, d read and
  * written), or step 0 when the degree has no middle step (1 or 2);
+ * AMG_HIP_SM_LINE_JACOBI: refused (AMG_HIP_EUNSUPPORTED; a sweep is four launches);
  * AMG_HIP_SM_MULTICOLOR_GS: the first launch of the symmetric pass (K-Patch form: two colour
  * stages over the level; colour kernels: colour 0).  The level-0 solution is restored
  * afterwards.                                                                  */
@@ -583,6 +613,14 @@ amg_hip_status amg_hip_smooth_chebyshev(int64_t n, const int32_t* colptr, const 
                                         const double* val, double* u, const double* b,
                                         int32_t degree, double lower, double upper,
                                         int64_t n_iters);
+/* The line smoother (AMG_HIP_SM_LINE_JACOBI) on host arrays: `iters` sweeps
+ * u <- u + omega T^-1 (f - A u) with the lines at distance `stride`; stride = 0 takes the
+ * automatic rule, any stride >= 1 is legal (every stride >= n means the same thing, each row
+ * its own line, i.e. weighted Jacobi, and is taken as n).  u is updated in place.  AMG_HIP_EINVAL: stride < 0, iters < 0, omega
+ * outside (0, 2), or a pivot of T that is zero or not finite (row in the message).         */
+amg_hip_status amg_hip_smooth_line(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                   const double* val, int64_t stride, double omega, int64_t iters,
+                                   double* u, const double* f);
 /* One lexicographic sweep, dir=+1 forward (smoother.hpp:148-157) or -1 backward
  * (:167-174). */
 amg_hip_status amg_hip_spgs_sweep(int32_t dir, int64_t n, const int32_t* colptr,

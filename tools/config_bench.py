@@ -4,9 +4,10 @@ headline) and records the convergence factor next to every rate.
 usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configuration
        config_bench.py all                                         the README table
        config_bench.py cheb                                        the Chebyshev rows
+       config_bench.py line                                        the line-smoother rows (line and Jacobi legs alternate)
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
-smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1).  Setup runs on the device (amg_hip_create_poisson);
+smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
 smoothers that need host structures fall back to the host path inside it."""
 import os
 import sys
@@ -21,7 +22,8 @@ KW = {"spgs": dict(smoother=amg.SM_SPGS, smoother_iters=1),
       "jacobi1": dict(smoother=amg.SM_JACOBI, smoother_iters=1, omega=0.6),
       "multicolor": dict(smoother=amg.SM_MULTICOLOR_GS, smoother_iters=1),
       "cheb": dict(smoother=amg.SM_CHEBYSHEV, smoother_iters=1, cheb_degree=2),
-      "cheb3": dict(smoother=amg.SM_CHEBYSHEV, smoother_iters=1, cheb_degree=3)}
+      "cheb3": dict(smoother=amg.SM_CHEBYSHEV, smoother_iters=1, cheb_degree=3),
+      "line": dict(smoother=amg.SM_LINE_JACOBI, smoother_iters=1, omega=0.7)}
 
 
 def run(dim, n, L, sm, cycles=10, warm=6, **extra):
@@ -79,6 +81,56 @@ def run_rs(n, sm, cycles=10, theta=0.25, min_coarse=500, dim=2):
         print(f"   PCG on the same hierarchy: {it} iterations to relative residual {rel:.2e} in {(t3-t2)*1e3:.1f} ms "
               f"(incl. copying the solution back)", flush=True)
     mg.close()
+
+
+def run_to_tol(dim, n, L, sms=("line", "jacobi"), tol=1e-8, cap=3000, reps=3, pcg_levels=None):
+    """V-cycles/s, and cycles and milliseconds to ||r|| / ||r0|| <= tol from u = 0 (Grid::rhs), for
+    every smoother of `sms` on the same problem, the legs alternating, `reps` repeats.  The run to
+    tol checks rss every `chunk` cycles (one device synchronise per chunk) and its time is the wall
+    time of the whole run, checks included.  pcg_levels: also PCG to tol on that many levels."""
+    mgs = {sm: amg.Multigrid.poisson(n, L, dim=dim, **KW[sm]) for sm in sms}
+    for mg in mgs.values():
+        mg.vcycle(3)
+        mg.sync()
+    for rep_ in range(reps):
+        for sm, mg in mgs.items():
+            cyc = 10
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            mg.vcycle(cyc)
+            mg.sync()
+            dt = (time.perf_counter() - t0) / cyc
+            mg.zero_vec(0, "u")
+            mg.sync()
+            r0 = mg.rss()
+            chunk = 1 if sm == "line" else 25
+            done, rel = 0, 1.0
+            t1 = time.perf_counter()
+            while done < cap and rel > tol:
+                mg.vcycle(chunk)
+                done += chunk
+                rel = (mg.rss() / r0) ** 0.5
+            t2 = time.perf_counter()
+            arrived = "reached" if rel <= tol else "NOT reached"
+            print(f"dim={dim} n={n} levels={L} {sm} rep {rep_}: {dt*1e3:.3f} ms/V-cycle = {1/dt:.1f} V-cycles/s; "
+                  f"||r||/||r0|| {rel:.2e} after {done} cycles ({tol:g} {arrived}, checked every {chunk}) in "
+                  f"{(t2-t1)*1e3:.1f} ms; factor per cycle {rel ** (1 / done):.4f}", flush=True)
+    for mg in mgs.values():
+        mg.close()
+    if pcg_levels:
+        for sm in sms:
+            mg = amg.Multigrid.poisson(n, pcg_levels, dim=dim, **KW[sm])
+            mg.pcg(1e-2, 5)                     # warm-up: graph capture
+            for rep_ in range(reps):
+                mg.zero_vec(0, "u")
+                mg.sync()
+                t0 = time.perf_counter()
+                _, it, rel = mg.pcg(tol, 1000)
+                t1 = time.perf_counter()
+                print(f"dim={dim} n={n} levels={pcg_levels} {sm} PCG rep {rep_}: {it} iterations to {rel:.2e} in "
+                      f"{(t1-t0)*1e3:.1f} ms (incl. copying the solution back)", flush=True)
+            mg.close()
 
 
 def block_memory(mg, kp, cheb):
@@ -167,6 +219,12 @@ elif len(sys.argv) > 1 and sys.argv[1] == "cheb":
     run_rs(1024, "jacobi")
     run(3, 256, 17, "cheb", 10)                        # 256^3 3-D
     run(3, 256, 17, "jacobi", 10)
+elif len(sys.argv) > 1 and sys.argv[1] == "line":
+    run_to_tol(2, 4096, 16, pcg_levels=9)              # the bench.py problem: line 1+1 next to true Jacobi 2+2
+    run_to_tol(2, 1024, 12)
+    run_to_tol(3, 256, 17, cap=200, reps=1)            # 3-D: no gain expected (a line covers one of two directions)
+elif len(sys.argv) > 2 and sys.argv[1] == "line10":    # ten cycles of one smoother at 4096^2 (kernel traces)
+    run(2, 4096, 16, sys.argv[2], 10, warm=2)
 elif len(sys.argv) > 1 and sys.argv[1] == "rs":
     for n in (512, 1024, 2048):
         run_rs(n, "multicolor")
