@@ -105,6 +105,12 @@ _SIGS = {
                                         C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_create_poisson": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(Options),
                                          C.POINTER(C.c_void_p)]),
+    "amg_hip_create_tensor": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
+                                        C.c_int32, C.POINTER(Options), C.POINTER(C.c_void_p)]),
+    "amg_hip_get_level_dims": (C.c_int, [C.c_void_p, C.c_int32, _i64p]),
+    "amg_hip_level_transfer_kind": (C.c_int, [C.c_void_p, C.c_int32, _i32p]),
+    "amg_hip_tensor_restrict": (C.c_int, [C.c_int32, _i64p, _f64p, _f64p]),
+    "amg_hip_tensor_prolong_add": (C.c_int, [C.c_int32, _i64p, _f64p, _f64p]),
     "amg_hip_destroy": (None, [C.c_void_p]),
     "amg_hip_vcycle": (C.c_int, [C.c_void_p]),
     "amg_hip_vcycles": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -504,6 +510,67 @@ class Multigrid:
         return self
 
     @classmethod
+    def tensor(cls, colptr, rowind, val, b, dims, n_levels, smoother=SM_SPGS, smoother_iters=1, omega=1.0,
+               tolerance=1e-9, compute_error_every_n_iters=10, n_iters=100, device=-1, use_graph=True,
+               stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
+               no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
+               exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
+               window=False):
+        """AMG::Multigrid on a FULL-coarsening hierarchy of the grid `dims` = (nx, ny) or (nx, ny, nz),
+        x fastest (amg_hip_create_tensor): every axis m -> m // 2, tensor-product linear interpolation,
+        matrix-free transfer kernels unless stencil_transfers=False.  A is the caller's matrix on
+        that grid."""
+        if compute_error_every_n_iters > n_iters:
+            raise ValueError("`compute_error_every_n_iters` must be leq to `n_iters`, got "
+                             f"{compute_error_every_n_iters} and {n_iters}")
+        colptr, rowind, val, b = _a32(colptr), _a32(rowind), _a64(val), _a64(b)
+        n = colptr.size - 1
+        if n != b.size:
+            raise ValueError("`A` and `b` must have the same number of degrees of freedom, "
+                             f"got {n} and {b.size}")
+        dim, d3 = _dims3(dims)
+        self = cls.__new__(cls)
+        self.tolerance, self.every, self.n_iters = tolerance, compute_error_every_n_iters, n_iters
+        o = cls._options(smoother, smoother_iters, omega, device, use_graph, stencil_transfers, layout,
+                         host_only, keep_structural_zeros, no_fusion, False, stream, fast_coarse_solve,
+                         False, keep_residual, exact_coarse_solve, exact_gs, cheb_degree, cheb_lower,
+                         cheb_upper)
+        o.window = int(window)
+        h = C.c_void_p()
+        st = lib().amg_hip_create_tensor(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
+                                         d3.ctypes.data_as(_i64p), int(n_levels), C.byref(o), C.byref(h))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        self._h = h
+        self._device = device
+        return self
+
+    @classmethod
+    def poisson_tensor(cls, n, n_levels, dim=2, **opts):
+        """Multigrid.tensor on A = Grid::laplacian(n), b = Grid::rhs(n) (the n^dim grid)."""
+        cp, ri, v = laplacian(n, dim)
+        return cls.tensor(cp, ri, v, rhs(n, dim), (n,) * dim, n_levels, **opts)
+
+    def level_dims(self, level):
+        """(nx, ny, nz) of `level` of a Multigrid.tensor solver (amg_hip_get_level_dims)."""
+        d = np.zeros(3, np.int64)
+        st = lib().amg_hip_get_level_dims(self._h, int(level), d.ctypes.data_as(_i64p))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return tuple(int(x) for x in d)
+
+    def level_transfer_kind(self, level):
+        """0 = CSR SpMV transfers, 1 = the flat stride-2 kernels, 2 = the tensor-product kernels."""
+        k = C.c_int32(-1)
+        st = lib().amg_hip_level_transfer_kind(self._h, int(level), C.byref(k))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return k.value
+
+    @classmethod
     def poisson(cls, n, n_levels, dim=2, smoother=SM_SPGS, smoother_iters=1, omega=1.0, tolerance=1e-9,
                 compute_error_every_n_iters=10, n_iters=100, device=-1, use_graph=True,
                 stencil_transfers=True, layout=None, keep_structural_zeros=False, no_fusion=False,
@@ -901,6 +968,49 @@ def linear_prolong_add(n_h, n_H, u_H, u_h):
     u_H = _a64(u_H)
     u_h = np.array(u_h, dtype=np.float64, copy=True)
     _chk(lib().amg_hip_linear_prolong_add(n_h, n_H, _p64(u_H), _p64(u_h)))
+    return u_h
+
+
+def _dims3(dims):
+    """(dim, int64[3]) of a 2- or 3-tuple of grid sizes, x fastest."""
+    dims = tuple(int(x) for x in dims)
+    if len(dims) not in (2, 3):
+        raise ValueError(f"`dims` must have 2 or 3 entries, got {len(dims)}")
+    return len(dims), np.array(dims + (1,) * (3 - len(dims)), np.int64)
+
+
+def _tensor_sizes(d3, dim):
+    c = [int(d3[0]) // 2, int(d3[1]) // 2, int(d3[2]) // 2 if dim == 3 else 1]
+    return int(d3[0] * d3[1] * d3[2]), c[0] * c[1] * c[2]
+
+
+def tensor_restrict(dims, r):
+    """f_H = R r for the full-coarsening transfer of the fine grid `dims` (amg_hip_tensor_restrict)."""
+    dim, d3 = _dims3(dims)
+    r = _a64(r)
+    n_h, n_H = _tensor_sizes(d3, dim)
+    if r.size != n_h:
+        raise ValueError(f"`r` must have {n_h} entries, got {r.size}")
+    out = np.empty(max(n_H, 0), np.float64)
+    st = lib().amg_hip_tensor_restrict(dim, d3.ctypes.data_as(_i64p), _p64(r), _p64(out))
+    if st == EINVAL:
+        raise ValueError(lib().amg_hip_last_error().decode())
+    _chk(st)
+    return out
+
+
+def tensor_prolong_add(dims, u_H, u_h):
+    """u_h + P u_H for the same transfer (amg_hip_tensor_prolong_add); returns a new array."""
+    dim, d3 = _dims3(dims)
+    u_H = _a64(u_H)
+    u_h = np.array(u_h, dtype=np.float64, copy=True)
+    n_h, n_H = _tensor_sizes(d3, dim)
+    if u_h.size != n_h or u_H.size != n_H:
+        raise ValueError(f"`u_h` / `u_H` must have {n_h} / {n_H} entries, got {u_h.size} / {u_H.size}")
+    st = lib().amg_hip_tensor_prolong_add(dim, d3.ctypes.data_as(_i64p), _p64(u_H), _p64(u_h))
+    if st == EINVAL:
+        raise ValueError(lib().amg_hip_last_error().decode())
+    _chk(st)
     return u_h
 
 

@@ -170,6 +170,53 @@ bool is_linear_P(const Sparse& P, int64_t n_h, int64_t n_H) {
   return same_arrays(P, linear_P(n_h, n_H));
 }
 
+// Full coarsening of an nx x ny x nz grid (x fastest): P = P1(nz) (x) P1(ny) (x) P1(nx) with P1(m)
+// the m x floor(m/2) matrix whose column j holds 0.5, 1.0, 0.5 on rows 2j, 2j+1, 2j+2 (guarded by
+// < m); an axis that is not coarsened (nz of a 2-D grid) contributes the identity.
+void tensor_coarse_dims(int dim, const int64_t d[3], int64_t c[3]) {
+  c[0] = d[0] / 2;
+  c[1] = d[1] / 2;
+  c[2] = dim == 3 ? d[2] / 2 : 1;
+}
+
+Sparse tensor_P(int dim, const int64_t d[3]) {
+  int64_t c[3];
+  tensor_coarse_dims(dim, d, c);
+  const int64_t nx = d[0], ny = d[1], nz = dim == 3 ? d[2] : 1;
+  Sparse P;  // CSC: outer = coarse column (K, J, I), I fastest
+  P.n_outer = c[0] * c[1] * c[2];
+  P.n_inner = nx * ny * nz;
+  P.ptr.resize((size_t)P.n_outer + 1);
+  P.ptr[0] = 0;
+  P.idx.reserve((size_t)(dim == 3 ? 27 : 9) * (size_t)P.n_outer);
+  P.val.reserve((size_t)(dim == 3 ? 27 : 9) * (size_t)P.n_outer);
+  static const double w3[3] = {0.5, 1.0, 0.5};
+  const int tz_n = dim == 3 ? 3 : 1;
+  int64_t col = 0;
+  for (int64_t K = 0; K < c[2]; ++K)
+    for (int64_t J = 0; J < c[1]; ++J)
+      for (int64_t I = 0; I < c[0]; ++I) {
+        for (int tz = 0; tz < tz_n; ++tz) {  // ascending fine row: k, then j, then i
+          const int64_t k = dim == 3 ? 2 * K + tz : 0;
+          if (k >= nz) continue;
+          const double wz = dim == 3 ? w3[tz] : 1.0;
+          for (int ty = 0; ty < 3; ++ty) {
+            const int64_t j = 2 * J + ty;
+            if (j >= ny) continue;
+            const double wzy = wz * w3[ty];
+            for (int tx = 0; tx < 3; ++tx) {
+              const int64_t i = 2 * I + tx;
+              if (i >= nx) continue;
+              P.idx.push_back((int32_t)((k * ny + j) * nx + i));
+              P.val.push_back(wzy * w3[tx]);  // products of powers of two: exact
+            }
+          }
+        }
+        P.ptr[(size_t)++col] = (int32_t)P.idx.size();
+      }
+  return P;
+}
+
 // ------------------------------------------------------------------ SpGEMM ---
 namespace {
 struct RowBlockOut {

@@ -34,6 +34,13 @@ Sparse linear_P(int64_t n_h, int64_t n_H);
 // true when P (CSC, n_h x n_H) is exactly what linear_P produces
 bool is_linear_P(const Sparse& P, int64_t n_h, int64_t n_H);
 
+// Full coarsening of an nx x ny (x nz) grid, x fastest (dof = (k ny + j) nx + i): every axis of
+// length m goes to floor(m / 2); dim = 2 leaves nz = 1 alone.  tensor_P returns the tensor-product
+// linear interpolation P1(nz) (x) P1(ny) (x) P1(nx) in CSC (n_h x n_H), P1(m) being m x floor(m/2)
+// with 0.5, 1.0, 0.5 on rows 2j, 2j+1, 2j+2 (< m) of column j; R = transpose(P).
+void tensor_coarse_dims(int dim, const int64_t dims[3], int64_t coarse[3]);
+Sparse tensor_P(int dim, const int64_t dims[3]);
+
 // multigrid.hpp:127-130
 inline int64_t coarse_dofs(int64_t n_h) { return (n_h + 1) / 2 - 1; }
 

@@ -2746,6 +2746,175 @@ hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
   return hipGetLastError();
 }
 
+// ------------------------------------- K-TensorRestrict / K-TensorProlong ---
+// Full coarsening (host_setup.hpp: tensor_P): P = P1(nz) (x) P1(ny) (x) P1(nx), R = P^T, every axis
+// m -> floor(m / 2), weights 0.5, 1.0, 0.5 on fine points 2J, 2J+1, 2J+2 (< m) of coarse point J.
+// All weights are products of powers of two, so every term w * v is exact and only the ORDER of
+// the additions decides the bits: both kernels add in the order the CSR SpMV with R / P does.
+struct TensorGrid {
+  uint32_t nx, ny, nz;  // fine
+  uint32_t mx, my, mz;  // coarse (mz == nz == 1 when z is not coarsened)
+  uint32_t cz;          // 1: z is coarsened (3-D)
+};
+
+// One lane per coarse point (I, J, K): f_H = sum over k, j, i ascending (row order of R) of
+// (wz wy wx) r[(k ny + j) nx + i], from +0.0.  The x-neighbours 2I, 2I+1 come as one aligned
+// 16-byte load where the address allows (always, on rows of even length), 2I+2 as a scalar load of
+// the line the next lane's pair sits in.  r is dead after this kernel.  VEC: r is 16-byte aligned.
+template <bool VEC>
+__global__ __launch_bounds__(256) void tensor_restrict_kernel(
+    TensorGrid g, const double* __restrict__ r, double* __restrict__ fH, double* __restrict__ uH) {
+  const uint32_t nH = g.mx * g.my * g.mz;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= nH) return;
+  const uint32_t I = t % g.mx, q = t / g.mx, J = q % g.my, K = q / g.my;
+  if (uH) uH[t] = 0.0;
+  const uint32_t i0 = 2u * I;        // i0 + 1 < nx always (I < floor(nx / 2))
+  const bool third = i0 + 2u < g.nx;
+  double s = 0.0;
+#pragma unroll
+  for (uint32_t tz = 0; tz < 3; ++tz) {
+    if (!g.cz && tz > 0) break;
+    const uint32_t k = g.cz ? 2u * K + tz : 0u;
+    if (k >= g.nz) break;
+    const double wz = g.cz ? (tz == 1 ? 1.0 : 0.5) : 1.0;
+#pragma unroll
+    for (uint32_t ty = 0; ty < 3; ++ty) {
+      const uint32_t j = 2u * J + ty;
+      if (j >= g.ny) break;
+      const double w = wz * (ty == 1 ? 1.0 : 0.5);
+      const int64_t a = ((int64_t)k * g.ny + j) * g.nx + i0;  // a + 1 (and a + 2 when third) < n_h
+      double v0, v1, v2 = 0.0;
+      if (VEC && (a & 1) == 0) {
+        const double2 p = *reinterpret_cast<const double2*>(r + a);
+        v0 = p.x;
+        v1 = p.y;
+        if (third) v2 = r[a + 2];
+      } else if (VEC && third) {
+        v0 = r[a];
+        const double2 p = *reinterpret_cast<const double2*>(r + a + 1);
+        v1 = p.x;
+        v2 = p.y;
+      } else {
+        v0 = r[a];
+        v1 = r[a + 1];
+        if (third) v2 = r[a + 2];
+      }
+      s += (w * 0.5) * v0;
+      s += (w * 1.0) * v1;
+      if (third) s += (w * 0.5) * v2;
+    }
+  }
+  fH[t] = s;
+}
+
+// One lane per fine pair (2p, 2p+1) of a fine grid line: u_h += t, t = sum over K, J, I ascending
+// (row order of P) of (wz wy wx) u_H[(K my + J) mx + I] from +0.0; 16-byte read-modify-write of
+// u_h where the address allows.  An odd fine index has the one coarse neighbour (i - 1) / 2 with
+// weight 1, an even one i / 2 - 1 and i / 2 with weight 0.5 (those that exist).
+template <bool VEC>
+__global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
+    TensorGrid g, const double* __restrict__ uH, double* uh) {
+  const uint32_t px = (g.nx + 1u) / 2u;  // pairs per fine line
+  const uint32_t total = px * g.ny * g.nz;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= total) return;
+  const uint32_t p = t % px, row = t / px, j = row % g.ny, k = row / g.ny;
+  // coarse neighbours along y and z: (index, weight, exists), ascending
+  uint32_t Jc[2], Kc[2];
+  double wy[2], wz[2];
+  bool oky[2], okz[2];
+  if (j & 1u) {
+    Jc[0] = (j - 1u) / 2u; wy[0] = 1.0; oky[0] = Jc[0] < g.my;
+    Jc[1] = 0; wy[1] = 0.0; oky[1] = false;
+  } else {
+    Jc[0] = j / 2u - 1u; wy[0] = 0.5; oky[0] = j >= 2u && Jc[0] < g.my;
+    Jc[1] = j / 2u; wy[1] = 0.5; oky[1] = Jc[1] < g.my;
+  }
+  if (!g.cz) {
+    Kc[0] = 0; wz[0] = 1.0; okz[0] = true;
+    Kc[1] = 0; wz[1] = 0.0; okz[1] = false;
+  } else if (k & 1u) {
+    Kc[0] = (k - 1u) / 2u; wz[0] = 1.0; okz[0] = Kc[0] < g.mz;
+    Kc[1] = 0; wz[1] = 0.0; okz[1] = false;
+  } else {
+    Kc[0] = k / 2u - 1u; wz[0] = 0.5; okz[0] = k >= 2u && Kc[0] < g.mz;
+    Kc[1] = k / 2u; wz[1] = 0.5; okz[1] = Kc[1] < g.mz;
+  }
+  const bool left = p >= 1u && p - 1u < g.mx;  // coarse I = p - 1 feeds fine 2p
+  const bool mid = p < g.mx;                   // coarse I = p feeds fine 2p and 2p + 1
+  double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      if (okz[a] && oky[b]) {
+        const double w = wz[a] * wy[b];
+        const double* c = uH + ((int64_t)Kc[a] * g.my + Jc[b]) * g.mx;
+        if (left) t0 += (w * 0.5) * c[p - 1u];
+        if (mid) {
+          const double m = c[p];
+          t0 += (w * 0.5) * m;
+          t1 += (w * 1.0) * m;
+        }
+      }
+    }
+  }
+  const int64_t i = (int64_t)row * g.nx + 2u * p;
+  if (2u * p + 1u < g.nx) {
+    if (VEC && (i & 1) == 0) {
+      double2 u = *reinterpret_cast<const double2*>(uh + i);
+      u.x = u.x + t0;
+      u.y = u.y + t1;
+      *reinterpret_cast<double2*>(uh + i) = u;
+    } else {
+      uh[i] = uh[i] + t0;
+      uh[i + 1] = uh[i + 1] + t1;
+    }
+  } else {
+    uh[i] = uh[i] + t0;
+  }
+}
+
+static bool tensor_grid(int dim, const int64_t dims[3], TensorGrid* g) {
+  if ((dim != 2 && dim != 3) || !dims) return false;
+  const int64_t nx = dims[0], ny = dims[1], nz = dim == 3 ? dims[2] : 1;
+  if (nx < 2 || ny < 2 || (dim == 3 && nz < 2) || (dim == 2 && dims[2] != 1)) return false;
+  if (nx >= ((int64_t)1 << 31) / ny / nz - 2) return false;  // 32-bit lane indices
+  g->nx = (uint32_t)nx;
+  g->ny = (uint32_t)ny;
+  g->nz = (uint32_t)nz;
+  g->mx = (uint32_t)(nx / 2);
+  g->my = (uint32_t)(ny / 2);
+  g->mz = dim == 3 ? (uint32_t)(nz / 2) : 1u;
+  g->cz = dim == 3 ? 1u : 0u;
+  return true;
+}
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], const double* r, double* fH,
+                                  double* uH_zero, hipStream_t st) {
+  TensorGrid g;
+  if (!tensor_grid(dim, dims, &g)) return hipErrorInvalidValue;
+  const uint32_t nH = g.mx * g.my * g.mz;
+  const dim3 grid((nH + 255u) / 256u), block(256);
+  if ((reinterpret_cast<uintptr_t>(r) & 15) == 0)
+    hipLaunchKernelGGL(tensor_restrict_kernel<true>, grid, block, 0, st, g, r, fH, uH_zero);
+  else
+    hipLaunchKernelGGL(tensor_restrict_kernel<false>, grid, block, 0, st, g, r, fH, uH_zero);
+  return hipGetLastError();
+}
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], const double* uH, double* uh,
+                                     hipStream_t st) {
+  TensorGrid g;
+  if (!tensor_grid(dim, dims, &g)) return hipErrorInvalidValue;
+  const uint32_t total = ((g.nx + 1u) / 2u) * g.ny * g.nz;
+  const dim3 grid((total + 255u) / 256u), block(256);
+  if ((reinterpret_cast<uintptr_t>(uh) & 15) == 0)
+    hipLaunchKernelGGL(tensor_prolong_add_kernel<true>, grid, block, 0, st, g, uH, uh);
+  else
+    hipLaunchKernelGGL(tensor_prolong_add_kernel<false>, grid, block, 0, st, g, uH, uh);
+  return hipGetLastError();
+}
+
 // First Jacobi sweep from a zero guess (coarse levels on the way down,
 // multigrid.hpp:278 then :268): with u == 0 every a_ij*u_j is +-0 and the row sum
 // is +0.0, so the sweep needs only f and the diagonal -- same operations, same

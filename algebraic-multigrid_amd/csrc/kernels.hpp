@@ -301,6 +301,16 @@ hipError_t launch_linear_restrict(int64_t n_h, int64_t n_H, const double* r, dou
                                   double* uH_zero, hipStream_t st);
 hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
                                      double* uh, hipStream_t st);
+// K-TensorRestrict / K-TensorProlong: the transfers of the full-coarsening hierarchies (host_setup.hpp:
+// tensor_P) without a matrix.  dims = fine grid (x fastest; dim = 2: dims[2] == 1 is not coarsened);
+// every coarsened axis must have at least 2 points and the fine level fewer than 2^31 - 2 rows, else
+// hipErrorInvalidValue.  Bit-identical to the CSR SpMV with R / P (same terms, same order).
+// f_H = R r, uH_zero (may be null) zero-filled in the same pass
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], const double* r, double* fH,
+                                  double* uH_zero, hipStream_t st);
+// u_h = u_h + P u_H
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], const double* uH, double* uh,
+                                     hipStream_t st);
 hipError_t launch_add_inplace(int64_t n, const double* x, double* y, hipStream_t st);
 // *out = sum x_i (square=0) or sum x_i^2 (square=1); scratch: 1024 doubles
 hipError_t launch_sum(int64_t n, const double* x, double* out, double* scratch, int square,

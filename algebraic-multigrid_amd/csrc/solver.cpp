@@ -1044,13 +1044,21 @@ struct Level {
   int64_t n_coarse = 0;
   const Sparse& P() const {
     if (lazy_linear && P_csc.ptr.empty()) P_csc = linear_P(n, n_coarse);  // interpolator.hpp:106-129
+    if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims);
     return P_csc;
   }
   const Sparse& R() const {
-    if (lazy_linear && R_csc.ptr.empty()) R_csc = transpose(P());         // :132-134
+    if ((lazy_linear || tensor_stencil) && R_csc.ptr.empty()) R_csc = transpose(P());  // :132-134
     return R_csc;
   }
   bool linear = false;
+  // full coarsening (amg_hip_create_tensor): the level's grid (x fastest; on every level of such a
+  // solver, the coarsest included) and whether the level's transfers are the tensor-product pair.
+  // tensor_stencil: they run matrix-free (opt.stencil_transfers), and the host copies of P / R are
+  // only kept while somebody needs them (the Galerkin product, a getter, the block CSR copies)
+  int tdim = 0;
+  int64_t dims[3] = {0, 0, 0};
+  bool tensor = false, tensor_stencil = false;
   DevCsr P_rows, R_rows;   // CSR(P), CSR(R)
   // exact lexicographic schedules
   std::unique_ptr<LexOnDev> lex_fwd, lex_bwd;
@@ -1855,6 +1863,10 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
         HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(),
                                        zero_known ? nullptr : C.u.as<double>(), st));
         s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
+      } else if (L.tensor_stencil) {                               // the same two steps, full coarsening
+        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.r.as<double>(), C.f.as<double>(),
+                                       zero_known ? nullptr : C.u.as<double>(), st));
+        s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
       } else {
         if (!zero_known) HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st)); // :278
         const DevCsr& R = L.R_rows;
@@ -1958,6 +1970,9 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
       else
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
       s->acct(8.0 * C.n + 16.0 * L.n);
+    } else if (L.tensor_stencil) {
+      HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, C.u.as<double>(), L.u.as<double>(), st));
+      s->acct(8.0 * C.n + 16.0 * L.n);
     } else {
       const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
       HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz,
@@ -2055,8 +2070,14 @@ void compute_bytes(amg_hip_solver* s) {
       total += sweep * sweeps_per_smooth + extra;
       const double nH = (double)s->lv[l + 1].n, nh = (double)L.n;
       total += 8.0 * nH;                                   // zero
-      total += 12.0 * 3 * nH + 4 * nH + 8 * nh + 8 * nH;   // restrict (CSR R)
-      total += 12.0 * 3 * nH + 4 * nh + 8 * nH + 16 * nh;  // prolong + add (CSR P)
+      if (L.tensor_stencil) {                              // K-TensorRestrict / K-TensorProlong
+        total += 8 * nh + 8 * nH;
+        total += 16 * nh + 8 * nH;
+        continue;
+      }
+      const double pnnz = L.tensor ? (L.tdim == 3 ? 27.0 : 9.0) : 3.0;  // entries per column of P
+      total += 12.0 * pnnz * nH + 4 * nH + 8 * nh + 8 * nH;   // restrict (CSR R)
+      total += 12.0 * pnnz * nH + 4 * nh + 8 * nH + 16 * nh;  // prolong + add (CSR P)
     }
   }
   s->cycle_bytes = total;
@@ -2071,7 +2092,8 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
                             const double* const* Pv, const int32_t* const* Rc,
                             const int32_t* const* Rr, const double* const* Rv,
                             const amg_hip_options* opts, amg_hip_solver** out,
-                            double rs_theta = -1.0, int64_t rs_min_coarse = 0) {
+                            double rs_theta = -1.0, int64_t rs_min_coarse = 0, int tensor_dim = 0,
+                            const int64_t* tensor_dims = nullptr) {
   if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
   *out = nullptr;
   if (!colptr || !rowind || !val || !b) return fail(AMG_HIP_EINVAL, "null input array");
@@ -2152,6 +2174,10 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     L0.A_csc = from_raw(n, n, colptr, rowind, val);
     std::string v = validate(L0.A_csc, "A");
     if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
+    if (tensor_dim) {
+      L0.tdim = tensor_dim;
+      for (int a = 0; a < 3; ++a) L0.dims[a] = tensor_dims[a];
+    }
   }
   // ---- hierarchy (multigrid.hpp:211-237) ----
   Sparse A_r = transpose(s->lv[0].A_csc);  // CSR(A_0)
@@ -2347,10 +2373,38 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       }
       L.R_csc = transpose(L.P_csc);
       L.linear = false;
+    } else if (tensor_dim) {
+      // full coarsening: every axis m -> floor(m / 2), possible while every coarsened axis has 2 points
+      if (L.dims[0] < 2 || L.dims[1] < 2 || (tensor_dim == 3 && L.dims[2] < 2))
+        return fail(AMG_HIP_EINVAL, "level " + std::to_string(l + 1) + " is not possible: level " +
+                                        std::to_string(l) + " is a " + std::to_string(L.dims[0]) + " x " +
+                                        std::to_string(L.dims[1]) + " x " + std::to_string(L.dims[2]) +
+                                        " grid and an axis of fewer than 2 points cannot be coarsened; "
+                                        "reduce `n_levels`");
+      Level& C = s->lv[l + 1];
+      C.tdim = tensor_dim;
+      tensor_coarse_dims(tensor_dim, L.dims, C.dims);
+      n_H = C.dims[0] * C.dims[1] * C.dims[2];
+      L.tensor = true;
+      L.n_coarse = n_H;
+      // the matrix-free kernels index lanes with 32 bits (kernels.hip: tensor_grid)
+      L.tensor_stencil = s->opt.stencil_transfers && L.n < ((int64_t)1 << 31) - 4;
+      if (!L.tensor_stencil) {
+        L.P_csc = tensor_P(tensor_dim, L.dims);
+        L.R_csc = transpose(L.P_csc);
+      }
     } else if (n_H < 1) {
       return fail(AMG_HIP_EINVAL, "level " + std::to_string(l + 1) +
                                       " would have no degrees of freedom; reduce `n_levels`");
     } else if (Pc) {
+      // The arrays carry no coarse size.  The reference's rule is the default; operators of another
+      // coarsening (full coarsening of a grid, aggregation) say theirs through R_l, whose rows are
+      // the coarse dofs: largest row index + 1.
+      if (Rc[l] && Rr[l]) {
+        int64_t rows = 0;
+        for (int32_t q = 0, e = Rc[l][n_h]; q < e; ++q) rows = std::max<int64_t>(rows, (int64_t)Rr[l][q] + 1);
+        if (rows >= 1 && rows != n_H) n_H = rows;
+      }
       L.P_csc = from_raw(n_H, n_h, Pc[l], Pr[l], Pv[l]);
       L.R_csc = from_raw(n_h, n_H, Rc[l], Rr[l], Rv[l]);
       std::string v = validate(L.P_csc, "P");
@@ -2365,7 +2419,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     // the matrix-free kernels need no device copy of the linear operators, and the
     // device Galerkin product no host copy
     const bool dev_galerkin = dev && L.linear && !s->opt.host_galerkin;
-    const bool dev_rows = dev && !(L.linear && s->opt.stencil_transfers);
+    const bool dev_rows = dev && !(L.linear && s->opt.stencil_transfers) && !L.tensor_stencil;
     Sparse P_r, R_r;
     if (dev_rows || !dev_galerkin) {
       P_r = transpose(L.P());  // CSR(P)
@@ -2387,7 +2441,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       galerkin_A = std::move(next);
       galerkin_on_dev = true;
       done = true;
-    } else if (dev && dev_rows && !s->opt.host_galerkin) {
+    } else if (dev && dev_rows && !s->opt.host_galerkin && !L.tensor) {
       // custom interpolator: general K-way-merge product on the device (CSR(P), CSR(R) were
       // uploaded for the transfer kernels anyway)
       if (!galerkin_on_dev) HIP_TRY(upload_csr(A_r, &galerkin_A));
@@ -2401,6 +2455,10 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     if (!done) {
       AH_r = galerkin_csr(R_r, A_r, P_r, nt);
       galerkin_on_dev = false;
+    }
+    if (L.tensor_stencil) {  // rebuilt when a getter or the block cycle asks (Level::P)
+      L.P_csc = Sparse();
+      L.R_csc = Sparse();
     }
     timer.lap(T_RAP);
     Level& C = s->lv[l + 1];
@@ -2893,6 +2951,13 @@ amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
     for (int l = 0; l < nl; ++l) {
       Level& L = s->lv[l];
       BlockLevel& Q = B.lv[(size_t)l];
+      if (L.tensor_stencil && l + 1 < nl && L.P_rows.n_rows == 0) {
+        // the block transfers of a full-coarsening level are the CSR kernels (same bits)
+        HIP_TRY(upload_csr(transpose(L.P()), &L.P_rows));
+        HIP_TRY(upload_csr(transpose(L.R()), &L.R_rows));
+        L.P_csc = Sparse();
+        L.R_csc = Sparse();
+      }
       if (l + 1 == nl && l > 0) continue;  // the coarsest level only takes the direct solve
       // the entry set of the device matrices: exact zeros dropped unless keep_structural_zeros,
       // ascending column order (A_rows is plain CSR already when its layout is)
@@ -3209,6 +3274,53 @@ amg_hip_status amg_hip_create_rs(int64_t n, const int32_t* colptr, const int32_t
   if (min_coarse < 1) return fail(AMG_HIP_EINVAL, "`min_coarse` must be at least 1");
   return build_solver(n, colptr, rowind, val, b, max_levels, nullptr, nullptr, nullptr, nullptr,
                       nullptr, nullptr, opts, out, theta, min_coarse);
+}
+
+static std::string tensor_dims_error(int32_t dim, const int64_t* dims) {
+  if (dim != 2 && dim != 3) return "`dim` must be 2 or 3";
+  if (!dims) return "`dims` is null";
+  if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return "every entry of `dims` must be at least 1";
+  if (dim == 2 && dims[2] != 1) return "`dims[2]` must be 1 when `dim` is 2";
+  if (dims[0] >= ((int64_t)1 << 31) / dims[1] / dims[2]) return "the grid has 2^31 points or more";
+  return "";
+}
+
+amg_hip_status amg_hip_create_tensor(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                     const double* val, const double* b, int32_t dim,
+                                     const int64_t* dims, int32_t n_levels,
+                                     const amg_hip_options* opts, amg_hip_solver** out) {
+  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
+  *out = nullptr;
+  const std::string e = tensor_dims_error(dim, dims);
+  if (!e.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor: " + e);
+  if (n != dims[0] * dims[1] * dims[2])
+    return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor: `n` = " + std::to_string(n) + " is not the " +
+                                    std::to_string(dims[0]) + " x " + std::to_string(dims[1]) + " x " +
+                                    std::to_string(dims[2]) + " grid of `dims`");
+  if (opts && opts->window)
+    return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_tensor: window solvers (opt.window) coarsen the "
+                                      "flat index; a full-coarsening hierarchy is not sharded");
+  return build_solver(n, colptr, rowind, val, b, n_levels, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      nullptr, opts, out, -1.0, 0, dim, dims);
+}
+
+amg_hip_status amg_hip_get_level_dims(const amg_hip_solver* s, int32_t level, int64_t* dims) {
+  if (!s || !dims) return fail(AMG_HIP_EINVAL, "null argument");
+  if (level < 0 || level >= (int)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
+  const Level& L = s->lv[level];
+  if (!L.tdim)
+    return fail(AMG_HIP_EINVAL, "amg_hip_get_level_dims: the solver was not made by amg_hip_create_tensor");
+  for (int a = 0; a < 3; ++a) dims[a] = L.dims[a];
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_level_transfer_kind(const amg_hip_solver* s, int32_t level, int32_t* kind) {
+  if (!s || !kind) return fail(AMG_HIP_EINVAL, "null argument");
+  if (level < 0 || level + 1 >= (int)s->lv.size())
+    return fail(AMG_HIP_EINVAL, "level out of range (the coarsest level has no transfers)");
+  const Level& L = s->lv[level];
+  *kind = L.tensor_stencil ? 2 : ((L.linear && s->opt.stencil_transfers) ? 1 : 0);
+  return AMG_HIP_OK;
 }
 
 amg_hip_status amg_hip_create_poisson(int32_t dim, int64_t n, int32_t n_levels,
@@ -3554,6 +3666,8 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       Level& C = s->lv[level + 1];
       if (L.linear && s->opt.stencil_transfers) {
         HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
+      } else if (L.tensor_stencil) {
+        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
       } else {
         HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st));
         const DevCsr& R = L.R_rows;
@@ -3567,6 +3681,8 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       Level& C = s->lv[level + 1];
       if (L.linear && s->opt.stencil_transfers) {
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
+      } else if (L.tensor_stencil) {
+        HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, C.u.as<double>(), L.u.as<double>(), st));
       } else {
         const DevCsr& P = L.P_rows;
         HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz, P.rowptr(),
@@ -4130,6 +4246,51 @@ amg_hip_status amg_hip_linear_restrict(int64_t n_h, int64_t n_H, const double* r
   HIP_TRY(launch_linear_restrict(n_h, n_H, dr.as<double>(), df.as<double>(), nullptr, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(f_H, df.p, sizeof(double) * n_H, hipMemcpyDeviceToHost));
+  return AMG_HIP_OK;
+}
+
+// the fine grid of a stand-alone tensor transfer: every coarsened axis needs 2 points
+static amg_hip_status tensor_transfer_args(const char* who, int32_t dim, const int64_t* dims, int64_t* n_h,
+                                           int64_t* n_H) {
+  std::string e = tensor_dims_error(dim, dims);
+  if (e.empty() && (dims[0] < 2 || dims[1] < 2 || (dim == 3 && dims[2] < 2)))
+    e = "an axis of fewer than 2 points cannot be coarsened";
+  if (!e.empty()) return fail(AMG_HIP_EINVAL, std::string(who) + ": " + e);
+  int64_t c[3];
+  tensor_coarse_dims(dim, dims, c);
+  *n_h = dims[0] * dims[1] * dims[2];
+  *n_H = c[0] * c[1] * c[2];
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_tensor_restrict(int32_t dim, const int64_t* dims_h, const double* r, double* f_H) {
+  int64_t n_h = 0, n_H = 0;
+  amg_hip_status st = tensor_transfer_args("amg_hip_tensor_restrict", dim, dims_h, &n_h, &n_H);
+  if (st != AMG_HIP_OK) return st;
+  if (!r || !f_H) return fail(AMG_HIP_EINVAL, "bad argument");
+  if ((st = need_device()) != AMG_HIP_OK) return st;
+  DevMem dr, df;
+  HIP_TRY(upload(dr, r, (size_t)n_h));
+  HIP_TRY(df.alloc(sizeof(double) * n_H));
+  HIP_TRY(launch_tensor_restrict(dim, dims_h, dr.as<double>(), df.as<double>(), nullptr, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(f_H, df.p, sizeof(double) * n_H, hipMemcpyDeviceToHost));
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_tensor_prolong_add(int32_t dim, const int64_t* dims_h, const double* u_H,
+                                          double* u_h) {
+  int64_t n_h = 0, n_H = 0;
+  amg_hip_status st = tensor_transfer_args("amg_hip_tensor_prolong_add", dim, dims_h, &n_h, &n_H);
+  if (st != AMG_HIP_OK) return st;
+  if (!u_H || !u_h) return fail(AMG_HIP_EINVAL, "bad argument");
+  if ((st = need_device()) != AMG_HIP_OK) return st;
+  DevMem dH, dh;
+  HIP_TRY(upload(dH, u_H, (size_t)n_H));
+  HIP_TRY(upload(dh, u_h, (size_t)n_h));
+  HIP_TRY(launch_tensor_prolong_add(dim, dims_h, dH.as<double>(), dh.as<double>(), nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(u_h, dh.p, sizeof(double) * n_h, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
 }
 

@@ -7,6 +7,7 @@
 #pragma once
 #include <array>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include <amg/eigen_lite.hpp>
@@ -44,8 +45,15 @@ class InterpolatorBase {
 
   const Sparse& get_P(size_t level) const { return prolong_[level]; }
   const Sparse& get_R(size_t level) const { return restrict_[level]; }
-  void set_level_to_P(size_t level, Sparse& P) { prolong_[level] = P; }
-  void set_level_to_R(size_t level, Sparse& R) { restrict_[level] = R; }
+  // (an interpolator constructed without a level count grows on demand)
+  void set_level_to_P(size_t level, Sparse& P) {
+    if (level >= prolong_.size()) prolong_.resize(level + 1);
+    prolong_[level] = P;
+  }
+  void set_level_to_R(size_t level, Sparse& R) {
+    if (level >= restrict_.size()) restrict_.resize(level + 1);
+    restrict_[level] = R;
+  }
   size_t n_operator_levels() const { return prolong_.size(); }
 };
 
@@ -92,6 +100,74 @@ class RugeStuebenInterpolator : public InterpolatorBase<EleType> {
   void make_operators(size_t, size_t, size_t) override {
     throw std::logic_error("RugeStuebenInterpolator: the operators depend on the level matrix; "
                            "AMG::Multigrid builds them");
+  }
+};
+
+// Full coarsening of an nx x ny (x nz) grid, x fastest (dof = (k ny + j) nx + i): the 1-D rule of
+// LinearInterpolator applied per axis -- NO reference counterpart (the reference halves the flat
+// index, which coarsens x only).  Every axis of length m goes to floor(m / 2) (nz = 1: a 2-D grid,
+// z is left alone), P = P1(nz) (x) P1(ny) (x) P1(nx) with P1(m) the m x floor(m / 2) matrix holding
+// 1/2, 1, 1/2 on rows 2j, 2j+1, 2j+2 (< m) of column j, R = P^T.  The level sizes differ from the
+// reference's (n + 1) / 2 - 1, so AMG::Multigrid recognises the class and lets the library build
+// the hierarchy (amg_hip_create_tensor: the matrix-free transfer kernels); get_P / get_R hold the
+// operators afterwards, and make_operators gives exactly those for a caller that wants them alone.
+template <class EleType>
+class TensorInterpolator : public InterpolatorBase<EleType> {
+  std::array<size_t, 3> dims_;
+  bool three_d_;
+
+ public:
+  TensorInterpolator(size_t nx, size_t ny, size_t nz = 1) : dims_{nx, ny, nz}, three_d_(nz > 1) {
+    if (nx < 1 || ny < 1 || nz < 1) throw std::invalid_argument("TensorInterpolator: empty grid");
+  }
+  int dim() const { return three_d_ ? 3 : 2; }
+  std::array<size_t, 3> dims() const { return dims_; }
+  // grid of `level` (level 0 = the constructor's)
+  std::array<size_t, 3> level_dims(size_t level) const {
+    std::array<size_t, 3> d = dims_;
+    for (size_t l = 0; l < level; ++l) {
+      d[0] /= 2;
+      d[1] /= 2;
+      if (three_d_) d[2] /= 2;
+    }
+    return d;
+  }
+
+  void make_operators(size_t n_h_dofs, size_t n_H_dofs, size_t level) override {
+    static const std::array<EleType, 3> weight = {EleType(0.5), EleType(1.0), EleType(0.5)};
+    const std::array<size_t, 3> d = level_dims(level), c = level_dims(level + 1);
+    if (d[0] * d[1] * d[2] != n_h_dofs || c[0] * c[1] * c[2] != n_H_dofs || n_H_dofs < 1)
+      throw std::invalid_argument("TensorInterpolator: level " + std::to_string(level) + " is a " +
+                                  std::to_string(d[0]) + " x " + std::to_string(d[1]) + " x " +
+                                  std::to_string(d[2]) + " grid, its coarse level has " +
+                                  std::to_string(c[0] * c[1] * c[2]) + " dofs");
+    const size_t tz_n = three_d_ ? 3 : 1;
+    std::vector<Eigen::Triplet<EleType>> entries;
+    entries.reserve((three_d_ ? 27 : 9) * n_H_dofs);
+    for (size_t K = 0; K < c[2]; ++K)
+      for (size_t J = 0; J < c[1]; ++J)
+        for (size_t I = 0; I < c[0]; ++I) {
+          const size_t coarse = (K * c[1] + J) * c[0] + I;
+          for (size_t tz = 0; tz < tz_n; ++tz) {
+            const size_t k = three_d_ ? 2 * K + tz : 0;
+            if (k >= d[2]) continue;
+            const EleType wz = three_d_ ? weight[tz] : EleType(1.0);
+            for (size_t ty = 0; ty < 3; ++ty) {
+              const size_t j = 2 * J + ty;
+              if (j >= d[1]) continue;
+              for (size_t tx = 0; tx < 3; ++tx) {
+                const size_t i = 2 * I + tx;
+                if (i >= d[0]) continue;
+                entries.emplace_back((k * d[1] + j) * d[0] + i, coarse, wz * weight[ty] * weight[tx]);
+              }
+            }
+          }
+        }
+    Eigen::SparseMatrix<EleType> P(n_h_dofs, n_H_dofs);
+    P.setFromTriplets(entries.begin(), entries.end());
+    Eigen::SparseMatrix<EleType> R = P.transpose();
+    this->set_level_to_P(level, P);
+    this->set_level_to_R(level, R);
   }
 };
 

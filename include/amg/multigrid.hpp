@@ -127,12 +127,23 @@ class Multigrid {
       opt.smoother_iters = 0;
     }
 
-    if (auto* rs = dynamic_cast<RugeStuebenInterpolator<EleType>*>(interpolator)) {
-      // strength-based coarsening: the library derives level sizes and operators from A
+    auto* rs = dynamic_cast<RugeStuebenInterpolator<EleType>*>(interpolator);
+    auto* tp = dynamic_cast<TensorInterpolator<EleType>*>(interpolator);
+    if (rs || tp) {
       const Sparse A0 = detail::compressed(A);
-      detail::check(amg_hip_create_rs(A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(),
-                                      b.data(), (int32_t)n_levels, (double)rs->theta(),
-                                      (int64_t)rs->min_coarse(), &opt, &handle));
+      if (rs) {
+        // strength-based coarsening: the library derives level sizes and operators from A
+        detail::check(amg_hip_create_rs(A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(),
+                                        b.data(), (int32_t)n_levels, (double)rs->theta(),
+                                        (int64_t)rs->min_coarse(), &opt, &handle));
+      } else {
+        // full coarsening of the interpolator's grid: level sizes floor(m / 2) per axis, the
+        // matrix-free tensor transfer kernels
+        const std::array<size_t, 3> d = tp->dims();
+        const int64_t dims[3] = {(int64_t)d[0], (int64_t)d[1], (int64_t)d[2]};
+        detail::check(amg_hip_create_tensor(A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(),
+                                            b.data(), tp->dim(), dims, (int32_t)n_levels, &opt, &handle));
+      }
       try {
         n_levels = (size_t)amg_hip_n_levels(handle);
         level_to_n_dofs.resize(n_levels);

@@ -251,7 +251,9 @@ amg_hip_status amg_hip_create(int64_t n, const int32_t* colptr,
 /* Same, for a user InterpolatorBase subclass (interpolator.hpp:43-44): the C++
  * layer runs make_operators(n_h, n_H, level) on the host for every level and
  * hands over P_l (n_l x n_{l+1}) and R_l (n_{l+1} x n_l), l = 0..n_levels-2,
- * as arrays of CSC triples.                                                    */
+ * as arrays of CSC triples.  n_{l+1} is the reference's (n_l + 1) / 2 - 1 unless R_l says
+ * otherwise: when its largest row index + 1 differs, that is the coarse size (operators of
+ * another coarsening, e.g. the Kronecker products of amg_hip_create_tensor built by hand).  */
 amg_hip_status amg_hip_create_custom(int64_t n, const int32_t* colptr,
                                      const int32_t* rowind, const double* val,
                                      const double* b, int32_t n_levels,
@@ -276,6 +278,37 @@ amg_hip_status amg_hip_create_rs(int64_t n, const int32_t* colptr, const int32_t
                                  const double* val, const double* b, int32_t max_levels,
                                  double theta, int64_t min_coarse, const amg_hip_options* opts,
                                  amg_hip_solver** out);
+
+/* Full coarsening of a structured grid (NO reference counterpart: the reference halves the flat
+ * index, which coarsens the x axis only; this is its LinearInterpolator, interpolator.hpp:106-141,
+ * applied per axis).  The caller supplies A on the grid dims = (nx, ny, nz), x fastest: dof =
+ * (k ny + j) nx + i, n = nx ny nz; dim = 2 needs nz = 1 and leaves it alone.  Per axis of length m
+ * the coarse length is floor(m / 2) -- not the reference's (m + 1) / 2 - 1, which for even m leaves
+ * the last grid line without a coarse point -- and P1(m) is the m x floor(m / 2) matrix whose
+ * column j holds 0.5, 1.0, 0.5 on rows 2j, 2j+1, 2j+2 (those < m).  P_l = P1(nz) (x) P1(ny) (x)
+ * P1(nx) (Kronecker products; every entry a product of powers of two, hence exact), R_l = P_l^T,
+ * A_{l+1} = R_l (A_l P_l) by the host Galerkin product in the summation order of
+ * amg_hip_create_custom on the same P / R (bit-identical level matrices).  A level is possible
+ * while every coarsened axis has at least 2 points; asking for more returns AMG_HIP_EINVAL with the
+ * level in the message, as do n != nx ny nz and dim outside {2, 3}.  opts as for
+ * amg_hip_create_custom (every smoother, host_only, the layouts), except opts->window = 1:
+ * AMG_HIP_EUNSUPPORTED.  With opts->stencil_transfers (the default) the transfers run as the
+ * matrix-free kernels K-TensorRestrict / K-TensorProlong (amg_hip_level_transfer_kind = 2), with
+ * stencil_transfers = 0 as CSR SpMV with the uploaded P / R: the same bits either way.  The
+ * patch / marching / pair / tail fusions of the flat hierarchy do not fire on these levels, and
+ * amg_hip_slab_setup refuses (there are no K-Patch levels).                                   */
+amg_hip_status amg_hip_create_tensor(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                     const double* val, const double* b, int32_t dim,
+                                     const int64_t* dims /* 3 */, int32_t n_levels,
+                                     const amg_hip_options* opts, amg_hip_solver** out);
+/* Grid of `level` (3 entries, x fastest) of a solver made by amg_hip_create_tensor; also on
+ * host_only solvers.  AMG_HIP_EINVAL for every other solver.                                    */
+amg_hip_status amg_hip_get_level_dims(const amg_hip_solver* s, int32_t level, int64_t* dims /* 3 */);
+/* How the transfers between `level` and `level` + 1 run in the V-cycle: 0 = CSR SpMV with the
+ * uploaded P / R, 1 = the reference's flat stride-2 kernels (LinearInterpolator operators with
+ * opts->stencil_transfers), 2 = the tensor-product kernels of amg_hip_create_tensor.  Also on
+ * host_only solvers (what a device solver with the same options would run).                     */
+amg_hip_status amg_hip_level_transfer_kind(const amg_hip_solver* s, int32_t level, int32_t* kind);
 
 /* The same constructor for the reference's own model problem, A = Grid::laplacian(n) and
  * b = Grid::rhs(n) (grid.hpp:88-98,108-140; dim = 3: the 7-point analogue), with the built-in
@@ -641,6 +674,16 @@ amg_hip_status amg_hip_spmv(int64_t rows, int64_t cols, const int32_t* colptr,
 amg_hip_status amg_hip_linear_restrict(int64_t n_h, int64_t n_H, const double* r,
                                        double* f_H);
 amg_hip_status amg_hip_linear_prolong_add(int64_t n_h, int64_t n_H,
+                                          const double* u_H, double* u_h);
+/* The transfers of amg_hip_create_tensor without a matrix, on host arrays: dims_h = the FINE grid
+ * (3 entries, x fastest; dim = 2: dims_h[2] = 1), every coarsened axis at least 2 points, the
+ * coarse grid floor(m / 2) per axis.  f_H = R r and u_h += P u_H, bit-identical to amg_hip_spmv
+ * with the R / P that amg_hip_get_transfer returns: K-TensorRestrict adds the 9 (27) terms of a
+ * coarse value in ascending fine index, K-TensorProlong the terms of a fine value in ascending
+ * coarse index, and every weight product is exact.                                              */
+amg_hip_status amg_hip_tensor_restrict(int32_t dim, const int64_t* dims_h /* 3 */, const double* r,
+                                       double* f_H);
+amg_hip_status amg_hip_tensor_prolong_add(int32_t dim, const int64_t* dims_h /* 3 */,
                                           const double* u_H, double* u_h);
 /* AMG::rss(A, u, b), common.hpp:17-27. */
 amg_hip_status amg_hip_rss_host(int64_t n, const int32_t* colptr,

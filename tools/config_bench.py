@@ -5,6 +5,8 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py all                                         the README table
        config_bench.py cheb                                        the Chebyshev rows
        config_bench.py line                                        the line-smoother rows (line and Jacobi legs alternate)
+       config_bench.py tensor                                      full-coarsening hierarchies next to the flat ones (legs alternate)
+       config_bench.py tensor10 <n> <levels> [csr]                 ten cycles of one tensor hierarchy (kernel traces)
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -133,6 +135,73 @@ def run_to_tol(dim, n, L, sms=("line", "jacobi"), tol=1e-8, cap=3000, reps=3, pc
             mg.close()
 
 
+TENSOR_KW = {"jacobi": dict(smoother=amg.SM_JACOBI, smoother_iters=2, omega=0.8),
+             "cheb": dict(smoother=amg.SM_CHEBYSHEV, smoother_iters=1, cheb_degree=2)}
+
+
+def run_tensor(n, L_tensor, L_flat, tol=1e-8, reps=3, flat_cap=200):
+    """The full-coarsening hierarchy (amg_hip_create_tensor; true Jacobi omega 0.8 2+2 and Chebyshev(2)
+    1+1, matrix-free transfers, and the Jacobi one again through the CSR transfer kernels) next to
+    the flat hierarchy of amg_hip_create_poisson (true Jacobi 2+2, line smoother omega 0.7 1+1) on
+    Grid::laplacian(n) / Grid::rhs(n), in ONE run with the legs alternating, `reps` repeats.  Per
+    leg: V-cycles/s, the per-cycle factor, cycles and wall milliseconds from u = 0 to ||r|| / ||r0||
+    <= tol with one rss after EVERY cycle (the flat true-Jacobi leg stops at `flat_cap` cycles, it
+    needs thousands), set-up seconds, and PCG iterations and milliseconds to tol."""
+    legs = {}
+
+    def add(name, mk):
+        t0 = time.time()
+        mg = mk()
+        mg.sync()
+        legs[name] = (mg, time.time() - t0)
+
+    add("tensor jacobi 2+2", lambda: amg.Multigrid.poisson_tensor(n, L_tensor, **TENSOR_KW["jacobi"]))
+    add("tensor cheb(2) 1+1", lambda: amg.Multigrid.poisson_tensor(n, L_tensor, **TENSOR_KW["cheb"]))
+    add("tensor jacobi 2+2, CSR transfers",
+        lambda: amg.Multigrid.poisson_tensor(n, L_tensor, stencil_transfers=False, **TENSOR_KW["jacobi"]))
+    add("flat jacobi 2+2", lambda: amg.Multigrid.poisson(n, L_flat, **KW["jacobi"]))
+    add("flat line 1+1", lambda: amg.Multigrid.poisson(n, L_flat, **KW["line"]))
+    for name, (mg, setup) in legs.items():
+        kinds = sorted({mg.level_transfer_kind(l) for l in range(mg.n_levels - 1)})
+        print(f"n={n} {name}: {mg.n_levels} levels, coarsest {mg.get_n_dofs(mg.n_levels - 1)} dofs, transfer kinds "
+              f"{kinds}, setup {setup:.2f}s, must-move {mg.cycle_must_move() / 1e6:.1f} MB/cycle", flush=True)
+        mg.vcycle(3)
+        mg.pcg(1e-2, 3)                         # warm-up: graph captures
+        mg.sync()
+    for rep_ in range(reps):
+        for name, (mg, _) in legs.items():
+            cyc = 10
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            mg.vcycle(cyc)
+            mg.sync()
+            dt = (time.perf_counter() - t0) / cyc
+            mg.zero_vec(0, "u")
+            mg.sync()
+            r0 = mg.rss()
+            cap = flat_cap if name == "flat jacobi 2+2" else 100
+            done, rel, prev = 0, 1.0, 1.0
+            t1 = time.perf_counter()
+            while done < cap and rel > tol:
+                mg.vcycle(1)
+                done += 1
+                prev, rel = rel, (mg.rss() / r0) ** 0.5
+            t2 = time.perf_counter()
+            arrived = "reached" if rel <= tol else "NOT reached"
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t3 = time.perf_counter()
+            _, it, prel = mg.pcg(tol, 1000)
+            t4 = time.perf_counter()
+            print(f"n={n} {name} rep {rep_}: {dt*1e3:.3f} ms/V-cycle = {1/dt:.1f} V-cycles/s; ||r||/||r0|| {rel:.2e} "
+                  f"after {done} cycles ({tol:g} {arrived}, rss after every cycle) in {(t2-t1)*1e3:.1f} ms; factor "
+                  f"per cycle {rel ** (1 / done):.4f}, last {rel / prev:.4f}; PCG {it} iterations to {prel:.2e} in "
+                  f"{(t4-t3)*1e3:.1f} ms (incl. copying the solution back)", flush=True)
+    for mg, _ in legs.values():
+        mg.close()
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -211,6 +280,17 @@ elif len(sys.argv) > 2 and sys.argv[1] == "block8":   # one workload at k = 8 (k
     else:
         run_block("poisson(4096, 16) jacobi 2+2", lambda: amg.Multigrid.poisson(4096, 16, **KW["jacobi"]), cycles=4,
                   reps=1, ks=(8,))
+elif len(sys.argv) > 1 and sys.argv[1] == "tensor":
+    run_tensor(4096, 10, 16)                           # the bench.py problem; coarsest 8 x 8
+    run_tensor(1024, 8, 12)
+elif len(sys.argv) > 3 and sys.argv[1] == "tensor10":
+    mg = amg.Multigrid.poisson_tensor(int(sys.argv[2]), int(sys.argv[3]), stencil_transfers=len(sys.argv) < 5,
+                                      **TENSOR_KW["jacobi"])
+    mg.vcycle(5)                                       # warm-up
+    mg.sync()
+    mg.vcycle(10)
+    mg.sync()
+    mg.close()
 elif len(sys.argv) > 1 and sys.argv[1] == "cheb":
     run(2, 4096, 16, "cheb", 20)                       # the bench.py problem, Chebyshev(2) 1+1
     run(2, 4096, 16, "jacobi", 20)                     # ... next to true Jacobi 2+2
