@@ -105,6 +105,9 @@ _SIGS = {
                                         C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_create_poisson": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(Options),
                                          C.POINTER(C.c_void_p)]),
+    "amg_hip_create_poisson_tensor": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(Options),
+                                                C.POINTER(C.c_void_p)]),
+    "amg_hip_setup_on_device": (C.c_int, [C.c_void_p, _i32p]),
     "amg_hip_create_tensor": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
                                         C.c_int32, C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_get_level_dims": (C.c_int, [C.c_void_p, C.c_int32, _i64p]),
@@ -547,10 +550,50 @@ class Multigrid:
         return self
 
     @classmethod
-    def poisson_tensor(cls, n, n_levels, dim=2, **opts):
-        """Multigrid.tensor on A = Grid::laplacian(n), b = Grid::rhs(n) (the n^dim grid)."""
-        cp, ri, v = laplacian(n, dim)
-        return cls.tensor(cp, ri, v, rhs(n, dim), (n,) * dim, n_levels, **opts)
+    def poisson_tensor(cls, n, n_levels, dim=2, device_setup=False, **opts):
+        """Multigrid.tensor on A = Grid::laplacian(n), b = Grid::rhs(n) (the n^dim grid).
+        device_setup=True: amg_hip_create_poisson_tensor, the same solver with the generator, the
+        Galerkin chain (K-TensorGalerkin) and the encoder on the device (options that need host
+        structures silently take the host constructor: see setup_on_device)."""
+        if not device_setup:
+            cp, ri, v = laplacian(n, dim)
+            return cls.tensor(cp, ri, v, rhs(n, dim), (n,) * dim, n_levels, **opts)
+        return cls._poisson_tensor_device(n, n_levels, dim, **opts)
+
+    @classmethod
+    def _poisson_tensor_device(cls, n, n_levels, dim, smoother=SM_SPGS, smoother_iters=1, omega=1.0,
+                               tolerance=1e-9, compute_error_every_n_iters=10, n_iters=100, device=-1,
+                               use_graph=True, stencil_transfers=True, layout=None, host_only=False,
+                               keep_structural_zeros=False, no_fusion=False, stream=None,
+                               fast_coarse_solve=False, keep_residual=False, exact_coarse_solve=False,
+                               exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0, window=False,
+                               host_galerkin=False, fuse_prolong=False):
+        if compute_error_every_n_iters > n_iters:
+            raise ValueError("`compute_error_every_n_iters` must be leq to `n_iters`, got "
+                             f"{compute_error_every_n_iters} and {n_iters}")
+        self = cls.__new__(cls)
+        self.tolerance, self.every, self.n_iters = tolerance, compute_error_every_n_iters, n_iters
+        o = cls._options(smoother, smoother_iters, omega, device, use_graph, stencil_transfers, layout,
+                         host_only, keep_structural_zeros, no_fusion, fuse_prolong, stream, fast_coarse_solve,
+                         host_galerkin, keep_residual, exact_coarse_solve, exact_gs, cheb_degree, cheb_lower,
+                         cheb_upper)
+        o.window = int(window)
+        h = C.c_void_p()
+        st = lib().amg_hip_create_poisson_tensor(int(dim), int(n), int(n_levels), C.byref(o), C.byref(h))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        self._h = h
+        self._device = device
+        return self
+
+    @property
+    def setup_on_device(self):
+        """1: the hierarchy was built by a device-only path (Multigrid.poisson, poisson_tensor with
+        device_setup=True), 0: by the host constructor, the silent fallbacks included."""
+        on = C.c_int32(-1)
+        _chk(lib().amg_hip_setup_on_device(self._h, C.byref(on)))
+        return on.value
 
     def level_dims(self, level):
         """(nx, ny, nz) of `level` of a Multigrid.tensor solver (amg_hip_get_level_dims)."""

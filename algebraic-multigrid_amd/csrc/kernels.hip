@@ -5018,6 +5018,190 @@ hipError_t launch_galerkin_rap(bool fill, int64_t n_h, int64_t n_H, const int32_
   return hipGetLastError();
 }
 
+// ------------------------------------------------------- K-TensorGalerkin -----
+// A_H = R (A P) for the full-coarsening pair (host_setup.hpp: tensor_P; R = P^T) from a general
+// CSR(A) on the fine grid.  P, R and A P are never stored: P(k, J) and R(I, i) are closed forms of
+// the grid coordinates (per axis 1.0 at distance 1 of 2J, 0.5 at distance 0 and 2, nothing else).
+//
+// Order (the same bits as host_setup.cpp: spgemm_csr on the Kronecker operators).  Every weight is
+// a product of powers of two, so a * w and r * (A P) are exact and only the order of the additions
+// counts.  Entry (i, J) of A P receives a_ik P(k, J) in ascending k (A's row order; a row k of P
+// holds J at most once), the first product assigned, the others added; it exists as soon as one k
+// of the row has P(k, J) != 0, whatever a_ik is (exact zeros are kept).  Entry (I, J) of R (A P)
+// receives R(I, i) (A P)(i, J) in ascending fine index i, first assigned, others added.
+//
+// Form.  The coarse columns of a fine row are not monotone in k (a row of P spreads over 2^(dim-1)
+// coarse lines), so there is no single open accumulator.  Instead one LANE owns one output entry
+// (I, J): a group of SLOTS lanes takes coarse row I, finds the box of coarse columns the rows i of
+// R's row I can reach (lane s walks fine row i_s, then a min / max butterfly over the group), and
+// lane s takes the s-th column of the box in (z, y, x) order -- ascending J, the order of the output
+// row.  It then walks the rows i ascending and their entries k ascending and accumulates its own
+// entry in registers, A P fused into the R pass.  The lanes of a group read the same entries of A
+// (one broadcast load per wave), a fine row is shared by at most 2^dim neighbouring groups, so A is
+// streamed from memory once and the only other traffic is the output.  A box of more than SLOTS
+// columns (9 of 16 in 2-D, 27 of 32 in 3-D for the 5- / 9- and 7- / 27-point rows) raises *overflow;
+// nothing is truncated, the caller takes the host product.
+__device__ __forceinline__ void tg_divmod(uint32_t k, uint32_t n, double inv_n, uint32_t* q, uint32_t* r) {
+  uint32_t qq = (uint32_t)((double)k * inv_n);  // within 1 of floor(k / n) for k < 2^31
+  int32_t rr = (int32_t)(k - qq * n);
+  if (rr < 0) { --qq; rr += (int32_t)n; }
+  else if ((uint32_t)rr >= n) { ++qq; rr -= (int32_t)n; }
+  *q = qq;
+  *r = (uint32_t)rr;
+}
+// coarse columns [l, h] of row k of P1(m): k odd: (k - 1) / 2; k even: k / 2 - 1 and k / 2, inside [0, m)
+__device__ __forceinline__ void tg_cols(uint32_t k, uint32_t m, int32_t* l, int32_t* h) {
+  if (k & 1u) {
+    *l = *h = (int32_t)((k - 1u) >> 1);
+  } else {
+    const int32_t c = (int32_t)(k >> 1);
+    *l = c >= 1 ? c - 1 : 0;
+    *h = c < (int32_t)m ? c : (int32_t)m - 1;
+  }
+}
+// P1(k, J) for a column J inside [0, m)
+__device__ __forceinline__ double tg_weight(uint32_t k, int32_t J) {
+  const int32_t t = (int32_t)k - 2 * J;
+  return t == 1 ? 1.0 : ((t == 0 || t == 2) ? 0.5 : 0.0);
+}
+template <int SLOTS, bool FILL>
+__global__ __launch_bounds__(256) void tensor_galerkin_kernel(
+    TensorGrid g, double inv_nx, double inv_ny, const int32_t* __restrict__ arp,
+    const int32_t* __restrict__ acol, const double* __restrict__ aval, int32_t* __restrict__ cnt,
+    const int32_t* __restrict__ orp, int32_t* __restrict__ ocol, double* __restrict__ oval,
+    int32_t* __restrict__ overflow) {
+  constexpr uint32_t RPB = 256u / SLOTS;  // coarse rows of a workgroup
+  const uint32_t nH = g.mx * g.my * g.mz;
+  const uint32_t s = threadIdx.x % SLOTS;
+  const uint32_t row0 = blockIdx.x * RPB + threadIdx.x / SLOTS;
+  const bool live = row0 < nH;
+  const uint32_t row = live ? row0 : nH - 1u;  // the tail lanes repeat the last row and write nothing
+  const uint32_t I = row % g.mx, qr = row / g.mx, J = qr % g.my, K = qr / g.my;
+  const uint32_t nt = g.cz ? 27u : 9u;  // fine rows of R's row, (z, y, x) ascending
+  // the box of coarse columns
+  int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
+  if (s < nt) {
+    const uint32_t ix = 2u * I + s % 3u, iy = 2u * J + (s / 3u) % 3u, iz = g.cz ? 2u * K + s / 9u : 0u;
+    if (ix < g.nx && iy < g.ny && iz < g.nz) {
+      const uint32_t i = (iz * g.ny + iy) * g.nx + ix;
+      for (int32_t p = arp[i], e = arp[i + 1]; p < e; ++p) {
+        uint32_t kx, ky, kz, q;
+        tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
+        tg_divmod(q, g.ny, inv_ny, &kz, &ky);
+        int32_t l[3], h[3];
+        tg_cols(kx, g.mx, &l[0], &h[0]);
+        tg_cols(ky, g.my, &l[1], &h[1]);
+        if (g.cz) tg_cols(kz, g.mz, &l[2], &h[2]);
+        else l[2] = h[2] = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          lo[a] = l[a] < lo[a] ? l[a] : lo[a];
+          hi[a] = h[a] > hi[a] ? h[a] : hi[a];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int d = SLOTS / 2; d >= 1; d >>= 1)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int32_t ol = __shfl_xor(lo[a], d, SLOTS), oh = __shfl_xor(hi[a], d, SLOTS);
+      lo[a] = ol < lo[a] ? ol : lo[a];
+      hi[a] = oh > hi[a] ? oh : hi[a];
+    }
+  uint32_t bx = 0, by = 0, vol = 0;
+  if (hi[0] >= lo[0]) {  // else: every row of A under this coarse row is empty
+    bx = (uint32_t)(hi[0] - lo[0] + 1);
+    by = (uint32_t)(hi[1] - lo[1] + 1);
+    const uint32_t bz = (uint32_t)(hi[2] - lo[2] + 1);
+    if (bx > (uint32_t)SLOTS || by > (uint32_t)SLOTS || bz > (uint32_t)SLOTS || bx * by * bz > (uint32_t)SLOTS) {
+      if (s == 0 && live) atomicOr(overflow, 1);
+    } else {
+      vol = bx * by * bz;
+    }
+  }
+  // this lane's entry (I, J) of R (A P)
+  bool hit = false;
+  double acc = 0.0;
+  int32_t Jx = 0, Jy = 0, Jz = 0;
+  if (s < vol) {
+    Jx = lo[0] + (int32_t)(s % bx);
+    Jy = lo[1] + (int32_t)((s / bx) % by);
+    Jz = lo[2] + (int32_t)(s / (bx * by));
+    for (uint32_t tz = 0; tz < 3; ++tz) {
+      if (!g.cz && tz > 0) break;
+      const uint32_t iz = g.cz ? 2u * K + tz : 0u;
+      if (iz >= g.nz) break;
+      const double rz = g.cz ? (tz == 1 ? 1.0 : 0.5) : 1.0;
+      for (uint32_t ty = 0; ty < 3; ++ty) {
+        const uint32_t iy = 2u * J + ty;
+        if (iy >= g.ny) break;
+        const double rzy = rz * (ty == 1 ? 1.0 : 0.5);
+        for (uint32_t tx = 0; tx < 3; ++tx) {
+          const uint32_t ix = 2u * I + tx;
+          if (ix >= g.nx) break;
+          const double r = rzy * (tx == 1 ? 1.0 : 0.5);  // R(I, i)
+          const uint32_t i = (iz * g.ny + iy) * g.nx + ix;
+          bool hit_i = false;
+          double ap = 0.0;  // (A P)(i, J)
+          for (int32_t p = arp[i], e = arp[i + 1]; p < e; ++p) {
+            uint32_t kx, ky, kz, q;
+            tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
+            tg_divmod(q, g.ny, inv_ny, &kz, &ky);
+            double w = tg_weight(kx, Jx) * tg_weight(ky, Jy);
+            w = g.cz ? w * tg_weight(kz, Jz) : ((int32_t)kz == Jz ? w : 0.0);
+            if (w != 0.0) {
+              if (FILL) {
+                const double t = aval[p] * w;
+                ap = hit_i ? ap + t : t;  // first product: assign
+              }
+              hit_i = true;
+            }
+          }
+          if (hit_i) {
+            if (FILL) {
+              const double t = r * ap;
+              acc = hit ? acc + t : t;
+            }
+            hit = true;
+          }
+        }
+      }
+    }
+  }
+  const unsigned long long ball = __ballot(hit);
+  const uint32_t g0 = ((threadIdx.x & 63u) / SLOTS) * SLOTS;
+  const unsigned long long mine = (ball >> g0) & (SLOTS == 64 ? ~0ull : ((1ull << SLOTS) - 1ull));
+  if (!FILL) {
+    if (s == 0 && live) cnt[row] = (int32_t)__popcll(mine);
+  } else if (hit && live) {
+    const int32_t at = orp[row] + (int32_t)__popcll(mine & ((1ull << s) - 1ull));
+    ocol[at] = (int32_t)(((uint32_t)Jz * g.my + (uint32_t)Jy) * g.mx + (uint32_t)Jx);
+    oval[at] = acc;
+  }
+}
+hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], const int32_t* arp,
+                                  const int32_t* acol, const double* aval, int32_t* cnt,
+                                  const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
+                                  hipStream_t st) {
+  TensorGrid g;
+  if (!tensor_grid(dim, dims, &g)) return hipErrorInvalidValue;
+  const uint32_t nH = g.mx * g.my * g.mz;
+  const double inv_nx = 1.0 / (double)g.nx, inv_ny = 1.0 / (double)g.ny;
+#define TG_LAUNCH(SLOTS, FILL)                                                                        \
+  hipLaunchKernelGGL((tensor_galerkin_kernel<SLOTS, FILL>), dim3((nH + 256u / SLOTS - 1u) / (256u / SLOTS)), \
+                     dim3(256), 0, st, g, inv_nx, inv_ny, arp, acol, aval, cnt, orp, ocol, oval, overflow)
+  if (dim == 3) {
+    if (fill) TG_LAUNCH(32, true);
+    else TG_LAUNCH(32, false);
+  } else {
+    if (fill) TG_LAUNCH(16, true);
+    else TG_LAUNCH(16, false);
+  }
+#undef TG_LAUNCH
+  return hipGetLastError();
+}
+
 // --------------------------------------------------------------- K-Setup ------
 // Setup on the device end to end: the Grid generators
 // (grid.hpp:88-98 and the 7-point analogue) as kernels, and the dictionary encoder of the

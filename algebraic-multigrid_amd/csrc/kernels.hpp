@@ -432,6 +432,16 @@ hipError_t launch_galerkin_ap(bool fill, int64_t n_h, int64_t n_H, const int32_t
 hipError_t launch_galerkin_rap(bool fill, int64_t n_h, int64_t n_H, const int32_t* prp,
                                const int32_t* pcol, const double* pval, int32_t* cnt,
                                const int32_t* orp, int32_t* ocol, double* oval, hipStream_t st);
+// K-TensorGalerkin (setup): A_H = R (A P) for the full-coarsening pair of the fine grid `dims`
+// (host_setup.hpp: tensor_P, R = P^T) from a general CSR(A) on that grid, without P, R or A P in
+// memory; count pass (cnt[coarse row]) / fill pass (orp = scanned counts).  Same entry order and
+// bits as galerkin_csr on the Kronecker operators, structural zeros included.  *overflow (zeroed
+// by the caller) is set when a coarse row reaches more coarse columns than a lane group holds
+// (16 in 2-D, 32 in 3-D): the result is then unusable and the caller takes the host product.
+hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], const int32_t* arp,
+                                  const int32_t* acol, const double* aval, int32_t* cnt,
+                                  const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
+                                  hipStream_t st);
 
 // K-Setup: Grid generators and the dictionary encoder on the device (kernels.hip)
 hipError_t launch_laplacian_count(int dim, int64_t n, int64_t n_last, int64_t N, int32_t* cnt, hipStream_t st);

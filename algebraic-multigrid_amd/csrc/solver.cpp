@@ -180,6 +180,44 @@ hipError_t device_galerkin(const DevCsr& A, int64_t n_H, DevCsr* AH, Sparse* hos
   return hipSuccess;
 }
 
+// Setup on the device (K-TensorGalerkin): AH = R (A P) for the full-coarsening pair of the grid
+// `dims` from CSR(A) on the device.  *ok = false: a coarse row reaches more columns than the
+// kernel's lane group holds; hipErrorInvalidValue: the product is beyond int32 indexing.  Either
+// way the caller takes the host path.
+hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], int64_t n_H, DevCsr* AH,
+                                  bool* ok) {
+  *ok = false;
+  hipError_t e;
+  DevMem cnt, bsum, total, ovf;
+  if ((e = cnt.alloc(sizeof(int32_t) * (n_H + 1))) != hipSuccess) return e;
+  if ((e = bsum.alloc(sizeof(int64_t) * ((n_H + 1023) / 1024 + 1))) != hipSuccess) return e;
+  if ((e = total.alloc(sizeof(int64_t))) != hipSuccess) return e;
+  if ((e = ovf.alloc(sizeof(int32_t))) != hipSuccess) return e;
+  if ((e = hipMemset(ovf.p, 0, sizeof(int32_t))) != hipSuccess) return e;
+  if ((e = launch_tensor_galerkin(false, dim, dims, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
+                                  nullptr, nullptr, ovf.as<int32_t>(), nullptr)) != hipSuccess)
+    return e;
+  int32_t over = 0;
+  if ((e = hipMemcpy(&over, ovf.p, sizeof(int32_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  if (over) return hipSuccess;
+  if ((e = AH->ptr.alloc(sizeof(int32_t) * (n_H + 1))) != hipSuccess) return e;
+  if ((e = launch_exclusive_scan(n_H, cnt.as<int32_t>(), AH->ptr.as<int32_t>(), bsum.as<int64_t>(),
+                                 total.as<int64_t>(), nullptr)) != hipSuccess)
+    return e;
+  int64_t nnz = 0;
+  if ((e = hipMemcpy(&nnz, total.p, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  if (nnz >= ((int64_t)1 << 31) - 1) return hipErrorInvalidValue;
+  if ((e = AH->idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
+  if ((e = AH->val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
+  if ((e = launch_tensor_galerkin(true, dim, dims, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
+                                  AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr)) != hipSuccess)
+    return e;
+  AH->n_rows = AH->n_cols = n_H;
+  AH->nnz = nnz;
+  *ok = true;
+  return hipSuccess;
+}
+
 // C = A B on the device (general CSR operands: custom interpolators), count -> scan -> fill.
 // *ok = false: a row of A is longer than the kernel's merge width, or an index overflow:
 // the caller takes the host product.
@@ -1157,6 +1195,7 @@ struct amg_hip_solver {
   hipStream_t stream = nullptr;
   bool own_stream = true;
   std::vector<Level> lv;
+  bool device_setup = false;  // the hierarchy was built by build_poisson_device (amg_hip_setup_on_device)
   CoarseOnDev coarse;  // coarsest level factor
   DevMem scratch;   // 1024 doubles + 1 result
   DevMem pcg_x, pcg_p, pcg_q, pcg_b;  // PCG work vectors (allocated on first use)
@@ -1203,6 +1242,13 @@ double mat_bytes(const DevMat& A) {
 
 // ---- smoother on one level --------------------------------------------------
 amg_hip_status enqueue_multicolor(amg_hip_solver* s, Level& L, hipStream_t st, bool again);
+
+// full coarsening: level l (grid d) has an axis that cannot be coarsened, so level l + 1 is not possible
+std::string tensor_level_error(int l, const int64_t d[3]) {
+  return "level " + std::to_string(l + 1) + " is not possible: level " + std::to_string(l) + " is a " +
+         std::to_string(d[0]) + " x " + std::to_string(d[1]) + " x " + std::to_string(d[2]) +
+         " grid and an axis of fewer than 2 points cannot be coarsened; reduce `n_levels`";
+}
 
 // phase 0: u_l is arbitrary.  phase 1: u_l is known to be zero (pre-smoothing of a
 // coarse level, multigrid.hpp:278).  phase 2: u_l still lacks the correction
@@ -2376,11 +2422,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     } else if (tensor_dim) {
       // full coarsening: every axis m -> floor(m / 2), possible while every coarsened axis has 2 points
       if (L.dims[0] < 2 || L.dims[1] < 2 || (tensor_dim == 3 && L.dims[2] < 2))
-        return fail(AMG_HIP_EINVAL, "level " + std::to_string(l + 1) + " is not possible: level " +
-                                        std::to_string(l) + " is a " + std::to_string(L.dims[0]) + " x " +
-                                        std::to_string(L.dims[1]) + " x " + std::to_string(L.dims[2]) +
-                                        " grid and an axis of fewer than 2 points cannot be coarsened; "
-                                        "reduce `n_levels`");
+        return fail(AMG_HIP_EINVAL, tensor_level_error(l, L.dims));
       Level& C = s->lv[l + 1];
       C.tdim = tensor_dim;
       tensor_coarse_dims(tensor_dim, L.dims, C.dims);
@@ -2644,7 +2686,7 @@ void rhs_threads(int dim, int64_t n, double* b, int nt, int64_t d0 = 0, int64_t 
 // [unit0, unit1): the grid lines (2-D) / x-y planes (3-D) of a window solver, else unit1 < 0.
 amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const amg_hip_options* opts,
                                     amg_hip_solver** out, bool* unsupported, int64_t unit0 = 0,
-                                    int64_t unit1 = -1) {
+                                    int64_t unit1 = -1, bool tensor = false) {
   *unsupported = true;
   amg_hip_options o;
   if (opts) o = *opts;
@@ -2659,6 +2701,8 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       o.smoother == AMG_HIP_SM_MULTICOLOR_GS || (lex && (o.exact_gs || N <= GS_SCAN_MIN_ROWS)) ||
       n_levels < 2 || N >= ((int64_t)1 << 28))
     return AMG_HIP_OK;
+  // full coarsening: the lexicographic and the line smoothers build through the host constructor
+  if (tensor && (lex || o.smoother == AMG_HIP_SM_LINE_JACOBI)) return AMG_HIP_OK;
   if (o.smoother_iters < 0 || (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0)) ||
       o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_JACOBI)
     return AMG_HIP_OK;  // the host path words the argument error
@@ -2736,10 +2780,15 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
   HIP_TRY(stats.alloc(sizeof(int32_t) * 2));
   if (cheb) HIP_TRY(gbound.alloc(sizeof(uint64_t) * 2));
   const bool prune = !o.keep_structural_zeros;
+  int64_t tdims[3] = {n, n, dim == 3 ? n : 1};  // full coarsening: the grid of the current level
   for (int l = 0; l < n_levels; ++l) {
     Level& L = s->lv[l];
     L.n = cur.n_rows;
     L.nnz_struct = cur.nnz;
+    if (tensor) {
+      L.tdim = dim;
+      for (int a = 0; a < 3; ++a) L.dims[a] = tdims[a];
+    }
     if (cheb) {  // Gershgorin bound of D^-1 A on the device CSR (K-Setup: gershgorin_kernel)
       HIP_TRY(launch_gershgorin(L.n, cur.rowptr(), cur.col(), cur.v(), gbound.as<uint64_t>(), nullptr));
       uint64_t g[2];
@@ -2829,6 +2878,23 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       if (L.A_csc.ptr.empty()) L.A_dev = std::move(cur);
       break;
     }
+    DevCsr next;
+    if (tensor) {  // every axis m -> floor(m / 2), matrix-free transfers, K-TensorGalerkin
+      if (L.dims[0] < 2 || L.dims[1] < 2 || (dim == 3 && L.dims[2] < 2))
+        return fail(AMG_HIP_EINVAL, tensor_level_error(l, L.dims));
+      tensor_coarse_dims(dim, L.dims, tdims);
+      L.tensor = true;
+      L.tensor_stencil = true;  // o.stencil_transfers is set and N < 2^28
+      L.n_coarse = tdims[0] * tdims[1] * tdims[2];
+      bool ok_g = false;
+      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.n_coarse, &next, &ok_g);
+      if (ge == hipErrorInvalidValue || (ge == hipSuccess && !ok_g)) {
+        if (timing) std::fprintf(stderr, "amg_hip device setup: Galerkin product of level %d exceeds %s -> host path\n", l,
+                                 ge == hipSuccess ? "the kernel's columns per coarse row" : "int32 indexing");
+        return AMG_HIP_OK;
+      }
+      HIP_TRY(ge);
+    } else {
     const int64_t n_H = coarse_dofs(L.n);  // multigrid.hpp:214
     if (n_H < 1)
       return fail(AMG_HIP_EINVAL, "level " + std::to_string(l + 1) +
@@ -2836,7 +2902,6 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
     L.lazy_linear = true;
     L.n_coarse = n_H;
     L.linear = true;
-    DevCsr next;
     {
       const hipError_t ge = device_galerkin(cur, n_H, &next, nullptr);
       if (ge == hipErrorInvalidValue) {  // an intermediate product beyond int32 indices: host path
@@ -2844,6 +2909,7 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
         return AMG_HIP_OK;
       }
       HIP_TRY(ge);
+    }
     }
     if (L.A_csc.ptr.empty()) L.A_dev = std::move(cur);
     cur = std::move(next);
@@ -2867,6 +2933,7 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
   }
   compute_bytes(s.get());
   HIP_TRY(hipDeviceSynchronize());
+  s->device_setup = true;
   *unsupported = false;
   *out = s.release();
   return AMG_HIP_OK;
@@ -3336,6 +3403,49 @@ amg_hip_status amg_hip_create_poisson(int32_t dim, int64_t n, int32_t n_levels,
   std::vector<double> b((size_t)A.n_outer);
   rhs_threads(dim, n, b.data(), host_threads());
   return amg_hip_create(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, opts, out);
+}
+
+amg_hip_status amg_hip_create_poisson_tensor(int32_t dim, int64_t n, int32_t n_levels,
+                                             const amg_hip_options* opts, amg_hip_solver** out) {
+  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
+  *out = nullptr;
+  if (dim != 2 && dim != 3) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: `dim` must be 2 or 3");
+  if (n < 2) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: `n` must be at least 2");
+  if (n >= ((int64_t)1 << 31) / n / (dim == 3 ? n : 1))
+    return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: the grid has 2^31 points or more");
+  if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
+  if (opts && opts->window)
+    return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_tensor: window solvers (opt.window) coarsen the "
+                                      "flat index; a full-coarsening hierarchy is not sharded");
+  int64_t dims[3] = {n, n, dim == 3 ? n : 1};
+  {  // the levels the rule allows, before the device is touched
+    int64_t d[3] = {dims[0], dims[1], dims[2]};
+    for (int l = 0; l + 1 < n_levels; ++l) {
+      if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
+      int64_t c[3];
+      tensor_coarse_dims(dim, d, c);
+      for (int a = 0; a < 3; ++a) d[a] = c[a];
+    }
+  }
+  if (opts && opts->smoother == AMG_HIP_SM_CHEBYSHEV) {
+    const std::string e = cheb_options_error(opts->cheb_degree, opts->cheb_lower, opts->cheb_upper);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+  }
+  bool unsupported = true;
+  amg_hip_status r = build_poisson_device(dim, n, n_levels, opts, out, &unsupported, 0, -1, true);
+  if (r != AMG_HIP_OK || !unsupported) return r;
+  // options that need host structures: generate on the host and take the host constructor
+  Sparse A = laplacian(dim, n);
+  std::vector<double> b((size_t)A.n_outer);
+  rhs_threads(dim, n, b.data(), host_threads());
+  return amg_hip_create_tensor(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims,
+                               n_levels, opts, out);
+}
+
+amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on) {
+  if (!s || !on) return fail(AMG_HIP_EINVAL, "null argument");
+  *on = s->device_setup ? 1 : 0;
+  return AMG_HIP_OK;
 }
 
 amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t unit_begin, int64_t unit_end,

@@ -323,6 +323,33 @@ amg_hip_status amg_hip_level_transfer_kind(const amg_hip_solver* s, int32_t leve
 amg_hip_status amg_hip_create_poisson(int32_t dim, int64_t n, int32_t n_levels,
                                       const amg_hip_options* opts, amg_hip_solver** out);
 
+/* amg_hip_create_tensor for A = Grid::laplacian(n), b = Grid::rhs(n) on the n^dim grid (dim = 2
+ * or 3, every axis n -> floor(n / 2) per level) with the SETUP ON THE DEVICE: the generator, the
+ * Galerkin chain (K-TensorGalerkin: A_H = R (A P) from CSR(A) with neither P, R nor A P in memory,
+ * in the summation order of the host product), the dictionary encoder, the diagonal, the symmetry
+ * check and the Chebyshev bounds are kernels.  The solver is indistinguishable from
+ * amg_hip_create_tensor on the host-generated arrays with the same options: levels, dims, level
+ * matrices bit for bit (structural zeros included), transfers (rebuilt when a getter asks),
+ * transfer kind 2, bounds, right-hand side (evaluated on the host threads: libm's exp()), and
+ * every cycle, apply, PCG and block call.  No host copy of a level matrix is made unless a getter,
+ * the block cycle or a panel upload asks for one: levels that do not take the dictionary (the
+ * 27-entry rows of the 3-D coarse levels, a level that is not bitwise symmetric) go to the host
+ * once, and the coarsest operator is factored there.  Device path: true Jacobi and Chebyshev.
+ * Everything else silently takes the host path (generate, then amg_hip_create_tensor): host_only,
+ * host_galerkin, stencil_transfers = 0, fuse_prolong, a layout other than AUTO / DICT, multicolour
+ * GS, the lexicographic smoothers, the line smoother, n^dim >= 2^28, a product beyond int32
+ * indexing.  amg_hip_setup_on_device tells the two apart.
+ * AMG_HIP_EINVAL: dim outside {2, 3}, n < 2, more levels than the rule allows (the level in the
+ * message, worded as by amg_hip_create_tensor), bad Chebyshev options; AMG_HIP_EUNSUPPORTED:
+ * opts->window = 1.  These checks come before the device is touched.                            */
+amg_hip_status amg_hip_create_poisson_tensor(int32_t dim, int64_t n, int32_t n_levels,
+                                             const amg_hip_options* opts, amg_hip_solver** out);
+/* *on = 1: the hierarchy was built by a device-only path (amg_hip_create_poisson,
+ * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor when they did not fall back),
+ * 0: by the host constructor -- every other entry point and the silent fallbacks.  Also on
+ * host_only solvers (0).                                                                        */
+amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on);
+
 void amg_hip_destroy(amg_hip_solver* s); /* ~Multigrid, multigrid.hpp:135 */
 
 /* One V-cycle, multigrid.hpp:263-305 (including the smoothing + residual on

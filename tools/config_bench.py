@@ -7,6 +7,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py line                                        the line-smoother rows (line and Jacobi legs alternate)
        config_bench.py tensor                                      full-coarsening hierarchies next to the flat ones (legs alternate)
        config_bench.py tensor10 <n> <levels> [csr]                 ten cycles of one tensor hierarchy (kernel traces)
+       config_bench.py tensor-setup [<dim> <n> <levels>]           set-up seconds of the full-coarsening hierarchy, host and device construction alternating
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -202,6 +203,28 @@ def run_tensor(n, L_tensor, L_flat, tol=1e-8, reps=3, flat_cap=200):
         mg.close()
 
 
+def run_tensor_setup(dim, n, L, reps=3):
+    """Set-up seconds of the full-coarsening Poisson hierarchy: Multigrid.poisson_tensor through the
+    host constructor (generate on the host, amg_hip_create_tensor) and through the device set-up
+    (amg_hip_create_poisson_tensor), alternating in one process, `reps` repeats.  Wall time around
+    the constructor, closed by a device synchronise; with AMG_HIP_TIMING set the library writes
+    its laps to stderr."""
+    best = {}
+    for rep_ in range(reps):
+        for name, dev in (("host", False), ("device", True)):
+            t0 = time.perf_counter()
+            mg = amg.Multigrid.poisson_tensor(n, L, dim=dim, device_setup=dev, **TENSOR_KW["jacobi"])
+            mg.sync()
+            dt = time.perf_counter() - t0
+            assert mg.setup_on_device == int(dev)
+            best[name] = min(best.get(name, dt), dt)
+            print(f"tensor-setup {n}^{dim} {L} levels, {name} rep {rep_}: {dt:.3f} s "
+                  f"(setup_on_device {mg.setup_on_device}, coarsest {mg.get_n_dofs(L - 1)} dofs)", flush=True)
+            mg.close()
+    print(f"tensor-setup {n}^{dim} {L} levels: best host {best['host']:.3f} s, best device {best['device']:.3f} s, "
+          f"ratio {best['host'] / best['device']:.1f}", flush=True)
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -283,6 +306,14 @@ elif len(sys.argv) > 2 and sys.argv[1] == "block8":   # one workload at k = 8 (k
 elif len(sys.argv) > 1 and sys.argv[1] == "tensor":
     run_tensor(4096, 10, 16)                           # the bench.py problem; coarsest 8 x 8
     run_tensor(1024, 8, 12)
+elif len(sys.argv) > 1 and sys.argv[1] == "tensor-setup":
+    os.environ.setdefault("AMG_HIP_TIMING", "1")
+    if len(sys.argv) > 4:
+        run_tensor_setup(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
+    else:
+        run_tensor_setup(2, 1024, 8)
+        run_tensor_setup(2, 4096, 10)
+        run_tensor_setup(3, 256, 7)
 elif len(sys.argv) > 3 and sys.argv[1] == "tensor10":
     mg = amg.Multigrid.poisson_tensor(int(sys.argv[2]), int(sys.argv[3]), stencil_transfers=len(sys.argv) < 5,
                                       **TENSOR_KW["jacobi"])
