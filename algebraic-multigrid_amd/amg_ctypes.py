@@ -110,6 +110,9 @@ _SIGS = {
     "amg_hip_setup_on_device": (C.c_int, [C.c_void_p, _i32p]),
     "amg_hip_create_tensor": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
                                         C.c_int32, C.POINTER(Options), C.POINTER(C.c_void_p)]),
+    "amg_hip_create_tensor_dev": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int32, _i64p, C.c_int32, C.POINTER(Options),
+                                            C.POINTER(C.c_void_p)]),
     "amg_hip_get_level_dims": (C.c_int, [C.c_void_p, C.c_int32, _i64p]),
     "amg_hip_level_transfer_kind": (C.c_int, [C.c_void_p, C.c_int32, _i32p]),
     "amg_hip_tensor_restrict": (C.c_int, [C.c_int32, _i64p, _f64p, _f64p]),
@@ -542,6 +545,79 @@ class Multigrid:
         h = C.c_void_p()
         st = lib().amg_hip_create_tensor(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
                                          d3.ctypes.data_as(_i64p), int(n_levels), C.byref(o), C.byref(h))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        self._h = h
+        self._device = device
+        return self
+
+    @classmethod
+    def tensor_dev(cls, crow, col, val, b, dims, n_levels, smoother=SM_SPGS, smoother_iters=1, omega=1.0,
+                   tolerance=1e-9, compute_error_every_n_iters=10, n_iters=100, device=-1, use_graph=True,
+                   stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
+                   no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
+                   exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
+                   window=False, host_galerkin=False, fuse_prolong=False):
+        """Multigrid.tensor for a matrix that sits on the device, with the set-up on the device
+        (amg_hip_create_tensor_dev).  A is in CSR: crow (n + 1 int32 row pointers), col (int32,
+        ascending inside a row), val (float64), and b (n float64), each a contiguous 1-D torch tensor
+        on the GPU (e.g. the crow_indices() / col_indices() / values() of a torch CSR tensor, cast to
+        int32) or a numpy array, which is uploaded through torch first.  The arrays are copied.
+        Options that need host structures silently take the host constructor: see setup_on_device."""
+        if compute_error_every_n_iters > n_iters:
+            raise ValueError("`compute_error_every_n_iters` must be leq to `n_iters`, got "
+                             f"{compute_error_every_n_iters} and {n_iters}")
+        import torch
+        want = (("crow", crow, torch.int32, np.int32), ("col", col, torch.int32, np.int32),
+                ("val", val, torch.float64, np.float64), ("b", b, torch.float64, np.float64))
+        given = []
+        for name, a, tdt, ndt in want:
+            if isinstance(a, np.ndarray):
+                if a.dtype != ndt:
+                    raise ValueError(f"{name}: expected dtype {np.dtype(ndt).name}, got {a.dtype}")
+            elif isinstance(a, torch.Tensor):
+                if a.dtype != tdt:
+                    raise ValueError(f"{name}: expected dtype {tdt}, got {a.dtype}")
+                if not a.is_contiguous():
+                    raise ValueError(f"{name}: expected a contiguous tensor")
+            else:
+                raise ValueError(f"{name}: expected a torch tensor or a numpy array, got {type(a).__name__}")
+            if a.ndim != 1:
+                raise ValueError(f"{name}: expected a 1-D array, got {a.ndim} dimensions")
+            given.append(a)
+        n = given[0].shape[0] - 1
+        if n != given[3].shape[0]:
+            raise ValueError("`A` and `b` must have the same number of degrees of freedom, "
+                             f"got {n} and {given[3].shape[0]}")
+        if given[1].shape[0] != given[2].shape[0]:
+            raise ValueError(f"`col` and `val` must have the same length, got {given[1].shape[0]} and "
+                             f"{given[2].shape[0]}")
+        dim, d3 = _dims3(dims)
+        o = cls._options(smoother, smoother_iters, omega, device, use_graph, stencil_transfers, layout,
+                         host_only, keep_structural_zeros, no_fusion, fuse_prolong, stream, fast_coarse_solve,
+                         host_galerkin, keep_residual, exact_coarse_solve, exact_gs, cheb_degree, cheb_lower,
+                         cheb_upper)
+        o.window = int(window)
+        if device_count() > 0:
+            tdev = torch.device("cuda", device if device >= 0 else torch.cuda.current_device())
+            dev = []
+            for (name, _, _, _), a in zip(want, given):
+                if isinstance(a, np.ndarray):
+                    a = torch.from_numpy(np.ascontiguousarray(a)).to(tdev)
+                elif a.device != tdev:
+                    raise ValueError(f"{name}: expected a tensor on {tdev}, got {a.device}")
+                dev.append(a)
+            torch.cuda.current_stream(tdev).synchronize()  # the tensors are torch's work; the copy is the solver's
+            ptrs = [C.c_void_p(a.data_ptr() or 8) for a in dev]  # an empty tensor has no storage: never read
+        else:  # no device: the library words the refusal (after its argument checks); nothing is dereferenced
+            dev, ptrs = [], [C.c_void_p(8)] * 4
+        self = cls.__new__(cls)
+        self.tolerance, self.every, self.n_iters = tolerance, compute_error_every_n_iters, n_iters
+        h = C.c_void_p()
+        st = lib().amg_hip_create_tensor_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
+                                             d3.ctypes.data_as(_i64p), int(n_levels), C.byref(o), C.byref(h))
+        del dev
         if st == EINVAL:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)

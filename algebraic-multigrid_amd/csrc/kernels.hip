@@ -5374,6 +5374,229 @@ hipError_t launch_dict_types(int64_t n, const uint64_t* codes, int words, const 
   return hipGetLastError();
 }
 
+// K-CsrCheck: the argument check of a caller's device CSR arrays (amg_hip_create_tensor_dev).  One lane
+// per row; *first_bad (initialised to INT32_MAX) = smallest offending row.  nnz is the caller's
+// rowptr[n], read beforehand: a lane reads col only inside [0, nnz), and only when its own pair of
+// row pointers lies in that range in ascending order, whatever the other rows hold.
+__global__ __launch_bounds__(256) void csr_check_kernel(int64_t n, int64_t nnz, const int32_t* __restrict__ rowptr,
+                                                        const int32_t* __restrict__ col,
+                                                        int32_t* __restrict__ first_bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t a = rowptr[i], b = rowptr[i + 1];
+  bool bad = (i == 0 && a != 0) || a < 0 || b < a || b > nnz;
+  if (!bad) {
+    int64_t prev = -1;
+    for (int64_t p = a; p < b; ++p) {
+      const int64_t c = col[p];
+      if (c <= prev || c >= n) { bad = true; break; }  // c < 0 included: prev starts at -1
+      prev = c;
+    }
+  }
+  if (bad) atomicMin(first_bad, (int32_t)i);
+}
+hipError_t launch_csr_check(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int32_t* first_bad,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(csr_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, nnz, rowptr, col,
+                     first_bad);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- K-SellPack ----
+// The panel layouts of upload_mat (SELL-64, or pruned CSR) from a CSR matrix that already sits on
+// the device.  Pass 1 (sell_count_kernel), one lane per row, one wave per 64-row panel: kept[r] =
+// entries of row r that stay (exact zeros dropped when prune), pslots[p] = 64 * longest kept row of
+// panel p (scanned into soff by the caller), stats[0] = longest kept row, stats[1] = 1 when a kept
+// entry lies farther than 32767 columns from its row (no 16-bit relative indices), stats[2] = most
+// kept entries in a 256-row block (K-CSR's LDS staging).  Pass 2 is sell_fill_kernel or
+// csr_compact_kernel, after the caller has chosen the layout by upload_mat's rule.
+__global__ __launch_bounds__(256) void sell_count_kernel(int64_t n, const int32_t* __restrict__ rowptr,
+                                                         const int32_t* __restrict__ col,
+                                                         const double* __restrict__ val, int prune,
+                                                         int32_t* __restrict__ kept, int32_t* __restrict__ pslots,
+                                                         int32_t* __restrict__ stats) {
+  __shared__ int32_t wsum[4];
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int len = 0;
+  bool far = false;
+  if (r < n) {
+    for (int32_t p = rowptr[r]; p < rowptr[r + 1]; ++p) {
+      if (prune && val[p] == 0.0) continue;
+      ++len;
+      const int64_t d = (int64_t)col[p] - r;
+      far = far || d < -32767 || d > 32767;
+    }
+    kept[r] = len;
+  }
+  int w = len, sum = len;
+  for (int o = 32; o > 0; o >>= 1) {  // every lane of the wave is here: rows past n count 0
+    w = max(w, __shfl_xor(w, o, 64));
+    sum += __shfl_xor(sum, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    wsum[wave] = sum;
+    const int64_t p = (int64_t)blockIdx.x * 4 + wave;
+    if (p * 64 < n) {
+      pslots[p] = w * 64;
+      atomicMax(&stats[0], w);
+    }
+  }
+  if (far) atomicOr(&stats[1], 1);
+  __syncthreads();
+  if (threadIdx.x == 0) atomicMax(&stats[2], wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+}
+__global__ __launch_bounds__(256) void sell_soff_kernel(int64_t np1, const int32_t* __restrict__ off32,
+                                                        int64_t* __restrict__ soff) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p < np1) soff[p] = off32[p];
+}
+// One lane per row, the padding rows of the last panel included: for every j the wave stores 64
+// consecutive slots (base + j * 64) and reads its rows with a stride of one row.
+template <bool IDX16>
+__global__ __launch_bounds__(256) void sell_fill_kernel(int64_t n, const int32_t* __restrict__ rowptr,
+                                                        const int32_t* __restrict__ col,
+                                                        const double* __restrict__ val, int prune,
+                                                        const int64_t* __restrict__ soff, void* __restrict__ scol,
+                                                        double* __restrict__ sval) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t p = r >> 6;
+  if (p * 64 >= n) return;
+  const int64_t base = soff[p] + (r & 63);
+  const int64_t w = (soff[p + 1] - soff[p]) >> 6;
+  int16_t* c16 = reinterpret_cast<int16_t*>(scol);
+  int32_t* c32 = reinterpret_cast<int32_t*>(scol);
+  int64_t j = 0;
+  if (r < n) {
+    for (int32_t q = rowptr[r]; q < rowptr[r + 1] && j < w; ++q) {
+      const double v = val[q];
+      if (prune && v == 0.0) continue;
+      const int32_t c = col[q];
+      if (IDX16) c16[base + j * 64] = (int16_t)((int64_t)c - r);
+      else c32[base + j * 64] = c;
+      sval[base + j * 64] = v;
+      ++j;
+    }
+  }
+  for (; j < w; ++j) {
+    if (IDX16) c16[base + j * 64] = (int16_t)-32768;
+    else c32[base + j * 64] = -1;
+    sval[base + j * 64] = 0.0;
+  }
+}
+// optr = exclusive scan of kept: row r's kept entries in their order
+__global__ __launch_bounds__(256) void csr_compact_kernel(int64_t n, const int32_t* __restrict__ rowptr,
+                                                          const int32_t* __restrict__ col,
+                                                          const double* __restrict__ val, int prune,
+                                                          const int32_t* __restrict__ optr, int32_t* __restrict__ ocol,
+                                                          double* __restrict__ oval) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  int32_t o = optr[r];
+  const int32_t oe = optr[r + 1];
+  for (int32_t q = rowptr[r]; q < rowptr[r + 1] && o < oe; ++q) {
+    const double v = val[q];
+    if (prune && v == 0.0) continue;
+    ocol[o] = col[q];
+    oval[o] = v;
+    ++o;
+  }
+}
+hipError_t launch_sell_count(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val, bool prune,
+                             int32_t* kept, int32_t* pslots, int32_t* stats, hipStream_t st) {
+  hipLaunchKernelGGL(sell_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, rowptr, col, val,
+                     prune ? 1 : 0, kept, pslots, stats);
+  return hipGetLastError();
+}
+hipError_t launch_sell_fill(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val, bool prune,
+                            const int32_t* off32, int64_t* soff, bool idx16, void* scol, double* sval,
+                            hipStream_t st) {
+  const int64_t np = (n + 63) / 64;
+  hipLaunchKernelGGL(sell_soff_kernel, dim3((unsigned)((np + 1 + 255) / 256)), dim3(256), 0, st, np + 1, off32, soff);
+  const unsigned grid = (unsigned)((np * 64 + 255) / 256);
+  if (idx16)
+    hipLaunchKernelGGL(sell_fill_kernel<true>, dim3(grid), dim3(256), 0, st, n, rowptr, col, val, prune ? 1 : 0, soff,
+                       scol, sval);
+  else
+    hipLaunchKernelGGL(sell_fill_kernel<false>, dim3(grid), dim3(256), 0, st, n, rowptr, col, val, prune ? 1 : 0, soff,
+                       scol, sval);
+  return hipGetLastError();
+}
+hipError_t launch_csr_compact(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val, bool prune,
+                              const int32_t* optr, int32_t* ocol, double* oval, hipStream_t st) {
+  hipLaunchKernelGGL(csr_compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, rowptr, col, val,
+                     prune ? 1 : 0, optr, ocol, oval);
+  return hipGetLastError();
+}
+
+// --------------------------------------------------------------- K-Transpose ----
+// CSR(A) -> CSC(A) of a square matrix on the device: count per column (atomicAdd), scan (the
+// caller), scatter through per-column cursors, then one lane per column sorts its entries by row
+// index, which makes the result that of the host transpose whatever order the atomics ran in (row
+// indices are unique inside a column).  The sort is a serial insertion sort per lane, meant for
+// stencil-sized columns: a column of more than TRANSPOSE_MAX_COL entries sets *overflow and is
+// left alone; the caller then discards the result and transposes on the host.
+__global__ __launch_bounds__(256) void transpose_count_kernel(int64_t nnz, const int32_t* __restrict__ col,
+                                                              int32_t* __restrict__ cnt) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p < nnz) atomicAdd(&cnt[col[p]], 1);
+}
+__global__ __launch_bounds__(256) void transpose_scatter_kernel(int64_t n, const int32_t* __restrict__ rowptr,
+                                                                const int32_t* __restrict__ col,
+                                                                const double* __restrict__ val,
+                                                                const int32_t* __restrict__ cptr,
+                                                                int32_t* __restrict__ cursor,
+                                                                int32_t* __restrict__ orow, double* __restrict__ oval) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  for (int32_t p = rowptr[r]; p < rowptr[r + 1]; ++p) {
+    const int32_t c = col[p];
+    const int32_t q = cptr[c] + atomicAdd(&cursor[c], 1);
+    if (q < cptr[c + 1]) {  // always, when cptr is the scan of this matrix's column counts
+      orow[q] = (int32_t)r;
+      oval[q] = val[p];
+    }
+  }
+}
+__global__ __launch_bounds__(256) void transpose_sort_kernel(int64_t n, const int32_t* __restrict__ cptr,
+                                                             int32_t* __restrict__ orow, double* __restrict__ oval,
+                                                             int32_t* __restrict__ overflow) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const int32_t s = cptr[c];
+  const int len = cptr[c + 1] - s;
+  if (len > TRANSPOSE_MAX_COL) {
+    atomicOr(overflow, 1);
+    return;
+  }
+  for (int a = 1; a < len; ++a) {  // insertion sort in place: the scatter leaves columns nearly sorted
+    const int32_t kr = orow[s + a];
+    const double kv = oval[s + a];
+    int b = a - 1;
+    while (b >= 0 && orow[s + b] > kr) {
+      orow[s + b + 1] = orow[s + b];
+      oval[s + b + 1] = oval[s + b];
+      --b;
+    }
+    orow[s + b + 1] = kr;
+    oval[s + b + 1] = kv;
+  }
+}
+hipError_t launch_transpose_count(int64_t nnz, const int32_t* col, int32_t* cnt, hipStream_t st) {
+  if (nnz <= 0) return hipSuccess;
+  hipLaunchKernelGGL(transpose_count_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, col, cnt);
+  return hipGetLastError();
+}
+hipError_t launch_transpose_fill(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
+                                 const int32_t* cptr, int32_t* cursor, int32_t* orow, double* oval, int32_t* overflow,
+                                 hipStream_t st) {
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(transpose_scatter_kernel, dim3(grid), dim3(256), 0, st, n, rowptr, col, val, cptr, cursor, orow,
+                     oval);
+  hipLaunchKernelGGL(transpose_sort_kernel, dim3(grid), dim3(256), 0, st, n, cptr, orow, oval, overflow);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ K-Block ----
 // Multi-right-hand-side (block) forms of the V-cycle's row kernels (solver.cpp: "block cycle").
 // Vectors are ROW-major panels of n x KP doubles (entry (i, j) at i * KP + j), KP a power of two

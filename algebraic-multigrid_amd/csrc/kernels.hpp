@@ -457,6 +457,30 @@ hipError_t launch_dict_encode(int64_t n, const int32_t* rowptr, const int32_t* c
                               uint64_t* codes, int32_t* fail, hipStream_t st);
 hipError_t launch_dict_types(int64_t n, const uint64_t* codes, int words, const uint64_t* rwords,
                              int ntypes, uint8_t* rtype, int32_t* fail, hipStream_t st);
+// K-CsrCheck: rowptr[0] == 0, rowptr non-decreasing and within [0, nnz], columns in [0, n) and
+// strictly ascending inside a row.  *first_bad (INT32_MAX before the launch) = first offending row.
+hipError_t launch_csr_check(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int32_t* first_bad,
+                            hipStream_t st);
+// K-SellPack: upload_mat's panel layouts from a device CSR.  Count pass: kept[n] (row lengths after
+// pruning), pslots[ceil(n / 64)] (64 * panel width), stats[3] zeroed by the caller = {longest kept
+// row, 1 when 16-bit relative indices do not fit, most kept entries of a 256-row block}.  Fill pass:
+// off32 = exclusive scan of pslots (widened into soff), scol int16 relative or int32 absolute.
+hipError_t launch_sell_count(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val, bool prune,
+                             int32_t* kept, int32_t* pslots, int32_t* stats, hipStream_t st);
+hipError_t launch_sell_fill(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val, bool prune,
+                            const int32_t* off32, int64_t* soff, bool idx16, void* scol, double* sval,
+                            hipStream_t st);
+// the CSR outcome: kept entries only, optr = exclusive scan of kept
+hipError_t launch_csr_compact(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val, bool prune,
+                              const int32_t* optr, int32_t* ocol, double* oval, hipStream_t st);
+// K-Transpose: CSR -> CSC of a square matrix.  cnt[n] zeroed by the caller, then scanned into cptr;
+// cursor[n] zeroed; *overflow (zeroed) is set when a column has more than TRANSPOSE_MAX_COL entries
+// (the result is then unusable).  The result equals the host transpose, structural zeros included.
+constexpr int TRANSPOSE_MAX_COL = 32;
+hipError_t launch_transpose_count(int64_t nnz, const int32_t* col, int32_t* cnt, hipStream_t st);
+hipError_t launch_transpose_fill(int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
+                                 const int32_t* cptr, int32_t* cursor, int32_t* orow, double* oval, int32_t* overflow,
+                                 hipStream_t st);
 
 // K-Block (kernels.hip): multi-right-hand-side forms for the block cycle.  Vectors are row-major
 // panels of n x kp doubles (entry (i, j) at i * kp + j), kp in {1, 2, 4, 8, 16}; per column the

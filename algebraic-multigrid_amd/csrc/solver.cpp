@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -2575,7 +2576,8 @@ hipError_t device_dict_encode(const DevCsr& A, bool prune, int maxlen, DevMat* D
   const int nw = T.words;
   std::map<std::pair<int32_t, uint64_t>, int> pairs;
   auto add_pairs = [&](const HostRows& R) {
-    for (size_t r = 0; r + 1 < R.ptr.size(); ++r)
+    for (size_t r = 0; r + 1 < R.ptr.size(); ++r) {
+      if (T.doff.size() > 255) return;  // does not qualify: no need to number the rest of the sample
       for (int32_t p = R.ptr[r] - R.ptr[0]; p < R.ptr[r + 1] - R.ptr[0]; ++p) {
         if (prune && R.val[p] == 0.0) continue;
         uint64_t bits;
@@ -2586,6 +2588,7 @@ hipError_t device_dict_encode(const DevCsr& A, bool prune, int maxlen, DevMat* D
           T.dval.push_back(R.val[p]);
         }
       }
+    }
   };
   const int64_t S = std::min<int64_t>(n, 65536);
   HostRows R;
@@ -2675,9 +2678,156 @@ hipError_t device_dict_encode(const DevCsr& A, bool prune, int maxlen, DevMat* D
   return hipSuccess;
 }
 
+// K-SellPack: what upload_mat(M, layout) uploads for the pruned CSR matrix M = A when it does not
+// take the dictionary (SELL-64 panels or CSR by the same rule, the same index width and
+// non-temporal bit, the same arrays bit for bit), made from the device arrays of A.  *ok = false:
+// the panels need 2^31 slots or more; the caller takes the host upload.
+hipError_t device_sell_pack(const DevCsr& A, int layout, bool prune, DevMat* D, bool* ok) {
+  *ok = false;
+  const int64_t n = A.n_rows;
+  if (n < 1 || n >= ((int64_t)1 << 31) - 512) return hipSuccess;
+  const int64_t np = (n + 63) / 64;
+  hipError_t e;
+  DevMem kept, pslots, stats, bsum, total, off32, optr;
+  if ((e = kept.alloc(sizeof(int32_t) * (n + 1))) != hipSuccess) return e;
+  if ((e = pslots.alloc(sizeof(int32_t) * (np + 1))) != hipSuccess) return e;
+  if ((e = stats.alloc(sizeof(int32_t) * 3)) != hipSuccess) return e;
+  if ((e = bsum.alloc(sizeof(int64_t) * ((n + 1023) / 1024 + 1))) != hipSuccess) return e;
+  if ((e = total.alloc(sizeof(int64_t))) != hipSuccess) return e;
+  if ((e = optr.alloc(sizeof(int32_t) * (n + 1))) != hipSuccess) return e;
+  if ((e = off32.alloc(sizeof(int32_t) * (np + 1))) != hipSuccess) return e;
+  if ((e = hipMemset(stats.p, 0, sizeof(int32_t) * 3)) != hipSuccess) return e;
+  if ((e = launch_sell_count(n, A.rowptr(), A.col(), A.v(), prune, kept.as<int32_t>(), pslots.as<int32_t>(),
+                             stats.as<int32_t>(), nullptr)) != hipSuccess)
+    return e;
+  int64_t nnz = 0, slots = 0;
+  if ((e = launch_exclusive_scan(n, kept.as<int32_t>(), optr.as<int32_t>(), bsum.as<int64_t>(), total.as<int64_t>(),
+                                 nullptr)) != hipSuccess)
+    return e;
+  if ((e = hipMemcpy(&nnz, total.p, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  if ((e = launch_exclusive_scan(np, pslots.as<int32_t>(), off32.as<int32_t>(), bsum.as<int64_t>(),
+                                 total.as<int64_t>(), nullptr)) != hipSuccess)
+    return e;
+  if ((e = hipMemcpy(&slots, total.p, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  int32_t st[3];
+  if ((e = hipMemcpy(st, stats.p, sizeof(st), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  if (slots >= ((int64_t)1 << 31) - 1) return hipSuccess;  // the scan's offsets are 32-bit
+  // upload_mat's rule: an explicit SELL or CSR request holds (a dictionary request that did not
+  // qualify is a SELL request), AUTO takes SELL-64 unless padding exceeds 25 %
+  bool sell = layout != AMG_HIP_LAYOUT_CSR;
+  if (layout == AMG_HIP_LAYOUT_AUTO) sell = (double)slots <= 1.25 * (double)nnz + 4096.0;
+  D->n_rows = n;
+  D->nnz = nnz;
+  D->dict = false;
+  D->sell = sell;
+  if (!sell) {
+    DevCsr& C = D->csr;
+    C.n_rows = n;
+    C.n_cols = A.n_cols;
+    C.nnz = nnz;
+    C.max_block_nnz = st[2];
+    C.max_row_nnz = st[0];
+    if ((e = C.idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
+    if ((e = C.val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
+    if ((e = launch_csr_compact(n, A.rowptr(), A.col(), A.v(), prune, optr.as<int32_t>(), C.idx.as<int32_t>(),
+                                C.val.as<double>(), nullptr)) != hipSuccess)
+      return e;
+    C.ptr = std::move(optr);
+    *ok = true;
+    return hipSuccess;
+  }
+  D->max_width = st[0];
+  D->slots = slots;
+  const bool fits = g_index16 != 0 && st[1] == 0;
+  const double stream_bytes = (double)slots * (fits ? 10.0 : 12.0);
+  D->idx16 = (fits ? 1 : 0) | ((g_nontemporal && stream_bytes > 192.0e6) ? 2 : 0);
+  if ((e = D->soff.alloc(sizeof(int64_t) * (np + 1))) != hipSuccess) return e;
+  if ((e = D->scol.alloc((size_t)slots * (fits ? sizeof(int16_t) : sizeof(int32_t)))) != hipSuccess) return e;
+  if ((e = D->sval.alloc(sizeof(double) * (size_t)slots)) != hipSuccess) return e;
+  if ((e = launch_sell_fill(n, A.rowptr(), A.col(), A.v(), prune, off32.as<int32_t>(), D->soff.as<int64_t>(), fits,
+                            D->scol.p, D->sval.as<double>(), nullptr)) != hipSuccess)
+    return e;
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return e;  // off32 is released on return
+  *ok = true;
+  return hipSuccess;
+}
+
+// K-Transpose: T = CSC(A) of the square device matrix A, equal to the host transpose(), structural
+// zeros included.  *ok = false: a column has more entries than the kernel sorts.
+hipError_t device_transpose(const DevCsr& A, DevCsr* T, bool* ok) {
+  *ok = false;
+  const int64_t n = A.n_rows, nnz = A.nnz;
+  hipError_t e;
+  DevMem cnt, bsum, total, ovf;
+  if ((e = cnt.alloc(sizeof(int32_t) * (n + 1))) != hipSuccess) return e;
+  if ((e = bsum.alloc(sizeof(int64_t) * ((n + 1023) / 1024 + 1))) != hipSuccess) return e;
+  if ((e = total.alloc(sizeof(int64_t))) != hipSuccess) return e;
+  if ((e = ovf.alloc(sizeof(int32_t))) != hipSuccess) return e;
+  if ((e = hipMemset(cnt.p, 0, sizeof(int32_t) * (n + 1))) != hipSuccess) return e;
+  if ((e = hipMemset(ovf.p, 0, sizeof(int32_t))) != hipSuccess) return e;
+  if ((e = launch_transpose_count(nnz, A.col(), cnt.as<int32_t>(), nullptr)) != hipSuccess) return e;
+  if ((e = T->ptr.alloc(sizeof(int32_t) * (n + 1))) != hipSuccess) return e;
+  if ((e = launch_exclusive_scan(n, cnt.as<int32_t>(), T->ptr.as<int32_t>(), bsum.as<int64_t>(), total.as<int64_t>(),
+                                 nullptr)) != hipSuccess)
+    return e;
+  if ((e = hipMemset(cnt.p, 0, sizeof(int32_t) * (n + 1))) != hipSuccess) return e;  // now the cursors
+  if ((e = T->idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
+  if ((e = T->val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
+  if ((e = launch_transpose_fill(n, A.rowptr(), A.col(), A.v(), T->ptr.as<int32_t>(), cnt.as<int32_t>(),
+                                 T->idx.as<int32_t>(), T->val.as<double>(), ovf.as<int32_t>(), nullptr)) != hipSuccess)
+    return e;
+  int32_t over = 0;
+  if ((e = hipMemcpy(&over, ovf.p, sizeof(int32_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  if (over) return hipSuccess;
+  T->n_rows = T->n_cols = n;
+  T->nnz = nnz;
+  *ok = true;
+  return hipSuccess;
+}
+
 void rhs_threads(int dim, int64_t n, double* b, int nt, int64_t d0 = 0, int64_t d1 = -1);  // below
 
-// AMG::Multigrid's constructor (multigrid.hpp:151-244) for A = Grid::laplacian(n), b =
+// AMG_HIP_TIMING=1: wall time of the phases of a device set-up on stderr
+struct SetupLap {
+  bool on = std::getenv("AMG_HIP_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  void operator()(const char* what) {
+    if (!on) return;
+    (void)hipDeviceSynchronize();
+    const auto t1 = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "amg_hip device setup: %s %.3fs\n", what, std::chrono::duration<double>(t1 - t0).count());
+    t0 = t1;
+  }
+};
+// a solver with the options `o`, bound to its device and stream
+amg_hip_status device_setup_begin(const amg_hip_options& o, std::unique_ptr<amg_hip_solver>* sp) {
+  std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
+  s->opt = o;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(AMG_HIP_EHIP, "no HIP device available (this library has no CPU fallback)");
+  if (o.device >= 0) {
+    if (o.device >= ndev) return fail(AMG_HIP_EINVAL, "device ordinal out of range");
+    s->device = o.device;
+  } else {
+    HIP_TRY(hipGetDevice(&s->device));
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  if (o.stream) {
+    s->stream = (hipStream_t)o.stream;
+    s->own_stream = false;
+  } else {
+    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  }
+  *sp = std::move(s);
+  return AMG_HIP_OK;
+}
+// The level loop of the device set-ups (defined below the model problem's front end).
+amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const int64_t dims0[3], bool tensor,
+                                 bool user, int32_t n_levels, SetupLap& lap,
+                                 const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported);
+
+// Front end of the model problem: AMG::Multigrid's constructor (multigrid.hpp:151-244) for A = Grid::laplacian(n), b =
 // Grid::rhs(n) without host matrices: generator, Galerkin chain, dictionary encoder, diagonal
 // and symmetry check all run on the device; only b (n^dim exp() calls, kept on the host so that
 // the bits are libm's, like the reference's) and the coarsest operator (factored on the host)
@@ -2718,33 +2868,12 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
     if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
     if (o.window) return fail(AMG_HIP_EUNSUPPORTED, "the line smoother is not available in a window solver");
   }
-  std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
-  s->opt = o;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(AMG_HIP_EHIP, "no HIP device available (this library has no CPU fallback)");
-  if (o.device >= 0) {
-    if (o.device >= ndev) return fail(AMG_HIP_EINVAL, "device ordinal out of range");
-    s->device = o.device;
-  } else {
-    HIP_TRY(hipGetDevice(&s->device));
+  std::unique_ptr<amg_hip_solver> s;
+  {
+    const amg_hip_status r = device_setup_begin(o, &s);
+    if (r != AMG_HIP_OK) return r;
   }
-  HIP_TRY(hipSetDevice(s->device));
-  if (o.stream) {
-    s->stream = (hipStream_t)o.stream;
-    s->own_stream = false;
-  } else {
-    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  }
-  const bool timing = std::getenv("AMG_HIP_TIMING") != nullptr;
-  auto t_start = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    (void)hipDeviceSynchronize();
-    const auto t1 = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "amg_hip device setup: %s %.3fs\n", what, std::chrono::duration<double>(t1 - t_start).count());
-    t_start = t1;
-  };
+  SetupLap lap;
   // b on the host threads while the device builds the hierarchy
   std::vector<double> b((size_t)N);
   std::thread rhs_thread([&] { rhs_threads(dim, n, b.data(), host_threads(), unit0 * unit_rows, unit1 * unit_rows); });
@@ -2775,12 +2904,56 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
     cur.nnz = nnz;
   }
   lap("generator");
+  const int64_t dims0[3] = {n, n, dim == 3 ? n : 1};
+  auto put_rhs = [&](Level& L0) -> amg_hip_status {
+    joiner.t.join();
+    HIP_TRY(hipMemcpy(L0.f.p, b.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(L0.r.p, b.data(), sizeof(double) * N, hipMemcpyHostToDevice));  // b - A*0
+    return AMG_HIP_OK;
+  };
+  const amg_hip_status r = device_level_loop(s.get(), cur, dim, dims0, tensor, false, n_levels, lap, put_rhs,
+                                             unsupported);
+  if (r != AMG_HIP_OK || *unsupported) return r;
+  *out = s.release();
+  return AMG_HIP_OK;
+}
+
+// The level loop of the device set-ups: from CSR(A_0) on the device (`cur`, consumed) and the grid
+// `dims0` of level 0 (tensor) to the finished hierarchy; put_rhs fills f and r of level 0 once the
+// levels exist.  Returns with *unsupported still true when the hierarchy needs the host
+// constructor after all.  user: A_0 is a caller's matrix (amg_hip_create_tensor_dev): every
+// opt.layout is honoured, levels that do not take the dictionary are packed by K-SellPack with
+// upload_mat's rule, and levels that are not bitwise symmetric are transposed by K-Transpose, so
+// that no level crosses to the host.  The model problem's front ends keep the launches they had.
+amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const int64_t dims0[3], bool tensor,
+                                 bool user, int32_t n_levels, SetupLap& lap,
+                                 const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported) {
+  *unsupported = true;
+  const amg_hip_options& o = s->opt;
+  const bool lex = o.smoother <= AMG_HIP_SM_SOR;
+  const bool cheb = o.smoother == AMG_HIP_SM_CHEBYSHEV;
+  const bool line = o.smoother == AMG_HIP_SM_LINE_JACOBI;
+  const bool timing = lap.on;
+  const bool try_dict = o.layout == AMG_HIP_LAYOUT_AUTO || o.layout == AMG_HIP_LAYOUT_DICT;
   s->lv.resize(n_levels);
   DevMem stats, gbound;
   HIP_TRY(stats.alloc(sizeof(int32_t) * 2));
   if (cheb) HIP_TRY(gbound.alloc(sizeof(uint64_t) * 2));
   const bool prune = !o.keep_structural_zeros;
-  int64_t tdims[3] = {n, n, dim == 3 ? n : 1};  // full coarsening: the grid of the current level
+  int64_t tdims[3] = {dims0[0], dims0[1], dims0[2]};  // full coarsening: the grid of the current level
+  // user: one form of a level (its rows, or its columns walked as rows) into its device layout
+  // without the host: the dictionary when the layout allows it and the matrix qualifies, else
+  // K-SellPack.  *done = false: the host upload has to do it.
+  auto encode_dev = [&](int l, const DevCsr& M, int maxlen, DevMat* D, bool* done) -> amg_hip_status {
+    *done = false;
+    if (try_dict) HIP_TRY(device_dict_encode(M, prune, maxlen, D, done));
+    if (*done) return AMG_HIP_OK;
+    HIP_TRY(device_sell_pack(M, o.layout, prune, D, done));
+    if (timing && *done)
+      std::fprintf(stderr, "amg_hip device setup: level %d (%lld rows, longest row %d) -> K-SellPack (%s)\n", l,
+                   (long long)M.n_rows, maxlen, D->sell ? "SELL-64" : "CSR");
+    return AMG_HIP_OK;
+  };
   for (int l = 0; l < n_levels; ++l) {
     Level& L = s->lv[l];
     L.n = cur.n_rows;
@@ -2817,6 +2990,38 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       // Both forms of this one level are made on the host (transpose) and uploaded; the chain
       // itself stays on the device.
       if (lex) return AMG_HIP_OK;
+      bool both = false;
+      if (user) {  // K-Transpose, then both forms like any level
+        DevCsr csc;
+        bool tr = false;
+        HIP_TRY(device_transpose(cur, &csc, &tr));
+        if (timing) std::fprintf(stderr, "amg_hip device setup: level %d (%lld rows) not bitwise symmetric -> K-Transpose%s\n",
+                                 l, (long long)L.n, tr ? "" : " refused (a column is too long)");
+        if (tr) {
+          bool rows_done = false, cols_done = true;
+          amg_hip_status er = encode_dev(l, cur, st[0], &L.A_rows, &rows_done);
+          if (er != AMG_HIP_OK) return er;
+          // the smoothers that walk the columns of A (build_solver: true Jacobi; Chebyshev and the
+          // line smoother use its rows)
+          if (rows_done && o.smoother == AMG_HIP_SM_JACOBI) {
+            HIP_TRY(hipMemset(stats.p, 0, sizeof(int32_t) * 2));  // longest column, for the encoder
+            HIP_TRY(launch_csr_inspect(L.n, csc.rowptr(), csc.col(), csc.v(), prune, stats.as<int32_t>(), nullptr,
+                                       nullptr));
+            int32_t st2[2];
+            HIP_TRY(hipMemcpy(st2, stats.p, sizeof(st2), hipMemcpyDeviceToHost));
+            er = encode_dev(l, csc, st2[0], &L.A_cols_own, &cols_done);
+            if (er != AMG_HIP_OK) return er;
+          }
+          both = rows_done && cols_done;
+          if (both) {
+            L.A_dev = std::move(csc);  // CSC(A): what ensure_host_matrix downloads
+          } else {
+            L.A_rows = DevMat();
+            L.A_cols_own = DevMat();
+          }
+        }
+      }
+      if (!both) {
       if (timing) std::fprintf(stderr, "amg_hip device setup: level %d (%lld rows) not bitwise symmetric -> rows and columns uploaded separately\n",
                                l, (long long)L.n);
       Sparse H;
@@ -2830,7 +3035,11 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       HIP_TRY(upload_mat_pruned(H, o.layout, prune, &L.A_rows));       // H = CSR(A)
       L.A_csc = transpose(H);                                           // CSC(A)
       HIP_TRY(upload_mat_pruned(L.A_csc, o.layout, prune, &L.A_cols_own));
+      }
       ok = true;
+    } else if (user) {
+      const amg_hip_status er = encode_dev(l, cur, st[0], &L.A_rows, &ok);
+      if (er != AMG_HIP_OK) return er;
     } else {
       HIP_TRY(device_dict_encode(cur, prune, st[0], &L.A_rows, &ok));
     }
@@ -2849,7 +3058,7 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       HIP_TRY(hipMemcpy(H.ptr.data(), cur.ptr.p, sizeof(int32_t) * H.ptr.size(), hipMemcpyDeviceToHost));
       HIP_TRY(hipMemcpy(H.idx.data(), cur.idx.p, sizeof(int32_t) * H.idx.size(), hipMemcpyDeviceToHost));
       HIP_TRY(hipMemcpy(H.val.data(), cur.val.p, sizeof(double) * H.val.size(), hipMemcpyDeviceToHost));
-      HIP_TRY(upload_mat_pruned(H, AMG_HIP_LAYOUT_SELL, prune, &L.A_rows));
+      HIP_TRY(upload_mat_pruned(H, user ? o.layout : AMG_HIP_LAYOUT_SELL, prune, &L.A_rows));
       L.A_csc = std::move(H);  // symmetric: the CSR arrays are the CSC arrays
     }
     if (o.smoother != AMG_HIP_SM_JACOBI) L.diag.release();
@@ -2875,7 +3084,7 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       L.scan_ring = ring;
     }
     if (l + 1 == n_levels) {
-      if (L.A_csc.ptr.empty()) L.A_dev = std::move(cur);
+      if (L.A_csc.ptr.empty() && L.A_dev.n_rows == 0) L.A_dev = std::move(cur);
       break;
     }
     DevCsr next;
@@ -2911,13 +3120,14 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       HIP_TRY(ge);
     }
     }
-    if (L.A_csc.ptr.empty()) L.A_dev = std::move(cur);
+    if (L.A_csc.ptr.empty() && L.A_dev.n_rows == 0) L.A_dev = std::move(cur);
     cur = std::move(next);
   }
   lap("hierarchy");
-  joiner.t.join();
-  HIP_TRY(hipMemcpy(s->lv[0].f.p, b.data(), sizeof(double) * N, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s->lv[0].r.p, b.data(), sizeof(double) * N, hipMemcpyHostToDevice));  // b - A*0
+  {
+    const amg_hip_status r = put_rhs(s->lv[0]);
+    if (r != AMG_HIP_OK) return r;
+  }
   lap("rhs");
   if (!o.window) {
     const int want = o.fast_coarse_solve ? 1 : (o.exact_coarse_solve ? -1 : 0);
@@ -2928,14 +3138,13 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
   lap("coarse factor");
   HIP_TRY(s->scratch.alloc(sizeof(double) * 1100));
   {
-    amg_hip_status r = set_patch_coarse_flags(s.get());
+    amg_hip_status r = set_patch_coarse_flags(s);
     if (r != AMG_HIP_OK) return r;
   }
-  compute_bytes(s.get());
+  compute_bytes(s);
   HIP_TRY(hipDeviceSynchronize());
   s->device_setup = true;
   *unsupported = false;
-  *out = s.release();
   return AMG_HIP_OK;
 }
 
@@ -3440,6 +3649,151 @@ amg_hip_status amg_hip_create_poisson_tensor(int32_t dim, int64_t n, int32_t n_l
   rhs_threads(dim, n, b.data(), host_threads());
   return amg_hip_create_tensor(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims,
                                n_levels, opts, out);
+}
+
+// Front end of amg_hip_create_tensor_dev: the caller's device arrays are copied on the solver's
+// stream and checked by K-CsrCheck; then the level loop, unless the options need host structures.
+// *unsupported = true on return with AMG_HIP_OK: the (checked) matrix takes the host constructor.
+static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr, const int32_t* col,
+                                               const double* val, const double* b, int dim, const int64_t* dims,
+                                               int32_t n_levels, const amg_hip_options& o, amg_hip_solver** out,
+                                               bool* unsupported) {
+  *unsupported = true;
+  std::unique_ptr<amg_hip_solver> s;
+  {
+    const amg_hip_status r = device_setup_begin(o, &s);
+    if (r != AMG_HIP_OK) return r;
+  }
+  SetupLap lap;
+  DevCsr cur;
+  DevMem rhs, bad;
+  const hipStream_t st = s->stream;
+  HIP_TRY(cur.ptr.alloc(sizeof(int32_t) * (n + 1)));
+  HIP_TRY(hipMemcpyAsync(cur.ptr.p, rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToDevice, st));
+  int32_t nnz32 = -1;
+  HIP_TRY(hipMemcpyAsync(&nnz32, cur.ptr.as<int32_t>() + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (nnz32 < 0 || nnz32 == INT32_MAX)
+    return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor_dev: `rowptr[n]` = " + std::to_string(nnz32) +
+                                    " is not a number of entries (row " + std::to_string(n - 1) + ")");
+  const int64_t nnz = nnz32;
+  HIP_TRY(cur.idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
+  HIP_TRY(cur.val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1)));
+  HIP_TRY(rhs.alloc(sizeof(double) * n));
+  HIP_TRY(bad.alloc(sizeof(int32_t)));
+  const int32_t none = INT32_MAX;
+  int32_t first_bad = none;
+  HIP_TRY(hipMemcpyAsync(bad.p, &none, sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (nnz > 0) HIP_TRY(hipMemcpyAsync(cur.idx.p, col, sizeof(int32_t) * nnz, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(launch_csr_check(n, nnz, cur.rowptr(), cur.col(), bad.as<int32_t>(), st));
+  HIP_TRY(hipMemcpyAsync(&first_bad, bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (nnz > 0) HIP_TRY(hipMemcpyAsync(cur.val.p, val, sizeof(double) * nnz, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(rhs.p, b, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (first_bad != none)
+    return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor_dev: row " + std::to_string(first_bad) +
+                                    " of the CSR arrays is malformed (`rowptr` must start at 0 and never decrease; "
+                                    "the columns of a row must lie in [0, n) and ascend strictly)");
+  cur.n_rows = cur.n_cols = n;
+  cur.nnz = nnz;
+  lap("copy + check");
+  const bool on_device = (o.smoother == AMG_HIP_SM_JACOBI || o.smoother == AMG_HIP_SM_CHEBYSHEV ||
+                          o.smoother == AMG_HIP_SM_LINE_JACOBI) &&
+                         !o.host_only && !o.host_galerkin && o.stencil_transfers && !o.fuse_prolong && n_levels >= 2 &&
+                         n < ((int64_t)1 << 28);
+  if (!on_device) return AMG_HIP_OK;
+  auto put_rhs = [&](Level& L0) -> amg_hip_status {
+    HIP_TRY(hipMemcpy(L0.f.p, rhs.p, sizeof(double) * n, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(L0.r.p, rhs.p, sizeof(double) * n, hipMemcpyDeviceToDevice));  // b - A*0
+    return AMG_HIP_OK;
+  };
+  const amg_hip_status r = device_level_loop(s.get(), cur, dim, dims, true, true, n_levels, lap, put_rhs, unsupported);
+  if (r != AMG_HIP_OK || *unsupported) return r;
+  *out = s.release();
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                         const double* val_dev, const double* b_dev, int32_t dim,
+                                         const int64_t* dims, int32_t n_levels, const amg_hip_options* opts,
+                                         amg_hip_solver** out) {
+  static const std::string who = "amg_hip_create_tensor_dev: ";
+  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
+  *out = nullptr;
+  if (!rowptr_dev || !col_dev || !val_dev || !b_dev) return fail(AMG_HIP_EINVAL, "null input array");
+  const std::string e = tensor_dims_error(dim, dims);
+  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
+  if (n != dims[0] * dims[1] * dims[2])
+    return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
+                                    " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
+                                    " grid of `dims`");
+  amg_hip_options o;
+  if (opts) o = *opts;
+  else amg_hip_default_options(&o);
+  if (o.window)
+    return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a full-coarsening "
+                                            "hierarchy is not sharded");
+  if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
+  {  // the levels the rule allows
+    int64_t d[3] = {dims[0], dims[1], dims[2]};
+    for (int l = 0; l + 1 < n_levels; ++l) {
+      if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
+      int64_t c[3];
+      tensor_coarse_dims(dim, d, c);
+      for (int a = 0; a < 3; ++a) d[a] = c[a];
+    }
+  }
+  // build_solver's option checks, in its words
+  if (o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_JACOBI) return fail(AMG_HIP_EINVAL, "unknown smoother kind");
+  if (o.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
+  if (o.smoother == AMG_HIP_SM_CHEBYSHEV) {
+    const std::string ce = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
+    if (!ce.empty()) return fail(AMG_HIP_EINVAL, ce);
+  }
+  if (o.smoother == AMG_HIP_SM_LINE_JACOBI) {
+    const std::string le = line_options_error(o.omega);
+    if (!le.empty()) return fail(AMG_HIP_EINVAL, le);
+  }
+  if (o.layout < AMG_HIP_LAYOUT_AUTO || o.layout > AMG_HIP_LAYOUT_DICT)
+    return fail(AMG_HIP_EINVAL, "unknown matrix layout");
+  if (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0))
+    return fail(AMG_HIP_EINVAL, "`omega` must be in [0, 2] but got omega=" + std::to_string(o.omega) + "\n");
+  bool unsupported = true;
+  amg_hip_status r = build_tensor_user_device(n, rowptr_dev, col_dev, val_dev, b_dev, dim, dims, n_levels, o, out,
+                                              &unsupported);
+  if (r != AMG_HIP_OK || !unsupported) return r;
+  // options that need host structures (or a product the kernels refused): the checked arrays are
+  // downloaded, transposed on the host and given to the host constructor
+  int64_t nnz = 0;
+  Sparse H;  // CSR(A)
+  std::vector<double> b((size_t)n);
+  {
+    int dev_before = 0;
+    HIP_TRY(hipGetDevice(&dev_before));
+    if (o.device >= 0) HIP_TRY(hipSetDevice(o.device));
+    Scoped own;
+    hipStream_t st = (hipStream_t)o.stream;
+    if (!st) {
+      HIP_TRY(hipStreamCreateWithFlags(&own.st, hipStreamNonBlocking));
+      st = own.st;
+    }
+    H.n_outer = H.n_inner = n;
+    H.ptr.resize((size_t)n + 1);
+    HIP_TRY(hipMemcpyAsync(H.ptr.data(), rowptr_dev, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b.data(), b_dev, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    nnz = H.ptr[(size_t)n];
+    H.idx.resize((size_t)nnz);
+    H.val.resize((size_t)nnz);
+    if (nnz > 0) {
+      HIP_TRY(hipMemcpyAsync(H.idx.data(), col_dev, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(H.val.data(), val_dev, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (o.device >= 0) HIP_TRY(hipSetDevice(dev_before));
+  }
+  const Sparse A = transpose(H);  // CSC(A)
+  return amg_hip_create_tensor(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims, n_levels, &o, out);
 }
 
 amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on) {

@@ -344,8 +344,39 @@ amg_hip_status amg_hip_create_poisson(int32_t dim, int64_t n, int32_t n_levels,
  * opts->window = 1.  These checks come before the device is touched.                            */
 amg_hip_status amg_hip_create_poisson_tensor(int32_t dim, int64_t n, int32_t n_levels,
                                              const amg_hip_options* opts, amg_hip_solver** out);
+/* amg_hip_create_tensor for a caller's matrix that already sits in DEVICE memory, with the SETUP
+ * ON THE DEVICE.  A is in CSR (the rows of A, columns strictly ascending inside a row) -- NOT the
+ * CSC arrays of the host constructors -- and b_dev holds n doubles.  Both are copied; the caller's
+ * arrays are only read, on the solver's stream, and the call returns after a synchronisation.
+ * The hierarchy is that of amg_hip_create_tensor on the CSC arrays of the same A and b with the
+ * same options: levels, dims, level matrices bit for bit (structural zeros included), layouts
+ * (amg_hip_level_layout), transfer kind 2, Chebyshev bounds, line strides, and every cycle, apply,
+ * PCG and block call.  The level loop is amg_hip_create_poisson_tensor's; on top of it, levels that
+ * do not take the dictionary are packed into SELL-64 panels or pruned CSR on the device
+ * (K-SellPack, upload_mat's rule for opts->layout) and levels that are not bitwise symmetric are
+ * transposed there (K-Transpose), so that no level matrix crosses to the host during set-up but the
+ * coarsest operator for its factorisation.  Two per-level detours to the host remain: a column of
+ * more than 32 entries on a level that is not bitwise symmetric, and panels of 2^31 slots or more.
+ * Device path: true Jacobi, Chebyshev and the line smoother with stencil_transfers, every layout,
+ * n_levels >= 2 and n < 2^28.  Everything else silently downloads the arrays, transposes them on
+ * the host and calls amg_hip_create_tensor: host_only, host_galerkin, stencil_transfers = 0,
+ * fuse_prolong, multicolour GS, the lexicographic smoothers, one level, a coarse row beyond
+ * K-TensorGalerkin's lane group, a product beyond int32 indexing.  amg_hip_setup_on_device tells
+ * the two apart.
+ * Before the device is touched -- AMG_HIP_EINVAL: null pointers, dim outside {2, 3}, n != nx ny nz,
+ * dim == 2 with nz != 1, more levels than the rule allows (the level in the message), bad smoother,
+ * Chebyshev, line or layout options; AMG_HIP_EUNSUPPORTED: opts->window = 1.  Then the arrays are
+ * checked by one kernel (K-CsrCheck: rowptr[0] == 0, rowptr non-decreasing, columns in [0, n) and
+ * strictly ascending inside a row); a failure is AMG_HIP_EINVAL with the first offending row in
+ * the message, and nothing else runs on such a matrix.  rowptr_dev[n] states the length of
+ * col_dev / val_dev: the check reads nothing beyond it.                                          */
+amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                         const double* val_dev, const double* b_dev, int32_t dim,
+                                         const int64_t* dims /* 3, host */, int32_t n_levels,
+                                         const amg_hip_options* opts, amg_hip_solver** out);
 /* *on = 1: the hierarchy was built by a device-only path (amg_hip_create_poisson,
- * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor when they did not fall back),
+ * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor, amg_hip_create_tensor_dev when
+ * they did not fall back),
  * 0: by the host constructor -- every other entry point and the silent fallbacks.  Also on
  * host_only solvers (0).                                                                        */
 amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on);

@@ -8,6 +8,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py tensor                                      full-coarsening hierarchies next to the flat ones (legs alternate)
        config_bench.py tensor10 <n> <levels> [csr]                 ten cycles of one tensor hierarchy (kernel traces)
        config_bench.py tensor-setup [<dim> <n> <levels>]           set-up seconds of the full-coarsening hierarchy, host and device construction alternating
+       config_bench.py tensor-user-setup [<nx> <ny> <nz> <levels>] set-up seconds for a variable-coefficient operator assembled on the GPU: host constructor and amg_hip_create_tensor_dev alternating
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -225,6 +226,89 @@ def run_tensor_setup(dim, n, L, reps=3):
           f"ratio {best['host'] / best['device']:.1f}", flush=True)
 
 
+def torch_diffusion(dims, seed=1):
+    """-div(kappa grad u) + u on the grid `dims` (x fastest), kappa uniform in [1, 10] per face, assembled
+    on the GPU with torch: (crow int32, col int32, val float64, b float64) device tensors in CSR with
+    ascending columns.  Both triangles hold the same bits, so the arrays are the CSC arrays as well."""
+    import torch
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    dim = len(dims)
+    ext = tuple(dims) + (1,) * (3 - dim)
+    n = ext[0] * ext[1] * ext[2]
+    i = torch.arange(n, device=dev)
+    coord = [i % ext[0], (i // ext[0]) % ext[1], i // (ext[0] * ext[1])]
+    stride = [1, ext[0], ext[0] * ext[1]]
+    kap = [torch.rand(n, generator=g, device=dev, dtype=torch.float64) * 9.0 + 1.0 for _ in range(dim)]  # face i | i + stride
+    w = 2 * dim + 1
+    cols = torch.zeros((n, w), dtype=torch.int64, device=dev)
+    vals = torch.zeros((n, w), dtype=torch.float64, device=dev)
+    mask = torch.zeros((n, w), dtype=torch.bool, device=dev)
+    diag = torch.ones(n, dtype=torch.float64, device=dev)
+    for a in range(dim):
+        lo_ok, hi_ok = coord[a] > 0, coord[a] < ext[a] - 1
+        k_lo = torch.where(lo_ok, torch.roll(kap[a], stride[a]), torch.full_like(kap[a], 5.5))  # Dirichlet faces: 5.5
+        k_hi = torch.where(hi_ok, kap[a], torch.full_like(kap[a], 5.5))
+        diag = diag + k_lo + k_hi
+        s_lo, s_hi = dim - 1 - a, dim + 1 + a  # ascending column order
+        cols[:, s_lo], vals[:, s_lo], mask[:, s_lo] = i - stride[a], -k_lo, lo_ok
+        cols[:, s_hi], vals[:, s_hi], mask[:, s_hi] = i + stride[a], -k_hi, hi_ok
+    cols[:, dim], vals[:, dim], mask[:, dim] = i, diag, True
+    crow = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    crow[1:] = torch.cumsum(mask.sum(1), 0).to(torch.int32)
+    col = cols[mask].to(torch.int32).contiguous()
+    val = vals[mask].contiguous()
+    b = torch.rand(n, generator=g, device=dev, dtype=torch.float64)
+    return crow, col, val, b
+
+
+def run_tensor_user_setup(dims, L, reps=3, tol=1e-8, cap=60):
+    """Set-up seconds of the full-coarsening hierarchy of a variable-coefficient operator that was
+    assembled on the GPU: the host constructor (Multigrid.tensor on host copies of the arrays; the
+    copy itself is not timed) and the device set-up (Multigrid.tensor_dev on the device arrays),
+    alternating in one process, `reps` repeats; wall time around the constructor, closed by a device
+    synchronise.  With AMG_HIP_TIMING set the library writes its laps to stderr.  Then, once, the
+    V-cycles the device-built solver needs for a residual reduction of `tol`."""
+    import torch
+    crow, col, val, b = torch_diffusion(dims)
+    torch.cuda.synchronize()
+    h = [a.cpu().numpy() for a in (crow, col, val, b)]
+    tag = " x ".join(str(d) for d in dims)
+    best, keep = {}, None
+    for rep_ in range(reps):
+        for name in ("host", "device"):
+            t0 = time.perf_counter()
+            if name == "host":
+                mg = amg.Multigrid.tensor(h[0], h[1], h[2], h[3], dims, L, **TENSOR_KW["jacobi"])
+            else:
+                mg = amg.Multigrid.tensor_dev(crow, col, val, b, dims, L, **TENSOR_KW["jacobi"])
+            mg.sync()
+            dt = time.perf_counter() - t0
+            assert mg.setup_on_device == int(name == "device")
+            best[name] = min(best.get(name, dt), dt)
+            print(f"tensor-user-setup {tag} {L} levels, {name} rep {rep_}: {dt:.3f} s (setup_on_device "
+                  f"{mg.setup_on_device}, level-0 layout {mg.level_layout(0)}, coarsest {mg.get_n_dofs(L - 1)} dofs)",
+                  flush=True)
+            if name == "device" and rep_ == reps - 1:
+                keep = mg
+            else:
+                mg.close()
+    print(f"tensor-user-setup {tag} {L} levels: best host {best['host']:.3f} s, best device {best['device']:.3f} s, "
+          f"ratio {best['host'] / best['device']:.1f}", flush=True)
+    r0 = keep.rss()
+    done, rel = 0, 1.0
+    t0 = time.perf_counter()
+    while rel > tol and done < cap:
+        keep.vcycle(1)
+        done += 1
+        rel = (keep.rss() / r0) ** 0.5
+    keep.sync()
+    print(f"tensor-user-setup {tag}: ||r|| / ||r0|| = {rel:.2e} after {done} V-cycles (jacobi 2+2, omega 0.8), "
+          f"{(time.perf_counter() - t0) * 1e3:.1f} ms including one rss per cycle", flush=True)
+    keep.close()
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -314,6 +398,17 @@ elif len(sys.argv) > 1 and sys.argv[1] == "tensor-setup":
         run_tensor_setup(2, 1024, 8)
         run_tensor_setup(2, 4096, 10)
         run_tensor_setup(3, 256, 7)
+elif len(sys.argv) > 1 and sys.argv[1] == "tensor-user-setup":
+    os.environ.setdefault("AMG_HIP_TIMING", "1")
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    if len(sys.argv) > 5:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_tensor_user_setup(d if d[2] > 1 else d[:2], int(sys.argv[5]))
+    else:
+        run_tensor_user_setup((1024, 1024), 8)
+        run_tensor_user_setup((4096, 4096), 10)
+        run_tensor_user_setup((256, 256, 256), 7)
+        run_tensor_user_setup((4096, 1024), 9)
 elif len(sys.argv) > 3 and sys.argv[1] == "tensor10":
     mg = amg.Multigrid.poisson_tensor(int(sys.argv[2]), int(sys.argv[3]), stencil_transfers=len(sys.argv) < 5,
                                       **TENSOR_KW["jacobi"])
