@@ -131,6 +131,9 @@ _SIGS = {
     "amg_hip_block_pcg": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int64,
                                     _i64p, _f64p]),
     "amg_hip_block_must_move": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
+    "amg_hip_apply_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "amg_hip_pcg_mixed": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, _i64p, _f64p]),
+    "amg_hip_f32_must_move": (C.c_int, [C.c_void_p, _f64p]),
     "amg_hip_n_levels": (C.c_int32, [C.c_void_p]),
     "amg_hip_get_n_dofs": (C.c_int64, [C.c_void_p, C.c_int32]),
     "amg_hip_get_level_nnz": (C.c_int64, [C.c_void_p, C.c_int32]),
@@ -921,6 +924,24 @@ class Multigrid:
         it, rel = C.c_int64(0), C.c_double(0)
         _chk(lib().amg_hip_pcg(self._h, rtol, max_iters, C.byref(it), C.byref(rel)))
         return self.get_soln(0), it.value, rel.value
+
+    def apply_f32(self, v_dev, z_dev):
+        """z = M32^-1 v: apply_dev with the whole cycle in single precision (amg_hip_apply_f32);
+        device pointers to float64 vectors.  The solver's own vectors are not touched."""
+        _chk(lib().amg_hip_apply_f32(self._h, C.c_void_p(v_dev), C.c_void_p(z_dev)))
+
+    def pcg_mixed(self, rtol=1e-10, max_iters=100):
+        """pcg() with the single-precision cycle as M^-1, everything else in float64
+        (amg_hip_pcg_mixed); returns (x, iters, relres)."""
+        it, rel = C.c_int64(0), C.c_double(0)
+        _chk(lib().amg_hip_pcg_mixed(self._h, rtol, max_iters, C.byref(it), C.byref(rel)))
+        return self.get_soln(0), it.value, rel.value
+
+    def f32_must_move(self):
+        """bytes one apply_f32 has to move (amg_hip_f32_must_move)"""
+        b = C.c_double(0)
+        _chk(lib().amg_hip_f32_must_move(self._h, C.byref(b)))
+        return b.value
 
     # ---- block (multi-right-hand-side) cycles: amg_hip_block_* ---------------------------
     def _block_check(self, name, t, k=None):

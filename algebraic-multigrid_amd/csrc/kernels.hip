@@ -36,6 +36,8 @@
 // K-Galerkin (galerkin_*)   -- setup: R (A P) for the linear interpolation pair.
 // K-Halo / K-Gather         -- multi-GPU neighbour exchange and all-gather as
 //   graph-capturable kernels over hipIpc-mapped peer memory.
+// K-F32 (sell_f32_kernel, csr_f32_kernel, to_f32 / to_f64) -- the row kernels and transfers in
+//   float for the single-precision preconditioner of the fp64 PCG.
 // =============================================================================
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -2662,61 +2664,78 @@ hipError_t launch_dict(int mode, int64_t n, const DictRef& D, const double* x, c
 // f_H[j] = ((0 + 0.5 r[2j]) + 1.0 r[2j+1]) + 0.5 r[2j+2]   (Eigen column-major
 // scatter order of R*v, interpolator.hpp:64-68 with R = P^T, :132-134).
 // uH (optional) is zero-filled in the same pass (multigrid.hpp:278).
+// T: double (the V-cycle) or float (K-F32, the single-precision preconditioner); the pair type of
+// the 2-element lane accesses follows it.
+template <class T> struct Pair;
+template <> struct Pair<double> { using type = double2; };
+template <> struct Pair<float> { using type = float2; };
+template <class T>
+static bool pair_aligned(const T* p) { return (reinterpret_cast<uintptr_t>(p) & (2 * sizeof(T) - 1)) == 0; }
+
+template <class T>
 __global__ __launch_bounds__(256) void linear_restrict_kernel(
-    int64_t n_h, int64_t n_H, const double* __restrict__ r, double* __restrict__ fH,
-    double* __restrict__ uH) {
+    int64_t n_h, int64_t n_H, const T* __restrict__ r, T* __restrict__ fH,
+    T* __restrict__ uH) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n_H) return;
-  if (uH) uH[j] = 0.0;
+  if (uH) uH[j] = T(0.0);
   const int64_t i = 2 * j;
-  double s = 0.0;  // r is dead after this kernel: stream it
-  if (i < n_h) s += 0.5 * __builtin_nontemporal_load(r + i);
-  if (i + 1 < n_h) s += 1.0 * __builtin_nontemporal_load(r + i + 1);
-  if (i + 2 < n_h) s += 0.5 * r[i + 2];
+  T s = T(0.0);  // r is dead after this kernel: stream it
+  if (i < n_h) s += T(0.5) * __builtin_nontemporal_load(r + i);
+  if (i + 1 < n_h) s += T(1.0) * __builtin_nontemporal_load(r + i + 1);
+  if (i + 2 < n_h) s += T(0.5) * r[i + 2];
   fH[j] = s;
 }
 // u_h[i] = u_h[i] + t[i], t = P u_H: t[2j+1] = 0 + 1.0 u_H[j];
 // t[2j] = (0 + 0.5 u_H[j-1]) + 0.5 u_H[j]; rows past 2 n_H get t = 0
 // (interpolator.hpp:52-56, multigrid.hpp:294-296).
+template <class T>
 __global__ __launch_bounds__(256) void linear_prolong_add_kernel(
-    int64_t n_h, int64_t n_H, const double* __restrict__ uH, double* __restrict__ uh) {
+    int64_t n_h, int64_t n_H, const T* __restrict__ uH, T* __restrict__ uh) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_h) return;
-  double t = 0.0;
+  T t = T(0.0);
   const int64_t j = i >> 1;
   if (i & 1) {
-    if (j < n_H) t += 1.0 * uH[j];
+    if (j < n_H) t += T(1.0) * uH[j];
   } else {
-    if (j >= 1 && j - 1 < n_H) t += 0.5 * uH[j - 1];  // column j-1, row 2(j-1)+2
-    if (j < n_H) t += 0.5 * uH[j];                    // column j,   row 2j
+    if (j >= 1 && j - 1 < n_H) t += T(0.5) * uH[j - 1];  // column j-1, row 2(j-1)+2
+    if (j < n_H) t += T(0.5) * uH[j];                    // column j,   row 2j
   }
   uh[i] = uh[i] + t;
 }
-hipError_t launch_linear_restrict(int64_t n_h, int64_t n_H, const double* r, double* fH,
-                                  double* uH_zero, hipStream_t st) {
+template <class T>
+static hipError_t launch_linear_restrict_t(int64_t n_h, int64_t n_H, const T* r, T* fH, T* uH_zero,
+                                           hipStream_t st) {
   if (n_H <= 0) return hipSuccess;
-  hipLaunchKernelGGL(linear_restrict_kernel, dim3((unsigned)((n_H + 255) / 256)),
+  hipLaunchKernelGGL(linear_restrict_kernel<T>, dim3((unsigned)((n_H + 255) / 256)),
                      dim3(256), 0, st, n_h, n_H, r, fH, uH_zero);
   return hipGetLastError();
 }
-// Two fine rows (2j, 2j+1) per lane: 16-byte load/store of u, same arithmetic.
+hipError_t launch_linear_restrict(int64_t n_h, int64_t n_H, const double* r, double* fH,
+                                  double* uH_zero, hipStream_t st) {
+  return launch_linear_restrict_t<double>(n_h, n_H, r, fH, uH_zero, st);
+}
+// Two fine rows (2j, 2j+1) per lane: one pair load/store of u (16 bytes in double), same arithmetic.
+template <class T>
 __global__ __launch_bounds__(256) void linear_prolong_add2_kernel(
-    int64_t n_h, int64_t n_H, const double* __restrict__ uH, const double* uh_in, double* uh) {
+    int64_t n_h, int64_t n_H, const T* __restrict__ uH, const T* uh_in, T* uh) {
+  using P2 = typename Pair<T>::type;
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t i = 2 * j;
   if (i >= n_h) return;
-  double t0 = 0.0, t1 = 0.0;
-  const double b = (j < n_H) ? uH[j] : 0.0;
-  if (j >= 1 && j - 1 < n_H) t0 += 0.5 * uH[j - 1];
+  T t0 = T(0.0), t1 = T(0.0);
+  const T b = (j < n_H) ? uH[j] : T(0.0);
+  if (j >= 1 && j - 1 < n_H) t0 += T(0.5) * uH[j - 1];
   if (j < n_H) {
-    t0 += 0.5 * b;
-    t1 += 1.0 * b;
+    t0 += T(0.5) * b;
+    t1 += T(1.0) * b;
   }
   if (i + 1 < n_h) {
-    double2 u = *reinterpret_cast<const double2*>(uh_in + i);
+    P2 u = *reinterpret_cast<const P2*>(uh_in + i);
     u.x = u.x + t0;
     u.y = u.y + t1;
-    *reinterpret_cast<double2*>(uh + i) = u;
+    *reinterpret_cast<P2*>(uh + i) = u;
   } else {
     uh[i] = uh_in[i] + t0;
   }
@@ -2728,22 +2747,26 @@ hipError_t launch_linear_prolong_to(int64_t n_h, int64_t n_H, const double* uH,
   if (((reinterpret_cast<uintptr_t>(uh_in) | reinterpret_cast<uintptr_t>(uh_out)) & 15) != 0)
     return hipErrorInvalidValue;
   const int64_t nt = (n_h + 1) / 2;
-  hipLaunchKernelGGL(linear_prolong_add2_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(linear_prolong_add2_kernel<double>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0,
                      st, n_h, n_H, uH, uh_in, uh_out);
+  return hipGetLastError();
+}
+template <class T>
+static hipError_t launch_linear_prolong_add_t(int64_t n_h, int64_t n_H, const T* uH, T* uh, hipStream_t st) {
+  if (n_h <= 0) return hipSuccess;
+  if (pair_aligned(uh)) {
+    const int64_t nt = (n_h + 1) / 2;
+    hipLaunchKernelGGL(linear_prolong_add2_kernel<T>, dim3((unsigned)((nt + 255) / 256)), dim3(256),
+                       0, st, n_h, n_H, uH, uh, uh);
+  } else {
+    hipLaunchKernelGGL(linear_prolong_add_kernel<T>, dim3((unsigned)((n_h + 255) / 256)),
+                       dim3(256), 0, st, n_h, n_H, uH, uh);
+  }
   return hipGetLastError();
 }
 hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
                                      double* uh, hipStream_t st) {
-  if (n_h <= 0) return hipSuccess;
-  if ((reinterpret_cast<uintptr_t>(uh) & 15) == 0) {
-    const int64_t nt = (n_h + 1) / 2;
-    hipLaunchKernelGGL(linear_prolong_add2_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256),
-                       0, st, n_h, n_H, uH, uh, uh);
-  } else {
-    hipLaunchKernelGGL(linear_prolong_add_kernel, dim3((unsigned)((n_h + 255) / 256)),
-                       dim3(256), 0, st, n_h, n_H, uH, uh);
-  }
-  return hipGetLastError();
+  return launch_linear_prolong_add_t<double>(n_h, n_H, uH, uh, st);
 }
 
 // ------------------------------------- K-TensorRestrict / K-TensorProlong ---
@@ -2760,39 +2783,41 @@ struct TensorGrid {
 // One lane per coarse point (I, J, K): f_H = sum over k, j, i ascending (row order of R) of
 // (wz wy wx) r[(k ny + j) nx + i], from +0.0.  The x-neighbours 2I, 2I+1 come as one aligned
 // 16-byte load where the address allows (always, on rows of even length), 2I+2 as a scalar load of
-// the line the next lane's pair sits in.  r is dead after this kernel.  VEC: r is 16-byte aligned.
-template <bool VEC>
+// the line the next lane's pair sits in.  r is dead after this kernel.  VEC: r is 16-byte aligned
+// (T = float, K-F32: the pair is 8 bytes and r 8-byte aligned; the weights are exact in float too).
+template <class T, bool VEC>
 __global__ __launch_bounds__(256) void tensor_restrict_kernel(
-    TensorGrid g, const double* __restrict__ r, double* __restrict__ fH, double* __restrict__ uH) {
+    TensorGrid g, const T* __restrict__ r, T* __restrict__ fH, T* __restrict__ uH) {
+  using P2 = typename Pair<T>::type;
   const uint32_t nH = g.mx * g.my * g.mz;
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
   if (t >= nH) return;
   const uint32_t I = t % g.mx, q = t / g.mx, J = q % g.my, K = q / g.my;
-  if (uH) uH[t] = 0.0;
+  if (uH) uH[t] = T(0.0);
   const uint32_t i0 = 2u * I;        // i0 + 1 < nx always (I < floor(nx / 2))
   const bool third = i0 + 2u < g.nx;
-  double s = 0.0;
+  T s = T(0.0);
 #pragma unroll
   for (uint32_t tz = 0; tz < 3; ++tz) {
     if (!g.cz && tz > 0) break;
     const uint32_t k = g.cz ? 2u * K + tz : 0u;
     if (k >= g.nz) break;
-    const double wz = g.cz ? (tz == 1 ? 1.0 : 0.5) : 1.0;
+    const T wz = g.cz ? (tz == 1 ? T(1.0) : T(0.5)) : T(1.0);
 #pragma unroll
     for (uint32_t ty = 0; ty < 3; ++ty) {
       const uint32_t j = 2u * J + ty;
       if (j >= g.ny) break;
-      const double w = wz * (ty == 1 ? 1.0 : 0.5);
+      const T w = wz * (ty == 1 ? T(1.0) : T(0.5));
       const int64_t a = ((int64_t)k * g.ny + j) * g.nx + i0;  // a + 1 (and a + 2 when third) < n_h
-      double v0, v1, v2 = 0.0;
+      T v0, v1, v2 = T(0.0);
       if (VEC && (a & 1) == 0) {
-        const double2 p = *reinterpret_cast<const double2*>(r + a);
+        const P2 p = *reinterpret_cast<const P2*>(r + a);
         v0 = p.x;
         v1 = p.y;
         if (third) v2 = r[a + 2];
       } else if (VEC && third) {
         v0 = r[a];
-        const double2 p = *reinterpret_cast<const double2*>(r + a + 1);
+        const P2 p = *reinterpret_cast<const P2*>(r + a + 1);
         v1 = p.x;
         v2 = p.y;
       } else {
@@ -2800,9 +2825,9 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
         v1 = r[a + 1];
         if (third) v2 = r[a + 2];
       }
-      s += (w * 0.5) * v0;
-      s += (w * 1.0) * v1;
-      if (third) s += (w * 0.5) * v2;
+      s += (w * T(0.5)) * v0;
+      s += (w * T(1.0)) * v1;
+      if (third) s += (w * T(0.5)) * v2;
     }
   }
   fH[t] = s;
@@ -2812,9 +2837,10 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
 // (row order of P) of (wz wy wx) u_H[(K my + J) mx + I] from +0.0; 16-byte read-modify-write of
 // u_h where the address allows.  An odd fine index has the one coarse neighbour (i - 1) / 2 with
 // weight 1, an even one i / 2 - 1 and i / 2 with weight 0.5 (those that exist).
-template <bool VEC>
+template <class T, bool VEC>
 __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
-    TensorGrid g, const double* __restrict__ uH, double* uh) {
+    TensorGrid g, const T* __restrict__ uH, T* uh) {
+  using P2 = typename Pair<T>::type;
   const uint32_t px = (g.nx + 1u) / 2u;  // pairs per fine line
   const uint32_t total = px * g.ny * g.nz;
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -2822,7 +2848,7 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   const uint32_t p = t % px, row = t / px, j = row % g.ny, k = row / g.ny;
   // coarse neighbours along y and z: (index, weight, exists), ascending
   uint32_t Jc[2], Kc[2];
-  double wy[2], wz[2];
+  T wy[2], wz[2];
   bool oky[2], okz[2];
   if (j & 1u) {
     Jc[0] = (j - 1u) / 2u; wy[0] = 1.0; oky[0] = Jc[0] < g.my;
@@ -2843,19 +2869,19 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   }
   const bool left = p >= 1u && p - 1u < g.mx;  // coarse I = p - 1 feeds fine 2p
   const bool mid = p < g.mx;                   // coarse I = p feeds fine 2p and 2p + 1
-  double t0 = 0.0, t1 = 0.0;
+  T t0 = T(0.0), t1 = T(0.0);
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       if (okz[a] && oky[b]) {
-        const double w = wz[a] * wy[b];
-        const double* c = uH + ((int64_t)Kc[a] * g.my + Jc[b]) * g.mx;
-        if (left) t0 += (w * 0.5) * c[p - 1u];
+        const T w = wz[a] * wy[b];
+        const T* c = uH + ((int64_t)Kc[a] * g.my + Jc[b]) * g.mx;
+        if (left) t0 += (w * T(0.5)) * c[p - 1u];
         if (mid) {
-          const double m = c[p];
-          t0 += (w * 0.5) * m;
-          t1 += (w * 1.0) * m;
+          const T m = c[p];
+          t0 += (w * T(0.5)) * m;
+          t1 += (w * T(1.0)) * m;
         }
       }
     }
@@ -2863,10 +2889,10 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   const int64_t i = (int64_t)row * g.nx + 2u * p;
   if (2u * p + 1u < g.nx) {
     if (VEC && (i & 1) == 0) {
-      double2 u = *reinterpret_cast<const double2*>(uh + i);
+      P2 u = *reinterpret_cast<const P2*>(uh + i);
       u.x = u.x + t0;
       u.y = u.y + t1;
-      *reinterpret_cast<double2*>(uh + i) = u;
+      *reinterpret_cast<P2*>(uh + i) = u;
     } else {
       uh[i] = uh[i] + t0;
       uh[i + 1] = uh[i + 1] + t1;
@@ -2890,29 +2916,38 @@ static bool tensor_grid(int dim, const int64_t dims[3], TensorGrid* g) {
   g->cz = dim == 3 ? 1u : 0u;
   return true;
 }
-hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], const double* r, double* fH,
-                                  double* uH_zero, hipStream_t st) {
+template <class T>
+static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], const T* r, T* fH, T* uH_zero,
+                                           hipStream_t st) {
   TensorGrid g;
   if (!tensor_grid(dim, dims, &g)) return hipErrorInvalidValue;
   const uint32_t nH = g.mx * g.my * g.mz;
   const dim3 grid((nH + 255u) / 256u), block(256);
-  if ((reinterpret_cast<uintptr_t>(r) & 15) == 0)
-    hipLaunchKernelGGL(tensor_restrict_kernel<true>, grid, block, 0, st, g, r, fH, uH_zero);
+  if (pair_aligned(r))
+    hipLaunchKernelGGL((tensor_restrict_kernel<T, true>), grid, block, 0, st, g, r, fH, uH_zero);
   else
-    hipLaunchKernelGGL(tensor_restrict_kernel<false>, grid, block, 0, st, g, r, fH, uH_zero);
+    hipLaunchKernelGGL((tensor_restrict_kernel<T, false>), grid, block, 0, st, g, r, fH, uH_zero);
   return hipGetLastError();
 }
-hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], const double* uH, double* uh,
-                                     hipStream_t st) {
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], const double* r, double* fH,
+                                  double* uH_zero, hipStream_t st) {
+  return launch_tensor_restrict_t<double>(dim, dims, r, fH, uH_zero, st);
+}
+template <class T>
+static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], const T* uH, T* uh, hipStream_t st) {
   TensorGrid g;
   if (!tensor_grid(dim, dims, &g)) return hipErrorInvalidValue;
   const uint32_t total = ((g.nx + 1u) / 2u) * g.ny * g.nz;
   const dim3 grid((total + 255u) / 256u), block(256);
-  if ((reinterpret_cast<uintptr_t>(uh) & 15) == 0)
-    hipLaunchKernelGGL(tensor_prolong_add_kernel<true>, grid, block, 0, st, g, uH, uh);
+  if (pair_aligned(uh))
+    hipLaunchKernelGGL((tensor_prolong_add_kernel<T, true>), grid, block, 0, st, g, uH, uh);
   else
-    hipLaunchKernelGGL(tensor_prolong_add_kernel<false>, grid, block, 0, st, g, uH, uh);
+    hipLaunchKernelGGL((tensor_prolong_add_kernel<T, false>), grid, block, 0, st, g, uH, uh);
   return hipGetLastError();
+}
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], const double* uH, double* uh,
+                                     hipStream_t st) {
+  return launch_tensor_prolong_add_t<double>(dim, dims, uH, uh, st);
 }
 
 // First Jacobi sweep from a zero guess (coarse levels on the way down,
@@ -6333,5 +6368,263 @@ hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, doubl
                      L.v, L.w, omega, u);
   return hipGetLastError();
 }
+
+// ------------------------------------------------------------------ K-F32 ----
+// The single-precision preconditioner (solver.cpp: "fp32 cycle"): the V-cycle's row kernels on
+// float vectors and float matrix values.  The outer PCG stays in double; nothing here is bitwise
+// against the double kernels, only deterministic.
+//
+// sell_f32_kernel: sell_kernel's walk (one lane per storage row, panel offsets and 16- or 32-bit
+// indices SHARED with the double matrix, ascending column order, all loads of a pass issued before
+// the first use) with x, f, out, d and the values in float: a wave's value load is one 256-B
+// segment, its 16-bit index load one 128-B line.  Modes CSR_RESID, CSR_JACOBI and the Chebyshev
+// steps; no non-temporal form.
+template <int MODE>
+__device__ __forceinline__ float cheb_update_f32(float t, float xi, float di, float alpha, float beta, float& dn) {
+  const float z = t - xi;
+  dn = cheb_first(MODE) ? beta * z : alpha * di + beta * z;
+  return xi + dn;
+}
+template <int MODE>
+__device__ __forceinline__ void f32_row_epilogue(int64_t row, float fi, float xi, float di, float acc, float diag,
+                                                 float omega, float alpha, float* out, float* dvec) {
+  if (MODE == CSR_RESID || MODE == CSR_SPMV) {
+    out[row] = acc;
+  } else if (MODE == CSR_SPMV_ADD) {
+    out[row] = fi + acc;
+  } else if (MODE == CSR_JACOBI) {
+    out[row] = (diag == 0.0f) ? xi : xi + omega * ((fi - acc) / diag - xi);
+  } else {  // Chebyshev step
+    float dn;
+    out[row] = cheb_update_f32<MODE>((diag == 0.0f) ? xi : (fi - acc) / diag, xi, di, alpha, omega, dn);
+    if (!cheb_last(MODE)) dvec[row] = dn;
+  }
+}
+
+template <int MODE, bool IDX16>
+__global__ __launch_bounds__(256) void sell_f32_kernel(
+    int n, const int64_t* __restrict__ soff, const void* __restrict__ scol_v, const float* __restrict__ sval,
+    const float* x, const float* __restrict__ f, float* out, float omega, float* dvec, float alpha) {
+  const int32_t* __restrict__ scol = static_cast<const int32_t*>(scol_v);
+  const int16_t* __restrict__ scol16 = static_cast<const int16_t*>(scol_v);
+  const int row = blockIdx.x * 256 + threadIdx.x;  // storage row = row
+  const int s = row >> 6;
+  if ((s << 6) >= n) return;  // whole wave past the end
+  const int64_t o0 = soff[s], o1 = soff[s + 1];
+  const int w = (int)((o1 - o0) >> 6);  // wave-uniform panel width
+  const int64_t base = o0 + (row & 63);
+  const bool live = row < n;
+  float fi = 0.0f, xi = 0.0f, di = 0.0f;
+  if (live) {
+    fi = f[row];
+    if (mode_jac(MODE)) xi = x[row];
+    if (mode_cheb(MODE) && !cheb_first(MODE)) di = dvec[row];
+  }
+  float acc = (MODE == CSR_RESID) ? fi : 0.0f;
+  float diag = 0.0f;
+  auto pass = [&](int j0, auto UU) {
+    constexpr int UN = decltype(UU)::value;
+    int32_t c[UN];
+    float v[UN], xx[UN];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int j = j0 + u < w ? j0 + u : j0;
+      const int64_t at = base + ((int64_t)j << 6);
+      if (IDX16) {
+        const int d = scol16[at];
+        c[u] = (d == -32768) ? -1 : row + d;
+      } else {
+        c[u] = scol[at];
+      }
+      v[u] = sval[at];
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) xx[u] = x[c[u] >= 0 ? c[u] : 0];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      if (j0 + u < w && c[u] >= 0) {
+        if (MODE == CSR_RESID) {
+          acc -= v[u] * xx[u];
+        } else {
+          if (c[u] == row) diag = v[u];
+          else acc += v[u] * xx[u];
+        }
+      }
+    }
+  };
+  if (w <= 3) pass(0, std::integral_constant<int, 3>{});
+  else if (w <= 5) pass(0, std::integral_constant<int, 5>{});
+  else if (w <= 7) pass(0, std::integral_constant<int, 7>{});
+  else if (w <= 9) pass(0, std::integral_constant<int, 9>{});
+  else
+    for (int j0 = 0; j0 < w; j0 += 8) pass(j0, std::integral_constant<int, 8>{});
+  if (live) f32_row_epilogue<MODE>(row, fi, xi, di, acc, diag, omega, alpha, out, dvec);
+}
+
+// csr_f32_kernel: plain CSR, one lane per row (the levels SELL would pad by more than a quarter, and
+// the CSR transfers P / R of the classical hierarchies: small or irregular matrices).  Modes as
+// above plus CSR_SPMV and CSR_SPMV_ADD (f may be out).  rowptr / col are the double matrix's.
+template <int MODE>
+__global__ __launch_bounds__(256) void csr_f32_kernel(
+    int64_t n, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ val,
+    const float* __restrict__ x, const float* f, float* out, float omega, float* dvec, float alpha) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n) return;
+  const int32_t rs = rowptr[row], re = rowptr[row + 1];
+  float fi = 0.0f, xi = 0.0f, di = 0.0f;
+  if (MODE != CSR_SPMV) fi = f[row];
+  if (mode_jac(MODE)) xi = x[row];
+  if (mode_cheb(MODE) && !cheb_first(MODE)) di = dvec[row];
+  float acc = (MODE == CSR_RESID) ? fi : 0.0f;
+  float diag = 0.0f;
+  constexpr int U = 4;  // gathers issued together; the sum itself stays in row order
+  for (int32_t p = rs; p < re; p += U) {
+    int32_t c[U];
+    float v[U], xx[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int32_t q = p + u < re ? p + u : p;
+      c[u] = col[q];
+      v[u] = val[q];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) xx[u] = x[c[u]];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (p + u < re) {
+        if (MODE == CSR_RESID) {
+          acc -= v[u] * xx[u];
+        } else if (mode_jac(MODE)) {
+          if ((int64_t)c[u] == row) diag = v[u];
+          else acc += v[u] * xx[u];
+        } else {
+          acc += v[u] * xx[u];
+        }
+      }
+    }
+  }
+  f32_row_epilogue<MODE>(row, fi, xi, di, acc, diag, omega, alpha, out, dvec);
+}
+
+#define AMG_F32_MODES(X)                                             \
+  switch (mode) {                                                    \
+    case CSR_RESID: X(CSR_RESID); break;                             \
+    case CSR_JACOBI: X(CSR_JACOBI); break;                           \
+    case cheb_kernel_mode(false, false): X(cheb_kernel_mode(false, false)); break; \
+    case cheb_kernel_mode(true, false): X(cheb_kernel_mode(true, false)); break;   \
+    case cheb_kernel_mode(false, true): X(cheb_kernel_mode(false, true)); break;   \
+    case cheb_kernel_mode(true, true): X(cheb_kernel_mode(true, true)); break;     \
+    default: return hipErrorInvalidValue;                            \
+  }
+
+hipError_t launch_sell_f32(int mode, int64_t n, int idx16, const int64_t* soff, const void* scol, const float* sval,
+                           const float* x, const float* f, float* out, float omega, float* dvec, float alpha,
+                           hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (n >= ((int64_t)1 << 31) - 256 || x == out) return hipErrorInvalidValue;
+  if (mode_cheb(mode) && !dvec) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + 255) / 256));
+#define AMG_F32_SELL(M)                                                                                          \
+  if (idx16 & 1)                                                                                                 \
+    hipLaunchKernelGGL((sell_f32_kernel<M, true>), grid, dim3(256), 0, st, (int)n, soff, scol, sval, x, f, out,  \
+                       omega, dvec, alpha);                                                                      \
+  else                                                                                                           \
+    hipLaunchKernelGGL((sell_f32_kernel<M, false>), grid, dim3(256), 0, st, (int)n, soff, scol, sval, x, f, out, \
+                       omega, dvec, alpha)
+  AMG_F32_MODES(AMG_F32_SELL)
+#undef AMG_F32_SELL
+  return hipGetLastError();
+}
+
+hipError_t launch_csr_f32(int mode, int64_t n, const int32_t* rowptr, const int32_t* col, const float* val,
+                          const float* x, const float* f, float* out, float omega, float* dvec, float alpha,
+                          hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (x == out) return hipErrorInvalidValue;
+  if (mode_cheb(mode) && !dvec) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + 255) / 256));
+#define AMG_F32_CSR(M) \
+  hipLaunchKernelGGL((csr_f32_kernel<M>), grid, dim3(256), 0, st, n, rowptr, col, val, x, f, out, omega, dvec, alpha)
+  switch (mode) {
+    case CSR_SPMV: AMG_F32_CSR(CSR_SPMV); return hipGetLastError();
+    case CSR_SPMV_ADD: AMG_F32_CSR(CSR_SPMV_ADD); return hipGetLastError();
+  }
+  AMG_F32_MODES(AMG_F32_CSR)
+#undef AMG_F32_CSR
+  return hipGetLastError();
+}
+#undef AMG_F32_MODES
+
+// double <-> float, four entries per lane: 16-byte lane accesses on the float side and on both
+// halves of the double side when both pointers are 16-byte aligned (VEC), else one entry per lane.
+template <bool VEC>
+__global__ __launch_bounds__(256) void to_f32_kernel(int64_t n, const double* __restrict__ src,
+                                                     float* __restrict__ dst) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (!VEC) {
+    if (t < n) dst[t] = (float)src[t];
+    return;
+  }
+  const int64_t i = 4 * t;
+  if (i + 3 < n) {
+    const double2 a = *reinterpret_cast<const double2*>(src + i);
+    const double2 b = *reinterpret_cast<const double2*>(src + i + 2);
+    *reinterpret_cast<float4*>(dst + i) = make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
+  } else {
+    for (int64_t k = i; k < n; ++k) dst[k] = (float)src[k];
+  }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void to_f64_kernel(int64_t n, const float* __restrict__ src,
+                                                     double* __restrict__ dst) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (!VEC) {
+    if (t < n) dst[t] = (double)src[t];
+    return;
+  }
+  const int64_t i = 4 * t;
+  if (i + 3 < n) {
+    const float4 a = *reinterpret_cast<const float4*>(src + i);
+    *reinterpret_cast<double2*>(dst + i) = make_double2((double)a.x, (double)a.y);
+    *reinterpret_cast<double2*>(dst + i + 2) = make_double2((double)a.z, (double)a.w);
+  } else {
+    for (int64_t k = i; k < n; ++k) dst[k] = (double)src[k];
+  }
+}
+hipError_t launch_to_f32(int64_t n, const double* src, float* dst, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0)
+    hipLaunchKernelGGL(to_f32_kernel<true>, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, st, n, src, dst);
+  else
+    hipLaunchKernelGGL(to_f32_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, src, dst);
+  return hipGetLastError();
+}
+hipError_t launch_to_f64(int64_t n, const float* src, double* dst, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0)
+    hipLaunchKernelGGL(to_f64_kernel<true>, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, st, n, src, dst);
+  else
+    hipLaunchKernelGGL(to_f64_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, src, dst);
+  return hipGetLastError();
+}
+
+// the float instantiations of the matrix-free transfers (K-Restrict / K-ProlongAdd, K-TensorRestrict /
+// K-TensorProlong): same kernels, T = float
+hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, float* fH, float* uH_zero,
+                                      hipStream_t st) {
+  return launch_linear_restrict_t<float>(n_h, n_H, r, fH, uH_zero, st);
+}
+hipError_t launch_linear_prolong_add_f32(int64_t n_h, int64_t n_H, const float* uH, float* uh, hipStream_t st) {
+  return launch_linear_prolong_add_t<float>(n_h, n_H, uH, uh, st);
+}
+hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], const float* r, float* fH, float* uH_zero,
+                                      hipStream_t st) {
+  return launch_tensor_restrict_t<float>(dim, dims, r, fH, uH_zero, st);
+}
+hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], const float* uH, float* uh,
+                                         hipStream_t st) {
+  return launch_tensor_prolong_add_t<float>(dim, dims, uH, uh, st);
+}
+
 
 }  // namespace amg_hip

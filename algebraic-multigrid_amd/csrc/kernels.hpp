@@ -512,4 +512,26 @@ hipError_t launch_block_pcg_update_xr(int kp, int64_t n, const double* num, cons
 hipError_t launch_block_pcg_update_p(int kp, int64_t n, const double* num, const double* den, const int32_t* act,
                                      double* p, const double* z, hipStream_t st);
 
+// K-F32 (kernels.hip): the row kernels and transfers of the single-precision preconditioner.  mode:
+// CSR_RESID, CSR_JACOBI or cheb_kernel_mode(first, last) (omega = the step's beta, dvec = its d);
+// launch_csr_f32 also takes CSR_SPMV and CSR_SPMV_ADD (f may be out).  soff / scol (idx16 bit 0:
+// 16-bit relative indices) and rowptr / col are the double matrix's arrays; x != out.
+hipError_t launch_sell_f32(int mode, int64_t n, int idx16, const int64_t* soff, const void* scol, const float* sval,
+                           const float* x, const float* f, float* out, float omega, float* dvec, float alpha,
+                           hipStream_t st);
+hipError_t launch_csr_f32(int mode, int64_t n, const int32_t* rowptr, const int32_t* col, const float* val,
+                          const float* x, const float* f, float* out, float omega, float* dvec, float alpha,
+                          hipStream_t st);
+// dst[i] = (float)src[i] / (double)src[i], round to nearest
+hipError_t launch_to_f32(int64_t n, const double* src, float* dst, hipStream_t st);
+hipError_t launch_to_f64(int64_t n, const float* src, double* dst, hipStream_t st);
+// float instantiations of launch_linear_restrict / _prolong_add and launch_tensor_restrict / _prolong_add
+hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, float* fH, float* uH_zero,
+                                      hipStream_t st);
+hipError_t launch_linear_prolong_add_f32(int64_t n_h, int64_t n_H, const float* uH, float* uh, hipStream_t st);
+hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], const float* r, float* fH, float* uH_zero,
+                                      hipStream_t st);
+hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], const float* uH, float* uh,
+                                         hipStream_t st);
+
 }  // namespace amg_hip

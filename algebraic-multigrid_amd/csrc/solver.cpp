@@ -1175,6 +1175,35 @@ struct Block {
   }
 };
 
+// Single-precision cycle (amg_hip_apply_f32 / amg_hip_pcg_mixed): float copies of the matrix values
+// the double sweep and residual of a level read (the SELL panel offsets and indices, the CSR row
+// pointers and columns are the double matrix's own arrays), float level vectors, and the cycle's
+// captured graph.  Made at the first call, freed with the solver, never rebuilt.
+struct F32Mat {
+  const DevMat* src = nullptr;  // layout and index arrays
+  DevMem val;                   // src's sval (SELL) or csr.val (CSR) as floats
+};
+struct F32Level {
+  F32Mat rows, cols_own;
+  const F32Mat* cols = nullptr;  // what the Jacobi sweep walks; = &rows on a bitwise symmetric level
+  DevMem u, f, r, tmp, d;        // floats; d: Chebyshev
+  DevMem pval, rval;             // CSR transfers (kind 0): values of P_rows / R_rows as floats
+};
+struct F32 {
+  bool ready = false;
+  std::vector<F32Level> lv;
+  DevMem cf, cy, cx;             // coarsest system in double: f, scratch, x
+  DevMem pr, pz;                 // amg_hip_pcg_mixed: r and z (doubles, level-0 size)
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  void reset_graph() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    exec = nullptr;
+    graph = nullptr;
+  }
+};
+
 // amg_hip_set_tail_fusion / AMG_HIP_TAIL_FUSION=1: K-Tail (deepest levels + coarsest solve in one
 // launch).  Off by default: bit-identical, and measured 0.5 % SLOWER than one launch per step on the
 // 4096^2 cycle (1282 / 1291 / 1293 against 1299 / 1301 / 1294 V-cycles/s, alternating runs).
@@ -1220,8 +1249,14 @@ struct amg_hip_solver {
     block_mm[0] += mat;
     block_mm[1] += per_col;
   }
+  F32 f32;
+  // bytes of one single-precision application, counted by the dry enqueue (amg_hip_f32_must_move)
+  bool f32_acct = false;
+  double f32_mm = 0;
+  void facct(double bytes) { if (f32_acct) f32_mm += bytes; }
 
   ~amg_hip_solver() {
+    f32.reset_graph();
     blk.reset_graphs();
     slab.reset_graphs();
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
@@ -3468,6 +3503,240 @@ amg_hip_status block_sums_to_host(amg_hip_solver* s, int kp, const double* x, co
   return AMG_HIP_OK;
 }
 
+// ---- fp32 cycle (single-precision preconditioner) -------------------------------
+// multigrid.hpp:263-305 from a zero guess on float vectors with the K-F32 kernels, one plain launch
+// per step on the solver's stream (enqueue_block_vcycle's order).  Not bitwise against the double
+// cycle: a zero-filled u_H plus the normal sweep stands for the from-zero sweep, and the coarsest
+// system is solved in double with the solver's factor ("Single-precision preconditioner").
+// steps 3 to 5 of the argument checks (include/amg_hip.h), then the device
+amg_hip_status f32_supported(amg_hip_solver* s) {
+  if (s->opt.window)
+    return fail(AMG_HIP_EUNSUPPORTED, "single-precision cycle: a window solver (opt.window) is not supported");
+  if (s->opt.smoother != AMG_HIP_SM_JACOBI && s->opt.smoother != AMG_HIP_SM_CHEBYSHEV)
+    return fail(AMG_HIP_EUNSUPPORTED, std::string("single-precision cycle: the smoother ") +
+                                          block_smoother_name(s->opt.smoother) +
+                                          " is not supported (true Jacobi and Chebyshev are)");
+  if (s->lv.size() < 2)
+    return fail(AMG_HIP_EUNSUPPORTED, "single-precision cycle: a one-level solver has no cycle (the direct solve "
+                                      "stays in double); use amg_hip_apply");
+  return set_device(s);
+}
+
+amg_hip_status f32_copy_values(const DevMat& A, F32Mat* M, hipStream_t st) {
+  M->src = &A;
+  const double* src = A.sell ? A.sval.as<double>() : A.csr.v();
+  const int64_t count = A.sell ? A.slots : A.csr.nnz;
+  HIP_TRY(M->val.alloc(sizeof(float) * (size_t)std::max<int64_t>(count, 1)));
+  HIP_TRY(launch_to_f32(count, src, M->val.as<float>(), st));
+  return AMG_HIP_OK;
+}
+
+amg_hip_status ensure_f32(amg_hip_solver* s) {
+  F32& F = s->f32;
+  if (F.ready) return AMG_HIP_OK;
+  const int nl = (int)s->lv.size();
+  const bool jac = s->opt.smoother == AMG_HIP_SM_JACOBI;
+  for (int l = 0; l + 1 < nl; ++l) {
+    const Level& L = s->lv[l];
+    if (L.A_rows.dict || (jac && L.A_cols().dict))
+      return fail(AMG_HIP_EUNSUPPORTED,
+                  "single-precision cycle: level " + std::to_string(l) +
+                      " is stored in the dictionary layout (AMG_HIP_LAYOUT_DICT), which has no float form; "
+                      "create the solver with `layout` = AMG_HIP_LAYOUT_SELL");
+  }
+  hipStream_t st = s->stream;
+  amg_hip_status r;
+  std::vector<F32Level> lv((size_t)nl);
+  for (int l = 0; l < nl; ++l) {
+    const Level& L = s->lv[l];
+    F32Level& Q = lv[(size_t)l];
+    const size_t bytes = sizeof(float) * (size_t)L.n;
+    HIP_TRY(Q.u.alloc(bytes));
+    HIP_TRY(Q.f.alloc(bytes));
+    if (l + 1 == nl) continue;  // the coarsest level only takes the direct solve
+    HIP_TRY(Q.r.alloc(bytes));
+    HIP_TRY(Q.tmp.alloc(bytes));
+    if (!jac) HIP_TRY(Q.d.alloc(bytes));
+    if ((r = f32_copy_values(L.A_rows, &Q.rows, st)) != AMG_HIP_OK) return r;
+    if (jac && !L.symmetric)
+      if ((r = f32_copy_values(L.A_cols_own, &Q.cols_own, st)) != AMG_HIP_OK) return r;
+    if (!(L.linear && s->opt.stencil_transfers) && !L.tensor_stencil) {
+      HIP_TRY(Q.pval.alloc(sizeof(float) * (size_t)std::max<int64_t>(L.P_rows.nnz, 1)));
+      HIP_TRY(Q.rval.alloc(sizeof(float) * (size_t)std::max<int64_t>(L.R_rows.nnz, 1)));
+      HIP_TRY(launch_to_f32(L.P_rows.nnz, L.P_rows.v(), Q.pval.as<float>(), st));
+      HIP_TRY(launch_to_f32(L.R_rows.nnz, L.R_rows.v(), Q.rval.as<float>(), st));
+    }
+  }
+  const size_t cb = sizeof(double) * (size_t)s->lv[(size_t)nl - 1].n;
+  HIP_TRY(F.cf.alloc(cb));
+  HIP_TRY(F.cy.alloc(cb));
+  HIP_TRY(F.cx.alloc(cb));
+  F.lv = std::move(lv);
+  for (int l = 0; l + 1 < nl; ++l) {  // after the move: the vector's storage is final
+    F32Level& Q = F.lv[(size_t)l];
+    Q.cols = (jac && !s->lv[l].symmetric) ? &Q.cols_own : &Q.rows;
+  }
+  F.ready = true;
+  return AMG_HIP_OK;
+}
+
+// one launch of a level matrix in float; bytes: SELL 4 + w per entry and 8 per panel, CSR 8 per
+// entry and 4 per row pointer
+hipError_t launch_mat_f32(int mode, const F32Mat& M, const float* x, const float* f, float* out, float omega,
+                          float* dvec, float alpha, hipStream_t st) {
+  const DevMat& A = *M.src;
+  if (A.sell)
+    return launch_sell_f32(mode, A.n_rows, A.idx16, A.soff.as<int64_t>(), A.scol.p, M.val.as<float>(), x, f, out,
+                           omega, dvec, alpha, st);
+  const DevCsr& C = A.csr;
+  return launch_csr_f32(mode, C.n_rows, C.rowptr(), C.col(), M.val.as<float>(), x, f, out, omega, dvec, alpha, st);
+}
+double mat_bytes_f32(const F32Mat& M) {
+  const DevMat& A = *M.src;
+  if (A.sell) return (double)A.slots * ((A.idx16 & 1) ? 6.0 : 8.0) + 8.0 * (double)((A.n_rows + 63) / 64);
+  return 8.0 * (double)A.csr.nnz + 4.0 * (double)(A.csr.n_rows + 1);
+}
+
+// dry: count the bytes, launch nothing (amg_hip_f32_must_move)
+#define F32_DO(expr)              \
+  do {                            \
+    if (!dry) HIP_TRY(expr);      \
+  } while (0)
+
+amg_hip_status enqueue_f32_smooth(amg_hip_solver* s, int l, bool dry) {
+  const Level& L = s->lv[l];
+  F32Level& Q = s->f32.lv[(size_t)l];
+  hipStream_t st = s->stream;
+  const double n = (double)L.n;
+  float* a = Q.u.as<float>();
+  float* b = Q.tmp.as<float>();
+  int64_t passes = 0;
+  if (s->opt.smoother == AMG_HIP_SM_JACOBI) {
+    for (int it = 0; it < s->opt.smoother_iters; ++it) {
+      F32_DO(launch_mat_f32(CSR_JACOBI, *Q.cols, a, Q.f.as<float>(), b, (float)s->opt.omega, nullptr, 0.0f, st));
+      s->facct(mat_bytes_f32(*Q.cols) + 12.0 * n);  // matrix; x, f, out
+      std::swap(a, b);
+      ++passes;
+    }
+  } else {
+    const int k = s->opt.cheb_degree;
+    std::vector<double> alpha, beta;
+    cheb_coefs(L.cheb_lo, L.cheb_hi, k, &alpha, &beta);  // in double, rounded at the launch
+    for (int it = 0; it < s->opt.smoother_iters; ++it) {
+      for (int j = 0; j < k; ++j) {
+        const bool first = j == 0, last = j == k - 1;
+        F32_DO(launch_mat_f32(cheb_kernel_mode(first, last), Q.rows, a, Q.f.as<float>(), b, (float)beta[(size_t)j],
+                              Q.d.as<float>(), (float)alpha[(size_t)j], st));
+        s->facct(mat_bytes_f32(Q.rows) + 12.0 * n + (first ? 0.0 : 4.0 * n) + (last ? 0.0 : 4.0 * n));
+        std::swap(a, b);
+        ++passes;
+      }
+    }
+  }
+  if (passes & 1) {  // result sits in tmp: bring it home (keeps the graph static)
+    F32_DO(hipMemcpyAsync(Q.u.p, Q.tmp.p, sizeof(float) * (size_t)L.n, hipMemcpyDeviceToDevice, st));
+    s->facct(8.0 * n);
+  }
+  return AMG_HIP_OK;
+}
+
+// level 0's f holds the right-hand side, its u receives the result
+amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
+  const int nl = (int)s->lv.size();
+  hipStream_t st = s->stream;
+  F32& F = s->f32;
+  amg_hip_status r;
+  F32_DO(hipMemsetAsync(F.lv[0].u.p, 0, sizeof(float) * (size_t)s->lv[0].n, st));  // the zero guess
+  s->facct(4.0 * (double)s->lv[0].n);
+  for (int l = 0; l + 1 < nl; ++l) {
+    const Level& L = s->lv[l];
+    const Level& C = s->lv[l + 1];
+    F32Level& Q = F.lv[(size_t)l];
+    F32Level& QC = F.lv[(size_t)l + 1];
+    if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;  // :268
+    F32_DO(launch_mat_f32(CSR_RESID, Q.rows, Q.u.as<float>(), Q.f.as<float>(), Q.r.as<float>(), 1.0f, nullptr, 0.0f,
+                          st));                                        // :272-274
+    s->facct(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);
+    if (L.linear && s->opt.stencil_transfers) {                        // :278 + :281-282
+      F32_DO(launch_linear_restrict_f32(L.n, C.n, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
+      s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
+    } else if (L.tensor_stencil) {
+      F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
+      s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
+    } else {
+      F32_DO(hipMemsetAsync(QC.u.p, 0, sizeof(float) * (size_t)C.n, st));
+      const DevCsr& R = L.R_rows;
+      F32_DO(launch_csr_f32(CSR_SPMV, R.n_rows, R.rowptr(), R.col(), Q.rval.as<float>(), Q.r.as<float>(), nullptr,
+                            QC.f.as<float>(), 1.0f, nullptr, 0.0f, st));
+      s->facct(8.0 * (double)R.nnz + 4.0 * (double)(R.n_rows + 1) + 4.0 * (double)L.n + 8.0 * (double)C.n);
+    }
+  }
+  {  // :287-288 in double: widen f_L, the solver's factor, round the result
+    const Level& C = s->lv[(size_t)nl - 1];
+    F32Level& QC = F.lv[(size_t)nl - 1];
+    F32_DO(launch_to_f64(C.n, QC.f.as<float>(), F.cf.as<double>(), st));
+    F32_DO(launch_coarse(s->coarse, F.cf.as<double>(), F.cy.as<double>(), F.cx.as<double>(), st));
+    F32_DO(launch_to_f32(C.n, F.cx.as<double>(), QC.u.as<float>(), st));
+    // the two conversions; the band of L forwards and backwards, D, f, u (enqueue_vcycle_body)
+    s->facct(24.0 * (double)C.n + 16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * (double)C.n);
+  }
+  for (int l = nl - 2; l >= 0; --l) {                                  // :291
+    const Level& L = s->lv[l];
+    const Level& C = s->lv[l + 1];
+    F32Level& Q = F.lv[(size_t)l];
+    F32Level& QC = F.lv[(size_t)l + 1];
+    if (L.linear && s->opt.stencil_transfers) {                        // :294-296
+      F32_DO(launch_linear_prolong_add_f32(L.n, C.n, QC.u.as<float>(), Q.u.as<float>(), st));
+      s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
+    } else if (L.tensor_stencil) {
+      F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, QC.u.as<float>(), Q.u.as<float>(), st));
+      s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
+    } else {
+      const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
+      F32_DO(launch_csr_f32(CSR_SPMV_ADD, P.n_rows, P.rowptr(), P.col(), Q.pval.as<float>(), QC.u.as<float>(),
+                            Q.u.as<float>(), Q.u.as<float>(), 1.0f, nullptr, 0.0f, st));
+      s->facct(8.0 * (double)P.nnz + 4.0 * (double)(P.n_rows + 1) + 4.0 * (double)C.n + 8.0 * (double)L.n);
+    }
+    if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;  // :300
+  }
+  return AMG_HIP_OK;
+}
+#undef F32_DO
+
+// z = M32^-1 v: round v into level 0's float right-hand side, the cycle (its captured graph, or the
+// same enqueue eagerly with use_graph = 0), widen level 0's float solution into z
+amg_hip_status f32_apply(amg_hip_solver* s, const double* v, double* z) {
+  F32& F = s->f32;
+  const int64_t n = s->lv[0].n;
+  HIP_TRY(launch_to_f32(n, v, F.lv[0].f.as<float>(), s->stream));
+  if (!s->opt.use_graph) {
+    amg_hip_status r = enqueue_f32_vcycle(s, false);
+    if (r != AMG_HIP_OK) return r;
+  } else {
+    if (!F.exec) {
+      HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+      amg_hip_status r = enqueue_f32_vcycle(s, false);
+      hipGraph_t gr = nullptr;
+      hipError_t e = hipStreamEndCapture(s->stream, &gr);
+      if (r != AMG_HIP_OK) {
+        if (gr) (void)hipGraphDestroy(gr);
+        return r;
+      }
+      if (e != hipSuccess) return fail(AMG_HIP_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+      e = hipGraphInstantiate(&F.exec, gr, nullptr, nullptr, 0);
+      if (e != hipSuccess) {
+        (void)hipGraphDestroy(gr);
+        F.exec = nullptr;
+        return fail(AMG_HIP_EHIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+      }
+      F.graph = gr;
+    }
+    HIP_TRY(hipGraphLaunch(F.exec, s->stream));
+  }
+  HIP_TRY(launch_to_f64(n, F.lv[0].u.as<float>(), z, s->stream));
+  return AMG_HIP_OK;
+}
+
 }  // namespace
 
 namespace amg_hip {
@@ -4230,13 +4499,12 @@ amg_hip_status amg_hip_apply(amg_hip_solver* s, const double* v_dev, double* z_d
 // iteration level 0's f holds the residual r and level 0's u receives z = M^-1 r (no copies
 // around the cycle); x, p, q = A p live in the work vectors.  Start: x = the level-0
 // solution; on return it holds the result and f is b again.
-amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, int64_t* iters,
-                           double* relres) {
-  if (!s) return fail(AMG_HIP_EINVAL, "null solver");
-  if (!(rtol >= 0) || max_iters < 0) return fail(AMG_HIP_EINVAL, "bad tolerance / iteration limit");
-  amg_hip_status st0 = set_device(s);
-  if (st0 != AMG_HIP_OK) return st0;
-  if ((st0 = pcg_alloc(s)) != AMG_HIP_OK) return st0;
+// The iteration shared by amg_hip_pcg and amg_hip_pcg_mixed.  r: where the residual lives, z: where
+// precond() leaves M^-1 r (enqueued on the solver's stream).  b is taken from level 0's f and parked
+// while r may be that very vector; x starts as level 0's u and is copied back there at the end.
+extern "C++" template <class Precond>
+static amg_hip_status pcg_run(amg_hip_solver* s, double rtol, int64_t max_iters, int64_t* iters, double* relres,
+                              double* r, double* z, Precond precond) {
   Level& L = s->lv[0];
   const int64_t n = L.n;
   const size_t bytes = sizeof(double) * (size_t)n;
@@ -4245,8 +4513,6 @@ amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, in
   double* p = s->pcg_p.as<double>();
   double* q = s->pcg_q.as<double>();
   double* bsv = s->pcg_b.as<double>();
-  double* r = L.f.as<double>();   // residual lives where the cycle expects its right-hand side
-  double* z = L.u.as<double>();   // and the cycle leaves M^-1 r here
   double* sc = s->scratch.as<double>();
   double* part = sc;              // 1024 partials
   double* d_rz = sc + 1030;       // device scalars: r.z, p.q, new r.z, r.r
@@ -4255,12 +4521,12 @@ amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, in
   double* d_rr = sc + 1033;
   double h[2];
   // b . b
-  HIP_TRY(launch_dot(n, r, r, d_rr, part, st));
+  HIP_TRY(launch_dot(n, L.f.as<double>(), L.f.as<double>(), d_rr, part, st));
   HIP_TRY(hipMemcpyAsync(h, d_rr, sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const double bnorm = std::sqrt(h[0]);
-  HIP_TRY(hipMemcpyAsync(bsv, r, bytes, hipMemcpyDeviceToDevice, st));   // park b
-  HIP_TRY(hipMemcpyAsync(x, z, bytes, hipMemcpyDeviceToDevice, st));     // x = u_0
+  HIP_TRY(hipMemcpyAsync(bsv, L.f.p, bytes, hipMemcpyDeviceToDevice, st));   // park b
+  HIP_TRY(hipMemcpyAsync(x, L.u.p, bytes, hipMemcpyDeviceToDevice, st));     // x = u_0
   // r = b - A x (multigrid.hpp:272-274 arithmetic), in place of b
   HIP_TRY(launch_mat(CSR_RESID, L.A_rows, x, bsv, r, 1.0, st));
   int64_t it = 0;
@@ -4279,8 +4545,7 @@ amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, in
   rel = bnorm > 0 ? std::sqrt(h[0]) / bnorm : std::sqrt(h[0]);
   if (rel <= rtol || max_iters == 0) return finish();
   // z = M^-1 r; p = z; rz = r . z
-  HIP_TRY(hipMemsetAsync(z, 0, bytes, st));
-  amg_hip_status rc = amg_hip_vcycles(s, 1);
+  amg_hip_status rc = precond();
   if (rc != AMG_HIP_OK) return rc;
   HIP_TRY(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, st));
   HIP_TRY(launch_dot(n, r, z, d_rz, part, st));
@@ -4294,13 +4559,71 @@ amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, in
     it += 1;
     rel = bnorm > 0 ? std::sqrt(h[0]) / bnorm : std::sqrt(h[0]);
     if (!(rel > rtol) || it >= max_iters) break;                         // NaN leaves too
-    HIP_TRY(hipMemsetAsync(z, 0, bytes, st));
-    if ((rc = amg_hip_vcycles(s, 1)) != AMG_HIP_OK) return rc;           // z = M^-1 r
+    if ((rc = precond()) != AMG_HIP_OK) return rc;                       // z = M^-1 r
     HIP_TRY(launch_dot(n, r, z, d_rzn, part, st));
     HIP_TRY(launch_pcg_update_p(n, d_rzn, d_rz, p, z, st));              // beta = rz_new / rz
     HIP_TRY(hipMemcpyAsync(d_rz, d_rzn, sizeof(double), hipMemcpyDeviceToDevice, st));
   }
   return finish();
+}
+
+amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, int64_t* iters,
+                           double* relres) {
+  if (!s) return fail(AMG_HIP_EINVAL, "null solver");
+  if (!(rtol >= 0) || max_iters < 0) return fail(AMG_HIP_EINVAL, "bad tolerance / iteration limit");
+  amg_hip_status st0 = set_device(s);
+  if (st0 != AMG_HIP_OK) return st0;
+  if ((st0 = pcg_alloc(s)) != AMG_HIP_OK) return st0;
+  Level& L = s->lv[0];
+  // the residual lives where the cycle expects its right-hand side, and the cycle leaves M^-1 r in u
+  return pcg_run(s, rtol, max_iters, iters, relres, L.f.as<double>(), L.u.as<double>(), [s, &L]() -> amg_hip_status {
+    HIP_TRY(hipMemsetAsync(L.u.p, 0, sizeof(double) * (size_t)L.n, s->stream));
+    return amg_hip_vcycles(s, 1);
+  });
+}
+
+// ---- single-precision preconditioner (include/amg_hip.h) ------------------------------------
+amg_hip_status amg_hip_apply_f32(amg_hip_solver* s, const double* v_dev, double* z_dev) {
+  if (!s || !v_dev || !z_dev) return fail(AMG_HIP_EINVAL, "null argument");
+  amg_hip_status r = f32_supported(s);
+  if (r != AMG_HIP_OK) return r;
+  if ((r = ensure_f32(s)) != AMG_HIP_OK) return r;
+  return f32_apply(s, v_dev, z_dev);
+}
+
+// r and z are ordinary device vectors of this path: level 0's f stays b and its u the start vector
+// until the result replaces it
+amg_hip_status amg_hip_pcg_mixed(amg_hip_solver* s, double rtol, int64_t max_iters, int64_t* iters,
+                                 double* relres) {
+  if (!s) return fail(AMG_HIP_EINVAL, "null solver");
+  if (!(rtol >= 0) || max_iters < 0) return fail(AMG_HIP_EINVAL, "bad tolerance / iteration limit");
+  amg_hip_status st0 = f32_supported(s);
+  if (st0 != AMG_HIP_OK) return st0;
+  if ((st0 = ensure_f32(s)) != AMG_HIP_OK) return st0;
+  if ((st0 = pcg_alloc(s)) != AMG_HIP_OK) return st0;
+  F32& F = s->f32;
+  if (!F.pr.p) {
+    const size_t bytes = sizeof(double) * (size_t)s->lv[0].n;
+    HIP_TRY(F.pr.alloc(bytes));
+    HIP_TRY(F.pz.alloc(bytes));
+  }
+  double* r = F.pr.as<double>();
+  double* z = F.pz.as<double>();
+  return pcg_run(s, rtol, max_iters, iters, relres, r, z, [s, r, z]() { return f32_apply(s, r, z); });
+}
+
+amg_hip_status amg_hip_f32_must_move(amg_hip_solver* s, double* bytes) {
+  if (!s || !bytes) return fail(AMG_HIP_EINVAL, "null argument");
+  amg_hip_status r = f32_supported(s);
+  if (r != AMG_HIP_OK) return r;
+  if ((r = ensure_f32(s)) != AMG_HIP_OK) return r;
+  s->f32_mm = 0.0;
+  s->f32_acct = true;
+  r = enqueue_f32_vcycle(s, true);
+  s->f32_acct = false;
+  if (r != AMG_HIP_OK) return r;
+  *bytes = s->f32_mm + 24.0 * (double)s->lv[0].n;  // v -> float and float -> z: 8 + 4 bytes per row each
+  return AMG_HIP_OK;
 }
 
 amg_hip_status amg_hip_solve(amg_hip_solver* s, double tol, int64_t every, int64_t n_iters,

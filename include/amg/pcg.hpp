@@ -18,12 +18,15 @@ class PCG {
   size_t max_iters;
   size_t n_done{0};
   EleType relres{0};
+  bool mixed;
 
  public:
   // mg: its smoother must make the cycle symmetric (SparseGaussSeidel, TrueJacobi); a
-  // user-defined SmootherBase runs on the host and cannot take part in the device iteration
-  PCG(Multigrid<EleType>* mg_, EleType rtol_ = 1e-10, size_t max_iters_ = 100)
-      : mg(mg_), rtol(rtol_), max_iters(max_iters_) {
+  // user-defined SmootherBase runs on the host and cannot take part in the device iteration.
+  // mixed_precision_: the V-cycle runs in single precision (amg_hip_pcg_mixed; true Jacobi or
+  // Chebyshev smoother, no dictionary-coded level), the iteration itself stays in double
+  PCG(Multigrid<EleType>* mg_, EleType rtol_ = 1e-10, size_t max_iters_ = 100, bool mixed_precision_ = false)
+      : mg(mg_), rtol(rtol_), max_iters(max_iters_), mixed(mixed_precision_) {
     if (!mg) throw std::invalid_argument("`mg` must not be null");
     if (!mg->runs_on_device())
       throw std::invalid_argument("PCG needs a Multigrid whose smoother runs on the device");
@@ -32,7 +35,8 @@ class PCG {
   const Vector& solve() {
     int64_t it = 0;
     double rel = 0;
-    detail::check(amg_hip_pcg(mg->native_handle(), (double)rtol, (int64_t)max_iters, &it, &rel));
+    detail::check((mixed ? amg_hip_pcg_mixed : amg_hip_pcg)(mg->native_handle(), (double)rtol, (int64_t)max_iters,
+                                                           &it, &rel));
     n_done = (size_t)it;
     relres = (EleType)rel;
     if (relres <= rtol) std::cout << "PCG converged after " << n_done << " iterations." << std::endl;

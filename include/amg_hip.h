@@ -579,6 +579,39 @@ amg_hip_status amg_hip_block_pcg(amg_hip_solver* s, int32_t k, const double* B, 
  * 12 B per entry + 4 B per row), every vector 8 k bytes per row (padded columns not counted). */
 amg_hip_status amg_hip_block_must_move(amg_hip_solver* s, int32_t k, double* bytes);
 
+/* ---- single-precision preconditioner ("Single-precision preconditioner") -------------
+ * The V-cycle of amg_hip_apply with every level vector, every level matrix value and every transfer
+ * in float, as M^-1 of a PCG whose SpMV, dot products, updates and stopping rule stay in double.  CG
+ * only needs a fixed, symmetric, reasonably accurate M^-1; the outer iteration keeps fp64 accuracy.
+ * The path owns float copies of the matrix VALUES (SELL-64 panel offsets and 16- / 32-bit indices and
+ * CSR row pointers / columns are shared with the double matrices) and float level vectors, made at
+ * the first call and freed with the solver; the coarsest system is solved in double with the
+ * existing factor.  The solver's own level vectors, right-hand side and solution are never touched,
+ * and no existing entry point changes its results.  Not bitwise against anything; deterministic, and
+ * use_graph = 0 / 1 give the same bits.
+ * v is not scaled: entries of v below about 1e-30 in magnitude lose bits to float denormals, and
+ * above 3e38 overflow.  Harmless for rtol >= 1e-12 on right-hand sides of ordinary magnitude.
+ *
+ * Checks, in this order, before the device is touched: AMG_HIP_EINVAL null pointers; AMG_HIP_EINVAL
+ * bad rtol / max_iters (amg_hip_pcg_mixed); AMG_HIP_EUNSUPPORTED a window solver; AMG_HIP_EUNSUPPORTED
+ * a smoother other than AMG_HIP_SM_JACOBI / AMG_HIP_SM_CHEBYSHEV; AMG_HIP_EUNSUPPORTED a one-level
+ * solver.  Then a host_only solver fails (AMG_HIP_EINVAL), then AMG_HIP_EUNSUPPORTED for a level
+ * stored in the dictionary layout (the level in the message): create the solver with
+ * layout = AMG_HIP_LAYOUT_SELL.
+ *
+ * amg_hip_apply_f32: z = M32^-1 v.  v_dev / z_dev: DEVICE pointers to n_dofs(0) doubles (may alias);
+ * v is rounded to float, one float V-cycle from zero runs, the result is widened into z.  Enqueued on
+ * the solver's stream.                                                                          */
+amg_hip_status amg_hip_apply_f32(amg_hip_solver* s, const double* v_dev, double* z_dev);
+/* amg_hip_pcg step for step (same arguments, same contract: starts from the level-0 solution,
+ * leaves the result there, the right-hand side is b again) with amg_hip_apply_f32's cycle as M^-1. */
+amg_hip_status amg_hip_pcg_mixed(amg_hip_solver* s, double rtol, int64_t max_iters, int64_t* iters,
+                                 double* relres);
+/* Bytes the launches of one amg_hip_apply_f32 have to move: per SELL entry 4 + w (w = 2 or 4 index
+ * bytes) and 8 per panel, CSR 8 per entry + 4 per row pointer, every float vector pass 4 per row; the
+ * coarsest solve and the conversions around it and around the cycle in their own widths. */
+amg_hip_status amg_hip_f32_must_move(amg_hip_solver* s, double* bytes);
+
 /* Getters, multigrid.hpp:339-354. */
 int32_t amg_hip_n_levels(const amg_hip_solver* s);
 int64_t amg_hip_get_n_dofs(const amg_hip_solver* s, int32_t level);

@@ -9,6 +9,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py tensor10 <n> <levels> [csr]                 ten cycles of one tensor hierarchy (kernel traces)
        config_bench.py tensor-setup [<dim> <n> <levels>]           set-up seconds of the full-coarsening hierarchy, host and device construction alternating
        config_bench.py tensor-user-setup [<nx> <ny> <nz> <levels>] set-up seconds for a variable-coefficient operator assembled on the GPU: host constructor and amg_hip_create_tensor_dev alternating
+       config_bench.py mixed [<nx> <ny> <nz> <levels>]             amg_hip_pcg and amg_hip_pcg_mixed (single-precision V-cycle) alternating on a variable-coefficient operator, true Jacobi 2+2 and Chebyshev(2) 1+1
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -309,6 +310,63 @@ def run_tensor_user_setup(dims, L, reps=3, tol=1e-8, cap=60):
     keep.close()
 
 
+def run_mixed(dims, L, reps=3, rtol=1e-8, applies=10):
+    """amg_hip_pcg (double V-cycle) and amg_hip_pcg_mixed (float V-cycle) to `rtol` from x = 0,
+    alternating in one process, `reps` repeats, on the variable-coefficient operator of
+    tensor-user-setup (tensor_dev, layout SELL), for true Jacobi 2+2 and Chebyshev(2) 1+1.  Per run:
+    iterations and wall ms (the solvers synchronise themselves); then ms per preconditioner application
+    over `applies` calls closed by one synchronise, and the must-move bytes of one application over
+    that time as a fraction of 8 TB/s.  The double figure is the V-cycle alone (vcycle(): what
+    amg_hip_pcg runs per iteration, amg_hip_cycle_must_move bytes); amg_hip_apply, which also parks and
+    restores level 0's two vectors (64 bytes per row), is timed next to it.  The mixed figure is
+    amg_hip_apply_f32 (what amg_hip_pcg_mixed runs per iteration, amg_hip_f32_must_move bytes)."""
+    import torch
+    crow, col, val, b = torch_diffusion(dims)
+    torch.cuda.synchronize()
+    tag = " x ".join(str(d) for d in dims)
+    n = b.numel()
+    z = torch.empty_like(b)
+    for sm in ("jacobi", "cheb"):
+        mg = amg.Multigrid.tensor_dev(crow, col, val, b, dims, L, layout=amg.LAYOUT_SELL, **TENSOR_KW[sm])
+        mg.sync()
+        calls = {"double": (mg.pcg, mg.apply_dev, mg.cycle_must_move()), "mixed": (mg.pcg_mixed, mg.apply_f32, None)}
+        calls["mixed"] = calls["mixed"][:2] + (mg.f32_must_move(),)
+        for name in calls:  # first calls: work vectors, float copies, captured graphs
+            calls[name][1](b.data_ptr(), z.data_ptr())
+        mg.sync()
+        best = {}
+        for rep_ in range(reps):
+            for name, (solve, apply, mm) in calls.items():
+                mg.zero_vec(0, "u")
+                mg.sync()
+                t0 = time.perf_counter()
+                _, it, rel = solve(rtol=rtol, max_iters=100)
+                dt = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                for _ in range(applies):
+                    apply(b.data_ptr(), z.data_ptr())
+                mg.sync()
+                da = (time.perf_counter() - t0) / applies
+                extra = ""
+                if name == "double":  # the cycle without amg_hip_apply's park and restore
+                    mg.zero_vec(0, "u")
+                    mg.sync()
+                    t0 = time.perf_counter()
+                    mg.vcycle(applies)
+                    mg.sync()
+                    extra = f" (amg_hip_apply {da * 1e3:.3f} ms)"
+                    da = (time.perf_counter() - t0) / applies
+                best[name] = (min(best.get(name, (dt, da))[0], dt), min(best.get(name, (dt, da))[1], da))
+                print(f"mixed {tag} {L} levels {sm}, {name} rep {rep_}: {it} iterations, {dt * 1e3:.2f} ms to "
+                      f"{rtol:g} (relres {rel:.2e}), {da * 1e3:.3f} ms per application{extra}, must-move {mm / 1e6:.1f} MB = "
+                      f"{mm / da / 8e12 * 100:.1f} % of 8 TB/s", flush=True)
+        print(f"mixed {tag} {L} levels {sm} ({n} dofs): best solve double {best['double'][0] * 1e3:.2f} ms, mixed "
+              f"{best['mixed'][0] * 1e3:.2f} ms, ratio {best['double'][0] / best['mixed'][0]:.2f}; best application "
+              f"double {best['double'][1] * 1e3:.3f} ms, mixed {best['mixed'][1] * 1e3:.3f} ms, ratio "
+              f"{best['double'][1] / best['mixed'][1]:.2f}", flush=True)
+        mg.close()
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -409,6 +467,15 @@ elif len(sys.argv) > 1 and sys.argv[1] == "tensor-user-setup":
         run_tensor_user_setup((4096, 4096), 10)
         run_tensor_user_setup((256, 256, 256), 7)
         run_tensor_user_setup((4096, 1024), 9)
+elif len(sys.argv) > 1 and sys.argv[1] == "mixed":
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    if len(sys.argv) > 5:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_mixed(d if d[2] > 1 else d[:2], int(sys.argv[5]))
+    else:
+        run_mixed((1024, 1024), 8)
+        run_mixed((4096, 4096), 10)
+        run_mixed((256, 256, 256), 7)
 elif len(sys.argv) > 3 and sys.argv[1] == "tensor10":
     mg = amg.Multigrid.poisson_tensor(int(sys.argv[2]), int(sys.argv[3]), stencil_transfers=len(sys.argv) < 5,
                                       **TENSOR_KW["jacobi"])
