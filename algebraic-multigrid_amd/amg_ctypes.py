@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libamg_hip.so")
 
 OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED, ECOMM = 0, 1, 2, 3, 4, 5
 SM_SPGS, SM_REF_JACOBI, SM_SOR, SM_JACOBI, SM_MULTICOLOR_GS, SM_CHEBYSHEV, SM_LINE_JACOBI = 0, 1, 2, 3, 4, 5, 6
+SM_LINE_ALT = 7
 LAYOUT_AUTO, LAYOUT_CSR, LAYOUT_SELL, LAYOUT_DICT = 0, 1, 2, 3
 
 _i32p = C.POINTER(C.c_int32)
@@ -179,6 +180,9 @@ _SIGS = {
     "amg_hip_line_stride": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "amg_hip_smooth_line": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, C.c_int64, C.c_double, C.c_int64,
                                       _f64p, _f64p]),
+    "amg_hip_line_directions": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "amg_hip_smooth_line_alt": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, C.c_int32, C.POINTER(C.c_int64),
+                                          C.c_double, C.c_int64, C.c_int32, _f64p, _f64p]),
     "amg_hip_smooth_chebyshev": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int32,
                                            C.c_double, C.c_double, C.c_int64]),
     "amg_hip_cycle_bytes": (C.c_int, [C.c_void_p, _f64p, _f64p]),
@@ -884,6 +888,17 @@ class Multigrid:
         _chk(st)
         return s.value
 
+    def line_directions(self, level):
+        """The strides of the alternating line smoother's directions on `level`, ascending
+        (amg_hip_line_directions): a list of 0 to 3 integers."""
+        nd = C.c_int32(0)
+        st3 = (C.c_int64 * 3)()
+        st = lib().amg_hip_line_directions(self._h, int(level), C.byref(nd), st3)
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return [int(st3[d]) for d in range(nd.value)]
+
     def coarse_solve_kind(self):
         return {0: "band (one wave, sequential, bit-exact)", 1: "spike (partitioned, parallel)",
                 2: "band-wide (blocked sequential, any half-bandwidth, bit-exact)",
@@ -1068,6 +1083,22 @@ def smooth_line(colptr, rowind, val, u, f, stride=0, omega=0.7, iters=1):
     u = np.array(u, dtype=np.float64, copy=True)
     st = lib().amg_hip_smooth_line(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), int(stride),
                                    float(omega), int(iters), _p64(u), _p64(f))
+    if st == EINVAL:
+        raise ValueError(lib().amg_hip_last_error().decode())
+    _chk(st)
+    return u
+
+
+def smooth_line_alt(colptr, rowind, val, u, f, dims, omega=0.8, iters=1, reverse=False):
+    """amg_hip_smooth_line_alt: `iters` applications of the alternating line smoother on the grid
+    `dims` (2 or 3 entries, x fastest), directions ascending (descending with `reverse`); returns the
+    new u."""
+    colptr, rowind, val, f = _a32(colptr), _a32(rowind), _a64(val), _a64(f)
+    u = np.array(u, dtype=np.float64, copy=True)
+    dims = [int(d) for d in dims]
+    d3 = (C.c_int64 * 3)(*(dims + [1] * (3 - len(dims)))[:3]) if 1 <= len(dims) <= 3 else (C.c_int64 * 3)(0, 0, 0)
+    st = lib().amg_hip_smooth_line_alt(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), len(dims), d3,
+                                       float(omega), int(iters), 1 if reverse else 0, _p64(u), _p64(f))
     if st == EINVAL:
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)

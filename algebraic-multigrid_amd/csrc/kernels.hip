@@ -5951,15 +5951,19 @@ constexpr int LINE_INT = LINE_SEG - 1;  // interior rows of a full segment
 __host__ __device__ inline bool line_bad_pivot(double p) { return !(p == p) || p == 0.0 || p - p != 0.0; }
 
 // rows of T from CSR(A): dl -> L.dl, diagonal -> L.ip, du -> L.w
-__host__ __device__ inline void line_extract_row(int64_t i, int64_t n, int64_t s, const int32_t* rowptr,
+// m > 0: the chain positions p = i / s form grid lines of m positions, and an entry that joins two
+// lines (AMG_HIP_SM_LINE_ALT: +-nx across a plane end) stays out of T
+__host__ __device__ inline void line_extract_row(int64_t i, int64_t n, int64_t s, int64_t m, const int32_t* rowptr,
                                                  const int32_t* col, const double* val, double* dl, double* dd,
                                                  double* du) {
   double a = 0.0, b = 0.0, c = 0.0;
+  const int64_t q = m > 0 ? (i / s) % m : 0;
+  const bool lower = m <= 0 || q > 0, upper = m <= 0 || q < m - 1;
   for (int32_t p = rowptr[i]; p < rowptr[i + 1]; ++p) {
     const int64_t j = col[p];
     if (j == i) b = val[p];
-    else if (j == i - s) a = val[p];
-    else if (j == i + s) c = val[p];
+    else if (j == i - s && lower) a = val[p];
+    else if (j == i + s && upper) c = val[p];
   }
   dl[i] = a;
   dd[i] = b;
@@ -6034,7 +6038,7 @@ __global__ __launch_bounds__(256) void line_extract_kernel(LineRef L, const int3
                                                            const int32_t* __restrict__ col,
                                                            const double* __restrict__ val) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < L.n) line_extract_row(i, L.n, L.s, rowptr, col, val, L.dl, L.ip, L.w);
+  if (i < L.n) line_extract_row(i, L.n, L.s, L.m, rowptr, col, val, L.dl, L.ip, L.w);
 }
 __global__ __launch_bounds__(256) void line_factor_seg_kernel(LineRef L, int64_t nch, int64_t nseg,
                                                               unsigned long long* bad) {
@@ -6324,7 +6328,8 @@ hipError_t launch_line_setup(const LineRef& L, const int32_t* rowptr, const int3
   hipLaunchKernelGGL(line_factor_chain_kernel, line_grid(nch), dim3(256), 0, st, L, nch, o);
   return hipGetLastError();
 }
-int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32_t* col, const double* val) {
+int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32_t* col, const double* val,
+                        int64_t m) {
   std::vector<double> a[5];
   for (auto& x : a) x.assign((size_t)n, 0.0);
   LineRef L;
@@ -6335,7 +6340,7 @@ int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32
   L.cp = a[2].data();
   L.v = a[3].data();
   L.w = a[4].data();
-  for (int64_t i = 0; i < n; ++i) line_extract_row(i, n, s, rowptr, col, val, L.dl, L.ip, L.w);
+  for (int64_t i = 0; i < n; ++i) line_extract_row(i, n, s, m, rowptr, col, val, L.dl, L.ip, L.w);
   const int64_t nch = line_chains(n, L.s), nseg = line_segments(n, L.s);
   int64_t bad = -1;
   auto note = [&](int64_t b) {
@@ -6366,6 +6371,169 @@ hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, doubl
   }
   hipLaunchKernelGGL(line_update_kernel, line_grid(n), dim3(256), 0, st, n, (uint32_t)s, y,
                      L.v, L.w, omega, u);
+  return hipGetLastError();
+}
+
+// ---- K-LineX: the x lines of a tensor grid (AMG_HIP_SM_LINE_ALT; kernels.hpp: LineXRef) --------
+// T_x is tridiagonal on the flat index with its couplings across line ends removed, so the plain
+// Thomas factors (dl, ip = 1 / pivot, cp = upper / pivot) carry dl = 0 on the first and cp = 0 on
+// the last row of every line: a walk along the flat index restarts by itself at every line.  The
+// level is cut into runs of `len` rows (whole lines: one line of nx >= LINEX_COLS rows, or
+// LINEX_COLS / nx short ones).  One wave owns LINEX_RUNS neighbouring runs and walks them in
+// chunks of LINEX_COLS columns: all 64 lanes load the chunk (a 512-byte row of every run:
+// neighbouring lanes, neighbouring addresses) into LDS, lanes 0 .. LINEX_RUNS - 1 each walk one
+// run's row of the chunk there and carry the recurrence in a register to the next chunk, all lanes
+// write the chunk back.  The loads of the next chunk are issued before the walk of this one.
+//   linex_kernel<LX_FACTOR>  dd, du -> ip, cp (setup)
+//   linex_kernel<LX_FWD>     r <- y: y_i = (r_i - dl_i y_(i-1)) ip_i          (in place)
+//   linex_kernel<LX_BWD>     x_i = y_i - cp_i x_(i+1); u_i += omega x_i       (chunks descending)
+namespace {
+enum { LX_FACTOR = 0, LX_FWD = 1, LX_BWD = 2 };
+constexpr int LINEX_PITCH = LINEX_COLS + 1;  // doubles per LDS row: the walking lanes hit different banks
+
+__host__ __device__ inline void linex_row(int64_t i, int64_t nx, const int32_t* rowptr, const int32_t* col,
+                                          const double* val, double& dl, double& dd, double& du) {
+  const int64_t x = i % nx;
+  dl = dd = du = 0.0;
+  for (int32_t p = rowptr[i]; p < rowptr[i + 1]; ++p) {
+    const int64_t j = col[p];
+    if (j == i) dd = val[p];
+    else if (j == i - 1 && x > 0) dl = val[p];
+    else if (j == i + 1 && x < nx - 1) du = val[p];
+  }
+}
+__global__ __launch_bounds__(256) void linex_extract_kernel(LineXRef L, const int32_t* __restrict__ rowptr,
+                                                            const int32_t* __restrict__ col,
+                                                            const double* __restrict__ val) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < L.n) linex_row(i, L.nx, rowptr, col, val, L.dl[i], L.ip[i], L.cp[i]);
+}
+
+// a, b, c: the three arrays a chunk reads (FACTOR: dl, dd, du; FWD: r, dl, ip; BWD: y, cp, u);
+// o1, o2: what it writes (FACTOR: ip, cp; FWD: y = a; BWD: u = c)
+template <int MODE>
+__global__ __launch_bounds__(64) void linex_kernel(int64_t n, int64_t len, int64_t nruns, const double* a,
+                                                   const double* b, const double* c, double* o1, double* o2,
+                                                   double omega, unsigned long long* bad) {
+  __shared__ double sa[LINEX_RUNS * LINEX_PITCH], sb[LINEX_RUNS * LINEX_PITCH], sc[LINEX_RUNS * LINEX_PITCH];
+  const int lane = threadIdx.x;
+  const int64_t run0 = (int64_t)blockIdx.x * LINEX_RUNS;
+  const int64_t nchunks = (len + LINEX_COLS - 1) / LINEX_COLS;
+  double ra[LINEX_RUNS], rb[LINEX_RUNS], rc[LINEX_RUNS];
+  // row of run q at this lane's column of chunk ch, or -1 outside the run / the level
+  auto row_of = [&](int q, int64_t ch) -> int64_t {
+    const int64_t run = run0 + q, k = ch * LINEX_COLS + lane;
+    if (run >= nruns || k >= len) return -1;
+    const int64_t i = run * len + k;
+    return i < n ? i : -1;
+  };
+  auto fetch = [&](int64_t ch) {
+#pragma unroll
+    for (int q = 0; q < LINEX_RUNS; ++q) {
+      const int64_t i = row_of(q, ch);
+      ra[q] = i >= 0 ? a[i] : 0.0;
+      rb[q] = i >= 0 ? b[i] : 0.0;
+      rc[q] = i >= 0 ? c[i] : 0.0;
+    }
+  };
+  double carry = 0.0;  // lanes < LINEX_RUNS: cp (FACTOR), y (FWD) or x (BWD) of the row walked last
+  fetch(MODE == LX_BWD ? nchunks - 1 : 0);
+  for (int64_t t = 0; t < nchunks; ++t) {
+    const int64_t ch = MODE == LX_BWD ? nchunks - 1 - t : t;
+#pragma unroll
+    for (int q = 0; q < LINEX_RUNS; ++q) {
+      sa[q * LINEX_PITCH + lane] = ra[q];
+      sb[q * LINEX_PITCH + lane] = rb[q];
+      sc[q * LINEX_PITCH + lane] = rc[q];
+    }
+    __syncthreads();
+    if (t + 1 < nchunks) fetch(MODE == LX_BWD ? ch - 1 : ch + 1);
+    if (lane < LINEX_RUNS) {
+      double* pa = sa + lane * LINEX_PITCH;
+      double* pb = sb + lane * LINEX_PITCH;
+      double* pc = sc + lane * LINEX_PITCH;
+      if (MODE == LX_FACTOR) {
+        const int64_t i0 = (run0 + lane) * len + ch * LINEX_COLS;
+        int64_t first_bad = -1;
+#pragma unroll 8
+        for (int k = 0; k < LINEX_COLS; ++k) {
+          const double piv = pb[k] - pa[k] * carry;
+          const bool in = run0 + lane < nruns && ch * LINEX_COLS + k < len && i0 + k < n;
+          if (in && first_bad < 0 && line_bad_pivot(piv)) first_bad = i0 + k;
+          const double ip = in ? 1.0 / piv : 0.0;
+          carry = pc[k] * ip;
+          pb[k] = ip;
+          pc[k] = carry;
+        }
+        if (first_bad >= 0) atomicMin(bad, (unsigned long long)first_bad);
+      } else if (MODE == LX_FWD) {
+#pragma unroll 8
+        for (int k = 0; k < LINEX_COLS; ++k) {
+          carry = (pa[k] - pb[k] * carry) * pc[k];
+          pa[k] = carry;
+        }
+      } else {
+#pragma unroll 8
+        for (int k = LINEX_COLS - 1; k >= 0; --k) {
+          carry = pa[k] - pb[k] * carry;
+          pa[k] = carry;
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < LINEX_RUNS; ++q) {
+      const int64_t i = row_of(q, ch);
+      if (i < 0) continue;
+      if (MODE == LX_FACTOR) {
+        o1[i] = sb[q * LINEX_PITCH + lane];
+        o2[i] = sc[q * LINEX_PITCH + lane];
+      } else if (MODE == LX_FWD) {
+        o1[i] = sa[q * LINEX_PITCH + lane];
+      } else {
+        o1[i] = sc[q * LINEX_PITCH + lane] + omega * sa[q * LINEX_PITCH + lane];
+      }
+    }
+    __syncthreads();
+  }
+}
+inline bool linex_ok(const LineXRef& L) {
+  return L.n > 0 && L.nx >= 1 && L.n < ((int64_t)1 << 31) && L.n % L.nx == 0;
+}
+}  // namespace
+
+int64_t linex_run(int64_t nx) { return nx >= LINEX_COLS ? nx : nx * (LINEX_COLS / nx); }
+
+hipError_t launch_linex_setup(const LineXRef& L, const int32_t* rowptr, const int32_t* col, const double* val,
+                              uint64_t* bad, hipStream_t st) {
+  if (!linex_ok(L)) return hipErrorInvalidValue;
+  auto* o = reinterpret_cast<unsigned long long*>(bad);
+  const int64_t len = linex_run(L.nx), nruns = (L.n + len - 1) / len;
+  hipLaunchKernelGGL(line_init2_kernel, dim3(1), dim3(64), 0, st, o, ~0ull, 0ull);
+  hipLaunchKernelGGL(linex_extract_kernel, line_grid(L.n), dim3(256), 0, st, L, rowptr, col, val);
+  hipLaunchKernelGGL(linex_kernel<LX_FACTOR>, line_grid(nruns, LINEX_RUNS), dim3(64), 0, st, L.n, len, nruns, L.dl,
+                     L.ip, L.cp, L.ip, L.cp, 0.0, o);
+  return hipGetLastError();
+}
+int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int32_t* col, const double* val) {
+  double cprev = 0.0;
+  for (int64_t i = 0; i < n; ++i) {
+    double dl, dd, du;
+    linex_row(i, nx, rowptr, col, val, dl, dd, du);
+    const double piv = dd - dl * cprev;
+    if (line_bad_pivot(piv)) return i;
+    cprev = du * (1.0 / piv);
+  }
+  return -1;
+}
+hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double omega, hipStream_t st) {
+  if (!linex_ok(L)) return hipErrorInvalidValue;
+  const int64_t len = linex_run(L.nx), nruns = (L.n + len - 1) / len;
+  const dim3 grid = line_grid(nruns, LINEX_RUNS);
+  hipLaunchKernelGGL(linex_kernel<LX_FWD>, grid, dim3(64), 0, st, L.n, len, nruns, r, L.dl, L.ip, r, nullptr, 0.0,
+                     nullptr);
+  hipLaunchKernelGGL(linex_kernel<LX_BWD>, grid, dim3(64), 0, st, L.n, len, nruns, r, L.cp, u, u, nullptr, omega,
+                     nullptr);
   return hipGetLastError();
 }
 

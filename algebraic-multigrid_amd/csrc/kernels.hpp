@@ -59,6 +59,7 @@ hipError_t launch_gershgorin(int64_t n, const int32_t* rowptr, const int32_t* co
 constexpr int LINE_SEG = 32;
 struct LineRef {
   int64_t n = 0, s = 1;
+  int64_t m = 0;  // set-up only, > 0: chain positions come in grid lines of m; entries across a line end stay out of T
   double *dl = nullptr, *ip = nullptr, *cp = nullptr, *v = nullptr, *w = nullptr;
 };
 // stride rule on a device CSR matrix: out[1] = the largest distance d = |j - i| >= 1 whose weight
@@ -72,12 +73,31 @@ int64_t line_stride_host(int64_t n, const int32_t* rowptr, const int32_t* col, c
 // discarded; returns that row or -1.
 hipError_t launch_line_setup(const LineRef& L, const int32_t* rowptr, const int32_t* col, const double* val,
                              uint64_t* bad, hipStream_t st);
-int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32_t* col, const double* val);
+int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32_t* col, const double* val,
+                        int64_t m = 0);
 // u += omega T^-1 r.  y: n doubles of scratch, r is not written.  Three launches (two on a level
 // without separators): line_seg_kernel, line_sep_few_kernel or line_sep_many_kernel, line_update_kernel.
 hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
                              hipStream_t st);
 bool line_few_chains(int64_t s);  // the reduced systems run as one workgroup per chain
+// K-LineX, the x lines of a tensor grid (AMG_HIP_SM_LINE_ALT): n / nx lines of nx rows, each
+// contiguous in memory.  T_x = the diagonal of A and its entries at column offsets +-1 that stay
+// inside a line; dl, ip, cp (n doubles each) are its plain Thomas factors, dl = 0 on the first and
+// cp = 0 on the last row of every line.  A wave walks LINEX_RUNS runs of whole lines (linex_run(nx)
+// rows each) in chunks of LINEX_COLS columns through LDS (kernels.hip: K-LineX).  n < 2^31.
+constexpr int LINEX_COLS = 64, LINEX_RUNS = 8;
+struct LineXRef {
+  int64_t n = 0, nx = 1;
+  double *dl = nullptr, *ip = nullptr, *cp = nullptr;
+};
+int64_t linex_run(int64_t nx);  // rows of one run: nx, or the whole lines that fit LINEX_COLS
+// extract T_x from CSR(A) and factor it; bad as launch_line_setup.  linex_setup_host: the same
+// elimination on the host, factors discarded; returns the first row with a bad pivot or -1.
+hipError_t launch_linex_setup(const LineXRef& L, const int32_t* rowptr, const int32_t* col, const double* val,
+                              uint64_t* bad, hipStream_t st);
+int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int32_t* col, const double* val);
+// u += omega T_x^-1 r; r is overwritten (the forward values).  Two launches.
+hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double omega, hipStream_t st);
 // Same operations on a SELL-64 matrix (64-row panels, lane-interleaved):
 // soff[n/64 + 1] panel offsets, scol/sval padded with col = -1.
 // idx16 bit 0: scol holds int16 offsets from the diagonal column (pad -32768);

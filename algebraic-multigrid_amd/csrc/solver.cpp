@@ -814,18 +814,22 @@ std::string line_options_error(double omega) {
     return "line smoother: `omega` must lie in (0, 2), got " + std::to_string(omega);
   return "";
 }
-std::string line_bad_pivot(int l, int64_t row) {
-  return "line smoother: level " + std::to_string(l) + " row " + std::to_string(row) +
+// dir: the direction of AMG_HIP_SM_LINE_ALT whose elimination failed ("x", "y", "z"), else null
+std::string line_bad_pivot(int l, int64_t row, const char* dir = nullptr) {
+  return "line smoother: level " + std::to_string(l) + (dir ? std::string(" direction ") + dir : std::string()) +
+         " row " + std::to_string(row) +
          " has a zero or non-finite pivot in the elimination of its line (the smoother needs a diagonally "
          "dominant operator)";
 }
 struct LineOnDev {  // factors of T (n doubles each) and the scratch vector y
   int64_t n = 0, s = 0;
+  int64_t m = 0;  // LineRef::m
   DevMem dl, ip, cp, v, w, y;
   LineRef ref() const {
     LineRef R;
     R.n = n;
     R.s = s;
+    R.m = m;
     R.dl = dl.as<double>();
     R.ip = ip.as<double>();
     R.cp = cp.as<double>();
@@ -850,9 +854,10 @@ struct LineOnDev {  // factors of T (n doubles each) and the scratch vector y
 };
 // stride (0: the automatic rule, on the device) and factors of one level from its device CSR rows
 amg_hip_status line_setup_dev(int l, int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
-                              int64_t stride, LineOnDev* out) {
+                              int64_t stride, LineOnDev* out, int64_t m = 0, const char* dir = nullptr) {
   LineOnDev& D = *out;
   D.n = n;
+  D.m = m;
   for (DevMem* m : {&D.dl, &D.ip, &D.cp, &D.v, &D.w, &D.y}) HIP_TRY(m->alloc(sizeof(double) * (size_t)n));
   DevMem flag;
   HIP_TRY(flag.alloc(sizeof(uint64_t) * 2));
@@ -867,7 +872,7 @@ amg_hip_status line_setup_dev(int l, int64_t n, const int32_t* rowptr, const int
   D.s = std::min<int64_t>(stride, n);
   HIP_TRY(launch_line_setup(D.ref(), rowptr, col, val, flag.as<uint64_t>(), nullptr));
   HIP_TRY(hipMemcpy(h, flag.p, sizeof(h), hipMemcpyDeviceToHost));
-  if (h[0] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, (int64_t)h[0]));
+  if (h[0] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, (int64_t)h[0], dir));
   return AMG_HIP_OK;
 }
 // n_iters sweeps u <- u + omega T^-1 (f - A u); r: n doubles of scratch for the residual
@@ -876,6 +881,93 @@ hipError_t launch_line_sweep(const DevMat& A, const LineOnDev& D, double* u, con
   hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
   if (e != hipSuccess) return e;
   return launch_line_solve(D.ref(), r, D.y.as<double>(), u, omega, st);
+}
+
+// ---- alternating-direction line smoother (AMG_HIP_SM_LINE_ALT; kernels.hip: K-LineX, K-Line) ----
+// The directions of a level: its axes of length >= 2 in the order x, y, z.  x runs as K-LineX, y and
+// z as K-Line with the strides nx and nx ny (m = ny, nz: entries across a plane end stay out of T).
+// A level without a direction (one row) is weighted Jacobi: K-Line with every row its own chain.
+const char* const ALT_AXIS[3] = {"x", "y", "z"};
+const char* const ALT_NEEDS_GRID =
+    "unknown smoother kind for this constructor: AMG_HIP_SM_LINE_ALT needs the level grids of amg_hip_create_tensor";
+struct AltOnDev {
+  int n_dir = 0;
+  int axis[3] = {0, 0, 0};
+  int64_t stride[3] = {0, 0, 0}, len[3] = {0, 0, 0};
+  int64_t n = 0;
+  DevMem xdl, xip, xcp;  // K-LineX factors (direction x)
+  LineOnDev yz[2];       // K-Line factors of the directions y, z; yz[0] of the level without directions
+  void set_grid(int64_t rows, const int64_t dims[3]) {
+    n = rows;
+    n_dir = 0;
+    int64_t st = 1;
+    for (int a = 0; a < 3; ++a) {
+      if (dims[a] >= 2) {
+        axis[n_dir] = a;
+        stride[n_dir] = st;
+        len[n_dir] = dims[a];
+        ++n_dir;
+      }
+      st *= dims[a];
+    }
+  }
+  LineXRef xref() const {
+    LineXRef R;
+    R.n = n;
+    R.nx = len[0];
+    R.dl = xdl.as<double>();
+    R.ip = xip.as<double>();
+    R.cp = xcp.as<double>();
+    return R;
+  }
+  // bytes the solve of direction d (or of the level without directions, d = 0) has to move.  K-LineX:
+  // r, dl, ip in and y out, then y, cp, u in and u out: 64 B per row
+  double solve_bytes(int d) const {
+    if (n_dir == 0) return yz[0].solve_bytes();
+    return axis[d] == 0 ? 64.0 * (double)n : yz[axis[d] - 1].solve_bytes();
+  }
+};
+// host_only: the pivot check of every direction on the host
+amg_hip_status alt_setup_host(int l, const int32_t* rowptr, const int32_t* col, const double* val, AltOnDev* D) {
+  if (D->n_dir == 0) {
+    const int64_t bad = line_setup_host(D->n, D->n, rowptr, col, val);
+    if (bad >= 0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, bad));
+  }
+  for (int d = 0; d < D->n_dir; ++d) {
+    const int64_t bad = D->axis[d] == 0 ? linex_setup_host(D->n, D->len[d], rowptr, col, val)
+                                        : line_setup_host(D->n, D->stride[d], rowptr, col, val, D->len[d]);
+    if (bad >= 0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, bad, ALT_AXIS[D->axis[d]]));
+  }
+  return AMG_HIP_OK;
+}
+amg_hip_status alt_setup_dev(int l, const int32_t* rowptr, const int32_t* col, const double* val, AltOnDev* D) {
+  const int64_t n = D->n;
+  if (D->n_dir == 0) return line_setup_dev(l, n, rowptr, col, val, n, &D->yz[0]);
+  for (int d = 0; d < D->n_dir; ++d) {
+    const int a = D->axis[d];
+    if (a > 0) {
+      const amg_hip_status r = line_setup_dev(l, n, rowptr, col, val, D->stride[d], &D->yz[a - 1], D->len[d], ALT_AXIS[a]);
+      if (r != AMG_HIP_OK) return r;
+      continue;
+    }
+    for (DevMem* m : {&D->xdl, &D->xip, &D->xcp}) HIP_TRY(m->alloc(sizeof(double) * (size_t)n));
+    DevMem flag;
+    HIP_TRY(flag.alloc(sizeof(uint64_t) * 2));
+    uint64_t h[2];
+    HIP_TRY(launch_linex_setup(D->xref(), rowptr, col, val, flag.as<uint64_t>(), nullptr));
+    HIP_TRY(hipMemcpy(h, flag.p, sizeof(h), hipMemcpyDeviceToHost));
+    if (h[0] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, (int64_t)h[0], ALT_AXIS[0]));
+  }
+  return AMG_HIP_OK;
+}
+// sub-sweep d of one application: u <- u + omega T_a^-1 (f - A u); r: n doubles of scratch
+hipError_t launch_alt_subsweep(const DevMat& A, const AltOnDev& D, int d, double* u, const double* f, double* r,
+                               double omega, hipStream_t st) {
+  hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
+  if (e != hipSuccess) return e;
+  if (D.n_dir > 0 && D.axis[d] == 0) return launch_linex_solve(D.xref(), r, u, omega, st);
+  const LineOnDev& Y = D.yz[D.n_dir == 0 ? 0 : D.axis[d] - 1];
+  return launch_line_solve(Y.ref(), r, Y.y.as<double>(), u, omega, st);
 }
 
 struct SpikeOnDev {  // device copy of a SpikeFactor + scratch
@@ -1075,6 +1167,7 @@ struct Level {
   double cheb_lo = 0.0, cheb_hi = 0.0;  // Chebyshev smoother: interval of D^-1 A's spectrum
   DevMem cheb_d;           //   and its update vector d (r stays the residual: keep_residual)
   LineOnDev line;          // line smoother: stride, factors of T and scratch (host_only: stride only)
+  AltOnDev alt;            // alternating line smoother: directions and their factors (host_only: directions only)
   // transfers to level+1 (absent on the coarsest level)
   // host copies; for the built-in LinearInterpolator they are only materialised when a
   // getter, the CSR transfer kernels or the host Galerkin product ask for them
@@ -1484,8 +1577,9 @@ static bool march_fill(const amg_hip_solver* s, int l, MarchRef* R) {
 }
 // phase 3: the first sweep was already done by the fused kernel of the finer level
 // (result in tmp).  prolong_into >= 0: the last sweep also adds P u_l to that level's u.
+// reverse: the application of the up-leg (AMG_HIP_SM_LINE_ALT runs its directions in descending order).
 amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolong_into = -1,
-                              double* prolong_out = nullptr) {
+                              double* prolong_out = nullptr, bool reverse = false) {
   Level& L = s->lv[l];
   hipStream_t st = s->stream;
   const int iters = s->opt.smoother_iters;
@@ -1624,6 +1718,20 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
                                   s->opt.omega, st));
         s->acct(mat_bytes(A) + 24.0 * L.n + L.line.solve_bytes());  // matrix, f, u, r; K-Line
       }
+      return AMG_HIP_OK;
+    }
+    case AMG_HIP_SM_LINE_ALT: {
+      // one application = one sub-sweep per direction (ascending on the way down, descending on the
+      // way up), each the residual of the current u into tmp and then the direction's line solve
+      const DevMat& A = L.A_rows;
+      const int nd = std::max(L.alt.n_dir, 1);
+      for (int it = 0; it < iters; ++it)
+        for (int q = 0; q < nd; ++q) {
+          const int d = reverse ? nd - 1 - q : q;
+          HIP_TRY(launch_alt_subsweep(A, L.alt, d, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
+                                      s->opt.omega, st));
+          s->acct(mat_bytes(A) + 24.0 * L.n + L.alt.solve_bytes(d));  // matrix, f, u, r; the line solve
+        }
       return AMG_HIP_OK;
     }
   }
@@ -2071,7 +2179,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
       s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
       continue;
     }
-    amg_hip_status r = enqueue_smooth(s, l, 0, into, into >= 0 ? up_target(into) : nullptr);  // :300
+    amg_hip_status r = enqueue_smooth(s, l, 0, into, into >= 0 ? up_target(into) : nullptr, true);  // :300
     if (r != AMG_HIP_OK) return r;
   }
   return AMG_HIP_OK;
@@ -2145,7 +2253,15 @@ void compute_bytes(amg_hip_solver* s) {
     const double sweep = 12.0 * (double)L.nnz_struct + 28.0 * (double)L.n;
     if (l == 0) s->fine_sweep_bytes = sweep;
     // line smoother: every sweep is a residual plus the K-Line solve (80 B per row)
-    const double extra = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI ? 80.0 * (double)L.n * sweeps_per_smooth : 0.0;
+    double extra = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI ? 80.0 * (double)L.n * sweeps_per_smooth : 0.0;
+    // alternating line smoother: a residual plus a line solve per direction (K-LineX 64, K-Line 80 B per row)
+    if (s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
+      const int nd = std::max(L.alt.n_dir, 1);
+      sweeps_per_smooth = iters * nd;
+      extra = 0.0;
+      for (int d = 0; d < nd; ++d)
+        extra += (L.alt.n_dir > 0 && L.alt.axis[d] == 0 ? 64.0 : 80.0) * (double)L.n * iters;
+    }
     // pre-smooth + residual on every level; post-smooth on all but the coarsest
     total += sweep * (sweeps_per_smooth + 1) + extra;
     if (l + 1 != nl) {
@@ -2185,8 +2301,10 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
   if (opts) s->opt = *opts;
   else amg_hip_default_options(&s->opt);
-  if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_LINE_JACOBI)
+  if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_LINE_ALT)
     return fail(AMG_HIP_EINVAL, "unknown smoother kind");
+  const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
+  if (alt && !tensor_dim) return fail(AMG_HIP_EINVAL, ALT_NEEDS_GRID);
   if (s->opt.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
   const bool cheb = s->opt.smoother == AMG_HIP_SM_CHEBYSHEV;
   if (cheb) {
@@ -2195,7 +2313,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     if (s->opt.window) return fail(AMG_HIP_EUNSUPPORTED, "the Chebyshev smoother is not available in a window solver");
   }
   const bool line = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI;
-  if (line) {
+  if (line || alt) {
     const std::string e = line_options_error(s->opt.omega);
     if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
     if (s->opt.window) return fail(AMG_HIP_EUNSUPPORTED, "the line smoother is not available in a window solver");
@@ -2291,6 +2409,19 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       const amg_hip_status lr = line_setup_dev(l, L.n, rows.rowptr(), rows.col(), rows.v(), 0, &L.line);
       if (lr != AMG_HIP_OK) return lr;
     }
+    if (alt) {  // directions of the level's grid; pivot check on the host (host_only) or the device set-up
+      if (L.n >= ((int64_t)1 << 31)) return fail(AMG_HIP_EUNSUPPORTED, "line smoother: levels of 2^31 rows or more");
+      L.alt.set_grid(L.n, L.dims);
+      if (!dev) {
+        const amg_hip_status ar = alt_setup_host(l, A_r.ptr.data(), A_r.idx.data(), A_r.val.data(), &L.alt);
+        if (ar != AMG_HIP_OK) return ar;
+      } else {
+        DevCsr rows;
+        HIP_TRY(upload_csr(A_r, &rows));
+        const amg_hip_status ar = alt_setup_dev(l, rows.rowptr(), rows.col(), rows.v(), &L.alt);
+        if (ar != AMG_HIP_OK) return ar;
+      }
+    }
     if (dev) {
     const bool prune = !s->opt.keep_structural_zeros;
     // Symmetric levels headed for the dictionary layout are encoded ON THE DEVICE from CSR(A_l)
@@ -2317,7 +2448,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     }
     if (!encoded) {
       HIP_TRY(upload_mat_pruned(A_r, s->opt.layout, prune, &L.A_rows));
-      if (!L.symmetric && s->opt.smoother >= AMG_HIP_SM_JACOBI && !cheb && !line)  // Chebyshev, line: rows of A
+      if (!L.symmetric && s->opt.smoother >= AMG_HIP_SM_JACOBI && !cheb && !line && !alt)  // Chebyshev, line: rows of A
         HIP_TRY(upload_mat_pruned(L.A_csc, s->opt.layout, prune, &L.A_cols_own));
     }
     if (s->opt.smoother == AMG_HIP_SM_JACOBI && !L.diag.p) {  // diagonal of the column-as-row walk
@@ -2887,7 +3018,7 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
       n_levels < 2 || N >= ((int64_t)1 << 28))
     return AMG_HIP_OK;
   // full coarsening: the lexicographic and the line smoothers build through the host constructor
-  if (tensor && (lex || o.smoother == AMG_HIP_SM_LINE_JACOBI)) return AMG_HIP_OK;
+  if (tensor && (lex || o.smoother == AMG_HIP_SM_LINE_JACOBI || o.smoother == AMG_HIP_SM_LINE_ALT)) return AMG_HIP_OK;
   if (o.smoother_iters < 0 || (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0)) ||
       o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_JACOBI)
     return AMG_HIP_OK;  // the host path words the argument error
@@ -2968,6 +3099,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
   const bool lex = o.smoother <= AMG_HIP_SM_SOR;
   const bool cheb = o.smoother == AMG_HIP_SM_CHEBYSHEV;
   const bool line = o.smoother == AMG_HIP_SM_LINE_JACOBI;
+  const bool alt = o.smoother == AMG_HIP_SM_LINE_ALT;
   const bool timing = lap.on;
   const bool try_dict = o.layout == AMG_HIP_LAYOUT_AUTO || o.layout == AMG_HIP_LAYOUT_DICT;
   s->lv.resize(n_levels);
@@ -3010,6 +3142,11 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
     if (line) {  // stride rule and factors of T on the device CSR (K-Line setup)
       const amg_hip_status lr = line_setup_dev(l, L.n, cur.rowptr(), cur.col(), cur.v(), 0, &L.line);
       if (lr != AMG_HIP_OK) return lr;
+    }
+    if (alt) {  // directions of the level's grid and their factors (K-LineX and K-Line set-up)
+      L.alt.set_grid(L.n, L.dims);
+      const amg_hip_status ar = alt_setup_dev(l, cur.rowptr(), cur.col(), cur.v(), &L.alt);
+      if (ar != AMG_HIP_OK) return ar;
     }
     HIP_TRY(L.diag.alloc(sizeof(double) * L.n));
     HIP_TRY(hipMemset(stats.p, 0, sizeof(int32_t) * 2));
@@ -3225,6 +3362,7 @@ const char* block_smoother_name(int32_t sm) {
     case AMG_HIP_SM_SOR: return "SOR (AMG_HIP_SM_SOR)";
     case AMG_HIP_SM_MULTICOLOR_GS: return "multicolour Gauss-Seidel (AMG_HIP_SM_MULTICOLOR_GS)";
     case AMG_HIP_SM_LINE_JACOBI: return "line Jacobi (AMG_HIP_SM_LINE_JACOBI)";
+    case AMG_HIP_SM_LINE_ALT: return "alternating line Jacobi (AMG_HIP_SM_LINE_ALT)";
   }
   return "unknown";
 }
@@ -3967,7 +4105,7 @@ static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr,
   cur.nnz = nnz;
   lap("copy + check");
   const bool on_device = (o.smoother == AMG_HIP_SM_JACOBI || o.smoother == AMG_HIP_SM_CHEBYSHEV ||
-                          o.smoother == AMG_HIP_SM_LINE_JACOBI) &&
+                          o.smoother == AMG_HIP_SM_LINE_JACOBI || o.smoother == AMG_HIP_SM_LINE_ALT) &&
                          !o.host_only && !o.host_galerkin && o.stencil_transfers && !o.fuse_prolong && n_levels >= 2 &&
                          n < ((int64_t)1 << 28);
   if (!on_device) return AMG_HIP_OK;
@@ -4013,13 +4151,13 @@ amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, c
     }
   }
   // build_solver's option checks, in its words
-  if (o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_JACOBI) return fail(AMG_HIP_EINVAL, "unknown smoother kind");
+  if (o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_ALT) return fail(AMG_HIP_EINVAL, "unknown smoother kind");
   if (o.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
   if (o.smoother == AMG_HIP_SM_CHEBYSHEV) {
     const std::string ce = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
     if (!ce.empty()) return fail(AMG_HIP_EINVAL, ce);
   }
-  if (o.smoother == AMG_HIP_SM_LINE_JACOBI) {
+  if (o.smoother == AMG_HIP_SM_LINE_JACOBI || o.smoother == AMG_HIP_SM_LINE_ALT) {
     const std::string le = line_options_error(o.omega);
     if (!le.empty()) return fail(AMG_HIP_EINVAL, le);
   }
@@ -4086,6 +4224,7 @@ amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t uni
   amg_hip_options o;
   if (opts) o = *opts;
   else amg_hip_default_options(&o);
+  if (o.smoother == AMG_HIP_SM_LINE_ALT) return fail(AMG_HIP_EINVAL, ALT_NEEDS_GRID);
   if (o.smoother == AMG_HIP_SM_CHEBYSHEV)
     return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_window: the Chebyshev smoother is not sharded");
   if (o.smoother == AMG_HIP_SM_LINE_JACOBI)
@@ -4195,7 +4334,7 @@ amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world
   if (s->opt.window) return fail(AMG_HIP_EINVAL, "amg_hip_slab_setup: a window solver is cut already (amg_hip_window_setup)");
   if (s->opt.smoother == AMG_HIP_SM_CHEBYSHEV)
     return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_slab_setup: the Chebyshev smoother is not sharded");
-  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI)
+  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT)
     return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_slab_setup: the line smoother is not sharded");
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
@@ -4447,6 +4586,17 @@ amg_hip_status amg_hip_line_stride(const amg_hip_solver* s, int32_t level, int64
     return fail(AMG_HIP_EINVAL, "amg_hip_line_stride: the solver's smoother is not AMG_HIP_SM_LINE_JACOBI");
   if (level < 0 || level >= (int)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
   *stride = s->lv[level].line.s;
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_line_directions(const amg_hip_solver* s, int32_t level, int32_t* n_dir, int64_t strides[3]) {
+  if (!s || !n_dir || !strides) return fail(AMG_HIP_EINVAL, "null argument");
+  if (s->opt.smoother != AMG_HIP_SM_LINE_ALT)
+    return fail(AMG_HIP_EINVAL, "amg_hip_line_directions: the solver's smoother is not AMG_HIP_SM_LINE_ALT");
+  if (level < 0 || level >= (int)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
+  const AltOnDev& D = s->lv[level].alt;
+  *n_dir = D.n_dir;
+  for (int d = 0; d < 3; ++d) strides[d] = d < D.n_dir ? D.stride[d] : 0;
   return AMG_HIP_OK;
 }
 
@@ -4905,7 +5055,7 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
 amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int32_t name_cap,
                                        int32_t* sweeps_per_launch, double* bytes_per_launch) {
   if (!s || !name || name_cap < 32) return fail(AMG_HIP_EINVAL, "bad argument");
-  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI)
+  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT)
     return fail(AMG_HIP_EUNSUPPORTED, "fine_sweep_info: a line-smoother sweep is not one launch");
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no device matrices");
   const Level& L = s->lv[0];
@@ -5321,6 +5471,50 @@ amg_hip_status amg_hip_smooth_line(int64_t n, const int32_t* colptr, const int32
   HIP_TRY(dr.alloc(sizeof(double) * n));
   for (int64_t it = 0; it < iters; ++it)
     HIP_TRY(launch_line_sweep(M, D, du.as<double>(), df.as<double>(), dr.as<double>(), omega, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(u, du.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_smooth_line_alt(int64_t n, const int32_t* colptr, const int32_t* rowind, const double* val,
+                                       int32_t dim, const int64_t* dims, double omega, int64_t iters,
+                                       int32_t reverse, double* u, const double* f) {
+  static const std::string who = "amg_hip_smooth_line_alt: ";
+  if (n <= 0 || !colptr || !rowind || !val || !u || !f) return fail(AMG_HIP_EINVAL, "bad argument");
+  std::string v = tensor_dims_error(dim, dims);
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, who + v);
+  if (n != dims[0] * dims[1] * dims[2])
+    return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
+                                    " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
+                                    " grid of `dims`");
+  if (iters < 0) return fail(AMG_HIP_EINVAL, "`iters` must be >= 0");
+  v = line_options_error(omega);
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
+  Sparse A = from_raw(n, n, colptr, rowind, val);
+  v = validate(A, "A");
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
+  Sparse Ar = transpose(A);  // T and the residual are taken from the rows of A
+  AltOnDev D;
+  D.set_grid(n, dims);
+  amg_hip_status st = alt_setup_host(0, Ar.ptr.data(), Ar.idx.data(), Ar.val.data(), &D);  // before the device
+  if (st != AMG_HIP_OK) return st;
+  st = need_device();
+  if (st != AMG_HIP_OK) return st;
+  DevCsr rows;
+  HIP_TRY(upload_csr(Ar, &rows));
+  st = alt_setup_dev(0, rows.rowptr(), rows.col(), rows.v(), &D);
+  if (st != AMG_HIP_OK) return st;
+  DevMat M;
+  HIP_TRY(upload_mat(Ar, g_default_layout, &M));
+  DevMem du, df, dr;
+  HIP_TRY(upload(du, u, (size_t)n));
+  HIP_TRY(upload(df, f, (size_t)n));
+  HIP_TRY(dr.alloc(sizeof(double) * n));
+  const int nd = std::max(D.n_dir, 1);
+  for (int64_t it = 0; it < iters; ++it)
+    for (int q = 0; q < nd; ++q)
+      HIP_TRY(launch_alt_subsweep(M, D, reverse ? nd - 1 - q : q, du.as<double>(), df.as<double>(), dr.as<double>(),
+                                  omega, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(u, du.p, sizeof(double) * n, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;

@@ -109,6 +109,9 @@ class Multigrid {
     } else if (auto* lj = dynamic_cast<LineJacobi<EleType>*>(smoother)) {
       opt.smoother = AMG_HIP_SM_LINE_JACOBI;
       opt.omega = lj->get_omega();
+    } else if (auto* la = dynamic_cast<LineAlternating<EleType>*>(smoother)) {
+      opt.smoother = AMG_HIP_SM_LINE_ALT;  // the level grids come from the TensorInterpolator
+      opt.omega = la->get_omega();
     } else {
       // user-defined SmootherBase: its smooth() runs on the host, everything else of the
       // V-cycle on the device; the device-side smoother is never used

@@ -184,4 +184,44 @@ class LineJacobi : public SmootherBase<EleType> {
   }
 };
 
+// Build-side addition (no reference counterpart): alternating-direction line relaxation on the
+// nx x ny (x nz) grid of a full-coarsening hierarchy (amg_hip.h: AMG_HIP_SM_LINE_ALT).  One
+// application is one sub-sweep u <- u + omega T_a^-1 (b - A u) per axis of length >= 2, x first;
+// inside a Multigrid built with a TensorInterpolator every level uses its own grid and the up-leg
+// runs the axes in descending order (any other interpolator is refused).  smooth() is the
+// stand-alone ascending application on the grid given here.  omega in (0, 2); 0.8 is recommended.
+template <class EleType>
+class LineAlternating : public SmootherBase<EleType> {
+  double omega{0.8};
+  int dim_{2};
+  int64_t dims_[3]{1, 1, 1};
+
+ public:
+  LineAlternating(size_t nx, size_t ny, double omega_ = 0.8, size_t n_iters_ = 1) : omega(omega_) {
+    init(2, nx, ny, 1, n_iters_);
+  }
+  LineAlternating(size_t nx, size_t ny, size_t nz, double omega_, size_t n_iters_) : omega(omega_) {
+    init(3, nx, ny, nz, n_iters_);
+  }
+  double get_omega() const { return omega; }
+  void smooth(const Eigen::SparseMatrix<EleType>& A, Eigen::Matrix<EleType, -1, 1>& u,
+              const Eigen::Matrix<EleType, -1, 1>& b) override {
+    static_assert(sizeof(EleType) == sizeof(double), "the MI355X path is fp64 only");
+    const Eigen::SparseMatrix<EleType> C = detail::compressed(A);
+    detail::check(amg_hip_smooth_line_alt(C.rows(), C.outerIndexPtr(), C.innerIndexPtr(), C.valuePtr(), dim_, dims_,
+                                          omega, (int64_t)this->n_iters, 0, u.data(), b.data()));
+  }
+
+ private:
+  void init(int dim, size_t nx, size_t ny, size_t nz, size_t n_iters_) {
+    dim_ = dim;
+    dims_[0] = (int64_t)nx;
+    dims_[1] = (int64_t)ny;
+    dims_[2] = (int64_t)nz;
+    this->n_iters = n_iters_;
+    this->compute_error_every_n_iters = 0;
+    if (!(omega > 0.0 && omega < 2.0)) throw std::invalid_argument("`omega` must lie in (0, 2)");
+  }
+};
+
 }  // namespace AMG

@@ -43,7 +43,7 @@ typedef enum {
 } amg_hip_status;
 
 /* Smoother plug-ins (smoother.hpp).  0-2 are the reference's three classes;
- * 3-6 are build-side additions the reference does not contain.   */
+ * 3-7 are build-side additions the reference does not contain.   */
 typedef enum {
   AMG_HIP_SM_SPGS = 0,          /* AMG::SparseGaussSeidel smoother.hpp:86-216:
                                    n_iters x (forward + backward lexicographic
@@ -58,7 +58,7 @@ typedef enum {
                                    G = Gershgorin bound of D^-1 A per level (rows
                                    of A); smoother_iters applications per leg,
                                    each cheb_degree Jacobi-shaped passes        */
-  AMG_HIP_SM_LINE_JACOBI = 6    /* line relaxation, Jacobi between the lines: with T
+  AMG_HIP_SM_LINE_JACOBI = 6,   /* line relaxation, Jacobi between the lines: with T
                                    = the entries of A at column offsets 0, +s and -s
                                    (tridiagonal on each of the min(s, n) chains of
                                    rows c, c + s, c + 2s, ...), one sweep is
@@ -81,6 +81,33 @@ typedef enum {
                                    T is symmetric when A is, so the V-cycle stays a
                                    valid PCG preconditioner.  Window solvers, slab
                                    sharding and the block entry points refuse it
+                                   (AMG_HIP_EUNSUPPORTED).                       */
+  AMG_HIP_SM_LINE_ALT = 7       /* alternating-direction line relaxation, only on
+                                   solvers that know their level grids
+                                   (amg_hip_create_tensor, _tensor_dev,
+                                   _poisson_tensor; every other constructor refuses
+                                   it with AMG_HIP_EINVAL).  The directions of a
+                                   level with grid (nx, ny, nz), x fastest, are its
+                                   axes of length >= 2 in the order x, y, z, with
+                                   strides 1, nx, nx ny (amg_hip_line_directions).
+                                   One sub-sweep in direction a is
+                                   u <- u + omega T_a^-1 (f - A u), the residual
+                                   taken from the current u, T_a = the diagonal of A
+                                   plus its entries at column offsets +-stride_a that
+                                   join two points of the same grid line of that
+                                   axis (an entry at +-1 across a line end, or at
+                                   +-nx across a plane end, stays in A only): every
+                                   grid line is its own tridiagonal system.  One
+                                   application runs the directions in ascending
+                                   order on the way down and in descending order on
+                                   the way up, smoother_iters applications per leg,
+                                   so the post-smoother is the adjoint of the
+                                   pre-smoother and the V-cycle of a symmetric A is
+                                   a symmetric PCG preconditioner.  A level without
+                                   such an axis does weighted Jacobi.  omega in
+                                   (0, 2), 0.8 recommended; pivots as for
+                                   AMG_HIP_SM_LINE_JACOBI (level, direction and row
+                                   in the message).  Refused where that one is
                                    (AMG_HIP_EUNSUPPORTED).                       */
 } amg_hip_smoother;
 
@@ -684,6 +711,12 @@ amg_hip_status amg_hip_cheb_bounds(const amg_hip_solver* s, int32_t level, doubl
  * AMG_HIP_EINVAL for other smoothers.                                                      */
 amg_hip_status amg_hip_line_stride(const amg_hip_solver* s, int32_t level, int64_t* stride);
 
+/* AMG_HIP_SM_LINE_ALT: the directions of `level`: *n_dir of them (0 .. 3) and their strides in
+ * ascending order in strides[0 .. *n_dir) (the rest 0).  Also on host_only solvers.
+ * AMG_HIP_EINVAL for other smoothers.                                                      */
+amg_hip_status amg_hip_line_directions(const amg_hip_solver* s, int32_t level, int32_t* n_dir,
+                                       int64_t strides[3]);
+
 /* Sum over levels of the algorithmic HBM bytes of one V-cycle (SURVEY 8(d)
  * formulae) and the per-sweep bytes of level 0; used by bench.py.             */
 amg_hip_status amg_hip_cycle_bytes(const amg_hip_solver* s, double* cycle_bytes,
@@ -704,7 +737,7 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
  * AMG_HIP_SM_JACOBI: one launch = one sweep over level 0 (K-Patch: the level's down-leg);
  * AMG_HIP_SM_CHEBYSHEV: one middle step of the polynomial over level 0 (u -> tmp, d read and
  * written), or step 0 when the degree has no middle step (1 or 2);
- * AMG_HIP_SM_LINE_JACOBI: refused (AMG_HIP_EUNSUPPORTED; a sweep is four launches);
+ * AMG_HIP_SM_LINE_JACOBI, AMG_HIP_SM_LINE_ALT: refused (AMG_HIP_EUNSUPPORTED; a sweep is several launches);
  * AMG_HIP_SM_MULTICOLOR_GS: the first launch of the symmetric pass (K-Patch form: two colour
  * stages over the level; colour kernels: colour 0).  The level-0 solution is restored
  * afterwards.                                                                  */
@@ -745,6 +778,14 @@ amg_hip_status amg_hip_smooth_chebyshev(int64_t n, const int32_t* colptr, const 
 amg_hip_status amg_hip_smooth_line(int64_t n, const int32_t* colptr, const int32_t* rowind,
                                    const double* val, int64_t stride, double omega, int64_t iters,
                                    double* u, const double* f);
+/* The alternating line smoother (AMG_HIP_SM_LINE_ALT) on host arrays: `iters` applications on the
+ * dims[0] x dims[1] x dims[2] grid (dim 2 or 3, as amg_hip_create_tensor), directions ascending,
+ * or descending with reverse = 1.  u is updated in place.  AMG_HIP_EINVAL: n != nx ny nz, a bad
+ * dim or dims, omega outside (0, 2), iters < 0, or a bad pivot (direction and row in the message);
+ * all of them are found before the device is touched.                                        */
+amg_hip_status amg_hip_smooth_line_alt(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                       const double* val, int32_t dim, const int64_t* dims, double omega,
+                                       int64_t iters, int32_t reverse, double* u, const double* f);
 /* One lexicographic sweep, dir=+1 forward (smoother.hpp:148-157) or -1 backward
  * (:167-174). */
 amg_hip_status amg_hip_spgs_sweep(int32_t dir, int64_t n, const int32_t* colptr,

@@ -9,6 +9,8 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py tensor10 <n> <levels> [csr]                 ten cycles of one tensor hierarchy (kernel traces)
        config_bench.py tensor-setup [<dim> <n> <levels>]           set-up seconds of the full-coarsening hierarchy, host and device construction alternating
        config_bench.py tensor-user-setup [<nx> <ny> <nz> <levels>] set-up seconds for a variable-coefficient operator assembled on the GPU: host constructor and amg_hip_create_tensor_dev alternating
+       config_bench.py alt [<nx> <ny> <levels>]                    alternating line smoother 1+1 next to true Jacobi 2+2 and the line smoother 1+1 through tensor_dev, isotropic and split-anisotropy operators (legs alternate)
+       config_bench.py alt10 <nx> <ny> <levels>                    ten cycles of the alternating line smoother (kernel traces)
        config_bench.py mixed [<nx> <ny> <nz> <levels>]             amg_hip_pcg and amg_hip_pcg_mixed (single-precision V-cycle) alternating on a variable-coefficient operator, true Jacobi 2+2 and Chebyshev(2) 1+1
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
@@ -310,6 +312,105 @@ def run_tensor_user_setup(dims, L, reps=3, tol=1e-8, cap=60):
     keep.close()
 
 
+def torch_split_anisotropy(dims, eps=1e-3):
+    """5-point diffusion on the 2-D grid `dims` with harmonic-mean edge coefficients of the point
+    coefficients (x, y) = (1, eps) in the left half of the domain and (eps, 1) in the right half
+    (Dirichlet; a boundary edge takes the point's own coefficient), assembled on the GPU: (crow, col,
+    val, b) as torch_diffusion."""
+    import torch
+    dev = torch.device("cuda")
+    nx, ny = dims
+    n = nx * ny
+    i = torch.arange(n, device=dev)
+    x, y = i % nx, i // nx
+    left = x < nx // 2
+    one, small = torch.ones(n, dtype=torch.float64, device=dev), torch.full((n,), eps, dtype=torch.float64, device=dev)
+    c = [torch.where(left, one, small), torch.where(left, small, one)]
+    coord, ext, stride = [x, y], [nx, ny], [1, nx]
+    cols = torch.zeros((n, 5), dtype=torch.int64, device=dev)
+    vals = torch.zeros((n, 5), dtype=torch.float64, device=dev)
+    mask = torch.zeros((n, 5), dtype=torch.bool, device=dev)
+    diag = torch.zeros(n, dtype=torch.float64, device=dev)
+    for a in range(2):
+        lo_ok, hi_ok = coord[a] > 0, coord[a] < ext[a] - 1
+        c_lo, c_hi = torch.roll(c[a], stride[a]), torch.roll(c[a], -stride[a])
+        k_lo = torch.where(lo_ok, 2.0 * c[a] * c_lo / (c[a] + c_lo), c[a])
+        k_hi = torch.where(hi_ok, 2.0 * c[a] * c_hi / (c[a] + c_hi), c[a])
+        diag = diag + k_lo + k_hi
+        s_lo, s_hi = 1 - a, 3 + a
+        cols[:, s_lo], vals[:, s_lo], mask[:, s_lo] = i - stride[a], -k_lo, lo_ok
+        cols[:, s_hi], vals[:, s_hi], mask[:, s_hi] = i + stride[a], -k_hi, hi_ok
+    cols[:, 2], vals[:, 2], mask[:, 2] = i, diag, True
+    crow = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    crow[1:] = torch.cumsum(mask.sum(1), 0).to(torch.int32)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    b = torch.rand(n, generator=g, device=dev, dtype=torch.float64)
+    return crow, col_of(cols, mask), vals[mask].contiguous(), b
+
+
+def col_of(cols, mask):
+    import torch
+    return cols[mask].to(torch.int32).contiguous()
+
+
+ALT_KW = {"alt 1+1": dict(smoother=amg.SM_LINE_ALT, smoother_iters=1, omega=0.8),
+          "jacobi 2+2": dict(smoother=amg.SM_JACOBI, smoother_iters=2, omega=0.8),
+          "line 1+1": dict(smoother=amg.SM_LINE_JACOBI, smoother_iters=1, omega=0.7)}
+
+
+def run_alt(dims, L, reps=3, tol=1e-8, cap=60):
+    """The alternating line smoother (omega 0.8, 1+1) next to true Jacobi (omega 0.8, 2+2) and the
+    single-direction line smoother (omega 0.7, 1+1) through tensor_dev on the isotropic
+    variable-coefficient operator of tensor-user-setup and on the split-anisotropy operator, the three
+    legs alternating in one run, `reps` repeats.  Per leg: ms per V-cycle, and cycles and wall ms from
+    u = 0 to ||r|| / ||r0|| <= tol with one rss after every cycle; a run that stops at `cap` cycles
+    counts as its cap."""
+    tag = " x ".join(str(d) for d in dims)
+    for op, arrays in (("isotropic", torch_diffusion(dims)), ("split-anisotropy 1e-3", torch_split_anisotropy(dims))):
+        legs = {}
+        for name, kw in ALT_KW.items():
+            t0 = time.time()
+            mg = amg.Multigrid.tensor_dev(*arrays, dims, L, **kw)
+            mg.sync()
+            assert mg.setup_on_device == 1
+            print(f"alt {tag} {L} levels {op}, {name}: setup {time.time() - t0:.2f} s, level-0 layout "
+                  f"{mg.level_layout(0)}, must-move {mg.cycle_must_move() / 1e6:.1f} MB/cycle", flush=True)
+            mg.vcycle(3)
+            mg.sync()
+            legs[name] = mg
+        best = {}
+        for rep_ in range(reps):
+            for name, mg in legs.items():
+                cyc = 10
+                mg.zero_vec(0, "u")
+                mg.sync()
+                t0 = time.perf_counter()
+                mg.vcycle(cyc)
+                mg.sync()
+                dt = (time.perf_counter() - t0) / cyc
+                mg.zero_vec(0, "u")
+                mg.sync()
+                r0 = mg.rss()
+                done, rel = 0, 1.0
+                t1 = time.perf_counter()
+                while done < cap and rel > tol:
+                    mg.vcycle(1)
+                    done += 1
+                    rel = (mg.rss() / r0) ** 0.5
+                t2 = time.perf_counter() - t1
+                best[name] = min(best.get(name, t2), t2)
+                print(f"alt {tag} {op}, {name} rep {rep_}: {dt * 1e3:.3f} ms/V-cycle = "
+                      f"{mg.cycle_must_move() / dt / 8e12 * 100:.1f} % of 8 TB/s; ||r||/||r0|| {rel:.2e} after {done} "
+                      f"cycles ({tol:g} {'reached' if rel <= tol else 'NOT reached: capped'}) in {t2 * 1e3:.1f} ms",
+                      flush=True)
+        print(f"alt {tag} {op}: best time to {tol:g}: " + ", ".join(f"{k} {v * 1e3:.1f} ms" for k, v in best.items()) +
+              f"; alt / jacobi {best['alt 1+1'] / best['jacobi 2+2']:.3f}, alt / line "
+              f"{best['alt 1+1'] / best['line 1+1']:.3f}", flush=True)
+        for mg in legs.values():
+            mg.close()
+
+
 def run_mixed(dims, L, reps=3, rtol=1e-8, applies=10):
     """amg_hip_pcg (double V-cycle) and amg_hip_pcg_mixed (float V-cycle) to `rtol` from x = 0,
     alternating in one process, `reps` repeats, on the variable-coefficient operator of
@@ -467,6 +568,22 @@ elif len(sys.argv) > 1 and sys.argv[1] == "tensor-user-setup":
         run_tensor_user_setup((4096, 4096), 10)
         run_tensor_user_setup((256, 256, 256), 7)
         run_tensor_user_setup((4096, 1024), 9)
+elif len(sys.argv) > 1 and sys.argv[1] == "alt":
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    if len(sys.argv) > 4:
+        run_alt((int(sys.argv[2]), int(sys.argv[3])), int(sys.argv[4]))
+    else:
+        run_alt((4096, 4096), 10)
+        run_alt((4096, 1024), 9)
+elif len(sys.argv) > 2 and sys.argv[1] == "alt10":     # ten cycles of the alternating smoother (kernel traces)
+    import torch  # noqa: F401
+    d = (int(sys.argv[2]), int(sys.argv[3]))
+    mg = amg.Multigrid.tensor_dev(*torch_split_anisotropy(d), d, int(sys.argv[4]), **ALT_KW["alt 1+1"])
+    mg.vcycle(2)
+    mg.sync()
+    mg.vcycle(10)
+    mg.sync()
+    mg.close()
 elif len(sys.argv) > 1 and sys.argv[1] == "mixed":
     import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
     if len(sys.argv) > 5:
