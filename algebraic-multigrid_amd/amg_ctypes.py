@@ -152,6 +152,7 @@ _SIGS = {
     "amg_hip_set_band_chain": (None, [C.c_int32]),
     "amg_hip_set_tail_fusion": (None, [C.c_int32]),
     "amg_hip_set_patch_tile_flags": (None, [C.c_int32]),
+    "amg_hip_set_patch_xf": (None, [C.c_int32]),
     "amg_hip_create_rs": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, C.c_double, C.c_int64,
                                     C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_slab_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SlabInfo)]),
@@ -364,6 +365,10 @@ def slab_plan(lines, rank, world, levels):
 
 def set_patch_tile_flags(on):
     lib().amg_hip_set_patch_tile_flags(int(bool(on)))
+
+
+def set_patch_xf(on):
+    lib().amg_hip_set_patch_xf(int(bool(on)))
 
 
 def set_tail_fusion(on):

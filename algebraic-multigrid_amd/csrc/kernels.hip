@@ -1421,7 +1421,9 @@ struct __attribute__((aligned(8))) PatchPair { double x, y; };  // 16-byte load,
 // PROLONG: the loaded vector is x + P uH (up-leg); else plain x.
 // UNI: every row of the patch and its halo has the row type `tf` (patch_tile_flags_kernel found
 // that out at setup): no row-type loads, no bounds checks, the wave-uniform path for all waves.
-template <bool PROLONG, bool UNI>
+// XF: x is not loaded and nothing is written to LDS: the caller forms the cells from pc.f once the
+// row type's diagonal is at hand (patch_form_x).
+template <bool PROLONG, bool UNI, bool XF = false>
 __device__ __forceinline__ void patch_load(PatchCells& pc, uint32_t tf, int n, int m, int j0, int i0,
                                            const double* __restrict__ x,
                                            const double* __restrict__ f,
@@ -1441,14 +1443,14 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, uint32_t tf, int n, i
     const int64_t r64 = r0 + (int64_t)k * m;
     pc.live[k] = UNI || (r64 >= 0 && r64 < (int64_t)n);
     const int row = pc.live[k] ? (int)r64 : 0;
-    xv[k] = x[row];
+    if (!XF) xv[k] = x[row];
     pc.f[k] = f[row];
     pc.ty[k] = UNI ? tf : (uint32_t)rtype[row];
   }
 #pragma unroll
   for (int k = 0; k < PATCH_K; ++k) {
     const int row = pc.row0 + k * m;
-    double x0 = pc.live[k] ? xv[k] : 0.0;
+    double x0 = (!XF && pc.live[k]) ? xv[k] : 0.0;
     if (PROLONG) {  // linear_prolong_add_kernel, same guards and order, written with selects
       const int j = pc.live[k] ? (row >> 1) : 0;
       const bool odd = (row & 1) != 0;
@@ -1465,7 +1467,7 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, uint32_t tf, int n, i
       t = b_ok ? t + (odd ? 1.0 : 0.5) * b : t;
       x0 = pc.live[k] ? x0 + t : x0;
     }
-    buf[pc.cell0 + k * PATCH_EC] = x0;
+    if (!XF) buf[pc.cell0 + k * PATCH_EC] = x0;
     const uint32_t nty = (uint32_t)ntypes;
     pc.ty[k] = (pc.live[k] && pc.ty[k] < nty) ? pc.ty[k] : nty;  // 255 = empty row -> absent row
     pc.f[k] = pc.live[k] ? pc.f[k] : 0.0;
@@ -1577,8 +1579,36 @@ __device__ __forceinline__ void patch_prologue(const PatchCells& pc, double* buf
   patch_load_u(U, pc.uniform ? pc.tu : 0u, utabd, utabi);
 }
 
+// XF: the held cells as the from-zero sweep of their rows, x = Jacobi(0; f), instead of a load of
+// the vector the finer level's kernel would have stored: the expression of jacobi_from_zero_kernel
+// and of the restriction loop below, operand for operand, on the f the thread holds anyway.  d = the
+// diagonal of the cell's row type: the bits of the level's diagonal vector (the dictionary coding is
+// exact; the sweeps divide by this very value) -- in scalar registers on a wave-uniform wave, else
+// from the per-type table in global memory (utabd, 19 doubles per type: the LDS tables are not
+// staged yet).  The absent type `ntypes` (rows outside the matrix, empty rows) has d = 0: x = 0.0.
+__device__ __forceinline__ void patch_form_x(const PatchCells& pc, const PatchU& U,
+                                             const double* __restrict__ utabd, double omega, double* buf) {
+  double dv[PATCH_K];
+  if (pc.uniform) {
+#pragma unroll
+    for (int k = 0; k < PATCH_K; ++k) dv[k] = U.diag;
+  } else {
+#pragma unroll
+    for (int k = 0; k < PATCH_K; ++k) dv[k] = utabd[(size_t)pc.ty[k] * 19 + 18];
+  }
+#pragma unroll
+  for (int k = 0; k < PATCH_K; ++k) {
+    const double sum = pc.f[k], d = dv[k];
+    const double xi = 0.0, acc = 0.0;  // jacobi_from_zero_kernel
+    const double x0 = (d == 0.0) ? xi : xi + omega * ((sum - acc) / d - xi);
+    buf[pc.cell0 + k * PATCH_EC] = pc.live[k] ? x0 : 0.0;
+  }
+}
+
 // FIRST: the input is the level's u and both pre-sweeps run here (level 0); else the input
 // is the result of the first sweep (done by the finer level's kernel) and one sweep runs.
+// XF (with !FIRST): that first sweep is not loaded but formed from f (patch_form_x); the finer
+// level's kernel then was launched with uH1 == nullptr and stored f_H only.
 // (Tried and dropped: at most 1024 workgroups per launch, each walking several patches of its XCD's
 // run with the tables staged once -- the loop alone cost 20 % (165 vs 134 us on level 0), with
 // 1024 workgroups 204 us: the slots of a CU standing empty 40 % of the time
@@ -1607,12 +1637,17 @@ hipError_t debug_set_patch_stamps(unsigned long long* p) {
 #else
 #define PATCH_STAMP(k)
 #endif
-template <int UN, int UM, bool FIRST, bool NT>
+template <int UN, int UM, bool FIRST, bool NT, bool XF = false>
 // (four workgroups per CU = 7 waves per SIMD = 72 registers: measured against 6 and 5 waves again in
 // round 3 -- level-0 down-leg 131-135 us at 7, 138-144 at 6, 142-143 at 5.  The down-legs of the
 // 7- and 9-point levels spill 2-7 registers at 72 and run at 6 waves (80 registers, three
 // workgroups per CU): cycle 1288 / 1290 / 1291 -> 1315 / 1305 / 1308 V-cycles/s in alternating runs;
-// their up-legs, which fit, stay at 7: 1296 / 1298 with both at 6.)
+// their up-legs, which fit, stay at 7: 1296 / 1298 with both at 6.
+// The XF variants hold no xv[8] while loading, but the peak is in the stages: compiled at 72 the
+// 7- and 9-point XF kernels still spill 7-8 registers (20-24 B of scratch per lane; the stored
+// form: 4-12 registers, 12-28 B), so they do not fit 7 waves either and stay at 6, where the
+// compiler reports 80 registers and 24-28 B of scratch for XF against 20-24 B for the stored form
+// (7-point: none for both).  The 5-point XF kernel fits 72 without scratch, like the stored form.)
 #ifndef AMG_PATCH_WAVES
 #define AMG_PATCH_WAVES 7
 #endif
@@ -1636,10 +1671,12 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
   // every coarse row under this patch has the diagonal dHu (launch_patch_coarse_flags found that
   // out at setup): the first coarse sweep then needs no load of the coarse diagonal at the very
   // end of the workgroup's life, where nothing is left to hide its latency behind
-  const bool cuni = cflag && cflag[(py + py0) * px_count + px] != 0;
-  if (tf != 255u) patch_load<false, true>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
-  else patch_load<false, false>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
+  const bool cuni = uH1 && cflag && cflag[(py + py0) * px_count + px] != 0;
+  static_assert(!(FIRST && XF), "level 0 starts from its own u");
+  if (tf != 255u) patch_load<false, true, XF>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
+  else patch_load<false, false, XF>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
   patch_prologue(pc, buf, tabJ, tabR, ptab, nent, utabd, utabi, U);
+  if (XF) patch_form_x(pc, U, utabd, omega, buf);
   lds_barrier();
   PATCH_STAMP(1);
   if (FIRST) {
@@ -1660,6 +1697,8 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
   PATCH_STAMP(4);
   const double* rsb = buf;
   // restriction + first coarse sweep: coarse row c <-> even fine row 2c of the patch
+  // (uH1 == nullptr: the coarse level's kernel forms that sweep from f_H itself -- XF -- and f_H
+  // alone is stored: no coarse diagonal, no division)
   for (int q = threadIdx.x; q < PATCH_TH * (PATCH_TW / 2); q += PATCH_NT) {
     const int lj = q / (PATCH_TW / 2), cx = q - lj * (PATCH_TW / 2);
     const int64_t i = (int64_t)(j0 + lj) * m + i0 + 2 * cx;   // fine row 2c
@@ -1671,6 +1710,7 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
     if (i + 1 < n) sum += 1.0 * rs[1];
     if (i + 2 < n) sum += 0.5 * rs[2];
     fH[c] = sum;
+    if (uH1 == nullptr) continue;
     const double xi = 0.0, acc = 0.0;  // jacobi_from_zero_kernel
     const double d = cuni ? dHu : diagH[c];
     uH1[c] = (d == 0.0) ? xi : xi + omega * ((sum - acc) / d - xi);
@@ -1870,9 +1910,10 @@ static hipError_t patch_dispatch(int un, int umask, bool nt, F&& go) {
 hipError_t launch_patch_down(bool first, int64_t n, int64_t m, const PatchRef& P, const double* x,
                              const double* f, double* u_out, double* r_out, int64_t nH, double* fH,
                              const double* diagH, double* uH1, double omega, hipStream_t st,
-                             int64_t line_lo, int64_t line_hi) {
+                             int64_t line_lo, int64_t line_hi, bool xf) {
+  // uH1 == nullptr: f_H only (the coarse level runs the xf form); xf: x is formed from f, not read
   if (!patch_geometry_ok(n, m) || !P.rtype || !P.ptab || !P.utabd || !P.utabi || (P.ntypes + 1) * patch_un(P.un) > PATCH_MAXTAB ||
-      P.nent != P.ntypes * patch_un(P.un) || !fH || !diagH || !uH1 || !u_out || u_out == x)
+      P.nent != P.ntypes * patch_un(P.un) || !fH || (uH1 && !diagH) || !u_out || u_out == x || (xf ? first : !x))
     return hipErrorInvalidValue;
   int pxc = 0, py0 = 0;
   const unsigned grid = patch_grid(n, m, line_lo, line_hi, &pxc, &py0);
@@ -1881,6 +1922,10 @@ hipError_t launch_patch_down(bool first, int64_t n, int64_t m, const PatchRef& P
   return patch_dispatch(P.un, P.umask, P.nt != 0, [&](auto U, auto M, auto NTF) {
     if (first)
       hipLaunchKernelGGL((patch_down_kernel<decltype(U)::value, decltype(M)::value, true, decltype(NTF)::value>), dim3(grid),
+                         dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, P.nent, P.ntypes, x, f, u_out,
+                         r_out, (int)nH, fH, diagH, uH1, omega, xm, py0, P.tflag, P.cflag, P.dHu);
+    else if (xf)
+      hipLaunchKernelGGL((patch_down_kernel<decltype(U)::value, decltype(M)::value, false, decltype(NTF)::value, true>), dim3(grid),
                          dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, P.nent, P.ntypes, x, f, u_out,
                          r_out, (int)nH, fH, diagH, uH1, omega, xm, py0, P.tflag, P.cflag, P.dHu);
     else

@@ -229,11 +229,14 @@ int patch_kind_umask(int un, int umask);
 int patch_lds_pitch();
 int patch_max_entries();
 // first: both pre-sweeps (x = u) else the second only (x = result of the first sweep);
-// u_out = smoothed level vector (never x), r_out optional, f_H / uH1 as launch_dict_resid_restrict
+// u_out = smoothed level vector (never x), r_out optional, f_H / uH1 as launch_dict_resid_restrict.
+// uH1 == nullptr: f_H alone is stored (neither diagH nor P.dHu is read): for a coarse level whose
+// own down-leg runs with xf.  xf (never with first): x is not read; the kernel forms the first
+// sweep from f and the row types' diagonals, bit for bit what uH1 of the finer level would hold.
 hipError_t launch_patch_down(bool first, int64_t n, int64_t m, const PatchRef& P, const double* x,
                              const double* f, double* u_out, double* r_out, int64_t nH, double* fH,
                              const double* diagH, double* uH1, double omega, hipStream_t st,
-                             int64_t line_lo = 0, int64_t line_hi = -1);
+                             int64_t line_lo = 0, int64_t line_hi = -1, bool xf = false);
 // The patch launchers take a range of grid lines [line_lo, line_hi) (line_hi < 0: the whole
 // level): only the tiles that meet it run (row-block sharding, solver.cpp "slab").
 int patch_tile_lines();

@@ -280,6 +280,7 @@ hipError_t device_galerkin_generic(const DevCsr& A, const DevCsr& P, const DevCs
 }
 
 int g_patch_tile_flags = 1;  // amg_hip_set_patch_tile_flags: A/B switch (same bits either way)
+int g_patch_xf = 1;          // amg_hip_set_patch_xf: A/B switch (same bits either way)
 
 // A level matrix on the device in one of the two layouts the kernels take.
 struct DevMat {
@@ -1314,6 +1315,7 @@ int64_t g_patch_min_rows = 1000000;  // amg_hip_set_patch_min_rows (level 4 of 4
 struct amg_hip_solver {
   amg_hip_options opt;
   int64_t patch_min_rows = g_patch_min_rows;  // the process-wide value when the solver was made
+  int patch_xf = g_patch_xf;                  // likewise
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = true;
@@ -1419,6 +1421,12 @@ bool patch_level_ok(const amg_hip_solver* s, int l) {
         L.n >= s->patch_min_rows && s->lv[l + 1].diag.p != nullptr))
     return false;
   return l == 0 || patch_level_ok(s, l - 1);
+}
+// The hand-over between two K-Patch levels: the down-leg of level l + 1 forms its first sweep from
+// f_{l+1} (the xf form of patch_down_kernel), so the down-leg of level l stores f_{l+1} alone.  ONE
+// predicate decides both sides of the pair, for whole-level and ranged (slab, window) launches alike.
+bool patch_xf_pair(const amg_hip_solver* s, int l) {
+  return s->patch_xf && patch_level_ok(s, l) && patch_level_ok(s, l + 1);
 }
 
 // Multicolour smoother on a level whose colours repeat on the 2 x 2 cells of its 2-D band (the
@@ -1823,7 +1831,8 @@ amg_hip_status enqueue_residual(amg_hip_solver* s, int l) {
 // multigrid.hpp:263-305.  part: the whole cycle, or one of the three pieces a slab-sharded
 // cycle is cut into at its two exchange points (struct Slab): the down-legs of the slab levels
 // over this rank's lines, the replicated rest below them (it begins by redoing the from-zero
-// sweep of its first level on the gathered right-hand side), the up-legs of the slab levels.
+// sweep of its first level on the gathered right-hand side, unless that level is a K-Patch level
+// that forms the sweep itself: patch_xf_pair), the up-legs of the slab levels.
 enum { CYCLE_ALL = 0, CYCLE_SLAB_DOWN = 1, CYCLE_SLAB_TAIL = 2, CYCLE_SLAB_UP = 3 };
 // roctx ranges per level and leg, AMG_HIP_ROCTX=1: "L<l> down" / "L<l> up" /
 // "coarse solve" around what is ENQUEUED for them (librocprofiler-sdk-roctx by dlopen; the ranges
@@ -1894,9 +1903,11 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
   bool tail_done = false;
   if (part == CYCLE_SLAB_TAIL) {
     Level& L = s->lv[k];
-    HIP_TRY(launch_jacobi_from_zero(L.n, L.diag.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
-                                    s->opt.omega, st));
-    s->acct(24.0 * L.n);
+    if (!patch_xf_pair(s, k - 1)) {  // (a K-Patch level below the cut forms that sweep itself)
+      HIP_TRY(launch_jacobi_from_zero(L.n, L.diag.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
+                                      s->opt.omega, st));
+      s->acct(24.0 * L.n);
+    }
     first_sweep_done = true;
   }
   const int down_from = part == CYCLE_SLAB_TAIL ? k : 0;
@@ -1944,22 +1955,25 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
       Level& L = s->lv[l];
       Level& C = s->lv[l + 1];
       const DevMat& A = L.A_rows;
-      const bool first = l == 0;  // l >= 1: the first sweep came from level l-1's kernel (in tmp)
+      const bool first = l == 0;  // l >= 1: the first sweep came from level l-1's kernel (in tmp) ...
+      const bool xf_in = l >= 1 && patch_xf_pair(s, l - 1);  // ... or is formed from f here
+      const bool xf_out = patch_xf_pair(s, l);               // level l+1 forms its own: f_H only
       HIP_TRY(launch_patch_down(first, L.n, A.patch_m, A.patch_ref(),
-                                first ? L.u.as<double>() : L.tmp.as<double>(), L.f.as<double>(),
-                                first ? L.tmp.as<double>() : L.u.as<double>(),
+                                first ? L.u.as<double>() : (xf_in ? nullptr : L.tmp.as<double>()),
+                                L.f.as<double>(), first ? L.tmp.as<double>() : L.u.as<double>(),
                                 s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
-                                C.f.as<double>(), C.diag.as<double>(), C.tmp.as<double>(),
+                                C.f.as<double>(), C.diag.as<double>(), xf_out ? nullptr : C.tmp.as<double>(),
                                 s->opt.omega, st, ranged ? sb.down_lo[l] : 0,
-                                ranged ? sb.down_hi[l] : -1));
-      {  // row types + x + f + smoothed u; f_H, first coarse sweep, coarse diagonal
+                                ranged ? sb.down_hi[l] : -1, xf_in));
+      {  // row types + [x +] f + smoothed u; f_H [, first coarse sweep, coarse diagonal]
         double frac = 1.0;
         if (ranged && sb.down_hi[l] >= 0) {
           const double lines = (double)((L.n + A.patch_m - 1) / A.patch_m);
           frac = std::min(1.0, (double)(sb.down_hi[l] - sb.down_lo[l]) / lines);
         }
         // (the coarse diagonal is not read under the tiles that take it as an argument)
-        s->acct(frac * (25.0 * L.n + (24.0 - 8.0 * A.patch_cfrac) * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0)));
+        s->acct(frac * ((xf_in ? 17.0 : 25.0) * L.n + (xf_out ? 8.0 : 24.0 - 8.0 * A.patch_cfrac) * C.n +
+                        (s->opt.keep_residual ? 8.0 * L.n : 0.0)));
       }
       first_sweep_done = true;
       continue;
@@ -3915,6 +3929,7 @@ void amg_hip_set_row_types(int32_t on) { g_row_types = on ? 1 : 0; }
 void amg_hip_set_dict_rows(int32_t rows_per_lane) { set_dict_rows_per_lane(rows_per_lane); }
 void amg_hip_set_dict_stencil(int32_t on) { set_dict_stencil(on); }
 void amg_hip_set_patch_tile_flags(int32_t on) { g_patch_tile_flags = on ? 1 : 0; }
+void amg_hip_set_patch_xf(int32_t on) { g_patch_xf = on ? 1 : 0; }
 void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
 void amg_hip_set_patch_min_rows(int64_t rows) { g_patch_min_rows = rows < 0 ? INT64_MAX : rows; }
@@ -5011,7 +5026,8 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
       Level& C = s->lv[1];
       HIP_TRY(launch_patch_down(true, L.n, A.patch_m, A.patch_ref(), L.u.as<double>(),
                                 L.f.as<double>(), L.tmp.as<double>(), nullptr, C.n, C.f.as<double>(),
-                                C.diag.as<double>(), C.tmp.as<double>(), s->opt.omega, s->stream,
+                                C.diag.as<double>(), patch_xf_pair(s, 0) ? nullptr : C.tmp.as<double>(),
+                                s->opt.omega, s->stream,
                                 slab ? s->slab.down_lo[0] : 0, slab ? s->slab.down_hi[0] : -1));
     } else {
       HIP_TRY(launch_mat(CSR_JACOBI, A, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
@@ -5097,11 +5113,12 @@ amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int3
                         : rows / (double)L.n * (12.0 * (double)L.nnz_struct + 28.0 * (double)L.n);
     }
   } else if (A.dict && patch_level_ok(s, 0)) {
-    // row types + x + f + smoothed u per fine row; f_H, first coarse sweep, coarse diagonal
-    std::snprintf(name, (size_t)name_cap, "patch_down_kernel<%d, %d, true, %s>", patch_un(A.patch_un),
+    // row types + x + f + smoothed u per fine row; f_H and, unless level 1 forms it from f_H itself
+    // (patch_xf_pair), the first coarse sweep and the coarse diagonal
+    std::snprintf(name, (size_t)name_cap, "patch_down_kernel<%d, %d, true, %s, false>", patch_un(A.patch_un),
                   patch_kind_umask(A.patch_un, A.patch_umask), A.dict_nt ? "true" : "false");
     sweeps = 2;
-    bytes = 25.0 * (double)L.n + (24.0 - 8.0 * A.patch_cfrac) * (double)s->lv[1].n;
+    bytes = 25.0 * (double)L.n + (patch_xf_pair(s, 0) ? 8.0 : 24.0 - 8.0 * A.patch_cfrac) * (double)s->lv[1].n;
     if (s->slab.levels > 0 && s->slab.world > 1) {  // the tiles this rank's launch covers
       const int64_t th = patch_tile_lines();
       const int64_t l0 = s->slab.down_lo[0] / th * th;

@@ -247,6 +247,12 @@ void amg_hip_set_patch_min_rows(int64_t rows);
 /* K-Patch per-tile row-type flags (patches whose rows all share one type skip the row-type
  * loads and the bounds checks) on / off; process-wide, read at launch.  Same bits either way. */
 void amg_hip_set_patch_tile_flags(int32_t on);
+/* K-Patch hand-over between two consecutive K-Patch levels: on (default), the down-leg of the
+ * coarser level forms its first from-zero Jacobi sweep from the right-hand side it holds anyway,
+ * and the finer level's down-leg stores that right-hand side alone instead of the sweep as well
+ * (one vector less written and read per level pair).  Process-wide, read when a solver is
+ * created.  Same bits either way: an A/B switch for tests and measurements.              */
+void amg_hip_set_patch_xf(int32_t on);
 /* K-BandChain (coarsest solve kind 3) on / off; process-wide, read when a solver is created.
  * Same bits either way: an A/B switch for tests and tuning.                             */
 void amg_hip_set_band_chain(int32_t on);

@@ -28,6 +28,8 @@ N = 4096
 LEVEL_ROWS = [16777216, 8388607, 4194303, 2097151, 1048575]          # 4096^2 hierarchy
 LEVEL_NNZ = [83869696, 75485173, 37742581, 18871285, 9435637]
 PITCH = [4096, 2048, 1024, 512, 256]
+PATCH_LEVELS = 5            # levels 0-4 of the 4096^2 cycle are K-Patch levels (at least 10^6 rows)
+XF_HANDOVER = True          # set from the kernel names in main(): a patch_down_kernel<..., true> ran
 
 
 def patch_grid(l):
@@ -39,12 +41,16 @@ def patch_grid(l):
 
 def classify(name, grid):
     """(kind, level, code words) of a launch, or (None, None, 0)"""
-    m = re.match(r"patch_(down|up)_kernel<(\d+), ", name)
+    m = re.match(r"patch_(down|up)_kernel<([\w, ]+)>", name)
     if m:
+        targs = m.group(2).split(", ")
         for l in range(len(LEVEL_ROWS)):
             if patch_grid(l) == grid:
-                first = ", true, " in name and m.group(1) == "down"
-                return ("patch_down_first" if first else "patch_" + m.group(1)), l, 0
+                if m.group(1) == "up":
+                    return "patch_up", l, 0
+                # <slots, mask, first, nt, xf>: xf = the first sweep is formed from f, not loaded
+                return ("patch_down_first" if targs[2] == "true" else
+                        "patch_down_xf" if targs[4:5] == ["true"] else "patch_down"), l, 0
         return None, None, 0
     rows, kind, words = None, None, 0
     m = re.match(r"dict_kernel<(\d+), (\d+), \d+, \w+, (\d+)>", name)
@@ -75,8 +81,12 @@ def must_move(kind, l):
         return n * 17 + nH * 24
     if kind == "jacobi_prolong":             # + read-modify-write of the finer u
         return n * 25 + LEVEL_ROWS[l - 1] * 16
-    if kind in ("patch_down_first", "patch_down"):   # x, f, type, smoothed u; f_H, u_H (the coarse diagonal is a
-        return n * 25 + nH * 16                      # kernel argument under interior tiles: > 99 % of them)
+    # K-Patch down-legs: [x,] f, type, smoothed u; f_H and, where the coarser level is no K-Patch level
+    # (XF_HANDOVER false), its first sweep u_H (the coarse diagonal is a kernel argument under interior
+    # tiles: > 99 % of them).  Between K-Patch levels the coarser one forms that sweep from f_H itself.
+    if kind in ("patch_down_first", "patch_down", "patch_down_xf"):
+        handover = XF_HANDOVER and l + 1 < PATCH_LEVELS
+        return n * (17 if kind == "patch_down_xf" else 25) + nH * (8 if handover else 16)
     if kind == "patch_up":                   # x, f, type, u_H in; u out
         return n * 25 + nH * 8
     if kind == "sell":
@@ -86,7 +96,9 @@ def must_move(kind, l):
 
 def main():
     from bench import source_sha16
+    global XF_HANDOVER
     f, w, tag = load(sys.argv[1]), load(sys.argv[2]), sys.argv[3]
+    XF_HANDOVER = any(classify(name, grid)[0] == "patch_down_xf" for name, grid in f)
     note = sys.argv[4] if len(sys.argv) > 4 else "default layout (dictionary-coded rows, K-Patch on levels 0-3)"
     lines = [f"# rocprofv3 PMC traffic, {tag} (MI355X, bench.py, 4096^2, {note})", "",
              "Two separate passes (`rocprofv3 --pmc FETCH_SIZE --kernel-trace` and `--pmc WRITE_SIZE --kernel-trace`),",
@@ -111,8 +123,9 @@ def main():
                                "traffic_bytes": tr, "must_move_bytes": mm, "csr_formula_bytes": alg}
     lines += ["", "`must move` = what one launch has to read and write once (bench.py roofline.algorithmic_bytes_per_launch):",
               "dict_kernel: 1 B row type + f + x + out per row; the fused forms add their transfer operands;",
-              "patch_down_kernel<slots, mask, first, nt>: the level's whole down-leg (x, f, type in; smoothed u, f_H, first coarse",
-              "sweep out; the coarse diagonal is a kernel argument under interior tiles), patch_up_kernel: the up-leg (x, f, type,",
+              "patch_down_kernel<slots, mask, first, nt, xf>: the level's whole down-leg (x, f, type in; smoothed u, f_H, first coarse",
+              "sweep out; the coarse diagonal is a kernel argument under interior tiles; xf: x is formed from f and not read, and a",
+              "level whose coarser level runs the xf form stores f_H alone), patch_up_kernel: the up-leg (x, f, type,",
               "u_H in; u out).  traffic / must move",
               "above 1 = halo re-reads that miss the L2 / Infinity Cache.", ""]
     out_dir = os.environ.get("PMC_OUT_DIR", os.path.join(ROOT, "profiles"))
