@@ -115,6 +115,16 @@ _SIGS = {
                                             C.c_int32, _i64p, C.c_int32, C.POINTER(Options),
                                             C.POINTER(C.c_void_p)]),
     "amg_hip_get_level_dims": (C.c_int, [C.c_void_p, C.c_int32, _i64p]),
+    "amg_hip_create_tensor_semi": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
+                                             C.c_int32, _i32p, C.c_double, C.c_int64, C.POINTER(Options),
+                                             C.POINTER(C.c_void_p)]),
+    "amg_hip_create_tensor_semi_dev": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int32, _i64p, C.c_int32, _i32p, C.c_double, C.c_int64,
+                                                 C.POINTER(Options), C.POINTER(C.c_void_p)]),
+    "amg_hip_get_level_axes": (C.c_int, [C.c_void_p, C.c_int32, _i32p]),
+    "amg_hip_tensor_axis_strength": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, C.c_int32, _i64p, _f64p]),
+    "amg_hip_tensor_restrict_axes": (C.c_int, [C.c_int32, _i64p, C.c_int32, _f64p, _f64p]),
+    "amg_hip_tensor_prolong_add_axes": (C.c_int, [C.c_int32, _i64p, C.c_int32, _f64p, _f64p]),
     "amg_hip_level_transfer_kind": (C.c_int, [C.c_void_p, C.c_int32, _i32p]),
     "amg_hip_tensor_restrict": (C.c_int, [C.c_int32, _i64p, _f64p, _f64p]),
     "amg_hip_tensor_prolong_add": (C.c_int, [C.c_int32, _i64p, _f64p, _f64p]),
@@ -533,7 +543,7 @@ class Multigrid:
                stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
                no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
-               window=False):
+               window=False, _semi=None):
         """AMG::Multigrid on a FULL-coarsening hierarchy of the grid `dims` = (nx, ny) or (nx, ny, nz),
         x fastest (amg_hip_create_tensor): every axis m -> m // 2, tensor-product linear interpolation,
         matrix-free transfer kernels unless stencil_transfers=False.  A is the caller's matrix on
@@ -555,8 +565,15 @@ class Multigrid:
                          cheb_upper)
         o.window = int(window)
         h = C.c_void_p()
-        st = lib().amg_hip_create_tensor(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
-                                         d3.ctypes.data_as(_i64p), int(n_levels), C.byref(o), C.byref(h))
+        if _semi is not None:  # tensor_semi
+            masks, theta, min_coarse = _semi
+            st = lib().amg_hip_create_tensor_semi(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
+                                                  d3.ctypes.data_as(_i64p), int(n_levels),
+                                                  None if masks is None else _p32(masks), float(theta),
+                                                  int(min_coarse), C.byref(o), C.byref(h))
+        else:
+            st = lib().amg_hip_create_tensor(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
+                                             d3.ctypes.data_as(_i64p), int(n_levels), C.byref(o), C.byref(h))
         if st == EINVAL:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)
@@ -570,7 +587,7 @@ class Multigrid:
                    stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
                    no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                    exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
-                   window=False, host_galerkin=False, fuse_prolong=False):
+                   window=False, host_galerkin=False, fuse_prolong=False, _semi=None):
         """Multigrid.tensor for a matrix that sits on the device, with the set-up on the device
         (amg_hip_create_tensor_dev).  A is in CSR: crow (n + 1 int32 row pointers), col (int32,
         ascending inside a row), val (float64), and b (n float64), each a contiguous 1-D torch tensor
@@ -627,8 +644,15 @@ class Multigrid:
         self = cls.__new__(cls)
         self.tolerance, self.every, self.n_iters = tolerance, compute_error_every_n_iters, n_iters
         h = C.c_void_p()
-        st = lib().amg_hip_create_tensor_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
-                                             d3.ctypes.data_as(_i64p), int(n_levels), C.byref(o), C.byref(h))
+        if _semi is not None:  # tensor_semi_dev
+            masks, theta, min_coarse = _semi
+            st = lib().amg_hip_create_tensor_semi_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
+                                                      d3.ctypes.data_as(_i64p), int(n_levels),
+                                                      None if masks is None else _p32(masks), float(theta),
+                                                      int(min_coarse), C.byref(o), C.byref(h))
+        else:
+            st = lib().amg_hip_create_tensor_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
+                                                 d3.ctypes.data_as(_i64p), int(n_levels), C.byref(o), C.byref(h))
         del dev
         if st == EINVAL:
             raise ValueError(lib().amg_hip_last_error().decode())
@@ -636,6 +660,35 @@ class Multigrid:
         self._h = h
         self._device = device
         return self
+
+    @staticmethod
+    def _semi_rule(n_levels, axis_masks, theta, min_coarse):
+        if axis_masks is None:
+            return (None, theta, min_coarse)
+        masks = np.ascontiguousarray([int(m) for m in axis_masks], dtype=np.int32)
+        if masks.size != int(n_levels) - 1:
+            raise ValueError(f"`axis_masks` must have n_levels - 1 = {int(n_levels) - 1} entries, got {masks.size}")
+        return (masks, theta, min_coarse)
+
+    @classmethod
+    def tensor_semi(cls, colptr, rowind, val, b, dims, n_levels, axis_masks=None, theta=0.5, min_coarse=32,
+                    **opts):
+        """AMG::Multigrid on a SEMI-coarsening hierarchy of the grid `dims` (amg_hip_create_tensor_semi):
+        level l coarsens the axes of its mask (bit 0 = x, 1 = y, 2 = z) and leaves the others alone.
+        axis_masks: n_levels - 1 explicit masks, or None for the automatic rule -- coarsen the axes
+        whose strongest coupling is at least theta times the strongest of all, until n_levels, a level
+        of at most min_coarse rows, or no axis of 2 points (n_levels tells).  For operators that are
+        anisotropic along a grid axis; options as for Multigrid.tensor."""
+        return cls.tensor(colptr, rowind, val, b, dims, n_levels,
+                          _semi=cls._semi_rule(n_levels, axis_masks, theta, min_coarse), **opts)
+
+    @classmethod
+    def tensor_semi_dev(cls, crow, col, val, b, dims, n_levels, axis_masks=None, theta=0.5, min_coarse=32,
+                        **opts):
+        """Multigrid.tensor_semi for a CSR matrix that sits on the device, with the set-up on the device
+        (amg_hip_create_tensor_semi_dev); arguments as for Multigrid.tensor_dev."""
+        return cls.tensor_dev(crow, col, val, b, dims, n_levels,
+                              _semi=cls._semi_rule(n_levels, axis_masks, theta, min_coarse), **opts)
 
     @classmethod
     def poisson_tensor(cls, n, n_levels, dim=2, device_setup=False, **opts):
@@ -691,6 +744,16 @@ class Multigrid:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)
         return tuple(int(x) for x in d)
+
+    def level_axes(self, level):
+        """Axis mask (bit 0 = x, 1 = y, 2 = z) of the transfers between `level` and `level` + 1 of a
+        tensor solver (amg_hip_get_level_axes)."""
+        m = C.c_int32(-1)
+        st = lib().amg_hip_get_level_axes(self._h, int(level), C.byref(m))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return m.value
 
     def level_transfer_kind(self, level):
         """0 = CSR SpMV transfers, 1 = the flat stride-2 kernels, 2 = the tensor-product kernels."""
@@ -1155,35 +1218,58 @@ def _dims3(dims):
     return len(dims), np.array(dims + (1,) * (3 - len(dims)), np.int64)
 
 
-def _tensor_sizes(d3, dim):
-    c = [int(d3[0]) // 2, int(d3[1]) // 2, int(d3[2]) // 2 if dim == 3 else 1]
+def _tensor_sizes(d3, dim, axes=None):
+    m = (7 if dim == 3 else 3) if axes is None else int(axes)
+    c = [int(d3[a]) // 2 if (m >> a) & 1 and a < dim else int(d3[a]) for a in range(3)]
     return int(d3[0] * d3[1] * d3[2]), c[0] * c[1] * c[2]
 
 
-def tensor_restrict(dims, r):
-    """f_H = R r for the full-coarsening transfer of the fine grid `dims` (amg_hip_tensor_restrict)."""
+def tensor_axis_strength(colptr, rowind, val, dims):
+    """w of the automatic semi-coarsening rule: per axis the largest |a_ij| between neighbours along
+    that axis alone (amg_hip_tensor_axis_strength; host only)."""
+    colptr, rowind, val = _a32(colptr), _a32(rowind), _a64(val)
+    dim, d3 = _dims3(dims)
+    w = np.zeros(3, np.float64)
+    st = lib().amg_hip_tensor_axis_strength(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), dim,
+                                            d3.ctypes.data_as(_i64p), _p64(w))
+    if st == EINVAL:
+        raise ValueError(lib().amg_hip_last_error().decode())
+    _chk(st)
+    return w
+
+
+def tensor_restrict(dims, r, axes=None):
+    """f_H = R r for the full-coarsening transfer of the fine grid `dims` (amg_hip_tensor_restrict);
+    axes: the mask of coarsened axes instead (amg_hip_tensor_restrict_axes)."""
     dim, d3 = _dims3(dims)
     r = _a64(r)
-    n_h, n_H = _tensor_sizes(d3, dim)
+    n_h, n_H = _tensor_sizes(d3, dim, axes)
     if r.size != n_h:
         raise ValueError(f"`r` must have {n_h} entries, got {r.size}")
     out = np.empty(max(n_H, 0), np.float64)
-    st = lib().amg_hip_tensor_restrict(dim, d3.ctypes.data_as(_i64p), _p64(r), _p64(out))
+    if axes is not None:
+        st = lib().amg_hip_tensor_restrict_axes(dim, d3.ctypes.data_as(_i64p), int(axes), _p64(r), _p64(out))
+    else:
+        st = lib().amg_hip_tensor_restrict(dim, d3.ctypes.data_as(_i64p), _p64(r), _p64(out))
     if st == EINVAL:
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)
     return out
 
 
-def tensor_prolong_add(dims, u_H, u_h):
-    """u_h + P u_H for the same transfer (amg_hip_tensor_prolong_add); returns a new array."""
+def tensor_prolong_add(dims, u_H, u_h, axes=None):
+    """u_h + P u_H for the same transfer (amg_hip_tensor_prolong_add, or amg_hip_tensor_prolong_add_axes
+    with the mask `axes`); returns a new array."""
     dim, d3 = _dims3(dims)
     u_H = _a64(u_H)
     u_h = np.array(u_h, dtype=np.float64, copy=True)
-    n_h, n_H = _tensor_sizes(d3, dim)
+    n_h, n_H = _tensor_sizes(d3, dim, axes)
     if u_h.size != n_h or u_H.size != n_H:
         raise ValueError(f"`u_h` / `u_H` must have {n_h} / {n_H} entries, got {u_h.size} / {u_H.size}")
-    st = lib().amg_hip_tensor_prolong_add(dim, d3.ctypes.data_as(_i64p), _p64(u_H), _p64(u_h))
+    if axes is not None:
+        st = lib().amg_hip_tensor_prolong_add_axes(dim, d3.ctypes.data_as(_i64p), int(axes), _p64(u_H), _p64(u_h))
+    else:
+        st = lib().amg_hip_tensor_prolong_add(dim, d3.ctypes.data_as(_i64p), _p64(u_H), _p64(u_h))
     if st == EINVAL:
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)

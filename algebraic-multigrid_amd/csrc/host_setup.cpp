@@ -173,48 +173,88 @@ bool is_linear_P(const Sparse& P, int64_t n_h, int64_t n_H) {
 // Full coarsening of an nx x ny x nz grid (x fastest): P = P1(nz) (x) P1(ny) (x) P1(nx) with P1(m)
 // the m x floor(m/2) matrix whose column j holds 0.5, 1.0, 0.5 on rows 2j, 2j+1, 2j+2 (guarded by
 // < m); an axis that is not coarsened (nz of a 2-D grid) contributes the identity.
+void tensor_coarse_dims(int dim, const int64_t d[3], uint32_t mask, int64_t c[3]) {
+  c[0] = (mask & 1u) ? d[0] / 2 : d[0];
+  c[1] = (mask & 2u) ? d[1] / 2 : d[1];
+  c[2] = (dim == 3 && (mask & 4u)) ? d[2] / 2 : (dim == 3 ? d[2] : 1);
+}
 void tensor_coarse_dims(int dim, const int64_t d[3], int64_t c[3]) {
-  c[0] = d[0] / 2;
-  c[1] = d[1] / 2;
-  c[2] = dim == 3 ? d[2] / 2 : 1;
+  tensor_coarse_dims(dim, d, tensor_full_mask(dim), c);
 }
 
-Sparse tensor_P(int dim, const int64_t d[3]) {
+Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask) {
   int64_t c[3];
-  tensor_coarse_dims(dim, d, c);
+  tensor_coarse_dims(dim, d, mask, c);
   const int64_t nx = d[0], ny = d[1], nz = dim == 3 ? d[2] : 1;
+  const bool cx = (mask & 1u) != 0, cy = (mask & 2u) != 0, cz = dim == 3 && (mask & 4u) != 0;
   Sparse P;  // CSC: outer = coarse column (K, J, I), I fastest
   P.n_outer = c[0] * c[1] * c[2];
   P.n_inner = nx * ny * nz;
   P.ptr.resize((size_t)P.n_outer + 1);
   P.ptr[0] = 0;
-  P.idx.reserve((size_t)(dim == 3 ? 27 : 9) * (size_t)P.n_outer);
-  P.val.reserve((size_t)(dim == 3 ? 27 : 9) * (size_t)P.n_outer);
+  const size_t per = (size_t)(cx ? 3 : 1) * (cy ? 3 : 1) * (cz ? 3 : 1);
+  P.idx.reserve(per * (size_t)P.n_outer);
+  P.val.reserve(per * (size_t)P.n_outer);
   static const double w3[3] = {0.5, 1.0, 0.5};
-  const int tz_n = dim == 3 ? 3 : 1;
+  const int tx_n = cx ? 3 : 1, ty_n = cy ? 3 : 1, tz_n = cz ? 3 : 1;
   int64_t col = 0;
   for (int64_t K = 0; K < c[2]; ++K)
     for (int64_t J = 0; J < c[1]; ++J)
       for (int64_t I = 0; I < c[0]; ++I) {
         for (int tz = 0; tz < tz_n; ++tz) {  // ascending fine row: k, then j, then i
-          const int64_t k = dim == 3 ? 2 * K + tz : 0;
+          const int64_t k = cz ? 2 * K + tz : K;
           if (k >= nz) continue;
-          const double wz = dim == 3 ? w3[tz] : 1.0;
-          for (int ty = 0; ty < 3; ++ty) {
-            const int64_t j = 2 * J + ty;
+          const double wz = cz ? w3[tz] : 1.0;
+          for (int ty = 0; ty < ty_n; ++ty) {
+            const int64_t j = cy ? 2 * J + ty : J;
             if (j >= ny) continue;
-            const double wzy = wz * w3[ty];
-            for (int tx = 0; tx < 3; ++tx) {
-              const int64_t i = 2 * I + tx;
+            const double wzy = wz * (cy ? w3[ty] : 1.0);
+            for (int tx = 0; tx < tx_n; ++tx) {
+              const int64_t i = cx ? 2 * I + tx : I;
               if (i >= nx) continue;
               P.idx.push_back((int32_t)((k * ny + j) * nx + i));
-              P.val.push_back(wzy * w3[tx]);  // products of powers of two: exact
+              P.val.push_back(wzy * (cx ? w3[tx] : 1.0));  // products of powers of two: exact
             }
           }
         }
         P.ptr[(size_t)++col] = (int32_t)P.idx.size();
       }
   return P;
+}
+Sparse tensor_P(int dim, const int64_t d[3]) { return tensor_P(dim, d, tensor_full_mask(dim)); }
+
+void tensor_axis_strength(const Sparse& M, int dim, const int64_t d[3], double w[3]) {
+  const int64_t nx = d[0], ny = d[1];
+  (void)dim;
+  w[0] = w[1] = w[2] = 0.0;
+  for (int64_t o = 0; o < M.n_outer; ++o) {
+    const int64_t oi = o % nx, oj = (o / nx) % ny, ok = o / (nx * ny);
+    for (int32_t p = M.ptr[o]; p < M.ptr[o + 1]; ++p) {
+      const int64_t c = M.idx[p];
+      const int64_t dx = c % nx - oi, dy = (c / nx) % ny - oj, dz = c / (nx * ny) - ok;
+      const int64_t ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy, az = dz < 0 ? -dz : dz;
+      if (ax + ay + az != 1) continue;
+      const int a = ax ? 0 : (ay ? 1 : 2);
+      const double v = std::fabs(M.val[p]);
+      if (v > w[a]) w[a] = v;  // NaN never wins, as in the device reduction
+    }
+  }
+}
+
+uint32_t tensor_auto_mask(int dim, const int64_t d[3], const double w[3], double theta) {
+  double top = 0.0;
+  bool any = false;
+  for (int a = 0; a < dim; ++a)
+    if (d[a] >= 2) {
+      any = true;
+      if (w[a] > top) top = w[a];
+    }
+  if (!any) return 0u;
+  const double cut = theta * top;
+  uint32_t mask = 0u;
+  for (int a = 0; a < dim; ++a)
+    if (d[a] >= 2 && w[a] >= cut) mask |= 1u << a;
+  return mask;
 }
 
 // ------------------------------------------------------------------ SpGEMM ---

@@ -41,6 +41,21 @@ bool is_linear_P(const Sparse& P, int64_t n_h, int64_t n_H);
 void tensor_coarse_dims(int dim, const int64_t dims[3], int64_t coarse[3]);
 Sparse tensor_P(int dim, const int64_t dims[3]);
 
+// Semi-coarsening: `mask` names the axes that are coarsened (bit 0 = x, bit 1 = y, bit 2 = z).  A
+// masked axis of length m goes to floor(m / 2) with P1(m), an unmasked one keeps its length with
+// the identity; P = P_z (x) P_y (x) P_x, R = transpose(P).  The signatures above pass the full mask.
+inline uint32_t tensor_full_mask(int dim) { return dim == 3 ? 7u : 3u; }
+void tensor_coarse_dims(int dim, const int64_t dims[3], uint32_t mask, int64_t coarse[3]);
+Sparse tensor_P(int dim, const int64_t dims[3], uint32_t mask);
+// The automatic rule.  w[a] = max |a_ij| over the entries of A (rows_as: either compressed form,
+// the maximum does not depend on it) whose column's grid coordinates differ from the row's by
+// +-1 in axis a and by 0 in the others; 0 when there is none.  A maximum of non-negative doubles
+// does not depend on the order, so the device reduction (K-AxisStrength) gives the same bits.
+void tensor_axis_strength(const Sparse& rows_as, int dim, const int64_t dims[3], double w[3]);
+// Axis a is eligible when dims[a] >= 2 (and a < dim); an eligible axis is coarsened iff
+// w[a] >= theta * max over the eligible axes of w.  0: no axis is eligible.
+uint32_t tensor_auto_mask(int dim, const int64_t dims[3], const double w[3], double theta);
+
 // multigrid.hpp:127-130
 inline int64_t coarse_dofs(int64_t n_h) { return (n_h + 1) / 2 - 1; }
 

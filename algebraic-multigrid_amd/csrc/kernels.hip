@@ -314,6 +314,60 @@ hipError_t launch_gershgorin(int64_t n, const int32_t* rowptr, const int32_t* co
   return hipGetLastError();
 }
 
+// K-AxisStrength (kernels.hpp: launch_axis_strength): per grid axis the maximum of |a_ij| over the
+// entries whose column is the row's neighbour along that axis alone; one lane per row.  Like the
+// Gershgorin bound: a maximum of non-negative doubles is order-independent and orders like the bit
+// patterns, so the three block maxima go out as 64-bit atomic maxima and equal the host's bits.
+__global__ __launch_bounds__(256) void axis_strength_kernel(uint32_t n, uint32_t nx, uint32_t ny,
+                                                            const int32_t* __restrict__ rowptr,
+                                                            const int32_t* __restrict__ col,
+                                                            const double* __restrict__ val,
+                                                            unsigned long long* out) {
+  __shared__ double red[3][256];
+  const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+  double w[3] = {0.0, 0.0, 0.0};
+  if (row < n) {
+    const uint32_t ri = row % nx, rq = row / nx, rj = rq % ny, rk = rq / ny;
+    for (int32_t p = rowptr[row], e = rowptr[row + 1]; p < e; ++p) {
+      const uint32_t c = (uint32_t)col[p];
+      const uint32_t ci = c % nx, cq = c / nx, cj = cq % ny, ck = cq / ny;
+      const int32_t dx = (int32_t)ci - (int32_t)ri, dy = (int32_t)cj - (int32_t)rj, dz = (int32_t)ck - (int32_t)rk;
+      const int32_t ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy, az = dz < 0 ? -dz : dz;
+      if (ax + ay + az != 1) continue;
+      const double v = fabs(val[p]);
+      if (ax) { if (v > w[0]) w[0] = v; }
+      else if (ay) { if (v > w[1]) w[1] = v; }
+      else { if (v > w[2]) w[2] = v; }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) red[a][threadIdx.x] = w[a];
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) red[a][threadIdx.x] = fmax(red[a][threadIdx.x], red[a][threadIdx.x + h]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) atomicMax(out + threadIdx.x, (unsigned long long)__double_as_longlong(red[threadIdx.x][0]));
+}
+__global__ void axis_strength_init_kernel(unsigned long long* out) {
+  if (threadIdx.x < 3) out[threadIdx.x] = 0ull;
+}
+hipError_t launch_axis_strength(int64_t n, int dim, const int64_t dims[3], const int32_t* rowptr, const int32_t* col,
+                                const double* val, uint64_t* out, hipStream_t st) {
+  if ((dim != 2 && dim != 3) || !dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1 ||
+      n != dims[0] * dims[1] * dims[2] || n >= ((int64_t)1 << 31))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(axis_strength_init_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned long long*>(out));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(axis_strength_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (uint32_t)n,
+                     (uint32_t)dims[0], (uint32_t)dims[1], rowptr, col, val, reinterpret_cast<unsigned long long*>(out));
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- K-SELL -----
 // Same four operations on the solver's own level matrices, stored as CSR sliced
 // into 64-row panels with each panel lane-interleaved (SELL-64): entry j of row
@@ -2817,12 +2871,14 @@ hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
 // ------------------------------------- K-TensorRestrict / K-TensorProlong ---
 // Full coarsening (host_setup.hpp: tensor_P): P = P1(nz) (x) P1(ny) (x) P1(nx), R = P^T, every axis
 // m -> floor(m / 2), weights 0.5, 1.0, 0.5 on fine points 2J, 2J+1, 2J+2 (< m) of coarse point J.
+// Semi-coarsening (the axis mask of tensor_P): an axis that is not coarsened keeps its length and
+// contributes the identity -- one fine point J with weight 1.0 instead of three.
 // All weights are products of powers of two, so every term w * v is exact and only the ORDER of
 // the additions decides the bits: both kernels add in the order the CSR SpMV with R / P does.
 struct TensorGrid {
   uint32_t nx, ny, nz;  // fine
-  uint32_t mx, my, mz;  // coarse (mz == nz == 1 when z is not coarsened)
-  uint32_t cz;          // 1: z is coarsened (3-D)
+  uint32_t mx, my, mz;  // coarse (m == n on an axis that is not coarsened)
+  uint32_t cx, cy, cz;  // 1: the axis is coarsened
 };
 
 // One lane per coarse point (I, J, K): f_H = sum over k, j, i ascending (row order of R) of
@@ -2839,21 +2895,26 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
   if (t >= nH) return;
   const uint32_t I = t % g.mx, q = t / g.mx, J = q % g.my, K = q / g.my;
   if (uH) uH[t] = T(0.0);
-  const uint32_t i0 = 2u * I;        // i0 + 1 < nx always (I < floor(nx / 2))
+  const uint32_t i0 = g.cx ? 2u * I : I;  // cx: i0 + 1 < nx always (I < floor(nx / 2))
   const bool third = i0 + 2u < g.nx;
   T s = T(0.0);
 #pragma unroll
   for (uint32_t tz = 0; tz < 3; ++tz) {
     if (!g.cz && tz > 0) break;
-    const uint32_t k = g.cz ? 2u * K + tz : 0u;
+    const uint32_t k = g.cz ? 2u * K + tz : K;
     if (k >= g.nz) break;
     const T wz = g.cz ? (tz == 1 ? T(1.0) : T(0.5)) : T(1.0);
 #pragma unroll
     for (uint32_t ty = 0; ty < 3; ++ty) {
-      const uint32_t j = 2u * J + ty;
+      if (!g.cy && ty > 0) break;
+      const uint32_t j = g.cy ? 2u * J + ty : J;
       if (j >= g.ny) break;
-      const T w = wz * (ty == 1 ? T(1.0) : T(0.5));
+      const T w = wz * (g.cy ? (ty == 1 ? T(1.0) : T(0.5)) : T(1.0));
       const int64_t a = ((int64_t)k * g.ny + j) * g.nx + i0;  // a + 1 (and a + 2 when third) < n_h
+      if (!g.cx) {  // x is not coarsened: the one fine point I, neighbouring lanes read neighbours
+        s += (w * T(1.0)) * r[a];
+        continue;
+      }
       T v0, v1, v2 = T(0.0);
       if (VEC && (a & 1) == 0) {
         const P2 p = *reinterpret_cast<const P2*>(r + a);
@@ -2881,7 +2942,9 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
 // One lane per fine pair (2p, 2p+1) of a fine grid line: u_h += t, t = sum over K, J, I ascending
 // (row order of P) of (wz wy wx) u_H[(K my + J) mx + I] from +0.0; 16-byte read-modify-write of
 // u_h where the address allows.  An odd fine index has the one coarse neighbour (i - 1) / 2 with
-// weight 1, an even one i / 2 - 1 and i / 2 with weight 0.5 (those that exist).
+// weight 1, an even one i / 2 - 1 and i / 2 with weight 0.5 (those that exist).  On an axis that is
+// not coarsened a fine point has the one coarse neighbour of its own index with weight 1; along x
+// the lane's fine pair then reads the coarse pair (2p, 2p+1), 16 bytes where that address allows.
 template <class T, bool VEC>
 __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
     TensorGrid g, const T* __restrict__ uH, T* uh) {
@@ -2895,7 +2958,10 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   uint32_t Jc[2], Kc[2];
   T wy[2], wz[2];
   bool oky[2], okz[2];
-  if (j & 1u) {
+  if (!g.cy) {
+    Jc[0] = j; wy[0] = 1.0; oky[0] = true;
+    Jc[1] = 0; wy[1] = 0.0; oky[1] = false;
+  } else if (j & 1u) {
     Jc[0] = (j - 1u) / 2u; wy[0] = 1.0; oky[0] = Jc[0] < g.my;
     Jc[1] = 0; wy[1] = 0.0; oky[1] = false;
   } else {
@@ -2903,7 +2969,7 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
     Jc[1] = j / 2u; wy[1] = 0.5; oky[1] = Jc[1] < g.my;
   }
   if (!g.cz) {
-    Kc[0] = 0; wz[0] = 1.0; okz[0] = true;
+    Kc[0] = k; wz[0] = 1.0; okz[0] = true;
     Kc[1] = 0; wz[1] = 0.0; okz[1] = false;
   } else if (k & 1u) {
     Kc[0] = (k - 1u) / 2u; wz[0] = 1.0; okz[0] = Kc[0] < g.mz;
@@ -2912,8 +2978,9 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
     Kc[0] = k / 2u - 1u; wz[0] = 0.5; okz[0] = k >= 2u && Kc[0] < g.mz;
     Kc[1] = k / 2u; wz[1] = 0.5; okz[1] = Kc[1] < g.mz;
   }
-  const bool left = p >= 1u && p - 1u < g.mx;  // coarse I = p - 1 feeds fine 2p
-  const bool mid = p < g.mx;                   // coarse I = p feeds fine 2p and 2p + 1
+  const bool left = g.cx && p >= 1u && p - 1u < g.mx;  // coarse I = p - 1 feeds fine 2p
+  const bool mid = g.cx && p < g.mx;                   // coarse I = p feeds fine 2p and 2p + 1
+  const bool two = 2u * p + 1u < g.nx;                 // the lane's pair is whole
   T t0 = T(0.0), t1 = T(0.0);
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
@@ -2922,6 +2989,17 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
       if (okz[a] && oky[b]) {
         const T w = wz[a] * wy[b];
         const T* c = uH + ((int64_t)Kc[a] * g.my + Jc[b]) * g.mx;
+        if (!g.cx) {  // mx == nx: coarse 2p feeds fine 2p, coarse 2p + 1 fine 2p + 1
+          const T* c2 = c + 2u * p;
+          if (VEC && two && (reinterpret_cast<uintptr_t>(c2) & (sizeof(P2) - 1u)) == 0) {
+            const P2 m = *reinterpret_cast<const P2*>(c2);
+            t0 += (w * T(1.0)) * m.x;
+            t1 += (w * T(1.0)) * m.y;
+          } else {
+            t0 += (w * T(1.0)) * c2[0];
+            if (two) t1 += (w * T(1.0)) * c2[1];
+          }
+        }
         if (left) t0 += (w * T(0.5)) * c[p - 1u];
         if (mid) {
           const T m = c[p];
@@ -2932,7 +3010,7 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
     }
   }
   const int64_t i = (int64_t)row * g.nx + 2u * p;
-  if (2u * p + 1u < g.nx) {
+  if (two) {
     if (VEC && (i & 1) == 0) {
       P2 u = *reinterpret_cast<const P2*>(uh + i);
       u.x = u.x + t0;
@@ -2947,25 +3025,29 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   }
 }
 
-static bool tensor_grid(int dim, const int64_t dims[3], TensorGrid* g) {
+static bool tensor_grid(int dim, const int64_t dims[3], uint32_t mask, TensorGrid* g) {
   if ((dim != 2 && dim != 3) || !dims) return false;
+  if (mask == 0u || mask > (dim == 3 ? 7u : 3u)) return false;
   const int64_t nx = dims[0], ny = dims[1], nz = dim == 3 ? dims[2] : 1;
-  if (nx < 2 || ny < 2 || (dim == 3 && nz < 2) || (dim == 2 && dims[2] != 1)) return false;
+  if (nx < 1 || ny < 1 || nz < 1 || (dim == 2 && dims[2] != 1)) return false;
+  g->cx = mask & 1u;
+  g->cy = (mask >> 1) & 1u;
+  g->cz = (mask >> 2) & 1u;
+  if ((g->cx && nx < 2) || (g->cy && ny < 2) || (g->cz && nz < 2)) return false;
   if (nx >= ((int64_t)1 << 31) / ny / nz - 2) return false;  // 32-bit lane indices
   g->nx = (uint32_t)nx;
   g->ny = (uint32_t)ny;
   g->nz = (uint32_t)nz;
-  g->mx = (uint32_t)(nx / 2);
-  g->my = (uint32_t)(ny / 2);
-  g->mz = dim == 3 ? (uint32_t)(nz / 2) : 1u;
-  g->cz = dim == 3 ? 1u : 0u;
+  g->mx = (uint32_t)(g->cx ? nx / 2 : nx);
+  g->my = (uint32_t)(g->cy ? ny / 2 : ny);
+  g->mz = (uint32_t)(g->cz ? nz / 2 : nz);
   return true;
 }
 template <class T>
-static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], const T* r, T* fH, T* uH_zero,
+static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], uint32_t mask, const T* r, T* fH, T* uH_zero,
                                            hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, &g)) return hipErrorInvalidValue;
   const uint32_t nH = g.mx * g.my * g.mz;
   const dim3 grid((nH + 255u) / 256u), block(256);
   if (pair_aligned(r))
@@ -2974,14 +3056,15 @@ static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], const
     hipLaunchKernelGGL((tensor_restrict_kernel<T, false>), grid, block, 0, st, g, r, fH, uH_zero);
   return hipGetLastError();
 }
-hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], const double* r, double* fH,
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, const double* r, double* fH,
                                   double* uH_zero, hipStream_t st) {
-  return launch_tensor_restrict_t<double>(dim, dims, r, fH, uH_zero, st);
+  return launch_tensor_restrict_t<double>(dim, dims, mask, r, fH, uH_zero, st);
 }
 template <class T>
-static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], const T* uH, T* uh, hipStream_t st) {
+static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], uint32_t mask, const T* uH, T* uh,
+                                              hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, &g)) return hipErrorInvalidValue;
   const uint32_t total = ((g.nx + 1u) / 2u) * g.ny * g.nz;
   const dim3 grid((total + 255u) / 256u), block(256);
   if (pair_aligned(uh))
@@ -2990,9 +3073,9 @@ static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], co
     hipLaunchKernelGGL((tensor_prolong_add_kernel<T, false>), grid, block, 0, st, g, uH, uh);
   return hipGetLastError();
 }
-hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], const double* uH, double* uh,
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, const double* uH, double* uh,
                                      hipStream_t st) {
-  return launch_tensor_prolong_add_t<double>(dim, dims, uH, uh, st);
+  return launch_tensor_prolong_add_t<double>(dim, dims, mask, uH, uh, st);
 }
 
 // First Jacobi sweep from a zero guess (coarse levels on the way down,
@@ -5121,6 +5204,9 @@ hipError_t launch_galerkin_rap(bool fill, int64_t n_h, int64_t n_H, const int32_
 // streamed from memory once and the only other traffic is the output.  A box of more than SLOTS
 // columns (9 of 16 in 2-D, 27 of 32 in 3-D for the 5- / 9- and 7- / 27-point rows) raises *overflow;
 // nothing is truncated, the caller takes the host product.
+//
+// Semi-coarsening (g.cx / cy / cz): on an axis that is not coarsened P1 is the identity -- row k has
+// the one column k with weight 1, and R's row I the one fine row I instead of three.
 __device__ __forceinline__ void tg_divmod(uint32_t k, uint32_t n, double inv_n, uint32_t* q, uint32_t* r) {
   uint32_t qq = (uint32_t)((double)k * inv_n);  // within 1 of floor(k / n) for k < 2^31
   int32_t rr = (int32_t)(k - qq * n);
@@ -5130,8 +5216,11 @@ __device__ __forceinline__ void tg_divmod(uint32_t k, uint32_t n, double inv_n, 
   *r = (uint32_t)rr;
 }
 // coarse columns [l, h] of row k of P1(m): k odd: (k - 1) / 2; k even: k / 2 - 1 and k / 2, inside [0, m)
-__device__ __forceinline__ void tg_cols(uint32_t k, uint32_t m, int32_t* l, int32_t* h) {
-  if (k & 1u) {
+// (c = 0, the axis is not coarsened: column k alone)
+__device__ __forceinline__ void tg_cols(uint32_t k, uint32_t m, uint32_t c, int32_t* l, int32_t* h) {
+  if (!c) {
+    *l = *h = (int32_t)k;
+  } else if (k & 1u) {
     *l = *h = (int32_t)((k - 1u) >> 1);
   } else {
     const int32_t c = (int32_t)(k >> 1);
@@ -5140,7 +5229,8 @@ __device__ __forceinline__ void tg_cols(uint32_t k, uint32_t m, int32_t* l, int3
   }
 }
 // P1(k, J) for a column J inside [0, m)
-__device__ __forceinline__ double tg_weight(uint32_t k, int32_t J) {
+__device__ __forceinline__ double tg_weight(uint32_t k, int32_t J, uint32_t c) {
+  if (!c) return (int32_t)k == J ? 1.0 : 0.0;
   const int32_t t = (int32_t)k - 2 * J;
   return t == 1 ? 1.0 : ((t == 0 || t == 2) ? 0.5 : 0.0);
 }
@@ -5157,11 +5247,13 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
   const bool live = row0 < nH;
   const uint32_t row = live ? row0 : nH - 1u;  // the tail lanes repeat the last row and write nothing
   const uint32_t I = row % g.mx, qr = row / g.mx, J = qr % g.my, K = qr / g.my;
-  const uint32_t nt = g.cz ? 27u : 9u;  // fine rows of R's row, (z, y, x) ascending
+  const uint32_t rx = g.cx ? 3u : 1u, ry = g.cy ? 3u : 1u, rz = g.cz ? 3u : 1u;
+  const uint32_t nt = rx * ry * rz;  // fine rows of R's row, (z, y, x) ascending
   // the box of coarse columns
   int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
   if (s < nt) {
-    const uint32_t ix = 2u * I + s % 3u, iy = 2u * J + (s / 3u) % 3u, iz = g.cz ? 2u * K + s / 9u : 0u;
+    const uint32_t ix = g.cx ? 2u * I + s % rx : I, iy = g.cy ? 2u * J + (s / rx) % ry : J,
+                   iz = g.cz ? 2u * K + s / (rx * ry) : K;
     if (ix < g.nx && iy < g.ny && iz < g.nz) {
       const uint32_t i = (iz * g.ny + iy) * g.nx + ix;
       for (int32_t p = arp[i], e = arp[i + 1]; p < e; ++p) {
@@ -5169,10 +5261,9 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
         tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
         tg_divmod(q, g.ny, inv_ny, &kz, &ky);
         int32_t l[3], h[3];
-        tg_cols(kx, g.mx, &l[0], &h[0]);
-        tg_cols(ky, g.my, &l[1], &h[1]);
-        if (g.cz) tg_cols(kz, g.mz, &l[2], &h[2]);
-        else l[2] = h[2] = 0;
+        tg_cols(kx, g.mx, g.cx, &l[0], &h[0]);
+        tg_cols(ky, g.my, g.cy, &l[1], &h[1]);
+        tg_cols(kz, g.mz, g.cz, &l[2], &h[2]);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
           lo[a] = l[a] < lo[a] ? l[a] : lo[a];
@@ -5210,17 +5301,19 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
     Jz = lo[2] + (int32_t)(s / (bx * by));
     for (uint32_t tz = 0; tz < 3; ++tz) {
       if (!g.cz && tz > 0) break;
-      const uint32_t iz = g.cz ? 2u * K + tz : 0u;
+      const uint32_t iz = g.cz ? 2u * K + tz : K;
       if (iz >= g.nz) break;
-      const double rz = g.cz ? (tz == 1 ? 1.0 : 0.5) : 1.0;
+      const double wz = g.cz ? (tz == 1 ? 1.0 : 0.5) : 1.0;
       for (uint32_t ty = 0; ty < 3; ++ty) {
-        const uint32_t iy = 2u * J + ty;
+        if (!g.cy && ty > 0) break;
+        const uint32_t iy = g.cy ? 2u * J + ty : J;
         if (iy >= g.ny) break;
-        const double rzy = rz * (ty == 1 ? 1.0 : 0.5);
+        const double rzy = wz * (g.cy ? (ty == 1 ? 1.0 : 0.5) : 1.0);
         for (uint32_t tx = 0; tx < 3; ++tx) {
-          const uint32_t ix = 2u * I + tx;
+          if (!g.cx && tx > 0) break;
+          const uint32_t ix = g.cx ? 2u * I + tx : I;
           if (ix >= g.nx) break;
-          const double r = rzy * (tx == 1 ? 1.0 : 0.5);  // R(I, i)
+          const double r = rzy * (g.cx ? (tx == 1 ? 1.0 : 0.5) : 1.0);  // R(I, i)
           const uint32_t i = (iz * g.ny + iy) * g.nx + ix;
           bool hit_i = false;
           double ap = 0.0;  // (A P)(i, J)
@@ -5228,8 +5321,7 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
             uint32_t kx, ky, kz, q;
             tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
             tg_divmod(q, g.ny, inv_ny, &kz, &ky);
-            double w = tg_weight(kx, Jx) * tg_weight(ky, Jy);
-            w = g.cz ? w * tg_weight(kz, Jz) : ((int32_t)kz == Jz ? w : 0.0);
+            const double w = tg_weight(kx, Jx, g.cx) * tg_weight(ky, Jy, g.cy) * tg_weight(kz, Jz, g.cz);
             if (w != 0.0) {
               if (FILL) {
                 const double t = aval[p] * w;
@@ -5260,12 +5352,12 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
     oval[at] = acc;
   }
 }
-hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], const int32_t* arp,
+hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, const int32_t* arp,
                                   const int32_t* acol, const double* aval, int32_t* cnt,
                                   const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
                                   hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, &g)) return hipErrorInvalidValue;
   const uint32_t nH = g.mx * g.my * g.mz;
   const double inv_nx = 1.0 / (double)g.nx, inv_ny = 1.0 / (double)g.ny;
 #define TG_LAUNCH(SLOTS, FILL)                                                                        \
@@ -6830,13 +6922,13 @@ hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, 
 hipError_t launch_linear_prolong_add_f32(int64_t n_h, int64_t n_H, const float* uH, float* uh, hipStream_t st) {
   return launch_linear_prolong_add_t<float>(n_h, n_H, uH, uh, st);
 }
-hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], const float* r, float* fH, float* uH_zero,
+hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st) {
-  return launch_tensor_restrict_t<float>(dim, dims, r, fH, uH_zero, st);
+  return launch_tensor_restrict_t<float>(dim, dims, mask, r, fH, uH_zero, st);
 }
-hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], const float* uH, float* uh,
+hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, const float* uH, float* uh,
                                          hipStream_t st) {
-  return launch_tensor_prolong_add_t<float>(dim, dims, uH, uh, st);
+  return launch_tensor_prolong_add_t<float>(dim, dims, mask, uH, uh, st);
 }
 
 

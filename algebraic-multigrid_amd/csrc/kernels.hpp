@@ -328,11 +328,13 @@ hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
 // tensor_P) without a matrix.  dims = fine grid (x fastest; dim = 2: dims[2] == 1 is not coarsened);
 // every coarsened axis must have at least 2 points and the fine level fewer than 2^31 - 2 rows, else
 // hipErrorInvalidValue.  Bit-identical to the CSR SpMV with R / P (same terms, same order).
+// mask: the coarsened axes (bit 0 = x, 1 = y, 2 = z; host_setup.hpp: tensor_P with a mask) -- 3 / 7
+// for full coarsening; an axis outside the mask keeps its length (identity) and may have 1 point.
 // f_H = R r, uH_zero (may be null) zero-filled in the same pass
-hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], const double* r, double* fH,
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, const double* r, double* fH,
                                   double* uH_zero, hipStream_t st);
 // u_h = u_h + P u_H
-hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], const double* uH, double* uh,
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, const double* uH, double* uh,
                                      hipStream_t st);
 hipError_t launch_add_inplace(int64_t n, const double* x, double* y, hipStream_t st);
 // *out = sum x_i (square=0) or sum x_i^2 (square=1); scratch: 1024 doubles
@@ -461,10 +463,16 @@ hipError_t launch_galerkin_rap(bool fill, int64_t n_h, int64_t n_H, const int32_
 // bits as galerkin_csr on the Kronecker operators, structural zeros included.  *overflow (zeroed
 // by the caller) is set when a coarse row reaches more coarse columns than a lane group holds
 // (16 in 2-D, 32 in 3-D): the result is then unusable and the caller takes the host product.
-hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], const int32_t* arp,
+// mask: the coarsened axes, as for launch_tensor_restrict.
+hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, const int32_t* arp,
                                   const int32_t* acol, const double* aval, int32_t* cnt,
                                   const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
                                   hipStream_t st);
+// K-AxisStrength (setup): out[a] = bits of max |a_ij| over the entries of CSR(A) on the grid `dims`
+// whose column is the row's neighbour along axis a alone (host_setup.hpp: tensor_axis_strength,
+// same bits); 0.0 when there is none.  out: 3 words, initialised by the launch.
+hipError_t launch_axis_strength(int64_t n, int dim, const int64_t dims[3], const int32_t* rowptr, const int32_t* col,
+                                const double* val, uint64_t* out, hipStream_t st);
 
 // K-Setup: Grid generators and the dictionary encoder on the device (kernels.hip)
 hipError_t launch_laplacian_count(int dim, int64_t n, int64_t n_last, int64_t N, int32_t* cnt, hipStream_t st);
@@ -552,9 +560,9 @@ hipError_t launch_to_f64(int64_t n, const float* src, double* dst, hipStream_t s
 hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st);
 hipError_t launch_linear_prolong_add_f32(int64_t n_h, int64_t n_H, const float* uH, float* uh, hipStream_t st);
-hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], const float* r, float* fH, float* uH_zero,
+hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st);
-hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], const float* uH, float* uh,
+hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, const float* uH, float* uh,
                                          hipStream_t st);
 
 }  // namespace amg_hip

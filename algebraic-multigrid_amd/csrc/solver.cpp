@@ -181,11 +181,11 @@ hipError_t device_galerkin(const DevCsr& A, int64_t n_H, DevCsr* AH, Sparse* hos
   return hipSuccess;
 }
 
-// Setup on the device (K-TensorGalerkin): AH = R (A P) for the full-coarsening pair of the grid
-// `dims` from CSR(A) on the device.  *ok = false: a coarse row reaches more columns than the
+// Setup on the device (K-TensorGalerkin): AH = R (A P) for the tensor-product pair of the grid
+// `dims` (mask: the coarsened axes) from CSR(A) on the device.  *ok = false: a coarse row reaches more columns than the
 // kernel's lane group holds; hipErrorInvalidValue: the product is beyond int32 indexing.  Either
 // way the caller takes the host path.
-hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], int64_t n_H, DevCsr* AH,
+hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], uint32_t mask, int64_t n_H, DevCsr* AH,
                                   bool* ok) {
   *ok = false;
   hipError_t e;
@@ -195,7 +195,7 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if ((e = total.alloc(sizeof(int64_t))) != hipSuccess) return e;
   if ((e = ovf.alloc(sizeof(int32_t))) != hipSuccess) return e;
   if ((e = hipMemset(ovf.p, 0, sizeof(int32_t))) != hipSuccess) return e;
-  if ((e = launch_tensor_galerkin(false, dim, dims, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
+  if ((e = launch_tensor_galerkin(false, dim, dims, mask, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
                                   nullptr, nullptr, ovf.as<int32_t>(), nullptr)) != hipSuccess)
     return e;
   int32_t over = 0;
@@ -210,7 +210,7 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if (nnz >= ((int64_t)1 << 31) - 1) return hipErrorInvalidValue;
   if ((e = AH->idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
   if ((e = AH->val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
-  if ((e = launch_tensor_galerkin(true, dim, dims, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
+  if ((e = launch_tensor_galerkin(true, dim, dims, mask, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
                                   AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr)) != hipSuccess)
     return e;
   AH->n_rows = AH->n_cols = n_H;
@@ -1177,7 +1177,7 @@ struct Level {
   int64_t n_coarse = 0;
   const Sparse& P() const {
     if (lazy_linear && P_csc.ptr.empty()) P_csc = linear_P(n, n_coarse);  // interpolator.hpp:106-129
-    if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims);
+    if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims, tmask);
     return P_csc;
   }
   const Sparse& R() const {
@@ -1189,9 +1189,12 @@ struct Level {
   // solver, the coarsest included) and whether the level's transfers are the tensor-product pair.
   // tensor_stencil: they run matrix-free (opt.stencil_transfers), and the host copies of P / R are
   // only kept while somebody needs them (the Galerkin product, a getter, the block CSR copies)
+  // tmask: the axes the level's transfers coarsen (bit 0 = x, 1 = y, 2 = z): all of them, or the
+  // level's mask in a semi-coarsening hierarchy (amg_hip_create_tensor_semi)
   int tdim = 0;
   int64_t dims[3] = {0, 0, 0};
   bool tensor = false, tensor_stencil = false;
+  uint32_t tmask = 0;
   DevCsr P_rows, R_rows;   // CSR(P), CSR(R)
   // exact lexicographic schedules
   std::unique_ptr<LexOnDev> lex_fwd, lex_bwd;
@@ -2068,7 +2071,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
                                        zero_known ? nullptr : C.u.as<double>(), st));
         s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
       } else if (L.tensor_stencil) {                               // the same two steps, full coarsening
-        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.r.as<double>(), C.f.as<double>(),
+        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.r.as<double>(), C.f.as<double>(),
                                        zero_known ? nullptr : C.u.as<double>(), st));
         s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
       } else {
@@ -2175,7 +2178,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
       s->acct(8.0 * C.n + 16.0 * L.n);
     } else if (L.tensor_stencil) {
-      HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, C.u.as<double>(), L.u.as<double>(), st));
+      HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, C.u.as<double>(), L.u.as<double>(), st));
       s->acct(8.0 * C.n + 16.0 * L.n);
     } else {
       const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
@@ -2287,7 +2290,8 @@ void compute_bytes(amg_hip_solver* s) {
         total += 16 * nh + 8 * nH;
         continue;
       }
-      const double pnnz = L.tensor ? (L.tdim == 3 ? 27.0 : 9.0) : 3.0;  // entries per column of P
+      double pnnz = 3.0;  // entries per column of P
+      if (L.tensor) pnnz = ((L.tmask & 1u) ? 3.0 : 1.0) * ((L.tmask & 2u) ? 3.0 : 1.0) * ((L.tmask & 4u) ? 3.0 : 1.0);
       total += 12.0 * pnnz * nH + 4 * nH + 8 * nh + 8 * nH;   // restrict (CSR R)
       total += 12.0 * pnnz * nH + 4 * nh + 8 * nH + 16 * nh;  // prolong + add (CSR P)
     }
@@ -2298,6 +2302,27 @@ void compute_bytes(amg_hip_solver* s) {
 // ---- setup --------------------------------------------------------------------
 hipError_t device_dict_encode(const DevCsr& A, bool prune, int maxlen, DevMat* D, bool* ok);
 
+// Semi-coarsening (amg_hip_create_tensor_semi): masks = the n_levels - 1 explicit axis masks, or
+// null for the automatic rule (host_setup.hpp: tensor_auto_mask) with theta and min_coarse.
+struct SemiRule {
+  const int32_t* masks = nullptr;
+  double theta = 0.5;
+  int64_t min_coarse = 1;
+};
+// "" or what is wrong with the axis mask of level l on the grid d
+std::string semi_mask_error(int l, int dim, const int64_t d[3], int64_t mask) {
+  const std::string at = "level " + std::to_string(l) + ": axis mask " + std::to_string(mask);
+  if (mask == 0) return at + " coarsens no axis";
+  if (mask < 0 || mask > 7) return at + " has bits other than 1 (x), 2 (y) and 4 (z)";
+  if (dim == 2 && (mask & 4)) return at + " coarsens z, and `dim` is 2";
+  for (int a = 0; a < 3; ++a)
+    if (((mask >> a) & 1) && d[a] < 2)
+      return at + " coarsens axis " + std::string(1, "xyz"[a]) + ", which has " + std::to_string(d[a]) +
+             " point on this level (the grid is " + std::to_string(d[0]) + " x " + std::to_string(d[1]) + " x " +
+             std::to_string(d[2]) + ")";
+  return "";
+}
+
 amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* rowind,
                             const double* val, const double* b, int32_t n_levels,
                             const int32_t* const* Pc, const int32_t* const* Pr,
@@ -2305,7 +2330,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
                             const int32_t* const* Rr, const double* const* Rv,
                             const amg_hip_options* opts, amg_hip_solver** out,
                             double rs_theta = -1.0, int64_t rs_min_coarse = 0, int tensor_dim = 0,
-                            const int64_t* tensor_dims = nullptr) {
+                            const int64_t* tensor_dims = nullptr, const SemiRule* semi = nullptr) {
   if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
   *out = nullptr;
   if (!colptr || !rowind || !val || !b) return fail(AMG_HIP_EINVAL, "null input array");
@@ -2400,6 +2425,25 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   timer.lap(T_IN);
   for (int l = 0; l < n_levels; ++l) {
     Level& L = s->lv[l];
+    if (tensor_dim && l + 1 < n_levels) {  // the axes this level coarsens
+      L.tmask = tensor_full_mask(tensor_dim);
+      if (semi && semi->masks) {
+        L.tmask = (uint32_t)semi->masks[l];
+      } else if (semi) {  // the hierarchy ends at a small level or when no axis is eligible
+        bool last = L.n <= semi->min_coarse;
+        if (!last) {
+          double w[3];
+          tensor_axis_strength(A_r, tensor_dim, L.dims, w);
+          L.tmask = tensor_auto_mask(tensor_dim, L.dims, w, semi->theta);
+          last = L.tmask == 0;
+        }
+        if (last) {
+          L.tmask = 0;
+          n_levels = l + 1;
+          s->lv.resize((size_t)n_levels);
+        }
+      }
+    }
     L.symmetric = same_arrays(A_r, L.A_csc);
     L.nnz_struct = L.A_csc.nnz();
     if (cheb) {  // bound of D^-1 A from the rows of A_l (CSR(A_l) = A_r)
@@ -2601,19 +2645,23 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       L.R_csc = transpose(L.P_csc);
       L.linear = false;
     } else if (tensor_dim) {
-      // full coarsening: every axis m -> floor(m / 2), possible while every coarsened axis has 2 points
-      if (L.dims[0] < 2 || L.dims[1] < 2 || (tensor_dim == 3 && L.dims[2] < 2))
+      // every coarsened axis m -> floor(m / 2), possible while it has 2 points
+      if (semi) {
+        const std::string e = semi_mask_error(l, tensor_dim, L.dims, L.tmask);
+        if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+      } else if (L.dims[0] < 2 || L.dims[1] < 2 || (tensor_dim == 3 && L.dims[2] < 2)) {
         return fail(AMG_HIP_EINVAL, tensor_level_error(l, L.dims));
+      }
       Level& C = s->lv[l + 1];
       C.tdim = tensor_dim;
-      tensor_coarse_dims(tensor_dim, L.dims, C.dims);
+      tensor_coarse_dims(tensor_dim, L.dims, L.tmask, C.dims);
       n_H = C.dims[0] * C.dims[1] * C.dims[2];
       L.tensor = true;
       L.n_coarse = n_H;
       // the matrix-free kernels index lanes with 32 bits (kernels.hip: tensor_grid)
       L.tensor_stencil = s->opt.stencil_transfers && L.n < ((int64_t)1 << 31) - 4;
       if (!L.tensor_stencil) {
-        L.P_csc = tensor_P(tensor_dim, L.dims);
+        L.P_csc = tensor_P(tensor_dim, L.dims, L.tmask);
         L.R_csc = transpose(L.P_csc);
       }
     } else if (n_H < 1) {
@@ -3005,7 +3053,8 @@ amg_hip_status device_setup_begin(const amg_hip_options& o, std::unique_ptr<amg_
 // The level loop of the device set-ups (defined below the model problem's front end).
 amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const int64_t dims0[3], bool tensor,
                                  bool user, int32_t n_levels, SetupLap& lap,
-                                 const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported);
+                                 const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported,
+                                 const SemiRule* semi = nullptr);
 
 // Front end of the model problem: AMG::Multigrid's constructor (multigrid.hpp:151-244) for A = Grid::laplacian(n), b =
 // Grid::rhs(n) without host matrices: generator, Galerkin chain, dictionary encoder, diagonal
@@ -3105,9 +3154,12 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
 // opt.layout is honoured, levels that do not take the dictionary are packed by K-SellPack with
 // upload_mat's rule, and levels that are not bitwise symmetric are transposed by K-Transpose, so
 // that no level crosses to the host.  The model problem's front ends keep the launches they had.
+// semi (amg_hip_create_tensor_semi_dev): the levels coarsen the axes of its masks, or those the
+// automatic rule picks from K-AxisStrength's maxima; n_levels is then an upper bound.
 amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const int64_t dims0[3], bool tensor,
                                  bool user, int32_t n_levels, SetupLap& lap,
-                                 const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported) {
+                                 const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported,
+                                 const SemiRule* semi) {
   *unsupported = true;
   const amg_hip_options& o = s->opt;
   const bool lex = o.smoother <= AMG_HIP_SM_SOR;
@@ -3117,8 +3169,9 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
   const bool timing = lap.on;
   const bool try_dict = o.layout == AMG_HIP_LAYOUT_AUTO || o.layout == AMG_HIP_LAYOUT_DICT;
   s->lv.resize(n_levels);
-  DevMem stats, gbound;
+  DevMem stats, gbound, axis_w;
   HIP_TRY(stats.alloc(sizeof(int32_t) * 2));
+  if (semi && !semi->masks) HIP_TRY(axis_w.alloc(sizeof(uint64_t) * 3));
   if (cheb) HIP_TRY(gbound.alloc(sizeof(uint64_t) * 2));
   const bool prune = !o.keep_structural_zeros;
   int64_t tdims[3] = {dims0[0], dims0[1], dims0[2]};  // full coarsening: the grid of the current level
@@ -3142,6 +3195,26 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
     if (tensor) {
       L.tdim = dim;
       for (int a = 0; a < 3; ++a) L.dims[a] = tdims[a];
+    }
+    if (tensor && l + 1 < n_levels) {  // the axes this level coarsens (build_solver's rule)
+      L.tmask = tensor_full_mask(dim);
+      if (semi && semi->masks) {
+        L.tmask = (uint32_t)semi->masks[l];
+      } else if (semi) {
+        bool last = L.n <= semi->min_coarse;
+        if (!last) {
+          HIP_TRY(launch_axis_strength(L.n, dim, L.dims, cur.rowptr(), cur.col(), cur.v(), axis_w.as<uint64_t>(), nullptr));
+          double w[3];
+          HIP_TRY(hipMemcpy(w, axis_w.p, sizeof(w), hipMemcpyDeviceToHost));
+          L.tmask = tensor_auto_mask(dim, L.dims, w, semi->theta);
+          last = L.tmask == 0;
+        }
+        if (last) {
+          L.tmask = 0;
+          n_levels = l + 1;
+          s->lv.resize((size_t)n_levels);
+        }
+      }
     }
     if (cheb) {  // Gershgorin bound of D^-1 A on the device CSR (K-Setup: gershgorin_kernel)
       HIP_TRY(launch_gershgorin(L.n, cur.rowptr(), cur.col(), cur.v(), gbound.as<uint64_t>(), nullptr));
@@ -3274,15 +3347,19 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
       break;
     }
     DevCsr next;
-    if (tensor) {  // every axis m -> floor(m / 2), matrix-free transfers, K-TensorGalerkin
-      if (L.dims[0] < 2 || L.dims[1] < 2 || (dim == 3 && L.dims[2] < 2))
+    if (tensor) {  // every coarsened axis m -> floor(m / 2), matrix-free transfers, K-TensorGalerkin
+      if (semi) {
+        const std::string e = semi_mask_error(l, dim, L.dims, L.tmask);
+        if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+      } else if (L.dims[0] < 2 || L.dims[1] < 2 || (dim == 3 && L.dims[2] < 2)) {
         return fail(AMG_HIP_EINVAL, tensor_level_error(l, L.dims));
-      tensor_coarse_dims(dim, L.dims, tdims);
+      }
+      tensor_coarse_dims(dim, L.dims, L.tmask, tdims);
       L.tensor = true;
       L.tensor_stencil = true;  // o.stencil_transfers is set and N < 2^28
       L.n_coarse = tdims[0] * tdims[1] * tdims[2];
       bool ok_g = false;
-      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.n_coarse, &next, &ok_g);
+      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.tmask, L.n_coarse, &next, &ok_g);
       if (ge == hipErrorInvalidValue || (ge == hipSuccess && !ok_g)) {
         if (timing) std::fprintf(stderr, "amg_hip device setup: Galerkin product of level %d exceeds %s -> host path\n", l,
                                  ge == hipSuccess ? "the kernel's columns per coarse row" : "int32 indexing");
@@ -3813,7 +3890,7 @@ amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
       F32_DO(launch_linear_restrict_f32(L.n, C.n, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
       s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
     } else if (L.tensor_stencil) {
-      F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
+      F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
       s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
     } else {
       F32_DO(hipMemsetAsync(QC.u.p, 0, sizeof(float) * (size_t)C.n, st));
@@ -3841,7 +3918,7 @@ amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
       F32_DO(launch_linear_prolong_add_f32(L.n, C.n, QC.u.as<float>(), Q.u.as<float>(), st));
       s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
     } else if (L.tensor_stencil) {
-      F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, QC.u.as<float>(), Q.u.as<float>(), st));
+      F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, QC.u.as<float>(), Q.u.as<float>(), st));
       s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
     } else {
       const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
@@ -4002,6 +4079,79 @@ amg_hip_status amg_hip_create_tensor(int64_t n, const int32_t* colptr, const int
                       nullptr, opts, out, -1.0, 0, dim, dims);
 }
 
+// The argument checks of the semi-coarsening constructors, before any device call: the explicit
+// masks level by level on the grids they produce, or the automatic rule's parameters.
+static amg_hip_status semi_args(const std::string& who, int32_t dim, const int64_t* dims, int32_t n_levels,
+                                const int32_t* axis_masks, double theta, int64_t min_coarse, SemiRule* rule) {
+  if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
+  rule->masks = axis_masks;
+  if (axis_masks) {
+    int64_t d[3] = {dims[0], dims[1], dims[2]};
+    for (int l = 0; l + 1 < n_levels; ++l) {
+      const std::string e = semi_mask_error(l, dim, d, axis_masks[l]);
+      if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
+      int64_t c[3];
+      tensor_coarse_dims(dim, d, (uint32_t)axis_masks[l], c);
+      for (int a = 0; a < 3; ++a) d[a] = c[a];
+    }
+    return AMG_HIP_OK;
+  }
+  if (!(theta > 0.0 && theta <= 1.0)) return fail(AMG_HIP_EINVAL, who + "`theta` must be in (0, 1]");
+  if (min_coarse < 1) return fail(AMG_HIP_EINVAL, who + "`min_coarse` must be at least 1");
+  rule->theta = theta;
+  rule->min_coarse = min_coarse;
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                          const double* val, const double* b, int32_t dim, const int64_t* dims,
+                                          int32_t n_levels, const int32_t* axis_masks, double theta,
+                                          int64_t min_coarse, const amg_hip_options* opts, amg_hip_solver** out) {
+  static const std::string who = "amg_hip_create_tensor_semi: ";
+  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
+  *out = nullptr;
+  const std::string e = tensor_dims_error(dim, dims);
+  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
+  if (n != dims[0] * dims[1] * dims[2])
+    return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
+                                    " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
+                                    " grid of `dims`");
+  if (opts && opts->window)
+    return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a semi-coarsening "
+                                            "hierarchy is not sharded");
+  SemiRule rule;
+  const amg_hip_status r = semi_args(who, dim, dims, n_levels, axis_masks, theta, min_coarse, &rule);
+  if (r != AMG_HIP_OK) return r;
+  return build_solver(n, colptr, rowind, val, b, n_levels, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      nullptr, opts, out, -1.0, 0, dim, dims, &rule);
+}
+
+amg_hip_status amg_hip_get_level_axes(const amg_hip_solver* s, int32_t level, int32_t* axis_mask) {
+  if (!s || !axis_mask) return fail(AMG_HIP_EINVAL, "null argument");
+  if (level < 0 || level + 1 >= (int)s->lv.size())
+    return fail(AMG_HIP_EINVAL, "level out of range (the coarsest level has no transfers)");
+  const Level& L = s->lv[level];
+  if (!L.tdim || !L.tensor)
+    return fail(AMG_HIP_EINVAL, "amg_hip_get_level_axes: the solver was not made by a tensor constructor");
+  *axis_mask = (int32_t)L.tmask;
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_tensor_axis_strength(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                            const double* val, int32_t dim, const int64_t* dims, double* w) {
+  static const std::string who = "amg_hip_tensor_axis_strength: ";
+  if (!colptr || !rowind || !val || !w) return fail(AMG_HIP_EINVAL, "null argument");
+  const std::string e = tensor_dims_error(dim, dims);
+  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
+  if (n != dims[0] * dims[1] * dims[2])
+    return fail(AMG_HIP_EINVAL, who + "`n` is not the number of points of `dims`");
+  const Sparse A = from_raw(n, n, colptr, rowind, val);
+  const std::string v = validate(A, "A");
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
+  tensor_axis_strength(A, dim, dims, w);
+  return AMG_HIP_OK;
+}
+
 amg_hip_status amg_hip_get_level_dims(const amg_hip_solver* s, int32_t level, int64_t* dims) {
   if (!s || !dims) return fail(AMG_HIP_EINVAL, "null argument");
   if (level < 0 || level >= (int)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
@@ -4079,7 +4229,7 @@ amg_hip_status amg_hip_create_poisson_tensor(int32_t dim, int64_t n, int32_t n_l
 static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr, const int32_t* col,
                                                const double* val, const double* b, int dim, const int64_t* dims,
                                                int32_t n_levels, const amg_hip_options& o, amg_hip_solver** out,
-                                               bool* unsupported) {
+                                               bool* unsupported, const SemiRule* semi, const std::string& who) {
   *unsupported = true;
   std::unique_ptr<amg_hip_solver> s;
   {
@@ -4096,7 +4246,7 @@ static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr,
   HIP_TRY(hipMemcpyAsync(&nnz32, cur.ptr.as<int32_t>() + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (nnz32 < 0 || nnz32 == INT32_MAX)
-    return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor_dev: `rowptr[n]` = " + std::to_string(nnz32) +
+    return fail(AMG_HIP_EINVAL, who + "`rowptr[n]` = " + std::to_string(nnz32) +
                                     " is not a number of entries (row " + std::to_string(n - 1) + ")");
   const int64_t nnz = nnz32;
   HIP_TRY(cur.idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
@@ -4113,7 +4263,7 @@ static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr,
   HIP_TRY(hipMemcpyAsync(rhs.p, b, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (first_bad != none)
-    return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor_dev: row " + std::to_string(first_bad) +
+    return fail(AMG_HIP_EINVAL, who + "row " + std::to_string(first_bad) +
                                     " of the CSR arrays is malformed (`rowptr` must start at 0 and never decrease; "
                                     "the columns of a row must lie in [0, n) and ascend strictly)");
   cur.n_rows = cur.n_cols = n;
@@ -4129,17 +4279,19 @@ static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr,
     HIP_TRY(hipMemcpy(L0.r.p, rhs.p, sizeof(double) * n, hipMemcpyDeviceToDevice));  // b - A*0
     return AMG_HIP_OK;
   };
-  const amg_hip_status r = device_level_loop(s.get(), cur, dim, dims, true, true, n_levels, lap, put_rhs, unsupported);
+  const amg_hip_status r = device_level_loop(s.get(), cur, dim, dims, true, true, n_levels, lap, put_rhs, unsupported,
+                                             semi);
   if (r != AMG_HIP_OK || *unsupported) return r;
   *out = s.release();
   return AMG_HIP_OK;
 }
 
-amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
-                                         const double* val_dev, const double* b_dev, int32_t dim,
-                                         const int64_t* dims, int32_t n_levels, const amg_hip_options* opts,
-                                         amg_hip_solver** out) {
-  static const std::string who = "amg_hip_create_tensor_dev: ";
+// amg_hip_create_tensor_dev and, with `semi_on`, amg_hip_create_tensor_semi_dev
+static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, int64_t n, const int32_t* rowptr_dev,
+                                        const int32_t* col_dev, const double* val_dev, const double* b_dev,
+                                        int32_t dim, const int64_t* dims, int32_t n_levels,
+                                        const int32_t* axis_masks, double theta, int64_t min_coarse,
+                                        const amg_hip_options* opts, amg_hip_solver** out) {
   if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
   *out = nullptr;
   if (!rowptr_dev || !col_dev || !val_dev || !b_dev) return fail(AMG_HIP_EINVAL, "null input array");
@@ -4153,10 +4305,15 @@ amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, c
   if (opts) o = *opts;
   else amg_hip_default_options(&o);
   if (o.window)
-    return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a full-coarsening "
-                                            "hierarchy is not sharded");
+    return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a " +
+                                          (semi_on ? "semi" : "full") + "-coarsening hierarchy is not sharded");
   if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
-  {  // the levels the rule allows
+  SemiRule rule;
+  const SemiRule* semi = semi_on ? &rule : nullptr;
+  if (semi_on) {
+    const amg_hip_status sr = semi_args(who, dim, dims, n_levels, axis_masks, theta, min_coarse, &rule);
+    if (sr != AMG_HIP_OK) return sr;
+  } else {  // the levels the rule allows
     int64_t d[3] = {dims[0], dims[1], dims[2]};
     for (int l = 0; l + 1 < n_levels; ++l) {
       if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
@@ -4182,7 +4339,7 @@ amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, c
     return fail(AMG_HIP_EINVAL, "`omega` must be in [0, 2] but got omega=" + std::to_string(o.omega) + "\n");
   bool unsupported = true;
   amg_hip_status r = build_tensor_user_device(n, rowptr_dev, col_dev, val_dev, b_dev, dim, dims, n_levels, o, out,
-                                              &unsupported);
+                                              &unsupported, semi, who);
   if (r != AMG_HIP_OK || !unsupported) return r;
   // options that need host structures (or a product the kernels refused): the checked arrays are
   // downloaded, transposed on the host and given to the host constructor
@@ -4215,7 +4372,27 @@ amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, c
     if (o.device >= 0) HIP_TRY(hipSetDevice(dev_before));
   }
   const Sparse A = transpose(H);  // CSC(A)
+  if (semi_on)
+    return amg_hip_create_tensor_semi(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims, n_levels,
+                                      axis_masks, theta, min_coarse, &o, out);
   return amg_hip_create_tensor(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims, n_levels, &o, out);
+}
+
+amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                         const double* val_dev, const double* b_dev, int32_t dim,
+                                         const int64_t* dims, int32_t n_levels, const amg_hip_options* opts,
+                                         amg_hip_solver** out) {
+  return create_tensor_dev("amg_hip_create_tensor_dev: ", false, n, rowptr_dev, col_dev, val_dev, b_dev, dim, dims,
+                           n_levels, nullptr, 0.0, 0, opts, out);
+}
+
+amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                              const double* val_dev, const double* b_dev, int32_t dim,
+                                              const int64_t* dims, int32_t n_levels, const int32_t* axis_masks,
+                                              double theta, int64_t min_coarse, const amg_hip_options* opts,
+                                              amg_hip_solver** out) {
+  return create_tensor_dev("amg_hip_create_tensor_semi_dev: ", true, n, rowptr_dev, col_dev, val_dev, b_dev, dim,
+                           dims, n_levels, axis_masks, theta, min_coarse, opts, out);
 }
 
 amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on) {
@@ -4554,7 +4731,7 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       if (L.linear && s->opt.stencil_transfers) {
         HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
       } else if (L.tensor_stencil) {
-        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
+        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
       } else {
         HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st));
         const DevCsr& R = L.R_rows;
@@ -4569,7 +4746,7 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       if (L.linear && s->opt.stencil_transfers) {
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
       } else if (L.tensor_stencil) {
-        HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, C.u.as<double>(), L.u.as<double>(), st));
+        HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, C.u.as<double>(), L.u.as<double>(), st));
       } else {
         const DevCsr& P = L.P_rows;
         HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz, P.rowptr(),
@@ -5203,49 +5380,74 @@ amg_hip_status amg_hip_linear_restrict(int64_t n_h, int64_t n_H, const double* r
   return AMG_HIP_OK;
 }
 
-// the fine grid of a stand-alone tensor transfer: every coarsened axis needs 2 points
-static amg_hip_status tensor_transfer_args(const char* who, int32_t dim, const int64_t* dims, int64_t* n_h,
-                                           int64_t* n_H) {
+// the fine grid of a stand-alone tensor transfer: every coarsened axis needs 2 points.  mask < 0:
+// full coarsening (the entry points without a mask)
+static amg_hip_status tensor_transfer_args(const char* who, int32_t dim, const int64_t* dims, int64_t mask_in,
+                                           uint32_t* mask, int64_t* n_h, int64_t* n_H) {
   std::string e = tensor_dims_error(dim, dims);
-  if (e.empty() && (dims[0] < 2 || dims[1] < 2 || (dim == 3 && dims[2] < 2)))
-    e = "an axis of fewer than 2 points cannot be coarsened";
+  if (e.empty() && mask_in < 0) {
+    if (dims[0] < 2 || dims[1] < 2 || (dim == 3 && dims[2] < 2)) e = "an axis of fewer than 2 points cannot be coarsened";
+    mask_in = tensor_full_mask(dim);
+  } else if (e.empty()) {
+    e = semi_mask_error(0, dim, dims, mask_in);
+  }
   if (!e.empty()) return fail(AMG_HIP_EINVAL, std::string(who) + ": " + e);
   int64_t c[3];
-  tensor_coarse_dims(dim, dims, c);
+  *mask = (uint32_t)mask_in;
+  tensor_coarse_dims(dim, dims, *mask, c);
   *n_h = dims[0] * dims[1] * dims[2];
   *n_H = c[0] * c[1] * c[2];
   return AMG_HIP_OK;
 }
 
-amg_hip_status amg_hip_tensor_restrict(int32_t dim, const int64_t* dims_h, const double* r, double* f_H) {
+static amg_hip_status tensor_restrict_host(const char* who, int32_t dim, const int64_t* dims_h, int64_t mask_in,
+                                           const double* r, double* f_H) {
   int64_t n_h = 0, n_H = 0;
-  amg_hip_status st = tensor_transfer_args("amg_hip_tensor_restrict", dim, dims_h, &n_h, &n_H);
+  uint32_t mask = 0;
+  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, &mask, &n_h, &n_H);
   if (st != AMG_HIP_OK) return st;
   if (!r || !f_H) return fail(AMG_HIP_EINVAL, "bad argument");
   if ((st = need_device()) != AMG_HIP_OK) return st;
   DevMem dr, df;
   HIP_TRY(upload(dr, r, (size_t)n_h));
   HIP_TRY(df.alloc(sizeof(double) * n_H));
-  HIP_TRY(launch_tensor_restrict(dim, dims_h, dr.as<double>(), df.as<double>(), nullptr, nullptr));
+  HIP_TRY(launch_tensor_restrict(dim, dims_h, mask, dr.as<double>(), df.as<double>(), nullptr, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(f_H, df.p, sizeof(double) * n_H, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
 }
+amg_hip_status amg_hip_tensor_restrict(int32_t dim, const int64_t* dims_h, const double* r, double* f_H) {
+  return tensor_restrict_host("amg_hip_tensor_restrict", dim, dims_h, -1, r, f_H);
+}
+amg_hip_status amg_hip_tensor_restrict_axes(int32_t dim, const int64_t* dims_h, int32_t axis_mask, const double* r,
+                                            double* f_H) {
+  return tensor_restrict_host("amg_hip_tensor_restrict_axes", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, r, f_H);
+}
 
-amg_hip_status amg_hip_tensor_prolong_add(int32_t dim, const int64_t* dims_h, const double* u_H,
-                                          double* u_h) {
+static amg_hip_status tensor_prolong_add_host(const char* who, int32_t dim, const int64_t* dims_h, int64_t mask_in,
+                                              const double* u_H, double* u_h) {
   int64_t n_h = 0, n_H = 0;
-  amg_hip_status st = tensor_transfer_args("amg_hip_tensor_prolong_add", dim, dims_h, &n_h, &n_H);
+  uint32_t mask = 0;
+  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, &mask, &n_h, &n_H);
   if (st != AMG_HIP_OK) return st;
   if (!u_H || !u_h) return fail(AMG_HIP_EINVAL, "bad argument");
   if ((st = need_device()) != AMG_HIP_OK) return st;
   DevMem dH, dh;
   HIP_TRY(upload(dH, u_H, (size_t)n_H));
   HIP_TRY(upload(dh, u_h, (size_t)n_h));
-  HIP_TRY(launch_tensor_prolong_add(dim, dims_h, dH.as<double>(), dh.as<double>(), nullptr));
+  HIP_TRY(launch_tensor_prolong_add(dim, dims_h, mask, dH.as<double>(), dh.as<double>(), nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(u_h, dh.p, sizeof(double) * n_h, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
+}
+amg_hip_status amg_hip_tensor_prolong_add(int32_t dim, const int64_t* dims_h, const double* u_H,
+                                          double* u_h) {
+  return tensor_prolong_add_host("amg_hip_tensor_prolong_add", dim, dims_h, -1, u_H, u_h);
+}
+amg_hip_status amg_hip_tensor_prolong_add_axes(int32_t dim, const int64_t* dims_h, int32_t axis_mask,
+                                               const double* u_H, double* u_h) {
+  return tensor_prolong_add_host("amg_hip_tensor_prolong_add_axes", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, u_H,
+                                 u_h);
 }
 
 amg_hip_status amg_hip_linear_prolong_add(int64_t n_h, int64_t n_H, const double* u_H,

@@ -6,8 +6,10 @@
 // the operators of LinearInterpolator are recognised and replaced by matrix-free kernels.
 #pragma once
 #include <array>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <amg/eigen_lite.hpp>
@@ -168,6 +170,33 @@ class TensorInterpolator : public InterpolatorBase<EleType> {
     Eigen::SparseMatrix<EleType> R = P.transpose();
     this->set_level_to_P(level, P);
     this->set_level_to_R(level, R);
+  }
+};
+
+// Semi-coarsening of the same grids (amg_hip_create_tensor_semi; NO reference counterpart): level l
+// coarsens the axes of its mask (bit 0 = x, 1 = y, 2 = z) with P1 and leaves the others alone
+// (identity).  `masks` empty: the library's automatic rule -- the axes whose strongest pure-axis
+// coupling is at least theta times the strongest of all, until n_levels, a level of at most
+// min_coarse rows or a grid without an axis of 2 points (Multigrid::get_n_levels tells).  The
+// operators depend on the level matrices, so AMG::Multigrid lets the library build the hierarchy;
+// get_P / get_R hold the operators afterwards.  For operators that are anisotropic along a grid
+// axis, where full coarsening with a point smoother stalls.
+template <class EleType>
+class SemiTensorInterpolator : public TensorInterpolator<EleType> {
+  std::vector<int32_t> masks_;
+  double theta_;
+  size_t min_coarse_;
+
+ public:
+  SemiTensorInterpolator(size_t nx, size_t ny, size_t nz = 1, std::vector<int32_t> masks = {},
+                         double theta = 0.5, size_t min_coarse = 32)
+      : TensorInterpolator<EleType>(nx, ny, nz), masks_(std::move(masks)), theta_(theta), min_coarse_(min_coarse) {}
+  const std::vector<int32_t>& masks() const { return masks_; }
+  double theta() const { return theta_; }
+  size_t min_coarse() const { return min_coarse_; }
+  void make_operators(size_t, size_t, size_t) override {
+    throw std::logic_error("SemiTensorInterpolator: the coarsened axes depend on the level matrix; "
+                           "AMG::Multigrid builds the operators");
   }
 };
 

@@ -144,8 +144,19 @@ class Multigrid {
         // matrix-free tensor transfer kernels
         const std::array<size_t, 3> d = tp->dims();
         const int64_t dims[3] = {(int64_t)d[0], (int64_t)d[1], (int64_t)d[2]};
-        detail::check(amg_hip_create_tensor(A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(),
-                                            b.data(), tp->dim(), dims, (int32_t)n_levels, &opt, &handle));
+        if (auto* semi = dynamic_cast<SemiTensorInterpolator<EleType>*>(interpolator)) {
+          // semi-coarsening: explicit masks (one per transfer), or the library's automatic rule
+          if (!semi->masks().empty() && semi->masks().size() + 1 != n_levels)
+            throw std::invalid_argument("SemiTensorInterpolator: " + std::to_string(semi->masks().size()) +
+                                        " axis masks for " + std::to_string(n_levels) + " levels");
+          detail::check(amg_hip_create_tensor_semi(
+              A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(), b.data(), tp->dim(), dims,
+              (int32_t)n_levels, semi->masks().empty() ? nullptr : semi->masks().data(), semi->theta(),
+              (int64_t)semi->min_coarse(), &opt, &handle));
+        } else {
+          detail::check(amg_hip_create_tensor(A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(),
+                                              b.data(), tp->dim(), dims, (int32_t)n_levels, &opt, &handle));
+        }
       }
       try {
         n_levels = (size_t)amg_hip_n_levels(handle);

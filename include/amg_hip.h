@@ -334,6 +334,45 @@ amg_hip_status amg_hip_create_tensor(int64_t n, const int32_t* colptr, const int
                                      const double* val, const double* b, int32_t dim,
                                      const int64_t* dims /* 3 */, int32_t n_levels,
                                      const amg_hip_options* opts, amg_hip_solver** out);
+/* Semi-coarsening of a structured grid (NO reference counterpart): amg_hip_create_tensor with a
+ * per-level AXIS MASK, bit 0 = x, bit 1 = y, bit 2 = z.  A masked axis of length m goes to
+ * floor(m / 2) with P1(m), an unmasked one keeps its length with the identity: P_l = P_z (x) P_y (x)
+ * P_x, R_l = P_l^T, A_{l+1} = R_l (A_l P_l).  Every weight is still a product of powers of two, so
+ * the bit-for-bit statements of amg_hip_create_tensor carry over (level matrices equal
+ * amg_hip_create_custom on the same P / R; transfer kind 2 and kind 0 give the same bits).  For
+ * operators that are anisotropic along a grid axis -- stretched grids, thin layers, a diffusivity
+ * that differs by direction -- on which full coarsening with a point smoother stalls: only the
+ * strongly coupled axes are coarsened and the point smoothers (true Jacobi, Chebyshev, with their
+ * block and float forms) stay effective; the price is operator complexity.
+ * axis_masks != NULL: n_levels - 1 explicit masks; `theta` and `min_coarse` are ignored and the
+ * solver has exactly n_levels levels.  AMG_HIP_EINVAL, with the level in the message, for a zero
+ * mask, bit 2 when dim = 2, bits above 7 and a masked axis of fewer than 2 points.
+ * axis_masks == NULL: the automatic rule, n_levels being a maximum.  On a level's grid w_a =
+ * max |a_ij| over the entries whose column's grid coordinates differ from the row's by +-1 in axis
+ * a and by 0 in the others (0 without such an entry); an axis is eligible when it has at least 2
+ * points; an eligible axis a is coarsened iff w_a >= theta * max over the eligible b of w_b.  The
+ * hierarchy ends at n_levels, at a level of at most `min_coarse` rows, or when no axis is eligible
+ * (amg_hip_n_levels tells).  The rule does not depend on any order of evaluation.  theta must lie
+ * in (0, 1] (0.5 is a good choice) and min_coarse be at least 1, else AMG_HIP_EINVAL.
+ * Everything else as amg_hip_create_tensor: every smoother, AMG_HIP_SM_LINE_ALT included (the level
+ * grids are known), host_only, the layouts; opts->window = 1: AMG_HIP_EUNSUPPORTED.  All argument
+ * checks come before the device is touched.  amg_hip_get_level_dims, amg_hip_level_transfer_kind,
+ * amg_hip_get_transfer and amg_hip_line_directions work on these solvers.                       */
+amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                          const double* val, const double* b, int32_t dim,
+                                          const int64_t* dims /* 3 */, int32_t n_levels,
+                                          const int32_t* axis_masks /* n_levels - 1, or NULL */,
+                                          double theta, int64_t min_coarse,
+                                          const amg_hip_options* opts, amg_hip_solver** out);
+/* Axis mask of the transfers between `level` and `level` + 1 of a solver made by one of the tensor
+ * constructors (the full-coarsening ones report 3 in 2-D and 7 in 3-D); also on host_only solvers.
+ * AMG_HIP_EINVAL on the coarsest level and for every other solver.                              */
+amg_hip_status amg_hip_get_level_axes(const amg_hip_solver* s, int32_t level, int32_t* axis_mask);
+/* The w of the automatic rule of amg_hip_create_tensor_semi for a matrix on the grid `dims`, on
+ * host arrays (CSC or CSR: the maxima are the same); no device is needed.                       */
+amg_hip_status amg_hip_tensor_axis_strength(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                            const double* val, int32_t dim, const int64_t* dims /* 3 */,
+                                            double* w /* 3 */);
 /* Grid of `level` (3 entries, x fastest) of a solver made by amg_hip_create_tensor; also on
  * host_only solvers.  AMG_HIP_EINVAL for every other solver.                                    */
 amg_hip_status amg_hip_get_level_dims(const amg_hip_solver* s, int32_t level, int64_t* dims /* 3 */);
@@ -407,9 +446,23 @@ amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, c
                                          const double* val_dev, const double* b_dev, int32_t dim,
                                          const int64_t* dims /* 3, host */, int32_t n_levels,
                                          const amg_hip_options* opts, amg_hip_solver** out);
+/* amg_hip_create_tensor_semi for a caller's matrix in DEVICE memory (CSR, as for
+ * amg_hip_create_tensor_dev), on top of that constructor's level loop: the Galerkin products run
+ * as K-TensorGalerkin with the level's mask, and the automatic rule takes its w from K-AxisStrength,
+ * a maximum of non-negative doubles and therefore the host's bits -- masks, dims, level matrices
+ * and every cycle equal amg_hip_create_tensor_semi on the CSC arrays of the same A.  Same device
+ * path, same silent fallbacks to the host constructor and same argument checks as
+ * amg_hip_create_tensor_dev, plus those of amg_hip_create_tensor_semi; amg_hip_setup_on_device
+ * tells the two paths apart.                                                                     */
+amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                              const double* val_dev, const double* b_dev, int32_t dim,
+                                              const int64_t* dims /* 3, host */, int32_t n_levels,
+                                              const int32_t* axis_masks /* n_levels - 1, host, or NULL */,
+                                              double theta, int64_t min_coarse,
+                                              const amg_hip_options* opts, amg_hip_solver** out);
 /* *on = 1: the hierarchy was built by a device-only path (amg_hip_create_poisson,
- * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor, amg_hip_create_tensor_dev when
- * they did not fall back),
+ * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor, amg_hip_create_tensor_dev,
+ * amg_hip_create_tensor_semi_dev when they did not fall back),
  * 0: by the host constructor -- every other entry point and the silent fallbacks.  Also on
  * host_only solvers (0).                                                                        */
 amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on);
@@ -823,6 +876,14 @@ amg_hip_status amg_hip_tensor_restrict(int32_t dim, const int64_t* dims_h /* 3 *
                                        double* f_H);
 amg_hip_status amg_hip_tensor_prolong_add(int32_t dim, const int64_t* dims_h /* 3 */,
                                           const double* u_H, double* u_h);
+/* The same two transfers with an axis mask (amg_hip_create_tensor_semi: bit 0 = x, 1 = y, 2 = z): a
+ * masked axis needs 2 points and goes to floor(m / 2), an unmasked one keeps its length.  Still
+ * bit-identical to amg_hip_spmv with the R / P of amg_hip_get_transfer.  AMG_HIP_EINVAL for a zero
+ * mask, bit 2 when dim = 2, bits above 7 and a masked axis of fewer than 2 points.              */
+amg_hip_status amg_hip_tensor_restrict_axes(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
+                                            const double* r, double* f_H);
+amg_hip_status amg_hip_tensor_prolong_add_axes(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
+                                               const double* u_H, double* u_h);
 /* AMG::rss(A, u, b), common.hpp:17-27. */
 amg_hip_status amg_hip_rss_host(int64_t n, const int32_t* colptr,
                                 const int32_t* rowind, const double* val,

@@ -12,6 +12,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py alt [<nx> <ny> <levels>]                    alternating line smoother 1+1 next to true Jacobi 2+2 and the line smoother 1+1 through tensor_dev, isotropic and split-anisotropy operators (legs alternate)
        config_bench.py alt10 <nx> <ny> <levels>                    ten cycles of the alternating line smoother (kernel traces)
        config_bench.py mixed [<nx> <ny> <nz> <levels>]             amg_hip_pcg and amg_hip_pcg_mixed (single-precision V-cycle) alternating on a variable-coefficient operator, true Jacobi 2+2 and Chebyshev(2) 1+1
+       config_bench.py semi [<nx> <ny> <nz> <eps_x> <eps_y> <eps_z>] PCG to 1e-8 on an axis-scaled diffusion operator: full coarsening + Jacobi, semi-coarsening + Jacobi, full coarsening + alternating lines, semi-coarsening + amg_hip_pcg_mixed (legs alternate)
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -229,10 +230,11 @@ def run_tensor_setup(dim, n, L, reps=3):
           f"ratio {best['host'] / best['device']:.1f}", flush=True)
 
 
-def torch_diffusion(dims, seed=1):
-    """-div(kappa grad u) + u on the grid `dims` (x fastest), kappa uniform in [1, 10] per face, assembled
-    on the GPU with torch: (crow int32, col int32, val float64, b float64) device tensors in CSR with
-    ascending columns.  Both triangles hold the same bits, so the arrays are the CSC arrays as well."""
+def torch_diffusion(dims, seed=1, eps=None, shift=1.0):
+    """-div(kappa grad u) + shift u on the grid `dims` (x fastest), kappa uniform in [1, 10] per face,
+    assembled on the GPU with torch: (crow int32, col int32, val float64, b float64) device tensors in
+    CSR with ascending columns.  Both triangles hold the same bits, so the arrays are the CSC arrays as
+    well.  eps: a factor per axis on that axis's kappa (the scaled operator of the semi mode)."""
     import torch
     dev = torch.device("cuda")
     g = torch.Generator(device=dev)
@@ -248,11 +250,13 @@ def torch_diffusion(dims, seed=1):
     cols = torch.zeros((n, w), dtype=torch.int64, device=dev)
     vals = torch.zeros((n, w), dtype=torch.float64, device=dev)
     mask = torch.zeros((n, w), dtype=torch.bool, device=dev)
-    diag = torch.ones(n, dtype=torch.float64, device=dev)
+    diag = torch.full((n,), float(shift), dtype=torch.float64, device=dev)
     for a in range(dim):
         lo_ok, hi_ok = coord[a] > 0, coord[a] < ext[a] - 1
         k_lo = torch.where(lo_ok, torch.roll(kap[a], stride[a]), torch.full_like(kap[a], 5.5))  # Dirichlet faces: 5.5
         k_hi = torch.where(hi_ok, kap[a], torch.full_like(kap[a], 5.5))
+        if eps is not None:
+            k_lo, k_hi = k_lo * float(eps[a]), k_hi * float(eps[a])
         diag = diag + k_lo + k_hi
         s_lo, s_hi = dim - 1 - a, dim + 1 + a  # ascending column order
         cols[:, s_lo], vals[:, s_lo], mask[:, s_lo] = i - stride[a], -k_lo, lo_ok
@@ -468,6 +472,79 @@ def run_mixed(dims, L, reps=3, rtol=1e-8, applies=10):
         mg.close()
 
 
+def full_levels(dims, min_coarse=32):
+    """levels of the full-coarsening hierarchy that ends like the automatic semi rule: at a level of at
+    most min_coarse rows or where an axis has fewer than 2 points"""
+    d, nl = list(dims), 1
+    while min(d) >= 2 and d[0] * d[1] * (d[2] if len(d) == 3 else 1) > min_coarse:
+        d, nl = [m // 2 for m in d], nl + 1
+    return nl
+
+
+def run_semi(dims, eps, reps=3, rtol=1e-8, max_iters=300, theta=0.5, min_coarse=32):
+    """PCG from x = 0 to `rtol` on the diffusion operator of tensor-user-setup with the conductivities
+    of axis a scaled by eps[a] and mass 0.01, set up on the device, four legs alternating in one
+    process, `reps` repeats: full coarsening + true Jacobi 2+2 (tensor_dev), semi-coarsening + true
+    Jacobi 2+2 (tensor_semi_dev, automatic masks), full coarsening + alternating lines 1+1, and
+    semi-coarsening + amg_hip_pcg_mixed (layout SELL).  Per run: iterations and wall ms of the solve (the
+    solvers synchronise themselves); a leg that stops at `max_iters` counts as capped.  Once per leg:
+    levels, masks, the device matrix bytes of the smoothed levels over level 0's (the operator complexity
+    as the cycle pays for it) and ms per V-cycle."""
+    import torch
+    arrays = torch_diffusion(dims, eps=eps, shift=0.01)
+    torch.cuda.synchronize()
+    tag = " x ".join(str(d) for d in dims) + " eps " + "/".join(f"{e:g}" for e in eps)
+    L = full_levels(dims, min_coarse)
+    jac, alt = TENSOR_KW["jacobi"], ALT_KW["alt 1+1"]
+    mk = {"full + jacobi": lambda: amg.Multigrid.tensor_dev(*arrays, dims, L, **jac),
+          "semi + jacobi": lambda: amg.Multigrid.tensor_semi_dev(*arrays, dims, 24, theta=theta,
+                                                                 min_coarse=min_coarse, **jac),
+          "full + alt": lambda: amg.Multigrid.tensor_dev(*arrays, dims, L, **alt),
+          "semi + mixed": lambda: amg.Multigrid.tensor_semi_dev(*arrays, dims, 24, theta=theta, min_coarse=min_coarse,
+                                                                layout=amg.LAYOUT_SELL, **jac)}
+    names = {1: "x", 2: "y", 3: "xy", 4: "z", 5: "xz", 6: "yz", 7: "xyz"}
+    legs = {}
+    for name, make in mk.items():
+        t0 = time.perf_counter()
+        mg = make()
+        mg.sync()
+        dt = time.perf_counter() - t0
+        nl = mg.n_levels
+        mat = [mg.level_layout(l)[1] for l in range(nl - 1)]  # the smoothed levels' matrix bytes per sweep
+        masks = " ".join(names[mg.level_axes(l)] for l in range(nl - 1))
+        mg.vcycle(3)
+        mg.sync()
+        mg.zero_vec(0, "u")
+        mg.sync()
+        t0 = time.perf_counter()
+        mg.vcycle(10)
+        mg.sync()
+        cyc = (time.perf_counter() - t0) / 10
+        print(f"semi {tag}, {name}: setup {dt:.2f} s (setup_on_device {mg.setup_on_device}), {nl} levels, axes [{masks}], "
+              f"coarsest {mg.get_n_dofs(nl - 1)} dofs, matrix bytes of the smoothed levels / level 0 "
+              f"{sum(mat) / mat[0]:.2f}, {cyc * 1e3:.3f} ms/V-cycle, "
+              f"must-move {mg.cycle_must_move() / 1e6:.1f} MB", flush=True)
+        solve = mg.pcg_mixed if name.endswith("mixed") else mg.pcg
+        mg.zero_vec(0, "u")
+        solve(rtol=rtol, max_iters=max_iters)  # first call: work vectors, float copies, captured graphs
+        legs[name] = (mg, solve)
+    best = {}
+    for rep_ in range(reps):
+        for name, (mg, solve) in legs.items():
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            _, it, rel = solve(rtol=rtol, max_iters=max_iters)
+            dt = time.perf_counter() - t0
+            best[name] = min(best.get(name, dt), dt)
+            print(f"semi {tag}, {name} rep {rep_}: {it} iterations, {dt * 1e3:.2f} ms to {rtol:g} (relres {rel:.2e}, "
+                  f"{'reached' if rel <= rtol else 'NOT reached: capped'})", flush=True)
+    print(f"semi {tag}: best time to {rtol:g}: " + ", ".join(f"{k} {v * 1e3:.2f} ms" for k, v in best.items()),
+          flush=True)
+    for mg, _ in legs.values():
+        mg.close()
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -593,6 +670,15 @@ elif len(sys.argv) > 1 and sys.argv[1] == "mixed":
         run_mixed((1024, 1024), 8)
         run_mixed((4096, 4096), 10)
         run_mixed((256, 256, 256), 7)
+elif len(sys.argv) > 1 and sys.argv[1] == "semi":
+    # profiles/semi_config_bench.txt: a 4096 x 1024 grid with a weak y axis, a 256^3 box with a weak z axis
+    if len(sys.argv) > 7:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        e = tuple(float(x) for x in sys.argv[5:8])
+        run_semi(d if d[2] > 1 else d[:2], e if d[2] > 1 else e[:2])
+    else:
+        run_semi((4096, 1024), (1.0, 1e-2))
+        run_semi((256, 256, 256), (1.0, 1.0, 1e-2))
 elif len(sys.argv) > 3 and sys.argv[1] == "tensor10":
     mg = amg.Multigrid.poisson_tensor(int(sys.argv[2]), int(sys.argv[3]), stencil_transfers=len(sys.argv) < 5,
                                       **TENSOR_KW["jacobi"])
