@@ -404,6 +404,74 @@ def set_xcd_mapping(on):
     lib().amg_hip_set_xcd_mapping(int(on))
 
 
+class DevMat:
+    """amg_hip_devmat: a CSR block (rows x ncols, row i's diagonal in column i + diag_shift) uploaded
+    in one of the solver's device layouts; exact zeros are pruned.  The operations take and return
+    numpy arrays and move them through torch tensors on `device`."""
+
+    RESIDUAL, JACOBI, SPMV = 0, 1, 2
+
+    def __init__(self, rowptr, col, val, ncols, layout=LAYOUT_AUTO, diag_shift=0, device=0):
+        rowptr, col, val = _a32(rowptr), _a32(col), _a64(val)
+        self.rows, self.cols = int(rowptr.size - 1), int(ncols)
+        self.diag_shift, self.device = int(diag_shift), int(device)
+        self._h = C.c_void_p()
+        st = lib().amg_hip_devmat_create(self.rows, self.cols, _p32(rowptr), _p32(col), _p64(val), int(layout),
+                                         self.diag_shift, self.device, C.byref(self._h))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+
+    def layout(self):
+        """(LAYOUT_CSR / _SELL / _DICT, bytes of the matrix stream of one application)."""
+        lay, nb = C.c_int32(0), C.c_int64(0)
+        _chk(lib().amg_hip_devmat_layout(self._h, C.byref(lay), C.byref(nb)))
+        return lay.value, int(nb.value)
+
+    def apply(self, op, x, f=None, omega=1.0, diag_shift=None):
+        """RESIDUAL: f - A x;  JACOBI: one sweep x_i + omega ((f_i - sum_{j != i} a_ij x_j) / a_ii - x_i)
+        for the rows' own entries x[diag_shift : diag_shift + rows] (rows without a diagonal keep
+        theirs);  SPMV: A x.  x has `ncols` entries, f and the result `rows`."""
+        import torch
+        if not self._h:
+            raise ValueError("DevMat is closed")
+        x = _a64(x)
+        if x.size != self.cols:
+            raise ValueError(f"`x` must have {self.cols} entries, got {x.size}")
+        if op != self.SPMV:
+            if f is None:
+                raise ValueError("`f` is required for this operation")
+            f = _a64(f)
+            if f.size != self.rows:
+                raise ValueError(f"`f` must have {self.rows} entries, got {f.size}")
+        shift = self.diag_shift if diag_shift is None else int(diag_shift)
+        if op == self.JACOBI and (shift < 0 or self.rows + shift > self.cols):
+            raise ValueError("a Jacobi sweep needs rows + diag_shift <= ncols")
+        dev = torch.device("cuda", self.device)
+        xt = torch.tensor(x, device=dev)    # copies: x may be read-only
+        ft = torch.tensor(f, device=dev) if op != self.SPMV else None
+        out = torch.empty(self.rows, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        st = lib().amg_hip_devmat_apply(self._h, int(op), xt.data_ptr(), ft.data_ptr() if ft is not None else None,
+                                        out.data_ptr(), float(omega), shift, None)
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy()
+
+    def close(self):
+        if self._h:
+            lib().amg_hip_devmat_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- Grid<double> ------------------------------------------------------------
 def laplacian(n, dim=2):
     """grid.hpp:88-98.  Returns (colptr, rowind, val) of the CSC matrix."""

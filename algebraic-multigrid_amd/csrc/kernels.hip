@@ -478,8 +478,11 @@ __global__ __launch_bounds__(256) void sell_kernel(
     }
   };
   // the pass length follows the PANEL's width (wave-uniform branch): a 7-wide
-  // panel walked with a 9-entry pass would issue 2 dead loads + 2 dead gathers
-  if (w <= 3) pass(0, std::integral_constant<int, 3>{});
+  // panel walked with a 9-entry pass would issue 2 dead loads + 2 dead gathers.
+  // A panel of empty rows (w == 0) owns no slot: soff[s] is the next panel's first slot, or
+  // `slots` itself for a trailing one, so no pass may run (a pass clamps j to j0 and loads)
+  if (w == 0) {
+  } else if (w <= 3) pass(0, std::integral_constant<int, 3>{});
   else if (w <= 5) pass(0, std::integral_constant<int, 5>{});
   else if (w <= 7) pass(0, std::integral_constant<int, 7>{});
   else if (w <= 9) pass(0, std::integral_constant<int, 9>{});
@@ -6757,7 +6760,8 @@ __global__ __launch_bounds__(256) void sell_f32_kernel(
       }
     }
   };
-  if (w <= 3) pass(0, std::integral_constant<int, 3>{});
+  if (w == 0) {  // a panel of empty rows owns no slot (sell_kernel)
+  } else if (w <= 3) pass(0, std::integral_constant<int, 3>{});
   else if (w <= 5) pass(0, std::integral_constant<int, 5>{});
   else if (w <= 7) pass(0, std::integral_constant<int, 7>{});
   else if (w <= 9) pass(0, std::integral_constant<int, 9>{});
