@@ -41,7 +41,8 @@ class Options(C.Structure):
                 ("keep_residual", C.c_int32), ("exact_coarse_solve", C.c_int32),
                 ("exact_gs", C.c_int32),
                 ("stream", C.c_void_p), ("window", C.c_int32), ("cheb_degree", C.c_int32),
-                ("cheb_lower", C.c_double), ("cheb_upper", C.c_double)]
+                ("cheb_lower", C.c_double), ("cheb_upper", C.c_double),
+                ("natural_sides", C.c_int32), ("singular", C.c_int32)]
 
 
 SLAB_MAX_LEVELS = 8
@@ -122,6 +123,9 @@ _SIGS = {
                                                  C.c_int32, _i64p, C.c_int32, _i32p, C.c_double, C.c_int64,
                                                  C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_get_level_axes": (C.c_int, [C.c_void_p, C.c_int32, _i32p]),
+    "amg_hip_get_natural_sides": (C.c_int, [C.c_void_p, _i32p]),
+    "amg_hip_tensor_restrict_bc": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int32, _f64p, _f64p]),
+    "amg_hip_tensor_prolong_add_bc": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int32, _f64p, _f64p]),
     "amg_hip_tensor_axis_strength": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, C.c_int32, _i64p, _f64p]),
     "amg_hip_tensor_restrict_axes": (C.c_int, [C.c_int32, _i64p, C.c_int32, _f64p, _f64p]),
     "amg_hip_tensor_prolong_add_axes": (C.c_int, [C.c_int32, _i64p, C.c_int32, _f64p, _f64p]),
@@ -611,11 +615,13 @@ class Multigrid:
                stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
                no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
-               window=False, _semi=None):
+               window=False, natural_sides=0, singular=False, _semi=None):
         """AMG::Multigrid on a FULL-coarsening hierarchy of the grid `dims` = (nx, ny) or (nx, ny, nz),
         x fastest (amg_hip_create_tensor): every axis m -> m // 2, tensor-product linear interpolation,
         matrix-free transfer kernels unless stencil_transfers=False.  A is the caller's matrix on
-        that grid."""
+        that grid.  natural_sides: mask of the sides without a Dirichlet condition (bit 2a = low side
+        of axis a, bit 2a + 1 = high side); singular=True (all sides natural): A has the constants as
+        its null space and the coarsest solve pins its last unknown."""
         if compute_error_every_n_iters > n_iters:
             raise ValueError("`compute_error_every_n_iters` must be leq to `n_iters`, got "
                              f"{compute_error_every_n_iters} and {n_iters}")
@@ -632,6 +638,7 @@ class Multigrid:
                          False, keep_residual, exact_coarse_solve, exact_gs, cheb_degree, cheb_lower,
                          cheb_upper)
         o.window = int(window)
+        o.natural_sides, o.singular = int(natural_sides), int(singular)
         h = C.c_void_p()
         if _semi is not None:  # tensor_semi
             masks, theta, min_coarse = _semi
@@ -655,7 +662,8 @@ class Multigrid:
                    stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
                    no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                    exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
-                   window=False, host_galerkin=False, fuse_prolong=False, _semi=None):
+                   window=False, host_galerkin=False, fuse_prolong=False, natural_sides=0, singular=False,
+                   _semi=None):
         """Multigrid.tensor for a matrix that sits on the device, with the set-up on the device
         (amg_hip_create_tensor_dev).  A is in CSR: crow (n + 1 int32 row pointers), col (int32,
         ascending inside a row), val (float64), and b (n float64), each a contiguous 1-D torch tensor
@@ -696,6 +704,7 @@ class Multigrid:
                          host_galerkin, keep_residual, exact_coarse_solve, exact_gs, cheb_degree, cheb_lower,
                          cheb_upper)
         o.window = int(window)
+        o.natural_sides, o.singular = int(natural_sides), int(singular)
         if device_count() > 0:
             tdev = torch.device("cuda", device if device >= 0 else torch.cuda.current_device())
             dev = []
@@ -812,6 +821,13 @@ class Multigrid:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)
         return tuple(int(x) for x in d)
+
+    def natural_sides(self):
+        """The solver's mask of natural boundary sides (amg_hip_get_natural_sides); 0 on solvers that
+        are not tensor hierarchies."""
+        m = C.c_int32(-1)
+        _chk(lib().amg_hip_get_natural_sides(self._h, C.byref(m)))
+        return m.value
 
     def level_axes(self, level):
         """Axis mask (bit 0 = x, 1 = y, 2 = z) of the transfers between `level` and `level` + 1 of a
@@ -1306,16 +1322,20 @@ def tensor_axis_strength(colptr, rowind, val, dims):
     return w
 
 
-def tensor_restrict(dims, r, axes=None):
+def tensor_restrict(dims, r, axes=None, natural_sides=0):
     """f_H = R r for the full-coarsening transfer of the fine grid `dims` (amg_hip_tensor_restrict);
-    axes: the mask of coarsened axes instead (amg_hip_tensor_restrict_axes)."""
+    axes: the mask of coarsened axes instead (amg_hip_tensor_restrict_axes); natural_sides != 0: the
+    mask of sides without a Dirichlet condition (amg_hip_tensor_restrict_bc)."""
     dim, d3 = _dims3(dims)
     r = _a64(r)
     n_h, n_H = _tensor_sizes(d3, dim, axes)
     if r.size != n_h:
         raise ValueError(f"`r` must have {n_h} entries, got {r.size}")
     out = np.empty(max(n_H, 0), np.float64)
-    if axes is not None:
+    if natural_sides:
+        st = lib().amg_hip_tensor_restrict_bc(dim, d3.ctypes.data_as(_i64p), (7 if dim == 3 else 3) if axes is None
+                                              else int(axes), int(natural_sides), _p64(r), _p64(out))
+    elif axes is not None:
         st = lib().amg_hip_tensor_restrict_axes(dim, d3.ctypes.data_as(_i64p), int(axes), _p64(r), _p64(out))
     else:
         st = lib().amg_hip_tensor_restrict(dim, d3.ctypes.data_as(_i64p), _p64(r), _p64(out))
@@ -1325,16 +1345,19 @@ def tensor_restrict(dims, r, axes=None):
     return out
 
 
-def tensor_prolong_add(dims, u_H, u_h, axes=None):
-    """u_h + P u_H for the same transfer (amg_hip_tensor_prolong_add, or amg_hip_tensor_prolong_add_axes
-    with the mask `axes`); returns a new array."""
+def tensor_prolong_add(dims, u_H, u_h, axes=None, natural_sides=0):
+    """u_h + P u_H for the same transfer (amg_hip_tensor_prolong_add, amg_hip_tensor_prolong_add_axes
+    with the mask `axes`, amg_hip_tensor_prolong_add_bc with natural_sides != 0); returns a new array."""
     dim, d3 = _dims3(dims)
     u_H = _a64(u_H)
     u_h = np.array(u_h, dtype=np.float64, copy=True)
     n_h, n_H = _tensor_sizes(d3, dim, axes)
     if u_h.size != n_h or u_H.size != n_H:
         raise ValueError(f"`u_h` / `u_H` must have {n_h} / {n_H} entries, got {u_h.size} / {u_H.size}")
-    if axes is not None:
+    if natural_sides:
+        st = lib().amg_hip_tensor_prolong_add_bc(dim, d3.ctypes.data_as(_i64p), (7 if dim == 3 else 3) if axes is None
+                                                 else int(axes), int(natural_sides), _p64(u_H), _p64(u_h))
+    elif axes is not None:
         st = lib().amg_hip_tensor_prolong_add_axes(dim, d3.ctypes.data_as(_i64p), int(axes), _p64(u_H), _p64(u_h))
     else:
         st = lib().amg_hip_tensor_prolong_add(dim, d3.ctypes.data_as(_i64p), _p64(u_H), _p64(u_h))

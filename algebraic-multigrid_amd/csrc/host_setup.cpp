@@ -182,7 +182,15 @@ void tensor_coarse_dims(int dim, const int64_t d[3], int64_t c[3]) {
   tensor_coarse_dims(dim, d, tensor_full_mask(dim), c);
 }
 
-Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask) {
+// sides (natural boundary sides, amg_hip.h): bit 2a = low side of axis a, bit 2a + 1 = high side; on
+// a flagged side the boundary row of P1 -- fine point 0, fine point m - 1 of an odd m -- carries 1.0
+// instead of 0.5 (P1N).  w1n: the weight of fine point 2 J + t of coarse point J on an axis of length m.
+static inline double w1n(int64_t J, int t, int64_t m, uint32_t lo, uint32_t hi) {
+  if (t == 1) return 1.0;
+  if (t == 0) return (lo && J == 0) ? 1.0 : 0.5;
+  return (hi && 2 * J + 2 == m - 1) ? 1.0 : 0.5;
+}
+Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask, uint32_t sides) {
   int64_t c[3];
   tensor_coarse_dims(dim, d, mask, c);
   const int64_t nx = d[0], ny = d[1], nz = dim == 3 ? d[2] : 1;
@@ -195,7 +203,8 @@ Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask) {
   const size_t per = (size_t)(cx ? 3 : 1) * (cy ? 3 : 1) * (cz ? 3 : 1);
   P.idx.reserve(per * (size_t)P.n_outer);
   P.val.reserve(per * (size_t)P.n_outer);
-  static const double w3[3] = {0.5, 1.0, 0.5};
+  const uint32_t lx = sides & 1u, hx = (sides >> 1) & 1u, ly = (sides >> 2) & 1u, hy = (sides >> 3) & 1u,
+                 lz = (sides >> 4) & 1u, hz = (sides >> 5) & 1u;
   const int tx_n = cx ? 3 : 1, ty_n = cy ? 3 : 1, tz_n = cz ? 3 : 1;
   int64_t col = 0;
   for (int64_t K = 0; K < c[2]; ++K)
@@ -204,16 +213,16 @@ Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask) {
         for (int tz = 0; tz < tz_n; ++tz) {  // ascending fine row: k, then j, then i
           const int64_t k = cz ? 2 * K + tz : K;
           if (k >= nz) continue;
-          const double wz = cz ? w3[tz] : 1.0;
+          const double wz = cz ? w1n(K, tz, nz, lz, hz) : 1.0;
           for (int ty = 0; ty < ty_n; ++ty) {
             const int64_t j = cy ? 2 * J + ty : J;
             if (j >= ny) continue;
-            const double wzy = wz * (cy ? w3[ty] : 1.0);
+            const double wzy = wz * (cy ? w1n(J, ty, ny, ly, hy) : 1.0);
             for (int tx = 0; tx < tx_n; ++tx) {
               const int64_t i = cx ? 2 * I + tx : I;
               if (i >= nx) continue;
               P.idx.push_back((int32_t)((k * ny + j) * nx + i));
-              P.val.push_back(wzy * (cx ? w3[tx] : 1.0));  // products of powers of two: exact
+              P.val.push_back(wzy * (cx ? w1n(I, tx, nx, lx, hx) : 1.0));  // products of powers of two: exact
             }
           }
         }
@@ -221,7 +230,6 @@ Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask) {
       }
   return P;
 }
-Sparse tensor_P(int dim, const int64_t d[3]) { return tensor_P(dim, d, tensor_full_mask(dim)); }
 
 void tensor_axis_strength(const Sparse& M, int dim, const int64_t d[3], double w[3]) {
   const int64_t nx = d[0], ny = d[1];

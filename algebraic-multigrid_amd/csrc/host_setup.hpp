@@ -39,14 +39,16 @@ bool is_linear_P(const Sparse& P, int64_t n_h, int64_t n_H);
 // linear interpolation P1(nz) (x) P1(ny) (x) P1(nx) in CSC (n_h x n_H), P1(m) being m x floor(m/2)
 // with 0.5, 1.0, 0.5 on rows 2j, 2j+1, 2j+2 (< m) of column j; R = transpose(P).
 void tensor_coarse_dims(int dim, const int64_t dims[3], int64_t coarse[3]);
-Sparse tensor_P(int dim, const int64_t dims[3]);
 
 // Semi-coarsening: `mask` names the axes that are coarsened (bit 0 = x, bit 1 = y, bit 2 = z).  A
 // masked axis of length m goes to floor(m / 2) with P1(m), an unmasked one keeps its length with
-// the identity; P = P_z (x) P_y (x) P_x, R = transpose(P).  The signatures above pass the full mask.
+// the identity; P = P_z (x) P_y (x) P_x, R = transpose(P).  tensor_full_mask: full coarsening.
 inline uint32_t tensor_full_mask(int dim) { return dim == 3 ? 7u : 3u; }
 void tensor_coarse_dims(int dim, const int64_t dims[3], uint32_t mask, int64_t coarse[3]);
-Sparse tensor_P(int dim, const int64_t dims[3], uint32_t mask);
+// Natural boundary sides (amg_hip.h: opts->natural_sides): bit 2a = the low side of axis a, bit 2a + 1
+// its high side.  On a flagged side of a coarsened axis the boundary row of P1(m) -- row 0, row m - 1
+// of an odd m -- holds 1.0 instead of 0.5; the pattern is the same.  sides = 0: every side Dirichlet.
+Sparse tensor_P(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides);
 // The automatic rule.  w[a] = max |a_ij| over the entries of A (rows_as: either compressed form,
 // the maximum does not depend on it) whose column's grid coordinates differ from the row's by
 // +-1 in axis a and by 0 in the others; 0 when there is none.  A maximum of non-negative doubles

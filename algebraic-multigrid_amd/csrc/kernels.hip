@@ -2878,11 +2878,22 @@ hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
 // contributes the identity -- one fine point J with weight 1.0 instead of three.
 // All weights are products of powers of two, so every term w * v is exact and only the ORDER of
 // the additions decides the bits: both kernels add in the order the CSR SpMV with R / P does.
+// Natural boundary sides (amg_hip.h: opts->natural_sides; host_setup.hpp: tensor_P with sides): on a
+// flagged side the boundary row of P1 carries 1.0 instead of 0.5 -- fine point 0 (low side), fine
+// point n - 1 of an odd n (high side).  Still powers of two, the same terms in the same order.
 struct TensorGrid {
   uint32_t nx, ny, nz;  // fine
   uint32_t mx, my, mz;  // coarse (m == n on an axis that is not coarsened)
   uint32_t cx, cy, cz;  // 1: the axis is coarsened
+  uint32_t sides;       // bit 2a: low side of axis a is natural, bit 2a + 1: its high side
 };
+// P1N(2 J + t, J) on a coarsened axis of n fine points, t = 0, 1, 2; lo / hi: the axis' side bits
+template <class T>
+__device__ __forceinline__ T tn_weight(uint32_t J, uint32_t t, uint32_t n, uint32_t lo, uint32_t hi) {
+  if (t == 1u) return T(1.0);
+  if (t == 0u) return (lo && J == 0u) ? T(1.0) : T(0.5);
+  return (hi && 2u * J + 3u == n) ? T(1.0) : T(0.5);
+}
 
 // One lane per coarse point (I, J, K): f_H = sum over k, j, i ascending (row order of R) of
 // (wz wy wx) r[(k ny + j) nx + i], from +0.0.  The x-neighbours 2I, 2I+1 come as one aligned
@@ -2900,19 +2911,21 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
   if (uH) uH[t] = T(0.0);
   const uint32_t i0 = g.cx ? 2u * I : I;  // cx: i0 + 1 < nx always (I < floor(nx / 2))
   const bool third = i0 + 2u < g.nx;
+  const T wx0 = tn_weight<T>(I, 0u, g.nx, g.sides & 1u, g.sides & 2u);
+  const T wx2 = tn_weight<T>(I, 2u, g.nx, g.sides & 1u, g.sides & 2u);
   T s = T(0.0);
 #pragma unroll
   for (uint32_t tz = 0; tz < 3; ++tz) {
     if (!g.cz && tz > 0) break;
     const uint32_t k = g.cz ? 2u * K + tz : K;
     if (k >= g.nz) break;
-    const T wz = g.cz ? (tz == 1 ? T(1.0) : T(0.5)) : T(1.0);
+    const T wz = g.cz ? tn_weight<T>(K, tz, g.nz, g.sides & 16u, g.sides & 32u) : T(1.0);
 #pragma unroll
     for (uint32_t ty = 0; ty < 3; ++ty) {
       if (!g.cy && ty > 0) break;
       const uint32_t j = g.cy ? 2u * J + ty : J;
       if (j >= g.ny) break;
-      const T w = wz * (g.cy ? (ty == 1 ? T(1.0) : T(0.5)) : T(1.0));
+      const T w = wz * (g.cy ? tn_weight<T>(J, ty, g.ny, g.sides & 4u, g.sides & 8u) : T(1.0));
       const int64_t a = ((int64_t)k * g.ny + j) * g.nx + i0;  // a + 1 (and a + 2 when third) < n_h
       if (!g.cx) {  // x is not coarsened: the one fine point I, neighbouring lanes read neighbours
         s += (w * T(1.0)) * r[a];
@@ -2934,9 +2947,9 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
         v1 = r[a + 1];
         if (third) v2 = r[a + 2];
       }
-      s += (w * T(0.5)) * v0;
+      s += (w * wx0) * v0;
       s += (w * T(1.0)) * v1;
-      if (third) s += (w * T(0.5)) * v2;
+      if (third) s += (w * wx2) * v2;
     }
   }
   fH[t] = s;
@@ -2968,8 +2981,8 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
     Jc[0] = (j - 1u) / 2u; wy[0] = 1.0; oky[0] = Jc[0] < g.my;
     Jc[1] = 0; wy[1] = 0.0; oky[1] = false;
   } else {
-    Jc[0] = j / 2u - 1u; wy[0] = 0.5; oky[0] = j >= 2u && Jc[0] < g.my;
-    Jc[1] = j / 2u; wy[1] = 0.5; oky[1] = Jc[1] < g.my;
+    Jc[0] = j / 2u - 1u; wy[0] = ((g.sides & 8u) && j + 1u == g.ny) ? 1.0 : 0.5; oky[0] = j >= 2u && Jc[0] < g.my;
+    Jc[1] = j / 2u; wy[1] = ((g.sides & 4u) && j == 0u) ? 1.0 : 0.5; oky[1] = Jc[1] < g.my;
   }
   if (!g.cz) {
     Kc[0] = k; wz[0] = 1.0; okz[0] = true;
@@ -2978,12 +2991,15 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
     Kc[0] = (k - 1u) / 2u; wz[0] = 1.0; okz[0] = Kc[0] < g.mz;
     Kc[1] = 0; wz[1] = 0.0; okz[1] = false;
   } else {
-    Kc[0] = k / 2u - 1u; wz[0] = 0.5; okz[0] = k >= 2u && Kc[0] < g.mz;
-    Kc[1] = k / 2u; wz[1] = 0.5; okz[1] = Kc[1] < g.mz;
+    Kc[0] = k / 2u - 1u; wz[0] = ((g.sides & 32u) && k + 1u == g.nz) ? 1.0 : 0.5; okz[0] = k >= 2u && Kc[0] < g.mz;
+    Kc[1] = k / 2u; wz[1] = ((g.sides & 16u) && k == 0u) ? 1.0 : 0.5; okz[1] = Kc[1] < g.mz;
   }
   const bool left = g.cx && p >= 1u && p - 1u < g.mx;  // coarse I = p - 1 feeds fine 2p
   const bool mid = g.cx && p < g.mx;                   // coarse I = p feeds fine 2p and 2p + 1
   const bool two = 2u * p + 1u < g.nx;                 // the lane's pair is whole
+  // fine 2p is the last point of an odd line / the first point: the natural sides' weight 1
+  const T wl = ((g.sides & 2u) && 2u * p + 1u == g.nx) ? T(1.0) : T(0.5);
+  const T wm = ((g.sides & 1u) && p == 0u) ? T(1.0) : T(0.5);
   T t0 = T(0.0), t1 = T(0.0);
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
@@ -3003,10 +3019,10 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
             if (two) t1 += (w * T(1.0)) * c2[1];
           }
         }
-        if (left) t0 += (w * T(0.5)) * c[p - 1u];
+        if (left) t0 += (w * wl) * c[p - 1u];
         if (mid) {
           const T m = c[p];
-          t0 += (w * T(0.5)) * m;
+          t0 += (w * wm) * m;
           t1 += (w * T(1.0)) * m;
         }
       }
@@ -3028,8 +3044,10 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   }
 }
 
-static bool tensor_grid(int dim, const int64_t dims[3], uint32_t mask, TensorGrid* g) {
+static bool tensor_grid(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, TensorGrid* g) {
   if ((dim != 2 && dim != 3) || !dims) return false;
+  if (sides >= (1u << (2 * dim))) return false;
+  g->sides = sides;
   if (mask == 0u || mask > (dim == 3 ? 7u : 3u)) return false;
   const int64_t nx = dims[0], ny = dims[1], nz = dim == 3 ? dims[2] : 1;
   if (nx < 1 || ny < 1 || nz < 1 || (dim == 2 && dims[2] != 1)) return false;
@@ -3047,10 +3065,10 @@ static bool tensor_grid(int dim, const int64_t dims[3], uint32_t mask, TensorGri
   return true;
 }
 template <class T>
-static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], uint32_t mask, const T* r, T* fH, T* uH_zero,
+static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const T* r, T* fH, T* uH_zero,
                                            hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, mask, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, sides, &g)) return hipErrorInvalidValue;
   const uint32_t nH = g.mx * g.my * g.mz;
   const dim3 grid((nH + 255u) / 256u), block(256);
   if (pair_aligned(r))
@@ -3059,15 +3077,15 @@ static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], uint3
     hipLaunchKernelGGL((tensor_restrict_kernel<T, false>), grid, block, 0, st, g, r, fH, uH_zero);
   return hipGetLastError();
 }
-hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, const double* r, double* fH,
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const double* r, double* fH,
                                   double* uH_zero, hipStream_t st) {
-  return launch_tensor_restrict_t<double>(dim, dims, mask, r, fH, uH_zero, st);
+  return launch_tensor_restrict_t<double>(dim, dims, mask, sides, r, fH, uH_zero, st);
 }
 template <class T>
-static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], uint32_t mask, const T* uH, T* uh,
+static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const T* uH, T* uh,
                                               hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, mask, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, sides, &g)) return hipErrorInvalidValue;
   const uint32_t total = ((g.nx + 1u) / 2u) * g.ny * g.nz;
   const dim3 grid((total + 255u) / 256u), block(256);
   if (pair_aligned(uh))
@@ -3076,9 +3094,9 @@ static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], ui
     hipLaunchKernelGGL((tensor_prolong_add_kernel<T, false>), grid, block, 0, st, g, uH, uh);
   return hipGetLastError();
 }
-hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, const double* uH, double* uh,
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const double* uH, double* uh,
                                      hipStream_t st) {
-  return launch_tensor_prolong_add_t<double>(dim, dims, mask, uH, uh, st);
+  return launch_tensor_prolong_add_t<double>(dim, dims, mask, sides, uH, uh, st);
 }
 
 // First Jacobi sweep from a zero guess (coarse levels on the way down,
@@ -3099,6 +3117,19 @@ hipError_t launch_jacobi_from_zero(int64_t n, const double* diag, const double* 
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(jacobi_from_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      st, n, diag, f, out, omega);
+  return hipGetLastError();
+}
+
+// x[j * stride] = +0.0, j < count (count <= 64): the pinned entry of the coarsest right-hand side of a
+// singular solver (solver.cpp: launch_coarse), one per column in the block cycle: all columns of a
+// panel in one launch.
+__global__ __launch_bounds__(64) void zero_strided_kernel(double* __restrict__ x, int64_t stride, int count) {
+  if ((int)threadIdx.x < count) x[(int64_t)threadIdx.x * stride] = 0.0;
+}
+hipError_t launch_zero_strided(double* x, int64_t stride, int count, hipStream_t st) {
+  if (count <= 0) return hipSuccess;
+  if (count > 64 || !x) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(zero_strided_kernel, dim3(1), dim3(64), 0, st, x, stride, count);
   return hipGetLastError();
 }
 
@@ -5231,11 +5262,14 @@ __device__ __forceinline__ void tg_cols(uint32_t k, uint32_t m, uint32_t c, int3
     *h = c < (int32_t)m ? c : (int32_t)m - 1;
   }
 }
-// P1(k, J) for a column J inside [0, m)
-__device__ __forceinline__ double tg_weight(uint32_t k, int32_t J, uint32_t c) {
+// P1N(k, J) for a column J inside [0, m) on an axis of n fine points; lo / hi: the axis' side bits
+__device__ __forceinline__ double tg_weight(uint32_t k, int32_t J, uint32_t c, uint32_t n, uint32_t lo, uint32_t hi) {
   if (!c) return (int32_t)k == J ? 1.0 : 0.0;
   const int32_t t = (int32_t)k - 2 * J;
-  return t == 1 ? 1.0 : ((t == 0 || t == 2) ? 0.5 : 0.0);
+  if (t == 1) return 1.0;
+  if (t == 0) return (lo && J == 0) ? 1.0 : 0.5;
+  if (t == 2) return (hi && k + 1u == n) ? 1.0 : 0.5;
+  return 0.0;
 }
 template <int SLOTS, bool FILL>
 __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
@@ -5306,17 +5340,17 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
       if (!g.cz && tz > 0) break;
       const uint32_t iz = g.cz ? 2u * K + tz : K;
       if (iz >= g.nz) break;
-      const double wz = g.cz ? (tz == 1 ? 1.0 : 0.5) : 1.0;
+      const double wz = g.cz ? tn_weight<double>(K, tz, g.nz, g.sides & 16u, g.sides & 32u) : 1.0;
       for (uint32_t ty = 0; ty < 3; ++ty) {
         if (!g.cy && ty > 0) break;
         const uint32_t iy = g.cy ? 2u * J + ty : J;
         if (iy >= g.ny) break;
-        const double rzy = wz * (g.cy ? (ty == 1 ? 1.0 : 0.5) : 1.0);
+        const double rzy = wz * (g.cy ? tn_weight<double>(J, ty, g.ny, g.sides & 4u, g.sides & 8u) : 1.0);
         for (uint32_t tx = 0; tx < 3; ++tx) {
           if (!g.cx && tx > 0) break;
           const uint32_t ix = g.cx ? 2u * I + tx : I;
           if (ix >= g.nx) break;
-          const double r = rzy * (g.cx ? (tx == 1 ? 1.0 : 0.5) : 1.0);  // R(I, i)
+          const double r = rzy * (g.cx ? tn_weight<double>(I, tx, g.nx, g.sides & 1u, g.sides & 2u) : 1.0);  // R(I, i)
           const uint32_t i = (iz * g.ny + iy) * g.nx + ix;
           bool hit_i = false;
           double ap = 0.0;  // (A P)(i, J)
@@ -5324,7 +5358,9 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
             uint32_t kx, ky, kz, q;
             tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
             tg_divmod(q, g.ny, inv_ny, &kz, &ky);
-            const double w = tg_weight(kx, Jx, g.cx) * tg_weight(ky, Jy, g.cy) * tg_weight(kz, Jz, g.cz);
+            const double w = tg_weight(kx, Jx, g.cx, g.nx, g.sides & 1u, g.sides & 2u) *
+                             tg_weight(ky, Jy, g.cy, g.ny, g.sides & 4u, g.sides & 8u) *
+                             tg_weight(kz, Jz, g.cz, g.nz, g.sides & 16u, g.sides & 32u);
             if (w != 0.0) {
               if (FILL) {
                 const double t = aval[p] * w;
@@ -5355,12 +5391,12 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
     oval[at] = acc;
   }
 }
-hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, const int32_t* arp,
+hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const int32_t* arp,
                                   const int32_t* acol, const double* aval, int32_t* cnt,
                                   const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
                                   hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, mask, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, sides, &g)) return hipErrorInvalidValue;
   const uint32_t nH = g.mx * g.my * g.mz;
   const double inv_nx = 1.0 / (double)g.nx, inv_ny = 1.0 / (double)g.ny;
 #define TG_LAUNCH(SLOTS, FILL)                                                                        \
@@ -6926,13 +6962,13 @@ hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, 
 hipError_t launch_linear_prolong_add_f32(int64_t n_h, int64_t n_H, const float* uH, float* uh, hipStream_t st) {
   return launch_linear_prolong_add_t<float>(n_h, n_H, uH, uh, st);
 }
-hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, const float* r, float* fH, float* uH_zero,
+hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st) {
-  return launch_tensor_restrict_t<float>(dim, dims, mask, r, fH, uH_zero, st);
+  return launch_tensor_restrict_t<float>(dim, dims, mask, sides, r, fH, uH_zero, st);
 }
-hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, const float* uH, float* uh,
+hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const float* uH, float* uh,
                                          hipStream_t st) {
-  return launch_tensor_prolong_add_t<float>(dim, dims, mask, uH, uh, st);
+  return launch_tensor_prolong_add_t<float>(dim, dims, mask, sides, uH, uh, st);
 }
 
 

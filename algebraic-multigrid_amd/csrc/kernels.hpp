@@ -330,12 +330,16 @@ hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
 // hipErrorInvalidValue.  Bit-identical to the CSR SpMV with R / P (same terms, same order).
 // mask: the coarsened axes (bit 0 = x, 1 = y, 2 = z; host_setup.hpp: tensor_P with a mask) -- 3 / 7
 // for full coarsening; an axis outside the mask keeps its length (identity) and may have 1 point.
+// sides: the natural boundary sides (bit 2a = low side of axis a, 2a + 1 = high side; host_setup.hpp:
+// tensor_P with sides), 0 = every side Dirichlet; bits at or above 2 dim: hipErrorInvalidValue.
 // f_H = R r, uH_zero (may be null) zero-filled in the same pass
-hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, const double* r, double* fH,
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const double* r, double* fH,
                                   double* uH_zero, hipStream_t st);
 // u_h = u_h + P u_H
-hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, const double* uH, double* uh,
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const double* uH, double* uh,
                                      hipStream_t st);
+// x[j * stride] = +0.0 for j < count (count <= 64, else hipErrorInvalidValue)
+hipError_t launch_zero_strided(double* x, int64_t stride, int count, hipStream_t st);
 hipError_t launch_add_inplace(int64_t n, const double* x, double* y, hipStream_t st);
 // *out = sum x_i (square=0) or sum x_i^2 (square=1); scratch: 1024 doubles
 hipError_t launch_sum(int64_t n, const double* x, double* out, double* scratch, int square,
@@ -463,8 +467,8 @@ hipError_t launch_galerkin_rap(bool fill, int64_t n_h, int64_t n_H, const int32_
 // bits as galerkin_csr on the Kronecker operators, structural zeros included.  *overflow (zeroed
 // by the caller) is set when a coarse row reaches more coarse columns than a lane group holds
 // (16 in 2-D, 32 in 3-D): the result is then unusable and the caller takes the host product.
-// mask: the coarsened axes, as for launch_tensor_restrict.
-hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, const int32_t* arp,
+// mask, sides: the coarsened axes and the natural sides, as for launch_tensor_restrict.
+hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const int32_t* arp,
                                   const int32_t* acol, const double* aval, int32_t* cnt,
                                   const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
                                   hipStream_t st);
@@ -560,9 +564,9 @@ hipError_t launch_to_f64(int64_t n, const float* src, double* dst, hipStream_t s
 hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st);
 hipError_t launch_linear_prolong_add_f32(int64_t n_h, int64_t n_H, const float* uH, float* uh, hipStream_t st);
-hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, const float* r, float* fH, float* uH_zero,
+hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st);
-hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, const float* uH, float* uh,
+hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const float* uH, float* uh,
                                          hipStream_t st);
 
 }  // namespace amg_hip

@@ -182,10 +182,11 @@ hipError_t device_galerkin(const DevCsr& A, int64_t n_H, DevCsr* AH, Sparse* hos
 }
 
 // Setup on the device (K-TensorGalerkin): AH = R (A P) for the tensor-product pair of the grid
-// `dims` (mask: the coarsened axes) from CSR(A) on the device.  *ok = false: a coarse row reaches more columns than the
+// `dims` (mask: the coarsened axes, sides: the natural boundary sides) from CSR(A) on the device.  *ok = false: a coarse row reaches more columns than the
 // kernel's lane group holds; hipErrorInvalidValue: the product is beyond int32 indexing.  Either
 // way the caller takes the host path.
-hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], uint32_t mask, int64_t n_H, DevCsr* AH,
+hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, int64_t n_H,
+                                  DevCsr* AH,
                                   bool* ok) {
   *ok = false;
   hipError_t e;
@@ -195,7 +196,7 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if ((e = total.alloc(sizeof(int64_t))) != hipSuccess) return e;
   if ((e = ovf.alloc(sizeof(int32_t))) != hipSuccess) return e;
   if ((e = hipMemset(ovf.p, 0, sizeof(int32_t))) != hipSuccess) return e;
-  if ((e = launch_tensor_galerkin(false, dim, dims, mask, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
+  if ((e = launch_tensor_galerkin(false, dim, dims, mask, sides, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
                                   nullptr, nullptr, ovf.as<int32_t>(), nullptr)) != hipSuccess)
     return e;
   int32_t over = 0;
@@ -210,7 +211,7 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if (nnz >= ((int64_t)1 << 31) - 1) return hipErrorInvalidValue;
   if ((e = AH->idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
   if ((e = AH->val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
-  if ((e = launch_tensor_galerkin(true, dim, dims, mask, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
+  if ((e = launch_tensor_galerkin(true, dim, dims, mask, sides, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
                                   AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr)) != hipSuccess)
     return e;
   AH->n_rows = AH->n_cols = n_H;
@@ -1010,6 +1011,7 @@ struct CoarseOnDev {
   int m = 0;
   DevMem sf, sb, d;                  // BAND / WIDE schedules
   std::unique_ptr<SpikeOnDev> spike;
+  bool pin = false;                  // opt.singular: the factor is that of pinned_last(A), see launch_coarse
 };
 // level-0 rows from which the lexicographic smoothers take the line-scan form by default
 constexpr int64_t GS_SCAN_MIN_ROWS = 65536;
@@ -1038,8 +1040,41 @@ int64_t mc_one_launch_max_rows() {
   }();
   return v;
 }
+// Singular solvers (opt.singular: A semidefinite, the constants its null space): A with its last row
+// and column replaced by those of the identity.  With the last entry of the right-hand side zeroed,
+// every kind of the banded solve then returns x[n-1] = +0.0 and x[0 : n-1] = the solution of the
+// leading principal block, which is SPD.
+Sparse pinned_last(const Sparse& A) {
+  const int32_t last = (int32_t)A.n_outer - 1;
+  Sparse B;
+  B.n_outer = A.n_outer;
+  B.n_inner = A.n_inner;
+  B.ptr.assign(1, 0);
+  B.ptr.reserve(A.ptr.size());
+  B.idx.reserve(A.idx.size());
+  B.val.reserve(A.val.size());
+  for (int32_t c = 0; c <= last; ++c) {
+    if (c == last) {
+      B.idx.push_back(last);
+      B.val.push_back(1.0);
+    } else {
+      for (int32_t p = A.ptr[(size_t)c], e = A.ptr[(size_t)c + 1]; p < e; ++p)
+        if (A.idx[(size_t)p] != last) {
+          B.idx.push_back(A.idx[(size_t)p]);
+          B.val.push_back(A.val[(size_t)p]);
+        }
+    }
+    B.ptr.push_back((int32_t)B.idx.size());
+  }
+  return B;
+}
 // want_fast: 1 = partitioned whenever it applies, 0 = by size, -1 = never
-amg_hip_status upload_coarse(const Sparse& A, int want_fast, CoarseOnDev* C) {
+// pin: factor pinned_last(A_in) instead; the launches then zero the last right-hand side entry
+amg_hip_status upload_coarse(const Sparse& A_in, int want_fast, CoarseOnDev* C, bool pin) {
+  Sparse A_pin;
+  if (pin) A_pin = pinned_last(A_in);
+  const Sparse& A = pin ? A_pin : A_in;
+  C->pin = pin;
   BandFactor F;
   std::string e = band_factor(A, (size_t)8 << 30, &F);
   if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
@@ -1086,9 +1121,14 @@ amg_hip_status upload_coarse(const Sparse& A, int want_fast, CoarseOnDev* C) {
 }
 // x = A^-1 f; y: scratch of n doubles (BAND / WIDE)
 // uh_out (K-BandChain only): also uh_out = uh_in + P x, the prolongation into the level above
-hipError_t launch_coarse(const CoarseOnDev& C, const double* f, double* y, double* x,
+// C.pin: f[n-1] is zeroed first (one more static node of a captured graph)
+hipError_t launch_coarse(const CoarseOnDev& C, double* f, double* y, double* x,
                          hipStream_t st, int64_t n_h = 0, const double* uh_in = nullptr,
                          double* uh_out = nullptr) {
+  if (C.pin) {
+    const hipError_t e = launch_zero_strided(f + (C.n - 1), 0, 1, st);
+    if (e != hipSuccess) return e;
+  }
   switch (C.kind) {
     case COARSE_SPIKE: {
       SpikeArgs a = C.spike->a;
@@ -1177,7 +1217,7 @@ struct Level {
   int64_t n_coarse = 0;
   const Sparse& P() const {
     if (lazy_linear && P_csc.ptr.empty()) P_csc = linear_P(n, n_coarse);  // interpolator.hpp:106-129
-    if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims, tmask);
+    if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims, tmask, tsides);
     return P_csc;
   }
   const Sparse& R() const {
@@ -1195,6 +1235,7 @@ struct Level {
   int64_t dims[3] = {0, 0, 0};
   bool tensor = false, tensor_stencil = false;
   uint32_t tmask = 0;
+  uint32_t tsides = 0;  // the solver's natural boundary sides (opt.natural_sides), the same on every level
   DevCsr P_rows, R_rows;   // CSR(P), CSR(R)
   // exact lexicographic schedules
   std::unique_ptr<LexOnDev> lex_fwd, lex_bwd;
@@ -1533,7 +1574,7 @@ bool pair_up_ok(const amg_hip_solver* s, int l) {  // its second sweep prolongs 
 // into lt - 1 run as ONE launch (kernels.hip: tail_kernel), or -1.
 int tail_from(const amg_hip_solver* s) {
   const int nl = (int)s->lv.size();
-  if (!g_tail_fusion || s->opt.keep_residual || s->opt.window || nl < 3 || s->coarse.kind != COARSE_CHAIN ||
+  if (!g_tail_fusion || s->opt.keep_residual || s->opt.window || nl < 3 || s->coarse.kind != COARSE_CHAIN || s->coarse.pin ||
       s->coarse.n > tail_max_coarse())
     return -1;
   int lt = nl - 1;
@@ -2071,7 +2112,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
                                        zero_known ? nullptr : C.u.as<double>(), st));
         s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
       } else if (L.tensor_stencil) {                               // the same two steps, full coarsening
-        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.r.as<double>(), C.f.as<double>(),
+        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.r.as<double>(), C.f.as<double>(),
                                        zero_known ? nullptr : C.u.as<double>(), st));
         s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
       } else {
@@ -2178,7 +2219,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
       s->acct(8.0 * C.n + 16.0 * L.n);
     } else if (L.tensor_stencil) {
-      HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, C.u.as<double>(), L.u.as<double>(), st));
+      HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, C.u.as<double>(), L.u.as<double>(), st));
       s->acct(8.0 * C.n + 16.0 * L.n);
     } else {
       const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
@@ -2309,6 +2350,31 @@ struct SemiRule {
   double theta = 0.5;
   int64_t min_coarse = 1;
 };
+// a one-level solver's coarsest right-hand side is the caller's b, which the pinned solve must not alter
+const char* const SINGULAR_ONE_LEVEL =
+    "`singular` = 1 needs a hierarchy of at least 2 levels: with one level the pinned solve would zero the last entry of "
+    "the caller's own right-hand side";
+// "" or what is wrong with opt.natural_sides / opt.singular; dim = 0: a constructor without level
+// grids, which takes neither
+std::string sides_error(const amg_hip_options& o, int dim) {
+  if (o.singular != 0 && o.singular != 1)
+    return "`singular` must be 0 or 1, got " + std::to_string(o.singular);
+  if (!dim) {
+    if (o.natural_sides != 0)
+      return "`natural_sides` = " + std::to_string(o.natural_sides) + ": only the tensor constructors (amg_hip_create_tensor, "
+             "_tensor_semi, _tensor_dev, _tensor_semi_dev) know the sides of a grid; this constructor needs 0";
+    if (o.singular)
+      return "`singular` = 1 needs every side in `natural_sides`, which only the tensor constructors take";
+    return "";
+  }
+  if (o.natural_sides < 0 || o.natural_sides >= (1 << (2 * dim)))
+    return "`natural_sides` = " + std::to_string(o.natural_sides) + " has bits other than the " + std::to_string(2 * dim) +
+           " sides of a " + std::to_string(dim) + "-D grid (bit 2a = low side of axis a, bit 2a + 1 = high side)";
+  if (o.singular && o.natural_sides != (1 << (2 * dim)) - 1)
+    return "`singular` = 1 needs every side natural: `natural_sides` = " + std::to_string((1 << (2 * dim)) - 1) + ", got " +
+           std::to_string(o.natural_sides);
+  return "";
+}
 // "" or what is wrong with the axis mask of level l on the grid d
 std::string semi_mask_error(int l, int dim, const int64_t d[3], int64_t mask) {
   const std::string at = "level " + std::to_string(l) + ": axis mask " + std::to_string(mask);
@@ -2342,6 +2408,11 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   else amg_hip_default_options(&s->opt);
   if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_LINE_ALT)
     return fail(AMG_HIP_EINVAL, "unknown smoother kind");
+  {
+    const std::string e = sides_error(s->opt, tensor_dim);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+    if (s->opt.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
+  }
   const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
   if (alt && !tensor_dim) return fail(AMG_HIP_EINVAL, ALT_NEEDS_GRID);
   if (s->opt.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
@@ -2425,6 +2496,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   timer.lap(T_IN);
   for (int l = 0; l < n_levels; ++l) {
     Level& L = s->lv[l];
+    if (tensor_dim) L.tsides = (uint32_t)s->opt.natural_sides;
     if (tensor_dim && l + 1 < n_levels) {  // the axes this level coarsens
       L.tmask = tensor_full_mask(tensor_dim);
       if (semi && semi->masks) {
@@ -2661,7 +2733,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       // the matrix-free kernels index lanes with 32 bits (kernels.hip: tensor_grid)
       L.tensor_stencil = s->opt.stencil_transfers && L.n < ((int64_t)1 << 31) - 4;
       if (!L.tensor_stencil) {
-        L.P_csc = tensor_P(tensor_dim, L.dims, L.tmask);
+        L.P_csc = tensor_P(tensor_dim, L.dims, L.tmask, L.tsides);
         L.R_csc = transpose(L.P_csc);
       }
     } else if (n_H < 1) {
@@ -2741,6 +2813,8 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     A_r.val.swap(AH_r.val);
     A_r.n_outer = A_r.n_inner = n_H;
   }
+  // the automatic semi-coarsening rule may have stopped at level 0
+  if (s->opt.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
   if (!dev) {
     compute_bytes(s.get());
     *out = s.release();
@@ -2752,7 +2826,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   // ---- coarsest factor (multigrid.hpp:240-243) ----
   if (!s->opt.window) {
     const int want = s->opt.fast_coarse_solve ? 1 : (s->opt.exact_coarse_solve ? -1 : 0);
-    amg_hip_status r = upload_coarse(s->lv[n_levels - 1].A_csc, want, &s->coarse);
+    amg_hip_status r = upload_coarse(s->lv[n_levels - 1].A_csc, want, &s->coarse, s->opt.singular != 0);
     if (r != AMG_HIP_OK) return r;
   }
   timer.lap(T_BAND);
@@ -3195,6 +3269,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
     if (tensor) {
       L.tdim = dim;
       for (int a = 0; a < 3; ++a) L.dims[a] = tdims[a];
+      L.tsides = (uint32_t)o.natural_sides;
     }
     if (tensor && l + 1 < n_levels) {  // the axes this level coarsens (build_solver's rule)
       L.tmask = tensor_full_mask(dim);
@@ -3359,7 +3434,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
       L.tensor_stencil = true;  // o.stencil_transfers is set and N < 2^28
       L.n_coarse = tdims[0] * tdims[1] * tdims[2];
       bool ok_g = false;
-      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.tmask, L.n_coarse, &next, &ok_g);
+      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.tmask, L.tsides, L.n_coarse, &next, &ok_g);
       if (ge == hipErrorInvalidValue || (ge == hipSuccess && !ok_g)) {
         if (timing) std::fprintf(stderr, "amg_hip device setup: Galerkin product of level %d exceeds %s -> host path\n", l,
                                  ge == hipSuccess ? "the kernel's columns per coarse row" : "int32 indexing");
@@ -3387,6 +3462,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
     cur = std::move(next);
   }
   lap("hierarchy");
+  if (o.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
   {
     const amg_hip_status r = put_rhs(s->lv[0]);
     if (r != AMG_HIP_OK) return r;
@@ -3395,7 +3471,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
   if (!o.window) {
     const int want = o.fast_coarse_solve ? 1 : (o.exact_coarse_solve ? -1 : 0);
     HIP_TRY(s->lv[n_levels - 1].ensure_host_matrix());
-    amg_hip_status r = upload_coarse(s->lv[n_levels - 1].A_csc, want, &s->coarse);
+    amg_hip_status r = upload_coarse(s->lv[n_levels - 1].A_csc, want, &s->coarse, s->opt.singular != 0);
     if (r != AMG_HIP_OK) return r;
   }
   lap("coarse factor");
@@ -3641,6 +3717,8 @@ amg_hip_status enqueue_block_vcycle(amg_hip_solver* s, int kp, bool dry) {
     double* cy = B.cy.as<double>();
     double* cx = B.cx.as<double>();
     BLK(launch_block_columns(kp, C.n, QC.F.as<double>(), cf, true, st));
+    if (K.pin)  // opt.singular: the last entry of every column's right-hand side (launch_coarse)
+      BLK(launch_zero_strided(cf + (C.n - 1), C.n, kp, st));
     const double factor = 16.0 * (double)C.n * (double)std::max<int64_t>(K.w, 1);
     switch (K.kind) {
       case COARSE_SPIKE:
@@ -3890,7 +3968,7 @@ amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
       F32_DO(launch_linear_restrict_f32(L.n, C.n, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
       s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
     } else if (L.tensor_stencil) {
-      F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
+      F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, L.tsides, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
       s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
     } else {
       F32_DO(hipMemsetAsync(QC.u.p, 0, sizeof(float) * (size_t)C.n, st));
@@ -3918,7 +3996,7 @@ amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
       F32_DO(launch_linear_prolong_add_f32(L.n, C.n, QC.u.as<float>(), Q.u.as<float>(), st));
       s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
     } else if (L.tensor_stencil) {
-      F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, QC.u.as<float>(), Q.u.as<float>(), st));
+      F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, L.tsides, QC.u.as<float>(), Q.u.as<float>(), st));
       s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
     } else {
       const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
@@ -4126,6 +4204,12 @@ amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, cons
                       nullptr, opts, out, -1.0, 0, dim, dims, &rule);
 }
 
+amg_hip_status amg_hip_get_natural_sides(const amg_hip_solver* s, int32_t* mask) {
+  if (!s || !mask) return fail(AMG_HIP_EINVAL, "null argument");
+  *mask = (!s->lv.empty() && s->lv[0].tdim) ? (int32_t)s->lv[0].tsides : 0;
+  return AMG_HIP_OK;
+}
+
 amg_hip_status amg_hip_get_level_axes(const amg_hip_solver* s, int32_t level, int32_t* axis_mask) {
   if (!s || !axis_mask) return fail(AMG_HIP_EINVAL, "null argument");
   if (level < 0 || level + 1 >= (int)s->lv.size())
@@ -4176,6 +4260,10 @@ amg_hip_status amg_hip_create_poisson(int32_t dim, int64_t n, int32_t n_levels,
   if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
   *out = nullptr;
   if ((dim != 2 && dim != 3) || n < 1) return fail(AMG_HIP_EINVAL, "dim must be 2 or 3 and n >= 1");
+  if (opts) {
+    const std::string e = sides_error(*opts, 0);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson: " + e);
+  }
   bool unsupported = true;
   amg_hip_status r = build_poisson_device(dim, n, n_levels, opts, out, &unsupported);
   if (r != AMG_HIP_OK || !unsupported) return r;
@@ -4195,6 +4283,10 @@ amg_hip_status amg_hip_create_poisson_tensor(int32_t dim, int64_t n, int32_t n_l
   if (n >= ((int64_t)1 << 31) / n / (dim == 3 ? n : 1))
     return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: the grid has 2^31 points or more");
   if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
+  if (opts) {  // the model problem is Dirichlet on every side
+    const std::string e = sides_error(*opts, 0);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: " + e);
+  }
   if (opts && opts->window)
     return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_tensor: window solvers (opt.window) coarsen the "
                                       "flat index; a full-coarsening hierarchy is not sharded");
@@ -4324,6 +4416,11 @@ static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, in
   }
   // build_solver's option checks, in its words
   if (o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_ALT) return fail(AMG_HIP_EINVAL, "unknown smoother kind");
+  {
+    const std::string se = sides_error(o, dim);
+    if (!se.empty()) return fail(AMG_HIP_EINVAL, se);
+    if (o.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
+  }
   if (o.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
   if (o.smoother == AMG_HIP_SM_CHEBYSHEV) {
     const std::string ce = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
@@ -4417,6 +4514,10 @@ amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t uni
   if (opts) o = *opts;
   else amg_hip_default_options(&o);
   if (o.smoother == AMG_HIP_SM_LINE_ALT) return fail(AMG_HIP_EINVAL, ALT_NEEDS_GRID);
+  {
+    const std::string e = sides_error(o, 0);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_window: " + e);
+  }
   if (o.smoother == AMG_HIP_SM_CHEBYSHEV)
     return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_window: the Chebyshev smoother is not sharded");
   if (o.smoother == AMG_HIP_SM_LINE_JACOBI)
@@ -4731,7 +4832,7 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       if (L.linear && s->opt.stencil_transfers) {
         HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
       } else if (L.tensor_stencil) {
-        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
+        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
       } else {
         HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st));
         const DevCsr& R = L.R_rows;
@@ -4746,7 +4847,7 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       if (L.linear && s->opt.stencil_transfers) {
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
       } else if (L.tensor_stencil) {
-        HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, C.u.as<double>(), L.u.as<double>(), st));
+        HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, C.u.as<double>(), L.u.as<double>(), st));
       } else {
         const DevCsr& P = L.P_rows;
         HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz, P.rowptr(),
@@ -5382,9 +5483,13 @@ amg_hip_status amg_hip_linear_restrict(int64_t n_h, int64_t n_H, const double* r
 
 // the fine grid of a stand-alone tensor transfer: every coarsened axis needs 2 points.  mask < 0:
 // full coarsening (the entry points without a mask)
+// sides: the natural boundary sides of the _bc entry points (0 for the others)
 static amg_hip_status tensor_transfer_args(const char* who, int32_t dim, const int64_t* dims, int64_t mask_in,
-                                           uint32_t* mask, int64_t* n_h, int64_t* n_H) {
+                                           int32_t sides, uint32_t* mask, int64_t* n_h, int64_t* n_H) {
   std::string e = tensor_dims_error(dim, dims);
+  if (e.empty() && (sides < 0 || sides >= (1 << (2 * dim))))
+    e = "`natural_sides` = " + std::to_string(sides) + " has bits other than the " + std::to_string(2 * dim) +
+        " sides of the grid";
   if (e.empty() && mask_in < 0) {
     if (dims[0] < 2 || dims[1] < 2 || (dim == 3 && dims[2] < 2)) e = "an axis of fewer than 2 points cannot be coarsened";
     mask_in = tensor_full_mask(dim);
@@ -5401,53 +5506,63 @@ static amg_hip_status tensor_transfer_args(const char* who, int32_t dim, const i
 }
 
 static amg_hip_status tensor_restrict_host(const char* who, int32_t dim, const int64_t* dims_h, int64_t mask_in,
-                                           const double* r, double* f_H) {
+                                           int32_t sides, const double* r, double* f_H) {
   int64_t n_h = 0, n_H = 0;
   uint32_t mask = 0;
-  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, &mask, &n_h, &n_H);
+  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, sides, &mask, &n_h, &n_H);
   if (st != AMG_HIP_OK) return st;
   if (!r || !f_H) return fail(AMG_HIP_EINVAL, "bad argument");
   if ((st = need_device()) != AMG_HIP_OK) return st;
   DevMem dr, df;
   HIP_TRY(upload(dr, r, (size_t)n_h));
   HIP_TRY(df.alloc(sizeof(double) * n_H));
-  HIP_TRY(launch_tensor_restrict(dim, dims_h, mask, dr.as<double>(), df.as<double>(), nullptr, nullptr));
+  HIP_TRY(launch_tensor_restrict(dim, dims_h, mask, (uint32_t)sides, dr.as<double>(), df.as<double>(), nullptr, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(f_H, df.p, sizeof(double) * n_H, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
 }
 amg_hip_status amg_hip_tensor_restrict(int32_t dim, const int64_t* dims_h, const double* r, double* f_H) {
-  return tensor_restrict_host("amg_hip_tensor_restrict", dim, dims_h, -1, r, f_H);
+  return tensor_restrict_host("amg_hip_tensor_restrict", dim, dims_h, -1, 0, r, f_H);
 }
 amg_hip_status amg_hip_tensor_restrict_axes(int32_t dim, const int64_t* dims_h, int32_t axis_mask, const double* r,
                                             double* f_H) {
-  return tensor_restrict_host("amg_hip_tensor_restrict_axes", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, r, f_H);
+  return tensor_restrict_host("amg_hip_tensor_restrict_axes", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, 0, r, f_H);
+}
+amg_hip_status amg_hip_tensor_restrict_bc(int32_t dim, const int64_t* dims_h, int32_t axis_mask, int32_t natural_sides,
+                                          const double* r, double* f_H) {
+  return tensor_restrict_host("amg_hip_tensor_restrict_bc", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, natural_sides,
+                              r, f_H);
 }
 
 static amg_hip_status tensor_prolong_add_host(const char* who, int32_t dim, const int64_t* dims_h, int64_t mask_in,
-                                              const double* u_H, double* u_h) {
+                                              int32_t sides, const double* u_H, double* u_h) {
   int64_t n_h = 0, n_H = 0;
   uint32_t mask = 0;
-  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, &mask, &n_h, &n_H);
+  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, sides, &mask, &n_h, &n_H);
   if (st != AMG_HIP_OK) return st;
   if (!u_H || !u_h) return fail(AMG_HIP_EINVAL, "bad argument");
   if ((st = need_device()) != AMG_HIP_OK) return st;
   DevMem dH, dh;
   HIP_TRY(upload(dH, u_H, (size_t)n_H));
   HIP_TRY(upload(dh, u_h, (size_t)n_h));
-  HIP_TRY(launch_tensor_prolong_add(dim, dims_h, mask, dH.as<double>(), dh.as<double>(), nullptr));
+  HIP_TRY(launch_tensor_prolong_add(dim, dims_h, mask, (uint32_t)sides, dH.as<double>(), dh.as<double>(), nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(u_h, dh.p, sizeof(double) * n_h, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
 }
 amg_hip_status amg_hip_tensor_prolong_add(int32_t dim, const int64_t* dims_h, const double* u_H,
                                           double* u_h) {
-  return tensor_prolong_add_host("amg_hip_tensor_prolong_add", dim, dims_h, -1, u_H, u_h);
+  return tensor_prolong_add_host("amg_hip_tensor_prolong_add", dim, dims_h, -1, 0, u_H, u_h);
 }
 amg_hip_status amg_hip_tensor_prolong_add_axes(int32_t dim, const int64_t* dims_h, int32_t axis_mask,
                                                const double* u_H, double* u_h) {
-  return tensor_prolong_add_host("amg_hip_tensor_prolong_add_axes", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, u_H,
-                                 u_h);
+  return tensor_prolong_add_host("amg_hip_tensor_prolong_add_axes", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, 0,
+                                 u_H, u_h);
+}
+amg_hip_status amg_hip_tensor_prolong_add_bc(int32_t dim, const int64_t* dims_h, int32_t axis_mask,
+                                             int32_t natural_sides, const double* u_H, double* u_h) {
+  return tensor_prolong_add_host("amg_hip_tensor_prolong_add_bc", dim, dims_h, axis_mask < 0 ? 8 : axis_mask,
+                                 natural_sides, u_H, u_h);
 }
 
 amg_hip_status amg_hip_linear_prolong_add(int64_t n_h, int64_t n_H, const double* u_H,
@@ -5499,7 +5614,7 @@ amg_hip_status amg_hip_coarse_solve(int64_t n, const int32_t* colptr, const int3
   std::string v = validate(A, "A");
   if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
   CoarseOnDev C;
-  if ((st = upload_coarse(A, -1, &C)) != AMG_HIP_OK) return st;  // bit-exact forms only
+  if ((st = upload_coarse(A, -1, &C, false)) != AMG_HIP_OK) return st;  // bit-exact forms only
   if (halfbw) *halfbw = C.w;
   DevMem df, dy, dx;
   HIP_TRY(upload(df, f, (size_t)n));

@@ -201,6 +201,18 @@ typedef struct {
                               sigma = theta / delta, rho_0 = 1 / sigma.  A zero diagonal is
                               refused at setup (AMG_HIP_EINVAL).                        */
   double cheb_upper;       /* AMG_HIP_SM_CHEBYSHEV: upper end factor (default 1.0)    */
+  int32_t natural_sides;   /* tensor constructors only ("natural boundary sides" below): 6-bit
+                              mask of the sides of the box on which the operator carries NO
+                              Dirichlet condition (Neumann, Robin, symmetry plane, outflow).
+                              Bit 2a = the low side of axis a (x = 0, y = 1, z = 2), bit 2a + 1
+                              its high side.  Default 0 = every side Dirichlet: the hierarchy
+                              of the earlier releases bit for bit.  Every other constructor
+                              refuses a non-zero value (AMG_HIP_EINVAL).                     */
+  int32_t singular;        /* 1: the caller states that A is singular with the constant vector as
+                              its null space (pure Neumann); needs every side of natural_sides
+                              set.  The coarsest solve then pins its last unknown to 0.  Not
+                              verified -- the caller's statement, as symmetry is for
+                              amg_hip_pcg.  Default 0.                                        */
 } amg_hip_options;
 
 typedef struct amg_hip_solver amg_hip_solver; /* opaque; owns device memory    */
@@ -364,6 +376,41 @@ amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, cons
                                           const int32_t* axis_masks /* n_levels - 1, or NULL */,
                                           double theta, int64_t min_coarse,
                                           const amg_hip_options* opts, amg_hip_solver** out);
+/* Natural boundary sides (opts->natural_sides, opts->singular; honoured by amg_hip_create_tensor,
+ * _tensor_semi, _tensor_dev and _tensor_semi_dev).  P1(m) interpolates fine point 0 -- and fine point
+ * m - 1 of an odd m -- from its one coarse neighbour with weight 0.5: linear interpolation towards a
+ * zero boundary value, which is wrong on a side without a Dirichlet condition (P 1 != 1 there, so
+ * the coarse grids cannot correct smooth error next to that side and the iteration count grows with
+ * the grid).  P1N(m; lo, hi) is P1(m) with entry (0, 0) = 1.0 when `lo` is set and, for odd m, entry
+ * (m - 1, m / 2 - 1) = 1.0 when `hi` is set; for even m `hi` changes nothing, fine point m - 1 being
+ * a coarse point.  The pattern does not change and every weight is still a product of powers of
+ * two, so all bit-for-bit statements of the tensor family carry over.  A level uses P_l = P_z (x)
+ * P_y (x) P_x with P1N on the coarsened axes (an axis outside the level's mask keeps the identity),
+ * R_l = P_l^T, A_{l+1} = R_l (A_l P_l) in the same summation order; the same side mask holds on every
+ * level.  The matrix-free transfers, K-TensorGalerkin, the CSR transfers of stencil_transfers = 0,
+ * the float cycle and the block cycle all honour it.
+ * Set a bit for every side on which the discrete operator has no Dirichlet term (its boundary rows
+ * sum to zero there as the interior rows do); leave it clear on Dirichlet sides.
+ * opts->singular = 1 (needs all 2 dim bits): the constants are then in the null space of every
+ * Galerkin operator, and the coarsest solve -- every kind, also in the float and the block cycle --
+ * PINS THE LAST UNKNOWN: with n the coarsest size, x[n-1] = +0.0 and x[0 : n-1] solves the leading
+ * principal (n-1) x (n-1) block by the same banded LDL^T (SPD when A is semidefinite with the
+ * constants as its only null vector; the coarse right-hand side is consistent up to rounding because
+ * 1^T R r = 1^T r, so the dropped equation holds by itself).  The last entry of the coarsest
+ * right-hand side is zeroed on the stream just ahead of the solve and reads 0 after a cycle;
+ * amg_hip_get_level_matrix still returns the true (singular) coarsest operator.  No mean projection is
+ * applied anywhere: a cycle, amg_hip_pcg and the other solvers return a solution up to an additive
+ * constant, and the right-hand side has to be consistent (zero mean for a symmetric A).
+ * AMG_HIP_EINVAL before the device is touched, the field named in the message: natural_sides negative
+ * or with bits at or above 2 dim; natural_sides != 0 on amg_hip_create, _custom, _rs, _poisson,
+ * _poisson_window and _poisson_tensor (its model problem is Dirichlet); singular outside {0, 1};
+ * singular = 1 unless all 2 dim bits of natural_sides are set; singular = 1 with fewer than 2 levels
+ * (asked for, or where the automatic semi-coarsening rule stops at level 0): the coarsest right-hand
+ * side would be the caller's own b.  K-Tail (amg_hip_set_tail_fusion, off by default) is not taken
+ * on a singular solver; its cycles run the unfused launches.                                      */
+/* Side mask of a solver (opts->natural_sides of a tensor constructor); 0 on every other solver.  Also
+ * on host_only solvers.                                                                          */
+amg_hip_status amg_hip_get_natural_sides(const amg_hip_solver* s, int32_t* mask);
 /* Axis mask of the transfers between `level` and `level` + 1 of a solver made by one of the tensor
  * constructors (the full-coarsening ones report 3 in 2-D and 7 in 3-D); also on host_only solvers.
  * AMG_HIP_EINVAL on the coarsest level and for every other solver.                              */
@@ -884,6 +931,14 @@ amg_hip_status amg_hip_tensor_restrict_axes(int32_t dim, const int64_t* dims_h /
                                             const double* r, double* f_H);
 amg_hip_status amg_hip_tensor_prolong_add_axes(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
                                                const double* u_H, double* u_h);
+/* The same two transfers with an axis mask and the side mask of opts->natural_sides (P1N on the
+ * coarsened axes): bit-identical to amg_hip_spmv with the R / P of amg_hip_get_transfer of a solver
+ * made with that side mask.  The argument checks of the _axes forms, plus AMG_HIP_EINVAL for a
+ * negative `natural_sides` or bits at or above 2 dim.  natural_sides = 0: the _axes forms.        */
+amg_hip_status amg_hip_tensor_restrict_bc(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
+                                          int32_t natural_sides, const double* r, double* f_H);
+amg_hip_status amg_hip_tensor_prolong_add_bc(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
+                                             int32_t natural_sides, const double* u_H, double* u_h);
 /* AMG::rss(A, u, b), common.hpp:17-27. */
 amg_hip_status amg_hip_rss_host(int64_t n, const int32_t* colptr,
                                 const int32_t* rowind, const double* val,

@@ -13,6 +13,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py alt10 <nx> <ny> <levels>                    ten cycles of the alternating line smoother (kernel traces)
        config_bench.py mixed [<nx> <ny> <nz> <levels>]             amg_hip_pcg and amg_hip_pcg_mixed (single-precision V-cycle) alternating on a variable-coefficient operator, true Jacobi 2+2 and Chebyshev(2) 1+1
        config_bench.py semi [<nx> <ny> <nz> <eps_x> <eps_y> <eps_z>] PCG to 1e-8 on an axis-scaled diffusion operator: full coarsening + Jacobi, semi-coarsening + Jacobi, full coarsening + alternating lines, semi-coarsening + amg_hip_pcg_mixed (legs alternate)
+       config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -230,11 +231,13 @@ def run_tensor_setup(dim, n, L, reps=3):
           f"ratio {best['host'] / best['device']:.1f}", flush=True)
 
 
-def torch_diffusion(dims, seed=1, eps=None, shift=1.0):
+def torch_diffusion(dims, seed=1, eps=None, shift=1.0, dirichlet=None):
     """-div(kappa grad u) + shift u on the grid `dims` (x fastest), kappa uniform in [1, 10] per face,
     assembled on the GPU with torch: (crow int32, col int32, val float64, b float64) device tensors in
     CSR with ascending columns.  Both triangles hold the same bits, so the arrays are the CSC arrays as
-    well.  eps: a factor per axis on that axis's kappa (the scaled operator of the semi mode)."""
+    well.  eps: a factor per axis on that axis's kappa (the scaled operator of the semi mode).
+    dirichlet: mask of the sides that carry the Dirichlet face term (bit 2a = low side of axis a, bit
+    2a + 1 = high side; None = every side); the other sides are natural (no face term)."""
     import torch
     dev = torch.device("cuda")
     g = torch.Generator(device=dev)
@@ -253,8 +256,10 @@ def torch_diffusion(dims, seed=1, eps=None, shift=1.0):
     diag = torch.full((n,), float(shift), dtype=torch.float64, device=dev)
     for a in range(dim):
         lo_ok, hi_ok = coord[a] > 0, coord[a] < ext[a] - 1
-        k_lo = torch.where(lo_ok, torch.roll(kap[a], stride[a]), torch.full_like(kap[a], 5.5))  # Dirichlet faces: 5.5
-        k_hi = torch.where(hi_ok, kap[a], torch.full_like(kap[a], 5.5))
+        f_lo = 5.5 if dirichlet is None or (dirichlet >> (2 * a)) & 1 else 0.0  # Dirichlet faces: 5.5
+        f_hi = 5.5 if dirichlet is None or (dirichlet >> (2 * a + 1)) & 1 else 0.0
+        k_lo = torch.where(lo_ok, torch.roll(kap[a], stride[a]), torch.full_like(kap[a], f_lo))
+        k_hi = torch.where(hi_ok, kap[a], torch.full_like(kap[a], f_hi))
         if eps is not None:
             k_lo, k_hi = k_lo * float(eps[a]), k_hi * float(eps[a])
         diag = diag + k_lo + k_hi
@@ -545,6 +550,71 @@ def run_semi(dims, eps, reps=3, rtol=1e-8, max_iters=300, theta=0.5, min_coarse=
         mg.close()
 
 
+def run_natural(dims, reps=3, rtol=1e-8, max_iters=300):
+    """PCG from x = 0 to `rtol` on the diffusion operator of tensor-user-setup without mass term, full
+    coarsening, true Jacobi 2+2, set up on the device (tensor_dev): once without a Dirichlet side (A is
+    singular, b has zero mean) and once with Dirichlet on x-low only.  Two legs per operator alternate in
+    one process, `reps` repeats: natural_sides = 0 (the hierarchy of the Dirichlet box) and the proper
+    side mask (with singular = 1 on the first operator).  Per run: iterations and wall ms of amg_hip_pcg
+    itself (it synchronises before it returns); the copy of x to the host, whose time scatters by more
+    than a short solve takes, stays outside the clock."""
+    import ctypes
+    import torch
+
+    def solve(mg):
+        it, rel = ctypes.c_int64(0), ctypes.c_double(0)
+        st = amg.lib().amg_hip_pcg(mg._h, rtol, max_iters, ctypes.byref(it), ctypes.byref(rel))
+        assert st == 0, amg.lib().amg_hip_last_error().decode()
+        return it.value, rel.value
+
+    dim = len(dims)
+    every = (1 << (2 * dim)) - 1
+    L = full_levels(dims)
+    tag = " x ".join(str(d) for d in dims)
+    for what, dirichlet in (("no Dirichlet side", 0), ("Dirichlet on x-low", 1)):
+        crow, col, val, b = torch_diffusion(dims, shift=0.0, dirichlet=dirichlet)
+        if not dirichlet:
+            b = b - b.mean()
+        torch.cuda.synchronize()
+        sides = every & ~dirichlet
+        legs = {}
+        for name, kw in (("natural_sides 0", dict()),
+                         (f"natural_sides {sides}", dict(natural_sides=sides, singular=not dirichlet))):
+            t0 = time.perf_counter()
+            mg = amg.Multigrid.tensor_dev(crow, col, val, b, dims, L, **TENSOR_KW["jacobi"], **kw)
+            mg.sync()
+            dt = time.perf_counter() - t0
+            mg.vcycle(3)
+            mg.sync()
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            mg.vcycle(10)
+            mg.sync()
+            cyc = (time.perf_counter() - t0) / 10
+            print(f"natural {tag}, {what}, {name}: setup {dt:.2f} s (setup_on_device {mg.setup_on_device}), "
+                  f"{mg.n_levels} levels, coarsest {mg.get_n_dofs(mg.n_levels - 1)} dofs "
+                  f"({mg.coarse_solve_kind().split(' ')[0]}), {cyc * 1e3:.3f} ms/V-cycle", flush=True)
+            mg.zero_vec(0, "u")
+            solve(mg)  # first call: work vectors, captured graph
+            legs[name] = mg
+        best = {}
+        for rep_ in range(reps):
+            for name, mg in legs.items():
+                mg.zero_vec(0, "u")
+                mg.sync()
+                t0 = time.perf_counter()
+                it, rel = solve(mg)
+                dt = time.perf_counter() - t0
+                best[name] = min(best.get(name, (it, dt)), (it, dt), key=lambda v: v[1])
+                print(f"natural {tag}, {what}, {name} rep {rep_}: {it} iterations, {dt * 1e3:.2f} ms to {rtol:g} "
+                      f"(relres {rel:.2e}, {'reached' if rel <= rtol else 'NOT reached: capped'})", flush=True)
+        print(f"natural {tag}, {what}: best to {rtol:g}: " +
+              ", ".join(f"{k} {v[0]} iterations {v[1] * 1e3:.2f} ms" for k, v in best.items()), flush=True)
+        for mg in legs.values():
+            mg.close()
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -679,6 +749,14 @@ elif len(sys.argv) > 1 and sys.argv[1] == "semi":
     else:
         run_semi((4096, 1024), (1.0, 1e-2))
         run_semi((256, 256, 256), (1.0, 1.0, 1e-2))
+elif len(sys.argv) > 1 and sys.argv[1] == "natural":
+    # profiles/natural_config_bench.txt
+    if len(sys.argv) > 4:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_natural(d if d[2] > 1 else d[:2])
+    else:
+        run_natural((4096, 1024))
+        run_natural((256, 256, 256))
 elif len(sys.argv) > 3 and sys.argv[1] == "tensor10":
     mg = amg.Multigrid.poisson_tensor(int(sys.argv[2]), int(sys.argv[3]), stencil_transfers=len(sys.argv) < 5,
                                       **TENSOR_KW["jacobi"])
