@@ -699,12 +699,10 @@ struct DictEntry {
   int32_t off8;  // BYTE offset of the column from the row's diagonal column
   int32_t pad[3];
 };
+// entry threadIdx.x from its pair (v, o), already in registers
 template <int MODE>
-__device__ __forceinline__ void dict_stage_table(DictEntry* tab, const int32_t* __restrict__ doff,
-                                                 const double* __restrict__ dval, int ntab) {
+__device__ __forceinline__ void dict_put_table(DictEntry* tab, double v, int32_t o, int ntab) {
   const int t = threadIdx.x;  // 256 threads, 256 entries
-  const double v = t < ntab ? dval[t] : 0.0;
-  const int32_t o = t < ntab ? doff[t] : 0;
   DictEntry e;
   constexpr bool split = mode_jac(MODE) || MODE == CSR_GS;
   e.a = (split && o == 0) ? 0.0 : v;
@@ -712,6 +710,14 @@ __device__ __forceinline__ void dict_stage_table(DictEntry* tab, const int32_t* 
   e.off8 = o * 8;
   e.pad[0] = e.pad[1] = e.pad[2] = 0;
   tab[t] = e;
+}
+template <int MODE>
+__device__ __forceinline__ void dict_stage_table(DictEntry* tab, const int32_t* __restrict__ doff,
+                                                 const double* __restrict__ dval, int ntab) {
+  const int t = threadIdx.x;
+  const double v = t < ntab ? dval[t] : 0.0;
+  const int32_t o = t < ntab ? doff[t] : 0;
+  dict_put_table<MODE>(tab, v, o, ntab);
 }
 // decode + gather + row arithmetic of the R rows of one lane.  The kernels are issue
 // bound as much as bandwidth bound (a wave64 VALU instruction occupies its SIMD for 4
@@ -1013,6 +1019,78 @@ __device__ __forceinline__ void dict_prolong_tail(int tile, int n, const double*
     }
   }
 }
+// The same two tails with their global operand already in registers (the pair kernels issue
+// every load at kernel entry): *_pre is the load, under the guards of the tail that uses it.
+// R = 2: a lane owns one coarse row of the restriction, two coarse points of the prolongation.
+__device__ __forceinline__ double dict_restrict_pre(int tile, int nH, const double* __restrict__ diagH) {
+  const int q = threadIdx.x, j = tile * 255 + q;
+  return (q < 255 && j < nH) ? diagH[j] : 0.0;
+}
+__device__ __forceinline__ void dict_restrict_tail(int tile, int n, const double* rs, int nH,
+                                                   double* __restrict__ fH, double dH,
+                                                   double* __restrict__ uH1, double omega) {
+  const int q = threadIdx.x, j = tile * 255 + q;
+  if (q >= 255 || j >= nH) return;
+  const int64_t i = 2 * (int64_t)j;  // linear_restrict_kernel, same guards and order
+  double sum = 0.0;
+  if (i < n) sum += 0.5 * rs[2 * q];
+  if (i + 1 < n) sum += 1.0 * rs[2 * q + 1];
+  if (i + 2 < n) sum += 0.5 * rs[2 * q + 2];
+  fH[j] = sum;
+  const double xi = 0.0, acc = 0.0;  // jacobi_from_zero_kernel
+  const double d = dH;
+  uH1[j] = (d == 0.0) ? xi : xi + omega * ((sum - acc) / d - xi);
+}
+typedef double pair_f64x2 __attribute__((ext_vector_type(2)));
+// (lone: the last entry of uh_in when n_h is odd -- at most one of a lane's two coarse points has
+// it -- in a register of its own: loaded into pre[r].x, the two forms share registers and the
+// compiler drains every load in flight between them)
+__device__ __forceinline__ void dict_prolong_pre(int tile, int n, int n_h, const double* uh_in,
+                                                 pair_f64x2 (&pre)[2], double& lone) {
+  bool two[2], one[2];
+  int64_t i[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int q = (int)threadIdx.x * 2 + r;
+    const int j = tile * 510 + q;
+    const bool on = !((q == 0 && tile != 0) || q > 510 || j > n);
+    i[r] = 2 * (int64_t)j;
+    two[r] = on && i[r] + 1 < n_h;
+    one[r] = on && i[r] + 1 == n_h;
+    pre[r].x = pre[r].y = 0.0;
+  }
+  lone = 0.0;
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+    if (two[r]) pre[r] = *reinterpret_cast<const pair_f64x2*>(uh_in + i[r]);
+  if (one[0] || one[1]) lone = uh_in[n_h - 1];
+}
+__device__ __forceinline__ void dict_prolong_tail(int tile, int n, const double* rs, int n_h,
+                                                  const pair_f64x2 (&pre)[2], double lone,
+                                                  double* uh_out) {
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int q = (int)threadIdx.x * 2 + r;
+    const int j = tile * 510 + q;
+    if ((q == 0 && tile != 0) || q > 510 || j > n) continue;
+    double t0 = 0.0, t1 = 0.0;
+    const double b = (j < n) ? rs[q] : 0.0;
+    if (j >= 1 && j - 1 < n) t0 += 0.5 * rs[q - 1];
+    if (j < n) {
+      t0 += 0.5 * b;
+      t1 += 1.0 * b;
+    }
+    const int64_t i = 2 * (int64_t)j;
+    if (i + 1 < n_h) {
+      pair_f64x2 u = pre[r];
+      u.x = u.x + t0;
+      u.y = u.y + t1;
+      *reinterpret_cast<pair_f64x2*>(uh_out + i) = u;
+    } else if (i < n_h) {
+      uh_out[i] = lone + t0;
+    }
+  }
+}
 template <int WORDS, int UN, bool NT, int R>
 __global__ __launch_bounds__(256) void dict_resid_restrict_kernel(
     int n, const uint64_t* __restrict__ codes, const uint8_t* __restrict__ rtype,
@@ -1094,29 +1172,189 @@ __global__ __launch_bounds__(256) void dict_jacobi_prolong_kernel(
 //   up:   sweep + (sweep + prolongation into the finer level)     [dict_pair_up_kernel]
 // Same row arithmetic (dict_rows) and the same tails, so the V-cycle stays bit-identical.
 // R = 2 rows per lane, plain loads/stores.  w0 = tile start - hbw (hbw even >= hb).
+//
+// Memory phase.  Every operand of a tile is known at kernel entry, so the workgroup issues ALL its
+// global loads there, waits once, and afterwards touches global memory only to store:
+//   the table entries, the window of `a` the first sweep gathers from (rows [w0 - hbw,
+//   w0 + W + hbw), W = 512 + 2 hbw; 0.0 outside the matrix), f and the row types (or the code
+//   words) of the W window rows -> LDS;  the operand of the tail (coarse diagonal / the fine u
+//   the prolongation adds to) -> registers.
+// Both sweeps then gather from LDS (aw, then uw) and read f / types / codes from LDS: one global
+// round trip per launch on levels whose work is a few microseconds (gathering the first sweep from
+// global memory behind the staged tables, fetching f and the types per step and loading the tail's
+// operand at the end were five to seven dependent ones: DESIGN.md section 4).
 constexpr int PAIR_HB = 66;                       // largest half-window, in rows
-constexpr int PAIR_W = 512 + 2 * PAIR_HB;         // window capacity
+constexpr int PAIR_W = 512 + 2 * PAIR_HB;         // window capacity: rows the first sweep forms
+constexpr int PAIR_AW = PAIR_W + 2 * PAIR_HB;     // rows of `a` under them
+constexpr int PAIR_AP = (PAIR_AW / 2 + 255) / 256;  // passes of 256 lanes x 2 rows over aw
+static_assert(PAIR_W <= 1024 && PAIR_HB % 2 == 0, "two passes of 512 rows cover the window");
 
-// first stage: Jacobi sweep of the window rows [w0, w0 + 512 + 2 hbw) from global `a` into
-// uw (0.0 for rows outside the matrix); rows of the tile are also stored to u_out if given
+typedef uint64_t pair_u64x2 __attribute__((ext_vector_type(2)));
+// What one lane has in flight between kernel entry and the first barrier.  The loads land in
+// registers that nothing writes again before the commit (defaults first, then the loads under
+// their guards), so that no wait sits between two loads.
+template <int WORDS>
+struct PairLoads {
+  double tv;        // table entry threadIdx.x
+  int32_t to;
+  uint64_t rw[WORDS];
+  pair_f64x2 a[PAIR_AP];       // rows w0 - hbw + 2 (k 256 + t), + 1 of a
+  // window rows 2 (k 256 + t), + 1: f, the two row types or the code words (words 2 j, 2 j + 1 of
+  // the 2 WORDS).  *l: the same for the matrix's last row when it has no partner.
+  pair_f64x2 f[2];
+  double fl[2];
+  uint32_t ty[2], tl[2];
+  pair_u64x2 c[2][WORDS], cl[2];
+};
+// TYPES: the matrix has row types (the caller branches once, so that each form is straight code
+// and leaves the other form's registers alone).
+template <int WORDS, bool TYPES>
+__device__ __forceinline__ void dict_pair_issue(PairLoads<WORDS>& g, int n, int w0, int hbw,
+                                                const uint64_t* __restrict__ codes,
+                                                const uint8_t* __restrict__ rtype,
+                                                const uint64_t* __restrict__ rwords,
+                                                const int32_t* __restrict__ doff,
+                                                const double* __restrict__ dval, int ntab,
+                                                const double* a, const double* __restrict__ f) {
+  const int t = threadIdx.x;
+  const int W = 512 + 2 * hbw, AW = W + 2 * hbw;
+  g.tv = t < ntab ? dval[t] : 0.0;
+  g.to = t < ntab ? doff[t] : 0;
+#pragma unroll
+  for (int k = 0; k < WORDS; ++k) g.rw[k] = TYPES ? rwords[t * WORDS + k] : 0;
+#pragma unroll
+  for (int k = 0; k < PAIR_AP; ++k) {
+    const int idx = (k * 256 + t) * 2;
+    const int row = w0 - hbw + idx;  // even: a pair is either entirely before row 0 or not at all
+    g.a[k].x = g.a[k].y = 0.0;
+    if (idx < AW && row >= 0) {
+      if (row + 1 < n) g.a[k] = *reinterpret_cast<const pair_f64x2*>(a + row);
+      else if (row < n) g.a[k].x = a[row];
+    }
+  }
+  // rows before the matrix (first tile), past it or past the window: empty rows, no loads
+  bool both[2], lone[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int lw = (k * 256 + t) * 2, row0 = w0 + lw;
+    const bool inside = row0 >= 0 && lw < W;
+    both[k] = inside && row0 + 1 < n;
+    lone[k] = inside && row0 + 1 == n;
+    g.f[k].x = g.f[k].y = g.fl[k] = 0.0;
+    if (both[k]) g.f[k] = *reinterpret_cast<const pair_f64x2*>(f + row0);
+    if (lone[k]) g.fl[k] = f[row0];
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int row0 = w0 + (k * 256 + t) * 2;
+    if (TYPES) {
+      g.ty[k] = 0xFFFFu;
+      g.tl[k] = 0xFFu;
+      if (both[k]) g.ty[k] = *reinterpret_cast<const uint16_t*>(rtype + row0);
+      if (lone[k]) g.tl[k] = rtype[row0];
+    } else {
+      g.cl[k].x = g.cl[k].y = ~(uint64_t)0;
+#pragma unroll
+      for (int j = 0; j < WORDS; ++j) g.c[k][j].x = g.c[k][j].y = ~(uint64_t)0;
+      const uint64_t* cp = codes + (int64_t)row0 * WORDS;
+      if (both[k]) {
+#pragma unroll
+        for (int j = 0; j < WORDS; ++j) g.c[k][j] = reinterpret_cast<const pair_u64x2*>(cp)[j];
+      }
+      if (lone[k]) {
+        if (WORDS == 2) g.cl[k] = *reinterpret_cast<const pair_u64x2*>(cp);
+        else g.cl[k].x = cp[0];
+      }
+    }
+  }
+}
+// wc: the word table of the row types when the matrix has them, else the code words of the window
+template <int WORDS, bool TYPES>
+__device__ __forceinline__ void dict_pair_commit(const PairLoads<WORDS>& g, int n, int w0, int hbw,
+                                                 uint64_t* wc, uint16_t* tw, double* aw,
+                                                 double* fw) {
+  const int t = threadIdx.x;
+  const int W = 512 + 2 * hbw, AW = W + 2 * hbw;
+  if (TYPES) {
+#pragma unroll
+    for (int k = 0; k < WORDS; ++k) wc[t * WORDS + k] = g.rw[k];
+  }
+#pragma unroll
+  for (int k = 0; k < PAIR_AP; ++k) {
+    const int idx = (k * 256 + t) * 2;
+    if (idx < AW) *reinterpret_cast<pair_f64x2*>(aw + idx) = g.a[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int lw = (k * 256 + t) * 2;
+    if (lw >= W) continue;
+    const bool both = w0 + lw >= 0 && w0 + lw + 1 < n;  // else: the lone last row, or no row at all
+    pair_f64x2 fv = g.f[k];
+    fv.x = both ? fv.x : g.fl[k];
+    *reinterpret_cast<pair_f64x2*>(fw + lw) = fv;
+    if (TYPES) {
+      // (the empty asm keeps the OR here: formed right behind its load, in the one wave that holds
+      // the matrix's last row, it would put a wait between the loads.  That rests on the compiler's
+      // scheduling -- ROCm 7.2, AMD clang 22 -- and tools/pair_loads_check.py shows it in the assembly.)
+      uint32_t tl = g.tl[k];
+      asm volatile("" : "+v"(tl));
+      tw[lw >> 1] = (uint16_t)(both ? g.ty[k] : (tl | 0xFF00u));
+    } else {
+      pair_u64x2* wp = reinterpret_cast<pair_u64x2*>(wc + lw * WORDS);
+      wp[0] = both ? g.c[k][0] : g.cl[k];
+      if (WORDS == 2) wp[1] = g.c[k][WORDS - 1];
+    }
+  }
+}
+// the stream of window rows lw, lw + 1 (matrix rows row0, row0 + 1) from LDS; xi is the caller's
+template <int WORDS>
+__device__ __forceinline__ void dict_pair_stream(DictStream<WORDS, 2>& s, int lw, int W, int row0, int n,
+                                                 bool types, const uint64_t* wc, const uint16_t* tw,
+                                                 const double* fw) {
+  const bool inside = row0 >= 0 && lw < W;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    s.live[r] = inside && row0 + r < n;
+    s.cw[r][0] = s.cw[r][1] = ~(uint64_t)0;
+    s.fi[r] = s.xi[r] = s.di[r] = 0.0;
+  }
+  s.ty = 0xFFFFu;
+  if (lw < W) {  // rows outside the matrix were committed as empty rows
+    const pair_f64x2 fv = *reinterpret_cast<const pair_f64x2*>(fw + lw);
+    s.fi[0] = fv.x; s.fi[1] = fv.y;
+    if (types) {
+      s.ty = tw[lw >> 1];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int j = 0; j < WORDS; ++j) s.cw[r][j] = wc[(lw + r) * WORDS + j];
+    }
+  }
+}
+
+// first stage: Jacobi sweep of the window rows [w0, w0 + 512 + 2 hbw) from the LDS copy of `a`
+// (aw[i] = a[w0 - hbw + i]) into uw (0.0 for rows outside the matrix); rows of the tile are also
+// stored to u_out if given.  A row that is not live has all codes 0xFF: it gathers aw[0].
 template <int WORDS, int UN>
-__device__ __forceinline__ void dict_pair_stage1(int n, int w0, int hbw, const uint64_t* codes,
-                                                 const uint8_t* rtype, const DictEntry* tabJ,
-                                                 const uint64_t* wtab, const double* a,
-                                                 const double* f, double omega, double* uw,
+__device__ __forceinline__ void dict_pair_stage1(int n, int w0, int hbw, bool types,
+                                                 const DictEntry* tabJ, const uint64_t* wc,
+                                                 const uint16_t* tw, const double* aw,
+                                                 const double* fw, double omega, double* uw,
                                                  double* u_out) {
   const int W = 512 + 2 * hbw;
   for (int base = 0; base < W; base += 512) {  // 2 passes, the second one over the 2 hbw rows left
     const int lw = base + (int)threadIdx.x * 2;  // index in the window
     const int row0 = w0 + lw;
     DictStream<WORDS, 2> s;
-    // rows before the matrix (first tile) or past the window: an empty stream, no loads.
-    // (row0 is even, so a pair is either entirely before row 0 or not at all.)
-    const bool inside = row0 >= 0 && lw < W;
-    dict_fetch<CSR_JACOBI, WORDS, false, 2>(s, inside ? row0 : 0, inside ? n : 0, codes, rtype, f, a, 0);
-    if (rtype) dict_expand<WORDS, 2>(s, wtab);
+    dict_pair_stream<WORDS>(s, lw, W, row0, n, types, wc, tw, fw);
+    if (lw < W) {
+      s.xi[0] = aw[lw + hbw];
+      s.xi[1] = aw[lw + hbw + 1];
+    }
+    if (types) dict_expand<WORDS, 2>(s, wc);
     double res[2];
-    dict_rows<CSR_JACOBI, WORDS, UN, 2>(s, row0, tabJ, a, omega, 0, res);
+    dict_rows<CSR_JACOBI, WORDS, UN, 2>(s, lw + hbw, tabJ, aw, omega, 0, res);
     if (lw < W) {
       uw[lw] = s.live[0] ? res[0] : 0.0;
       uw[lw + 1] = s.live[1] ? res[1] : 0.0;
@@ -1134,28 +1372,37 @@ __global__ __launch_bounds__(256) void dict_pair_down_kernel(
     int xcd_map) {
   __shared__ DictEntry tabJ[256];
   __shared__ DictEntry tabR[256];
-  __shared__ uint64_t wtab[256 * WORDS];
+  __shared__ __attribute__((aligned(16))) uint64_t wc[PAIR_W * WORDS];
+  __shared__ uint16_t tw[PAIR_W / 2];
+  __shared__ __attribute__((aligned(16))) double aw[PAIR_AW];
+  __shared__ __attribute__((aligned(16))) double fw[PAIR_W];
   __shared__ double uw[PAIR_W];
   __shared__ double rs[512];
   const int tile = xcd_tile(blockIdx.x, gridDim.x, xcd_map);
-  const int t0 = tile * 510, w0 = t0 - hbw;
-  dict_stage_table<CSR_JACOBI>(tabJ, doff, dval, ntab);
-  dict_stage_table<CSR_RESID>(tabR, doff, dval, ntab);
-  if (rtype) dict_stage_words<WORDS>(wtab, rwords);
+  const int t0 = tile * 510, w0 = t0 - hbw, W = 512 + 2 * hbw;
+  const bool types = rtype != nullptr;
+  PairLoads<WORDS> g;
+  if (types) dict_pair_issue<WORDS, true>(g, n, w0, hbw, codes, rtype, rwords, doff, dval, ntab, a, f);
+  else dict_pair_issue<WORDS, false>(g, n, w0, hbw, codes, rtype, rwords, doff, dval, ntab, a, f);
+  const double dH = dict_restrict_pre(tile, nH, diagH);
+  dict_put_table<CSR_JACOBI>(tabJ, g.tv, g.to, ntab);
+  dict_put_table<CSR_RESID>(tabR, g.tv, g.to, ntab);
+  if (types) dict_pair_commit<WORDS, true>(g, n, w0, hbw, wc, tw, aw, fw);
+  else dict_pair_commit<WORDS, false>(g, n, w0, hbw, wc, tw, aw, fw);
   __syncthreads();
-  dict_pair_stage1<WORDS, UN>(n, w0, hbw, codes, rtype, tabJ, wtab, a, f, omega, uw, u_out);
+  dict_pair_stage1<WORDS, UN>(n, w0, hbw, types, tabJ, wc, tw, aw, fw, omega, uw, u_out);
   __syncthreads();
   const int row0 = t0 + (int)threadIdx.x * 2;
   DictStream<WORDS, 2> s;
-  dict_fetch<CSR_RESID, WORDS, false, 2>(s, row0, n, codes, rtype, f, a, 0);
-  if (rtype) dict_expand<WORDS, 2>(s, wtab);
+  dict_pair_stream<WORDS>(s, row0 - w0, W, row0, n, types, wc, tw, fw);
+  if (types) dict_expand<WORDS, 2>(s, wc);
   double res[2];
   dict_rows<CSR_RESID, WORDS, UN, 2>(s, row0 - w0, tabR, uw, omega, 0, res);  // x = the LDS window
   if (r_out) dict_store<WORDS, false, 2>(s, row0, res, r_out);
   rs[threadIdx.x * 2] = s.live[0] ? res[0] : 0.0;
   rs[threadIdx.x * 2 + 1] = s.live[1] ? res[1] : 0.0;
   __syncthreads();
-  dict_restrict_tail<2>(tile, n, rs, nH, fH, diagH, uH1, nullptr, omega);
+  dict_restrict_tail(tile, n, rs, nH, fH, dH, uH1, omega);
 }
 template <int WORDS, int UN>
 __global__ __launch_bounds__(256) void dict_pair_up_kernel(
@@ -1165,29 +1412,40 @@ __global__ __launch_bounds__(256) void dict_pair_up_kernel(
     double* u_out, double omega, int hbw, int n_h, const double* uh_in, double* uh_out,
     int xcd_map) {
   __shared__ DictEntry tabJ[256];
-  __shared__ uint64_t wtab[256 * WORDS];
+  __shared__ __attribute__((aligned(16))) uint64_t wc[PAIR_W * WORDS];
+  __shared__ uint16_t tw[PAIR_W / 2];
+  __shared__ __attribute__((aligned(16))) double aw[PAIR_AW];
+  __shared__ __attribute__((aligned(16))) double fw[PAIR_W];
   __shared__ double uw[PAIR_W];
   __shared__ double rs[512];
   const int tile = xcd_tile(blockIdx.x, gridDim.x, xcd_map);
-  const int t0 = tile * 510, w0 = t0 - hbw;
-  dict_stage_table<CSR_JACOBI>(tabJ, doff, dval, ntab);
-  if (rtype) dict_stage_words<WORDS>(wtab, rwords);
+  const int t0 = tile * 510, w0 = t0 - hbw, W = 512 + 2 * hbw;
+  const bool types = rtype != nullptr;
+  PairLoads<WORDS> g;
+  if (types) dict_pair_issue<WORDS, true>(g, n, w0, hbw, codes, rtype, rwords, doff, dval, ntab, a, f);
+  else dict_pair_issue<WORDS, false>(g, n, w0, hbw, codes, rtype, rwords, doff, dval, ntab, a, f);
+  pair_f64x2 pre[2];  // uh_in may be uh_out: a lane reads only the rows it later writes
+  double pre1;        // the lone last entry
+  dict_prolong_pre(tile, n, n_h, uh_in, pre, pre1);
+  dict_put_table<CSR_JACOBI>(tabJ, g.tv, g.to, ntab);
+  if (types) dict_pair_commit<WORDS, true>(g, n, w0, hbw, wc, tw, aw, fw);
+  else dict_pair_commit<WORDS, false>(g, n, w0, hbw, wc, tw, aw, fw);
   __syncthreads();
-  dict_pair_stage1<WORDS, UN>(n, w0, hbw, codes, rtype, tabJ, wtab, a, f, omega, uw, nullptr);
+  dict_pair_stage1<WORDS, UN>(n, w0, hbw, types, tabJ, wc, tw, aw, fw, omega, uw, nullptr);
   __syncthreads();
   const int row0 = t0 + (int)threadIdx.x * 2;
   DictStream<WORDS, 2> s;
-  dict_fetch<CSR_RESID, WORDS, false, 2>(s, row0, n, codes, rtype, f, a, 0);  // types + f; xi from the window
+  dict_pair_stream<WORDS>(s, row0 - w0, W, row0, n, types, wc, tw, fw);
   s.xi[0] = uw[row0 - w0];
   s.xi[1] = uw[row0 - w0 + 1];
-  if (rtype) dict_expand<WORDS, 2>(s, wtab);
+  if (types) dict_expand<WORDS, 2>(s, wc);
   double res[2];
   dict_rows<CSR_JACOBI, WORDS, UN, 2>(s, row0 - w0, tabJ, uw, omega, 0, res);
   dict_store<WORDS, false, 2>(s, row0, res, u_out);
   rs[threadIdx.x * 2] = s.live[0] ? res[0] : 0.0;
   rs[threadIdx.x * 2 + 1] = s.live[1] ? res[1] : 0.0;
   __syncthreads();
-  dict_prolong_tail<2>(tile, n, rs, n_h, uh_in, uh_out);
+  dict_prolong_tail(tile, n, rs, n_h, pre, pre1, uh_out);
 }
 
 // ---- K-Patch: the level's whole down-leg / up-leg in ONE pass over the level ------------
