@@ -167,6 +167,8 @@ _SIGS = {
     "amg_hip_set_tail_fusion": (None, [C.c_int32]),
     "amg_hip_set_patch_tile_flags": (None, [C.c_int32]),
     "amg_hip_set_patch_xf": (None, [C.c_int32]),
+    "amg_hip_set_patch_tall": (None, [C.c_int32]),
+    "amg_hip_patch_leg_lines": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "amg_hip_create_rs": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, C.c_double, C.c_int64,
                                     C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_slab_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SlabInfo)]),
@@ -383,6 +385,10 @@ def set_patch_tile_flags(on):
 
 def set_patch_xf(on):
     lib().amg_hip_set_patch_xf(int(bool(on)))
+
+
+def set_patch_tall(on):
+    lib().amg_hip_set_patch_tall(int(bool(on)))
 
 
 def set_tail_fusion(on):
@@ -1003,6 +1009,10 @@ class Multigrid:
         b = C.c_double(0)
         _chk(lib().amg_hip_cycle_must_move(self._h, int(part), C.byref(b)))
         return b.value
+
+    def patch_leg_lines(self, level, leg):
+        """lines of the K-Patch tiles of `level`'s down-leg (leg 0) / up-leg (leg 1); 0 = no K-Patch level"""
+        return int(lib().amg_hip_patch_leg_lines(self._h, int(level), int(leg)))
 
     def profile_fine_sweep(self, n_launches):
         """(avg_ms, min_ms, sweeps per launch, kernel name) of the level-0 Jacobi sweep

@@ -1453,7 +1453,7 @@ __global__ __launch_bounds__(256) void dict_pair_up_kernel(
 // output again, 25 B per row and sweep.  The 2+2 true-Jacobi cycle touches such a level
 // five times on the way down (sweep, sweep, residual + restriction) and three times on the
 // way up (prolongation, sweep, sweep).  These kernels do each leg in one launch (temporal
-// blocking): a workgroup owns a 2-D PATCH of the level -- PATCH_TH grid lines x PATCH_TW
+// blocking): a workgroup owns a 2-D PATCH of the level -- patch_th(RINGS) grid lines x PATCH_TW
 // columns of the flat index (row = line * m + column; m = the pitch of the band: 4096,
 // 2048, ...) -- loads it once with the halo the later stages need (one ring of lines and
 // columns per stage), and runs the stages LDS -> LDS with a barrier in between.  The halo
@@ -1471,8 +1471,13 @@ __global__ __launch_bounds__(256) void dict_pair_up_kernel(
 // cell costs one byte of matrix and no decode chain.  Interior rows share one type: the
 // table reads of a wave are broadcasts.
 constexpr int PATCH_TW = 64;                 // columns of a patch (output)
-constexpr int PATCH_TH = 42;                 // lines of a patch (output)
-constexpr int PATCH_EH = PATCH_TH + 6;       // lines held, 3 rings
+constexpr int PATCH_EH = 48;                 // lines held: the output lines + RINGS halo lines above and below
+// lines of a patch (output).  RINGS = dependent stencil stages a launch runs on the loaded data, one
+// ring of halo lines each: 3 for the level-0 down-leg (sweep, sweep, residual) and the colour
+// launches -> 42 lines; 2 for every up-leg (sweep, sweep) and the down-legs of the levels >= 1
+// (sweep, residual) -> 44 lines in the same held frame, threads and LDS
+constexpr int patch_th(int rings) { return PATCH_EH - 2 * rings; }
+static bool patch_rings_ok(int rings) { return rings == 2 || rings == 3; }
 constexpr int PATCH_EC = PATCH_TW + 8;       // columns held: [-4, TW + 4)
 constexpr int PATCH_NT = 432;                // threads = 6 line groups x 72 columns (4 workgroups per CU)
 constexpr int PATCH_K = PATCH_EH * PATCH_EC / PATCH_NT;  // cells per thread: 8 consecutive lines
@@ -1674,7 +1679,7 @@ __device__ __forceinline__ double patch_eval(const double* buf, int cell, uint32
 // latency-bound stages need).  Cells outside the region or outside the matrix keep their
 // value; ZERO: such cells inside the region are set to 0.0 instead (the residual that the
 // restriction reads).  out (optional): rows of the patch proper also go to global memory.
-template <int UN, int UM, bool RESID, bool NT, bool ZERO>
+template <int UN, int UM, bool RESID, bool NT, bool ZERO, int TH>
 __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int ntypes, double* buf,
                                             const PatchU& U, const PatchJ* tabJ, const PatchR* tabR,
                                             double omega, int l0, int l1, int c0, int c1, double* out) {
@@ -1706,7 +1711,7 @@ __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int nty
     if (did[k]) buf[pc.cell0 + k * PATCH_EC] = res[k];
     else if (ZERO && inr[k]) buf[pc.cell0 + k * PATCH_EC] = 0.0;
     const int lj = pc.lj0 + k;
-    if (outc && did[k] && lj >= 0 && lj < PATCH_TH) {
+    if (outc && did[k] && lj >= 0 && lj < TH) {
       double* op = out + (pc.row0 + k * m);
       if (NT) __builtin_nontemporal_store(res[k], op);
       else *op = res[k];
@@ -1718,14 +1723,14 @@ __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int nty
 // patch, so every store of a wave covers whole, aligned 128-byte lines.  (Stored straight from
 // the stage's registers, a line was split 60 + 4 entries between two waves -- the thread map
 // has 72 columns -- and the PMC write traffic was 1.5 x the vector.)
-template <bool NT>
+template <bool NT, int RINGS>
 __device__ __forceinline__ void patch_copy_out(const double* buf, double* __restrict__ out, int n, int m,
                                                int j0, int i0) {
-  for (int q = threadIdx.x; q < PATCH_TH * PATCH_TW; q += PATCH_NT) {
+  for (int q = threadIdx.x; q < patch_th(RINGS) * PATCH_TW; q += PATCH_NT) {
     const int lj = q / PATCH_TW, li = q - lj * PATCH_TW;
     const int64_t row = (int64_t)(j0 + lj) * m + i0 + li;
     if (row < (int64_t)n) {
-      const double v = buf[(lj + 4) * PATCH_EC + li + 4];
+      const double v = buf[(lj + RINGS + 1) * PATCH_EC + li + 4];
       if (NT) __builtin_nontemporal_store(v, out + row);
       else out[row] = v;
     }
@@ -1738,7 +1743,8 @@ struct __attribute__((aligned(8))) PatchPair { double x, y; };  // 16-byte load,
 // that out at setup): no row-type loads, no bounds checks, the wave-uniform path for all waves.
 // XF: x is not loaded and nothing is written to LDS: the caller forms the cells from pc.f once the
 // row type's diagonal is at hand (patch_form_x).
-template <bool PROLONG, bool UNI, bool XF = false>
+// RINGS: the first held line is line -RINGS of the patch.
+template <int RINGS, bool PROLONG, bool UNI, bool XF = false>
 __device__ __forceinline__ void patch_load(PatchCells& pc, uint32_t tf, int n, int m, int j0, int i0,
                                            const double* __restrict__ x,
                                            const double* __restrict__ f,
@@ -1746,7 +1752,7 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, uint32_t tf, int n, i
                                            const double* __restrict__ uH, int nH, double* buf) {
   const int g = (int)threadIdx.x / PATCH_EC, col = (int)threadIdx.x - g * PATCH_EC;
   const int le = g * PATCH_K;            // first of the thread's PATCH_K consecutive lines
-  pc.lj0 = le - 3;
+  pc.lj0 = le - RINGS;
   pc.li = col - 4;
   pc.cell0 = (le + 1) * PATCH_EC + col;  // + 1: guard line
   const int64_t r0 = (int64_t)(j0 + pc.lj0) * m + i0 + pc.li;
@@ -1798,14 +1804,14 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, uint32_t tf, int n, i
   pc.uniform = __builtin_amdgcn_ballot_w64(mism != 0) == 0 && pc.tu < (uint32_t)ntypes;
 }
 
-// flag[tile] = the row type shared by EVERY row a patch kernel loads for the tile (lines
-// -3 .. TH+3, columns -4 .. TW+4 of the flat index, all inside the matrix), else 255.
-__global__ __launch_bounds__(256) void patch_tile_flags_kernel(int n, int m, int px_count,
+// flag[tile] = the row type shared by EVERY row a patch kernel of `rings` rings loads for the tile
+// (lines -rings .. TH+rings, columns -4 .. TW+4 of the flat index, all inside the matrix), else 255.
+__global__ __launch_bounds__(256) void patch_tile_flags_kernel(int n, int m, int px_count, int rings,
                                                                const uint8_t* __restrict__ rtype,
                                                                int ntypes, uint8_t* __restrict__ flag) {
   const int tile = blockIdx.x;
   const int py = tile / px_count, px = tile - py * px_count;
-  const int64_t base = (int64_t)(py * PATCH_TH - 3) * m + px * PATCH_TW - 4;
+  const int64_t base = (int64_t)(py * patch_th(rings) - rings) * m + px * PATCH_TW - 4;
   const int64_t first = base < 0 ? 0 : (base < n ? base : n - 1);
   const uint32_t t0 = rtype[first];
   int ok = base >= 0 && t0 < (uint32_t)ntypes;
@@ -1817,29 +1823,30 @@ __global__ __launch_bounds__(256) void patch_tile_flags_kernel(int n, int m, int
   ok = __syncthreads_and(ok);
   if (threadIdx.x == 0) flag[tile] = ok ? (uint8_t)t0 : (uint8_t)255;
 }
-hipError_t launch_patch_tile_flags(int64_t n, int64_t m, const uint8_t* rtype, int ntypes, uint8_t* flag,
-                                   int64_t* n_tiles, hipStream_t st) {
-  if (!patch_geometry_ok(n, m)) return hipErrorInvalidValue;
+hipError_t launch_patch_tile_flags(int64_t n, int64_t m, int rings, const uint8_t* rtype, int ntypes,
+                                   uint8_t* flag, int64_t* n_tiles, hipStream_t st) {
+  if (!patch_geometry_ok(n, m) || !patch_rings_ok(rings)) return hipErrorInvalidValue;
   const int64_t lines = (n + m - 1) / m;
   const int pxc = (int)(m / PATCH_TW);
-  const int64_t tiles = (lines + PATCH_TH - 1) / PATCH_TH * pxc;
+  const int64_t th = patch_th(rings);
+  const int64_t tiles = (lines + th - 1) / th * pxc;
   if (n_tiles) *n_tiles = tiles;
   if (!flag) return hipSuccess;
   hipLaunchKernelGGL(patch_tile_flags_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (int)n, (int)m, pxc,
-                     rtype, ntypes, flag);
+                     rings, rtype, ntypes, flag);
   return hipGetLastError();
 }
 
-// cflag[tile] = 1 when every coarse row the down-leg of the tile produces (c = i / 2 for the even
-// fine rows i of the patch) has the diagonal dref, bit for bit.
-__global__ __launch_bounds__(256) void patch_coarse_flags_kernel(int n, int m, int px_count, int nH,
+// cflag[tile] = 1 when every coarse row the down-leg of the tile (th lines) produces (c = i / 2 for
+// the even fine rows i of the patch) has the diagonal dref, bit for bit.
+__global__ __launch_bounds__(256) void patch_coarse_flags_kernel(int n, int m, int px_count, int th, int nH,
                                                                  const double* __restrict__ diagH, double dref,
                                                                  uint8_t* __restrict__ cflag) {
   const int tile = blockIdx.x;
   const int py = tile / px_count, px = tile - py * px_count;
-  const int j0 = py * PATCH_TH, i0 = px * PATCH_TW;
+  const int j0 = py * th, i0 = px * PATCH_TW;
   int ok = 1;
-  for (int q = threadIdx.x; q < PATCH_TH * (PATCH_TW / 2); q += 256) {
+  for (int q = threadIdx.x; q < th * (PATCH_TW / 2); q += 256) {
     const int lj = q / (PATCH_TW / 2), cx = q - lj * (PATCH_TW / 2);
     const int64_t i = (int64_t)(j0 + lj) * m + i0 + 2 * cx;
     const int64_t c = i >> 1;
@@ -1849,14 +1856,15 @@ __global__ __launch_bounds__(256) void patch_coarse_flags_kernel(int n, int m, i
   ok = __syncthreads_and(ok);
   if (threadIdx.x == 0) cflag[tile] = ok ? 1 : 0;
 }
-hipError_t launch_patch_coarse_flags(int64_t n, int64_t m, int64_t nH, const double* diagH, double dref,
-                                     uint8_t* cflag, hipStream_t st) {
-  if (!patch_geometry_ok(n, m) || !diagH || !cflag) return hipErrorInvalidValue;
+hipError_t launch_patch_coarse_flags(int64_t n, int64_t m, int rings, int64_t nH, const double* diagH,
+                                     double dref, uint8_t* cflag, hipStream_t st) {
+  if (!patch_geometry_ok(n, m) || !patch_rings_ok(rings) || !diagH || !cflag) return hipErrorInvalidValue;
   const int64_t lines = (n + m - 1) / m;
   const int pxc = (int)(m / PATCH_TW);
-  const int64_t tiles = (lines + PATCH_TH - 1) / PATCH_TH * pxc;
+  const int64_t th = patch_th(rings);
+  const int64_t tiles = (lines + th - 1) / th * pxc;
   hipLaunchKernelGGL(patch_coarse_flags_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (int)n, (int)m, pxc,
-                     (int)nH, diagH, dref, cflag);
+                     (int)th, (int)nH, diagH, dref, cflag);
   return hipGetLastError();
 }
 
@@ -1952,7 +1960,7 @@ hipError_t debug_set_patch_stamps(unsigned long long* p) {
 #else
 #define PATCH_STAMP(k)
 #endif
-template <int UN, int UM, bool FIRST, bool NT, bool XF = false>
+template <int UN, int UM, bool FIRST, bool NT, bool XF = false, int RINGS = 3>
 // (four workgroups per CU = 7 waves per SIMD = 72 registers: measured against 6 and 5 waves again in
 // round 3 -- level-0 down-leg 131-135 us at 7, 138-144 at 6, 142-143 at 5.  The down-legs of the
 // 7- and 9-point levels spill 2-7 registers at 72 and run at 6 waves (80 registers, three
@@ -1979,7 +1987,8 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
   PATCH_STAMP(0);
   const int tile = xcd_tile(blockIdx.x, gridDim.x, xcd_map);
   const int py = tile / px_count, px = tile - py * px_count;
-  const int j0 = (py + py0) * PATCH_TH, i0 = px * PATCH_TW;
+  constexpr int TH = patch_th(RINGS);
+  const int j0 = (py + py0) * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
   const uint32_t tf = tflag ? (uint32_t)tflag[(py + py0) * px_count + px] : 255u;
@@ -1988,38 +1997,39 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
   // end of the workgroup's life, where nothing is left to hide its latency behind
   const bool cuni = uH1 && cflag && cflag[(py + py0) * px_count + px] != 0;
   static_assert(!(FIRST && XF), "level 0 starts from its own u");
-  if (tf != 255u) patch_load<false, true, XF>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
-  else patch_load<false, false, XF>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
+  static_assert(RINGS == 3 || (RINGS == 2 && !FIRST), "three dependent stages (FIRST) need three rings");
+  if (tf != 255u) patch_load<RINGS, false, true, XF>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
+  else patch_load<RINGS, false, false, XF>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
   patch_prologue(pc, buf, tabJ, tabR, ptab, nent, utabd, utabi, U);
   if (XF) patch_form_x(pc, U, utabd, omega, buf);
   lds_barrier();
   PATCH_STAMP(1);
   if (FIRST) {
-    patch_stage<UN, UM, false, NT, false>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -2, PATCH_TH + 2, -2,
-                                          PATCH_TW + 3, nullptr);
+    patch_stage<UN, UM, false, NT, false, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -2, TH + 2, -2,
+                                              PATCH_TW + 3, nullptr);
     lds_barrier();
   }
   PATCH_STAMP(2);
-  patch_stage<UN, UM, false, NT, false>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -1, PATCH_TH + 1, -1,
-                                        PATCH_TW + 2, nullptr);
+  patch_stage<UN, UM, false, NT, false, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -1, TH + 1, -1,
+                                            PATCH_TW + 2, nullptr);
   lds_barrier();
   PATCH_STAMP(3);
-  patch_copy_out<NT>(buf, u_out, n, m, j0, i0);  // the residual stage below only reads until its barrier
+  patch_copy_out<NT, RINGS>(buf, u_out, n, m, j0, i0);  // the residual stage below only reads until its barrier
   // residual; rows outside the matrix read as 0.0 for the restriction (ZERO)
-  patch_stage<UN, UM, true, NT, true>(pc, m, ntypes, buf, U, tabJ, tabR, omega, 0, PATCH_TH, 0, PATCH_TW + 1,
-                                      r_out);
+  patch_stage<UN, UM, true, NT, true, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, 0, TH, 0, PATCH_TW + 1,
+                                          r_out);
   lds_barrier();
   PATCH_STAMP(4);
   const double* rsb = buf;
   // restriction + first coarse sweep: coarse row c <-> even fine row 2c of the patch
   // (uH1 == nullptr: the coarse level's kernel forms that sweep from f_H itself -- XF -- and f_H
   // alone is stored: no coarse diagonal, no division)
-  for (int q = threadIdx.x; q < PATCH_TH * (PATCH_TW / 2); q += PATCH_NT) {
+  for (int q = threadIdx.x; q < TH * (PATCH_TW / 2); q += PATCH_NT) {
     const int lj = q / (PATCH_TW / 2), cx = q - lj * (PATCH_TW / 2);
     const int64_t i = (int64_t)(j0 + lj) * m + i0 + 2 * cx;   // fine row 2c
     const int64_t c = i >> 1;
     if (i >= (int64_t)n || c >= nH) continue;
-    const double* rs = rsb + (lj + 4) * PATCH_EC + 2 * cx + 4;
+    const double* rs = rsb + (lj + RINGS + 1) * PATCH_EC + 2 * cx + 4;
     double sum = 0.0;  // dict_restrict_tail / linear_restrict_kernel, same guards and order
     if (i < n) sum += 0.5 * rs[0];
     if (i + 1 < n) sum += 1.0 * rs[1];
@@ -2033,7 +2043,7 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
   PATCH_STAMP(5);
 }
 
-template <int UN, int UM, bool NT>
+template <int UN, int UM, bool NT, int RINGS = 3>
 __global__ __launch_bounds__(PATCH_NT, AMG_PATCH_WAVES) void patch_up_kernel(
     int n, int m, int px_count, const uint8_t* __restrict__ rtype, const double* __restrict__ ptab,
     const double* __restrict__ utabd, const int32_t* __restrict__ utabi,
@@ -2044,21 +2054,23 @@ __global__ __launch_bounds__(PATCH_NT, AMG_PATCH_WAVES) void patch_up_kernel(
   __shared__ PatchR tabR[PATCH_MAXTAB];
   const int tile = xcd_tile(blockIdx.x, gridDim.x, xcd_map);
   const int py = tile / px_count, px = tile - py * px_count;
-  const int j0 = (py + py0) * PATCH_TH, i0 = px * PATCH_TW;
+  static_assert(RINGS == 2 || RINGS == 3, "two dependent stages");
+  constexpr int TH = patch_th(RINGS);
+  const int j0 = (py + py0) * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
   const uint32_t tf = tflag ? (uint32_t)tflag[(py + py0) * px_count + px] : 255u;
-  if (tf != 255u) patch_load<true, true>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
-  else patch_load<true, false>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
+  if (tf != 255u) patch_load<RINGS, true, true>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
+  else patch_load<RINGS, true, false>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
   patch_prologue(pc, buf, tabJ, tabR, ptab, nent, utabd, utabi, U);
   lds_barrier();
-  patch_stage<UN, UM, false, NT, false>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -1, PATCH_TH + 1, -1,
-                                        PATCH_TW + 1, nullptr);
+  patch_stage<UN, UM, false, NT, false, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -1, TH + 1, -1,
+                                            PATCH_TW + 1, nullptr);
   lds_barrier();
-  patch_stage<UN, UM, false, NT, false>(pc, m, ntypes, buf, U, tabJ, tabR, omega, 0, PATCH_TH, 0, PATCH_TW,
-                                        nullptr);
+  patch_stage<UN, UM, false, NT, false, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, 0, TH, 0, PATCH_TW,
+                                            nullptr);
   lds_barrier();
-  patch_copy_out<NT>(buf, u_out, n, m, j0, i0);
+  patch_copy_out<NT, RINGS>(buf, u_out, n, m, j0, i0);
 }
 
 // ---- multicolour Gauss-Seidel on a patch (colours laid out on the 2 x 2 cells of the grid) ----
@@ -2139,12 +2151,13 @@ __global__ __launch_bounds__(PATCH_NT, AMG_RB_WAVES) void patch_rb_kernel(
   __shared__ PatchR tabR[PATCH_MAXTAB];
   const int tile = xcd_tile(blockIdx.x, gridDim.x, xcd_map);
   const int py = tile / px_count, px = tile - py * px_count;
-  const int j0 = (py + py0) * PATCH_TH, i0 = px * PATCH_TW;
+  constexpr int RINGS = 3, TH = patch_th(RINGS);  // up to three dependent stages
+  const int j0 = (py + py0) * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
   const uint32_t tf = tflag ? (uint32_t)tflag[(py + py0) * px_count + px] : 255u;
-  if (tf != 255u) patch_load<PROLONG, true>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
-  else patch_load<PROLONG, false>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
+  if (tf != 255u) patch_load<RINGS, PROLONG, true>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
+  else patch_load<RINGS, PROLONG, false>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
   patch_prologue(pc, buf, tabJ, tabR, ptab, nent, utabd, utabi, U);
   uint32_t cbits = 0;
   {
@@ -2162,21 +2175,21 @@ __global__ __launch_bounds__(PATCH_NT, AMG_RB_WAVES) void patch_rb_kernel(
   const int nst = (int)(stages & 7u);
   for (int sg = 0; sg < nst; ++sg) {
     const int ext = nst - 1 - sg + E;  // rings the later stages still read
-    patch_stage_color<UN, UM>(pc, ntypes, buf, U, tabJ, tabR, -ext, PATCH_TH + ext, -ext, PATCH_TW + ext + E,
+    patch_stage_color<UN, UM>(pc, ntypes, buf, U, tabJ, tabR, -ext, TH + ext, -ext, PATCH_TW + ext + E,
                               cbits, (stages >> (4 + 2 * sg)) & 3u);
     lds_barrier();
   }
-  patch_copy_out<NT>(buf, u_out, n, m, j0, i0);
+  patch_copy_out<NT, RINGS>(buf, u_out, n, m, j0, i0);
   if (TAIL) {
-    patch_stage<UN, UM, true, NT, true>(pc, m, ntypes, buf, U, tabJ, tabR, 1.0, 0, PATCH_TH, 0, PATCH_TW + 1,
-                                    r_out);
+    patch_stage<UN, UM, true, NT, true, TH>(pc, m, ntypes, buf, U, tabJ, tabR, 1.0, 0, TH, 0, PATCH_TW + 1,
+                                            r_out);
     lds_barrier();
-    for (int q = threadIdx.x; q < PATCH_TH * (PATCH_TW / 2); q += PATCH_NT) {
+    for (int q = threadIdx.x; q < TH * (PATCH_TW / 2); q += PATCH_NT) {
       const int lj = q / (PATCH_TW / 2), cx = q - lj * (PATCH_TW / 2);
       const int64_t i = (int64_t)(j0 + lj) * m + i0 + 2 * cx;   // fine row 2c
       const int64_t c = i >> 1;
       if (i >= (int64_t)n || c >= nH) continue;
-      const double* rs = buf + (lj + 4) * PATCH_EC + 2 * cx + 4;
+      const double* rs = buf + (lj + RINGS + 1) * PATCH_EC + 2 * cx + 4;
       double sum = 0.0;  // dict_restrict_tail / linear_restrict_kernel, same guards and order
       if (i < n) sum += 0.5 * rs[0];
       if (i + 1 < n) sum += 1.0 * rs[1];
@@ -2190,18 +2203,22 @@ int patch_un(int un) { return un <= 5 ? 5 : un <= 7 ? 7 : 9; }
 bool patch_geometry_ok(int64_t n, int64_t m) {
   return m >= 2 * PATCH_TW && (m % PATCH_TW) == 0 && n >= m && n < ((int64_t)1 << 31) - 4 * m - 64;
 }
-// tiles of the lines [line_lo, line_hi) (line_hi < 0: all); *py0 = first tile row
-static unsigned patch_grid(int64_t n, int64_t m, int64_t line_lo, int64_t line_hi, int* px_count,
+// tiles (of th lines) that meet the lines [line_lo, line_hi) (line_hi < 0: all); *py0 = first tile row
+static unsigned patch_grid(int64_t n, int64_t m, int th, int64_t line_lo, int64_t line_hi, int* px_count,
                            int* py0) {
   const int64_t lines = (n + m - 1) / m;
   if (line_hi < 0 || line_hi > lines) line_hi = lines;
   if (line_lo < 0) line_lo = 0;
   if (line_lo > line_hi) line_lo = line_hi;
   *px_count = (int)(m / PATCH_TW);
-  *py0 = (int)(line_lo / PATCH_TH);
-  return (unsigned)(((line_hi + PATCH_TH - 1) / PATCH_TH - *py0) * *px_count);
+  *py0 = (int)(line_lo / th);
+  return (unsigned)(((line_hi + th - 1) / th - *py0) * *px_count);
 }
-int patch_tile_lines() { return PATCH_TH; }
+int patch_tile_lines(int rings) { return patch_rings_ok(rings) ? patch_th(rings) : 0; }
+// THE choice of a Jacobi leg's geometry where tall legs are on: the level-0 down-leg (first) runs
+// three dependent stages on the loaded data, every other leg two.  (A kernel kind that came out
+// slower on 44 lines than on 42 would be kept on three rings here.)
+int patch_leg_rings(bool first) { return first ? 3 : 2; }
 // kernel kinds: (row width of the per-lane path, slots of the interior row type -- the scalar path)
 //   (5, 0x0BA) the 5-point level 0; (7, 0x1D7) / (9, 0x1D7) level 1, whose +-1 entries are exact
 //   zeros and pruned (its line ends keep rows of 9); (9, 0x1FF) the 9-point levels
@@ -2228,41 +2245,46 @@ hipError_t launch_patch_down(bool first, int64_t n, int64_t m, const PatchRef& P
                              int64_t line_lo, int64_t line_hi, bool xf) {
   // uH1 == nullptr: f_H only (the coarse level runs the xf form); xf: x is formed from f, not read
   if (!patch_geometry_ok(n, m) || !P.rtype || !P.ptab || !P.utabd || !P.utabi || (P.ntypes + 1) * patch_un(P.un) > PATCH_MAXTAB ||
-      P.nent != P.ntypes * patch_un(P.un) || !fH || (uH1 && !diagH) || !u_out || u_out == x || (xf ? first : !x))
+      P.nent != P.ntypes * patch_un(P.un) || !fH || (uH1 && !diagH) || !u_out || u_out == x || (xf ? first : !x) ||
+      !patch_rings_ok(P.rings) || P.rings < patch_leg_rings(first))
     return hipErrorInvalidValue;
+  // P.rings is the geometry of everything below: the tile grid, py0, the flags P carries, the kernel
   int pxc = 0, py0 = 0;
-  const unsigned grid = patch_grid(n, m, line_lo, line_hi, &pxc, &py0);
+  const unsigned grid = patch_grid(n, m, patch_th(P.rings), line_lo, line_hi, &pxc, &py0);
   if (grid == 0) return hipSuccess;
   const int xm = g_xcd_map ? 1 : 0;  // halo lines of neighbouring patches meet in one L2
   return patch_dispatch(P.un, P.umask, P.nt != 0, [&](auto U, auto M, auto NTF) {
-    if (first)
-      hipLaunchKernelGGL((patch_down_kernel<decltype(U)::value, decltype(M)::value, true, decltype(NTF)::value>), dim3(grid),
-                         dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, P.nent, P.ntypes, x, f, u_out,
-                         r_out, (int)nH, fH, diagH, uH1, omega, xm, py0, P.tflag, P.cflag, P.dHu);
-    else if (xf)
-      hipLaunchKernelGGL((patch_down_kernel<decltype(U)::value, decltype(M)::value, false, decltype(NTF)::value, true>), dim3(grid),
-                         dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, P.nent, P.ntypes, x, f, u_out,
-                         r_out, (int)nH, fH, diagH, uH1, omega, xm, py0, P.tflag, P.cflag, P.dHu);
-    else
-      hipLaunchKernelGGL((patch_down_kernel<decltype(U)::value, decltype(M)::value, false, decltype(NTF)::value>), dim3(grid),
-                         dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, P.nent, P.ntypes, x, f, u_out,
-                         r_out, (int)nH, fH, diagH, uH1, omega, xm, py0, P.tflag, P.cflag, P.dHu);
+#define AMG_DOWN(FST, XFF, RG)                                                                                 \
+  hipLaunchKernelGGL((patch_down_kernel<decltype(U)::value, decltype(M)::value, FST, decltype(NTF)::value, XFF, RG>), \
+                     dim3(grid), dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, \
+                     P.nent, P.ntypes, x, f, u_out, r_out, (int)nH, fH, diagH, uH1, omega, xm, py0, P.tflag,    \
+                     P.cflag, P.dHu)
+    if (first) AMG_DOWN(true, false, 3);
+    else if (xf && P.rings == 2) AMG_DOWN(false, true, 2);
+    else if (xf) AMG_DOWN(false, true, 3);
+    else if (P.rings == 2) AMG_DOWN(false, false, 2);
+    else AMG_DOWN(false, false, 3);
+#undef AMG_DOWN
   });
 }
 hipError_t launch_patch_up(int64_t n, int64_t m, const PatchRef& P, const double* x, const double* f,
                            const double* uH, int64_t nH, double* u_out, double omega,
                            hipStream_t st, int64_t line_lo, int64_t line_hi) {
   if (!patch_geometry_ok(n, m) || !P.rtype || !P.ptab || !P.utabd || !P.utabi || (P.ntypes + 1) * patch_un(P.un) > PATCH_MAXTAB ||
-      P.nent != P.ntypes * patch_un(P.un) || !uH || !u_out || u_out == x)
+      P.nent != P.ntypes * patch_un(P.un) || !uH || !u_out || u_out == x || !patch_rings_ok(P.rings))
     return hipErrorInvalidValue;
   int pxc = 0, py0 = 0;
-  const unsigned grid = patch_grid(n, m, line_lo, line_hi, &pxc, &py0);
+  const unsigned grid = patch_grid(n, m, patch_th(P.rings), line_lo, line_hi, &pxc, &py0);
   if (grid == 0) return hipSuccess;
   const int xm = g_xcd_map ? 1 : 0;  // halo lines of neighbouring patches meet in one L2
   return patch_dispatch(P.un, P.umask, P.nt != 0, [&](auto U, auto M, auto NTF) {
-    hipLaunchKernelGGL((patch_up_kernel<decltype(U)::value, decltype(M)::value, decltype(NTF)::value>), dim3(grid),
-                       dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, P.nent, P.ntypes, x, f, uH,
-                       (int)nH, u_out, omega, xm, py0, P.tflag);
+#define AMG_UP(RG)                                                                                            \
+  hipLaunchKernelGGL((patch_up_kernel<decltype(U)::value, decltype(M)::value, decltype(NTF)::value, RG>),     \
+                     dim3(grid), dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, \
+                     P.nent, P.ntypes, x, f, uH, (int)nH, u_out, omega, xm, py0, P.tflag)
+    if (P.rings == 2) AMG_UP(2);
+    else AMG_UP(3);
+#undef AMG_UP
   });
 }
 // the halo a patch is loaded with (3 lines above and below, 4 columns left and right; the lines
@@ -2281,10 +2303,10 @@ hipError_t launch_patch_rb(bool prolong, bool tail, int64_t n, int64_t m, const 
   const int nst = (int)(stages & 7u);
   if (!patch_geometry_ok(n, m) || !P.rtype || !P.ptab || !P.utabd || !P.utabi || (P.ntypes + 1) * patch_un(P.un) > PATCH_MAXTAB ||
       P.nent != P.ntypes * patch_un(P.un) || !u_out || u_out == x || (prolong && (!uH || tail)) || (tail && !fH) || nH < 2 ||
-      nst < 1 || nst > patch_rb_max_stages(tail) || (m & 1))
+      nst < 1 || nst > patch_rb_max_stages(tail) || (m & 1) || P.rings != 3)
     return hipErrorInvalidValue;
   int pxc = 0, py0 = 0;
-  const unsigned grid = patch_grid(n, m, line_lo, line_hi, &pxc, &py0);
+  const unsigned grid = patch_grid(n, m, patch_th(3), line_lo, line_hi, &pxc, &py0);
   if (grid == 0) return hipSuccess;
   const int xm = g_xcd_map ? 1 : 0;
   return patch_dispatch(P.un, P.umask, P.nt != 0, [&](auto U, auto M, auto NTF) {

@@ -208,6 +208,11 @@ struct PatchRef {
   // slots, mask of slots in use}
   const double* utabd = nullptr;
   const int32_t* utabi = nullptr;
+  // geometry of the launch: halo rings of lines = dependent stencil stages that run on the loaded
+  // data (3: tiles of 42 lines, 2: tiles of 44 lines -- patch_tile_lines).  The tile grid, the
+  // instantiation and the meaning of tflag / cflag all follow from it: the flags handed over here
+  // must have been built for this very ring count.
+  int rings = 3;
   // per tile of the level: the row type every row of the tile and its halo has, or 255
   // (launch_patch_tile_flags); null = always take the general path
   const uint8_t* tflag = nullptr;
@@ -217,11 +222,12 @@ struct PatchRef {
   const uint8_t* cflag = nullptr;
   double dHu = 0.0;
 };
-hipError_t launch_patch_coarse_flags(int64_t n, int64_t m, int64_t nH, const double* diagH, double dref,
-                                     uint8_t* cflag, hipStream_t st);
+// (both: for the tiles of a launch with `rings` rings)
+hipError_t launch_patch_coarse_flags(int64_t n, int64_t m, int rings, int64_t nH, const double* diagH,
+                                     double dref, uint8_t* cflag, hipStream_t st);
 // flag == null: only *n_tiles is computed (the size of the array)
-hipError_t launch_patch_tile_flags(int64_t n, int64_t m, const uint8_t* rtype, int ntypes, uint8_t* flag,
-                                   int64_t* n_tiles, hipStream_t st);
+hipError_t launch_patch_tile_flags(int64_t n, int64_t m, int rings, const uint8_t* rtype, int ntypes,
+                                   uint8_t* flag, int64_t* n_tiles, hipStream_t st);
 bool patch_geometry_ok(int64_t n, int64_t m);
 int patch_un(int longest_row);
 int patch_default_umask(int un);
@@ -239,7 +245,10 @@ hipError_t launch_patch_down(bool first, int64_t n, int64_t m, const PatchRef& P
                              int64_t line_lo = 0, int64_t line_hi = -1, bool xf = false);
 // The patch launchers take a range of grid lines [line_lo, line_hi) (line_hi < 0: the whole
 // level): only the tiles that meet it run (row-block sharding, solver.cpp "slab").
-int patch_tile_lines();
+int patch_tile_lines(int rings);  // output lines of a tile: 48 - 2 rings
+// rings of a Jacobi leg on tall tiles: 3 for the level-0 down-leg (first: sweep, sweep, residual on
+// the loaded data), 2 for every other leg.  launch_patch_down refuses fewer rings than its leg needs.
+int patch_leg_rings(bool first);
 // u_out = two Jacobi sweeps of (x + P uH); u_out must not be x
 hipError_t launch_patch_up(int64_t n, int64_t m, const PatchRef& P, const double* x, const double* f,
                            const double* uH, int64_t nH, double* u_out, double omega,

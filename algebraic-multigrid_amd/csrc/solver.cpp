@@ -282,6 +282,7 @@ hipError_t device_galerkin_generic(const DevCsr& A, const DevCsr& P, const DevCs
 
 int g_patch_tile_flags = 1;  // amg_hip_set_patch_tile_flags: A/B switch (same bits either way)
 int g_patch_xf = 1;          // amg_hip_set_patch_xf: A/B switch (same bits either way)
+int g_patch_tall = 1;        // amg_hip_set_patch_tall: A/B switch (same bits either way)
 
 // A level matrix on the device in one of the two layouts the kernels take.
 struct DevMat {
@@ -312,15 +313,25 @@ struct DevMat {
   bool patch = false;
   int64_t patch_m = 0;
   int patch_un = 0, patch_ntypes = 0, patch_umask = 0;
-  DevMem patch_tab, patch_utabd, patch_utabi, patch_flags;
-  DevMem patch_cflags;      // per tile: the coarse rows under it share the diagonal patch_dH (set_patch_coarse_flags)
+  // A tile flag describes the rows a kernel loads for a tile, so there is one array per geometry:
+  // patch_flags for the launches with three halo rings (tiles of 42 lines), patch_flags2 for those
+  // with two (44 lines).  Both are built with the matrix (a byte per tile), whichever the level's
+  // launches turn out to use.
+  DevMem patch_tab, patch_utabd, patch_utabi, patch_flags, patch_flags2;
+  // per tile of the level's down-leg (patch_crings rings): the coarse rows under it share the
+  // diagonal patch_dH (set_patch_coarse_flags)
+  DevMem patch_cflags;
+  int patch_crings = 3;
   double patch_dH = 0.0;
-  double patch_cfrac = 0.0;  // fraction of the tiles whose flag is set (bytes accounting)
-  PatchRef patch_ref() const {
+  // fraction of the 42-line tiles whose coarse flag is set (bytes accounting: the model is stated
+  // on that tiling whatever the tile height of the launch, so it does not move with the geometry)
+  double patch_cfrac = 0.0;
+  PatchRef patch_ref(int rings = 3) const {
     PatchRef P;
+    P.rings = rings;
     P.rtype = drtype.as<uint8_t>();
-    P.tflag = g_patch_tile_flags ? patch_flags.as<uint8_t>() : nullptr;
-    P.cflag = g_patch_tile_flags ? patch_cflags.as<uint8_t>() : nullptr;
+    P.tflag = g_patch_tile_flags ? (rings == 2 ? patch_flags2 : patch_flags).as<uint8_t>() : nullptr;
+    P.cflag = g_patch_tile_flags && rings == patch_crings ? patch_cflags.as<uint8_t>() : nullptr;
     P.dHu = patch_dH;
     P.ptab = patch_tab.as<double>();
     P.utabd = patch_utabd.as<double>();
@@ -628,10 +639,13 @@ hipError_t finish_dict(const DictMat& T, int64_t n, int64_t diag_shift, DevMat* 
       if ((e = upload(D->patch_utabi, ui.data(), ui.size())) != hipSuccess) return e;
       // which patches consist of one row type only (the interior of the level)
       int64_t tiles = 0;
-      if ((e = launch_patch_tile_flags(n, D->patch_m, nullptr, nty, nullptr, &tiles, nullptr)) != hipSuccess) return e;
-      if ((e = D->patch_flags.alloc((size_t)tiles)) != hipSuccess) return e;
-      if ((e = launch_patch_tile_flags(n, D->patch_m, D->drtype.as<uint8_t>(), nty,
-                                       D->patch_flags.as<uint8_t>(), nullptr, nullptr)) != hipSuccess) return e;
+      for (int rings = 2; rings <= 3; ++rings) {  // (3 last: `tiles` below counts the 42-line tiles)
+        DevMem& F = rings == 2 ? D->patch_flags2 : D->patch_flags;
+        if ((e = launch_patch_tile_flags(n, D->patch_m, rings, nullptr, nty, nullptr, &tiles, nullptr)) != hipSuccess) return e;
+        if ((e = F.alloc((size_t)tiles)) != hipSuccess) return e;
+        if ((e = launch_patch_tile_flags(n, D->patch_m, rings, D->drtype.as<uint8_t>(), nty, F.as<uint8_t>(),
+                                         nullptr, nullptr)) != hipSuccess) return e;
+      }
       if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
       // the interior row type = the type most tiles consist of; its slots choose the kernel kind
       {
@@ -1360,6 +1374,7 @@ struct amg_hip_solver {
   amg_hip_options opt;
   int64_t patch_min_rows = g_patch_min_rows;  // the process-wide value when the solver was made
   int patch_xf = g_patch_xf;                  // likewise
+  int patch_tall = g_patch_tall;              // likewise
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = true;
@@ -1465,6 +1480,12 @@ bool patch_level_ok(const amg_hip_solver* s, int l) {
         L.n >= s->patch_min_rows && s->lv[l + 1].diag.p != nullptr))
     return false;
   return l == 0 || patch_level_ok(s, l - 1);
+}
+// Halo rings of a K-Patch Jacobi leg of this solver (first_down: the level-0 down-leg): the geometry of
+// the launch AND of the flag arrays handed to it (DevMat::patch_ref).  Tall legs off: the three-ring
+// frame of 42 lines everywhere.
+int patch_rings(const amg_hip_solver* s, bool first_down) {
+  return s->patch_tall ? patch_leg_rings(first_down) : 3;
 }
 // The hand-over between two K-Patch levels: the down-leg of level l + 1 forms its first sweep from
 // f_{l+1} (the xf form of patch_down_kernel), so the down-leg of level l stores f_{l+1} alone.  ONE
@@ -2002,7 +2023,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
       const bool first = l == 0;  // l >= 1: the first sweep came from level l-1's kernel (in tmp) ...
       const bool xf_in = l >= 1 && patch_xf_pair(s, l - 1);  // ... or is formed from f here
       const bool xf_out = patch_xf_pair(s, l);               // level l+1 forms its own: f_H only
-      HIP_TRY(launch_patch_down(first, L.n, A.patch_m, A.patch_ref(),
+      HIP_TRY(launch_patch_down(first, L.n, A.patch_m, A.patch_ref(patch_rings(s, first)),
                                 first ? L.u.as<double>() : (xf_in ? nullptr : L.tmp.as<double>()),
                                 L.f.as<double>(), first ? L.tmp.as<double>() : L.u.as<double>(),
                                 s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
@@ -2187,7 +2208,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
       const DevMat& A = L.A_rows;
       const bool top = l == 0;
       const double* uH = patch_level_ok(s, l + 1) ? C.tmp.as<double>() : C.u.as<double>();
-      HIP_TRY(launch_patch_up(L.n, A.patch_m, A.patch_ref(),
+      HIP_TRY(launch_patch_up(L.n, A.patch_m, A.patch_ref(patch_rings(s, false)),
                               top ? L.tmp.as<double>() : L.u.as<double>(), L.f.as<double>(), uH, C.n,
                               top ? L.u.as<double>() : L.tmp.as<double>(), s->opt.omega, st,
                               ranged ? sb.up_lo[l] : 0, ranged ? sb.up_hi[l] : -1));
@@ -2276,22 +2297,30 @@ amg_hip_status set_patch_coarse_flags(amg_hip_solver* s) {
     Level& C = s->lv[l + 1];
     DevMat& A = L.A_rows;
     if (!A.patch || !C.diag.p || C.n < 1) continue;
-    int64_t tiles = 0;
-    HIP_TRY(launch_patch_tile_flags(L.n, A.patch_m, nullptr, A.patch_ntypes, nullptr, &tiles, nullptr));
+    // geometry of the level's down-leg (the colour launches run on three rings)
+    const int rings = s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS ? 3 : patch_rings(s, l == 0);
     // reference value: the coarse row under the middle of the middle line (C.n / 2 would be a line end)
     const int64_t lines = (L.n + A.patch_m - 1) / A.patch_m;
     const int64_t cref = std::min<int64_t>(C.n - 1, ((lines / 2) * A.patch_m + A.patch_m / 2) >> 1);
     double dref = 0.0;
     HIP_TRY(hipMemcpy(&dref, C.diag.as<double>() + cref, sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(A.patch_cflags.alloc((size_t)tiles));
-    HIP_TRY(launch_patch_coarse_flags(L.n, A.patch_m, C.n, C.diag.as<double>(), dref,
-                                      A.patch_cflags.as<uint8_t>(), nullptr));
+    // the 42-line tiling first: its share of set flags is what the bytes model quotes (patch_cfrac);
+    // then, where the down-leg runs on other tiles, the flags of those
+    for (int rg = 3; rg >= rings; --rg) {
+      int64_t tiles = 0;
+      HIP_TRY(launch_patch_tile_flags(L.n, A.patch_m, rg, nullptr, A.patch_ntypes, nullptr, &tiles, nullptr));
+      HIP_TRY(A.patch_cflags.alloc((size_t)tiles));
+      HIP_TRY(launch_patch_coarse_flags(L.n, A.patch_m, rg, C.n, C.diag.as<double>(), dref,
+                                        A.patch_cflags.as<uint8_t>(), nullptr));
+      if (rg != 3) continue;
+      std::vector<uint8_t> fl((size_t)tiles);
+      HIP_TRY(hipMemcpy(fl.data(), A.patch_cflags.p, fl.size(), hipMemcpyDeviceToHost));
+      int64_t on = 0;
+      for (uint8_t f : fl) on += f != 0;
+      A.patch_cfrac = g_patch_tile_flags && tiles > 0 ? (double)on / (double)tiles : 0.0;
+    }
+    A.patch_crings = rings;
     A.patch_dH = dref;
-    std::vector<uint8_t> fl((size_t)tiles);
-    HIP_TRY(hipMemcpy(fl.data(), A.patch_cflags.p, fl.size(), hipMemcpyDeviceToHost));
-    int64_t on = 0;
-    for (uint8_t f : fl) on += f != 0;
-    A.patch_cfrac = g_patch_tile_flags && tiles > 0 ? (double)on / (double)tiles : 0.0;
   }
   HIP_TRY(hipDeviceSynchronize());
   return AMG_HIP_OK;
@@ -4085,6 +4114,7 @@ void amg_hip_set_dict_rows(int32_t rows_per_lane) { set_dict_rows_per_lane(rows_
 void amg_hip_set_dict_stencil(int32_t on) { set_dict_stencil(on); }
 void amg_hip_set_patch_tile_flags(int32_t on) { g_patch_tile_flags = on ? 1 : 0; }
 void amg_hip_set_patch_xf(int32_t on) { g_patch_xf = on ? 1 : 0; }
+void amg_hip_set_patch_tall(int32_t on) { g_patch_tall = on ? 1 : 0; }
 void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
 void amg_hip_set_patch_min_rows(int64_t rows) { g_patch_min_rows = rows < 0 ? INT64_MAX : rows; }
@@ -5346,6 +5376,13 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
   return AMG_HIP_OK;
 }
 
+int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t leg) {
+  if (!s || s->opt.host_only || level < 0 || level >= (int32_t)s->lv.size() || leg < 0 || leg > 1) return 0;
+  if (mc_patch_ok(s, level)) return patch_tile_lines(3);
+  if (!patch_level_ok(s, level)) return 0;
+  return patch_tile_lines(patch_rings(s, leg == 0 && level == 0));
+}
+
 amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int32_t name_cap,
                                        int32_t* sweeps_per_launch, double* bytes_per_launch) {
   if (!s || !name || name_cap < 32) return fail(AMG_HIP_EINVAL, "bad argument");
@@ -5393,12 +5430,12 @@ amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int3
   } else if (A.dict && patch_level_ok(s, 0)) {
     // row types + x + f + smoothed u per fine row; f_H and, unless level 1 forms it from f_H itself
     // (patch_xf_pair), the first coarse sweep and the coarse diagonal
-    std::snprintf(name, (size_t)name_cap, "patch_down_kernel<%d, %d, true, %s, false>", patch_un(A.patch_un),
+    std::snprintf(name, (size_t)name_cap, "patch_down_kernel<%d, %d, true, %s, false, 3>", patch_un(A.patch_un),
                   patch_kind_umask(A.patch_un, A.patch_umask), A.dict_nt ? "true" : "false");
     sweeps = 2;
     bytes = 25.0 * (double)L.n + (patch_xf_pair(s, 0) ? 8.0 : 24.0 - 8.0 * A.patch_cfrac) * (double)s->lv[1].n;
     if (s->slab.levels > 0 && s->slab.world > 1) {  // the tiles this rank's launch covers
-      const int64_t th = patch_tile_lines();
+      const int64_t th = patch_tile_lines(patch_rings(s, true));  // the level-0 down-leg's tiles
       const int64_t l0 = s->slab.down_lo[0] / th * th;
       const int64_t l1 = std::min<int64_t>(s->slab.lines, (s->slab.down_hi[0] + th - 1) / th * th);
       bytes *= (double)(l1 - l0) / (double)s->slab.lines;

@@ -265,6 +265,12 @@ void amg_hip_set_patch_tile_flags(int32_t on);
  * (one vector less written and read per level pair).  Process-wide, read when a solver is
  * created.  Same bits either way: an A/B switch for tests and measurements.              */
 void amg_hip_set_patch_xf(int32_t on);
+/* K-Patch tall legs: on (default), the Jacobi legs that run two dependent stencil stages on the data
+ * they load -- every up-leg and the down-legs of the levels >= 1 -- use tiles of 44 lines with two
+ * halo rings of lines instead of 42 with three; the level-0 down-leg (three stages) keeps 42.  Off:
+ * 42 lines everywhere.  Process-wide, read when a solver is created.  Same bits either way: an
+ * A/B switch for tests and measurements.                                                      */
+void amg_hip_set_patch_tall(int32_t on);
 /* K-BandChain (coarsest solve kind 3) on / off; process-wide, read when a solver is created.
  * Same bits either way: an A/B switch for tests and tuning.                             */
 void amg_hip_set_band_chain(int32_t on);
@@ -849,6 +855,9 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
  * afterwards.                                                                  */
 amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
                                           double* avg_ms, double* min_ms);
+/* Lines of the tiles the V-cycle of this solver launches on `level` for its down-leg (leg 0) or
+ * up-leg (leg 1): 42 or 44 on a K-Patch level, 0 where the level is no K-Patch level.        */
+int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t leg);
 /* Name of the kernel amg_hip_profile_fine_sweep times (as rocprofv3 prints it, without the
  * namespace), the number of Jacobi sweeps over level 0 one launch of it performs, and the
  * bytes one launch has to move (what the kernel reads and writes once: SURVEY 8(d)'s CSR

@@ -32,11 +32,12 @@ PATCH_LEVELS = 5            # levels 0-4 of the 4096^2 cycle are K-Patch levels 
 XF_HANDOVER = True          # set from the kernel names in main(): a patch_down_kernel<..., true> ran
 
 
-def patch_grid(l):
-    """threads of a K-Patch launch on level l: tiles of 42 lines x 64 columns, 432 threads each"""
+def patch_grids(l):
+    """threads of a K-Patch launch on level l: tiles of 42 lines (three halo rings) or 44 lines (two)
+    x 64 columns, 432 threads each"""
     n, m = LEVEL_ROWS[l], PITCH[l]
     lines = (n + m - 1) // m
-    return ((lines + 41) // 42) * (m // 64) * 432
+    return [((lines + th - 1) // th) * (m // 64) * 432 for th in (42, 44)]
 
 
 def classify(name, grid):
@@ -45,10 +46,10 @@ def classify(name, grid):
     if m:
         targs = m.group(2).split(", ")
         for l in range(len(LEVEL_ROWS)):
-            if patch_grid(l) == grid:
+            if grid in patch_grids(l):
                 if m.group(1) == "up":
                     return "patch_up", l, 0
-                # <slots, mask, first, nt, xf>: xf = the first sweep is formed from f, not loaded
+                # <slots, mask, first, nt, xf, rings>: xf = the first sweep is formed from f, not loaded
                 return ("patch_down_first" if targs[2] == "true" else
                         "patch_down_xf" if targs[4:5] == ["true"] else "patch_down"), l, 0
         return None, None, 0
@@ -123,7 +124,7 @@ def main():
                                "traffic_bytes": tr, "must_move_bytes": mm, "csr_formula_bytes": alg}
     lines += ["", "`must move` = what one launch has to read and write once (bench.py roofline.algorithmic_bytes_per_launch):",
               "dict_kernel: 1 B row type + f + x + out per row; the fused forms add their transfer operands;",
-              "patch_down_kernel<slots, mask, first, nt, xf>: the level's whole down-leg (x, f, type in; smoothed u, f_H, first coarse",
+              "patch_down_kernel<slots, mask, first, nt, xf, rings>: the level's whole down-leg (x, f, type in; smoothed u, f_H, first coarse",
               "sweep out; the coarse diagonal is a kernel argument under interior tiles; xf: x is formed from f and not read, and a",
               "level whose coarser level runs the xf form stores f_H alone), patch_up_kernel: the up-leg (x, f, type,",
               "u_H in; u out).  traffic / must move",
