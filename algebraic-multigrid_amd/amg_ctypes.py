@@ -124,6 +124,15 @@ _SIGS = {
                                                  C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_get_level_axes": (C.c_int, [C.c_void_p, C.c_int32, _i32p]),
     "amg_hip_get_natural_sides": (C.c_int, [C.c_void_p, _i32p]),
+    "amg_hip_create_tensor_periodic": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
+                                                 C.c_int32, C.c_int32, _i32p, C.POINTER(Options),
+                                                 C.POINTER(C.c_void_p)]),
+    "amg_hip_create_tensor_periodic_dev": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_int32, _i64p, C.c_int32, C.c_int32, _i32p,
+                                                     C.POINTER(Options), C.POINTER(C.c_void_p)]),
+    "amg_hip_get_periodic_axes": (C.c_int, [C.c_void_p, _i32p]),
+    "amg_hip_tensor_restrict_per": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p]),
+    "amg_hip_tensor_prolong_add_per": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p]),
     "amg_hip_tensor_restrict_bc": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int32, _f64p, _f64p]),
     "amg_hip_tensor_prolong_add_bc": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int32, _f64p, _f64p]),
     "amg_hip_tensor_axis_strength": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, C.c_int32, _i64p, _f64p]),
@@ -621,7 +630,7 @@ class Multigrid:
                stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
                no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
-               window=False, natural_sides=0, singular=False, _semi=None):
+               window=False, natural_sides=0, singular=False, _semi=None, _periodic=None):
         """AMG::Multigrid on a FULL-coarsening hierarchy of the grid `dims` = (nx, ny) or (nx, ny, nz),
         x fastest (amg_hip_create_tensor): every axis m -> m // 2, tensor-product linear interpolation,
         matrix-free transfer kernels unless stencil_transfers=False.  A is the caller's matrix on
@@ -646,7 +655,13 @@ class Multigrid:
         o.window = int(window)
         o.natural_sides, o.singular = int(natural_sides), int(singular)
         h = C.c_void_p()
-        if _semi is not None:  # tensor_semi
+        if _periodic is not None:  # tensor_periodic
+            per, masks = _periodic
+            st = lib().amg_hip_create_tensor_periodic(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
+                                                      d3.ctypes.data_as(_i64p), int(per), int(n_levels),
+                                                      None if masks is None else _p32(masks), C.byref(o),
+                                                      C.byref(h))
+        elif _semi is not None:  # tensor_semi
             masks, theta, min_coarse = _semi
             st = lib().amg_hip_create_tensor_semi(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
                                                   d3.ctypes.data_as(_i64p), int(n_levels),
@@ -669,7 +684,7 @@ class Multigrid:
                    no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                    exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
                    window=False, host_galerkin=False, fuse_prolong=False, natural_sides=0, singular=False,
-                   _semi=None):
+                   _semi=None, _periodic=None):
         """Multigrid.tensor for a matrix that sits on the device, with the set-up on the device
         (amg_hip_create_tensor_dev).  A is in CSR: crow (n + 1 int32 row pointers), col (int32,
         ascending inside a row), val (float64), and b (n float64), each a contiguous 1-D torch tensor
@@ -727,7 +742,13 @@ class Multigrid:
         self = cls.__new__(cls)
         self.tolerance, self.every, self.n_iters = tolerance, compute_error_every_n_iters, n_iters
         h = C.c_void_p()
-        if _semi is not None:  # tensor_semi_dev
+        if _periodic is not None:  # tensor_periodic_dev
+            per, masks = _periodic
+            st = lib().amg_hip_create_tensor_periodic_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
+                                                          d3.ctypes.data_as(_i64p), int(per), int(n_levels),
+                                                          None if masks is None else _p32(masks), C.byref(o),
+                                                          C.byref(h))
+        elif _semi is not None:  # tensor_semi_dev
             masks, theta, min_coarse = _semi
             st = lib().amg_hip_create_tensor_semi_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
                                                       d3.ctypes.data_as(_i64p), int(n_levels),
@@ -772,6 +793,26 @@ class Multigrid:
         (amg_hip_create_tensor_semi_dev); arguments as for Multigrid.tensor_dev."""
         return cls.tensor_dev(crow, col, val, b, dims, n_levels,
                               _semi=cls._semi_rule(n_levels, axis_masks, theta, min_coarse), **opts)
+
+    @classmethod
+    def tensor_periodic(cls, colptr, rowind, val, b, dims, n_levels, periodic_axes, axis_masks=None, **opts):
+        """Multigrid.tensor / tensor_semi for an operator with PERIODIC axes (amg_hip_create_tensor_periodic).
+        periodic_axes: bit a = axis a wraps around (1 = x, 2 = y, 4 = z); a coarsened periodic axis needs
+        an even length of at least 4 on its level and interpolates fine point 0 between coarse points 0
+        and m/2 - 1.  axis_masks=None: full coarsening with exactly n_levels levels, else n_levels - 1
+        explicit masks (there is no automatic rule).  natural_sides names sides of the other axes only;
+        singular=True needs all of those (none when every axis is periodic).  Options as for
+        Multigrid.tensor."""
+        masks = cls._semi_rule(n_levels, axis_masks, 0.5, 1)[0]
+        return cls.tensor(colptr, rowind, val, b, dims, n_levels, _periodic=(int(periodic_axes), masks), **opts)
+
+    @classmethod
+    def tensor_periodic_dev(cls, crow, col, val, b, dims, n_levels, periodic_axes, axis_masks=None, **opts):
+        """Multigrid.tensor_periodic for a CSR matrix that sits on the device
+        (amg_hip_create_tensor_periodic_dev); arguments as for Multigrid.tensor_dev.  The hierarchy is
+        built by the host constructor: setup_on_device() reports 0."""
+        masks = cls._semi_rule(n_levels, axis_masks, 0.5, 1)[0]
+        return cls.tensor_dev(crow, col, val, b, dims, n_levels, _periodic=(int(periodic_axes), masks), **opts)
 
     @classmethod
     def poisson_tensor(cls, n, n_levels, dim=2, device_setup=False, **opts):
@@ -827,6 +868,13 @@ class Multigrid:
             raise ValueError(lib().amg_hip_last_error().decode())
         _chk(st)
         return tuple(int(x) for x in d)
+
+    def periodic_axes(self):
+        """The solver's mask of periodic axes (amg_hip_get_periodic_axes); 0 on solvers that were not
+        made by tensor_periodic / tensor_periodic_dev."""
+        m = C.c_int32(0)
+        _chk(lib().amg_hip_get_periodic_axes(self._h, C.byref(m)))
+        return int(m.value)
 
     def natural_sides(self):
         """The solver's mask of natural boundary sides (amg_hip_get_natural_sides); 0 on solvers that
@@ -1332,17 +1380,22 @@ def tensor_axis_strength(colptr, rowind, val, dims):
     return w
 
 
-def tensor_restrict(dims, r, axes=None, natural_sides=0):
+def tensor_restrict(dims, r, axes=None, natural_sides=0, periodic_axes=0):
     """f_H = R r for the full-coarsening transfer of the fine grid `dims` (amg_hip_tensor_restrict);
     axes: the mask of coarsened axes instead (amg_hip_tensor_restrict_axes); natural_sides != 0: the
-    mask of sides without a Dirichlet condition (amg_hip_tensor_restrict_bc)."""
+    mask of sides without a Dirichlet condition (amg_hip_tensor_restrict_bc); periodic_axes != 0: the
+    mask of periodic axes (amg_hip_tensor_restrict_per)."""
     dim, d3 = _dims3(dims)
     r = _a64(r)
     n_h, n_H = _tensor_sizes(d3, dim, axes)
     if r.size != n_h:
         raise ValueError(f"`r` must have {n_h} entries, got {r.size}")
     out = np.empty(max(n_H, 0), np.float64)
-    if natural_sides:
+    if periodic_axes:
+        st = lib().amg_hip_tensor_restrict_per(dim, d3.ctypes.data_as(_i64p), (7 if dim == 3 else 3) if axes is None
+                                               else int(axes), int(natural_sides), int(periodic_axes), _p64(r),
+                                               _p64(out))
+    elif natural_sides:
         st = lib().amg_hip_tensor_restrict_bc(dim, d3.ctypes.data_as(_i64p), (7 if dim == 3 else 3) if axes is None
                                               else int(axes), int(natural_sides), _p64(r), _p64(out))
     elif axes is not None:
@@ -1355,16 +1408,21 @@ def tensor_restrict(dims, r, axes=None, natural_sides=0):
     return out
 
 
-def tensor_prolong_add(dims, u_H, u_h, axes=None, natural_sides=0):
+def tensor_prolong_add(dims, u_H, u_h, axes=None, natural_sides=0, periodic_axes=0):
     """u_h + P u_H for the same transfer (amg_hip_tensor_prolong_add, amg_hip_tensor_prolong_add_axes
-    with the mask `axes`, amg_hip_tensor_prolong_add_bc with natural_sides != 0); returns a new array."""
+    with the mask `axes`, amg_hip_tensor_prolong_add_bc with natural_sides != 0,
+    amg_hip_tensor_prolong_add_per with periodic_axes != 0); returns a new array."""
     dim, d3 = _dims3(dims)
     u_H = _a64(u_H)
     u_h = np.array(u_h, dtype=np.float64, copy=True)
     n_h, n_H = _tensor_sizes(d3, dim, axes)
     if u_h.size != n_h or u_H.size != n_H:
         raise ValueError(f"`u_h` / `u_H` must have {n_h} / {n_H} entries, got {u_h.size} / {u_H.size}")
-    if natural_sides:
+    if periodic_axes:
+        st = lib().amg_hip_tensor_prolong_add_per(dim, d3.ctypes.data_as(_i64p), (7 if dim == 3 else 3) if axes is None
+                                                  else int(axes), int(natural_sides), int(periodic_axes), _p64(u_H),
+                                                  _p64(u_h))
+    elif natural_sides:
         st = lib().amg_hip_tensor_prolong_add_bc(dim, d3.ctypes.data_as(_i64p), (7 if dim == 3 else 3) if axes is None
                                                  else int(axes), int(natural_sides), _p64(u_H), _p64(u_h))
     elif axes is not None:

@@ -190,7 +190,10 @@ static inline double w1n(int64_t J, int t, int64_t m, uint32_t lo, uint32_t hi) 
   if (t == 0) return (lo && J == 0) ? 1.0 : 0.5;
   return (hi && 2 * J + 2 == m - 1) ? 1.0 : 0.5;
 }
-Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask, uint32_t sides) {
+// periodic: bit a = axis a is periodic.  A coarsened periodic axis of even length m >= 4 takes
+// P1per(m) = P1(m) plus the entry (0, m/2 - 1) = 0.5: the third fine point of the last coarse point
+// is (2 J + 2) mod m = 0.  The rows of a column stay ascending, so the wrapped point comes first.
+Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask, uint32_t sides, uint32_t periodic) {
   int64_t c[3];
   tensor_coarse_dims(dim, d, mask, c);
   const int64_t nx = d[0], ny = d[1], nz = dim == 3 ? d[2] : 1;
@@ -206,23 +209,30 @@ Sparse tensor_P(int dim, const int64_t d[3], uint32_t mask, uint32_t sides) {
   const uint32_t lx = sides & 1u, hx = (sides >> 1) & 1u, ly = (sides >> 2) & 1u, hy = (sides >> 3) & 1u,
                  lz = (sides >> 4) & 1u, hz = (sides >> 5) & 1u;
   const int tx_n = cx ? 3 : 1, ty_n = cy ? 3 : 1, tz_n = cz ? 3 : 1;
+  const bool px = cx && (periodic & 1u), py = cy && (periodic & 2u), pz = cz && (periodic & 4u);
+  // the t-th fine point (ascending) of coarse point J on a coarsened axis of length m and its weight;
+  // at the seam of a periodic axis the points are 0, m - 2, m - 1 with 0.5, 0.5, 1.0
+  struct Pt { int64_t i; double w; };
+  auto point = [](int64_t J, int t, int64_t m, bool per, uint32_t lo, uint32_t hi) -> Pt {
+    if (per && 2 * J + 2 == m) return t == 0 ? Pt{0, 0.5} : Pt{2 * J + t - 1, t == 2 ? 1.0 : 0.5};
+    return Pt{2 * J + t, w1n(J, t, m, lo, hi)};
+  };
   int64_t col = 0;
   for (int64_t K = 0; K < c[2]; ++K)
     for (int64_t J = 0; J < c[1]; ++J)
       for (int64_t I = 0; I < c[0]; ++I) {
         for (int tz = 0; tz < tz_n; ++tz) {  // ascending fine row: k, then j, then i
-          const int64_t k = cz ? 2 * K + tz : K;
-          if (k >= nz) continue;
-          const double wz = cz ? w1n(K, tz, nz, lz, hz) : 1.0;
+          const Pt z = cz ? point(K, tz, nz, pz, lz, hz) : Pt{K, 1.0};
+          if (z.i >= nz) continue;
           for (int ty = 0; ty < ty_n; ++ty) {
-            const int64_t j = cy ? 2 * J + ty : J;
-            if (j >= ny) continue;
-            const double wzy = wz * (cy ? w1n(J, ty, ny, ly, hy) : 1.0);
+            const Pt y = cy ? point(J, ty, ny, py, ly, hy) : Pt{J, 1.0};
+            if (y.i >= ny) continue;
+            const double wzy = z.w * y.w;
             for (int tx = 0; tx < tx_n; ++tx) {
-              const int64_t i = cx ? 2 * I + tx : I;
-              if (i >= nx) continue;
-              P.idx.push_back((int32_t)((k * ny + j) * nx + i));
-              P.val.push_back(wzy * (cx ? w1n(I, tx, nx, lx, hx) : 1.0));  // products of powers of two: exact
+              const Pt x = cx ? point(I, tx, nx, px, lx, hx) : Pt{I, 1.0};
+              if (x.i >= nx) continue;
+              P.idx.push_back((int32_t)((z.i * ny + y.i) * nx + x.i));
+              P.val.push_back(wzy * x.w);  // products of powers of two: exact
             }
           }
         }

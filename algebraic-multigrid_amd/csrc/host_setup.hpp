@@ -48,7 +48,12 @@ void tensor_coarse_dims(int dim, const int64_t dims[3], uint32_t mask, int64_t c
 // Natural boundary sides (amg_hip.h: opts->natural_sides): bit 2a = the low side of axis a, bit 2a + 1
 // its high side.  On a flagged side of a coarsened axis the boundary row of P1(m) -- row 0, row m - 1
 // of an odd m -- holds 1.0 instead of 0.5; the pattern is the same.  sides = 0: every side Dirichlet.
-Sparse tensor_P(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides);
+// Periodic axes (amg_hip.h: amg_hip_create_tensor_periodic): bit a of `periodic` = axis a.  A
+// coarsened periodic axis has an even length m >= 4 (the caller checks) and no side bits; its factor
+// is P1per(m), m x m/2 with 0.5, 1.0, 0.5 on rows 2j, 2j+1, (2j+2) mod m of column j -- P1(m) plus
+// the entry (0, m/2 - 1).  Every row sums to 1.  The rows of each CSC column ascend: in the last
+// column of a periodic axis the wrapped row 0 comes first.  periodic = 0: no periodic axis.
+Sparse tensor_P(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic);
 // The automatic rule.  w[a] = max |a_ij| over the entries of A (rows_as: either compressed form,
 // the maximum does not depend on it) whose column's grid coordinates differ from the row's by
 // +-1 in axis a and by 0 in the others; 0 when there is none.  A maximum of non-negative doubles

@@ -3161,11 +3161,19 @@ hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
 // Natural boundary sides (amg_hip.h: opts->natural_sides; host_setup.hpp: tensor_P with sides): on a
 // flagged side the boundary row of P1 carries 1.0 instead of 0.5 -- fine point 0 (low side), fine
 // point n - 1 of an odd n (high side).  Still powers of two, the same terms in the same order.
+// Periodic axes (amg_hip.h: amg_hip_create_tensor_periodic; host_setup.hpp: tensor_P with periodic):
+// a coarsened periodic axis has an even length n >= 4 and P1per(n) = P1(n) plus the entry
+// (0, n / 2 - 1) = 0.5.  Coarse point n / 2 - 1 then has the fine points 0, n - 2, n - 1 (ascending)
+// with weights 0.5, 0.5, 1.0, and fine point 0 the coarse points 0 and n / 2 - 1, 0.5 each.  The
+// kernels' PER instantiation knows the seam; PER = false is the code without it, unchanged.
 struct TensorGrid {
   uint32_t nx, ny, nz;  // fine
   uint32_t mx, my, mz;  // coarse (m == n on an axis that is not coarsened)
   uint32_t cx, cy, cz;  // 1: the axis is coarsened
   uint32_t sides;       // bit 2a: low side of axis a is natural, bit 2a + 1: its high side
+                        // bit 8 + a: axis a is periodic AND coarsened (its side bits are 0, n even, >= 4);
+                        // kept in the same word so that the kernels' arguments lie where they lay
+  __host__ __device__ uint32_t per() const { return sides >> 8; }
 };
 // P1N(2 J + t, J) on a coarsened axis of n fine points, t = 0, 1, 2; lo / hi: the axis' side bits
 template <class T>
@@ -3180,7 +3188,9 @@ __device__ __forceinline__ T tn_weight(uint32_t J, uint32_t t, uint32_t n, uint3
 // 16-byte load where the address allows (always, on rows of even length), 2I+2 as a scalar load of
 // the line the next lane's pair sits in.  r is dead after this kernel.  VEC: r is 16-byte aligned
 // (T = float, K-F32: the pair is 8 bytes and r 8-byte aligned; the weights are exact in float too).
-template <class T, bool VEC>
+// PER: the last coarse point of a periodic axis takes fine point 0 first (ascending fine index);
+// on x that point is the first entry of the same line, a scalar load next to the pair (2I, 2I+1).
+template <class T, bool VEC, bool PER>
 __global__ __launch_bounds__(256) void tensor_restrict_kernel(
     TensorGrid g, const T* __restrict__ r, T* __restrict__ fH, T* __restrict__ uH) {
   using P2 = typename Pair<T>::type;
@@ -3193,19 +3203,26 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
   const bool third = i0 + 2u < g.nx;
   const T wx0 = tn_weight<T>(I, 0u, g.nx, g.sides & 1u, g.sides & 2u);
   const T wx2 = tn_weight<T>(I, 2u, g.nx, g.sides & 1u, g.sides & 2u);
+  // PER: this lane's coarse point is the last one of a periodic axis (2 m == n there, m >= 2)
+  const bool seamx = PER && (g.per() & 1u) && i0 + 2u == g.nx;
+  const bool seamy = PER && (g.per() & 2u) && 2u * J + 2u == g.ny;
+  const bool seamz = PER && (g.per() & 4u) && 2u * K + 2u == g.nz;
   T s = T(0.0);
 #pragma unroll
   for (uint32_t tz = 0; tz < 3; ++tz) {
     if (!g.cz && tz > 0) break;
-    const uint32_t k = g.cz ? 2u * K + tz : K;
+    // seam: fine points 0, n - 2, n - 1 with weights 0.5, 0.5, 1.0
+    const uint32_t k = seamz ? (tz == 0u ? 0u : 2u * K + tz - 1u) : (g.cz ? 2u * K + tz : K);
     if (k >= g.nz) break;
-    const T wz = g.cz ? tn_weight<T>(K, tz, g.nz, g.sides & 16u, g.sides & 32u) : T(1.0);
+    const T wz = seamz ? (tz == 2u ? T(1.0) : T(0.5))
+                       : (g.cz ? tn_weight<T>(K, tz, g.nz, g.sides & 16u, g.sides & 32u) : T(1.0));
 #pragma unroll
     for (uint32_t ty = 0; ty < 3; ++ty) {
       if (!g.cy && ty > 0) break;
-      const uint32_t j = g.cy ? 2u * J + ty : J;
+      const uint32_t j = seamy ? (ty == 0u ? 0u : 2u * J + ty - 1u) : (g.cy ? 2u * J + ty : J);
       if (j >= g.ny) break;
-      const T w = wz * (g.cy ? tn_weight<T>(J, ty, g.ny, g.sides & 4u, g.sides & 8u) : T(1.0));
+      const T w = wz * (seamy ? (ty == 2u ? T(1.0) : T(0.5))
+                              : (g.cy ? tn_weight<T>(J, ty, g.ny, g.sides & 4u, g.sides & 8u) : T(1.0)));
       const int64_t a = ((int64_t)k * g.ny + j) * g.nx + i0;  // a + 1 (and a + 2 when third) < n_h
       if (!g.cx) {  // x is not coarsened: the one fine point I, neighbouring lanes read neighbours
         s += (w * T(1.0)) * r[a];
@@ -3227,6 +3244,7 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
         v1 = r[a + 1];
         if (third) v2 = r[a + 2];
       }
+      if (seamx) s += (w * T(0.5)) * r[a - i0];  // fine point 0 of this line (i0 = nx - 2, third is false)
       s += (w * wx0) * v0;
       s += (w * T(1.0)) * v1;
       if (third) s += (w * wx2) * v2;
@@ -3241,7 +3259,9 @@ __global__ __launch_bounds__(256) void tensor_restrict_kernel(
 // weight 1, an even one i / 2 - 1 and i / 2 with weight 0.5 (those that exist).  On an axis that is
 // not coarsened a fine point has the one coarse neighbour of its own index with weight 1; along x
 // the lane's fine pair then reads the coarse pair (2p, 2p+1), 16 bytes where that address allows.
-template <class T, bool VEC>
+// PER: fine point 0 of a periodic axis has the coarse neighbours 0 and m - 1, in that order, 0.5
+// each; on x that is lane p = 0 of every line, whose wrapped term comes after the `mid` term.
+template <class T, bool VEC, bool PER>
 __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
     TensorGrid g, const T* __restrict__ uH, T* uh) {
   using P2 = typename Pair<T>::type;
@@ -3257,6 +3277,9 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   if (!g.cy) {
     Jc[0] = j; wy[0] = 1.0; oky[0] = true;
     Jc[1] = 0; wy[1] = 0.0; oky[1] = false;
+  } else if (PER && (g.per() & 2u) && j == 0u) {
+    Jc[0] = 0; wy[0] = 0.5; oky[0] = true;
+    Jc[1] = g.my - 1u; wy[1] = 0.5; oky[1] = true;  // my >= 2
   } else if (j & 1u) {
     Jc[0] = (j - 1u) / 2u; wy[0] = 1.0; oky[0] = Jc[0] < g.my;
     Jc[1] = 0; wy[1] = 0.0; oky[1] = false;
@@ -3267,6 +3290,9 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   if (!g.cz) {
     Kc[0] = k; wz[0] = 1.0; okz[0] = true;
     Kc[1] = 0; wz[1] = 0.0; okz[1] = false;
+  } else if (PER && (g.per() & 4u) && k == 0u) {
+    Kc[0] = 0; wz[0] = 0.5; okz[0] = true;
+    Kc[1] = g.mz - 1u; wz[1] = 0.5; okz[1] = true;  // mz >= 2
   } else if (k & 1u) {
     Kc[0] = (k - 1u) / 2u; wz[0] = 1.0; okz[0] = Kc[0] < g.mz;
     Kc[1] = 0; wz[1] = 0.0; okz[1] = false;
@@ -3277,6 +3303,7 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   const bool left = g.cx && p >= 1u && p - 1u < g.mx;  // coarse I = p - 1 feeds fine 2p
   const bool mid = g.cx && p < g.mx;                   // coarse I = p feeds fine 2p and 2p + 1
   const bool two = 2u * p + 1u < g.nx;                 // the lane's pair is whole
+  const bool wrap = PER && (g.per() & 1u) && p == 0u;    // coarse I = mx - 1 feeds fine 0 (mx >= 2: mid holds)
   // fine 2p is the last point of an odd line / the first point: the natural sides' weight 1
   const T wl = ((g.sides & 2u) && 2u * p + 1u == g.nx) ? T(1.0) : T(0.5);
   const T wm = ((g.sides & 1u) && p == 0u) ? T(1.0) : T(0.5);
@@ -3305,6 +3332,7 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
           t0 += (w * wm) * m;
           t1 += (w * T(1.0)) * m;
         }
+        if (wrap) t0 += (w * T(0.5)) * c[g.mx - 1u];
       }
     }
   }
@@ -3324,10 +3352,17 @@ __global__ __launch_bounds__(256) void tensor_prolong_add_kernel(
   }
 }
 
-static bool tensor_grid(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, TensorGrid* g) {
+static bool tensor_grid(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                        TensorGrid* g) {
   if ((dim != 2 && dim != 3) || !dims) return false;
   if (sides >= (1u << (2 * dim))) return false;
-  g->sides = sides;
+  if (periodic >= (1u << dim)) return false;
+  for (int a = 0; a < dim; ++a)  // a periodic axis has no sides; coarsened, it is even and >= 4
+    if ((periodic >> a) & 1u) {
+      if ((sides >> (2 * a)) & 3u) return false;
+      if (((mask >> a) & 1u) && (dims[a] < 4 || (dims[a] & 1))) return false;
+    }
+  g->sides = sides | ((periodic & mask) << 8);
   if (mask == 0u || mask > (dim == 3 ? 7u : 3u)) return false;
   const int64_t nx = dims[0], ny = dims[1], nz = dim == 3 ? dims[2] : 1;
   if (nx < 1 || ny < 1 || nz < 1 || (dim == 2 && dims[2] != 1)) return false;
@@ -3345,38 +3380,48 @@ static bool tensor_grid(int dim, const int64_t dims[3], uint32_t mask, uint32_t 
   return true;
 }
 template <class T>
-static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const T* r, T* fH, T* uH_zero,
-                                           hipStream_t st) {
+static hipError_t launch_tensor_restrict_t(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                                           const T* r, T* fH, T* uH_zero, hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, mask, sides, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, sides, periodic, &g)) return hipErrorInvalidValue;
   const uint32_t nH = g.mx * g.my * g.mz;
   const dim3 grid((nH + 255u) / 256u), block(256);
-  if (pair_aligned(r))
-    hipLaunchKernelGGL((tensor_restrict_kernel<T, true>), grid, block, 0, st, g, r, fH, uH_zero);
+  if (g.per()) {  // a seam on a coarsened axis
+    if (pair_aligned(r))
+      hipLaunchKernelGGL((tensor_restrict_kernel<T, true, true>), grid, block, 0, st, g, r, fH, uH_zero);
+    else
+      hipLaunchKernelGGL((tensor_restrict_kernel<T, false, true>), grid, block, 0, st, g, r, fH, uH_zero);
+  } else if (pair_aligned(r))
+    hipLaunchKernelGGL((tensor_restrict_kernel<T, true, false>), grid, block, 0, st, g, r, fH, uH_zero);
   else
-    hipLaunchKernelGGL((tensor_restrict_kernel<T, false>), grid, block, 0, st, g, r, fH, uH_zero);
+    hipLaunchKernelGGL((tensor_restrict_kernel<T, false, false>), grid, block, 0, st, g, r, fH, uH_zero);
   return hipGetLastError();
 }
-hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const double* r, double* fH,
-                                  double* uH_zero, hipStream_t st) {
-  return launch_tensor_restrict_t<double>(dim, dims, mask, sides, r, fH, uH_zero, st);
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                                  const double* r, double* fH, double* uH_zero, hipStream_t st) {
+  return launch_tensor_restrict_t<double>(dim, dims, mask, sides, periodic, r, fH, uH_zero, st);
 }
 template <class T>
-static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const T* uH, T* uh,
-                                              hipStream_t st) {
+static hipError_t launch_tensor_prolong_add_t(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                                              const T* uH, T* uh, hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, mask, sides, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, sides, periodic, &g)) return hipErrorInvalidValue;
   const uint32_t total = ((g.nx + 1u) / 2u) * g.ny * g.nz;
   const dim3 grid((total + 255u) / 256u), block(256);
-  if (pair_aligned(uh))
-    hipLaunchKernelGGL((tensor_prolong_add_kernel<T, true>), grid, block, 0, st, g, uH, uh);
+  if (g.per()) {
+    if (pair_aligned(uh))
+      hipLaunchKernelGGL((tensor_prolong_add_kernel<T, true, true>), grid, block, 0, st, g, uH, uh);
+    else
+      hipLaunchKernelGGL((tensor_prolong_add_kernel<T, false, true>), grid, block, 0, st, g, uH, uh);
+  } else if (pair_aligned(uh))
+    hipLaunchKernelGGL((tensor_prolong_add_kernel<T, true, false>), grid, block, 0, st, g, uH, uh);
   else
-    hipLaunchKernelGGL((tensor_prolong_add_kernel<T, false>), grid, block, 0, st, g, uH, uh);
+    hipLaunchKernelGGL((tensor_prolong_add_kernel<T, false, false>), grid, block, 0, st, g, uH, uh);
   return hipGetLastError();
 }
-hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const double* uH, double* uh,
-                                     hipStream_t st) {
-  return launch_tensor_prolong_add_t<double>(dim, dims, mask, sides, uH, uh, st);
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                                     const double* uH, double* uh, hipStream_t st) {
+  return launch_tensor_prolong_add_t<double>(dim, dims, mask, sides, periodic, uH, uh, st);
 }
 
 // First Jacobi sweep from a zero guess (coarse levels on the way down,
@@ -5676,7 +5721,7 @@ hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uin
                                   const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
                                   hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, mask, sides, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, sides, 0u, &g)) return hipErrorInvalidValue;
   const uint32_t nH = g.mx * g.my * g.mz;
   const double inv_nx = 1.0 / (double)g.nx, inv_ny = 1.0 / (double)g.ny;
 #define TG_LAUNCH(SLOTS, FILL)                                                                        \
@@ -7242,13 +7287,13 @@ hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, 
 hipError_t launch_linear_prolong_add_f32(int64_t n_h, int64_t n_H, const float* uH, float* uh, hipStream_t st) {
   return launch_linear_prolong_add_t<float>(n_h, n_H, uH, uh, st);
 }
-hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const float* r, float* fH, float* uH_zero,
+hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st) {
-  return launch_tensor_restrict_t<float>(dim, dims, mask, sides, r, fH, uH_zero, st);
+  return launch_tensor_restrict_t<float>(dim, dims, mask, sides, periodic, r, fH, uH_zero, st);
 }
-hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const float* uH, float* uh,
+hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic, const float* uH, float* uh,
                                          hipStream_t st) {
-  return launch_tensor_prolong_add_t<float>(dim, dims, mask, sides, uH, uh, st);
+  return launch_tensor_prolong_add_t<float>(dim, dims, mask, sides, periodic, uH, uh, st);
 }
 
 

@@ -341,12 +341,16 @@ hipError_t launch_linear_prolong_add(int64_t n_h, int64_t n_H, const double* uH,
 // for full coarsening; an axis outside the mask keeps its length (identity) and may have 1 point.
 // sides: the natural boundary sides (bit 2a = low side of axis a, 2a + 1 = high side; host_setup.hpp:
 // tensor_P with sides), 0 = every side Dirichlet; bits at or above 2 dim: hipErrorInvalidValue.
+// periodic: the periodic axes (bit a = axis a; host_setup.hpp: tensor_P with periodic), 0 = none.  A
+// periodic axis has no side bits and, where the mask coarsens it, an even length of at least 4; bits
+// at or above dim: hipErrorInvalidValue.  With no coarsened periodic axis the launch is the one of
+// periodic = 0, the same kernel and the same bits.
 // f_H = R r, uH_zero (may be null) zero-filled in the same pass
-hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const double* r, double* fH,
-                                  double* uH_zero, hipStream_t st);
+hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                                  const double* r, double* fH, double* uH_zero, hipStream_t st);
 // u_h = u_h + P u_H
-hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const double* uH, double* uh,
-                                     hipStream_t st);
+hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                                     const double* uH, double* uh, hipStream_t st);
 // x[j * stride] = +0.0 for j < count (count <= 64, else hipErrorInvalidValue)
 hipError_t launch_zero_strided(double* x, int64_t stride, int count, hipStream_t st);
 hipError_t launch_add_inplace(int64_t n, const double* x, double* y, hipStream_t st);
@@ -573,9 +577,9 @@ hipError_t launch_to_f64(int64_t n, const float* src, double* dst, hipStream_t s
 hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st);
 hipError_t launch_linear_prolong_add_f32(int64_t n_h, int64_t n_H, const float* uH, float* uh, hipStream_t st);
-hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const float* r, float* fH, float* uH_zero,
+hipError_t launch_tensor_restrict_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st);
-hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const float* uH, float* uh,
+hipError_t launch_tensor_prolong_add_f32(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic, const float* uH, float* uh,
                                          hipStream_t st);
 
 }  // namespace amg_hip

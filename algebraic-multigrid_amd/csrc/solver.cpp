@@ -1231,7 +1231,7 @@ struct Level {
   int64_t n_coarse = 0;
   const Sparse& P() const {
     if (lazy_linear && P_csc.ptr.empty()) P_csc = linear_P(n, n_coarse);  // interpolator.hpp:106-129
-    if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims, tmask, tsides);
+    if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims, tmask, tsides, tper);
     return P_csc;
   }
   const Sparse& R() const {
@@ -1250,6 +1250,7 @@ struct Level {
   bool tensor = false, tensor_stencil = false;
   uint32_t tmask = 0;
   uint32_t tsides = 0;  // the solver's natural boundary sides (opt.natural_sides), the same on every level
+  uint32_t tper = 0;    // the solver's periodic axes (amg_hip_create_tensor_periodic), the same on every level
   DevCsr P_rows, R_rows;   // CSR(P), CSR(R)
   // exact lexicographic schedules
   std::unique_ptr<LexOnDev> lex_fwd, lex_bwd;
@@ -2133,7 +2134,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
                                        zero_known ? nullptr : C.u.as<double>(), st));
         s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
       } else if (L.tensor_stencil) {                               // the same two steps, full coarsening
-        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.r.as<double>(), C.f.as<double>(),
+        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(),
                                        zero_known ? nullptr : C.u.as<double>(), st));
         s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
       } else {
@@ -2240,7 +2241,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
       s->acct(8.0 * C.n + 16.0 * L.n);
     } else if (L.tensor_stencil) {
-      HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, C.u.as<double>(), L.u.as<double>(), st));
+      HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
       s->acct(8.0 * C.n + 16.0 * L.n);
     } else {
       const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
@@ -2385,7 +2386,9 @@ const char* const SINGULAR_ONE_LEVEL =
     "the caller's own right-hand side";
 // "" or what is wrong with opt.natural_sides / opt.singular; dim = 0: a constructor without level
 // grids, which takes neither
-std::string sides_error(const amg_hip_options& o, int dim) {
+// periodic (amg_hip_create_tensor_periodic, != 0): a periodic axis has no sides, and `singular` needs
+// the sides of the other axes only
+std::string sides_error(const amg_hip_options& o, int dim, uint32_t periodic = 0) {
   if (o.singular != 0 && o.singular != 1)
     return "`singular` must be 0 or 1, got " + std::to_string(o.singular);
   if (!dim) {
@@ -2399,6 +2402,23 @@ std::string sides_error(const amg_hip_options& o, int dim) {
   if (o.natural_sides < 0 || o.natural_sides >= (1 << (2 * dim)))
     return "`natural_sides` = " + std::to_string(o.natural_sides) + " has bits other than the " + std::to_string(2 * dim) +
            " sides of a " + std::to_string(dim) + "-D grid (bit 2a = low side of axis a, bit 2a + 1 = high side)";
+  if (periodic) {
+    int want = 0;
+    for (int a = 0; a < dim; ++a) {
+      if (!((periodic >> a) & 1u)) {
+        want |= 3 << (2 * a);
+      } else if ((o.natural_sides >> (2 * a)) & 3) {
+        return "`natural_sides` = " + std::to_string(o.natural_sides) + " names a side of axis " +
+               std::string(1, "xyz"[a]) + ", which `periodic_axes` = " + std::to_string(periodic) +
+               " makes periodic: a periodic axis has no sides";
+      }
+    }
+    if (o.singular && o.natural_sides != want)
+      return "`singular` = 1 needs every side of the axes that are not periodic natural: `natural_sides` = " +
+             std::to_string(want) + " with `periodic_axes` = " + std::to_string(periodic) + ", got " +
+             std::to_string(o.natural_sides);
+    return "";
+  }
   if (o.singular && o.natural_sides != (1 << (2 * dim)) - 1)
     return "`singular` = 1 needs every side natural: `natural_sides` = " + std::to_string((1 << (2 * dim)) - 1) + ", got " +
            std::to_string(o.natural_sides);
@@ -2417,6 +2437,24 @@ std::string semi_mask_error(int l, int dim, const int64_t d[3], int64_t mask) {
              std::to_string(d[2]) + ")";
   return "";
 }
+// "" or what is wrong with `periodic_axes` itself
+std::string periodic_axes_error(int dim, int64_t periodic) {
+  if (periodic < 0 || periodic >= (1 << dim))
+    return "`periodic_axes` = " + std::to_string(periodic) + " has bits other than the " + std::to_string(dim) +
+           " axes of a " + std::to_string(dim) + "-D grid (bit a = axis a: 1 = x, 2 = y, 4 = z)";
+  return "";
+}
+// "" or the periodic axis that level l (grid d) cannot coarsen: P1per needs an even length of at least 4
+std::string periodic_level_error(int l, int dim, const int64_t d[3], uint32_t mask, uint32_t periodic) {
+  for (int a = 0; a < dim; ++a)
+    if (((mask & periodic) >> a) & 1u)
+      if (d[a] < 4 || (d[a] & 1))
+        return "level " + std::to_string(l) + ": `periodic_axes` = " + std::to_string(periodic) + " makes axis " +
+               std::string(1, "xyz"[a]) + " periodic, and it has " + std::to_string(d[a]) +
+               " points on this level; a coarsened periodic axis needs an even length of at least 4 (the grid is " +
+               std::to_string(d[0]) + " x " + std::to_string(d[1]) + " x " + std::to_string(d[2]) + ")";
+  return "";
+}
 
 amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* rowind,
                             const double* val, const double* b, int32_t n_levels,
@@ -2425,7 +2463,8 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
                             const int32_t* const* Rr, const double* const* Rv,
                             const amg_hip_options* opts, amg_hip_solver** out,
                             double rs_theta = -1.0, int64_t rs_min_coarse = 0, int tensor_dim = 0,
-                            const int64_t* tensor_dims = nullptr, const SemiRule* semi = nullptr) {
+                            const int64_t* tensor_dims = nullptr, const SemiRule* semi = nullptr,
+                            uint32_t tensor_periodic = 0) {
   if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
   *out = nullptr;
   if (!colptr || !rowind || !val || !b) return fail(AMG_HIP_EINVAL, "null input array");
@@ -2438,7 +2477,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_LINE_ALT)
     return fail(AMG_HIP_EINVAL, "unknown smoother kind");
   {
-    const std::string e = sides_error(s->opt, tensor_dim);
+    const std::string e = sides_error(s->opt, tensor_dim, tensor_periodic);
     if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
     if (s->opt.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
   }
@@ -2526,6 +2565,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   for (int l = 0; l < n_levels; ++l) {
     Level& L = s->lv[l];
     if (tensor_dim) L.tsides = (uint32_t)s->opt.natural_sides;
+    if (tensor_dim) L.tper = tensor_periodic;
     if (tensor_dim && l + 1 < n_levels) {  // the axes this level coarsens
       L.tmask = tensor_full_mask(tensor_dim);
       if (semi && semi->masks) {
@@ -2762,7 +2802,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       // the matrix-free kernels index lanes with 32 bits (kernels.hip: tensor_grid)
       L.tensor_stencil = s->opt.stencil_transfers && L.n < ((int64_t)1 << 31) - 4;
       if (!L.tensor_stencil) {
-        L.P_csc = tensor_P(tensor_dim, L.dims, L.tmask, L.tsides);
+        L.P_csc = tensor_P(tensor_dim, L.dims, L.tmask, L.tsides, L.tper);
         L.R_csc = transpose(L.P_csc);
       }
     } else if (n_H < 1) {
@@ -3997,7 +4037,7 @@ amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
       F32_DO(launch_linear_restrict_f32(L.n, C.n, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
       s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
     } else if (L.tensor_stencil) {
-      F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, L.tsides, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
+      F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
       s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
     } else {
       F32_DO(hipMemsetAsync(QC.u.p, 0, sizeof(float) * (size_t)C.n, st));
@@ -4025,7 +4065,7 @@ amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
       F32_DO(launch_linear_prolong_add_f32(L.n, C.n, QC.u.as<float>(), Q.u.as<float>(), st));
       s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
     } else if (L.tensor_stencil) {
-      F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, L.tsides, QC.u.as<float>(), Q.u.as<float>(), st));
+      F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, QC.u.as<float>(), Q.u.as<float>(), st));
       s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
     } else {
       const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
@@ -4240,6 +4280,68 @@ amg_hip_status amg_hip_get_natural_sides(const amg_hip_solver* s, int32_t* mask)
   return AMG_HIP_OK;
 }
 
+amg_hip_status amg_hip_get_periodic_axes(const amg_hip_solver* s, int32_t* mask) {
+  if (!s || !mask) return fail(AMG_HIP_EINVAL, "null argument");
+  *mask = (!s->lv.empty() && s->lv[0].tdim) ? (int32_t)s->lv[0].tper : 0;
+  return AMG_HIP_OK;
+}
+
+// The argument checks of the periodic constructors that need no matrix, before any device call:
+// those of amg_hip_create_tensor (axis_masks null) or of amg_hip_create_tensor_semi with explicit
+// masks, then the periodic mask on every level's grid, then the sides a periodic axis cannot have.
+static amg_hip_status periodic_args(const std::string& who, int64_t n, int32_t dim, const int64_t* dims,
+                                    int32_t periodic_axes, int32_t n_levels, const int32_t* axis_masks,
+                                    const amg_hip_options& o, SemiRule* rule) {
+  const std::string e = tensor_dims_error(dim, dims);
+  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
+  if (n != dims[0] * dims[1] * dims[2])
+    return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
+                                    " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
+                                    " grid of `dims`");
+  if (o.window)
+    return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a " +
+                                          (axis_masks ? "semi" : "full") + "-coarsening hierarchy is not sharded");
+  const std::string pe = periodic_axes_error(dim, periodic_axes);
+  if (!pe.empty()) return fail(AMG_HIP_EINVAL, who + pe);
+  if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
+  rule->masks = axis_masks;
+  int64_t d[3] = {dims[0], dims[1], dims[2]};
+  for (int l = 0; l + 1 < n_levels; ++l) {
+    const uint32_t mask = axis_masks ? (uint32_t)axis_masks[l] : tensor_full_mask(dim);
+    if (axis_masks) {
+      const std::string me = semi_mask_error(l, dim, d, axis_masks[l]);
+      if (!me.empty()) return fail(AMG_HIP_EINVAL, who + me);
+    } else if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) {
+      return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
+    }
+    const std::string le = periodic_level_error(l, dim, d, mask, (uint32_t)periodic_axes);
+    if (!le.empty()) return fail(AMG_HIP_EINVAL, who + le);
+    int64_t c[3];
+    tensor_coarse_dims(dim, d, mask, c);
+    for (int a = 0; a < 3; ++a) d[a] = c[a];
+  }
+  const std::string se = sides_error(o, dim, (uint32_t)periodic_axes);
+  if (!se.empty()) return fail(AMG_HIP_EINVAL, se);
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_create_tensor_periodic(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                              const double* val, const double* b, int32_t dim, const int64_t* dims,
+                                              int32_t periodic_axes, int32_t n_levels, const int32_t* axis_masks,
+                                              const amg_hip_options* opts, amg_hip_solver** out) {
+  static const std::string who = "amg_hip_create_tensor_periodic: ";
+  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
+  *out = nullptr;
+  amg_hip_options o;
+  if (opts) o = *opts;
+  else amg_hip_default_options(&o);
+  SemiRule rule;
+  const amg_hip_status r = periodic_args(who, n, dim, dims, periodic_axes, n_levels, axis_masks, o, &rule);
+  if (r != AMG_HIP_OK) return r;
+  return build_solver(n, colptr, rowind, val, b, n_levels, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      &o, out, -1.0, 0, dim, dims, axis_masks ? &rule : nullptr, (uint32_t)periodic_axes);
+}
+
 amg_hip_status amg_hip_get_level_axes(const amg_hip_solver* s, int32_t level, int32_t* axis_mask) {
   if (!s || !axis_mask) return fail(AMG_HIP_EINVAL, "null argument");
   if (level < 0 || level + 1 >= (int)s->lv.size())
@@ -4409,45 +4511,53 @@ static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr,
 }
 
 // amg_hip_create_tensor_dev and, with `semi_on`, amg_hip_create_tensor_semi_dev
+// and, with `per_on`, amg_hip_create_tensor_periodic_dev: its hierarchy is built on the host (the
+// checked arrays take the host constructor), so the level loop on the device is never entered
 static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, int64_t n, const int32_t* rowptr_dev,
                                         const int32_t* col_dev, const double* val_dev, const double* b_dev,
                                         int32_t dim, const int64_t* dims, int32_t n_levels,
                                         const int32_t* axis_masks, double theta, int64_t min_coarse,
-                                        const amg_hip_options* opts, amg_hip_solver** out) {
+                                        const amg_hip_options* opts, amg_hip_solver** out, bool per_on = false,
+                                        int32_t periodic_axes = 0) {
   if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
   *out = nullptr;
   if (!rowptr_dev || !col_dev || !val_dev || !b_dev) return fail(AMG_HIP_EINVAL, "null input array");
-  const std::string e = tensor_dims_error(dim, dims);
-  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
-  if (n != dims[0] * dims[1] * dims[2])
-    return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
-                                    " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
-                                    " grid of `dims`");
   amg_hip_options o;
   if (opts) o = *opts;
   else amg_hip_default_options(&o);
-  if (o.window)
-    return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a " +
-                                          (semi_on ? "semi" : "full") + "-coarsening hierarchy is not sharded");
-  if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
   SemiRule rule;
   const SemiRule* semi = semi_on ? &rule : nullptr;
-  if (semi_on) {
-    const amg_hip_status sr = semi_args(who, dim, dims, n_levels, axis_masks, theta, min_coarse, &rule);
-    if (sr != AMG_HIP_OK) return sr;
-  } else {  // the levels the rule allows
-    int64_t d[3] = {dims[0], dims[1], dims[2]};
-    for (int l = 0; l + 1 < n_levels; ++l) {
-      if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
-      int64_t c[3];
-      tensor_coarse_dims(dim, d, c);
-      for (int a = 0; a < 3; ++a) d[a] = c[a];
+  if (per_on) {  // grid, masks, levels and sides: the host constructor's one check
+    const amg_hip_status ps = periodic_args(who, n, dim, dims, periodic_axes, n_levels, axis_masks, o, &rule);
+    if (ps != AMG_HIP_OK) return ps;
+  } else {
+    const std::string e = tensor_dims_error(dim, dims);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
+    if (n != dims[0] * dims[1] * dims[2])
+      return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
+                                      " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
+                                      " grid of `dims`");
+    if (o.window)
+      return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a " +
+                                            (semi_on ? "semi" : "full") + "-coarsening hierarchy is not sharded");
+    if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
+    if (semi_on) {
+      const amg_hip_status sr = semi_args(who, dim, dims, n_levels, axis_masks, theta, min_coarse, &rule);
+      if (sr != AMG_HIP_OK) return sr;
+    } else {  // the levels the rule allows
+      int64_t d[3] = {dims[0], dims[1], dims[2]};
+      for (int l = 0; l + 1 < n_levels; ++l) {
+        if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
+        int64_t c[3];
+        tensor_coarse_dims(dim, d, c);
+        for (int a = 0; a < 3; ++a) d[a] = c[a];
+      }
     }
   }
   // build_solver's option checks, in its words
   if (o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_ALT) return fail(AMG_HIP_EINVAL, "unknown smoother kind");
   {
-    const std::string se = sides_error(o, dim);
+    const std::string se = per_on ? std::string() : sides_error(o, dim);
     if (!se.empty()) return fail(AMG_HIP_EINVAL, se);
     if (o.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
   }
@@ -4465,7 +4575,9 @@ static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, in
   if (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0))
     return fail(AMG_HIP_EINVAL, "`omega` must be in [0, 2] but got omega=" + std::to_string(o.omega) + "\n");
   bool unsupported = true;
-  amg_hip_status r = build_tensor_user_device(n, rowptr_dev, col_dev, val_dev, b_dev, dim, dims, n_levels, o, out,
+  amg_hip_options od = o;
+  if (per_on) od.host_galerkin = 1;  // copy + check only: K-TensorGalerkin does not know the seam
+  amg_hip_status r = build_tensor_user_device(n, rowptr_dev, col_dev, val_dev, b_dev, dim, dims, n_levels, od, out,
                                               &unsupported, semi, who);
   if (r != AMG_HIP_OK || !unsupported) return r;
   // options that need host structures (or a product the kernels refused): the checked arrays are
@@ -4499,6 +4611,9 @@ static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, in
     if (o.device >= 0) HIP_TRY(hipSetDevice(dev_before));
   }
   const Sparse A = transpose(H);  // CSC(A)
+  if (per_on)  // the arguments are checked: what amg_hip_create_tensor_periodic does after its checks
+    return build_solver(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, &o, out, -1.0, 0, dim, dims, semi, (uint32_t)periodic_axes);
   if (semi_on)
     return amg_hip_create_tensor_semi(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims, n_levels,
                                       axis_masks, theta, min_coarse, &o, out);
@@ -4520,6 +4635,15 @@ amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_d
                                               amg_hip_solver** out) {
   return create_tensor_dev("amg_hip_create_tensor_semi_dev: ", true, n, rowptr_dev, col_dev, val_dev, b_dev, dim,
                            dims, n_levels, axis_masks, theta, min_coarse, opts, out);
+}
+
+amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                                  const double* val_dev, const double* b_dev, int32_t dim,
+                                                  const int64_t* dims, int32_t periodic_axes, int32_t n_levels,
+                                                  const int32_t* axis_masks, const amg_hip_options* opts,
+                                                  amg_hip_solver** out) {
+  return create_tensor_dev("amg_hip_create_tensor_periodic_dev: ", axis_masks != nullptr, n, rowptr_dev, col_dev,
+                           val_dev, b_dev, dim, dims, n_levels, axis_masks, 0.0, 0, opts, out, true, periodic_axes);
 }
 
 amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on) {
@@ -4862,7 +4986,7 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       if (L.linear && s->opt.stencil_transfers) {
         HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
       } else if (L.tensor_stencil) {
-        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
+        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
       } else {
         HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st));
         const DevCsr& R = L.R_rows;
@@ -4877,7 +5001,7 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
       if (L.linear && s->opt.stencil_transfers) {
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
       } else if (L.tensor_stencil) {
-        HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, C.u.as<double>(), L.u.as<double>(), st));
+        HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
       } else {
         const DevCsr& P = L.P_rows;
         HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz, P.rowptr(),
@@ -5521,9 +5645,12 @@ amg_hip_status amg_hip_linear_restrict(int64_t n_h, int64_t n_H, const double* r
 // the fine grid of a stand-alone tensor transfer: every coarsened axis needs 2 points.  mask < 0:
 // full coarsening (the entry points without a mask)
 // sides: the natural boundary sides of the _bc entry points (0 for the others)
+// periodic: the periodic axes of the _per entry points (0 for the others)
 static amg_hip_status tensor_transfer_args(const char* who, int32_t dim, const int64_t* dims, int64_t mask_in,
-                                           int32_t sides, uint32_t* mask, int64_t* n_h, int64_t* n_H) {
+                                           int32_t sides, int32_t periodic, uint32_t* mask, int64_t* n_h,
+                                           int64_t* n_H) {
   std::string e = tensor_dims_error(dim, dims);
+  if (e.empty()) e = periodic_axes_error(dim, periodic);
   if (e.empty() && (sides < 0 || sides >= (1 << (2 * dim))))
     e = "`natural_sides` = " + std::to_string(sides) + " has bits other than the " + std::to_string(2 * dim) +
         " sides of the grid";
@@ -5532,6 +5659,13 @@ static amg_hip_status tensor_transfer_args(const char* who, int32_t dim, const i
     mask_in = tensor_full_mask(dim);
   } else if (e.empty()) {
     e = semi_mask_error(0, dim, dims, mask_in);
+  }
+  if (e.empty() && periodic) {
+    e = periodic_level_error(0, dim, dims, (uint32_t)mask_in, (uint32_t)periodic);
+    for (int a = 0; e.empty() && a < dim; ++a)
+      if (((periodic >> a) & 1) && ((sides >> (2 * a)) & 3))
+        e = "`natural_sides` = " + std::to_string(sides) + " names a side of axis " + std::string(1, "xyz"[a]) +
+            ", which `periodic_axes` = " + std::to_string(periodic) + " makes periodic: a periodic axis has no sides";
   }
   if (!e.empty()) return fail(AMG_HIP_EINVAL, std::string(who) + ": " + e);
   int64_t c[3];
@@ -5543,17 +5677,17 @@ static amg_hip_status tensor_transfer_args(const char* who, int32_t dim, const i
 }
 
 static amg_hip_status tensor_restrict_host(const char* who, int32_t dim, const int64_t* dims_h, int64_t mask_in,
-                                           int32_t sides, const double* r, double* f_H) {
+                                           int32_t sides, const double* r, double* f_H, int32_t periodic = 0) {
   int64_t n_h = 0, n_H = 0;
   uint32_t mask = 0;
-  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, sides, &mask, &n_h, &n_H);
+  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, sides, periodic, &mask, &n_h, &n_H);
   if (st != AMG_HIP_OK) return st;
   if (!r || !f_H) return fail(AMG_HIP_EINVAL, "bad argument");
   if ((st = need_device()) != AMG_HIP_OK) return st;
   DevMem dr, df;
   HIP_TRY(upload(dr, r, (size_t)n_h));
   HIP_TRY(df.alloc(sizeof(double) * n_H));
-  HIP_TRY(launch_tensor_restrict(dim, dims_h, mask, (uint32_t)sides, dr.as<double>(), df.as<double>(), nullptr, nullptr));
+  HIP_TRY(launch_tensor_restrict(dim, dims_h, mask, (uint32_t)sides, (uint32_t)periodic, dr.as<double>(), df.as<double>(), nullptr, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(f_H, df.p, sizeof(double) * n_H, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
@@ -5570,19 +5704,24 @@ amg_hip_status amg_hip_tensor_restrict_bc(int32_t dim, const int64_t* dims_h, in
   return tensor_restrict_host("amg_hip_tensor_restrict_bc", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, natural_sides,
                               r, f_H);
 }
+amg_hip_status amg_hip_tensor_restrict_per(int32_t dim, const int64_t* dims_h, int32_t axis_mask, int32_t natural_sides,
+                                           int32_t periodic_axes, const double* r, double* f_H) {
+  return tensor_restrict_host("amg_hip_tensor_restrict_per", dim, dims_h, axis_mask < 0 ? 8 : axis_mask, natural_sides,
+                              r, f_H, periodic_axes);
+}
 
 static amg_hip_status tensor_prolong_add_host(const char* who, int32_t dim, const int64_t* dims_h, int64_t mask_in,
-                                              int32_t sides, const double* u_H, double* u_h) {
+                                              int32_t sides, const double* u_H, double* u_h, int32_t periodic = 0) {
   int64_t n_h = 0, n_H = 0;
   uint32_t mask = 0;
-  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, sides, &mask, &n_h, &n_H);
+  amg_hip_status st = tensor_transfer_args(who, dim, dims_h, mask_in, sides, periodic, &mask, &n_h, &n_H);
   if (st != AMG_HIP_OK) return st;
   if (!u_H || !u_h) return fail(AMG_HIP_EINVAL, "bad argument");
   if ((st = need_device()) != AMG_HIP_OK) return st;
   DevMem dH, dh;
   HIP_TRY(upload(dH, u_H, (size_t)n_H));
   HIP_TRY(upload(dh, u_h, (size_t)n_h));
-  HIP_TRY(launch_tensor_prolong_add(dim, dims_h, mask, (uint32_t)sides, dH.as<double>(), dh.as<double>(), nullptr));
+  HIP_TRY(launch_tensor_prolong_add(dim, dims_h, mask, (uint32_t)sides, (uint32_t)periodic, dH.as<double>(), dh.as<double>(), nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(u_h, dh.p, sizeof(double) * n_h, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
@@ -5600,6 +5739,12 @@ amg_hip_status amg_hip_tensor_prolong_add_bc(int32_t dim, const int64_t* dims_h,
                                              int32_t natural_sides, const double* u_H, double* u_h) {
   return tensor_prolong_add_host("amg_hip_tensor_prolong_add_bc", dim, dims_h, axis_mask < 0 ? 8 : axis_mask,
                                  natural_sides, u_H, u_h);
+}
+amg_hip_status amg_hip_tensor_prolong_add_per(int32_t dim, const int64_t* dims_h, int32_t axis_mask,
+                                              int32_t natural_sides, int32_t periodic_axes, const double* u_H,
+                                              double* u_h) {
+  return tensor_prolong_add_host("amg_hip_tensor_prolong_add_per", dim, dims_h, axis_mask < 0 ? 8 : axis_mask,
+                                 natural_sides, u_H, u_h, periodic_axes);
 }
 
 amg_hip_status amg_hip_linear_prolong_add(int64_t n_h, int64_t n_H, const double* u_H,

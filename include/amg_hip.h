@@ -417,6 +417,45 @@ amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, cons
 /* Side mask of a solver (opts->natural_sides of a tensor constructor); 0 on every other solver.  Also
  * on host_only solvers.                                                                          */
 amg_hip_status amg_hip_get_natural_sides(const amg_hip_solver* s, int32_t* mask);
+/* Periodic axes.  `periodic_axes` is a bit mask, bit a = axis a (1 = x, 2 = y, 4 = z): the operator
+ * couples the first and the last point of such an axis (channel flows, annuli, doubly and triply
+ * periodic boxes); those wrap entries are ordinary entries of A.  On a coarsened periodic axis of
+ * even length m >= 4 the 1-D factor is P1per(m), m x m/2 with 0.5, 1.0, 0.5 on rows 2j, 2j+1,
+ * (2j+2) mod m of column j: P1(m) plus the one entry (0, m/2 - 1) = 0.5, so that fine point 0 is
+ * interpolated between coarse points 0 and m/2 - 1 and every row sums to 1.  A level uses P_l = P_z
+ * (x) P_y (x) P_x with P1per on the coarsened periodic axes, P1N with the axis' side bits on the
+ * other coarsened axes and the identity outside the level's mask; R_l = P_l^T, A_{l+1} = R_l (A_l
+ * P_l) by the same host product in the same summation order; the same mask holds on every level.
+ * An axis that is periodic but not coarsened on a level needs nothing, the wrap being in A.  The
+ * weights are still products of powers of two: level matrices equal amg_hip_create_custom on the
+ * same P / R bit for bit, transfer kind 2 (K-TensorRestrict / K-TensorProlong with the seam) and
+ * kind 0 give the same bits, and the float cycle and the block cycle honour the mask.  The rows of
+ * a column of P ascend (amg_hip_get_transfer): in the last column of a periodic axis row 0 is first.
+ * axis_masks == NULL: full coarsening with exactly n_levels levels; otherwise n_levels - 1 explicit
+ * masks as for amg_hip_create_tensor_semi.  The automatic rule of that constructor is not offered.
+ * Everything else as amg_hip_create_tensor / _tensor_semi with explicit masks: every smoother
+ * (AMG_HIP_SM_LINE_ALT included), every layout, host_only, stencil_transfers 0 / 1, natural_sides
+ * and singular from `opts`.  periodic_axes = 0 gives the solver of those constructors bit for bit.
+ * The smoothers see the level matrices only.  The line smoothers treat a wrap entry as a coupling
+ * off the line, like any entry outside the tridiagonal part: THERE IS NO CYCLIC TRIDIAGONAL SOLVE,
+ * and a line along a periodic axis is relaxed as an open line.
+ * The coarsest operator of a periodic box has a band as wide as the wrap, so its factorisation runs
+ * the any-bandwidth substitution: coarsen until the coarsest level is small (a few hundred rows).
+ * AMG_HIP_EINVAL before the device is touched, the argument or field named in the message: what
+ * amg_hip_create_tensor / _tensor_semi check, in their words; periodic_axes negative or with bits
+ * at or above dim; a coarsened periodic axis whose length on that level is odd or below 4 (the
+ * level in the message); a natural_sides bit on a periodic axis, which has no sides; singular = 1
+ * unless both side bits of every axis that is NOT periodic are set -- all axes periodic with
+ * natural_sides = 0 is the fully periodic singular case.  opts->window = 1: AMG_HIP_EUNSUPPORTED. */
+amg_hip_status amg_hip_create_tensor_periodic(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                              const double* val, const double* b, int32_t dim,
+                                              const int64_t* dims /* 3 */, int32_t periodic_axes,
+                                              int32_t n_levels,
+                                              const int32_t* axis_masks /* n_levels - 1, or NULL = full coarsening */,
+                                              const amg_hip_options* opts, amg_hip_solver** out);
+/* Periodic mask of a solver made by amg_hip_create_tensor_periodic / _periodic_dev; 0 on every other
+ * solver.  Also on host_only solvers.                                                            */
+amg_hip_status amg_hip_get_periodic_axes(const amg_hip_solver* s, int32_t* mask);
 /* Axis mask of the transfers between `level` and `level` + 1 of a solver made by one of the tensor
  * constructors (the full-coarsening ones report 3 in 2-D and 7 in 3-D); also on host_only solvers.
  * AMG_HIP_EINVAL on the coarsest level and for every other solver.                              */
@@ -513,6 +552,18 @@ amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_d
                                               const int32_t* axis_masks /* n_levels - 1, host, or NULL */,
                                               double theta, int64_t min_coarse,
                                               const amg_hip_options* opts, amg_hip_solver** out);
+/* amg_hip_create_tensor_periodic for a caller's matrix in DEVICE memory (CSR, as for
+ * amg_hip_create_tensor_dev).  The arguments are checked as by the host constructor, the arrays by
+ * K-CsrCheck; then they are downloaded, transposed on the host and given to
+ * amg_hip_create_tensor_periodic -- the silent host path of amg_hip_create_tensor_dev, always:
+ * K-TensorGalerkin does not know the seam yet.  The solver equals the host constructor's bit for
+ * bit and amg_hip_setup_on_device reports 0.                                                     */
+amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                                  const double* val_dev, const double* b_dev, int32_t dim,
+                                                  const int64_t* dims /* 3, host */, int32_t periodic_axes,
+                                                  int32_t n_levels,
+                                                  const int32_t* axis_masks /* n_levels - 1, host, or NULL */,
+                                                  const amg_hip_options* opts, amg_hip_solver** out);
 /* *on = 1: the hierarchy was built by a device-only path (amg_hip_create_poisson,
  * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor, amg_hip_create_tensor_dev,
  * amg_hip_create_tensor_semi_dev when they did not fall back),
@@ -948,6 +999,18 @@ amg_hip_status amg_hip_tensor_restrict_bc(int32_t dim, const int64_t* dims_h /* 
                                           int32_t natural_sides, const double* r, double* f_H);
 amg_hip_status amg_hip_tensor_prolong_add_bc(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
                                              int32_t natural_sides, const double* u_H, double* u_h);
+/* The same two transfers with an axis mask, a side mask and the periodic mask of
+ * amg_hip_create_tensor_periodic (P1per on the coarsened periodic axes): bit-identical to
+ * amg_hip_spmv with the R / P of amg_hip_get_transfer of such a solver.  The argument checks of the
+ * _bc forms, plus AMG_HIP_EINVAL for `periodic_axes` negative or with bits at or above dim, a
+ * coarsened periodic axis of odd length or fewer than 4 points, and a `natural_sides` bit on a
+ * periodic axis.  periodic_axes = 0: the _bc forms, the same kernel and the same bits.            */
+amg_hip_status amg_hip_tensor_restrict_per(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
+                                           int32_t natural_sides, int32_t periodic_axes, const double* r,
+                                           double* f_H);
+amg_hip_status amg_hip_tensor_prolong_add_per(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
+                                              int32_t natural_sides, int32_t periodic_axes, const double* u_H,
+                                              double* u_h);
 /* AMG::rss(A, u, b), common.hpp:17-27. */
 amg_hip_status amg_hip_rss_host(int64_t n, const int32_t* colptr,
                                 const int32_t* rowind, const double* val,

@@ -14,6 +14,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py mixed [<nx> <ny> <nz> <levels>]             amg_hip_pcg and amg_hip_pcg_mixed (single-precision V-cycle) alternating on a variable-coefficient operator, true Jacobi 2+2 and Chebyshev(2) 1+1
        config_bench.py semi [<nx> <ny> <nz> <eps_x> <eps_y> <eps_z>] PCG to 1e-8 on an axis-scaled diffusion operator: full coarsening + Jacobi, semi-coarsening + Jacobi, full coarsening + alternating lines, semi-coarsening + amg_hip_pcg_mixed (legs alternate)
        config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
+       config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -615,6 +616,126 @@ def run_natural(dims, reps=3, rtol=1e-8, max_iters=300):
             mg.close()
 
 
+def torch_periodic_diffusion(dims, periodic, seed=1):
+    """torch_diffusion without mass term and without Dirichlet faces whose axes of the mask `periodic`
+    (bit a = axis a) wrap around: point m - 1 is coupled to point 0 through the face conductivity stored
+    at m - 1.  The wrap entries do not sit in stencil order, so the columns of a row are sorted.  Both
+    triangles hold the same bits.  An axis of fewer than 3 points cannot be periodic here (its two
+    couplings would share a column)."""
+    import torch
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    dim = len(dims)
+    ext = tuple(dims) + (1,) * (3 - dim)
+    assert all(ext[a] >= 3 for a in range(dim) if (periodic >> a) & 1)
+    n = ext[0] * ext[1] * ext[2]
+    i = torch.arange(n, device=dev)
+    coord = [i % ext[0], (i // ext[0]) % ext[1], i // (ext[0] * ext[1])]
+    stride = [1, ext[0], ext[0] * ext[1]]
+    kap = [torch.rand(n, generator=g, device=dev, dtype=torch.float64) * 9.0 + 1.0 for _ in range(dim)]  # face i | next
+    w = 2 * dim + 1
+    cols = torch.full((n, w), n, dtype=torch.int64, device=dev)  # n: no entry, sorts last
+    vals = torch.zeros((n, w), dtype=torch.float64, device=dev)
+    diag = torch.zeros((n,), dtype=torch.float64, device=dev)
+    for a in range(dim):
+        per = bool((periodic >> a) & 1)
+        first, last = coord[a] == 0, coord[a] == ext[a] - 1
+        lo = torch.where(first, i + (ext[a] - 1) * stride[a], i - stride[a])
+        hi = torch.where(last, i - (ext[a] - 1) * stride[a], i + stride[a])
+        lo_ok = ~first if not per else torch.ones_like(first)
+        hi_ok = ~last if not per else torch.ones_like(last)
+        k_lo = torch.where(lo_ok, kap[a][lo], torch.zeros_like(kap[a]))
+        k_hi = torch.where(hi_ok, kap[a], torch.zeros_like(kap[a]))
+        diag = diag + k_lo + k_hi
+        cols[:, 2 * a] = torch.where(lo_ok, lo, cols[:, 2 * a])
+        cols[:, 2 * a + 1] = torch.where(hi_ok, hi, cols[:, 2 * a + 1])
+        vals[:, 2 * a], vals[:, 2 * a + 1] = -k_lo, -k_hi
+    cols[:, w - 1], vals[:, w - 1] = i, diag
+    cols, order = torch.sort(cols, dim=1)
+    vals = torch.gather(vals, 1, order)
+    mask = cols < n
+    crow = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    crow[1:] = torch.cumsum(mask.sum(1), 0).to(torch.int32)
+    col = cols[mask].to(torch.int32).contiguous()
+    val = vals[mask].contiguous()
+    b = torch.rand(n, generator=g, device=dev, dtype=torch.float64)
+    return crow, col, val, b - b.mean()
+
+
+def periodic_levels(dims, min_coarse=32):
+    """levels of the full-coarsening hierarchy of a box whose axes are all periodic: coarsen while the
+    level has more than min_coarse rows and every axis is even with at least 4 points"""
+    d, nl = list(dims), 1
+    while all(m >= 4 and m % 2 == 0 for m in d) and d[0] * d[1] * (d[2] if len(d) == 3 else 1) > min_coarse:
+        d, nl = [m // 2 for m in d], nl + 1
+    return nl
+
+
+def run_periodic(dims, reps=3, rtol=1e-8, max_iters=300):
+    """PCG from x = 0 to `rtol` on the diffusion operator of tensor-user-setup without mass term whose
+    axes are all periodic (A is singular, b has zero mean), full coarsening, true Jacobi 2+2.  Two legs
+    alternate in one process, `reps` repeats: the periodic hierarchy (tensor_periodic_dev) and the best
+    hierarchy without it, natural_sides on every side with singular = 1 (tensor_dev).  Both are built by
+    the host constructor (setup_on_device 0): tensor_dev leaves its device path on an operator with wrap
+    entries.  Per run: iterations and wall ms of amg_hip_pcg itself; once per
+    leg: set-up seconds and ms per V-cycle."""
+    import ctypes
+    import torch
+
+    def solve(mg):
+        it, rel = ctypes.c_int64(0), ctypes.c_double(0)
+        st = amg.lib().amg_hip_pcg(mg._h, rtol, max_iters, ctypes.byref(it), ctypes.byref(rel))
+        assert st == 0, amg.lib().amg_hip_last_error().decode()
+        return it.value, rel.value
+
+    dim = len(dims)
+    per, every = (1 << dim) - 1, (1 << (2 * dim)) - 1
+    L = periodic_levels(dims)
+    tag = " x ".join(str(d) for d in dims)
+    arrays = torch_periodic_diffusion(dims, per)
+    torch.cuda.synchronize()
+    jac = TENSOR_KW["jacobi"]
+    mk = {f"periodic_axes {per}": lambda: amg.Multigrid.tensor_periodic_dev(*arrays, dims, L, per, singular=True, **jac),
+          f"natural_sides {every}": lambda: amg.Multigrid.tensor_dev(*arrays, dims, L, natural_sides=every,
+                                                                     singular=True, **jac)}
+    legs = {}
+    for name, make in mk.items():
+        t0 = time.perf_counter()
+        mg = make()
+        mg.sync()
+        dt = time.perf_counter() - t0
+        mg.vcycle(3)
+        mg.sync()
+        mg.zero_vec(0, "u")
+        mg.sync()
+        t0 = time.perf_counter()
+        mg.vcycle(10)
+        mg.sync()
+        cyc = (time.perf_counter() - t0) / 10
+        print(f"periodic {tag}, {name}: setup {dt:.2f} s (setup_on_device {mg.setup_on_device}), "
+              f"{mg.n_levels} levels, coarsest {mg.get_n_dofs(mg.n_levels - 1)} dofs "
+              f"({mg.coarse_solve_kind().split(' ')[0]}), {cyc * 1e3:.3f} ms/V-cycle", flush=True)
+        mg.zero_vec(0, "u")
+        solve(mg)  # first call: work vectors, captured graph
+        legs[name] = mg
+    best = {}
+    for rep_ in range(reps):
+        for name, mg in legs.items():
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            it, rel = solve(mg)
+            dt = time.perf_counter() - t0
+            best[name] = min(best.get(name, (it, dt)), (it, dt), key=lambda v: v[1])
+            print(f"periodic {tag}, {name} rep {rep_}: {it} iterations, {dt * 1e3:.2f} ms to {rtol:g} "
+                  f"(relres {rel:.2e}, {'reached' if rel <= rtol else 'NOT reached: capped'})", flush=True)
+    print(f"periodic {tag}: best to {rtol:g}: " +
+          ", ".join(f"{k} {v[0]} iterations {v[1] * 1e3:.2f} ms" for k, v in best.items()), flush=True)
+    for mg in legs.values():
+        mg.close()
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -757,6 +878,14 @@ elif len(sys.argv) > 1 and sys.argv[1] == "natural":
     else:
         run_natural((4096, 1024))
         run_natural((256, 256, 256))
+elif len(sys.argv) > 1 and sys.argv[1] == "periodic":
+    # profiles/periodic_config_bench.txt
+    if len(sys.argv) > 4:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_periodic(d if d[2] > 1 else d[:2])
+    else:
+        run_periodic((4096, 1024))
+        run_periodic((256, 256, 256))
 elif len(sys.argv) > 3 and sys.argv[1] == "tensor10":
     mg = amg.Multigrid.poisson_tensor(int(sys.argv[2]), int(sys.argv[3]), stencil_transfers=len(sys.argv) < 5,
                                       **TENSOR_KW["jacobi"])
