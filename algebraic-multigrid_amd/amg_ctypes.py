@@ -158,6 +158,9 @@ _SIGS = {
     "amg_hip_apply_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "amg_hip_pcg_mixed": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, _i64p, _f64p]),
     "amg_hip_f32_must_move": (C.c_int, [C.c_void_p, _f64p]),
+    "amg_hip_f32_get_vec": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    "amg_hip_f32_set_vec": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    "amg_hip_f32_level_op": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "amg_hip_n_levels": (C.c_int32, [C.c_void_p]),
     "amg_hip_get_n_dofs": (C.c_int64, [C.c_void_p, C.c_int32]),
     "amg_hip_get_level_nnz": (C.c_int64, [C.c_void_p, C.c_int32]),
@@ -1167,6 +1170,27 @@ class Multigrid:
         b = C.c_double(0)
         _chk(lib().amg_hip_f32_must_move(self._h, C.byref(b)))
         return b.value
+
+    # ---- test hooks on the float cycle (amg_hip_f32_get_vec / _set_vec / _level_op) ----------
+    def f32_get_vec(self, level, which):
+        """float32 copy of the float cycle's vector `which` ("u", "f" or "r") of `level`."""
+        out = np.empty(self.get_n_dofs(level), np.float32)
+        _chk(lib().amg_hip_f32_get_vec(self._h, int(level), {"u": 0, "f": 1, "r": 2}[which],
+                                       out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def f32_set_vec(self, level, which, v):
+        """Set the float cycle's vector `which` of `level`; v must be float32 already (no rounding here)."""
+        v = np.asarray(v)
+        if v.dtype != np.float32 or v.shape != (self.get_n_dofs(level),):
+            raise ValueError("f32_set_vec: expected a float32 vector of n_dofs(level) entries")
+        v = np.ascontiguousarray(v)
+        _chk(lib().amg_hip_f32_set_vec(self._h, int(level), {"u": 0, "f": 1, "r": 2}[which],
+                                       v.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def f32_level_op(self, level, op):
+        """One step of the float cycle on the float vectors; op as level_op's."""
+        _chk(lib().amg_hip_f32_level_op(self._h, int(level), int(op)))
 
     # ---- block (multi-right-hand-side) cycles: amg_hip_block_* ---------------------------
     def _block_check(self, name, t, k=None):

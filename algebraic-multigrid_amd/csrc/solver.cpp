@@ -4016,64 +4016,93 @@ amg_hip_status enqueue_f32_smooth(amg_hip_solver* s, int l, bool dry) {
   return AMG_HIP_OK;
 }
 
+// The steps of the cycle, one helper each: enqueue_f32_vcycle strings them together, and
+// amg_hip_f32_level_op (a test hook) runs one of them alone -- the same launches either way.
+// r_l = f_l - A_l u_l (:272-274)
+amg_hip_status enqueue_f32_residual(amg_hip_solver* s, int l, bool dry) {
+  const Level& L = s->lv[l];
+  F32Level& Q = s->f32.lv[(size_t)l];
+  F32_DO(launch_mat_f32(CSR_RESID, Q.rows, Q.u.as<float>(), Q.f.as<float>(), Q.r.as<float>(), 1.0f, nullptr, 0.0f,
+                        s->stream));
+  s->facct(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);
+  return AMG_HIP_OK;
+}
+
+// u_{l+1} = 0, f_{l+1} = R_l r_l (:278 + :281-282)
+amg_hip_status enqueue_f32_restrict(amg_hip_solver* s, int l, bool dry) {
+  const Level& L = s->lv[l];
+  const Level& C = s->lv[l + 1];
+  F32Level& Q = s->f32.lv[(size_t)l];
+  F32Level& QC = s->f32.lv[(size_t)l + 1];
+  hipStream_t st = s->stream;
+  if (L.linear && s->opt.stencil_transfers) {
+    F32_DO(launch_linear_restrict_f32(L.n, C.n, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
+    s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
+  } else if (L.tensor_stencil) {
+    F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
+    s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
+  } else {
+    F32_DO(hipMemsetAsync(QC.u.p, 0, sizeof(float) * (size_t)C.n, st));
+    const DevCsr& R = L.R_rows;
+    F32_DO(launch_csr_f32(CSR_SPMV, R.n_rows, R.rowptr(), R.col(), Q.rval.as<float>(), Q.r.as<float>(), nullptr,
+                          QC.f.as<float>(), 1.0f, nullptr, 0.0f, st));
+    s->facct(8.0 * (double)R.nnz + 4.0 * (double)(R.n_rows + 1) + 4.0 * (double)L.n + 8.0 * (double)C.n);
+  }
+  return AMG_HIP_OK;
+}
+
+// :287-288 in double: widen f_L, the solver's factor, round the result
+amg_hip_status enqueue_f32_coarse(amg_hip_solver* s, bool dry) {
+  F32& F = s->f32;
+  const int nl = (int)s->lv.size();
+  const Level& C = s->lv[(size_t)nl - 1];
+  F32Level& QC = F.lv[(size_t)nl - 1];
+  hipStream_t st = s->stream;
+  F32_DO(launch_to_f64(C.n, QC.f.as<float>(), F.cf.as<double>(), st));
+  F32_DO(launch_coarse(s->coarse, F.cf.as<double>(), F.cy.as<double>(), F.cx.as<double>(), st));
+  F32_DO(launch_to_f32(C.n, F.cx.as<double>(), QC.u.as<float>(), st));
+  // the two conversions; the band of L forwards and backwards, D, f, u (enqueue_vcycle_body)
+  s->facct(24.0 * (double)C.n + 16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * (double)C.n);
+  return AMG_HIP_OK;
+}
+
+// u_l = u_l + P_l u_{l+1} (:294-296)
+amg_hip_status enqueue_f32_prolong(amg_hip_solver* s, int l, bool dry) {
+  const Level& L = s->lv[l];
+  const Level& C = s->lv[l + 1];
+  F32Level& Q = s->f32.lv[(size_t)l];
+  F32Level& QC = s->f32.lv[(size_t)l + 1];
+  hipStream_t st = s->stream;
+  if (L.linear && s->opt.stencil_transfers) {
+    F32_DO(launch_linear_prolong_add_f32(L.n, C.n, QC.u.as<float>(), Q.u.as<float>(), st));
+    s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
+  } else if (L.tensor_stencil) {
+    F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, QC.u.as<float>(), Q.u.as<float>(), st));
+    s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
+  } else {
+    const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
+    F32_DO(launch_csr_f32(CSR_SPMV_ADD, P.n_rows, P.rowptr(), P.col(), Q.pval.as<float>(), QC.u.as<float>(),
+                          Q.u.as<float>(), Q.u.as<float>(), 1.0f, nullptr, 0.0f, st));
+    s->facct(8.0 * (double)P.nnz + 4.0 * (double)(P.n_rows + 1) + 4.0 * (double)C.n + 8.0 * (double)L.n);
+  }
+  return AMG_HIP_OK;
+}
+
 // level 0's f holds the right-hand side, its u receives the result
 amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
   const int nl = (int)s->lv.size();
-  hipStream_t st = s->stream;
-  F32& F = s->f32;
   amg_hip_status r;
-  F32_DO(hipMemsetAsync(F.lv[0].u.p, 0, sizeof(float) * (size_t)s->lv[0].n, st));  // the zero guess
+  F32_DO(hipMemsetAsync(s->f32.lv[0].u.p, 0, sizeof(float) * (size_t)s->lv[0].n, s->stream));  // the zero guess
   s->facct(4.0 * (double)s->lv[0].n);
   for (int l = 0; l + 1 < nl; ++l) {
-    const Level& L = s->lv[l];
-    const Level& C = s->lv[l + 1];
-    F32Level& Q = F.lv[(size_t)l];
-    F32Level& QC = F.lv[(size_t)l + 1];
-    if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;  // :268
-    F32_DO(launch_mat_f32(CSR_RESID, Q.rows, Q.u.as<float>(), Q.f.as<float>(), Q.r.as<float>(), 1.0f, nullptr, 0.0f,
-                          st));                                        // :272-274
-    s->facct(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);
-    if (L.linear && s->opt.stencil_transfers) {                        // :278 + :281-282
-      F32_DO(launch_linear_restrict_f32(L.n, C.n, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
-      s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
-    } else if (L.tensor_stencil) {
-      F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
-      s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
-    } else {
-      F32_DO(hipMemsetAsync(QC.u.p, 0, sizeof(float) * (size_t)C.n, st));
-      const DevCsr& R = L.R_rows;
-      F32_DO(launch_csr_f32(CSR_SPMV, R.n_rows, R.rowptr(), R.col(), Q.rval.as<float>(), Q.r.as<float>(), nullptr,
-                            QC.f.as<float>(), 1.0f, nullptr, 0.0f, st));
-      s->facct(8.0 * (double)R.nnz + 4.0 * (double)(R.n_rows + 1) + 4.0 * (double)L.n + 8.0 * (double)C.n);
-    }
+    if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;    // :268
+    if ((r = enqueue_f32_residual(s, l, dry)) != AMG_HIP_OK) return r;
+    if ((r = enqueue_f32_restrict(s, l, dry)) != AMG_HIP_OK) return r;
   }
-  {  // :287-288 in double: widen f_L, the solver's factor, round the result
-    const Level& C = s->lv[(size_t)nl - 1];
-    F32Level& QC = F.lv[(size_t)nl - 1];
-    F32_DO(launch_to_f64(C.n, QC.f.as<float>(), F.cf.as<double>(), st));
-    F32_DO(launch_coarse(s->coarse, F.cf.as<double>(), F.cy.as<double>(), F.cx.as<double>(), st));
-    F32_DO(launch_to_f32(C.n, F.cx.as<double>(), QC.u.as<float>(), st));
-    // the two conversions; the band of L forwards and backwards, D, f, u (enqueue_vcycle_body)
-    s->facct(24.0 * (double)C.n + 16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * (double)C.n);
-  }
-  for (int l = nl - 2; l >= 0; --l) {                                  // :291
-    const Level& L = s->lv[l];
-    const Level& C = s->lv[l + 1];
-    F32Level& Q = F.lv[(size_t)l];
-    F32Level& QC = F.lv[(size_t)l + 1];
-    if (L.linear && s->opt.stencil_transfers) {                        // :294-296
-      F32_DO(launch_linear_prolong_add_f32(L.n, C.n, QC.u.as<float>(), Q.u.as<float>(), st));
-      s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
-    } else if (L.tensor_stencil) {
-      F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, QC.u.as<float>(), Q.u.as<float>(), st));
-      s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
-    } else {
-      const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
-      F32_DO(launch_csr_f32(CSR_SPMV_ADD, P.n_rows, P.rowptr(), P.col(), Q.pval.as<float>(), QC.u.as<float>(),
-                            Q.u.as<float>(), Q.u.as<float>(), 1.0f, nullptr, 0.0f, st));
-      s->facct(8.0 * (double)P.nnz + 4.0 * (double)(P.n_rows + 1) + 4.0 * (double)C.n + 8.0 * (double)L.n);
-    }
-    if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;  // :300
+  if ((r = enqueue_f32_coarse(s, dry)) != AMG_HIP_OK) return r;
+  for (int l = nl - 2; l >= 0; --l) {                                   // :291
+    if ((r = enqueue_f32_prolong(s, l, dry)) != AMG_HIP_OK) return r;
+    if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;    // :300
   }
   return AMG_HIP_OK;
 }
@@ -5221,6 +5250,71 @@ amg_hip_status amg_hip_f32_must_move(amg_hip_solver* s, double* bytes) {
   if (r != AMG_HIP_OK) return r;
   *bytes = s->f32_mm + 24.0 * (double)s->lv[0].n;  // v -> float and float -> z: 8 + 4 bytes per row each
   return AMG_HIP_OK;
+}
+
+// ---- test hooks on the float cycle (include/amg_hip.h) ---------------------------------------
+// the float vector `which` of `level`, or null: the coarsest level has u and f only
+static DevMem* f32_pick_vec(amg_hip_solver* s, int32_t level, int32_t which) {
+  F32Level& Q = s->f32.lv[(size_t)level];
+  if (which == 0) return &Q.u;
+  if (which == 1) return &Q.f;
+  return (which == 2 && level + 1 < (int32_t)s->lv.size()) ? &Q.r : nullptr;
+}
+// the checks shared by the three hooks: bad arguments (`bad`: what else is wrong with them, or null),
+// then amg_hip_apply_f32's, then the float copies
+static amg_hip_status f32_hook_ready(amg_hip_solver* s, int32_t level, const char* bad) {
+  if (!s) return fail(AMG_HIP_EINVAL, "null solver");
+  if (level < 0 || level >= (int32_t)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
+  if (bad) return fail(AMG_HIP_EINVAL, bad);
+  amg_hip_status r = f32_supported(s);
+  if (r != AMG_HIP_OK) return r;
+  return ensure_f32(s);
+}
+static const char* f32_vec_error(const amg_hip_solver* s, int32_t level, int32_t which, const void* host) {
+  if (!host) return "null argument";
+  if (which < 0 || which > 2) return "bad vector selector";
+  if (s && which == 2 && level + 1 == (int32_t)s->lv.size())
+    return "the coarsest level of the single-precision cycle has no residual vector";
+  return nullptr;
+}
+
+amg_hip_status amg_hip_f32_get_vec(amg_hip_solver* s, int32_t level, int32_t which, float* out_host) {
+  amg_hip_status r = f32_hook_ready(s, level, f32_vec_error(s, level, which, out_host));
+  if (r != AMG_HIP_OK) return r;
+  DevMem* m = f32_pick_vec(s, level, which);
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpy(out_host, m->p, sizeof(float) * (size_t)s->lv[level].n, hipMemcpyDeviceToHost));
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_f32_set_vec(amg_hip_solver* s, int32_t level, int32_t which, const float* in_host) {
+  amg_hip_status r = f32_hook_ready(s, level, f32_vec_error(s, level, which, in_host));
+  if (r != AMG_HIP_OK) return r;
+  DevMem* m = f32_pick_vec(s, level, which);
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpy(m->p, in_host, sizeof(float) * (size_t)s->lv[level].n, hipMemcpyHostToDevice));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_f32_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
+  const char* bad = nullptr;
+  if (s) {
+    const int32_t nl = (int32_t)s->lv.size();
+    if (op < 0 || op > 4) bad = "unknown level operation";
+    else if (op == 4 && level != nl - 1) bad = "the direct solve belongs to the coarsest level";
+    else if (op < 4 && level + 1 >= nl)  // the coarsest level has no float matrix and no transfers
+      bad = "no coarser level: the coarsest level only takes the direct solve";
+  }
+  amg_hip_status r = f32_hook_ready(s, level, bad);
+  if (r != AMG_HIP_OK) return r;
+  switch (op) {
+    case 0: return enqueue_f32_smooth(s, level, false);
+    case 1: return enqueue_f32_residual(s, level, false);
+    case 2: return enqueue_f32_restrict(s, level, false);
+    case 3: return enqueue_f32_prolong(s, level, false);
+    default: return enqueue_f32_coarse(s, false);
+  }
 }
 
 amg_hip_status amg_hip_solve(amg_hip_solver* s, double tol, int64_t every, int64_t n_iters,

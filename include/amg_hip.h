@@ -777,8 +777,11 @@ amg_hip_status amg_hip_block_must_move(amg_hip_solver* s, int32_t k, double* byt
  * CSR row pointers / columns are shared with the double matrices) and float level vectors, made at
  * the first call and freed with the solver; the coarsest system is solved in double with the
  * existing factor.  The solver's own level vectors, right-hand side and solution are never touched,
- * and no existing entry point changes its results.  Not bitwise against anything; deterministic, and
- * use_graph = 0 / 1 give the same bits.
+ * and no existing entry point changes its results.  Not bitwise against the double cycle, but every
+ * step is the float32 restatement of tests/f32_twin.py bit for bit: each row summed in ascending column
+ * order from a fixed start with separate, correctly rounded multiplies, adds and divisions, the
+ * transfers in the row order of the CSR R / P, the coarsest solve the double solve between two
+ * roundings.  Deterministic, and use_graph = 0 / 1 give the same bits.
  * v is not scaled: entries of v below about 1e-30 in magnitude lose bits to float denormals, and
  * above 3e38 overflow.  Harmless for rtol >= 1e-12 on right-hand sides of ordinary magnitude.
  *
@@ -801,6 +804,25 @@ amg_hip_status amg_hip_pcg_mixed(amg_hip_solver* s, double rtol, int64_t max_ite
  * bytes) and 8 per panel, CSR 8 per entry + 4 per row pointer, every float vector pass 4 per row; the
  * coarsest solve and the conversions around it and around the cycle in their own widths. */
 amg_hip_status amg_hip_f32_must_move(amg_hip_solver* s, double* bytes);
+/* TEST HOOKS on the float cycle, the float counterparts of amg_hip_get_vec / amg_hip_set_vec /
+ * amg_hip_level_op: they let a test pin single steps of amg_hip_apply_f32 bit for bit and are not
+ * meant for applications.  All three run amg_hip_apply_f32's checks in the order above (the first
+ * of them, AMG_HIP_EINVAL, also for a level out of range, a bad `which`, an `op` the level does not
+ * have), then make the float copies if this is the first float call.
+ * amg_hip_f32_get_vec / amg_hip_f32_set_vec: n_dofs(level) floats to / from HOST memory; which: 0 = u,
+ * 1 = f, 2 = r.  The coarsest level has u and f only (which = 2 there: AMG_HIP_EINVAL).  Both
+ * synchronise the solver's stream.  After amg_hip_apply_f32 the vectors hold what the cycle left on
+ * every level (level 0's f: v rounded to float, level 0's u: z before it is widened).
+ * amg_hip_f32_level_op: one step of the float cycle on the float vectors -- the very launches
+ * amg_hip_apply_f32 makes for it -- eagerly on the solver's stream; op as amg_hip_level_op's:
+ *   0 smooth (smoother_iters sweeps, or applications of the Chebyshev polynomial)  level < L-1
+ *   1 r_l = f_l - A_l u_l                                                          level < L-1
+ *   2 u_{l+1} = 0 and f_{l+1} = R_l r_l                                            level < L-1
+ *   3 u_l = u_l + P_l u_{l+1}                                                      level < L-1
+ *   4 widen f_L, the solver's double coarse solve, round into u_L                  level = L-1 */
+amg_hip_status amg_hip_f32_get_vec(amg_hip_solver* s, int32_t level, int32_t which, float* out_host);
+amg_hip_status amg_hip_f32_set_vec(amg_hip_solver* s, int32_t level, int32_t which, const float* in_host);
+amg_hip_status amg_hip_f32_level_op(amg_hip_solver* s, int32_t level, int32_t op);
 
 /* Getters, multigrid.hpp:339-354. */
 int32_t amg_hip_n_levels(const amg_hip_solver* s);
