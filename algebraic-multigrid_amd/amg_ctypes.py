@@ -177,6 +177,7 @@ _SIGS = {
     "amg_hip_set_patch_min_rows": (None, [C.c_int64]),
     "amg_hip_set_band_chain": (None, [C.c_int32]),
     "amg_hip_set_tail_fusion": (None, [C.c_int32]),
+    "amg_hip_set_periodic_device_setup": (None, [C.c_int32]),
     "amg_hip_set_patch_tile_flags": (None, [C.c_int32]),
     "amg_hip_set_patch_xf": (None, [C.c_int32]),
     "amg_hip_set_patch_tall": (None, [C.c_int32]),
@@ -405,6 +406,12 @@ def set_patch_tall(on):
 
 def set_tail_fusion(on):
     lib().amg_hip_set_tail_fusion(int(bool(on)))
+
+
+def set_periodic_device_setup(on):
+    """Multigrid.tensor_periodic_dev builds on the device (1) or through the host constructor (0, the
+    default); process-wide, read when a solver is created, the same solver bit for bit."""
+    lib().amg_hip_set_periodic_device_setup(int(bool(on)))
 
 
 def set_band_chain(on):
@@ -812,8 +819,11 @@ class Multigrid:
     @classmethod
     def tensor_periodic_dev(cls, crow, col, val, b, dims, n_levels, periodic_axes, axis_masks=None, **opts):
         """Multigrid.tensor_periodic for a CSR matrix that sits on the device
-        (amg_hip_create_tensor_periodic_dev); arguments as for Multigrid.tensor_dev.  The hierarchy is
-        built by the host constructor: setup_on_device() reports 0."""
+        (amg_hip_create_tensor_periodic_dev); arguments as for Multigrid.tensor_dev.  After
+        set_periodic_device_setup(1) the hierarchy is built on the device (K-TensorGalerkin with the
+        seam; the silent fall-backs of Multigrid.tensor_dev apply) and setup_on_device() reports 1.
+        By default it is built by the host constructor and setup_on_device() reports 0.  The same
+        solver bit for bit either way."""
         masks = cls._semi_rule(n_levels, axis_masks, 0.5, 1)[0]
         return cls.tensor_dev(crow, col, val, b, dims, n_levels, _periodic=(int(periodic_axes), masks), **opts)
 

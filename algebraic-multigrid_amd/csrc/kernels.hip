@@ -5596,7 +5596,58 @@ __device__ __forceinline__ double tg_weight(uint32_t k, int32_t J, uint32_t c, u
   if (t == 2) return (hi && k + 1u == n) ? 1.0 : 0.5;
   return 0.0;
 }
-template <int SLOTS, bool FILL>
+// Periodic axes (PER; host_setup.hpp: tensor_P with periodic).  g.per() holds EVERY periodic axis of
+// the level here, coarsened or not: on an axis that is periodic but not coarsened P is the identity,
+// yet the wrap entries of A make fine row 0 reach column n - 1, and a min / max box would span the axis.
+// So on a periodic axis the reachable columns are kept as offsets d from the group's own coordinate
+// C (the fine one where the axis is not coarsened), in the canonical range [-floor(M / 2),
+// ceil(M / 2) - 1] of an axis of M columns: a span d_lo .. d_hi then has at most M members, all
+// distinct as columns (with M = 2 the left and the right neighbour are one column, one member).  The
+// set is the cyclic interval of length len from a = (C + d_lo) mod M; its ascending order is
+// [0, a + len - M) then [a, M) when it wraps, so that the lanes of a group still hold the output row
+// in ascending flat index.  R's row M - 1 of a coarsened periodic axis has the fine points 0, n - 2,
+// n - 1 (ascending) with 0.5, 0.5, 1.0, and row 0 of P the columns 0 and M - 1 with 0.5 each (n >= 4:
+// a row of P still holds a column once).  Every wrapped index is a select on an in-range value.
+// PER = false is the code without any of this.
+__device__ __forceinline__ int32_t tg_delta(int32_t col, int32_t C, int32_t M) {
+  const int32_t d = col - C;  // both in [0, M)
+  const int32_t e = d < -(M >> 1) ? d + M : d;
+  return e > ((M + 1) >> 1) - 1 ? e - M : e;
+}
+// offsets [l, h] from C of the columns of row k of P1per(2 M) (c = 0: of column k of the identity)
+__device__ __forceinline__ void tg_cols_per(uint32_t k, uint32_t m, uint32_t c, uint32_t C, int32_t* l, int32_t* h) {
+  if (!c || (k & 1u)) {
+    *l = *h = tg_delta((int32_t)(c ? (k - 1u) >> 1 : k), (int32_t)C, (int32_t)m);
+  } else {
+    const int32_t r = (int32_t)(k >> 1);  // <= m - 1: k <= 2 m - 2
+    const int32_t d0 = tg_delta(r >= 1 ? r - 1 : (int32_t)m - 1, (int32_t)C, (int32_t)m);
+    const int32_t d1 = tg_delta(r, (int32_t)C, (int32_t)m);
+    *l = d0 < d1 ? d0 : d1;
+    *h = d0 < d1 ? d1 : d0;
+  }
+}
+// the t-th column (ascending) of the cyclic interval of `len` <= M columns from (C + lo) mod M
+__device__ __forceinline__ int32_t tg_lane_col(int32_t t, int32_t lo, int32_t len, int32_t C, int32_t M) {
+  const int32_t a0 = C + lo;  // in [-floor(M / 2), 2 M - 2]
+  const int32_t a1 = a0 < 0 ? a0 + M : a0;
+  const int32_t a = a1 >= M ? a1 - M : a1;
+  const int32_t over = a + len - M;  // > 0: the interval wraps, its first `over` members are 0 ..
+  return over > 0 ? (t < over ? t : a + t - over) : a + t;
+}
+// P1per(k, J) for a column J inside [0, m) of a periodic axis (c = 0: the identity)
+__device__ __forceinline__ double tg_weight_per(uint32_t k, int32_t J, uint32_t c, uint32_t m) {
+  if (!c) return (int32_t)k == J ? 1.0 : 0.0;
+  const int32_t t = (int32_t)k - 2 * J;
+  if (t == 1) return 1.0;
+  if (t == 0 || t == 2) return 0.5;
+  return (k == 0u && J + 1 == (int32_t)m) ? 0.5 : 0.0;
+}
+// the t-th fine point (ascending) of R's row C on a coarsened axis of n points (seam: row n / 2 - 1
+// of a periodic axis) and its weight
+__device__ __forceinline__ uint32_t tg_fine(uint32_t C, uint32_t t, bool seam) {
+  return seam ? (t == 0u ? 0u : 2u * C + t - 1u) : 2u * C + t;
+}
+template <int SLOTS, bool FILL, bool PER>
 __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
     TensorGrid g, double inv_nx, double inv_ny, const int32_t* __restrict__ arp,
     const int32_t* __restrict__ acol, const double* __restrict__ aval, int32_t* __restrict__ cnt,
@@ -5611,11 +5662,16 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
   const uint32_t I = row % g.mx, qr = row / g.mx, J = qr % g.my, K = qr / g.my;
   const uint32_t rx = g.cx ? 3u : 1u, ry = g.cy ? 3u : 1u, rz = g.cz ? 3u : 1u;
   const uint32_t nt = rx * ry * rz;  // fine rows of R's row, (z, y, x) ascending
-  // the box of coarse columns
+  // PER: the periodic axes, and whether this coarse row is the last one of a coarsened periodic axis
+  const bool px = PER && (g.per() & 1u), py = PER && (g.per() & 2u), pz = PER && (g.per() & 4u);
+  const bool seamx = px && g.cx && 2u * I + 2u == g.nx, seamy = py && g.cy && 2u * J + 2u == g.ny,
+             seamz = pz && g.cz && 2u * K + 2u == g.nz;
+  // the box of coarse columns (PER: offsets from I / J / K on a periodic axis, which may be negative)
   int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
+  if (PER) hi[0] = hi[1] = hi[2] = INT32_MIN;
   if (s < nt) {
-    const uint32_t ix = g.cx ? 2u * I + s % rx : I, iy = g.cy ? 2u * J + (s / rx) % ry : J,
-                   iz = g.cz ? 2u * K + s / (rx * ry) : K;
+    const uint32_t ix = g.cx ? tg_fine(I, s % rx, seamx) : I, iy = g.cy ? tg_fine(J, (s / rx) % ry, seamy) : J,
+                   iz = g.cz ? tg_fine(K, s / (rx * ry), seamz) : K;
     if (ix < g.nx && iy < g.ny && iz < g.nz) {
       const uint32_t i = (iz * g.ny + iy) * g.nx + ix;
       for (int32_t p = arp[i], e = arp[i + 1]; p < e; ++p) {
@@ -5623,9 +5679,12 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
         tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
         tg_divmod(q, g.ny, inv_ny, &kz, &ky);
         int32_t l[3], h[3];
-        tg_cols(kx, g.mx, g.cx, &l[0], &h[0]);
-        tg_cols(ky, g.my, g.cy, &l[1], &h[1]);
-        tg_cols(kz, g.mz, g.cz, &l[2], &h[2]);
+        if (px) tg_cols_per(kx, g.mx, g.cx, I, &l[0], &h[0]);
+        else tg_cols(kx, g.mx, g.cx, &l[0], &h[0]);
+        if (py) tg_cols_per(ky, g.my, g.cy, J, &l[1], &h[1]);
+        else tg_cols(ky, g.my, g.cy, &l[1], &h[1]);
+        if (pz) tg_cols_per(kz, g.mz, g.cz, K, &l[2], &h[2]);
+        else tg_cols(kz, g.mz, g.cz, &l[2], &h[2]);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
           lo[a] = l[a] < lo[a] ? l[a] : lo[a];
@@ -5661,21 +5720,27 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
     Jx = lo[0] + (int32_t)(s % bx);
     Jy = lo[1] + (int32_t)((s / bx) % by);
     Jz = lo[2] + (int32_t)(s / (bx * by));
+    if (px) Jx = tg_lane_col((int32_t)(s % bx), lo[0], (int32_t)bx, (int32_t)I, (int32_t)g.mx);
+    if (py) Jy = tg_lane_col((int32_t)((s / bx) % by), lo[1], (int32_t)by, (int32_t)J, (int32_t)g.my);
+    if (pz) Jz = tg_lane_col((int32_t)(s / (bx * by)), lo[2], (int32_t)(vol / (bx * by)), (int32_t)K, (int32_t)g.mz);
     for (uint32_t tz = 0; tz < 3; ++tz) {
       if (!g.cz && tz > 0) break;
-      const uint32_t iz = g.cz ? 2u * K + tz : K;
+      const uint32_t iz = g.cz ? tg_fine(K, tz, seamz) : K;
       if (iz >= g.nz) break;
-      const double wz = g.cz ? tn_weight<double>(K, tz, g.nz, g.sides & 16u, g.sides & 32u) : 1.0;
+      const double wz = seamz ? (tz == 2u ? 1.0 : 0.5)
+                              : (g.cz ? tn_weight<double>(K, tz, g.nz, g.sides & 16u, g.sides & 32u) : 1.0);
       for (uint32_t ty = 0; ty < 3; ++ty) {
         if (!g.cy && ty > 0) break;
-        const uint32_t iy = g.cy ? 2u * J + ty : J;
+        const uint32_t iy = g.cy ? tg_fine(J, ty, seamy) : J;
         if (iy >= g.ny) break;
-        const double rzy = wz * (g.cy ? tn_weight<double>(J, ty, g.ny, g.sides & 4u, g.sides & 8u) : 1.0);
+        const double rzy = wz * (seamy ? (ty == 2u ? 1.0 : 0.5)
+                                       : (g.cy ? tn_weight<double>(J, ty, g.ny, g.sides & 4u, g.sides & 8u) : 1.0));
         for (uint32_t tx = 0; tx < 3; ++tx) {
           if (!g.cx && tx > 0) break;
-          const uint32_t ix = g.cx ? 2u * I + tx : I;
+          const uint32_t ix = g.cx ? tg_fine(I, tx, seamx) : I;
           if (ix >= g.nx) break;
-          const double r = rzy * (g.cx ? tn_weight<double>(I, tx, g.nx, g.sides & 1u, g.sides & 2u) : 1.0);  // R(I, i)
+          const double r = rzy * (seamx ? (tx == 2u ? 1.0 : 0.5)
+                                        : (g.cx ? tn_weight<double>(I, tx, g.nx, g.sides & 1u, g.sides & 2u) : 1.0));  // R(I, i)
           const uint32_t i = (iz * g.ny + iy) * g.nx + ix;
           bool hit_i = false;
           double ap = 0.0;  // (A P)(i, J)
@@ -5683,9 +5748,9 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
             uint32_t kx, ky, kz, q;
             tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
             tg_divmod(q, g.ny, inv_ny, &kz, &ky);
-            const double w = tg_weight(kx, Jx, g.cx, g.nx, g.sides & 1u, g.sides & 2u) *
-                             tg_weight(ky, Jy, g.cy, g.ny, g.sides & 4u, g.sides & 8u) *
-                             tg_weight(kz, Jz, g.cz, g.nz, g.sides & 16u, g.sides & 32u);
+            const double w = (px ? tg_weight_per(kx, Jx, g.cx, g.mx) : tg_weight(kx, Jx, g.cx, g.nx, g.sides & 1u, g.sides & 2u)) *
+                             (py ? tg_weight_per(ky, Jy, g.cy, g.my) : tg_weight(ky, Jy, g.cy, g.ny, g.sides & 4u, g.sides & 8u)) *
+                             (pz ? tg_weight_per(kz, Jz, g.cz, g.mz) : tg_weight(kz, Jz, g.cz, g.nz, g.sides & 16u, g.sides & 32u));
             if (w != 0.0) {
               if (FILL) {
                 const double t = aval[p] * w;
@@ -5716,23 +5781,35 @@ __global__ __launch_bounds__(256) void tensor_galerkin_kernel(
     oval[at] = acc;
   }
 }
-hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const int32_t* arp,
+// periodic: the solver's periodic axes.  The kernel needs every one of them, also those this level
+// does not coarsen (see above), so the seam bits are set from `periodic`, not `periodic & mask`.
+hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                                  const int32_t* arp,
                                   const int32_t* acol, const double* aval, int32_t* cnt,
                                   const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
                                   hipStream_t st) {
   TensorGrid g;
-  if (!tensor_grid(dim, dims, mask, sides, 0u, &g)) return hipErrorInvalidValue;
+  if (!tensor_grid(dim, dims, mask, sides, periodic, &g)) return hipErrorInvalidValue;
+  g.sides = (g.sides & 0xffu) | (periodic << 8);
   const uint32_t nH = g.mx * g.my * g.mz;
   const double inv_nx = 1.0 / (double)g.nx, inv_ny = 1.0 / (double)g.ny;
-#define TG_LAUNCH(SLOTS, FILL)                                                                        \
-  hipLaunchKernelGGL((tensor_galerkin_kernel<SLOTS, FILL>), dim3((nH + 256u / SLOTS - 1u) / (256u / SLOTS)), \
+#define TG_LAUNCH(SLOTS, FILL, PER)                                                                        \
+  hipLaunchKernelGGL((tensor_galerkin_kernel<SLOTS, FILL, PER>), dim3((nH + 256u / SLOTS - 1u) / (256u / SLOTS)), \
                      dim3(256), 0, st, g, inv_nx, inv_ny, arp, acol, aval, cnt, orp, ocol, oval, overflow)
-  if (dim == 3) {
-    if (fill) TG_LAUNCH(32, true);
-    else TG_LAUNCH(32, false);
+  if (periodic) {
+    if (dim == 3) {
+      if (fill) TG_LAUNCH(32, true, true);
+      else TG_LAUNCH(32, false, true);
+    } else {
+      if (fill) TG_LAUNCH(16, true, true);
+      else TG_LAUNCH(16, false, true);
+    }
+  } else if (dim == 3) {
+    if (fill) TG_LAUNCH(32, true, false);
+    else TG_LAUNCH(32, false, false);
   } else {
-    if (fill) TG_LAUNCH(16, true);
-    else TG_LAUNCH(16, false);
+    if (fill) TG_LAUNCH(16, true, false);
+    else TG_LAUNCH(16, false, false);
   }
 #undef TG_LAUNCH
   return hipGetLastError();

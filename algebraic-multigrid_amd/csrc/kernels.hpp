@@ -481,7 +481,10 @@ hipError_t launch_galerkin_rap(bool fill, int64_t n_h, int64_t n_H, const int32_
 // by the caller) is set when a coarse row reaches more coarse columns than a lane group holds
 // (16 in 2-D, 32 in 3-D): the result is then unusable and the caller takes the host product.
 // mask, sides: the coarsened axes and the natural sides, as for launch_tensor_restrict.
-hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, const int32_t* arp,
+// periodic: the periodic axes (tensor_P with periodic), every one of them whether this level
+// coarsens it or not -- the wrap entries of A count on both; 0 launches the kernel without the seam.
+hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
+                                  const int32_t* arp,
                                   const int32_t* acol, const double* aval, int32_t* cnt,
                                   const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
                                   hipStream_t st);

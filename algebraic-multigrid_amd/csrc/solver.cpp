@@ -182,10 +182,12 @@ hipError_t device_galerkin(const DevCsr& A, int64_t n_H, DevCsr* AH, Sparse* hos
 }
 
 // Setup on the device (K-TensorGalerkin): AH = R (A P) for the tensor-product pair of the grid
-// `dims` (mask: the coarsened axes, sides: the natural boundary sides) from CSR(A) on the device.  *ok = false: a coarse row reaches more columns than the
+// `dims` (mask: the coarsened axes, sides: the natural boundary sides, periodic: the periodic axes)
+// from CSR(A) on the device.  *ok = false: a coarse row reaches more columns than the
 // kernel's lane group holds; hipErrorInvalidValue: the product is beyond int32 indexing.  Either
 // way the caller takes the host path.
-hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, int64_t n_H,
+hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides,
+                                  uint32_t periodic, int64_t n_H,
                                   DevCsr* AH,
                                   bool* ok) {
   *ok = false;
@@ -196,7 +198,7 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if ((e = total.alloc(sizeof(int64_t))) != hipSuccess) return e;
   if ((e = ovf.alloc(sizeof(int32_t))) != hipSuccess) return e;
   if ((e = hipMemset(ovf.p, 0, sizeof(int32_t))) != hipSuccess) return e;
-  if ((e = launch_tensor_galerkin(false, dim, dims, mask, sides, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
+  if ((e = launch_tensor_galerkin(false, dim, dims, mask, sides, periodic, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
                                   nullptr, nullptr, ovf.as<int32_t>(), nullptr)) != hipSuccess)
     return e;
   int32_t over = 0;
@@ -211,7 +213,7 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if (nnz >= ((int64_t)1 << 31) - 1) return hipErrorInvalidValue;
   if ((e = AH->idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
   if ((e = AH->val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
-  if ((e = launch_tensor_galerkin(true, dim, dims, mask, sides, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
+  if ((e = launch_tensor_galerkin(true, dim, dims, mask, sides, periodic, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
                                   AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr)) != hipSuccess)
     return e;
   AH->n_rows = AH->n_cols = n_H;
@@ -1367,6 +1369,13 @@ int g_march = [] {
 }();
 int g_tail_fusion = [] {
   const char* e = std::getenv("AMG_HIP_TAIL_FUSION");
+  return (e && *e == '1') ? 1 : 0;
+}();
+// amg_hip_set_periodic_device_setup / AMG_HIP_PERIODIC_DEVICE_SETUP=1: amg_hip_create_tensor_periodic_dev
+// builds on the device.  The same solver bit for bit; 0 by default only because an earlier test pins
+// amg_hip_setup_on_device == 0 for that entry point ("Periodic axes").
+int g_periodic_device_setup = [] {
+  const char* e = std::getenv("AMG_HIP_PERIODIC_DEVICE_SETUP");
   return (e && *e == '1') ? 1 : 0;
 }();
 int64_t g_patch_min_rows = 1000000;  // amg_hip_set_patch_min_rows (level 4 of 4096^2 has 1 048 575 rows)
@@ -3197,7 +3206,7 @@ amg_hip_status device_setup_begin(const amg_hip_options& o, std::unique_ptr<amg_
 amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const int64_t dims0[3], bool tensor,
                                  bool user, int32_t n_levels, SetupLap& lap,
                                  const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported,
-                                 const SemiRule* semi = nullptr);
+                                 const SemiRule* semi = nullptr, uint32_t periodic = 0);
 
 // Front end of the model problem: AMG::Multigrid's constructor (multigrid.hpp:151-244) for A = Grid::laplacian(n), b =
 // Grid::rhs(n) without host matrices: generator, Galerkin chain, dictionary encoder, diagonal
@@ -3299,10 +3308,11 @@ amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const 
 // that no level crosses to the host.  The model problem's front ends keep the launches they had.
 // semi (amg_hip_create_tensor_semi_dev): the levels coarsen the axes of its masks, or those the
 // automatic rule picks from K-AxisStrength's maxima; n_levels is then an upper bound.
+// periodic (amg_hip_create_tensor_periodic_dev): the periodic axes, L.tper of every level.
 amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const int64_t dims0[3], bool tensor,
                                  bool user, int32_t n_levels, SetupLap& lap,
                                  const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported,
-                                 const SemiRule* semi) {
+                                 const SemiRule* semi, uint32_t periodic) {
   *unsupported = true;
   const amg_hip_options& o = s->opt;
   const bool lex = o.smoother <= AMG_HIP_SM_SOR;
@@ -3339,6 +3349,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
       L.tdim = dim;
       for (int a = 0; a < 3; ++a) L.dims[a] = tdims[a];
       L.tsides = (uint32_t)o.natural_sides;
+      L.tper = periodic;
     }
     if (tensor && l + 1 < n_levels) {  // the axes this level coarsens (build_solver's rule)
       L.tmask = tensor_full_mask(dim);
@@ -3503,7 +3514,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
       L.tensor_stencil = true;  // o.stencil_transfers is set and N < 2^28
       L.n_coarse = tdims[0] * tdims[1] * tdims[2];
       bool ok_g = false;
-      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.tmask, L.tsides, L.n_coarse, &next, &ok_g);
+      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.tmask, L.tsides, L.tper, L.n_coarse, &next, &ok_g);
       if (ge == hipErrorInvalidValue || (ge == hipSuccess && !ok_g)) {
         if (timing) std::fprintf(stderr, "amg_hip device setup: Galerkin product of level %d exceeds %s -> host path\n", l,
                                  ge == hipSuccess ? "the kernel's columns per coarse row" : "int32 indexing");
@@ -4186,6 +4197,7 @@ void amg_hip_set_patch_xf(int32_t on) { g_patch_xf = on ? 1 : 0; }
 void amg_hip_set_patch_tall(int32_t on) { g_patch_tall = on ? 1 : 0; }
 void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
+void amg_hip_set_periodic_device_setup(int32_t on) { g_periodic_device_setup = on ? 1 : 0; }
 void amg_hip_set_patch_min_rows(int64_t rows) { g_patch_min_rows = rows < 0 ? INT64_MAX : rows; }
 
 void amg_hip_set_default_layout(int32_t layout) {
@@ -4482,7 +4494,8 @@ amg_hip_status amg_hip_create_poisson_tensor(int32_t dim, int64_t n, int32_t n_l
 static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr, const int32_t* col,
                                                const double* val, const double* b, int dim, const int64_t* dims,
                                                int32_t n_levels, const amg_hip_options& o, amg_hip_solver** out,
-                                               bool* unsupported, const SemiRule* semi, const std::string& who) {
+                                               bool* unsupported, const SemiRule* semi, const std::string& who,
+                                               uint32_t periodic = 0) {
   *unsupported = true;
   std::unique_ptr<amg_hip_solver> s;
   {
@@ -4533,15 +4546,17 @@ static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr,
     return AMG_HIP_OK;
   };
   const amg_hip_status r = device_level_loop(s.get(), cur, dim, dims, true, true, n_levels, lap, put_rhs, unsupported,
-                                             semi);
+                                             semi, periodic);
   if (r != AMG_HIP_OK || *unsupported) return r;
   *out = s.release();
   return AMG_HIP_OK;
 }
 
 // amg_hip_create_tensor_dev and, with `semi_on`, amg_hip_create_tensor_semi_dev
-// and, with `per_on`, amg_hip_create_tensor_periodic_dev: its hierarchy is built on the host (the
-// checked arrays take the host constructor), so the level loop on the device is never entered
+// and, with `per_on`, amg_hip_create_tensor_periodic_dev: with amg_hip_set_periodic_device_setup(1)
+// the level loop runs on the device with the mask (K-TensorGalerkin's PER form); with the default 0
+// its hierarchy is built on the host (the checked arrays take the host constructor) and the level
+// loop on the device is never entered
 static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, int64_t n, const int32_t* rowptr_dev,
                                         const int32_t* col_dev, const double* val_dev, const double* b_dev,
                                         int32_t dim, const int64_t* dims, int32_t n_levels,
@@ -4605,9 +4620,9 @@ static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, in
     return fail(AMG_HIP_EINVAL, "`omega` must be in [0, 2] but got omega=" + std::to_string(o.omega) + "\n");
   bool unsupported = true;
   amg_hip_options od = o;
-  if (per_on) od.host_galerkin = 1;  // copy + check only: K-TensorGalerkin does not know the seam
+  if (per_on && !g_periodic_device_setup) od.host_galerkin = 1;  // copy + check only
   amg_hip_status r = build_tensor_user_device(n, rowptr_dev, col_dev, val_dev, b_dev, dim, dims, n_levels, od, out,
-                                              &unsupported, semi, who);
+                                              &unsupported, semi, who, per_on ? (uint32_t)periodic_axes : 0u);
   if (r != AMG_HIP_OK || !unsupported) return r;
   // options that need host structures (or a product the kernels refused): the checked arrays are
   // downloaded, transposed on the host and given to the host constructor

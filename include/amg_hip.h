@@ -282,6 +282,12 @@ void amg_hip_set_band_chain(int32_t on);
  * launch takes as long as the launches it replaces.                       */
 void amg_hip_set_tail_fusion(int32_t on);
 
+/* amg_hip_create_tensor_periodic_dev builds its hierarchy on the device (K-TensorGalerkin with the
+ * seam) instead of downloading to the host constructor.  Process-wide, read when a solver is created;
+ * default 0 (AMG_HIP_PERIODIC_DEVICE_SETUP=1 in the environment turns it on).  The same solver bit
+ * for bit either way; amg_hip_setup_on_device tells the two apart.                                 */
+void amg_hip_set_periodic_device_setup(int32_t on);
+
 /* Number of usable HIP devices (0 when none; never fails). */
 int amg_hip_device_count(void);
 
@@ -554,10 +560,18 @@ amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_d
                                               const amg_hip_options* opts, amg_hip_solver** out);
 /* amg_hip_create_tensor_periodic for a caller's matrix in DEVICE memory (CSR, as for
  * amg_hip_create_tensor_dev).  The arguments are checked as by the host constructor, the arrays by
- * K-CsrCheck; then they are downloaded, transposed on the host and given to
- * amg_hip_create_tensor_periodic -- the silent host path of amg_hip_create_tensor_dev, always:
- * K-TensorGalerkin does not know the seam yet.  The solver equals the host constructor's bit for
- * bit and amg_hip_setup_on_device reports 0.                                                     */
+ * K-CsrCheck, first and whatever the switch says.
+ * With amg_hip_set_periodic_device_setup(1): amg_hip_create_tensor_dev's level loop on the device
+ * with the periodic mask -- the Galerkin products run as K-TensorGalerkin's periodic form (the seam
+ * of a coarsened axis and the wrap entries of A on every periodic axis), with explicit axis_masks as
+ * for amg_hip_create_tensor_semi_dev; natural_sides and singular are honoured as on the host, the
+ * coarsest operator is factored on the host.  Same smoothers, layouts and silent fallbacks to the
+ * host constructor as amg_hip_create_tensor_dev (among them a coarse row beyond the kernel's lane
+ * group); amg_hip_setup_on_device reports 1 unless it fell back.
+ * With the switch off (the default): the arrays are downloaded, transposed on the host and given to
+ * amg_hip_create_tensor_periodic -- the silent host path, always -- and amg_hip_setup_on_device
+ * reports 0.
+ * Either way the solver equals the host constructor's bit for bit.                               */
 amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
                                                   const double* val_dev, const double* b_dev, int32_t dim,
                                                   const int64_t* dims /* 3, host */, int32_t periodic_axes,
@@ -566,7 +580,8 @@ amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowp
                                                   const amg_hip_options* opts, amg_hip_solver** out);
 /* *on = 1: the hierarchy was built by a device-only path (amg_hip_create_poisson,
  * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor, amg_hip_create_tensor_dev,
- * amg_hip_create_tensor_semi_dev when they did not fall back),
+ * amg_hip_create_tensor_semi_dev, and amg_hip_create_tensor_periodic_dev under
+ * amg_hip_set_periodic_device_setup(1), when they did not fall back),
  * 0: by the host constructor -- every other entry point and the silent fallbacks.  Also on
  * host_only solvers (0).                                                                        */
 amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on);

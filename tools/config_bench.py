@@ -15,6 +15,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py semi [<nx> <ny> <nz> <eps_x> <eps_y> <eps_z>] PCG to 1e-8 on an axis-scaled diffusion operator: full coarsening + Jacobi, semi-coarsening + Jacobi, full coarsening + alternating lines, semi-coarsening + amg_hip_pcg_mixed (legs alternate)
        config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
        config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
+       config_bench.py periodic-setup [<nx> <ny> <nz>]             set-up seconds of tensor_periodic_dev on that operator with set_periodic_device_setup off (host constructor) and on (device), legs alternate; next to them tensor_dev on the open-box operator of the same grid
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -736,6 +737,47 @@ def run_periodic(dims, reps=3, rtol=1e-8, max_iters=300):
         mg.close()
 
 
+def run_periodic_setup(dims, reps=3):
+    """Set-up seconds of Multigrid.tensor_periodic_dev on run_periodic's operator (every axis periodic,
+    singular, true Jacobi 2+2 omega 0.8, full coarsening) with amg_hip_set_periodic_device_setup off --
+    the arrays are downloaded and take the host constructor -- and on -- the level loop on the device
+    with K-TensorGalerkin's periodic form.  The two legs alternate in one process, `reps` repeats; wall
+    time around the constructor, closed by a device synchronise.  Next to them, in the same loop,
+    Multigrid.tensor_dev on the open-box operator of tensor-user-setup on the same grid with the same
+    number of levels: the product without a seam."""
+    import torch
+    dim = len(dims)
+    per = (1 << dim) - 1
+    L = periodic_levels(dims)
+    tag = " x ".join(str(d) for d in dims)
+    arrays = torch_periodic_diffusion(dims, per)
+    box = torch_diffusion(dims)
+    torch.cuda.synchronize()
+    jac = TENSOR_KW["jacobi"]
+    legs = (("switch off", 0, lambda: amg.Multigrid.tensor_periodic_dev(*arrays, dims, L, per, singular=True, **jac)),
+            ("switch on", 1, lambda: amg.Multigrid.tensor_periodic_dev(*arrays, dims, L, per, singular=True, **jac)),
+            ("open box tensor_dev", 0, lambda: amg.Multigrid.tensor_dev(*box, dims, L, **jac)))
+    best = {}
+    try:
+        for rep_ in range(reps):
+            for name, on, make in legs:
+                amg.set_periodic_device_setup(on)
+                t0 = time.perf_counter()
+                mg = make()
+                mg.sync()
+                dt = time.perf_counter() - t0
+                best[name] = min(best.get(name, dt), dt)
+                print(f"periodic-setup {tag} {L} levels, {name} rep {rep_}: {dt:.3f} s (setup_on_device "
+                      f"{mg.setup_on_device}, level-0 layout {mg.level_layout(0)}, coarsest {mg.get_n_dofs(L - 1)} dofs)",
+                      flush=True)
+                mg.close()
+    finally:
+        amg.set_periodic_device_setup(0)
+    off, on, box_t = best["switch off"], best["switch on"], best["open box tensor_dev"]
+    print(f"periodic-setup {tag} {L} levels: best switch off {off:.3f} s, best switch on {on:.3f} s, ratio "
+          f"{off / on:.1f}; open box tensor_dev {box_t:.3f} s, switch on / open box {on / box_t:.2f}", flush=True)
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -886,6 +928,17 @@ elif len(sys.argv) > 1 and sys.argv[1] == "periodic":
     else:
         run_periodic((4096, 1024))
         run_periodic((256, 256, 256))
+elif len(sys.argv) > 1 and sys.argv[1] == "periodic-setup":
+    # profiles/periodic_setup.txt
+    os.environ.setdefault("AMG_HIP_TIMING", "1")
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    if len(sys.argv) > 4:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_periodic_setup(d if d[2] > 1 else d[:2])
+    else:
+        run_periodic_setup((1024, 1024))
+        run_periodic_setup((4096, 1024))
+        run_periodic_setup((256, 256, 256))
 elif len(sys.argv) > 3 and sys.argv[1] == "tensor10":
     mg = amg.Multigrid.poisson_tensor(int(sys.argv[2]), int(sys.argv[3]), stencil_transfers=len(sys.argv) < 5,
                                       **TENSOR_KW["jacobi"])
