@@ -40,6 +40,7 @@ class Options(C.Structure):
                 ("fast_coarse_solve", C.c_int32), ("host_galerkin", C.c_int32),
                 ("keep_residual", C.c_int32), ("exact_coarse_solve", C.c_int32),
                 ("exact_gs", C.c_int32),
+                ("cyclic_lines", C.c_int32),  # in the former alignment padding in front of `stream`
                 ("stream", C.c_void_p), ("window", C.c_int32), ("cheb_degree", C.c_int32),
                 ("cheb_lower", C.c_double), ("cheb_upper", C.c_double),
                 ("natural_sides", C.c_int32), ("singular", C.c_int32)]
@@ -213,6 +214,9 @@ _SIGS = {
     "amg_hip_line_directions": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "amg_hip_smooth_line_alt": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, C.c_int32, C.POINTER(C.c_int64),
                                           C.c_double, C.c_int64, C.c_int32, _f64p, _f64p]),
+    "amg_hip_line_cyclic": (C.c_int, [C.c_void_p, C.c_int32, _i32p]),
+    "amg_hip_smooth_line_alt_per": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, C.c_int32, C.POINTER(C.c_int64),
+                                              C.c_int32, C.c_double, C.c_int64, C.c_int32, _f64p, _f64p]),
     "amg_hip_smooth_chebyshev": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int32,
                                            C.c_double, C.c_double, C.c_int64]),
     "amg_hip_cycle_bytes": (C.c_int, [C.c_void_p, _f64p, _f64p]),
@@ -640,7 +644,7 @@ class Multigrid:
                stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
                no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
-               window=False, natural_sides=0, singular=False, _semi=None, _periodic=None):
+               window=False, natural_sides=0, singular=False, cyclic_lines=False, _semi=None, _periodic=None):
         """AMG::Multigrid on a FULL-coarsening hierarchy of the grid `dims` = (nx, ny) or (nx, ny, nz),
         x fastest (amg_hip_create_tensor): every axis m -> m // 2, tensor-product linear interpolation,
         matrix-free transfer kernels unless stencil_transfers=False.  A is the caller's matrix on
@@ -664,6 +668,7 @@ class Multigrid:
                          cheb_upper)
         o.window = int(window)
         o.natural_sides, o.singular = int(natural_sides), int(singular)
+        o.cyclic_lines = int(cyclic_lines)
         h = C.c_void_p()
         if _periodic is not None:  # tensor_periodic
             per, masks = _periodic
@@ -694,7 +699,7 @@ class Multigrid:
                    no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                    exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
                    window=False, host_galerkin=False, fuse_prolong=False, natural_sides=0, singular=False,
-                   _semi=None, _periodic=None):
+                   cyclic_lines=False, _semi=None, _periodic=None):
         """Multigrid.tensor for a matrix that sits on the device, with the set-up on the device
         (amg_hip_create_tensor_dev).  A is in CSR: crow (n + 1 int32 row pointers), col (int32,
         ascending inside a row), val (float64), and b (n float64), each a contiguous 1-D torch tensor
@@ -736,6 +741,7 @@ class Multigrid:
                          cheb_upper)
         o.window = int(window)
         o.natural_sides, o.singular = int(natural_sides), int(singular)
+        o.cyclic_lines = int(cyclic_lines)
         if device_count() > 0:
             tdev = torch.device("cuda", device if device >= 0 else torch.cuda.current_device())
             dev = []
@@ -811,8 +817,10 @@ class Multigrid:
         an even length of at least 4 on its level and interpolates fine point 0 between coarse points 0
         and m/2 - 1.  axis_masks=None: full coarsening with exactly n_levels levels, else n_levels - 1
         explicit masks (there is no automatic rule).  natural_sides names sides of the other axes only;
-        singular=True needs all of those (none when every axis is periodic).  Options as for
-        Multigrid.tensor."""
+        singular=True needs all of those (none when every axis is periodic).  cyclic_lines=True
+        (smoother SM_LINE_ALT only): the line directions along a periodic axis of 3 points or more are
+        solved as cyclic tridiagonal systems, wrap entries included (line_cyclic tells which).  Options as
+        for Multigrid.tensor."""
         masks = cls._semi_rule(n_levels, axis_masks, 0.5, 1)[0]
         return cls.tensor(colptr, rowind, val, b, dims, n_levels, _periodic=(int(periodic_axes), masks), **opts)
 
@@ -1122,6 +1130,16 @@ class Multigrid:
         _chk(st)
         return [int(st3[d]) for d in range(nd.value)]
 
+    def line_cyclic(self, level):
+        """The mask of the axes of `level` whose lines the alternating line smoother solves cyclically
+        (amg_hip_line_cyclic; bit a = axis a); 0 without cyclic_lines."""
+        m = C.c_int32(0)
+        st = lib().amg_hip_line_cyclic(self._h, int(level), C.byref(m))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return m.value
+
     def coarse_solve_kind(self):
         return {0: "band (one wave, sequential, bit-exact)", 1: "spike (partitioned, parallel)",
                 2: "band-wide (blocked sequential, any half-bandwidth, bit-exact)",
@@ -1333,16 +1351,22 @@ def smooth_line(colptr, rowind, val, u, f, stride=0, omega=0.7, iters=1):
     return u
 
 
-def smooth_line_alt(colptr, rowind, val, u, f, dims, omega=0.8, iters=1, reverse=False):
+def smooth_line_alt(colptr, rowind, val, u, f, dims, omega=0.8, iters=1, reverse=False, periodic_axes=None):
     """amg_hip_smooth_line_alt: `iters` applications of the alternating line smoother on the grid
     `dims` (2 or 3 entries, x fastest), directions ascending (descending with `reverse`); returns the
-    new u."""
+    new u.  periodic_axes (a mask, bit a = axis a): amg_hip_smooth_line_alt_per, cyclic lines along
+    those axes where they have 3 points or more."""
     colptr, rowind, val, f = _a32(colptr), _a32(rowind), _a64(val), _a64(f)
     u = np.array(u, dtype=np.float64, copy=True)
     dims = [int(d) for d in dims]
     d3 = (C.c_int64 * 3)(*(dims + [1] * (3 - len(dims)))[:3]) if 1 <= len(dims) <= 3 else (C.c_int64 * 3)(0, 0, 0)
-    st = lib().amg_hip_smooth_line_alt(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), len(dims), d3,
-                                       float(omega), int(iters), 1 if reverse else 0, _p64(u), _p64(f))
+    if periodic_axes is None:
+        st = lib().amg_hip_smooth_line_alt(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), len(dims), d3,
+                                           float(omega), int(iters), 1 if reverse else 0, _p64(u), _p64(f))
+    else:
+        st = lib().amg_hip_smooth_line_alt_per(colptr.size - 1, _p32(colptr), _p32(rowind), _p64(val), len(dims),
+                                               d3, int(periodic_axes), float(omega), int(iters),
+                                               1 if reverse else 0, _p64(u), _p64(f))
     if st == EINVAL:
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)

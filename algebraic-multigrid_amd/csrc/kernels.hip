@@ -6528,12 +6528,51 @@ constexpr int LINE_INT = LINE_SEG - 1;  // interior rows of a full segment
 
 __host__ __device__ inline bool line_bad_pivot(double p) { return !(p == p) || p == 0.0 || p - p != 0.0; }
 
+// a_ij from the CSR rows, 0 when absent
+__host__ __device__ inline double line_entry(const int32_t* rowptr, const int32_t* col, const double* val, int64_t i,
+                                             int64_t j) {
+  for (int32_t p = rowptr[i]; p < rowptr[i + 1]; ++p)
+    if (col[p] == j) return val[p];
+  return 0.0;
+}
+// Cyclic lines (kernels.hpp: SeamRef).  The line of row i has stride s and m >= 3 rows, first row i0,
+// last row i1; alpha = a(i0, i1) and beta = a(i1, i0) are its wrap entries, gamma = -a(i0, i0).
+// Row i of T' = the open row with the diagonal d(i0) - gamma on the first and d(i1) - alpha beta /
+// gamma on the last row of the line; transposed: row i of T'^T (its lower entry is the upper entry
+// of the row before, its upper entry the lower entry of the row after).
+__host__ __device__ inline void line_cyclic_row(int64_t i, int64_t s, int64_t m, const int32_t* rowptr,
+                                                const int32_t* col, const double* val, bool transposed, double& dl,
+                                                double& dd, double& du) {
+  const int64_t q = (i / s) % m;
+  const int64_t i0 = i - q * s, i1 = i0 + (m - 1) * s;
+  dd = line_entry(rowptr, col, val, i, i);
+  if (transposed) {
+    dl = q > 0 ? line_entry(rowptr, col, val, i - s, i) : 0.0;
+    du = q < m - 1 ? line_entry(rowptr, col, val, i + s, i) : 0.0;
+  } else {
+    dl = q > 0 ? line_entry(rowptr, col, val, i, i - s) : 0.0;
+    du = q < m - 1 ? line_entry(rowptr, col, val, i, i + s) : 0.0;
+  }
+  if (q == 0) {
+    const double gamma = 0.0 - dd;
+    dd = dd - gamma;
+  } else if (q == m - 1) {
+    const double alpha = line_entry(rowptr, col, val, i0, i1), beta = line_entry(rowptr, col, val, i1, i0);
+    const double gamma = 0.0 - line_entry(rowptr, col, val, i0, i0);
+    dd = dd - alpha * beta / gamma;
+  }
+}
 // rows of T from CSR(A): dl -> L.dl, diagonal -> L.ip, du -> L.w
 // m > 0: the chain positions p = i / s form grid lines of m positions, and an entry that joins two
 // lines (AMG_HIP_SM_LINE_ALT: +-nx across a plane end) stays out of T
+// cyc (cyclic lines, m >= 3): 1 = T' of the Sherman-Morrison splitting (line_cyclic_row), 2 = its transpose
 __host__ __device__ inline void line_extract_row(int64_t i, int64_t n, int64_t s, int64_t m, const int32_t* rowptr,
                                                  const int32_t* col, const double* val, double* dl, double* dd,
-                                                 double* du) {
+                                                 double* du, int cyc = 0) {
+  if (cyc) {
+    line_cyclic_row(i, s, m, rowptr, col, val, cyc == 2, dl[i], dd[i], du[i]);
+    return;
+  }
   double a = 0.0, b = 0.0, c = 0.0;
   const int64_t q = m > 0 ? (i / s) % m : 0;
   const bool lower = m <= 0 || q > 0, upper = m <= 0 || q < m - 1;
@@ -6616,7 +6655,7 @@ __global__ __launch_bounds__(256) void line_extract_kernel(LineRef L, const int3
                                                            const int32_t* __restrict__ col,
                                                            const double* __restrict__ val) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < L.n) line_extract_row(i, L.n, L.s, L.m, rowptr, col, val, L.dl, L.ip, L.w);
+  if (i < L.n) line_extract_row(i, L.n, L.s, L.m, rowptr, col, val, L.dl, L.ip, L.w, L.cyc);
 }
 __global__ __launch_bounds__(256) void line_factor_seg_kernel(LineRef L, int64_t nch, int64_t nseg,
                                                               unsigned long long* bad) {
@@ -6907,7 +6946,7 @@ hipError_t launch_line_setup(const LineRef& L, const int32_t* rowptr, const int3
   return hipGetLastError();
 }
 int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32_t* col, const double* val,
-                        int64_t m) {
+                        int64_t m, int cyc) {
   std::vector<double> a[5];
   for (auto& x : a) x.assign((size_t)n, 0.0);
   LineRef L;
@@ -6918,7 +6957,7 @@ int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32
   L.cp = a[2].data();
   L.v = a[3].data();
   L.w = a[4].data();
-  for (int64_t i = 0; i < n; ++i) line_extract_row(i, n, s, m, rowptr, col, val, L.dl, L.ip, L.w);
+  for (int64_t i = 0; i < n; ++i) line_extract_row(i, n, s, m, rowptr, col, val, L.dl, L.ip, L.w, cyc);
   const int64_t nch = line_chains(n, L.s), nseg = line_segments(n, L.s);
   int64_t bad = -1;
   auto note = [&](int64_t b) {
@@ -6970,7 +7009,11 @@ enum { LX_FACTOR = 0, LX_FWD = 1, LX_BWD = 2 };
 constexpr int LINEX_PITCH = LINEX_COLS + 1;  // doubles per LDS row: the walking lanes hit different banks
 
 __host__ __device__ inline void linex_row(int64_t i, int64_t nx, const int32_t* rowptr, const int32_t* col,
-                                          const double* val, double& dl, double& dd, double& du) {
+                                          const double* val, double& dl, double& dd, double& du, int cyc = 0) {
+  if (cyc) {  // cyclic x lines: T' or its transpose (K-Line: line_cyclic_row)
+    line_cyclic_row(i, 1, nx, rowptr, col, val, cyc == 2, dl, dd, du);
+    return;
+  }
   const int64_t x = i % nx;
   dl = dd = du = 0.0;
   for (int32_t p = rowptr[i]; p < rowptr[i + 1]; ++p) {
@@ -6984,7 +7027,7 @@ __global__ __launch_bounds__(256) void linex_extract_kernel(LineXRef L, const in
                                                             const int32_t* __restrict__ col,
                                                             const double* __restrict__ val) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < L.n) linex_row(i, L.nx, rowptr, col, val, L.dl[i], L.ip[i], L.cp[i]);
+  if (i < L.n) linex_row(i, L.nx, rowptr, col, val, L.dl[i], L.ip[i], L.cp[i], L.cyc);
 }
 
 // a, b, c: the three arrays a chunk reads (FACTOR: dl, dd, du; FWD: r, dl, ip; BWD: y, cp, u);
@@ -7093,11 +7136,12 @@ hipError_t launch_linex_setup(const LineXRef& L, const int32_t* rowptr, const in
                      L.ip, L.cp, L.ip, L.cp, 0.0, o);
   return hipGetLastError();
 }
-int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int32_t* col, const double* val) {
+int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int32_t* col, const double* val,
+                         int cyc) {
   double cprev = 0.0;
   for (int64_t i = 0; i < n; ++i) {
     double dl, dd, du;
-    linex_row(i, nx, rowptr, col, val, dl, dd, du);
+    linex_row(i, nx, rowptr, col, val, dl, dd, du, cyc);
     const double piv = dd - dl * cprev;
     if (line_bad_pivot(piv)) return i;
     cprev = du * (1.0 / piv);
@@ -7112,6 +7156,195 @@ hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double om
                      nullptr);
   hipLaunchKernelGGL(linex_kernel<LX_BWD>, grid, dim3(64), 0, st, L.n, len, nruns, r, L.cp, u, u, nullptr, omega,
                      nullptr);
+  return hipGetLastError();
+}
+
+// ---- K-LineSeam: the rank-one correction of a cyclic line solve (kernels.hpp: SeamRef) ----------
+// Per line: fac = (sum over the line of p_i r_i) / den; r(i0) -= fac gamma; r(i1) -= fac beta.  The
+// open solve with the factors of T' that follows then gives T_a^-1 r of the cyclic T_a.
+//   seamx_kernel<W>     x lines (s = 1).  W = 4 .. 64 lanes run across a line, 64 / W lines to a wave.
+//                       A lane sums its columns k, k + W, k + 2 W, ... in ascending order (the loads of
+//                       SEAM_BATCH columns are issued before the first is used), a butterfly of log2 W
+//                       __shfl_xor steps adds the lanes, lane 0 of the line corrects the two ends.
+//   seam_stride_kernel  y and z lines.  One lane per line walks its m rows at stride s in ascending
+//                       order; neighbouring lanes hold neighbouring lines, so every step is a
+//                       coalesced row of loads.
+// The order of every sum is fixed by (m, s) alone.
+namespace {
+constexpr int SEAM_BATCH = 4;
+template <int W>
+__global__ __launch_bounds__(256) void seamx_kernel(int64_t nlines, int64_t m, const double* __restrict__ p,
+                                                    const double* __restrict__ coef, double* r) {
+  constexpr int LPW = 64 / W;  // lines per wave
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const int k = lane & (W - 1);
+  const int64_t line = wave * LPW + lane / W;
+  const bool live = line < nlines;
+  const int64_t i0 = live ? line * m : 0;
+  double acc = 0.0;
+  if (live) {
+    for (int64_t c0 = k; c0 < m; c0 += (int64_t)SEAM_BATCH * W) {
+      double pv[SEAM_BATCH], rv[SEAM_BATCH];
+#pragma unroll
+      for (int j = 0; j < SEAM_BATCH; ++j) {
+        const int64_t c = c0 + (int64_t)j * W;
+        pv[j] = c < m ? p[i0 + c] : 0.0;
+        rv[j] = c < m ? r[i0 + c] : 0.0;
+      }
+#pragma unroll
+      for (int j = 0; j < SEAM_BATCH; ++j)
+        if (c0 + (int64_t)j * W < m) acc = acc + pv[j] * rv[j];
+    }
+  }
+#pragma unroll
+  for (int off = W / 2; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, W);
+  if (live && k == 0) {
+    const double fac = acc / coef[line];
+    const int64_t i1 = i0 + m - 1;
+    r[i0] = r[i0] - fac * coef[nlines + line];
+    r[i1] = r[i1] - fac * coef[2 * nlines + line];
+  }
+}
+constexpr int SEAM_WALK = 8;
+__global__ __launch_bounds__(256) void seam_stride_kernel(int64_t nlines, int64_t s, int64_t m,
+                                                          const double* __restrict__ p,
+                                                          const double* __restrict__ coef, double* r) {
+  const int64_t line = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (line >= nlines) return;
+  const int64_t b = line / s;
+  const int64_t i0 = b * s * m + (line - b * s);
+  double acc = 0.0;
+  for (int64_t k0 = 0; k0 < m; k0 += SEAM_WALK) {
+    double pv[SEAM_WALK], rv[SEAM_WALK];
+#pragma unroll
+    for (int j = 0; j < SEAM_WALK; ++j) {
+      const bool on = k0 + j < m;
+      pv[j] = on ? p[i0 + (k0 + j) * s] : 0.0;
+      rv[j] = on ? r[i0 + (k0 + j) * s] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < SEAM_WALK; ++j)
+      if (k0 + j < m) acc = acc + pv[j] * rv[j];
+  }
+  const double fac = acc / coef[line];
+  const int64_t i1 = i0 + (m - 1) * s;
+  r[i0] = r[i0] - fac * coef[nlines + line];
+  r[i1] = r[i1] - fac * coef[2 * nlines + line];
+}
+
+// set-up: the two right-hand sides u = gamma e(i0) + beta e(i1), v = e(i0) + (alpha / gamma) e(i1)
+__host__ __device__ inline void seam_wrap(int64_t i0, int64_t s, int64_t m, const int32_t* rowptr, const int32_t* col,
+                                          const double* val, double& alpha, double& beta, double& gamma) {
+  const int64_t i1 = i0 + (m - 1) * s;
+  alpha = line_entry(rowptr, col, val, i0, i1);
+  beta = line_entry(rowptr, col, val, i1, i0);
+  gamma = 0.0 - line_entry(rowptr, col, val, i0, i0);
+}
+__global__ __launch_bounds__(256) void seam_rhs_kernel(int64_t n, int64_t s, int64_t m,
+                                                       const int32_t* __restrict__ rowptr,
+                                                       const int32_t* __restrict__ col,
+                                                       const double* __restrict__ val, double* u, double* v) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t q = (i / s) % m;
+  double uu = 0.0, vv = 0.0;
+  if (q == 0 || q == m - 1) {
+    double alpha, beta, gamma;
+    seam_wrap(i - q * s, s, m, rowptr, col, val, alpha, beta, gamma);
+    uu = q == 0 ? gamma : beta;
+    vv = q == 0 ? 1.0 : alpha / gamma;
+  }
+  u[i] = uu;
+  v[i] = vv;
+}
+__host__ __device__ inline double seam_den(double alpha, double gamma, double q0, double q1) {
+  return (1.0 + q0) + (alpha / gamma) * q1;
+}
+// coef = den | gamma | beta of every line from q = T'^-1 u; bad[0] = first row of the first line whose
+// den is zero or not finite
+__global__ __launch_bounds__(256) void seam_coef_kernel(int64_t nlines, int64_t s, int64_t m,
+                                                        const int32_t* __restrict__ rowptr,
+                                                        const int32_t* __restrict__ col,
+                                                        const double* __restrict__ val,
+                                                        const double* __restrict__ q, double* coef,
+                                                        unsigned long long* bad) {
+  const int64_t line = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (line >= nlines) return;
+  const int64_t b = line / s;
+  const int64_t i0 = b * s * m + (line - b * s), i1 = i0 + (m - 1) * s;
+  double alpha, beta, gamma;
+  seam_wrap(i0, s, m, rowptr, col, val, alpha, beta, gamma);
+  const double den = seam_den(alpha, gamma, q[i0], q[i1]);
+  coef[line] = den;
+  coef[nlines + line] = gamma;
+  coef[2 * nlines + line] = beta;
+  if (line_bad_pivot(den)) atomicMin(bad, (unsigned long long)i0);
+}
+inline bool seam_ok(int64_t n, int64_t s, int64_t m) {
+  return n > 0 && n < ((int64_t)1 << 31) && s >= 1 && m >= 3 && s * m <= n && n % (s * m) == 0;
+}
+}  // namespace
+
+hipError_t launch_seam_rhs(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, const int32_t* col,
+                           const double* val, double* u, double* v, hipStream_t st) {
+  if (!seam_ok(n, s, m)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seam_rhs_kernel, line_grid(n), dim3(256), 0, st, n, s, m, rowptr, col, val, u, v);
+  return hipGetLastError();
+}
+hipError_t launch_seam_coef(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, const int32_t* col,
+                            const double* val, const double* q, double* coef, uint64_t* bad, hipStream_t st) {
+  if (!seam_ok(n, s, m)) return hipErrorInvalidValue;
+  auto* o = reinterpret_cast<unsigned long long*>(bad);
+  hipLaunchKernelGGL(line_init2_kernel, dim3(1), dim3(64), 0, st, o, ~0ull, 0ull);
+  hipLaunchKernelGGL(seam_coef_kernel, line_grid(n / m), dim3(256), 0, st, n / m, s, m, rowptr, col, val, q, coef, o);
+  return hipGetLastError();
+}
+int64_t seam_setup_host(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, const int32_t* col,
+                        const double* val) {
+  std::vector<double> cp((size_t)m), y((size_t)m);
+  for (int64_t line = 0; line < n / m; ++line) {
+    const int64_t b = line / s;
+    const int64_t i0 = b * s * m + (line - b * s);
+    double alpha, beta, gamma;
+    seam_wrap(i0, s, m, rowptr, col, val, alpha, beta, gamma);
+    double cprev = 0.0, yprev = 0.0;  // plain Thomas on T' q = gamma e(i0) + beta e(i1)
+    for (int64_t k = 0; k < m; ++k) {
+      double dl, dd, du;
+      line_cyclic_row(i0 + k * s, s, m, rowptr, col, val, false, dl, dd, du);
+      const double ip = 1.0 / (dd - dl * cprev);
+      const double rhs = k == 0 ? gamma : k == m - 1 ? beta : 0.0;
+      yprev = (rhs - dl * yprev) * ip;
+      cprev = du * ip;
+      y[(size_t)k] = yprev;
+      cp[(size_t)k] = cprev;
+    }
+    double x = 0.0, q0 = 0.0, q1 = 0.0;
+    for (int64_t k = m - 1; k >= 0; --k) {
+      x = y[(size_t)k] - cp[(size_t)k] * x;
+      if (k == m - 1) q1 = x;
+      if (k == 0) q0 = x;
+    }
+    if (line_bad_pivot(seam_den(alpha, gamma, q0, q1))) return i0;
+  }
+  return -1;
+}
+hipError_t launch_line_seam(const SeamRef& S, double* r, hipStream_t st) {
+  if (!seam_ok(S.n, S.s, S.m)) return hipErrorInvalidValue;
+  const int64_t nlines = S.n / S.m;
+  if (S.s > 1) {
+    hipLaunchKernelGGL(seam_stride_kernel, line_grid(nlines), dim3(256), 0, st, nlines, S.s, S.m, S.p, S.coef, r);
+    return hipGetLastError();
+  }
+#define SEAMX(W)                                                                                                  \
+  hipLaunchKernelGGL(seamx_kernel<W>, line_grid((nlines + 64 / W - 1) / (64 / W) * 64), dim3(256), 0, st, nlines, \
+                     S.m, S.p, S.coef, r)
+  if (S.m <= 4) SEAMX(4);
+  else if (S.m <= 8) SEAMX(8);
+  else if (S.m <= 16) SEAMX(16);
+  else if (S.m <= 32) SEAMX(32);
+  else SEAMX(64);
+#undef SEAMX
   return hipGetLastError();
 }
 

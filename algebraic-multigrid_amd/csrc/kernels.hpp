@@ -60,6 +60,7 @@ constexpr int LINE_SEG = 32;
 struct LineRef {
   int64_t n = 0, s = 1;
   int64_t m = 0;  // set-up only, > 0: chain positions come in grid lines of m; entries across a line end stay out of T
+  int32_t cyc = 0;  // set-up only, with m >= 3: 1 = T' of a cyclic line (SeamRef), 2 = its transpose
   double *dl = nullptr, *ip = nullptr, *cp = nullptr, *v = nullptr, *w = nullptr;
 };
 // stride rule on a device CSR matrix: out[1] = the largest distance d = |j - i| >= 1 whose weight
@@ -74,7 +75,7 @@ int64_t line_stride_host(int64_t n, const int32_t* rowptr, const int32_t* col, c
 hipError_t launch_line_setup(const LineRef& L, const int32_t* rowptr, const int32_t* col, const double* val,
                              uint64_t* bad, hipStream_t st);
 int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32_t* col, const double* val,
-                        int64_t m = 0);
+                        int64_t m = 0, int cyc = 0);
 // u += omega T^-1 r.  y: n doubles of scratch, r is not written.  Three launches (two on a level
 // without separators): line_seg_kernel, line_sep_few_kernel or line_sep_many_kernel, line_update_kernel.
 hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
@@ -89,15 +90,40 @@ constexpr int LINEX_COLS = 64, LINEX_RUNS = 8;
 struct LineXRef {
   int64_t n = 0, nx = 1;
   double *dl = nullptr, *ip = nullptr, *cp = nullptr;
+  int32_t cyc = 0;  // set-up only, with nx >= 3: as LineRef::cyc
 };
 int64_t linex_run(int64_t nx);  // rows of one run: nx, or the whole lines that fit LINEX_COLS
 // extract T_x from CSR(A) and factor it; bad as launch_line_setup.  linex_setup_host: the same
 // elimination on the host, factors discarded; returns the first row with a bad pivot or -1.
 hipError_t launch_linex_setup(const LineXRef& L, const int32_t* rowptr, const int32_t* col, const double* val,
                               uint64_t* bad, hipStream_t st);
-int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int32_t* col, const double* val);
+int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int32_t* col, const double* val,
+                         int cyc = 0);
 // u += omega T_x^-1 r; r is overwritten (the forward values).  Two launches.
 hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double omega, hipStream_t st);
+// K-LineSeam, cyclic lines along a periodic axis (AMG_HIP_SM_LINE_ALT with cyclic_lines): the lines of
+// stride s and length m >= 3 (n a multiple of s m; row i on position (i / s) % m of its line, first row
+// i0, last row i1) carry the wrap entries alpha = a(i0, i1), beta = a(i1, i0).  With gamma = -a(i0, i0),
+//   T' = the open T with the diagonal d(i0) - gamma and d(i1) - alpha beta / gamma (LineRef::cyc = 1),
+//   u = gamma e(i0) + beta e(i1), v = e(i0) + (alpha / gamma) e(i1):   cyclic T = T' + u v^T,
+// so T^-1 r = T'^-1 (r - fac u), fac = (p . r) / den, p = T'^-T v, den = 1 + v . T'^-1 u
+// (Sherman-Morrison).  p: n doubles; coef: den | gamma | beta, n / m doubles each.
+struct SeamRef {
+  int64_t n = 0, s = 1, m = 0;
+  const double* p = nullptr;
+  const double* coef = nullptr;
+};
+// set-up: u and v (n doubles each); then coef from q = T'^-1 u, bad as launch_line_setup (the first
+// row of a line whose den is zero or not finite).  seam_setup_host: the den check on the host with a
+// plain Thomas solve; returns that row or -1.
+hipError_t launch_seam_rhs(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, const int32_t* col,
+                           const double* val, double* u, double* v, hipStream_t st);
+hipError_t launch_seam_coef(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, const int32_t* col,
+                            const double* val, const double* q, double* coef, uint64_t* bad, hipStream_t st);
+int64_t seam_setup_host(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, const int32_t* col,
+                        const double* val);
+// r(i0) -= fac gamma, r(i1) -= fac beta on every line, in place.  One launch.
+hipError_t launch_line_seam(const SeamRef& S, double* r, hipStream_t st);
 // Same operations on a SELL-64 matrix (64-row panels, lane-interleaved):
 // soff[n/64 + 1] panel offsets, scol/sval padded with col = -1.
 // idx16 bit 0: scol holds int16 offsets from the diagonal column (pad -32768);

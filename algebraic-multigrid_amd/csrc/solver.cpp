@@ -4,6 +4,7 @@
 // operations and device-pointer launchers.  No CPU fallback anywhere: every
 // compute entry point needs a HIP device and fails with AMG_HIP_EHIP otherwise.
 // =============================================================================
+#include <cstddef>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -842,12 +843,14 @@ std::string line_bad_pivot(int l, int64_t row, const char* dir = nullptr) {
 struct LineOnDev {  // factors of T (n doubles each) and the scratch vector y
   int64_t n = 0, s = 0;
   int64_t m = 0;  // LineRef::m
+  int cyc = 0;    // LineRef::cyc
   DevMem dl, ip, cp, v, w, y;
   LineRef ref() const {
     LineRef R;
     R.n = n;
     R.s = s;
     R.m = m;
+    R.cyc = cyc;
     R.dl = dl.as<double>();
     R.ip = ip.as<double>();
     R.cp = cp.as<double>();
@@ -872,10 +875,12 @@ struct LineOnDev {  // factors of T (n doubles each) and the scratch vector y
 };
 // stride (0: the automatic rule, on the device) and factors of one level from its device CSR rows
 amg_hip_status line_setup_dev(int l, int64_t n, const int32_t* rowptr, const int32_t* col, const double* val,
-                              int64_t stride, LineOnDev* out, int64_t m = 0, const char* dir = nullptr) {
+                              int64_t stride, LineOnDev* out, int64_t m = 0, const char* dir = nullptr,
+                              int cyc = 0) {
   LineOnDev& D = *out;
   D.n = n;
   D.m = m;
+  D.cyc = cyc;
   for (DevMem* m : {&D.dl, &D.ip, &D.cp, &D.v, &D.w, &D.y}) HIP_TRY(m->alloc(sizeof(double) * (size_t)n));
   DevMem flag;
   HIP_TRY(flag.alloc(sizeof(uint64_t) * 2));
@@ -905,6 +910,8 @@ hipError_t launch_line_sweep(const DevMat& A, const LineOnDev& D, double* u, con
 // The directions of a level: its axes of length >= 2 in the order x, y, z.  x runs as K-LineX, y and
 // z as K-Line with the strides nx and nx ny (m = ny, nz: entries across a plane end stay out of T).
 // A level without a direction (one row) is weighted Jacobi: K-Line with every row its own chain.
+// Cyclic directions (opt.cyclic_lines: a periodic axis of length >= 3): the factors are those of T',
+// and K-LineSeam corrects the residual between the residual and the solve (kernels.hpp: SeamRef).
 const char* const ALT_AXIS[3] = {"x", "y", "z"};
 const char* const ALT_NEEDS_GRID =
     "unknown smoother kind for this constructor: AMG_HIP_SM_LINE_ALT needs the level grids of amg_hip_create_tensor";
@@ -915,7 +922,10 @@ struct AltOnDev {
   int64_t n = 0;
   DevMem xdl, xip, xcp;  // K-LineX factors (direction x)
   LineOnDev yz[2];       // K-Line factors of the directions y, z; yz[0] of the level without directions
-  void set_grid(int64_t rows, const int64_t dims[3]) {
+  bool cyc[3] = {false, false, false};  // direction d is solved cyclically
+  DevMem seam_p[3], seam_coef[3];       // SeamRef::p, ::coef of the cyclic directions
+  // cyclic: the periodic axes whose lines are solved cyclically where the level has 3 points or more
+  void set_grid(int64_t rows, const int64_t dims[3], uint32_t cyclic = 0) {
     n = rows;
     n_dir = 0;
     int64_t st = 1;
@@ -924,6 +934,7 @@ struct AltOnDev {
         axis[n_dir] = a;
         stride[n_dir] = st;
         len[n_dir] = dims[a];
+        cyc[n_dir] = ((cyclic >> a) & 1u) && dims[a] >= 3;
         ++n_dir;
       }
       st *= dims[a];
@@ -938,13 +949,38 @@ struct AltOnDev {
     R.cp = xcp.as<double>();
     return R;
   }
+  int32_t cyclic_mask() const {
+    int32_t mask = 0;
+    for (int d = 0; d < n_dir; ++d)
+      if (cyc[d]) mask |= 1 << axis[d];
+    return mask;
+  }
+  SeamRef seam(int d) const {
+    SeamRef S;
+    S.n = n;
+    S.s = stride[d];
+    S.m = len[d];
+    S.p = seam_p[d].as<double>();
+    S.coef = seam_coef[d].as<double>();
+    return S;
+  }
+  // K-LineSeam of a cyclic direction: p and r in (16 B per row); den, gamma, beta in and the two ends
+  // of r out (40 B per line)
+  double seam_bytes(int d) const {
+    return d < n_dir && cyc[d] ? 16.0 * (double)n + 40.0 * (double)(n / len[d]) : 0.0;
+  }
   // bytes the solve of direction d (or of the level without directions, d = 0) has to move.  K-LineX:
   // r, dl, ip in and y out, then y, cp, u in and u out: 64 B per row
   double solve_bytes(int d) const {
     if (n_dir == 0) return yz[0].solve_bytes();
-    return axis[d] == 0 ? 64.0 * (double)n : yz[axis[d] - 1].solve_bytes();
+    return (axis[d] == 0 ? 64.0 * (double)n : yz[axis[d] - 1].solve_bytes()) + seam_bytes(d);
   }
 };
+std::string seam_bad_den(int l, int64_t row, const char* dir) {
+  return "line smoother: level " + std::to_string(l) + " direction " + dir + " row " + std::to_string(row) +
+         " starts a cyclic line whose Sherman-Morrison denominator is zero or not finite (the cyclic line "
+         "operator is singular or far from diagonally dominant)";
+}
 // host_only: the pivot check of every direction on the host
 amg_hip_status alt_setup_host(int l, const int32_t* rowptr, const int32_t* col, const double* val, AltOnDev* D) {
   if (D->n_dir == 0) {
@@ -952,10 +988,72 @@ amg_hip_status alt_setup_host(int l, const int32_t* rowptr, const int32_t* col, 
     if (bad >= 0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, bad));
   }
   for (int d = 0; d < D->n_dir; ++d) {
-    const int64_t bad = D->axis[d] == 0 ? linex_setup_host(D->n, D->len[d], rowptr, col, val)
-                                        : line_setup_host(D->n, D->stride[d], rowptr, col, val, D->len[d]);
-    if (bad >= 0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, bad, ALT_AXIS[D->axis[d]]));
+    // a cyclic direction: the pivots of T', those of its transpose, then the denominators
+    for (int cyc = D->cyc[d] ? 1 : 0; cyc <= (D->cyc[d] ? 2 : 0); ++cyc) {
+      const int64_t bad = D->axis[d] == 0
+                              ? linex_setup_host(D->n, D->len[d], rowptr, col, val, cyc)
+                              : line_setup_host(D->n, D->stride[d], rowptr, col, val, D->len[d], cyc);
+      if (bad >= 0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, bad, ALT_AXIS[D->axis[d]]));
+    }
+    if (D->cyc[d]) {
+      const int64_t bad = seam_setup_host(D->n, D->stride[d], D->len[d], rowptr, col, val);
+      if (bad >= 0) return fail(AMG_HIP_EINVAL, seam_bad_den(l, bad, ALT_AXIS[D->axis[d]]));
+    }
   }
+  return AMG_HIP_OK;
+}
+// factors of direction x into X (K-LineX set-up)
+amg_hip_status altx_factor_dev(int l, const LineXRef& X, const int32_t* rowptr, const int32_t* col,
+                               const double* val) {
+  DevMem flag;
+  HIP_TRY(flag.alloc(sizeof(uint64_t) * 2));
+  uint64_t h[2];
+  HIP_TRY(launch_linex_setup(X, rowptr, col, val, flag.as<uint64_t>(), nullptr));
+  HIP_TRY(hipMemcpy(h, flag.p, sizeof(h), hipMemcpyDeviceToHost));
+  if (h[0] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, (int64_t)h[0], ALT_AXIS[0]));
+  return AMG_HIP_OK;
+}
+// The cyclic direction d, after its factors of T': p = T'^-T v (kept) from the factors of T'^T on
+// temporaries, q = T'^-1 u (a temporary) with the kept factors, then den, gamma, beta of every line.
+// Both solves are the sub-sweep's own launchers on a zero vector with omega = 1.
+amg_hip_status alt_seam_setup_dev(int l, int d, const int32_t* rowptr, const int32_t* col, const double* val,
+                                  AltOnDev* D) {
+  const int64_t n = D->n, s = D->stride[d], m = D->len[d];
+  const int a = D->axis[d];
+  DevMem u, v, q, flag;
+  for (DevMem* x : {&u, &v, &q, &D->seam_p[d]}) HIP_TRY(x->alloc(sizeof(double) * (size_t)n));
+  HIP_TRY(D->seam_coef[d].alloc(sizeof(double) * 3 * (size_t)(n / m)));
+  HIP_TRY(flag.alloc(sizeof(uint64_t) * 2));
+  HIP_TRY(launch_seam_rhs(n, s, m, rowptr, col, val, u.as<double>(), v.as<double>(), nullptr));
+  HIP_TRY(hipMemsetAsync(q.p, 0, sizeof(double) * (size_t)n, nullptr));
+  HIP_TRY(hipMemsetAsync(D->seam_p[d].p, 0, sizeof(double) * (size_t)n, nullptr));
+  if (a == 0) {
+    DevMem tdl, tip, tcp;
+    for (DevMem* x : {&tdl, &tip, &tcp}) HIP_TRY(x->alloc(sizeof(double) * (size_t)n));
+    LineXRef T = D->xref();
+    T.dl = tdl.as<double>();
+    T.ip = tip.as<double>();
+    T.cp = tcp.as<double>();
+    T.cyc = 2;
+    const amg_hip_status r = altx_factor_dev(l, T, rowptr, col, val);
+    if (r != AMG_HIP_OK) return r;
+    HIP_TRY(launch_linex_solve(T, v.as<double>(), D->seam_p[d].as<double>(), 1.0, nullptr));
+    HIP_TRY(launch_linex_solve(D->xref(), u.as<double>(), q.as<double>(), 1.0, nullptr));
+    HIP_TRY(hipDeviceSynchronize());  // the temporaries go out of scope
+  } else {
+    LineOnDev T;
+    const amg_hip_status r = line_setup_dev(l, n, rowptr, col, val, s, &T, m, ALT_AXIS[a], 2);
+    if (r != AMG_HIP_OK) return r;
+    HIP_TRY(launch_line_solve(T.ref(), v.as<double>(), T.y.as<double>(), D->seam_p[d].as<double>(), 1.0, nullptr));
+    const LineOnDev& Y = D->yz[a - 1];
+    HIP_TRY(launch_line_solve(Y.ref(), u.as<double>(), Y.y.as<double>(), q.as<double>(), 1.0, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  uint64_t h[2];
+  HIP_TRY(launch_seam_coef(n, s, m, rowptr, col, val, q.as<double>(), D->seam_coef[d].as<double>(),
+                           flag.as<uint64_t>(), nullptr));
+  HIP_TRY(hipMemcpy(h, flag.p, sizeof(h), hipMemcpyDeviceToHost));
+  if (h[0] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, seam_bad_den(l, (int64_t)h[0], ALT_AXIS[a]));
   return AMG_HIP_OK;
 }
 amg_hip_status alt_setup_dev(int l, const int32_t* rowptr, const int32_t* col, const double* val, AltOnDev* D) {
@@ -964,17 +1062,20 @@ amg_hip_status alt_setup_dev(int l, const int32_t* rowptr, const int32_t* col, c
   for (int d = 0; d < D->n_dir; ++d) {
     const int a = D->axis[d];
     if (a > 0) {
-      const amg_hip_status r = line_setup_dev(l, n, rowptr, col, val, D->stride[d], &D->yz[a - 1], D->len[d], ALT_AXIS[a]);
+      const amg_hip_status r = line_setup_dev(l, n, rowptr, col, val, D->stride[d], &D->yz[a - 1], D->len[d],
+                                              ALT_AXIS[a], D->cyc[d] ? 1 : 0);
       if (r != AMG_HIP_OK) return r;
-      continue;
+    } else {
+      for (DevMem* m : {&D->xdl, &D->xip, &D->xcp}) HIP_TRY(m->alloc(sizeof(double) * (size_t)n));
+      LineXRef X = D->xref();
+      X.cyc = D->cyc[d] ? 1 : 0;
+      const amg_hip_status r = altx_factor_dev(l, X, rowptr, col, val);
+      if (r != AMG_HIP_OK) return r;
     }
-    for (DevMem* m : {&D->xdl, &D->xip, &D->xcp}) HIP_TRY(m->alloc(sizeof(double) * (size_t)n));
-    DevMem flag;
-    HIP_TRY(flag.alloc(sizeof(uint64_t) * 2));
-    uint64_t h[2];
-    HIP_TRY(launch_linex_setup(D->xref(), rowptr, col, val, flag.as<uint64_t>(), nullptr));
-    HIP_TRY(hipMemcpy(h, flag.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (h[0] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, (int64_t)h[0], ALT_AXIS[0]));
+    if (D->cyc[d]) {
+      const amg_hip_status r = alt_seam_setup_dev(l, d, rowptr, col, val, D);
+      if (r != AMG_HIP_OK) return r;
+    }
   }
   return AMG_HIP_OK;
 }
@@ -983,6 +1084,7 @@ hipError_t launch_alt_subsweep(const DevMat& A, const AltOnDev& D, int d, double
                                double omega, hipStream_t st) {
   hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
   if (e != hipSuccess) return e;
+  if (D.n_dir > 0 && D.cyc[d] && (e = launch_line_seam(D.seam(d), r, st)) != hipSuccess) return e;
   if (D.n_dir > 0 && D.axis[d] == 0) return launch_linex_solve(D.xref(), r, u, omega, st);
   const LineOnDev& Y = D.yz[D.n_dir == 0 ? 0 : D.axis[d] - 1];
   return launch_line_solve(Y.ref(), r, Y.y.as<double>(), u, omega, st);
@@ -2357,7 +2459,7 @@ void compute_bytes(amg_hip_solver* s) {
       sweeps_per_smooth = iters * nd;
       extra = 0.0;
       for (int d = 0; d < nd; ++d)
-        extra += (L.alt.n_dir > 0 && L.alt.axis[d] == 0 ? 64.0 : 80.0) * (double)L.n * iters;
+        extra += ((L.alt.n_dir > 0 && L.alt.axis[d] == 0 ? 64.0 : 80.0) * (double)L.n + L.alt.seam_bytes(d)) * iters;
     }
     // pre-smooth + residual on every level; post-smooth on all but the coarsest
     total += sweep * (sweeps_per_smooth + 1) + extra;
@@ -2397,7 +2499,16 @@ const char* const SINGULAR_ONE_LEVEL =
 // grids, which takes neither
 // periodic (amg_hip_create_tensor_periodic, != 0): a periodic axis has no sides, and `singular` needs
 // the sides of the other axes only
-std::string sides_error(const amg_hip_options& o, int dim, uint32_t periodic = 0) {
+// per_ctor: the constructor is amg_hip_create_tensor_periodic or _periodic_dev (`cyclic_lines`)
+std::string sides_error(const amg_hip_options& o, int dim, uint32_t periodic = 0, bool per_ctor = false) {
+  if (o.cyclic_lines != 0 && o.cyclic_lines != 1)
+    return "`cyclic_lines` must be 0 or 1, got " + std::to_string(o.cyclic_lines);
+  if (o.cyclic_lines && !per_ctor)
+    return "`cyclic_lines` = 1: only amg_hip_create_tensor_periodic and amg_hip_create_tensor_periodic_dev know "
+           "the periodic axes of a grid; this constructor needs 0";
+  if (o.cyclic_lines && o.smoother != AMG_HIP_SM_LINE_ALT)
+    return "`cyclic_lines` = 1 needs the smoother AMG_HIP_SM_LINE_ALT (AMG_HIP_SM_LINE_JACOBI knows no grid "
+           "lines and keeps open chains)";
   if (o.singular != 0 && o.singular != 1)
     return "`singular` must be 0 or 1, got " + std::to_string(o.singular);
   if (!dim) {
@@ -2473,7 +2584,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
                             const amg_hip_options* opts, amg_hip_solver** out,
                             double rs_theta = -1.0, int64_t rs_min_coarse = 0, int tensor_dim = 0,
                             const int64_t* tensor_dims = nullptr, const SemiRule* semi = nullptr,
-                            uint32_t tensor_periodic = 0) {
+                            uint32_t tensor_periodic = 0, bool periodic_ctor = false) {
   if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
   *out = nullptr;
   if (!colptr || !rowind || !val || !b) return fail(AMG_HIP_EINVAL, "null input array");
@@ -2486,7 +2597,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_LINE_ALT)
     return fail(AMG_HIP_EINVAL, "unknown smoother kind");
   {
-    const std::string e = sides_error(s->opt, tensor_dim, tensor_periodic);
+    const std::string e = sides_error(s->opt, tensor_dim, tensor_periodic, periodic_ctor);
     if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
     if (s->opt.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
   }
@@ -2619,7 +2730,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     }
     if (alt) {  // directions of the level's grid; pivot check on the host (host_only) or the device set-up
       if (L.n >= ((int64_t)1 << 31)) return fail(AMG_HIP_EUNSUPPORTED, "line smoother: levels of 2^31 rows or more");
-      L.alt.set_grid(L.n, L.dims);
+      L.alt.set_grid(L.n, L.dims, s->opt.cyclic_lines ? tensor_periodic : 0u);
       if (!dev) {
         const amg_hip_status ar = alt_setup_host(l, A_r.ptr.data(), A_r.idx.data(), A_r.val.data(), &L.alt);
         if (ar != AMG_HIP_OK) return ar;
@@ -3386,7 +3497,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
       if (lr != AMG_HIP_OK) return lr;
     }
     if (alt) {  // directions of the level's grid and their factors (K-LineX and K-Line set-up)
-      L.alt.set_grid(L.n, L.dims);
+      L.alt.set_grid(L.n, L.dims, o.cyclic_lines ? periodic : 0u);
       const amg_hip_status ar = alt_setup_dev(l, cur.rowptr(), cur.col(), cur.v(), &L.alt);
       if (ar != AMG_HIP_OK) return ar;
     }
@@ -4165,6 +4276,11 @@ extern "C" {
 
 const char* amg_hip_last_error(void) { return g_err.c_str(); }
 
+// `cyclic_lines` sits in the alignment padding that the struct had in front of `stream`: no other field
+// moves and the size stays, so callers built against the earlier header pass a valid struct
+static_assert(offsetof(amg_hip_options, cyclic_lines) == 68 && offsetof(amg_hip_options, stream) == 72 &&
+                  offsetof(amg_hip_options, singular) == 108 && sizeof(amg_hip_options) == 112,
+              "amg_hip_options: the layout of the earlier releases must not move");
 void amg_hip_default_options(amg_hip_options* o) {
   if (!o) return;
   std::memset(o, 0, sizeof(*o));
@@ -4361,7 +4477,7 @@ static amg_hip_status periodic_args(const std::string& who, int64_t n, int32_t d
     tensor_coarse_dims(dim, d, mask, c);
     for (int a = 0; a < 3; ++a) d[a] = c[a];
   }
-  const std::string se = sides_error(o, dim, (uint32_t)periodic_axes);
+  const std::string se = sides_error(o, dim, (uint32_t)periodic_axes, true);
   if (!se.empty()) return fail(AMG_HIP_EINVAL, se);
   return AMG_HIP_OK;
 }
@@ -4380,7 +4496,7 @@ amg_hip_status amg_hip_create_tensor_periodic(int64_t n, const int32_t* colptr, 
   const amg_hip_status r = periodic_args(who, n, dim, dims, periodic_axes, n_levels, axis_masks, o, &rule);
   if (r != AMG_HIP_OK) return r;
   return build_solver(n, colptr, rowind, val, b, n_levels, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      &o, out, -1.0, 0, dim, dims, axis_masks ? &rule : nullptr, (uint32_t)periodic_axes);
+                      &o, out, -1.0, 0, dim, dims, axis_masks ? &rule : nullptr, (uint32_t)periodic_axes, true);
 }
 
 amg_hip_status amg_hip_get_level_axes(const amg_hip_solver* s, int32_t level, int32_t* axis_mask) {
@@ -4657,7 +4773,7 @@ static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, in
   const Sparse A = transpose(H);  // CSC(A)
   if (per_on)  // the arguments are checked: what amg_hip_create_tensor_periodic does after its checks
     return build_solver(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, &o, out, -1.0, 0, dim, dims, semi, (uint32_t)periodic_axes);
+                        nullptr, nullptr, nullptr, &o, out, -1.0, 0, dim, dims, semi, (uint32_t)periodic_axes, true);
   if (semi_on)
     return amg_hip_create_tensor_semi(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims, n_levels,
                                       axis_masks, theta, min_coarse, &o, out);
@@ -5088,6 +5204,15 @@ amg_hip_status amg_hip_line_directions(const amg_hip_solver* s, int32_t level, i
   const AltOnDev& D = s->lv[level].alt;
   *n_dir = D.n_dir;
   for (int d = 0; d < 3; ++d) strides[d] = d < D.n_dir ? D.stride[d] : 0;
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_line_cyclic(const amg_hip_solver* s, int32_t level, int32_t* axis_mask) {
+  if (!s || !axis_mask) return fail(AMG_HIP_EINVAL, "null argument");
+  if (s->opt.smoother != AMG_HIP_SM_LINE_ALT)
+    return fail(AMG_HIP_EINVAL, "amg_hip_line_cyclic: the solver's smoother is not AMG_HIP_SM_LINE_ALT");
+  if (level < 0 || level >= (int)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
+  *axis_mask = s->lv[level].alt.cyclic_mask();
   return AMG_HIP_OK;
 }
 
@@ -6101,12 +6226,13 @@ amg_hip_status amg_hip_smooth_line(int64_t n, const int32_t* colptr, const int32
   return AMG_HIP_OK;
 }
 
-amg_hip_status amg_hip_smooth_line_alt(int64_t n, const int32_t* colptr, const int32_t* rowind, const double* val,
-                                       int32_t dim, const int64_t* dims, double omega, int64_t iters,
-                                       int32_t reverse, double* u, const double* f) {
-  static const std::string who = "amg_hip_smooth_line_alt: ";
+static amg_hip_status smooth_line_alt(const std::string& who, int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                      const double* val, int32_t dim, const int64_t* dims, int32_t periodic_axes,
+                                      double omega, int64_t iters, int32_t reverse, double* u, const double* f) {
   if (n <= 0 || !colptr || !rowind || !val || !u || !f) return fail(AMG_HIP_EINVAL, "bad argument");
   std::string v = tensor_dims_error(dim, dims);
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, who + v);
+  v = periodic_axes_error(dim, periodic_axes);
   if (!v.empty()) return fail(AMG_HIP_EINVAL, who + v);
   if (n != dims[0] * dims[1] * dims[2])
     return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
@@ -6120,7 +6246,7 @@ amg_hip_status amg_hip_smooth_line_alt(int64_t n, const int32_t* colptr, const i
   if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
   Sparse Ar = transpose(A);  // T and the residual are taken from the rows of A
   AltOnDev D;
-  D.set_grid(n, dims);
+  D.set_grid(n, dims, (uint32_t)periodic_axes);
   amg_hip_status st = alt_setup_host(0, Ar.ptr.data(), Ar.idx.data(), Ar.val.data(), &D);  // before the device
   if (st != AMG_HIP_OK) return st;
   st = need_device();
@@ -6143,6 +6269,19 @@ amg_hip_status amg_hip_smooth_line_alt(int64_t n, const int32_t* colptr, const i
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(u, du.p, sizeof(double) * n, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_smooth_line_alt(int64_t n, const int32_t* colptr, const int32_t* rowind, const double* val,
+                                       int32_t dim, const int64_t* dims, double omega, int64_t iters,
+                                       int32_t reverse, double* u, const double* f) {
+  return smooth_line_alt("amg_hip_smooth_line_alt: ", n, colptr, rowind, val, dim, dims, 0, omega, iters, reverse, u,
+                         f);
+}
+amg_hip_status amg_hip_smooth_line_alt_per(int64_t n, const int32_t* colptr, const int32_t* rowind, const double* val,
+                                           int32_t dim, const int64_t* dims, int32_t periodic_axes, double omega,
+                                           int64_t iters, int32_t reverse, double* u, const double* f) {
+  return smooth_line_alt("amg_hip_smooth_line_alt_per: ", n, colptr, rowind, val, dim, dims, periodic_axes, omega,
+                         iters, reverse, u, f);
 }
 
 amg_hip_status amg_hip_spgs_sweep(int32_t dir, int64_t n, const int32_t* colptr,

@@ -179,6 +179,16 @@ typedef struct {
                               q_k u_{k-1} solved by a parallel affine scan: same sweep,
                               different rounding order, ~1e-13 relative); smaller
                               problems keep the exact kernel.                          */
+  int32_t cyclic_lines;    /* amg_hip_create_tensor_periodic / _periodic_dev with AMG_HIP_SM_LINE_ALT
+                              only ("cyclic lines" at that constructor).  1: every line direction
+                              along a periodic axis that has 3 points or more on its level is
+                              solved as a cyclic tridiagonal system, wrap entries included.
+                              Default 0: open lines, the earlier releases bit for bit.  Every
+                              other constructor and smoother refuses 1 (AMG_HIP_EINVAL).
+                              The field takes the four bytes of alignment padding that earlier
+                              releases had in front of `stream`: the size of the struct and the
+                              offset of every other field are unchanged, and natural_sides,
+                              singular stay its last two fields.                             */
   void* stream;            /* hipStream_t to run on; NULL (default) = the solver creates
                               and owns a non-blocking stream.  A caller that already
                               orders its device work on a stream (torch's current
@@ -442,9 +452,29 @@ amg_hip_status amg_hip_get_natural_sides(const amg_hip_solver* s, int32_t* mask)
  * Everything else as amg_hip_create_tensor / _tensor_semi with explicit masks: every smoother
  * (AMG_HIP_SM_LINE_ALT included), every layout, host_only, stencil_transfers 0 / 1, natural_sides
  * and singular from `opts`.  periodic_axes = 0 gives the solver of those constructors bit for bit.
- * The smoothers see the level matrices only.  The line smoothers treat a wrap entry as a coupling
- * off the line, like any entry outside the tridiagonal part: THERE IS NO CYCLIC TRIDIAGONAL SOLVE,
- * and a line along a periodic axis is relaxed as an open line.
+ * The smoothers see the level matrices only.  By default the line smoothers treat a wrap entry as
+ * a coupling off the line, like any entry outside the tridiagonal part, and a line along a periodic
+ * axis is relaxed as an open line.
+ * Cyclic lines (opts->cyclic_lines = 1, AMG_HIP_SM_LINE_ALT only): on every level, each direction
+ * along a periodic axis of length m >= 3 solves the cyclic tridiagonal T_a = the open T_a plus the two
+ * wrap entries alpha = A[i0, i1], beta = A[i1, i0] of every grid line (first row i0, last row i1; 0
+ * when absent).  Entries that wrap to a different line (the diagonal neighbours across the seam of a
+ * 9- / 27-point level) stay in A only; at m = 2 the wrap edge is the ordinary edge and nothing
+ * changes.  The solve is Sherman-Morrison on the open kernels: with gamma = -A[i0, i0], T' = the open
+ * T_a with the diagonal d(i0) - gamma and d(i1) - alpha beta / gamma, u = gamma e(i0) + beta e(i1),
+ * v = e(i0) + (alpha / gamma) e(i1), T_a = T' + u v^T.  Set-up keeps p = T'^-T v (8 B per row) and
+ * den = 1 + v . T'^-1 u, gamma, beta (24 B per line); a sub-sweep computes r = f - A u, K-LineSeam
+ * subtracts fac gamma and fac beta from r(i0) and r(i1) with fac = (p . r) / den of the line, and the
+ * open solve with the factors of T' follows: u += omega T_a^-1 r.  A symmetric A keeps T_a symmetric,
+ * so the cycle stays a symmetric preconditioner.  Pick it when the coupling is strong ALONG a periodic
+ * axis: the open line leaves the mode that is constant along the line and oscillates across it
+ * undamped.  A zero or non-finite pivot of T' or T'^T, or such a den, is
+ * AMG_HIP_EINVAL (level, direction and row in the message).  A cyclic T_a that is singular in exact
+ * arithmetic (a line with zero row sums and no coupling off the line) is the caller's error and is
+ * NOT reliably detected: rounding can leave a tiny non-zero den.  AMG_HIP_SM_LINE_JACOBI knows no
+ * grid lines and keeps open chains.  With periodic_axes = 0 the option is accepted and changes no
+ * bit.  AMG_HIP_EINVAL before the device is touched, `cyclic_lines` named: a value outside {0, 1};
+ * 1 on any other constructor; 1 with any other smoother.
  * The coarsest operator of a periodic box has a band as wide as the wrap, so its factorisation runs
  * the any-bandwidth substitution: coarsen until the coarsest level is small (a few hundred rows).
  * AMG_HIP_EINVAL before the device is touched, the argument or field named in the message: what
@@ -917,8 +947,15 @@ amg_hip_status amg_hip_line_stride(const amg_hip_solver* s, int32_t level, int64
 amg_hip_status amg_hip_line_directions(const amg_hip_solver* s, int32_t level, int32_t* n_dir,
                                        int64_t strides[3]);
 
+/* AMG_HIP_SM_LINE_ALT: the axes of `level` whose lines are solved cyclically (opts->cyclic_lines):
+ * bit a = axis a, as in periodic_axes; 0 with cyclic_lines = 0, and for an axis with fewer than 3
+ * points on the level.  Also on host_only solvers.  AMG_HIP_EINVAL for other smoothers.       */
+amg_hip_status amg_hip_line_cyclic(const amg_hip_solver* s, int32_t level, int32_t* axis_mask);
+
 /* Sum over levels of the algorithmic HBM bytes of one V-cycle (SURVEY 8(d)
- * formulae) and the per-sweep bytes of level 0; used by bench.py.             */
+ * formulae) and the per-sweep bytes of level 0; used by bench.py.  A cyclic sub-sweep
+ * (opts->cyclic_lines) adds K-LineSeam's 16 B per row (p, r read) and 40 B per line (den, gamma,
+ * beta read; two entries of r written).                                        */
 amg_hip_status amg_hip_cycle_bytes(const amg_hip_solver* s, double* cycle_bytes,
                                    double* fine_sweep_bytes);
 
@@ -989,6 +1026,14 @@ amg_hip_status amg_hip_smooth_line(int64_t n, const int32_t* colptr, const int32
 amg_hip_status amg_hip_smooth_line_alt(int64_t n, const int32_t* colptr, const int32_t* rowind,
                                        const double* val, int32_t dim, const int64_t* dims, double omega,
                                        int64_t iters, int32_t reverse, double* u, const double* f);
+/* amg_hip_smooth_line_alt with cyclic lines on the axes of `periodic_axes` (bit a = axis a) that
+ * have 3 points or more ("cyclic lines" at amg_hip_create_tensor_periodic).  periodic_axes = 0 gives
+ * amg_hip_smooth_line_alt bit for bit.  AMG_HIP_EINVAL: that function's checks, periodic_axes
+ * negative or with bits at or above dim, a bad pivot of T' or T'^T or a bad denominator.       */
+amg_hip_status amg_hip_smooth_line_alt_per(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                           const double* val, int32_t dim, const int64_t* dims,
+                                           int32_t periodic_axes, double omega, int64_t iters,
+                                           int32_t reverse, double* u, const double* f);
 /* One lexicographic sweep, dir=+1 forward (smoother.hpp:148-157) or -1 backward
  * (:167-174). */
 amg_hip_status amg_hip_spgs_sweep(int32_t dir, int64_t n, const int32_t* colptr,

@@ -16,6 +16,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
        config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
        config_bench.py periodic-setup [<nx> <ny> <nz>]             set-up seconds of tensor_periodic_dev on that operator with set_periodic_device_setup off (host constructor) and on (device), legs alternate; next to them tensor_dev on the open-box operator of the same grid
+       config_bench.py periodic-lines                              PCG to 1e-8 and ms per V-cycle of AMG_HIP_SM_LINE_ALT on diffusion that is strong along a periodic x axis (4096 x 1024, 256^3): open lines (cyclic_lines 0) against cyclic lines (cyclic_lines 1), legs alternate
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -778,6 +779,109 @@ def run_periodic_setup(dims, reps=3):
           f"{off / on:.1f}; open box tensor_dev {box_t:.3f} s, switch on / open box {on / box_t:.2f}", flush=True)
 
 
+def torch_scaled_periodic(dims, eps, periodic):
+    """Constant-coefficient diffusion on the device as CSR: eps[a] times (-1, 2, -1) along axis a, the
+    axes of the mask `periodic` wrap around, every other side is Dirichlet; b random."""
+    import torch
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    dim = len(dims)
+    ext = tuple(dims) + (1,) * (3 - dim)
+    assert all(ext[a] >= 3 for a in range(dim) if (periodic >> a) & 1)
+    n = ext[0] * ext[1] * ext[2]
+    i = torch.arange(n, device=dev)
+    coord = [i % ext[0], (i // ext[0]) % ext[1], i // (ext[0] * ext[1])]
+    stride = [1, ext[0], ext[0] * ext[1]]
+    w = 2 * dim + 1
+    cols = torch.full((n, w), n, dtype=torch.int64, device=dev)  # n: no entry, sorts last
+    vals = torch.zeros((n, w), dtype=torch.float64, device=dev)
+    for a in range(dim):
+        per = bool((periodic >> a) & 1)
+        first, last = coord[a] == 0, coord[a] == ext[a] - 1
+        lo = torch.where(first, i + (ext[a] - 1) * stride[a], i - stride[a])
+        hi = torch.where(last, i - (ext[a] - 1) * stride[a], i + stride[a])
+        lo_ok = ~first if not per else torch.ones_like(first)
+        hi_ok = ~last if not per else torch.ones_like(last)
+        cols[:, 2 * a] = torch.where(lo_ok, lo, cols[:, 2 * a])
+        cols[:, 2 * a + 1] = torch.where(hi_ok, hi, cols[:, 2 * a + 1])
+        vals[:, 2 * a] = torch.where(lo_ok, -float(eps[a]), 0.0)
+        vals[:, 2 * a + 1] = torch.where(hi_ok, -float(eps[a]), 0.0)
+    cols[:, w - 1], vals[:, w - 1] = i, 2.0 * float(sum(eps[:dim]))
+    cols, order = torch.sort(cols, dim=1)
+    vals = torch.gather(vals, 1, order)
+    mask = cols < n
+    crow = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    crow[1:] = torch.cumsum(mask.sum(1), 0).to(torch.int32)
+    col = cols[mask].to(torch.int32).contiguous()
+    val = vals[mask].contiguous()
+    b = torch.rand(n, generator=g, device=dev, dtype=torch.float64) - 0.5
+    return crow, col, val, b
+
+
+def run_periodic_lines(dims, eps, L, reps=3, rtol=1e-8, max_iters=300):
+    """AMG_HIP_SM_LINE_ALT 1+1 omega 0.8 on axis-scaled diffusion, x periodic and strongly coupled, every
+    other side Dirichlet, full coarsening with L levels: open lines (cyclic_lines 0) next to cyclic lines
+    (cyclic_lines 1: K-LineSeam between the residual and the solve of every x sub-sweep).  The two legs
+    alternate in one process, `reps` repeats.  Per run: iterations and wall ms of amg_hip_pcg itself;
+    once per leg: set-up seconds, ms per V-cycle (their difference is the cost of K-LineSeam) and the
+    bytes one cycle has to move."""
+    import ctypes
+    import torch
+
+    def solve(mg):
+        it, rel = ctypes.c_int64(0), ctypes.c_double(0)
+        st = amg.lib().amg_hip_pcg(mg._h, rtol, max_iters, ctypes.byref(it), ctypes.byref(rel))
+        assert st == 0, amg.lib().amg_hip_last_error().decode()
+        return it.value, rel.value
+
+    tag = " x ".join(str(d) for d in dims)
+    arrays = torch_scaled_periodic(dims, eps, 1)
+    torch.cuda.synchronize()
+    legs = {}
+    for cyc in (0, 1):
+        name = f"cyclic_lines {cyc}"
+        t0 = time.perf_counter()
+        mg = amg.Multigrid.tensor_periodic_dev(*arrays, dims, L, 1, cyclic_lines=cyc, **ALT_KW["alt 1+1"])
+        mg.sync()
+        dt = time.perf_counter() - t0
+        mg.vcycle(3)
+        mg.sync()
+        best_cyc = float("inf")
+        for _ in range(reps):
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            mg.vcycle(10)
+            mg.sync()
+            best_cyc = min(best_cyc, (time.perf_counter() - t0) / 10)
+        print(f"periodic-lines {tag} eps {eps}, {name}: setup {dt:.2f} s (setup_on_device {mg.setup_on_device}), "
+              f"{mg.n_levels} levels, cyclic axes per level {[mg.line_cyclic(l) for l in range(mg.n_levels)]}, "
+              f"{best_cyc * 1e3:.3f} ms/V-cycle (best of {reps} x 10), must move {mg.cycle_must_move() / 1e6:.1f} MB",
+              flush=True)
+        mg.zero_vec(0, "u")
+        solve(mg)  # first call: work vectors, captured graph
+        legs[name] = (mg, best_cyc)
+    best = {}
+    for rep_ in range(reps):
+        for name, (mg, _) in legs.items():
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            it, rel = solve(mg)
+            dt = time.perf_counter() - t0
+            best[name] = min(best.get(name, (it, dt)), (it, dt), key=lambda v: v[1])
+            print(f"periodic-lines {tag}, {name} rep {rep_}: {it} iterations, {dt * 1e3:.2f} ms to {rtol:g} "
+                  f"(relres {rel:.2e}, {'reached' if rel <= rtol else 'NOT reached: capped'})", flush=True)
+    c0, c1 = legs["cyclic_lines 0"][1], legs["cyclic_lines 1"][1]
+    print(f"periodic-lines {tag}: best to {rtol:g}: " +
+          ", ".join(f"{k} {v[0]} iterations {v[1] * 1e3:.2f} ms" for k, v in best.items()) +
+          f"; V-cycle {c0 * 1e3:.3f} -> {c1 * 1e3:.3f} ms (K-LineSeam {(c1 - c0) * 1e3:+.3f} ms, {(c1 / c0 - 1) * 100:+.1f} %)",
+          flush=True)
+    for mg, _ in legs.values():
+        mg.close()
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -928,6 +1032,12 @@ elif len(sys.argv) > 1 and sys.argv[1] == "periodic":
     else:
         run_periodic((4096, 1024))
         run_periodic((256, 256, 256))
+elif len(sys.argv) > 1 and sys.argv[1] == "periodic-lines":
+    # profiles/periodic_cyclic_config_bench.txt
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    amg.set_periodic_device_setup(1)  # the hierarchy on the device: the same solver, set up sooner
+    run_periodic_lines((4096, 1024), (1.0, 1e-2), 9)
+    run_periodic_lines((256, 256, 256), (1.0, 1e-2, 1e-2), 7)
 elif len(sys.argv) > 1 and sys.argv[1] == "periodic-setup":
     # profiles/periodic_setup.txt
     os.environ.setdefault("AMG_HIP_TIMING", "1")
