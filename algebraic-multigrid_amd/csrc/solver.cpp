@@ -47,6 +47,11 @@ amg_hip_status fail(amg_hip_status st, const std::string& msg) {
       return fail(_e == hipErrorOutOfMemory ? AMG_HIP_ENOMEM : AMG_HIP_EHIP,   \
                   std::string(#expr) + ": " + hipGetErrorString(_e));          \
   } while (0)
+#define AMG_TRY(expr)                                                          \
+  do {                                                                         \
+    const amg_hip_status _s = (expr);                                          \
+    if (_s != AMG_HIP_OK) return _s;                                           \
+  } while (0)
 
 int host_threads() {
   unsigned h = std::thread::hardware_concurrency();
@@ -98,6 +103,27 @@ struct DevCsr {  // row-major view on the device
   const int32_t* col() const { return idx.as<int32_t>(); }
   const double* v() const { return val.as<double>(); }
 };
+
+// The square CSR matrix of n rows behind three device pointers, copied to the host on the stream
+// `st`; the number of entries is read from the row pointers, and an empty matrix copies only those.
+hipError_t download_csr(int64_t n, const int32_t* ptr, const int32_t* idx, const double* val, hipStream_t st,
+                        Sparse* H) {
+  H->n_outer = H->n_inner = n;
+  H->ptr.resize((size_t)n + 1);
+  hipError_t e = hipMemcpyAsync(H->ptr.data(), ptr, sizeof(int32_t) * H->ptr.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return e;
+  const size_t nnz = (size_t)H->ptr.back();
+  H->idx.resize(nnz);
+  H->val.resize(nnz);
+  if (nnz == 0) return hipSuccess;
+  e = hipMemcpyAsync(H->idx.data(), idx, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(H->val.data(), val, sizeof(double) * nnz, hipMemcpyDeviceToHost, st);
+  return e == hipSuccess ? hipStreamSynchronize(st) : e;
+}
+hipError_t download_csr(const DevCsr& A, Sparse* H) {
+  return download_csr(A.n_rows, A.rowptr(), A.col(), A.v(), nullptr, H);
+}
 
 void csr_shape(const Sparse& M, int* max_block, int* max_row) {
   int mb = 0, mr = 0;
@@ -1303,16 +1329,7 @@ struct Level {
   hipError_t ensure_host_matrix() const {
     if (!A_csc.ptr.empty() || A_dev.n_rows <= 0) return hipSuccess;
     Sparse H;  // symmetric: the CSR arrays are the CSC arrays
-    H.n_outer = H.n_inner = A_dev.n_rows;
-    H.ptr.resize((size_t)A_dev.n_rows + 1);
-    H.idx.resize((size_t)A_dev.nnz);
-    H.val.resize((size_t)A_dev.nnz);
-    hipError_t e = hipMemcpy(H.ptr.data(), A_dev.ptr.p, sizeof(int32_t) * H.ptr.size(), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && A_dev.nnz > 0) {
-      e = hipMemcpy(H.idx.data(), A_dev.idx.p, sizeof(int32_t) * H.idx.size(), hipMemcpyDeviceToHost);
-      if (e == hipSuccess)
-        e = hipMemcpy(H.val.data(), A_dev.val.p, sizeof(double) * H.val.size(), hipMemcpyDeviceToHost);
-    }
+    const hipError_t e = download_csr(A_dev, &H);
     if (e == hipSuccess) A_csc = std::move(H);
     return e;
   }
@@ -2576,70 +2593,191 @@ std::string periodic_level_error(int l, int dim, const int64_t d[3], uint32_t ma
   return "";
 }
 
-amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* rowind,
-                            const double* val, const double* b, int32_t n_levels,
-                            const int32_t* const* Pc, const int32_t* const* Pr,
-                            const double* const* Pv, const int32_t* const* Rc,
-                            const int32_t* const* Rr, const double* const* Rv,
-                            const amg_hip_options* opts, amg_hip_solver** out,
-                            double rs_theta = -1.0, int64_t rs_min_coarse = 0, int tensor_dim = 0,
-                            const int64_t* tensor_dims = nullptr, const SemiRule* semi = nullptr,
-                            uint32_t tensor_periodic = 0, bool periodic_ctor = false) {
+// What a constructor asks of the hierarchy beyond A, b, n_levels and the options.
+struct HierarchySpec {
+  // amg_hip_create_custom: the transfer operators of every level, else the built-in ones
+  const int32_t* const* Pc = nullptr;
+  const int32_t* const* Pr = nullptr;
+  const double* const* Pv = nullptr;
+  const int32_t* const* Rc = nullptr;
+  const int32_t* const* Rr = nullptr;
+  const double* const* Rv = nullptr;
+  // amg_hip_create_rs (theta >= 0): strength-based C/F coarsening, n_levels is an upper bound
+  double rs_theta = -1.0;
+  int64_t rs_min_coarse = 0;
+  // the tensor constructors: the grid of level 0 (dim 0: the flat index is coarsened), the
+  // semi-coarsening rule (null: every axis), the periodic axes
+  int dim = 0;
+  const int64_t* dims = nullptr;
+  const SemiRule* semi = nullptr;
+  uint32_t periodic = 0;
+  bool periodic_ctor = false;  // amg_hip_create_tensor_periodic or _periodic_dev: takes `cyclic_lines`
+};
+
+// ---- the pieces the constructors share; each front end calls them in its own order ----
+// the `out` pointer of a constructor and its options, the caller's or the defaults
+amg_hip_status out_and_options(const amg_hip_options* opts, amg_hip_solver** out, amg_hip_options* o) {
   if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
   *out = nullptr;
+  if (opts) *o = *opts;
+  else amg_hip_default_options(o);
+  return AMG_HIP_OK;
+}
+// full coarsening: every axis of the grid d can be halved
+bool full_level_ok(int dim, const int64_t d[3]) { return d[0] >= 2 && d[1] >= 2 && (dim != 3 || d[2] >= 2); }
+// "" or why level l (grid d) cannot coarsen the axes `mask`: a mask of the semi-coarsening rule, else all axes
+std::string level_mask_error(int l, int dim, const int64_t d[3], int64_t mask, bool semi) {
+  if (semi) return semi_mask_error(l, dim, d, mask);
+  return full_level_ok(dim, d) ? "" : tensor_level_error(l, d);
+}
+// The levels of a hierarchy whose masks are known up front (masks null: full coarsening), walked
+// before any device call: "" or what the first level that cannot coarsen says, in the level loops'
+// words.  `who` goes in front of what only a front end can name: a mask, a periodic axis.
+std::string level_walk_error(const std::string& who, int dim, const int64_t* dims, int32_t n_levels,
+                             const int32_t* masks, uint32_t periodic) {
+  int64_t d[3] = {dims[0], dims[1], dims[2]};
+  for (int l = 0; l + 1 < n_levels; ++l) {
+    const uint32_t mask = masks ? (uint32_t)masks[l] : tensor_full_mask(dim);
+    std::string e = level_mask_error(l, dim, d, masks ? (int64_t)masks[l] : (int64_t)mask, masks != nullptr);
+    if (!e.empty()) return masks ? who + e : e;
+    e = periodic_level_error(l, dim, d, mask, periodic);
+    if (!e.empty()) return who + e;
+    int64_t c[3];
+    tensor_coarse_dims(dim, d, mask, c);
+    for (int a = 0; a < 3; ++a) d[a] = c[a];
+  }
+  return "";
+}
+// The options of a constructor with the grid dimension tensor_dim (0: none) and n_levels levels, in
+// the one order every constructor reports them.
+amg_hip_status smoother_options_error(const amg_hip_options& o, int tensor_dim, int32_t n_levels,
+                                      uint32_t periodic = 0, bool periodic_ctor = false) {
+  if (o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_ALT) return fail(AMG_HIP_EINVAL, "unknown smoother kind");
+  {
+    const std::string e = sides_error(o, tensor_dim, periodic, periodic_ctor);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+    if (o.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
+  }
+  const bool alt = o.smoother == AMG_HIP_SM_LINE_ALT;
+  if (alt && !tensor_dim) return fail(AMG_HIP_EINVAL, ALT_NEEDS_GRID);
+  if (o.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
+  if (o.smoother == AMG_HIP_SM_CHEBYSHEV) {
+    const std::string e = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+    if (o.window) return fail(AMG_HIP_EUNSUPPORTED, "the Chebyshev smoother is not available in a window solver");
+  }
+  if (o.smoother == AMG_HIP_SM_LINE_JACOBI || alt) {
+    const std::string e = line_options_error(o.omega);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
+    if (o.window) return fail(AMG_HIP_EUNSUPPORTED, "the line smoother is not available in a window solver");
+  }
+  if (o.layout < AMG_HIP_LAYOUT_AUTO || o.layout > AMG_HIP_LAYOUT_DICT)
+    return fail(AMG_HIP_EINVAL, "unknown matrix layout");
+  if (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0))
+    return fail(AMG_HIP_EINVAL, "`omega` must be in [0, 2] but got omega=" + std::to_string(o.omega) +
+                                    "\n");  // smoother.hpp:286-293
+  return AMG_HIP_OK;
+}
+// binds the solver to the device and the stream its options name
+amg_hip_status bind_device(amg_hip_solver* s) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(AMG_HIP_EHIP, "no HIP device available (this library has no CPU fallback)");
+  if (s->opt.device >= 0) {
+    if (s->opt.device >= ndev) return fail(AMG_HIP_EINVAL, "device ordinal out of range");
+    s->device = s->opt.device;
+  } else {
+    HIP_TRY(hipGetDevice(&s->device));
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  if (s->opt.stream) {
+    s->stream = (hipStream_t)s->opt.stream;
+    s->own_stream = false;
+  } else {
+    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  }
+  return AMG_HIP_OK;
+}
+// The axes level L (not the last) of a tensor hierarchy coarsens: all of them, the rule's explicit
+// mask, or the automatic rule's from the three axis strengths that strengths(w) yields (the host
+// loop from its CSR copy, the device loop from K-AxisStrength).  *last: the rule ends the hierarchy here.
+template <class Strengths>
+amg_hip_status level_axis_mask(const Level& L, int l, int dim, const SemiRule* semi, Strengths&& strengths,
+                               uint32_t* mask, bool* last) {
+  *last = false;
+  *mask = tensor_full_mask(dim);
+  if (semi && semi->masks) {
+    *mask = (uint32_t)semi->masks[l];
+  } else if (semi) {  // the hierarchy ends at a small level or when no axis is eligible
+    *last = L.n <= semi->min_coarse;
+    if (!*last) {
+      double w[3];
+      AMG_TRY(strengths(w));
+      *mask = tensor_auto_mask(dim, L.dims, w, semi->theta);
+      *last = *mask == 0;
+    }
+    if (*last) *mask = 0;
+  }
+  return AMG_HIP_OK;
+}
+// u, f, r (zeroed) and tmp of a level, and the Chebyshev smoother's update vector
+amg_hip_status alloc_level_vectors(Level& L, bool cheb) {
+  HIP_TRY(L.u.alloc(sizeof(double) * L.n));
+  HIP_TRY(L.f.alloc(sizeof(double) * L.n));
+  HIP_TRY(L.r.alloc(sizeof(double) * L.n));
+  HIP_TRY(L.tmp.alloc(sizeof(double) * L.n));
+  HIP_TRY(hipMemset(L.u.p, 0, sizeof(double) * L.n));
+  HIP_TRY(hipMemset(L.f.p, 0, sizeof(double) * L.n));
+  HIP_TRY(hipMemset(L.r.p, 0, sizeof(double) * L.n));
+  if (cheb) {
+    HIP_TRY(L.cheb_d.alloc(sizeof(double) * L.n));
+    HIP_TRY(hipMemset(L.cheb_d.p, 0, sizeof(double) * L.n));
+  }
+  return AMG_HIP_OK;
+}
+// K-GS-scan on the dictionary matrix A: the chunk length and the ring of new values, or false
+// when the chunks would be too short or the ring would not fit the LDS
+bool gs_scan_params(const DevMat& A, int* C_out, int* ring_out) {
+  int ring = 128;
+  int C = (int)std::min<int64_t>(A.scan_gap, gs_scan_long_chunks_ok(A.dict_ref()) ? gs_scan_max_chunk() : 1024);
+  if (C > 1024 && A.scan_far + C + 1 > 16384) C = 1024;  // the ring of new values must fit the LDS
+  while (ring < A.scan_far + C + 1 && ring <= 16384) ring *= 2;
+  if (A.scan_gap < GS_SCAN_MIN_GAP || ring > 16384) return false;
+  *C_out = C;
+  *ring_out = ring;
+  return true;
+}
+// The closing steps of a set-up on a device: the coarsest factor (multigrid.hpp:240-243; no window
+// solver has one), scratch, the K-Patch flags, the bytes model.  coarse_done() laps the caller's timer.
+template <class Lap>
+amg_hip_status finish_device_solver(amg_hip_solver* s, Lap&& coarse_done) {
+  if (!s->opt.window) {
+    const int want = s->opt.fast_coarse_solve ? 1 : (s->opt.exact_coarse_solve ? -1 : 0);
+    AMG_TRY(upload_coarse(s->lv.back().A_csc, want, &s->coarse, s->opt.singular != 0));
+  }
+  coarse_done();
+  HIP_TRY(s->scratch.alloc(sizeof(double) * 1100));
+  AMG_TRY(set_patch_coarse_flags(s));
+  compute_bytes(s);
+  HIP_TRY(hipDeviceSynchronize());
+  return AMG_HIP_OK;
+}
+
+amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* rowind, const double* val,
+                            const double* b, int32_t n_levels, const amg_hip_options* opts, amg_hip_solver** out,
+                            const HierarchySpec& h = HierarchySpec()) {
+  std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
+  AMG_TRY(out_and_options(opts, out, &s->opt));
   if (!colptr || !rowind || !val || !b) return fail(AMG_HIP_EINVAL, "null input array");
-  const bool rs = rs_theta >= 0.0;  // strength-based C/F coarsening: n_levels is an upper bound
+  const bool rs = h.rs_theta >= 0.0;
   if (n <= 0) return fail(AMG_HIP_EINVAL, "`A` must have at least one degree of freedom");
   if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
-  std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
-  if (opts) s->opt = *opts;
-  else amg_hip_default_options(&s->opt);
-  if (s->opt.smoother < 0 || s->opt.smoother > AMG_HIP_SM_LINE_ALT)
-    return fail(AMG_HIP_EINVAL, "unknown smoother kind");
-  {
-    const std::string e = sides_error(s->opt, tensor_dim, tensor_periodic, periodic_ctor);
-    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
-    if (s->opt.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
-  }
+  AMG_TRY(smoother_options_error(s->opt, h.dim, n_levels, h.periodic, h.periodic_ctor));
   const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
-  if (alt && !tensor_dim) return fail(AMG_HIP_EINVAL, ALT_NEEDS_GRID);
-  if (s->opt.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
   const bool cheb = s->opt.smoother == AMG_HIP_SM_CHEBYSHEV;
-  if (cheb) {
-    const std::string e = cheb_options_error(s->opt.cheb_degree, s->opt.cheb_lower, s->opt.cheb_upper);
-    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
-    if (s->opt.window) return fail(AMG_HIP_EUNSUPPORTED, "the Chebyshev smoother is not available in a window solver");
-  }
   const bool line = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI;
-  if (line || alt) {
-    const std::string e = line_options_error(s->opt.omega);
-    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
-    if (s->opt.window) return fail(AMG_HIP_EUNSUPPORTED, "the line smoother is not available in a window solver");
-  }
-  if (s->opt.layout < AMG_HIP_LAYOUT_AUTO || s->opt.layout > AMG_HIP_LAYOUT_DICT)
-    return fail(AMG_HIP_EINVAL, "unknown matrix layout");
-  if (s->opt.smoother == AMG_HIP_SM_SOR && (s->opt.omega > 2 || s->opt.omega < 0))
-    return fail(AMG_HIP_EINVAL, "`omega` must be in [0, 2] but got omega=" +
-                                    std::to_string(s->opt.omega) + "\n");  // smoother.hpp:286-293
   const bool dev = !s->opt.host_only;
-  if (dev) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-      return fail(AMG_HIP_EHIP, "no HIP device available (this library has no CPU fallback)");
-    if (s->opt.device >= 0) {
-      if (s->opt.device >= ndev) return fail(AMG_HIP_EINVAL, "device ordinal out of range");
-      s->device = s->opt.device;
-    } else {
-      HIP_TRY(hipGetDevice(&s->device));
-    }
-    HIP_TRY(hipSetDevice(s->device));
-    if (s->opt.stream) {
-      s->stream = (hipStream_t)s->opt.stream;
-      s->own_stream = false;
-    } else {
-      HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    }
-  }
+  if (dev) AMG_TRY(bind_device(s.get()));
 
   // AMG_HIP_TIMING=1: wall time of the setup phases on stderr
   struct PhaseTimer {
@@ -2672,9 +2810,9 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     L0.A_csc = from_raw(n, n, colptr, rowind, val);
     std::string v = validate(L0.A_csc, "A");
     if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
-    if (tensor_dim) {
-      L0.tdim = tensor_dim;
-      for (int a = 0; a < 3; ++a) L0.dims[a] = tensor_dims[a];
+    if (h.dim) {
+      L0.tdim = h.dim;
+      for (int a = 0; a < 3; ++a) L0.dims[a] = h.dims[a];
     }
   }
   // ---- hierarchy (multigrid.hpp:211-237) ----
@@ -2684,25 +2822,17 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   timer.lap(T_IN);
   for (int l = 0; l < n_levels; ++l) {
     Level& L = s->lv[l];
-    if (tensor_dim) L.tsides = (uint32_t)s->opt.natural_sides;
-    if (tensor_dim) L.tper = tensor_periodic;
-    if (tensor_dim && l + 1 < n_levels) {  // the axes this level coarsens
-      L.tmask = tensor_full_mask(tensor_dim);
-      if (semi && semi->masks) {
-        L.tmask = (uint32_t)semi->masks[l];
-      } else if (semi) {  // the hierarchy ends at a small level or when no axis is eligible
-        bool last = L.n <= semi->min_coarse;
-        if (!last) {
-          double w[3];
-          tensor_axis_strength(A_r, tensor_dim, L.dims, w);
-          L.tmask = tensor_auto_mask(tensor_dim, L.dims, w, semi->theta);
-          last = L.tmask == 0;
-        }
-        if (last) {
-          L.tmask = 0;
-          n_levels = l + 1;
-          s->lv.resize((size_t)n_levels);
-        }
+    if (h.dim) L.tsides = (uint32_t)s->opt.natural_sides;
+    if (h.dim) L.tper = h.periodic;
+    if (h.dim && l + 1 < n_levels) {  // the axes this level coarsens
+      bool last = false;
+      AMG_TRY(level_axis_mask(L, l, h.dim, h.semi, [&](double w[3]) {
+        tensor_axis_strength(A_r, h.dim, L.dims, w);
+        return AMG_HIP_OK;
+      }, &L.tmask, &last));
+      if (last) {
+        n_levels = l + 1;
+        s->lv.resize((size_t)n_levels);
       }
     }
     L.symmetric = same_arrays(A_r, L.A_csc);
@@ -2730,7 +2860,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     }
     if (alt) {  // directions of the level's grid; pivot check on the host (host_only) or the device set-up
       if (L.n >= ((int64_t)1 << 31)) return fail(AMG_HIP_EUNSUPPORTED, "line smoother: levels of 2^31 rows or more");
-      L.alt.set_grid(L.n, L.dims, s->opt.cyclic_lines ? tensor_periodic : 0u);
+      L.alt.set_grid(L.n, L.dims, s->opt.cyclic_lines ? h.periodic : 0u);
       if (!dev) {
         const amg_hip_status ar = alt_setup_host(l, A_r.ptr.data(), A_r.idx.data(), A_r.val.data(), &L.alt);
         if (ar != AMG_HIP_OK) return ar;
@@ -2777,35 +2907,14 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
           if (L.A_csc.idx[p] == c) dg[c] = L.A_csc.val[p];
       HIP_TRY(upload(L.diag, dg.data(), dg.size()));
     }
-    HIP_TRY(L.u.alloc(sizeof(double) * L.n));
-    HIP_TRY(L.f.alloc(sizeof(double) * L.n));
-    HIP_TRY(L.r.alloc(sizeof(double) * L.n));
-    HIP_TRY(L.tmp.alloc(sizeof(double) * L.n));
-    HIP_TRY(hipMemset(L.u.p, 0, sizeof(double) * L.n));
-    HIP_TRY(hipMemset(L.f.p, 0, sizeof(double) * L.n));
-    HIP_TRY(hipMemset(L.r.p, 0, sizeof(double) * L.n));
-    if (cheb) {
-      HIP_TRY(L.cheb_d.alloc(sizeof(double) * L.n));
-      HIP_TRY(hipMemset(L.cheb_d.p, 0, sizeof(double) * L.n));
-    }
+    AMG_TRY(alloc_level_vectors(L, cheb));
     timer.lap(T_ENC);
     // smoother-specific structures
     // Lexicographic sweeps at size: the line-scan form, unless opt.exact_gs or a small
     // problem (the exact dependency-scheduled kernel is bit-exact and fast enough there)
     if (s->opt.smoother <= AMG_HIP_SM_SOR && !s->opt.exact_gs && s->lv[0].n > GS_SCAN_MIN_ROWS &&
-        L.symmetric) {
-      const DevMat& A = L.A_rows;
-      if (A.dict && A.dict_shift == 0 && A.scan_gap >= GS_SCAN_MIN_GAP) {
-        int ring = 128;
-        int C = (int)std::min<int64_t>(A.scan_gap, gs_scan_long_chunks_ok(A.dict_ref()) ? gs_scan_max_chunk() : 1024);
-        if (C > 1024 && A.scan_far + C + 1 > 16384) C = 1024;  // the ring of new values must fit the LDS
-        while (ring < A.scan_far + C + 1 && ring <= 16384) ring *= 2;
-        if (ring <= 16384) {
-          L.scan_C = C;
-          L.scan_ring = ring;
-        }
-      }
-    }
+        L.symmetric && L.A_rows.dict && L.A_rows.dict_shift == 0)
+      (void)gs_scan_params(L.A_rows, &L.scan_C, &L.scan_ring);
     if (L.scan_C > 0) {
       // no schedule needed
     } else if (s->opt.smoother == AMG_HIP_SM_SPGS) {
@@ -2891,9 +3000,9 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     if (rs) {
       // host_setup.hpp: ruge_stueben_P.  The hierarchy ends where a level is small enough for
       // the direct solve or no longer coarsens.
-      bool last = n_h <= rs_min_coarse;
+      bool last = n_h <= h.rs_min_coarse;
       if (!last) {
-        L.P_csc = ruge_stueben_P(A_r, rs_theta);
+        L.P_csc = ruge_stueben_P(A_r, h.rs_theta);
         n_H = L.P_csc.n_outer;
         last = n_H < 1 || n_H >= n_h;
       }
@@ -2905,40 +3014,36 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       }
       L.R_csc = transpose(L.P_csc);
       L.linear = false;
-    } else if (tensor_dim) {
+    } else if (h.dim) {
       // every coarsened axis m -> floor(m / 2), possible while it has 2 points
-      if (semi) {
-        const std::string e = semi_mask_error(l, tensor_dim, L.dims, L.tmask);
-        if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
-      } else if (L.dims[0] < 2 || L.dims[1] < 2 || (tensor_dim == 3 && L.dims[2] < 2)) {
-        return fail(AMG_HIP_EINVAL, tensor_level_error(l, L.dims));
-      }
+      const std::string e = level_mask_error(l, h.dim, L.dims, L.tmask, h.semi != nullptr);
+      if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
       Level& C = s->lv[l + 1];
-      C.tdim = tensor_dim;
-      tensor_coarse_dims(tensor_dim, L.dims, L.tmask, C.dims);
+      C.tdim = h.dim;
+      tensor_coarse_dims(h.dim, L.dims, L.tmask, C.dims);
       n_H = C.dims[0] * C.dims[1] * C.dims[2];
       L.tensor = true;
       L.n_coarse = n_H;
       // the matrix-free kernels index lanes with 32 bits (kernels.hip: tensor_grid)
       L.tensor_stencil = s->opt.stencil_transfers && L.n < ((int64_t)1 << 31) - 4;
       if (!L.tensor_stencil) {
-        L.P_csc = tensor_P(tensor_dim, L.dims, L.tmask, L.tsides, L.tper);
+        L.P_csc = tensor_P(h.dim, L.dims, L.tmask, L.tsides, L.tper);
         L.R_csc = transpose(L.P_csc);
       }
     } else if (n_H < 1) {
       return fail(AMG_HIP_EINVAL, "level " + std::to_string(l + 1) +
                                       " would have no degrees of freedom; reduce `n_levels`");
-    } else if (Pc) {
+    } else if (h.Pc) {
       // The arrays carry no coarse size.  The reference's rule is the default; operators of another
       // coarsening (full coarsening of a grid, aggregation) say theirs through R_l, whose rows are
       // the coarse dofs: largest row index + 1.
-      if (Rc[l] && Rr[l]) {
+      if (h.Rc[l] && h.Rr[l]) {
         int64_t rows = 0;
-        for (int32_t q = 0, e = Rc[l][n_h]; q < e; ++q) rows = std::max<int64_t>(rows, (int64_t)Rr[l][q] + 1);
+        for (int32_t q = 0, e = h.Rc[l][n_h]; q < e; ++q) rows = std::max<int64_t>(rows, (int64_t)h.Rr[l][q] + 1);
         if (rows >= 1 && rows != n_H) n_H = rows;
       }
-      L.P_csc = from_raw(n_H, n_h, Pc[l], Pr[l], Pv[l]);
-      L.R_csc = from_raw(n_h, n_H, Rc[l], Rr[l], Rv[l]);
+      L.P_csc = from_raw(n_H, n_h, h.Pc[l], h.Pr[l], h.Pv[l]);
+      L.R_csc = from_raw(n_h, n_H, h.Rc[l], h.Rr[l], h.Rv[l]);
       std::string v = validate(L.P_csc, "P");
       if (v.empty()) v = validate(L.R_csc, "R");
       if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
@@ -3012,20 +3117,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
   // rhs / initial state (multigrid.hpp:196-204)
   HIP_TRY(hipMemcpy(s->lv[0].f.p, b, sizeof(double) * n, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(s->lv[0].r.p, b, sizeof(double) * n, hipMemcpyHostToDevice));  // b - A*0
-  // ---- coarsest factor (multigrid.hpp:240-243) ----
-  if (!s->opt.window) {
-    const int want = s->opt.fast_coarse_solve ? 1 : (s->opt.exact_coarse_solve ? -1 : 0);
-    amg_hip_status r = upload_coarse(s->lv[n_levels - 1].A_csc, want, &s->coarse, s->opt.singular != 0);
-    if (r != AMG_HIP_OK) return r;
-  }
-  timer.lap(T_BAND);
-  HIP_TRY(s->scratch.alloc(sizeof(double) * 1100));
-  {
-    amg_hip_status r = set_patch_coarse_flags(s.get());
-    if (r != AMG_HIP_OK) return r;
-  }
-  compute_bytes(s.get());
-  HIP_TRY(hipDeviceSynchronize());
+  AMG_TRY(finish_device_solver(s.get(), [&] { timer.lap(T_BAND); }));
   *out = s.release();
   return AMG_HIP_OK;
 }
@@ -3294,136 +3386,26 @@ struct SetupLap {
 amg_hip_status device_setup_begin(const amg_hip_options& o, std::unique_ptr<amg_hip_solver>* sp) {
   std::unique_ptr<amg_hip_solver> s(new amg_hip_solver);
   s->opt = o;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(AMG_HIP_EHIP, "no HIP device available (this library has no CPU fallback)");
-  if (o.device >= 0) {
-    if (o.device >= ndev) return fail(AMG_HIP_EINVAL, "device ordinal out of range");
-    s->device = o.device;
-  } else {
-    HIP_TRY(hipGetDevice(&s->device));
-  }
-  HIP_TRY(hipSetDevice(s->device));
-  if (o.stream) {
-    s->stream = (hipStream_t)o.stream;
-    s->own_stream = false;
-  } else {
-    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  }
+  AMG_TRY(bind_device(s.get()));
   *sp = std::move(s);
   return AMG_HIP_OK;
 }
-// The level loop of the device set-ups (defined below the model problem's front end).
-amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const int64_t dims0[3], bool tensor,
-                                 bool user, int32_t n_levels, SetupLap& lap,
-                                 const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported,
-                                 const SemiRule* semi = nullptr, uint32_t periodic = 0);
 
-// Front end of the model problem: AMG::Multigrid's constructor (multigrid.hpp:151-244) for A = Grid::laplacian(n), b =
-// Grid::rhs(n) without host matrices: generator, Galerkin chain, dictionary encoder, diagonal
-// and symmetry check all run on the device; only b (n^dim exp() calls, kept on the host so that
-// the bits are libm's, like the reference's) and the coarsest operator (factored on the host)
-// cross PCIe.  *unsupported = true: the options need host structures (exact lexicographic
-// schedules, multicolouring, non-dictionary layouts): the caller takes the host path instead.
-// [unit0, unit1): the grid lines (2-D) / x-y planes (3-D) of a window solver, else unit1 < 0.
-amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const amg_hip_options* opts,
-                                    amg_hip_solver** out, bool* unsupported, int64_t unit0 = 0,
-                                    int64_t unit1 = -1, bool tensor = false) {
-  *unsupported = true;
-  amg_hip_options o;
-  if (opts) o = *opts;
-  else amg_hip_default_options(&o);
-  if (unit1 < 0) { unit0 = 0; unit1 = n; }
-  const int64_t n_last = unit1 - unit0;
-  const int64_t unit_rows = dim == 3 ? n * n : n;
-  const int64_t N = unit_rows * n_last;
-  const bool lex = o.smoother <= AMG_HIP_SM_SOR;
-  if (o.host_only || o.host_galerkin || !o.stencil_transfers || o.fuse_prolong ||
-      (o.layout != AMG_HIP_LAYOUT_AUTO && o.layout != AMG_HIP_LAYOUT_DICT) ||
-      o.smoother == AMG_HIP_SM_MULTICOLOR_GS || (lex && (o.exact_gs || N <= GS_SCAN_MIN_ROWS)) ||
-      n_levels < 2 || N >= ((int64_t)1 << 28))
-    return AMG_HIP_OK;
-  // full coarsening: the lexicographic and the line smoothers build through the host constructor
-  if (tensor && (lex || o.smoother == AMG_HIP_SM_LINE_JACOBI || o.smoother == AMG_HIP_SM_LINE_ALT)) return AMG_HIP_OK;
-  if (o.smoother_iters < 0 || (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0)) ||
-      o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_JACOBI)
-    return AMG_HIP_OK;  // the host path words the argument error
-  const bool cheb = o.smoother == AMG_HIP_SM_CHEBYSHEV;
-  if (cheb) {
-    const std::string e = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
-    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
-    if (o.window) return fail(AMG_HIP_EUNSUPPORTED, "the Chebyshev smoother is not available in a window solver");
-  }
-  const bool line = o.smoother == AMG_HIP_SM_LINE_JACOBI;
-  if (line) {
-    const std::string e = line_options_error(o.omega);
-    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
-    if (o.window) return fail(AMG_HIP_EUNSUPPORTED, "the line smoother is not available in a window solver");
-  }
-  std::unique_ptr<amg_hip_solver> s;
-  {
-    const amg_hip_status r = device_setup_begin(o, &s);
-    if (r != AMG_HIP_OK) return r;
-  }
-  SetupLap lap;
-  // b on the host threads while the device builds the hierarchy
-  std::vector<double> b((size_t)N);
-  std::thread rhs_thread([&] { rhs_threads(dim, n, b.data(), host_threads(), unit0 * unit_rows, unit1 * unit_rows); });
-  struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{rhs_thread};
-  // A_0 (grid.hpp:88-98)
-  DevCsr cur;
-  {
-    DevMem cnt, bsum, total;
-    HIP_TRY(cnt.alloc(sizeof(int32_t) * (N + 1)));
-    HIP_TRY(bsum.alloc(sizeof(int64_t) * ((N + 1023) / 1024 + 1)));
-    HIP_TRY(total.alloc(sizeof(int64_t)));
-    HIP_TRY(launch_laplacian_count(dim, n, n_last, N, cnt.as<int32_t>(), nullptr));
-    HIP_TRY(cur.ptr.alloc(sizeof(int32_t) * (N + 1)));
-    HIP_TRY(launch_exclusive_scan(N, cnt.as<int32_t>(), cur.ptr.as<int32_t>(), bsum.as<int64_t>(),
-                                  total.as<int64_t>(), nullptr));
-    int64_t nnz = 0;
-    HIP_TRY(hipMemcpy(&nnz, total.p, sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (nnz >= ((int64_t)1 << 31) - 1) return AMG_HIP_OK;
-    HIP_TRY(cur.idx.alloc(sizeof(int32_t) * nnz));
-    HIP_TRY(cur.val.alloc(sizeof(double) * nnz));
-    const double h = 2.0 / (double)(n + 1), hh = h * h;
-    const double off = 1.0 / hh, dg = -2.0 / hh;
-    double diag = dg + dg;
-    if (dim == 3) diag = diag + dg;
-    HIP_TRY(launch_laplacian_fill(dim, n, n_last, N, cur.ptr.as<int32_t>(), cur.idx.as<int32_t>(),
-                                  cur.val.as<double>(), off, diag, nullptr));
-    cur.n_rows = cur.n_cols = N;
-    cur.nnz = nnz;
-  }
-  lap("generator");
-  const int64_t dims0[3] = {n, n, dim == 3 ? n : 1};
-  auto put_rhs = [&](Level& L0) -> amg_hip_status {
-    joiner.t.join();
-    HIP_TRY(hipMemcpy(L0.f.p, b.data(), sizeof(double) * N, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(L0.r.p, b.data(), sizeof(double) * N, hipMemcpyHostToDevice));  // b - A*0
-    return AMG_HIP_OK;
-  };
-  const amg_hip_status r = device_level_loop(s.get(), cur, dim, dims0, tensor, false, n_levels, lap, put_rhs,
-                                             unsupported);
-  if (r != AMG_HIP_OK || *unsupported) return r;
-  *out = s.release();
-  return AMG_HIP_OK;
-}
-
-// The level loop of the device set-ups: from CSR(A_0) on the device (`cur`, consumed) and the grid
-// `dims0` of level 0 (tensor) to the finished hierarchy; put_rhs fills f and r of level 0 once the
-// levels exist.  Returns with *unsupported still true when the hierarchy needs the host
-// constructor after all.  user: A_0 is a caller's matrix (amg_hip_create_tensor_dev): every
-// opt.layout is honoured, levels that do not take the dictionary are packed by K-SellPack with
-// upload_mat's rule, and levels that are not bitwise symmetric are transposed by K-Transpose, so
-// that no level crosses to the host.  The model problem's front ends keep the launches they had.
-// semi (amg_hip_create_tensor_semi_dev): the levels coarsen the axes of its masks, or those the
-// automatic rule picks from K-AxisStrength's maxima; n_levels is then an upper bound.
-// periodic (amg_hip_create_tensor_periodic_dev): the periodic axes, L.tper of every level.
-amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const int64_t dims0[3], bool tensor,
-                                 bool user, int32_t n_levels, SetupLap& lap,
-                                 const std::function<amg_hip_status(Level&)>& put_rhs, bool* unsupported,
-                                 const SemiRule* semi, uint32_t periodic) {
+// The level loop of the device set-ups: from CSR(A_0) on the device (`cur`, consumed) to the finished
+// hierarchy; put_rhs(L0) fills f and r of level 0 once the levels exist.  Returns with *unsupported
+// still true when the hierarchy needs the host constructor after all.  user: A_0 is a caller's
+// matrix (amg_hip_create_tensor_dev): every opt.layout is honoured, levels that do not take the
+// dictionary are packed by K-SellPack with upload_mat's rule, and levels that are not bitwise
+// symmetric are transposed by K-Transpose, so that no level crosses to the host.  The model
+// problem's front ends keep the launches they had.  Of h: the grid of level 0 (dim 0: the flat
+// index is coarsened), the semi-coarsening rule, whose automatic form takes K-AxisStrength's maxima
+// and makes n_levels an upper bound, and the periodic axes, L.tper of every level.
+template <class PutRhs>
+amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, const HierarchySpec& h, bool user, int32_t n_levels,
+                                 SetupLap& lap, PutRhs&& put_rhs, bool* unsupported) {
+  const int dim = h.dim;
+  const bool tensor = dim != 0;
+  const SemiRule* semi = h.semi;
   *unsupported = true;
   const amg_hip_options& o = s->opt;
   const bool lex = o.smoother <= AMG_HIP_SM_SOR;
@@ -3438,7 +3420,8 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
   if (semi && !semi->masks) HIP_TRY(axis_w.alloc(sizeof(uint64_t) * 3));
   if (cheb) HIP_TRY(gbound.alloc(sizeof(uint64_t) * 2));
   const bool prune = !o.keep_structural_zeros;
-  int64_t tdims[3] = {dims0[0], dims0[1], dims0[2]};  // full coarsening: the grid of the current level
+  int64_t tdims[3] = {1, 1, 1};  // tensor: the grid of the current level
+  for (int a = 0; tensor && a < 3; ++a) tdims[a] = h.dims[a];
   // user: one form of a level (its rows, or its columns walked as rows) into its device layout
   // without the host: the dictionary when the layout allows it and the matrix qualifies, else
   // K-SellPack.  *done = false: the host upload has to do it.
@@ -3460,26 +3443,18 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
       L.tdim = dim;
       for (int a = 0; a < 3; ++a) L.dims[a] = tdims[a];
       L.tsides = (uint32_t)o.natural_sides;
-      L.tper = periodic;
+      L.tper = h.periodic;
     }
-    if (tensor && l + 1 < n_levels) {  // the axes this level coarsens (build_solver's rule)
-      L.tmask = tensor_full_mask(dim);
-      if (semi && semi->masks) {
-        L.tmask = (uint32_t)semi->masks[l];
-      } else if (semi) {
-        bool last = L.n <= semi->min_coarse;
-        if (!last) {
-          HIP_TRY(launch_axis_strength(L.n, dim, L.dims, cur.rowptr(), cur.col(), cur.v(), axis_w.as<uint64_t>(), nullptr));
-          double w[3];
-          HIP_TRY(hipMemcpy(w, axis_w.p, sizeof(w), hipMemcpyDeviceToHost));
-          L.tmask = tensor_auto_mask(dim, L.dims, w, semi->theta);
-          last = L.tmask == 0;
-        }
-        if (last) {
-          L.tmask = 0;
-          n_levels = l + 1;
-          s->lv.resize((size_t)n_levels);
-        }
+    if (tensor && l + 1 < n_levels) {  // the axes this level coarsens
+      bool last = false;
+      AMG_TRY(level_axis_mask(L, l, dim, semi, [&](double w[3]) -> amg_hip_status {
+        HIP_TRY(launch_axis_strength(L.n, dim, L.dims, cur.rowptr(), cur.col(), cur.v(), axis_w.as<uint64_t>(), nullptr));
+        HIP_TRY(hipMemcpy(w, axis_w.p, sizeof(double) * 3, hipMemcpyDeviceToHost));
+        return AMG_HIP_OK;
+      }, &L.tmask, &last));
+      if (last) {
+        n_levels = l + 1;
+        s->lv.resize((size_t)n_levels);
       }
     }
     if (cheb) {  // Gershgorin bound of D^-1 A on the device CSR (K-Setup: gershgorin_kernel)
@@ -3497,7 +3472,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
       if (lr != AMG_HIP_OK) return lr;
     }
     if (alt) {  // directions of the level's grid and their factors (K-LineX and K-Line set-up)
-      L.alt.set_grid(L.n, L.dims, o.cyclic_lines ? periodic : 0u);
+      L.alt.set_grid(L.n, L.dims, o.cyclic_lines ? h.periodic : 0u);
       const amg_hip_status ar = alt_setup_dev(l, cur.rowptr(), cur.col(), cur.v(), &L.alt);
       if (ar != AMG_HIP_OK) return ar;
     }
@@ -3550,13 +3525,7 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
       if (timing) std::fprintf(stderr, "amg_hip device setup: level %d (%lld rows) not bitwise symmetric -> rows and columns uploaded separately\n",
                                l, (long long)L.n);
       Sparse H;
-      H.n_outer = H.n_inner = L.n;
-      H.ptr.resize((size_t)L.n + 1);
-      H.idx.resize((size_t)cur.nnz);
-      H.val.resize((size_t)cur.nnz);
-      HIP_TRY(hipMemcpy(H.ptr.data(), cur.ptr.p, sizeof(int32_t) * H.ptr.size(), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(H.idx.data(), cur.idx.p, sizeof(int32_t) * H.idx.size(), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(H.val.data(), cur.val.p, sizeof(double) * H.val.size(), hipMemcpyDeviceToHost));
+      HIP_TRY(download_csr(cur, &H));
       HIP_TRY(upload_mat_pruned(H, o.layout, prune, &L.A_rows));       // H = CSR(A)
       L.A_csc = transpose(H);                                           // CSC(A)
       HIP_TRY(upload_mat_pruned(L.A_csc, o.layout, prune, &L.A_cols_own));
@@ -3576,50 +3545,23 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
                                l, (long long)L.n, (int)st[0]);
       L.A_dev.n_rows = 0;
       Sparse H;
-      H.n_outer = H.n_inner = L.n;
-      H.ptr.resize((size_t)L.n + 1);
-      H.idx.resize((size_t)cur.nnz);
-      H.val.resize((size_t)cur.nnz);
-      HIP_TRY(hipMemcpy(H.ptr.data(), cur.ptr.p, sizeof(int32_t) * H.ptr.size(), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(H.idx.data(), cur.idx.p, sizeof(int32_t) * H.idx.size(), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(H.val.data(), cur.val.p, sizeof(double) * H.val.size(), hipMemcpyDeviceToHost));
+      HIP_TRY(download_csr(cur, &H));
       HIP_TRY(upload_mat_pruned(H, user ? o.layout : AMG_HIP_LAYOUT_SELL, prune, &L.A_rows));
       L.A_csc = std::move(H);  // symmetric: the CSR arrays are the CSC arrays
     }
     if (o.smoother != AMG_HIP_SM_JACOBI) L.diag.release();
-    HIP_TRY(L.u.alloc(sizeof(double) * L.n));
-    HIP_TRY(L.f.alloc(sizeof(double) * L.n));
-    HIP_TRY(L.r.alloc(sizeof(double) * L.n));
-    HIP_TRY(L.tmp.alloc(sizeof(double) * L.n));
-    HIP_TRY(hipMemset(L.u.p, 0, sizeof(double) * L.n));
-    HIP_TRY(hipMemset(L.f.p, 0, sizeof(double) * L.n));
-    HIP_TRY(hipMemset(L.r.p, 0, sizeof(double) * L.n));
-    if (cheb) {
-      HIP_TRY(L.cheb_d.alloc(sizeof(double) * L.n));
-      HIP_TRY(hipMemset(L.cheb_d.p, 0, sizeof(double) * L.n));
-    }
-    if (lex && (l + 1 < n_levels || o.keep_residual)) {  // K-GS-scan on every smoothed level, or the host path
-      const DevMat& A = L.A_rows;
-      int ring = 128;
-      int C = (int)std::min<int64_t>(A.scan_gap, gs_scan_long_chunks_ok(A.dict_ref()) ? gs_scan_max_chunk() : 1024);
-      if (C > 1024 && A.scan_far + C + 1 > 16384) C = 1024;  // the ring of new values must fit the LDS
-      while (ring < A.scan_far + C + 1 && ring <= 16384) ring *= 2;
-      if (A.scan_gap < GS_SCAN_MIN_GAP || ring > 16384) return AMG_HIP_OK;
-      L.scan_C = C;
-      L.scan_ring = ring;
-    }
+    AMG_TRY(alloc_level_vectors(L, cheb));
+    // K-GS-scan on every smoothed level, or the host path
+    if (lex && (l + 1 < n_levels || o.keep_residual) && !gs_scan_params(L.A_rows, &L.scan_C, &L.scan_ring))
+      return AMG_HIP_OK;
     if (l + 1 == n_levels) {
       if (L.A_csc.ptr.empty() && L.A_dev.n_rows == 0) L.A_dev = std::move(cur);
       break;
     }
     DevCsr next;
     if (tensor) {  // every coarsened axis m -> floor(m / 2), matrix-free transfers, K-TensorGalerkin
-      if (semi) {
-        const std::string e = semi_mask_error(l, dim, L.dims, L.tmask);
-        if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
-      } else if (L.dims[0] < 2 || L.dims[1] < 2 || (dim == 3 && L.dims[2] < 2)) {
-        return fail(AMG_HIP_EINVAL, tensor_level_error(l, L.dims));
-      }
+      const std::string e = level_mask_error(l, dim, L.dims, L.tmask, semi != nullptr);
+      if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
       tensor_coarse_dims(dim, L.dims, L.tmask, tdims);
       L.tensor = true;
       L.tensor_stencil = true;  // o.stencil_transfers is set and N < 2^28
@@ -3654,27 +3596,88 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, int dim, const 
   }
   lap("hierarchy");
   if (o.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
-  {
-    const amg_hip_status r = put_rhs(s->lv[0]);
-    if (r != AMG_HIP_OK) return r;
-  }
+  AMG_TRY(put_rhs(s->lv[0]));
   lap("rhs");
-  if (!o.window) {
-    const int want = o.fast_coarse_solve ? 1 : (o.exact_coarse_solve ? -1 : 0);
-    HIP_TRY(s->lv[n_levels - 1].ensure_host_matrix());
-    amg_hip_status r = upload_coarse(s->lv[n_levels - 1].A_csc, want, &s->coarse, s->opt.singular != 0);
-    if (r != AMG_HIP_OK) return r;
-  }
-  lap("coarse factor");
-  HIP_TRY(s->scratch.alloc(sizeof(double) * 1100));
-  {
-    amg_hip_status r = set_patch_coarse_flags(s);
-    if (r != AMG_HIP_OK) return r;
-  }
-  compute_bytes(s);
-  HIP_TRY(hipDeviceSynchronize());
+  if (!o.window) HIP_TRY(s->lv[n_levels - 1].ensure_host_matrix());  // for the coarsest factor
+  AMG_TRY(finish_device_solver(s, [&] { lap("coarse factor"); }));
   s->device_setup = true;
   *unsupported = false;
+  return AMG_HIP_OK;
+}
+
+// Front end of the model problem: AMG::Multigrid's constructor (multigrid.hpp:151-244) for A = Grid::laplacian(n), b =
+// Grid::rhs(n) without host matrices: generator, Galerkin chain, dictionary encoder, diagonal
+// and symmetry check all run on the device; only b (n^dim exp() calls, kept on the host so that
+// the bits are libm's, like the reference's) and the coarsest operator (factored on the host)
+// cross PCIe.  *unsupported = true: the options need host structures (exact lexicographic
+// schedules, multicolouring, non-dictionary layouts): the caller takes the host path instead.
+// [unit0, unit1): the grid lines (2-D) / x-y planes (3-D) of a window solver, else unit1 < 0.
+amg_hip_status build_poisson_device(int dim, int64_t n, int32_t n_levels, const amg_hip_options& o,
+                                    amg_hip_solver** out, bool* unsupported, int64_t unit0 = 0,
+                                    int64_t unit1 = -1, bool tensor = false) {
+  *unsupported = true;
+  if (unit1 < 0) { unit0 = 0; unit1 = n; }
+  const int64_t n_last = unit1 - unit0;
+  const int64_t unit_rows = dim == 3 ? n * n : n;
+  const int64_t N = unit_rows * n_last;
+  const bool lex = o.smoother <= AMG_HIP_SM_SOR;
+  if (o.host_only || o.host_galerkin || !o.stencil_transfers || o.fuse_prolong ||
+      (o.layout != AMG_HIP_LAYOUT_AUTO && o.layout != AMG_HIP_LAYOUT_DICT) ||
+      o.smoother == AMG_HIP_SM_MULTICOLOR_GS || (lex && (o.exact_gs || N <= GS_SCAN_MIN_ROWS)) ||
+      n_levels < 2 || N >= ((int64_t)1 << 28))
+    return AMG_HIP_OK;
+  // full coarsening: the lexicographic and the line smoothers build through the host constructor
+  if (tensor && (lex || o.smoother == AMG_HIP_SM_LINE_JACOBI || o.smoother == AMG_HIP_SM_LINE_ALT)) return AMG_HIP_OK;
+  // a bad option (and the alternating line smoother without a grid): the host path words the error
+  if (smoother_options_error(o, tensor ? dim : 0, n_levels) != AMG_HIP_OK) return AMG_HIP_OK;
+  std::unique_ptr<amg_hip_solver> s;
+  AMG_TRY(device_setup_begin(o, &s));
+  SetupLap lap;
+  // b on the host threads while the device builds the hierarchy
+  std::vector<double> b((size_t)N);
+  std::thread rhs_thread([&] { rhs_threads(dim, n, b.data(), host_threads(), unit0 * unit_rows, unit1 * unit_rows); });
+  struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{rhs_thread};
+  // A_0 (grid.hpp:88-98)
+  DevCsr cur;
+  {
+    DevMem cnt, bsum, total;
+    HIP_TRY(cnt.alloc(sizeof(int32_t) * (N + 1)));
+    HIP_TRY(bsum.alloc(sizeof(int64_t) * ((N + 1023) / 1024 + 1)));
+    HIP_TRY(total.alloc(sizeof(int64_t)));
+    HIP_TRY(launch_laplacian_count(dim, n, n_last, N, cnt.as<int32_t>(), nullptr));
+    HIP_TRY(cur.ptr.alloc(sizeof(int32_t) * (N + 1)));
+    HIP_TRY(launch_exclusive_scan(N, cnt.as<int32_t>(), cur.ptr.as<int32_t>(), bsum.as<int64_t>(),
+                                  total.as<int64_t>(), nullptr));
+    int64_t nnz = 0;
+    HIP_TRY(hipMemcpy(&nnz, total.p, sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (nnz >= ((int64_t)1 << 31) - 1) return AMG_HIP_OK;
+    HIP_TRY(cur.idx.alloc(sizeof(int32_t) * nnz));
+    HIP_TRY(cur.val.alloc(sizeof(double) * nnz));
+    const double h = 2.0 / (double)(n + 1), hh = h * h;
+    const double off = 1.0 / hh, dg = -2.0 / hh;
+    double diag = dg + dg;
+    if (dim == 3) diag = diag + dg;
+    HIP_TRY(launch_laplacian_fill(dim, n, n_last, N, cur.ptr.as<int32_t>(), cur.idx.as<int32_t>(),
+                                  cur.val.as<double>(), off, diag, nullptr));
+    cur.n_rows = cur.n_cols = N;
+    cur.nnz = nnz;
+  }
+  lap("generator");
+  const int64_t dims0[3] = {n, n, dim == 3 ? n : 1};
+  auto put_rhs = [&](Level& L0) -> amg_hip_status {
+    joiner.t.join();
+    HIP_TRY(hipMemcpy(L0.f.p, b.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(L0.r.p, b.data(), sizeof(double) * N, hipMemcpyHostToDevice));  // b - A*0
+    return AMG_HIP_OK;
+  };
+  HierarchySpec h;
+  if (tensor) {
+    h.dim = dim;
+    h.dims = dims0;
+  }
+  const amg_hip_status r = device_level_loop(s.get(), cur, h, false, n_levels, lap, put_rhs, unsupported);
+  if (r != AMG_HIP_OK || *unsupported) return r;
+  *out = s.release();
   return AMG_HIP_OK;
 }
 
@@ -4329,8 +4332,7 @@ int amg_hip_device_count(void) {
 amg_hip_status amg_hip_create(int64_t n, const int32_t* colptr, const int32_t* rowind,
                               const double* val, const double* b, int32_t n_levels,
                               const amg_hip_options* opts, amg_hip_solver** out) {
-  return build_solver(n, colptr, rowind, val, b, n_levels, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, opts, out);
+  return build_solver(n, colptr, rowind, val, b, n_levels, opts, out);
 }
 
 amg_hip_status amg_hip_create_custom(int64_t n, const int32_t* colptr, const int32_t* rowind,
@@ -4342,8 +4344,10 @@ amg_hip_status amg_hip_create_custom(int64_t n, const int32_t* colptr, const int
                                      const amg_hip_options* opts, amg_hip_solver** out) {
   if (n_levels > 1 && (!P_colptr || !P_rowind || !P_val || !R_colptr || !R_rowind || !R_val))
     return fail(AMG_HIP_EINVAL, "custom transfer operator arrays are null");
-  return build_solver(n, colptr, rowind, val, b, n_levels, P_colptr, P_rowind, P_val, R_colptr,
-                      R_rowind, R_val, opts, out);
+  HierarchySpec h;
+  h.Pc = P_colptr, h.Pr = P_rowind, h.Pv = P_val;
+  h.Rc = R_colptr, h.Rr = R_rowind, h.Rv = R_val;
+  return build_solver(n, colptr, rowind, val, b, n_levels, opts, out, h);
 }
 
 amg_hip_status amg_hip_create_rs(int64_t n, const int32_t* colptr, const int32_t* rowind,
@@ -4352,8 +4356,10 @@ amg_hip_status amg_hip_create_rs(int64_t n, const int32_t* colptr, const int32_t
                                  amg_hip_solver** out) {
   if (!(theta >= 0.0 && theta <= 1.0)) return fail(AMG_HIP_EINVAL, "`theta` must be in [0, 1]");
   if (min_coarse < 1) return fail(AMG_HIP_EINVAL, "`min_coarse` must be at least 1");
-  return build_solver(n, colptr, rowind, val, b, max_levels, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, opts, out, theta, min_coarse);
+  HierarchySpec h;
+  h.rs_theta = theta;
+  h.rs_min_coarse = min_coarse;
+  return build_solver(n, colptr, rowind, val, b, max_levels, opts, out, h);
 }
 
 static std::string tensor_dims_error(int32_t dim, const int64_t* dims) {
@@ -4365,46 +4371,62 @@ static std::string tensor_dims_error(int32_t dim, const int64_t* dims) {
   return "";
 }
 
+// "" or why a hierarchy of this kind ("full", "semi") cannot be a window solver's
+static std::string window_error(const std::string& who, const char* kind) {
+  return who + "window solvers (opt.window) coarsen the flat index; a " + kind + "-coarsening hierarchy is not sharded";
+}
+// "" or that `n` is not the size of the (valid) grid `dims`; figures: with the numbers
+static std::string grid_size_error(int64_t n, const int64_t* dims, bool figures) {
+  if (n == dims[0] * dims[1] * dims[2]) return "";
+  const std::string grid = std::to_string(dims[0]) + " x " + std::to_string(dims[1]) + " x " +
+                           std::to_string(dims[2]) + " grid";
+  return "`n`" + (figures ? " = " + std::to_string(n) : "") + " is not the " + (figures ? grid : "number of points") +
+         " of `dims`";
+}
+// The grid arguments of a tensor entry point, with its prefix: `dim` and `dims`, `n` against them,
+// and no window solver of this kind of hierarchy.  kind null: a query, which has no options and
+// words `n` without the figures.
+static amg_hip_status tensor_grid_args(const std::string& who, int64_t n, int32_t dim, const int64_t* dims,
+                                       int32_t window, const char* kind) {
+  std::string e = tensor_dims_error(dim, dims);
+  if (e.empty()) e = grid_size_error(n, dims, kind != nullptr);
+  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
+  if (kind && window) return fail(AMG_HIP_EUNSUPPORTED, window_error(who, kind));
+  return AMG_HIP_OK;
+}
+// the spec of a tensor hierarchy on the grid `dims`
+static HierarchySpec tensor_spec(int32_t dim, const int64_t* dims, const SemiRule* semi = nullptr,
+                                 int32_t periodic_axes = 0, bool periodic_ctor = false) {
+  HierarchySpec h;
+  h.dim = dim;
+  h.dims = dims;
+  h.semi = semi;
+  h.periodic = (uint32_t)periodic_axes;
+  h.periodic_ctor = periodic_ctor;
+  return h;
+}
+
 amg_hip_status amg_hip_create_tensor(int64_t n, const int32_t* colptr, const int32_t* rowind,
                                      const double* val, const double* b, int32_t dim,
                                      const int64_t* dims, int32_t n_levels,
                                      const amg_hip_options* opts, amg_hip_solver** out) {
-  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
-  *out = nullptr;
-  const std::string e = tensor_dims_error(dim, dims);
-  if (!e.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor: " + e);
-  if (n != dims[0] * dims[1] * dims[2])
-    return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor: `n` = " + std::to_string(n) + " is not the " +
-                                    std::to_string(dims[0]) + " x " + std::to_string(dims[1]) + " x " +
-                                    std::to_string(dims[2]) + " grid of `dims`");
-  if (opts && opts->window)
-    return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_tensor: window solvers (opt.window) coarsen the "
-                                      "flat index; a full-coarsening hierarchy is not sharded");
-  return build_solver(n, colptr, rowind, val, b, n_levels, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, opts, out, -1.0, 0, dim, dims);
+  amg_hip_options o;
+  AMG_TRY(out_and_options(opts, out, &o));
+  AMG_TRY(tensor_grid_args("amg_hip_create_tensor: ", n, dim, dims, o.window, "full"));
+  return build_solver(n, colptr, rowind, val, b, n_levels, &o, out, tensor_spec(dim, dims));
 }
 
-// The argument checks of the semi-coarsening constructors, before any device call: the explicit
-// masks level by level on the grids they produce, or the automatic rule's parameters.
+// The rule of the semi-coarsening constructors, before any device call: the explicit masks level by
+// level on the grids they produce, or the automatic rule's parameters.
 static amg_hip_status semi_args(const std::string& who, int32_t dim, const int64_t* dims, int32_t n_levels,
-                                const int32_t* axis_masks, double theta, int64_t min_coarse, SemiRule* rule) {
+                                const SemiRule& rule) {
   if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
-  rule->masks = axis_masks;
-  if (axis_masks) {
-    int64_t d[3] = {dims[0], dims[1], dims[2]};
-    for (int l = 0; l + 1 < n_levels; ++l) {
-      const std::string e = semi_mask_error(l, dim, d, axis_masks[l]);
-      if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
-      int64_t c[3];
-      tensor_coarse_dims(dim, d, (uint32_t)axis_masks[l], c);
-      for (int a = 0; a < 3; ++a) d[a] = c[a];
-    }
-    return AMG_HIP_OK;
+  if (rule.masks) {
+    const std::string e = level_walk_error(who, dim, dims, n_levels, rule.masks, 0);
+    return e.empty() ? AMG_HIP_OK : fail(AMG_HIP_EINVAL, e);
   }
-  if (!(theta > 0.0 && theta <= 1.0)) return fail(AMG_HIP_EINVAL, who + "`theta` must be in (0, 1]");
-  if (min_coarse < 1) return fail(AMG_HIP_EINVAL, who + "`min_coarse` must be at least 1");
-  rule->theta = theta;
-  rule->min_coarse = min_coarse;
+  if (!(rule.theta > 0.0 && rule.theta <= 1.0)) return fail(AMG_HIP_EINVAL, who + "`theta` must be in (0, 1]");
+  if (rule.min_coarse < 1) return fail(AMG_HIP_EINVAL, who + "`min_coarse` must be at least 1");
   return AMG_HIP_OK;
 }
 
@@ -4413,22 +4435,12 @@ amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, cons
                                           int32_t n_levels, const int32_t* axis_masks, double theta,
                                           int64_t min_coarse, const amg_hip_options* opts, amg_hip_solver** out) {
   static const std::string who = "amg_hip_create_tensor_semi: ";
-  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
-  *out = nullptr;
-  const std::string e = tensor_dims_error(dim, dims);
-  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
-  if (n != dims[0] * dims[1] * dims[2])
-    return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
-                                    " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
-                                    " grid of `dims`");
-  if (opts && opts->window)
-    return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a semi-coarsening "
-                                            "hierarchy is not sharded");
-  SemiRule rule;
-  const amg_hip_status r = semi_args(who, dim, dims, n_levels, axis_masks, theta, min_coarse, &rule);
-  if (r != AMG_HIP_OK) return r;
-  return build_solver(n, colptr, rowind, val, b, n_levels, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, opts, out, -1.0, 0, dim, dims, &rule);
+  amg_hip_options o;
+  AMG_TRY(out_and_options(opts, out, &o));
+  AMG_TRY(tensor_grid_args(who, n, dim, dims, o.window, "semi"));
+  const SemiRule rule{axis_masks, theta, min_coarse};
+  AMG_TRY(semi_args(who, dim, dims, n_levels, rule));
+  return build_solver(n, colptr, rowind, val, b, n_levels, &o, out, tensor_spec(dim, dims, &rule));
 }
 
 amg_hip_status amg_hip_get_natural_sides(const amg_hip_solver* s, int32_t* mask) {
@@ -4448,35 +4460,13 @@ amg_hip_status amg_hip_get_periodic_axes(const amg_hip_solver* s, int32_t* mask)
 // masks, then the periodic mask on every level's grid, then the sides a periodic axis cannot have.
 static amg_hip_status periodic_args(const std::string& who, int64_t n, int32_t dim, const int64_t* dims,
                                     int32_t periodic_axes, int32_t n_levels, const int32_t* axis_masks,
-                                    const amg_hip_options& o, SemiRule* rule) {
-  const std::string e = tensor_dims_error(dim, dims);
-  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
-  if (n != dims[0] * dims[1] * dims[2])
-    return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
-                                    " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
-                                    " grid of `dims`");
-  if (o.window)
-    return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a " +
-                                          (axis_masks ? "semi" : "full") + "-coarsening hierarchy is not sharded");
+                                    const amg_hip_options& o) {
+  AMG_TRY(tensor_grid_args(who, n, dim, dims, o.window, axis_masks ? "semi" : "full"));
   const std::string pe = periodic_axes_error(dim, periodic_axes);
   if (!pe.empty()) return fail(AMG_HIP_EINVAL, who + pe);
   if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
-  rule->masks = axis_masks;
-  int64_t d[3] = {dims[0], dims[1], dims[2]};
-  for (int l = 0; l + 1 < n_levels; ++l) {
-    const uint32_t mask = axis_masks ? (uint32_t)axis_masks[l] : tensor_full_mask(dim);
-    if (axis_masks) {
-      const std::string me = semi_mask_error(l, dim, d, axis_masks[l]);
-      if (!me.empty()) return fail(AMG_HIP_EINVAL, who + me);
-    } else if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) {
-      return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
-    }
-    const std::string le = periodic_level_error(l, dim, d, mask, (uint32_t)periodic_axes);
-    if (!le.empty()) return fail(AMG_HIP_EINVAL, who + le);
-    int64_t c[3];
-    tensor_coarse_dims(dim, d, mask, c);
-    for (int a = 0; a < 3; ++a) d[a] = c[a];
-  }
+  const std::string le = level_walk_error(who, dim, dims, n_levels, axis_masks, (uint32_t)periodic_axes);
+  if (!le.empty()) return fail(AMG_HIP_EINVAL, le);
   const std::string se = sides_error(o, dim, (uint32_t)periodic_axes, true);
   if (!se.empty()) return fail(AMG_HIP_EINVAL, se);
   return AMG_HIP_OK;
@@ -4486,17 +4476,12 @@ amg_hip_status amg_hip_create_tensor_periodic(int64_t n, const int32_t* colptr, 
                                               const double* val, const double* b, int32_t dim, const int64_t* dims,
                                               int32_t periodic_axes, int32_t n_levels, const int32_t* axis_masks,
                                               const amg_hip_options* opts, amg_hip_solver** out) {
-  static const std::string who = "amg_hip_create_tensor_periodic: ";
-  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
-  *out = nullptr;
   amg_hip_options o;
-  if (opts) o = *opts;
-  else amg_hip_default_options(&o);
-  SemiRule rule;
-  const amg_hip_status r = periodic_args(who, n, dim, dims, periodic_axes, n_levels, axis_masks, o, &rule);
-  if (r != AMG_HIP_OK) return r;
-  return build_solver(n, colptr, rowind, val, b, n_levels, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      &o, out, -1.0, 0, dim, dims, axis_masks ? &rule : nullptr, (uint32_t)periodic_axes, true);
+  AMG_TRY(out_and_options(opts, out, &o));
+  AMG_TRY(periodic_args("amg_hip_create_tensor_periodic: ", n, dim, dims, periodic_axes, n_levels, axis_masks, o));
+  const SemiRule rule{axis_masks};
+  return build_solver(n, colptr, rowind, val, b, n_levels, &o, out,
+                      tensor_spec(dim, dims, axis_masks ? &rule : nullptr, periodic_axes, true));
 }
 
 amg_hip_status amg_hip_get_level_axes(const amg_hip_solver* s, int32_t level, int32_t* axis_mask) {
@@ -4514,10 +4499,7 @@ amg_hip_status amg_hip_tensor_axis_strength(int64_t n, const int32_t* colptr, co
                                             const double* val, int32_t dim, const int64_t* dims, double* w) {
   static const std::string who = "amg_hip_tensor_axis_strength: ";
   if (!colptr || !rowind || !val || !w) return fail(AMG_HIP_EINVAL, "null argument");
-  const std::string e = tensor_dims_error(dim, dims);
-  if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
-  if (n != dims[0] * dims[1] * dims[2])
-    return fail(AMG_HIP_EINVAL, who + "`n` is not the number of points of `dims`");
+  AMG_TRY(tensor_grid_args(who, n, dim, dims, 0, nullptr));
   const Sparse A = from_raw(n, n, colptr, rowind, val);
   const std::string v = validate(A, "A");
   if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
@@ -4546,78 +4528,68 @@ amg_hip_status amg_hip_level_transfer_kind(const amg_hip_solver* s, int32_t leve
 
 amg_hip_status amg_hip_create_poisson(int32_t dim, int64_t n, int32_t n_levels,
                                       const amg_hip_options* opts, amg_hip_solver** out) {
-  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
-  *out = nullptr;
+  amg_hip_options o;
+  AMG_TRY(out_and_options(opts, out, &o));
   if ((dim != 2 && dim != 3) || n < 1) return fail(AMG_HIP_EINVAL, "dim must be 2 or 3 and n >= 1");
-  if (opts) {
-    const std::string e = sides_error(*opts, 0);
+  {
+    const std::string e = sides_error(o, 0);
     if (!e.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson: " + e);
   }
   bool unsupported = true;
-  amg_hip_status r = build_poisson_device(dim, n, n_levels, opts, out, &unsupported);
+  amg_hip_status r = build_poisson_device(dim, n, n_levels, o, out, &unsupported);
   if (r != AMG_HIP_OK || !unsupported) return r;
   // options that need host structures: generate on the host and take the general constructor
   Sparse A = laplacian(dim, n);
   std::vector<double> b((size_t)A.n_outer);
   rhs_threads(dim, n, b.data(), host_threads());
-  return amg_hip_create(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, opts, out);
+  return build_solver(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, &o, out);
 }
 
 amg_hip_status amg_hip_create_poisson_tensor(int32_t dim, int64_t n, int32_t n_levels,
                                              const amg_hip_options* opts, amg_hip_solver** out) {
-  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
-  *out = nullptr;
+  static const std::string who = "amg_hip_create_poisson_tensor: ";
+  amg_hip_options o;
+  AMG_TRY(out_and_options(opts, out, &o));
   if (dim != 2 && dim != 3) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: `dim` must be 2 or 3");
   if (n < 2) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: `n` must be at least 2");
   if (n >= ((int64_t)1 << 31) / n / (dim == 3 ? n : 1))
     return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: the grid has 2^31 points or more");
   if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
-  if (opts) {  // the model problem is Dirichlet on every side
-    const std::string e = sides_error(*opts, 0);
-    if (!e.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_poisson_tensor: " + e);
+  {  // the model problem is Dirichlet on every side
+    const std::string e = sides_error(o, 0);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
   }
-  if (opts && opts->window)
-    return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_tensor: window solvers (opt.window) coarsen the "
-                                      "flat index; a full-coarsening hierarchy is not sharded");
-  int64_t dims[3] = {n, n, dim == 3 ? n : 1};
+  if (o.window) return fail(AMG_HIP_EUNSUPPORTED, window_error(who, "full"));
+  const int64_t dims[3] = {n, n, dim == 3 ? n : 1};
   {  // the levels the rule allows, before the device is touched
-    int64_t d[3] = {dims[0], dims[1], dims[2]};
-    for (int l = 0; l + 1 < n_levels; ++l) {
-      if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
-      int64_t c[3];
-      tensor_coarse_dims(dim, d, c);
-      for (int a = 0; a < 3; ++a) d[a] = c[a];
-    }
+    const std::string e = level_walk_error(who, dim, dims, n_levels, nullptr, 0);
+    if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
   }
-  if (opts && opts->smoother == AMG_HIP_SM_CHEBYSHEV) {
-    const std::string e = cheb_options_error(opts->cheb_degree, opts->cheb_lower, opts->cheb_upper);
+  if (o.smoother == AMG_HIP_SM_CHEBYSHEV) {  // ahead of the other options: the order of this entry point
+    const std::string e = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
     if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
   }
   bool unsupported = true;
-  amg_hip_status r = build_poisson_device(dim, n, n_levels, opts, out, &unsupported, 0, -1, true);
+  amg_hip_status r = build_poisson_device(dim, n, n_levels, o, out, &unsupported, 0, -1, true);
   if (r != AMG_HIP_OK || !unsupported) return r;
   // options that need host structures: generate on the host and take the host constructor
   Sparse A = laplacian(dim, n);
   std::vector<double> b((size_t)A.n_outer);
   rhs_threads(dim, n, b.data(), host_threads());
-  return amg_hip_create_tensor(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims,
-                               n_levels, opts, out);
+  return build_solver(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, &o, out,
+                      tensor_spec(dim, dims));
 }
 
 // Front end of amg_hip_create_tensor_dev: the caller's device arrays are copied on the solver's
 // stream and checked by K-CsrCheck; then the level loop, unless the options need host structures.
 // *unsupported = true on return with AMG_HIP_OK: the (checked) matrix takes the host constructor.
-static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr, const int32_t* col,
-                                               const double* val, const double* b, int dim, const int64_t* dims,
-                                               int32_t n_levels, const amg_hip_options& o, amg_hip_solver** out,
-                                               bool* unsupported, const SemiRule* semi, const std::string& who,
-                                               uint32_t periodic = 0) {
+static amg_hip_status build_tensor_user_device(const std::string& who, int64_t n, const int32_t* rowptr,
+                                               const int32_t* col, const double* val, const double* b,
+                                               int32_t n_levels, const HierarchySpec& h, const amg_hip_options& o,
+                                               amg_hip_solver** out, bool* unsupported) {
   *unsupported = true;
   std::unique_ptr<amg_hip_solver> s;
-  {
-    const amg_hip_status r = device_setup_begin(o, &s);
-    if (r != AMG_HIP_OK) return r;
-  }
+  AMG_TRY(device_setup_begin(o, &s));
   SetupLap lap;
   DevCsr cur;
   DevMem rhs, bad;
@@ -4661,88 +4633,46 @@ static amg_hip_status build_tensor_user_device(int64_t n, const int32_t* rowptr,
     HIP_TRY(hipMemcpy(L0.r.p, rhs.p, sizeof(double) * n, hipMemcpyDeviceToDevice));  // b - A*0
     return AMG_HIP_OK;
   };
-  const amg_hip_status r = device_level_loop(s.get(), cur, dim, dims, true, true, n_levels, lap, put_rhs, unsupported,
-                                             semi, periodic);
+  const amg_hip_status r = device_level_loop(s.get(), cur, h, true, n_levels, lap, put_rhs, unsupported);
   if (r != AMG_HIP_OK || *unsupported) return r;
   *out = s.release();
   return AMG_HIP_OK;
 }
 
-// amg_hip_create_tensor_dev and, with `semi_on`, amg_hip_create_tensor_semi_dev
-// and, with `per_on`, amg_hip_create_tensor_periodic_dev: with amg_hip_set_periodic_device_setup(1)
-// the level loop runs on the device with the mask (K-TensorGalerkin's PER form); with the default 0
-// its hierarchy is built on the host (the checked arrays take the host constructor) and the level
-// loop on the device is never entered
-static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, int64_t n, const int32_t* rowptr_dev,
+// amg_hip_create_tensor_dev, amg_hip_create_tensor_semi_dev (rule: what the caller asks) and
+// amg_hip_create_tensor_periodic_dev (h.periodic_ctor; rule: its explicit masks, or null).  With
+// amg_hip_set_periodic_device_setup(1) the periodic level loop runs on the device with the mask
+// (K-TensorGalerkin's PER form); with the default 0 its hierarchy is built on the host (the checked
+// arrays take the host constructor) and the level loop on the device is never entered.
+static amg_hip_status create_tensor_dev(const std::string& who, int64_t n, const int32_t* rowptr_dev,
                                         const int32_t* col_dev, const double* val_dev, const double* b_dev,
-                                        int32_t dim, const int64_t* dims, int32_t n_levels,
-                                        const int32_t* axis_masks, double theta, int64_t min_coarse,
-                                        const amg_hip_options* opts, amg_hip_solver** out, bool per_on = false,
-                                        int32_t periodic_axes = 0) {
-  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
-  *out = nullptr;
-  if (!rowptr_dev || !col_dev || !val_dev || !b_dev) return fail(AMG_HIP_EINVAL, "null input array");
+                                        int32_t n_levels, HierarchySpec h, const SemiRule* rule,
+                                        const amg_hip_options* opts, amg_hip_solver** out) {
   amg_hip_options o;
-  if (opts) o = *opts;
-  else amg_hip_default_options(&o);
-  SemiRule rule;
-  const SemiRule* semi = semi_on ? &rule : nullptr;
-  if (per_on) {  // grid, masks, levels and sides: the host constructor's one check
-    const amg_hip_status ps = periodic_args(who, n, dim, dims, periodic_axes, n_levels, axis_masks, o, &rule);
-    if (ps != AMG_HIP_OK) return ps;
+  AMG_TRY(out_and_options(opts, out, &o));
+  if (!rowptr_dev || !col_dev || !val_dev || !b_dev) return fail(AMG_HIP_EINVAL, "null input array");
+  h.semi = rule;
+  if (h.periodic_ctor) {  // grid, masks, levels and sides: the host constructor's one check
+    AMG_TRY(periodic_args(who, n, h.dim, h.dims, (int32_t)h.periodic, n_levels, rule ? rule->masks : nullptr, o));
   } else {
-    const std::string e = tensor_dims_error(dim, dims);
-    if (!e.empty()) return fail(AMG_HIP_EINVAL, who + e);
-    if (n != dims[0] * dims[1] * dims[2])
-      return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
-                                      " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
-                                      " grid of `dims`");
-    if (o.window)
-      return fail(AMG_HIP_EUNSUPPORTED, who + "window solvers (opt.window) coarsen the flat index; a " +
-                                            (semi_on ? "semi" : "full") + "-coarsening hierarchy is not sharded");
+    AMG_TRY(tensor_grid_args(who, n, h.dim, h.dims, o.window, rule ? "semi" : "full"));
     if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
-    if (semi_on) {
-      const amg_hip_status sr = semi_args(who, dim, dims, n_levels, axis_masks, theta, min_coarse, &rule);
-      if (sr != AMG_HIP_OK) return sr;
+    if (rule) {
+      AMG_TRY(semi_args(who, h.dim, h.dims, n_levels, *rule));
     } else {  // the levels the rule allows
-      int64_t d[3] = {dims[0], dims[1], dims[2]};
-      for (int l = 0; l + 1 < n_levels; ++l) {
-        if (d[0] < 2 || d[1] < 2 || (dim == 3 && d[2] < 2)) return fail(AMG_HIP_EINVAL, tensor_level_error(l, d));
-        int64_t c[3];
-        tensor_coarse_dims(dim, d, c);
-        for (int a = 0; a < 3; ++a) d[a] = c[a];
-      }
+      const std::string e = level_walk_error(who, h.dim, h.dims, n_levels, nullptr, 0);
+      if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
     }
   }
-  // build_solver's option checks, in its words
-  if (o.smoother < 0 || o.smoother > AMG_HIP_SM_LINE_ALT) return fail(AMG_HIP_EINVAL, "unknown smoother kind");
-  {
-    const std::string se = per_on ? std::string() : sides_error(o, dim);
-    if (!se.empty()) return fail(AMG_HIP_EINVAL, se);
-    if (o.singular && n_levels < 2) return fail(AMG_HIP_EINVAL, SINGULAR_ONE_LEVEL);
-  }
-  if (o.smoother_iters < 0) return fail(AMG_HIP_EINVAL, "`smoother_iters` must be >= 0");
-  if (o.smoother == AMG_HIP_SM_CHEBYSHEV) {
-    const std::string ce = cheb_options_error(o.cheb_degree, o.cheb_lower, o.cheb_upper);
-    if (!ce.empty()) return fail(AMG_HIP_EINVAL, ce);
-  }
-  if (o.smoother == AMG_HIP_SM_LINE_JACOBI || o.smoother == AMG_HIP_SM_LINE_ALT) {
-    const std::string le = line_options_error(o.omega);
-    if (!le.empty()) return fail(AMG_HIP_EINVAL, le);
-  }
-  if (o.layout < AMG_HIP_LAYOUT_AUTO || o.layout > AMG_HIP_LAYOUT_DICT)
-    return fail(AMG_HIP_EINVAL, "unknown matrix layout");
-  if (o.smoother == AMG_HIP_SM_SOR && (o.omega > 2 || o.omega < 0))
-    return fail(AMG_HIP_EINVAL, "`omega` must be in [0, 2] but got omega=" + std::to_string(o.omega) + "\n");
+  AMG_TRY(smoother_options_error(o, h.dim, n_levels, h.periodic, h.periodic_ctor));
   bool unsupported = true;
   amg_hip_options od = o;
-  if (per_on && !g_periodic_device_setup) od.host_galerkin = 1;  // copy + check only
-  amg_hip_status r = build_tensor_user_device(n, rowptr_dev, col_dev, val_dev, b_dev, dim, dims, n_levels, od, out,
-                                              &unsupported, semi, who, per_on ? (uint32_t)periodic_axes : 0u);
+  if (h.periodic_ctor && !g_periodic_device_setup) od.host_galerkin = 1;  // copy + check only
+  amg_hip_status r = build_tensor_user_device(who, n, rowptr_dev, col_dev, val_dev, b_dev, n_levels, h, od, out,
+                                              &unsupported);
   if (r != AMG_HIP_OK || !unsupported) return r;
   // options that need host structures (or a product the kernels refused): the checked arrays are
   // downloaded, transposed on the host and given to the host constructor
-  int64_t nnz = 0;
   Sparse H;  // CSR(A)
   std::vector<double> b((size_t)n);
   {
@@ -4755,37 +4685,20 @@ static amg_hip_status create_tensor_dev(const std::string& who, bool semi_on, in
       HIP_TRY(hipStreamCreateWithFlags(&own.st, hipStreamNonBlocking));
       st = own.st;
     }
-    H.n_outer = H.n_inner = n;
-    H.ptr.resize((size_t)n + 1);
-    HIP_TRY(hipMemcpyAsync(H.ptr.data(), rowptr_dev, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(b.data(), b_dev, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    nnz = H.ptr[(size_t)n];
-    H.idx.resize((size_t)nnz);
-    H.val.resize((size_t)nnz);
-    if (nnz > 0) {
-      HIP_TRY(hipMemcpyAsync(H.idx.data(), col_dev, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(H.val.data(), val_dev, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-    }
+    HIP_TRY(download_csr(n, rowptr_dev, col_dev, val_dev, st, &H));
     if (o.device >= 0) HIP_TRY(hipSetDevice(dev_before));
   }
   const Sparse A = transpose(H);  // CSC(A)
-  if (per_on)  // the arguments are checked: what amg_hip_create_tensor_periodic does after its checks
-    return build_solver(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, &o, out, -1.0, 0, dim, dims, semi, (uint32_t)periodic_axes, true);
-  if (semi_on)
-    return amg_hip_create_tensor_semi(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims, n_levels,
-                                      axis_masks, theta, min_coarse, &o, out);
-  return amg_hip_create_tensor(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), dim, dims, n_levels, &o, out);
+  return build_solver(n, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, &o, out, h);
 }
 
 amg_hip_status amg_hip_create_tensor_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
                                          const double* val_dev, const double* b_dev, int32_t dim,
                                          const int64_t* dims, int32_t n_levels, const amg_hip_options* opts,
                                          amg_hip_solver** out) {
-  return create_tensor_dev("amg_hip_create_tensor_dev: ", false, n, rowptr_dev, col_dev, val_dev, b_dev, dim, dims,
-                           n_levels, nullptr, 0.0, 0, opts, out);
+  return create_tensor_dev("amg_hip_create_tensor_dev: ", n, rowptr_dev, col_dev, val_dev, b_dev, n_levels,
+                           tensor_spec(dim, dims), nullptr, opts, out);
 }
 
 amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
@@ -4793,8 +4706,9 @@ amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_d
                                               const int64_t* dims, int32_t n_levels, const int32_t* axis_masks,
                                               double theta, int64_t min_coarse, const amg_hip_options* opts,
                                               amg_hip_solver** out) {
-  return create_tensor_dev("amg_hip_create_tensor_semi_dev: ", true, n, rowptr_dev, col_dev, val_dev, b_dev, dim,
-                           dims, n_levels, axis_masks, theta, min_coarse, opts, out);
+  const SemiRule rule{axis_masks, theta, min_coarse};
+  return create_tensor_dev("amg_hip_create_tensor_semi_dev: ", n, rowptr_dev, col_dev, val_dev, b_dev, n_levels,
+                           tensor_spec(dim, dims), &rule, opts, out);
 }
 
 amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
@@ -4802,8 +4716,10 @@ amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowp
                                                   const int64_t* dims, int32_t periodic_axes, int32_t n_levels,
                                                   const int32_t* axis_masks, const amg_hip_options* opts,
                                                   amg_hip_solver** out) {
-  return create_tensor_dev("amg_hip_create_tensor_periodic_dev: ", axis_masks != nullptr, n, rowptr_dev, col_dev,
-                           val_dev, b_dev, dim, dims, n_levels, axis_masks, 0.0, 0, opts, out, true, periodic_axes);
+  const SemiRule rule{axis_masks};
+  return create_tensor_dev("amg_hip_create_tensor_periodic_dev: ", n, rowptr_dev, col_dev, val_dev, b_dev, n_levels,
+                           tensor_spec(dim, dims, nullptr, periodic_axes, true), axis_masks ? &rule : nullptr, opts,
+                           out);
 }
 
 amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on) {
@@ -4815,8 +4731,8 @@ amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on) {
 amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t unit_begin, int64_t unit_end,
                                              int32_t n_levels, const amg_hip_options* opts,
                                              amg_hip_solver** out) {
-  if (!out) return fail(AMG_HIP_EINVAL, "out handle pointer is null");
-  *out = nullptr;
+  amg_hip_options o;
+  AMG_TRY(out_and_options(opts, out, &o));
   if ((dim != 2 && dim != 3) || n < 1) return fail(AMG_HIP_EINVAL, "dim must be 2 or 3 and n >= 1");
   if (unit_begin < 0 || unit_end > n || unit_end - unit_begin < 1)
     return fail(AMG_HIP_EINVAL, "window units must satisfy 0 <= unit_begin < unit_end <= n");
@@ -4824,9 +4740,6 @@ amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t uni
   if ((unit_begin * unit_rows) & 1)
     return fail(AMG_HIP_EINVAL, "a window must begin at an even flat index (coarse dof j <-> fine dof 2j+1, multigrid.hpp:127-130)");
   if (n_levels < 2) return fail(AMG_HIP_EINVAL, "a window solver needs at least one distributed level (n_levels >= 2)");
-  amg_hip_options o;
-  if (opts) o = *opts;
-  else amg_hip_default_options(&o);
   if (o.smoother == AMG_HIP_SM_LINE_ALT) return fail(AMG_HIP_EINVAL, ALT_NEEDS_GRID);
   {
     const std::string e = sides_error(o, 0);
@@ -4838,13 +4751,13 @@ amg_hip_status amg_hip_create_poisson_window(int32_t dim, int64_t n, int64_t uni
     return fail(AMG_HIP_EUNSUPPORTED, "amg_hip_create_poisson_window: the line smoother is not sharded");
   o.window = 1;
   bool unsupported = true;
-  amg_hip_status r = build_poisson_device(dim, n, n_levels, &o, out, &unsupported, unit_begin, unit_end);
+  amg_hip_status r = build_poisson_device(dim, n, n_levels, o, out, &unsupported, unit_begin, unit_end);
   if (r != AMG_HIP_OK || !unsupported) return r;
   // options that need host structures (multicolouring, ...): generate the window on the host
   Sparse A = laplacian(dim, n, unit_end - unit_begin);
   std::vector<double> b((size_t)A.n_outer);
   rhs_threads(dim, n, b.data(), host_threads(), unit_begin * unit_rows, unit_end * unit_rows);
-  return amg_hip_create(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, &o, out);
+  return build_solver(A.n_outer, A.ptr.data(), A.idx.data(), A.val.data(), b.data(), n_levels, &o, out);
 }
 
 void amg_hip_destroy(amg_hip_solver* s) {
@@ -6234,10 +6147,8 @@ static amg_hip_status smooth_line_alt(const std::string& who, int64_t n, const i
   if (!v.empty()) return fail(AMG_HIP_EINVAL, who + v);
   v = periodic_axes_error(dim, periodic_axes);
   if (!v.empty()) return fail(AMG_HIP_EINVAL, who + v);
-  if (n != dims[0] * dims[1] * dims[2])
-    return fail(AMG_HIP_EINVAL, who + "`n` = " + std::to_string(n) + " is not the " + std::to_string(dims[0]) +
-                                    " x " + std::to_string(dims[1]) + " x " + std::to_string(dims[2]) +
-                                    " grid of `dims`");
+  v = grid_size_error(n, dims, true);
+  if (!v.empty()) return fail(AMG_HIP_EINVAL, who + v);
   if (iters < 0) return fail(AMG_HIP_EINVAL, "`iters` must be >= 0");
   v = line_options_error(omega);
   if (!v.empty()) return fail(AMG_HIP_EINVAL, v);
