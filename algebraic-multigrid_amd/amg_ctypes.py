@@ -6,6 +6,7 @@ HIP kernels.  If the shared library is missing the import fails loudly; if no
 HIP device is present every compute call raises AmgHipError (status EHIP) --
 there is no CPU fallback.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -162,6 +163,9 @@ _SIGS = {
     "amg_hip_f32_get_vec": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
     "amg_hip_f32_set_vec": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
     "amg_hip_f32_level_op": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "amg_hip_f32_line_subsweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "amg_hip_f32_line_factors": (C.c_int, [C.c_void_p, C.c_int32] + [C.POINTER(C.c_float)] * 3),
+    "amg_hip_set_f32_lines": (None, [C.c_int32]),
     "amg_hip_n_levels": (C.c_int32, [C.c_void_p]),
     "amg_hip_get_n_dofs": (C.c_int64, [C.c_void_p, C.c_int32]),
     "amg_hip_get_level_nnz": (C.c_int64, [C.c_void_p, C.c_int32]),
@@ -416,6 +420,22 @@ def set_periodic_device_setup(on):
     """Multigrid.tensor_periodic_dev builds on the device (1) or through the host constructor (0, the
     default); process-wide, read when a solver is created, the same solver bit for bit."""
     lib().amg_hip_set_periodic_device_setup(int(bool(on)))
+
+
+def set_f32_lines(on):
+    """The single-precision entry points accept line-smoother solvers (1) or refuse them (0, the
+    default); process-wide, read whenever a float entry point runs its checks."""
+    lib().amg_hip_set_f32_lines(int(bool(on)))
+
+
+@contextlib.contextmanager
+def f32_lines():
+    """with amg.f32_lines(): ... -- set_f32_lines(1) inside the block, 0 again after it."""
+    set_f32_lines(1)
+    try:
+        yield
+    finally:
+        set_f32_lines(0)
 
 
 def set_band_chain(on):
@@ -1219,6 +1239,18 @@ class Multigrid:
     def f32_level_op(self, level, op):
         """One step of the float cycle on the float vectors; op as level_op's."""
         _chk(lib().amg_hip_f32_level_op(self._h, int(level), int(op)))
+
+    def f32_line_subsweep(self, level, d=0, reverse=False):
+        """One float sub-sweep of direction index d of a line smoother on the float vectors of `level`
+        (amg_hip_f32_line_subsweep; needs set_f32_lines(1))."""
+        _chk(lib().amg_hip_f32_line_subsweep(self._h, int(level), int(d), int(bool(reverse))))
+
+    def f32_line_factors(self, level):
+        """(dl, ip, cp): the float K-LineX factors of `level` (amg_hip_f32_line_factors)."""
+        out = [np.empty(self.get_n_dofs(level), np.float32) for _ in range(3)]
+        _chk(lib().amg_hip_f32_line_factors(self._h, int(level),
+                                            *(a.ctypes.data_as(C.POINTER(C.c_float)) for a in out)))
+        return tuple(out)
 
     # ---- block (multi-right-hand-side) cycles: amg_hip_block_* ---------------------------
     def _block_check(self, name, t, k=None):

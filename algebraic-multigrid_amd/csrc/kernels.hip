@@ -6671,27 +6671,30 @@ __global__ __launch_bounds__(256) void line_factor_chain_kernel(LineRef L, int64
   if (b >= 0) atomicMin(bad, (unsigned long long)b);
 }
 
+// The solve kernels are templates on the scalar type T: double for the cycle, float for the
+// single-precision cycle (solver.cpp: "fp32 cycle"), which walks float copies of the same factors in
+// the same order.
 // y_g = B_g^-1 r_g: the forward values stay in registers (the loops are fully unrolled), so the
 // dependent chain is arithmetic only and the loads of r and of the factors run ahead of it
+template <typename T>
 __global__ __launch_bounds__(256) void line_seg_kernel(int64_t n, int64_t s, int64_t nch, int64_t nseg,
-                                                       const double* __restrict__ r,
-                                                       const double* __restrict__ dl,
-                                                       const double* __restrict__ ip,
-                                                       const double* __restrict__ cp, double* __restrict__ y) {
+                                                       const T* __restrict__ r, const T* __restrict__ dl,
+                                                       const T* __restrict__ ip, const T* __restrict__ cp,
+                                                       T* __restrict__ y) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nch * nseg) return;
   const int64_t g = t / nch, c = t - g * nch;
   const int64_t i0 = (g * LINE_SEG) * s + c;
-  double yv[LINE_INT];
-  double prev = 0.0;
+  T yv[LINE_INT];
+  T prev = T(0);
 #pragma unroll
   for (int k = 0; k < LINE_INT; ++k) {
     const int64_t i = i0 + (int64_t)k * s;
     if (i < n) prev = k > 0 ? (r[i] - dl[i] * prev) * ip[i] : r[i] * ip[i];
-    else prev = 0.0;
+    else prev = T(0);
     yv[k] = prev;
   }
-  double nxt = 0.0;
+  T nxt = T(0);
 #pragma unroll
   for (int k = LINE_INT - 1; k >= 0; --k) {
     const int64_t i = i0 + (int64_t)k * s;
@@ -6703,9 +6706,9 @@ __global__ __launch_bounds__(256) void line_seg_kernel(int64_t n, int64_t s, int
 }
 
 // right-hand side of the reduced system at separator row i
-__device__ inline double line_sep_rhs(int64_t i, int64_t n, int64_t s, const double* r, const double* dl,
-                                      const double* w, const double* y) {
-  double b = r[i] - dl[i] * y[i - s];
+template <typename T>
+__device__ inline T line_sep_rhs(int64_t i, int64_t n, int64_t s, const T* r, const T* dl, const T* w, const T* y) {
+  T b = r[i] - dl[i] * y[i - s];
   if (i + s < n) b = b - w[i] * y[i + s];
   return b;
 }
@@ -6713,25 +6716,26 @@ __device__ inline double line_sep_rhs(int64_t i, int64_t n, int64_t s, const dou
 // LINE_BATCH separators is loaded before its dependent steps run, so a chain of m / 32 separators
 // costs m / (32 LINE_BATCH) memory latencies per direction.
 constexpr int LINE_BATCH = 8;
-__global__ __launch_bounds__(64) void line_sep_many_kernel(int64_t n, int64_t s, int64_t nch, const double* r,
-                                                           const double* dl, const double* ip, const double* cp,
-                                                           const double* v, const double* w, double* y) {
+template <typename T>
+__global__ __launch_bounds__(64) void line_sep_many_kernel(int64_t n, int64_t s, int64_t nch, const T* r,
+                                                           const T* dl, const T* ip, const T* cp, const T* v,
+                                                           const T* w, T* y) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nch) return;
   const int64_t step = (int64_t)LINE_SEG * s;
   const int64_t first = (int64_t)LINE_INT * s + c;
   if (first >= n) return;
   const int64_t nsep = (n - 1 - first) / step + 1;
-  double t = 0.0;
+  T t = T(0);
   for (int64_t g0 = 0; g0 < nsep; g0 += LINE_BATCH) {
-    double b[LINE_BATCH], lo[LINE_BATCH], pv[LINE_BATCH];
+    T b[LINE_BATCH], lo[LINE_BATCH], pv[LINE_BATCH];
 #pragma unroll
     for (int j = 0; j < LINE_BATCH; ++j) {
       const int64_t i = first + (g0 + j) * step;
       const bool on = g0 + j < nsep;
-      b[j] = on ? line_sep_rhs(i, n, s, r, dl, w, y) : 0.0;
-      lo[j] = on ? v[i] : 0.0;
-      pv[j] = on ? ip[i] : 0.0;
+      b[j] = on ? line_sep_rhs(i, n, s, r, dl, w, y) : T(0);
+      lo[j] = on ? v[i] : T(0);
+      pv[j] = on ? ip[i] : T(0);
     }
 #pragma unroll
     for (int j = 0; j < LINE_BATCH; ++j) {
@@ -6741,15 +6745,15 @@ __global__ __launch_bounds__(64) void line_sep_many_kernel(int64_t n, int64_t s,
       }
     }
   }
-  double x = 0.0;
+  T x = T(0);
   for (int64_t g1 = nsep; g1 > 0; g1 -= LINE_BATCH) {  // separators g1-1, g1-2, ...
-    double tt[LINE_BATCH], cc[LINE_BATCH];
+    T tt[LINE_BATCH], cc[LINE_BATCH];
 #pragma unroll
     for (int j = 0; j < LINE_BATCH; ++j) {
       const int64_t g = g1 - 1 - j;
       const int64_t i = first + g * step;
-      tt[j] = g >= 0 ? y[i] : 0.0;
-      cc[j] = g >= 0 ? cp[i] : 0.0;
+      tt[j] = g >= 0 ? y[i] : T(0);
+      cc[j] = g >= 0 ? cp[i] : T(0);
     }
 #pragma unroll
     for (int j = 0; j < LINE_BATCH; ++j) {
@@ -6765,18 +6769,19 @@ __global__ __launch_bounds__(64) void line_sep_many_kernel(int64_t n, int64_t s,
 // lane 0 walks it there (an LDS round trip per step instead of a memory one) and carries the
 // recurrence into the next chunk, all lanes write the chunk back.  Same arithmetic in the same
 // order as line_sep_many_kernel.
-constexpr int LINE_FEW_CHUNK = 1024;  // 3 arrays of doubles: 24 KB of LDS
-__global__ __launch_bounds__(256) void line_sep_few_kernel(int64_t n, int64_t s, const double* r, const double* dl,
-                                                           const double* ip, const double* cp, const double* v,
-                                                           const double* w, double* y) {
-  __shared__ double b[LINE_FEW_CHUNK], lo[LINE_FEW_CHUNK], pv[LINE_FEW_CHUNK];
-  __shared__ double carry;
+constexpr int LINE_FEW_CHUNK = 1024;  // 3 arrays: 24 KB of LDS in double, 12 KB in float
+template <typename T>
+__global__ __launch_bounds__(256) void line_sep_few_kernel(int64_t n, int64_t s, const T* r, const T* dl,
+                                                           const T* ip, const T* cp, const T* v, const T* w,
+                                                           T* y) {
+  __shared__ T b[LINE_FEW_CHUNK], lo[LINE_FEW_CHUNK], pv[LINE_FEW_CHUNK];
+  __shared__ T carry;
   const int64_t c = blockIdx.x;
   const int64_t step = (int64_t)LINE_SEG * s;
   const int64_t first = (int64_t)LINE_INT * s + c;
   if (first >= n) return;  // the whole workgroup
   const int64_t nsep = (n - 1 - first) / step + 1;
-  if (threadIdx.x == 0) carry = 0.0;
+  if (threadIdx.x == 0) carry = T(0);
   __syncthreads();
   for (int64_t g0 = 0; g0 < nsep; g0 += LINE_FEW_CHUNK) {
     const int m = (int)(nsep - g0 < LINE_FEW_CHUNK ? nsep - g0 : LINE_FEW_CHUNK);
@@ -6788,7 +6793,7 @@ __global__ __launch_bounds__(256) void line_sep_few_kernel(int64_t n, int64_t s,
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      double t = carry;
+      T t = carry;
       for (int g = 0; g < m; ++g) {
         t = (b[g] - lo[g] * t) * pv[g];
         b[g] = t;
@@ -6799,7 +6804,7 @@ __global__ __launch_bounds__(256) void line_sep_few_kernel(int64_t n, int64_t s,
     for (int g = threadIdx.x; g < m; g += blockDim.x) y[first + (g0 + g) * step] = b[g];
     __syncthreads();
   }
-  if (threadIdx.x == 0) carry = 0.0;
+  if (threadIdx.x == 0) carry = T(0);
   __syncthreads();
   for (int64_t g1 = nsep; g1 > 0; g1 -= LINE_FEW_CHUNK) {  // separators [g1 - m, g1)
     const int m = (int)(g1 < LINE_FEW_CHUNK ? g1 : LINE_FEW_CHUNK);
@@ -6811,7 +6816,7 @@ __global__ __launch_bounds__(256) void line_sep_few_kernel(int64_t n, int64_t s,
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      double x = carry;
+      T x = carry;
       for (int g = m - 1; g >= 0; --g) {
         x = b[g] - lo[g] * x;
         b[g] = x;
@@ -6825,15 +6830,15 @@ __global__ __launch_bounds__(256) void line_sep_few_kernel(int64_t n, int64_t s,
 }
 
 // x_i = y_i - v_i x_(separator before) - w_i x_(separator after); u_i += omega x_i
-__global__ __launch_bounds__(256) void line_update_kernel(int64_t n, uint32_t s, const double* __restrict__ y,
-                                                          const double* __restrict__ v,
-                                                          const double* __restrict__ w, double omega,
-                                                          double* __restrict__ u) {
+template <typename T>
+__global__ __launch_bounds__(256) void line_update_kernel(int64_t n, uint32_t s, const T* __restrict__ y,
+                                                          const T* __restrict__ v, const T* __restrict__ w,
+                                                          T omega, T* __restrict__ u) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t p = (uint32_t)i / s;
   const uint32_t k = p % LINE_SEG;
-  double x = y[i];
+  T x = y[i];
   if (k != LINE_INT) {
     const int64_t before = i - ((int64_t)k + 1) * s;
     const int64_t after = i + (int64_t)(LINE_INT - k) * s;
@@ -6970,25 +6975,33 @@ int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32
 }
 
 bool line_few_chains(int64_t s) { return s < 64; }
-hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
-                             hipStream_t st) {
-  if (L.n <= 0 || L.s < 1 || L.s > L.n || L.n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-  const int64_t n = L.n, s = L.s;
+namespace {
+template <typename T>
+hipError_t line_solve_t(int64_t n, int64_t s, const T* dl, const T* ip, const T* cp, const T* v, const T* w,
+                        const T* r, T* y, T* u, T omega, hipStream_t st) {
+  if (n <= 0 || s < 1 || s > n || n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
   const int64_t nch = line_chains(n, s), nseg = line_segments(n, s);
-  hipLaunchKernelGGL(line_seg_kernel, line_grid(nch * nseg), dim3(256), 0, st, n, s, nch, nseg, r, L.dl, L.ip, L.cp,
-                     y);
+  hipLaunchKernelGGL(line_seg_kernel<T>, line_grid(nch * nseg), dim3(256), 0, st, n, s, nch, nseg, r, dl, ip, cp, y);
   if ((int64_t)LINE_INT * s < n) {  // the level has separators
     if (line_few_chains(s)) {
-      hipLaunchKernelGGL(line_sep_few_kernel, dim3((unsigned)nch), dim3(256), 0, st, n, s, r, L.dl, L.ip, L.cp, L.v,
-                         L.w, y);
+      hipLaunchKernelGGL(line_sep_few_kernel<T>, dim3((unsigned)nch), dim3(256), 0, st, n, s, r, dl, ip, cp, v, w, y);
     } else {
-      hipLaunchKernelGGL(line_sep_many_kernel, line_grid(nch, 64), dim3(64), 0, st, n, s, nch, r, L.dl, L.ip, L.cp,
-                         L.v, L.w, y);
+      hipLaunchKernelGGL(line_sep_many_kernel<T>, line_grid(nch, 64), dim3(64), 0, st, n, s, nch, r, dl, ip, cp, v,
+                         w, y);
     }
   }
-  hipLaunchKernelGGL(line_update_kernel, line_grid(n), dim3(256), 0, st, n, (uint32_t)s, y,
-                     L.v, L.w, omega, u);
+  hipLaunchKernelGGL(line_update_kernel<T>, line_grid(n), dim3(256), 0, st, n, (uint32_t)s, (const T*)y, v, w, omega,
+                     u);
   return hipGetLastError();
+}
+}  // namespace
+hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
+                             hipStream_t st) {
+  return line_solve_t<double>(L.n, L.s, L.dl, L.ip, L.cp, L.v, L.w, r, y, u, omega, st);
+}
+hipError_t launch_line_solve_f32(const LineRefF32& L, const float* r, float* y, float* u, float omega,
+                                 hipStream_t st) {
+  return line_solve_t<float>(L.n, L.s, L.dl, L.ip, L.cp, L.v, L.w, r, y, u, omega, st);
 }
 
 // ---- K-LineX: the x lines of a tensor grid (AMG_HIP_SM_LINE_ALT; kernels.hpp: LineXRef) --------
@@ -7032,15 +7045,15 @@ __global__ __launch_bounds__(256) void linex_extract_kernel(LineXRef L, const in
 
 // a, b, c: the three arrays a chunk reads (FACTOR: dl, dd, du; FWD: r, dl, ip; BWD: y, cp, u);
 // o1, o2: what it writes (FACTOR: ip, cp; FWD: y = a; BWD: u = c)
-template <int MODE>
-__global__ __launch_bounds__(64) void linex_kernel(int64_t n, int64_t len, int64_t nruns, const double* a,
-                                                   const double* b, const double* c, double* o1, double* o2,
-                                                   double omega, unsigned long long* bad) {
-  __shared__ double sa[LINEX_RUNS * LINEX_PITCH], sb[LINEX_RUNS * LINEX_PITCH], sc[LINEX_RUNS * LINEX_PITCH];
+// T = float (FWD and BWD only): the same chunks of LINEX_COLS columns, 256 B per row and array
+template <int MODE, typename T>
+__global__ __launch_bounds__(64) void linex_kernel(int64_t n, int64_t len, int64_t nruns, const T* a, const T* b,
+                                                   const T* c, T* o1, T* o2, T omega, unsigned long long* bad) {
+  __shared__ T sa[LINEX_RUNS * LINEX_PITCH], sb[LINEX_RUNS * LINEX_PITCH], sc[LINEX_RUNS * LINEX_PITCH];
   const int lane = threadIdx.x;
   const int64_t run0 = (int64_t)blockIdx.x * LINEX_RUNS;
   const int64_t nchunks = (len + LINEX_COLS - 1) / LINEX_COLS;
-  double ra[LINEX_RUNS], rb[LINEX_RUNS], rc[LINEX_RUNS];
+  T ra[LINEX_RUNS], rb[LINEX_RUNS], rc[LINEX_RUNS];
   // row of run q at this lane's column of chunk ch, or -1 outside the run / the level
   auto row_of = [&](int q, int64_t ch) -> int64_t {
     const int64_t run = run0 + q, k = ch * LINEX_COLS + lane;
@@ -7052,12 +7065,12 @@ __global__ __launch_bounds__(64) void linex_kernel(int64_t n, int64_t len, int64
 #pragma unroll
     for (int q = 0; q < LINEX_RUNS; ++q) {
       const int64_t i = row_of(q, ch);
-      ra[q] = i >= 0 ? a[i] : 0.0;
-      rb[q] = i >= 0 ? b[i] : 0.0;
-      rc[q] = i >= 0 ? c[i] : 0.0;
+      ra[q] = i >= 0 ? a[i] : T(0);
+      rb[q] = i >= 0 ? b[i] : T(0);
+      rc[q] = i >= 0 ? c[i] : T(0);
     }
   };
-  double carry = 0.0;  // lanes < LINEX_RUNS: cp (FACTOR), y (FWD) or x (BWD) of the row walked last
+  T carry = T(0);  // lanes < LINEX_RUNS: cp (FACTOR), y (FWD) or x (BWD) of the row walked last
   fetch(MODE == LX_BWD ? nchunks - 1 : 0);
   for (int64_t t = 0; t < nchunks; ++t) {
     const int64_t ch = MODE == LX_BWD ? nchunks - 1 - t : t;
@@ -7070,18 +7083,18 @@ __global__ __launch_bounds__(64) void linex_kernel(int64_t n, int64_t len, int64
     __syncthreads();
     if (t + 1 < nchunks) fetch(MODE == LX_BWD ? ch - 1 : ch + 1);
     if (lane < LINEX_RUNS) {
-      double* pa = sa + lane * LINEX_PITCH;
-      double* pb = sb + lane * LINEX_PITCH;
-      double* pc = sc + lane * LINEX_PITCH;
+      T* pa = sa + lane * LINEX_PITCH;
+      T* pb = sb + lane * LINEX_PITCH;
+      T* pc = sc + lane * LINEX_PITCH;
       if (MODE == LX_FACTOR) {
         const int64_t i0 = (run0 + lane) * len + ch * LINEX_COLS;
         int64_t first_bad = -1;
 #pragma unroll 8
         for (int k = 0; k < LINEX_COLS; ++k) {
-          const double piv = pb[k] - pa[k] * carry;
+          const T piv = pb[k] - pa[k] * carry;
           const bool in = run0 + lane < nruns && ch * LINEX_COLS + k < len && i0 + k < n;
           if (in && first_bad < 0 && line_bad_pivot(piv)) first_bad = i0 + k;
-          const double ip = in ? 1.0 / piv : 0.0;
+          const T ip = in ? T(1) / piv : T(0);
           carry = pc[k] * ip;
           pb[k] = ip;
           pc[k] = carry;
@@ -7118,9 +7131,8 @@ __global__ __launch_bounds__(64) void linex_kernel(int64_t n, int64_t len, int64
     __syncthreads();
   }
 }
-inline bool linex_ok(const LineXRef& L) {
-  return L.n > 0 && L.nx >= 1 && L.n < ((int64_t)1 << 31) && L.n % L.nx == 0;
-}
+inline bool linex_ok(int64_t n, int64_t nx) { return n > 0 && nx >= 1 && n < ((int64_t)1 << 31) && n % nx == 0; }
+inline bool linex_ok(const LineXRef& L) { return linex_ok(L.n, L.nx); }
 }  // namespace
 
 int64_t linex_run(int64_t nx) { return nx >= LINEX_COLS ? nx : nx * (LINEX_COLS / nx); }
@@ -7132,7 +7144,7 @@ hipError_t launch_linex_setup(const LineXRef& L, const int32_t* rowptr, const in
   const int64_t len = linex_run(L.nx), nruns = (L.n + len - 1) / len;
   hipLaunchKernelGGL(line_init2_kernel, dim3(1), dim3(64), 0, st, o, ~0ull, 0ull);
   hipLaunchKernelGGL(linex_extract_kernel, line_grid(L.n), dim3(256), 0, st, L, rowptr, col, val);
-  hipLaunchKernelGGL(linex_kernel<LX_FACTOR>, line_grid(nruns, LINEX_RUNS), dim3(64), 0, st, L.n, len, nruns, L.dl,
+  hipLaunchKernelGGL((linex_kernel<LX_FACTOR, double>), line_grid(nruns, LINEX_RUNS), dim3(64), 0, st, L.n, len, nruns, L.dl,
                      L.ip, L.cp, L.ip, L.cp, 0.0, o);
   return hipGetLastError();
 }
@@ -7148,15 +7160,26 @@ int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int
   }
   return -1;
 }
-hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double omega, hipStream_t st) {
-  if (!linex_ok(L)) return hipErrorInvalidValue;
-  const int64_t len = linex_run(L.nx), nruns = (L.n + len - 1) / len;
+namespace {
+template <typename T>
+hipError_t linex_solve_t(int64_t n, int64_t nx, const T* dl, const T* ip, const T* cp, T* r, T* u, T omega,
+                         hipStream_t st) {
+  if (!linex_ok(n, nx)) return hipErrorInvalidValue;
+  const int64_t len = linex_run(nx), nruns = (n + len - 1) / len;
   const dim3 grid = line_grid(nruns, LINEX_RUNS);
-  hipLaunchKernelGGL(linex_kernel<LX_FWD>, grid, dim3(64), 0, st, L.n, len, nruns, r, L.dl, L.ip, r, nullptr, 0.0,
-                     nullptr);
-  hipLaunchKernelGGL(linex_kernel<LX_BWD>, grid, dim3(64), 0, st, L.n, len, nruns, r, L.cp, u, u, nullptr, omega,
-                     nullptr);
+  hipLaunchKernelGGL((linex_kernel<LX_FWD, T>), grid, dim3(64), 0, st, n, len, nruns, (const T*)r, dl, ip, r,
+                     (T*)nullptr, T(0), (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((linex_kernel<LX_BWD, T>), grid, dim3(64), 0, st, n, len, nruns, (const T*)r, cp, (const T*)u, u,
+                     (T*)nullptr, omega, (unsigned long long*)nullptr);
   return hipGetLastError();
+}
+}  // namespace
+hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double omega, hipStream_t st) {
+  return linex_solve_t<double>(L.n, L.nx, L.dl, L.ip, L.cp, r, u, omega, st);
+}
+hipError_t launch_linex_solve_f32(int64_t n, int64_t nx, const float* dl, const float* ip, const float* cp, float* r,
+                                  float* u, float omega, hipStream_t st) {
+  return linex_solve_t<float>(n, nx, dl, ip, cp, r, u, omega, st);
 }
 
 // ---- K-LineSeam: the rank-one correction of a cyclic line solve (kernels.hpp: SeamRef) ----------
@@ -7172,9 +7195,9 @@ hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double om
 // The order of every sum is fixed by (m, s) alone.
 namespace {
 constexpr int SEAM_BATCH = 4;
-template <int W>
-__global__ __launch_bounds__(256) void seamx_kernel(int64_t nlines, int64_t m, const double* __restrict__ p,
-                                                    const double* __restrict__ coef, double* r) {
+template <int W, typename T>
+__global__ __launch_bounds__(256) void seamx_kernel(int64_t nlines, int64_t m, const T* __restrict__ p,
+                                                    const T* __restrict__ coef, T* r) {
   constexpr int LPW = 64 / W;  // lines per wave
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -7182,15 +7205,15 @@ __global__ __launch_bounds__(256) void seamx_kernel(int64_t nlines, int64_t m, c
   const int64_t line = wave * LPW + lane / W;
   const bool live = line < nlines;
   const int64_t i0 = live ? line * m : 0;
-  double acc = 0.0;
+  T acc = T(0);
   if (live) {
     for (int64_t c0 = k; c0 < m; c0 += (int64_t)SEAM_BATCH * W) {
-      double pv[SEAM_BATCH], rv[SEAM_BATCH];
+      T pv[SEAM_BATCH], rv[SEAM_BATCH];
 #pragma unroll
       for (int j = 0; j < SEAM_BATCH; ++j) {
         const int64_t c = c0 + (int64_t)j * W;
-        pv[j] = c < m ? p[i0 + c] : 0.0;
-        rv[j] = c < m ? r[i0 + c] : 0.0;
+        pv[j] = c < m ? p[i0 + c] : T(0);
+        rv[j] = c < m ? r[i0 + c] : T(0);
       }
 #pragma unroll
       for (int j = 0; j < SEAM_BATCH; ++j)
@@ -7200,34 +7223,35 @@ __global__ __launch_bounds__(256) void seamx_kernel(int64_t nlines, int64_t m, c
 #pragma unroll
   for (int off = W / 2; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, W);
   if (live && k == 0) {
-    const double fac = acc / coef[line];
+    const T fac = acc / coef[line];
     const int64_t i1 = i0 + m - 1;
     r[i0] = r[i0] - fac * coef[nlines + line];
     r[i1] = r[i1] - fac * coef[2 * nlines + line];
   }
 }
 constexpr int SEAM_WALK = 8;
+template <typename T>
 __global__ __launch_bounds__(256) void seam_stride_kernel(int64_t nlines, int64_t s, int64_t m,
-                                                          const double* __restrict__ p,
-                                                          const double* __restrict__ coef, double* r) {
+                                                          const T* __restrict__ p, const T* __restrict__ coef,
+                                                          T* r) {
   const int64_t line = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (line >= nlines) return;
   const int64_t b = line / s;
   const int64_t i0 = b * s * m + (line - b * s);
-  double acc = 0.0;
+  T acc = T(0);
   for (int64_t k0 = 0; k0 < m; k0 += SEAM_WALK) {
-    double pv[SEAM_WALK], rv[SEAM_WALK];
+    T pv[SEAM_WALK], rv[SEAM_WALK];
 #pragma unroll
     for (int j = 0; j < SEAM_WALK; ++j) {
       const bool on = k0 + j < m;
-      pv[j] = on ? p[i0 + (k0 + j) * s] : 0.0;
-      rv[j] = on ? r[i0 + (k0 + j) * s] : 0.0;
+      pv[j] = on ? p[i0 + (k0 + j) * s] : T(0);
+      rv[j] = on ? r[i0 + (k0 + j) * s] : T(0);
     }
 #pragma unroll
     for (int j = 0; j < SEAM_WALK; ++j)
       if (k0 + j < m) acc = acc + pv[j] * rv[j];
   }
-  const double fac = acc / coef[line];
+  const T fac = acc / coef[line];
   const int64_t i1 = i0 + (m - 1) * s;
   r[i0] = r[i0] - fac * coef[nlines + line];
   r[i1] = r[i1] - fac * coef[2 * nlines + line];
@@ -7329,23 +7353,33 @@ int64_t seam_setup_host(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, 
   }
   return -1;
 }
-hipError_t launch_line_seam(const SeamRef& S, double* r, hipStream_t st) {
-  if (!seam_ok(S.n, S.s, S.m)) return hipErrorInvalidValue;
-  const int64_t nlines = S.n / S.m;
-  if (S.s > 1) {
-    hipLaunchKernelGGL(seam_stride_kernel, line_grid(nlines), dim3(256), 0, st, nlines, S.s, S.m, S.p, S.coef, r);
+namespace {
+template <typename T>
+hipError_t line_seam_t(int64_t n, int64_t s, int64_t m, const T* p, const T* coef, T* r, hipStream_t st) {
+  if (!seam_ok(n, s, m)) return hipErrorInvalidValue;
+  const int64_t nlines = n / m;
+  if (s > 1) {
+    hipLaunchKernelGGL(seam_stride_kernel<T>, line_grid(nlines), dim3(256), 0, st, nlines, s, m, p, coef, r);
     return hipGetLastError();
   }
-#define SEAMX(W)                                                                                                  \
-  hipLaunchKernelGGL(seamx_kernel<W>, line_grid((nlines + 64 / W - 1) / (64 / W) * 64), dim3(256), 0, st, nlines, \
-                     S.m, S.p, S.coef, r)
-  if (S.m <= 4) SEAMX(4);
-  else if (S.m <= 8) SEAMX(8);
-  else if (S.m <= 16) SEAMX(16);
-  else if (S.m <= 32) SEAMX(32);
+#define SEAMX(W)                                                                                                       \
+  hipLaunchKernelGGL((seamx_kernel<W, T>), line_grid((nlines + 64 / W - 1) / (64 / W) * 64), dim3(256), 0, st, nlines, \
+                     m, p, coef, r)
+  if (m <= 4) SEAMX(4);
+  else if (m <= 8) SEAMX(8);
+  else if (m <= 16) SEAMX(16);
+  else if (m <= 32) SEAMX(32);
   else SEAMX(64);
 #undef SEAMX
   return hipGetLastError();
+}
+}  // namespace
+hipError_t launch_line_seam(const SeamRef& S, double* r, hipStream_t st) {
+  return line_seam_t<double>(S.n, S.s, S.m, S.p, S.coef, r, st);
+}
+hipError_t launch_line_seam_f32(int64_t n, int64_t s, int64_t m, const float* p, const float* coef, float* r,
+                                hipStream_t st) {
+  return line_seam_t<float>(n, s, m, p, coef, r, st);
 }
 
 // ------------------------------------------------------------------ K-F32 ----
@@ -7570,6 +7604,15 @@ __global__ __launch_bounds__(256) void to_f64_kernel(int64_t n, const float* __r
   } else {
     for (int64_t k = i; k < n; ++k) dst[k] = (double)src[k];
   }
+}
+__global__ __launch_bounds__(256) void zero_f32_kernel(int64_t n, float* __restrict__ x) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = 0.0f;
+}
+hipError_t launch_zero_f32(int64_t n, float* x, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, x);
+  return hipGetLastError();
 }
 hipError_t launch_to_f32(int64_t n, const double* src, float* dst, hipStream_t st) {
   if (n <= 0) return hipSuccess;

@@ -81,6 +81,14 @@ int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32
 hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
                              hipStream_t st);
 bool line_few_chains(int64_t s);  // the reduced systems run as one workgroup per chain
+// The solve in float (single-precision cycle): the same kernels instantiated on float, on float copies
+// of the factors (no float elimination).  y: n floats of scratch.
+struct LineRefF32 {
+  int64_t n = 0, s = 1;
+  const float *dl = nullptr, *ip = nullptr, *cp = nullptr, *v = nullptr, *w = nullptr;
+};
+hipError_t launch_line_solve_f32(const LineRefF32& L, const float* r, float* y, float* u, float omega,
+                                 hipStream_t st);
 // K-LineX, the x lines of a tensor grid (AMG_HIP_SM_LINE_ALT): n / nx lines of nx rows, each
 // contiguous in memory.  T_x = the diagonal of A and its entries at column offsets +-1 that stay
 // inside a line; dl, ip, cp (n doubles each) are its plain Thomas factors, dl = 0 on the first and
@@ -101,6 +109,9 @@ int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int
                          int cyc = 0);
 // u += omega T_x^-1 r; r is overwritten (the forward values).  Two launches.
 hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double omega, hipStream_t st);
+// the same two launches on float copies of dl, ip, cp (chunks of LINEX_COLS columns as in double)
+hipError_t launch_linex_solve_f32(int64_t n, int64_t nx, const float* dl, const float* ip, const float* cp, float* r,
+                                  float* u, float omega, hipStream_t st);
 // K-LineSeam, cyclic lines along a periodic axis (AMG_HIP_SM_LINE_ALT with cyclic_lines): the lines of
 // stride s and length m >= 3 (n a multiple of s m; row i on position (i / s) % m of its line, first row
 // i0, last row i1) carry the wrap entries alpha = a(i0, i1), beta = a(i1, i0).  With gamma = -a(i0, i0),
@@ -124,6 +135,9 @@ int64_t seam_setup_host(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, 
                         const double* val);
 // r(i0) -= fac gamma, r(i1) -= fac beta on every line, in place.  One launch.
 hipError_t launch_line_seam(const SeamRef& S, double* r, hipStream_t st);
+// the same launch on float copies of p and coef (SeamRef's n, s, m)
+hipError_t launch_line_seam_f32(int64_t n, int64_t s, int64_t m, const float* p, const float* coef, float* r,
+                                hipStream_t st);
 // Same operations on a SELL-64 matrix (64-row panels, lane-interleaved):
 // soff[n/64 + 1] panel offsets, scol/sval padded with col = -1.
 // idx16 bit 0: scol holds int16 offsets from the diagonal column (pad -32768);
@@ -602,6 +616,9 @@ hipError_t launch_csr_f32(int mode, int64_t n, const int32_t* rowptr, const int3
 // dst[i] = (float)src[i] / (double)src[i], round to nearest
 hipError_t launch_to_f32(int64_t n, const double* src, float* dst, hipStream_t st);
 hipError_t launch_to_f64(int64_t n, const float* src, double* dst, hipStream_t st);
+// x[i] = +0.0f as a kernel: the float cycle's captured graph holds no memset node (solver.cpp:
+// enqueue_f32_vcycle)
+hipError_t launch_zero_f32(int64_t n, float* x, hipStream_t st);
 // float instantiations of launch_linear_restrict / _prolong_add and launch_tensor_restrict / _prolong_add
 hipError_t launch_linear_restrict_f32(int64_t n_h, int64_t n_H, const float* r, float* fH, float* uH_zero,
                                       hipStream_t st);

@@ -1457,11 +1457,31 @@ struct F32Mat {
   const DevMat* src = nullptr;  // layout and index arrays
   DevMem val;                   // src's sval (SELL) or csr.val (CSR) as floats
 };
+// float copies of one K-Line factor set (LineOnDev) and its scratch vector
+struct F32Line {
+  DevMem dl, ip, cp, v, w, y;
+  LineRefF32 ref(const LineOnDev& D) const {
+    LineRefF32 R;
+    R.n = D.n;
+    R.s = D.s;
+    R.dl = dl.as<float>();
+    R.ip = ip.as<float>();
+    R.cp = cp.as<float>();
+    R.v = v.as<float>();
+    R.w = w.as<float>();
+    return R;
+  }
+};
 struct F32Level {
   F32Mat rows, cols_own;
   const F32Mat* cols = nullptr;  // what the Jacobi sweep walks; = &rows on a bitwise symmetric level
   DevMem u, f, r, tmp, d;        // floats; d: Chebyshev
   DevMem pval, rval;             // CSR transfers (kind 0): values of P_rows / R_rows as floats
+  // line smoothers (amg_hip_set_f32_lines): float copies of the level's double factors
+  F32Line line;                  // LINE_JACOBI: Level::line
+  DevMem xdl, xip, xcp;          // LINE_ALT: AltOnDev's K-LineX factors
+  F32Line yz[2];                 //           AltOnDev::yz
+  DevMem seam_p[3], seam_coef[3];  //         AltOnDev's K-LineSeam arrays
 };
 struct F32 {
   bool ready = false;
@@ -1495,6 +1515,13 @@ int g_tail_fusion = [] {
 // amg_hip_setup_on_device == 0 for that entry point ("Periodic axes").
 int g_periodic_device_setup = [] {
   const char* e = std::getenv("AMG_HIP_PERIODIC_DEVICE_SETUP");
+  return (e && *e == '1') ? 1 : 0;
+}();
+// amg_hip_set_f32_lines / AMG_HIP_F32_LINES=1: the single-precision cycle accepts the line smoothers
+// (K-LineF32).  0 by default only because earlier tests pin the refusal of the float entry points on
+// line-smoother solvers ("Single-precision preconditioner").
+int g_f32_lines = [] {
+  const char* e = std::getenv("AMG_HIP_F32_LINES");
   return (e && *e == '1') ? 1 : 0;
 }();
 int64_t g_patch_min_rows = 1000000;  // amg_hip_set_patch_min_rows (level 4 of 4096^2 has 1 048 575 rows)
@@ -4013,10 +4040,13 @@ amg_hip_status block_sums_to_host(amg_hip_solver* s, int kp, const double* x, co
 amg_hip_status f32_supported(amg_hip_solver* s) {
   if (s->opt.window)
     return fail(AMG_HIP_EUNSUPPORTED, "single-precision cycle: a window solver (opt.window) is not supported");
-  if (s->opt.smoother != AMG_HIP_SM_JACOBI && s->opt.smoother != AMG_HIP_SM_CHEBYSHEV)
-    return fail(AMG_HIP_EUNSUPPORTED, std::string("single-precision cycle: the smoother ") +
-                                          block_smoother_name(s->opt.smoother) +
-                                          " is not supported (true Jacobi and Chebyshev are)");
+  const bool line = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT;
+  if (s->opt.smoother != AMG_HIP_SM_JACOBI && s->opt.smoother != AMG_HIP_SM_CHEBYSHEV && !(g_f32_lines && line))
+    return fail(AMG_HIP_EUNSUPPORTED,
+                std::string("single-precision cycle: the smoother ") + block_smoother_name(s->opt.smoother) +
+                    (g_f32_lines ? " is not supported (true Jacobi, Chebyshev, AMG_HIP_SM_LINE_JACOBI and "
+                                   "AMG_HIP_SM_LINE_ALT are)"
+                                 : " is not supported (true Jacobi and Chebyshev are)"));
   if (s->lv.size() < 2)
     return fail(AMG_HIP_EUNSUPPORTED, "single-precision cycle: a one-level solver has no cycle (the direct solve "
                                       "stays in double); use amg_hip_apply");
@@ -4032,11 +4062,50 @@ amg_hip_status f32_copy_values(const DevMat& A, F32Mat* M, hipStream_t st) {
   return AMG_HIP_OK;
 }
 
+// a float copy of `count` doubles of a factor array, made on the device
+amg_hip_status f32_copy_array(const DevMem& src, int64_t count, DevMem* dst, hipStream_t st) {
+  HIP_TRY(dst->alloc(sizeof(float) * (size_t)std::max<int64_t>(count, 1)));
+  HIP_TRY(launch_to_f32(count, src.as<double>(), dst->as<float>(), st));
+  return AMG_HIP_OK;
+}
+amg_hip_status f32_copy_line(const LineOnDev& D, F32Line* Q, hipStream_t st) {
+  amg_hip_status r;
+  const DevMem* src[5] = {&D.dl, &D.ip, &D.cp, &D.v, &D.w};
+  DevMem* dst[5] = {&Q->dl, &Q->ip, &Q->cp, &Q->v, &Q->w};
+  for (int k = 0; k < 5; ++k)
+    if ((r = f32_copy_array(*src[k], D.n, dst[k], st)) != AMG_HIP_OK) return r;
+  HIP_TRY(Q->y.alloc(sizeof(float) * (size_t)D.n));
+  return AMG_HIP_OK;
+}
+// the float factors of a level's line smoother: copies of the double ones, no float elimination
+amg_hip_status f32_copy_line_factors(const amg_hip_solver* s, const Level& L, F32Level* Q, hipStream_t st) {
+  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI) return f32_copy_line(L.line, &Q->line, st);
+  const AltOnDev& D = L.alt;
+  amg_hip_status r;
+  if (D.n_dir == 0) return f32_copy_line(D.yz[0], &Q->yz[0], st);
+  for (int d = 0; d < D.n_dir; ++d) {
+    const int a = D.axis[d];
+    if (a == 0) {
+      if ((r = f32_copy_array(D.xdl, D.n, &Q->xdl, st)) != AMG_HIP_OK) return r;
+      if ((r = f32_copy_array(D.xip, D.n, &Q->xip, st)) != AMG_HIP_OK) return r;
+      if ((r = f32_copy_array(D.xcp, D.n, &Q->xcp, st)) != AMG_HIP_OK) return r;
+    } else if ((r = f32_copy_line(D.yz[a - 1], &Q->yz[a - 1], st)) != AMG_HIP_OK) {
+      return r;
+    }
+    if (D.cyc[d]) {
+      if ((r = f32_copy_array(D.seam_p[d], D.n, &Q->seam_p[d], st)) != AMG_HIP_OK) return r;
+      if ((r = f32_copy_array(D.seam_coef[d], 3 * (D.n / D.len[d]), &Q->seam_coef[d], st)) != AMG_HIP_OK) return r;
+    }
+  }
+  return AMG_HIP_OK;
+}
+
 amg_hip_status ensure_f32(amg_hip_solver* s) {
   F32& F = s->f32;
   if (F.ready) return AMG_HIP_OK;
   const int nl = (int)s->lv.size();
   const bool jac = s->opt.smoother == AMG_HIP_SM_JACOBI;
+  const bool line = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT;
   for (int l = 0; l + 1 < nl; ++l) {
     const Level& L = s->lv[l];
     if (L.A_rows.dict || (jac && L.A_cols().dict))
@@ -4054,11 +4123,17 @@ amg_hip_status ensure_f32(amg_hip_solver* s) {
     const size_t bytes = sizeof(float) * (size_t)L.n;
     HIP_TRY(Q.u.alloc(bytes));
     HIP_TRY(Q.f.alloc(bytes));
-    if (l + 1 == nl) continue;  // the coarsest level only takes the direct solve
+    // The coarsest level only takes the direct solve.  With a line smoother it still gets a float matrix,
+    // r and factors (it is small), so that amg_hip_f32_line_subsweep runs on every level as
+    // amg_hip_level_op does in double: a level of one row is always the coarsest.
+    const bool last = l + 1 == nl;
+    if (last && (!line || L.A_rows.dict)) continue;
     HIP_TRY(Q.r.alloc(bytes));
-    HIP_TRY(Q.tmp.alloc(bytes));
-    if (!jac) HIP_TRY(Q.d.alloc(bytes));
+    if (line && (r = f32_copy_line_factors(s, L, &Q, st)) != AMG_HIP_OK) return r;
     if ((r = f32_copy_values(L.A_rows, &Q.rows, st)) != AMG_HIP_OK) return r;
+    if (last) continue;
+    HIP_TRY(Q.tmp.alloc(bytes));
+    if (s->opt.smoother == AMG_HIP_SM_CHEBYSHEV) HIP_TRY(Q.d.alloc(bytes));
     if (jac && !L.symmetric)
       if ((r = f32_copy_values(L.A_cols_own, &Q.cols_own, st)) != AMG_HIP_OK) return r;
     if (!(L.linear && s->opt.stencil_transfers) && !L.tensor_stencil) {
@@ -4104,7 +4179,41 @@ double mat_bytes_f32(const F32Mat& M) {
     if (!dry) HIP_TRY(expr);      \
   } while (0)
 
-amg_hip_status enqueue_f32_smooth(amg_hip_solver* s, int l, bool dry) {
+// One sub-sweep of a line smoother in float (launch_line_sweep / launch_alt_subsweep on the float
+// copies): r = f - A u, K-LineSeam on r where direction d is cyclic, u += omega T^-1 r.  LINE_JACOBI:
+// d = 0.  Bytes: the matrix pass; then half of the double solve's (LineOnDev::solve_bytes,
+// AltOnDev::solve_bytes).
+amg_hip_status enqueue_f32_line_subsweep(amg_hip_solver* s, int l, int d, bool dry) {
+  const Level& L = s->lv[l];
+  F32Level& Q = s->f32.lv[(size_t)l];
+  hipStream_t st = s->stream;
+  float* u = Q.u.as<float>();
+  float* r = Q.r.as<float>();
+  const float omega = (float)s->opt.omega;
+  F32_DO(launch_mat_f32(CSR_RESID, Q.rows, u, Q.f.as<float>(), r, 1.0f, nullptr, 0.0f, st));
+  s->facct(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);  // matrix; u, f in and r out
+  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI) {
+    F32_DO(launch_line_solve_f32(Q.line.ref(L.line), r, Q.line.y.as<float>(), u, omega, st));
+    s->facct(0.5 * L.line.solve_bytes());
+    return AMG_HIP_OK;
+  }
+  const AltOnDev& D = L.alt;
+  if (D.n_dir > 0 && D.cyc[d])
+    F32_DO(launch_line_seam_f32(D.n, D.stride[d], D.len[d], Q.seam_p[d].as<float>(), Q.seam_coef[d].as<float>(), r,
+                                st));
+  if (D.n_dir > 0 && D.axis[d] == 0) {
+    F32_DO(launch_linex_solve_f32(D.n, D.len[0], Q.xdl.as<float>(), Q.xip.as<float>(), Q.xcp.as<float>(), r, u, omega,
+                                  st));
+  } else {
+    const int k = D.n_dir == 0 ? 0 : D.axis[d] - 1;
+    F32_DO(launch_line_solve_f32(Q.yz[k].ref(D.yz[k]), r, Q.yz[k].y.as<float>(), u, omega, st));
+  }
+  s->facct(0.5 * D.solve_bytes(d));
+  return AMG_HIP_OK;
+}
+
+// reverse: the way up (AMG_HIP_SM_LINE_ALT runs its directions descending there)
+amg_hip_status enqueue_f32_smooth(amg_hip_solver* s, int l, bool dry, bool reverse = false) {
   const Level& L = s->lv[l];
   F32Level& Q = s->f32.lv[(size_t)l];
   hipStream_t st = s->stream;
@@ -4112,6 +4221,16 @@ amg_hip_status enqueue_f32_smooth(amg_hip_solver* s, int l, bool dry) {
   float* a = Q.u.as<float>();
   float* b = Q.tmp.as<float>();
   int64_t passes = 0;
+  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
+    // enqueue_smooth's order: u is updated in place, so nothing has to come home
+    const int nd = s->opt.smoother == AMG_HIP_SM_LINE_ALT ? std::max(L.alt.n_dir, 1) : 1;
+    for (int it = 0; it < s->opt.smoother_iters; ++it)
+      for (int q = 0; q < nd; ++q) {
+        const amg_hip_status r = enqueue_f32_line_subsweep(s, l, reverse ? nd - 1 - q : q, dry);
+        if (r != AMG_HIP_OK) return r;
+      }
+    return AMG_HIP_OK;
+  }
   if (s->opt.smoother == AMG_HIP_SM_JACOBI) {
     for (int it = 0; it < s->opt.smoother_iters; ++it) {
       F32_DO(launch_mat_f32(CSR_JACOBI, *Q.cols, a, Q.f.as<float>(), b, (float)s->opt.omega, nullptr, 0.0f, st));
@@ -4167,7 +4286,7 @@ amg_hip_status enqueue_f32_restrict(amg_hip_solver* s, int l, bool dry) {
     F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
     s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
   } else {
-    F32_DO(hipMemsetAsync(QC.u.p, 0, sizeof(float) * (size_t)C.n, st));
+    F32_DO(launch_zero_f32(C.n, QC.u.as<float>(), st));  // as the zero guess: no memset node
     const DevCsr& R = L.R_rows;
     F32_DO(launch_csr_f32(CSR_SPMV, R.n_rows, R.rowptr(), R.col(), Q.rval.as<float>(), Q.r.as<float>(), nullptr,
                           QC.f.as<float>(), 1.0f, nullptr, 0.0f, st));
@@ -4217,7 +4336,9 @@ amg_hip_status enqueue_f32_prolong(amg_hip_solver* s, int l, bool dry) {
 amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
   const int nl = (int)s->lv.size();
   amg_hip_status r;
-  F32_DO(hipMemsetAsync(s->f32.lv[0].u.p, 0, sizeof(float) * (size_t)s->lv[0].n, s->stream));  // the zero guess
+  // the zero guess.  A kernel, not hipMemsetAsync: a memset node of the captured graph was seen to fill
+  // with stale bytes when the graph is replayed after a device-to-host copy (64 x 48 grid, 12288 bytes)
+  F32_DO(launch_zero_f32(s->lv[0].n, s->f32.lv[0].u.as<float>(), s->stream));
   s->facct(4.0 * (double)s->lv[0].n);
   for (int l = 0; l + 1 < nl; ++l) {
     if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;    // :268
@@ -4227,7 +4348,7 @@ amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
   if ((r = enqueue_f32_coarse(s, dry)) != AMG_HIP_OK) return r;
   for (int l = nl - 2; l >= 0; --l) {                                   // :291
     if ((r = enqueue_f32_prolong(s, l, dry)) != AMG_HIP_OK) return r;
-    if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;    // :300
+    if ((r = enqueue_f32_smooth(s, l, dry, true)) != AMG_HIP_OK) return r;  // :300
   }
   return AMG_HIP_OK;
 }
@@ -4317,6 +4438,7 @@ void amg_hip_set_patch_tall(int32_t on) { g_patch_tall = on ? 1 : 0; }
 void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
 void amg_hip_set_periodic_device_setup(int32_t on) { g_periodic_device_setup = on ? 1 : 0; }
+void amg_hip_set_f32_lines(int32_t on) { g_f32_lines = on ? 1 : 0; }
 void amg_hip_set_patch_min_rows(int64_t rows) { g_patch_min_rows = rows < 0 ? INT64_MAX : rows; }
 
 void amg_hip_set_default_layout(int32_t layout) {
@@ -5368,6 +5490,41 @@ amg_hip_status amg_hip_f32_level_op(amg_hip_solver* s, int32_t level, int32_t op
     case 3: return enqueue_f32_prolong(s, level, false);
     default: return enqueue_f32_coarse(s, false);
   }
+}
+
+// the checks of the two line hooks after f32_hook_ready's: a line smoother, a level with a float matrix
+static amg_hip_status f32_line_hook_ready(amg_hip_solver* s, int32_t level, const char* bad) {
+  amg_hip_status r = f32_hook_ready(s, level, bad);
+  if (r != AMG_HIP_OK) return r;
+  if (s->opt.smoother != AMG_HIP_SM_LINE_JACOBI && s->opt.smoother != AMG_HIP_SM_LINE_ALT)
+    return fail(AMG_HIP_EINVAL, "the solver has no line smoother");
+  if (!s->f32.lv[(size_t)level].rows.src)  // the coarsest level in the dictionary layout
+    return fail(AMG_HIP_EINVAL, "level " + std::to_string(level) + " has no float matrix");
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_f32_line_subsweep(amg_hip_solver* s, int32_t level, int32_t d, int32_t reverse) {
+  (void)reverse;  // a sub-sweep is one direction: the leg only orders them
+  amg_hip_status r = f32_line_hook_ready(s, level, d < 0 || d > 2 ? "direction index out of range" : nullptr);
+  if (r != AMG_HIP_OK) return r;
+  const int nd = s->opt.smoother == AMG_HIP_SM_LINE_ALT ? std::max(s->lv[level].alt.n_dir, 1) : 1;
+  if (d >= nd) return fail(AMG_HIP_EINVAL, "direction index out of range");
+  return enqueue_f32_line_subsweep(s, level, d, false);
+}
+
+amg_hip_status amg_hip_f32_line_factors(amg_hip_solver* s, int32_t level, float* dl, float* ip, float* cp) {
+  amg_hip_status r = f32_line_hook_ready(s, level, !dl || !ip || !cp ? "null argument" : nullptr);
+  if (r != AMG_HIP_OK) return r;
+  const AltOnDev& D = s->lv[level].alt;
+  if (s->opt.smoother != AMG_HIP_SM_LINE_ALT || D.n_dir == 0 || D.axis[0] != 0)
+    return fail(AMG_HIP_EINVAL, "level " + std::to_string(level) + " has no x direction (K-LineX factors)");
+  F32Level& Q = s->f32.lv[(size_t)level];
+  const size_t bytes = sizeof(float) * (size_t)D.n;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpy(dl, Q.xdl.p, bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ip, Q.xip.p, bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cp, Q.xcp.p, bytes, hipMemcpyDeviceToHost));
+  return AMG_HIP_OK;
 }
 
 amg_hip_status amg_hip_solve(amg_hip_solver* s, double tol, int64_t every, int64_t n_iters,

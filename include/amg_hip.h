@@ -298,6 +298,14 @@ void amg_hip_set_tail_fusion(int32_t on);
  * for bit either way; amg_hip_setup_on_device tells the two apart.                                 */
 void amg_hip_set_periodic_device_setup(int32_t on);
 
+/* The single-precision entry points (amg_hip_apply_f32, amg_hip_pcg_mixed, amg_hip_f32_*) accept
+ * solvers smoothed with AMG_HIP_SM_LINE_JACOBI and AMG_HIP_SM_LINE_ALT (K-LineF32: the line solve
+ * kernels instantiated on float, on float copies of the double factors).  Process-wide, read whenever a
+ * float entry point runs its checks; default 0 (AMG_HIP_F32_LINES=1 in the environment turns it on).
+ * Off: those solvers are refused as before (AMG_HIP_EUNSUPPORTED).  No double entry point is touched
+ * either way.                                                                                     */
+void amg_hip_set_f32_lines(int32_t on);
+
 /* Number of usable HIP devices (0 when none; never fails). */
 int amg_hip_device_count(void);
 
@@ -837,6 +845,14 @@ amg_hip_status amg_hip_block_must_move(amg_hip_solver* s, int32_t k, double* byt
  * stored in the dictionary layout (the level in the message): create the solver with
  * layout = AMG_HIP_LAYOUT_SELL.
  *
+ * With amg_hip_set_f32_lines(1) the smoother check also accepts AMG_HIP_SM_LINE_JACOBI and
+ * AMG_HIP_SM_LINE_ALT (cyclic_lines included); every other check and its place in the order stay.
+ * The line solves run in float on float copies of the double factors (made on the device at the
+ * first float call with to_f32; there is no float elimination): half of the 72 B (2-D) or 120 B
+ * (3-D) per row and level that the double factors of AMG_HIP_SM_LINE_ALT take, 24 B per row for
+ * AMG_HIP_SM_LINE_JACOBI.  One application differs from amg_hip_apply's by 1e-7 to 4e-5 relative,
+ * the strongly anisotropic operators at the upper end.
+ *
  * amg_hip_apply_f32: z = M32^-1 v.  v_dev / z_dev: DEVICE pointers to n_dofs(0) doubles (may alias);
  * v is rounded to float, one float V-cycle from zero runs, the result is widened into z.  Enqueued on
  * the solver's stream.                                                                          */
@@ -868,6 +884,22 @@ amg_hip_status amg_hip_f32_must_move(amg_hip_solver* s, double* bytes);
 amg_hip_status amg_hip_f32_get_vec(amg_hip_solver* s, int32_t level, int32_t which, float* out_host);
 amg_hip_status amg_hip_f32_set_vec(amg_hip_solver* s, int32_t level, int32_t which, const float* in_host);
 amg_hip_status amg_hip_f32_level_op(amg_hip_solver* s, int32_t level, int32_t op);
+/* TEST HOOKS on the float line smoothers (amg_hip_set_f32_lines).  Same checks as the three above
+ * (AMG_HIP_EINVAL first: null pointers, a level out of range, d outside 0..2), then AMG_HIP_EINVAL for a
+ * solver without a line smoother or a d the level does not have.  With a line smoother the coarsest
+ * level (small, and the only one that can have a single row) keeps a float matrix, r and factors too,
+ * so both hooks take every level, as amg_hip_level_op does (not a coarsest level stored in the
+ * dictionary layout: AMG_HIP_EINVAL).
+ * amg_hip_f32_line_subsweep: one sub-sweep on the float vectors of `level` with the launches the cycle
+ * makes for it: r = f - A u (into the float r), K-LineSeam where direction d is cyclic, then
+ * u += omega T_d^-1 r by K-LineX (which leaves its forward values in r) or K-Line.  d: the index among
+ * the level's directions (axes of length >= 2 in the order x, y, z); AMG_HIP_SM_LINE_JACOBI and a
+ * level without a direction: d = 0.  `reverse` names the leg (0 down, 1 up); a single sub-sweep is
+ * the same on both.
+ * amg_hip_f32_line_factors: the float K-LineX factors dl, ip, cp of `level` (n_dofs(level) floats each)
+ * to HOST memory; AMG_HIP_EINVAL where the level has no x direction.                               */
+amg_hip_status amg_hip_f32_line_subsweep(amg_hip_solver* s, int32_t level, int32_t d, int32_t reverse);
+amg_hip_status amg_hip_f32_line_factors(amg_hip_solver* s, int32_t level, float* dl, float* ip, float* cp);
 
 /* Getters, multigrid.hpp:339-354. */
 int32_t amg_hip_n_levels(const amg_hip_solver* s);

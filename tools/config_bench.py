@@ -17,6 +17,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
        config_bench.py periodic-setup [<nx> <ny> <nz>]             set-up seconds of tensor_periodic_dev on that operator with set_periodic_device_setup off (host constructor) and on (device), legs alternate; next to them tensor_dev on the open-box operator of the same grid
        config_bench.py periodic-lines                              PCG to 1e-8 and ms per V-cycle of AMG_HIP_SM_LINE_ALT on diffusion that is strong along a periodic x axis (4096 x 1024, 256^3): open lines (cyclic_lines 0) against cyclic lines (cyclic_lines 1), legs alternate
+       config_bench.py mixed-line [split2|split3|cyclic2|cyclic3]  amg_hip_pcg and amg_hip_pcg_mixed alternating on AMG_HIP_SM_LINE_ALT solvers (amg_hip_set_f32_lines): split-anisotropy through tensor_dev and the periodic-lines operator with cyclic lines, 4096 x 1024 and 256^3
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
@@ -882,6 +883,119 @@ def run_periodic_lines(dims, eps, L, reps=3, rtol=1e-8, max_iters=300):
         mg.close()
 
 
+def torch_split_anisotropy_nd(dims, eps=1e-3):
+    """torch_split_anisotropy in 2-D or 3-D: point coefficients (x, y) = (1, eps) in the left half of the
+    box and (eps, 1) in the right half, z = eps everywhere (one strong direction at every point);
+    harmonic means on the edges, Dirichlet; (crow, col, val, b) on the GPU."""
+    import torch
+    dev = torch.device("cuda")
+    dim = len(dims)
+    ext = tuple(dims) + (1,) * (3 - dim)
+    n = ext[0] * ext[1] * ext[2]
+    i = torch.arange(n, device=dev)
+    coord = [i % ext[0], (i // ext[0]) % ext[1], i // (ext[0] * ext[1])]
+    stride = [1, ext[0], ext[0] * ext[1]]
+    left = coord[0] < ext[0] // 2
+    one, small = torch.ones(n, dtype=torch.float64, device=dev), torch.full((n,), eps, dtype=torch.float64, device=dev)
+    c = [torch.where(left, one, small), torch.where(left, small, one), small]
+    w = 2 * dim + 1
+    cols = torch.full((n, w), n, dtype=torch.int64, device=dev)  # n: no entry, sorts last
+    vals = torch.zeros((n, w), dtype=torch.float64, device=dev)
+    diag = torch.zeros(n, dtype=torch.float64, device=dev)
+    for a in range(dim):
+        lo_ok, hi_ok = coord[a] > 0, coord[a] < ext[a] - 1
+        c_lo, c_hi = torch.roll(c[a], stride[a]), torch.roll(c[a], -stride[a])
+        k_lo = torch.where(lo_ok, 2.0 * c[a] * c_lo / (c[a] + c_lo), c[a])
+        k_hi = torch.where(hi_ok, 2.0 * c[a] * c_hi / (c[a] + c_hi), c[a])
+        diag = diag + k_lo + k_hi
+        cols[:, 2 * a] = torch.where(lo_ok, i - stride[a], cols[:, 2 * a])
+        cols[:, 2 * a + 1] = torch.where(hi_ok, i + stride[a], cols[:, 2 * a + 1])
+        vals[:, 2 * a], vals[:, 2 * a + 1] = -k_lo, -k_hi
+    cols[:, w - 1], vals[:, w - 1] = i, diag
+    cols, order = torch.sort(cols, dim=1)
+    vals = torch.gather(vals, 1, order)
+    mask = cols < n
+    crow = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    crow[1:] = torch.cumsum(mask.sum(1), 0).to(torch.int32)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    b = torch.rand(n, generator=g, device=dev, dtype=torch.float64)
+    return crow, cols[mask].to(torch.int32).contiguous(), vals[mask].contiguous(), b
+
+
+def run_mixed_line(label, make, reps=3, rtol=1e-8, applies=10):
+    """amg_hip_pcg (double cycle) and amg_hip_pcg_mixed (float cycle, amg_hip_set_f32_lines) to `rtol` from
+    x = 0 on one AMG_HIP_SM_LINE_ALT solver (omega 0.8, 1+1, layout SELL) made by make(), alternating in one
+    process, best of `reps`.  Per run: iterations and wall ms; then ms per preconditioner application over
+    `applies` calls closed by one synchronise (double: vcycle(), the cycle amg_hip_pcg runs; mixed:
+    amg_hip_apply_f32) and the must-move bytes of one application over that time as a share of 8 TB/s."""
+    import torch
+    t0 = time.perf_counter()
+    mg, b = make()
+    mg.sync()
+    print(f"mixed-line {label}: setup {time.perf_counter() - t0:.2f} s, {mg.n_levels} levels, level-0 layout "
+          f"{mg.level_layout(0)}, cyclic axes per level {[mg.line_cyclic(l) for l in range(mg.n_levels)]}", flush=True)
+    z = torch.empty_like(b)
+    calls = {"double": (mg.pcg, mg.apply_dev, mg.cycle_must_move()), "mixed": (mg.pcg_mixed, mg.apply_f32, mg.f32_must_move())}
+    for name in calls:  # first calls: work vectors, float copies, captured graphs
+        calls[name][1](b.data_ptr(), z.data_ptr())
+    mg.sync()
+    best = {}
+    for rep_ in range(reps):
+        for name, (solve, apply, mm) in calls.items():
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            _, it, rel = solve(rtol=rtol, max_iters=300)
+            dt = time.perf_counter() - t0
+            if name == "double":
+                mg.zero_vec(0, "u")
+                mg.sync()
+            t0 = time.perf_counter()
+            if name == "double":
+                mg.vcycle(applies)
+            else:
+                for _ in range(applies):
+                    apply(b.data_ptr(), z.data_ptr())
+            mg.sync()
+            da = (time.perf_counter() - t0) / applies
+            old = best.get(name, (it, dt, da))
+            best[name] = (it, min(old[1], dt), min(old[2], da))
+            print(f"mixed-line {label}, {name} rep {rep_}: {it} iterations, {dt * 1e3:.2f} ms to {rtol:g} (relres "
+                  f"{rel:.2e}, {'reached' if rel <= rtol else 'NOT reached'}), {da * 1e3:.3f} ms per application, "
+                  f"must-move {mm / 1e6:.1f} MB = {mm / da / 8e12 * 100:.1f} % of 8 TB/s", flush=True)
+    d, m = best["double"], best["mixed"]
+    print(f"mixed-line {label} ({b.numel()} dofs): best solve double {d[0]} iterations {d[1] * 1e3:.2f} ms, mixed "
+          f"{m[0]} iterations {m[1] * 1e3:.2f} ms, ratio {d[1] / m[1]:.2f}; best application double {d[2] * 1e3:.3f} ms, "
+          f"mixed {m[2] * 1e3:.3f} ms, ratio {d[2] / m[2]:.2f}", flush=True)
+    mg.close()
+
+
+def mixed_line_cases(which=None):
+    """profiles/mixed_line_config_bench.txt: the split-anisotropy operator through tensor_dev at 4096 x 1024
+    and 256^3, and the periodic cyclic-lines operator of `periodic-lines` at the same sizes."""
+    kw = dict(layout=amg.LAYOUT_SELL, **ALT_KW["alt 1+1"])
+
+    def split(dims, L):
+        def make():
+            crow, col, val, b = torch_split_anisotropy_nd(dims)
+            return amg.Multigrid.tensor_dev(crow, col, val, b, dims, L, **kw), b
+        return make
+
+    def cyclic(dims, eps, L):
+        def make():
+            crow, col, val, b = torch_scaled_periodic(dims, eps, 1)
+            return amg.Multigrid.tensor_periodic_dev(crow, col, val, b, dims, L, 1, cyclic_lines=1, **kw), b
+        return make
+    cases = {"split2": ("4096 x 1024 split-anisotropy 1e-3", split((4096, 1024), 9)),
+             "split3": ("256^3 split-anisotropy 1e-3", split((256, 256, 256), 7)),
+             "cyclic2": ("4096 x 1024 x periodic, cyclic lines", cyclic((4096, 1024), (1.0, 1e-2), 9)),
+             "cyclic3": ("256^3 x periodic, cyclic lines", cyclic((256, 256, 256), (1.0, 1e-2, 1e-2), 7))}
+    for key, (label, make) in cases.items():
+        if which in (None, key):
+            run_mixed_line(label, make)
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -1038,6 +1152,12 @@ elif len(sys.argv) > 1 and sys.argv[1] == "periodic-lines":
     amg.set_periodic_device_setup(1)  # the hierarchy on the device: the same solver, set up sooner
     run_periodic_lines((4096, 1024), (1.0, 1e-2), 9)
     run_periodic_lines((256, 256, 256), (1.0, 1e-2, 1e-2), 7)
+elif len(sys.argv) > 1 and sys.argv[1] == "mixed-line":
+    # profiles/mixed_line_config_bench.txt; an argument picks one case: split2 | split3 | cyclic2 | cyclic3
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    amg.set_periodic_device_setup(1)
+    amg.set_f32_lines(1)
+    mixed_line_cases(sys.argv[2] if len(sys.argv) > 2 else None)
 elif len(sys.argv) > 1 and sys.argv[1] == "periodic-setup":
     # profiles/periodic_setup.txt
     os.environ.setdefault("AMG_HIP_TIMING", "1")
