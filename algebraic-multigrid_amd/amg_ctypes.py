@@ -166,6 +166,7 @@ _SIGS = {
     "amg_hip_f32_line_subsweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "amg_hip_f32_line_factors": (C.c_int, [C.c_void_p, C.c_int32] + [C.POINTER(C.c_float)] * 3),
     "amg_hip_set_f32_lines": (None, [C.c_int32]),
+    "amg_hip_set_block_lines": (None, [C.c_int32]),
     "amg_hip_n_levels": (C.c_int32, [C.c_void_p]),
     "amg_hip_get_n_dofs": (C.c_int64, [C.c_void_p, C.c_int32]),
     "amg_hip_get_level_nnz": (C.c_int64, [C.c_void_p, C.c_int32]),
@@ -436,6 +437,22 @@ def f32_lines():
         yield
     finally:
         set_f32_lines(0)
+
+
+def set_block_lines(on):
+    """The block entry points accept line-smoother solvers (1) or refuse them (0, the default);
+    process-wide, read whenever a block entry point runs its checks."""
+    lib().amg_hip_set_block_lines(int(bool(on)))
+
+
+@contextlib.contextmanager
+def block_lines():
+    """with amg.block_lines(): ... -- set_block_lines(1) inside the block, 0 again after it."""
+    set_block_lines(1)
+    try:
+        yield
+    finally:
+        set_block_lines(0)
 
 
 def set_band_chain(on):

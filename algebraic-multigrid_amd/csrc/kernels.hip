@@ -7382,6 +7382,413 @@ hipError_t launch_line_seam_f32(int64_t n, int64_t s, int64_t m, const float* p,
   return line_seam_t<float>(n, s, m, p, coef, r, st);
 }
 
+// ---- K-LineBlock: the line smoothers on the panels of K-Block (kernels.hpp) ---------------------
+// Row-major n x KP panels (entry (i, j) at i * KP + j, a 64-bit index); the factor arrays are the
+// single-vector ones, indexed by row: the KP lanes of a row load the same factor words (served once)
+// and one contiguous 8 KP-byte segment of every panel.  Per (row, column) each kernel evaluates the
+// expressions of its single-vector kernel in the same order, so column j has that kernel's bits.
+//   block_line_seg_kernel       line_seg_kernel, lane = (segment, chain, column)
+//   block_line_sep_many_kernel  line_sep_many_kernel, lane = (chain, column): the dependent chain of
+//                               separators is walked once for the KP columns
+//   block_line_sep_few_kernel   line_sep_few_kernel, a workgroup per chain: lo and pv staged once, b
+//                               per column, KP lanes walk; the carries stay in their registers
+//   block_line_update_kernel    line_update_kernel, lane = (row, column)
+//   block_linex_fwd / _bwd      linex_kernel<LX_FWD / LX_BWD>, lane = (run, column): an x line has
+//                               stride KP in the panel, so the KP columns of a step are one segment
+//                               and the walk needs no transposition through LDS; the rows of the
+//                               next LINEXB_BATCH steps are loaded before this batch is walked
+//   block_seamx / _stride       seamx_kernel / seam_stride_kernel, lane = (line, column)
+namespace {
+__host__ __device__ constexpr int block_few_chunk_c(int kp) { return kp <= 4 ? LINE_FEW_CHUNK : 4 * LINE_FEW_CHUNK / kp; }
+
+template <int KP>
+__global__ __launch_bounds__(256) void block_line_seg_kernel(int64_t n, int64_t s, int64_t nch, int64_t nseg,
+                                                             const double* __restrict__ r,
+                                                             const double* __restrict__ dl,
+                                                             const double* __restrict__ ip,
+                                                             const double* __restrict__ cp, double* __restrict__ y) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nch * nseg * KP) return;
+  const int j = (int)(t % KP);
+  const int64_t q = t / KP;
+  const int64_t g = q / nch, c = q - g * nch;
+  const int64_t i0 = (g * LINE_SEG) * s + c;
+  double yv[LINE_INT];
+  double prev = 0.0;
+#pragma unroll
+  for (int k = 0; k < LINE_INT; ++k) {
+    const int64_t i = i0 + (int64_t)k * s;
+    if (i < n) prev = k > 0 ? (r[i * KP + j] - dl[i] * prev) * ip[i] : r[i * KP + j] * ip[i];
+    else prev = 0.0;
+    yv[k] = prev;
+  }
+  double nxt = 0.0;
+#pragma unroll
+  for (int k = LINE_INT - 1; k >= 0; --k) {
+    const int64_t i = i0 + (int64_t)k * s;
+    if (i < n) {
+      nxt = yv[k] - cp[i] * nxt;
+      y[i * KP + j] = nxt;
+    }
+  }
+}
+
+// line_sep_rhs of column j
+template <int KP>
+__device__ inline double block_line_sep_rhs(int64_t i, int j, int64_t n, int64_t s, const double* r, const double* dl,
+                                            const double* w, const double* y) {
+  double b = r[i * KP + j] - dl[i] * y[(i - s) * KP + j];
+  if (i + s < n) b = b - w[i] * y[(i + s) * KP + j];
+  return b;
+}
+template <int KP>
+__global__ __launch_bounds__(64) void block_line_sep_many_kernel(int64_t n, int64_t s, int64_t nch, const double* r,
+                                                                 const double* dl, const double* ip, const double* cp,
+                                                                 const double* v, const double* w, double* y) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nch * KP) return;
+  const int j = (int)(t % KP);
+  const int64_t c = t / KP;
+  const int64_t step = (int64_t)LINE_SEG * s;
+  const int64_t first = (int64_t)LINE_INT * s + c;
+  if (first >= n) return;
+  const int64_t nsep = (n - 1 - first) / step + 1;
+  double tv = 0.0;
+  for (int64_t g0 = 0; g0 < nsep; g0 += LINE_BATCH) {
+    double b[LINE_BATCH], lo[LINE_BATCH], pv[LINE_BATCH];
+#pragma unroll
+    for (int k = 0; k < LINE_BATCH; ++k) {
+      const int64_t i = first + (g0 + k) * step;
+      const bool on = g0 + k < nsep;
+      b[k] = on ? block_line_sep_rhs<KP>(i, j, n, s, r, dl, w, y) : 0.0;
+      lo[k] = on ? v[i] : 0.0;
+      pv[k] = on ? ip[i] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < LINE_BATCH; ++k) {
+      if (g0 + k < nsep) {
+        tv = (b[k] - lo[k] * tv) * pv[k];
+        y[(first + (g0 + k) * step) * KP + j] = tv;
+      }
+    }
+  }
+  double x = 0.0;
+  for (int64_t g1 = nsep; g1 > 0; g1 -= LINE_BATCH) {  // separators g1-1, g1-2, ...
+    double tt[LINE_BATCH], cc[LINE_BATCH];
+#pragma unroll
+    for (int k = 0; k < LINE_BATCH; ++k) {
+      const int64_t g = g1 - 1 - k;
+      const int64_t i = first + g * step;
+      tt[k] = g >= 0 ? y[i * KP + j] : 0.0;
+      cc[k] = g >= 0 ? cp[i] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < LINE_BATCH; ++k) {
+      const int64_t g = g1 - 1 - k;
+      if (g >= 0) {
+        x = tt[k] - cc[k] * x;
+        y[(first + g * step) * KP + j] = x;
+      }
+    }
+  }
+}
+// chunks of block_few_chunk_c(KP) separators: (KP + 2) doubles of LDS each, 48 KB at the most
+template <int KP>
+__global__ __launch_bounds__(256) void block_line_sep_few_kernel(int64_t n, int64_t s, const double* r,
+                                                                const double* dl, const double* ip, const double* cp,
+                                                                const double* v, const double* w, double* y) {
+  constexpr int CH = block_few_chunk_c(KP);
+  __shared__ double b[CH * KP], lo[CH], pv[CH];
+  const int tid = threadIdx.x;
+  const int64_t c = blockIdx.x;
+  const int64_t step = (int64_t)LINE_SEG * s;
+  const int64_t first = (int64_t)LINE_INT * s + c;
+  if (first >= n) return;  // the whole workgroup
+  const int64_t nsep = (n - 1 - first) / step + 1;
+  double carry = 0.0;  // lanes < KP: the recurrence of column tid, kept from chunk to chunk
+  for (int64_t g0 = 0; g0 < nsep; g0 += CH) {
+    const int m = (int)(nsep - g0 < CH ? nsep - g0 : CH);
+    for (int e = tid; e < m * KP; e += 256) {
+      const int g = e / KP, j = e % KP;
+      const int64_t i = first + (g0 + g) * step;
+      b[e] = block_line_sep_rhs<KP>(i, j, n, s, r, dl, w, y);
+      if (j == 0) {
+        lo[g] = v[i];
+        pv[g] = ip[i];
+      }
+    }
+    __syncthreads();
+    if (tid < KP) {
+      double t = carry;
+      for (int g = 0; g < m; ++g) {
+        t = (b[g * KP + tid] - lo[g] * t) * pv[g];
+        b[g * KP + tid] = t;
+      }
+      carry = t;
+    }
+    __syncthreads();
+    for (int e = tid; e < m * KP; e += 256) y[(first + (g0 + e / KP) * step) * KP + e % KP] = b[e];
+    __syncthreads();
+  }
+  carry = 0.0;
+  for (int64_t g1 = nsep; g1 > 0; g1 -= CH) {  // separators [g1 - m, g1)
+    const int m = (int)(g1 < CH ? g1 : CH);
+    const int64_t gb = g1 - m;
+    for (int e = tid; e < m * KP; e += 256) {
+      const int g = e / KP, j = e % KP;
+      const int64_t i = first + (gb + g) * step;
+      b[e] = y[i * KP + j];
+      if (j == 0) lo[g] = cp[i];
+    }
+    __syncthreads();
+    if (tid < KP) {
+      double x = carry;
+      for (int g = m - 1; g >= 0; --g) {
+        x = b[g * KP + tid] - lo[g] * x;
+        b[g * KP + tid] = x;
+      }
+      carry = x;
+    }
+    __syncthreads();
+    for (int e = tid; e < m * KP; e += 256) y[(first + (gb + e / KP) * step) * KP + e % KP] = b[e];
+    __syncthreads();
+  }
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void block_line_update_kernel(int64_t n, uint32_t s, const double* __restrict__ y,
+                                                               const double* __restrict__ v,
+                                                               const double* __restrict__ w, double omega,
+                                                               double* __restrict__ u) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * KP) return;
+  const int64_t i = e / KP;  // < 2^31: the row, not the panel index, goes through the 32-bit division
+  const int j = (int)(e % KP);
+  const uint32_t p = (uint32_t)i / s;
+  const uint32_t k = p % LINE_SEG;
+  double x = y[e];
+  if (k != LINE_INT) {
+    const int64_t before = i - ((int64_t)k + 1) * s;
+    const int64_t after = i + (int64_t)(LINE_INT - k) * s;
+    if (before >= 0) x = x - v[i] * y[before * KP + j];
+    if (after < n) x = x - w[i] * y[after * KP + j];
+  }
+  u[e] = u[e] + omega * x;
+}
+
+constexpr int LINEXB_BATCH = 8;
+// y_i = (r_i - dl_i y_(i-1)) ip_i over the rows [run len, run len + len) below n, in place
+template <int KP>
+__global__ __launch_bounds__(64) void block_linex_fwd_kernel(int64_t n, int64_t len, int64_t nruns, double* r,
+                                                             const double* __restrict__ dl,
+                                                             const double* __restrict__ ip) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t run = t / KP;
+  const int j = (int)(t % KP);
+  if (run >= nruns) return;
+  const int64_t i0 = run * len;
+  const int64_t cnt = n - i0 < len ? n - i0 : len;
+  double ra[LINEXB_BATCH], rb[LINEXB_BATCH], rc[LINEXB_BATCH];
+  auto fetch = [&](int64_t k0) {
+#pragma unroll
+    for (int q = 0; q < LINEXB_BATCH; ++q) {
+      const int64_t i = i0 + k0 + q;
+      const bool on = k0 + q < cnt;
+      ra[q] = on ? r[i * KP + j] : 0.0;
+      rb[q] = on ? dl[i] : 0.0;
+      rc[q] = on ? ip[i] : 0.0;
+    }
+  };
+  double carry = 0.0;
+  fetch(0);
+  for (int64_t k0 = 0; k0 < cnt; k0 += LINEXB_BATCH) {
+    double a[LINEXB_BATCH], b[LINEXB_BATCH], c[LINEXB_BATCH];
+#pragma unroll
+    for (int q = 0; q < LINEXB_BATCH; ++q) {
+      a[q] = ra[q];
+      b[q] = rb[q];
+      c[q] = rc[q];
+    }
+    if (k0 + LINEXB_BATCH < cnt) fetch(k0 + LINEXB_BATCH);
+#pragma unroll
+    for (int q = 0; q < LINEXB_BATCH; ++q) {
+      if (k0 + q < cnt) {
+        carry = (a[q] - b[q] * carry) * c[q];
+        r[(i0 + k0 + q) * KP + j] = carry;
+      }
+    }
+  }
+}
+// x_i = y_i - cp_i x_(i+1); u_i += omega x_i, the run's rows descending
+template <int KP>
+__global__ __launch_bounds__(64) void block_linex_bwd_kernel(int64_t n, int64_t len, int64_t nruns,
+                                                             const double* __restrict__ y,
+                                                             const double* __restrict__ cp, double* u, double omega) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t run = t / KP;
+  const int j = (int)(t % KP);
+  if (run >= nruns) return;
+  const int64_t i0 = run * len;
+  const int64_t cnt = n - i0 < len ? n - i0 : len;
+  double ra[LINEXB_BATCH], rb[LINEXB_BATCH], rc[LINEXB_BATCH];
+  auto fetch = [&](int64_t k0) {
+#pragma unroll
+    for (int q = 0; q < LINEXB_BATCH; ++q) {
+      const int64_t i = i0 + k0 + q;
+      const bool on = k0 + q < cnt;
+      ra[q] = on ? y[i * KP + j] : 0.0;
+      rb[q] = on ? cp[i] : 0.0;
+      rc[q] = on ? u[i * KP + j] : 0.0;
+    }
+  };
+  double carry = 0.0;
+  const int64_t last = (cnt - 1) / LINEXB_BATCH * LINEXB_BATCH;  // first row of the last batch (cnt >= 1)
+  fetch(last);
+  for (int64_t k0 = last; k0 >= 0; k0 -= LINEXB_BATCH) {
+    double a[LINEXB_BATCH], b[LINEXB_BATCH], c[LINEXB_BATCH];
+#pragma unroll
+    for (int q = 0; q < LINEXB_BATCH; ++q) {
+      a[q] = ra[q];
+      b[q] = rb[q];
+      c[q] = rc[q];
+    }
+    if (k0 > 0) fetch(k0 - LINEXB_BATCH);
+#pragma unroll
+    for (int q = LINEXB_BATCH - 1; q >= 0; --q) {
+      if (k0 + q < cnt) {
+        carry = a[q] - b[q] * carry;
+        u[(i0 + k0 + q) * KP + j] = c[q] + omega * carry;
+      }
+    }
+  }
+}
+
+// x lines: the W partial sums of seamx_kernel<W> (columns l, l + W, ... ascending) formed by the one
+// lane, then its butterfly as seen from lane 0: off = W / 2 .. 1, part[l] += part[l + off]
+template <int W>
+__global__ __launch_bounds__(256) void block_seamx_kernel(int64_t nlines, int64_t m, int kp,
+                                                          const double* __restrict__ p,
+                                                          const double* __restrict__ coef, double* r) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t line = t / kp;
+  const int j = (int)(t % kp);
+  if (line >= nlines) return;
+  const int64_t i0 = line * m;
+  double part[W];
+#pragma unroll
+  for (int l = 0; l < W; ++l) part[l] = 0.0;
+  for (int64_t c0 = 0; c0 < m; c0 += W) {
+#pragma unroll
+    for (int l = 0; l < W; ++l)
+      if (c0 + l < m) part[l] = part[l] + p[i0 + c0 + l] * r[(i0 + c0 + l) * kp + j];
+  }
+#pragma unroll
+  for (int off = W / 2; off >= 1; off >>= 1) {
+#pragma unroll
+    for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
+  }
+  const double fac = part[0] / coef[line];
+  const int64_t e0 = i0 * kp + j, e1 = (i0 + m - 1) * kp + j;
+  r[e0] = r[e0] - fac * coef[nlines + line];
+  r[e1] = r[e1] - fac * coef[2 * nlines + line];
+}
+__global__ __launch_bounds__(256) void block_seam_stride_kernel(int64_t nlines, int64_t s, int64_t m, int kp,
+                                                                const double* __restrict__ p,
+                                                                const double* __restrict__ coef, double* r) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t line = t / kp;
+  const int j = (int)(t % kp);
+  if (line >= nlines) return;
+  const int64_t b = line / s;
+  const int64_t i0 = b * s * m + (line - b * s);
+  double acc = 0.0;
+  for (int64_t k0 = 0; k0 < m; k0 += SEAM_WALK) {
+    double pv[SEAM_WALK], rv[SEAM_WALK];
+#pragma unroll
+    for (int q = 0; q < SEAM_WALK; ++q) {
+      const bool on = k0 + q < m;
+      pv[q] = on ? p[i0 + (k0 + q) * s] : 0.0;
+      rv[q] = on ? r[(i0 + (k0 + q) * s) * kp + j] : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < SEAM_WALK; ++q)
+      if (k0 + q < m) acc = acc + pv[q] * rv[q];
+  }
+  const double fac = acc / coef[line];
+  const int64_t e0 = i0 * kp + j, e1 = (i0 + (m - 1) * s) * kp + j;
+  r[e0] = r[e0] - fac * coef[nlines + line];
+  r[e1] = r[e1] - fac * coef[2 * nlines + line];
+}
+inline bool block_kp_ok(int kp) { return kp == 1 || kp == 2 || kp == 4 || kp == 8 || kp == 16; }
+// CALL(KP) with the pitch as a constant
+#define AMG_BLOCK_KP(kp, CALL) \
+  switch (kp) {                \
+    case 1: CALL(1); break;    \
+    case 2: CALL(2); break;    \
+    case 4: CALL(4); break;    \
+    case 8: CALL(8); break;    \
+    default: CALL(16); break;  \
+  }
+}  // namespace
+
+int block_line_few_chunk(int kp) { return block_few_chunk_c(kp); }
+
+hipError_t launch_block_line_solve(int kp, const LineRef& L, const double* r, double* y, double* u, double omega,
+                                   hipStream_t st) {
+  const int64_t n = L.n, s = L.s;
+  if (!block_kp_ok(kp) || n <= 0 || s < 1 || s > n || n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+  const int64_t nch = line_chains(n, s), nseg = line_segments(n, s);
+  const bool sep = (int64_t)LINE_INT * s < n, few = line_few_chains(s);
+#define AMG_BLOCK_LINE(KP)                                                                                           \
+  hipLaunchKernelGGL(block_line_seg_kernel<KP>, line_grid(nch * nseg * KP), dim3(256), 0, st, n, s, nch, nseg, r,    \
+                     L.dl, L.ip, L.cp, y);                                                                           \
+  if (sep && few)                                                                                                    \
+    hipLaunchKernelGGL(block_line_sep_few_kernel<KP>, dim3((unsigned)nch), dim3(256), 0, st, n, s, r, L.dl, L.ip,    \
+                       L.cp, L.v, L.w, y);                                                                           \
+  else if (sep)                                                                                                      \
+    hipLaunchKernelGGL(block_line_sep_many_kernel<KP>, line_grid(nch * KP, 64), dim3(64), 0, st, n, s, nch, r, L.dl, \
+                       L.ip, L.cp, L.v, L.w, y);                                                                     \
+  hipLaunchKernelGGL(block_line_update_kernel<KP>, line_grid(n * KP), dim3(256), 0, st, n, (uint32_t)s,              \
+                     (const double*)y, L.v, L.w, omega, u)
+  AMG_BLOCK_KP(kp, AMG_BLOCK_LINE)
+#undef AMG_BLOCK_LINE
+  return hipGetLastError();
+}
+
+hipError_t launch_block_linex_solve(int kp, const LineXRef& L, double* r, double* u, double omega, hipStream_t st) {
+  if (!block_kp_ok(kp) || !linex_ok(L)) return hipErrorInvalidValue;
+  const int64_t n = L.n, len = linex_run(L.nx), nruns = (n + len - 1) / len;
+  const dim3 grid = line_grid(nruns * kp, 64);
+#define AMG_BLOCK_LINEX(KP)                                                                                      \
+  hipLaunchKernelGGL(block_linex_fwd_kernel<KP>, grid, dim3(64), 0, st, n, len, nruns, r, L.dl, L.ip);           \
+  hipLaunchKernelGGL(block_linex_bwd_kernel<KP>, grid, dim3(64), 0, st, n, len, nruns, (const double*)r, L.cp, u, \
+                     omega)
+  AMG_BLOCK_KP(kp, AMG_BLOCK_LINEX)
+#undef AMG_BLOCK_LINEX
+  return hipGetLastError();
+}
+
+hipError_t launch_block_line_seam(int kp, const SeamRef& S, double* r, hipStream_t st) {
+  const int64_t n = S.n, s = S.s, m = S.m;
+  if (!block_kp_ok(kp) || !seam_ok(n, s, m)) return hipErrorInvalidValue;
+  const int64_t nlines = n / m;
+  const dim3 grid = line_grid(nlines * kp);
+  if (s > 1) {
+    hipLaunchKernelGGL(block_seam_stride_kernel, grid, dim3(256), 0, st, nlines, s, m, kp, S.p, S.coef, r);
+    return hipGetLastError();
+  }
+#define AMG_BLOCK_SEAMX(W) \
+  hipLaunchKernelGGL(block_seamx_kernel<W>, grid, dim3(256), 0, st, nlines, m, kp, S.p, S.coef, r)
+  if (m <= 4) AMG_BLOCK_SEAMX(4);
+  else if (m <= 8) AMG_BLOCK_SEAMX(8);
+  else if (m <= 16) AMG_BLOCK_SEAMX(16);
+  else if (m <= 32) AMG_BLOCK_SEAMX(32);
+  else AMG_BLOCK_SEAMX(64);
+#undef AMG_BLOCK_SEAMX
+  return hipGetLastError();
+}
+#undef AMG_BLOCK_KP
+
 // ------------------------------------------------------------------ K-F32 ----
 // The single-precision preconditioner (solver.cpp: "fp32 cycle"): the V-cycle's row kernels on
 // float vectors and float matrix values.  The outer PCG stays in double; nothing here is bitwise

@@ -603,6 +603,22 @@ hipError_t launch_block_pcg_update_xr(int kp, int64_t n, const double* num, cons
 hipError_t launch_block_pcg_update_p(int kp, int64_t n, const double* num, const double* den, const int32_t* act,
                                      double* p, const double* z, hipStream_t st);
 
+// K-LineBlock (kernels.hip): K-Line, K-LineX and K-LineSeam on the panels of K-Block.  The factors are
+// the single-vector arrays (one entry per row, read once for the kp columns); r, y, u are n x kp
+// panels and every panel index is 64-bit (n < 2^31, n kp may pass it).  Per (row, column) the
+// expressions and their order are the single-vector kernels', so column j has their bits on column j.
+// u += omega T^-1 r: the three stages of launch_line_solve (lane = (segment, chain, column); (chain,
+// column) or a workgroup per chain with kp walking lanes where line_few_chains(s); (row, column))
+hipError_t launch_block_line_solve(int kp, const LineRef& L, const double* r, double* y, double* u, double omega,
+                                   hipStream_t st);
+int block_line_few_chunk(int kp);  // separators per LDS chunk of the few-chains walk at pitch kp
+// x lines (stride kp in the panel): forward in place in r, then backward and update; lane = (run,
+// column) walks linex_run(nx) rows straight from memory, 64 / kp runs to a wave, no LDS
+hipError_t launch_block_linex_solve(int kp, const LineXRef& L, double* r, double* u, double omega, hipStream_t st);
+// launch_line_seam per column: lane = (line, column); the x lines' sum in the W partials and the tree
+// of seamx_kernel for the width W that line_seam_t picks for m
+hipError_t launch_block_line_seam(int kp, const SeamRef& S, double* r, hipStream_t st);
+
 // K-F32 (kernels.hip): the row kernels and transfers of the single-precision preconditioner.  mode:
 // CSR_RESID, CSR_JACOBI or cheb_kernel_mode(first, last) (omega = the step's beta, dvec = its d);
 // launch_csr_f32 also takes CSR_SPMV and CSR_SPMV_ADD (f may be out).  soff / scol (idx16 bit 0:

@@ -1428,6 +1428,7 @@ struct BlockLevel {
   const DevCsr* rows = nullptr;    // rows of A (residual, Chebyshev, rss, PCG)
   const DevCsr* cols = nullptr;    // columns of A walked as rows (Jacobi); = rows when symmetric
   DevMem U, F, R, T, D;            // solution, right-hand side, residual, ping-pong, Chebyshev d
+  DevMem Y;                        // K-Line's y panel (line smoothers only)
 };
 constexpr int BLOCK_K_MAX = 16;
 struct Block {
@@ -1522,6 +1523,13 @@ int g_periodic_device_setup = [] {
 // line-smoother solvers ("Single-precision preconditioner").
 int g_f32_lines = [] {
   const char* e = std::getenv("AMG_HIP_F32_LINES");
+  return (e && *e == '1') ? 1 : 0;
+}();
+// amg_hip_set_block_lines / AMG_HIP_BLOCK_LINES=1: the block entry points accept the line smoothers
+// (K-LineBlock).  0 by default only because earlier tests pin their refusal on line-smoother solvers
+// ("Block cycle").
+int g_block_lines = [] {
+  const char* e = std::getenv("AMG_HIP_BLOCK_LINES");
   return (e && *e == '1') ? 1 : 0;
 }();
 int64_t g_patch_min_rows = 1000000;  // amg_hip_set_patch_min_rows (level 4 of 4096^2 has 1 048 575 rows)
@@ -3764,10 +3772,13 @@ int block_kp(int32_t k) {
 amg_hip_status block_supported(amg_hip_solver* s) {
   if (s->opt.window)
     return fail(AMG_HIP_EUNSUPPORTED, "block cycles: a window solver (opt.window) is not supported");
-  if (s->opt.smoother != AMG_HIP_SM_JACOBI && s->opt.smoother != AMG_HIP_SM_CHEBYSHEV)
-    return fail(AMG_HIP_EUNSUPPORTED, std::string("block cycles: the smoother ") +
-                                          block_smoother_name(s->opt.smoother) +
-                                          " is not supported (true Jacobi and Chebyshev are)");
+  const bool line = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT;
+  if (s->opt.smoother != AMG_HIP_SM_JACOBI && s->opt.smoother != AMG_HIP_SM_CHEBYSHEV && !(g_block_lines && line))
+    return fail(AMG_HIP_EUNSUPPORTED,
+                std::string("block cycles: the smoother ") + block_smoother_name(s->opt.smoother) +
+                    (g_block_lines ? " is not supported (true Jacobi, Chebyshev, AMG_HIP_SM_LINE_JACOBI and "
+                                     "AMG_HIP_SM_LINE_ALT are)"
+                                   : " is not supported (true Jacobi and Chebyshev are)"));
   return set_device(s);
 }
 bool has_exact_zero(const Sparse& M) {
@@ -3823,6 +3834,7 @@ amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
   if (kp <= B.kp_alloc) return AMG_HIP_OK;
   B.reset_graphs();  // their pointers are about to change
   const bool cheb = s->opt.smoother == AMG_HIP_SM_CHEBYSHEV;
+  const bool line = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT;
   for (int l = 0; l < nl; ++l) {
     const size_t bytes = sizeof(double) * (size_t)s->lv[l].n * (size_t)kp;
     BlockLevel& Q = B.lv[(size_t)l];
@@ -3832,6 +3844,7 @@ amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
       HIP_TRY(Q.R.alloc(bytes));
       HIP_TRY(Q.T.alloc(bytes));
       if (cheb) HIP_TRY(Q.D.alloc(bytes));
+      if (line && l + 1 < nl) HIP_TRY(Q.Y.alloc(bytes));
     }
   }
   const size_t cb = sizeof(double) * (size_t)s->lv[nl - 1].n * (size_t)kp;
@@ -3857,12 +3870,62 @@ amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
     if (!dry) HIP_TRY(expr);      \
   } while (0)
 
-// the smoothing of one level (enqueue_smooth's plain launches): U -> T -> U ..., home after an odd count
-amg_hip_status enqueue_block_smooth(amg_hip_solver* s, int l, int kp, bool dry) {
+// K-Line on the panels (LineOnDev::solve_bytes with the factors counted once: dl, ip, cp, v, w of every
+// row; per column 40 B on an interior and 56 B on a separator row)
+void bacct_line(amg_hip_solver* s, const LineOnDev& D) {
+  const int64_t sep = D.separators();
+  s->bacct(40.0 * (double)D.n, 40.0 * (double)(D.n - sep) + 56.0 * (double)sep);
+}
+// sub-sweep d of AMG_HIP_SM_LINE_ALT on the panels (launch_alt_subsweep after its residual): T holds
+// the residual, U is updated in place
+amg_hip_status enqueue_block_alt_solve(amg_hip_solver* s, const AltOnDev& D, int d, int kp, BlockLevel& Q, bool dry) {
+  hipStream_t st = s->stream;
+  double* r = Q.T.as<double>();
+  double* u = Q.U.as<double>();
+  if (D.n_dir > 0 && D.cyc[d]) {
+    BLK(launch_block_line_seam(kp, D.seam(d), r, st));
+    // p, then den, gamma, beta of every line once; r in and the two ends of r out per column
+    const double lines = (double)(D.n / D.len[d]);
+    s->bacct(8.0 * (double)D.n + 24.0 * lines, 8.0 * (double)D.n + 16.0 * lines);
+  }
+  if (D.n_dir > 0 && D.axis[d] == 0) {
+    BLK(launch_block_linex_solve(kp, D.xref(), r, u, s->opt.omega, st));
+    s->bacct(24.0 * (double)D.n, 40.0 * (double)D.n);  // dl, ip, cp; r, y, y, u, u
+    return AMG_HIP_OK;
+  }
+  const LineOnDev& Y = D.yz[D.n_dir == 0 ? 0 : D.axis[d] - 1];
+  BLK(launch_block_line_solve(kp, Y.ref(), r, Q.Y.as<double>(), u, s->opt.omega, st));
+  bacct_line(s, Y);
+  return AMG_HIP_OK;
+}
+
+// the smoothing of one level (enqueue_smooth's plain launches): U -> T -> U ..., home after an odd count;
+// the line smoothers update U in place (reverse: the up-leg, AMG_HIP_SM_LINE_ALT's directions descend)
+amg_hip_status enqueue_block_smooth(amg_hip_solver* s, int l, int kp, bool dry, bool reverse) {
   Level& L = s->lv[l];
   BlockLevel& Q = s->blk.lv[(size_t)l];
   hipStream_t st = s->stream;
   const double n = (double)L.n;
+  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
+    const DevCsr& A = *Q.rows;
+    const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
+    const int nd = alt ? std::max(L.alt.n_dir, 1) : 1;
+    for (int it = 0; it < s->opt.smoother_iters; ++it)
+      for (int q = 0; q < nd; ++q) {
+        BLK(launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
+                             Q.T.as<double>(), 1.0, st));
+        s->bacct(csr_bytes(A), 24.0 * n);  // matrix; u, f, r
+        if (alt) {
+          const amg_hip_status r = enqueue_block_alt_solve(s, L.alt, reverse ? nd - 1 - q : q, kp, Q, dry);
+          if (r != AMG_HIP_OK) return r;
+        } else {
+          BLK(launch_block_line_solve(kp, L.line.ref(), Q.T.as<double>(), Q.Y.as<double>(), Q.U.as<double>(),
+                                      s->opt.omega, st));
+          bacct_line(s, L.line);
+        }
+      }
+    return AMG_HIP_OK;
+  }
   double* a = Q.U.as<double>();
   double* b = Q.T.as<double>();
   int64_t passes = 0;
@@ -3914,7 +3977,7 @@ amg_hip_status enqueue_block_vcycle(amg_hip_solver* s, int kp, bool dry) {
     Level& C = s->lv[l + 1];
     BlockLevel& Q = B.lv[(size_t)l];
     BlockLevel& QC = B.lv[(size_t)l + 1];
-    if ((r = enqueue_block_smooth(s, l, kp, dry)) != AMG_HIP_OK) return r;  // :268
+    if ((r = enqueue_block_smooth(s, l, kp, dry, false)) != AMG_HIP_OK) return r;  // :268
     const DevCsr& A = *Q.rows;                                               // :272-274
     BLK(launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
                          Q.R.as<double>(), 1.0, st));
@@ -3985,7 +4048,7 @@ amg_hip_status enqueue_block_vcycle(amg_hip_solver* s, int kp, bool dry) {
                            Q.U.as<double>(), Q.U.as<double>(), 1.0, st));
       s->bacct(csr_bytes(P), 8.0 * (double)C.n + 16.0 * (double)L.n);
     }
-    if ((r = enqueue_block_smooth(s, l, kp, dry)) != AMG_HIP_OK) return r;  // :300
+    if ((r = enqueue_block_smooth(s, l, kp, dry, true)) != AMG_HIP_OK) return r;  // :300
   }
   return AMG_HIP_OK;
 }
@@ -4439,6 +4502,7 @@ void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
 void amg_hip_set_periodic_device_setup(int32_t on) { g_periodic_device_setup = on ? 1 : 0; }
 void amg_hip_set_f32_lines(int32_t on) { g_f32_lines = on ? 1 : 0; }
+void amg_hip_set_block_lines(int32_t on) { g_block_lines = on ? 1 : 0; }
 void amg_hip_set_patch_min_rows(int64_t rows) { g_patch_min_rows = rows < 0 ? INT64_MAX : rows; }
 
 void amg_hip_set_default_layout(int32_t layout) {

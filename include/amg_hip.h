@@ -79,9 +79,10 @@ typedef enum {
                                    refuses with AMG_HIP_EINVAL (level and row in the
                                    message) a pivot that is zero or not finite.
                                    T is symmetric when A is, so the V-cycle stays a
-                                   valid PCG preconditioner.  Window solvers, slab
-                                   sharding and the block entry points refuse it
-                                   (AMG_HIP_EUNSUPPORTED).                       */
+                                   valid PCG preconditioner.  Window solvers and slab
+                                   sharding refuse it (AMG_HIP_EUNSUPPORTED); the
+                                   block entry points do too unless
+                                   amg_hip_set_block_lines(1) is in force.       */
   AMG_HIP_SM_LINE_ALT = 7       /* alternating-direction line relaxation, only on
                                    solvers that know their level grids
                                    (amg_hip_create_tensor, _tensor_dev,
@@ -108,7 +109,8 @@ typedef enum {
                                    (0, 2), 0.8 recommended; pivots as for
                                    AMG_HIP_SM_LINE_JACOBI (level, direction and row
                                    in the message).  Refused where that one is
-                                   (AMG_HIP_EUNSUPPORTED).                       */
+                                   (AMG_HIP_EUNSUPPORTED), and accepted by the block
+                                   entry points under the same switch.           */
 } amg_hip_smoother;
 
 /* Device layout of the level matrices (results are bit-identical in all).    */
@@ -305,6 +307,15 @@ void amg_hip_set_periodic_device_setup(int32_t on);
  * Off: those solvers are refused as before (AMG_HIP_EUNSUPPORTED).  No double entry point is touched
  * either way.                                                                                     */
 void amg_hip_set_f32_lines(int32_t on);
+
+/* The block entry points (amg_hip_block_vcycles, _rss, _pcg, _must_move) accept solvers smoothed with
+ * AMG_HIP_SM_LINE_JACOBI and AMG_HIP_SM_LINE_ALT, cyclic_lines included (K-LineBlock: the line solve
+ * kernels on row-major panels, reading the solver's own double factors once for all columns; column j
+ * keeps the bits of the single-vector path).  Process-wide, read whenever a block entry point runs its
+ * checks; default 0 (AMG_HIP_BLOCK_LINES=1 in the environment turns it on).  Off: those solvers are
+ * refused as before (AMG_HIP_EUNSUPPORTED).  No single-vector and no float entry point is touched
+ * either way.                                                                                      */
+void amg_hip_set_block_lines(int32_t on);
 
 /* Number of usable HIP devices (0 when none; never fails). */
 int amg_hip_device_count(void);
@@ -805,9 +816,12 @@ amg_hip_status amg_hip_rss(amg_hip_solver* s, double* out);
  * vectors are not touched.  Argument checks, in this order: null pointers, k outside 1..16,
  * n_cycles < 0, a misaligned pointer, bad rtol / max_iters -> AMG_HIP_EINVAL; a window solver or a
  * smoother other than AMG_HIP_SM_JACOBI / AMG_HIP_SM_CHEBYSHEV -> AMG_HIP_EUNSUPPORTED; then the
- * device (a host_only solver fails there).  The first call builds plain CSR copies of the level
+ * device (a host_only solver fails there).  With amg_hip_set_block_lines(1) the smoother check also
+ * accepts AMG_HIP_SM_LINE_JACOBI and AMG_HIP_SM_LINE_ALT (cyclic_lines included); every other check
+ * and its place in the order stay.  The first call builds plain CSR copies of the level
  * matrices that are not CSR already and n_l x kp panels per level (kp = k rounded up to a power
- * of two); with use_graph one captured graph per kp.                                          */
+ * of two; the line smoothers take one more panel per level); with use_graph one captured graph per
+ * kp.                                                                                          */
 amg_hip_status amg_hip_block_vcycles(amg_hip_solver* s, int32_t k, const double* F, double* U,
                                      int32_t n_cycles);           /* U in/out: n_cycles V-cycles */
 amg_hip_status amg_hip_block_rss(amg_hip_solver* s, int32_t k, const double* F, const double* U,

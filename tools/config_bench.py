@@ -20,8 +20,11 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py mixed-line [split2|split3|cyclic2|cyclic3]  amg_hip_pcg and amg_hip_pcg_mixed alternating on AMG_HIP_SM_LINE_ALT solvers (amg_hip_set_f32_lines): split-anisotropy through tensor_dev and the periodic-lines operator with cyclic lines, 4096 x 1024 and 256^3
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
+       config_bench.py block-line [jacobi|split2|split3|cyclic2]   the line smoothers through the block entry points (amg_hip_set_block_lines) and the single-vector path alternating, k = 1..16: cycles and PCG to 1e-8
+       config_bench.py block-line8 jacobi|split2|split3|cyclic2    one block-line case at k = 8, cycles only (kernel traces)
 smoother: spgs | jacobi | multicolor | cheb (degree 2, 1+1) | cheb3 (degree 3, 1+1) | line (omega 0.7, 1+1).  Setup runs on the device (amg_hip_create_poisson);
 smoothers that need host structures fall back to the host path inside it."""
+import ctypes
 import os
 import sys
 import time
@@ -1054,9 +1057,118 @@ def run_block(label, mk, cycles=10, reps=3, ks=(1, 2, 4, 8, 16)):
     mg.close()
 
 
+def run_block_line(label, make, cycles=4, reps=3, ks=(1, 2, 4, 8, 16), rtol=1e-8, pcg=True):
+    """A line-smoother solver made by make() (-> solver, level-0 right-hand side on the GPU) through the block
+    entry points (amg_hip_set_block_lines) and through the single-vector path, alternating in one run, best of
+    `reps`, per k: right-hand-side cycles per second (block_vcycles against vcycle) and right-hand-side solves
+    per second to `rtol` by PCG from x = 0 (block_pcg on k copies of b scaled by 1 .. k against pcg on b), the
+    block cycle's must-move bytes over its time as a share of 8 TB/s."""
+    import torch
+    t0 = time.perf_counter()
+    mg, b = make()
+    mg.sync()
+    n0 = mg.get_n_dofs(0)
+    print(f"block-line {label}: setup {time.perf_counter() - t0:.2f} s, {mg.n_levels} levels, {n0} dofs, level-0 "
+          f"layout {mg.level_layout(0)}", flush=True)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(1)
+    for k in ks:
+        U = torch.randn((n0, k), generator=g, device="cuda", dtype=torch.float64)
+        F = torch.randn((n0, k), generator=g, device="cuda", dtype=torch.float64)
+        B = (b[:, None] * torch.arange(1, k + 1, device="cuda", dtype=torch.float64)[None, :]).contiguous()
+        X = torch.zeros_like(B)
+        mg.block_vcycles(U, F, n=2)   # CSR copies, panels, captured graph
+        mg.vcycle(2)
+        torch.cuda.synchronize()
+        tb, ts, pb, ps = [], [], [], []
+        itb = its = relb = rels = None
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            mg.block_vcycles(U, F, n=cycles)
+            torch.cuda.synchronize()
+            tb.append((time.perf_counter() - t0) / cycles)
+            t0 = time.perf_counter()
+            mg.vcycle(cycles)
+            mg.sync()
+            ts.append((time.perf_counter() - t0) / cycles)
+            if not pcg:
+                continue
+            X.zero_()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, itb, relb = mg.block_pcg(B, X, rtol=rtol, max_iters=300)
+            torch.cuda.synchronize()
+            pb.append(time.perf_counter() - t0)
+            mg.copy_vec_dev(0, "f", b.data_ptr(), to_solver=True)
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            it1, rel1 = ctypes.c_int64(0), ctypes.c_double(0)   # amg_hip_pcg itself: the solution stays on the device
+            assert amg.lib().amg_hip_pcg(mg._h, rtol, 300, ctypes.byref(it1), ctypes.byref(rel1)) == 0
+            mg.sync()
+            ps.append(time.perf_counter() - t0)
+            its, rels = it1.value, rel1.value
+        blk, sgl = min(tb), min(ts)
+        mm = mg.block_must_move(k)
+        line = (f"  k={k:2d}: {blk*1e3:8.3f} ms/block cycle = {k/blk:8.1f} RHS-cycles/s | single {sgl*1e3:8.3f} ms = "
+                f"{1/sgl:7.1f} cycles/s | block/single {(k/blk)*sgl:5.2f}x | must-move {mm/1e6:9.1f} MB = "
+                f"{mm/blk/8e12*100:5.1f} % of 8 TB/s")
+        if pcg:
+            line += (f" | PCG to {rtol:g}: block {max(itb)} iterations {min(pb)*1e3:8.2f} ms = {k/min(pb):7.1f} RHS-solves/s"
+                     f" (worst relres {max(relb):.1e}) | single {its} iterations {min(ps)*1e3:8.2f} ms = "
+                     f"{1/min(ps):6.1f} solves/s (relres {rels:.1e}) | block/single {(k/min(pb))*min(ps):5.2f}x")
+        print(line, flush=True)
+        del U, F, B, X
+    mg.close()
+
+
+def block_line_cases(which=None, **kw):
+    """profiles/block_line_config_bench.txt: AMG_HIP_SM_LINE_JACOBI 1+1 omega 0.7 on poisson(4096, 16);
+    AMG_HIP_SM_LINE_ALT 1+1 omega 0.8 on the split-anisotropy operator (1e-3) at 4096 x 1024 / 9 levels and
+    256^3 / 7 levels; the 4096 x 1024 cyclic-lines operator of `periodic-lines` (x periodic)."""
+    import torch
+    alt = ALT_KW["alt 1+1"]
+
+    def poisson():
+        mg = amg.Multigrid.poisson(4096, 16, **KW["line"])
+        b = torch.empty(mg.get_n_dofs(0), dtype=torch.float64, device="cuda")
+        mg.copy_vec_dev(0, "f", b.data_ptr(), to_solver=False)
+        mg.sync()
+        return mg, b
+
+    def split(dims, L):
+        def make():
+            crow, col, val, b = torch_split_anisotropy_nd(dims)
+            return amg.Multigrid.tensor_dev(crow, col, val, b, dims, L, **alt), b
+        return make
+
+    def cyclic(dims, eps, L):
+        def make():
+            crow, col, val, b = torch_scaled_periodic(dims, eps, 1)
+            return amg.Multigrid.tensor_periodic_dev(crow, col, val, b, dims, L, 1, cyclic_lines=1, **alt), b
+        return make
+    cases = {"jacobi": ("poisson(4096, 16) line Jacobi 1+1 omega 0.7", poisson),
+             "split2": ("4096 x 1024 / 9 split-anisotropy 1e-3, alternating lines 1+1 omega 0.8", split((4096, 1024), 9)),
+             "split3": ("256^3 / 7 split-anisotropy 1e-3, alternating lines 1+1 omega 0.8", split((256, 256, 256), 7)),
+             "cyclic2": ("4096 x 1024 / 9 x periodic, cyclic lines, alternating lines 1+1 omega 0.8",
+                         cyclic((4096, 1024), (1.0, 1e-2), 9))}
+    for key, (label, make) in cases.items():
+        if which in (None, key):
+            run_block_line(label, make, **kw)
+
+
 if len(sys.argv) > 1 and sys.argv[1].startswith("block"):
     import torch  # noqa: F401  (before the library: torch needs its own HIP runtime, INTEGRATION.md section 2)
-if len(sys.argv) > 1 and sys.argv[1] == "block":
+if len(sys.argv) > 1 and sys.argv[1] == "block-line":
+    # profiles/block_line_config_bench.txt; an argument picks one case: jacobi | split2 | split3 | cyclic2
+    amg.set_periodic_device_setup(1)
+    amg.set_block_lines(1)
+    block_line_cases(sys.argv[2] if len(sys.argv) > 2 else None)
+elif len(sys.argv) > 2 and sys.argv[1] == "block-line8":   # one case at k = 8, cycles only (kernel traces)
+    amg.set_periodic_device_setup(1)
+    amg.set_block_lines(1)
+    block_line_cases(sys.argv[2], reps=1, ks=(8,), pcg=False)
+elif len(sys.argv) > 1 and sys.argv[1] == "block":
     def rs(sm):
         cp, ri, v = amg.laplacian(1024)
         return lambda: amg.Multigrid.ruge_stueben(cp, ri, v, amg.rhs(1024), 25, 0.25, 500, **KW[sm])
