@@ -1496,10 +1496,14 @@ struct PatchR { double a; int32_t loff, ok; };  // value, LDS offset, slot in us
 struct PatchCells {
   int cell0, row0, lj0, li;
   double f[PATCH_K];
-  uint32_t ty[PATCH_K];     // row type, clamped to the all-absent table row `ntypes`
+  uint32_t ty[PATCH_K / 4]; // row types, a byte each, clamped to the all-absent table row `ntypes`
   bool live[PATCH_K];       // row inside the matrix
   bool uniform;             // every cell of the wave has the type tu (then the table comes
   uint32_t tu;              // through scalar loads instead of per-lane LDS reads)
+  bool flagged;             // the tile's flag says so for the whole workgroup: ty[] is not filled in
+  __device__ __forceinline__ uint32_t type(int k) const {
+    return flagged ? tu : (ty[k >> 2] >> (8 * (k & 3))) & 255u;
+  }
 };
 
 // The table of ONE row type held in scalar registers (the wave-uniform fast path: in the
@@ -1702,7 +1706,7 @@ __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int nty
 #pragma unroll
     for (int k = 0; k < PATCH_K; ++k)
       res[k] = patch_eval<UN, RESID>(buf, pc.cell0 + k * PATCH_EC,
-                                     did[k] ? pc.ty[k] : (uint32_t)ntypes, tabJ, tabR, pc.f[k], omega);
+                                     did[k] ? pc.type(k) : (uint32_t)ntypes, tabJ, tabR, pc.f[k], omega);
   }
   lds_barrier();  // everybody has read the old values
   const bool outc = out != nullptr && pc.li >= 0 && pc.li < PATCH_TW;
@@ -1738,18 +1742,125 @@ __device__ __forceinline__ void patch_copy_out(const double* buf, double* __rest
 }
 
 struct __attribute__((aligned(8))) PatchPair { double x, y; };  // 16-byte load, 8-byte aligned
+
+// flag[idx] of a per-tile flag array, for a workgroup-uniform idx: the aligned 32-bit word that holds
+// the byte comes through a scalar load, so nothing on the vector side waits for it (the arrays are
+// padded to whole words where they are allocated: solver.cpp)
+__device__ __forceinline__ uint32_t patch_flag(const uint8_t* __restrict__ flag, int idx) {
+  const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(flag);
+  return (w[idx >> 2] >> (8 * (idx & 3))) & 255u;
+}
+
+// The per-lane tables in LDS (patch_eval): thread t loads row t of ptab (nent x {aJ, d, aR, loff as
+// double; -1e9 = unused slot}) into registers (patch_issue_tables) and writes it later, behind
+// loads issued after it (patch_stage_tables); slots past nent: absent.  One row per thread covers
+// the table.
+static_assert(PATCH_MAXTAB <= PATCH_NT, "one table row per thread");
+struct PatchTabRow { double v[4]; };
+__device__ __forceinline__ void patch_issue_tables(PatchTabRow& tb, const double* __restrict__ ptab, int nent) {
+  const int t = (int)threadIdx.x < nent ? (int)threadIdx.x : 0;  // (nent >= 1: threads past it re-read row 0)
+#pragma unroll
+  for (int q = 0; q < 4; ++q) tb.v[q] = ptab[4 * t + q];
+}
+__device__ __forceinline__ void patch_stage_tables(PatchJ* tabJ, PatchR* tabR, const PatchTabRow& tb, int nent) {
+  const int t = threadIdx.x;
+  if (t >= PATCH_MAXTAB) return;
+  PatchJ j = {0.0, 0.0};
+  PatchR r = {0.0, 0, 0};
+  if (t < nent) {
+    j.a = tb.v[0];
+    j.d = tb.v[1];
+    r.a = tb.v[2];
+    const double lo = tb.v[3];
+    r.ok = lo > -1.0e8 ? 1 : 0;
+    r.loff = r.ok ? (int)lo : 0;
+  }
+  tabJ[t] = j;
+  tabR[t] = r;
+}
+// guard lines: finite values for the reads of dropped cells
+__device__ __forceinline__ void patch_clear_guards(double* buf) {
+  for (int t = threadIdx.x; t < 2 * PATCH_EC; t += PATCH_NT)
+    buf[t < PATCH_EC ? t : PATCH_BUF - 2 * PATCH_EC + t] = 0.0;
+}
+// The rest of the common prologue, after the cells (patch_load): guards, and the per-lane tables
+// where a flagged tile needs them.  Only a wave that is not on the scalar path reads them
+// (patch_stage: pc.uniform && U.rmask == UM).  On a flagged tile every wave has the type pc.tu, so
+// the tables are read only when that type is not the kernel kind's (a rare tile: a dependent load
+// here); every other flagged tile neither loads nor writes them.  A tile without a flag staged
+// them in patch_load, beside its row types.
+template <int UM>
+__device__ __forceinline__ void patch_prologue(const PatchCells& pc, const PatchU& U, double* buf, PatchJ* tabJ,
+                                               PatchR* tabR, const double* __restrict__ ptab, int nent) {
+  if (pc.flagged && U.rmask != (uint32_t)UM) {
+    PatchTabRow tb;
+    patch_issue_tables(tb, ptab, nent);
+    patch_stage_tables(tabJ, tabR, tb, nent);
+  }
+  patch_clear_guards(buf);
+}
+
+// XF: the held cells as the from-zero sweep of their rows, x = Jacobi(0; f), instead of a load of
+// the vector the finer level's kernel would have stored: the expression of jacobi_from_zero_kernel
+// and of the restriction loop below, operand for operand, on the f the thread holds anyway.  d = the
+// diagonal of the cell's row type: the bits of the level's diagonal vector (the dictionary coding is
+// exact; the sweeps divide by this very value) -- in scalar registers on a wave-uniform wave, else
+// from the per-type table in global memory (utabd, 19 doubles per type: the LDS tables are not
+// staged yet).  The absent type `ntypes` (rows outside the matrix, empty rows) has d = 0: x = 0.0.
+__device__ __forceinline__ void patch_form_x(const PatchCells& pc, const PatchU& U,
+                                             const double* __restrict__ utabd, double omega, double* buf) {
+  double dv[PATCH_K];
+  if (pc.uniform) {
+#pragma unroll
+    for (int k = 0; k < PATCH_K; ++k) dv[k] = U.diag;
+  } else {
+#pragma unroll
+    for (int k = 0; k < PATCH_K; ++k) dv[k] = utabd[(size_t)pc.type(k) * 19 + 18];
+  }
+#pragma unroll
+  for (int k = 0; k < PATCH_K; ++k) {
+    const double sum = pc.f[k], d = dv[k];
+    const double xi = 0.0, acc = 0.0;  // jacobi_from_zero_kernel
+    const double x0 = (d == 0.0) ? xi : xi + omega * ((sum - acc) / d - xi);
+    buf[pc.cell0 + k * PATCH_EC] = pc.live[k] ? x0 : 0.0;
+  }
+}
+
+// Everything a patch kernel does before its first barrier but the guards (patch_prologue): the loads
+// of the tile, the row types, the uniform type's table and the cells' way into LDS.
+// Every global load whose address does not hang on loaded data is ISSUED AT ENTRY, before anything
+// is waited for, and waited for where its value is used:
+//   x [-> uH pairs] -> f                          vector loads, in this order (they return in order)
+//   tile flag -> the flagged type's table (U)     scalar loads, beside them
+// so a workgroup of a flagged tile exposes ONE memory round trip before its first LDS write: the
+// wait for x; f is first read inside the first stage and is not waited for before the first
+// barrier.  The rows are the clamped ones of the general path -- the flag is not known yet; on a
+// flagged tile every row is inside the matrix, so these are its own rows.
+// The up-leg (PROLONG) holds x and the uH pairs, 48 registers, at entry and issues f as those
+// retire into LDS: all three at once do not fit the 72 registers of four workgroups per CU.
+// tf: the tile's flag (patch_flag of tflag[tile]; 255, or no tflag: no flag, rows of several types or
+// outside the matrix), read once the tile is in flight -- a scalar wait is a wait for every scalar
+// load, the kernel's arguments among them, so the flag's round trip must not stand before the
+// tile's: every row of the patch and its halo has the row type tf (patch_tile_flags_kernel found that out
+// at setup) -- no row-type loads, the wave-uniform path for all waves.  Only tf == 255 keeps
+// dependent loads: the row types (what the flags were introduced to skip) with the per-lane
+// tables beside them, then the table of the type a wave found uniform.
 // PROLONG: the loaded vector is x + P uH (up-leg); else plain x.
-// UNI: every row of the patch and its halo has the row type `tf` (patch_tile_flags_kernel found
-// that out at setup): no row-type loads, no bounds checks, the wave-uniform path for all waves.
-// XF: x is not loaded and nothing is written to LDS: the caller forms the cells from pc.f once the
-// row type's diagonal is at hand (patch_form_x).
+// XF: x is not loaded and the cells are formed from f once the row type's diagonal is at hand
+// (patch_form_x, called here).
 // RINGS: the first held line is line -RINGS of the patch.
-template <int RINGS, bool PROLONG, bool UNI, bool XF = false>
-__device__ __forceinline__ void patch_load(PatchCells& pc, uint32_t tf, int n, int m, int j0, int i0,
-                                           const double* __restrict__ x,
+// (pc.f of a row outside the matrix is f[0]: such a cell is never `did`, its results are dropped.)
+template <int RINGS, bool PROLONG, bool XF = false>
+__device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint8_t* __restrict__ tflag,
+                                           int tile, int n, int m,
+                                           int j0, int i0, const double* __restrict__ x,
                                            const double* __restrict__ f,
                                            const uint8_t* __restrict__ rtype, int ntypes,
-                                           const double* __restrict__ uH, int nH, double* buf) {
+                                           const double* __restrict__ uH, int nH,
+                                           const double* __restrict__ ptab, int nent,
+                                           const double* __restrict__ utabd,
+                                           const int32_t* __restrict__ utabi, double omega, double* buf,
+                                           PatchJ* tabJ, PatchR* tabR) {
   const int g = (int)threadIdx.x / PATCH_EC, col = (int)threadIdx.x - g * PATCH_EC;
   const int le = g * PATCH_K;            // first of the thread's PATCH_K consecutive lines
   pc.lj0 = le - RINGS;
@@ -1757,51 +1868,104 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, uint32_t tf, int n, i
   pc.cell0 = (le + 1) * PATCH_EC + col;  // + 1: guard line
   const int64_t r0 = (int64_t)(j0 + pc.lj0) * m + i0 + pc.li;
   pc.row0 = (int)(r0 < -((int64_t)1 << 30) ? -((int64_t)1 << 30) : r0);
-  uint32_t mism = 0;
   double xv[PATCH_K];
+  PatchPair pr[PATCH_K];
 #pragma unroll
   for (int k = 0; k < PATCH_K; ++k) {
     const int64_t r64 = r0 + (int64_t)k * m;
-    pc.live[k] = UNI || (r64 >= 0 && r64 < (int64_t)n);
-    const int row = pc.live[k] ? (int)r64 : 0;
-    if (!XF) xv[k] = x[row];
-    pc.f[k] = f[row];
-    pc.ty[k] = UNI ? tf : (uint32_t)rtype[row];
+    pc.live[k] = r64 >= 0 && r64 < (int64_t)n;
+    if (!XF) xv[k] = x[pc.live[k] ? (int)r64 : 0];
   }
+  if (PROLONG) {
 #pragma unroll
-  for (int k = 0; k < PATCH_K; ++k) {
-    const int row = pc.row0 + k * m;
-    double x0 = (!XF && pc.live[k]) ? xv[k] : 0.0;
-    if (PROLONG) {  // linear_prolong_add_kernel, same guards and order, written with selects
+    for (int k = 0; k < PATCH_K; ++k) {
+      const int row = pc.row0 + k * m;
       const int j = pc.live[k] ? (row >> 1) : 0;
-      const bool odd = (row & 1) != 0;
-      const bool a_ok = pc.live[k] && !odd && j >= 1 && j - 1 < nH;
-      const bool b_ok = pc.live[k] && j < nH;
       // uH[j - 1] and uH[j] as ONE 16-byte load of the pair (jc - 1, jc), jc = j clamped to
       // [1, nH - 1] (nH >= 2 on a patch level): half the load instructions of two gathers
       const int jc = j < 1 ? 1 : (j > nH - 1 ? nH - 1 : j);
-      const PatchPair pr = *reinterpret_cast<const PatchPair*>(uH + (jc - 1));
-      const double a = (j == jc) ? pr.x : pr.y;   // j - 1 == jc - 1, or j - 1 == jc (j == nH)
-      const double b = (j == jc) ? pr.y : pr.x;   // j == jc, or j == jc - 1 (j == 0)
+      pr[k] = *reinterpret_cast<const PatchPair*>(uH + (jc - 1));
+    }
+  }
+  if (!PROLONG) {
+#pragma unroll
+    for (int k = 0; k < PATCH_K; ++k) {
+      const int64_t r64 = r0 + (int64_t)k * m;
+      pc.f[k] = f[pc.live[k] ? (int)r64 : 0];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);  // the tile is in flight before the flag is looked at
+  const uint32_t tf = tflag ? patch_flag(tflag, tile) : 255u;
+  const uint32_t nty = (uint32_t)ntypes;
+  pc.flagged = tf != 255u;
+  if (pc.flagged) {
+    // (ty[] is not filled in -- type() does not read it: two registers less while the tile is in flight)
+    pc.tu = tf;
+    pc.uniform = true;
+  } else {
+    PatchTabRow tb;
+    patch_issue_tables(tb, ptab, nent);
+    uint32_t mism = 0, ty[PATCH_K];
+#pragma unroll
+    for (int k = 0; k < PATCH_K; ++k) {
+      const int64_t r64 = r0 + (int64_t)k * m;
+      ty[k] = (uint32_t)rtype[pc.live[k] ? (int)r64 : 0];
+    }
+#pragma unroll
+    for (int q = 0; q < PATCH_K / 4; ++q) pc.ty[q] = 0;
+#pragma unroll
+    for (int k = 0; k < PATCH_K; ++k) {
+      ty[k] = (pc.live[k] && ty[k] < nty) ? ty[k] : nty;  // 255 = empty row -> absent row
+      pc.ty[k >> 2] |= ty[k] << (8 * (k & 3));            // (nty < 256: the table holds (nty + 1) rows)
+    }
+    pc.tu = (uint32_t)__builtin_amdgcn_readfirstlane((int)ty[0]);
+#pragma unroll
+    for (int q = 0; q < PATCH_K / 4; ++q) mism |= pc.ty[q] ^ (pc.tu * 0x01010101u);
+    pc.uniform = __builtin_amdgcn_ballot_w64(mism != 0) == 0 && pc.tu < nty;
+    patch_stage_tables(tabJ, tabR, tb, nent);
+  }
+  {
+    // (opaque from here on: else the compiler folds type() back into eight registers of tf, filled --
+    // and in the up-leg spilled -- on the flagged path)
+    int fl = pc.flagged;
+    asm("" : "+v"(fl));
+    pc.flagged = __builtin_amdgcn_readfirstlane(fl) != 0;
+  }
+  // the uniform type's table (scalar loads): on a flagged tile issued before the first vector wait
+  patch_load_u(U, pc.uniform ? pc.tu : 0u, utabd, utabi);
+  __builtin_amdgcn_sched_barrier(0);
+  if (XF) patch_form_x(pc, U, utabd, omega, buf);
+  if (PROLONG) {
+    // j, jc and the rows of f are worked out again from here on: kept across the loads they cost
+    // the registers that the 48 of x and the uH pairs need (the compiler would keep, then spill, them)
+    int row0 = pc.row0;
+    asm volatile("" : "+v"(row0));
+    pc.row0 = row0;
+  }
+#pragma unroll
+  for (int k = 0; k < PATCH_K && !XF; ++k) {
+    const int row = pc.row0 + k * m;
+    double x0 = pc.live[k] ? xv[k] : 0.0;
+    if (PROLONG) {  // linear_prolong_add_kernel, same guards and order, written with selects
+      const int j = pc.live[k] ? (row >> 1) : 0;
+      const int jc = j < 1 ? 1 : (j > nH - 1 ? nH - 1 : j);
+      const bool odd = (row & 1) != 0;
+      const bool a_ok = pc.live[k] && !odd && j >= 1 && j - 1 < nH;
+      const bool b_ok = pc.live[k] && j < nH;
+      const double a = (j == jc) ? pr[k].x : pr[k].y;   // j - 1 == jc - 1, or j - 1 == jc (j == nH)
+      const double b = (j == jc) ? pr[k].y : pr[k].x;   // j == jc, or j == jc - 1 (j == 0)
       double t = 0.0;
       t = a_ok ? t + 0.5 * a : t;
       t = b_ok ? t + (odd ? 1.0 : 0.5) * b : t;
       x0 = pc.live[k] ? x0 + t : x0;
     }
-    if (!XF) buf[pc.cell0 + k * PATCH_EC] = x0;
-    const uint32_t nty = (uint32_t)ntypes;
-    pc.ty[k] = (pc.live[k] && pc.ty[k] < nty) ? pc.ty[k] : nty;  // 255 = empty row -> absent row
-    pc.f[k] = pc.live[k] ? pc.f[k] : 0.0;
+    buf[pc.cell0 + k * PATCH_EC] = x0;
   }
-  if (UNI) {
-    pc.tu = tf;
-    pc.uniform = true;
-    return;
-  }
-  pc.tu = (uint32_t)__builtin_amdgcn_readfirstlane((int)pc.ty[0]);
+  if (PROLONG) {
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int k = 0; k < PATCH_K; ++k) mism |= pc.ty[k] ^ pc.tu;
-  pc.uniform = __builtin_amdgcn_ballot_w64(mism != 0) == 0 && pc.tu < (uint32_t)ntypes;
+    for (int k = 0; k < PATCH_K; ++k) pc.f[k] = f[pc.live[k] ? pc.row0 + k * m : 0];  // (a live row is row0 + k m)
+  }
 }
 
 // flag[tile] = the row type shared by EVERY row a patch kernel of `rings` rings loads for the tile
@@ -1868,66 +2032,6 @@ hipError_t launch_patch_coarse_flags(int64_t n, int64_t m, int rings, int64_t nH
   return hipGetLastError();
 }
 
-__device__ __forceinline__ void patch_stage_tables(PatchJ* tabJ, PatchR* tabR,
-                                                   const double* __restrict__ ptab, int nent) {
-  // ptab: nent x {aJ, d, aR, loff (as double; -1e9 = unused slot)}; slots past nent: absent
-  for (int t = threadIdx.x; t < PATCH_MAXTAB; t += PATCH_NT) {
-    PatchJ j = {0.0, 0.0};
-    PatchR r = {0.0, 0, 0};
-    if (t < nent) {
-      j.a = ptab[4 * t];
-      j.d = ptab[4 * t + 1];
-      r.a = ptab[4 * t + 2];
-      const double lo = ptab[4 * t + 3];
-      r.ok = lo > -1.0e8 ? 1 : 0;
-      r.loff = r.ok ? (int)lo : 0;
-    }
-    tabJ[t] = j;
-    tabR[t] = r;
-  }
-}
-// guard lines: finite values for the reads of dropped cells
-__device__ __forceinline__ void patch_clear_guards(double* buf) {
-  for (int t = threadIdx.x; t < 2 * PATCH_EC; t += PATCH_NT)
-    buf[t < PATCH_EC ? t : PATCH_BUF - 2 * PATCH_EC + t] = 0.0;
-}
-
-// common prologue: tables, guards and the uniform type's table (scalar loads)
-__device__ __forceinline__ void patch_prologue(const PatchCells& pc, double* buf, PatchJ* tabJ,
-                                               PatchR* tabR, const double* __restrict__ ptab,
-                                               int nent, const double* __restrict__ utabd,
-                                               const int32_t* __restrict__ utabi, PatchU& U) {
-  patch_stage_tables(tabJ, tabR, ptab, nent);
-  patch_clear_guards(buf);
-  patch_load_u(U, pc.uniform ? pc.tu : 0u, utabd, utabi);
-}
-
-// XF: the held cells as the from-zero sweep of their rows, x = Jacobi(0; f), instead of a load of
-// the vector the finer level's kernel would have stored: the expression of jacobi_from_zero_kernel
-// and of the restriction loop below, operand for operand, on the f the thread holds anyway.  d = the
-// diagonal of the cell's row type: the bits of the level's diagonal vector (the dictionary coding is
-// exact; the sweeps divide by this very value) -- in scalar registers on a wave-uniform wave, else
-// from the per-type table in global memory (utabd, 19 doubles per type: the LDS tables are not
-// staged yet).  The absent type `ntypes` (rows outside the matrix, empty rows) has d = 0: x = 0.0.
-__device__ __forceinline__ void patch_form_x(const PatchCells& pc, const PatchU& U,
-                                             const double* __restrict__ utabd, double omega, double* buf) {
-  double dv[PATCH_K];
-  if (pc.uniform) {
-#pragma unroll
-    for (int k = 0; k < PATCH_K; ++k) dv[k] = U.diag;
-  } else {
-#pragma unroll
-    for (int k = 0; k < PATCH_K; ++k) dv[k] = utabd[(size_t)pc.ty[k] * 19 + 18];
-  }
-#pragma unroll
-  for (int k = 0; k < PATCH_K; ++k) {
-    const double sum = pc.f[k], d = dv[k];
-    const double xi = 0.0, acc = 0.0;  // jacobi_from_zero_kernel
-    const double x0 = (d == 0.0) ? xi : xi + omega * ((sum - acc) / d - xi);
-    buf[pc.cell0 + k * PATCH_EC] = pc.live[k] ? x0 : 0.0;
-  }
-}
-
 // FIRST: the input is the level's u and both pre-sweeps run here (level 0); else the input
 // is the result of the first sweep (done by the finer level's kernel) and one sweep runs.
 // XF (with !FIRST): that first sweep is not loaded but formed from f (patch_form_x); the finer
@@ -1991,17 +2095,17 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
   const int j0 = (py + py0) * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
-  const uint32_t tf = tflag ? (uint32_t)tflag[(py + py0) * px_count + px] : 255u;
-  // every coarse row under this patch has the diagonal dHu (launch_patch_coarse_flags found that
-  // out at setup): the first coarse sweep then needs no load of the coarse diagonal at the very
-  // end of the workgroup's life, where nothing is left to hide its latency behind
-  const bool cuni = uH1 && cflag && cflag[(py + py0) * px_count + px] != 0;
+  const int ftile = (py + py0) * px_count + px;
   static_assert(!(FIRST && XF), "level 0 starts from its own u");
   static_assert(RINGS == 3 || (RINGS == 2 && !FIRST), "three dependent stages (FIRST) need three rings");
-  if (tf != 255u) patch_load<RINGS, false, true, XF>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
-  else patch_load<RINGS, false, false, XF>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, buf);
-  patch_prologue(pc, buf, tabJ, tabR, ptab, nent, utabd, utabi, U);
-  if (XF) patch_form_x(pc, U, utabd, omega, buf);
+  patch_load<RINGS, false, XF>(pc, U, tflag, ftile, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, ptab, nent,
+                               utabd, utabi, omega, buf, tabJ, tabR);
+  patch_prologue<UM>(pc, U, buf, tabJ, tabR, ptab, nent);
+  // every coarse row under this patch has the diagonal dHu (launch_patch_coarse_flags found that
+  // out at setup): the first coarse sweep then needs no load of the coarse diagonal at the very
+  // end of the workgroup's life, where nothing is left to hide its latency behind.  (A scalar load
+  // like the tile flag's, issued behind the tile; read in the restriction loop.)
+  const bool cuni = uH1 && cflag && patch_flag(cflag, ftile) != 0;
   lds_barrier();
   PATCH_STAMP(1);
   if (FIRST) {
@@ -2059,10 +2163,9 @@ __global__ __launch_bounds__(PATCH_NT, AMG_PATCH_WAVES) void patch_up_kernel(
   const int j0 = (py + py0) * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
-  const uint32_t tf = tflag ? (uint32_t)tflag[(py + py0) * px_count + px] : 255u;
-  if (tf != 255u) patch_load<RINGS, true, true>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
-  else patch_load<RINGS, true, false>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
-  patch_prologue(pc, buf, tabJ, tabR, ptab, nent, utabd, utabi, U);
+  patch_load<RINGS, true>(pc, U, tflag, (py + py0) * px_count + px, n, m, j0, i0, x, f, rtype, ntypes, uH, nH,
+                          ptab, nent, utabd, utabi, omega, buf, tabJ, tabR);
+  patch_prologue<UM>(pc, U, buf, tabJ, tabR, ptab, nent);
   lds_barrier();
   patch_stage<UN, UM, false, NT, false, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -1, TH + 1, -1,
                                             PATCH_TW + 1, nullptr);
@@ -2108,7 +2211,7 @@ __device__ __forceinline__ void patch_stage_color(const PatchCells& pc, int ntyp
 #pragma unroll
     for (int k = 0; k < PATCH_K; ++k)
       res[k] = patch_eval<UN, false, true>(buf, pc.cell0 + k * PATCH_EC,
-                                           did[k] ? pc.ty[k] : (uint32_t)ntypes, tabJ, tabR, pc.f[k], 1.0);
+                                           did[k] ? pc.type(k) : (uint32_t)ntypes, tabJ, tabR, pc.f[k], 1.0);
   }
   // cells of one colour do not read each other: no barrier between the reads and the writes
 #pragma unroll
@@ -2155,10 +2258,9 @@ __global__ __launch_bounds__(PATCH_NT, AMG_RB_WAVES) void patch_rb_kernel(
   const int j0 = (py + py0) * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
-  const uint32_t tf = tflag ? (uint32_t)tflag[(py + py0) * px_count + px] : 255u;
-  if (tf != 255u) patch_load<RINGS, PROLONG, true>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
-  else patch_load<RINGS, PROLONG, false>(pc, tf, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, buf);
-  patch_prologue(pc, buf, tabJ, tabR, ptab, nent, utabd, utabi, U);
+  patch_load<RINGS, PROLONG>(pc, U, tflag, (py + py0) * px_count + px, n, m, j0, i0, x, f, rtype, ntypes, uH, nH,
+                             ptab, nent, utabd, utabi, 1.0, buf, tabJ, tabR);
+  patch_prologue<UM>(pc, U, buf, tabJ, tabR, ptab, nent);
   uint32_t cbits = 0;
   {
     // the cell is flat row (j0 + lj) * m + i0 + li: beyond a line's end that is a row of the next / previous line
@@ -2171,10 +2273,14 @@ __global__ __launch_bounds__(PATCH_NT, AMG_RB_WAVES) void patch_rb_kernel(
       cbits |= ((ctab >> (2u * (((line + (uint32_t)k) & 1u) * 6u + cls))) & 3u) << (2 * k);
   }
   lds_barrier();
+  if (pc.flagged) pc.ty[0] = pc.ty[1] = 0;  // (not read; defined for the asm in the loop below)
   constexpr int E = TAIL ? 1 : 0;  // the residual stage needs one more ring (and the restriction one more column)
   const int nst = (int)(stages & 7u);
   for (int sg = 0; sg < nst; ++sg) {
     const int ext = nst - 1 - sg + E;  // rings the later stages still read
+    // (the packed row types are unpacked at their use: hoisted out of this loop the bytes cost eight
+    // registers again, and the kernel spills)
+    asm volatile("" : "+v"(pc.ty[0]), "+v"(pc.ty[1]));
     patch_stage_color<UN, UM>(pc, ntypes, buf, U, tabJ, tabR, -ext, TH + ext, -ext, PATCH_TW + ext + E,
                               cbits, (stages >> (4 + 2 * sg)) & 3u);
     lds_barrier();

@@ -671,7 +671,9 @@ hipError_t finish_dict(const DictMat& T, int64_t n, int64_t diag_shift, DevMat* 
       for (int rings = 2; rings <= 3; ++rings) {  // (3 last: `tiles` below counts the 42-line tiles)
         DevMem& F = rings == 2 ? D->patch_flags2 : D->patch_flags;
         if ((e = launch_patch_tile_flags(n, D->patch_m, rings, nullptr, nty, nullptr, &tiles, nullptr)) != hipSuccess) return e;
-        if ((e = F.alloc((size_t)tiles)) != hipSuccess) return e;
+        // whole 32-bit words, zero-filled: the kernels read the word that holds a tile's flag
+        if ((e = F.alloc(((size_t)tiles + 3) & ~(size_t)3)) != hipSuccess) return e;
+        if ((e = hipMemset(F.p, 0, F.bytes)) != hipSuccess) return e;
         if ((e = launch_patch_tile_flags(n, D->patch_m, rings, D->drtype.as<uint8_t>(), nty, F.as<uint8_t>(),
                                          nullptr, nullptr)) != hipSuccess) return e;
       }
@@ -2473,7 +2475,8 @@ amg_hip_status set_patch_coarse_flags(amg_hip_solver* s) {
     for (int rg = 3; rg >= rings; --rg) {
       int64_t tiles = 0;
       HIP_TRY(launch_patch_tile_flags(L.n, A.patch_m, rg, nullptr, A.patch_ntypes, nullptr, &tiles, nullptr));
-      HIP_TRY(A.patch_cflags.alloc((size_t)tiles));
+      HIP_TRY(A.patch_cflags.alloc(((size_t)tiles + 3) & ~(size_t)3));  // whole words, as the tile flags
+      HIP_TRY(hipMemset(A.patch_cflags.p, 0, A.patch_cflags.bytes));
       HIP_TRY(launch_patch_coarse_flags(L.n, A.patch_m, rg, C.n, C.diag.as<double>(), dref,
                                         A.patch_cflags.as<uint8_t>(), nullptr));
       if (rg != 3) continue;
