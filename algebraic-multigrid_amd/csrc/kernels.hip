@@ -6777,26 +6777,33 @@ __global__ __launch_bounds__(256) void line_factor_chain_kernel(LineRef L, int64
   if (b >= 0) atomicMin(bad, (unsigned long long)b);
 }
 
-// The solve kernels are templates on the scalar type T: double for the cycle, float for the
-// single-precision cycle (solver.cpp: "fp32 cycle"), which walks float copies of the same factors in
-// the same order.
-// y_g = B_g^-1 r_g: the forward values stay in registers (the loops are fully unrolled), so the
-// dependent chain is arithmetic only and the loads of r and of the factors run ahead of it
-template <typename T>
+// The solve kernels are templates on the scalar type T and the panel pitch KP.  T: double for the
+// cycle, float for the single-precision cycle (solver.cpp: "fp32 cycle"), which walks float copies of
+// the same factors in the same order.  KP: r, y and u are row-major n x KP panels (entry (i, j) at
+// i * KP + j, a 64-bit index; KP = 1: plain vectors, KP > 1: the panels of K-Block) and a lane works
+// on one column j.  The factor arrays are indexed by row: the KP lanes of a row load the same factor
+// words (served once) and one contiguous segment of every panel.  Per (row, column) the expressions
+// and their order do not depend on KP, so column j of a panel has the bits of the plain vector.
+// y_g = B_g^-1 r_g, lane = (segment, chain, column): the forward values stay in registers (the loops
+// are fully unrolled), so the dependent chain is arithmetic only and the loads of r and of the
+// factors run ahead of it
+template <typename T, int KP>
 __global__ __launch_bounds__(256) void line_seg_kernel(int64_t n, int64_t s, int64_t nch, int64_t nseg,
                                                        const T* __restrict__ r, const T* __restrict__ dl,
                                                        const T* __restrict__ ip, const T* __restrict__ cp,
                                                        T* __restrict__ y) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nch * nseg) return;
-  const int64_t g = t / nch, c = t - g * nch;
+  if (t >= nch * nseg * KP) return;
+  const int j = (int)(t % KP);
+  const int64_t q = t / KP;
+  const int64_t g = q / nch, c = q - g * nch;
   const int64_t i0 = (g * LINE_SEG) * s + c;
   T yv[LINE_INT];
   T prev = T(0);
 #pragma unroll
   for (int k = 0; k < LINE_INT; ++k) {
     const int64_t i = i0 + (int64_t)k * s;
-    if (i < n) prev = k > 0 ? (r[i] - dl[i] * prev) * ip[i] : r[i] * ip[i];
+    if (i < n) prev = k > 0 ? (r[i * KP + j] - dl[i] * prev) * ip[i] : r[i * KP + j] * ip[i];
     else prev = T(0);
     yv[k] = prev;
   }
@@ -6806,48 +6813,51 @@ __global__ __launch_bounds__(256) void line_seg_kernel(int64_t n, int64_t s, int
     const int64_t i = i0 + (int64_t)k * s;
     if (i < n) {
       nxt = yv[k] - cp[i] * nxt;
-      y[i] = nxt;
+      y[i * KP + j] = nxt;
     }
   }
 }
 
-// right-hand side of the reduced system at separator row i
-template <typename T>
-__device__ inline T line_sep_rhs(int64_t i, int64_t n, int64_t s, const T* r, const T* dl, const T* w, const T* y) {
-  T b = r[i] - dl[i] * y[i - s];
-  if (i + s < n) b = b - w[i] * y[i + s];
+// right-hand side of the reduced system at separator row i, column j
+template <typename T, int KP>
+__device__ inline T line_sep_rhs(int64_t i, int j, int64_t n, int64_t s, const T* r, const T* dl, const T* w,
+                                 const T* y) {
+  T b = r[i * KP + j] - dl[i] * y[(i - s) * KP + j];
+  if (i + s < n) b = b - w[i] * y[(i + s) * KP + j];
   return b;
 }
-// many chains: one lane per chain, neighbouring lanes neighbouring addresses.  Each batch of
+// many chains: lane = (chain, column), neighbouring lanes neighbouring addresses.  Each batch of
 // LINE_BATCH separators is loaded before its dependent steps run, so a chain of m / 32 separators
-// costs m / (32 LINE_BATCH) memory latencies per direction.
+// costs m / (32 LINE_BATCH) memory latencies per direction, once for the KP columns.
 constexpr int LINE_BATCH = 8;
-template <typename T>
+template <typename T, int KP>
 __global__ __launch_bounds__(64) void line_sep_many_kernel(int64_t n, int64_t s, int64_t nch, const T* r,
                                                            const T* dl, const T* ip, const T* cp, const T* v,
                                                            const T* w, T* y) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= nch) return;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nch * KP) return;
+  const int j = (int)(t % KP);
+  const int64_t c = t / KP;
   const int64_t step = (int64_t)LINE_SEG * s;
   const int64_t first = (int64_t)LINE_INT * s + c;
   if (first >= n) return;
   const int64_t nsep = (n - 1 - first) / step + 1;
-  T t = T(0);
+  T tv = T(0);
   for (int64_t g0 = 0; g0 < nsep; g0 += LINE_BATCH) {
     T b[LINE_BATCH], lo[LINE_BATCH], pv[LINE_BATCH];
 #pragma unroll
-    for (int j = 0; j < LINE_BATCH; ++j) {
-      const int64_t i = first + (g0 + j) * step;
-      const bool on = g0 + j < nsep;
-      b[j] = on ? line_sep_rhs(i, n, s, r, dl, w, y) : T(0);
-      lo[j] = on ? v[i] : T(0);
-      pv[j] = on ? ip[i] : T(0);
+    for (int k = 0; k < LINE_BATCH; ++k) {
+      const int64_t i = first + (g0 + k) * step;
+      const bool on = g0 + k < nsep;
+      b[k] = on ? line_sep_rhs<T, KP>(i, j, n, s, r, dl, w, y) : T(0);
+      lo[k] = on ? v[i] : T(0);
+      pv[k] = on ? ip[i] : T(0);
     }
 #pragma unroll
-    for (int j = 0; j < LINE_BATCH; ++j) {
-      if (g0 + j < nsep) {
-        t = (b[j] - lo[j] * t) * pv[j];
-        y[first + (g0 + j) * step] = t;
+    for (int k = 0; k < LINE_BATCH; ++k) {
+      if (g0 + k < nsep) {
+        tv = (b[k] - lo[k] * tv) * pv[k];
+        y[(first + (g0 + k) * step) * KP + j] = tv;
       }
     }
   }
@@ -6855,103 +6865,111 @@ __global__ __launch_bounds__(64) void line_sep_many_kernel(int64_t n, int64_t s,
   for (int64_t g1 = nsep; g1 > 0; g1 -= LINE_BATCH) {  // separators g1-1, g1-2, ...
     T tt[LINE_BATCH], cc[LINE_BATCH];
 #pragma unroll
-    for (int j = 0; j < LINE_BATCH; ++j) {
-      const int64_t g = g1 - 1 - j;
+    for (int k = 0; k < LINE_BATCH; ++k) {
+      const int64_t g = g1 - 1 - k;
       const int64_t i = first + g * step;
-      tt[j] = g >= 0 ? y[i] : T(0);
-      cc[j] = g >= 0 ? cp[i] : T(0);
+      tt[k] = g >= 0 ? y[i * KP + j] : T(0);
+      cc[k] = g >= 0 ? cp[i] : T(0);
     }
 #pragma unroll
-    for (int j = 0; j < LINE_BATCH; ++j) {
-      const int64_t g = g1 - 1 - j;
+    for (int k = 0; k < LINE_BATCH; ++k) {
+      const int64_t g = g1 - 1 - k;
       if (g >= 0) {
-        x = tt[j] - cc[j] * x;
-        y[first + g * step] = x;
+        x = tt[k] - cc[k] * x;
+        y[(first + g * step) * KP + j] = x;
       }
     }
   }
 }
-// few long chains: one workgroup per chain.  All lanes stage a chunk of the reduced system in LDS,
-// lane 0 walks it there (an LDS round trip per step instead of a memory one) and carries the
-// recurrence into the next chunk, all lanes write the chunk back.  Same arithmetic in the same
-// order as line_sep_many_kernel.
-constexpr int LINE_FEW_CHUNK = 1024;  // 3 arrays: 24 KB of LDS in double, 12 KB in float
-template <typename T>
+// few long chains: one workgroup per chain.  All lanes stage a chunk of the reduced system in LDS
+// (lo and pv once, b per column), lanes 0 .. KP - 1 each walk one column there (an LDS round trip
+// per step instead of a memory one) and keep the recurrence in a register from chunk to chunk, all
+// lanes write the chunk back.  Same arithmetic in the same order as line_sep_many_kernel.
+// Chunks of line_few_chunk_c(KP) separators, (KP + 2) T of LDS each: 24 KB in double and 12 KB in
+// float up to KP = 4, 36 KB in double at KP = 16.
+constexpr int LINE_FEW_CHUNK = 1024;
+__host__ __device__ constexpr int line_few_chunk_c(int kp) { return kp <= 4 ? LINE_FEW_CHUNK : 4 * LINE_FEW_CHUNK / kp; }
+template <typename T, int KP>
 __global__ __launch_bounds__(256) void line_sep_few_kernel(int64_t n, int64_t s, const T* r, const T* dl,
                                                            const T* ip, const T* cp, const T* v, const T* w,
                                                            T* y) {
-  __shared__ T b[LINE_FEW_CHUNK], lo[LINE_FEW_CHUNK], pv[LINE_FEW_CHUNK];
-  __shared__ T carry;
+  constexpr int CH = line_few_chunk_c(KP);
+  __shared__ T b[CH * KP], lo[CH], pv[CH];
+  const int tid = threadIdx.x;
   const int64_t c = blockIdx.x;
   const int64_t step = (int64_t)LINE_SEG * s;
   const int64_t first = (int64_t)LINE_INT * s + c;
   if (first >= n) return;  // the whole workgroup
   const int64_t nsep = (n - 1 - first) / step + 1;
-  if (threadIdx.x == 0) carry = T(0);
-  __syncthreads();
-  for (int64_t g0 = 0; g0 < nsep; g0 += LINE_FEW_CHUNK) {
-    const int m = (int)(nsep - g0 < LINE_FEW_CHUNK ? nsep - g0 : LINE_FEW_CHUNK);
-    for (int g = threadIdx.x; g < m; g += blockDim.x) {
+  T carry = T(0);  // lanes < KP: the recurrence of column tid
+  for (int64_t g0 = 0; g0 < nsep; g0 += CH) {
+    const int m = (int)(nsep - g0 < CH ? nsep - g0 : CH);
+    for (int e = tid; e < m * KP; e += 256) {
+      const int g = e / KP, j = e % KP;
       const int64_t i = first + (g0 + g) * step;
-      b[g] = line_sep_rhs(i, n, s, r, dl, w, y);
-      lo[g] = v[i];
-      pv[g] = ip[i];
+      b[e] = line_sep_rhs<T, KP>(i, j, n, s, r, dl, w, y);
+      if (j == 0) {
+        lo[g] = v[i];
+        pv[g] = ip[i];
+      }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (tid < KP) {
       T t = carry;
       for (int g = 0; g < m; ++g) {
-        t = (b[g] - lo[g] * t) * pv[g];
-        b[g] = t;
+        t = (b[g * KP + tid] - lo[g] * t) * pv[g];
+        b[g * KP + tid] = t;
       }
       carry = t;
     }
     __syncthreads();
-    for (int g = threadIdx.x; g < m; g += blockDim.x) y[first + (g0 + g) * step] = b[g];
+    for (int e = tid; e < m * KP; e += 256) y[(first + (g0 + e / KP) * step) * KP + e % KP] = b[e];
     __syncthreads();
   }
-  if (threadIdx.x == 0) carry = T(0);
-  __syncthreads();
-  for (int64_t g1 = nsep; g1 > 0; g1 -= LINE_FEW_CHUNK) {  // separators [g1 - m, g1)
-    const int m = (int)(g1 < LINE_FEW_CHUNK ? g1 : LINE_FEW_CHUNK);
+  carry = T(0);
+  for (int64_t g1 = nsep; g1 > 0; g1 -= CH) {  // separators [g1 - m, g1)
+    const int m = (int)(g1 < CH ? g1 : CH);
     const int64_t gb = g1 - m;
-    for (int g = threadIdx.x; g < m; g += blockDim.x) {
+    for (int e = tid; e < m * KP; e += 256) {
+      const int g = e / KP, j = e % KP;
       const int64_t i = first + (gb + g) * step;
-      b[g] = y[i];
-      lo[g] = cp[i];
+      b[e] = y[i * KP + j];
+      if (j == 0) lo[g] = cp[i];
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (tid < KP) {
       T x = carry;
       for (int g = m - 1; g >= 0; --g) {
-        x = b[g] - lo[g] * x;
-        b[g] = x;
+        x = b[g * KP + tid] - lo[g] * x;
+        b[g * KP + tid] = x;
       }
       carry = x;
     }
     __syncthreads();
-    for (int g = threadIdx.x; g < m; g += blockDim.x) y[first + (gb + g) * step] = b[g];
+    for (int e = tid; e < m * KP; e += 256) y[(first + (gb + e / KP) * step) * KP + e % KP] = b[e];
     __syncthreads();
   }
 }
 
-// x_i = y_i - v_i x_(separator before) - w_i x_(separator after); u_i += omega x_i
-template <typename T>
+// x_i = y_i - v_i x_(separator before) - w_i x_(separator after); u_i += omega x_i, lane = (row, column)
+template <typename T, int KP>
 __global__ __launch_bounds__(256) void line_update_kernel(int64_t n, uint32_t s, const T* __restrict__ y,
                                                           const T* __restrict__ v, const T* __restrict__ w,
                                                           T omega, T* __restrict__ u) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * KP) return;
+  const int64_t i = e / KP;  // < 2^31: the row, not the panel index, goes through the 32-bit division
+  const int j = (int)(e % KP);
   const uint32_t p = (uint32_t)i / s;
   const uint32_t k = p % LINE_SEG;
-  T x = y[i];
+  T x = y[e];
   if (k != LINE_INT) {
     const int64_t before = i - ((int64_t)k + 1) * s;
     const int64_t after = i + (int64_t)(LINE_INT - k) * s;
-    if (before >= 0) x = x - v[i] * y[before];
-    if (after < n) x = x - w[i] * y[after];
+    if (before >= 0) x = x - v[i] * y[before * KP + j];
+    if (after < n) x = x - w[i] * y[after * KP + j];
   }
-  u[i] = u[i] + omega * x;
+  u[e] = u[e] + omega * x;
 }
 
 // ---- stride rule: w(d) = sum of |a_ij| over |j - i| = d >= 1 -----------------------------------
@@ -7081,33 +7099,55 @@ int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32
 }
 
 bool line_few_chains(int64_t s) { return s < 64; }
+int block_line_few_chunk(int kp) { return line_few_chunk_c(kp); }
 namespace {
-template <typename T>
-hipError_t line_solve_t(int64_t n, int64_t s, const T* dl, const T* ip, const T* cp, const T* v, const T* w,
-                        const T* r, T* y, T* u, T omega, hipStream_t st) {
+inline bool block_kp_ok(int kp) { return kp == 1 || kp == 2 || kp == 4 || kp == 8 || kp == 16; }
+// CALL(KP) with the pitch as a constant
+#define AMG_BLOCK_KP(kp, CALL) \
+  switch (kp) {                \
+    case 1: CALL(1); break;    \
+    case 2: CALL(2); break;    \
+    case 4: CALL(4); break;    \
+    case 8: CALL(8); break;    \
+    default: CALL(16); break;  \
+  }
+template <typename T, int KP>
+hipError_t line_solve_t(const LineRefT<T>& L, const T* r, T* y, T* u, T omega, hipStream_t st) {
+  const int64_t n = L.n, s = L.s;
   if (n <= 0 || s < 1 || s > n || n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
   const int64_t nch = line_chains(n, s), nseg = line_segments(n, s);
-  hipLaunchKernelGGL(line_seg_kernel<T>, line_grid(nch * nseg), dim3(256), 0, st, n, s, nch, nseg, r, dl, ip, cp, y);
+  hipLaunchKernelGGL((line_seg_kernel<T, KP>), line_grid(nch * nseg * KP), dim3(256), 0, st, n, s, nch, nseg, r,
+                     (const T*)L.dl, (const T*)L.ip, (const T*)L.cp, y);
   if ((int64_t)LINE_INT * s < n) {  // the level has separators
     if (line_few_chains(s)) {
-      hipLaunchKernelGGL(line_sep_few_kernel<T>, dim3((unsigned)nch), dim3(256), 0, st, n, s, r, dl, ip, cp, v, w, y);
+      hipLaunchKernelGGL((line_sep_few_kernel<T, KP>), dim3((unsigned)nch), dim3(256), 0, st, n, s, r, (const T*)L.dl,
+                         (const T*)L.ip, (const T*)L.cp, (const T*)L.v, (const T*)L.w, y);
     } else {
-      hipLaunchKernelGGL(line_sep_many_kernel<T>, line_grid(nch, 64), dim3(64), 0, st, n, s, nch, r, dl, ip, cp, v,
-                         w, y);
+      hipLaunchKernelGGL((line_sep_many_kernel<T, KP>), line_grid(nch * KP, 64), dim3(64), 0, st, n, s, nch, r,
+                         (const T*)L.dl, (const T*)L.ip, (const T*)L.cp, (const T*)L.v, (const T*)L.w, y);
     }
   }
-  hipLaunchKernelGGL(line_update_kernel<T>, line_grid(n), dim3(256), 0, st, n, (uint32_t)s, (const T*)y, v, w, omega,
-                     u);
+  hipLaunchKernelGGL((line_update_kernel<T, KP>), line_grid(n * KP), dim3(256), 0, st, n, (uint32_t)s, (const T*)y,
+                     (const T*)L.v, (const T*)L.w, omega, u);
   return hipGetLastError();
 }
 }  // namespace
 hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
                              hipStream_t st) {
-  return line_solve_t<double>(L.n, L.s, L.dl, L.ip, L.cp, L.v, L.w, r, y, u, omega, st);
+  return line_solve_t<double, 1>(L, r, y, u, omega, st);
 }
-hipError_t launch_line_solve_f32(const LineRefF32& L, const float* r, float* y, float* u, float omega,
+hipError_t launch_line_solve_f32(const LineRefT<float>& L, const float* r, float* y, float* u, float omega,
                                  hipStream_t st) {
-  return line_solve_t<float>(L.n, L.s, L.dl, L.ip, L.cp, L.v, L.w, r, y, u, omega, st);
+  return line_solve_t<float, 1>(L, r, y, u, omega, st);
+}
+hipError_t launch_block_line_solve(int kp, const LineRef& L, const double* r, double* y, double* u, double omega,
+                                   hipStream_t st) {
+  if (!block_kp_ok(kp)) return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+#define LINE_KP(KP) e = line_solve_t<double, KP>(L, r, y, u, omega, st)
+  AMG_BLOCK_KP(kp, LINE_KP)
+#undef LINE_KP
+  return e;
 }
 
 // ---- K-LineX: the x lines of a tensor grid (AMG_HIP_SM_LINE_ALT; kernels.hpp: LineXRef) --------
@@ -7237,8 +7277,10 @@ __global__ __launch_bounds__(64) void linex_kernel(int64_t n, int64_t len, int64
     __syncthreads();
   }
 }
-inline bool linex_ok(int64_t n, int64_t nx) { return n > 0 && nx >= 1 && n < ((int64_t)1 << 31) && n % nx == 0; }
-inline bool linex_ok(const LineXRef& L) { return linex_ok(L.n, L.nx); }
+template <typename T>
+inline bool linex_ok(const LineXRefT<T>& L) {
+  return L.n > 0 && L.nx >= 1 && L.n < ((int64_t)1 << 31) && L.n % L.nx == 0;
+}
 }  // namespace
 
 int64_t linex_run(int64_t nx) { return nx >= LINEX_COLS ? nx : nx * (LINEX_COLS / nx); }
@@ -7268,24 +7310,22 @@ int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int
 }
 namespace {
 template <typename T>
-hipError_t linex_solve_t(int64_t n, int64_t nx, const T* dl, const T* ip, const T* cp, T* r, T* u, T omega,
-                         hipStream_t st) {
-  if (!linex_ok(n, nx)) return hipErrorInvalidValue;
-  const int64_t len = linex_run(nx), nruns = (n + len - 1) / len;
+hipError_t linex_solve_t(const LineXRefT<T>& L, T* r, T* u, T omega, hipStream_t st) {
+  if (!linex_ok(L)) return hipErrorInvalidValue;
+  const int64_t n = L.n, len = linex_run(L.nx), nruns = (n + len - 1) / len;
   const dim3 grid = line_grid(nruns, LINEX_RUNS);
-  hipLaunchKernelGGL((linex_kernel<LX_FWD, T>), grid, dim3(64), 0, st, n, len, nruns, (const T*)r, dl, ip, r,
-                     (T*)nullptr, T(0), (unsigned long long*)nullptr);
-  hipLaunchKernelGGL((linex_kernel<LX_BWD, T>), grid, dim3(64), 0, st, n, len, nruns, (const T*)r, cp, (const T*)u, u,
-                     (T*)nullptr, omega, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((linex_kernel<LX_FWD, T>), grid, dim3(64), 0, st, n, len, nruns, (const T*)r, (const T*)L.dl,
+                     (const T*)L.ip, r, (T*)nullptr, T(0), (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((linex_kernel<LX_BWD, T>), grid, dim3(64), 0, st, n, len, nruns, (const T*)r, (const T*)L.cp,
+                     (const T*)u, u, (T*)nullptr, omega, (unsigned long long*)nullptr);
   return hipGetLastError();
 }
 }  // namespace
 hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double omega, hipStream_t st) {
-  return linex_solve_t<double>(L.n, L.nx, L.dl, L.ip, L.cp, r, u, omega, st);
+  return linex_solve_t(L, r, u, omega, st);
 }
-hipError_t launch_linex_solve_f32(int64_t n, int64_t nx, const float* dl, const float* ip, const float* cp, float* r,
-                                  float* u, float omega, hipStream_t st) {
-  return linex_solve_t<float>(n, nx, dl, ip, cp, r, u, omega, st);
+hipError_t launch_linex_solve_f32(const LineXRefT<float>& L, float* r, float* u, float omega, hipStream_t st) {
+  return linex_solve_t(L, r, u, omega, st);
 }
 
 // ---- K-LineSeam: the rank-one correction of a cyclic line solve (kernels.hpp: SeamRef) ----------
@@ -7336,11 +7376,14 @@ __global__ __launch_bounds__(256) void seamx_kernel(int64_t nlines, int64_t m, c
   }
 }
 constexpr int SEAM_WALK = 8;
-template <typename T>
+// r: an n x KP panel as in K-Line, lane = (line, column)
+template <typename T, int KP>
 __global__ __launch_bounds__(256) void seam_stride_kernel(int64_t nlines, int64_t s, int64_t m,
                                                           const T* __restrict__ p, const T* __restrict__ coef,
                                                           T* r) {
-  const int64_t line = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t line = t / KP;
+  const int j = (int)(t % KP);
   if (line >= nlines) return;
   const int64_t b = line / s;
   const int64_t i0 = b * s * m + (line - b * s);
@@ -7348,19 +7391,19 @@ __global__ __launch_bounds__(256) void seam_stride_kernel(int64_t nlines, int64_
   for (int64_t k0 = 0; k0 < m; k0 += SEAM_WALK) {
     T pv[SEAM_WALK], rv[SEAM_WALK];
 #pragma unroll
-    for (int j = 0; j < SEAM_WALK; ++j) {
-      const bool on = k0 + j < m;
-      pv[j] = on ? p[i0 + (k0 + j) * s] : T(0);
-      rv[j] = on ? r[i0 + (k0 + j) * s] : T(0);
+    for (int q = 0; q < SEAM_WALK; ++q) {
+      const bool on = k0 + q < m;
+      pv[q] = on ? p[i0 + (k0 + q) * s] : T(0);
+      rv[q] = on ? r[(i0 + (k0 + q) * s) * KP + j] : T(0);
     }
 #pragma unroll
-    for (int j = 0; j < SEAM_WALK; ++j)
-      if (k0 + j < m) acc = acc + pv[j] * rv[j];
+    for (int q = 0; q < SEAM_WALK; ++q)
+      if (k0 + q < m) acc = acc + pv[q] * rv[q];
   }
   const T fac = acc / coef[line];
-  const int64_t i1 = i0 + (m - 1) * s;
-  r[i0] = r[i0] - fac * coef[nlines + line];
-  r[i1] = r[i1] - fac * coef[2 * nlines + line];
+  const int64_t e0 = i0 * KP + j, e1 = (i0 + (m - 1) * s) * KP + j;
+  r[e0] = r[e0] - fac * coef[nlines + line];
+  r[e1] = r[e1] - fac * coef[2 * nlines + line];
 }
 
 // set-up: the two right-hand sides u = gamma e(i0) + beta e(i1), v = e(i0) + (alpha / gamma) e(i1)
@@ -7461,11 +7504,13 @@ int64_t seam_setup_host(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, 
 }
 namespace {
 template <typename T>
-hipError_t line_seam_t(int64_t n, int64_t s, int64_t m, const T* p, const T* coef, T* r, hipStream_t st) {
-  if (!seam_ok(n, s, m)) return hipErrorInvalidValue;
-  const int64_t nlines = n / m;
+hipError_t line_seam_t(const SeamRefT<T>& S, T* r, hipStream_t st) {
+  const int64_t s = S.s, m = S.m;
+  const T *p = S.p, *coef = S.coef;
+  if (!seam_ok(S.n, s, m)) return hipErrorInvalidValue;
+  const int64_t nlines = S.n / m;
   if (s > 1) {
-    hipLaunchKernelGGL(seam_stride_kernel<T>, line_grid(nlines), dim3(256), 0, st, nlines, s, m, p, coef, r);
+    hipLaunchKernelGGL((seam_stride_kernel<T, 1>), line_grid(nlines), dim3(256), 0, st, nlines, s, m, p, coef, r);
     return hipGetLastError();
   }
 #define SEAMX(W)                                                                                                       \
@@ -7480,208 +7525,21 @@ hipError_t line_seam_t(int64_t n, int64_t s, int64_t m, const T* p, const T* coe
   return hipGetLastError();
 }
 }  // namespace
-hipError_t launch_line_seam(const SeamRef& S, double* r, hipStream_t st) {
-  return line_seam_t<double>(S.n, S.s, S.m, S.p, S.coef, r, st);
-}
-hipError_t launch_line_seam_f32(int64_t n, int64_t s, int64_t m, const float* p, const float* coef, float* r,
-                                hipStream_t st) {
-  return line_seam_t<float>(n, s, m, p, coef, r, st);
-}
+hipError_t launch_line_seam(const SeamRef& S, double* r, hipStream_t st) { return line_seam_t(S, r, st); }
+hipError_t launch_line_seam_f32(const SeamRefT<float>& S, float* r, hipStream_t st) { return line_seam_t(S, r, st); }
 
 // ---- K-LineBlock: the line smoothers on the panels of K-Block (kernels.hpp) ---------------------
-// Row-major n x KP panels (entry (i, j) at i * KP + j, a 64-bit index); the factor arrays are the
-// single-vector ones, indexed by row: the KP lanes of a row load the same factor words (served once)
-// and one contiguous 8 KP-byte segment of every panel.  Per (row, column) each kernel evaluates the
-// expressions of its single-vector kernel in the same order, so column j has that kernel's bits.
-//   block_line_seg_kernel       line_seg_kernel, lane = (segment, chain, column)
-//   block_line_sep_many_kernel  line_sep_many_kernel, lane = (chain, column): the dependent chain of
-//                               separators is walked once for the KP columns
-//   block_line_sep_few_kernel   line_sep_few_kernel, a workgroup per chain: lo and pv staged once, b
-//                               per column, KP lanes walk; the carries stay in their registers
-//   block_line_update_kernel    line_update_kernel, lane = (row, column)
+// Row-major n x KP panels; the factor arrays are the single-vector ones, indexed by row.  K-Line and
+// the strided seams are their own kernels at KP > 1 (line_*_kernel<T, KP>, seam_stride_kernel<T, KP>).
+// The x direction keeps kernels of its own, because the panel makes it a different algorithm (a
+// merge with linex_kernel / seamx_kernel would only add branches); per (row, column) they still
+// evaluate the expressions of the single-vector kernel in the same order, so column j has its bits:
 //   block_linex_fwd / _bwd      linex_kernel<LX_FWD / LX_BWD>, lane = (run, column): an x line has
 //                               stride KP in the panel, so the KP columns of a step are one segment
 //                               and the walk needs no transposition through LDS; the rows of the
 //                               next LINEXB_BATCH steps are loaded before this batch is walked
-//   block_seamx / _stride       seamx_kernel / seam_stride_kernel, lane = (line, column)
+//   block_seamx                 seamx_kernel, lane = (line, column): the butterfly as seen from one lane
 namespace {
-__host__ __device__ constexpr int block_few_chunk_c(int kp) { return kp <= 4 ? LINE_FEW_CHUNK : 4 * LINE_FEW_CHUNK / kp; }
-
-template <int KP>
-__global__ __launch_bounds__(256) void block_line_seg_kernel(int64_t n, int64_t s, int64_t nch, int64_t nseg,
-                                                             const double* __restrict__ r,
-                                                             const double* __restrict__ dl,
-                                                             const double* __restrict__ ip,
-                                                             const double* __restrict__ cp, double* __restrict__ y) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nch * nseg * KP) return;
-  const int j = (int)(t % KP);
-  const int64_t q = t / KP;
-  const int64_t g = q / nch, c = q - g * nch;
-  const int64_t i0 = (g * LINE_SEG) * s + c;
-  double yv[LINE_INT];
-  double prev = 0.0;
-#pragma unroll
-  for (int k = 0; k < LINE_INT; ++k) {
-    const int64_t i = i0 + (int64_t)k * s;
-    if (i < n) prev = k > 0 ? (r[i * KP + j] - dl[i] * prev) * ip[i] : r[i * KP + j] * ip[i];
-    else prev = 0.0;
-    yv[k] = prev;
-  }
-  double nxt = 0.0;
-#pragma unroll
-  for (int k = LINE_INT - 1; k >= 0; --k) {
-    const int64_t i = i0 + (int64_t)k * s;
-    if (i < n) {
-      nxt = yv[k] - cp[i] * nxt;
-      y[i * KP + j] = nxt;
-    }
-  }
-}
-
-// line_sep_rhs of column j
-template <int KP>
-__device__ inline double block_line_sep_rhs(int64_t i, int j, int64_t n, int64_t s, const double* r, const double* dl,
-                                            const double* w, const double* y) {
-  double b = r[i * KP + j] - dl[i] * y[(i - s) * KP + j];
-  if (i + s < n) b = b - w[i] * y[(i + s) * KP + j];
-  return b;
-}
-template <int KP>
-__global__ __launch_bounds__(64) void block_line_sep_many_kernel(int64_t n, int64_t s, int64_t nch, const double* r,
-                                                                 const double* dl, const double* ip, const double* cp,
-                                                                 const double* v, const double* w, double* y) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nch * KP) return;
-  const int j = (int)(t % KP);
-  const int64_t c = t / KP;
-  const int64_t step = (int64_t)LINE_SEG * s;
-  const int64_t first = (int64_t)LINE_INT * s + c;
-  if (first >= n) return;
-  const int64_t nsep = (n - 1 - first) / step + 1;
-  double tv = 0.0;
-  for (int64_t g0 = 0; g0 < nsep; g0 += LINE_BATCH) {
-    double b[LINE_BATCH], lo[LINE_BATCH], pv[LINE_BATCH];
-#pragma unroll
-    for (int k = 0; k < LINE_BATCH; ++k) {
-      const int64_t i = first + (g0 + k) * step;
-      const bool on = g0 + k < nsep;
-      b[k] = on ? block_line_sep_rhs<KP>(i, j, n, s, r, dl, w, y) : 0.0;
-      lo[k] = on ? v[i] : 0.0;
-      pv[k] = on ? ip[i] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < LINE_BATCH; ++k) {
-      if (g0 + k < nsep) {
-        tv = (b[k] - lo[k] * tv) * pv[k];
-        y[(first + (g0 + k) * step) * KP + j] = tv;
-      }
-    }
-  }
-  double x = 0.0;
-  for (int64_t g1 = nsep; g1 > 0; g1 -= LINE_BATCH) {  // separators g1-1, g1-2, ...
-    double tt[LINE_BATCH], cc[LINE_BATCH];
-#pragma unroll
-    for (int k = 0; k < LINE_BATCH; ++k) {
-      const int64_t g = g1 - 1 - k;
-      const int64_t i = first + g * step;
-      tt[k] = g >= 0 ? y[i * KP + j] : 0.0;
-      cc[k] = g >= 0 ? cp[i] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < LINE_BATCH; ++k) {
-      const int64_t g = g1 - 1 - k;
-      if (g >= 0) {
-        x = tt[k] - cc[k] * x;
-        y[(first + g * step) * KP + j] = x;
-      }
-    }
-  }
-}
-// chunks of block_few_chunk_c(KP) separators: (KP + 2) doubles of LDS each, 48 KB at the most
-template <int KP>
-__global__ __launch_bounds__(256) void block_line_sep_few_kernel(int64_t n, int64_t s, const double* r,
-                                                                const double* dl, const double* ip, const double* cp,
-                                                                const double* v, const double* w, double* y) {
-  constexpr int CH = block_few_chunk_c(KP);
-  __shared__ double b[CH * KP], lo[CH], pv[CH];
-  const int tid = threadIdx.x;
-  const int64_t c = blockIdx.x;
-  const int64_t step = (int64_t)LINE_SEG * s;
-  const int64_t first = (int64_t)LINE_INT * s + c;
-  if (first >= n) return;  // the whole workgroup
-  const int64_t nsep = (n - 1 - first) / step + 1;
-  double carry = 0.0;  // lanes < KP: the recurrence of column tid, kept from chunk to chunk
-  for (int64_t g0 = 0; g0 < nsep; g0 += CH) {
-    const int m = (int)(nsep - g0 < CH ? nsep - g0 : CH);
-    for (int e = tid; e < m * KP; e += 256) {
-      const int g = e / KP, j = e % KP;
-      const int64_t i = first + (g0 + g) * step;
-      b[e] = block_line_sep_rhs<KP>(i, j, n, s, r, dl, w, y);
-      if (j == 0) {
-        lo[g] = v[i];
-        pv[g] = ip[i];
-      }
-    }
-    __syncthreads();
-    if (tid < KP) {
-      double t = carry;
-      for (int g = 0; g < m; ++g) {
-        t = (b[g * KP + tid] - lo[g] * t) * pv[g];
-        b[g * KP + tid] = t;
-      }
-      carry = t;
-    }
-    __syncthreads();
-    for (int e = tid; e < m * KP; e += 256) y[(first + (g0 + e / KP) * step) * KP + e % KP] = b[e];
-    __syncthreads();
-  }
-  carry = 0.0;
-  for (int64_t g1 = nsep; g1 > 0; g1 -= CH) {  // separators [g1 - m, g1)
-    const int m = (int)(g1 < CH ? g1 : CH);
-    const int64_t gb = g1 - m;
-    for (int e = tid; e < m * KP; e += 256) {
-      const int g = e / KP, j = e % KP;
-      const int64_t i = first + (gb + g) * step;
-      b[e] = y[i * KP + j];
-      if (j == 0) lo[g] = cp[i];
-    }
-    __syncthreads();
-    if (tid < KP) {
-      double x = carry;
-      for (int g = m - 1; g >= 0; --g) {
-        x = b[g * KP + tid] - lo[g] * x;
-        b[g * KP + tid] = x;
-      }
-      carry = x;
-    }
-    __syncthreads();
-    for (int e = tid; e < m * KP; e += 256) y[(first + (gb + e / KP) * step) * KP + e % KP] = b[e];
-    __syncthreads();
-  }
-}
-
-template <int KP>
-__global__ __launch_bounds__(256) void block_line_update_kernel(int64_t n, uint32_t s, const double* __restrict__ y,
-                                                               const double* __restrict__ v,
-                                                               const double* __restrict__ w, double omega,
-                                                               double* __restrict__ u) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n * KP) return;
-  const int64_t i = e / KP;  // < 2^31: the row, not the panel index, goes through the 32-bit division
-  const int j = (int)(e % KP);
-  const uint32_t p = (uint32_t)i / s;
-  const uint32_t k = p % LINE_SEG;
-  double x = y[e];
-  if (k != LINE_INT) {
-    const int64_t before = i - ((int64_t)k + 1) * s;
-    const int64_t after = i + (int64_t)(LINE_INT - k) * s;
-    if (before >= 0) x = x - v[i] * y[before * KP + j];
-    if (after < n) x = x - w[i] * y[after * KP + j];
-  }
-  u[e] = u[e] + omega * x;
-}
-
 constexpr int LINEXB_BATCH = 8;
 // y_i = (r_i - dl_i y_(i-1)) ip_i over the rows [run len, run len + len) below n, in place
 template <int KP>
@@ -7798,68 +7656,7 @@ __global__ __launch_bounds__(256) void block_seamx_kernel(int64_t nlines, int64_
   r[e0] = r[e0] - fac * coef[nlines + line];
   r[e1] = r[e1] - fac * coef[2 * nlines + line];
 }
-__global__ __launch_bounds__(256) void block_seam_stride_kernel(int64_t nlines, int64_t s, int64_t m, int kp,
-                                                                const double* __restrict__ p,
-                                                                const double* __restrict__ coef, double* r) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t line = t / kp;
-  const int j = (int)(t % kp);
-  if (line >= nlines) return;
-  const int64_t b = line / s;
-  const int64_t i0 = b * s * m + (line - b * s);
-  double acc = 0.0;
-  for (int64_t k0 = 0; k0 < m; k0 += SEAM_WALK) {
-    double pv[SEAM_WALK], rv[SEAM_WALK];
-#pragma unroll
-    for (int q = 0; q < SEAM_WALK; ++q) {
-      const bool on = k0 + q < m;
-      pv[q] = on ? p[i0 + (k0 + q) * s] : 0.0;
-      rv[q] = on ? r[(i0 + (k0 + q) * s) * kp + j] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < SEAM_WALK; ++q)
-      if (k0 + q < m) acc = acc + pv[q] * rv[q];
-  }
-  const double fac = acc / coef[line];
-  const int64_t e0 = i0 * kp + j, e1 = (i0 + (m - 1) * s) * kp + j;
-  r[e0] = r[e0] - fac * coef[nlines + line];
-  r[e1] = r[e1] - fac * coef[2 * nlines + line];
-}
-inline bool block_kp_ok(int kp) { return kp == 1 || kp == 2 || kp == 4 || kp == 8 || kp == 16; }
-// CALL(KP) with the pitch as a constant
-#define AMG_BLOCK_KP(kp, CALL) \
-  switch (kp) {                \
-    case 1: CALL(1); break;    \
-    case 2: CALL(2); break;    \
-    case 4: CALL(4); break;    \
-    case 8: CALL(8); break;    \
-    default: CALL(16); break;  \
-  }
 }  // namespace
-
-int block_line_few_chunk(int kp) { return block_few_chunk_c(kp); }
-
-hipError_t launch_block_line_solve(int kp, const LineRef& L, const double* r, double* y, double* u, double omega,
-                                   hipStream_t st) {
-  const int64_t n = L.n, s = L.s;
-  if (!block_kp_ok(kp) || n <= 0 || s < 1 || s > n || n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-  const int64_t nch = line_chains(n, s), nseg = line_segments(n, s);
-  const bool sep = (int64_t)LINE_INT * s < n, few = line_few_chains(s);
-#define AMG_BLOCK_LINE(KP)                                                                                           \
-  hipLaunchKernelGGL(block_line_seg_kernel<KP>, line_grid(nch * nseg * KP), dim3(256), 0, st, n, s, nch, nseg, r,    \
-                     L.dl, L.ip, L.cp, y);                                                                           \
-  if (sep && few)                                                                                                    \
-    hipLaunchKernelGGL(block_line_sep_few_kernel<KP>, dim3((unsigned)nch), dim3(256), 0, st, n, s, r, L.dl, L.ip,    \
-                       L.cp, L.v, L.w, y);                                                                           \
-  else if (sep)                                                                                                      \
-    hipLaunchKernelGGL(block_line_sep_many_kernel<KP>, line_grid(nch * KP, 64), dim3(64), 0, st, n, s, nch, r, L.dl, \
-                       L.ip, L.cp, L.v, L.w, y);                                                                     \
-  hipLaunchKernelGGL(block_line_update_kernel<KP>, line_grid(n * KP), dim3(256), 0, st, n, (uint32_t)s,              \
-                     (const double*)y, L.v, L.w, omega, u)
-  AMG_BLOCK_KP(kp, AMG_BLOCK_LINE)
-#undef AMG_BLOCK_LINE
-  return hipGetLastError();
-}
 
 hipError_t launch_block_linex_solve(int kp, const LineXRef& L, double* r, double* u, double omega, hipStream_t st) {
   if (!block_kp_ok(kp) || !linex_ok(L)) return hipErrorInvalidValue;
@@ -7880,7 +7677,10 @@ hipError_t launch_block_line_seam(int kp, const SeamRef& S, double* r, hipStream
   const int64_t nlines = n / m;
   const dim3 grid = line_grid(nlines * kp);
   if (s > 1) {
-    hipLaunchKernelGGL(block_seam_stride_kernel, grid, dim3(256), 0, st, nlines, s, m, kp, S.p, S.coef, r);
+#define AMG_BLOCK_SEAM(KP) \
+  hipLaunchKernelGGL((seam_stride_kernel<double, KP>), grid, dim3(256), 0, st, nlines, s, m, S.p, S.coef, r)
+    AMG_BLOCK_KP(kp, AMG_BLOCK_SEAM)
+#undef AMG_BLOCK_SEAM
     return hipGetLastError();
   }
 #define AMG_BLOCK_SEAMX(W) \

@@ -57,12 +57,16 @@ hipError_t launch_gershgorin(int64_t n, const int32_t* rowptr, const int32_t* co
 // (kernels.hip: K-Line).  n doubles each, 1 <= s <= n < 2^31 (the launchers refuse anything else; s = n
 // stands for every stride >= n: each row its own chain).
 constexpr int LINE_SEG = 32;
-struct LineRef {
+// T = double: the cycle and the set-up.  T = float: the single-precision cycle's float copies of the
+// same factors (no float elimination); the set-up-only members stay at their defaults there.
+template <typename T>
+struct LineRefT {
   int64_t n = 0, s = 1;
   int64_t m = 0;  // set-up only, > 0: chain positions come in grid lines of m; entries across a line end stay out of T
   int32_t cyc = 0;  // set-up only, with m >= 3: 1 = T' of a cyclic line (SeamRef), 2 = its transpose
-  double *dl = nullptr, *ip = nullptr, *cp = nullptr, *v = nullptr, *w = nullptr;
+  T *dl = nullptr, *ip = nullptr, *cp = nullptr, *v = nullptr, *w = nullptr;
 };
+using LineRef = LineRefT<double>;
 // stride rule on a device CSR matrix: out[1] = the largest distance d = |j - i| >= 1 whose weight
 // w(d) = sum |a_ij| reaches (1 - 1e-9) max w, or 1 without off-diagonal entries; out[0] = bits of
 // max w.  wd: n doubles of scratch.  line_stride_host: the same rule on host arrays.
@@ -81,13 +85,8 @@ int64_t line_setup_host(int64_t n, int64_t s, const int32_t* rowptr, const int32
 hipError_t launch_line_solve(const LineRef& L, const double* r, double* y, double* u, double omega,
                              hipStream_t st);
 bool line_few_chains(int64_t s);  // the reduced systems run as one workgroup per chain
-// The solve in float (single-precision cycle): the same kernels instantiated on float, on float copies
-// of the factors (no float elimination).  y: n floats of scratch.
-struct LineRefF32 {
-  int64_t n = 0, s = 1;
-  const float *dl = nullptr, *ip = nullptr, *cp = nullptr, *v = nullptr, *w = nullptr;
-};
-hipError_t launch_line_solve_f32(const LineRefF32& L, const float* r, float* y, float* u, float omega,
+// The solve in float (single-precision cycle): the same kernels instantiated on float.  y: n floats of scratch.
+hipError_t launch_line_solve_f32(const LineRefT<float>& L, const float* r, float* y, float* u, float omega,
                                  hipStream_t st);
 // K-LineX, the x lines of a tensor grid (AMG_HIP_SM_LINE_ALT): n / nx lines of nx rows, each
 // contiguous in memory.  T_x = the diagonal of A and its entries at column offsets +-1 that stay
@@ -95,11 +94,13 @@ hipError_t launch_line_solve_f32(const LineRefF32& L, const float* r, float* y, 
 // cp = 0 on the last row of every line.  A wave walks LINEX_RUNS runs of whole lines (linex_run(nx)
 // rows each) in chunks of LINEX_COLS columns through LDS (kernels.hip: K-LineX).  n < 2^31.
 constexpr int LINEX_COLS = 64, LINEX_RUNS = 8;
-struct LineXRef {
+template <typename T>
+struct LineXRefT {
   int64_t n = 0, nx = 1;
-  double *dl = nullptr, *ip = nullptr, *cp = nullptr;
+  T *dl = nullptr, *ip = nullptr, *cp = nullptr;
   int32_t cyc = 0;  // set-up only, with nx >= 3: as LineRef::cyc
 };
+using LineXRef = LineXRefT<double>;
 int64_t linex_run(int64_t nx);  // rows of one run: nx, or the whole lines that fit LINEX_COLS
 // extract T_x from CSR(A) and factor it; bad as launch_line_setup.  linex_setup_host: the same
 // elimination on the host, factors discarded; returns the first row with a bad pivot or -1.
@@ -110,8 +111,7 @@ int64_t linex_setup_host(int64_t n, int64_t nx, const int32_t* rowptr, const int
 // u += omega T_x^-1 r; r is overwritten (the forward values).  Two launches.
 hipError_t launch_linex_solve(const LineXRef& L, double* r, double* u, double omega, hipStream_t st);
 // the same two launches on float copies of dl, ip, cp (chunks of LINEX_COLS columns as in double)
-hipError_t launch_linex_solve_f32(int64_t n, int64_t nx, const float* dl, const float* ip, const float* cp, float* r,
-                                  float* u, float omega, hipStream_t st);
+hipError_t launch_linex_solve_f32(const LineXRefT<float>& L, float* r, float* u, float omega, hipStream_t st);
 // K-LineSeam, cyclic lines along a periodic axis (AMG_HIP_SM_LINE_ALT with cyclic_lines): the lines of
 // stride s and length m >= 3 (n a multiple of s m; row i on position (i / s) % m of its line, first row
 // i0, last row i1) carry the wrap entries alpha = a(i0, i1), beta = a(i1, i0).  With gamma = -a(i0, i0),
@@ -119,11 +119,13 @@ hipError_t launch_linex_solve_f32(int64_t n, int64_t nx, const float* dl, const 
 //   u = gamma e(i0) + beta e(i1), v = e(i0) + (alpha / gamma) e(i1):   cyclic T = T' + u v^T,
 // so T^-1 r = T'^-1 (r - fac u), fac = (p . r) / den, p = T'^-T v, den = 1 + v . T'^-1 u
 // (Sherman-Morrison).  p: n doubles; coef: den | gamma | beta, n / m doubles each.
-struct SeamRef {
+template <typename T>
+struct SeamRefT {
   int64_t n = 0, s = 1, m = 0;
-  const double* p = nullptr;
-  const double* coef = nullptr;
+  const T* p = nullptr;
+  const T* coef = nullptr;
 };
+using SeamRef = SeamRefT<double>;
 // set-up: u and v (n doubles each); then coef from q = T'^-1 u, bad as launch_line_setup (the first
 // row of a line whose den is zero or not finite).  seam_setup_host: the den check on the host with a
 // plain Thomas solve; returns that row or -1.
@@ -135,9 +137,8 @@ int64_t seam_setup_host(int64_t n, int64_t s, int64_t m, const int32_t* rowptr, 
                         const double* val);
 // r(i0) -= fac gamma, r(i1) -= fac beta on every line, in place.  One launch.
 hipError_t launch_line_seam(const SeamRef& S, double* r, hipStream_t st);
-// the same launch on float copies of p and coef (SeamRef's n, s, m)
-hipError_t launch_line_seam_f32(int64_t n, int64_t s, int64_t m, const float* p, const float* coef, float* r,
-                                hipStream_t st);
+// the same launch on float copies of p and coef
+hipError_t launch_line_seam_f32(const SeamRefT<float>& S, float* r, hipStream_t st);
 // Same operations on a SELL-64 matrix (64-row panels, lane-interleaved):
 // soff[n/64 + 1] panel offsets, scol/sval padded with col = -1.
 // idx16 bit 0: scol holds int16 offsets from the diagonal column (pad -32768);
@@ -607,7 +608,7 @@ hipError_t launch_block_pcg_update_p(int kp, int64_t n, const double* num, const
 // the single-vector arrays (one entry per row, read once for the kp columns); r, y, u are n x kp
 // panels and every panel index is 64-bit (n < 2^31, n kp may pass it).  Per (row, column) the
 // expressions and their order are the single-vector kernels', so column j has their bits on column j.
-// u += omega T^-1 r: the three stages of launch_line_solve (lane = (segment, chain, column); (chain,
+// u += omega T^-1 r: launch_line_solve's kernels at pitch kp (lane = (segment, chain, column); (chain,
 // column) or a workgroup per chain with kp walking lanes where line_few_chains(s); (row, column))
 hipError_t launch_block_line_solve(int kp, const LineRef& L, const double* r, double* y, double* u, double omega,
                                    hipStream_t st);

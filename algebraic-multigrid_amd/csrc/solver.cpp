@@ -23,6 +23,7 @@
 #include <dlfcn.h>
 
 #include "../../include/amg_hip.h"
+#include "capture_once.hpp"
 #include "host_setup.hpp"
 #include "kernels.hpp"
 
@@ -926,13 +927,6 @@ amg_hip_status line_setup_dev(int l, int64_t n, const int32_t* rowptr, const int
   if (h[0] != ~(uint64_t)0) return fail(AMG_HIP_EINVAL, line_bad_pivot(l, (int64_t)h[0], dir));
   return AMG_HIP_OK;
 }
-// n_iters sweeps u <- u + omega T^-1 (f - A u); r: n doubles of scratch for the residual
-hipError_t launch_line_sweep(const DevMat& A, const LineOnDev& D, double* u, const double* f, double* r,
-                             double omega, hipStream_t st) {
-  hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
-  if (e != hipSuccess) return e;
-  return launch_line_solve(D.ref(), r, D.y.as<double>(), u, omega, st);
-}
 
 // ---- alternating-direction line smoother (AMG_HIP_SM_LINE_ALT; kernels.hip: K-LineX, K-Line) ----
 // The directions of a level: its axes of length >= 2 in the order x, y, z.  x runs as K-LineX, y and
@@ -992,6 +986,11 @@ struct AltOnDev {
     S.coef = seam_coef[d].as<double>();
     return S;
   }
+  // What sub-sweep d runs (d = 0 on a level without directions): K-LineSeam first where cyclic(d), then
+  // K-LineX where along_x(d), else K-Line with yz[yz_of(d)]
+  bool cyclic(int d) const { return n_dir > 0 && cyc[d]; }
+  bool along_x(int d) const { return n_dir > 0 && axis[d] == 0; }
+  int yz_of(int d) const { return n_dir == 0 || axis[d] == 0 ? 0 : axis[d] - 1; }
   // K-LineSeam of a cyclic direction: p and r in (16 B per row); den, gamma, beta in and the two ends
   // of r out (40 B per line)
   double seam_bytes(int d) const {
@@ -1107,15 +1106,77 @@ amg_hip_status alt_setup_dev(int l, const int32_t* rowptr, const int32_t* col, c
   }
   return AMG_HIP_OK;
 }
-// sub-sweep d of one application: u <- u + omega T_a^-1 (f - A u); r: n doubles of scratch
+
+// ---- one line sub-sweep and one smoothing application, for the double, the block and the float cycle ----
+// The launchers of one precision and pitch behind one signature.  kp = 0: plain double vectors (the
+// single-vector kernels); kp >= 1: the n x kp panels of the block cycle (K-LineBlock).  Float vectors
+// are always plain.
+hipError_t line_seam_any(int kp, const SeamRef& S, double* r, hipStream_t st) {
+  return kp ? launch_block_line_seam(kp, S, r, st) : launch_line_seam(S, r, st);
+}
+hipError_t line_seam_any(int, const SeamRefT<float>& S, float* r, hipStream_t st) {
+  return launch_line_seam_f32(S, r, st);
+}
+hipError_t linex_solve_any(int kp, const LineXRef& X, double* r, double* u, double omega, hipStream_t st) {
+  return kp ? launch_block_linex_solve(kp, X, r, u, omega, st) : launch_linex_solve(X, r, u, omega, st);
+}
+hipError_t linex_solve_any(int, const LineXRefT<float>& X, float* r, float* u, float omega, hipStream_t st) {
+  return launch_linex_solve_f32(X, r, u, omega, st);
+}
+hipError_t line_solve_any(int kp, const LineRef& Y, const double* r, double* y, double* u, double omega,
+                          hipStream_t st) {
+  return kp ? launch_block_line_solve(kp, Y, r, y, u, omega, st) : launch_line_solve(Y, r, y, u, omega, st);
+}
+hipError_t line_solve_any(int, const LineRefT<float>& Y, const float* r, float* y, float* u, float omega,
+                          hipStream_t st) {
+  return launch_line_solve_f32(Y, r, y, u, omega, st);
+}
+// A sub-sweep after its residual r = f - A u: K-LineSeam on r where the direction is cyclic (S), then
+// u += omega T^-1 r as K-LineX where the direction is the x axis (X), else as K-Line with Y and the
+// scratch y.  X and S are null where the direction has none.  dry: launch nothing.
+template <typename T>
+hipError_t launch_line_dir(const LineRefT<T>& Y, const LineXRefT<T>* X, const SeamRefT<T>* S, int kp, T* r, T* y,
+                           T* u, T omega, bool dry, hipStream_t st) {
+  if (dry) return hipSuccess;
+  hipError_t e;
+  if (S && (e = line_seam_any(kp, *S, r, st)) != hipSuccess) return e;
+  return X ? linex_solve_any(kp, *X, r, u, omega, st) : line_solve_any(kp, Y, r, y, u, omega, st);
+}
+// launch_line_dir for direction d of D (AltOnDev::cyclic).  y: the scratch panel of the block cycle;
+// plain vectors (kp = 0) use the direction's own
+hipError_t launch_alt_dir(const AltOnDev& D, int d, int kp, double* r, double* y, double* u, double omega, bool dry,
+                          hipStream_t st) {
+  const SeamRef S = D.seam(d);
+  const LineXRef X = D.xref();
+  const LineOnDev& Y = D.yz[D.yz_of(d)];
+  return launch_line_dir(Y.ref(), D.along_x(d) ? &X : nullptr, D.cyclic(d) ? &S : nullptr, kp, r,
+                         kp ? y : Y.y.as<double>(), u, omega, dry, st);
+}
+// One smoothing application of a line smoother: `iters` times its nd sub-sweeps, the directions
+// ascending on the way down and descending on the way up (reverse).  sub(d) enqueues sub-sweep d.
+template <typename F>
+amg_hip_status line_subsweeps(int64_t iters, int nd, bool reverse, F&& sub) {
+  for (int64_t it = 0; it < iters; ++it)
+    for (int q = 0; q < nd; ++q) AMG_TRY(sub(reverse ? nd - 1 - q : q));
+  return AMG_HIP_OK;
+}
+// sub-sweeps of one application: AMG_HIP_SM_LINE_ALT one per direction, AMG_HIP_SM_LINE_JACOBI one
+int line_dirs(int32_t smoother, const AltOnDev& D) {
+  return smoother == AMG_HIP_SM_LINE_ALT ? std::max(D.n_dir, 1) : 1;
+}
+// sub-sweep of AMG_HIP_SM_LINE_JACOBI on plain vectors: u <- u + omega T^-1 (f - A u); r: n doubles of scratch
+hipError_t launch_line_sweep(const DevMat& A, const LineOnDev& D, double* u, const double* f, double* r,
+                             double omega, hipStream_t st) {
+  hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
+  if (e != hipSuccess) return e;
+  return launch_line_dir<double>(D.ref(), nullptr, nullptr, 0, r, D.y.as<double>(), u, omega, false, st);
+}
+// sub-sweep d of AMG_HIP_SM_LINE_ALT: u <- u + omega T_a^-1 (f - A u)
 hipError_t launch_alt_subsweep(const DevMat& A, const AltOnDev& D, int d, double* u, const double* f, double* r,
                                double omega, hipStream_t st) {
   hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
   if (e != hipSuccess) return e;
-  if (D.n_dir > 0 && D.cyc[d] && (e = launch_line_seam(D.seam(d), r, st)) != hipSuccess) return e;
-  if (D.n_dir > 0 && D.axis[d] == 0) return launch_linex_solve(D.xref(), r, u, omega, st);
-  const LineOnDev& Y = D.yz[D.n_dir == 0 ? 0 : D.axis[d] - 1];
-  return launch_line_solve(Y.ref(), r, Y.y.as<double>(), u, omega, st);
+  return launch_alt_dir(D, d, 0, r, nullptr, u, omega, false, st);
 }
 
 struct SpikeOnDev {  // device copy of a SpikeFactor + scratch
@@ -1463,8 +1524,8 @@ struct F32Mat {
 // float copies of one K-Line factor set (LineOnDev) and its scratch vector
 struct F32Line {
   DevMem dl, ip, cp, v, w, y;
-  LineRefF32 ref(const LineOnDev& D) const {
-    LineRefF32 R;
+  LineRefT<float> ref(const LineOnDev& D) const {
+    LineRefT<float> R;
     R.n = D.n;
     R.s = D.s;
     R.dl = dl.as<float>();
@@ -1485,6 +1546,24 @@ struct F32Level {
   DevMem xdl, xip, xcp;          // LINE_ALT: AltOnDev's K-LineX factors
   F32Line yz[2];                 //           AltOnDev::yz
   DevMem seam_p[3], seam_coef[3];  //         AltOnDev's K-LineSeam arrays
+  LineXRefT<float> xref(const AltOnDev& D) const {
+    LineXRefT<float> R;
+    R.n = D.n;
+    R.nx = D.len[0];
+    R.dl = xdl.as<float>();
+    R.ip = xip.as<float>();
+    R.cp = xcp.as<float>();
+    return R;
+  }
+  SeamRefT<float> seam(const AltOnDev& D, int d) const {
+    SeamRefT<float> S;
+    S.n = D.n;
+    S.s = D.stride[d];
+    S.m = D.len[d];
+    S.p = seam_p[d].as<float>();
+    S.coef = seam_coef[d].as<float>();
+    return S;
+  }
 };
 struct F32 {
   bool ready = false;
@@ -1948,30 +2027,22 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
       }
       return AMG_HIP_OK;
     }
-    case AMG_HIP_SM_LINE_JACOBI: {
-      // residual of the old u into tmp, then K-Line adds omega T^-1 tmp to u in place (phases 1 / 2
-      // have no shortcut: u is read as it is); plain launches, r stays the cycle's residual
-      const DevMat& A = L.A_rows;
-      for (int it = 0; it < iters; ++it) {
-        HIP_TRY(launch_line_sweep(A, L.line, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
-                                  s->opt.omega, st));
-        s->acct(mat_bytes(A) + 24.0 * L.n + L.line.solve_bytes());  // matrix, f, u, r; K-Line
-      }
-      return AMG_HIP_OK;
-    }
+    case AMG_HIP_SM_LINE_JACOBI:
     case AMG_HIP_SM_LINE_ALT: {
-      // one application = one sub-sweep per direction (ascending on the way down, descending on the
-      // way up), each the residual of the current u into tmp and then the direction's line solve
+      // a sub-sweep: the residual of the current u into tmp, then the line solve adds omega T^-1 tmp
+      // to u in place (phases 1 / 2 have no shortcut: u is read as it is); plain launches, r stays the
+      // cycle's residual.  LINE_ALT: one sub-sweep per direction
       const DevMat& A = L.A_rows;
-      const int nd = std::max(L.alt.n_dir, 1);
-      for (int it = 0; it < iters; ++it)
-        for (int q = 0; q < nd; ++q) {
-          const int d = reverse ? nd - 1 - q : q;
-          HIP_TRY(launch_alt_subsweep(A, L.alt, d, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
-                                      s->opt.omega, st));
-          s->acct(mat_bytes(A) + 24.0 * L.n + L.alt.solve_bytes(d));  // matrix, f, u, r; the line solve
-        }
-      return AMG_HIP_OK;
+      const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
+      return line_subsweeps(iters, line_dirs(s->opt.smoother, L.alt), reverse, [&](int d) {
+        HIP_TRY(alt ? launch_alt_subsweep(A, L.alt, d, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
+                                          s->opt.omega, st)
+                    : launch_line_sweep(A, L.line, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
+                                        s->opt.omega, st));
+        // matrix, f, u, r; the line solve
+        s->acct(mat_bytes(A) + 24.0 * L.n + (alt ? L.alt.solve_bytes(d) : L.line.solve_bytes()));
+        return AMG_HIP_OK;
+      });
     }
   }
   return fail(AMG_HIP_EINVAL, "unknown smoother kind");
@@ -2432,17 +2503,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
 
 amg_hip_status ensure_graph(amg_hip_solver* s) {
   if (s->graph_ready) return AMG_HIP_OK;
-  HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-  amg_hip_status r = enqueue_vcycle(s);
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(s->stream, &g);
-  if (r != AMG_HIP_OK) {
-    if (g) (void)hipGraphDestroy(g);
-    return r;
-  }
-  if (e != hipSuccess) return fail(AMG_HIP_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  s->graph = g;
-  HIP_TRY(hipGraphInstantiate(&s->graph_exec, s->graph, nullptr, nullptr, 0));
+  AMG_TRY(capture_once(s->stream, [s] { return enqueue_vcycle(s); }, &s->graph, &s->graph_exec));
   s->graph_ready = true;
   return AMG_HIP_OK;
 }
@@ -3879,27 +3940,15 @@ void bacct_line(amg_hip_solver* s, const LineOnDev& D) {
   const int64_t sep = D.separators();
   s->bacct(40.0 * (double)D.n, 40.0 * (double)(D.n - sep) + 56.0 * (double)sep);
 }
-// sub-sweep d of AMG_HIP_SM_LINE_ALT on the panels (launch_alt_subsweep after its residual): T holds
-// the residual, U is updated in place
-amg_hip_status enqueue_block_alt_solve(amg_hip_solver* s, const AltOnDev& D, int d, int kp, BlockLevel& Q, bool dry) {
-  hipStream_t st = s->stream;
-  double* r = Q.T.as<double>();
-  double* u = Q.U.as<double>();
-  if (D.n_dir > 0 && D.cyc[d]) {
-    BLK(launch_block_line_seam(kp, D.seam(d), r, st));
+// the bytes of sub-sweep d of AMG_HIP_SM_LINE_ALT on the panels, after its residual
+void bacct_alt(amg_hip_solver* s, const AltOnDev& D, int d) {
+  if (D.cyclic(d)) {
     // p, then den, gamma, beta of every line once; r in and the two ends of r out per column
     const double lines = (double)(D.n / D.len[d]);
     s->bacct(8.0 * (double)D.n + 24.0 * lines, 8.0 * (double)D.n + 16.0 * lines);
   }
-  if (D.n_dir > 0 && D.axis[d] == 0) {
-    BLK(launch_block_linex_solve(kp, D.xref(), r, u, s->opt.omega, st));
-    s->bacct(24.0 * (double)D.n, 40.0 * (double)D.n);  // dl, ip, cp; r, y, y, u, u
-    return AMG_HIP_OK;
-  }
-  const LineOnDev& Y = D.yz[D.n_dir == 0 ? 0 : D.axis[d] - 1];
-  BLK(launch_block_line_solve(kp, Y.ref(), r, Q.Y.as<double>(), u, s->opt.omega, st));
-  bacct_line(s, Y);
-  return AMG_HIP_OK;
+  if (D.along_x(d)) s->bacct(24.0 * (double)D.n, 40.0 * (double)D.n);  // dl, ip, cp; r, y, y, u, u
+  else bacct_line(s, D.yz[D.yz_of(d)]);
 }
 
 // the smoothing of one level (enqueue_smooth's plain launches): U -> T -> U ..., home after an odd count;
@@ -3912,22 +3961,19 @@ amg_hip_status enqueue_block_smooth(amg_hip_solver* s, int l, int kp, bool dry, 
   if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
     const DevCsr& A = *Q.rows;
     const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
-    const int nd = alt ? std::max(L.alt.n_dir, 1) : 1;
-    for (int it = 0; it < s->opt.smoother_iters; ++it)
-      for (int q = 0; q < nd; ++q) {
-        BLK(launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
-                             Q.T.as<double>(), 1.0, st));
-        s->bacct(csr_bytes(A), 24.0 * n);  // matrix; u, f, r
-        if (alt) {
-          const amg_hip_status r = enqueue_block_alt_solve(s, L.alt, reverse ? nd - 1 - q : q, kp, Q, dry);
-          if (r != AMG_HIP_OK) return r;
-        } else {
-          BLK(launch_block_line_solve(kp, L.line.ref(), Q.T.as<double>(), Q.Y.as<double>(), Q.U.as<double>(),
-                                      s->opt.omega, st));
-          bacct_line(s, L.line);
-        }
-      }
-    return AMG_HIP_OK;
+    // a sub-sweep: T = F - A U, then the line solve updates U in place (Y: K-Line's scratch panel)
+    return line_subsweeps(s->opt.smoother_iters, line_dirs(s->opt.smoother, L.alt), reverse, [&](int d) {
+      BLK(launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
+                           Q.T.as<double>(), 1.0, st));
+      s->bacct(csr_bytes(A), 24.0 * n);  // matrix; u, f, r
+      HIP_TRY(alt ? launch_alt_dir(L.alt, d, kp, Q.T.as<double>(), Q.Y.as<double>(), Q.U.as<double>(), s->opt.omega,
+                                   dry, st)
+                  : launch_line_dir<double>(L.line.ref(), nullptr, nullptr, kp, Q.T.as<double>(), Q.Y.as<double>(),
+                                            Q.U.as<double>(), s->opt.omega, dry, st));
+      if (alt) bacct_alt(s, L.alt, d);
+      else bacct_line(s, L.line);
+      return AMG_HIP_OK;
+    });
   }
   double* a = Q.U.as<double>();
   double* b = Q.T.as<double>();
@@ -4071,19 +4117,8 @@ amg_hip_status run_block_cycles(amg_hip_solver* s, int kp, int32_t n) {
     return AMG_HIP_OK;
   }
   const int g = log2i(kp);
-  if (!B.exec[g]) {
-    HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    amg_hip_status r = enqueue_block_vcycle(s, kp, false);
-    hipGraph_t gr = nullptr;
-    hipError_t e = hipStreamEndCapture(s->stream, &gr);
-    if (r != AMG_HIP_OK) {
-      if (gr) (void)hipGraphDestroy(gr);
-      return r;
-    }
-    if (e != hipSuccess) return fail(AMG_HIP_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    B.graph[g] = gr;
-    HIP_TRY(hipGraphInstantiate(&B.exec[g], B.graph[g], nullptr, nullptr, 0));
-  }
+  if (!B.exec[g])
+    AMG_TRY(capture_once(s->stream, [s, kp] { return enqueue_block_vcycle(s, kp, false); }, &B.graph[g], &B.exec[g]));
   for (int i = 0; i < n; ++i) HIP_TRY(hipGraphLaunch(B.exec[g], s->stream));
   return AMG_HIP_OK;
 }
@@ -4259,21 +4294,17 @@ amg_hip_status enqueue_f32_line_subsweep(amg_hip_solver* s, int l, int d, bool d
   F32_DO(launch_mat_f32(CSR_RESID, Q.rows, u, Q.f.as<float>(), r, 1.0f, nullptr, 0.0f, st));
   s->facct(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);  // matrix; u, f in and r out
   if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI) {
-    F32_DO(launch_line_solve_f32(Q.line.ref(L.line), r, Q.line.y.as<float>(), u, omega, st));
+    HIP_TRY(launch_line_dir<float>(Q.line.ref(L.line), nullptr, nullptr, 0, r, Q.line.y.as<float>(), u, omega, dry,
+                                   st));
     s->facct(0.5 * L.line.solve_bytes());
     return AMG_HIP_OK;
   }
   const AltOnDev& D = L.alt;
-  if (D.n_dir > 0 && D.cyc[d])
-    F32_DO(launch_line_seam_f32(D.n, D.stride[d], D.len[d], Q.seam_p[d].as<float>(), Q.seam_coef[d].as<float>(), r,
-                                st));
-  if (D.n_dir > 0 && D.axis[d] == 0) {
-    F32_DO(launch_linex_solve_f32(D.n, D.len[0], Q.xdl.as<float>(), Q.xip.as<float>(), Q.xcp.as<float>(), r, u, omega,
-                                  st));
-  } else {
-    const int k = D.n_dir == 0 ? 0 : D.axis[d] - 1;
-    F32_DO(launch_line_solve_f32(Q.yz[k].ref(D.yz[k]), r, Q.yz[k].y.as<float>(), u, omega, st));
-  }
+  const SeamRefT<float> S = Q.seam(D, d);
+  const LineXRefT<float> X = Q.xref(D);
+  const int k = D.yz_of(d);
+  HIP_TRY(launch_line_dir(Q.yz[k].ref(D.yz[k]), D.along_x(d) ? &X : nullptr, D.cyclic(d) ? &S : nullptr, 0, r,
+                          Q.yz[k].y.as<float>(), u, omega, dry, st));
   s->facct(0.5 * D.solve_bytes(d));
   return AMG_HIP_OK;
 }
@@ -4289,13 +4320,8 @@ amg_hip_status enqueue_f32_smooth(amg_hip_solver* s, int l, bool dry, bool rever
   int64_t passes = 0;
   if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
     // enqueue_smooth's order: u is updated in place, so nothing has to come home
-    const int nd = s->opt.smoother == AMG_HIP_SM_LINE_ALT ? std::max(L.alt.n_dir, 1) : 1;
-    for (int it = 0; it < s->opt.smoother_iters; ++it)
-      for (int q = 0; q < nd; ++q) {
-        const amg_hip_status r = enqueue_f32_line_subsweep(s, l, reverse ? nd - 1 - q : q, dry);
-        if (r != AMG_HIP_OK) return r;
-      }
-    return AMG_HIP_OK;
+    return line_subsweeps(s->opt.smoother_iters, line_dirs(s->opt.smoother, L.alt), reverse,
+                          [&](int d) { return enqueue_f32_line_subsweep(s, l, d, dry); });
   }
   if (s->opt.smoother == AMG_HIP_SM_JACOBI) {
     for (int it = 0; it < s->opt.smoother_iters; ++it) {
@@ -4430,24 +4456,7 @@ amg_hip_status f32_apply(amg_hip_solver* s, const double* v, double* z) {
     amg_hip_status r = enqueue_f32_vcycle(s, false);
     if (r != AMG_HIP_OK) return r;
   } else {
-    if (!F.exec) {
-      HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-      amg_hip_status r = enqueue_f32_vcycle(s, false);
-      hipGraph_t gr = nullptr;
-      hipError_t e = hipStreamEndCapture(s->stream, &gr);
-      if (r != AMG_HIP_OK) {
-        if (gr) (void)hipGraphDestroy(gr);
-        return r;
-      }
-      if (e != hipSuccess) return fail(AMG_HIP_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-      e = hipGraphInstantiate(&F.exec, gr, nullptr, nullptr, 0);
-      if (e != hipSuccess) {
-        (void)hipGraphDestroy(gr);
-        F.exec = nullptr;
-        return fail(AMG_HIP_EHIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-      }
-      F.graph = gr;
-    }
+    if (!F.exec) AMG_TRY(capture_once(s->stream, [s] { return enqueue_f32_vcycle(s, false); }, &F.graph, &F.exec));
     HIP_TRY(hipGraphLaunch(F.exec, s->stream));
   }
   HIP_TRY(launch_to_f64(n, F.lv[0].u.as<float>(), z, s->stream));
@@ -5114,19 +5123,8 @@ amg_hip_status amg_hip_slab_run(amg_hip_solver* s, int32_t part) {
   if (r != AMG_HIP_OK) return r;
   if (!s->opt.use_graph) return enqueue_vcycle(s, part);
   const int gi = part - 1;
-  if (!sb.exec[gi]) {
-    HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    r = enqueue_vcycle(s, part);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(s->stream, &g);
-    if (r != AMG_HIP_OK) {
-      if (g) (void)hipGraphDestroy(g);
-      return r;
-    }
-    if (e != hipSuccess) return fail(AMG_HIP_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    sb.graph[gi] = g;
-    HIP_TRY(hipGraphInstantiate(&sb.exec[gi], g, nullptr, nullptr, 0));
-  }
+  if (!sb.exec[gi])
+    AMG_TRY(capture_once(s->stream, [s, part] { return enqueue_vcycle(s, part); }, &sb.graph[gi], &sb.exec[gi]));
   HIP_TRY(hipGraphLaunch(sb.exec[gi], s->stream));
   return AMG_HIP_OK;
 }
@@ -5574,8 +5572,7 @@ amg_hip_status amg_hip_f32_line_subsweep(amg_hip_solver* s, int32_t level, int32
   (void)reverse;  // a sub-sweep is one direction: the leg only orders them
   amg_hip_status r = f32_line_hook_ready(s, level, d < 0 || d > 2 ? "direction index out of range" : nullptr);
   if (r != AMG_HIP_OK) return r;
-  const int nd = s->opt.smoother == AMG_HIP_SM_LINE_ALT ? std::max(s->lv[level].alt.n_dir, 1) : 1;
-  if (d >= nd) return fail(AMG_HIP_EINVAL, "direction index out of range");
+  if (d >= line_dirs(s->opt.smoother, s->lv[level].alt)) return fail(AMG_HIP_EINVAL, "direction index out of range");
   return enqueue_f32_line_subsweep(s, level, d, false);
 }
 
@@ -6396,11 +6393,11 @@ static amg_hip_status smooth_line_alt(const std::string& who, int64_t n, const i
   HIP_TRY(upload(du, u, (size_t)n));
   HIP_TRY(upload(df, f, (size_t)n));
   HIP_TRY(dr.alloc(sizeof(double) * n));
-  const int nd = std::max(D.n_dir, 1);
-  for (int64_t it = 0; it < iters; ++it)
-    for (int q = 0; q < nd; ++q)
-      HIP_TRY(launch_alt_subsweep(M, D, reverse ? nd - 1 - q : q, du.as<double>(), df.as<double>(), dr.as<double>(),
-                                  omega, nullptr));
+  st = line_subsweeps(iters, line_dirs(AMG_HIP_SM_LINE_ALT, D), reverse != 0, [&](int d) {
+    HIP_TRY(launch_alt_subsweep(M, D, d, du.as<double>(), df.as<double>(), dr.as<double>(), omega, nullptr));
+    return AMG_HIP_OK;
+  });
+  if (st != AMG_HIP_OK) return st;
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(u, du.p, sizeof(double) * n, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
