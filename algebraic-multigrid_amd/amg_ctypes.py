@@ -187,6 +187,7 @@ _SIGS = {
     "amg_hip_set_patch_tile_flags": (None, [C.c_int32]),
     "amg_hip_set_patch_xf": (None, [C.c_int32]),
     "amg_hip_set_patch_tall": (None, [C.c_int32]),
+    "amg_hip_set_patch_seam": (None, [C.c_int32]),
     "amg_hip_patch_leg_lines": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "amg_hip_create_rs": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, C.c_double, C.c_int64,
                                     C.POINTER(Options), C.POINTER(C.c_void_p)]),
@@ -411,6 +412,10 @@ def set_patch_xf(on):
 
 def set_patch_tall(on):
     lib().amg_hip_set_patch_tall(int(bool(on)))
+
+
+def set_patch_seam(on):
+    lib().amg_hip_set_patch_seam(int(bool(on)))
 
 
 def set_tail_fusion(on):
@@ -1111,13 +1116,15 @@ class Multigrid:
         return a.value, b.value
 
     def cycle_must_move(self, part=0):
-        """bytes the launches of one V-cycle (or of one part of a sharded one) have to move"""
+        """bytes the launches of one V-cycle (or of one part of a sharded one) have to move; part 4: of one
+        steady-state cycle of vcycle(n >= 2), which the K-Patch seam makes 25 n_0 bytes lighter"""
         b = C.c_double(0)
         _chk(lib().amg_hip_cycle_must_move(self._h, int(part), C.byref(b)))
         return b.value
 
     def patch_leg_lines(self, level, leg):
-        """lines of the K-Patch tiles of `level`'s down-leg (leg 0) / up-leg (leg 1); 0 = no K-Patch level"""
+        """lines of the K-Patch tiles of `level`'s down-leg (leg 0) / up-leg (leg 1); 0 = no K-Patch level.
+        leg 2: of the seam launch that vcycle(n >= 2) runs on level 0; 0 = this solver runs none"""
         return int(lib().amg_hip_patch_leg_lines(self._h, int(level), int(leg)))
 
     def profile_fine_sweep(self, n_launches):

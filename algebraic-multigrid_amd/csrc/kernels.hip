@@ -1484,6 +1484,19 @@ constexpr int PATCH_K = PATCH_EH * PATCH_EC / PATCH_NT;  // cells per thread: 8 
 constexpr int PATCH_BUF = (PATCH_EH + 2) * PATCH_EC;     // + one guard line above and below
 constexpr int PATCH_MAXTAB = 192;            // table capacity: (types + 1) x slots
 static_assert(PATCH_EH * PATCH_EC == PATCH_K * PATCH_NT && PATCH_NT % PATCH_EC == 0, "patch geometry");
+// The held frame as a parameter of the patch functions: EH lines x EC columns [-CL, EC - CL) around
+// the PATCH_TW output columns, PATCH_K consecutive lines per thread.  PatchFrame is the frame of the
+// legs above (every function defaults to it); the seam kernel, five dependent stages, holds a
+// wider one (patch_seam_kernel).
+template <int EH_, int EC_>
+struct PatchFrameT {
+  static constexpr int EH = EH_, EC = EC_, CL = (EC_ - PATCH_TW) / 2;
+  static constexpr int NT = EH_ / PATCH_K * EC_, BUF = (EH_ + 2) * EC_;
+  static constexpr int th(int rings) { return EH_ - 2 * rings; }
+  static_assert(EH_ % PATCH_K == 0 && (EC_ - PATCH_TW) % 2 == 0 && NT >= PATCH_MAXTAB && NT <= 1024, "patch frame");
+};
+using PatchFrame = PatchFrameT<PATCH_EH, PATCH_EC>;
+static_assert(PatchFrame::NT == PATCH_NT && PatchFrame::BUF == PATCH_BUF && PatchFrame::CL == 4, "patch geometry");
 
 struct PatchJ { double a, d; };              // off-diagonal value (else +0.0), diagonal value (else +0.0)
 struct PatchR { double a; int32_t loff, ok; };  // value, LDS offset, slot in use
@@ -1552,14 +1565,14 @@ __device__ __forceinline__ void patch_load_u(PatchU& U, uint32_t tu, const doubl
 // selects.  Same bits as the generic form (MASK < 0): a Jacobi accumulator starts at +0.0 and
 // never becomes -0.0, so skipping a (+0.0) x term changes nothing for finite x; the residual's
 // generic form selects absent terms away, which is what not computing them does.
-template <bool RESID, bool CORNERS, bool GS = false, int MASK = -1>
+template <bool RESID, bool CORNERS, bool GS = false, int MASK = -1, class FR = PatchFrame>
 __device__ __forceinline__ void patch_eval_u(const double* buf, int cell0, const PatchU& U,
                                              const double (&f)[PATCH_K], double omega,
                                              double (&res)[PATCH_K]) {
-  const double* p = buf + cell0 - PATCH_EC;  // line above the first cell
+  const double* p = buf + cell0 - FR::EC;  // line above the first cell
   if (!CORNERS && !RESID && U.diag == 0.0) {  // rows without a diagonal keep their value (smoother.hpp:133)
 #pragma unroll
-    for (int k = 0; k < PATCH_K; ++k) res[k] = p[(k + 1) * PATCH_EC];
+    for (int k = 0; k < PATCH_K; ++k) res[k] = p[(k + 1) * FR::EC];
     return;
   }
   // (5-point rows: the test above is wave-uniform and sits OUTSIDE the cell loop; inside it, it
@@ -1571,15 +1584,15 @@ __device__ __forceinline__ void patch_eval_u(const double* buf, int cell0, const
 #pragma unroll
   for (int r = 0; r < 2; ++r)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) w[r][c] = (CORNERS || c == 1 || r == 1) ? p[r * PATCH_EC + c - 1] : 0.0;
+    for (int c = 0; c < 3; ++c) w[r][c] = (CORNERS || c == 1 || r == 1) ? p[r * FR::EC + c - 1] : 0.0;
 #pragma unroll
   for (int k = 0; k < PATCH_K; ++k) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-      w[2][c] = (CORNERS || c == 1) ? p[(k + 2) * PATCH_EC + c - 1] : 0.0;
+      w[2][c] = (CORNERS || c == 1) ? p[(k + 2) * FR::EC + c - 1] : 0.0;
     if (!CORNERS) {  // left / right of line k + 1 become the middle row's of the next cell
-      w[2][0] = p[(k + 2) * PATCH_EC - 1];
-      w[2][2] = p[(k + 2) * PATCH_EC + 1];
+      w[2][0] = p[(k + 2) * FR::EC - 1];
+      w[2][2] = p[(k + 2) * FR::EC + 1];
     }
     const double xi = w[1][1];
     if (RESID) {
@@ -1683,7 +1696,7 @@ __device__ __forceinline__ double patch_eval(const double* buf, int cell, uint32
 // latency-bound stages need).  Cells outside the region or outside the matrix keep their
 // value; ZERO: such cells inside the region are set to 0.0 instead (the residual that the
 // restriction reads).  out (optional): rows of the patch proper also go to global memory.
-template <int UN, int UM, bool RESID, bool NT, bool ZERO, int TH>
+template <int UN, int UM, bool RESID, bool NT, bool ZERO, int TH, class FR = PatchFrame>
 __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int ntypes, double* buf,
                                             const PatchU& U, const PatchJ* tabJ, const PatchR* tabR,
                                             double omega, int l0, int l1, int c0, int c1, double* out) {
@@ -1701,19 +1714,19 @@ __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int nty
     // for the whole wave, weights in scalar registers; cells outside the region are evaluated
     // with it too (their reads stay inside the guard lines) and dropped.  Every other wave
     // (level boundaries) takes the per-lane table.
-    patch_eval_u<RESID, (UM & 0x145) != 0, false, (UM & 0x145) ? -1 : UM>(buf, pc.cell0, U, pc.f, omega, res);
+    patch_eval_u<RESID, (UM & 0x145) != 0, false, (UM & 0x145) ? -1 : UM, FR>(buf, pc.cell0, U, pc.f, omega, res);
   } else {
 #pragma unroll
     for (int k = 0; k < PATCH_K; ++k)
-      res[k] = patch_eval<UN, RESID>(buf, pc.cell0 + k * PATCH_EC,
+      res[k] = patch_eval<UN, RESID>(buf, pc.cell0 + k * FR::EC,
                                      did[k] ? pc.type(k) : (uint32_t)ntypes, tabJ, tabR, pc.f[k], omega);
   }
   lds_barrier();  // everybody has read the old values
   const bool outc = out != nullptr && pc.li >= 0 && pc.li < PATCH_TW;
 #pragma unroll
   for (int k = 0; k < PATCH_K; ++k) {
-    if (did[k]) buf[pc.cell0 + k * PATCH_EC] = res[k];
-    else if (ZERO && inr[k]) buf[pc.cell0 + k * PATCH_EC] = 0.0;
+    if (did[k]) buf[pc.cell0 + k * FR::EC] = res[k];
+    else if (ZERO && inr[k]) buf[pc.cell0 + k * FR::EC] = 0.0;
     const int lj = pc.lj0 + k;
     if (outc && did[k] && lj >= 0 && lj < TH) {
       double* op = out + (pc.row0 + k * m);
@@ -1727,14 +1740,14 @@ __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int nty
 // patch, so every store of a wave covers whole, aligned 128-byte lines.  (Stored straight from
 // the stage's registers, a line was split 60 + 4 entries between two waves -- the thread map
 // has 72 columns -- and the PMC write traffic was 1.5 x the vector.)
-template <bool NT, int RINGS>
+template <bool NT, int RINGS, class FR = PatchFrame>
 __device__ __forceinline__ void patch_copy_out(const double* buf, double* __restrict__ out, int n, int m,
                                                int j0, int i0) {
-  for (int q = threadIdx.x; q < patch_th(RINGS) * PATCH_TW; q += PATCH_NT) {
+  for (int q = threadIdx.x; q < FR::th(RINGS) * PATCH_TW; q += FR::NT) {
     const int lj = q / PATCH_TW, li = q - lj * PATCH_TW;
     const int64_t row = (int64_t)(j0 + lj) * m + i0 + li;
     if (row < (int64_t)n) {
-      const double v = buf[(lj + RINGS + 1) * PATCH_EC + li + 4];
+      const double v = buf[(lj + RINGS + 1) * FR::EC + li + FR::CL];
       if (NT) __builtin_nontemporal_store(v, out + row);
       else out[row] = v;
     }
@@ -1762,6 +1775,7 @@ __device__ __forceinline__ void patch_issue_tables(PatchTabRow& tb, const double
 #pragma unroll
   for (int q = 0; q < 4; ++q) tb.v[q] = ptab[4 * t + q];
 }
+template <class FR = PatchFrame>
 __device__ __forceinline__ void patch_stage_tables(PatchJ* tabJ, PatchR* tabR, const PatchTabRow& tb, int nent) {
   const int t = threadIdx.x;
   if (t >= PATCH_MAXTAB) return;
@@ -1774,14 +1788,17 @@ __device__ __forceinline__ void patch_stage_tables(PatchJ* tabJ, PatchR* tabR, c
     const double lo = tb.v[3];
     r.ok = lo > -1.0e8 ? 1 : 0;
     r.loff = r.ok ? (int)lo : 0;
+    // the table's offsets dj * PATCH_EC + di (|di| <= 1) in a frame of another pitch
+    if (FR::EC != PATCH_EC) r.loff += (r.loff > PATCH_EC / 2 ? 1 : (r.loff < -PATCH_EC / 2 ? -1 : 0)) * (FR::EC - PATCH_EC);
   }
   tabJ[t] = j;
   tabR[t] = r;
 }
 // guard lines: finite values for the reads of dropped cells
+template <class FR = PatchFrame>
 __device__ __forceinline__ void patch_clear_guards(double* buf) {
-  for (int t = threadIdx.x; t < 2 * PATCH_EC; t += PATCH_NT)
-    buf[t < PATCH_EC ? t : PATCH_BUF - 2 * PATCH_EC + t] = 0.0;
+  for (int t = threadIdx.x; t < 2 * FR::EC; t += FR::NT)
+    buf[t < FR::EC ? t : FR::BUF - 2 * FR::EC + t] = 0.0;
 }
 // The rest of the common prologue, after the cells (patch_load): guards, and the per-lane tables
 // where a flagged tile needs them.  Only a wave that is not on the scalar path reads them
@@ -1789,15 +1806,15 @@ __device__ __forceinline__ void patch_clear_guards(double* buf) {
 // the tables are read only when that type is not the kernel kind's (a rare tile: a dependent load
 // here); every other flagged tile neither loads nor writes them.  A tile without a flag staged
 // them in patch_load, beside its row types.
-template <int UM>
+template <int UM, class FR = PatchFrame>
 __device__ __forceinline__ void patch_prologue(const PatchCells& pc, const PatchU& U, double* buf, PatchJ* tabJ,
                                                PatchR* tabR, const double* __restrict__ ptab, int nent) {
   if (pc.flagged && U.rmask != (uint32_t)UM) {
     PatchTabRow tb;
     patch_issue_tables(tb, ptab, nent);
-    patch_stage_tables(tabJ, tabR, tb, nent);
+    patch_stage_tables<FR>(tabJ, tabR, tb, nent);
   }
-  patch_clear_guards(buf);
+  patch_clear_guards<FR>(buf);
 }
 
 // XF: the held cells as the from-zero sweep of their rows, x = Jacobi(0; f), instead of a load of
@@ -1807,6 +1824,7 @@ __device__ __forceinline__ void patch_prologue(const PatchCells& pc, const Patch
 // exact; the sweeps divide by this very value) -- in scalar registers on a wave-uniform wave, else
 // from the per-type table in global memory (utabd, 19 doubles per type: the LDS tables are not
 // staged yet).  The absent type `ntypes` (rows outside the matrix, empty rows) has d = 0: x = 0.0.
+template <class FR = PatchFrame>
 __device__ __forceinline__ void patch_form_x(const PatchCells& pc, const PatchU& U,
                                              const double* __restrict__ utabd, double omega, double* buf) {
   double dv[PATCH_K];
@@ -1822,7 +1840,7 @@ __device__ __forceinline__ void patch_form_x(const PatchCells& pc, const PatchU&
     const double sum = pc.f[k], d = dv[k];
     const double xi = 0.0, acc = 0.0;  // jacobi_from_zero_kernel
     const double x0 = (d == 0.0) ? xi : xi + omega * ((sum - acc) / d - xi);
-    buf[pc.cell0 + k * PATCH_EC] = pc.live[k] ? x0 : 0.0;
+    buf[pc.cell0 + k * FR::EC] = pc.live[k] ? x0 : 0.0;
   }
 }
 
@@ -1850,7 +1868,7 @@ __device__ __forceinline__ void patch_form_x(const PatchCells& pc, const PatchU&
 // (patch_form_x, called here).
 // RINGS: the first held line is line -RINGS of the patch.
 // (pc.f of a row outside the matrix is f[0]: such a cell is never `did`, its results are dropped.)
-template <int RINGS, bool PROLONG, bool XF = false>
+template <int RINGS, bool PROLONG, bool XF = false, class FR = PatchFrame>
 __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint8_t* __restrict__ tflag,
                                            int tile, int n, int m,
                                            int j0, int i0, const double* __restrict__ x,
@@ -1861,11 +1879,11 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint
                                            const double* __restrict__ utabd,
                                            const int32_t* __restrict__ utabi, double omega, double* buf,
                                            PatchJ* tabJ, PatchR* tabR) {
-  const int g = (int)threadIdx.x / PATCH_EC, col = (int)threadIdx.x - g * PATCH_EC;
+  const int g = (int)threadIdx.x / FR::EC, col = (int)threadIdx.x - g * FR::EC;
   const int le = g * PATCH_K;            // first of the thread's PATCH_K consecutive lines
   pc.lj0 = le - RINGS;
-  pc.li = col - 4;
-  pc.cell0 = (le + 1) * PATCH_EC + col;  // + 1: guard line
+  pc.li = col - FR::CL;
+  pc.cell0 = (le + 1) * FR::EC + col;  // + 1: guard line
   const int64_t r0 = (int64_t)(j0 + pc.lj0) * m + i0 + pc.li;
   pc.row0 = (int)(r0 < -((int64_t)1 << 30) ? -((int64_t)1 << 30) : r0);
   double xv[PATCH_K];
@@ -1922,7 +1940,7 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint
 #pragma unroll
     for (int q = 0; q < PATCH_K / 4; ++q) mism |= pc.ty[q] ^ (pc.tu * 0x01010101u);
     pc.uniform = __builtin_amdgcn_ballot_w64(mism != 0) == 0 && pc.tu < nty;
-    patch_stage_tables(tabJ, tabR, tb, nent);
+    patch_stage_tables<FR>(tabJ, tabR, tb, nent);
   }
   {
     // (opaque from here on: else the compiler folds type() back into eight registers of tf, filled --
@@ -1934,7 +1952,7 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint
   // the uniform type's table (scalar loads): on a flagged tile issued before the first vector wait
   patch_load_u(U, pc.uniform ? pc.tu : 0u, utabd, utabi);
   __builtin_amdgcn_sched_barrier(0);
-  if (XF) patch_form_x(pc, U, utabd, omega, buf);
+  if (XF) patch_form_x<FR>(pc, U, utabd, omega, buf);
   if (PROLONG) {
     // j, jc and the rows of f are worked out again from here on: kept across the loads they cost
     // the registers that the 48 of x and the uH pairs need (the compiler would keep, then spill, them)
@@ -1959,7 +1977,7 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint
       t = b_ok ? t + (odd ? 1.0 : 0.5) * b : t;
       x0 = pc.live[k] ? x0 + t : x0;
     }
-    buf[pc.cell0 + k * PATCH_EC] = x0;
+    buf[pc.cell0 + k * FR::EC] = x0;
   }
   if (PROLONG) {
     __builtin_amdgcn_sched_barrier(0);
@@ -1970,17 +1988,18 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint
 
 // flag[tile] = the row type shared by EVERY row a patch kernel of `rings` rings loads for the tile
 // (lines -rings .. TH+rings, columns -4 .. TW+4 of the flat index, all inside the matrix), else 255.
-__global__ __launch_bounds__(256) void patch_tile_flags_kernel(int n, int m, int px_count, int rings,
+// (eh, ec: the held frame, columns -(ec - TW) / 2 .. of the flat index: that of the legs, or the seam kernel's)
+__global__ __launch_bounds__(256) void patch_tile_flags_kernel(int n, int m, int px_count, int rings, int eh, int ec,
                                                                const uint8_t* __restrict__ rtype,
                                                                int ntypes, uint8_t* __restrict__ flag) {
   const int tile = blockIdx.x;
   const int py = tile / px_count, px = tile - py * px_count;
-  const int64_t base = (int64_t)(py * patch_th(rings) - rings) * m + px * PATCH_TW - 4;
+  const int64_t base = (int64_t)(py * (eh - 2 * rings) - rings) * m + px * PATCH_TW - (ec - PATCH_TW) / 2;
   const int64_t first = base < 0 ? 0 : (base < n ? base : n - 1);
   const uint32_t t0 = rtype[first];
   int ok = base >= 0 && t0 < (uint32_t)ntypes;
-  for (int q = threadIdx.x; q < PATCH_EH * PATCH_EC; q += 256) {
-    const int le = q / PATCH_EC, c = q - le * PATCH_EC;
+  for (int q = threadIdx.x; q < eh * ec; q += 256) {
+    const int le = q / ec, c = q - le * ec;
     const int64_t r = base + (int64_t)le * m + c;
     ok = ok && r >= 0 && r < (int64_t)n && rtype[r < 0 ? 0 : (r < n ? r : n - 1)] == t0;
   }
@@ -1997,7 +2016,7 @@ hipError_t launch_patch_tile_flags(int64_t n, int64_t m, int rings, const uint8_
   if (n_tiles) *n_tiles = tiles;
   if (!flag) return hipSuccess;
   hipLaunchKernelGGL(patch_tile_flags_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (int)n, (int)m, pxc,
-                     rings, rtype, ntypes, flag);
+                     rings, PATCH_EH, PATCH_EC, rtype, ntypes, flag);
   return hipGetLastError();
 }
 
@@ -2174,6 +2193,59 @@ __global__ __launch_bounds__(PATCH_NT, AMG_PATCH_WAVES) void patch_up_kernel(
                                             nullptr);
   lds_barrier();
   patch_copy_out<NT, RINGS>(buf, u_out, n, m, j0, i0);
+}
+
+// The seam between two cycles on level 0: the up-leg of cycle k and the down-leg of cycle k + 1 in ONE
+// launch, on one loaded tile -- x = u + P u_H (patch_load, the up-leg's), post-sweep 1, post-sweep 2,
+// pre-sweep 1, pre-sweep 2 (stored), residual, restriction (f_H alone: level 1 forms its first sweep
+// from it, the uH1 == nullptr form of the down-leg).  The vector u between the two legs is neither
+// stored nor loaded, f and the row types are read once.  Five dependent stencil stages: five rings
+// of halo lines, and columns [-5, TW + 6) -- the frame FR (columns [-6, TW + 6)).  Every stage is
+// the legs' own patch_stage on the legs' regions grown by the rings still to come, so every value
+// has the bits the two launches give it (halo cells are recomputed, as everywhere in K-Patch).
+constexpr int PATCH_SEAM_RINGS = 5;
+template <int UN, int UM, bool NT, class FR, int WAVES>
+__global__ __launch_bounds__(FR::NT, WAVES) void patch_seam_kernel(
+    int n, int m, int px_count, const uint8_t* __restrict__ rtype, const double* __restrict__ ptab,
+    const double* __restrict__ utabd, const int32_t* __restrict__ utabi,
+    int nent, int ntypes, const double* x, const double* __restrict__ f, const double* __restrict__ uH, int nH,
+    double* u_out, double* __restrict__ fH, double omega, int xcd_map, const uint8_t* __restrict__ tflag) {
+  __shared__ double buf[FR::BUF];
+  __shared__ PatchJ tabJ[PATCH_MAXTAB];
+  __shared__ PatchR tabR[PATCH_MAXTAB];
+  const int tile = xcd_tile(blockIdx.x, gridDim.x, xcd_map);
+  const int py = tile / px_count, px = tile - py * px_count;
+  constexpr int RINGS = PATCH_SEAM_RINGS, TH = FR::th(RINGS);
+  static_assert(TH >= 1 && FR::CL >= RINGS + 1, "five stages and the restriction's column");
+  const int j0 = py * TH, i0 = px * PATCH_TW;
+  PatchCells pc;
+  PatchU U;
+  patch_load<RINGS, true, false, FR>(pc, U, tflag, tile, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, ptab, nent,
+                                     utabd, utabi, omega, buf, tabJ, tabR);
+  patch_prologue<UM, FR>(pc, U, buf, tabJ, tabR, ptab, nent);
+  lds_barrier();
+#pragma unroll
+  for (int q = 4; q >= 1; --q) {  // post-sweeps 1, 2, pre-sweeps 1, 2: q rings are still to come
+    patch_stage<UN, UM, false, NT, false, TH, FR>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -q, TH + q, -q,
+                                                  PATCH_TW + q + 1, nullptr);
+    lds_barrier();
+  }
+  patch_copy_out<NT, RINGS, FR>(buf, u_out, n, m, j0, i0);  // the residual stage below only reads until its barrier
+  patch_stage<UN, UM, true, NT, true, TH, FR>(pc, m, ntypes, buf, U, tabJ, tabR, omega, 0, TH, 0, PATCH_TW + 1,
+                                              nullptr);
+  lds_barrier();
+  for (int q = threadIdx.x; q < TH * (PATCH_TW / 2); q += FR::NT) {  // patch_down_kernel's loop, f_H alone
+    const int lj = q / (PATCH_TW / 2), cx = q - lj * (PATCH_TW / 2);
+    const int64_t i = (int64_t)(j0 + lj) * m + i0 + 2 * cx;   // fine row 2c
+    const int64_t c = i >> 1;
+    if (i >= (int64_t)n || c >= nH) continue;
+    const double* rs = buf + (lj + RINGS + 1) * FR::EC + 2 * cx + FR::CL;
+    double sum = 0.0;  // dict_restrict_tail / linear_restrict_kernel, same guards and order
+    if (i < n) sum += 0.5 * rs[0];
+    if (i + 1 < n) sum += 1.0 * rs[1];
+    if (i + 2 < n) sum += 0.5 * rs[2];
+    fH[c] = sum;
+  }
 }
 
 // ---- multicolour Gauss-Seidel on a patch (colours laid out on the 2 x 2 cells of the grid) ----
@@ -2392,6 +2464,51 @@ hipError_t launch_patch_up(int64_t n, int64_t m, const PatchRef& P, const double
     else AMG_UP(3);
 #undef AMG_UP
   });
+}
+// The seam kernel's frame: 48 held lines x 76 columns [-6, 70), 38 output lines, 456 threads (eight
+// waves, the last one of 8 lanes), three workgroups per CU at 6 waves per SIMD (76 registers, 36.5 KB
+// of LDS, no scratch).  Timed alone on 4096^2 against the two legs it replaces (217 us): 48 x 76
+// 196 us, 40 x 76 (30 lines, four workgroups per CU) 223 us, 56 x 76 (46 lines, 7 waves per SIMD,
+// 72 registers) 247 us ("K-Patch seam").
+using SeamFrame = PatchFrameT<48, 76>;
+constexpr int PATCH_SEAM_WAVES = 6;
+int patch_seam_lines() { return SeamFrame::th(PATCH_SEAM_RINGS); }
+static bool patch_seam_geometry_ok(int64_t n, int64_t m) {
+  return patch_geometry_ok(n, m) && n < ((int64_t)1 << 31) - 64 * m - 128;
+}
+hipError_t launch_patch_seam_flags(int64_t n, int64_t m, const uint8_t* rtype, int ntypes, uint8_t* flag,
+                                   int64_t* n_tiles, hipStream_t st) {
+  if (!patch_seam_geometry_ok(n, m)) return hipErrorInvalidValue;
+  const int64_t lines = (n + m - 1) / m;
+  const int pxc = (int)(m / PATCH_TW);
+  const int64_t th = patch_seam_lines();
+  const int64_t tiles = (lines + th - 1) / th * pxc;
+  if (n_tiles) *n_tiles = tiles;
+  if (!flag) return hipSuccess;
+  hipLaunchKernelGGL(patch_tile_flags_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (int)n, (int)m, pxc,
+                     PATCH_SEAM_RINGS, SeamFrame::EH, SeamFrame::EC, rtype, ntypes, flag);
+  return hipGetLastError();
+}
+hipError_t launch_patch_seam(int64_t n, int64_t m, const PatchRef& P, const double* x, const double* f,
+                             const double* uH, int64_t nH, double* u_out, double* fH, double omega,
+                             hipStream_t st) {
+  if (!patch_seam_geometry_ok(n, m) || !P.rtype || !P.ptab || !P.utabd || !P.utabi ||
+      (P.ntypes + 1) * patch_un(P.un) > PATCH_MAXTAB || P.nent != P.ntypes * patch_un(P.un) || !x || !f || !uH ||
+      nH < 2 || !u_out || u_out == x || !fH || P.rings != PATCH_SEAM_RINGS || patch_un(P.un) != 5)
+    return hipErrorInvalidValue;
+  int pxc = 0, py0 = 0;
+  const unsigned grid = patch_grid(n, m, patch_seam_lines(), 0, -1, &pxc, &py0);
+  if (grid == 0) return hipSuccess;
+  const int xm = g_xcd_map ? 1 : 0;
+  // (the 5-point kind alone is instantiated: a 7- or 9-point level 0 keeps the two launches)
+#define AMG_SEAM(NTF)                                                                                          \
+  hipLaunchKernelGGL((patch_seam_kernel<5, 0x0BA, NTF, SeamFrame, PATCH_SEAM_WAVES>), dim3(grid), dim3(SeamFrame::NT), \
+                     0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, P.nent, P.ntypes, x, f, uH,  \
+                     (int)nH, u_out, fH, omega, xm, P.tflag)
+  if (P.nt) AMG_SEAM(true);
+  else AMG_SEAM(false);
+#undef AMG_SEAM
+  return hipGetLastError();
 }
 // the halo a patch is loaded with (3 lines above and below, 4 columns left and right; the lines
 // beyond are guard lines of zeros) bounds the dependent stages of one launch: stage s of S reads

@@ -294,6 +294,16 @@ int patch_leg_rings(bool first);
 hipError_t launch_patch_up(int64_t n, int64_t m, const PatchRef& P, const double* x, const double* f,
                            const double* uH, int64_t nH, double* u_out, double omega,
                            hipStream_t st, int64_t line_lo = 0, int64_t line_hi = -1);
+// The level-0 seam between two cycles, one launch: u_out = the two post-sweeps of (x + P uH) followed
+// by the two pre-sweeps of the next cycle, fH = the restricted residual of u_out (u_out must not be x).
+// Tiles of patch_seam_lines() lines on five halo rings: P.rings == 5 and P.tflag from
+// launch_patch_seam_flags (or null).  5-point levels only (patch_un(P.un) == 5).
+int patch_seam_lines();
+hipError_t launch_patch_seam_flags(int64_t n, int64_t m, const uint8_t* rtype, int ntypes, uint8_t* flag,
+                                   int64_t* n_tiles, hipStream_t st);
+hipError_t launch_patch_seam(int64_t n, int64_t m, const PatchRef& P, const double* x, const double* f,
+                             const double* uH, int64_t nH, double* u_out, double* fH, double omega,
+                             hipStream_t st);
 // Multicolour Gauss-Seidel on patches: up to patch_rb_max_stages(tail) colour stages per launch
 // (stages = patch_rb_stages(colours, count)), u_out != x.  prolong: the input is x + P uH;
 // tail: followed by the residual (r_out optional), the restriction into fH and the zeroing of

@@ -313,6 +313,7 @@ hipError_t device_galerkin_generic(const DevCsr& A, const DevCsr& P, const DevCs
 int g_patch_tile_flags = 1;  // amg_hip_set_patch_tile_flags: A/B switch (same bits either way)
 int g_patch_xf = 1;          // amg_hip_set_patch_xf: A/B switch (same bits either way)
 int g_patch_tall = 1;        // amg_hip_set_patch_tall: A/B switch (same bits either way)
+int g_patch_seam = 1;        // amg_hip_set_patch_seam: A/B switch (same bits either way)
 
 // A level matrix on the device in one of the two layouts the kernels take.
 struct DevMat {
@@ -345,9 +346,10 @@ struct DevMat {
   int patch_un = 0, patch_ntypes = 0, patch_umask = 0;
   // A tile flag describes the rows a kernel loads for a tile, so there is one array per geometry:
   // patch_flags for the launches with three halo rings (tiles of 42 lines), patch_flags2 for those
-  // with two (44 lines).  Both are built with the matrix (a byte per tile), whichever the level's
+  // with two (44 lines), patch_flags5 for the seam launch (five rings in its wider frame, 38 lines;
+  // 5-point levels only).  All are built with the matrix (a byte per tile), whichever the level's
   // launches turn out to use.
-  DevMem patch_tab, patch_utabd, patch_utabi, patch_flags, patch_flags2;
+  DevMem patch_tab, patch_utabd, patch_utabi, patch_flags, patch_flags2, patch_flags5;
   // per tile of the level's down-leg (patch_crings rings): the coarse rows under it share the
   // diagonal patch_dH (set_patch_coarse_flags)
   DevMem patch_cflags;
@@ -360,7 +362,8 @@ struct DevMat {
     PatchRef P;
     P.rings = rings;
     P.rtype = drtype.as<uint8_t>();
-    P.tflag = g_patch_tile_flags ? (rings == 2 ? patch_flags2 : patch_flags).as<uint8_t>() : nullptr;
+    P.tflag = g_patch_tile_flags ? (rings == 2 ? patch_flags2 : (rings == 5 ? patch_flags5 : patch_flags)).as<uint8_t>()
+                                 : nullptr;
     P.cflag = g_patch_tile_flags && rings == patch_crings ? patch_cflags.as<uint8_t>() : nullptr;
     P.dHu = patch_dH;
     P.ptab = patch_tab.as<double>();
@@ -677,6 +680,15 @@ hipError_t finish_dict(const DictMat& T, int64_t n, int64_t diag_shift, DevMat* 
         if ((e = hipMemset(F.p, 0, F.bytes)) != hipSuccess) return e;
         if ((e = launch_patch_tile_flags(n, D->patch_m, rings, D->drtype.as<uint8_t>(), nty, F.as<uint8_t>(),
                                          nullptr, nullptr)) != hipSuccess) return e;
+      }
+      if (patch_un(un) == 5) {  // the seam launch's tiles (the kernel kind it is instantiated for)
+        int64_t t5 = 0;
+        if ((e = launch_patch_seam_flags(n, D->patch_m, nullptr, nty, nullptr, &t5, nullptr)) == hipSuccess) {
+          if ((e = D->patch_flags5.alloc(((size_t)t5 + 3) & ~(size_t)3)) != hipSuccess) return e;
+          if ((e = hipMemset(D->patch_flags5.p, 0, D->patch_flags5.bytes)) != hipSuccess) return e;
+          if ((e = launch_patch_seam_flags(n, D->patch_m, D->drtype.as<uint8_t>(), nty, D->patch_flags5.as<uint8_t>(),
+                                           nullptr, nullptr)) != hipSuccess) return e;
+        }  // (a level too large for the seam frame's index range keeps the two launches: no flags, patch_seam_ok)
       }
       if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
       // the interior row type = the type most tiles consist of; its slots choose the kernel kind
@@ -1620,6 +1632,7 @@ struct amg_hip_solver {
   int64_t patch_min_rows = g_patch_min_rows;  // the process-wide value when the solver was made
   int patch_xf = g_patch_xf;                  // likewise
   int patch_tall = g_patch_tall;              // likewise
+  int patch_seam = g_patch_seam;              // likewise
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = true;
@@ -1634,9 +1647,24 @@ struct amg_hip_solver {
   double cycle_bytes = 0, fine_sweep_bytes = 0;
   // bytes the launches of one V-cycle HAVE TO move (what each kernel reads and writes once in the
   // layout it really streams), summed while the cycle is enqueued; [part] as enqueue_vcycle's
-  double must_move[4] = {0, 0, 0, 0};
+  // [4]: one steady-state seam cycle (seam launch + levels 1 .. L-1; amg_hip_vcycles), [5]: its head and finish
+  double must_move[6] = {0, 0, 0, 0, 0, 0};
   int acct_part = -1;  // -1: not inside enqueue_vcycle
   void acct(double bytes) { if (acct_part >= 0) must_move[acct_part] += bytes; }
+  // K-Patch seam (amg_hip_vcycles with n >= 2, patch_seam_ok): the piece being enqueued and the
+  // level-0 buffer it hands over in (0: tmp, 1: r), and the captured pieces -- head and seam cycle
+  // per buffer, the finish
+  int seam_piece = 0, seam_src = 0;
+  hipGraph_t seam_graph[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipGraphExec_t seam_exec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  void reset_seam_graphs() {
+    for (int i = 0; i < 5; ++i) {
+      if (seam_exec[i]) (void)hipGraphExecDestroy(seam_exec[i]);
+      if (seam_graph[i]) (void)hipGraphDestroy(seam_graph[i]);
+      seam_exec[i] = nullptr;
+      seam_graph[i] = nullptr;
+    }
+  }
   Slab slab;
   Block blk;
   // block cycle bytes, counted while it is enqueued: matrix bytes (once per launch) and bytes per
@@ -1658,6 +1686,7 @@ struct amg_hip_solver {
     f32.reset_graph();
     blk.reset_graphs();
     slab.reset_graphs();
+    reset_seam_graphs();
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     if (graph) (void)hipGraphDestroy(graph);
     if (stream && own_stream) (void)hipStreamDestroy(stream);
@@ -1737,6 +1766,26 @@ int patch_rings(const amg_hip_solver* s, bool first_down) {
 // predicate decides both sides of the pair, for whole-level and ranged (slab, window) launches alike.
 bool patch_xf_pair(const amg_hip_solver* s, int l) {
   return s->patch_xf && patch_level_ok(s, l) && patch_level_ok(s, l + 1);
+}
+
+// The seam between two cycles run back to back (amg_hip_vcycles with n >= 2): the level-0 up-leg of one
+// and the level-0 down-leg of the next as ONE launch (kernels.hip: patch_seam_kernel), so the vector
+// between them is neither stored nor loaded.  ONE predicate: levels 0 and 1 are K-Patch Jacobi levels
+// with the hand-over between them (which implies the true-Jacobi 2+2 smoother with fusion on, and at
+// least three levels), the cycle is whole, the residual is not kept (the level's r is then free: the
+// handed-over vector alternates between tmp and r), and level 0 is of the kernel's 5-point kind.
+enum { SEAM_OFF = 0, SEAM_HEAD = 1, SEAM_CYCLE = 2, SEAM_FINISH = 3 };
+bool patch_seam_ok(const amg_hip_solver* s) {
+  if (!s->patch_seam || s->lv.size() < 2 || s->opt.window || s->slab.levels != 0 || s->opt.keep_residual ||
+      s->opt.no_fusion || s->opt.smoother != AMG_HIP_SM_JACOBI)
+    return false;
+  const Level& L = s->lv[0];
+  return patch_xf_pair(s, 0) && patch_un(L.A_rows.patch_un) == 5 && L.A_rows.patch_flags5.p != nullptr &&
+         L.r.p != nullptr && L.r.bytes >= sizeof(double) * (size_t)L.n;
+}
+// the level-0 vector a piece of the seam sequence hands over: tmp or r
+double* seam_buf(amg_hip_solver* s, int which) {
+  return which ? s->lv[0].r.as<double>() : s->lv[0].tmp.as<double>();
 }
 
 // Multicolour smoother on a level whose colours repeat on the 2 x 2 cells of its 2-D band (the
@@ -2175,8 +2224,10 @@ struct RoctxRange {
 
 amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part);
 amg_hip_status enqueue_vcycle(amg_hip_solver* s, int part = CYCLE_ALL) {
-  s->must_move[part] = 0;
-  s->acct_part = part;
+  // (the pieces of the seam sequence count apart: [0] stays the stand-alone cycle)
+  const int slot = s->seam_piece == SEAM_CYCLE ? 4 : (s->seam_piece != SEAM_OFF ? 5 : part);
+  s->must_move[slot] = 0;
+  s->acct_part = slot;
   amg_hip_status r = enqueue_vcycle_body(s, part);
   // a level K-March swept on one leg only (the coarsest one: it has no up-leg) ends the cycle with
   // u and tmp traded: its solution goes home so that the next cycle, or the next replay of the
@@ -2212,8 +2263,12 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
     }
     first_sweep_done = true;
   }
+  // the seam sequence (part == CYCLE_ALL): head = the cycle without the level-0 up-leg, its level-0
+  // down-leg writing seam_buf(src); seam cycle = the seam launch from seam_buf(src) into the other
+  // buffer, then levels 1 .. L-1 as in the cycle; finish = the level-0 up-leg alone, from tmp
+  const int piece = s->seam_piece;
   const int down_from = part == CYCLE_SLAB_TAIL ? k : 0;
-  const int down_to = part == CYCLE_SLAB_DOWN ? k : (part == CYCLE_SLAB_UP ? 0 : nl);
+  const int down_to = part == CYCLE_SLAB_DOWN ? k : ((part == CYCLE_SLAB_UP || piece == SEAM_FINISH) ? 0 : nl);
   for (int l = down_from; l < down_to; ++l) {
     RoctxRange range("down", l);
     // On the coarsest level the reference smooths and forms the residual, then overwrites
@@ -2257,12 +2312,22 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
       Level& L = s->lv[l];
       Level& C = s->lv[l + 1];
       const DevMat& A = L.A_rows;
+      if (l == 0 && piece == SEAM_CYCLE) {  // up-leg of the last cycle + this down-leg: one launch
+        HIP_TRY(launch_patch_seam(L.n, A.patch_m, A.patch_ref(5), seam_buf(s, s->seam_src), L.f.as<double>(),
+                                  C.tmp.as<double>(), C.n, seam_buf(s, 1 - s->seam_src), C.f.as<double>(),
+                                  s->opt.omega, st));
+        s->acct(25.0 * L.n + 16.0 * C.n);  // row types + x + f + smoothed u; u_H, f_H
+        first_sweep_done = true;
+        continue;
+      }
       const bool first = l == 0;  // l >= 1: the first sweep came from level l-1's kernel (in tmp) ...
       const bool xf_in = l >= 1 && patch_xf_pair(s, l - 1);  // ... or is formed from f here
       const bool xf_out = patch_xf_pair(s, l);               // level l+1 forms its own: f_H only
       HIP_TRY(launch_patch_down(first, L.n, A.patch_m, A.patch_ref(patch_rings(s, first)),
                                 first ? L.u.as<double>() : (xf_in ? nullptr : L.tmp.as<double>()),
-                                L.f.as<double>(), first ? L.tmp.as<double>() : L.u.as<double>(),
+                                L.f.as<double>(),
+                                first ? (piece == SEAM_HEAD ? seam_buf(s, s->seam_src) : L.tmp.as<double>())
+                                      : L.u.as<double>(),
                                 s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
                                 C.f.as<double>(), C.diag.as<double>(), xf_out ? nullptr : C.tmp.as<double>(),
                                 s->opt.omega, st, ranged ? sb.down_lo[l] : 0,
@@ -2390,7 +2455,7 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
     return pair_up_ok(s, l) ? s->lv[l].tmp.as<double>() : s->lv[l].u.as<double>();
   };
   int prolonged_by_solve = -1;  // level whose :294-296 the coarsest solve's launch did (K-BandChain)
-  if (!ranged && !tail_done) {                                     // :287-288
+  if (!ranged && !tail_done && piece != SEAM_FINISH) {             // :287-288
     RoctxRange range("coarse solve", -1);
     if (s->opt.window)
       return fail(AMG_HIP_EINVAL, "a window solver (opt.window) runs by parts: amg_hip_window_run");
@@ -2412,8 +2477,8 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
     // banded L D L^T solve: the band of L forwards and backwards, D, f, u
     s->acct(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
   }
-  const int up_from = part == CYCLE_SLAB_UP ? k - 1 : (part == CYCLE_SLAB_DOWN ? -1 : (tail_done ? tail_lt - 1 : nl - 2));
-  const int up_to = part == CYCLE_SLAB_TAIL ? k : 0;
+  const int up_from = piece == SEAM_FINISH ? 0 : (part == CYCLE_SLAB_UP ? k - 1 : (part == CYCLE_SLAB_DOWN ? -1 : (tail_done ? tail_lt - 1 : nl - 2)));
+  const int up_to = part == CYCLE_SLAB_TAIL ? k : ((piece == SEAM_HEAD || piece == SEAM_CYCLE) ? 1 : 0);
   for (int l = up_from; l >= up_to; --l) {                         // :291
     RoctxRange range("up", l);
     Level& L = s->lv[l];
@@ -2505,6 +2570,26 @@ amg_hip_status ensure_graph(amg_hip_solver* s) {
   if (s->graph_ready) return AMG_HIP_OK;
   AMG_TRY(capture_once(s->stream, [s] { return enqueue_vcycle(s); }, &s->graph, &s->graph_exec));
   s->graph_ready = true;
+  return AMG_HIP_OK;
+}
+
+// One piece of the seam sequence (SEAM_HEAD / SEAM_CYCLE with the buffer src it hands over in, or
+// SEAM_FINISH), enqueued or replayed from its graph, captured on first use.  The piece is a mode of
+// enqueue_vcycle for the length of this call only: no vector changes its role, so a failure anywhere
+// leaves the solver as a stand-alone cycle expects it.
+amg_hip_status run_seam_piece(amg_hip_solver* s, int piece, int src) {
+  auto enqueue = [s, piece, src] {
+    s->seam_piece = piece;
+    s->seam_src = src;
+    const amg_hip_status r = enqueue_vcycle(s);
+    s->seam_piece = SEAM_OFF;
+    s->seam_src = 0;
+    return r;
+  };
+  if (!s->opt.use_graph) return enqueue();
+  const int gi = piece == SEAM_FINISH ? 4 : (piece == SEAM_HEAD ? 0 : 2) + src;
+  if (!s->seam_exec[gi]) AMG_TRY(capture_once(s->stream, enqueue, &s->seam_graph[gi], &s->seam_exec[gi]));
+  HIP_TRY(hipGraphLaunch(s->seam_exec[gi], s->stream));
   return AMG_HIP_OK;
 }
 
@@ -4510,6 +4595,7 @@ void amg_hip_set_dict_stencil(int32_t on) { set_dict_stencil(on); }
 void amg_hip_set_patch_tile_flags(int32_t on) { g_patch_tile_flags = on ? 1 : 0; }
 void amg_hip_set_patch_xf(int32_t on) { g_patch_xf = on ? 1 : 0; }
 void amg_hip_set_patch_tall(int32_t on) { g_patch_tall = on ? 1 : 0; }
+void amg_hip_set_patch_seam(int32_t on) { g_patch_seam = on ? 1 : 0; }
 void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
 void amg_hip_set_periodic_device_setup(int32_t on) { g_periodic_device_setup = on ? 1 : 0; }
@@ -4971,6 +5057,16 @@ amg_hip_status amg_hip_vcycles(amg_hip_solver* s, int32_t n) {
   if (!s) return fail(AMG_HIP_EINVAL, "null solver");
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
+  if (n >= 2 && patch_seam_ok(s)) {
+    // head, n - 1 seam cycles, finish.  The handed-over level-0 vector alternates between tmp and r;
+    // the head starts on the buffer that makes the last seam cycle write tmp, where a stand-alone
+    // cycle leaves that vector, so the finish is the cycle's own last launch.
+    int src = (n - 1) & 1;
+    if ((r = run_seam_piece(s, SEAM_HEAD, src)) != AMG_HIP_OK) return r;
+    for (int i = 1; i < n; ++i, src ^= 1)
+      if ((r = run_seam_piece(s, SEAM_CYCLE, src)) != AMG_HIP_OK) return r;
+    return run_seam_piece(s, SEAM_FINISH, 0);
+  }
   if (s->opt.use_graph) {
     if ((r = ensure_graph(s)) != AMG_HIP_OK) return r;
     for (int i = 0; i < n; ++i) HIP_TRY(hipGraphLaunch(s->graph_exec, s->stream));
@@ -5098,6 +5194,7 @@ amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world
     sb.levels = 0;  // not configured: amg_hip_slab_run refuses
     return r;
   }
+  s->reset_seam_graphs();
   if (s->graph_ready) {  // the whole-cycle graph holds the old pointers
     (void)hipGraphExecDestroy(s->graph_exec);
     (void)hipGraphDestroy(s->graph);
@@ -5601,9 +5698,12 @@ amg_hip_status amg_hip_solve(amg_hip_solver* s, double tol, int64_t every, int64
   int64_t iter = 0;
   double error = 100;  // multigrid.hpp:313
   while (iter < n_iters && error > tol) {
-    amg_hip_status r = amg_hip_vcycles(s, 1);
+    // `error` only changes at the multiples of `every`: the cycles up to the next one (or to n_iters)
+    // run as one call, so that they meet at their seams (amg_hip_vcycles)
+    const int64_t k = std::min<int64_t>(std::min(every - iter % every, n_iters - iter), 1 << 20);
+    amg_hip_status r = amg_hip_vcycles(s, (int32_t)k);
     if (r != AMG_HIP_OK) return r;
-    iter += 1;
+    iter += k;
     if ((iter % every) == 0) {
       if ((r = amg_hip_rss(s, &error)) != AMG_HIP_OK) return r;
     }
@@ -5852,8 +5952,27 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
 }
 
 amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* bytes) {
-  if (!s || !bytes || part < 0 || part > 3) return fail(AMG_HIP_EINVAL, "bad argument");
+  if (!s || !bytes || part < 0 || part > 4) return fail(AMG_HIP_EINVAL, "bad argument");
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no device cycle");
+  if (part == 4) {
+    // one steady-state cycle of amg_hip_vcycles(s, n >= 2): the seam cycle where the solver runs one
+    // (counted while its graph is captured), else the stand-alone cycle
+    if (!patch_seam_ok(s)) return amg_hip_cycle_must_move(s, CYCLE_ALL, bytes);
+    if (s->must_move[4] == 0.0) {
+      amg_hip_status r = set_device(s);
+      if (r != AMG_HIP_OK) return r;
+      if (!s->opt.use_graph) return fail(AMG_HIP_EINVAL, "amg_hip_cycle_must_move: run two V-cycles in one call first");
+      const int gi = 2;  // the seam cycle that reads tmp: captured, not run
+      s->seam_piece = SEAM_CYCLE;
+      s->seam_src = 0;
+      r = s->seam_exec[gi] ? AMG_HIP_OK
+                           : capture_once(s->stream, [s] { return enqueue_vcycle(s); }, &s->seam_graph[gi], &s->seam_exec[gi]);
+      s->seam_piece = SEAM_OFF;
+      if (r != AMG_HIP_OK) return r;
+    }
+    *bytes = s->must_move[4];
+    return AMG_HIP_OK;
+  }
   if (part == CYCLE_ALL && s->must_move[0] == 0.0 && !s->opt.window) {
     // not enqueued yet: capturing the graph walks the cycle without running it
     amg_hip_status r = set_device(s);
@@ -5869,7 +5988,8 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
 }
 
 int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t leg) {
-  if (!s || s->opt.host_only || level < 0 || level >= (int32_t)s->lv.size() || leg < 0 || leg > 1) return 0;
+  if (!s || s->opt.host_only || level < 0 || level >= (int32_t)s->lv.size() || leg < 0 || leg > 2) return 0;
+  if (leg == 2) return (level == 0 && patch_seam_ok(s)) ? patch_seam_lines() : 0;  // the seam launch
   if (mc_patch_ok(s, level)) return patch_tile_lines(3);
   if (!patch_level_ok(s, level)) return 0;
   return patch_tile_lines(patch_rings(s, leg == 0 && level == 0));

@@ -283,6 +283,15 @@ void amg_hip_set_patch_xf(int32_t on);
  * 42 lines everywhere.  Process-wide, read when a solver is created.  Same bits either way: an
  * A/B switch for tests and measurements.                                                      */
 void amg_hip_set_patch_tall(int32_t on);
+/* K-Patch seam: on (default), amg_hip_vcycles(s, n) with n >= 2 -- and amg_hip_solve between two
+ * residual checks -- runs the level-0 up-leg of one cycle and the level-0 down-leg of the next as ONE
+ * launch, so the level-0 vector between two cycles is neither stored nor loaded again (25 n_0 bytes
+ * less per cycle).  Taken where levels 0 and 1 are K-Patch Jacobi levels with the hand-over between
+ * them, level 0 is a 5-point level, the cycle is whole (no slab, no window) and keep_residual and
+ * no_fusion are off (the level-0 residual vector then serves as the second buffer of the handed-over
+ * vector); a single cycle, amg_hip_apply and PCG run as before.  Process-wide, read when a solver is
+ * created.  Same bits either way: an A/B switch for tests and measurements.                        */
+void amg_hip_set_patch_seam(int32_t on);
 /* K-BandChain (coarsest solve kind 3) on / off; process-wide, read when a solver is created.
  * Same bits either way: an A/B switch for tests and tuning.                             */
 void amg_hip_set_band_chain(int32_t on);
@@ -1010,7 +1019,11 @@ amg_hip_status amg_hip_cycle_bytes(const amg_hip_solver* s, double* cycle_bytes,
  * 25 n + 24 n_H down, 25 n + 8 n_H up; SELL / CSR: indices + values; vectors 8 B per entry),
  * summed while the cycle is enqueued.  part 0 = the whole cycle (bench.py divides it by the
  * measured time per cycle: the whole-cycle fraction of the HBM roof), 1 / 2 / 3 = the parts of
- * amg_hip_slab_run / amg_hip_window_run once they have run.                                  */
+ * amg_hip_slab_run / amg_hip_window_run once they have run.  part 0 describes ONE STAND-ALONE cycle
+ * whatever amg_hip_vcycles runs, so bench.py's whole_cycle fraction is quoted on the stand-alone
+ * cycle's bytes; part 4 = one steady-state cycle of amg_hip_vcycles(s, n >= 2): with the K-Patch
+ * seam (amg_hip_set_patch_seam) the seam launch (25 n_0 + 16 n_1) and levels 1 .. L-1, i.e. part 0
+ * less 25 n_0; without it, part 0.                                                             */
 amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* bytes);
 
 /* Measurement hook for bench.py: launches the level-0 smoother sweep kernel
@@ -1027,7 +1040,8 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
 amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
                                           double* avg_ms, double* min_ms);
 /* Lines of the tiles the V-cycle of this solver launches on `level` for its down-leg (leg 0) or
- * up-leg (leg 1): 42 or 44 on a K-Patch level, 0 where the level is no K-Patch level.        */
+ * up-leg (leg 1): 42 or 44 on a K-Patch level, 0 where the level is no K-Patch level.  leg 2: of the
+ * seam launch amg_hip_vcycles(s, n >= 2) runs on level 0 (38), 0 where this solver runs none.   */
 int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t leg);
 /* Name of the kernel amg_hip_profile_fine_sweep times (as rocprofv3 prints it, without the
  * namespace), the number of Jacobi sweeps over level 0 one launch of it performs, and the

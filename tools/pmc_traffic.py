@@ -40,8 +40,17 @@ def patch_grids(l):
     return [((lines + th - 1) // th) * (m // 64) * 432 for th in (42, 44)]
 
 
+def seam_grid():
+    """threads of the level-0 seam launch: tiles of 38 lines (five halo rings) x 64 columns, 456 threads each"""
+    n, m = LEVEL_ROWS[0], PITCH[0]
+    lines = (n + m - 1) // m
+    return ((lines + 37) // 38) * (m // 64) * 456
+
+
 def classify(name, grid):
     """(kind, level, code words) of a launch, or (None, None, 0)"""
+    if name.startswith("patch_seam_kernel<"):
+        return ("patch_seam", 0, 0) if grid == seam_grid() else (None, None, 0)
     m = re.match(r"patch_(down|up)_kernel<([\w, ]+)>", name)
     if m:
         targs = m.group(2).split(", ")
@@ -90,6 +99,8 @@ def must_move(kind, l):
         return n * (17 if kind == "patch_down_xf" else 25) + nH * (8 if handover else 16)
     if kind == "patch_up":                   # x, f, type, u_H in; u out
         return n * 25 + nH * 8
+    if kind == "patch_seam":                 # x, f, type, u_H in; smoothed u, f_H out
+        return n * 25 + nH * 16
     if kind == "sell":
         return 12 * LEVEL_NNZ[l] + 28 * n
     return None
@@ -127,7 +138,8 @@ def main():
               "patch_down_kernel<slots, mask, first, nt, xf, rings>: the level's whole down-leg (x, f, type in; smoothed u, f_H, first coarse",
               "sweep out; the coarse diagonal is a kernel argument under interior tiles; xf: x is formed from f and not read, and a",
               "level whose coarser level runs the xf form stores f_H alone), patch_up_kernel: the up-leg (x, f, type,",
-              "u_H in; u out).  traffic / must move",
+              "u_H in; u out), patch_seam_kernel: the level-0 up-leg of one cycle and down-leg of the next in one launch",
+              "(x, f, type, u_H in; smoothed u, f_H out).  traffic / must move",
               "above 1 = halo re-reads that miss the L2 / Infinity Cache.", ""]
     out_dir = os.environ.get("PMC_OUT_DIR", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
