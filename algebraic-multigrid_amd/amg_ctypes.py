@@ -166,6 +166,7 @@ _SIGS = {
     "amg_hip_f32_line_subsweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "amg_hip_f32_line_factors": (C.c_int, [C.c_void_p, C.c_int32] + [C.POINTER(C.c_float)] * 3),
     "amg_hip_set_f32_lines": (None, [C.c_int32]),
+    "amg_hip_set_f32_dict": (None, [C.c_int32]),
     "amg_hip_set_block_lines": (None, [C.c_int32]),
     "amg_hip_n_levels": (C.c_int32, [C.c_void_p]),
     "amg_hip_get_n_dofs": (C.c_int64, [C.c_void_p, C.c_int32]),
@@ -442,6 +443,22 @@ def f32_lines():
         yield
     finally:
         set_f32_lines(0)
+
+
+def set_f32_dict(on):
+    """The single-precision entry points accept solvers with dictionary-coded levels (1) or refuse them
+    (0, the default); process-wide, read when a float entry point first makes a solver's float copies."""
+    lib().amg_hip_set_f32_dict(int(bool(on)))
+
+
+@contextlib.contextmanager
+def f32_dict():
+    """with amg.f32_dict(): ... -- set_f32_dict(1) inside the block, 0 again after it."""
+    set_f32_dict(1)
+    try:
+        yield
+    finally:
+        set_f32_dict(0)
 
 
 def set_block_lines(on):

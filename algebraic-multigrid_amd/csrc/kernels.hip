@@ -38,6 +38,8 @@
 //   graph-capturable kernels over hipIpc-mapped peer memory.
 // K-F32 (sell_f32_kernel, csr_f32_kernel, to_f32 / to_f64) -- the row kernels and transfers in
 //   float for the single-precision preconditioner of the fp64 PCG.
+// K-DictF32 (dict_f32_kernel) -- K-Dict's plain row path on float vectors: the double matrix's codes,
+//   row types and offsets, a float copy of the pair table's values.
 // =============================================================================
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -7995,6 +7997,243 @@ hipError_t launch_csr_f32(int mode, int64_t n, const int32_t* rowptr, const int3
   }
   AMG_F32_MODES(AMG_F32_CSR)
 #undef AMG_F32_CSR
+  return hipGetLastError();
+}
+
+// dict_f32_kernel (K-DictF32): dict_kernel's plain path (dict_fetch / dict_expand / dict_rows /
+// dict_store) on float vectors.  The matrix is the DOUBLE matrix's own: code words or row types with
+// their word table, the pair table's column offsets, the typed / untyped choice; the only float array
+// is the pair table's values, tabv[t] = (float)dval[t].  LDS: one 16-byte entry per code {a, d, off4}
+// (off4 = BYTE offset of the column from the row's diagonal column in a float vector; entry 255 = no
+// entry = all zero, its gather reads the row's own x) and the word table of the double kernel.
+// Arithmetic = tests/f32_twin.py: a row's entries in code order (ascending column), every product
+// rounded on its own (no contraction), CSR_RESID from f_i with empty slots dropped by a select (acc -
+// (+0.0f) == acc for every acc), Jacobi / Chebyshev from +0.0f over the off-diagonal entries with
+// (+0.0f) * x added for the diagonal slot and for empty slots as dict_rows does in double, the diagonal
+// from the d column, f32_row_epilogue's expressions.  CONDITION: finite vectors.  For finite x the
+// added term is +-0.0f, and a sum that starts at +0.0f never becomes -0.0f, so the result has the bits
+// of skipping the slot; an infinite or NaN x in the row's own column would turn the row into NaN where
+// the SELL / CSR float kernels do not read it.
+// R rows per lane (2: 8-byte lane accesses of x, f, d, out and 16-bit row-type loads; 4: 16-byte
+// accesses and 32-bit row-type loads); a lane whose R rows are not all below n takes them one at a
+// time.  The gathers of at most G rows are in flight together (two-word rows: 2).  No wave-uniform
+// stencil path, no non-temporal accesses, no fused forms.
+struct __attribute__((aligned(16))) DictEntryF32 {
+  float a;
+  float d;
+  int32_t off4;
+  int32_t pad;
+};
+template <int MODE, int WORDS, int UN, int R>
+__global__ __launch_bounds__(256) void dict_f32_kernel(
+    int n, const uint64_t* __restrict__ codes, const uint8_t* __restrict__ rtype,
+    const uint64_t* __restrict__ rwords, const int32_t* __restrict__ doff, const float* __restrict__ tabv,
+    int ntab, const float* x, const float* __restrict__ f, float* out, float omega, int xcd_map, float* dvec,
+    float alpha) {
+  static_assert(R == 2 || R == 4, "rows per lane");
+  typedef float fvec __attribute__((ext_vector_type(R)));
+  typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+  constexpr bool jac = mode_jac(MODE);
+  constexpr bool read_d = mode_cheb(MODE) && !cheb_first(MODE);
+  __shared__ DictEntryF32 tab[256];
+  __shared__ uint64_t wtab[256 * WORDS];
+  const int row0 = (xcd_tile(blockIdx.x, gridDim.x, xcd_map) * 256 + (int)threadIdx.x) * R;
+  // ---- the streamed operands: in flight while the tables are staged
+  uint64_t cw[R][WORDS];
+  uint32_t ty = 0xFFFFFFFFu;  // byte r = type of row r, 255 = empty
+  float fi[R], xi[R], di[R];
+  bool live[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    live[r] = row0 + r < n;
+    fi[r] = xi[r] = di[r] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < WORDS; ++k) cw[r][k] = ~(uint64_t)0;
+  }
+  const bool full = live[R - 1];
+  if (full) {
+    if (rtype) {  // wave-uniform
+      if (R == 4) ty = *reinterpret_cast<const uint32_t*>(rtype + row0);
+      else ty = 0xFFFF0000u | *reinterpret_cast<const uint16_t*>(rtype + row0);
+    } else {
+      const u64x2* vp = reinterpret_cast<const u64x2*>(codes + (int64_t)row0 * WORDS);
+#pragma unroll
+      for (int q = 0; q < R * WORDS / 2; ++q) {
+        const u64x2 t = vp[q];
+        cw[(2 * q) / WORDS][(2 * q) % WORDS] = t.x;
+        cw[(2 * q + 1) / WORDS][(2 * q + 1) % WORDS] = t.y;
+      }
+    }
+    const fvec tf = *reinterpret_cast<const fvec*>(f + row0);
+#pragma unroll
+    for (int r = 0; r < R; ++r) fi[r] = tf[r];
+    if (jac) {
+      const fvec tx = *reinterpret_cast<const fvec*>(x + row0);
+#pragma unroll
+      for (int r = 0; r < R; ++r) xi[r] = tx[r];
+    }
+    if (read_d) {
+      const fvec td = *reinterpret_cast<const fvec*>(dvec + row0);
+#pragma unroll
+      for (int r = 0; r < R; ++r) di[r] = td[r];
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (!live[r]) continue;
+      if (rtype) {
+        ty = (ty & ~(0xFFu << (8 * r))) | ((uint32_t)rtype[row0 + r] << (8 * r));
+      } else {
+#pragma unroll
+        for (int k = 0; k < WORDS; ++k) cw[r][k] = codes[(int64_t)(row0 + r) * WORDS + k];
+      }
+      fi[r] = f[row0 + r];
+      if (jac) xi[r] = x[row0 + r];
+      if (read_d) di[r] = dvec[row0 + r];
+    }
+  }
+  // ---- the tables
+  {
+    const int t = threadIdx.x;  // 256 threads, 256 entries
+    const float v = t < ntab ? tabv[t] : 0.0f;
+    const int32_t o = t < ntab ? doff[t] : 0;
+    DictEntryF32 e;
+    e.a = (jac && o == 0) ? 0.0f : v;
+    e.d = (jac && o == 0 && t < ntab) ? v : 0.0f;
+    e.off4 = o * 4;
+    e.pad = 0;
+    tab[t] = e;
+  }
+  if (rtype) dict_stage_words<WORDS>(wtab, rwords);
+  __syncthreads();
+  if (rtype) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int k = 0; k < WORDS; ++k) cw[r][k] = wtab[((ty >> (8 * r)) & 0xFFu) * WORDS + k];
+  }
+  // ---- decode, gather, row arithmetic: G rows at a time
+  constexpr int G = (WORDS == 2 && R > 2) ? 2 : R;
+  const char* xb = reinterpret_cast<const char*>(x);
+  float res[R], dn[R];
+#pragma unroll
+  for (int g0 = 0; g0 < R; g0 += G) {
+    uint32_t c4[G][UN];
+    float v[G][UN], vd[G][UN], xx[G][UN];
+    bool ok[G][UN];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int r = g0 + g;
+      const uint32_t drow4 = live[r] ? (uint32_t)(row0 + r) * 4u : 0u;
+#pragma unroll
+      for (int u = 0; u < UN; ++u) {
+        const uint32_t w32 = (uint32_t)(cw[r][u >> 3] >> (32 * ((u >> 2) & 1)));
+        const uint32_t code = (w32 >> (8 * (u & 3))) & 0xFFu;
+        const DictEntryF32 e = tab[code];
+        ok[g][u] = code != 0xFFu;
+        c4[g][u] = drow4 + (uint32_t)e.off4;
+        v[g][u] = e.a;
+        vd[g][u] = jac ? e.d : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int u = 0; u < UN; ++u) xx[g][u] = *reinterpret_cast<const float*>(xb + c4[g][u]);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int r = g0 + g;
+      float acc = (MODE == CSR_RESID) ? fi[r] : 0.0f;
+      float diag = 0.0f;
+#pragma unroll
+      for (int u = 0; u < UN; ++u) {
+        float t = v[g][u] * xx[g][u];
+        if (jac) {
+          acc += t;
+          diag += vd[g][u];
+        } else {
+          asm volatile("" : "+v"(t));  // keeps the product and its gather out of a branch (dict_rows)
+          t = ok[g][u] ? t : 0.0f;
+          acc -= t;
+        }
+      }
+      if (MODE == CSR_RESID) {
+        res[r] = acc;
+      } else {
+        // f32_row_epilogue's expressions; the division runs for every row (dict_rows)
+        const bool nod = diag == 0.0f;
+        float q = (fi[r] - acc) / (nod ? 1.0f : diag);
+        asm volatile("" : "+v"(q));
+        if (MODE == CSR_JACOBI) res[r] = nod ? xi[r] : xi[r] + omega * (q - xi[r]);
+        else res[r] = cheb_update_f32<MODE>(nod ? xi[r] : q, xi[r], di[r], alpha, omega, dn[r]);
+      }
+    }
+  }
+  // ---- store
+  constexpr bool write_d = mode_cheb(MODE) && !cheb_last(MODE);
+  if (full) {
+    fvec t;
+#pragma unroll
+    for (int r = 0; r < R; ++r) t[r] = res[r];
+    *reinterpret_cast<fvec*>(out + row0) = t;
+    if (write_d) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) t[r] = dn[r];
+      *reinterpret_cast<fvec*>(dvec + row0) = t;
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (!live[r]) continue;
+      out[row0 + r] = res[r];
+      if (write_d) dvec[row0 + r] = dn[r];
+    }
+  }
+}
+
+// Rows per lane of dict_f32_kernel: DICT_F32_ROWS, the faster one on the level-0 sweep of
+// poisson_tensor(4096) (66 us against 84 us with 4; DESIGN.md: "Single-precision preconditioner");
+// set_dict_rows_per_lane(1), the test switch of the double kernels, selects the other one.  Same bits
+// either way.
+constexpr int DICT_F32_ROWS = 2;
+static int dict_f32_rows() { return g_dict_rows_per_lane == 1 ? 6 - DICT_F32_ROWS : DICT_F32_ROWS; }
+hipError_t launch_dict_f32(int mode, int64_t n, const DictRef& D, const float* tabv, const float* x, const float* f,
+                           float* out, float omega, float* dvec, float alpha, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  // byte offsets of x are 32-bit: 4 (n + 1024) < 2^32
+  if (!dict_args_ok(n, D.words, D.wmax, D.ntab) || n >= ((int64_t)1 << 30) - 1024 || x == out || !tabv)
+    return hipErrorInvalidValue;
+  if (mode_cheb(mode) && !dvec) return hipErrorInvalidValue;
+  const int R = dict_f32_rows();
+  const uintptr_t vec = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(f) |
+                        reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dvec);
+  if ((vec & (uintptr_t)(4 * R - 1)) != 0) return hipErrorInvalidValue;
+  if (D.rtype ? (reinterpret_cast<uintptr_t>(D.rtype) & (uintptr_t)(R - 1)) != 0
+              : (reinterpret_cast<uintptr_t>(D.codes) & 15) != 0)
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + 256 * R - 1) / (256 * R)));
+  const int xcd = dict_xcd_map(D, 256 * R);
+#define AMG_F32_DICT_WU(M, W, U)                                                                                  \
+  do {                                                                                                            \
+    if (R == 4)                                                                                                   \
+      hipLaunchKernelGGL((dict_f32_kernel<M, W, U, 4>), grid, dim3(256), 0, st, (int)n, D.codes, D.rtype, D.rwords, \
+                         D.doff, tabv, D.ntab, x, f, out, omega, xcd, dvec, alpha);                               \
+    else                                                                                                          \
+      hipLaunchKernelGGL((dict_f32_kernel<M, W, U, 2>), grid, dim3(256), 0, st, (int)n, D.codes, D.rtype, D.rwords, \
+                         D.doff, tabv, D.ntab, x, f, out, omega, xcd, dvec, alpha);                               \
+  } while (0)
+#define AMG_F32_DICT(M)                                     \
+  if (D.words == 1) {                                       \
+    if (D.wmax <= 5) AMG_F32_DICT_WU(M, 1, 5);              \
+    else if (D.wmax <= 7) AMG_F32_DICT_WU(M, 1, 7);         \
+    else AMG_F32_DICT_WU(M, 1, 8);                          \
+  } else {                                                  \
+    if (D.wmax <= 9) AMG_F32_DICT_WU(M, 2, 9);              \
+    else AMG_F32_DICT_WU(M, 2, 16);                         \
+  }
+  AMG_F32_MODES(AMG_F32_DICT)
+#undef AMG_F32_DICT
+#undef AMG_F32_DICT_WU
   return hipGetLastError();
 }
 #undef AMG_F32_MODES

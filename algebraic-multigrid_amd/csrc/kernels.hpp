@@ -640,6 +640,13 @@ hipError_t launch_sell_f32(int mode, int64_t n, int idx16, const int64_t* soff, 
 hipError_t launch_csr_f32(int mode, int64_t n, const int32_t* rowptr, const int32_t* col, const float* val,
                           const float* x, const float* f, float* out, float omega, float* dvec, float alpha,
                           hipStream_t st);
+// K-DictF32: the same modes on a dictionary-coded matrix.  D is the DOUBLE matrix's view (codes or row
+// types + word table, column offsets; D.dval is not read), tabv its pair table's values as floats
+// (D.ntab of them).  hipErrorInvalidValue: x == out, a Chebyshev mode without dvec, n >= 2^30 - 1024
+// (the byte offsets of x are 32-bit), or x / f / out / dvec not aligned to 4 R bytes, the row types
+// not to R bytes, the code words not to 16 (R = rows per lane, 4 or 2).
+hipError_t launch_dict_f32(int mode, int64_t n, const DictRef& D, const float* tabv, const float* x, const float* f,
+                           float* out, float omega, float* dvec, float alpha, hipStream_t st);
 // dst[i] = (float)src[i] / (double)src[i], round to nearest
 hipError_t launch_to_f32(int64_t n, const double* src, float* dst, hipStream_t st);
 hipError_t launch_to_f64(int64_t n, const float* src, double* dst, hipStream_t st);

@@ -1531,7 +1531,7 @@ struct Block {
 // captured graph.  Made at the first call, freed with the solver, never rebuilt.
 struct F32Mat {
   const DevMat* src = nullptr;  // layout and index arrays
-  DevMem val;                   // src's sval (SELL) or csr.val (CSR) as floats
+  DevMem val;                   // src's sval (SELL), csr.val (CSR) or dval (dictionary: the pair table) as floats
 };
 // float copies of one K-Line factor set (LineOnDev) and its scratch vector
 struct F32Line {
@@ -1616,6 +1616,13 @@ int g_periodic_device_setup = [] {
 // line-smoother solvers ("Single-precision preconditioner").
 int g_f32_lines = [] {
   const char* e = std::getenv("AMG_HIP_F32_LINES");
+  return (e && *e == '1') ? 1 : 0;
+}();
+// amg_hip_set_f32_dict / AMG_HIP_F32_DICT=1: the single-precision cycle accepts levels stored in the
+// dictionary layout (K-DictF32).  0 by default only because an earlier test pins the refusal of the float
+// entry points on such a solver ("Single-precision preconditioner").
+int g_f32_dict = [] {
+  const char* e = std::getenv("AMG_HIP_F32_DICT");
   return (e && *e == '1') ? 1 : 0;
 }();
 // amg_hip_set_block_lines / AMG_HIP_BLOCK_LINES=1: the block entry points accept the line smoothers
@@ -4241,8 +4248,9 @@ amg_hip_status f32_supported(amg_hip_solver* s) {
 
 amg_hip_status f32_copy_values(const DevMat& A, F32Mat* M, hipStream_t st) {
   M->src = &A;
-  const double* src = A.sell ? A.sval.as<double>() : A.csr.v();
-  const int64_t count = A.sell ? A.slots : A.csr.nnz;
+  // a dictionary matrix has no per-entry values: its float form is the pair table alone
+  const double* src = A.dict ? A.dval.as<double>() : A.sell ? A.sval.as<double>() : A.csr.v();
+  const int64_t count = A.dict ? A.dict_ntab : A.sell ? A.slots : A.csr.nnz;
   HIP_TRY(M->val.alloc(sizeof(float) * (size_t)std::max<int64_t>(count, 1)));
   HIP_TRY(launch_to_f32(count, src, M->val.as<float>(), st));
   return AMG_HIP_OK;
@@ -4292,7 +4300,9 @@ amg_hip_status ensure_f32(amg_hip_solver* s) {
   const int nl = (int)s->lv.size();
   const bool jac = s->opt.smoother == AMG_HIP_SM_JACOBI;
   const bool line = s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT;
-  for (int l = 0; l + 1 < nl; ++l) {
+  // g_f32_dict is read here and nowhere else: nothing is cached on a refusal, so a solver refused with the
+  // switch off is accepted once it is on, and a solver whose copies exist (F.ready) never comes back here
+  for (int l = 0; l + 1 < nl && !g_f32_dict; ++l) {
     const Level& L = s->lv[l];
     if (L.A_rows.dict || (jac && L.A_cols().dict))
       return fail(AMG_HIP_EUNSUPPORTED,
@@ -4343,10 +4353,15 @@ amg_hip_status ensure_f32(amg_hip_solver* s) {
 }
 
 // one launch of a level matrix in float; bytes: SELL 4 + w per entry and 8 per panel, CSR 8 per
-// entry and 4 per row pointer
+// entry and 4 per row pointer, dictionary the double matrix's stream (layout_of) with 4-byte values in
+// the pair table
 hipError_t launch_mat_f32(int mode, const F32Mat& M, const float* x, const float* f, float* out, float omega,
                           float* dvec, float alpha, hipStream_t st) {
   const DevMat& A = *M.src;
+  if (A.dict) {
+    if (A.dict_shift != 0) return hipErrorInvalidValue;  // window blocks: refused before (f32_supported)
+    return launch_dict_f32(mode, A.n_rows, A.dict_ref(), M.val.as<float>(), x, f, out, omega, dvec, alpha, st);
+  }
   if (A.sell)
     return launch_sell_f32(mode, A.n_rows, A.idx16, A.soff.as<int64_t>(), A.scol.p, M.val.as<float>(), x, f, out,
                            omega, dvec, alpha, st);
@@ -4355,6 +4370,10 @@ hipError_t launch_mat_f32(int mode, const F32Mat& M, const float* x, const float
 }
 double mat_bytes_f32(const F32Mat& M) {
   const DevMat& A = *M.src;
+  if (A.dict)
+    return (A.dict_typed ? (double)A.n_rows + 256.0 * 8.0 * (double)A.dict_words
+                         : 8.0 * (double)A.dict_words * (double)A.n_rows) +
+           8.0 * (double)A.dict_ntab;
   if (A.sell) return (double)A.slots * ((A.idx16 & 1) ? 6.0 : 8.0) + 8.0 * (double)((A.n_rows + 63) / 64);
   return 8.0 * (double)A.csr.nnz + 4.0 * (double)(A.csr.n_rows + 1);
 }
@@ -4600,6 +4619,7 @@ void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
 void amg_hip_set_periodic_device_setup(int32_t on) { g_periodic_device_setup = on ? 1 : 0; }
 void amg_hip_set_f32_lines(int32_t on) { g_f32_lines = on ? 1 : 0; }
+void amg_hip_set_f32_dict(int32_t on) { g_f32_dict = on ? 1 : 0; }
 void amg_hip_set_block_lines(int32_t on) { g_block_lines = on ? 1 : 0; }
 void amg_hip_set_patch_min_rows(int64_t rows) { g_patch_min_rows = rows < 0 ? INT64_MAX : rows; }
 

@@ -317,6 +317,19 @@ void amg_hip_set_periodic_device_setup(int32_t on);
  * either way.                                                                                     */
 void amg_hip_set_f32_lines(int32_t on);
 
+/* The single-precision entry points (amg_hip_apply_f32, amg_hip_pcg_mixed, amg_hip_f32_*) accept
+ * solvers with levels stored in the dictionary layout (K-DictF32: the dictionary row kernel on float
+ * vectors; code words, row types and column offsets are the double matrix's own arrays, the only float
+ * copy is the pair table's values, at most 255 floats per matrix).  Process-wide, read whenever a float
+ * entry point runs its checks on a solver that has no float copies yet; default 0 (AMG_HIP_F32_DICT=1 in
+ * the environment turns it on).  Off: those solvers are refused as before (AMG_HIP_EUNSUPPORTED).  A
+ * solver first used with the switch on keeps working after it is turned off (its copies are made
+ * once); a solver refused with it off is accepted once it is on (a refusal leaves nothing behind).  No
+ * double entry point and no float result on SELL / CSR levels is touched either way.  With
+ * amg_hip_set_dict_rows(1) the float kernel runs its other rows-per-lane form (4 instead of 2): same
+ * bits, a test switch.                                                                             */
+void amg_hip_set_f32_dict(int32_t on);
+
 /* The block entry points (amg_hip_block_vcycles, _rss, _pcg, _must_move) accept solvers smoothed with
  * AMG_HIP_SM_LINE_JACOBI and AMG_HIP_SM_LINE_ALT, cyclic_lines included (K-LineBlock: the line solve
  * kernels on row-major panels, reading the solver's own double factors once for all columns; column j
@@ -865,8 +878,9 @@ amg_hip_status amg_hip_block_must_move(amg_hip_solver* s, int32_t k, double* byt
  * bad rtol / max_iters (amg_hip_pcg_mixed); AMG_HIP_EUNSUPPORTED a window solver; AMG_HIP_EUNSUPPORTED
  * a smoother other than AMG_HIP_SM_JACOBI / AMG_HIP_SM_CHEBYSHEV; AMG_HIP_EUNSUPPORTED a one-level
  * solver.  Then a host_only solver fails (AMG_HIP_EINVAL), then AMG_HIP_EUNSUPPORTED for a level
- * stored in the dictionary layout (the level in the message): create the solver with
- * layout = AMG_HIP_LAYOUT_SELL.
+ * stored in the dictionary layout (the level in the message),
+ * unless amg_hip_set_f32_dict(1) is in force: create the solver with layout = AMG_HIP_LAYOUT_SELL, or
+ * turn that switch on.
  *
  * With amg_hip_set_f32_lines(1) the smoother check also accepts AMG_HIP_SM_LINE_JACOBI and
  * AMG_HIP_SM_LINE_ALT (cyclic_lines included); every other check and its place in the order stay.
@@ -886,7 +900,10 @@ amg_hip_status amg_hip_pcg_mixed(amg_hip_solver* s, double rtol, int64_t max_ite
                                  double* relres);
 /* Bytes the launches of one amg_hip_apply_f32 have to move: per SELL entry 4 + w (w = 2 or 4 index
  * bytes) and 8 per panel, CSR 8 per entry + 4 per row pointer, every float vector pass 4 per row; the
- * coarsest solve and the conversions around it and around the cycle in their own widths. */
+ * coarsest solve and the conversions around it and around the cycle in their own widths.  A dictionary
+ * level (amg_hip_set_f32_dict): n_rows + 256 * 8 * words + 8 * ntab with row types, 8 * words * n_rows +
+ * 8 * ntab without (words = 1 or 2 code words per row, ntab = the distinct (column offset, value) pairs
+ * of the matrix): amg_hip_level_layout's matrix_stream_bytes less 4 * ntab. */
 amg_hip_status amg_hip_f32_must_move(amg_hip_solver* s, double* bytes);
 /* TEST HOOKS on the float cycle, the float counterparts of amg_hip_get_vec / amg_hip_set_vec /
  * amg_hip_level_op: they let a test pin single steps of amg_hip_apply_f32 bit for bit and are not

@@ -18,6 +18,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py periodic-setup [<nx> <ny> <nz>]             set-up seconds of tensor_periodic_dev on that operator with set_periodic_device_setup off (host constructor) and on (device), legs alternate; next to them tensor_dev on the open-box operator of the same grid
        config_bench.py periodic-lines                              PCG to 1e-8 and ms per V-cycle of AMG_HIP_SM_LINE_ALT on diffusion that is strong along a periodic x axis (4096 x 1024, 256^3): open lines (cyclic_lines 0) against cyclic lines (cyclic_lines 1), legs alternate
        config_bench.py mixed-line [split2|split3|cyclic2|cyclic3]  amg_hip_pcg and amg_hip_pcg_mixed alternating on AMG_HIP_SM_LINE_ALT solvers (amg_hip_set_f32_lines): split-anisotropy through tensor_dev and the periodic-lines operator with cyclic lines, 4096 x 1024 and 256^3
+       config_bench.py mixed-dict [t2|t3|c2|flat]                  amg_hip_pcg on the dictionary layout, amg_hip_pcg_mixed on a SELL solver and amg_hip_pcg_mixed on the dictionary solver (amg_hip_set_f32_dict) alternating: poisson_tensor 4096^2 and 256^3 (Jacobi 2+2), 4096^2 Chebyshev(2), poisson 4096^2 on the flat hierarchy
        config_bench.py block                                       block (multi-RHS) cycles, k = 1..16
        config_bench.py block8 rs|p4096                             one block workload at k = 8 (kernel traces)
        config_bench.py block-line [jacobi|split2|split3|cyclic2]   the line smoothers through the block entry points (amg_hip_set_block_lines) and the single-vector path alternating, k = 1..16: cycles and PCG to 1e-8
@@ -999,6 +1000,119 @@ def mixed_line_cases(which=None):
             run_mixed_line(label, make)
 
 
+def run_mixed_dict(label, make, reps=3, rtol=1e-8, applies=10, by_level=False):
+    """Three runs alternating in one process, best of `reps`, PCG to `rtol` from x = 0: amg_hip_pcg on the
+    default (dictionary) layout, amg_hip_pcg_mixed on a layout = SELL solver, amg_hip_pcg_mixed on the
+    dictionary solver (amg_hip_set_f32_dict).  Per run: iterations, wall ms, ms per preconditioner
+    application over `applies` calls closed by one synchronise (double: vcycle(), the cycle amg_hip_pcg
+    runs), and the must-move bytes of one application over that time as a share of 8 TB/s.  Then the level-0
+    Jacobi sweep of the float dictionary kernel in its two rows-per-lane forms (amg_hip_set_dict_rows), and
+    with by_level the float cycle's steps per level on both layouts."""
+    import torch
+    t0 = time.perf_counter()
+    mg = make()
+    sell = make(layout=amg.LAYOUT_SELL)
+    mg.sync()
+    nl = mg.n_levels
+    lay = [mg.level_layout(l)[0] for l in range(nl - 1)]
+    print(f"mixed-dict {label}: setup of both solvers {time.perf_counter() - t0:.2f} s, {nl} levels, layouts "
+          f"{lay} (3 = dictionary) / SELL solver {[sell.level_layout(l)[0] for l in range(nl - 1)]}", flush=True)
+    n = mg.get_n_dofs(0)
+    b = torch.from_numpy(mg.get_rhs(0)).cuda()
+    z = torch.empty_like(b)
+    amg.set_f32_dict(1)
+    runs = {"double dict": (mg, mg.pcg, None, mg.cycle_must_move()),
+            "float SELL": (sell, sell.pcg_mixed, sell.apply_f32, sell.f32_must_move()),
+            "float dict": (mg, mg.pcg_mixed, mg.apply_f32, mg.f32_must_move())}
+    mg.apply_dev(b.data_ptr(), z.data_ptr())  # first calls: work vectors, float copies, captured graphs
+    for name in ("float SELL", "float dict"):
+        runs[name][2](b.data_ptr(), z.data_ptr())
+    mg.sync()
+    sell.sync()
+    best = {}
+    for rep_ in range(reps):
+        for name, (m, solve, apply, mm) in runs.items():
+            m.zero_vec(0, "u")
+            m.sync()
+            t0 = time.perf_counter()
+            _, it, rel = solve(rtol=rtol, max_iters=300)
+            dt = time.perf_counter() - t0
+            m.zero_vec(0, "u")
+            m.sync()
+            t0 = time.perf_counter()
+            if apply is None:
+                m.vcycle(applies)
+            else:
+                for _ in range(applies):
+                    apply(b.data_ptr(), z.data_ptr())
+            m.sync()
+            da = (time.perf_counter() - t0) / applies
+            old = best.get(name, (it, dt, da))
+            best[name] = (it, min(old[1], dt), min(old[2], da))
+            print(f"mixed-dict {label}, {name} rep {rep_}: {it} iterations, {dt * 1e3:.2f} ms to {rtol:g} (relres "
+                  f"{rel:.2e}, {'reached' if rel <= rtol else 'NOT reached'}), {da * 1e3:.3f} ms per application, "
+                  f"must-move {mm / 1e6:.1f} MB = {mm / da / 8e12 * 100:.1f} % of 8 TB/s", flush=True)
+    d, s, f = best["double dict"], best["float SELL"], best["float dict"]
+    print(f"mixed-dict {label} ({n} dofs): best solve double dict {d[0]} it {d[1] * 1e3:.2f} ms, float SELL {s[0]} it "
+          f"{s[1] * 1e3:.2f} ms, float dict {f[0]} it {f[1] * 1e3:.2f} ms (double / float dict {d[1] / f[1]:.2f}, float "
+          f"SELL / float dict {s[1] / f[1]:.2f}); best application double dict {d[2] * 1e3:.3f} ms, float SELL "
+          f"{s[2] * 1e3:.3f} ms, float dict {f[2] * 1e3:.3f} ms (double / float dict {d[2] / f[2]:.2f}, float SELL / "
+          f"float dict {s[2] / f[2]:.2f})", flush=True)
+
+    def op_us(m, l, op, count=20):
+        m.f32_level_op(l, op)
+        m.sync()
+        t0 = time.perf_counter()
+        for _ in range(count):
+            m.f32_level_op(l, op)
+        m.sync()
+        return (time.perf_counter() - t0) / count * 1e6
+
+    if mg.level_layout(0)[0] == amg.LAYOUT_DICT:
+        # kernels.hip: DICT_F32_ROWS = 2 is the default form, amg_hip_set_dict_rows(1) selects the other
+        launches = 2  # two Jacobi sweeps, or the two steps of Chebyshev(2)
+        forms = {}
+        for rep_ in range(reps):
+            for rows, arg in ((2, 2), (4, 1)):
+                amg.set_dict_rows(arg)
+                us = op_us(mg, 0, 0) / launches
+                forms[rows] = min(forms.get(rows, us), us)
+        amg.set_dict_rows(2)
+        stream = mg.level_layout(0)[1] + 12 * n  # the matrix stream (4 bytes per pair too many: < 1 KB) and x, f, out
+        print(f"mixed-dict {label}: level-0 sweep of dict_f32_kernel, best of {reps} x 20 smoothings of 2 launches: "
+              + ", ".join(f"{r} rows per lane {forms[r]:.1f} us ({stream / forms[r] / 8e6 * 100:.1f} % of 8 TB/s)"
+                          for r in (2, 4)), flush=True)
+    if by_level:
+        for l in range(nl - 1):
+            row = []
+            for op, what in ((0, "smoothing"), (1, "residual"), (2, "restriction"), (3, "prolongation")):
+                row.append(f"{what} {op_us(mg, l, op, 10):.1f} / {op_us(sell, l, op, 10):.1f}")
+            print(f"mixed-dict {label}: level {l} ({mg.get_n_dofs(l)} rows, layout {mg.level_layout(l)[0]}) us per step, "
+                  "float dict / float SELL: " + ", ".join(row), flush=True)
+    amg.set_f32_dict(0)
+    mg.close()
+    sell.close()
+
+
+def mixed_dict_cases(which=None):
+    """profiles/mixed_dict_config_bench.txt"""
+    jac = dict(smoother=amg.SM_JACOBI, smoother_iters=2, omega=0.8)
+    cheb = dict(smoother=amg.SM_CHEBYSHEV, smoother_iters=1, cheb_degree=2)
+
+    def tensor(n, L, dim, opts):
+        return lambda **kw: amg.Multigrid.poisson_tensor(n, L, dim=dim, device_setup=True, **dict(opts, **kw))
+
+    def flat(**kw):
+        return amg.Multigrid.poisson(4096, 16, **dict(KW["jacobi"], **kw))
+    cases = {"t2": ("poisson_tensor 4096^2 / 10, Jacobi 0.8 2+2", tensor(4096, 10, 2, jac), True),
+             "t3": ("poisson_tensor 256^3 / 7, Jacobi 0.8 2+2", tensor(256, 7, 3, jac), True),
+             "c2": ("poisson_tensor 4096^2 / 10, Chebyshev(2) 1+1", tensor(4096, 10, 2, cheb), False),
+             "flat": ("poisson 4096^2 / 16 (flat index), Jacobi 0.6 2+2", flat, False)}
+    for key, (label, make, by_level) in cases.items():
+        if which in (None, key):
+            run_mixed_dict(label, make, by_level=by_level)
+
+
 def block_memory(mg, kp, cheb):
     """device bytes the block cycle adds for pitch kp: per-level panels (U, F, R, T and Chebyshev D;
     U, F on the coarsest level), the coarse solve's three column buffers, and the CSR copies of the
@@ -1270,6 +1384,10 @@ elif len(sys.argv) > 1 and sys.argv[1] == "mixed-line":
     amg.set_periodic_device_setup(1)
     amg.set_f32_lines(1)
     mixed_line_cases(sys.argv[2] if len(sys.argv) > 2 else None)
+elif len(sys.argv) > 1 and sys.argv[1] == "mixed-dict":
+    # profiles/mixed_dict_config_bench.txt; an argument picks one case: t2 | t3 | c2 | flat
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    mixed_dict_cases(sys.argv[2] if len(sys.argv) > 2 else None)
 elif len(sys.argv) > 1 and sys.argv[1] == "periodic-setup":
     # profiles/periodic_setup.txt
     os.environ.setdefault("AMG_HIP_TIMING", "1")
