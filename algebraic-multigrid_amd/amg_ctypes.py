@@ -152,6 +152,9 @@ _SIGS = {
     "amg_hip_rss": (C.c_int, [C.c_void_p, _f64p]),
     "amg_hip_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "amg_hip_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, _i64p, _f64p]),
+    "amg_hip_set_mean_projection": (C.c_int, [C.c_void_p, C.c_int32]),
+    "amg_hip_get_mean_projection": (C.c_int, [C.c_void_p, _i32p]),
+    "amg_hip_center_vec": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "amg_hip_block_vcycles": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
     "amg_hip_block_rss": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _f64p]),
     "amg_hip_block_pcg": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int64,
@@ -1241,6 +1244,21 @@ class Multigrid:
         it, rel = C.c_int64(0), C.c_double(0)
         _chk(lib().amg_hip_pcg(self._h, rtol, max_iters, C.byref(it), C.byref(rel)))
         return self.get_soln(0), it.value, rel.value
+
+    def set_mean_projection(self, on):
+        """singular solvers: pcg(), pcg_mixed() and block_pcg() project b, every preconditioned residual
+        and the result onto the complement of the constants (amg_hip_set_mean_projection)"""
+        _chk(lib().amg_hip_set_mean_projection(self._h, int(on)))
+
+    @property
+    def mean_projection(self):
+        on = C.c_int32(0)
+        _chk(lib().amg_hip_get_mean_projection(self._h, C.byref(on)))
+        return on.value
+
+    def center_vec(self, level, which):
+        """v = v - sum(v) / n on a level vector, which = "u" / 0 or "f" / 1 (amg_hip_center_vec)"""
+        _chk(lib().amg_hip_center_vec(self._h, int(level), {"u": 0, "f": 1}.get(which, which)))
 
     def apply_f32(self, v_dev, z_dev):
         """z = M32^-1 v: apply_dev with the whole cycle in single precision (amg_hip_apply_f32);

@@ -3789,6 +3789,74 @@ hipError_t launch_pcg_update_p(int64_t n, const double* num, const double* den, 
   return hipGetLastError();
 }
 
+// --------------------------------------------------------------- K-Center ----
+// Mean projection of the PCG drivers on singular solvers (amg_hip_set_mean_projection):
+// centre(v)_i = v_i - m with m = *sum / (double)n, one IEEE divide of launch_sum's device scalar
+// and one subtract per entry.
+// center_kernel: dst = centre(src), dst may be src.  Element-wise, so a lane takes two neighbours
+// in one 16-byte access (PAIRS; both pointers 16-byte aligned) and the odd last entry goes to the
+// thread after the last pair.
+template <bool PAIRS>
+__global__ __launch_bounds__(256) void center_kernel(int64_t n, const double* __restrict__ sum, const double* src,
+                                                     double* dst) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const double m = *sum / (double)n;
+  if (PAIRS) {
+    const int64_t np = n >> 1;
+    if (e < np) {
+      double2 v = reinterpret_cast<const double2*>(src)[e];
+      v.x = v.x - m;
+      v.y = v.y - m;
+      reinterpret_cast<double2*>(dst)[e] = v;
+    } else if (e == np && (n & 1)) {
+      dst[n - 1] = src[n - 1] - m;
+    }
+  } else {
+    if (e < n) dst[e] = src[e] - m;
+  }
+}
+hipError_t launch_center(int64_t n, const double* sum, const double* src, double* dst, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+    const int64_t threads = (n >> 1) + (n & 1);
+    hipLaunchKernelGGL(center_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, n, sum, src,
+                       dst);
+  } else {
+    hipLaunchKernelGGL(center_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, sum, src, dst);
+  }
+  return hipGetLastError();
+}
+// center_dot_kernel: z = centre(z) and the first stage of r . z in one pass: dot_kernel's grid,
+// grid-stride order and tree with the term r[i] * (z[i] - m), so the partials -- and after
+// sum_kernel the result -- have the bits of launch_dot(r, centre(z)).  The tree hands entry i to
+// thread i mod G, which leaves one entry per lane and access.
+__global__ __launch_bounds__(256) void center_dot_kernel(int64_t n, const double* __restrict__ sum,
+                                                         double* __restrict__ z, const double* __restrict__ r,
+                                                         double* __restrict__ out) {
+  __shared__ double part[4];
+  const double m = *sum / (double)n;
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const double zc = z[i] - m;
+    z[i] = zc;
+    s += r[i] * zc;
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
+}
+hipError_t launch_center_dot(int64_t n, const double* sum, double* z, const double* r, double* out,
+                             double* scratch, hipStream_t st) {
+  int64_t g = (n + 255) / 256;
+  if (g > 1024) g = 1024;
+  if (g < 1) g = 1;
+  hipLaunchKernelGGL(center_dot_kernel, dim3((unsigned)g), dim3(256), 0, st, n, sum, z, r, scratch);
+  hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, st, g, scratch, out, 0);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- K-GS-lex ---
 // Exact lexicographic Gauss-Seidel (smoother.hpp:101-174) under a dependency
 // schedule built on the host (host_setup.cpp: build_lex_schedule).  ONE
@@ -6731,6 +6799,103 @@ hipError_t launch_block_pcg_update_p(int kp, int64_t n, const double* num, const
   if (n <= 0) return hipSuccess;
   const int ks = __builtin_ctz((unsigned)kp);
   hipLaunchKernelGGL(block_pcg_p_kernel, block_grid(n * kp), dim3(256), 0, st, n, ks, num, den, act, p, z);
+  return hipGetLastError();
+}
+
+// K-Center per column of a panel: m_j = sums[j] / (double)n from launch_block_sum's device scalars.
+// The panels are allocations of the block path's own, so a row of kp >= 2 contiguous columns starts on
+// a 16-byte boundary and a lane takes two columns of one row per access.
+// block_center_kernel: v = centre(v) in every column.
+template <bool PAIRS>
+__global__ __launch_bounds__(256) void block_center_kernel(int64_t n, int ks, const double* __restrict__ sums,
+                                                           double* v) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const double dn = (double)n;
+  if (PAIRS) {
+    if (t >= ((n << ks) >> 1)) return;
+    const int c = (int)((2 * t) & ((1 << ks) - 1));
+    double2 w = reinterpret_cast<double2*>(v)[t];
+    w.x = w.x - sums[c] / dn;
+    w.y = w.y - sums[c + 1] / dn;
+    reinterpret_cast<double2*>(v)[t] = w;
+  } else {
+    if (t >= (n << ks)) return;
+    v[t] = v[t] - sums[t & ((1 << ks) - 1)] / dn;
+  }
+}
+hipError_t launch_block_center(int kp, int64_t n, const double* sums, double* v, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (((uintptr_t)v & 15) != 0) return hipErrorInvalidValue;
+  const int ks = __builtin_ctz((unsigned)kp);
+  if (kp >= 2)
+    hipLaunchKernelGGL(block_center_kernel<true>, block_grid(n * kp / 2), dim3(256), 0, st, n, ks, sums, v);
+  else
+    hipLaunchKernelGGL(block_center_kernel<false>, block_grid(n), dim3(256), 0, st, n, ks, sums, v);
+  return hipGetLastError();
+}
+// block_center_dot_kernel<KP>: center_dot_kernel on every column: block_sum_kernel<KP>'s rows per
+// thread, order and tree with the term r[i, j] * (z[i, j] - m_j), z stored centred.
+template <int KP>
+__global__ __launch_bounds__(256) void block_center_dot_kernel(int64_t n, const double* __restrict__ sums,
+                                                               double* __restrict__ z, const double* __restrict__ r,
+                                                               double* __restrict__ out) {
+  __shared__ double part[4][KP];
+  double s[KP], m[KP];
+#pragma unroll
+  for (int j = 0; j < KP; ++j) {
+    s[j] = 0.0;
+    m[j] = sums[j] / (double)n;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (KP >= 2) {
+      double2* zr = reinterpret_cast<double2*>(z + i * KP);
+      const double2* rr = reinterpret_cast<const double2*>(r + i * KP);
+#pragma unroll
+      for (int j = 0; j < KP / 2; ++j) {
+        double2 zc = zr[j];
+        const double2 rv = rr[j];
+        zc.x = zc.x - m[2 * j];
+        zc.y = zc.y - m[2 * j + 1];
+        zr[j] = zc;
+        s[2 * j] += rv.x * zc.x;
+        s[2 * j + 1] += rv.y * zc.y;
+      }
+    } else {
+      const double zc = z[i] - m[0];
+      z[i] = zc;
+      s[0] += r[i] * zc;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KP; ++j) {
+    const double w = wave_sum(s[j]);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][j] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < KP) {
+    const int j = threadIdx.x;
+    out[(int64_t)blockIdx.x * KP + j] = ((part[0][j] + part[1][j]) + part[2][j]) + part[3][j];
+  }
+}
+// z = centre(z) per column and out[j] = sum_i r[i, j] z[i, j] of the centred z; scratch: 1024 x kp doubles
+hipError_t launch_block_center_dot(int kp, int64_t n, const double* sums, double* z, const double* r, double* out,
+                                   double* scratch, hipStream_t st) {
+  if ((((uintptr_t)z | (uintptr_t)r) & 15) != 0) return hipErrorInvalidValue;
+  int64_t g = (n + 255) / 256;
+  if (g > 1024) g = 1024;
+  if (g < 1) g = 1;
+#define AMG_BLOCK_CENTER_DOT(KP)                                                                                  \
+  hipLaunchKernelGGL(block_center_dot_kernel<KP>, dim3((unsigned)g), dim3(256), 0, st, n, sums, z, r, scratch);  \
+  hipLaunchKernelGGL(block_sum_kernel<KP>, dim3(1), dim3(256), 0, st, g, scratch, (const double*)nullptr, out)
+  switch (kp) {
+    case 1: AMG_BLOCK_CENTER_DOT(1); break;
+    case 2: AMG_BLOCK_CENTER_DOT(2); break;
+    case 4: AMG_BLOCK_CENTER_DOT(4); break;
+    case 8: AMG_BLOCK_CENTER_DOT(8); break;
+    case 16: AMG_BLOCK_CENTER_DOT(16); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef AMG_BLOCK_CENTER_DOT
   return hipGetLastError();
 }
 

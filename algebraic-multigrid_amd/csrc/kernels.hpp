@@ -417,6 +417,12 @@ hipError_t launch_pcg_update_xr(int64_t n, const double* num, const double* den,
                                 const double* p, const double* q, hipStream_t st);
 hipError_t launch_pcg_update_p(int64_t n, const double* num, const double* den, double* p,
                                const double* z, hipStream_t st);
+// K-Center: centre(v)_i = v_i - *sum / (double)n, *sum the device scalar of launch_sum(v, square = 0).
+// launch_center: dst = centre(src) (dst may be src).  launch_center_dot: z = centre(z) and
+// *out = sum r_i z_i of the centred z in one pass, the bits of launch_dot(r, centre(z)); scratch: 1024 doubles
+hipError_t launch_center(int64_t n, const double* sum, const double* src, double* dst, hipStream_t st);
+hipError_t launch_center_dot(int64_t n, const double* sum, double* z, const double* r, double* out,
+                             double* scratch, hipStream_t st);
 
 // In-graph neighbour exchange (K-Halo).  All pointers are device pointers; *_at_*
 // and dst_* point into a neighbour's hipIpc-mapped arena.
@@ -613,6 +619,11 @@ hipError_t launch_block_pcg_update_xr(int kp, int64_t n, const double* num, cons
                                       double* x, double* r, const double* p, const double* q, hipStream_t st);
 hipError_t launch_block_pcg_update_p(int kp, int64_t n, const double* num, const double* den, const int32_t* act,
                                      double* p, const double* z, hipStream_t st);
+// K-Center per column j of a panel, m_j = sums[j] / (double)n (sums: launch_block_sum(v, null)):
+// v = centre(v); z = centre(z) with out[j] = sum_i r[i, j] z[i, j] of the centred z (scratch: 1024 kp)
+hipError_t launch_block_center(int kp, int64_t n, const double* sums, double* v, hipStream_t st);
+hipError_t launch_block_center_dot(int kp, int64_t n, const double* sums, double* z, const double* r, double* out,
+                                   double* scratch, hipStream_t st);
 
 // K-LineBlock (kernels.hip): K-Line, K-LineX and K-LineSeam on the panels of K-Block.  The factors are
 // the single-vector arrays (one entry per row, read once for the kp columns); r, y, u are n x kp

@@ -1648,6 +1648,7 @@ struct amg_hip_solver {
   CoarseOnDev coarse;  // coarsest level factor
   DevMem scratch;   // 1024 doubles + 1 result
   DevMem pcg_x, pcg_p, pcg_q, pcg_b;  // PCG work vectors (allocated on first use)
+  bool project_mean = false;  // amg_hip_set_mean_projection: the PCG drivers project onto the complement of the constants
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   bool graph_ready = false;
@@ -5485,6 +5486,9 @@ amg_hip_status amg_hip_apply(amg_hip_solver* s, const double* v_dev, double* z_d
 // The iteration shared by amg_hip_pcg and amg_hip_pcg_mixed.  r: where the residual lives, z: where
 // precond() leaves M^-1 r (enqueued on the solver's stream).  b is taken from level 0's f and parked
 // while r may be that very vector; x starts as level 0's u and is copied back there at the end.
+// With s->project_mean (K-Center; centre(v) = v - sum(v) / n): the right-hand side of the iteration is
+// centre(b), formed in q, which is free until the first q = A p; every z is centred in the pass that
+// forms r . z; x is centred on every way out.  Without it the launches are the ones listed here.
 extern "C++" template <class Precond>
 static amg_hip_status pcg_run(amg_hip_solver* s, double rtol, int64_t max_iters, int64_t* iters, double* relres,
                               double* r, double* z, Precond precond) {
@@ -5502,19 +5506,31 @@ static amg_hip_status pcg_run(amg_hip_solver* s, double rtol, int64_t max_iters,
   double* d_pq = sc + 1031;
   double* d_rzn = sc + 1032;
   double* d_rr = sc + 1033;
+  double* d_sum = sc + 1034;      // K-Center: the sum of the vector being centred
+  const bool project = s->project_mean;
   double h[2];
   // b . b
-  HIP_TRY(launch_dot(n, L.f.as<double>(), L.f.as<double>(), d_rr, part, st));
+  const double* b = L.f.as<double>();
+  if (project) {
+    HIP_TRY(launch_sum(n, b, d_sum, part, 0, st));
+    HIP_TRY(launch_center(n, d_sum, b, q, st));
+    b = q;
+  }
+  HIP_TRY(launch_dot(n, b, b, d_rr, part, st));
   HIP_TRY(hipMemcpyAsync(h, d_rr, sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const double bnorm = std::sqrt(h[0]);
   HIP_TRY(hipMemcpyAsync(bsv, L.f.p, bytes, hipMemcpyDeviceToDevice, st));   // park b
   HIP_TRY(hipMemcpyAsync(x, L.u.p, bytes, hipMemcpyDeviceToDevice, st));     // x = u_0
   // r = b - A x (multigrid.hpp:272-274 arithmetic), in place of b
-  HIP_TRY(launch_mat(CSR_RESID, L.A_rows, x, bsv, r, 1.0, st));
+  HIP_TRY(launch_mat(CSR_RESID, L.A_rows, x, project ? q : bsv, r, 1.0, st));
   int64_t it = 0;
   double rel = 0.0;
   auto finish = [&]() -> amg_hip_status {
+    if (project) {
+      HIP_TRY(launch_sum(n, x, d_sum, part, 0, st));
+      HIP_TRY(launch_center(n, d_sum, x, x, st));
+    }
     HIP_TRY(hipMemcpyAsync(L.f.p, bsv, bytes, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(L.u.p, x, bytes, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -5530,8 +5546,14 @@ static amg_hip_status pcg_run(amg_hip_solver* s, double rtol, int64_t max_iters,
   // z = M^-1 r; p = z; rz = r . z
   amg_hip_status rc = precond();
   if (rc != AMG_HIP_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(launch_dot(n, r, z, d_rz, part, st));
+  if (project) {  // z = centre(z) ahead of p = z
+    HIP_TRY(launch_sum(n, z, d_sum, part, 0, st));
+    HIP_TRY(launch_center_dot(n, d_sum, z, r, d_rz, part, st));
+    HIP_TRY(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, st));
+  } else {
+    HIP_TRY(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(launch_dot(n, r, z, d_rz, part, st));
+  }
   while (it < max_iters) {
     HIP_TRY(launch_mat(CSR_SPMV, L.A_rows, p, nullptr, q, 1.0, st));     // q = A p
     HIP_TRY(launch_dot(n, p, q, d_pq, part, st));
@@ -5543,7 +5565,12 @@ static amg_hip_status pcg_run(amg_hip_solver* s, double rtol, int64_t max_iters,
     rel = bnorm > 0 ? std::sqrt(h[0]) / bnorm : std::sqrt(h[0]);
     if (!(rel > rtol) || it >= max_iters) break;                         // NaN leaves too
     if ((rc = precond()) != AMG_HIP_OK) return rc;                       // z = M^-1 r
-    HIP_TRY(launch_dot(n, r, z, d_rzn, part, st));
+    if (project) {
+      HIP_TRY(launch_sum(n, z, d_sum, part, 0, st));
+      HIP_TRY(launch_center_dot(n, d_sum, z, r, d_rzn, part, st));
+    } else {
+      HIP_TRY(launch_dot(n, r, z, d_rzn, part, st));
+    }
     HIP_TRY(launch_pcg_update_p(n, d_rzn, d_rz, p, z, st));              // beta = rz_new / rz
     HIP_TRY(hipMemcpyAsync(d_rz, d_rzn, sizeof(double), hipMemcpyDeviceToDevice, st));
   }
@@ -5563,6 +5590,38 @@ amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, in
     HIP_TRY(hipMemsetAsync(L.u.p, 0, sizeof(double) * (size_t)L.n, s->stream));
     return amg_hip_vcycles(s, 1);
   });
+}
+
+// ---- mean projection (K-Center): the switch of the PCG drivers, and centre() on a level vector ----
+amg_hip_status amg_hip_set_mean_projection(amg_hip_solver* s, int32_t on) {
+  if (!s) return fail(AMG_HIP_EINVAL, "null solver");
+  if (on != 0 && on != 1)
+    return fail(AMG_HIP_EINVAL, "amg_hip_set_mean_projection: `on` must be 0 or 1, got " + std::to_string(on));
+  if (on && !s->opt.singular)
+    return fail(AMG_HIP_EINVAL, "amg_hip_set_mean_projection: the solver was not created with `singular` = 1 (the "
+                                "constants are not the null space of its operator)");
+  s->project_mean = on != 0;
+  return AMG_HIP_OK;
+}
+amg_hip_status amg_hip_get_mean_projection(const amg_hip_solver* s, int32_t* on) {
+  if (!s || !on) return fail(AMG_HIP_EINVAL, "null argument");
+  *on = s->project_mean ? 1 : 0;
+  return AMG_HIP_OK;
+}
+static DevMem* pick_vec(amg_hip_solver* s, int32_t level, int32_t which);  // with amg_hip_get_vec below
+amg_hip_status amg_hip_center_vec(amg_hip_solver* s, int32_t level, int32_t which) {
+  if (!s) return fail(AMG_HIP_EINVAL, "null solver");
+  if (level < 0 || level >= (int32_t)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
+  if (which != 0 && which != 1)
+    return fail(AMG_HIP_EINVAL, "amg_hip_center_vec: `which` must be 0 (u) or 1 (f), got " + std::to_string(which));
+  if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no vectors");
+  HIP_TRY(hipSetDevice(s->device));
+  double* v = pick_vec(s, level, which)->as<double>();
+  double* sc = s->scratch.as<double>();
+  const int64_t n = s->lv[level].n;
+  HIP_TRY(launch_sum(n, v, sc + 1034, sc, 0, s->stream));
+  HIP_TRY(launch_center(n, sc + 1034, v, v, s->stream));
+  return AMG_HIP_OK;
 }
 
 // ---- single-precision preconditioner (include/amg_hip.h) ------------------------------------
@@ -7022,6 +7081,14 @@ amg_hip_status amg_hip_block_pcg(amg_hip_solver* s, int32_t k, const double* Bv,
   int32_t on[BLOCK_K_MAX];
   HIP_TRY(launch_block_pitch(n, k, kp, Bv, b, true, st));
   HIP_TRY(launch_block_pitch(n, k, kp, X, x, true, st));
+  // s->project_mean (K-Center, pcg_run's steps per column): b = centre(b) in the panel, every z centred in
+  // the pass that forms r . z, x centred in all columns at the end; a padded column is zero and stays zero
+  const bool project = s->project_mean;
+  double* d_sum = d + 4 * BLOCK_K_MAX;  // past block_sums_to_host's
+  if (project) {
+    HIP_TRY(launch_block_sum(kp, n, b, nullptr, d_sum, part, st));
+    HIP_TRY(launch_block_center(kp, n, d_sum, b, st));
+  }
   if ((rc = block_sums_to_host(s, kp, b, b, h)) != AMG_HIP_OK) return rc;  // b . b
   for (int j = 0; j < kp; ++j) bnorm[j] = std::sqrt(h[j]);
   HIP_TRY(launch_block_csr(CSR_RESID, kp, n, A.rowptr(), A.col(), A.v(), x, b, r, 1.0, st));  // r = b - A x
@@ -7038,8 +7105,14 @@ amg_hip_status amg_hip_block_pcg(amg_hip_solver* s, int32_t k, const double* Bv,
     // z = M^-1 r; p = z; rz = r . z
     HIP_TRY(hipMemsetAsync(z, 0, bytes, st));
     if ((rc = run_block_cycles(s, kp, 1)) != AMG_HIP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(launch_block_sum(kp, n, r, z, d_rz, part, st));
+    if (project) {  // z = centre(z) ahead of p = z
+      HIP_TRY(launch_block_sum(kp, n, z, nullptr, d_sum, part, st));
+      HIP_TRY(launch_block_center_dot(kp, n, d_sum, z, r, d_rz, part, st));
+      HIP_TRY(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, st));
+    } else {
+      HIP_TRY(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(launch_block_sum(kp, n, r, z, d_rz, part, st));
+    }
   }
   while (live > 0) {
     HIP_TRY(launch_block_csr(CSR_SPMV, kp, n, A.rowptr(), A.col(), A.v(), p, nullptr, q, 1.0, st));  // q = A p
@@ -7058,9 +7131,18 @@ amg_hip_status amg_hip_block_pcg(amg_hip_solver* s, int32_t k, const double* Bv,
     HIP_TRY(hipMemcpy(act, on, sizeof(int32_t) * (size_t)kp, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(z, 0, bytes, st));
     if ((rc = run_block_cycles(s, kp, 1)) != AMG_HIP_OK) return rc;  // z = M^-1 r
-    HIP_TRY(launch_block_sum(kp, n, r, z, d_rzn, part, st));
+    if (project) {
+      HIP_TRY(launch_block_sum(kp, n, z, nullptr, d_sum, part, st));
+      HIP_TRY(launch_block_center_dot(kp, n, d_sum, z, r, d_rzn, part, st));
+    } else {
+      HIP_TRY(launch_block_sum(kp, n, r, z, d_rzn, part, st));
+    }
     HIP_TRY(launch_block_pcg_update_p(kp, n, d_rzn, d_rz, act, p, z, st));  // beta = rz_new / rz
     HIP_TRY(hipMemcpyAsync(d_rz, d_rzn, sizeof(double) * (size_t)kp, hipMemcpyDeviceToDevice, st));
+  }
+  if (project) {
+    HIP_TRY(launch_block_sum(kp, n, x, nullptr, d_sum, part, st));
+    HIP_TRY(launch_block_center(kp, n, d_sum, x, st));
   }
   HIP_TRY(launch_block_pitch(n, k, kp, x, X, false, st));
   HIP_TRY(hipStreamSynchronize(st));

@@ -271,6 +271,9 @@ class Multigrid {
   void display_error_off() { display_error = true; }  // sic: reference multigrid.hpp:361-364
 
   amg_hip_solver* native_handle() { return handle; }
+  // extension: the PCG drivers on this hierarchy project onto the complement of the constants
+  // (amg_hip_set_mean_projection; throws unless the hierarchy was created singular)
+  void set_mean_projection(bool on) { detail::check(amg_hip_set_mean_projection(handle, on ? 1 : 0)); }
   // false when smooth() of a user-defined (or rss-checking) smoother runs on the host
   bool runs_on_device() const { return !custom_smoother; }
 };

@@ -462,8 +462,10 @@ amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, cons
  * 1^T R r = 1^T r, so the dropped equation holds by itself).  The last entry of the coarsest
  * right-hand side is zeroed on the stream just ahead of the solve and reads 0 after a cycle;
  * amg_hip_get_level_matrix still returns the true (singular) coarsest operator.  No mean projection is
- * applied anywhere: a cycle, amg_hip_pcg and the other solvers return a solution up to an additive
- * constant, and the right-hand side has to be consistent (zero mean for a symmetric A).
+ * applied by default: a cycle, amg_hip_pcg and the other solvers return a solution up to an additive
+ * constant, and the right-hand side has to be consistent (zero mean for a symmetric A).  The PCG
+ * drivers project when amg_hip_set_mean_projection(s, 1) is in force; amg_hip_center_vec centres a
+ * level vector for the plain cycles.
  * AMG_HIP_EINVAL before the device is touched, the field named in the message: natural_sides negative
  * or with bits at or above 2 dim; natural_sides != 0 on amg_hip_create, _custom, _rs, _poisson,
  * _poisson_window and _poisson_tensor (its model problem is Dirichlet); singular outside {0, 1};
@@ -825,6 +827,30 @@ amg_hip_status amg_hip_apply(amg_hip_solver* s, const double* v_dev, double* z_d
  * (grid.hpp:88-98): CG runs on it unchanged (r.z and p.Ap are both negative).            */
 amg_hip_status amg_hip_pcg(amg_hip_solver* s, double rtol, int64_t max_iters, int64_t* iters,
                            double* relres);
+/* ---- mean projection for singular solvers (K-Center; DESIGN.md: "Mean projection") --------------
+ * For a symmetric A with the constants as its null space 1^T (b - A x) = 1^T b for every x: with a
+ * right-hand side that is consistent only up to its boundary data the residual cannot fall below
+ * |1^T b| / sqrt(n), the drivers cannot stop and the iterate grows along the constants.  With the
+ * switch on, amg_hip_pcg, amg_hip_pcg_mixed and amg_hip_block_pcg (per column) run on the complement
+ * of the constants (PETSc's MatNullSpace remedy).  centre(v) = v - m, m = S / (double)n with S the
+ * library's two-stage tree sum of v, one divide and one subtract per entry.  The iteration is
+ * amg_hip_pcg's with:  b~ = centre(b) in a work vector, ||b~||_2 in the stopping rule and
+ * r = b~ - A x0;  z = centre(M^-1 r) after every preconditioner call, in the pass that forms r . z
+ * (r is not centred again);  x = centre(x) on every way out, the early ones included.  The caller's b
+ * is the level-0 right-hand side again on return, bit for bit (amg_hip_block_pcg never writes B).
+ * Nothing else changes: amg_hip_apply, amg_hip_apply_f32, the cycles, amg_hip_solve and amg_hip_rss
+ * keep their bits, and with the switch off the drivers issue the launches they always did.
+ * Per solver, default 0; only stores a flag, so it works on host_only solvers too.  AMG_HIP_EINVAL:
+ * a null solver, `on` outside {0, 1}, on = 1 on a solver not created with opts->singular = 1
+ * (`singular` in the message).  on = 0 is accepted on every solver.  Not for a nonsymmetric A, whose
+ * left null vector is not the constants.                                                          */
+amg_hip_status amg_hip_set_mean_projection(amg_hip_solver* s, int32_t on);
+amg_hip_status amg_hip_get_mean_projection(const amg_hip_solver* s, int32_t* on);
+/* v = centre(v) on a level vector (which: 0 = u, 1 = f), enqueued on the solver's stream, on any
+ * device solver whatever the switch says: amg_hip_vcycles and amg_hip_solve do not project, a caller
+ * who iterates with plain cycles centres f once with this.  AMG_HIP_EINVAL: level out of range,
+ * `which` outside {0, 1}, a host_only solver.                                                     */
+amg_hip_status amg_hip_center_vec(amg_hip_solver* s, int32_t level, int32_t which /* 0 = u, 1 = f */);
 
 /* AMG::rss(A_0, u_0, b), common.hpp:17-27 (device tree reduction; agrees with
  * the sequential sum to ~1e-15 relative). */

@@ -14,6 +14,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py mixed [<nx> <ny> <nz> <levels>]             amg_hip_pcg and amg_hip_pcg_mixed (single-precision V-cycle) alternating on a variable-coefficient operator, true Jacobi 2+2 and Chebyshev(2) 1+1
        config_bench.py semi [<nx> <ny> <nz> <eps_x> <eps_y> <eps_z>] PCG to 1e-8 on an axis-scaled diffusion operator: full coarsening + Jacobi, semi-coarsening + Jacobi, full coarsening + alternating lines, semi-coarsening + amg_hip_pcg_mixed (legs alternate)
        config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
+       config_bench.py singular [<nx> <ny> <nz>]                   PCG to 1e-8 on that operator without a Dirichlet side, one solver: mean projection (amg_hip_set_mean_projection) off and on with the consistent b and on with b + 1e-6, legs alternate; the time added per iteration next to an estimate from the tree reduction's rate in the same run
        config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
        config_bench.py periodic-setup [<nx> <ny> <nz>]             set-up seconds of tensor_periodic_dev on that operator with set_periodic_device_setup off (host constructor) and on (device), legs alternate; next to them tensor_dev on the open-box operator of the same grid
        config_bench.py periodic-lines                              PCG to 1e-8 and ms per V-cycle of AMG_HIP_SM_LINE_ALT on diffusion that is strong along a periodic x axis (4096 x 1024, 256^3): open lines (cyclic_lines 0) against cyclic lines (cyclic_lines 1), legs alternate
@@ -621,6 +622,100 @@ def run_natural(dims, reps=3, rtol=1e-8, max_iters=300):
               ", ".join(f"{k} {v[0]} iterations {v[1] * 1e3:.2f} ms" for k, v in best.items()), flush=True)
         for mg in legs.values():
             mg.close()
+
+
+def run_singular(dims, reps=3, rtol=1e-8, max_iters=60):
+    """Mean projection (amg_hip_set_mean_projection) on run_natural's operator without a Dirichlet side: full
+    coarsening, true Jacobi 2+2, all sides natural, singular, set up on the device (tensor_dev).  ONE solver,
+    amg_hip_pcg from x = 0 to `rtol`, three legs alternating in one process, `reps` repeats: the switch off
+    and on with the consistent b (zero mean), and on with b + 1e-6.  Per leg the best run: iterations, wall ms
+    of amg_hip_pcg itself (it synchronises before it returns), ms per iteration, and for the legs with the
+    switch on the ms per iteration added to the off leg of the same run.
+    Held against: two more level-0 vector passes per iteration (the tree sum of z reads 8 n0 bytes, the
+    fused centring stores 8 n0 bytes that launch_dot does not) at the rate of the library's tree reduction
+    in this run, and two more launches at 4.6 us.  The rate: amg_hip_dev_sumsq
+    (launch_sum) over 2 n0 doubles, which moves the 16 n0 bytes of launch_dot(n0) through the same grid,
+    grid-stride order and tree as one stream instead of two; best of 20 after a warm-up, each timed
+    through a device synchronise."""
+    import ctypes
+    import torch
+
+    def solve(mg):
+        it, rel = ctypes.c_int64(0), ctypes.c_double(0)
+        st = amg.lib().amg_hip_pcg(mg._h, rtol, max_iters, ctypes.byref(it), ctypes.byref(rel))
+        assert st == 0, amg.lib().amg_hip_last_error().decode()
+        return it.value, rel.value
+
+    dim = len(dims)
+    every = (1 << (2 * dim)) - 1
+    L = full_levels(dims)
+    tag = " x ".join(str(d) for d in dims)
+    crow, col, val, b = torch_diffusion(dims, shift=0.0, dirichlet=0)
+    b = b - b.mean()
+    b_off = b + 1e-6
+    n0 = b.numel()
+    torch.cuda.synchronize()
+    mg = amg.Multigrid.tensor_dev(crow, col, val, b, dims, L, **TENSOR_KW["jacobi"], natural_sides=every, singular=True)
+    mg.sync()
+    print(f"singular {tag}: {n0} rows, {mg.n_levels} levels, coarsest {mg.get_n_dofs(mg.n_levels - 1)} dofs "
+          f"({mg.coarse_solve_kind().split(' ')[0]}), setup_on_device {mg.setup_on_device}", flush=True)
+    # the rate of the tree reduction over 16 n0 bytes
+    two = torch.rand(2 * n0, device="cuda", dtype=torch.float64)
+    out = torch.zeros(1, device="cuda", dtype=torch.float64)
+    scratch = torch.zeros(1100, device="cuda", dtype=torch.float64)
+    red = []
+    for k in range(23):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st = amg.lib().amg_hip_dev_sumsq(2 * n0, two.data_ptr(), out.data_ptr(), scratch.data_ptr(), None)
+        torch.cuda.synchronize()
+        assert st == 0
+        if k >= 3:
+            red.append(time.perf_counter() - t0)
+    t_red = min(red)
+    rate = 16.0 * n0 / t_red
+    estimate = 16.0 * n0 / rate + 2 * 4.6e-6
+    print(f"singular {tag}: tree reduction over 16 n0 = {16 * n0 / 1e6:.1f} MB: {t_red * 1e3:.4f} ms with its two "
+          f"launches and the synchronise ({rate / 1e9:.0f} GB/s); estimate of the addition per iteration "
+          f"{estimate * 1e3:.4f} ms", flush=True)
+    legs = (("off, b", 0, b), ("on, b", 1, b), ("on, b + 1e-6", 1, b_off))
+    for name, on, rhs in legs:  # first calls: work vectors, captured graph, code objects
+        mg.set_mean_projection(on)
+        mg.copy_vec_dev(0, "f", rhs.data_ptr(), True)
+        mg.zero_vec(0, "u")
+        solve(mg)
+    best = {}
+    for rep_ in range(reps):
+        for name, on, rhs in legs:
+            mg.set_mean_projection(on)
+            mg.copy_vec_dev(0, "f", rhs.data_ptr(), True)
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            it, rel = solve(mg)
+            dt = time.perf_counter() - t0
+            best[name] = min(best.get(name, (it, dt, rel)), (it, dt, rel), key=lambda v: v[1])
+            print(f"singular {tag}, {name} rep {rep_}: {it} iterations, {dt * 1e3:.2f} ms to {rtol:g} "
+                  f"(relres {rel:.2e}, {'reached' if rel <= rtol else 'NOT reached: capped'})", flush=True)
+    per_off = best["off, b"][1] / max(best["off, b"][0], 1)
+    for name, _, _ in legs:
+        it, dt, rel = best[name]
+        per = dt / max(it, 1)
+        line = f"singular {tag}, {name}: best {it} iterations, {dt * 1e3:.2f} ms, {per * 1e3:.4f} ms/iteration"
+        if name != "off, b":
+            add = per - per_off
+            line += (f", added {add * 1e3:+.4f} ms/iteration ({add / estimate:.2f} x the estimate "
+                     f"{estimate * 1e3:.4f} ms)")
+        print(line, flush=True)
+    # what the switch is for: the same b + 1e-6 with the switch off
+    mg.set_mean_projection(0)
+    mg.copy_vec_dev(0, "f", b_off.data_ptr(), True)
+    mg.zero_vec(0, "u")
+    it, rel = solve(mg)
+    x = mg.get_soln(0)
+    print(f"singular {tag}, off, b + 1e-6: {it} iterations, relres {rel:.2e} "
+          f"({'reached' if rel <= rtol else 'NOT reached: capped'}), max|x| {abs(x).max():.2e}", flush=True)
+    mg.close()
 
 
 def torch_periodic_diffusion(dims, periodic, seed=1):
@@ -1364,6 +1459,14 @@ elif len(sys.argv) > 1 and sys.argv[1] == "natural":
     else:
         run_natural((4096, 1024))
         run_natural((256, 256, 256))
+elif len(sys.argv) > 1 and sys.argv[1] == "singular":
+    # profiles/singular_config_bench.txt
+    if len(sys.argv) > 4:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_singular(d if d[2] > 1 else d[:2])
+    else:
+        run_singular((4096, 1024))
+        run_singular((256, 256, 256))
 elif len(sys.argv) > 1 and sys.argv[1] == "periodic":
     # profiles/periodic_config_bench.txt
     if len(sys.argv) > 4:
