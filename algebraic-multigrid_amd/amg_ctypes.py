@@ -125,6 +125,13 @@ _SIGS = {
                                                  C.c_int32, _i64p, C.c_int32, _i32p, C.c_double, C.c_int64,
                                                  C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_get_level_axes": (C.c_int, [C.c_void_p, C.c_int32, _i32p]),
+    "amg_hip_create_tensor_opdep": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
+                                              C.c_int32, _i32p, C.c_int64, C.POINTER(Options),
+                                              C.POINTER(C.c_void_p)]),
+    "amg_hip_set_axis_stencil": (None, [C.c_int32]),
+    "amg_hip_get_axis_weights": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
+    "amg_hip_axis_restrict": (C.c_int, [C.c_int32, _i64p, C.c_int32, _f64p, _f64p, _f64p]),
+    "amg_hip_axis_prolong_add": (C.c_int, [C.c_int32, _i64p, C.c_int32, _f64p, _f64p, _f64p]),
     "amg_hip_get_natural_sides": (C.c_int, [C.c_void_p, _i32p]),
     "amg_hip_create_tensor_periodic": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
                                                  C.c_int32, C.c_int32, _i32p, C.POINTER(Options),
@@ -408,6 +415,12 @@ def slab_plan(lines, rank, world, levels):
 
 def set_patch_tile_flags(on):
     lib().amg_hip_set_patch_tile_flags(int(bool(on)))
+
+
+def set_axis_stencil(on):
+    """A/B switch: False makes solvers created by Multigrid.tensor_opdep from now on run their transfers
+    as CSR SpMV (kind 0) instead of K-AxisRestrict / K-AxisProlong (kind 3); same bits either way."""
+    lib().amg_hip_set_axis_stencil(int(bool(on)))
 
 
 def set_patch_xf(on):
@@ -706,7 +719,8 @@ class Multigrid:
                stencil_transfers=True, layout=None, host_only=False, keep_structural_zeros=False,
                no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
-               window=False, natural_sides=0, singular=False, cyclic_lines=False, _semi=None, _periodic=None):
+               window=False, natural_sides=0, singular=False, cyclic_lines=False, _semi=None, _periodic=None,
+               _opdep=None):
         """AMG::Multigrid on a FULL-coarsening hierarchy of the grid `dims` = (nx, ny) or (nx, ny, nz),
         x fastest (amg_hip_create_tensor): every axis m -> m // 2, tensor-product linear interpolation,
         matrix-free transfer kernels unless stencil_transfers=False.  A is the caller's matrix on
@@ -738,6 +752,12 @@ class Multigrid:
                                                       d3.ctypes.data_as(_i64p), int(per), int(n_levels),
                                                       None if masks is None else _p32(masks), C.byref(o),
                                                       C.byref(h))
+        elif _opdep is not None:  # tensor_opdep
+            masks, _, min_coarse = _opdep
+            st = lib().amg_hip_create_tensor_opdep(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
+                                                   d3.ctypes.data_as(_i64p), int(n_levels),
+                                                   None if masks is None else _p32(masks), int(min_coarse),
+                                                   C.byref(o), C.byref(h))
         elif _semi is not None:  # tensor_semi
             masks, theta, min_coarse = _semi
             st = lib().amg_hip_create_tensor_semi(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
@@ -865,6 +885,31 @@ class Multigrid:
                           _semi=cls._semi_rule(n_levels, axis_masks, theta, min_coarse), **opts)
 
     @classmethod
+    def tensor_opdep(cls, colptr, rowind, val, b, dims, n_levels, axis_masks=None, min_coarse=32, **opts):
+        """AMG::Multigrid on a hierarchy with OPERATOR-DEPENDENT interpolation (amg_hip_create_tensor_opdep):
+        every level coarsens exactly one axis of the grid `dims`, and the 1-D interpolation weights along
+        it come from the rows of the level's matrix, collapsed onto that axis.  axis_masks: n_levels - 1
+        masks of one bit each (1 = x, 2 = y, 4 = z), or None for the automatic rule -- coarsen the axis
+        with the strongest coupling (the lowest on a tie) until n_levels, a level of at most min_coarse
+        rows, or no axis of 2 points (n_levels tells).  For coefficients that jump from cell to cell;
+        options as for Multigrid.tensor."""
+        return cls.tensor(colptr, rowind, val, b, dims, n_levels,
+                          _opdep=cls._semi_rule(n_levels, axis_masks, 1.0, min_coarse), **opts)
+
+    def axis_weights(self, level):
+        """The compact weights of `level` of a tensor_opdep solver (amg_hip_get_axis_weights): an array of
+        shape (n_l - n_{l+1}, 2), row e = (w_lo, w_hi) of the e-th fine point (x fastest) whose coordinate
+        on the level's axis is even."""
+        ok = 0 <= int(level) < self.n_levels - 1  # else the library words the refusal
+        n_h, n_H = (self.get_n_dofs(level), self.get_n_dofs(level + 1)) if ok else (0, 0)
+        W = np.zeros((max(n_h - n_H, 0), 2), np.float64)
+        st = lib().amg_hip_get_axis_weights(self._h, int(level), _p64(W))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return W
+
+    @classmethod
     def tensor_semi_dev(cls, crow, col, val, b, dims, n_levels, axis_masks=None, theta=0.5, min_coarse=32,
                         **opts):
         """Multigrid.tensor_semi for a CSR matrix that sits on the device, with the set-up on the device
@@ -977,7 +1022,8 @@ class Multigrid:
         return m.value
 
     def level_transfer_kind(self, level):
-        """0 = CSR SpMV transfers, 1 = the flat stride-2 kernels, 2 = the tensor-product kernels."""
+        """0 = CSR SpMV transfers, 1 = the flat stride-2 kernels, 2 = the tensor-product kernels,
+        3 = the single-axis kernels with per-point weights of tensor_opdep."""
         k = C.c_int32(-1)
         st = lib().amg_hip_level_transfer_kind(self._h, int(level), C.byref(k))
         if st == EINVAL:
@@ -1578,6 +1624,44 @@ def tensor_prolong_add(dims, u_H, u_h, axes=None, natural_sides=0, periodic_axes
         st = lib().amg_hip_tensor_prolong_add_axes(dim, d3.ctypes.data_as(_i64p), int(axes), _p64(u_H), _p64(u_h))
     else:
         st = lib().amg_hip_tensor_prolong_add(dim, d3.ctypes.data_as(_i64p), _p64(u_H), _p64(u_h))
+    if st == EINVAL:
+        raise ValueError(lib().amg_hip_last_error().decode())
+    _chk(st)
+    return u_h
+
+
+def _axis_sizes(dims, axis):
+    dim, d3 = _dims3(dims)
+    axis = int(axis)
+    n_h = int(d3[0] * d3[1] * d3[2])
+    n_H = n_h // int(d3[axis]) * (int(d3[axis]) // 2) if 0 <= axis < dim else 0
+    return dim, d3, axis, n_h, n_H
+
+
+def axis_restrict(dims, axis, W, r):
+    """f_H = R r for the single-axis transfer of the fine grid `dims` with the compact weights W of
+    Multigrid.axis_weights, 2 (n_h - n_H) doubles (amg_hip_axis_restrict: K-AxisRestrict)."""
+    dim, d3, axis, n_h, n_H = _axis_sizes(dims, axis)
+    W, r = _a64(np.ravel(W)), _a64(r)
+    if n_H and (r.size != n_h or W.size != 2 * (n_h - n_H)):
+        raise ValueError(f"`r` / `W` must have {n_h} / {2 * (n_h - n_H)} entries, got {r.size} / {W.size}")
+    out = np.empty(n_H, np.float64)
+    st = lib().amg_hip_axis_restrict(dim, d3.ctypes.data_as(_i64p), axis, _p64(W), _p64(r), _p64(out))
+    if st == EINVAL:
+        raise ValueError(lib().amg_hip_last_error().decode())
+    _chk(st)
+    return out
+
+
+def axis_prolong_add(dims, axis, W, u_H, u_h):
+    """u_h + P u_H for the same transfer (amg_hip_axis_prolong_add: K-AxisProlong); returns a new array."""
+    dim, d3, axis, n_h, n_H = _axis_sizes(dims, axis)
+    W, u_H = _a64(np.ravel(W)), _a64(u_H)
+    u_h = np.array(u_h, dtype=np.float64, copy=True)
+    if n_H and (u_h.size != n_h or u_H.size != n_H or W.size != 2 * (n_h - n_H)):
+        raise ValueError(f"`u_h` / `u_H` / `W` must have {n_h} / {n_H} / {2 * (n_h - n_H)} entries, got "
+                         f"{u_h.size} / {u_H.size} / {W.size}")
+    st = lib().amg_hip_axis_prolong_add(dim, d3.ctypes.data_as(_i64p), axis, _p64(W), _p64(u_H), _p64(u_h))
     if st == EINVAL:
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)

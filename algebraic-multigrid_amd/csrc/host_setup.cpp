@@ -275,6 +275,87 @@ uint32_t tensor_auto_mask(int dim, const int64_t d[3], const double w[3], double
   return mask;
 }
 
+uint32_t tensor_opdep_auto_mask(int dim, const int64_t d[3], const double w[3]) {
+  int best = -1;
+  for (int a = 0; a < dim; ++a)
+    if (d[a] >= 2 && (best < 0 || w[a] > w[best])) best = a;  // strictly larger: the lowest axis wins a tie
+  return best < 0 ? 0u : 1u << best;
+}
+
+Sparse axis_P_from_weights(int dim, const int64_t d[3], int axis, const double* W) {
+  int64_t c[3];
+  tensor_coarse_dims(dim, d, 1u << axis, c);
+  const int64_t m = d[axis], mH = c[axis];
+  const int64_t stride = axis == 0 ? 1 : (axis == 1 ? d[0] : d[0] * d[1]);  // of the axis, fine and even grids
+  int64_t ev[3] = {d[0], d[1], dim == 3 ? d[2] : 1};
+  ev[axis] = m - mH;
+  Sparse P;  // CSC: outer = coarse column, x fastest
+  P.n_outer = c[0] * c[1] * c[2];
+  P.n_inner = d[0] * d[1] * (dim == 3 ? d[2] : 1);
+  P.ptr.resize((size_t)P.n_outer + 1);
+  P.ptr[0] = 0;
+  P.idx.reserve(3 * (size_t)P.n_outer);
+  P.val.reserve(3 * (size_t)P.n_outer);
+  int64_t col = 0;
+  for (int64_t K = 0; K < c[2]; ++K)
+    for (int64_t J = 0; J < c[1]; ++J)
+      for (int64_t I = 0; I < c[0]; ++I) {
+        const int64_t H[3] = {I, J, K};
+        int64_t f[3] = {I, J, K}, e[3] = {I, J, K};
+        f[axis] = 2 * H[axis];  // fine point 2 J: this column is its high neighbour
+        const int64_t i0 = (f[2] * d[1] + f[1]) * d[0] + f[0];
+        const int64_t e0 = (e[2] * ev[1] + e[1]) * ev[0] + e[0];  // even point q = J
+        P.idx.push_back((int32_t)i0);
+        P.val.push_back(W[2 * e0 + 1]);
+        P.idx.push_back((int32_t)(i0 + stride));
+        P.val.push_back(1.0);
+        if (2 * H[axis] + 2 < m) {  // fine point 2 J + 2: this column is its low neighbour
+          P.idx.push_back((int32_t)(i0 + 2 * stride));
+          P.val.push_back(W[2 * (e0 + stride) + 0]);
+        }
+        P.ptr[(size_t)++col] = (int32_t)P.idx.size();
+      }
+  return P;
+}
+
+std::string axis_opdep_P(const Sparse& M, int dim, const int64_t d[3], int axis, Sparse* P,
+                         std::vector<double>* W) {
+  const int64_t m = d[axis], mH = m / 2;
+  const int64_t stride = axis == 0 ? 1 : (axis == 1 ? d[0] : d[0] * d[1]);
+  const int64_t n = M.n_outer;
+  W->assign((size_t)(2 * (n - (n / m) * mH)), 0.0);
+  int64_t e = 0;  // flat index on the grid of the even points: they come in ascending fine order
+  auto bad = [&](int64_t i, const char* what, double v) {
+    return "row " + std::to_string(i) + ": " + what + " is " + std::to_string(v) +
+           " (the entries of the row, collapsed onto axis " + std::string(1, "xyz"[axis]) + ")";
+  };
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t c = (i / stride) % m;
+    if (c & 1) continue;
+    double sm = 0.0, s0 = 0.0, sp = 0.0;
+    for (int32_t p = M.ptr[i]; p < M.ptr[i + 1]; ++p) {
+      const int64_t dc = (M.idx[p] / stride) % m - c;
+      if (dc == -1) sm += M.val[p];
+      else if (dc == 0) s0 += M.val[p];
+      else if (dc == 1) sp += M.val[p];
+    }
+    if (s0 == 0.0 || !std::isfinite(s0)) return bad(i, "the diagonal sum s_0", s0);
+    if (c >= 2) {
+      const double w = (-sm) / s0;
+      if (!std::isfinite(w)) return bad(i, "the weight w_lo", w);
+      (*W)[(size_t)(2 * e)] = w;
+    }
+    if (c + 1 < m) {
+      const double w = (-sp) / s0;
+      if (!std::isfinite(w)) return bad(i, "the weight w_hi", w);
+      (*W)[(size_t)(2 * e + 1)] = w;
+    }
+    ++e;
+  }
+  *P = axis_P_from_weights(dim, d, axis, W->data());
+  return "";
+}
+
 // ------------------------------------------------------------------ SpGEMM ---
 namespace {
 struct RowBlockOut {

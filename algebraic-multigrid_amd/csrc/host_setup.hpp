@@ -63,6 +63,28 @@ void tensor_axis_strength(const Sparse& rows_as, int dim, const int64_t dims[3],
 // w[a] >= theta * max over the eligible axes of w.  0: no axis is eligible.
 uint32_t tensor_auto_mask(int dim, const int64_t dims[3], const double w[3], double theta);
 
+// Operator-dependent interpolation along ONE axis (amg_hip_create_tensor_opdep).  The pattern and the
+// geometry are tensor_P's for the mask 1 << axis (coarse point J at fine coordinate 2 J + 1 of an axis
+// of length m -> floor(m / 2)); the values come from the rows of the level's matrix, collapsed onto
+// the axis.  rows: CSR(A_l).  For row i with axis coordinate c, the entries are added in ascending
+// column order into s_m, s_0, s_p (from +0.0) by the axis coordinate c - 1, c, c + 1 of their
+// column, whatever its other coordinates; entries at another axis distance are skipped, structural
+// zeros are added.  An odd c is the coarse point (c - 1) / 2 with the entry 1.0.  An even c takes
+// w_lo = (-s_m) / s_0 from coarse c / 2 - 1 (when c >= 2) and w_hi = (-s_p) / s_0 from coarse c / 2
+// (when c + 1 < m); an entry is kept for every neighbour that exists, even when it comes out 0.0.
+// W: the compact weights of the device kernels (K-AxisRestrict / K-AxisProlong), 2 (n_h - n_H)
+// doubles.  The fine points with even c = 2 q form a grid like dims with the axis shortened to
+// m - floor(m / 2); the point with flat index e on it (x fastest) holds W[2 e] = w_lo, W[2 e + 1] =
+// w_hi, 0.0 where the neighbour does not exist.
+// Returns "" or what is wrong (s_0 or a weight that is zero-divided or not finite), naming the row.
+std::string axis_opdep_P(const Sparse& rows, int dim, const int64_t dims[3], int axis, Sparse* P,
+                         std::vector<double>* W);
+// The CSC P (and nothing else) of a compact weight array: what axis_opdep_P builds from its own W.
+Sparse axis_P_from_weights(int dim, const int64_t dims[3], int axis, const double* W);
+// The automatic rule of amg_hip_create_tensor_opdep: the eligible axis (a < dim, dims[a] >= 2) with
+// the largest w[a] of tensor_axis_strength, the lowest axis on a tie; 0: no axis is eligible.
+uint32_t tensor_opdep_auto_mask(int dim, const int64_t dims[3], const double w[3]);
+
 // multigrid.hpp:127-130
 inline int64_t coarse_dofs(int64_t n_h) { return (n_h + 1) / 2 - 1; }
 

@@ -3649,6 +3649,203 @@ hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t ma
   return launch_tensor_prolong_add_t<double>(dim, dims, mask, sides, periodic, uH, uh, st);
 }
 
+// ----------------------------------------- K-AxisRestrict / K-AxisProlong ---
+// One coarsened axis per level, weights from the level's matrix (kernels.hpp: launch_axis_restrict;
+// host_setup.hpp: axis_opdep_P).  Coarse point H of the axis sits at fine coordinate 2 H + 1; column
+// H of P holds w_hi(2 H), 1.0, w_lo(2 H + 2) on the fine coordinates 2 H, 2 H + 1, 2 H + 2 (< m).
+// The weights are arbitrary doubles, so each product rounds (-ffp-contract=off keeps it apart from
+// the addition) and the sums run in the order of csr_stage_kernel on R / P: from +0.0, ascending column.
+struct AxisGrid {
+  uint32_t nx, ny, nz;  // fine
+  uint32_t m, mH, mE;   // the axis: fine length, coarse length floor(m / 2), even points m - mH
+};
+// the 16-byte pair (c[0], c[1]) where the address allows, c[1] only when `two`
+template <bool VEC>
+__device__ __forceinline__ void axis_load2(const double* c, bool two, double& v0, double& v1) {
+  if (VEC && two && (reinterpret_cast<uintptr_t>(c) & 15u) == 0) {
+    const double2 p = *reinterpret_cast<const double2*>(c);
+    v0 = p.x;
+    v1 = p.y;
+  } else {
+    v0 = c[0];
+    v1 = two ? c[1] : 0.0;
+  }
+}
+
+// One lane per coarse point: f_H = ((+0.0 + w_hi(2H) r(2H)) + 1.0 r(2H+1)) + w_lo(2H+2) r(2H+2), the
+// last term when 2H + 2 < m.  Along x the fine points 2I, 2I+1 come as one aligned 16-byte load
+// where the address allows (VEC: r is 16-byte aligned), as in tensor_restrict_kernel; along y / z
+// the three loads of a wave are contiguous lines.  The two weights are the second half of W's pair
+// e and the first half of pair e + stride.  uH (may be null) is zeroed in the same pass.
+template <int AXIS, bool VEC>
+__global__ __launch_bounds__(256) void axis_restrict_kernel(
+    AxisGrid g, const double* __restrict__ W, const double* __restrict__ r, double* __restrict__ fH,
+    double* __restrict__ uH) {
+  const uint32_t cx = AXIS == 0 ? g.mH : g.nx, cy = AXIS == 1 ? g.mH : g.ny, cz = AXIS == 2 ? g.mH : g.nz;
+  const uint32_t nH = cx * cy * cz;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= nH) return;
+  const uint32_t I = t % cx, q = t / cx, J = q % cy, K = q / cy;
+  if (uH) uH[t] = 0.0;
+  const uint32_t H = AXIS == 0 ? I : (AXIS == 1 ? J : K);
+  const bool third = 2u * H + 2u < g.m;
+  int64_t a, e, sd;  // fine index of coordinate 2 H, index of that even point, stride of the axis in both
+  if (AXIS == 0) {
+    a = ((int64_t)K * g.ny + J) * g.nx + 2u * I;
+    e = ((int64_t)K * g.ny + J) * g.mE + I;
+    sd = 1;
+  } else if (AXIS == 1) {
+    a = ((int64_t)K * g.ny + 2u * J) * g.nx + I;
+    e = ((int64_t)K * g.mE + J) * g.nx + I;
+    sd = g.nx;
+  } else {
+    a = ((int64_t)2u * K * g.ny + J) * g.nx + I;
+    e = ((int64_t)K * g.ny + J) * g.nx + I;
+    sd = (int64_t)g.nx * g.ny;
+  }
+  const double whi = W[2 * e + 1];
+  const double wlo = third ? W[2 * (e + sd)] : 0.0;
+  double v0, v1, v2 = 0.0;
+  if (AXIS == 0 && VEC && (a & 1) == 0) {
+    const double2 p = *reinterpret_cast<const double2*>(r + a);
+    v0 = p.x;
+    v1 = p.y;
+    if (third) v2 = r[a + 2];
+  } else if (AXIS == 0 && VEC && third) {
+    v0 = r[a];
+    const double2 p = *reinterpret_cast<const double2*>(r + a + 1);
+    v1 = p.x;
+    v2 = p.y;
+  } else {
+    v0 = r[a];
+    v1 = r[a + sd];
+    if (third) v2 = r[a + 2 * sd];
+  }
+  double s = 0.0;
+  s += whi * v0;
+  s += 1.0 * v1;
+  if (third) s += wlo * v2;
+  fH[t] = s;
+}
+
+// One lane per fine pair (2p, 2p+1) of a fine grid line: u_h += t with t summed from +0.0 over the
+// coarse neighbours in ascending order; 16-byte read-modify-write of u_h where the address allows
+// (VEC: u_h, u_H and W are 16-byte aligned).  An odd axis coordinate c has the one coarse neighbour
+// (c - 1) / 2 with weight 1.0; an even one c / 2 - 1 with w_lo (c >= 2) and c / 2 with w_hi
+// (c + 1 < m), one 16-byte load of W per fine point.  Along x the lane's even point is 2p and its
+// odd one 2p + 1; along y / z both points of the pair have the lane's c and read coarse pairs.
+template <int AXIS, bool VEC>
+__global__ __launch_bounds__(256) void axis_prolong_add_kernel(
+    AxisGrid g, const double2* __restrict__ W, const double* __restrict__ uH, double* uh) {
+  const uint32_t px = (g.nx + 1u) / 2u;  // pairs per fine line
+  const uint32_t total = px * g.ny * g.nz;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= total) return;
+  const uint32_t p = t % px, row = t / px, j = row % g.ny, k = row / g.ny;
+  const bool two = 2u * p + 1u < g.nx;  // the lane's pair is whole
+  double t0 = 0.0, t1 = 0.0;
+  if (AXIS == 0) {  // mE == px: the even point of the pair is point p of the line's even points
+    const double2 w = W[(int64_t)row * g.mE + p];
+    const double* c = uH + (int64_t)row * g.mH;
+    if (p >= 1u) t0 += w.x * c[p - 1u];
+    if (two) {  // coarse p exists iff fine 2p + 1 does
+      const double mid = c[p];
+      t0 += w.y * mid;
+      t1 += 1.0 * mid;
+    }
+  } else {
+    const uint32_t cc = AXIS == 1 ? j : k;
+    // coarse / even-grid index of the lane's x = 2p on the line with axis coordinate h
+    auto base = [&](uint32_t len, uint32_t h) -> int64_t {
+      return (AXIS == 1 ? ((int64_t)k * len + h) : ((int64_t)h * g.ny + j)) * g.nx + 2u * p;
+    };
+    double m0, m1;
+    if (cc & 1u) {
+      axis_load2<VEC>(uH + base(g.mH, (cc - 1u) / 2u), two, m0, m1);
+      t0 += 1.0 * m0;
+      if (two) t1 += 1.0 * m1;
+    } else {
+      const uint32_t h = cc / 2u;
+      const int64_t e = base(g.mE, h);
+      const double2 w0 = W[e];
+      const double2 w1 = two ? W[e + 1] : make_double2(0.0, 0.0);
+      if (cc >= 2u) {
+        axis_load2<VEC>(uH + base(g.mH, h - 1u), two, m0, m1);
+        t0 += w0.x * m0;
+        if (two) t1 += w1.x * m1;
+      }
+      if (cc + 1u < g.m) {
+        axis_load2<VEC>(uH + base(g.mH, h), two, m0, m1);
+        t0 += w0.y * m0;
+        if (two) t1 += w1.y * m1;
+      }
+    }
+  }
+  const int64_t i = (int64_t)row * g.nx + 2u * p;
+  if (two) {
+    if (VEC && (i & 1) == 0) {
+      double2 u = *reinterpret_cast<const double2*>(uh + i);
+      u.x = u.x + t0;
+      u.y = u.y + t1;
+      *reinterpret_cast<double2*>(uh + i) = u;
+    } else {
+      uh[i] = uh[i] + t0;
+      uh[i + 1] = uh[i + 1] + t1;
+    }
+  } else {
+    uh[i] = uh[i] + t0;
+  }
+}
+
+static bool axis_grid(int dim, const int64_t dims[3], int axis, AxisGrid* g) {
+  if ((dim != 2 && dim != 3) || !dims || axis < 0 || axis >= dim) return false;
+  const int64_t nx = dims[0], ny = dims[1], nz = dim == 3 ? dims[2] : 1;
+  if (nx < 1 || ny < 1 || nz < 1 || (dim == 2 && dims[2] != 1) || dims[axis] < 2) return false;
+  if (nx >= ((int64_t)1 << 31) / ny / nz - 2) return false;  // 32-bit lane indices
+  g->nx = (uint32_t)nx;
+  g->ny = (uint32_t)ny;
+  g->nz = (uint32_t)nz;
+  g->m = (uint32_t)dims[axis];
+  g->mH = g->m / 2u;
+  g->mE = g->m - g->mH;
+  return true;
+}
+hipError_t launch_axis_restrict(int dim, const int64_t dims[3], int axis, const double* W, const double* r,
+                                double* fH, double* uH_zero, hipStream_t st) {
+  AxisGrid g;
+  if (!axis_grid(dim, dims, axis, &g) || !pair_aligned(W)) return hipErrorInvalidValue;
+  const uint32_t nH = g.nx * g.ny * g.nz / g.m * g.mH;
+  const dim3 grid((nH + 255u) / 256u), block(256);
+  if (axis == 0) {
+    if (pair_aligned(r))
+      hipLaunchKernelGGL((axis_restrict_kernel<0, true>), grid, block, 0, st, g, W, r, fH, uH_zero);
+    else
+      hipLaunchKernelGGL((axis_restrict_kernel<0, false>), grid, block, 0, st, g, W, r, fH, uH_zero);
+  } else if (axis == 1) {
+    hipLaunchKernelGGL((axis_restrict_kernel<1, false>), grid, block, 0, st, g, W, r, fH, uH_zero);
+  } else {
+    hipLaunchKernelGGL((axis_restrict_kernel<2, false>), grid, block, 0, st, g, W, r, fH, uH_zero);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_axis_prolong_add(int dim, const int64_t dims[3], int axis, const double* W, const double* uH,
+                                   double* uh, hipStream_t st) {
+  AxisGrid g;
+  if (!axis_grid(dim, dims, axis, &g) || !pair_aligned(W)) return hipErrorInvalidValue;
+  const uint32_t total = ((g.nx + 1u) / 2u) * g.ny * g.nz;
+  const dim3 grid((total + 255u) / 256u), block(256);
+  const double2* W2 = reinterpret_cast<const double2*>(W);
+  const bool vec = pair_aligned(uh) && pair_aligned(uH);
+#define AMG_AXIS_PROLONG(AX)                                                                              \
+  if (vec) hipLaunchKernelGGL((axis_prolong_add_kernel<AX, true>), grid, block, 0, st, g, W2, uH, uh);   \
+  else hipLaunchKernelGGL((axis_prolong_add_kernel<AX, false>), grid, block, 0, st, g, W2, uH, uh)
+  if (axis == 0) { AMG_AXIS_PROLONG(0); }
+  else if (axis == 1) { AMG_AXIS_PROLONG(1); }
+  else { AMG_AXIS_PROLONG(2); }
+#undef AMG_AXIS_PROLONG
+  return hipGetLastError();
+}
+
 // First Jacobi sweep from a zero guess (coarse levels on the way down,
 // multigrid.hpp:278 then :268): with u == 0 every a_ij*u_j is +-0 and the row sum
 // is +0.0, so the sweep needs only f and the diagonal -- same operations, same

@@ -402,6 +402,20 @@ hipError_t launch_tensor_restrict(int dim, const int64_t dims[3], uint32_t mask,
 // u_h = u_h + P u_H
 hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t mask, uint32_t sides, uint32_t periodic,
                                      const double* uH, double* uh, hipStream_t st);
+// K-AxisRestrict / K-AxisProlong: the transfers of a level that coarsens ONE axis with weights taken
+// from its matrix (host_setup.hpp: axis_opdep_P), matrix-free.  dims = fine grid as above; axis: 0 = x,
+// 1 = y, 2 = z (< dim, dims[axis] >= 2, else hipErrorInvalidValue).  W: the compact weights, 16-byte
+// aligned -- the fine points with an even axis coordinate 2 q form a grid like dims with the axis
+// shortened to m - floor(m / 2); point e of it (x fastest) has W[2 e] = w_lo (coarse q - 1) and
+// W[2 e + 1] = w_hi (coarse q), 0.0 where the neighbour does not exist.  The weights are no powers
+// of two: every product is rounded, then added in the order of the CSR SpMV with R / P (from +0.0,
+// ascending column), so the bits are those of launch_csr(CSR_SPMV / CSR_SPMV_ADD) on R / P.
+// f_H = R r, uH_zero (may be null) zero-filled in the same pass
+hipError_t launch_axis_restrict(int dim, const int64_t dims[3], int axis, const double* W, const double* r,
+                                double* fH, double* uH_zero, hipStream_t st);
+// u_h = u_h + P u_H
+hipError_t launch_axis_prolong_add(int dim, const int64_t dims[3], int axis, const double* W, const double* uH,
+                                   double* uh, hipStream_t st);
 // x[j * stride] = +0.0 for j < count (count <= 64, else hipErrorInvalidValue)
 hipError_t launch_zero_strided(double* x, int64_t stride, int count, hipStream_t st);
 hipError_t launch_add_inplace(int64_t n, const double* x, double* y, hipStream_t st);

@@ -311,6 +311,7 @@ hipError_t device_galerkin_generic(const DevCsr& A, const DevCsr& P, const DevCs
 }
 
 int g_patch_tile_flags = 1;  // amg_hip_set_patch_tile_flags: A/B switch (same bits either way)
+int g_axis_stencil = 1;      // amg_hip_set_axis_stencil: A/B switch, read when a solver is created (same bits either way)
 int g_patch_xf = 1;          // amg_hip_set_patch_xf: A/B switch (same bits either way)
 int g_patch_tall = 1;        // amg_hip_set_patch_tall: A/B switch (same bits either way)
 int g_patch_seam = 1;        // amg_hip_set_patch_seam: A/B switch (same bits either way)
@@ -1448,6 +1449,14 @@ struct Level {
   uint32_t tsides = 0;  // the solver's natural boundary sides (opt.natural_sides), the same on every level
   uint32_t tper = 0;    // the solver's periodic axes (amg_hip_create_tensor_periodic), the same on every level
   DevCsr P_rows, R_rows;   // CSR(P), CSR(R)
+  // amg_hip_create_tensor_opdep: the one axis the level coarsens (-1: another kind of level), the
+  // compact weights of its P (host_setup.hpp: axis_opdep_P) on the host and, where the transfers run
+  // matrix-free (axis_stencil: K-AxisRestrict / K-AxisProlong, transfer kind 3), on the device.
+  // P_csc / R_csc stay on the host; CSR(P), CSR(R) reach the device when a float or block cycle asks.
+  int axis = -1;
+  bool axis_stencil = false;
+  std::vector<double> axis_W;
+  DevMem axis_W_dev;
   // exact lexicographic schedules
   std::unique_ptr<LexOnDev> lex_fwd, lex_bwd;
   int scan_C = 0, scan_ring = 0;  // > 0: the lexicographic sweeps run as K-GS-scan
@@ -2446,6 +2455,10 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
         HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(),
                                        zero_known ? nullptr : C.u.as<double>(), st));
         s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
+      } else if (L.axis_stencil) {                                 // the same two steps, one axis, weights of A_l
+        HIP_TRY(launch_axis_restrict(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), L.r.as<double>(),
+                                     C.f.as<double>(), zero_known ? nullptr : C.u.as<double>(), st));
+        s->acct(8.0 * L.n + 16.0 * (L.n - C.n) + (zero_known ? 8.0 : 16.0) * C.n);
       } else {
         if (!zero_known) HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st)); // :278
         const DevCsr& R = L.R_rows;
@@ -2552,6 +2565,10 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
     } else if (L.tensor_stencil) {
       HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
       s->acct(8.0 * C.n + 16.0 * L.n);
+    } else if (L.axis_stencil) {
+      HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), C.u.as<double>(),
+                                      L.u.as<double>(), st));
+      s->acct(16.0 * L.n + 16.0 * (L.n - C.n) + 8.0 * C.n);
     } else {
       const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
       HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz,
@@ -2681,6 +2698,11 @@ void compute_bytes(amg_hip_solver* s) {
         total += 16 * nh + 8 * nH;
         continue;
       }
+      if (L.axis_stencil) {                                // K-AxisRestrict / K-AxisProlong: plus the weights
+        total += 8 * nh + 16 * (nh - nH) + 8 * nH;
+        total += 16 * nh + 16 * (nh - nH) + 8 * nH;
+        continue;
+      }
       double pnnz = 3.0;  // entries per column of P
       if (L.tensor) pnnz = ((L.tmask & 1u) ? 3.0 : 1.0) * ((L.tmask & 2u) ? 3.0 : 1.0) * ((L.tmask & 4u) ? 3.0 : 1.0);
       total += 12.0 * pnnz * nH + 4 * nH + 8 * nh + 8 * nH;   // restrict (CSR R)
@@ -2699,6 +2721,9 @@ struct SemiRule {
   const int32_t* masks = nullptr;
   double theta = 0.5;
   int64_t min_coarse = 1;
+  // amg_hip_create_tensor_opdep: one axis per level (the automatic rule is tensor_opdep_auto_mask,
+  // theta is not used) and the weights of axis_opdep_P instead of tensor_P's
+  bool opdep = false;
 };
 // a one-level solver's coarsest right-hand side is the caller's b, which the pinned solve must not alter
 const char* const SINGULAR_ONE_LEVEL =
@@ -2825,12 +2850,16 @@ std::string level_mask_error(int l, int dim, const int64_t d[3], int64_t mask, b
 // The levels of a hierarchy whose masks are known up front (masks null: full coarsening), walked
 // before any device call: "" or what the first level that cannot coarsen says, in the level loops'
 // words.  `who` goes in front of what only a front end can name: a mask, a periodic axis.
+// one_axis (amg_hip_create_tensor_opdep): every mask names exactly one axis
 std::string level_walk_error(const std::string& who, int dim, const int64_t* dims, int32_t n_levels,
-                             const int32_t* masks, uint32_t periodic) {
+                             const int32_t* masks, uint32_t periodic, bool one_axis = false) {
   int64_t d[3] = {dims[0], dims[1], dims[2]};
   for (int l = 0; l + 1 < n_levels; ++l) {
     const uint32_t mask = masks ? (uint32_t)masks[l] : tensor_full_mask(dim);
     std::string e = level_mask_error(l, dim, d, masks ? (int64_t)masks[l] : (int64_t)mask, masks != nullptr);
+    if (e.empty() && one_axis && masks && (mask & (mask - 1u)))
+      e = "level " + std::to_string(l) + ": axis mask " + std::to_string(masks[l]) +
+          " names several axes; a level of this hierarchy coarsens exactly one (1, 2 or 4)";
     if (!e.empty()) return masks ? who + e : e;
     e = periodic_level_error(l, dim, d, mask, periodic);
     if (!e.empty()) return who + e;
@@ -2905,7 +2934,7 @@ amg_hip_status level_axis_mask(const Level& L, int l, int dim, const SemiRule* s
     if (!*last) {
       double w[3];
       AMG_TRY(strengths(w));
-      *mask = tensor_auto_mask(dim, L.dims, w, semi->theta);
+      *mask = semi->opdep ? tensor_opdep_auto_mask(dim, L.dims, w) : tensor_auto_mask(dim, L.dims, w, semi->theta);
       *last = *mask == 0;
     }
     if (*last) *mask = 0;
@@ -3218,7 +3247,15 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
       L.n_coarse = n_H;
       // the matrix-free kernels index lanes with 32 bits (kernels.hip: tensor_grid)
       L.tensor_stencil = s->opt.stencil_transfers && L.n < ((int64_t)1 << 31) - 4;
-      if (!L.tensor_stencil) {
+      if (h.semi && h.semi->opdep) {  // one axis, the weights of this level's rows; kind 3 or 0
+        L.axis_stencil = L.tensor_stencil && g_axis_stencil;
+        L.tensor_stencil = false;
+        for (L.axis = 0; !((L.tmask >> L.axis) & 1u); ++L.axis) {}
+        const std::string we = axis_opdep_P(A_r, h.dim, L.dims, L.axis, &L.P_csc, &L.axis_W);
+        if (!we.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor_opdep: level " + std::to_string(l) + ": " + we);
+        L.R_csc = transpose(L.P_csc);
+        if (dev && L.axis_stencil) HIP_TRY(upload(L.axis_W_dev, L.axis_W.data(), L.axis_W.size()));
+      } else if (!L.tensor_stencil) {
         L.P_csc = tensor_P(h.dim, L.dims, L.tmask, L.tsides, L.tper);
         L.R_csc = transpose(L.P_csc);
       }
@@ -3248,7 +3285,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
     // the matrix-free kernels need no device copy of the linear operators, and the
     // device Galerkin product no host copy
     const bool dev_galerkin = dev && L.linear && !s->opt.host_galerkin;
-    const bool dev_rows = dev && !(L.linear && s->opt.stencil_transfers) && !L.tensor_stencil;
+    const bool dev_rows = dev && !(L.linear && s->opt.stencil_transfers) && !L.tensor_stencil && !L.axis_stencil;
     Sparse P_r, R_r;
     if (dev_rows || !dev_galerkin) {
       P_r = transpose(L.P());  // CSR(P)
@@ -3945,6 +3982,15 @@ bool has_exact_zero(const Sparse& M) {
 }
 double csr_bytes(const DevCsr& M) { return 12.0 * (double)M.nnz + 4.0 * (double)(M.n_rows + 1); }
 
+// CSR(P), CSR(R) of a level whose transfers run as K-AxisRestrict / K-AxisProlong: the float and the
+// block cycles take their CSR kernels on such a level
+amg_hip_status ensure_axis_rows(Level& L) {
+  if (!L.axis_stencil || L.P_rows.n_rows != 0) return AMG_HIP_OK;
+  HIP_TRY(upload_csr(transpose(L.P_csc), &L.P_rows));
+  HIP_TRY(upload_csr(transpose(L.R_csc), &L.R_rows));
+  return AMG_HIP_OK;
+}
+
 // the CSR copies (once) and the panels for pitch kp (again only when kp grows)
 amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
   Block& B = s->blk;
@@ -3963,6 +4009,7 @@ amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
         L.P_csc = Sparse();
         L.R_csc = Sparse();
       }
+      AMG_TRY(ensure_axis_rows(L));
       if (l + 1 == nl && l > 0) continue;  // the coarsest level only takes the direct solve
       // the entry set of the device matrices: exact zeros dropped unless keep_structural_zeros,
       // ascending column order (A_rows is plain CSR already when its layout is)
@@ -4315,6 +4362,7 @@ amg_hip_status ensure_f32(amg_hip_solver* s) {
   amg_hip_status r;
   std::vector<F32Level> lv((size_t)nl);
   for (int l = 0; l < nl; ++l) {
+    AMG_TRY(ensure_axis_rows(s->lv[l]));  // kind 3: the float transfers are the CSR kernels
     const Level& L = s->lv[l];
     F32Level& Q = lv[(size_t)l];
     const size_t bytes = sizeof(float) * (size_t)L.n;
@@ -4613,6 +4661,7 @@ void amg_hip_set_row_types(int32_t on) { g_row_types = on ? 1 : 0; }
 void amg_hip_set_dict_rows(int32_t rows_per_lane) { set_dict_rows_per_lane(rows_per_lane); }
 void amg_hip_set_dict_stencil(int32_t on) { set_dict_stencil(on); }
 void amg_hip_set_patch_tile_flags(int32_t on) { g_patch_tile_flags = on ? 1 : 0; }
+void amg_hip_set_axis_stencil(int32_t on) { g_axis_stencil = on ? 1 : 0; }
 void amg_hip_set_patch_xf(int32_t on) { g_patch_xf = on ? 1 : 0; }
 void amg_hip_set_patch_tall(int32_t on) { g_patch_tall = on ? 1 : 0; }
 void amg_hip_set_patch_seam(int32_t on) { g_patch_seam = on ? 1 : 0; }
@@ -4727,7 +4776,7 @@ static amg_hip_status semi_args(const std::string& who, int32_t dim, const int64
                                 const SemiRule& rule) {
   if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
   if (rule.masks) {
-    const std::string e = level_walk_error(who, dim, dims, n_levels, rule.masks, 0);
+    const std::string e = level_walk_error(who, dim, dims, n_levels, rule.masks, 0, rule.opdep);
     return e.empty() ? AMG_HIP_OK : fail(AMG_HIP_EINVAL, e);
   }
   if (!(rule.theta > 0.0 && rule.theta <= 1.0)) return fail(AMG_HIP_EINVAL, who + "`theta` must be in (0, 1]");
@@ -4746,6 +4795,33 @@ amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, cons
   const SemiRule rule{axis_masks, theta, min_coarse};
   AMG_TRY(semi_args(who, dim, dims, n_levels, rule));
   return build_solver(n, colptr, rowind, val, b, n_levels, &o, out, tensor_spec(dim, dims, &rule));
+}
+
+// Operator-dependent interpolation, one axis per level (host_setup.hpp: axis_opdep_P).  The checks are
+// amg_hip_create_tensor_semi's; on top of them every explicit mask names exactly one axis.
+amg_hip_status amg_hip_create_tensor_opdep(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                           const double* val, const double* b, int32_t dim, const int64_t* dims,
+                                           int32_t n_levels, const int32_t* axis_masks, int64_t min_coarse,
+                                           const amg_hip_options* opts, amg_hip_solver** out) {
+  static const std::string who = "amg_hip_create_tensor_opdep: ";
+  amg_hip_options o;
+  AMG_TRY(out_and_options(opts, out, &o));
+  AMG_TRY(tensor_grid_args(who, n, dim, dims, o.window, "single-axis"));
+  SemiRule rule{axis_masks, 1.0, min_coarse};  // theta: not used; min_coarse: checked and used without masks only
+  rule.opdep = true;
+  AMG_TRY(semi_args(who, dim, dims, n_levels, rule));
+  return build_solver(n, colptr, rowind, val, b, n_levels, &o, out, tensor_spec(dim, dims, &rule));
+}
+
+amg_hip_status amg_hip_get_axis_weights(const amg_hip_solver* s, int32_t level, double* W) {
+  if (!s || !W) return fail(AMG_HIP_EINVAL, "null argument");
+  if (level < 0 || level + 1 >= (int)s->lv.size())
+    return fail(AMG_HIP_EINVAL, "level out of range (the coarsest level has no transfers)");
+  const Level& L = s->lv[level];
+  if (L.axis < 0)
+    return fail(AMG_HIP_EINVAL, "amg_hip_get_axis_weights: the solver was not made by amg_hip_create_tensor_opdep");
+  std::memcpy(W, L.axis_W.data(), sizeof(double) * L.axis_W.size());
+  return AMG_HIP_OK;
 }
 
 amg_hip_status amg_hip_get_natural_sides(const amg_hip_solver* s, int32_t* mask) {
@@ -4827,7 +4903,7 @@ amg_hip_status amg_hip_level_transfer_kind(const amg_hip_solver* s, int32_t leve
   if (level < 0 || level + 1 >= (int)s->lv.size())
     return fail(AMG_HIP_EINVAL, "level out of range (the coarsest level has no transfers)");
   const Level& L = s->lv[level];
-  *kind = L.tensor_stencil ? 2 : ((L.linear && s->opt.stencil_transfers) ? 1 : 0);
+  *kind = L.axis_stencil ? 3 : (L.tensor_stencil ? 2 : ((L.linear && s->opt.stencil_transfers) ? 1 : 0));
   return AMG_HIP_OK;
 }
 
@@ -5365,6 +5441,9 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
         HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
       } else if (L.tensor_stencil) {
         HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
+      } else if (L.axis_stencil) {
+        HIP_TRY(launch_axis_restrict(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), L.r.as<double>(),
+                                     C.f.as<double>(), C.u.as<double>(), st));
       } else {
         HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st));
         const DevCsr& R = L.R_rows;
@@ -5380,6 +5459,9 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
         HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
       } else if (L.tensor_stencil) {
         HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
+      } else if (L.axis_stencil) {
+        HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), C.u.as<double>(),
+                                        L.u.as<double>(), st));
       } else {
         const DevCsr& P = L.P_rows;
         HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz, P.rowptr(),
@@ -6293,6 +6375,50 @@ static amg_hip_status tensor_prolong_add_host(const char* who, int32_t dim, cons
   HIP_TRY(hipMemcpy(u_h, dh.p, sizeof(double) * n_h, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
 }
+// the fine grid, the axis and the sizes of a stand-alone K-AxisRestrict / K-AxisProlong call
+static amg_hip_status axis_transfer_args(const char* who, int32_t dim, const int64_t* dims, int32_t axis, int64_t* n_h,
+                                         int64_t* n_H) {
+  std::string e = tensor_dims_error(dim, dims);
+  if (e.empty() && (axis < 0 || axis >= dim)) e = "`axis` must be in [0, " + std::to_string(dim) + "), got " + std::to_string(axis);
+  if (e.empty()) e = semi_mask_error(0, dim, dims, (int64_t)1 << axis);
+  if (!e.empty()) return fail(AMG_HIP_EINVAL, std::string(who) + ": " + e);
+  *n_h = dims[0] * dims[1] * dims[2];
+  *n_H = *n_h / dims[axis] * (dims[axis] / 2);
+  return AMG_HIP_OK;
+}
+amg_hip_status amg_hip_axis_restrict(int32_t dim, const int64_t* dims, int32_t axis, const double* W, const double* r,
+                                     double* f_H) {
+  int64_t n_h = 0, n_H = 0;
+  amg_hip_status st = axis_transfer_args("amg_hip_axis_restrict", dim, dims, axis, &n_h, &n_H);
+  if (st != AMG_HIP_OK) return st;
+  if (!W || !r || !f_H) return fail(AMG_HIP_EINVAL, "bad argument");
+  if ((st = need_device()) != AMG_HIP_OK) return st;
+  DevMem dw, dr, df;
+  HIP_TRY(upload(dw, W, (size_t)(2 * (n_h - n_H))));
+  HIP_TRY(upload(dr, r, (size_t)n_h));
+  HIP_TRY(df.alloc(sizeof(double) * n_H));
+  HIP_TRY(launch_axis_restrict(dim, dims, axis, dw.as<double>(), dr.as<double>(), df.as<double>(), nullptr, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(f_H, df.p, sizeof(double) * n_H, hipMemcpyDeviceToHost));
+  return AMG_HIP_OK;
+}
+amg_hip_status amg_hip_axis_prolong_add(int32_t dim, const int64_t* dims, int32_t axis, const double* W,
+                                        const double* u_H, double* u_h) {
+  int64_t n_h = 0, n_H = 0;
+  amg_hip_status st = axis_transfer_args("amg_hip_axis_prolong_add", dim, dims, axis, &n_h, &n_H);
+  if (st != AMG_HIP_OK) return st;
+  if (!W || !u_H || !u_h) return fail(AMG_HIP_EINVAL, "bad argument");
+  if ((st = need_device()) != AMG_HIP_OK) return st;
+  DevMem dw, dH, dh;
+  HIP_TRY(upload(dw, W, (size_t)(2 * (n_h - n_H))));
+  HIP_TRY(upload(dH, u_H, (size_t)n_H));
+  HIP_TRY(upload(dh, u_h, (size_t)n_h));
+  HIP_TRY(launch_axis_prolong_add(dim, dims, axis, dw.as<double>(), dH.as<double>(), dh.as<double>(), nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(u_h, dh.p, sizeof(double) * n_h, hipMemcpyDeviceToHost));
+  return AMG_HIP_OK;
+}
+
 amg_hip_status amg_hip_tensor_prolong_add(int32_t dim, const int64_t* dims_h, const double* u_H,
                                           double* u_h) {
   return tensor_prolong_add_host("amg_hip_tensor_prolong_add", dim, dims_h, -1, 0, u_H, u_h);

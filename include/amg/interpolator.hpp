@@ -200,4 +200,29 @@ class SemiTensorInterpolator : public TensorInterpolator<EleType> {
   }
 };
 
+// Operator-dependent interpolation on the same grids (amg_hip_create_tensor_opdep; NO reference
+// counterpart): every level coarsens exactly ONE axis (masks of one bit: 1 = x, 2 = y, 4 = z), and the
+// 1-D weights along it come from the rows of the level's own matrix, collapsed onto that axis.
+// `masks` empty: the library's automatic rule -- the axis with the strongest pure-axis coupling, the
+// lowest on a tie, until n_levels, a level of at most min_coarse rows or a grid without an axis of 2
+// points (Multigrid::get_n_levels tells).  AMG::Multigrid lets the library build the hierarchy;
+// get_P / get_R hold the operators afterwards.  For coefficients that jump by orders of magnitude
+// from cell to cell, where fixed weights leave the smooth error to the Krylov method.
+template <class EleType>
+class OpdepTensorInterpolator : public TensorInterpolator<EleType> {
+  std::vector<int32_t> masks_;
+  size_t min_coarse_;
+
+ public:
+  OpdepTensorInterpolator(size_t nx, size_t ny, size_t nz = 1, std::vector<int32_t> masks = {},
+                          size_t min_coarse = 32)
+      : TensorInterpolator<EleType>(nx, ny, nz), masks_(std::move(masks)), min_coarse_(min_coarse) {}
+  const std::vector<int32_t>& masks() const { return masks_; }
+  size_t min_coarse() const { return min_coarse_; }
+  void make_operators(size_t, size_t, size_t) override {
+    throw std::logic_error("OpdepTensorInterpolator: the weights depend on the level matrix; "
+                           "AMG::Multigrid builds the operators");
+  }
+};
+
 }  // namespace AMG

@@ -153,6 +153,15 @@ class Multigrid {
               A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(), b.data(), tp->dim(), dims,
               (int32_t)n_levels, semi->masks().empty() ? nullptr : semi->masks().data(), semi->theta(),
               (int64_t)semi->min_coarse(), &opt, &handle));
+        } else if (auto* opdep = dynamic_cast<OpdepTensorInterpolator<EleType>*>(interpolator)) {
+          // operator-dependent weights, one axis per level: explicit masks, or the automatic rule
+          if (!opdep->masks().empty() && opdep->masks().size() + 1 != n_levels)
+            throw std::invalid_argument("OpdepTensorInterpolator: " + std::to_string(opdep->masks().size()) +
+                                        " axis masks for " + std::to_string(n_levels) + " levels");
+          detail::check(amg_hip_create_tensor_opdep(
+              A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(), b.data(), tp->dim(), dims,
+              (int32_t)n_levels, opdep->masks().empty() ? nullptr : opdep->masks().data(),
+              (int64_t)opdep->min_coarse(), &opt, &handle));
         } else {
           detail::check(amg_hip_create_tensor(A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(),
                                               b.data(), tp->dim(), dims, (int32_t)n_levels, &opt, &handle));

@@ -439,6 +439,61 @@ amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, cons
                                           const int32_t* axis_masks /* n_levels - 1, or NULL */,
                                           double theta, int64_t min_coarse,
                                           const amg_hip_options* opts, amg_hip_solver** out);
+/* Operator-dependent interpolation for a structured grid (NO reference counterpart).  Every level
+ * coarsens exactly ONE grid axis, and the 1-D interpolation weights along that axis come from the
+ * level's own matrix, so that P follows coefficients that jump by orders of magnitude from cell to
+ * cell (layered media, composites), where the fixed weights of the other tensor constructors leave
+ * the smooth error to the Krylov method.  Arrays, grid, options and argument checks are those of
+ * amg_hip_create_tensor_semi, all before the device is touched; opts->window = 1:
+ * AMG_HIP_EUNSUPPORTED.  There is no periodic form.
+ * axis_masks != NULL: n_levels - 1 masks of exactly one bit each (1, 2, or 4 when dim = 3);
+ * `min_coarse` is ignored and the solver has exactly n_levels levels.  AMG_HIP_EINVAL with the level
+ * in the message for a mask of several bits, a zero mask and a masked axis of fewer than 2 points.
+ * axis_masks == NULL: on each level w is amg_hip_tensor_axis_strength of the level's matrix and
+ * grid; an axis a < dim is eligible when it has at least 2 points; the eligible axis with the
+ * largest w_a is coarsened, the lowest axis on a tie.  The hierarchy ends at n_levels, at a level of
+ * at most `min_coarse` rows (min_coarse >= 1, else AMG_HIP_EINVAL) or when no axis is eligible
+ * (amg_hip_n_levels tells).  The rule does not depend on any order of evaluation.
+ * Grid: a masked axis of length m goes to floor(m / 2), coarse point J at fine coordinate 2 J + 1:
+ * the geometry and the sparsity pattern of amg_hip_create_tensor_semi's P for the same mask.
+ * Weights of level l, axis a: row i of A_l (the ROW, also for a nonsymmetric A), c its axis-a
+ * coordinate; its entries are added in ascending column order into s_m, s_0, s_p (from +0.0) by the
+ * axis-a coordinate c - 1, c, c + 1 of their column, whatever the column's other coordinates;
+ * entries at another axis-a distance are skipped, structural zeros are added.  Odd c: the point is
+ * coarse point (c - 1) / 2, one entry 1.0.  Even c: w_lo = (-s_m) / s_0 from coarse c / 2 - 1 when
+ * c >= 2, w_hi = (-s_p) / s_0 from coarse c / 2 when c + 1 < m, one negation and one division each;
+ * an entry is kept for every neighbour that exists, even when it comes out 0.0.  An s_0 that is
+ * zero or not finite, or a weight that is not finite: AMG_HIP_EINVAL with level and row in the
+ * message.  These weights are P1 in the interior of the constant-coefficient Laplacian (on a grid
+ * line next to a Dirichlet side of ANOTHER axis the collapsed s_0 keeps that side's term: 1/3
+ * instead of 1/2 on the 5-point model problem), 1.0 at a side without a Dirichlet term, and the
+ * flux-continuous k-/(k- + k+), k+/(k- + k+) across a jump; so
+ * opts->natural_sides does not enter them (it is validated and reported as on _tensor_semi and only
+ * serves opts->singular, which pins the coarsest solve as there; amg_hip_set_mean_projection works).
+ * R = P^T, A_{l+1} = R (A P) by the host Galerkin product in the summation order of
+ * amg_hip_create_custom: the level matrices are those of amg_hip_create_custom on the P / R of
+ * amg_hip_get_transfer, bit for bit.  Every smoother of _tensor_semi (AMG_HIP_SM_LINE_ALT included),
+ * host_only and every layout work; so do amg_hip_get_level_dims, _get_level_axes, _get_transfer and
+ * _line_directions.  With opts->stencil_transfers (the default) the transfers run matrix-free as
+ * K-AxisRestrict / K-AxisProlong on a compact per-point weight array (amg_hip_level_transfer_kind =
+ * 3), else as CSR SpMV with the uploaded P / R (kind 0): the same bits either way.  The float and
+ * block cycles take their CSR kernels on these levels.                                            */
+amg_hip_status amg_hip_create_tensor_opdep(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                           const double* val, const double* b, int32_t dim,
+                                           const int64_t* dims /* 3 */, int32_t n_levels,
+                                           const int32_t* axis_masks /* n_levels - 1 single-axis masks, or NULL */,
+                                           int64_t min_coarse, const amg_hip_options* opts, amg_hip_solver** out);
+/* 0: solvers made by amg_hip_create_tensor_opdep from now on take transfer kind 0 even with
+ * opts->stencil_transfers.  Process-wide, default 1, read when a solver is created.  Same bits
+ * either way: an A/B switch for tests and measurements.                                          */
+void amg_hip_set_axis_stencil(int32_t on);
+/* The compact weights of `level` of a solver made by amg_hip_create_tensor_opdep, 2 (n_l - n_{l+1})
+ * doubles; also on host_only solvers.  The fine points whose coordinate on the level's axis is even,
+ * c = 2 q, form a grid like the level's with that axis shortened to m - floor(m / 2); the point with
+ * flat index e on it (x fastest) has W[2 e] = w_lo (its coarse neighbour q - 1) and W[2 e + 1] =
+ * w_hi (coarse q), 0.0 where the neighbour does not exist.  AMG_HIP_EINVAL on the coarsest level
+ * and for every other solver.                                                                     */
+amg_hip_status amg_hip_get_axis_weights(const amg_hip_solver* s, int32_t level, double* W);
 /* Natural boundary sides (opts->natural_sides, opts->singular; honoured by amg_hip_create_tensor,
  * _tensor_semi, _tensor_dev and _tensor_semi_dev).  P1(m) interpolates fine point 0 -- and fine point
  * m - 1 of an odd m -- from its one coarse neighbour with weight 0.5: linear interpolation towards a
@@ -549,8 +604,11 @@ amg_hip_status amg_hip_tensor_axis_strength(int64_t n, const int32_t* colptr, co
 amg_hip_status amg_hip_get_level_dims(const amg_hip_solver* s, int32_t level, int64_t* dims /* 3 */);
 /* How the transfers between `level` and `level` + 1 run in the V-cycle: 0 = CSR SpMV with the
  * uploaded P / R, 1 = the reference's flat stride-2 kernels (LinearInterpolator operators with
- * opts->stencil_transfers), 2 = the tensor-product kernels of amg_hip_create_tensor.  Also on
- * host_only solvers (what a device solver with the same options would run).                     */
+ * opts->stencil_transfers), 2 = the tensor-product kernels of amg_hip_create_tensor, 3 = the
+ * single-axis kernels with per-point weights of amg_hip_create_tensor_opdep (K-AxisRestrict /
+ * K-AxisProlong; 0 on such a level with stencil_transfers = 0, after amg_hip_set_axis_stencil(0),
+ * or when the level has 2^31 - 4 rows or more).  Also on host_only solvers (what a device solver
+ * with the same options would run).                                                             */
 amg_hip_status amg_hip_level_transfer_kind(const amg_hip_solver* s, int32_t level, int32_t* kind);
 
 /* The same constructor for the reference's own model problem, A = Grid::laplacian(n) and
@@ -1176,6 +1234,15 @@ amg_hip_status amg_hip_tensor_restrict_axes(int32_t dim, const int64_t* dims_h /
                                             const double* r, double* f_H);
 amg_hip_status amg_hip_tensor_prolong_add_axes(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis_mask,
                                                const double* u_H, double* u_h);
+/* K-AxisRestrict / K-AxisProlong on host arrays: one coarsened `axis` (0 = x, 1 = y, 2 = z; < dim, at
+ * least 2 points) of the fine grid dims_h, with the compact weights W in the layout of
+ * amg_hip_get_axis_weights (2 (n_h - n_H) doubles, any values).  f_H = R r and u_h += P u_H,
+ * bit-identical to amg_hip_spmv with the R / P these weights stand for: every product is rounded
+ * and the terms are added from +0.0 in ascending column order.                                   */
+amg_hip_status amg_hip_axis_restrict(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis, const double* W,
+                                     const double* r, double* f_H);
+amg_hip_status amg_hip_axis_prolong_add(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis, const double* W,
+                                        const double* u_H, double* u_h);
 /* The same two transfers with an axis mask and the side mask of opts->natural_sides (P1N on the
  * coarsened axes): bit-identical to amg_hip_spmv with the R / P of amg_hip_get_transfer of a solver
  * made with that side mask.  The argument checks of the _axes forms, plus AMG_HIP_EINVAL for a

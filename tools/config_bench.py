@@ -13,6 +13,8 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py alt10 <nx> <ny> <levels>                    ten cycles of the alternating line smoother (kernel traces)
        config_bench.py mixed [<nx> <ny> <nz> <levels>]             amg_hip_pcg and amg_hip_pcg_mixed (single-precision V-cycle) alternating on a variable-coefficient operator, true Jacobi 2+2 and Chebyshev(2) 1+1
        config_bench.py semi [<nx> <ny> <nz> <eps_x> <eps_y> <eps_z>] PCG to 1e-8 on an axis-scaled diffusion operator: full coarsening + Jacobi, semi-coarsening + Jacobi, full coarsening + alternating lines, semi-coarsening + amg_hip_pcg_mixed (legs alternate)
+       config_bench.py opdep [<nx> <ny> <nz>]                      operator-dependent interpolation (tensor_opdep) on a diffusion operator whose conductivity jumps by 10^0..10^4 between blocks of 8 nodes: ms per V-cycle with the matrix-free transfers (kind 3) against CSR transfers (kind 0), PCG to 1e-8 against full coarsening (tensor), host set-up seconds and device matrix bytes (legs alternate)
+       config_bench.py opdep10 <nx> <ny> <nz> [csr]                ten cycles of one tensor_opdep hierarchy on that operator (kernel traces)
        config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
        config_bench.py singular [<nx> <ny> <nz>]                   PCG to 1e-8 on that operator without a Dirichlet side, one solver: mean projection (amg_hip_set_mean_projection) off and on with the consistent b and on with b + 1e-6, legs alternate; the time added per iteration next to an estimate from the tree reduction's rate in the same run
        config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
@@ -556,6 +558,119 @@ def run_semi(dims, eps, reps=3, rtol=1e-8, max_iters=300, theta=0.5, min_coarse=
     print(f"semi {tag}: best time to {rtol:g}: " + ", ".join(f"{k} {v * 1e3:.2f} ms" for k, v in best.items()),
           flush=True)
     for mg, _ in legs.values():
+        mg.close()
+
+
+def numpy_jump(dims, block=8, contrast=4, seed=7):
+    """CSC arrays and a random right-hand side of the 5- / 7-point diffusion operator with Dirichlet
+    sides whose conductivity is 10^k per block of `block` nodes per axis, k a random integer in
+    [0, contrast]; an edge takes the k of the block of its lower endpoint, a Dirichlet side adds the
+    boundary node's k to the diagonal.  Symmetric, so the CSR arrays are the CSC arrays."""
+    import numpy as np
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed)
+    n = int(np.prod(dims))
+    nb = [(m + block - 1) // block for m in dims]
+    kb = 10.0 ** rng.integers(0, contrast + 1, size=nb[::-1]).astype(np.float64)
+    idx = np.arange(n).reshape(dims[::-1])
+    knode = kb[tuple(np.meshgrid(*[np.arange(m) // block for m in dims[::-1]], indexing="ij"))].ravel()
+    diag = np.zeros(n)
+    rows, cols, vals = [np.arange(n)], [np.arange(n)], [diag]
+    for axis in range(len(dims)):
+        ax = len(dims) - 1 - axis
+        lo = np.take(idx, np.arange(dims[axis] - 1), axis=ax).ravel()
+        hi = np.take(idx, np.arange(1, dims[axis]), axis=ax).ravel()
+        k = knode[lo]
+        np.add.at(diag, lo, k)
+        np.add.at(diag, hi, k)
+        for side in (0, dims[axis] - 1):
+            s = np.take(idx, [side], axis=ax).ravel()
+            np.add.at(diag, s, knode[s])
+        rows += [lo, hi]
+        cols += [hi, lo]
+        vals += [-k, -k]
+    A = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n)).tocsc()
+    A.sort_indices()
+    return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data, np.random.default_rng(99).standard_normal(n)
+
+
+def cyclic_masks(dims, min_coarse=32):
+    """explicit single-axis masks x, y, (z,) x, ... over the axes that still have 2 points, down to a level
+    of at most min_coarse rows"""
+    d, masks, a = list(dims), [], 0
+    while max(d) >= 2 and d[0] * d[1] * (d[2] if len(d) == 3 else 1) > min_coarse:
+        if d[a] >= 2:
+            masks.append(1 << a)
+            d[a] //= 2
+        a = (a + 1) % len(d)
+    return masks
+
+
+def make_opdep(arrays, dims, csr=False, cyclic=False, **kw):
+    amg.set_axis_stencil(not csr)
+    try:
+        if cyclic:
+            masks = cyclic_masks(dims)
+            return amg.Multigrid.tensor_opdep(*arrays, dims, len(masks) + 1, axis_masks=masks, **TENSOR_KW["jacobi"], **kw)
+        return amg.Multigrid.tensor_opdep(*arrays, dims, 40, min_coarse=32, **TENSOR_KW["jacobi"], **kw)
+    finally:
+        amg.set_axis_stencil(True)
+
+
+def run_opdep(dims, reps=3, rtol=1e-8, max_iters=400, cycles=10):
+    """The jump operator (numpy_jump, contrast 1e4), true Jacobi omega 0.8 2+2, four legs alternating
+    in one process, `reps` repeats, best of them: tensor_opdep (automatic masks) with the matrix-free
+    transfers (K-AxisRestrict / K-AxisProlong, kind 3), the same solver with CSR transfers
+    (amg_hip_set_axis_stencil(0), kind 0, same bits), tensor_opdep with the explicit masks x, y, (z,) x, ...
+    (cyclic_masks, kind 3) and full coarsening (Multigrid.tensor).  Per leg:
+    host set-up seconds, levels, device matrix bytes of the smoothed levels over level 0's, ms per V-cycle
+    and must-move bytes; then amg_hip_pcg from x = 0 to `rtol`: iterations and wall ms."""
+    arrays = numpy_jump(dims)
+    tag = " x ".join(str(d) for d in dims) + " jump 1e4"
+    mk = {"opdep kind 3": lambda: make_opdep(arrays, dims),
+          "opdep kind 0": lambda: make_opdep(arrays, dims, csr=True),
+          "opdep cyclic masks": lambda: make_opdep(arrays, dims, cyclic=True),
+          "full": lambda: amg.Multigrid.tensor(*arrays, dims, full_levels(dims), **TENSOR_KW["jacobi"])}
+    legs = {}
+    for name, make in mk.items():
+        t0 = time.perf_counter()
+        mg = make()
+        mg.sync()
+        dt = time.perf_counter() - t0
+        nl = mg.n_levels
+        mat = [mg.level_layout(l)[1] for l in range(nl - 1)]
+        kinds = sorted(set(mg.level_transfer_kind(l) for l in range(nl - 1)))
+        axes = "".join("xyz"[mg.level_axes(l).bit_length() - 1] if kinds != [2] else "" for l in range(nl - 1))
+        mg.vcycle(3)
+        mg.sync()
+        print(f"opdep {tag}, {name}: host set-up {dt:.2f} s, {nl} levels, axes [{axes}], transfer kinds {kinds}, coarsest "
+              f"{mg.get_n_dofs(nl - 1)} dofs, matrix bytes of the smoothed levels / level 0 {sum(mat) / mat[0]:.2f}, "
+              f"must-move {mg.cycle_must_move() / 1e6:.1f} MB per V-cycle", flush=True)
+        mg.zero_vec(0, "u")
+        mg.pcg(rtol=rtol, max_iters=max_iters)  # first call: work vectors, captured graphs
+        legs[name] = mg
+    best_c, best_p, iters = {}, {}, {}
+    for rep_ in range(reps):
+        for name, mg in legs.items():
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            mg.vcycle(cycles)
+            mg.sync()
+            dt = (time.perf_counter() - t0) / cycles
+            best_c[name] = min(best_c.get(name, dt), dt)
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            _, it, rel = mg.pcg(rtol=rtol, max_iters=max_iters)
+            dp = time.perf_counter() - t0
+            best_p[name] = min(best_p.get(name, dp), dp)
+            iters[name] = it
+            print(f"opdep {tag}, {name} rep {rep_}: {dt * 1e3:.3f} ms/V-cycle; PCG {it} iterations, {dp * 1e3:.2f} ms to "
+                  f"{rtol:g} (relres {rel:.2e}, {'reached' if rel <= rtol else 'NOT reached: capped'})", flush=True)
+    print(f"opdep {tag}: best ms/V-cycle: " + ", ".join(f"{k} {v * 1e3:.3f}" for k, v in best_c.items()) +
+          "; best PCG ms: " + ", ".join(f"{k} {v * 1e3:.2f} ({iters[k]} it)" for k, v in best_p.items()), flush=True)
+    for mg in legs.values():
         mg.close()
 
 
@@ -1451,6 +1566,20 @@ elif len(sys.argv) > 1 and sys.argv[1] == "semi":
     else:
         run_semi((4096, 1024), (1.0, 1e-2))
         run_semi((256, 256, 256), (1.0, 1.0, 1e-2))
+elif len(sys.argv) > 1 and sys.argv[1] == "opdep":
+    if len(sys.argv) > 4:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_opdep(d if d[2] > 1 else d[:2])
+    else:
+        run_opdep((2048, 2048))
+        run_opdep((128, 128, 128))
+elif len(sys.argv) > 4 and sys.argv[1] == "opdep10":    # ten cycles of one hierarchy (kernel traces)
+    d = tuple(int(x) for x in sys.argv[2:5])
+    d = d if d[2] > 1 else d[:2]
+    mg = make_opdep(numpy_jump(d), d, csr=len(sys.argv) > 5)
+    mg.vcycle(10)
+    mg.sync()
+    mg.close()
 elif len(sys.argv) > 1 and sys.argv[1] == "natural":
     # profiles/natural_config_bench.txt
     if len(sys.argv) > 4:
