@@ -194,6 +194,11 @@ _SIGS = {
     "amg_hip_set_patch_min_rows": (None, [C.c_int64]),
     "amg_hip_set_band_chain": (None, [C.c_int32]),
     "amg_hip_set_tail_fusion": (None, [C.c_int32]),
+    "amg_hip_set_pair_duo": (None, [C.c_int32]),
+    "amg_hip_pair_duo_partner": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "amg_hip_duo_windows": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _i32p]),
+    "amg_hip_duo_owned": (C.c_int32, [C.c_int32, C.c_int32, _i32p]),
+    "amg_hip_duo_tile_rows": (C.c_int32, [C.c_int32]),
     "amg_hip_set_periodic_device_setup": (None, [C.c_int32]),
     "amg_hip_set_patch_tile_flags": (None, [C.c_int32]),
     "amg_hip_set_patch_xf": (None, [C.c_int32]),
@@ -437,6 +442,35 @@ def set_patch_seam(on):
 
 def set_tail_fusion(on):
     lib().amg_hip_set_tail_fusion(int(bool(on)))
+
+
+def set_pair_duo(on):
+    """K-Duo (two consecutive pair levels per launch) on (the default) / off; process-wide, read when a
+    solver is created, same bits either way"""
+    lib().amg_hip_set_pair_duo(int(bool(on)))
+
+
+DUO_WINDOWS_LEN = 31
+
+
+def duo_windows(hb_l, hb_l1, tile_rows=510):
+    """(fits, windows): amg_hip_duo_windows -- the 31 numbers described in include/amg_hip.h"""
+    out = np.zeros(DUO_WINDOWS_LEN, np.int32)
+    rc = lib().amg_hip_duo_windows(int(hb_l), int(hb_l1), int(tile_rows), out.ctypes.data_as(_i32p))
+    return rc == 0, out
+
+
+def duo_owned(tile, tile_rows=510):
+    """three half-open row ranges (levels l, l+1, l+2) that K-Duo tile number `tile` owns, unclipped"""
+    out = np.zeros(6, np.int32)
+    if lib().amg_hip_duo_owned(int(tile), int(tile_rows), out.ctypes.data_as(_i32p)) != 0:
+        raise ValueError("amg_hip_duo_owned: bad argument")
+    return [(int(out[0]), int(out[1])), (int(out[2]), int(out[3])), (int(out[4]), int(out[5]))]
+
+
+def duo_tile_rows(hb_l):
+    """rows of level l per tile that the K-Duo launchers use under half-bandwidth hb_l"""
+    return int(lib().amg_hip_duo_tile_rows(int(hb_l)))
 
 
 def set_periodic_device_setup(on):
@@ -1187,6 +1221,10 @@ class Multigrid:
         b = C.c_double(0)
         _chk(lib().amg_hip_cycle_must_move(self._h, int(part), C.byref(b)))
         return b.value
+
+    def pair_duo_partner(self, level):
+        """the other level of `level`'s K-Duo pair, or -1"""
+        return int(lib().amg_hip_pair_duo_partner(self._h, int(level)))
 
     def patch_leg_lines(self, level, leg):
         """lines of the K-Patch tiles of `level`'s down-leg (leg 0) / up-leg (leg 1); 0 = no K-Patch level.

@@ -1047,6 +1047,8 @@ typedef double pair_f64x2 __attribute__((ext_vector_type(2)));
 // (lone: the last entry of uh_in when n_h is odd -- at most one of a lane's two coarse points has
 // it -- in a register of its own: loaded into pre[r].x, the two forms share registers and the
 // compiler drains every load in flight between them)
+// (STRIDE: rows a tile advances by; the pair kernels' 510, K-Duo also runs shorter tiles)
+template <int STRIDE = 510>
 __device__ __forceinline__ void dict_prolong_pre(int tile, int n, int n_h, const double* uh_in,
                                                  pair_f64x2 (&pre)[2], double& lone) {
   bool two[2], one[2];
@@ -1054,8 +1056,8 @@ __device__ __forceinline__ void dict_prolong_pre(int tile, int n, int n_h, const
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     const int q = (int)threadIdx.x * 2 + r;
-    const int j = tile * 510 + q;
-    const bool on = !((q == 0 && tile != 0) || q > 510 || j > n);
+    const int j = tile * STRIDE + q;
+    const bool on = !((q == 0 && tile != 0) || q > STRIDE || j > n);
     i[r] = 2 * (int64_t)j;
     two[r] = on && i[r] + 1 < n_h;
     one[r] = on && i[r] + 1 == n_h;
@@ -1067,14 +1069,15 @@ __device__ __forceinline__ void dict_prolong_pre(int tile, int n, int n_h, const
     if (two[r]) pre[r] = *reinterpret_cast<const pair_f64x2*>(uh_in + i[r]);
   if (one[0] || one[1]) lone = uh_in[n_h - 1];
 }
+template <int STRIDE = 510>
 __device__ __forceinline__ void dict_prolong_tail(int tile, int n, const double* rs, int n_h,
                                                   const pair_f64x2 (&pre)[2], double lone,
                                                   double* uh_out) {
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     const int q = (int)threadIdx.x * 2 + r;
-    const int j = tile * 510 + q;
-    if ((q == 0 && tile != 0) || q > 510 || j > n) continue;
+    const int j = tile * STRIDE + q;
+    if ((q == 0 && tile != 0) || q > STRIDE || j > n) continue;
     double t0 = 0.0, t1 = 0.0;
     const double b = (j < n) ? rs[q] : 0.0;
     if (j >= 1 && j - 1 < n) t0 += 0.5 * rs[q - 1];
@@ -1448,6 +1451,437 @@ __global__ __launch_bounds__(256) void dict_pair_up_kernel(
   rs[threadIdx.x * 2 + 1] = s.live[1] ? res[1] : 0.0;
   __syncthreads();
   dict_prolong_tail(tile, n, rs, n_h, pre, pre1, uh_out);
+}
+
+// ---- K-Duo: two consecutive pair levels in one launch ---------------------------------------
+// The pair launches of the levels 6+ of the 4096^2 hierarchy sit within 2 us of the cost of an empty
+// launch, so one more step of the same kind: the down-legs of levels (l, l+1), or the up-legs of
+// (l+1, l), as ONE plain launch of independent workgroups.  A tile owns T rows of level l (DUO_T or
+// DUO_T_SMALL), the level-(l+1) rows c with 2c in it and the level-(l+2) rows cc with 4cc in it; everything
+// else it needs is recomputed from a wider window of the loaded operands (duo_windows: the
+// dependencies walked backwards).  All global loads are issued at entry and committed with one wait
+// (DuoLoads / duo_issue / duo_commit: PairLoads with the windows as arguments); every row comes from
+// dict_rows on LDS windows and the transfers are the expressions of dict_restrict_tail,
+// jacobi_from_zero_kernel, linear_prolong_add2_kernel and dict_prolong_tail, so a duo leaves the bits
+// of the four pair launches it replaces.  One DictEntry table serves both levels and both modes in
+// turn (rewritten from registers behind a barrier): the LDS stays below 64 KB.
+//
+// Windows.  hbw0 / hbw1: the even half-windows of levels l / l+1.  Level-(l+1) windows are given from
+// ce = (t0 / 2) & ~1 (t0 = the tile's first row: even, so that pairs never straddle an end), level-l
+// windows of the down-leg from 2 ce, those of the up-leg from t0: window = [base - lo, base - lo + count).
+enum {
+  DW_D_R1_LO, DW_D_R1,  // down: residual of l+1 (owned rows + 2)
+  DW_D_U1_LO, DW_D_U1,  //       second sweep of l+1
+  DW_D_M1_LO, DW_D_M1,  //       f_{l+1} and its first sweep from zero
+  DW_D_R0_LO, DW_D_R0,  //       residual of l
+  DW_D_M0_LO, DW_D_M0,  //       second sweep of l (f, row types)
+  DW_D_A0_LO, DW_D_A0,  //       tmp_l under it
+  DW_U_S1_LO, DW_U_S1,  // up:   second sweep of l+1
+  DW_U_M1_LO, DW_U_M1,  //       first sweep of l+1 (f, row types)
+  DW_U_A1_LO, DW_U_A1,  //       tmp_{l+1} under it
+  DW_U_S0_LO, DW_U_S0,  //       second sweep of l (the frame of the prolongation: tile + 2)
+  DW_U_M0_LO, DW_U_M0,  //       first sweep of l
+  DW_U_A0_LO, DW_U_A0,  //       u_l + P u_{l+1}
+  DW_CAP_D_M1, DW_CAP_D_M0, DW_CAP_D_A0, DW_CAP_U_M1, DW_CAP_U_A1, DW_CAP_U_M0, DW_CAP_U_A0,
+  DW_COUNT
+};
+// Rows of level l a tile owns: the pair kernels' 510 under a wide band; 254 where the halo is small
+// against the tile (half-window of level l <= DUO_T_SMALL_HBW), so that every window is one pass of
+// 256 lanes x 2 rows and twice as many workgroups share the work.  A duo's time is the chain of its
+// dependent passes, not its rows.
+constexpr int DUO_T = 510;
+constexpr int DUO_T_SMALL = 254;
+constexpr int DUO_T_SMALL_HBW = 34;
+constexpr int DUO_D_M1 = 448;                         // capacities, in rows
+constexpr int DUO_D_M0 = 1024;
+constexpr int DUO_D_A0 = DUO_D_M0 + 2 * PAIR_HB;
+constexpr int DUO_U_M1 = 512;
+constexpr int DUO_U_A1 = DUO_U_M1 + 2 * PAIR_HB;
+constexpr int DUO_U_M0 = 512 + 2 * PAIR_HB;
+constexpr int DUO_U_A0 = DUO_U_M0 + 2 * PAIR_HB;
+static_assert(DW_COUNT == AMG_DUO_WINDOWS_LEN, "kernels.hpp");
+__host__ __device__ inline void duo_windows(int hbw0, int hbw1, int T, int* w) {
+  const int r1 = (T / 2 + 4) & ~1;  // owned c + 2, + 1 for an odd t0 / 2
+  w[DW_D_R1_LO] = 0;                    w[DW_D_R1] = r1;
+  w[DW_D_U1_LO] = hbw1;                 w[DW_D_U1] = r1 + 2 * hbw1;
+  w[DW_D_M1_LO] = 2 * hbw1;             w[DW_D_M1] = r1 + 4 * hbw1;
+  w[DW_D_R0_LO] = 4 * hbw1;             w[DW_D_R0] = 2 * w[DW_D_M1] + 2;  // rows 2c .. 2c + 2
+  w[DW_D_M0_LO] = 4 * hbw1 + hbw0;      w[DW_D_M0] = w[DW_D_R0] + 2 * hbw0;
+  w[DW_D_A0_LO] = 4 * hbw1 + 2 * hbw0;  w[DW_D_A0] = w[DW_D_R0] + 4 * hbw0;
+  const int s0 = T + 2;
+  w[DW_U_S0_LO] = 0;         w[DW_U_S0] = s0;
+  w[DW_U_M0_LO] = hbw0;      w[DW_U_M0] = s0 + 2 * hbw0;
+  w[DW_U_A0_LO] = 2 * hbw0;  w[DW_U_A0] = s0 + 4 * hbw0;
+  // fine row i takes u_{l+1}[i / 2 - 1 .. i / 2] (even i) or [i / 2] (odd i)
+  const int s1 = (s0 / 2 + 2 * hbw0 + 4) & ~1;
+  w[DW_U_S1_LO] = hbw0 + 2;             w[DW_U_S1] = s1;
+  w[DW_U_M1_LO] = hbw0 + 2 + hbw1;      w[DW_U_M1] = s1 + 2 * hbw1;
+  w[DW_U_A1_LO] = hbw0 + 2 + 2 * hbw1;  w[DW_U_A1] = s1 + 4 * hbw1;
+  w[DW_CAP_D_M1] = DUO_D_M1; w[DW_CAP_D_M0] = DUO_D_M0; w[DW_CAP_D_A0] = DUO_D_A0;
+  w[DW_CAP_U_M1] = DUO_U_M1; w[DW_CAP_U_A1] = DUO_U_A1; w[DW_CAP_U_M0] = DUO_U_M0; w[DW_CAP_U_A0] = DUO_U_A0;
+}
+
+// What the tile that starts at row t0 of level l owns: rows [o[0], o[1]) of level l, the rows c of
+// level l+1 with 2c among them = [o[2], o[3]), the rows cc of level l+2 with 4cc among them =
+// [o[4], o[5]) -- before clipping to the levels' sizes.  t0 and T are even.
+__host__ __device__ inline void duo_owned(int t0, int T, int* o) {
+  o[0] = t0;             o[1] = t0 + T;
+  o[2] = t0 / 2;         o[3] = (t0 + T) / 2;
+  o[4] = (t0 + 3) >> 2;  o[5] = (t0 + T + 3) >> 2;
+}
+// PairLoads with the windows as arguments: AP passes of 256 lanes x 2 rows over the window of `a`
+// (AP == 0: the level has none), FP passes over the window of f / row types / code words.
+template <int WORDS, int AP, int FP>
+struct DuoLoads {
+  double tv;
+  int32_t to;
+  uint64_t rw[WORDS];
+  pair_f64x2 a[AP > 0 ? AP : 1];
+  pair_f64x2 f[FP];
+  double fl[FP];
+  uint32_t ty[FP], tl[FP];
+  pair_u64x2 c[FP][WORDS], cl[FP];
+};
+// a_lo / m_lo: the matrix rows of aw[0] / of window index 0 (even, may be negative); AW / W: rows
+template <int WORDS, bool TYPES, int AP, int FP>
+__device__ __forceinline__ void duo_issue(DuoLoads<WORDS, AP, FP>& g, int n, int a_lo, int AW, int m_lo,
+                                          int W, const uint64_t* __restrict__ codes,
+                                          const uint8_t* __restrict__ rtype,
+                                          const uint64_t* __restrict__ rwords,
+                                          const int32_t* __restrict__ doff,
+                                          const double* __restrict__ dval, int ntab, const double* a,
+                                          const double* __restrict__ f) {
+  const int t = threadIdx.x;
+  g.tv = t < ntab ? dval[t] : 0.0;
+  g.to = t < ntab ? doff[t] : 0;
+#pragma unroll
+  for (int k = 0; k < WORDS; ++k) g.rw[k] = TYPES ? rwords[t * WORDS + k] : 0;
+#pragma unroll
+  for (int k = 0; k < AP; ++k) {
+    const int idx = (k * 256 + t) * 2;
+    const int row = a_lo + idx;  // even: a pair is either entirely before row 0 or not at all
+    g.a[k].x = g.a[k].y = 0.0;
+    if (idx < AW && row >= 0) {
+      if (row + 1 < n) g.a[k] = *reinterpret_cast<const pair_f64x2*>(a + row);
+      else if (row < n) g.a[k].x = a[row];
+    }
+  }
+  bool both[FP], lone[FP];
+#pragma unroll
+  for (int k = 0; k < FP; ++k) {
+    const int lw = (k * 256 + t) * 2, row0 = m_lo + lw;
+    const bool inside = row0 >= 0 && lw < W;
+    both[k] = inside && row0 + 1 < n;
+    lone[k] = inside && row0 + 1 == n;
+    g.f[k].x = g.f[k].y = g.fl[k] = 0.0;
+    if (f) {  // (down-leg, level l+1: f is formed in LDS)
+      if (both[k]) g.f[k] = *reinterpret_cast<const pair_f64x2*>(f + row0);
+      if (lone[k]) g.fl[k] = f[row0];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < FP; ++k) {
+    const int row0 = m_lo + (k * 256 + t) * 2;
+    if (TYPES) {
+      g.ty[k] = 0xFFFFu;
+      g.tl[k] = 0xFFu;
+      if (both[k]) g.ty[k] = *reinterpret_cast<const uint16_t*>(rtype + row0);
+      if (lone[k]) g.tl[k] = rtype[row0];
+    } else {
+      g.cl[k].x = g.cl[k].y = ~(uint64_t)0;
+#pragma unroll
+      for (int j = 0; j < WORDS; ++j) g.c[k][j].x = g.c[k][j].y = ~(uint64_t)0;
+      const uint64_t* cp = codes + (int64_t)row0 * WORDS;
+      if (both[k]) {
+#pragma unroll
+        for (int j = 0; j < WORDS; ++j) g.c[k][j] = reinterpret_cast<const pair_u64x2*>(cp)[j];
+      }
+      if (lone[k]) {
+        if (WORDS == 2) g.cl[k] = *reinterpret_cast<const pair_u64x2*>(cp);
+        else g.cl[k].x = cp[0];
+      }
+    }
+  }
+}
+// fw == nullptr: f is not committed (the caller forms it)
+template <int WORDS, bool TYPES, int AP, int FP>
+__device__ __forceinline__ void duo_commit(const DuoLoads<WORDS, AP, FP>& g, int n, int AW, int m_lo, int W,
+                                           uint64_t* wc, uint16_t* tw, double* aw, double* fw) {
+  const int t = threadIdx.x;
+  if (TYPES) {
+#pragma unroll
+    for (int k = 0; k < WORDS; ++k) wc[t * WORDS + k] = g.rw[k];
+  }
+#pragma unroll
+  for (int k = 0; k < AP; ++k) {
+    const int idx = (k * 256 + t) * 2;
+    if (idx < AW) *reinterpret_cast<pair_f64x2*>(aw + idx) = g.a[k];
+  }
+#pragma unroll
+  for (int k = 0; k < FP; ++k) {
+    const int lw = (k * 256 + t) * 2;
+    if (lw >= W) continue;
+    const bool both = m_lo + lw >= 0 && m_lo + lw + 1 < n;  // else: the lone last row, or no row at all
+    if (fw) {
+      pair_f64x2 fv = g.f[k];
+      fv.x = both ? fv.x : g.fl[k];
+      *reinterpret_cast<pair_f64x2*>(fw + lw) = fv;
+    }
+    if (TYPES) {
+      uint32_t tl = g.tl[k];
+      asm volatile("" : "+v"(tl));  // see dict_pair_commit
+      tw[lw >> 1] = (uint16_t)(both ? g.ty[k] : (tl | 0xFF00u));
+    } else {
+      pair_u64x2* wp = reinterpret_cast<pair_u64x2*>(wc + lw * WORDS);
+      wp[0] = both ? g.c[k][0] : g.cl[k];
+      if (WORDS == 2) wp[1] = g.c[k][WORDS - 1];
+    }
+  }
+}
+// One stage on a window: rows [lo, lo + cnt) (window indices, lo even) of the level whose f / row
+// types / code words are fw / tw / wc with W rows from matrix row m_lo; x[xs + i] is the operand of
+// window row i.  Results go to out[i - lo] (0.0 for rows outside the matrix) and, for the matrix rows
+// in [own_lo, own_hi), to gout if given.
+template <int MODE, int WORDS, int UN>
+__device__ __forceinline__ void duo_stage(int n, int m_lo, int W, int lo, int cnt, bool types,
+                                          const DictEntry* tab, const uint64_t* wc, const uint16_t* tw,
+                                          const double* fw, const double* x, int xs, double omega,
+                                          double* out, double* gout, int own_lo, int own_hi) {
+  for (int base = 0; base < cnt; base += 512) {
+    const int k = base + (int)threadIdx.x * 2;
+    const bool in = k < cnt;
+    const int lw = in ? lo + k : W;  // W: no row
+    const int row0 = m_lo + lw;
+    DictStream<WORDS, 2> s;
+    dict_pair_stream<WORDS>(s, lw, W, row0, n, types, wc, tw, fw);
+    if (in && mode_jac(MODE)) {
+      s.xi[0] = x[xs + lw];
+      s.xi[1] = x[xs + lw + 1];
+    }
+    if (types) dict_expand<WORDS, 2>(s, wc);
+    double res[2];
+    dict_rows<MODE, WORDS, UN, 2>(s, in ? xs + lw : 0, tab, x, omega, 0, res);
+    if (in) {
+      out[k] = s.live[0] ? res[0] : 0.0;
+      out[k + 1] = s.live[1] ? res[1] : 0.0;
+      if (gout) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+          if (s.live[r] && row0 + r >= own_lo && row0 + r < own_hi) gout[row0 + r] = res[r];
+      }
+    }
+  }
+}
+// Restriction of the residuals rs (rs[0] = fine row 2 c_lo) to the coarse rows c_lo + q, q < cnt, and
+// their first Jacobi sweep from zero: dict_restrict_tail's sums and guards.  fo / vo: LDS windows
+// (or null), fH / uH1: global, rows in [own_lo, own_hi) only; d[q]: the coarse diagonal, preloaded.
+__device__ __forceinline__ void duo_restrict_row(int c, int n, int nH, const double* rs, int q, double d,
+                                                 double omega, double& sum_out, double& v_out) {
+  double sum = 0.0, v = 0.0;
+  if (c >= 0 && c < nH) {
+    const int64_t i = 2 * (int64_t)c;  // linear_restrict_kernel, same guards and order
+    if (i < n) sum += 0.5 * rs[2 * q];
+    if (i + 1 < n) sum += 1.0 * rs[2 * q + 1];
+    if (i + 2 < n) sum += 0.5 * rs[2 * q + 2];
+    const double xi = 0.0, acc = 0.0;  // jacobi_from_zero_kernel
+    v = (d == 0.0) ? xi : xi + omega * ((sum - acc) / d - xi);
+  }
+  sum_out = sum;
+  v_out = v;
+}
+
+template <int W0, int U0, int W1, int U1>
+__global__ __launch_bounds__(256) void dict_duo_down_kernel(
+    int n0, const uint64_t* __restrict__ codes0, const uint8_t* __restrict__ rtype0,
+    const uint64_t* __restrict__ rwords0, const int32_t* __restrict__ doff0,
+    const double* __restrict__ dval0, int ntab0, int hbw0,
+    int n1, const uint64_t* __restrict__ codes1, const uint8_t* __restrict__ rtype1,
+    const uint64_t* __restrict__ rwords1, const int32_t* __restrict__ doff1,
+    const double* __restrict__ dval1, int ntab1, int hbw1,
+    const double* a0, const double* __restrict__ f0, double* u0_out, double* r0_out,
+    double* __restrict__ f1_out, const double* __restrict__ diag1, double* u1_out, double* r1_out,
+    int n2, double* __restrict__ f2_out, const double* __restrict__ diag2, double* __restrict__ v2_out,
+    double omega, int T, int xcd_map) {
+  constexpr int WC0 = DUO_D_M0 * W0, WC1 = (DUO_D_M1 > 256 ? DUO_D_M1 : 256) * W1;
+  __shared__ DictEntry tab[256];
+  __shared__ __attribute__((aligned(16))) uint64_t wc0[WC0];
+  __shared__ __attribute__((aligned(16))) uint64_t wc1[WC1];
+  __shared__ uint16_t tw0[DUO_D_M0 / 2];
+  __shared__ uint16_t tw1[DUO_D_M1 / 2];
+  __shared__ __attribute__((aligned(16))) double aw0[DUO_D_A0];  // tmp_l; then the residuals of l
+  __shared__ __attribute__((aligned(16))) double fw0[DUO_D_M0];  // f_l; then f_{l+1} and its first sweep
+  __shared__ __attribute__((aligned(16))) double uw0[DUO_D_M0];  // u_l; then u_{l+1} and the residuals of l+1
+  static_assert(2 * DUO_D_M1 <= DUO_D_M0 && DUO_D_M1 + DUO_T / 2 + 8 <= DUO_D_M0, "the aliases fit");
+  double* rs0 = aw0;
+  double* fw1 = fw0;
+  double* vw1 = fw0 + DUO_D_M1;
+  double* uw1 = uw0;
+  double* rs1 = uw0 + DUO_D_M1;
+  int w[DW_COUNT];
+  duo_windows(hbw0, hbw1, T, w);
+  const int tile = xcd_tile(blockIdx.x, gridDim.x, xcd_map);
+  const int t0 = tile * T, ce = (t0 / 2) & ~1, b0 = 2 * ce;
+  const int m0 = b0 - w[DW_D_M0_LO], M0 = w[DW_D_M0], A0 = w[DW_D_A0];
+  const int m1 = ce - w[DW_D_M1_LO], M1 = w[DW_D_M1];
+  const bool types0 = rtype0 != nullptr, types1 = rtype1 != nullptr;
+  const int t = threadIdx.x;
+  DuoLoads<W0, (DUO_D_A0 / 2 + 255) / 256, DUO_D_M0 / 512> g0;
+  DuoLoads<W1, 0, 1> g1;
+  if (types0) duo_issue<W0, true>(g0, n0, m0 - hbw0, A0, m0, M0, codes0, rtype0, rwords0, doff0, dval0, ntab0, a0, f0);
+  else duo_issue<W0, false>(g0, n0, m0 - hbw0, A0, m0, M0, codes0, rtype0, rwords0, doff0, dval0, ntab0, a0, f0);
+  if (types1) duo_issue<W1, true>(g1, n1, 0, 0, m1, M1, codes1, rtype1, rwords1, doff1, dval1, ntab1, nullptr, nullptr);
+  else duo_issue<W1, false>(g1, n1, 0, 0, m1, M1, codes1, rtype1, rwords1, doff1, dval1, ntab1, nullptr, nullptr);
+  // the coarse diagonals: rows m1 + 2 t, + 1 of level l+1; the owned row cc_lo + t of level l+2
+  pair_f64x2 d1;
+  d1.x = d1.y = 0.0;
+  {
+    const int c = m1 + 2 * t;
+    if (2 * t < M1 && c >= 0) {
+      if (c + 1 < n1) d1 = *reinterpret_cast<const pair_f64x2*>(diag1 + c);
+      else if (c < n1) d1.x = diag1[c];
+    }
+  }
+  int own[6];
+  duo_owned(t0, T, own);
+  const int cc_lo = own[4], cc_hi = min(own[5], n2);
+  const double d2 = cc_lo + t < cc_hi ? diag2[cc_lo + t] : 0.0;
+  dict_put_table<CSR_JACOBI>(tab, g0.tv, g0.to, ntab0);
+  if (types0) duo_commit<W0, true>(g0, n0, A0, m0, M0, wc0, tw0, aw0, fw0);
+  else duo_commit<W0, false>(g0, n0, A0, m0, M0, wc0, tw0, aw0, fw0);
+  if (types1) duo_commit<W1, true>(g1, n1, 0, m1, M1, wc1, tw1, nullptr, nullptr);
+  else duo_commit<W1, false>(g1, n1, 0, m1, M1, wc1, tw1, nullptr, nullptr);
+  __syncthreads();
+  // level l: second pre-sweep (tmp_l -> u_l), residual
+  duo_stage<CSR_JACOBI, W0, U0>(n0, m0, M0, 0, M0, types0, tab, wc0, tw0, fw0, aw0, hbw0, omega, uw0, u0_out,
+                                own[0], own[1]);
+  __syncthreads();
+  dict_put_table<CSR_RESID>(tab, g0.tv, g0.to, ntab0);
+  __syncthreads();
+  duo_stage<CSR_RESID, W0, U0>(n0, m0, M0, hbw0, w[DW_D_R0], types0, tab, wc0, tw0, fw0, uw0, 0, omega, rs0,
+                               r0_out, own[0], own[1]);
+  __syncthreads();
+  // restriction to the window of level l+1 and its first sweep from zero (kept in LDS)
+  const int c_own = own[2], c_end = own[3];
+  if (2 * t < M1) {
+    double fv[2], vv[2];
+    duo_restrict_row(m1 + 2 * t, n0, n1, rs0, 2 * t, d1.x, omega, fv[0], vv[0]);
+    duo_restrict_row(m1 + 2 * t + 1, n0, n1, rs0, 2 * t + 1, d1.y, omega, fv[1], vv[1]);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int c = m1 + 2 * t + r;
+      fw1[2 * t + r] = fv[r];
+      vw1[2 * t + r] = vv[r];
+      if (c >= c_own && c < c_end && c < n1) f1_out[c] = fv[r];
+    }
+  }
+  dict_put_table<CSR_JACOBI>(tab, g1.tv, g1.to, ntab1);
+  __syncthreads();
+  // level l+1: second pre-sweep, residual
+  duo_stage<CSR_JACOBI, W1, U1>(n1, m1, M1, hbw1, w[DW_D_U1], types1, tab, wc1, tw1, fw1, vw1, 0, omega, uw1,
+                                u1_out, c_own, c_end);
+  __syncthreads();
+  dict_put_table<CSR_RESID>(tab, g1.tv, g1.to, ntab1);
+  __syncthreads();
+  duo_stage<CSR_RESID, W1, U1>(n1, m1, M1, 2 * hbw1, w[DW_D_R1], types1, tab, wc1, tw1, fw1, uw1, -hbw1, omega,
+                               rs1, r1_out, c_own, c_end);
+  __syncthreads();
+  // restriction to the owned rows of level l+2 and their first sweep
+  if (cc_lo + t < cc_hi) {
+    const int cc = cc_lo + t;
+    double fv, vv;
+    // rs1[0] is row ce of level l+1; row 2 cc sits at 2 cc - ce
+    duo_restrict_row(cc, n1, n2, rs1 + (2 * cc - ce) - 2 * t, t, d2, omega, fv, vv);
+    f2_out[cc] = fv;
+    v2_out[cc] = vv;
+  }
+}
+template <int W0, int U0, int W1, int U1>
+__global__ __launch_bounds__(256) void dict_duo_up_kernel(
+    int n0, const uint64_t* __restrict__ codes0, const uint8_t* __restrict__ rtype0,
+    const uint64_t* __restrict__ rwords0, const int32_t* __restrict__ doff0,
+    const double* __restrict__ dval0, int ntab0, int hbw0,
+    int n1, const uint64_t* __restrict__ codes1, const uint8_t* __restrict__ rtype1,
+    const uint64_t* __restrict__ rwords1, const int32_t* __restrict__ doff1,
+    const double* __restrict__ dval1, int ntab1, int hbw1,
+    const double* a1, const double* __restrict__ f1, double* u1_out,
+    const double* u0_in, const double* __restrict__ f0, double* u0_out,
+    double omega, int n_h, const double* uh_in, double* uh_out, int T, int xcd_map) {
+  constexpr int WC0 = DUO_U_M0 * W0, WC1 = DUO_U_M1 * W1;
+  __shared__ DictEntry tab[256];
+  __shared__ __attribute__((aligned(16))) uint64_t wc0[WC0];
+  __shared__ __attribute__((aligned(16))) uint64_t wc1[WC1];
+  __shared__ uint16_t tw0[DUO_U_M0 / 2];
+  __shared__ uint16_t tw1[DUO_U_M1 / 2];
+  __shared__ __attribute__((aligned(16))) double aw1[DUO_U_A1];  // tmp_{l+1}; then u_{l+1}
+  __shared__ __attribute__((aligned(16))) double fw1[DUO_U_M1];
+  __shared__ __attribute__((aligned(16))) double uw1[DUO_U_M1];
+  __shared__ __attribute__((aligned(16))) double aw0[DUO_U_A0];  // u_l, + P u_{l+1}; then the frame of u_l
+  __shared__ __attribute__((aligned(16))) double fw0[DUO_U_M0];
+  __shared__ __attribute__((aligned(16))) double uw0[DUO_U_M0];
+  double* vw1 = aw1;
+  double* rs = aw0;
+  int w[DW_COUNT];
+  duo_windows(hbw0, hbw1, T, w);
+  const int tile = xcd_tile(blockIdx.x, gridDim.x, xcd_map);
+  const int t0 = tile * T, ce = (t0 / 2) & ~1;
+  const int m0 = t0 - hbw0, M0 = w[DW_U_M0], A0 = w[DW_U_A0];
+  const int m1 = ce - w[DW_U_M1_LO], M1 = w[DW_U_M1], A1 = w[DW_U_A1];
+  const bool types0 = rtype0 != nullptr, types1 = rtype1 != nullptr;
+  const int t = threadIdx.x;
+  DuoLoads<W1, (DUO_U_A1 / 2 + 255) / 256, 1> g1;
+  DuoLoads<W0, (DUO_U_A0 / 2 + 255) / 256, (DUO_U_M0 + 511) / 512> g0;
+  if (types1) duo_issue<W1, true>(g1, n1, m1 - hbw1, A1, m1, M1, codes1, rtype1, rwords1, doff1, dval1, ntab1, a1, f1);
+  else duo_issue<W1, false>(g1, n1, m1 - hbw1, A1, m1, M1, codes1, rtype1, rwords1, doff1, dval1, ntab1, a1, f1);
+  if (types0) duo_issue<W0, true>(g0, n0, m0 - hbw0, A0, m0, M0, codes0, rtype0, rwords0, doff0, dval0, ntab0, u0_in, f0);
+  else duo_issue<W0, false>(g0, n0, m0 - hbw0, A0, m0, M0, codes0, rtype0, rwords0, doff0, dval0, ntab0, u0_in, f0);
+  pair_f64x2 pre[2];  // uh_in may be uh_out: a lane reads only the rows it later writes
+  double pre1;
+  if (T == DUO_T) dict_prolong_pre<DUO_T>(tile, n0, n_h, uh_in, pre, pre1);  // (T is one of the two)
+  else dict_prolong_pre<DUO_T_SMALL>(tile, n0, n_h, uh_in, pre, pre1);
+  dict_put_table<CSR_JACOBI>(tab, g1.tv, g1.to, ntab1);
+  if (types1) duo_commit<W1, true>(g1, n1, A1, m1, M1, wc1, tw1, aw1, fw1);
+  else duo_commit<W1, false>(g1, n1, A1, m1, M1, wc1, tw1, aw1, fw1);
+  if (types0) duo_commit<W0, true>(g0, n0, A0, m0, M0, wc0, tw0, aw0, fw0);
+  else duo_commit<W0, false>(g0, n0, A0, m0, M0, wc0, tw0, aw0, fw0);
+  __syncthreads();
+  // level l+1: both post-sweeps
+  duo_stage<CSR_JACOBI, W1, U1>(n1, m1, M1, 0, M1, types1, tab, wc1, tw1, fw1, aw1, hbw1, omega, uw1, nullptr, 0, 0);
+  __syncthreads();
+  int own[6];
+  duo_owned(t0, T, own);
+  const int c_own = own[2], c_end = own[3];
+  duo_stage<CSR_JACOBI, W1, U1>(n1, m1, M1, hbw1, w[DW_U_S1], types1, tab, wc1, tw1, fw1, uw1, 0, omega, vw1,
+                                u1_out, c_own, c_end);
+  __syncthreads();
+  dict_put_table<CSR_JACOBI>(tab, g0.tv, g0.to, ntab0);
+  // u_l + P u_{l+1} on the window of level l: linear_prolong_add2_kernel per coarse point j, fine rows
+  // 2j, 2j + 1.  vw1[0] is row s1 = ce - (hbw0 + 2) of level l+1, aw0[0] row m0 - hbw0 of level l.
+  {
+    const int s1 = ce - w[DW_U_S1_LO], a_lo = m0 - hbw0;
+    for (int k = 2 * t; k < A0; k += 512) {
+      const int i = a_lo + k;  // even
+      if (i < 0 || i >= n0) continue;
+      const int j = i >> 1;
+      double p0 = 0.0, p1 = 0.0;
+      const double b = (j < n1) ? vw1[j - s1] : 0.0;
+      if (j >= 1 && j - 1 < n1) p0 += 0.5 * vw1[j - 1 - s1];
+      if (j < n1) {
+        p0 += 0.5 * b;
+        p1 += 1.0 * b;
+      }
+      aw0[k] = aw0[k] + p0;
+      if (i + 1 < n0) aw0[k + 1] = aw0[k + 1] + p1;
+    }
+  }
+  __syncthreads();
+  // level l: both post-sweeps; the second one rests in tmp_l (u0_out) and feeds the prolongation
+  duo_stage<CSR_JACOBI, W0, U0>(n0, m0, M0, 0, M0, types0, tab, wc0, tw0, fw0, aw0, hbw0, omega, uw0, nullptr, 0, 0);
+  __syncthreads();
+  duo_stage<CSR_JACOBI, W0, U0>(n0, m0, M0, hbw0, w[DW_U_S0], types0, tab, wc0, tw0, fw0, uw0, 0, omega, rs, u0_out,
+                                own[0], own[1]);
+  __syncthreads();
+  if (T == DUO_T) dict_prolong_tail<DUO_T>(tile, n0, rs, n_h, pre, pre1, uh_out);
+  else dict_prolong_tail<DUO_T_SMALL>(tile, n0, rs, n_h, pre, pre1, uh_out);
 }
 
 // ---- K-Patch: the level's whole down-leg / up-leg in ONE pass over the level ------------
@@ -2781,19 +3215,31 @@ bool dict_pair_ok(int64_t n, const DictRef& D, int hb, const void* a, const void
          aligned16(a, b, c) && aligned16(D.rtype ? nullptr : D.codes, nullptr, nullptr) &&
          (!D.rtype || (reinterpret_cast<uintptr_t>(D.rtype) & 1) == 0);
 }
+// The (WORDS, UN) a level's rows are walked with, as a class 0 .. 6: one table for the pair kernels
+// and for the K-Duo kernels, which take one class per level.
+template <int C> struct DictWU;
+template <> struct DictWU<0> { static constexpr int W = 1, U = 3; };
+template <> struct DictWU<1> { static constexpr int W = 1, U = 5; };
+template <> struct DictWU<2> { static constexpr int W = 1, U = 7; };
+template <> struct DictWU<3> { static constexpr int W = 1, U = 8; };
+template <> struct DictWU<4> { static constexpr int W = 2, U = 9; };
+template <> struct DictWU<5> { static constexpr int W = 2, U = 12; };
+template <> struct DictWU<6> { static constexpr int W = 2, U = 16; };
+constexpr int DICT_WU_CLASSES = 7;
+static int dict_wu_class(int words, int wmax) {
+  if (words == 1) return wmax <= 3 ? 0 : (wmax <= 5 ? 1 : (wmax <= 7 ? 2 : 3));
+  return wmax <= 9 ? 4 : (wmax <= 12 ? 5 : 6);
+}
+template <int C, class F>
+static void dict_dispatch_class(int c, F&& go) {
+  if constexpr (C < DICT_WU_CLASSES) {
+    if (c == C) go(std::integral_constant<int, DictWU<C>::W>{}, std::integral_constant<int, DictWU<C>::U>{});
+    else dict_dispatch_class<C + 1>(c, go);
+  }
+}
 template <class F>
 static hipError_t dict_dispatch_wu(int words, int wmax, F&& go) {
-  using std::integral_constant;
-  if (words == 1) {
-    if (wmax <= 3) go(integral_constant<int, 1>{}, integral_constant<int, 3>{});
-    else if (wmax <= 5) go(integral_constant<int, 1>{}, integral_constant<int, 5>{});
-    else if (wmax <= 7) go(integral_constant<int, 1>{}, integral_constant<int, 7>{});
-    else go(integral_constant<int, 1>{}, integral_constant<int, 8>{});
-  } else {
-    if (wmax <= 9) go(integral_constant<int, 2>{}, integral_constant<int, 9>{});
-    else if (wmax <= 12) go(integral_constant<int, 2>{}, integral_constant<int, 12>{});
-    else go(integral_constant<int, 2>{}, integral_constant<int, 16>{});
-  }
+  dict_dispatch_class<0>(dict_wu_class(words, wmax), go);
   return hipGetLastError();
 }
 hipError_t launch_dict_pair_down(int64_t n, const DictRef& D, int hb, const double* a,
@@ -2824,6 +3270,115 @@ hipError_t launch_dict_pair_up(int64_t n, const DictRef& D, int hb, const double
                        dim3(256), 0, st, (int)n, D.codes, D.rtype, D.rwords, D.doff, D.dval, D.ntab,
                        a, f, u_out, omega, hbw, (int)n_h, uh_in, uh_out, dict_xcd_map(D));
   });
+}
+// K-Duo (dict_duo_down_kernel / dict_duo_up_kernel).  The windows of both legs, for the launchers, the
+// host's predicate and the tests: 0 when every window is within its capacity.
+int duo_windows_host(int hb0, int hb1, int tile_rows, int32_t* out) {
+  if (hb0 < 0 || hb1 < 0 || hb0 > PAIR_HB - 1 || hb1 > PAIR_HB - 1 || tile_rows < 4 || (tile_rows & 1) ||
+      tile_rows > DUO_T || !out)
+    return 1;
+  int w[DW_COUNT];
+  duo_windows((hb0 + 1) & ~1, (hb1 + 1) & ~1, tile_rows, w);
+  for (int i = 0; i < DW_COUNT; ++i) out[i] = w[i];
+  return (w[DW_D_M1] <= DUO_D_M1 && w[DW_D_M0] <= DUO_D_M0 && w[DW_D_A0] <= DUO_D_A0 && w[DW_U_M1] <= DUO_U_M1 &&
+          w[DW_U_A1] <= DUO_U_A1 && w[DW_U_M0] <= DUO_U_M0 && w[DW_U_A0] <= DUO_U_A0)
+             ? 0
+             : 1;
+}
+int duo_owned_host(int tile, int tile_rows, int32_t* out) {
+  if (tile < 0 || tile_rows < 4 || (tile_rows & 1) || tile_rows > DUO_T || !out ||
+      (int64_t)tile * tile_rows > ((int64_t)1 << 30))
+    return 1;
+  int o[6];
+  duo_owned(tile * tile_rows, tile_rows, o);
+  for (int i = 0; i < 6; ++i) out[i] = o[i];
+  return 0;
+}
+// (WORDS, UN) of a level as dict_dispatch_wu picks it, as a class 0 .. 6; the duo kernels exist for a
+// coarser level of the same class as the finer one, of up to DUO_CLASS_SPAN classes below it (the rows
+// of a Galerkin hierarchy get shorter as the band narrows: 4096^2 pairs <2,9>/<2,9>, <2,9>/<1,7> and
+// <1,5>/<1,5>) or of the class above (the level under a 5-point fine level: 8 entries over 9).  Any
+// other pair of levels keeps the pair form.
+constexpr int DUO_CLASS_SPAN = 3;
+static int duo_class(const DictRef& D) { return dict_wu_class(D.words, D.wmax); }
+template <int C0, int K, class F>
+static bool duo_dispatch_c1(int c1, F&& go) {
+  if constexpr (K > DUO_CLASS_SPAN) {
+    return false;
+  } else if constexpr (C0 - K < 0 || C0 - K >= DICT_WU_CLASSES) {
+    return duo_dispatch_c1<C0, K + 1>(c1, go);
+  } else {
+    if (c1 == C0 - K) {
+      go(std::integral_constant<int, C0>{}, std::integral_constant<int, C0 - K>{});
+      return true;
+    }
+    return duo_dispatch_c1<C0, K + 1>(c1, go);
+  }
+}
+template <int C0, class F>
+static bool duo_dispatch_c0(int c0, int c1, F&& go) {
+  if constexpr (C0 < DICT_WU_CLASSES) {
+    if (c0 == C0) return duo_dispatch_c1<C0, -1>(c1, go);
+    return duo_dispatch_c0<C0 + 1>(c0, c1, go);
+  } else {
+    return false;
+  }
+}
+// DUO_MAX_ROWS: a finer level with more rows runs its two pair launches.  Above it a level is bound by
+// its rows, not by its launches, and the recomputed halo costs more than the launch saves (DESIGN.md
+// section 4, K-Duo; 4096^2 hierarchy, down + up leg of the duo against the four pair launches: level 6,
+// 262 144 rows, 19.4 + 17.4 us against 15.6 + 15.5 us; level 7, 131 072 rows, 15.7 + 14.4 us against
+// 12.4 + 12.8 us; level 8, 65 536 rows, 10.0 + 9.9 us against 11.5 + 11.3 us)
+constexpr int64_t DUO_MAX_ROWS = 100000;
+int duo_tile_rows(int hb0) { return ((hb0 + 1) & ~1) <= DUO_T_SMALL_HBW ? DUO_T_SMALL : DUO_T; }
+bool dict_duo_ok(int64_t n0, const DictRef& D0, int hb0, int64_t n1, const DictRef& D1, int hb1, int64_t n2) {
+  int32_t w[DW_COUNT];
+  const int c0 = duo_class(D0), c1 = duo_class(D1);
+  return n0 <= DUO_MAX_ROWS && n1 >= 1 && n2 >= 1 && n1 <= (n0 + 1) / 2 && n2 <= (n1 + 1) / 2 &&
+         dict_pair_ok(n0, D0, hb0, nullptr, nullptr, nullptr) && dict_pair_ok(n1, D1, hb1, nullptr, nullptr, nullptr) &&
+         c1 <= c0 + 1 && c0 - c1 <= DUO_CLASS_SPAN && duo_windows_host(hb0, hb1, duo_tile_rows(hb0), w) == 0;
+}
+hipError_t launch_dict_duo_down(int64_t n0, const DictRef& D0, int hb0, int64_t n1, const DictRef& D1, int hb1,
+                                const double* a0, const double* f0, double* u0_out, double* r0_out,
+                                double* f1_out, const double* diag1, double* u1_out, double* r1_out, int64_t n2,
+                                double* f2_out, const double* diag2, double* v2_out, double omega,
+                                hipStream_t st) {
+  if (!dict_duo_ok(n0, D0, hb0, n1, D1, hb1, n2) || !a0 || !f0 || !u0_out || !f1_out || !diag1 || !u1_out ||
+      !f2_out || !diag2 || !v2_out || !aligned16(a0, f0, diag1) || !aligned16(r0_out, nullptr, nullptr))
+    return hipErrorInvalidValue;
+  const int hbw0 = (hb0 + 1) & ~1, hbw1 = (hb1 + 1) & ~1;
+  const int T = duo_tile_rows(hb0);
+  const unsigned tiles = (unsigned)((n0 + T - 1) / T);
+  const bool found = duo_dispatch_c0<0>(duo_class(D0), duo_class(D1), [&](auto C0, auto C1) {
+    using K0 = DictWU<decltype(C0)::value>;
+    using K1 = DictWU<decltype(C1)::value>;
+    hipLaunchKernelGGL((dict_duo_down_kernel<K0::W, K0::U, K1::W, K1::U>), dim3(tiles), dim3(256), 0, st, (int)n0,
+                       D0.codes, D0.rtype, D0.rwords, D0.doff, D0.dval, D0.ntab, hbw0, (int)n1, D1.codes, D1.rtype,
+                       D1.rwords, D1.doff, D1.dval, D1.ntab, hbw1, a0, f0, u0_out, r0_out, f1_out, diag1, u1_out,
+                       r1_out, (int)n2, f2_out, diag2, v2_out, omega, T, dict_xcd_map(D0));
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+hipError_t launch_dict_duo_up(int64_t n0, const DictRef& D0, int hb0, int64_t n1, const DictRef& D1, int hb1,
+                              const double* a1, const double* f1, double* u1_out, const double* u0_in,
+                              const double* f0, double* u0_out, double omega, int64_t n_h, const double* uh_in,
+                              double* uh_out, hipStream_t st) {
+  if (!dict_duo_ok(n0, D0, hb0, n1, D1, hb1, 1) || !a1 || !f1 || !u1_out || !u0_in || !f0 || !u0_out ||
+      u0_out == u0_in || n0 > n_h || !uh_in || !uh_out || !aligned16(a1, f1, u0_in) || !aligned16(f0, u0_out, uh_in) ||
+      !aligned16(uh_out, nullptr, nullptr))
+    return hipErrorInvalidValue;
+  const int hbw0 = (hb0 + 1) & ~1, hbw1 = (hb1 + 1) & ~1;
+  const int T = duo_tile_rows(hb0);
+  const unsigned tiles = (unsigned)((n0 + T - 1) / T);
+  const bool found = duo_dispatch_c0<0>(duo_class(D0), duo_class(D1), [&](auto C0, auto C1) {
+    using K0 = DictWU<decltype(C0)::value>;
+    using K1 = DictWU<decltype(C1)::value>;
+    hipLaunchKernelGGL((dict_duo_up_kernel<K0::W, K0::U, K1::W, K1::U>), dim3(tiles), dim3(256), 0, st, (int)n0,
+                       D0.codes, D0.rtype, D0.rwords, D0.doff, D0.dval, D0.ntab, hbw0, (int)n1, D1.codes, D1.rtype,
+                       D1.rwords, D1.doff, D1.dval, D1.ntab, hbw1, a1, f1, u1_out, u0_in, f0, u0_out, omega,
+                       (int)n_h, uh_in, uh_out, T, dict_xcd_map(D0));
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 // ---- K-March: two true-Jacobi sweeps of a 3-D 7-point level in ONE pass ---------------------
 // On the finest level of a 3-D hierarchy a sweep streams x, f and the output again (25 B per row),

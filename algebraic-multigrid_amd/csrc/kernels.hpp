@@ -203,6 +203,29 @@ hipError_t launch_dict_pair_down(int64_t n, const DictRef& D, int hb, const doub
 hipError_t launch_dict_pair_up(int64_t n, const DictRef& D, int hb, const double* a,
                                const double* f, double* u_out, double omega, int64_t n_h,
                                const double* uh_in, double* uh_out, hipStream_t st);
+// K-Duo: the pair launches of two consecutive pair levels (0 = l, 1 = l+1, 2 = l+2) as one launch.
+//   down: launch_dict_pair_down of l (a0 = tmp_l), then of l+1 whose first sweep stays on chip;
+//         v2_out = first sweep of level l+2
+//   up:   launch_dict_pair_up of l+1 (a1 = tmp_{l+1}), then of l on u0_in + P u_{l+1} formed on chip;
+//         the result of level l goes to u0_out (not u0_in: neighbouring tiles read its halo)
+// duo_windows_host: the windows of both legs (kernels.hip: the DW_* indices) for tiles of tile_rows
+// rows of level l; 0 when all of them are within the kernels' capacities.
+constexpr int AMG_DUO_WINDOWS_LEN = 31;
+int duo_windows_host(int hb0, int hb1, int tile_rows, int32_t* out);
+// rows the tile `tile` owns on levels l, l+1, l+2 as three half-open ranges, before clipping to the
+// levels' sizes (the kernels' own function); the tile height the launchers use under half-bandwidth hb0
+int duo_owned_host(int tile, int tile_rows, int32_t* out);
+int duo_tile_rows(int hb0);
+bool dict_duo_ok(int64_t n0, const DictRef& D0, int hb0, int64_t n1, const DictRef& D1, int hb1, int64_t n2);
+hipError_t launch_dict_duo_down(int64_t n0, const DictRef& D0, int hb0, int64_t n1, const DictRef& D1, int hb1,
+                                const double* a0, const double* f0, double* u0_out, double* r0_out,
+                                double* f1_out, const double* diag1, double* u1_out, double* r1_out, int64_t n2,
+                                double* f2_out, const double* diag2, double* v2_out, double omega,
+                                hipStream_t st);
+hipError_t launch_dict_duo_up(int64_t n0, const DictRef& D0, int hb0, int64_t n1, const DictRef& D1, int hb1,
+                              const double* a1, const double* f1, double* u1_out, const double* u0_in,
+                              const double* f0, double* u0_out, double omega, int64_t n_h, const double* uh_in,
+                              double* uh_out, hipStream_t st);
 // K-Tail (kernels.hip): the deepest levels of the 2+2 true-Jacobi cycle -- down-legs of levels
 // lt .. L-2, the coarsest solve (K-BandChain operands), up-legs and the prolongation into level
 // lt - 1 -- in ONE launch of one workgroup.

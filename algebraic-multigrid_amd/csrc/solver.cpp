@@ -1641,6 +1641,12 @@ int g_block_lines = [] {
   const char* e = std::getenv("AMG_HIP_BLOCK_LINES");
   return (e && *e == '1') ? 1 : 0;
 }();
+// amg_hip_set_pair_duo / AMG_HIP_PAIR_DUO=0: K-Duo (two consecutive pair levels per launch), read when
+// a solver is created.  Same bits either way.
+int g_pair_duo = [] {
+  const char* e = std::getenv("AMG_HIP_PAIR_DUO");
+  return (e && *e == '0') ? 0 : 1;
+}();
 int64_t g_patch_min_rows = 1000000;  // amg_hip_set_patch_min_rows (level 4 of 4096^2 has 1 048 575 rows)
 
 struct amg_hip_solver {
@@ -1649,6 +1655,11 @@ struct amg_hip_solver {
   int patch_xf = g_patch_xf;                  // likewise
   int patch_tall = g_patch_tall;              // likewise
   int patch_seam = g_patch_seam;              // likewise
+  int pair_duo = g_pair_duo;                  // likewise
+  // K-Duo pairing of the cycle enqueued last (a captured graph keeps what it was captured with): where
+  // the finer level of a duo rests follows what ran, not switches flipped since
+  std::vector<int> duo_last;
+  bool duo_known = false;
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = true;
@@ -1930,6 +1941,47 @@ int tail_from(const amg_hip_solver* s) {
   }
   return -1;
 }
+
+// K-Duo: the pair launches of levels l and l+1 as ONE launch per leg (kernels.hip: dict_duo_*_kernel).
+// Both are pair levels on both legs, neither belongs to K-Tail, both lie on one side of a slab cut,
+// the kernels exist for their row lengths and the windows fit.
+static bool duo_can(const amg_hip_solver* s, int l, int tail_lt) {
+  const int nl = (int)s->lv.size();
+  if (!s->pair_duo || s->opt.no_fusion || s->opt.window || l < 1 || l + 2 >= nl) return false;
+  if (s->slab.levels > 0 && l < s->slab.levels) return false;  // the parts below the cut run level by level
+  if (tail_lt >= 0 && l + 1 >= tail_lt) return false;
+  if (!(pair_level_ok(s, l) && pair_level_ok(s, l + 1) && pair_up_ok(s, l) && pair_up_ok(s, l + 1))) return false;
+  const Level& L0 = s->lv[l];
+  const Level& L1 = s->lv[l + 1];
+  const Level& L2 = s->lv[l + 2];
+  return L1.diag.p && L2.diag.p &&
+         dict_duo_ok(L0.n, L0.A_rows.dict_ref(), L0.A_rows.dict_hb, L1.n, L1.A_rows.dict_ref(), L1.A_rows.dict_hb, L2.n);
+}
+// partner[l] = the other level of l's duo, or -1: greedy from the finest pair level, a leftover
+// single level keeps the pair form
+static std::vector<int> duo_pairing(const amg_hip_solver* s) {
+  const int nl = (int)s->lv.size();
+  std::vector<int> partner((size_t)nl, -1);
+  if (!s->pair_duo || s->opt.host_only) return partner;
+  const int tail_lt = tail_from(s);
+  for (int l = 1; l + 2 < nl;) {
+    if (duo_can(s, l, tail_lt)) {
+      partner[(size_t)l] = l + 1;
+      partner[(size_t)l + 1] = l;
+      l += 2;
+    } else {
+      ++l;
+    }
+  }
+  return partner;
+}
+// the other level of l's duo in the cycle enqueued last (before the first one: in the one that would be)
+int duo_partner(const amg_hip_solver* s, int l) {
+  if (l < 0 || l >= (int)s->lv.size()) return -1;
+  return s->duo_known ? s->duo_last[(size_t)l] : duo_pairing(s)[(size_t)l];
+}
+// the finer level of a duo: both legs of (l, l+1) are one launch each, and u_l rests in tmp
+bool duo_first(const amg_hip_solver* s, int l) { return l >= 1 && duo_partner(s, l) == l + 1; }
 
 // K-March: the two plain Jacobi sweeps u -> tmp -> u of a 3-D 7-point level as ONE launch u -> tmp
 // (kernels.hip: march_kernel); the level's two vectors then trade places.  A level swept this way
@@ -2271,6 +2323,12 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
   bool first_sweep_done = false;  // by the fused residual+restrict kernel of level l-1
   const int tail_lt = (part == CYCLE_ALL || part == CYCLE_SLAB_TAIL) ? tail_from(s) : -1;
   bool tail_done = false;
+  // K-Duo: pairs of pair levels that run as one launch per leg (both levels inside this part)
+  const std::vector<int> duo = (part == CYCLE_ALL || part == CYCLE_SLAB_TAIL) ? duo_pairing(s) : std::vector<int>((size_t)nl, -1);
+  if (part == CYCLE_ALL || part == CYCLE_SLAB_TAIL) {
+    s->duo_last = duo;
+    s->duo_known = true;
+  }
   if (part == CYCLE_SLAB_TAIL) {
     Level& L = s->lv[k];
     if (!patch_xf_pair(s, k - 1)) {  // (a K-Patch level below the cut forms that sweep itself)
@@ -2407,6 +2465,24 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
       s->acct(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
       tail_done = true;
       break;
+    }
+    if (first_sweep_done && duo[(size_t)l] == l + 1) {  // the two launches below of levels l and l+1 in one
+      Level& L = s->lv[l];
+      Level& C = s->lv[l + 1];
+      Level& CC = s->lv[l + 2];
+      const DevMat& A = L.A_rows;
+      const DevMat& AC = C.A_rows;
+      const bool keep = s->opt.keep_residual != 0;
+      HIP_TRY(launch_dict_duo_down(A.n_rows, A.dict_ref(), A.dict_hb, AC.n_rows, AC.dict_ref(), AC.dict_hb,
+                                   L.tmp.as<double>(), L.f.as<double>(), L.u.as<double>(),
+                                   keep ? L.r.as<double>() : nullptr, C.f.as<double>(), C.diag.as<double>(),
+                                   C.u.as<double>(), keep ? C.r.as<double>() : nullptr, CC.n, CC.f.as<double>(),
+                                   CC.diag.as<double>(), CC.tmp.as<double>(), s->opt.omega, st));
+      // what the pair launches of the two levels would have moved
+      s->acct(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (keep ? 8.0 * L.n : 0.0));
+      s->acct(mat_bytes(AC) + 24.0 * C.n + 24.0 * CC.n + (keep ? 8.0 * C.n : 0.0));
+      ++l;  // level l+1 is done; first_sweep_done stays true for level l+2
+      continue;
     }
     if (first_sweep_done && pair_level_ok(s, l)) {  // second pre-sweep + residual + restriction
       Level& L = s->lv[l];
@@ -2575,6 +2651,21 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
                          P.rowptr(), P.col(), P.v(), C.u.as<double>(), L.u.as<double>(),
                          L.u.as<double>(), 1.0, 0, st));
       s->acct(12.0 * P.nnz + 4.0 * L.n + 8.0 * C.n + 16.0 * L.n);
+    }
+    if (l >= 2 && duo[(size_t)l] == l - 1) {  // :300 of levels l and l-1 and the prolongations between and after them: one launch
+      Level& F = s->lv[l - 1];
+      Level& FF = s->lv[l - 2];
+      const DevMat& A = L.A_cols();
+      const DevMat& AF = F.A_cols();
+      HIP_TRY(launch_dict_duo_up(AF.n_rows, AF.dict_ref(), AF.dict_hb, A.n_rows, A.dict_ref(), A.dict_hb,
+                                 L.tmp.as<double>(), L.f.as<double>(), L.u.as<double>(), F.u.as<double>(),
+                                 F.f.as<double>(), F.tmp.as<double>(), s->opt.omega, FF.n, FF.u.as<double>(),
+                                 up_target(l - 2), st));
+      // what the pair launches of the two levels would have moved
+      s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
+      s->acct(mat_bytes(AF) + 24.0 * F.n + 16.0 * FF.n);
+      --l;  // level l-1 is done: its solution rests in tmp (pick_vec)
+      continue;
     }
     if (pair_up_ok(s, l)) {                                        // :300, both sweeps
       Level& F = s->lv[l - 1];
@@ -4667,6 +4758,16 @@ void amg_hip_set_patch_tall(int32_t on) { g_patch_tall = on ? 1 : 0; }
 void amg_hip_set_patch_seam(int32_t on) { g_patch_seam = on ? 1 : 0; }
 void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
+void amg_hip_set_pair_duo(int32_t on) { g_pair_duo = on ? 1 : 0; }
+int32_t amg_hip_pair_duo_partner(const amg_hip_solver* s, int32_t level) {
+  if (!s || level < 0 || level >= (int32_t)s->lv.size()) return -1;
+  return duo_partner(s, level);
+}
+int32_t amg_hip_duo_windows(int32_t hb_l, int32_t hb_l1, int32_t tile_rows, int32_t* out) {
+  return duo_windows_host(hb_l, hb_l1, tile_rows, out);
+}
+int32_t amg_hip_duo_owned(int32_t tile, int32_t tile_rows, int32_t* out) { return duo_owned_host(tile, tile_rows, out); }
+int32_t amg_hip_duo_tile_rows(int32_t hb_l) { return hb_l < 0 ? -1 : duo_tile_rows(hb_l); }
 void amg_hip_set_periodic_device_setup(int32_t on) { g_periodic_device_setup = on ? 1 : 0; }
 void amg_hip_set_f32_lines(int32_t on) { g_f32_lines = on ? 1 : 0; }
 void amg_hip_set_f32_dict(int32_t on) { g_f32_dict = on ? 1 : 0; }
@@ -5379,12 +5480,41 @@ amg_hip_status amg_hip_get_stream(amg_hip_solver* s, void** stream) {
   return AMG_HIP_OK;
 }
 
+// Where a level's vector lives for the device-side accessors and the level operations: as for
+// amg_hip_get_vec, the solution of the finer level of a K-Duo pair rests in its second buffer.
+static void* dev_vec(amg_hip_solver* s, int32_t level, int32_t which) {
+  Level& L = s->lv[level];
+  if (which == 0) return (duo_first(s, level) ? L.tmp : L.u).p;
+  return which == 1 ? L.f.p : L.r.p;
+}
+// For the length of one level operation such a level trades its two buffers, so that the operation
+// reads the solution where set_vec put it and leaves it where get_vec looks for it.
+struct DuoView {
+  Level* lv[2] = {nullptr, nullptr};
+  DuoView(amg_hip_solver* s, int level) {
+    const int nl = (int)s->lv.size();
+    bool on[2];
+    for (int q = 0; q < 2; ++q) on[q] = level + q < nl && duo_first(s, level + q);  // asked before any trade
+    for (int q = 0; q < 2; ++q)
+      if (on[q]) {
+        lv[q] = &s->lv[level + q];
+        std::swap(lv[q]->u, lv[q]->tmp);
+      }
+  }
+  ~DuoView() {
+    for (Level* L : lv)
+      if (L) std::swap(L->u, L->tmp);
+  }
+  DuoView(const DuoView&) = delete;
+  DuoView& operator=(const DuoView&) = delete;
+};
+
 amg_hip_status amg_hip_vec_dev_ptr(amg_hip_solver* s, int32_t level, int32_t which, void** ptr, int64_t* n) {
   if (!s || !ptr || level < 0 || level >= (int32_t)s->lv.size() || which < 0 || which > 2)
     return fail(AMG_HIP_EINVAL, "bad argument");
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "solver was created with host_only = 1: no device state");
   Level& L = s->lv[level];
-  *ptr = which == 0 ? L.u.p : (which == 1 ? L.f.p : L.r.p);
+  *ptr = dev_vec(s, level, which);
   if (n) *n = L.n;
   return AMG_HIP_OK;
 }
@@ -5404,7 +5534,7 @@ amg_hip_status amg_hip_copy_vec_dev(amg_hip_solver* s, int32_t level, int32_t wh
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
   Level& L = s->lv[level];
-  void* v = which == 0 ? L.u.p : (which == 1 ? L.f.p : L.r.p);
+  void* v = dev_vec(s, level, which);
   if (to_solver)
     HIP_TRY(hipMemcpyAsync(v, dev_ptr, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream));
   else
@@ -5418,7 +5548,7 @@ amg_hip_status amg_hip_zero_vec(amg_hip_solver* s, int32_t level, int32_t which)
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
   Level& L = s->lv[level];
-  void* v = which == 0 ? L.u.p : (which == 1 ? L.f.p : L.r.p);
+  void* v = dev_vec(s, level, which);
   HIP_TRY(hipMemsetAsync(v, 0, sizeof(double) * L.n, s->stream));
   return AMG_HIP_OK;
 }
@@ -5431,6 +5561,7 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
   if (r != AMG_HIP_OK) return r;
   hipStream_t st = s->stream;
   Level& L = s->lv[level];
+  const DuoView view(s, level);  // this level and the coarser one, where their solution rests in tmp
   switch (op) {
     case 0: return enqueue_smooth(s, level, 0);
     case 1: return enqueue_residual(s, level);
@@ -5917,6 +6048,8 @@ static DevMem* pick_vec(amg_hip_solver* s, int32_t level, int32_t which) {
   Level& L = s->lv[level];
   // a coarse K-Patch level leaves its solution in the second buffer (its up-leg cannot run in place)
   if (which == 0 && level >= 1 && !s->opt.host_only && patch_level_ok(s, level)) return &L.tmp;
+  // so does the finer level of a K-Duo pair (its up-leg reads the halo of u that other tiles own)
+  if (which == 0 && level >= 1 && !s->opt.host_only && duo_first(s, level)) return &L.tmp;
   return which == 0 ? &L.u : (which == 1 ? &L.f : (which == 2 ? &L.r : nullptr));
 }
 amg_hip_status amg_hip_get_vec(amg_hip_solver* s, int32_t level, int32_t which, double* out) {

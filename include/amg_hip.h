@@ -303,6 +303,34 @@ void amg_hip_set_band_chain(int32_t on);
  * launch takes as long as the launches it replaces.                       */
 void amg_hip_set_tail_fusion(int32_t on);
 
+/* K-Duo: two consecutive pair levels (l, l+1) of the 2+2 true-Jacobi cycle run their down-legs as ONE
+ * launch and their up-legs as one, instead of one pair launch per level and leg.  Pairing is greedy
+ * from the finest pair level; a leftover level, a level of K-Tail's range and a pair of levels the
+ * kernels are not built for keep the pair form.  The finer level of a duo rests in its second buffer
+ * after the cycle; amg_hip_get_vec / amg_hip_set_vec follow that.  Process-wide, read when a solver
+ * is created; ON by default (AMG_HIP_PAIR_DUO=0 in the environment turns it off).  Same bits either
+ * way, and amg_hip_cycle_must_move reports what the pair launches would have moved.              */
+void amg_hip_set_pair_duo(int32_t on);
+/* the other level of `level`'s duo, or -1 */
+int32_t amg_hip_pair_duo_partner(const amg_hip_solver* s, int32_t level);
+/* The row windows of a K-Duo tile of `tile_rows` rows (even, at most 510) of a level with
+ * half-bandwidth hb_l over a level with half-bandwidth hb_l1: 31 numbers, (rows before the base, rows)
+ * of the twelve windows -- down-leg: residual, sweep and right-hand side of l+1, residual, sweep and
+ * input of l; up-leg: second sweep, first sweep and input of l+1, second sweep, first sweep and
+ * input of l -- then the capacities of the down-leg's right-hand side of l+1, sweep and input of l and
+ * of the up-leg's first sweep and input of l+1 and of l.  With t0 the tile's first row, level-(l+1)
+ * windows start at ((t0 / 2) & ~1) - before, level-l windows of the down-leg at 2 ((t0 / 2) & ~1) -
+ * before, those of the up-leg at t0 - before.  Returns 0 when every window is within its capacity, 1
+ * otherwise or on a bad argument.  Host only: needs no device.                                    */
+int32_t amg_hip_duo_windows(int32_t hb_l, int32_t hb_l1, int32_t tile_rows, int32_t* out);
+/* What tile number `tile` of a K-Duo launch owns (the kernels' own function): out[0 .. 1] = its rows of
+ * level l, out[2 .. 3] = of level l+1, out[4 .. 5] = of level l+2, each a half-open range before
+ * clipping to the level's size.  A launch runs ceil(n_l / tile_rows) tiles.  Returns 0, or 1 on a bad
+ * argument.  Host only.                                                                          */
+int32_t amg_hip_duo_owned(int32_t tile, int32_t tile_rows, int32_t* out);
+/* rows of level l per tile that the K-Duo launchers use under half-bandwidth hb_l: 254 or 510 */
+int32_t amg_hip_duo_tile_rows(int32_t hb_l);
+
 /* amg_hip_create_tensor_periodic_dev builds its hierarchy on the device (K-TensorGalerkin with the
  * seam) instead of downloading to the host constructor.  Process-wide, read when a solver is created;
  * default 0 (AMG_HIP_PERIODIC_DEVICE_SETUP=1 in the environment turns it on).  The same solver bit
