@@ -1649,6 +1649,48 @@ int g_pair_duo = [] {
 }();
 int64_t g_patch_min_rows = 1000000;  // amg_hip_set_patch_min_rows (level 4 of 4096^2 has 1 048 575 rows)
 
+// The cycle plan ("The cycle plan"): which launch form every level of the
+// double-precision V-cycle takes on each leg, chosen once per enqueue by build_cycle_plan.  The
+// enqueue dispatches on it and the accessors read it; nothing else asks an eligibility predicate.
+enum LegForm : uint8_t {
+  LEG_NONE,        // no launch of its own: the coarsest level (solved, not smoothed) when r is not kept
+  LEG_MC_PATCH,    // multicolour smoother, colour stages as patch launches
+  LEG_MC_STRIP,    // multicolour smoother, a narrow level as one strip launch
+  LEG_PATCH,       // K-Patch: the whole leg in one launch
+  LEG_TAIL_HEAD,   // K-Tail: this level .. L-2, the solve and the way back in one launch
+  LEG_IN_TAIL,     // a level inside that launch
+  LEG_DUO_FINE,    // K-Duo: the finer level of a duo (down-leg: it launches; up-leg: the coarser one does)
+  LEG_DUO_COARSE,  // K-Duo: the coarser level
+  LEG_PAIR,        // two sweeps of a small level in one launch
+  LEG_PLAIN        // enqueue_smooth, then the residual and the restriction
+};
+enum ProlongBy : uint8_t {
+  PROLONG_NONE,           // the coarsest level, or a level inside K-Tail
+  PROLONG_LOADING,        // the level's own up-leg kernel, while it loads
+  PROLONG_COARSER_SWEEP,  // the last sweep of level l+1 (plain, pair, duo or tail launch)
+  PROLONG_SOLVE,          // the launch of the coarsest solve
+  PROLONG_OWN_SMOOTHER,   // the first sweep of its own smoother (opt.fuse_prolong)
+  PROLONG_TRANSFER        // enqueue_prolong_add
+};
+struct LevelPlan {
+  LegForm down = LEG_NONE, up = LEG_NONE;
+  int phase = 0;                       // smoother phase of a plain down-leg: 0, 1 or 3 (enqueue_smooth)
+  bool xf_in = false, xf_out = false;  // K-Patch hand-over: this level / level l+1 forms its first sweep from f
+  bool restrict_fused = false;         // plain down-leg: residual + restriction (+ first coarse sweep) in one launch
+  ProlongBy prolong = PROLONG_NONE;    // who adds P u_{l+1} to this level
+  bool up_tmp = false;                 // ... and where: tmp, else u in place
+  bool march = false;                  // K-March sweeps the level (a plain leg in phase 0 that prolongs nowhere)
+  bool rests_tmp = false;              // the solution rests in tmp after the cycle, else in u
+  bool writes_r = true;                // r is written when keep_residual is 0
+};
+struct CyclePlan {
+  std::vector<LevelPlan> lv;
+  int tail_first = -1;      // the K-Tail head, or -1
+  bool seam = false;        // amg_hip_vcycles(n >= 2) runs the seam sequence
+  bool zero_known = false;  // coarse pre-smoothing starts from u == 0 without reading it
+  int part = 0;
+};
+
 struct amg_hip_solver {
   amg_hip_options opt;
   int64_t patch_min_rows = g_patch_min_rows;  // the process-wide value when the solver was made
@@ -1656,10 +1698,10 @@ struct amg_hip_solver {
   int patch_tall = g_patch_tall;              // likewise
   int patch_seam = g_patch_seam;              // likewise
   int pair_duo = g_pair_duo;                  // likewise
-  // K-Duo pairing of the cycle enqueued last (a captured graph keeps what it was captured with): where
-  // the finer level of a duo rests follows what ran, not switches flipped since
-  std::vector<int> duo_last;
-  bool duo_known = false;
+  // the plan of the whole cycle (or slab tail) enqueued last (a captured graph keeps what it was
+  // captured with): where a level rests follows what ran, not switches flipped since
+  CyclePlan plan;
+  bool plan_kept = false;
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = true;
@@ -1775,13 +1817,16 @@ bool fuses_resid_restrict(const amg_hip_solver* s, int l) {
 bool patch_level_ok(const amg_hip_solver* s, int l) {
   // needs a smoothed coarser level (a window's last level is one: it is smoothed by the tail solver)
   if (l < 0 || l + (s->opt.window ? 1 : 2) >= (int)s->lv.size()) return false;
-  const Level& L = s->lv[l];
-  const DevMat& A = L.A_rows;
-  if (!(jacobi_fuses_zero(s) && !s->opt.fuse_prolong && s->opt.smoother_iters == 2 && L.symmetric &&
-        A.dict && A.dict_shift == 0 && A.patch && L.linear && s->opt.stencil_transfers &&
-        L.n >= s->patch_min_rows && s->lv[l + 1].diag.p != nullptr))
+  if (!(jacobi_fuses_zero(s) && !s->opt.fuse_prolong && s->opt.smoother_iters == 2 && s->opt.stencil_transfers))
     return false;
-  return l == 0 || patch_level_ok(s, l - 1);
+  for (int q = 0; q <= l; ++q) {  // this level and every finer one
+    const Level& L = s->lv[q];
+    const DevMat& A = L.A_rows;
+    if (!(L.symmetric && A.dict && A.dict_shift == 0 && A.patch && L.linear && L.n >= s->patch_min_rows &&
+          s->lv[q + 1].diag.p != nullptr))
+      return false;
+  }
+  return true;
 }
 // Halo rings of a K-Patch Jacobi leg of this solver (first_down: the level-0 down-leg): the geometry of
 // the launch AND of the flag arrays handed to it (DevMat::patch_ref).  Tall legs off: the three-ring
@@ -1943,13 +1988,14 @@ int tail_from(const amg_hip_solver* s) {
 }
 
 // K-Duo: the pair launches of levels l and l+1 as ONE launch per leg (kernels.hip: dict_duo_*_kernel).
-// Both are pair levels on both legs, neither belongs to K-Tail, both lie on one side of a slab cut,
+// Both are pair levels on both legs, neither is a K-Patch level or belongs to K-Tail, both lie on one side of a slab cut,
 // the kernels exist for their row lengths and the windows fit.
 static bool duo_can(const amg_hip_solver* s, int l, int tail_lt) {
   const int nl = (int)s->lv.size();
   if (!s->pair_duo || s->opt.no_fusion || s->opt.window || l < 1 || l + 2 >= nl) return false;
   if (s->slab.levels > 0 && l < s->slab.levels) return false;  // the parts below the cut run level by level
   if (tail_lt >= 0 && l + 1 >= tail_lt) return false;
+  if (patch_level_ok(s, l)) return false;  // K-Patch comes first (a K-Patch level l+1 makes l one too)
   if (!(pair_level_ok(s, l) && pair_level_ok(s, l + 1) && pair_up_ok(s, l) && pair_up_ok(s, l + 1))) return false;
   const Level& L0 = s->lv[l];
   const Level& L1 = s->lv[l + 1];
@@ -1959,11 +2005,10 @@ static bool duo_can(const amg_hip_solver* s, int l, int tail_lt) {
 }
 // partner[l] = the other level of l's duo, or -1: greedy from the finest pair level, a leftover
 // single level keeps the pair form
-static std::vector<int> duo_pairing(const amg_hip_solver* s) {
+static std::vector<int> duo_pairing(const amg_hip_solver* s, int tail_lt) {
   const int nl = (int)s->lv.size();
   std::vector<int> partner((size_t)nl, -1);
-  if (!s->pair_duo || s->opt.host_only) return partner;
-  const int tail_lt = tail_from(s);
+  if (!s->pair_duo) return partner;
   for (int l = 1; l + 2 < nl;) {
     if (duo_can(s, l, tail_lt)) {
       partner[(size_t)l] = l + 1;
@@ -1975,18 +2020,12 @@ static std::vector<int> duo_pairing(const amg_hip_solver* s) {
   }
   return partner;
 }
-// the other level of l's duo in the cycle enqueued last (before the first one: in the one that would be)
-int duo_partner(const amg_hip_solver* s, int l) {
-  if (l < 0 || l >= (int)s->lv.size()) return -1;
-  return s->duo_known ? s->duo_last[(size_t)l] : duo_pairing(s)[(size_t)l];
-}
-// the finer level of a duo: both legs of (l, l+1) are one launch each, and u_l rests in tmp
-bool duo_first(const amg_hip_solver* s, int l) { return l >= 1 && duo_partner(s, l) == l + 1; }
 
 // K-March: the two plain Jacobi sweeps u -> tmp -> u of a 3-D 7-point level as ONE launch u -> tmp
 // (kernels.hip: march_kernel); the level's two vectors then trade places.  A level swept this way
 // on both legs ends the cycle with them where it found them; enqueue_vcycle brings back one that was
-// swept on one leg only.  Eligibility (finish_dict): the 7-point offsets of one interior type, n a
+// swept on one leg only.  Fills the launch's arguments; the plan builder also takes the answer as the
+// level's eligibility (finish_dict): the 7-point offsets of one interior type, n a
 // multiple of the plane, and no row on a line / plane edge coupling across it.
 static bool march_fill(const amg_hip_solver* s, int l, MarchRef* R) {
   const Level& L = s->lv[l];
@@ -2014,8 +2053,10 @@ static bool march_fill(const amg_hip_solver* s, int l, MarchRef* R) {
 // phase 3: the first sweep was already done by the fused kernel of the finer level
 // (result in tmp).  prolong_into >= 0: the last sweep also adds P u_l to that level's u.
 // reverse: the application of the up-leg (AMG_HIP_SM_LINE_ALT runs its directions in descending order).
+// march: the plan sweeps the level with K-March (only inside a whole V-cycle, which sweeps the level
+// twice: a lone smooth() must leave the vectors where a captured graph expects them).
 amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolong_into = -1,
-                              double* prolong_out = nullptr, bool reverse = false) {
+                              double* prolong_out = nullptr, bool reverse = false, bool march = false) {
   Level& L = s->lv[l];
   hipStream_t st = s->stream;
   const int iters = s->opt.smoother_iters;
@@ -2066,7 +2107,7 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
         s->acct(24.0 * L.n);  // diagonal, f, out
         std::swap(a, b);
         it = 1;
-      } else if (phase == 2 && jacobi_fuses_prolong(s, l)) {
+      } else if (phase == 2) {  // (asked for only where the plan has PROLONG_OWN_SMOOTHER)
         Level& C = s->lv[l + 1];
         HIP_TRY(launch_sell_jacobi_prolong(A.n_rows, A.idx16, A.soff.as<int64_t>(),
                                            A.scol.p, A.sval.as<double>(), a,
@@ -2076,17 +2117,14 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
         std::swap(a, b);
         it = 1;
       }
-      if (it == 0 && prolong_into < 0) {
+      if (it == 0 && prolong_into < 0 && march) {  // both sweeps in one pass: u -> tmp, then trade
         MarchRef R;
-        // (only inside a whole V-cycle, which sweeps the level twice: a lone smooth() must leave the
-        // vectors where a captured graph expects them)
-        if (s->acct_part == 0 /* CYCLE_ALL */ && march_fill(s, l, &R)) {  // both sweeps in one pass: u -> tmp, then trade
-          HIP_TRY(launch_march(R, st));
-          s->acct(mat_bytes(A) + 24.0 * L.n);
-          std::swap(L.u, L.tmp);
-          L.march_odd = !L.march_odd;
-          return AMG_HIP_OK;
-        }
+        (void)march_fill(s, l, &R);
+        HIP_TRY(launch_march(R, st));
+        s->acct(mat_bytes(A) + 24.0 * L.n);
+        std::swap(L.u, L.tmp);
+        L.march_odd = !L.march_odd;
+        return AMG_HIP_OK;
       }
       for (; it < iters; ++it) {
         if (prolong_into >= 0 && it == iters - 1) {
@@ -2169,15 +2207,21 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
 // K-Strip: the whole leg of a narrow multicolour level (below the K-Patch pitch) in one launch
 // over strips of rows.  *T_out: rows per strip -- about n / 256 (one wave of workgroups), within
 // what the LDS window leaves after the halo of (stages + 1) half-bandwidths on either side.
-bool mc_strip_ok(const amg_hip_solver* s, int l, int* T_out = nullptr, int* nst_out = nullptr) {
+static bool mc_strip_rows(const amg_hip_solver* s, int l, int* T_out, int* nst_out);
+bool mc_strip_ok(const amg_hip_solver* s, int l) {
   if (l < 0 || l + 1 >= (int)s->lv.size()) return false;
   const Level& L = s->lv[l];
   const DevMat& A = L.A_rows;
-  if (!(s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS && s->opt.smoother_iters >= 1 && !s->opt.no_fusion &&
-        L.symmetric && A.dict && A.dict_typed && A.dict_shift == 0 && L.linear && s->opt.stencil_transfers &&
-        L.mc_color8.p != nullptr && L.n_colors >= 1 && L.n_colors <= 15 && s->lv[l + 1].n >= 1 && L.n >= 2 &&
-        !mc_patch_ok(s, l)))
-    return false;
+  int T = 0, nst = 0;
+  return s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS && s->opt.smoother_iters >= 1 && !s->opt.no_fusion &&
+         L.symmetric && A.dict && A.dict_typed && A.dict_shift == 0 && L.linear && s->opt.stencil_transfers &&
+         L.mc_color8.p != nullptr && L.n_colors >= 1 && L.n_colors <= 15 && s->lv[l + 1].n >= 1 && L.n >= 2 &&
+         !mc_patch_ok(s, l) && mc_strip_rows(s, l, &T, &nst);
+}
+// the strip geometry of a level: rows per strip and colour stages; false where no strip fits
+static bool mc_strip_rows(const amg_hip_solver* s, int l, int* T_out, int* nst_out) {
+  const Level& L = s->lv[l];
+  const DevMat& A = L.A_rows;
   const int nst = 2 * L.n_colors * s->opt.smoother_iters - (2 * s->opt.smoother_iters - 1);  // mc_sequence
   if (nst < 1 || nst > 16) return false;
   const int hbw = (A.dict_hb + 1) & ~1;
@@ -2185,15 +2229,15 @@ bool mc_strip_ok(const amg_hip_solver* s, int l, int* T_out = nullptr, int* nst_
   if (T_max < 256) return false;
   int64_t T = ((L.n + 255) / 256 + 1) & ~(int64_t)1;
   T = std::min<int64_t>(std::max<int64_t>(T, 256), T_max);
-  if (T_out) *T_out = (int)T;
-  if (nst_out) *nst_out = nst;
+  *T_out = (int)T;
+  *nst_out = nst;
   return true;
 }
 static StripRef mc_strip_ref(amg_hip_solver* s, int l) {
   Level& L = s->lv[l];
   StripRef R;
   int T = 0, nst = 0;
-  (void)mc_strip_ok(s, l, &T, &nst);
+  (void)mc_strip_rows(s, l, &T, &nst);
   const std::vector<int> q = mc_sequence(L.n_colors, s->opt.smoother_iters);
   R.n = (int)L.n;
   R.nH = (int)s->lv[l + 1].n;
@@ -2205,6 +2249,129 @@ static StripRef mc_strip_ref(amg_hip_solver* s, int l) {
   R.f = L.f.as<double>();
   return R;
 }
+
+// ---- the cycle plan -----------------------------------------------------------
+// part: the whole cycle, or one of the three pieces a slab-sharded cycle is cut into at its two
+// exchange points (struct Slab): the down-legs of the slab levels over this rank's lines, the
+// replicated rest below them (it begins by redoing the from-zero sweep of its first level on the
+// gathered right-hand side, unless that level is a K-Patch level that forms the sweep itself: the
+// hand-over), the up-legs of the slab levels.
+enum { CYCLE_ALL = 0, CYCLE_SLAB_DOWN = 1, CYCLE_SLAB_TAIL = 2, CYCLE_SLAB_UP = 3 };
+
+// The ONE place that chooses launch forms: a pure host function of the solver's state (the
+// process-wide switches as they stand now included) and the part.  It walks the levels once down and
+// once up, in priority order (first match): multicolour patch, multicolour strip, K-Patch, K-Tail,
+// K-Duo, pair, plain.  Every level gets an entry whatever the part; the enqueue walks the part's range.
+CyclePlan build_cycle_plan(const amg_hip_solver* s, int part) {
+  const int nl = (int)s->lv.size();
+  CyclePlan P;
+  P.lv.resize((size_t)nl);
+  P.part = part;
+  if (s->opt.host_only) return P;  // no device cycle: nothing fused, everything rests in u
+  const bool whole = part == CYCLE_ALL || part == CYCLE_SLAB_TAIL;
+  const int k = s->slab.levels;
+  const bool keep = s->opt.keep_residual != 0;
+  P.zero_known = jacobi_fuses_zero(s);
+  P.seam = patch_seam_ok(s);
+  // K-Tail and K-Duo only where both levels lie inside the part
+  const int tail_lt = whole ? tail_from(s) : -1;
+  const std::vector<int> duo = whole ? duo_pairing(s, tail_lt) : std::vector<int>((size_t)nl, -1);
+  // K-March only in the stand-alone whole cycle, which sweeps a level on both legs
+  const bool march_cycle = part == CYCLE_ALL && s->seam_piece == SEAM_OFF;
+  for (int l = 0; l < nl; ++l) {
+    LevelPlan& Q = P.lv[(size_t)l];
+    MarchRef R;
+    Q.march = march_cycle && march_fill(s, l, &R);
+    Q.up_tmp = pair_up_ok(s, l);
+    Q.writes_r = !(fuses_resid_restrict(s, l) || patch_level_ok(s, l) || mc_patch_ok(s, l) || mc_strip_ok(s, l) ||
+                   (l == nl - 1 && l > 0));
+  }
+  // down: first_sweep_done = the launch of the finer level also did this level's first sweep (into tmp)
+  bool first_sweep_done = false;
+  for (int l = 0; l < nl; ++l) {
+    LevelPlan& Q = P.lv[(size_t)l];
+    if (part == CYCLE_SLAB_TAIL && l == k) first_sweep_done = true;  // redone on the gathered right-hand side
+    // On the coarsest level the reference smooths and forms the residual, then overwrites
+    // u with the direct solve of the level's rhs (multigrid.hpp:268-274, :287-288): unless
+    // the residual is to be kept, neither has an observable effect.
+    if (l == nl - 1 && nl > 1 && !keep) break;
+    if (mc_patch_ok(s, l) || mc_strip_ok(s, l)) {
+      Q.down = mc_patch_ok(s, l) ? LEG_MC_PATCH : LEG_MC_STRIP;
+      first_sweep_done = false;
+    } else if (patch_level_ok(s, l)) {
+      Q.down = LEG_PATCH;
+      Q.xf_in = l >= 1 && patch_xf_pair(s, l - 1);
+      Q.xf_out = patch_xf_pair(s, l);
+      first_sweep_done = true;
+    } else if (first_sweep_done && l == tail_lt) {
+      for (int q = l; q < nl; ++q) P.lv[(size_t)q].down = P.lv[(size_t)q].up = LEG_IN_TAIL;
+      Q.down = LEG_TAIL_HEAD;
+      P.tail_first = l;
+      break;
+    } else if (first_sweep_done && duo[(size_t)l] == l + 1) {
+      Q.down = LEG_DUO_FINE;
+      P.lv[(size_t)++l].down = LEG_DUO_COARSE;  // first_sweep_done stays true for level l+2
+    } else if (first_sweep_done && pair_level_ok(s, l)) {
+      Q.down = LEG_PAIR;  // first_sweep_done stays true for level l+1
+    } else {
+      Q.down = LEG_PLAIN;
+      Q.phase = first_sweep_done ? 3 : (l >= 1 && P.zero_known) ? 1 : 0;
+      Q.restrict_fused = fuses_resid_restrict(s, l);
+      first_sweep_done = Q.restrict_fused && P.zero_known;
+    }
+  }
+  // up.  The coarsest solve prolongs into level L-2 (one launch less) where no other launch does
+  const int lp = nl - 2;
+  const bool solve_prolongs =
+      P.tail_first < 0 && lp >= 0 && s->coarse.kind == COARSE_CHAIN && !s->opt.no_fusion && s->lv[lp].linear &&
+      s->opt.stencil_transfers && !mc_patch_ok(s, lp) && !mc_strip_ok(s, lp) && !patch_level_ok(s, lp) &&
+      !jacobi_fuses_prolong(s, lp) && !fuses_jacobi_prolong(s, lp) &&
+      (part == CYCLE_ALL || (part == CYCLE_SLAB_TAIL && lp >= k));
+  for (int l = P.tail_first >= 0 ? P.tail_first - 1 : nl - 2; l >= 0; --l) {
+    LevelPlan& Q = P.lv[(size_t)l];
+    if (mc_patch_ok(s, l) || mc_strip_ok(s, l)) {
+      Q.up = mc_patch_ok(s, l) ? LEG_MC_PATCH : LEG_MC_STRIP;
+      Q.prolong = PROLONG_LOADING;
+    } else if (patch_level_ok(s, l)) {
+      // level 0 rests in u (its down-leg wrote tmp); a coarser patch level ends in tmp (its up-leg
+      // cannot run in place)
+      Q.up = LEG_PATCH;
+      Q.prolong = PROLONG_LOADING;
+      Q.rests_tmp = l >= 1;
+    } else if (jacobi_fuses_prolong(s, l)) {
+      Q.up = LEG_PLAIN;
+      Q.prolong = PROLONG_OWN_SMOOTHER;
+    } else {
+      Q.prolong = fuses_jacobi_prolong(s, l) ? PROLONG_COARSER_SWEEP
+                                             : (l == lp && solve_prolongs) ? PROLONG_SOLVE : PROLONG_TRANSFER;
+      if (l >= 2 && duo[(size_t)l] == l - 1) {
+        // the finer level's up-leg reads the halo of u that other tiles own: it ends in tmp
+        Q.up = LEG_DUO_COARSE;
+        LevelPlan& F = P.lv[(size_t)--l];
+        F.up = LEG_DUO_FINE;
+        F.prolong = PROLONG_COARSER_SWEEP;
+        F.rests_tmp = true;
+      } else {
+        Q.up = pair_up_ok(s, l) ? LEG_PAIR : LEG_PLAIN;
+      }
+    }
+  }
+  return P;
+}
+// the plan the accessors answer from: of the cycle enqueued last, before the first one of the cycle
+// that would run
+CyclePlan current_plan(const amg_hip_solver* s) { return s->plan_kept ? s->plan : build_cycle_plan(s, CYCLE_ALL); }
+// where a level's solution rests between cycles
+DevMem& resting(amg_hip_solver* s, const CyclePlan& P, int l) {
+  return P.lv[(size_t)l].rests_tmp ? s->lv[l].tmp : s->lv[l].u;
+}
+// where the prolongation INTO level l lands: a level whose two post-sweeps run as one launch reads
+// u + P u_{l+1} from tmp (its second sweep then writes u; no in-place race between the tiles),
+// every other level takes it in place
+double* up_target(amg_hip_solver* s, const CyclePlan& P, int l) {
+  return (P.lv[(size_t)l].up_tmp ? s->lv[l].tmp : s->lv[l].u).as<double>();
+}
+
 // one symmetric pass: colours 0..nc-1 then nc-1..0; a colour that directly follows itself is not
 // launched again (mc_sequence: the repeat would store the bits already there).  again: the pass
 // follows another pass of the same smoothing call (its colour 0 directly follows colour 0).
@@ -2248,12 +2415,6 @@ amg_hip_status enqueue_residual(amg_hip_solver* s, int l) {
   return AMG_HIP_OK;
 }
 
-// multigrid.hpp:263-305.  part: the whole cycle, or one of the three pieces a slab-sharded
-// cycle is cut into at its two exchange points (struct Slab): the down-legs of the slab levels
-// over this rank's lines, the replicated rest below them (it begins by redoing the from-zero
-// sweep of its first level on the gathered right-hand side, unless that level is a K-Patch level
-// that forms the sweep itself: patch_xf_pair), the up-legs of the slab levels.
-enum { CYCLE_ALL = 0, CYCLE_SLAB_DOWN = 1, CYCLE_SLAB_TAIL = 2, CYCLE_SLAB_UP = 3 };
 // roctx ranges per level and leg, AMG_HIP_ROCTX=1: "L<l> down" / "L<l> up" /
 // "coarse solve" around what is ENQUEUED for them (librocprofiler-sdk-roctx by dlopen; the ranges
 // bracket the launches, so they line up with the kernels in a `rocprofv3 --marker-trace
@@ -2313,30 +2474,339 @@ amg_hip_status enqueue_vcycle(amg_hip_solver* s, int part = CYCLE_ALL) {
   s->acct_part = -1;
   return r;
 }
+// ---- the unfused transfers: linear, tensor, axis or CSR ----------------------------------------
+// f_{l+1} = R r_l (:281-282).  zero_coarse_u: also u_{l+1} = 0 (:278) -- when the smoother starts
+// from "u == 0" without reading u, the fill itself is dead (u_{l+1} is fully overwritten before
+// anyone reads it)
+amg_hip_status enqueue_restrict(amg_hip_solver* s, int l, bool zero_coarse_u) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  hipStream_t st = s->stream;
+  double* uH = zero_coarse_u ? C.u.as<double>() : nullptr;
+  if (L.linear && s->opt.stencil_transfers) {
+    HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(), uH, st));
+    s->acct(8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
+  } else if (L.tensor_stencil) {                               // the same two steps, full coarsening
+    HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(), uH, st));
+    s->acct(8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
+  } else if (L.axis_stencil) {                                 // the same two steps, one axis, weights of A_l
+    HIP_TRY(launch_axis_restrict(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), L.r.as<double>(),
+                                 C.f.as<double>(), uH, st));
+    s->acct(8.0 * L.n + 16.0 * (L.n - C.n) + (zero_coarse_u ? 16.0 : 8.0) * C.n);
+  } else {
+    if (zero_coarse_u) HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st));  // :278
+    const DevCsr& R = L.R_rows;
+    HIP_TRY(launch_csr(CSR_SPMV, R.n_rows, R.nnz, R.max_block_nnz, R.max_row_nnz,
+                       R.rowptr(), R.col(), R.v(), L.r.as<double>(), nullptr,
+                       C.f.as<double>(), 1.0, 0, st));
+    s->acct(12.0 * R.nnz + 4.0 * C.n + 8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
+  }
+  return AMG_HIP_OK;
+}
+// out = u_l + P u_{l+1} (:294-296); out is u_l itself, or (linear transfers only) the level's tmp
+amg_hip_status enqueue_prolong_add(amg_hip_solver* s, int l, double* out) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  hipStream_t st = s->stream;
+  if (L.linear && s->opt.stencil_transfers) {
+    if (out != L.u.as<double>())
+      HIP_TRY(launch_linear_prolong_to(L.n, C.n, C.u.as<double>(), L.u.as<double>(), out, st));
+    else
+      HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
+    s->acct(8.0 * C.n + 16.0 * L.n);
+  } else if (L.tensor_stencil) {
+    HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
+    s->acct(8.0 * C.n + 16.0 * L.n);
+  } else if (L.axis_stencil) {
+    HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), C.u.as<double>(),
+                                    L.u.as<double>(), st));
+    s->acct(16.0 * L.n + 16.0 * (L.n - C.n) + 8.0 * C.n);
+  } else {
+    const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
+    HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz,
+                       P.rowptr(), P.col(), P.v(), C.u.as<double>(), L.u.as<double>(),
+                       L.u.as<double>(), 1.0, 0, st));
+    s->acct(12.0 * P.nnz + 4.0 * L.n + 8.0 * C.n + 16.0 * L.n);
+  }
+  return AMG_HIP_OK;
+}
+
+// ---- one function per launch form and leg (multigrid.hpp:263-305) ------------------------------
+// share of a level's lines a ranged (slab, window) K-Patch launch covers
+double patch_range_frac(const Level& L, bool ranged, int64_t lo, int64_t hi) {
+  if (!ranged || hi < 0) return 1.0;
+  const double lines = (double)((L.n + L.A_rows.patch_m - 1) / L.A_rows.patch_m);
+  return std::min(1.0, (double)(hi - lo) / lines);
+}
+// :268 (the colour stages of the symmetric passes) + :272-282
+amg_hip_status down_mc_patch(amg_hip_solver* s, int l) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  const DevMat& A = L.A_rows;
+  int nd = 0;
+  const std::vector<McLaunch> plan = mc_plan(s, l, &nd);
+  for (int q = 0; q < nd; ++q) {
+    const McLaunch& M = plan[(size_t)q];
+    HIP_TRY(launch_patch_rb(false, M.tail, L.n, A.patch_m, A.patch_ref(), M.in, L.f.as<double>(), nullptr, C.n,
+                            M.out, (M.tail && s->opt.keep_residual) ? L.r.as<double>() : nullptr,
+                            M.tail ? C.f.as<double>() : nullptr, M.tail ? C.u.as<double>() : nullptr, M.stages,
+                            (uint32_t)L.mc_ctab, s->stream));
+  }
+  // each launch: row types + x + f + out; the last also f_H, zeroed u_H (and r when kept)
+  s->acct(nd * 25.0 * L.n + 16.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
+  return AMG_HIP_OK;
+}
+// :294-296 + :300 (the colour stages of the symmetric passes)
+amg_hip_status up_mc_patch(amg_hip_solver* s, int l) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  const DevMat& A = L.A_rows;
+  int nd = 0;
+  const std::vector<McLaunch> plan = mc_plan(s, l, &nd);
+  for (size_t q = (size_t)nd; q < plan.size(); ++q) {
+    const McLaunch& M = plan[q];
+    HIP_TRY(launch_patch_rb(M.prolong, false, L.n, A.patch_m, A.patch_ref(), M.in, L.f.as<double>(),
+                            M.prolong ? C.u.as<double>() : nullptr, C.n, M.out, nullptr, nullptr, nullptr,
+                            M.stages, (uint32_t)L.mc_ctab, s->stream));
+  }
+  s->acct((double)(plan.size() - (size_t)nd) * 25.0 * L.n + 8.0 * C.n);
+  return AMG_HIP_OK;
+}
+// :268 + :272-282 of a narrow level, one launch: u -> tmp
+amg_hip_status down_mc_strip(amg_hip_solver* s, int l) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  StripRef R = mc_strip_ref(s, l);
+  R.x = L.u.as<double>();
+  R.u_out = L.tmp.as<double>();
+  R.r_out = s->opt.keep_residual ? L.r.as<double>() : nullptr;
+  R.fH = C.f.as<double>();
+  R.uH_zero = C.u.as<double>();
+  HIP_TRY(launch_mc_strip(false, true, R, L.A_rows.dict_ref(), s->stream));
+  // row types + colours + x + f + out; f_H, zeroed u_H (and r when kept)
+  s->acct(26.0 * L.n + 16.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
+  return AMG_HIP_OK;
+}
+// :294-296 + :300 of a narrow level, one launch: tmp + P u_H -> u
+amg_hip_status up_mc_strip(amg_hip_solver* s, int l) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  StripRef R = mc_strip_ref(s, l);
+  R.x = L.tmp.as<double>();
+  R.u_out = L.u.as<double>();
+  R.uH = C.u.as<double>();
+  HIP_TRY(launch_mc_strip(true, false, R, L.A_rows.dict_ref(), s->stream));
+  s->acct(26.0 * L.n + 8.0 * C.n);
+  return AMG_HIP_OK;
+}
+// :268 (both sweeps) + :272-282 + :268 of l+1, one launch
+amg_hip_status down_patch(amg_hip_solver* s, const CyclePlan& P, int l) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  const DevMat& A = L.A_rows;
+  hipStream_t st = s->stream;
+  if (l == 0 && s->seam_piece == SEAM_CYCLE) {  // up-leg of the last cycle + this down-leg: one launch
+    HIP_TRY(launch_patch_seam(L.n, A.patch_m, A.patch_ref(5), seam_buf(s, s->seam_src), L.f.as<double>(),
+                              C.tmp.as<double>(), C.n, seam_buf(s, 1 - s->seam_src), C.f.as<double>(),
+                              s->opt.omega, st));
+    s->acct(25.0 * L.n + 16.0 * C.n);  // row types + x + f + smoothed u; u_H, f_H
+    return AMG_HIP_OK;
+  }
+  const Slab& sb = s->slab;
+  const bool ranged = P.part == CYCLE_SLAB_DOWN;
+  const bool first = l == 0;  // l >= 1: the first sweep came from level l-1's kernel (in tmp) ...
+  const bool xf_in = P.lv[(size_t)l].xf_in;    // ... or is formed from f here
+  const bool xf_out = P.lv[(size_t)l].xf_out;  // level l+1 forms its own: f_H only
+  HIP_TRY(launch_patch_down(first, L.n, A.patch_m, A.patch_ref(patch_rings(s, first)),
+                            first ? L.u.as<double>() : (xf_in ? nullptr : L.tmp.as<double>()),
+                            L.f.as<double>(),
+                            first ? (s->seam_piece == SEAM_HEAD ? seam_buf(s, s->seam_src) : L.tmp.as<double>())
+                                  : L.u.as<double>(),
+                            s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
+                            C.f.as<double>(), C.diag.as<double>(), xf_out ? nullptr : C.tmp.as<double>(),
+                            s->opt.omega, st, ranged ? sb.down_lo[l] : 0,
+                            ranged ? sb.down_hi[l] : -1, xf_in));
+  // row types + [x +] f + smoothed u; f_H [, first coarse sweep, coarse diagonal]
+  // (the coarse diagonal is not read under the tiles that take it as an argument)
+  s->acct(patch_range_frac(L, ranged, ranged ? sb.down_lo[l] : 0, ranged ? sb.down_hi[l] : -1) *
+          ((xf_in ? 17.0 : 25.0) * L.n + (xf_out ? 8.0 : 24.0 - 8.0 * A.patch_cfrac) * C.n +
+           (s->opt.keep_residual ? 8.0 * L.n : 0.0)));
+  return AMG_HIP_OK;
+}
+// :294-296 + :300 (both sweeps), one launch
+amg_hip_status up_patch(amg_hip_solver* s, const CyclePlan& P, int l) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  const DevMat& A = L.A_rows;
+  const Slab& sb = s->slab;
+  const bool ranged = P.part == CYCLE_SLAB_UP;
+  const bool top = l == 0;  // level 0 rests in u (its down-leg wrote tmp); coarser patch levels end in tmp
+  HIP_TRY(launch_patch_up(L.n, A.patch_m, A.patch_ref(patch_rings(s, false)),
+                          top ? L.tmp.as<double>() : L.u.as<double>(), L.f.as<double>(),
+                          resting(s, P, l + 1).as<double>(), C.n,
+                          top ? L.u.as<double>() : L.tmp.as<double>(), s->opt.omega, s->stream,
+                          ranged ? sb.up_lo[l] : 0, ranged ? sb.up_hi[l] : -1));
+  // row types + x + f + out; u_H
+  s->acct(patch_range_frac(L, ranged, ranged ? sb.up_lo[l] : 0, ranged ? sb.up_hi[l] : -1) * (25.0 * L.n + 8.0 * C.n));
+  return AMG_HIP_OK;
+}
+// K-Tail: levels l .. L-2, the solve and the way back: ONE launch
+amg_hip_status enqueue_tail(amg_hip_solver* s, const CyclePlan& P, int l) {
+  const int nl = (int)s->lv.size();
+  TailRef T;
+  std::memset(&T, 0, sizeof(T));
+  T.nlev = nl - 1 - l;
+  for (int q = 0; q < T.nlev; ++q) {
+    Level& Q = s->lv[l + q];
+    const DictRef D = Q.A_rows.dict_ref();
+    TailLevelRef& R = T.L[q];
+    R.n = (int)Q.n;
+    R.hbw = (Q.A_rows.dict_hb + 1) & ~1;
+    R.words = D.words;
+    R.ntab = D.ntab;
+    R.rtype = D.rtype;
+    R.rwords = D.rwords;
+    R.doff = D.doff;
+    R.dval = D.dval;
+    R.f = Q.f.as<double>();
+    R.u = Q.u.as<double>();
+    R.tmp = Q.tmp.as<double>();
+    R.diag = Q.diag.as<double>();
+  }
+  Level& C = s->lv[nl - 1];
+  T.nc = (int)C.n;
+  T.wc = (int)s->coarse.w;
+  T.cf = s->coarse.sf.as<double>();
+  T.cb = s->coarse.sb.as<double>();
+  T.dg = s->coarse.d.as<double>();
+  T.fc = C.f.as<double>();
+  T.uc = C.u.as<double>();
+  T.tmpc = C.tmp.as<double>();
+  T.diagc = C.diag.as<double>();
+  Level& F = s->lv[l - 1];
+  T.n_fine = (int)F.n;
+  T.uf_in = F.u.as<double>();
+  T.uf_out = up_target(s, P, l - 1);
+  T.omega = s->opt.omega;
+  HIP_TRY(launch_tail(T, s->stream));
+  for (int q = 0; q < T.nlev; ++q) {  // what the pair kernels of these levels would have moved
+    const Level& Q = s->lv[l + q];
+    const double nH = (double)s->lv[l + q + 1].n, nF = (double)s->lv[l + q - 1].n;
+    s->acct(2.0 * (mat_bytes(Q.A_rows) + 24.0 * Q.n) + 24.0 * nH + 16.0 * nF);
+  }
+  s->acct(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
+  return AMG_HIP_OK;
+}
+// K-Duo, down: the pair launches of levels l and l+1 in one
+amg_hip_status down_duo(amg_hip_solver* s, int l) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  Level& CC = s->lv[l + 2];
+  const DevMat& A = L.A_rows;
+  const DevMat& AC = C.A_rows;
+  const bool keep = s->opt.keep_residual != 0;
+  HIP_TRY(launch_dict_duo_down(A.n_rows, A.dict_ref(), A.dict_hb, AC.n_rows, AC.dict_ref(), AC.dict_hb,
+                               L.tmp.as<double>(), L.f.as<double>(), L.u.as<double>(),
+                               keep ? L.r.as<double>() : nullptr, C.f.as<double>(), C.diag.as<double>(),
+                               C.u.as<double>(), keep ? C.r.as<double>() : nullptr, CC.n, CC.f.as<double>(),
+                               CC.diag.as<double>(), CC.tmp.as<double>(), s->opt.omega, s->stream));
+  // what the pair launches of the two levels would have moved
+  s->acct(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (keep ? 8.0 * L.n : 0.0));
+  s->acct(mat_bytes(AC) + 24.0 * C.n + 24.0 * CC.n + (keep ? 8.0 * C.n : 0.0));
+  return AMG_HIP_OK;
+}
+// K-Duo, up (l: the coarser level): :300 of levels l and l-1 and the prolongations between and after
+// them in one launch; level l-1 ends in tmp
+amg_hip_status up_duo(amg_hip_solver* s, const CyclePlan& P, int l) {
+  Level& L = s->lv[l];
+  Level& F = s->lv[l - 1];
+  Level& FF = s->lv[l - 2];
+  const DevMat& A = L.A_cols();
+  const DevMat& AF = F.A_cols();
+  HIP_TRY(launch_dict_duo_up(AF.n_rows, AF.dict_ref(), AF.dict_hb, A.n_rows, A.dict_ref(), A.dict_hb,
+                             L.tmp.as<double>(), L.f.as<double>(), L.u.as<double>(), F.u.as<double>(),
+                             F.f.as<double>(), F.tmp.as<double>(), s->opt.omega, FF.n, FF.u.as<double>(),
+                             up_target(s, P, l - 2), s->stream));
+  // what the pair launches of the two levels would have moved
+  s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
+  s->acct(mat_bytes(AF) + 24.0 * F.n + 16.0 * FF.n);
+  return AMG_HIP_OK;
+}
+// second pre-sweep + residual + restriction + :268 of l+1
+amg_hip_status down_pair(amg_hip_solver* s, int l) {
+  Level& L = s->lv[l];
+  Level& C = s->lv[l + 1];
+  const DevMat& A = L.A_rows;
+  HIP_TRY(launch_dict_pair_down(A.n_rows, A.dict_ref(), A.dict_hb, L.tmp.as<double>(),
+                                L.f.as<double>(), L.u.as<double>(),
+                                s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
+                                C.f.as<double>(), C.diag.as<double>(), C.tmp.as<double>(),
+                                s->opt.omega, s->stream));
+  s->acct(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
+  return AMG_HIP_OK;
+}
+// :300, both sweeps; the second prolongs into level l-1
+amg_hip_status up_pair(amg_hip_solver* s, const CyclePlan& P, int l) {
+  Level& L = s->lv[l];
+  Level& F = s->lv[l - 1];
+  const DevMat& A = L.A_cols();
+  HIP_TRY(launch_dict_pair_up(A.n_rows, A.dict_ref(), A.dict_hb, L.tmp.as<double>(),
+                              L.f.as<double>(), L.u.as<double>(), s->opt.omega, F.n,
+                              F.u.as<double>(), up_target(s, P, l - 1), s->stream));
+  s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
+  return AMG_HIP_OK;
+}
+// :268, then :272-282 (+ :268 of l+1 when fused)
+amg_hip_status down_plain(amg_hip_solver* s, const CyclePlan& P, int l) {
+  const LevelPlan& Q = P.lv[(size_t)l];
+  AMG_TRY(enqueue_smooth(s, l, Q.phase, -1, nullptr, false, Q.march));  // :268
+  if (Q.restrict_fused) {                                                // :272-282 + :268 of l+1
+    Level& L = s->lv[l];
+    Level& C = s->lv[l + 1];
+    const DevMat& A = L.A_rows;
+    const bool zero_known = P.zero_known;
+    HIP_TRY(launch_dict_resid_restrict(A.n_rows, A.dict_ref(), L.u.as<double>(),
+                                       L.f.as<double>(),
+                                       s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
+                                       C.f.as<double>(),
+                                       zero_known ? C.diag.as<double>() : nullptr,
+                                       zero_known ? C.tmp.as<double>() : nullptr,
+                                       C.u.as<double>(), s->opt.omega, s->stream));
+    // matrix, u, f (r when kept); f_H and either the first coarse sweep + diagonal or the zeroed u_H
+    s->acct(mat_bytes(A) + 16.0 * L.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0) +
+            (zero_known ? 24.0 : 16.0) * C.n);
+    return AMG_HIP_OK;
+  }
+  AMG_TRY(enqueue_residual(s, l));                                       // :272-274
+  if (l + 1 != (int)s->lv.size()) AMG_TRY(enqueue_restrict(s, l, !P.zero_known));  // :278 + :281-282
+  return AMG_HIP_OK;
+}
+// :300; the last sweep also prolongs into level l-1 when that fuses
+amg_hip_status up_plain(amg_hip_solver* s, const CyclePlan& P, int l) {
+  const LevelPlan& Q = P.lv[(size_t)l];
+  const int into = (l >= 1 && P.lv[(size_t)l - 1].prolong == PROLONG_COARSER_SWEEP) ? l - 1 : -1;
+  double* out = into >= 0 ? up_target(s, P, into) : nullptr;
+  if (Q.prolong == PROLONG_OWN_SMOOTHER) return enqueue_smooth(s, l, 2, into, out);  // :294-296 inside :300
+  return enqueue_smooth(s, l, 0, into, out, true, Q.march);
+}
+
+// multigrid.hpp:263-305: two loops that dispatch on the plan.  The slab and window ranges (part) and
+// the seam pieces (s->seam_piece) are modes of this enqueue: they choose which levels it walks.
 amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
   const int nl = (int)s->lv.size();
   hipStream_t st = s->stream;
-  const Slab& sb = s->slab;
-  const int k = sb.levels;
+  const int k = s->slab.levels;
   const bool ranged = part == CYCLE_SLAB_DOWN || part == CYCLE_SLAB_UP;
-  const bool zero_known = jacobi_fuses_zero(s);  // coarse pre-smoothing starts from u == 0
-  bool first_sweep_done = false;  // by the fused residual+restrict kernel of level l-1
-  const int tail_lt = (part == CYCLE_ALL || part == CYCLE_SLAB_TAIL) ? tail_from(s) : -1;
-  bool tail_done = false;
-  // K-Duo: pairs of pair levels that run as one launch per leg (both levels inside this part)
-  const std::vector<int> duo = (part == CYCLE_ALL || part == CYCLE_SLAB_TAIL) ? duo_pairing(s) : std::vector<int>((size_t)nl, -1);
-  if (part == CYCLE_ALL || part == CYCLE_SLAB_TAIL) {
-    s->duo_last = duo;
-    s->duo_known = true;
+  const CyclePlan P = build_cycle_plan(s, part);
+  if (!ranged) {
+    s->plan = P;
+    s->plan_kept = true;
   }
-  if (part == CYCLE_SLAB_TAIL) {
+  if (part == CYCLE_SLAB_TAIL && !P.lv[(size_t)k - 1].xf_out) {  // (a K-Patch level below the cut forms that sweep itself)
     Level& L = s->lv[k];
-    if (!patch_xf_pair(s, k - 1)) {  // (a K-Patch level below the cut forms that sweep itself)
-      HIP_TRY(launch_jacobi_from_zero(L.n, L.diag.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
-                                      s->opt.omega, st));
-      s->acct(24.0 * L.n);
-    }
-    first_sweep_done = true;
+    HIP_TRY(launch_jacobi_from_zero(L.n, L.diag.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
+                                    s->opt.omega, st));
+    s->acct(24.0 * L.n);
   }
   // the seam sequence (part == CYCLE_ALL): head = the cycle without the level-0 up-leg, its level-0
   // down-leg writing seam_buf(src); seam cycle = the seam launch from seam_buf(src) into the other
@@ -2345,339 +2815,52 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
   const int down_from = part == CYCLE_SLAB_TAIL ? k : 0;
   const int down_to = part == CYCLE_SLAB_DOWN ? k : ((part == CYCLE_SLAB_UP || piece == SEAM_FINISH) ? 0 : nl);
   for (int l = down_from; l < down_to; ++l) {
+    const LegForm form = P.lv[(size_t)l].down;
+    if (form == LEG_NONE || form == LEG_IN_TAIL || form == LEG_DUO_COARSE) continue;  // no launch of its own
     RoctxRange range("down", l);
-    // On the coarsest level the reference smooths and forms the residual, then overwrites
-    // u with the direct solve of the level's rhs (multigrid.hpp:268-274, :287-288): unless
-    // the residual is to be kept, neither has an observable effect.
-    if (l == nl - 1 && nl > 1 && !s->opt.keep_residual) break;
-    if (mc_patch_ok(s, l)) {  // :268 (the colour stages of the symmetric passes) + :272-282
-      Level& L = s->lv[l];
-      Level& C = s->lv[l + 1];
-      const DevMat& A = L.A_rows;
-      int nd = 0;
-      const std::vector<McLaunch> plan = mc_plan(s, l, &nd);
-      for (int q = 0; q < nd; ++q) {
-        const McLaunch& M = plan[(size_t)q];
-        HIP_TRY(launch_patch_rb(false, M.tail, L.n, A.patch_m, A.patch_ref(), M.in, L.f.as<double>(), nullptr, C.n,
-                                M.out, (M.tail && s->opt.keep_residual) ? L.r.as<double>() : nullptr,
-                                M.tail ? C.f.as<double>() : nullptr, M.tail ? C.u.as<double>() : nullptr, M.stages,
-                                (uint32_t)L.mc_ctab, st));
-      }
-      // each launch: row types + x + f + out; the last also f_H, zeroed u_H (and r when kept)
-      s->acct(nd * 25.0 * L.n + 16.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
-      first_sweep_done = false;
-      continue;
-    }
-    if (mc_strip_ok(s, l)) {  // :268 + :272-282 of a narrow level, one launch: u -> tmp
-      Level& L = s->lv[l];
-      Level& C = s->lv[l + 1];
-      StripRef R = mc_strip_ref(s, l);
-      R.x = L.u.as<double>();
-      R.u_out = L.tmp.as<double>();
-      R.r_out = s->opt.keep_residual ? L.r.as<double>() : nullptr;
-      R.fH = C.f.as<double>();
-      R.uH_zero = C.u.as<double>();
-      HIP_TRY(launch_mc_strip(false, true, R, L.A_rows.dict_ref(), st));
-      // row types + colours + x + f + out; f_H, zeroed u_H (and r when kept)
-      s->acct(26.0 * L.n + 16.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
-      first_sweep_done = false;
-      continue;
-    }
-    if (patch_level_ok(s, l)) {  // :268 (both sweeps) + :272-282 + :268 of l+1, one launch
-      Level& L = s->lv[l];
-      Level& C = s->lv[l + 1];
-      const DevMat& A = L.A_rows;
-      if (l == 0 && piece == SEAM_CYCLE) {  // up-leg of the last cycle + this down-leg: one launch
-        HIP_TRY(launch_patch_seam(L.n, A.patch_m, A.patch_ref(5), seam_buf(s, s->seam_src), L.f.as<double>(),
-                                  C.tmp.as<double>(), C.n, seam_buf(s, 1 - s->seam_src), C.f.as<double>(),
-                                  s->opt.omega, st));
-        s->acct(25.0 * L.n + 16.0 * C.n);  // row types + x + f + smoothed u; u_H, f_H
-        first_sweep_done = true;
-        continue;
-      }
-      const bool first = l == 0;  // l >= 1: the first sweep came from level l-1's kernel (in tmp) ...
-      const bool xf_in = l >= 1 && patch_xf_pair(s, l - 1);  // ... or is formed from f here
-      const bool xf_out = patch_xf_pair(s, l);               // level l+1 forms its own: f_H only
-      HIP_TRY(launch_patch_down(first, L.n, A.patch_m, A.patch_ref(patch_rings(s, first)),
-                                first ? L.u.as<double>() : (xf_in ? nullptr : L.tmp.as<double>()),
-                                L.f.as<double>(),
-                                first ? (piece == SEAM_HEAD ? seam_buf(s, s->seam_src) : L.tmp.as<double>())
-                                      : L.u.as<double>(),
-                                s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
-                                C.f.as<double>(), C.diag.as<double>(), xf_out ? nullptr : C.tmp.as<double>(),
-                                s->opt.omega, st, ranged ? sb.down_lo[l] : 0,
-                                ranged ? sb.down_hi[l] : -1, xf_in));
-      {  // row types + [x +] f + smoothed u; f_H [, first coarse sweep, coarse diagonal]
-        double frac = 1.0;
-        if (ranged && sb.down_hi[l] >= 0) {
-          const double lines = (double)((L.n + A.patch_m - 1) / A.patch_m);
-          frac = std::min(1.0, (double)(sb.down_hi[l] - sb.down_lo[l]) / lines);
-        }
-        // (the coarse diagonal is not read under the tiles that take it as an argument)
-        s->acct(frac * ((xf_in ? 17.0 : 25.0) * L.n + (xf_out ? 8.0 : 24.0 - 8.0 * A.patch_cfrac) * C.n +
-                        (s->opt.keep_residual ? 8.0 * L.n : 0.0)));
-      }
-      first_sweep_done = true;
-      continue;
-    }
-    if (first_sweep_done && l == tail_lt) {  // levels l .. L-2, the solve and the way back: ONE launch
-      TailRef T;
-      std::memset(&T, 0, sizeof(T));
-      T.nlev = nl - 1 - l;
-      for (int q = 0; q < T.nlev; ++q) {
-        Level& Q = s->lv[l + q];
-        const DictRef D = Q.A_rows.dict_ref();
-        TailLevelRef& R = T.L[q];
-        R.n = (int)Q.n;
-        R.hbw = (Q.A_rows.dict_hb + 1) & ~1;
-        R.words = D.words;
-        R.ntab = D.ntab;
-        R.rtype = D.rtype;
-        R.rwords = D.rwords;
-        R.doff = D.doff;
-        R.dval = D.dval;
-        R.f = Q.f.as<double>();
-        R.u = Q.u.as<double>();
-        R.tmp = Q.tmp.as<double>();
-        R.diag = Q.diag.as<double>();
-      }
-      Level& C = s->lv[nl - 1];
-      T.nc = (int)C.n;
-      T.wc = (int)s->coarse.w;
-      T.cf = s->coarse.sf.as<double>();
-      T.cb = s->coarse.sb.as<double>();
-      T.dg = s->coarse.d.as<double>();
-      T.fc = C.f.as<double>();
-      T.uc = C.u.as<double>();
-      T.tmpc = C.tmp.as<double>();
-      T.diagc = C.diag.as<double>();
-      Level& F = s->lv[l - 1];
-      T.n_fine = (int)F.n;
-      T.uf_in = F.u.as<double>();
-      T.uf_out = pair_up_ok(s, l - 1) ? F.tmp.as<double>() : F.u.as<double>();
-      T.omega = s->opt.omega;
-      HIP_TRY(launch_tail(T, st));
-      for (int q = 0; q < T.nlev; ++q) {  // what the pair kernels of these levels would have moved
-        const Level& Q = s->lv[l + q];
-        const double nH = (double)s->lv[l + q + 1].n, nF = (double)s->lv[l + q - 1].n;
-        s->acct(2.0 * (mat_bytes(Q.A_rows) + 24.0 * Q.n) + 24.0 * nH + 16.0 * nF);
-      }
-      s->acct(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
-      tail_done = true;
-      break;
-    }
-    if (first_sweep_done && duo[(size_t)l] == l + 1) {  // the two launches below of levels l and l+1 in one
-      Level& L = s->lv[l];
-      Level& C = s->lv[l + 1];
-      Level& CC = s->lv[l + 2];
-      const DevMat& A = L.A_rows;
-      const DevMat& AC = C.A_rows;
-      const bool keep = s->opt.keep_residual != 0;
-      HIP_TRY(launch_dict_duo_down(A.n_rows, A.dict_ref(), A.dict_hb, AC.n_rows, AC.dict_ref(), AC.dict_hb,
-                                   L.tmp.as<double>(), L.f.as<double>(), L.u.as<double>(),
-                                   keep ? L.r.as<double>() : nullptr, C.f.as<double>(), C.diag.as<double>(),
-                                   C.u.as<double>(), keep ? C.r.as<double>() : nullptr, CC.n, CC.f.as<double>(),
-                                   CC.diag.as<double>(), CC.tmp.as<double>(), s->opt.omega, st));
-      // what the pair launches of the two levels would have moved
-      s->acct(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (keep ? 8.0 * L.n : 0.0));
-      s->acct(mat_bytes(AC) + 24.0 * C.n + 24.0 * CC.n + (keep ? 8.0 * C.n : 0.0));
-      ++l;  // level l+1 is done; first_sweep_done stays true for level l+2
-      continue;
-    }
-    if (first_sweep_done && pair_level_ok(s, l)) {  // second pre-sweep + residual + restriction
-      Level& L = s->lv[l];
-      Level& C = s->lv[l + 1];
-      const DevMat& A = L.A_rows;
-      HIP_TRY(launch_dict_pair_down(A.n_rows, A.dict_ref(), A.dict_hb, L.tmp.as<double>(),
-                                    L.f.as<double>(), L.u.as<double>(),
-                                    s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
-                                    C.f.as<double>(), C.diag.as<double>(), C.tmp.as<double>(),
-                                    s->opt.omega, st));
-      s->acct(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
-      continue;  // first_sweep_done stays true for level l+1
-    }
-    amg_hip_status r =
-        enqueue_smooth(s, l, first_sweep_done ? 3 : (l >= 1 && zero_known) ? 1 : 0);  // :268
-    if (r != AMG_HIP_OK) return r;
-    first_sweep_done = false;
-    if (fuses_resid_restrict(s, l)) {                              // :272-282 + :268 of l+1
-      Level& L = s->lv[l];
-      Level& C = s->lv[l + 1];
-      const DevMat& A = L.A_rows;
-      HIP_TRY(launch_dict_resid_restrict(A.n_rows, A.dict_ref(), L.u.as<double>(),
-                                         L.f.as<double>(),
-                                         s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
-                                         C.f.as<double>(),
-                                         zero_known ? C.diag.as<double>() : nullptr,
-                                         zero_known ? C.tmp.as<double>() : nullptr,
-                                         C.u.as<double>(), s->opt.omega, st));
-      // matrix, u, f (r when kept); f_H and either the first coarse sweep + diagonal or the zeroed u_H
-      s->acct(mat_bytes(A) + 16.0 * L.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0) +
-              (zero_known ? 24.0 : 16.0) * C.n);
-      first_sweep_done = zero_known;
-      continue;
-    }
-    if ((r = enqueue_residual(s, l)) != AMG_HIP_OK) return r;      // :272-274
-    if (l + 1 != nl) {
-      Level& L = s->lv[l];
-      Level& C = s->lv[l + 1];
-      // :278 -- when the smoother starts from "u == 0" without reading u, the
-      // fill itself is dead (u_{l+1} is fully overwritten before anyone reads it)
-      if (L.linear && s->opt.stencil_transfers) {                  // :278 + :281-282
-        HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(),
-                                       zero_known ? nullptr : C.u.as<double>(), st));
-        s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
-      } else if (L.tensor_stencil) {                               // the same two steps, full coarsening
-        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(),
-                                       zero_known ? nullptr : C.u.as<double>(), st));
-        s->acct(8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
-      } else if (L.axis_stencil) {                                 // the same two steps, one axis, weights of A_l
-        HIP_TRY(launch_axis_restrict(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), L.r.as<double>(),
-                                     C.f.as<double>(), zero_known ? nullptr : C.u.as<double>(), st));
-        s->acct(8.0 * L.n + 16.0 * (L.n - C.n) + (zero_known ? 8.0 : 16.0) * C.n);
-      } else {
-        if (!zero_known) HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st)); // :278
-        const DevCsr& R = L.R_rows;
-        HIP_TRY(launch_csr(CSR_SPMV, R.n_rows, R.nnz, R.max_block_nnz, R.max_row_nnz,
-                           R.rowptr(), R.col(), R.v(), L.r.as<double>(), nullptr,
-                           C.f.as<double>(), 1.0, 0, st));
-        s->acct(12.0 * R.nnz + 4.0 * C.n + 8.0 * L.n + (zero_known ? 8.0 : 16.0) * C.n);
-      }
+    switch (form) {
+      case LEG_MC_PATCH: AMG_TRY(down_mc_patch(s, l)); break;
+      case LEG_MC_STRIP: AMG_TRY(down_mc_strip(s, l)); break;
+      case LEG_PATCH: AMG_TRY(down_patch(s, P, l)); break;
+      case LEG_TAIL_HEAD: AMG_TRY(enqueue_tail(s, P, l)); break;
+      case LEG_DUO_FINE: AMG_TRY(down_duo(s, l)); break;
+      case LEG_PAIR: AMG_TRY(down_pair(s, l)); break;
+      default: AMG_TRY(down_plain(s, P, l)); break;
     }
   }
-  // where the prolongation INTO level l lands: a level whose two post-sweeps run as one
-  // launch reads u + P u_{l+1} from tmp (its second sweep then writes u; no in-place race
-  // between the tiles), every other level takes it in place
-  auto up_target = [&](int l) -> double* {
-    return pair_up_ok(s, l) ? s->lv[l].tmp.as<double>() : s->lv[l].u.as<double>();
-  };
-  int prolonged_by_solve = -1;  // level whose :294-296 the coarsest solve's launch did (K-BandChain)
+  const bool tail_done = P.tail_first >= 0 && down_to == nl;
   if (!ranged && !tail_done && piece != SEAM_FINISH) {             // :287-288
     RoctxRange range("coarse solve", -1);
     if (s->opt.window)
       return fail(AMG_HIP_EINVAL, "a window solver (opt.window) runs by parts: amg_hip_window_run");
     Level& C = s->lv[nl - 1];
     const int lp = nl - 2;  // plain stencil prolongation into level L-2: one launch less when fused
-    const bool fuse_p = lp >= 0 && s->coarse.kind == COARSE_CHAIN && !s->opt.no_fusion && s->lv[lp].linear &&
-                        s->opt.stencil_transfers && !mc_patch_ok(s, lp) && !mc_strip_ok(s, lp) &&
-                        !patch_level_ok(s, lp) && !jacobi_fuses_prolong(s, lp) && !fuses_jacobi_prolong(s, lp) &&
-                        (part == CYCLE_ALL || (part == CYCLE_SLAB_TAIL && lp >= k));
-    if (fuse_p) {
+    if (lp >= 0 && P.lv[(size_t)lp].prolong == PROLONG_SOLVE) {
       Level& Lp = s->lv[lp];
       HIP_TRY(launch_coarse(s->coarse, C.f.as<double>(), C.tmp.as<double>(), C.u.as<double>(), st, Lp.n,
-                            Lp.u.as<double>(), up_target(lp)));
+                            Lp.u.as<double>(), up_target(s, P, lp)));
       s->acct(16.0 * Lp.n);
-      prolonged_by_solve = lp;
     } else {
       HIP_TRY(launch_coarse(s->coarse, C.f.as<double>(), C.tmp.as<double>(), C.u.as<double>(), st));
     }
     // banded L D L^T solve: the band of L forwards and backwards, D, f, u
     s->acct(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
   }
-  const int up_from = piece == SEAM_FINISH ? 0 : (part == CYCLE_SLAB_UP ? k - 1 : (part == CYCLE_SLAB_DOWN ? -1 : (tail_done ? tail_lt - 1 : nl - 2)));
+  const int up_from = piece == SEAM_FINISH ? 0 : (part == CYCLE_SLAB_UP ? k - 1 : (part == CYCLE_SLAB_DOWN ? -1 : (tail_done ? P.tail_first - 1 : nl - 2)));
   const int up_to = part == CYCLE_SLAB_TAIL ? k : ((piece == SEAM_HEAD || piece == SEAM_CYCLE) ? 1 : 0);
   for (int l = up_from; l >= up_to; --l) {                         // :291
+    const LevelPlan& Q = P.lv[(size_t)l];
+    if (Q.up == LEG_DUO_FINE) continue;  // done by the launch of level l+1
     RoctxRange range("up", l);
-    Level& L = s->lv[l];
-    Level& C = s->lv[l + 1];
-    if (mc_patch_ok(s, l)) {  // :294-296 + :300 (the colour stages of the symmetric passes)
-      const DevMat& A = L.A_rows;
-      int nd = 0;
-      const std::vector<McLaunch> plan = mc_plan(s, l, &nd);
-      for (size_t q = (size_t)nd; q < plan.size(); ++q) {
-        const McLaunch& M = plan[q];
-        HIP_TRY(launch_patch_rb(M.prolong, false, L.n, A.patch_m, A.patch_ref(), M.in, L.f.as<double>(),
-                                M.prolong ? C.u.as<double>() : nullptr, C.n, M.out, nullptr, nullptr, nullptr,
-                                M.stages, (uint32_t)L.mc_ctab, st));
-      }
-      s->acct((double)(plan.size() - (size_t)nd) * 25.0 * L.n + 8.0 * C.n);
-      continue;
+    if (Q.prolong == PROLONG_TRANSFER) AMG_TRY(enqueue_prolong_add(s, l, up_target(s, P, l)));  // :294-296
+    switch (Q.up) {
+      case LEG_MC_PATCH: AMG_TRY(up_mc_patch(s, l)); break;
+      case LEG_MC_STRIP: AMG_TRY(up_mc_strip(s, l)); break;
+      case LEG_PATCH: AMG_TRY(up_patch(s, P, l)); break;
+      case LEG_DUO_COARSE: AMG_TRY(up_duo(s, P, l)); break;
+      case LEG_PAIR: AMG_TRY(up_pair(s, P, l)); break;
+      default: AMG_TRY(up_plain(s, P, l)); break;
     }
-    if (mc_strip_ok(s, l)) {  // :294-296 + :300 of a narrow level, one launch: tmp + P u_H -> u
-      StripRef R = mc_strip_ref(s, l);
-      R.x = L.tmp.as<double>();
-      R.u_out = L.u.as<double>();
-      R.uH = C.u.as<double>();
-      HIP_TRY(launch_mc_strip(true, false, R, L.A_rows.dict_ref(), st));
-      s->acct(26.0 * L.n + 8.0 * C.n);
-      continue;
-    }
-    if (patch_level_ok(s, l)) {  // :294-296 + :300 (both sweeps), one launch
-      // level 0 rests in u (its down-leg wrote tmp); coarser patch levels end in tmp
-      const DevMat& A = L.A_rows;
-      const bool top = l == 0;
-      const double* uH = patch_level_ok(s, l + 1) ? C.tmp.as<double>() : C.u.as<double>();
-      HIP_TRY(launch_patch_up(L.n, A.patch_m, A.patch_ref(patch_rings(s, false)),
-                              top ? L.tmp.as<double>() : L.u.as<double>(), L.f.as<double>(), uH, C.n,
-                              top ? L.u.as<double>() : L.tmp.as<double>(), s->opt.omega, st,
-                              ranged ? sb.up_lo[l] : 0, ranged ? sb.up_hi[l] : -1));
-      {
-        double frac = 1.0;
-        if (ranged && sb.up_hi[l] >= 0) {
-          const double lines = (double)((L.n + A.patch_m - 1) / A.patch_m);
-          frac = std::min(1.0, (double)(sb.up_hi[l] - sb.up_lo[l]) / lines);
-        }
-        s->acct(frac * (25.0 * L.n + 8.0 * C.n));  // row types + x + f + out; u_H
-      }
-      continue;
-    }
-    // the last sweep of this level also prolongs into level l-1 when that fuses
-    const int into = (l >= 1 && fuses_jacobi_prolong(s, l - 1)) ? l - 1 : -1;
-    if (jacobi_fuses_prolong(s, l)) {                              // :294-296 inside :300
-      amg_hip_status r = enqueue_smooth(s, l, 2, into, into >= 0 ? up_target(into) : nullptr);
-      if (r != AMG_HIP_OK) return r;
-      continue;
-    }
-    if (fuses_jacobi_prolong(s, l)) {
-      // :294-296 was done by the last sweep of level l+1
-    } else if (l == prolonged_by_solve) {
-      // :294-296 was done by the launch of the coarsest solve
-    } else if (L.linear && s->opt.stencil_transfers) {             // :294-296
-      if (up_target(l) != L.u.as<double>())
-        HIP_TRY(launch_linear_prolong_to(L.n, C.n, C.u.as<double>(), L.u.as<double>(), up_target(l), st));
-      else
-        HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
-      s->acct(8.0 * C.n + 16.0 * L.n);
-    } else if (L.tensor_stencil) {
-      HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
-      s->acct(8.0 * C.n + 16.0 * L.n);
-    } else if (L.axis_stencil) {
-      HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), C.u.as<double>(),
-                                      L.u.as<double>(), st));
-      s->acct(16.0 * L.n + 16.0 * (L.n - C.n) + 8.0 * C.n);
-    } else {
-      const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
-      HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz,
-                         P.rowptr(), P.col(), P.v(), C.u.as<double>(), L.u.as<double>(),
-                         L.u.as<double>(), 1.0, 0, st));
-      s->acct(12.0 * P.nnz + 4.0 * L.n + 8.0 * C.n + 16.0 * L.n);
-    }
-    if (l >= 2 && duo[(size_t)l] == l - 1) {  // :300 of levels l and l-1 and the prolongations between and after them: one launch
-      Level& F = s->lv[l - 1];
-      Level& FF = s->lv[l - 2];
-      const DevMat& A = L.A_cols();
-      const DevMat& AF = F.A_cols();
-      HIP_TRY(launch_dict_duo_up(AF.n_rows, AF.dict_ref(), AF.dict_hb, A.n_rows, A.dict_ref(), A.dict_hb,
-                                 L.tmp.as<double>(), L.f.as<double>(), L.u.as<double>(), F.u.as<double>(),
-                                 F.f.as<double>(), F.tmp.as<double>(), s->opt.omega, FF.n, FF.u.as<double>(),
-                                 up_target(l - 2), st));
-      // what the pair launches of the two levels would have moved
-      s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
-      s->acct(mat_bytes(AF) + 24.0 * F.n + 16.0 * FF.n);
-      --l;  // level l-1 is done: its solution rests in tmp (pick_vec)
-      continue;
-    }
-    if (pair_up_ok(s, l)) {                                        // :300, both sweeps
-      Level& F = s->lv[l - 1];
-      const DevMat& A = L.A_cols();
-      HIP_TRY(launch_dict_pair_up(A.n_rows, A.dict_ref(), A.dict_hb, L.tmp.as<double>(),
-                                  L.f.as<double>(), L.u.as<double>(), s->opt.omega, F.n,
-                                  F.u.as<double>(), up_target(l - 1), st));
-      s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
-      continue;
-    }
-    amg_hip_status r = enqueue_smooth(s, l, 0, into, into >= 0 ? up_target(into) : nullptr, true);  // :300
-    if (r != AMG_HIP_OK) return r;
   }
   return AMG_HIP_OK;
 }
@@ -4761,7 +4944,8 @@ void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
 void amg_hip_set_pair_duo(int32_t on) { g_pair_duo = on ? 1 : 0; }
 int32_t amg_hip_pair_duo_partner(const amg_hip_solver* s, int32_t level) {
   if (!s || level < 0 || level >= (int32_t)s->lv.size()) return -1;
-  return duo_partner(s, level);
+  const LegForm up = current_plan(s).lv[(size_t)level].up;
+  return up == LEG_DUO_FINE ? level + 1 : (up == LEG_DUO_COARSE ? level - 1 : -1);
 }
 int32_t amg_hip_duo_windows(int32_t hb_l, int32_t hb_l1, int32_t tile_rows, int32_t* out) {
   return duo_windows_host(hb_l, hb_l1, tile_rows, out);
@@ -5255,7 +5439,7 @@ amg_hip_status amg_hip_vcycles(amg_hip_solver* s, int32_t n) {
   if (!s) return fail(AMG_HIP_EINVAL, "null solver");
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
-  if (n >= 2 && patch_seam_ok(s)) {
+  if (n >= 2 && current_plan(s).seam) {
     // head, n - 1 seam cycles, finish.  The handed-over level-0 vector alternates between tmp and r;
     // the head starts on the buffer that makes the last seam cycle write tmp, where a stand-alone
     // cycle leaves that vector, so the finish is the cycle's own last launch.
@@ -5351,7 +5535,10 @@ amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
   int k = 0;
-  while (patch_level_ok(s, k)) ++k;
+  {
+    const CyclePlan P = current_plan(s);
+    while (k < (int)P.lv.size() && P.lv[(size_t)k].down == LEG_PATCH) ++k;
+  }
   if (max_levels >= 0 && k > max_levels) k = max_levels;
   if (k > AMG_HIP_SLAB_MAX_LEVELS) k = AMG_HIP_SLAB_MAX_LEVELS;
   if (k < 1)
@@ -5361,6 +5548,7 @@ amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world
   HIP_TRY(hipStreamSynchronize(s->stream));
   Slab& sb = s->slab;
   sb.reset_graphs();
+  s->plan_kept = false;
   sb.levels = 0;  // configured again only when everything below succeeds
   const Level& L0 = s->lv[0];
   const int64_t m0 = L0.A_rows.patch_m;
@@ -5436,6 +5624,7 @@ amg_hip_status amg_hip_window_setup(amg_hip_solver* s, const int64_t* down_lo, c
   const int k = (int)s->lv.size() - 1;
   Slab& sb = s->slab;
   sb.reset_graphs();
+  s->plan_kept = false;
   sb.levels = k;
   sb.rank = 0;
   sb.world = 1;
@@ -5480,23 +5669,25 @@ amg_hip_status amg_hip_get_stream(amg_hip_solver* s, void** stream) {
   return AMG_HIP_OK;
 }
 
-// Where a level's vector lives for the device-side accessors and the level operations: as for
-// amg_hip_get_vec, the solution of the finer level of a K-Duo pair rests in its second buffer.
-static void* dev_vec(amg_hip_solver* s, int32_t level, int32_t which) {
+// Where a level's vector lives, for every accessor and the level operations alike: the solution (which
+// == 0) where the plan says it rests -- a coarse K-Patch level and the finer level of a K-Duo pair
+// leave it in their second buffer -- f and r in their own.
+static DevMem* level_vec(amg_hip_solver* s, int32_t level, int32_t which) {
+  if (!s || level < 0 || level >= (int32_t)s->lv.size()) return nullptr;
   Level& L = s->lv[level];
-  if (which == 0) return (duo_first(s, level) ? L.tmp : L.u).p;
-  return which == 1 ? L.f.p : L.r.p;
+  if (which == 0) return &resting(s, current_plan(s), level);
+  return which == 1 ? &L.f : (which == 2 ? &L.r : nullptr);
 }
-// For the length of one level operation such a level trades its two buffers, so that the operation
-// reads the solution where set_vec put it and leaves it where get_vec looks for it.
+// For the length of one level operation a level that rests in tmp (this one, the coarser one) trades
+// its two buffers, so that the operation reads the solution where set_vec put it and leaves it where
+// get_vec looks for it.
 struct DuoView {
   Level* lv[2] = {nullptr, nullptr};
   DuoView(amg_hip_solver* s, int level) {
     const int nl = (int)s->lv.size();
-    bool on[2];
-    for (int q = 0; q < 2; ++q) on[q] = level + q < nl && duo_first(s, level + q);  // asked before any trade
+    const CyclePlan P = current_plan(s);  // asked before any trade
     for (int q = 0; q < 2; ++q)
-      if (on[q]) {
+      if (level + q < nl && P.lv[(size_t)level + q].rests_tmp) {
         lv[q] = &s->lv[level + q];
         std::swap(lv[q]->u, lv[q]->tmp);
       }
@@ -5514,7 +5705,7 @@ amg_hip_status amg_hip_vec_dev_ptr(amg_hip_solver* s, int32_t level, int32_t whi
     return fail(AMG_HIP_EINVAL, "bad argument");
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "solver was created with host_only = 1: no device state");
   Level& L = s->lv[level];
-  *ptr = dev_vec(s, level, which);
+  *ptr = level_vec(s, level, which)->p;
   if (n) *n = L.n;
   return AMG_HIP_OK;
 }
@@ -5534,7 +5725,7 @@ amg_hip_status amg_hip_copy_vec_dev(amg_hip_solver* s, int32_t level, int32_t wh
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
   Level& L = s->lv[level];
-  void* v = dev_vec(s, level, which);
+  void* v = level_vec(s, level, which)->p;
   if (to_solver)
     HIP_TRY(hipMemcpyAsync(v, dev_ptr, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream));
   else
@@ -5548,7 +5739,7 @@ amg_hip_status amg_hip_zero_vec(amg_hip_solver* s, int32_t level, int32_t which)
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
   Level& L = s->lv[level];
-  void* v = dev_vec(s, level, which);
+  void* v = level_vec(s, level, which)->p;
   HIP_TRY(hipMemsetAsync(v, 0, sizeof(double) * L.n, s->stream));
   return AMG_HIP_OK;
 }
@@ -5565,41 +5756,12 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
   switch (op) {
     case 0: return enqueue_smooth(s, level, 0);
     case 1: return enqueue_residual(s, level);
-    case 2: {
+    case 2:
       if (level + 1 >= nl) return fail(AMG_HIP_EINVAL, "no coarser level");
-      Level& C = s->lv[level + 1];
-      if (L.linear && s->opt.stencil_transfers) {
-        HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
-      } else if (L.tensor_stencil) {
-        HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(), C.u.as<double>(), st));
-      } else if (L.axis_stencil) {
-        HIP_TRY(launch_axis_restrict(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), L.r.as<double>(),
-                                     C.f.as<double>(), C.u.as<double>(), st));
-      } else {
-        HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st));
-        const DevCsr& R = L.R_rows;
-        HIP_TRY(launch_csr(CSR_SPMV, R.n_rows, R.nnz, R.max_block_nnz, R.max_row_nnz, R.rowptr(),
-                           R.col(), R.v(), L.r.as<double>(), nullptr, C.f.as<double>(), 1.0, 0, st));
-      }
-      return AMG_HIP_OK;
-    }
-    case 3: {
+      return enqueue_restrict(s, level, true);
+    case 3:
       if (level + 1 >= nl) return fail(AMG_HIP_EINVAL, "no coarser level");
-      Level& C = s->lv[level + 1];
-      if (L.linear && s->opt.stencil_transfers) {
-        HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
-      } else if (L.tensor_stencil) {
-        HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
-      } else if (L.axis_stencil) {
-        HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), C.u.as<double>(),
-                                        L.u.as<double>(), st));
-      } else {
-        const DevCsr& P = L.P_rows;
-        HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz, P.rowptr(),
-                           P.col(), P.v(), C.u.as<double>(), L.u.as<double>(), L.u.as<double>(), 1.0, 0, st));
-      }
-      return AMG_HIP_OK;
-    }
+      return enqueue_prolong_add(s, level, L.u.as<double>());
     case 4:
       if (level != nl - 1) return fail(AMG_HIP_EINVAL, "the direct solve belongs to the coarsest level");
       HIP_TRY(launch_coarse(s->coarse, L.f.as<double>(), L.tmp.as<double>(), L.u.as<double>(), st));
@@ -5821,7 +5983,6 @@ amg_hip_status amg_hip_get_mean_projection(const amg_hip_solver* s, int32_t* on)
   *on = s->project_mean ? 1 : 0;
   return AMG_HIP_OK;
 }
-static DevMem* pick_vec(amg_hip_solver* s, int32_t level, int32_t which);  // with amg_hip_get_vec below
 amg_hip_status amg_hip_center_vec(amg_hip_solver* s, int32_t level, int32_t which) {
   if (!s) return fail(AMG_HIP_EINVAL, "null solver");
   if (level < 0 || level >= (int32_t)s->lv.size()) return fail(AMG_HIP_EINVAL, "level out of range");
@@ -5829,7 +5990,7 @@ amg_hip_status amg_hip_center_vec(amg_hip_solver* s, int32_t level, int32_t whic
     return fail(AMG_HIP_EINVAL, "amg_hip_center_vec: `which` must be 0 (u) or 1 (f), got " + std::to_string(which));
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no vectors");
   HIP_TRY(hipSetDevice(s->device));
-  double* v = pick_vec(s, level, which)->as<double>();
+  double* v = level_vec(s, level, which)->as<double>();
   double* sc = s->scratch.as<double>();
   const int64_t n = s->lv[level].n;
   HIP_TRY(launch_sum(n, v, sc + 1034, sc, 0, s->stream));
@@ -6043,22 +6204,11 @@ amg_hip_status amg_hip_get_transfer(const amg_hip_solver* s, int32_t level, int3
   return AMG_HIP_OK;
 }
 
-static DevMem* pick_vec(amg_hip_solver* s, int32_t level, int32_t which) {
-  if (!s || level < 0 || level >= (int32_t)s->lv.size()) return nullptr;
-  Level& L = s->lv[level];
-  // a coarse K-Patch level leaves its solution in the second buffer (its up-leg cannot run in place)
-  if (which == 0 && level >= 1 && !s->opt.host_only && patch_level_ok(s, level)) return &L.tmp;
-  // so does the finer level of a K-Duo pair (its up-leg reads the halo of u that other tiles own)
-  if (which == 0 && level >= 1 && !s->opt.host_only && duo_first(s, level)) return &L.tmp;
-  return which == 0 ? &L.u : (which == 1 ? &L.f : (which == 2 ? &L.r : nullptr));
-}
 amg_hip_status amg_hip_get_vec(amg_hip_solver* s, int32_t level, int32_t which, double* out) {
-  DevMem* m = pick_vec(s, level, which);
+  DevMem* m = level_vec(s, level, which);
   if (!m || !out) return fail(AMG_HIP_EINVAL, "bad level / vector selector");
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no vectors");
-  if (which == 2 && !s->opt.keep_residual &&
-      (fuses_resid_restrict(s, level) || patch_level_ok(s, level) || mc_patch_ok(s, level) || mc_strip_ok(s, level) ||
-       (level == (int32_t)s->lv.size() - 1 && level > 0)))
+  if (which == 2 && !s->opt.keep_residual && !current_plan(s).lv[(size_t)level].writes_r)
     return fail(AMG_HIP_EINVAL, "the residual of this level is not kept (create the solver with "
                                 "opt.keep_residual = 1)");
   HIP_TRY(hipSetDevice(s->device));
@@ -6068,7 +6218,7 @@ amg_hip_status amg_hip_get_vec(amg_hip_solver* s, int32_t level, int32_t which, 
 }
 amg_hip_status amg_hip_set_vec(amg_hip_solver* s, int32_t level, int32_t which,
                                const double* in) {
-  DevMem* m = pick_vec(s, level, which);
+  DevMem* m = level_vec(s, level, which);
   if (!m || !in) return fail(AMG_HIP_EINVAL, "bad level / vector selector");
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no vectors");
   HIP_TRY(hipSetDevice(s->device));
@@ -6143,6 +6293,32 @@ void cheb_profiled_step(const amg_hip_solver* s, ChebStep* out) {
   c.last = j == k - 1;
   *out = c;
 }
+// n timed launches on the stream, each between two events; `after` is enqueued behind them, then the
+// stream is drained
+amg_hip_status no_launch() { return AMG_HIP_OK; }
+extern "C++" template <class After, class Launch>
+amg_hip_status time_launches(hipStream_t st, int n, double* avg_ms, double* min_ms, After after, Launch launch) {
+  std::vector<hipEvent_t> ev(2 * (size_t)n);
+  for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+  for (int i = 0; i < n; ++i) {
+    HIP_TRY(hipEventRecord(ev[2 * i], st));
+    AMG_TRY(launch());
+    HIP_TRY(hipEventRecord(ev[2 * i + 1], st));
+  }
+  AMG_TRY(after());
+  HIP_TRY(hipStreamSynchronize(st));
+  double sum = 0, mn = 1e30;
+  for (int i = 0; i < n; ++i) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
+    sum += ms;
+    mn = std::min<double>(mn, ms);
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  if (avg_ms) *avg_ms = sum / n;
+  if (min_ms) *min_ms = mn;
+  return AMG_HIP_OK;
+}
 }  // namespace
 
 amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
@@ -6159,44 +6335,35 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
     // one middle step (u -> tmp, d read and written; u is not written), else step 0
     ChebStep c;
     cheb_profiled_step(s, &c);
-    std::vector<hipEvent_t> ev(2 * (size_t)n_launches);
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    for (int i = 0; i < n_launches; ++i) {
-      HIP_TRY(hipEventRecord(ev[2 * i], s->stream));
+    return time_launches(s->stream, n_launches, avg_ms, min_ms, no_launch, [&]() -> amg_hip_status {
       HIP_TRY(launch_mat_cheb(L.A_rows, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(), c, s->stream));
-      HIP_TRY(hipEventRecord(ev[2 * i + 1], s->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    double sum = 0, mn = 1e30;
-    for (int i = 0; i < n_launches; ++i) {
-      float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
-      sum += ms;
-      mn = std::min<double>(mn, ms);
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    if (avg_ms) *avg_ms = sum / n_launches;
-    if (min_ms) *min_ms = mn;
-    return AMG_HIP_OK;
+      return AMG_HIP_OK;
+    });
   }
   const DevMat& A = L.A_cols();
+  const CyclePlan P = current_plan(s);
+  const LegForm form = P.lv[0].down;  // the launch level 0 runs
   const bool mc = s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS;
-  const bool mc_patch = mc && mc_patch_ok(s, 0);
+  const bool mc_patch = form == LEG_MC_PATCH;
   // multicolour, colour kernels: the launch updates u in place; keep a copy in r
   if (mc && !mc_patch)
     HIP_TRY(hipMemcpyAsync(L.r.p, L.u.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream));
-  std::vector<hipEvent_t> ev(2 * (size_t)n_launches);
-  for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
   // keep u: sweep u -> tmp only (u itself is never written).  With K-Patch the launch is the
   // level's whole down-leg (2 sweeps + residual + restriction + first coarse sweep); it also
   // rewrites f and tmp of level 1, which every V-cycle recomputes before use.
-  const bool patch = !mc && patch_level_ok(s, 0);
+  const bool patch = form == LEG_PATCH;
   MarchRef MR;
-  const bool march = !mc && !patch && march_fill(s, 0, &MR);
+  const bool march = !mc && !patch && P.lv[0].march;
+  if (march) (void)march_fill(s, 0, &MR);
   // slab-sharded solver: this rank's launch, i.e. its own lines + halo only
   const bool slab = patch && s->slab.levels > 0 && s->slab.world > 1;
-  for (int i = 0; i < n_launches; ++i) {
-    HIP_TRY(hipEventRecord(ev[2 * i], s->stream));
+  // (after the launches the multicolour colour kernels' u goes back)
+  auto restore = [&]() -> amg_hip_status {
+    if (mc && !mc_patch)
+      HIP_TRY(hipMemcpyAsync(L.u.p, L.r.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream));
+    return AMG_HIP_OK;
+  };
+  return time_launches(s->stream, n_launches, avg_ms, min_ms, restore, [&]() -> amg_hip_status {
     if (mc_patch) {  // the first launch of the level's down-leg (its colour stages): u -> tmp
       int nd = 0;
       const std::vector<McLaunch> plan = mc_plan(s, 0, &nd);
@@ -6220,29 +6387,15 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
       Level& C = s->lv[1];
       HIP_TRY(launch_patch_down(true, L.n, A.patch_m, A.patch_ref(), L.u.as<double>(),
                                 L.f.as<double>(), L.tmp.as<double>(), nullptr, C.n, C.f.as<double>(),
-                                C.diag.as<double>(), patch_xf_pair(s, 0) ? nullptr : C.tmp.as<double>(),
+                                C.diag.as<double>(), P.lv[0].xf_out ? nullptr : C.tmp.as<double>(),
                                 s->opt.omega, s->stream,
                                 slab ? s->slab.down_lo[0] : 0, slab ? s->slab.down_hi[0] : -1));
     } else {
       HIP_TRY(launch_mat(CSR_JACOBI, A, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
                          s->opt.omega, s->stream));
     }
-    HIP_TRY(hipEventRecord(ev[2 * i + 1], s->stream));
-  }
-  if (mc && !mc_patch)
-    HIP_TRY(hipMemcpyAsync(L.u.p, L.r.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  double sum = 0, mn = 1e30;
-  for (int i = 0; i < n_launches; ++i) {
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
-    sum += ms;
-    mn = std::min<double>(mn, ms);
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  if (avg_ms) *avg_ms = sum / n_launches;
-  if (min_ms) *min_ms = mn;
-  return AMG_HIP_OK;
+    return AMG_HIP_OK;
+  });
 }
 
 amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* bytes) {
@@ -6251,7 +6404,7 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
   if (part == 4) {
     // one steady-state cycle of amg_hip_vcycles(s, n >= 2): the seam cycle where the solver runs one
     // (counted while its graph is captured), else the stand-alone cycle
-    if (!patch_seam_ok(s)) return amg_hip_cycle_must_move(s, CYCLE_ALL, bytes);
+    if (!current_plan(s).seam) return amg_hip_cycle_must_move(s, CYCLE_ALL, bytes);
     if (s->must_move[4] == 0.0) {
       amg_hip_status r = set_device(s);
       if (r != AMG_HIP_OK) return r;
@@ -6283,9 +6436,11 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
 
 int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t leg) {
   if (!s || s->opt.host_only || level < 0 || level >= (int32_t)s->lv.size() || leg < 0 || leg > 2) return 0;
-  if (leg == 2) return (level == 0 && patch_seam_ok(s)) ? patch_seam_lines() : 0;  // the seam launch
-  if (mc_patch_ok(s, level)) return patch_tile_lines(3);
-  if (!patch_level_ok(s, level)) return 0;
+  const CyclePlan P = current_plan(s);
+  const LegForm form = P.lv[(size_t)level].up;  // (a patch level is one on both legs)
+  if (leg == 2) return (level == 0 && P.seam) ? patch_seam_lines() : 0;  // the seam launch
+  if (form == LEG_MC_PATCH) return patch_tile_lines(3);
+  if (form != LEG_PATCH) return 0;
   return patch_tile_lines(patch_rings(s, leg == 0 && level == 0));
 }
 
@@ -6297,6 +6452,8 @@ amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int3
   if (s->opt.host_only) return fail(AMG_HIP_EINVAL, "host_only solver has no device matrices");
   const Level& L = s->lv[0];
   const DevMat& A = L.A_cols();
+  const CyclePlan P = current_plan(s);
+  const LevelPlan& Q = P.lv[0];  // the launch level 0 runs
   int32_t lay = 0;
   int64_t mat = 0;
   layout_of(A, &lay, &mat);
@@ -6322,7 +6479,7 @@ amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int3
   } else if (s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS) {
     // one launch of the symmetric pass: two colour stages over the level (patch form), or one
     // colour of one direction (colour kernels: half the rows)
-    if (mc_patch_ok(s, 0)) {
+    if (Q.down == LEG_MC_PATCH) {
       std::snprintf(name, (size_t)name_cap, "patch_rb_kernel<%d, %d, %s, false, false>", patch_un(A.patch_un),
                     patch_kind_umask(A.patch_un, A.patch_umask), A.dict_nt ? "true" : "false");
       bytes = 25.0 * (double)L.n;
@@ -6333,20 +6490,20 @@ amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int3
       bytes = L.mc_dict ? rows * (8.0 * L.mc_words + 4.0 + 16.0)
                         : rows / (double)L.n * (12.0 * (double)L.nnz_struct + 28.0 * (double)L.n);
     }
-  } else if (A.dict && patch_level_ok(s, 0)) {
+  } else if (Q.down == LEG_PATCH) {
     // row types + x + f + smoothed u per fine row; f_H and, unless level 1 forms it from f_H itself
-    // (patch_xf_pair), the first coarse sweep and the coarse diagonal
+    // (the hand-over), the first coarse sweep and the coarse diagonal
     std::snprintf(name, (size_t)name_cap, "patch_down_kernel<%d, %d, true, %s, false, 3>", patch_un(A.patch_un),
                   patch_kind_umask(A.patch_un, A.patch_umask), A.dict_nt ? "true" : "false");
     sweeps = 2;
-    bytes = 25.0 * (double)L.n + (patch_xf_pair(s, 0) ? 8.0 : 24.0 - 8.0 * A.patch_cfrac) * (double)s->lv[1].n;
+    bytes = 25.0 * (double)L.n + (Q.xf_out ? 8.0 : 24.0 - 8.0 * A.patch_cfrac) * (double)s->lv[1].n;
     if (s->slab.levels > 0 && s->slab.world > 1) {  // the tiles this rank's launch covers
       const int64_t th = patch_tile_lines(patch_rings(s, true));  // the level-0 down-leg's tiles
       const int64_t l0 = s->slab.down_lo[0] / th * th;
       const int64_t l1 = std::min<int64_t>(s->slab.lines, (s->slab.down_hi[0] + th - 1) / th * th);
       bytes *= (double)(l1 - l0) / (double)s->slab.lines;
     }
-  } else if (MarchRef MR; A.dict && march_fill(s, 0, &MR)) {
+  } else if (Q.march) {
     // both sweeps of the level in one pass: row types + x + f + out
     std::snprintf(name, (size_t)name_cap, "march_kernel");
     sweeps = 2;

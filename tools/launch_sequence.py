@@ -1,0 +1,161 @@
+#!/usr/bin/env python3
+"""The launches of the double-precision V-cycle, for comparing two builds of the library.
+
+  run one configuration (eager: use_graph=False), vcycle(1) then vcycle(3), and print cycle_must_move()
+  of parts 0 and 4 as hexadecimal floats:
+      AMG_HIP_LIBRARY=<lib.so> rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- \
+          python3 tools/launch_sequence.py --config <name>
+  list the configurations:
+      python3 tools/launch_sequence.py --list
+  compare the traces and the printed bytes of two builds (<dir>/<config>/t_kernel_trace.csv and
+  <dir>/<config>.out of every configuration) and write the markdown report:
+      python3 tools/launch_sequence.py --compare <dir A> <dir B> > profiles/plan_launch_sequences.md
+
+Only the library's existing API is used, so either build can be measured."""
+import argparse
+import csv
+import glob
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "algebraic-multigrid_amd"), os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+
+def _configs():
+    """name -> (process-wide switches, constructor); the shapes are those of the named tests"""
+    import numpy as np
+    import amg_ctypes as amg
+    from oracle import oracle as O
+    O.build()
+    import test_gpu_pair_onchip as P
+    import test_gpu_patch_seam as S
+    import test_gpu_stencil_geometry as G
+
+    def csc(A):
+        return A.colptr, A.rowind, A.val
+
+    cfg = {}
+    for shape in ("lap256", "box300x50", "zerodiag128x50"):       # tests/test_gpu_pair_onchip.py
+        for keep in (0, 1):
+            cfg[f"{shape}_keep{keep}"] = ({}, lambda shape=shape, keep=keep: P._solver(amg, O, shape, bool(keep), use_graph=False))
+    # tests/test_gpu_patch_seam.py: K-Patch on levels 0 .. 2, the hand-over, the seam
+    cfg["lap512_patch"] = ({"patch_min_rows": 0}, lambda: S._solver(amg, O, "lap512", 1, use_graph=False))
+    cfg["poisson512_tail"] = ({"tail_fusion": 1}, lambda: amg.Multigrid.poisson(
+        512, 10, smoother=amg.SM_JACOBI, smoother_iters=2, omega=0.6, use_graph=False))
+
+    def multicolor():
+        A, b = O.laplacian(512), O.rhs(512)
+        return amg.Multigrid(*csc(A), b, 6, smoother=amg.SM_MULTICOLOR_GS, smoother_iters=1, use_graph=False)
+    cfg["multicolor512_patch"] = ({"patch_min_rows": 0}, multicolor)
+    cfg["multicolor512"] = ({}, multicolor)
+
+    def march():                                                  # tests/test_gpu_stencil_geometry.py
+        op = G.box3d(*G.MARCH_SHAPES[0])
+        n = op[0].size - 1
+        return amg.Multigrid(*op, G.rhs_for(n), G.levels_for(n), smoother=amg.SM_JACOBI, smoother_iters=2,
+                             omega=0.6, layout=amg.LAYOUT_DICT, exact_coarse_solve=True, use_graph=False)
+    cfg["march64x16x3"] = ({}, march)
+    # plain path, CSR transfers (tests/test_gpu_chebyshev.py) and tensor transfers (tests/test_gpu_line_alt.py)
+    cfg["chebyshev_rs64"] = ({}, lambda: amg.Multigrid.ruge_stueben(
+        *csc(O.laplacian(64)), O.rhs(64), 4, 0.25, 50, smoother=5, use_graph=False))
+    cfg["line_alt_tensor64"] = ({}, lambda: amg.Multigrid.poisson_tensor(
+        64, 4, smoother=7, omega=0.8, smoother_iters=1, use_graph=False))
+    return amg, cfg
+
+
+def run(name):
+    amg, cfg = _configs()
+    switches, make = cfg[name]
+    if "patch_min_rows" in switches:
+        amg.set_patch_min_rows(switches["patch_min_rows"])
+    if "tail_fusion" in switches:
+        amg.set_tail_fusion(switches["tail_fusion"])
+    mg = make()
+    try:
+        mg.vcycle(1)
+        mg.vcycle(3)
+        mg.sync()
+        for part in (0, 4):
+            print(f"{name} cycle_must_move({part}) = {float(mg.cycle_must_move(part)).hex()}")
+    finally:
+        mg.close()
+
+
+def _trace(path):
+    """ordered (kernel name, grid size, workgroup size) of a rocprofv3 kernel trace"""
+    files = glob.glob(os.path.join(path, "**", "*kernel_trace.csv"), recursive=True)
+    if len(files) != 1:
+        raise SystemExit(f"{path}: expected one kernel trace, found {files}")
+    with open(files[0], newline="") as f:
+        rows = list(csv.DictReader(f))
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]) if "Dispatch_Id" in r else int(r["Start_Timestamp"]))
+    dim = lambda r, what: "x".join(r[f"{what}_Size_{a}"] for a in "XYZ")
+    return [(r["Kernel_Name"], dim(r, "Grid"), dim(r, "Workgroup")) for r in rows]
+
+
+def _rle(ids):
+    out = []
+    for i in ids:
+        if out and out[-1][0] == i:
+            out[-1][1] += 1
+        else:
+            out.append([i, 1])
+    return " ".join(f"{i}" if c == 1 else f"{i}*{c}" for i, c in out)
+
+
+def compare(dir_a, dir_b):
+    names = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(dir_a, "*.out")))
+    table, verdicts, body = {}, [], []
+    for name in names:
+        seqs, outs = [], []
+        for d in (dir_a, dir_b):
+            seqs.append(_trace(os.path.join(d, name)))
+            with open(os.path.join(d, name + ".out")) as f:
+                outs.append([line.strip() for line in f if "cycle_must_move" in line])
+        same_seq, same_bytes = seqs[0] == seqs[1], outs[0] == outs[1] and len(outs[0]) == 2
+        verdicts.append((name, len(seqs[0]), len(seqs[1]), same_seq, same_bytes))
+        body.append(f"### {name}\n")
+        for tag, seq, out in zip("AB", seqs, outs):
+            ids = [table.setdefault(k, len(table)) for k in seq]
+            body.append(f"{tag}: {len(seq)} launches; " + "; ".join(out) + "\n")
+            body.append("```\n" + _rle(ids) + "\n```\n")
+    print("# Launch sequences of the V-cycle: parent (A) against the cycle plan (B)\n")
+    print("`tools/launch_sequence.py`, one `rocprofv3 --kernel-trace` run per configuration and build: the solver is")
+    print("created with `use_graph=False`, runs `vcycle(1)` and `vcycle(3)`, and prints `cycle_must_move()` of")
+    print("parts 0 and 4.  A list is every kernel launch of the process in dispatch order (set-up included) as")
+    print("an index into the table at the end, `k*c` for c launches of k in a row.\n")
+    print("| configuration | launches A | launches B | same (kernel, grid, workgroup) list | same bytes |")
+    print("|---|---|---|---|---|")
+    for name, na, nb, s, b in verdicts:
+        print(f"| {name} | {na} | {nb} | {'yes' if s else 'NO'} | {'yes' if b else 'NO'} |")
+    ok = all(s and b for *_, s, b in verdicts) and bool(verdicts)
+    print(f"\n**Verdict: {'identical' if ok else 'DIFFERENT'}** over {len(verdicts)} configurations.\n")
+    print("\n".join(body))
+    print("## Kernels\n")
+    print("| id | kernel | grid | workgroup |")
+    print("|---|---|---|---|")
+    for (k, g, w), i in sorted(table.items(), key=lambda kv: kv[1]):
+        print(f"| {i} | `{k}` | {g} | {w} |")
+    return 0 if ok else 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config")
+    ap.add_argument("--list", action="store_true")
+    ap.add_argument("--compare", nargs=2, metavar="DIR")
+    a = ap.parse_args()
+    if a.compare:
+        return compare(*a.compare)
+    if a.list:
+        print("\n".join(_configs()[1]))
+        return 0
+    run(a.config)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
