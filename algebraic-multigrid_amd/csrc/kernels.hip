@@ -5773,28 +5773,49 @@ __device__ __forceinline__ void band_chain_pass(int n, const double* ops, double
     __builtin_amdgcn_sched_barrier(0);
   }
 }
-// global -> LDS with the loads of a round issued TOGETHER (one memory round trip per 16 x 64
-// entries; written as a plain loop the compiler waited for every load before the next one:
-// seventeen dependent round trips for the 511-row level, more than the substitution itself)
-__device__ __forceinline__ void band_chain_stage(const double* __restrict__ src, double* dst, int valid,
-                                                 int total, int lane) {
-  constexpr int R = 16;
-  for (int base = 0; base < total; base += 64 * R) {
-    double t[R];
+// The stand-alone launch: a workgroup of CHAIN_T threads (four waves, one per SIMD) around the
+// recurrence, which wave 0 walks alone (tail_kernel's coarsest-solve block has the same form).
+// Everything that is parallel -- staging, the scaling by D^-1, the store of x, the prolongation --
+// is spread over all threads, and every global load the launch needs is issued at entry, before the
+// first wait: ONE memory round trip ahead of the forward pass for up to 512 rows (the headline's
+// 511), and none between the forward pass and the final stores.  Longer systems take further
+// rounds, written as loops of a few loads issued together.
+constexpr int CHAIN_T = 256;
+// one round of a global -> LDS copy: R loads per thread issued together (entries base + j * CHAIN_T
+// + tid below `valid`; past the end the last entry is read again and not stored: straight-line
+// loads, no branch around each), and their LDS stores
+template <int R>
+__device__ __forceinline__ void band_chain_load(double (&t)[R], const double* __restrict__ src, int valid,
+                                                int base, int tid) {
 #pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int k = base + j * 64 + lane;
-      t[j] = k < valid ? src[k] : 0.0;
-    }
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int k = base + j * 64 + lane;
-      if (k < total) dst[k] = t[j];
-    }
+  for (int j = 0; j < R; ++j) {
+    const int k = base + j * CHAIN_T + tid;
+    t[j] = src[min(k, valid - 1)];
   }
 }
+template <int R>
+__device__ __forceinline__ void band_chain_store(const double (&t)[R], double* dst, int valid, int base,
+                                                 int tid) {
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const int k = base + j * CHAIN_T + tid;
+    if (k < valid) dst[k] = t[j];
+  }
+}
+// the rounds after the first (whose loads the kernel issues at entry with everything else), and
+// the zero operands of the padding
+template <int R>
+__device__ __forceinline__ void band_chain_stage_rest(const double* __restrict__ src, double* dst, int valid,
+                                                      int total, int tid) {
+  for (int base = CHAIN_T * R; base < valid; base += CHAIN_T * R) {
+    double t[R];
+    band_chain_load<R>(t, src, valid, base, tid);
+    band_chain_store<R>(t, dst, valid, base, tid);
+  }
+  for (int k = valid + tid; k < total; k += CHAIN_T) dst[k] = 0.0;
+}
 template <int W>
-__global__ __launch_bounds__(64) void band_chain_kernel(
+__global__ __launch_bounds__(CHAIN_T) void band_chain_kernel(
     int n, const double* __restrict__ cf, const double* __restrict__ cb,
     const double* __restrict__ dg, const double* __restrict__ f, double* __restrict__ x, int n_h,
     const double* uh_in, double* uh_out, int pre, int64_t cstride) {
@@ -5807,69 +5828,94 @@ __global__ __launch_bounds__(64) void band_chain_kernel(
   // backward operands: staged with the forward ones when the LDS allows (pre: no global round
   // trip between the two passes), else over them after the first pass
   double* opb = pre ? v + np : ops;
-  const int lane = threadIdx.x;
-  double dgv[32];                    // the diagonal, mirrored, requested before the first pass
-#pragma unroll
-  for (int q = 0; q < 32; ++q) {
-    const int s = lane + 64 * q;
-    dgv[q] = s < n ? dg[n - 1 - s] : 1.0;
-  }
-  // the fine vector the result is prolonged into: its first 1024 rows are requested now, the solve
-  // hides the round trip
-  double a0[8], a1[8];
+  const int tid = threadIdx.x;
+  constexpr int RO = 4, RF = 2;      // loads per thread and round: operands (1024 entries), f (512)
+  // ---- entry: every load of the launch's first round, then the first wait ----
+  // the diagonal of the rows this thread scales between the passes: row tid and its mirror
+  const int nhalf = (n + 1) / 2;
+  double d_lo = dg[min(tid, n - 1)], d_hi = dg[max(n - 1 - tid, 0)];
+  // the fine vector the result is prolonged into: two pairs per thread and round (1024 fine rows)
+  double a0[2] = {0.0, 0.0}, a1[2] = {0.0, 0.0};
   auto fetch_fine = [&](int j0) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int i = 2 * (j0 + q * 64 + lane);
-      a0[q] = i < n_h ? uh_in[i] : 0.0;
-      a1[q] = i + 1 < n_h ? uh_in[i + 1] : 0.0;
+    for (int q = 0; q < 2; ++q) {
+      const int i = 2 * (j0 + q * CHAIN_T + tid);  // past the end: the last row again, never stored
+      a0[q] = uh_in[min(i, n_h - 1)];
+      a1[q] = uh_in[min(i + 1, n_h - 1)];
     }
   };
+  double tb[RO], tf[RF], to[RO];
+  band_chain_load<RO>(tb, cb, n * W, 0, tid);   // stored now (pre) or after the forward pass
+  band_chain_load<RF>(tf, f, n, 0, tid);
+  band_chain_load<RO>(to, cf, n * W, 0, tid);
   if (uh_out) fetch_fine(0);
-  band_chain_stage(cf, ops, n * W, np * W, lane);
-  band_chain_stage(f, v, n, np, lane);
-  if (pre) band_chain_stage(cb, opb, n * W, np * W, lane);
-  lds_barrier();
-  band_chain_pass<W>(n, ops, v);                 // L y = f
-  lds_barrier();
-  double z[32];                                  // n <= 2048: z = y / D, mirrored
-#pragma unroll
-  for (int q = 0; q < 32; ++q) {
-    const int s = lane + 64 * q;
-    z[q] = s < n ? v[n - 1 - s] / dgv[q] : 0.0;
-  }
-  if (!pre) band_chain_stage(cb, opb, n * W, n * W, lane);
-  lds_barrier();
-#pragma unroll
-  for (int q = 0; q < 32; ++q) {
-    const int s = lane + 64 * q;
-    if (s < n) v[s] = z[q];
+  band_chain_store<RO>(to, ops, n * W, 0, tid);
+  band_chain_store<RF>(tf, v, n, 0, tid);
+  band_chain_stage_rest<RO>(cf, ops, n * W, np * W, tid);
+  band_chain_stage_rest<RF>(f, v, n, np, tid);
+  if (pre) {
+    band_chain_store<RO>(tb, opb, n * W, 0, tid);
+    band_chain_stage_rest<RO>(cb, opb, n * W, np * W, tid);
   }
   lds_barrier();
-  band_chain_pass<W>(n, opb, v);                 // L^T x = z, step s = row n-1-s
+  if (tid < 64) band_chain_pass<W>(n, ops, v);   // L y = f
   lds_barrier();
-  for (int s = lane; s < n; s += 64) x[n - 1 - s] = v[s];
-  if (uh_out) {
-    // the prolongation into the level above (multigrid.hpp:294-296 for l = L-2), which would
-    // otherwise be a launch of its own: uh_out = uh_in + P x, linear_prolong_add2_kernel's
-    // expressions and order; x sits in v[] mirrored (x_j = v[n-1-j])
-    // (the loads of eight pairs issued together: one global round trip per 1024 fine rows)
-    for (int j0 = 0; 2 * j0 < n_h; j0 += 64 * 8) {
-      if (j0 > 0) fetch_fine(j0);
+  // ---- z = y / D, mirrored: step s of the backward pass is row n-1-s.  A thread takes a row and
+  // its mirror and swaps the two quotients in place: no other thread touches either entry ----
+  for (int i = tid; i < nhalf; i += CHAIN_T) {
+    const int m = n - 1 - i;
+    if (i >= CHAIN_T) {  // rows past the entry round: n > 512
+      d_lo = dg[i];
+      d_hi = dg[m];
+    }
+    const double z_lo = v[i] / d_lo, z_hi = v[m] / d_hi;
+    v[m] = z_lo;
+    v[i] = z_hi;
+  }
+  if (!pre) {  // ops is free: cb goes over it, the first round from the registers loaded at entry
+    band_chain_store<RO>(tb, opb, n * W, 0, tid);
+    band_chain_stage_rest<RO>(cb, opb, n * W, n * W, tid);  // the padding still holds cf's zeros
+  }
+  lds_barrier();
+  if (tid < 64) band_chain_pass<W>(n, opb, v);   // L^T x = z, step s = row n-1-s
+  lds_barrier();
+  // ---- exit: the sums of the first 1024 fine rows, then every store (stores count in vmcnt too:
+  // a wait for a fine pair issued behind a store would wait for that store) ----
+  // the prolongation into the level above (multigrid.hpp:294-296 for l = L-2), which would
+  // otherwise be a launch of its own: uh_out = uh_in + P x, linear_prolong_add2_kernel's
+  // expressions and order; x sits in v[] mirrored (x_j = v[n-1-j])
+  double o0[2], o1[2];
+  auto prolong_sums = [&](int j0) {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int j = j0 + q * 64 + lane, i = 2 * j;
-        if (i >= n_h) continue;
-        double t0 = 0.0, t1 = 0.0;
-        const double b = (j < n) ? v[n - 1 - j] : 0.0;
-        if (j >= 1 && j - 1 < n) t0 += 0.5 * v[n - j];
-        if (j < n) {
-          t0 += 0.5 * b;
-          t1 += 1.0 * b;
-        }
-        uh_out[i] = a0[q] + t0;
-        if (i + 1 < n_h) uh_out[i + 1] = a1[q] + t1;
+    for (int q = 0; q < 2; ++q) {
+      const int j = j0 + q * CHAIN_T + tid;
+      double t0 = 0.0, t1 = 0.0;
+      const double b = (j < n) ? v[n - 1 - j] : 0.0;
+      if (j >= 1 && j - 1 < n) t0 += 0.5 * v[n - j];
+      if (j < n) {
+        t0 += 0.5 * b;
+        t1 += 1.0 * b;
       }
+      o0[q] = a0[q] + t0;
+      o1[q] = a1[q] + t1;
+    }
+  };
+  auto prolong_store = [&](int j0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int i = 2 * (j0 + q * CHAIN_T + tid);
+      if (i < n_h) uh_out[i] = o0[q];
+      if (i + 1 < n_h) uh_out[i + 1] = o1[q];
+    }
+  };
+  prolong_sums(0);  // without uh_out: sums onto zeros that nobody stores, and no branch
+  for (int s = tid; s < n; s += CHAIN_T) x[n - 1 - s] = v[s];
+  if (uh_out) {
+    prolong_store(0);
+    for (int j0 = CHAIN_T * 2; 2 * j0 < n_h; j0 += CHAIN_T * 2) {
+      fetch_fine(j0);
+      prolong_sums(j0);
+      prolong_store(j0);
     }
   }
 }
@@ -5883,9 +5929,9 @@ hipError_t launch_band_chain(int64_t n, int w, const double* cf, const double* c
   const int pre = sizeof(double) * np * (size_t)(2 * w + 1) <= (size_t)48 * 1024 ? 1 : 0;
   const size_t lds = sizeof(double) * np * (size_t)(pre ? 2 * w + 1 : w + 1);
   switch (w) {
-    case 1: hipLaunchKernelGGL(band_chain_kernel<1>, dim3(cols), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
-    case 2: hipLaunchKernelGGL(band_chain_kernel<2>, dim3(cols), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
-    default: hipLaunchKernelGGL(band_chain_kernel<3>, dim3(cols), dim3(64), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
+    case 1: hipLaunchKernelGGL(band_chain_kernel<1>, dim3(cols), dim3(CHAIN_T), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
+    case 2: hipLaunchKernelGGL(band_chain_kernel<2>, dim3(cols), dim3(CHAIN_T), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
+    default: hipLaunchKernelGGL(band_chain_kernel<3>, dim3(cols), dim3(CHAIN_T), lds, st, (int)n, cf, cb, dg, f, x, (int)n_h, uh_in, uh_out, pre, cstride); break;
   }
   return hipGetLastError();
 }
