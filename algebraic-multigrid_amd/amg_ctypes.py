@@ -203,6 +203,8 @@ _SIGS = {
     "amg_hip_set_patch_tile_flags": (None, [C.c_int32]),
     "amg_hip_set_patch_xf": (None, [C.c_int32]),
     "amg_hip_set_patch_tall": (None, [C.c_int32]),
+    "amg_hip_set_patch_coltype": (None, [C.c_int32]),
+    "amg_hip_patch_tile_classes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i64p]),
     "amg_hip_set_patch_seam": (None, [C.c_int32]),
     "amg_hip_patch_leg_lines": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "amg_hip_create_rs": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, C.c_double, C.c_int64,
@@ -434,6 +436,12 @@ def set_patch_xf(on):
 
 def set_patch_tall(on):
     lib().amg_hip_set_patch_tall(int(bool(on)))
+
+
+def set_patch_coltype(on):
+    """K-Patch column-typed tiles (flag 254: the tiles at the line ends) on (the default) / off; process-wide,
+    read when a solver is created, same bits either way"""
+    lib().amg_hip_set_patch_coltype(int(bool(on)))
 
 
 def set_patch_seam(on):
@@ -1230,6 +1238,16 @@ class Multigrid:
         """lines of the K-Patch tiles of `level`'s down-leg (leg 0) / up-leg (leg 1); 0 = no K-Patch level.
         leg 2: of the seam launch that vcycle(n >= 2) runs on level 0; 0 = this solver runs none"""
         return int(lib().amg_hip_patch_leg_lines(self._h, int(level), int(leg)))
+
+    def patch_tile_classes(self, level, rings):
+        """(one-type, column-typed, general) tile counts of `level` for the launches with `rings` halo rings
+        (2: 44-line tiles, 3: 42, 5: the seam's); ValueError where the level is no K-Patch level"""
+        out = np.zeros(3, np.int64)
+        st = lib().amg_hip_patch_tile_classes(self._h, int(level), int(rings), out.ctypes.data_as(_i64p))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return tuple(int(v) for v in out)
 
     def profile_fine_sweep(self, n_launches):
         """(avg_ms, min_ms, sweeps per launch, kernel name) of the level-0 Jacobi sweep

@@ -1919,6 +1919,9 @@ constexpr int PATCH_NT = 432;                // threads = 6 line groups x 72 col
 constexpr int PATCH_K = PATCH_EH * PATCH_EC / PATCH_NT;  // cells per thread: 8 consecutive lines
 constexpr int PATCH_BUF = (PATCH_EH + 2) * PATCH_EC;     // + one guard line above and below
 constexpr int PATCH_MAXTAB = 192;            // table capacity: (types + 1) x slots
+// values of a tile flag that are no row type: a column-typed tile / a general one (patch_tile_flags_kernel)
+constexpr uint32_t PATCH_FLAG_COLTYPED = 254u, PATCH_FLAG_GENERAL = 255u;
+constexpr int PATCH_SEAM_RINGS_HOST = 5;  // (= PATCH_SEAM_RINGS, defined with the seam kernel below)
 static_assert(PATCH_EH * PATCH_EC == PATCH_K * PATCH_NT && PATCH_NT % PATCH_EC == 0, "patch geometry");
 // The held frame as a parameter of the patch functions: EH lines x EC columns [-CL, EC - CL) around
 // the PATCH_TW output columns, PATCH_K consecutive lines per thread.  PatchFrame is the frame of the
@@ -1950,9 +1953,12 @@ struct PatchCells {
   bool uniform;             // every cell of the wave has the type tu (then the table comes
   uint32_t tu;              // through scalar loads instead of per-lane LDS reads)
   bool flagged;             // the tile's flag says so for the whole workgroup: ty[] is not filled in
+  bool coltyped;            // column-typed tile (flag 254): all PATCH_K cells of the thread have ONE type, the
+                            // lane's, kept in ty[0]; every row is inside the matrix
   __device__ __forceinline__ uint32_t type(int k) const {
-    return flagged ? tu : (ty[k >> 2] >> (8 * (k & 3))) & 255u;
+    return flagged ? tu : (coltyped ? ty[0] : (ty[k >> 2] >> (8 * (k & 3))) & 255u);
   }
+  __device__ __forceinline__ uint32_t lane_type() const { return ty[0]; }
 };
 
 // The table of ONE row type held in scalar registers (the wave-uniform fast path: in the
@@ -2079,6 +2085,73 @@ __device__ __forceinline__ void patch_eval_u(const double* buf, int cell0, const
     }
   }
 }
+// Column-typed tiles (flag 254: the tiles at the line ends): the lane-typed twin of patch_eval_u.  All
+// PATCH_K cells of a thread share the lane's row type, so the thread walks them with the same sliding
+// 3 x 3 window -- 3 LDS reads per cell at static addresses instead of one dependent read per entry --
+// and takes its weights from the slot-form table of ITS type, which the workgroup staged in LDS in the
+// place of the per-entry tables (patch_load):
+//   ctabJ: per type wj[9] (off-diagonal values; +0.0 on the diagonal and where there is no entry), diag
+//   ctabR: per type wr[9] (values; +0.0 where there is no entry), rmask (the slots in use, as an integer)
+// The weights are re-read for every cell, half a row at a time (9 + 3 reads per cell; patch_eval: 28,
+// with addresses that hang on a loaded offset): beside the window's 18 registers, f and the results, a
+// lane's 9 weights held for the stage do not fit the 72 registers of four workgroups per CU.
+// BAR: scheduling barriers keep the compiler from issuing the reads of several cells at once, which
+// costs the same registers: the up-legs (72 registers) spill 3 registers without them and none with
+// them; the 7- and 9-point down-legs and the seam (80) spill none without them and 5-7 with them.  The
+// 5-point down-leg (72) spills either way and keeps the general path (profiles/coltype_isa.md).
+// Same bits as patch_eval: the slots in ascending order ARE the entries in ascending column order; an
+// absent slot adds (+0.0) x to a Jacobi accumulator that starts at +0.0 (the argument of patch_eval_u's
+// generic form) and is selected away in the residual; diag is the same sum of the type's entries; a lane
+// without a diagonal keeps its value and divides by 1.0.
+constexpr int PATCH_CT = 10;  // doubles per type in ctabJ / ctabR
+static_assert((PATCH_MAXTAB / 5) * PATCH_CT * sizeof(double) <= PATCH_MAXTAB * 16,
+              "the slot tables of (ntypes + 1) <= PATCH_MAXTAB / 5 types fit tabJ and tabR");
+template <bool RESID, bool BAR, class FR = PatchFrame>
+__device__ __forceinline__ void patch_eval_c(const double* buf, int cell0, uint32_t tl, const double* ctab,
+                                             const double (&f)[PATCH_K], double omega, double (&res)[PATCH_K]) {
+  const double* p = buf + cell0 - FR::EC;  // line above the first cell
+  int to = (int)tl * PATCH_CT;
+  uint32_t rmask = 0;
+  if (RESID) rmask = reinterpret_cast<const uint32_t*>(ctab + to + 9)[0];
+  double w[3][3];
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w[r][c] = p[r * FR::EC + c - 1];
+#pragma unroll
+  for (int k = 0; k < PATCH_K; ++k) {
+    // (!BAR: the table offset is opaque per cell, else the compiler hoists the weights of all cells into
+    // registers: the seam kernel then spills 8 of them)
+    if (!BAR) asm("" : "+v"(to));
+    const double* wt = ctab + to;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w[2][c] = p[(k + 2) * FR::EC + c - 1];
+    const double xi = w[1][1];
+    double acc = RESID ? f[k] : 0.0;
+#pragma unroll
+    for (int s9 = 0; s9 < 9; ++s9) {
+      if (BAR && s9 == 5) __builtin_amdgcn_sched_barrier(0);  // the second half of the weights after the first is used up
+      if (!RESID && s9 == 4) continue;
+      const double t = wt[s9] * w[s9 / 3][s9 % 3];
+      if (RESID) acc -= ((rmask >> s9) & 1u) ? t : 0.0;
+      else acc += t;
+    }
+    if (RESID) {
+      res[k] = acc;
+    } else {
+      const double diag = wt[9];
+      const bool nod = diag == 0.0;
+      const double q = (f[k] - acc) / (nod ? 1.0 : diag);  // smoother.hpp:136
+      res[k] = nod ? xi : xi + omega * (q - xi);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      w[0][c] = w[1][c];
+      w[1][c] = w[2][c];
+    }
+    if (BAR) __builtin_amdgcn_sched_barrier(0);  // one cell's reads at a time
+  }
+}
 // Row arithmetic of dict_rows, per-lane table entries from the LDS copy (mixed row types:
 // level boundaries).
 template <int UN, bool RESID, bool GS = false>
@@ -2132,7 +2205,7 @@ __device__ __forceinline__ double patch_eval(const double* buf, int cell, uint32
 // latency-bound stages need).  Cells outside the region or outside the matrix keep their
 // value; ZERO: such cells inside the region are set to 0.0 instead (the residual that the
 // restriction reads).  out (optional): rows of the patch proper also go to global memory.
-template <int UN, int UM, bool RESID, bool NT, bool ZERO, int TH, class FR = PatchFrame>
+template <int UN, int UM, bool RESID, bool NT, bool ZERO, int TH, class FR = PatchFrame, bool CBAR = false>
 __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int ntypes, double* buf,
                                             const PatchU& U, const PatchJ* tabJ, const PatchR* tabR,
                                             double omega, int l0, int l1, int c0, int c1, double* out) {
@@ -2151,6 +2224,11 @@ __device__ __forceinline__ void patch_stage(const PatchCells& pc, int m, int nty
     // with it too (their reads stay inside the guard lines) and dropped.  Every other wave
     // (level boundaries) takes the per-lane table.
     patch_eval_u<RESID, (UM & 0x145) != 0, false, (UM & 0x145) ? -1 : UM, FR>(buf, pc.cell0, U, pc.f, omega, res);
+  } else if (pc.coltyped) {
+    // a tile at a line end: the lane's type for all its cells (every row is inside the matrix; cells
+    // outside the region are evaluated and dropped, as on the scalar path)
+    patch_eval_c<RESID, CBAR, FR>(buf, pc.cell0, pc.lane_type(),
+                            reinterpret_cast<const double*>(RESID ? (const void*)tabR : (const void*)tabJ), pc.f, omega, res);
   } else {
 #pragma unroll
     for (int k = 0; k < PATCH_K; ++k)
@@ -2267,6 +2345,10 @@ __device__ __forceinline__ void patch_form_x(const PatchCells& pc, const PatchU&
   if (pc.uniform) {
 #pragma unroll
     for (int k = 0; k < PATCH_K; ++k) dv[k] = U.diag;
+  } else if (pc.coltyped) {  // one type per lane: one gather instead of PATCH_K
+    const double d = utabd[(size_t)pc.lane_type() * 19 + 18];
+#pragma unroll
+    for (int k = 0; k < PATCH_K; ++k) dv[k] = d;
   } else {
 #pragma unroll
     for (int k = 0; k < PATCH_K; ++k) dv[k] = utabd[(size_t)pc.type(k) * 19 + 18];
@@ -2304,9 +2386,14 @@ __device__ __forceinline__ void patch_form_x(const PatchCells& pc, const PatchU&
 // (patch_form_x, called here).
 // RINGS: the first held line is line -RINGS of the patch.
 // (pc.f of a row outside the matrix is f[0]: such a cell is never `did`, its results are dropped.)
-template <int RINGS, bool PROLONG, bool XF = false, class FR = PatchFrame>
+// ctype (the Jacobi legs and the seam; the multicolour kernel, !COLT, keeps the general path
+// there): the column types of the tiles with flag 254 (patch_tile_flags_kernel).  On such a tile a thread
+// reads ONE type byte, its column's, instead of PATCH_K row types, and the workgroup stages the slot-form
+// tables of patch_eval_c instead of the per-entry ones.  A wave of such a tile whose lanes all have one
+// type is `uniform` as on any tile.  Without ctype a flag 254 (none is built then) reads as 255.
+template <int RINGS, bool PROLONG, bool XF = false, class FR = PatchFrame, bool COLT = true>
 __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint8_t* __restrict__ tflag,
-                                           int tile, int n, int m,
+                                           const uint8_t* __restrict__ ctype, int tile, int n, int m,
                                            int j0, int i0, const double* __restrict__ x,
                                            const double* __restrict__ f,
                                            const uint8_t* __restrict__ rtype, int ntypes,
@@ -2349,13 +2436,32 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint
     }
   }
   __builtin_amdgcn_sched_barrier(0);  // the tile is in flight before the flag is looked at
-  const uint32_t tf = tflag ? patch_flag(tflag, tile) : 255u;
+  const uint32_t tf = tflag ? patch_flag(tflag, tile) : PATCH_FLAG_GENERAL;
   const uint32_t nty = (uint32_t)ntypes;
-  pc.flagged = tf != 255u;
+  pc.flagged = tf < PATCH_FLAG_COLTYPED;
+  pc.coltyped = COLT && ctype != nullptr && tf == PATCH_FLAG_COLTYPED;
   if (pc.flagged) {
     // (ty[] is not filled in -- type() does not read it: two registers less while the tile is in flight)
     pc.tu = tf;
     pc.uniform = true;
+  } else if (pc.coltyped) {
+    const uint32_t tl = (uint32_t)ctype[(int64_t)tile * FR::EC + col];  // (< ntypes: the flag kernel checked)
+    // slot tables of every type and of the absent one: entry t = (type t / PATCH_CT, word t % PATCH_CT)
+    const int t = (int)threadIdx.x, tt = t / PATCH_CT, tj = t - tt * PATCH_CT;
+    const bool stage = t < (ntypes + 1) * PATCH_CT;  // (<= PATCH_MAXTAB / 5 * PATCH_CT < FR::NT)
+    double vj = 0.0, vr = 0.0;
+    if (stage) {
+      vj = utabd[tt * 19 + (tj < 9 ? tj : 18)];
+      vr = tj < 9 ? utabd[tt * 19 + 9 + tj] : __longlong_as_double((long long)(uint32_t)utabi[tt * 2]);
+    }
+    pc.ty[0] = tl;
+    pc.ty[1] = 0;
+    pc.tu = (uint32_t)__builtin_amdgcn_readfirstlane((int)tl);
+    pc.uniform = __builtin_amdgcn_ballot_w64(tl != pc.tu) == 0;
+    if (stage) {
+      reinterpret_cast<double*>(tabJ)[t] = vj;
+      reinterpret_cast<double*>(tabR)[t] = vr;
+    }
   } else {
     PatchTabRow tb;
     patch_issue_tables(tb, ptab, nent);
@@ -2381,9 +2487,11 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint
   {
     // (opaque from here on: else the compiler folds type() back into eight registers of tf, filled --
     // and in the up-leg spilled -- on the flagged path)
-    int fl = pc.flagged;
+    int fl = (pc.flagged ? 1 : 0) | (pc.coltyped ? 2 : 0);
     asm("" : "+v"(fl));
-    pc.flagged = __builtin_amdgcn_readfirstlane(fl) != 0;
+    fl = __builtin_amdgcn_readfirstlane(fl);
+    pc.flagged = (fl & 1) != 0;
+    pc.coltyped = COLT && (fl & 2) != 0;
   }
   // the uniform type's table (scalar loads): on a flagged tile issued before the first vector wait
   patch_load_u(U, pc.uniform ? pc.tu : 0u, utabd, utabi);
@@ -2425,25 +2533,39 @@ __device__ __forceinline__ void patch_load(PatchCells& pc, PatchU& U, const uint
 // flag[tile] = the row type shared by EVERY row a patch kernel of `rings` rings loads for the tile
 // (lines -rings .. TH+rings, columns -4 .. TW+4 of the flat index, all inside the matrix), else 255.
 // (eh, ec: the held frame, columns -(ec - TW) / 2 .. of the flat index: that of the legs, or the seam kernel's)
+// ctype (optional): a tile that is not of one type but whose every held row is inside the matrix and whose
+// every held COLUMN has one row type over all eh lines (the tiles at the line ends, away from the first
+// and last lines) gets the flag PATCH_FLAG_COLTYPED, and ctype[tile * ec + c] = the type of held column c.
 __global__ __launch_bounds__(256) void patch_tile_flags_kernel(int n, int m, int px_count, int rings, int eh, int ec,
                                                                const uint8_t* __restrict__ rtype,
-                                                               int ntypes, uint8_t* __restrict__ flag) {
+                                                               int ntypes, uint8_t* __restrict__ flag,
+                                                               uint8_t* __restrict__ ctype) {
   const int tile = blockIdx.x;
   const int py = tile / px_count, px = tile - py * px_count;
   const int64_t base = (int64_t)(py * (eh - 2 * rings) - rings) * m + px * PATCH_TW - (ec - PATCH_TW) / 2;
   const int64_t first = base < 0 ? 0 : (base < n ? base : n - 1);
   const uint32_t t0 = rtype[first];
   int ok = base >= 0 && t0 < (uint32_t)ntypes;
+  int okc = base >= 0 && base + (int64_t)(eh - 1) * m + ec <= (int64_t)n;  // every held row is inside the matrix
   for (int q = threadIdx.x; q < eh * ec; q += 256) {
     const int le = q / ec, c = q - le * ec;
     const int64_t r = base + (int64_t)le * m + c;
-    ok = ok && r >= 0 && r < (int64_t)n && rtype[r < 0 ? 0 : (r < n ? r : n - 1)] == t0;
+    const uint32_t t = rtype[r < 0 ? 0 : (r < n ? r : n - 1)];
+    ok = ok && r >= 0 && r < (int64_t)n && t == t0;
+    if (okc) {
+      const uint32_t tc = rtype[base + c];  // the column's type on the first held line
+      okc = tc < (uint32_t)ntypes && t == tc;
+    }
   }
   ok = __syncthreads_and(ok);
-  if (threadIdx.x == 0) flag[tile] = ok ? (uint8_t)t0 : (uint8_t)255;
+  okc = __syncthreads_and(okc) && ctype != nullptr;
+  if (threadIdx.x == 0)
+    flag[tile] = ok ? (uint8_t)t0 : (okc ? (uint8_t)PATCH_FLAG_COLTYPED : (uint8_t)PATCH_FLAG_GENERAL);
+  if (!ok && okc && (int)threadIdx.x < ec) ctype[(int64_t)tile * ec + threadIdx.x] = rtype[base + threadIdx.x];
 }
+int patch_frame_columns(int rings) { return rings == PATCH_SEAM_RINGS_HOST ? 76 : PATCH_EC; }
 hipError_t launch_patch_tile_flags(int64_t n, int64_t m, int rings, const uint8_t* rtype, int ntypes,
-                                   uint8_t* flag, int64_t* n_tiles, hipStream_t st) {
+                                   uint8_t* flag, int64_t* n_tiles, hipStream_t st, uint8_t* ctype) {
   if (!patch_geometry_ok(n, m) || !patch_rings_ok(rings)) return hipErrorInvalidValue;
   const int64_t lines = (n + m - 1) / m;
   const int pxc = (int)(m / PATCH_TW);
@@ -2452,7 +2574,8 @@ hipError_t launch_patch_tile_flags(int64_t n, int64_t m, int rings, const uint8_
   if (n_tiles) *n_tiles = tiles;
   if (!flag) return hipSuccess;
   hipLaunchKernelGGL(patch_tile_flags_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (int)n, (int)m, pxc,
-                     rings, PATCH_EH, PATCH_EC, rtype, ntypes, flag);
+                     rings, PATCH_EH, PATCH_EC, rtype, ntypes, flag,
+                     ntypes < (int)PATCH_FLAG_COLTYPED ? ctype : nullptr);  // (the flag values 254, 255 are no types)
   return hipGetLastError();
 }
 
@@ -2499,9 +2622,16 @@ hipError_t launch_patch_coarse_flags(int64_t n, int64_t m, int rings, int64_t nH
 // DIAGNOSTIC BUILD ONLY (never shipped, never timed): per workgroup the 100 MHz wall clock at the
 // phase boundaries of the down-leg and the hardware id of the CU it ran on, into a buffer of its
 // own (tools/patch_stamps.py reads it: phase shares, workgroups resident per CU, dispatch gaps).
+// g_patch_stamps_rows != 0: only the launches on a level of that many rows leave stamps (one leg out
+// of a whole cycle).  Slot 6: (flag-array index of the tile << 8) | its flag as the kernel read it.
 __device__ unsigned long long* g_patch_stamps = nullptr;
-__device__ __forceinline__ void patch_stamp(int k) {
-  if (threadIdx.x == 0 && g_patch_stamps) {
+__device__ int g_patch_stamps_rows = 0;
+__device__ __forceinline__ void patch_stamp_flag(int n, int ftile, uint32_t tf) {
+  if (threadIdx.x == 0 && g_patch_stamps && (g_patch_stamps_rows == 0 || g_patch_stamps_rows == n))
+    g_patch_stamps[(size_t)blockIdx.x * 8 + 6] = ((unsigned long long)(unsigned)ftile << 8) | (tf & 255u);
+}
+__device__ __forceinline__ void patch_stamp(int k, int n) {
+  if (threadIdx.x == 0 && g_patch_stamps && (g_patch_stamps_rows == 0 || g_patch_stamps_rows == n)) {
     unsigned long long t = __builtin_amdgcn_s_memrealtime();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     g_patch_stamps[(size_t)blockIdx.x * 8 + k] = t;
@@ -2515,9 +2645,14 @@ __device__ __forceinline__ void patch_stamp(int k) {
 hipError_t debug_set_patch_stamps(unsigned long long* p) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_patch_stamps), &p, sizeof(p));
 }
-#define PATCH_STAMP(k) patch_stamp(k)
+hipError_t debug_set_patch_stamps_rows(int rows) {
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_patch_stamps_rows), &rows, sizeof(rows));
+}
+#define PATCH_STAMP(k) patch_stamp(k, n)
+#define PATCH_STAMP_FLAG(ftile, tf) patch_stamp_flag(n, ftile, tf)
 #else
 #define PATCH_STAMP(k)
+#define PATCH_STAMP_FLAG(ftile, tf)
 #endif
 template <int UN, int UM, bool FIRST, bool NT, bool XF = false, int RINGS = 3>
 // (four workgroups per CU = 7 waves per SIMD = 72 registers: measured against 6 and 5 waves again in
@@ -2539,7 +2674,7 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
     int nent, int ntypes, const double* x, const double* __restrict__ f, double* u_out, double* r_out, int nH,
     double* __restrict__ fH, const double* __restrict__ diagH, double* __restrict__ uH1,
     double omega, int xcd_map, int py0, const uint8_t* __restrict__ tflag,
-    const uint8_t* __restrict__ cflag, double dHu) {
+    const uint8_t* __restrict__ cflag, double dHu, const uint8_t* __restrict__ ctype) {
   __shared__ double buf[PATCH_BUF];
   __shared__ PatchJ tabJ[PATCH_MAXTAB];
   __shared__ PatchR tabR[PATCH_MAXTAB];
@@ -2553,7 +2688,8 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
   const int ftile = (py + py0) * px_count + px;
   static_assert(!(FIRST && XF), "level 0 starts from its own u");
   static_assert(RINGS == 3 || (RINGS == 2 && !FIRST), "three dependent stages (FIRST) need three rings");
-  patch_load<RINGS, false, XF>(pc, U, tflag, ftile, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, ptab, nent,
+  // (the 5-point kind keeps the general path on column-typed tiles: patch_eval_c's note)
+  patch_load<RINGS, false, XF, PatchFrame, UN != 5>(pc, U, tflag, ctype, ftile, n, m, j0, i0, x, f, rtype, ntypes, nullptr, 0, ptab, nent,
                                utabd, utabi, omega, buf, tabJ, tabR);
   patch_prologue<UM>(pc, U, buf, tabJ, tabR, ptab, nent);
   // every coarse row under this patch has the diagonal dHu (launch_patch_coarse_flags found that
@@ -2563,6 +2699,7 @@ __global__ __launch_bounds__(PATCH_NT, (UN == 5 ? AMG_PATCH_WAVES : AMG_PATCH_WA
   const bool cuni = uH1 && cflag && patch_flag(cflag, ftile) != 0;
   lds_barrier();
   PATCH_STAMP(1);
+  PATCH_STAMP_FLAG(ftile, pc.flagged ? pc.tu : (pc.coltyped ? PATCH_FLAG_COLTYPED : PATCH_FLAG_GENERAL));
   if (FIRST) {
     patch_stage<UN, UM, false, NT, false, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -2, TH + 2, -2,
                                               PATCH_TW + 3, nullptr);
@@ -2607,7 +2744,8 @@ __global__ __launch_bounds__(PATCH_NT, AMG_PATCH_WAVES) void patch_up_kernel(
     int n, int m, int px_count, const uint8_t* __restrict__ rtype, const double* __restrict__ ptab,
     const double* __restrict__ utabd, const int32_t* __restrict__ utabi,
     int nent, int ntypes, const double* x, const double* __restrict__ f, const double* __restrict__ uH, int nH,
-    double* u_out, double omega, int xcd_map, int py0, const uint8_t* __restrict__ tflag) {
+    double* u_out, double omega, int xcd_map, int py0, const uint8_t* __restrict__ tflag,
+    const uint8_t* __restrict__ ctype) {
   __shared__ double buf[PATCH_BUF];
   __shared__ PatchJ tabJ[PATCH_MAXTAB];
   __shared__ PatchR tabR[PATCH_MAXTAB];
@@ -2618,15 +2756,15 @@ __global__ __launch_bounds__(PATCH_NT, AMG_PATCH_WAVES) void patch_up_kernel(
   const int j0 = (py + py0) * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
-  patch_load<RINGS, true>(pc, U, tflag, (py + py0) * px_count + px, n, m, j0, i0, x, f, rtype, ntypes, uH, nH,
+  patch_load<RINGS, true>(pc, U, tflag, ctype, (py + py0) * px_count + px, n, m, j0, i0, x, f, rtype, ntypes, uH, nH,
                           ptab, nent, utabd, utabi, omega, buf, tabJ, tabR);
   patch_prologue<UM>(pc, U, buf, tabJ, tabR, ptab, nent);
   lds_barrier();
-  patch_stage<UN, UM, false, NT, false, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -1, TH + 1, -1,
-                                            PATCH_TW + 1, nullptr);
+  patch_stage<UN, UM, false, NT, false, TH, PatchFrame, true>(pc, m, ntypes, buf, U, tabJ, tabR, omega, -1, TH + 1, -1,
+                                                              PATCH_TW + 1, nullptr);
   lds_barrier();
-  patch_stage<UN, UM, false, NT, false, TH>(pc, m, ntypes, buf, U, tabJ, tabR, omega, 0, TH, 0, PATCH_TW,
-                                            nullptr);
+  patch_stage<UN, UM, false, NT, false, TH, PatchFrame, true>(pc, m, ntypes, buf, U, tabJ, tabR, omega, 0, TH, 0,
+                                                              PATCH_TW, nullptr);
   lds_barrier();
   patch_copy_out<NT, RINGS>(buf, u_out, n, m, j0, i0);
 }
@@ -2640,12 +2778,14 @@ __global__ __launch_bounds__(PATCH_NT, AMG_PATCH_WAVES) void patch_up_kernel(
 // the legs' own patch_stage on the legs' regions grown by the rings still to come, so every value
 // has the bits the two launches give it (halo cells are recomputed, as everywhere in K-Patch).
 constexpr int PATCH_SEAM_RINGS = 5;
+static_assert(PATCH_SEAM_RINGS == PATCH_SEAM_RINGS_HOST, "patch_frame_columns");
 template <int UN, int UM, bool NT, class FR, int WAVES>
 __global__ __launch_bounds__(FR::NT, WAVES) void patch_seam_kernel(
     int n, int m, int px_count, const uint8_t* __restrict__ rtype, const double* __restrict__ ptab,
     const double* __restrict__ utabd, const int32_t* __restrict__ utabi,
     int nent, int ntypes, const double* x, const double* __restrict__ f, const double* __restrict__ uH, int nH,
-    double* u_out, double* __restrict__ fH, double omega, int xcd_map, const uint8_t* __restrict__ tflag) {
+    double* u_out, double* __restrict__ fH, double omega, int xcd_map, const uint8_t* __restrict__ tflag,
+    const uint8_t* __restrict__ ctype) {
   __shared__ double buf[FR::BUF];
   __shared__ PatchJ tabJ[PATCH_MAXTAB];
   __shared__ PatchR tabR[PATCH_MAXTAB];
@@ -2656,7 +2796,7 @@ __global__ __launch_bounds__(FR::NT, WAVES) void patch_seam_kernel(
   const int j0 = py * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
-  patch_load<RINGS, true, false, FR>(pc, U, tflag, tile, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, ptab, nent,
+  patch_load<RINGS, true, false, FR>(pc, U, tflag, ctype, tile, n, m, j0, i0, x, f, rtype, ntypes, uH, nH, ptab, nent,
                                      utabd, utabi, omega, buf, tabJ, tabR);
   patch_prologue<UM, FR>(pc, U, buf, tabJ, tabR, ptab, nent);
   lds_barrier();
@@ -2766,7 +2906,7 @@ __global__ __launch_bounds__(PATCH_NT, AMG_RB_WAVES) void patch_rb_kernel(
   const int j0 = (py + py0) * TH, i0 = px * PATCH_TW;
   PatchCells pc;
   PatchU U;
-  patch_load<RINGS, PROLONG>(pc, U, tflag, (py + py0) * px_count + px, n, m, j0, i0, x, f, rtype, ntypes, uH, nH,
+  patch_load<RINGS, PROLONG, false, PatchFrame, false>(pc, U, tflag, nullptr, (py + py0) * px_count + px, n, m, j0, i0, x, f, rtype, ntypes, uH, nH,
                              ptab, nent, utabd, utabi, 1.0, buf, tabJ, tabR);
   patch_prologue<UM>(pc, U, buf, tabJ, tabR, ptab, nent);
   uint32_t cbits = 0;
@@ -2872,7 +3012,7 @@ hipError_t launch_patch_down(bool first, int64_t n, int64_t m, const PatchRef& P
   hipLaunchKernelGGL((patch_down_kernel<decltype(U)::value, decltype(M)::value, FST, decltype(NTF)::value, XFF, RG>), \
                      dim3(grid), dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, \
                      P.nent, P.ntypes, x, f, u_out, r_out, (int)nH, fH, diagH, uH1, omega, xm, py0, P.tflag,    \
-                     P.cflag, P.dHu)
+                     P.cflag, P.dHu, P.ctype)
     if (first) AMG_DOWN(true, false, 3);
     else if (xf && P.rings == 2) AMG_DOWN(false, true, 2);
     else if (xf) AMG_DOWN(false, true, 3);
@@ -2895,7 +3035,7 @@ hipError_t launch_patch_up(int64_t n, int64_t m, const PatchRef& P, const double
 #define AMG_UP(RG)                                                                                            \
   hipLaunchKernelGGL((patch_up_kernel<decltype(U)::value, decltype(M)::value, decltype(NTF)::value, RG>),     \
                      dim3(grid), dim3(PATCH_NT), 0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, \
-                     P.nent, P.ntypes, x, f, uH, (int)nH, u_out, omega, xm, py0, P.tflag)
+                     P.nent, P.ntypes, x, f, uH, (int)nH, u_out, omega, xm, py0, P.tflag, P.ctype)
     if (P.rings == 2) AMG_UP(2);
     else AMG_UP(3);
 #undef AMG_UP
@@ -2912,8 +3052,9 @@ int patch_seam_lines() { return SeamFrame::th(PATCH_SEAM_RINGS); }
 static bool patch_seam_geometry_ok(int64_t n, int64_t m) {
   return patch_geometry_ok(n, m) && n < ((int64_t)1 << 31) - 64 * m - 128;
 }
+static_assert(SeamFrame::EC == 76, "patch_frame_columns");
 hipError_t launch_patch_seam_flags(int64_t n, int64_t m, const uint8_t* rtype, int ntypes, uint8_t* flag,
-                                   int64_t* n_tiles, hipStream_t st) {
+                                   int64_t* n_tiles, hipStream_t st, uint8_t* ctype) {
   if (!patch_seam_geometry_ok(n, m)) return hipErrorInvalidValue;
   const int64_t lines = (n + m - 1) / m;
   const int pxc = (int)(m / PATCH_TW);
@@ -2922,7 +3063,8 @@ hipError_t launch_patch_seam_flags(int64_t n, int64_t m, const uint8_t* rtype, i
   if (n_tiles) *n_tiles = tiles;
   if (!flag) return hipSuccess;
   hipLaunchKernelGGL(patch_tile_flags_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (int)n, (int)m, pxc,
-                     PATCH_SEAM_RINGS, SeamFrame::EH, SeamFrame::EC, rtype, ntypes, flag);
+                     PATCH_SEAM_RINGS, SeamFrame::EH, SeamFrame::EC, rtype, ntypes, flag,
+                     ntypes < (int)PATCH_FLAG_COLTYPED ? ctype : nullptr);
   return hipGetLastError();
 }
 hipError_t launch_patch_seam(int64_t n, int64_t m, const PatchRef& P, const double* x, const double* f,
@@ -2940,7 +3082,7 @@ hipError_t launch_patch_seam(int64_t n, int64_t m, const PatchRef& P, const doub
 #define AMG_SEAM(NTF)                                                                                          \
   hipLaunchKernelGGL((patch_seam_kernel<5, 0x0BA, NTF, SeamFrame, PATCH_SEAM_WAVES>), dim3(grid), dim3(SeamFrame::NT), \
                      0, st, (int)n, (int)m, pxc, P.rtype, P.ptab, P.utabd, P.utabi, P.nent, P.ntypes, x, f, uH,  \
-                     (int)nH, u_out, fH, omega, xm, P.tflag)
+                     (int)nH, u_out, fH, omega, xm, P.tflag, P.ctype)
   if (P.nt) AMG_SEAM(true);
   else AMG_SEAM(false);
 #undef AMG_SEAM

@@ -280,6 +280,10 @@ struct PatchRef {
   // per tile of the level: the row type every row of the tile and its halo has, or 255
   // (launch_patch_tile_flags); null = always take the general path
   const uint8_t* tflag = nullptr;
+  // flag 254 = column-typed tile: every held row inside the matrix, every held column of one row type over
+  // all held lines; ctype[tile * patch_frame_columns(rings) + column] is that type.  null: the flags hold no 254
+  // (ctype: launch_patch_tile_flags / launch_patch_seam_flags, built beside tflag)
+  const uint8_t* ctype = nullptr;
   int nent = 0, ntypes = 0, un = 0, nt = 0;
   int umask = 0;  // slots (3 x 3, bit = slot) of the level's interior row type: selects the kernel kind
   // down-leg: per tile 1 when every coarse row under it has the diagonal dHu (launch_patch_coarse_flags)
@@ -291,7 +295,9 @@ hipError_t launch_patch_coarse_flags(int64_t n, int64_t m, int rings, int64_t nH
                                      double dref, uint8_t* cflag, hipStream_t st);
 // flag == null: only *n_tiles is computed (the size of the array)
 hipError_t launch_patch_tile_flags(int64_t n, int64_t m, int rings, const uint8_t* rtype, int ntypes,
-                                   uint8_t* flag, int64_t* n_tiles, hipStream_t st);
+                                   uint8_t* flag, int64_t* n_tiles, hipStream_t st, uint8_t* ctype = nullptr);
+// columns of the frame a launch of `rings` rings holds (72; the seam's, 5 rings: 76): the pitch of PatchRef::ctype
+int patch_frame_columns(int rings);
 bool patch_geometry_ok(int64_t n, int64_t m);
 int patch_un(int longest_row);
 int patch_default_umask(int un);
@@ -323,7 +329,7 @@ hipError_t launch_patch_up(int64_t n, int64_t m, const PatchRef& P, const double
 // launch_patch_seam_flags (or null).  5-point levels only (patch_un(P.un) == 5).
 int patch_seam_lines();
 hipError_t launch_patch_seam_flags(int64_t n, int64_t m, const uint8_t* rtype, int ntypes, uint8_t* flag,
-                                   int64_t* n_tiles, hipStream_t st);
+                                   int64_t* n_tiles, hipStream_t st, uint8_t* ctype = nullptr);
 hipError_t launch_patch_seam(int64_t n, int64_t m, const PatchRef& P, const double* x, const double* f,
                              const double* uH, int64_t nH, double* u_out, double* fH, double omega,
                              hipStream_t st);

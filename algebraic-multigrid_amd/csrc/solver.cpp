@@ -29,7 +29,10 @@
 
 using namespace amg_hip;
 #ifdef AMG_PATCH_STAMPS
-namespace amg_hip { hipError_t debug_set_patch_stamps(unsigned long long* p); }
+namespace amg_hip {
+hipError_t debug_set_patch_stamps(unsigned long long* p);
+hipError_t debug_set_patch_stamps_rows(int rows);
+}
 #endif
 
 namespace {
@@ -315,6 +318,15 @@ int g_axis_stencil = 1;      // amg_hip_set_axis_stencil: A/B switch, read when 
 int g_patch_xf = 1;          // amg_hip_set_patch_xf: A/B switch (same bits either way)
 int g_patch_tall = 1;        // amg_hip_set_patch_tall: A/B switch (same bits either way)
 int g_patch_seam = 1;        // amg_hip_set_patch_seam: A/B switch (same bits either way)
+int g_patch_coltype = 1;     // amg_hip_set_patch_coltype: A/B switch, read when a solver is created (same bits either way)
+// The column-type array beside a flag array of `tiles` tiles (whole words, zero-filled); left empty where the
+// switch is off: the flag kernels then build no flag 254.
+static hipError_t alloc_patch_ctype(DevMem& ct, int64_t tiles, int rings) {
+  ct.release();
+  if (!g_patch_coltype) return hipSuccess;
+  const hipError_t e = ct.alloc(((size_t)tiles * (size_t)patch_frame_columns(rings) + 3) & ~(size_t)3);
+  return e != hipSuccess ? e : hipMemset(ct.p, 0, ct.bytes);
+}
 
 // A level matrix on the device in one of the two layouts the kernels take.
 struct DevMat {
@@ -351,6 +363,9 @@ struct DevMat {
   // 5-point levels only).  All are built with the matrix (a byte per tile), whichever the level's
   // launches turn out to use.
   DevMem patch_tab, patch_utabd, patch_utabi, patch_flags, patch_flags2, patch_flags5;
+  // beside each flag array: the column types of its column-typed tiles (flag 254), a byte per tile and
+  // held column (patch_frame_columns(rings)); empty where the switch was off: the flags then hold no 254
+  DevMem patch_ctype, patch_ctype2, patch_ctype5;
   // per tile of the level's down-leg (patch_crings rings): the coarse rows under it share the
   // diagonal patch_dH (set_patch_coarse_flags)
   DevMem patch_cflags;
@@ -365,6 +380,7 @@ struct DevMat {
     P.rtype = drtype.as<uint8_t>();
     P.tflag = g_patch_tile_flags ? (rings == 2 ? patch_flags2 : (rings == 5 ? patch_flags5 : patch_flags)).as<uint8_t>()
                                  : nullptr;
+    P.ctype = P.tflag ? (rings == 2 ? patch_ctype2 : (rings == 5 ? patch_ctype5 : patch_ctype)).as<uint8_t>() : nullptr;
     P.cflag = g_patch_tile_flags && rings == patch_crings ? patch_cflags.as<uint8_t>() : nullptr;
     P.dHu = patch_dH;
     P.ptab = patch_tab.as<double>();
@@ -675,20 +691,23 @@ hipError_t finish_dict(const DictMat& T, int64_t n, int64_t diag_shift, DevMat* 
       int64_t tiles = 0;
       for (int rings = 2; rings <= 3; ++rings) {  // (3 last: `tiles` below counts the 42-line tiles)
         DevMem& F = rings == 2 ? D->patch_flags2 : D->patch_flags;
+        DevMem& CT = rings == 2 ? D->patch_ctype2 : D->patch_ctype;
         if ((e = launch_patch_tile_flags(n, D->patch_m, rings, nullptr, nty, nullptr, &tiles, nullptr)) != hipSuccess) return e;
         // whole 32-bit words, zero-filled: the kernels read the word that holds a tile's flag
         if ((e = F.alloc(((size_t)tiles + 3) & ~(size_t)3)) != hipSuccess) return e;
         if ((e = hipMemset(F.p, 0, F.bytes)) != hipSuccess) return e;
+        if ((e = alloc_patch_ctype(CT, tiles, rings)) != hipSuccess) return e;
         if ((e = launch_patch_tile_flags(n, D->patch_m, rings, D->drtype.as<uint8_t>(), nty, F.as<uint8_t>(),
-                                         nullptr, nullptr)) != hipSuccess) return e;
+                                         nullptr, nullptr, CT.as<uint8_t>())) != hipSuccess) return e;
       }
       if (patch_un(un) == 5) {  // the seam launch's tiles (the kernel kind it is instantiated for)
         int64_t t5 = 0;
         if ((e = launch_patch_seam_flags(n, D->patch_m, nullptr, nty, nullptr, &t5, nullptr)) == hipSuccess) {
           if ((e = D->patch_flags5.alloc(((size_t)t5 + 3) & ~(size_t)3)) != hipSuccess) return e;
           if ((e = hipMemset(D->patch_flags5.p, 0, D->patch_flags5.bytes)) != hipSuccess) return e;
+          if ((e = alloc_patch_ctype(D->patch_ctype5, t5, 5)) != hipSuccess) return e;
           if ((e = launch_patch_seam_flags(n, D->patch_m, D->drtype.as<uint8_t>(), nty, D->patch_flags5.as<uint8_t>(),
-                                           nullptr, nullptr)) != hipSuccess) return e;
+                                           nullptr, nullptr, D->patch_ctype5.as<uint8_t>())) != hipSuccess) return e;
         }  // (a level too large for the seam frame's index range keeps the two launches: no flags, patch_seam_ok)
       }
       if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
@@ -4939,6 +4958,7 @@ void amg_hip_set_axis_stencil(int32_t on) { g_axis_stencil = on ? 1 : 0; }
 void amg_hip_set_patch_xf(int32_t on) { g_patch_xf = on ? 1 : 0; }
 void amg_hip_set_patch_tall(int32_t on) { g_patch_tall = on ? 1 : 0; }
 void amg_hip_set_patch_seam(int32_t on) { g_patch_seam = on ? 1 : 0; }
+void amg_hip_set_patch_coltype(int32_t on) { g_patch_coltype = on ? 1 : 0; }
 void amg_hip_set_band_chain(int32_t on) { g_no_band_chain = on ? 0 : 1; }
 void amg_hip_set_tail_fusion(int32_t on) { g_tail_fusion = on ? 1 : 0; }
 void amg_hip_set_pair_duo(int32_t on) { g_pair_duo = on ? 1 : 0; }
@@ -5658,6 +5678,10 @@ amg_hip_status amg_hip_window_run(amg_hip_solver* s, int32_t part) {
 #ifdef AMG_PATCH_STAMPS
 amg_hip_status amg_hip_debug_patch_stamps(void* dev_ptr) {  // diagnostic build only (tools/patch_stamps.py)
   HIP_TRY(debug_set_patch_stamps((unsigned long long*)dev_ptr));
+  return AMG_HIP_OK;
+}
+amg_hip_status amg_hip_debug_patch_stamps_rows(int32_t rows) {  // 0: every down-leg stamps; else the level of `rows` rows
+  HIP_TRY(debug_set_patch_stamps_rows((int)rows));
   return AMG_HIP_OK;
 }
 #endif
@@ -6442,6 +6466,29 @@ int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t 
   if (form == LEG_MC_PATCH) return patch_tile_lines(3);
   if (form != LEG_PATCH) return 0;
   return patch_tile_lines(patch_rings(s, leg == 0 && level == 0));
+}
+
+amg_hip_status amg_hip_patch_tile_classes(amg_hip_solver* s, int32_t level, int32_t rings, int64_t* out) {
+  if (!s || !out || s->opt.host_only || level < 0 || level >= (int32_t)s->lv.size())
+    return fail(AMG_HIP_EINVAL, "amg_hip_patch_tile_classes: bad argument");
+  if (rings != 2 && rings != 3 && rings != 5)
+    return fail(AMG_HIP_EINVAL, "amg_hip_patch_tile_classes: rings is 2 (44-line tiles), 3 (42) or 5 (the seam's, 38)");
+  const LegForm form = current_plan(s).lv[(size_t)level].up;  // (a patch level is one on both legs)
+  const DevMat& A = s->lv[(size_t)level].A_rows;
+  const DevMem& F = rings == 2 ? A.patch_flags2 : (rings == 5 ? A.patch_flags5 : A.patch_flags);
+  if ((form != LEG_PATCH && form != LEG_MC_PATCH) || !A.patch || !F.p)
+    return fail(AMG_HIP_EINVAL, "amg_hip_patch_tile_classes: the level is no K-Patch level (or has no tiles of this geometry)");
+  int64_t tiles = 0;
+  const int64_t n = s->lv[(size_t)level].n;
+  const amg_hip_status r = set_device(s);
+  if (r != AMG_HIP_OK) return r;
+  HIP_TRY(rings == 5 ? launch_patch_seam_flags(n, A.patch_m, nullptr, A.patch_ntypes, nullptr, &tiles, nullptr)
+                     : launch_patch_tile_flags(n, A.patch_m, rings, nullptr, A.patch_ntypes, nullptr, &tiles, nullptr));
+  std::vector<uint8_t> fl((size_t)tiles);
+  HIP_TRY(hipMemcpy(fl.data(), F.p, fl.size(), hipMemcpyDeviceToHost));
+  out[0] = out[1] = out[2] = 0;
+  for (uint8_t f : fl) ++out[f == 255 ? 2 : (f == 254 ? 1 : 0)];
+  return AMG_HIP_OK;
 }
 
 amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int32_t name_cap,

@@ -283,6 +283,13 @@ void amg_hip_set_patch_xf(int32_t on);
  * 42 lines everywhere.  Process-wide, read when a solver is created.  Same bits either way: an
  * A/B switch for tests and measurements.                                                      */
 void amg_hip_set_patch_tall(int32_t on);
+/* K-Patch column-typed tiles: on (default), a tile whose held rows all lie inside the matrix and whose
+ * every held column has one row type over all held lines -- the tiles at the two ends of the grid lines,
+ * which never consist of one row type -- is recognised at set-up (tile flag 254) and evaluated with a
+ * sliding 3 x 3 window and the weights of the lane's type, instead of the per-entry tables of the general
+ * path.  Off: no such flag is built.  Process-wide, read when a solver is created.  Same bits either
+ * way: an A/B switch for tests and measurements.                                                    */
+void amg_hip_set_patch_coltype(int32_t on);
 /* K-Patch seam: on (default), amg_hip_vcycles(s, n) with n >= 2 -- and amg_hip_solve between two
  * residual checks -- runs the level-0 up-leg of one cycle and the level-0 down-leg of the next as ONE
  * launch, so the level-0 vector between two cycles is neither stored nor loaded again (25 n_0 bytes
@@ -1172,6 +1179,10 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
  * up-leg (leg 1): 42 or 44 on a K-Patch level, 0 where the level is no K-Patch level.  leg 2: of the
  * seam launch amg_hip_vcycles(s, n >= 2) runs on level 0 (38), 0 where this solver runs none.   */
 int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t leg);
+/* Tiles of `level` by class, for the launches with `rings` halo rings (2: tiles of 44 lines, 3: 42, 5: the
+ * seam launch's, 38): out[0] = tiles of one row type, out[1] = column-typed tiles, out[2] = general
+ * tiles.  AMG_HIP_EINVAL where the level is no K-Patch level or has no tiles of that geometry.        */
+amg_hip_status amg_hip_patch_tile_classes(amg_hip_solver* s, int32_t level, int32_t rings, int64_t* out);
 /* Name of the kernel amg_hip_profile_fine_sweep times (as rocprofv3 prints it, without the
  * namespace), the number of Jacobi sweeps over level 0 one launch of it performs, and the
  * bytes one launch has to move (what the kernel reads and writes once: SURVEY 8(d)'s CSR
