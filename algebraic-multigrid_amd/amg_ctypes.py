@@ -128,6 +128,9 @@ _SIGS = {
     "amg_hip_create_tensor_opdep": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
                                               C.c_int32, _i32p, C.c_int64, C.POINTER(Options),
                                               C.POINTER(C.c_void_p)]),
+    "amg_hip_create_tensor_opdep_dev": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_int32, _i64p, C.c_int32, _i32p, C.c_int64,
+                                                  C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_set_axis_stencil": (None, [C.c_int32]),
     "amg_hip_get_axis_weights": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
     "amg_hip_axis_restrict": (C.c_int, [C.c_int32, _i64p, C.c_int32, _f64p, _f64p, _f64p]),
@@ -823,7 +826,7 @@ class Multigrid:
                    no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                    exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
                    window=False, host_galerkin=False, fuse_prolong=False, natural_sides=0, singular=False,
-                   cyclic_lines=False, _semi=None, _periodic=None):
+                   cyclic_lines=False, _semi=None, _periodic=None, _opdep=None):
         """Multigrid.tensor for a matrix that sits on the device, with the set-up on the device
         (amg_hip_create_tensor_dev).  A is in CSR: crow (n + 1 int32 row pointers), col (int32,
         ascending inside a row), val (float64), and b (n float64), each a contiguous 1-D torch tensor
@@ -888,6 +891,12 @@ class Multigrid:
                                                           d3.ctypes.data_as(_i64p), int(per), int(n_levels),
                                                           None if masks is None else _p32(masks), C.byref(o),
                                                           C.byref(h))
+        elif _opdep is not None:  # tensor_opdep_dev
+            masks, _, min_coarse = _opdep
+            st = lib().amg_hip_create_tensor_opdep_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
+                                                       d3.ctypes.data_as(_i64p), int(n_levels),
+                                                       None if masks is None else _p32(masks), int(min_coarse),
+                                                       C.byref(o), C.byref(h))
         elif _semi is not None:  # tensor_semi_dev
             masks, theta, min_coarse = _semi
             st = lib().amg_hip_create_tensor_semi_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
@@ -958,6 +967,15 @@ class Multigrid:
         (amg_hip_create_tensor_semi_dev); arguments as for Multigrid.tensor_dev."""
         return cls.tensor_dev(crow, col, val, b, dims, n_levels,
                               _semi=cls._semi_rule(n_levels, axis_masks, theta, min_coarse), **opts)
+
+    @classmethod
+    def tensor_opdep_dev(cls, crow, col, val, b, dims, n_levels, axis_masks=None, min_coarse=32, **opts):
+        """Multigrid.tensor_opdep for a CSR matrix that sits on the device, with the set-up on the device
+        (amg_hip_create_tensor_opdep_dev: K-AxisWeights and K-AxisGalerkin per level); arguments as for
+        Multigrid.tensor_dev.  The same solver bit for bit as Multigrid.tensor_opdep on the CSC arrays;
+        the silent fall-backs of Multigrid.tensor_dev apply, and set_axis_stencil(0) is one more."""
+        return cls.tensor_dev(crow, col, val, b, dims, n_levels,
+                              _opdep=cls._semi_rule(n_levels, axis_masks, 1.0, min_coarse), **opts)
 
     @classmethod
     def tensor_periodic(cls, colptr, rowind, val, b, dims, n_levels, periodic_axes, axis_masks=None, **opts):

@@ -318,6 +318,33 @@ Sparse axis_P_from_weights(int dim, const int64_t d[3], int axis, const double* 
   return P;
 }
 
+std::string axis_opdep_row(int64_t i, const int32_t* idx, const double* val, int32_t len, int64_t stride, int64_t m,
+                           int axis, double w[2]) {
+  auto bad = [&](const char* what, double v) {
+    return "row " + std::to_string(i) + ": " + what + " is " + std::to_string(v) +
+           " (the entries of the row, collapsed onto axis " + std::string(1, "xyz"[axis]) + ")";
+  };
+  const int64_t c = (i / stride) % m;
+  w[0] = w[1] = 0.0;
+  double sm = 0.0, s0 = 0.0, sp = 0.0;
+  for (int32_t p = 0; p < len; ++p) {
+    const int64_t dc = (idx[p] / stride) % m - c;
+    if (dc == -1) sm += val[p];
+    else if (dc == 0) s0 += val[p];
+    else if (dc == 1) sp += val[p];
+  }
+  if (s0 == 0.0 || !std::isfinite(s0)) return bad("the diagonal sum s_0", s0);
+  if (c >= 2) {
+    w[0] = (-sm) / s0;
+    if (!std::isfinite(w[0])) return bad("the weight w_lo", w[0]);
+  }
+  if (c + 1 < m) {
+    w[1] = (-sp) / s0;
+    if (!std::isfinite(w[1])) return bad("the weight w_hi", w[1]);
+  }
+  return "";
+}
+
 std::string axis_opdep_P(const Sparse& M, int dim, const int64_t d[3], int axis, Sparse* P,
                          std::vector<double>* W) {
   const int64_t m = d[axis], mH = m / 2;
@@ -325,31 +352,12 @@ std::string axis_opdep_P(const Sparse& M, int dim, const int64_t d[3], int axis,
   const int64_t n = M.n_outer;
   W->assign((size_t)(2 * (n - (n / m) * mH)), 0.0);
   int64_t e = 0;  // flat index on the grid of the even points: they come in ascending fine order
-  auto bad = [&](int64_t i, const char* what, double v) {
-    return "row " + std::to_string(i) + ": " + what + " is " + std::to_string(v) +
-           " (the entries of the row, collapsed onto axis " + std::string(1, "xyz"[axis]) + ")";
-  };
   for (int64_t i = 0; i < n; ++i) {
-    const int64_t c = (i / stride) % m;
-    if (c & 1) continue;
-    double sm = 0.0, s0 = 0.0, sp = 0.0;
-    for (int32_t p = M.ptr[i]; p < M.ptr[i + 1]; ++p) {
-      const int64_t dc = (M.idx[p] / stride) % m - c;
-      if (dc == -1) sm += M.val[p];
-      else if (dc == 0) s0 += M.val[p];
-      else if (dc == 1) sp += M.val[p];
-    }
-    if (s0 == 0.0 || !std::isfinite(s0)) return bad(i, "the diagonal sum s_0", s0);
-    if (c >= 2) {
-      const double w = (-sm) / s0;
-      if (!std::isfinite(w)) return bad(i, "the weight w_lo", w);
-      (*W)[(size_t)(2 * e)] = w;
-    }
-    if (c + 1 < m) {
-      const double w = (-sp) / s0;
-      if (!std::isfinite(w)) return bad(i, "the weight w_hi", w);
-      (*W)[(size_t)(2 * e + 1)] = w;
-    }
+    if ((i / stride) % m & 1) continue;
+    const int32_t p0 = M.ptr[i];
+    const std::string bad =
+        axis_opdep_row(i, M.idx.data() + p0, M.val.data() + p0, M.ptr[i + 1] - p0, stride, m, axis, W->data() + 2 * e);
+    if (!bad.empty()) return bad;
     ++e;
   }
   *P = axis_P_from_weights(dim, d, axis, W->data());

@@ -79,6 +79,12 @@ uint32_t tensor_auto_mask(int dim, const int64_t dims[3], const double w[3], dou
 // Returns "" or what is wrong (s_0 or a weight that is zero-divided or not finite), naming the row.
 std::string axis_opdep_P(const Sparse& rows, int dim, const int64_t dims[3], int axis, Sparse* P,
                          std::vector<double>* W);
+// The per-row part of axis_opdep_P: row i (even axis coordinate; its `len` entries idx / val in
+// ascending column order) on an axis of length m and flat stride `stride`.  w[0] = w_lo, w[1] = w_hi,
+// 0.0 where the neighbour does not exist.  Returns "" or axis_opdep_P's message for this row; the
+// device set-up (K-AxisWeights) words the row it refused with it.
+std::string axis_opdep_row(int64_t i, const int32_t* idx, const double* val, int32_t len, int64_t stride, int64_t m,
+                           int axis, double w[2]);
 // The CSC P (and nothing else) of a compact weight array: what axis_opdep_P builds from its own W.
 Sparse axis_P_from_weights(int dim, const int64_t dims[3], int axis, const double* W);
 // The automatic rule of amg_hip_create_tensor_opdep: the eligible axis (a < dim, dims[a] >= 2) with

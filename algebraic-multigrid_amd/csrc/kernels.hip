@@ -7048,6 +7048,253 @@ hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uin
   return hipGetLastError();
 }
 
+// ------------------------------------------------ K-AxisWeights / K-AxisGalerkin ---
+// The device set-up of a level that coarsens ONE axis with weights from its own matrix
+// (amg_hip_create_tensor_opdep_dev; host_setup.hpp: axis_opdep_P, axis_opdep_row).
+//
+// K-AxisWeights.  One lane per fine point with an even axis coordinate, i.e. per pair of W: lane e
+// of the even-point grid (the level's grid with the axis shortened to mE = m - floor(m / 2), x
+// fastest) walks row i of CSR(A_l) in ascending column order and adds each value into s_m, s_0 or
+// s_p (from +0.0) by the axis coordinate of its column -- one serial chain per sum, the host's order,
+// so the bits are the host's.  One negation and one IEEE division per weight; 0.0 where the neighbour
+// does not exist.  A row the host would refuse (s_0 zero or not finite, a weight not finite) sends its
+// fine index through atomicMin into *first_bad (INT32_MAX before the launch), as K-CsrCheck does.
+// Index arithmetic: 32-bit under the device set-up's guard n < 2^28 (2 e + 1 included), coordinates
+// by tg_divmod.
+struct AxisSetupGrid {
+  uint32_t nx, ny, nz;  // fine
+  uint32_t m, mE;       // the axis: fine length, even points m - floor(m / 2)
+  uint32_t axis;
+  double inv_nx, inv_ny, inv_ex, inv_ey;  // reciprocals of nx, ny and of the even grid's x / y lengths
+};
+__device__ __forceinline__ uint32_t ax_coord(uint32_t k, const AxisSetupGrid& g) {  // axis coordinate of fine index k
+  uint32_t q, kx, ky, kz;
+  tg_divmod(k, g.nx, g.inv_nx, &q, &kx);
+  if (g.axis == 0u) return kx;
+  tg_divmod(q, g.ny, g.inv_ny, &kz, &ky);
+  return g.axis == 1u ? ky : kz;
+}
+__global__ __launch_bounds__(256) void axis_weights_kernel(AxisSetupGrid g, uint32_t n_even,
+                                                           const int32_t* __restrict__ arp,
+                                                           const int32_t* __restrict__ acol,
+                                                           const double* __restrict__ aval, double* __restrict__ W,
+                                                           int32_t* __restrict__ first_bad) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= n_even) return;
+  const uint32_t ex = g.axis == 0u ? g.mE : g.nx, ey = g.axis == 1u ? g.mE : g.ny;
+  uint32_t q, x, y, z;
+  tg_divmod(e, ex, g.inv_ex, &q, &x);
+  tg_divmod(q, ey, g.inv_ey, &z, &y);
+  const uint32_t c = 2u * (g.axis == 0u ? x : (g.axis == 1u ? y : z));
+  const uint32_t i = g.axis == 0u ? (z * g.ny + y) * g.nx + c
+                                  : (g.axis == 1u ? (z * g.ny + c) * g.nx + x : (c * g.ny + y) * g.nx + x);
+  double sm = 0.0, s0 = 0.0, sp = 0.0;
+  for (int32_t p = arp[i], pe = arp[i + 1]; p < pe; ++p) {
+    const int32_t dc = (int32_t)ax_coord((uint32_t)acol[p], g) - (int32_t)c;
+    const double v = aval[p];
+    if (dc == -1) sm += v;
+    else if (dc == 0) s0 += v;
+    else if (dc == 1) sp += v;
+  }
+  const bool has_lo = c >= 2u, has_hi = c + 1u < g.m;
+  const double wlo = has_lo ? (-sm) / s0 : 0.0;
+  const double whi = has_hi ? (-sp) / s0 : 0.0;
+  // finite: |x| < inf; a NaN fails the comparison
+  const bool bad = s0 == 0.0 || !(fabs(s0) < HUGE_VAL) || !(fabs(wlo) < HUGE_VAL) || !(fabs(whi) < HUGE_VAL);
+  if (bad) atomicMin(first_bad, (int32_t)i);
+  *reinterpret_cast<double2*>(W + 2u * (size_t)e) = make_double2(wlo, whi);  // W is 16-byte aligned
+}
+static bool axis_setup_grid(int dim, const int64_t dims[3], int axis, AxisSetupGrid* g, uint32_t* n_even) {
+  if ((dim != 2 && dim != 3) || !dims || axis < 0 || axis >= dim) return false;
+  const int64_t nx = dims[0], ny = dims[1], nz = dim == 3 ? dims[2] : 1;
+  if (nx < 1 || ny < 1 || nz < 1 || (dim == 2 && dims[2] != 1) || dims[axis] < 2) return false;
+  if (nx >= ((int64_t)1 << 28) / ny / nz) return false;  // 32-bit indices, 2 e + 1 included
+  g->nx = (uint32_t)nx;
+  g->ny = (uint32_t)ny;
+  g->nz = (uint32_t)nz;
+  g->m = (uint32_t)dims[axis];
+  g->mE = g->m - g->m / 2u;
+  g->axis = (uint32_t)axis;
+  const uint32_t ex = axis == 0 ? g->mE : g->nx, ey = axis == 1 ? g->mE : g->ny, ez = axis == 2 ? g->mE : g->nz;
+  g->inv_nx = 1.0 / (double)g->nx;
+  g->inv_ny = 1.0 / (double)g->ny;
+  g->inv_ex = 1.0 / (double)ex;
+  g->inv_ey = 1.0 / (double)ey;
+  *n_even = ex * ey * ez;
+  return true;
+}
+hipError_t launch_axis_weights(int dim, const int64_t dims[3], int axis, const int32_t* arp, const int32_t* acol,
+                               const double* aval, double* W, int32_t* first_bad, hipStream_t st) {
+  AxisSetupGrid g;
+  uint32_t n_even = 0;
+  if (!axis_setup_grid(dim, dims, axis, &g, &n_even) || (reinterpret_cast<uintptr_t>(W) & 15u)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(axis_weights_kernel, dim3((n_even + 255u) / 256u), dim3(256), 0, st, g, n_even, arp, acol, aval, W,
+                     first_bad);
+  return hipGetLastError();
+}
+
+// K-AxisGalerkin.  A_H = R (A P) for the one-axis pair with the weights W of K-AxisWeights; the form
+// is K-TensorGalerkin's (a group of SLOTS lanes per coarse row, the box of reachable coarse columns
+// by a min / max butterfly, lane s owning the s-th column in ascending order, A P fused into the R
+// pass in registers, *overflow when a box exceeds the group).  What differs:
+//  - P(k, J) along the axis, ck the axis coordinate of k: ck odd: 1.0 at J = (ck - 1) / 2; ck even:
+//    W[2 e(k)] at ck / 2 - 1 and W[2 e(k) + 1] at ck / 2, where that coarse point exists; the other
+//    coordinates equal.  R(I, i) = P(i, I): fine rows 2 I (w_hi of that point), 2 I + 1 (1.0) and
+//    2 I + 2 (w_lo of that point, when < m), ascending for every axis.
+//  - The structure is geometric: an entry of P exists for every neighbour that exists, whatever its
+//    value (axis_opdep_P keeps 0.0 and -0.0, spgemm_rows keeps an output entry as soon as one stored
+//    entry of P is touched), so the hit is "the neighbour exists", never w != 0.0, and a +-0.0 weight
+//    still contributes its signed-zero product.
+//  - The weights are no powers of two: every product rounds (-ffp-contract=off keeps it apart from
+//    the addition).  t = a_ik * P(k, J) for k ascending, first assigned, the rest added; then
+//    R(I, i) * (A P)(i, J) for i ascending, first assigned, the rest added -- spgemm_rows' order.
+//    The multiplications by 1.0 are done.
+// The count pass (FILL = false) reads neither the values nor W.
+template <int SLOTS, bool FILL>
+__global__ __launch_bounds__(256) void axis_galerkin_kernel(
+    TensorGrid g, uint32_t axis, uint32_t mE, double inv_nx, double inv_ny, const int32_t* __restrict__ arp,
+    const int32_t* __restrict__ acol, const double* __restrict__ aval, const double* __restrict__ W,
+    int32_t* __restrict__ cnt, const int32_t* __restrict__ orp, int32_t* __restrict__ ocol,
+    double* __restrict__ oval, int32_t* __restrict__ overflow) {
+  constexpr uint32_t RPB = 256u / SLOTS;  // coarse rows of a workgroup
+  const uint32_t nH = g.mx * g.my * g.mz;
+  const uint32_t s = threadIdx.x % SLOTS;
+  const uint32_t row0 = blockIdx.x * RPB + threadIdx.x / SLOTS;
+  const bool live = row0 < nH;
+  const uint32_t row = live ? row0 : nH - 1u;  // the tail lanes repeat the last row and write nothing
+  const uint32_t I = row % g.mx, qr = row / g.mx, J = qr % g.my, K = qr / g.my;
+  const uint32_t m = axis == 0u ? g.nx : (axis == 1u ? g.ny : g.nz);       // fine length of the axis
+  const uint32_t stride = axis == 0u ? 1u : (axis == 1u ? g.nx : g.nx * g.ny);  // of the axis, fine and even grids
+  const uint32_t H = axis == 0u ? I : (axis == 1u ? J : K);
+  // fine index of R's first row (axis coordinate 2 H) and the even-grid index of that point
+  const uint32_t i0 = axis == 0u ? (K * g.ny + J) * g.nx + 2u * I
+                                 : (axis == 1u ? (K * g.ny + 2u * J) * g.nx + I : (2u * K * g.ny + J) * g.nx + I);
+  const uint32_t e0 = axis == 0u ? (K * g.ny + J) * mE + I : (axis == 1u ? (K * mE + J) * g.nx + I : row);
+  const uint32_t nt = 2u * H + 2u < m ? 3u : 2u;  // fine rows of R's row
+  int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
+  if (s < nt) {
+    const uint32_t i = i0 + s * stride;
+    for (int32_t p = arp[i], e = arp[i + 1]; p < e; ++p) {
+      uint32_t kx, ky, kz, q;
+      tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
+      tg_divmod(q, g.ny, inv_ny, &kz, &ky);
+      int32_t l[3], h[3];
+      tg_cols(kx, g.mx, g.cx, &l[0], &h[0]);
+      tg_cols(ky, g.my, g.cy, &l[1], &h[1]);
+      tg_cols(kz, g.mz, g.cz, &l[2], &h[2]);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = l[a] < lo[a] ? l[a] : lo[a];
+        hi[a] = h[a] > hi[a] ? h[a] : hi[a];
+      }
+    }
+  }
+#pragma unroll
+  for (int d = SLOTS / 2; d >= 1; d >>= 1)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int32_t ol = __shfl_xor(lo[a], d, SLOTS), oh = __shfl_xor(hi[a], d, SLOTS);
+      lo[a] = ol < lo[a] ? ol : lo[a];
+      hi[a] = oh > hi[a] ? oh : hi[a];
+    }
+  uint32_t bx = 0, by = 0, vol = 0;
+  if (hi[0] >= lo[0]) {  // else: every row of A under this coarse row is empty
+    bx = (uint32_t)(hi[0] - lo[0] + 1);
+    by = (uint32_t)(hi[1] - lo[1] + 1);
+    const uint32_t bz = (uint32_t)(hi[2] - lo[2] + 1);
+    if (bx > (uint32_t)SLOTS || by > (uint32_t)SLOTS || bz > (uint32_t)SLOTS || bx * by * bz > (uint32_t)SLOTS) {
+      if (s == 0 && live) atomicOr(overflow, 1);
+    } else {
+      vol = bx * by * bz;
+    }
+  }
+  // this lane's entry (I, J) of R (A P)
+  bool hit = false;
+  double acc = 0.0;
+  int32_t Jc[3] = {0, 0, 0};
+  if (s < vol) {
+    Jc[0] = lo[0] + (int32_t)(s % bx);
+    Jc[1] = lo[1] + (int32_t)((s / bx) % by);
+    Jc[2] = lo[2] + (int32_t)(s / (bx * by));
+    const int32_t Ja = axis == 0u ? Jc[0] : (axis == 1u ? Jc[1] : Jc[2]);
+    for (uint32_t t = 0; t < nt; ++t) {
+      const uint32_t i = i0 + t * stride;
+      double r = 1.0;  // R(I, i)
+      if (FILL && t == 0u) r = W[2u * e0 + 1u];
+      if (FILL && t == 2u) r = W[2u * (e0 + stride)];
+      bool hit_i = false;
+      double ap = 0.0;  // (A P)(i, J)
+      for (int32_t p = arp[i], e = arp[i + 1]; p < e; ++p) {
+        uint32_t kc[3], q;
+        tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kc[0]);
+        tg_divmod(q, g.ny, inv_ny, &kc[2], &kc[1]);
+        const uint32_t ka = axis == 0u ? kc[0] : (axis == 1u ? kc[1] : kc[2]);
+        // the other coordinates equal; along the axis J is (ka - 1) / 2, or one of ka / 2 - 1, ka / 2
+        bool other = true;
+#pragma unroll
+        for (uint32_t a = 0; a < 3u; ++a) other = other && (a == axis || (int32_t)kc[a] == Jc[a]);
+        const int32_t half = (int32_t)(ka >> 1);
+        const bool odd = (ka & 1u) != 0u;
+        const bool at_lo = !odd && Ja == half - 1, at_hi = !odd && Ja == half;  // Ja lies in [0, floor(m / 2))
+        if (other && ((odd && Ja == half) || at_lo || at_hi)) {
+          if (FILL) {
+            double w = 1.0;
+            if (!odd) {  // even point ka / 2 of the axis, the other coordinates k's own
+              const uint32_t ek = axis == 0u ? (kc[2] * g.ny + kc[1]) * mE + (uint32_t)half
+                                             : (axis == 1u ? (kc[2] * mE + (uint32_t)half) * g.nx + kc[0]
+                                                           : ((uint32_t)half * g.ny + kc[1]) * g.nx + kc[0]);
+              w = W[2u * ek + (at_hi ? 1u : 0u)];
+            }
+            const double tt = aval[p] * w;
+            ap = hit_i ? ap + tt : tt;  // first product: assign
+          }
+          hit_i = true;
+        }
+      }
+      if (hit_i) {
+        if (FILL) {
+          const double tt = r * ap;
+          acc = hit ? acc + tt : tt;
+        }
+        hit = true;
+      }
+    }
+  }
+  const unsigned long long ball = __ballot(hit);
+  const uint32_t g0 = ((threadIdx.x & 63u) / SLOTS) * SLOTS;
+  const unsigned long long mine = (ball >> g0) & ((1ull << SLOTS) - 1ull);
+  if (!FILL) {
+    if (s == 0 && live) cnt[row] = (int32_t)__popcll(mine);
+  } else if (hit && live) {
+    const int32_t at = orp[row] + (int32_t)__popcll(mine & ((1ull << s) - 1ull));
+    ocol[at] = (int32_t)(((uint32_t)Jc[2] * g.my + (uint32_t)Jc[1]) * g.mx + (uint32_t)Jc[0]);
+    oval[at] = acc;
+  }
+}
+hipError_t launch_axis_galerkin(bool fill, int dim, const int64_t dims[3], int axis, const int32_t* arp,
+                                const int32_t* acol, const double* aval, const double* W, int32_t* cnt,
+                                const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow, hipStream_t st) {
+  TensorGrid g;
+  AxisSetupGrid ag;
+  uint32_t n_even = 0;
+  if (!axis_setup_grid(dim, dims, axis, &ag, &n_even) || !tensor_grid(dim, dims, 1u << axis, 0u, 0u, &g))
+    return hipErrorInvalidValue;
+  const uint32_t nH = g.mx * g.my * g.mz;
+#define AG_LAUNCH(SLOTS, FILL)                                                                                    \
+  hipLaunchKernelGGL((axis_galerkin_kernel<SLOTS, FILL>), dim3((nH + 256u / SLOTS - 1u) / (256u / SLOTS)), dim3(256), \
+                     0, st, g, (uint32_t)axis, ag.mE, ag.inv_nx, ag.inv_ny, arp, acol, aval, W, cnt, orp, ocol, oval, \
+                     overflow)
+  if (dim == 3) {
+    if (fill) AG_LAUNCH(32, true);
+    else AG_LAUNCH(32, false);
+  } else {
+    if (fill) AG_LAUNCH(16, true);
+    else AG_LAUNCH(16, false);
+  }
+#undef AG_LAUNCH
+  return hipGetLastError();
+}
+
 // --------------------------------------------------------------- K-Setup ------
 // Setup on the device end to end: the Grid generators
 // (grid.hpp:88-98 and the 7-point analogue) as kernels, and the dictionary encoder of the

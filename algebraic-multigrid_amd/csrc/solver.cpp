@@ -217,10 +217,12 @@ hipError_t device_galerkin(const DevCsr& A, int64_t n_H, DevCsr* AH, Sparse* hos
 // from CSR(A) on the device.  *ok = false: a coarse row reaches more columns than the
 // kernel's lane group holds; hipErrorInvalidValue: the product is beyond int32 indexing.  Either
 // way the caller takes the host path.
+// axis >= 0 (mask = 1 << axis): the one-axis pair with the weights W on the device (K-AxisGalerkin)
+// instead of the tensor-product pair.
 hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides,
                                   uint32_t periodic, int64_t n_H,
                                   DevCsr* AH,
-                                  bool* ok) {
+                                  bool* ok, int axis = -1, const double* W = nullptr) {
   *ok = false;
   hipError_t e;
   DevMem cnt, bsum, total, ovf;
@@ -229,9 +231,11 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if ((e = total.alloc(sizeof(int64_t))) != hipSuccess) return e;
   if ((e = ovf.alloc(sizeof(int32_t))) != hipSuccess) return e;
   if ((e = hipMemset(ovf.p, 0, sizeof(int32_t))) != hipSuccess) return e;
-  if ((e = launch_tensor_galerkin(false, dim, dims, mask, sides, periodic, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
-                                  nullptr, nullptr, ovf.as<int32_t>(), nullptr)) != hipSuccess)
-    return e;
+  e = axis >= 0 ? launch_axis_galerkin(false, dim, dims, axis, A.rowptr(), A.col(), A.v(), W, cnt.as<int32_t>(), nullptr,
+                                       nullptr, nullptr, ovf.as<int32_t>(), nullptr)
+                : launch_tensor_galerkin(false, dim, dims, mask, sides, periodic, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
+                                         nullptr, nullptr, ovf.as<int32_t>(), nullptr);
+  if (e != hipSuccess) return e;
   int32_t over = 0;
   if ((e = hipMemcpy(&over, ovf.p, sizeof(int32_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
   if (over) return hipSuccess;
@@ -244,9 +248,11 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if (nnz >= ((int64_t)1 << 31) - 1) return hipErrorInvalidValue;
   if ((e = AH->idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
   if ((e = AH->val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
-  if ((e = launch_tensor_galerkin(true, dim, dims, mask, sides, periodic, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
-                                  AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr)) != hipSuccess)
-    return e;
+  e = axis >= 0 ? launch_axis_galerkin(true, dim, dims, axis, A.rowptr(), A.col(), A.v(), W, nullptr, AH->ptr.as<int32_t>(),
+                                       AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr)
+                : launch_tensor_galerkin(true, dim, dims, mask, sides, periodic, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
+                                         AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr);
+  if (e != hipSuccess) return e;
   AH->n_rows = AH->n_cols = n_H;
   AH->nnz = nnz;
   *ok = true;
@@ -1448,10 +1454,12 @@ struct Level {
   const Sparse& P() const {
     if (lazy_linear && P_csc.ptr.empty()) P_csc = linear_P(n, n_coarse);  // interpolator.hpp:106-129
     if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims, tmask, tsides, tper);
+    if (axis >= 0 && P_csc.ptr.empty() && ensure_axis_weights() == hipSuccess)
+      P_csc = axis_P_from_weights(tdim, dims, axis, axis_W.data());
     return P_csc;
   }
   const Sparse& R() const {
-    if ((lazy_linear || tensor_stencil) && R_csc.ptr.empty()) R_csc = transpose(P());  // :132-134
+    if ((lazy_linear || tensor_stencil || axis >= 0) && R_csc.ptr.empty()) R_csc = transpose(P());  // :132-134
     return R_csc;
   }
   bool linear = false;
@@ -1472,10 +1480,20 @@ struct Level {
   // compact weights of its P (host_setup.hpp: axis_opdep_P) on the host and, where the transfers run
   // matrix-free (axis_stencil: K-AxisRestrict / K-AxisProlong, transfer kind 3), on the device.
   // P_csc / R_csc stay on the host; CSR(P), CSR(R) reach the device when a float or block cycle asks.
+  // A level built on the device (amg_hip_create_tensor_opdep_dev: K-AxisWeights) has its weights in
+  // axis_W_dev alone: ensure_axis_weights() downloads them on first use, P() / R() build the host
+  // operators from them (axis_P_from_weights) when a getter or a CSR cycle asks.
   int axis = -1;
   bool axis_stencil = false;
-  std::vector<double> axis_W;
+  mutable std::vector<double> axis_W;
   DevMem axis_W_dev;
+  hipError_t ensure_axis_weights() const {
+    if (!axis_W.empty() || !axis_W_dev.p) return hipSuccess;
+    std::vector<double> w((size_t)(2 * (n - n_coarse)));
+    const hipError_t e = hipMemcpy(w.data(), axis_W_dev.p, sizeof(double) * w.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) axis_W = std::move(w);
+    return e;
+  }
   // exact lexicographic schedules
   std::unique_ptr<LexOnDev> lex_fwd, lex_bwd;
   int scan_C = 0, scan_ring = 0;  // > 0: the lexicographic sweeps run as K-GS-scan
@@ -3017,6 +3035,7 @@ struct SemiRule {
   // amg_hip_create_tensor_opdep: one axis per level (the automatic rule is tensor_opdep_auto_mask,
   // theta is not used) and the weights of axis_opdep_P instead of tensor_P's
   bool opdep = false;
+  const char* opdep_who = "amg_hip_create_tensor_opdep: ";  // the entry point a refused row is reported under
 };
 // a one-level solver's coarsest right-hand side is the caller's b, which the pinned solve must not alter
 const char* const SINGULAR_ONE_LEVEL =
@@ -3545,7 +3564,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
         L.tensor_stencil = false;
         for (L.axis = 0; !((L.tmask >> L.axis) & 1u); ++L.axis) {}
         const std::string we = axis_opdep_P(A_r, h.dim, L.dims, L.axis, &L.P_csc, &L.axis_W);
-        if (!we.empty()) return fail(AMG_HIP_EINVAL, "amg_hip_create_tensor_opdep: level " + std::to_string(l) + ": " + we);
+        if (!we.empty()) return fail(AMG_HIP_EINVAL, std::string(h.semi->opdep_who) + "level " + std::to_string(l) + ": " + we);
         L.R_csc = transpose(L.P_csc);
         if (dev && L.axis_stencil) HIP_TRY(upload(L.axis_W_dev, L.axis_W.data(), L.axis_W.size()));
       } else if (!L.tensor_stencil) {
@@ -4088,8 +4107,47 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, const Hierarchy
       L.tensor = true;
       L.tensor_stencil = true;  // o.stencil_transfers is set and N < 2^28
       L.n_coarse = tdims[0] * tdims[1] * tdims[2];
+      const bool opdep = semi && semi->opdep;
+      std::chrono::steady_clock::time_point tk[3];
+      if (opdep) {  // one axis, K-AxisWeights from this level's rows into the transfers' own array; kind 3
+        L.tensor_stencil = false;
+        L.axis_stencil = true;
+        for (L.axis = 0; !((L.tmask >> L.axis) & 1u); ++L.axis) {}
+        HIP_TRY(L.axis_W_dev.alloc(sizeof(double) * 2 * (L.n - L.n_coarse)));
+        const int32_t none = INT32_MAX;
+        int32_t first_bad = none;
+        HIP_TRY(hipMemcpy(stats.p, &none, sizeof(int32_t), hipMemcpyHostToDevice));
+        if (timing) tk[0] = std::chrono::steady_clock::now();  // the copy above has synchronised
+        HIP_TRY(launch_axis_weights(dim, L.dims, L.axis, cur.rowptr(), cur.col(), cur.v(), L.axis_W_dev.as<double>(),
+                                    stats.as<int32_t>(), nullptr));
+        HIP_TRY(hipMemcpy(&first_bad, stats.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (timing) tk[1] = std::chrono::steady_clock::now();
+        if (first_bad != none) {  // that one row to the host, worded by the host constructor's code
+          int32_t rp[2];
+          HIP_TRY(hipMemcpy(rp, cur.rowptr() + first_bad, sizeof(rp), hipMemcpyDeviceToHost));
+          std::vector<int32_t> ci((size_t)std::max(rp[1] - rp[0], 1));
+          std::vector<double> cv(ci.size());
+          if (rp[1] > rp[0]) {
+            HIP_TRY(hipMemcpy(ci.data(), cur.col() + rp[0], sizeof(int32_t) * (rp[1] - rp[0]), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(cv.data(), cur.v() + rp[0], sizeof(double) * (rp[1] - rp[0]), hipMemcpyDeviceToHost));
+          }
+          const int64_t stride = L.axis == 0 ? 1 : (L.axis == 1 ? L.dims[0] : L.dims[0] * L.dims[1]);
+          double w2[2];
+          std::string we = axis_opdep_row(first_bad, ci.data(), cv.data(), rp[1] - rp[0], stride, L.dims[L.axis], L.axis, w2);
+          if (we.empty()) we = "row " + std::to_string(first_bad) + ": refused by K-AxisWeights";
+          return fail(AMG_HIP_EINVAL, std::string(semi->opdep_who) + "level " + std::to_string(l) + ": " + we);
+        }
+      }
       bool ok_g = false;
-      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.tmask, L.tsides, L.tper, L.n_coarse, &next, &ok_g);
+      const hipError_t ge = device_tensor_galerkin(cur, dim, L.dims, L.tmask, L.tsides, L.tper, L.n_coarse, &next, &ok_g,
+                                                   opdep ? L.axis : -1, L.axis_W_dev.as<double>());
+      if (opdep && timing && ge == hipSuccess && ok_g) {
+        (void)hipDeviceSynchronize();
+        tk[2] = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "amg_hip device setup: level %d (%lld rows, axis %c) K-AxisWeights %.3f ms, K-AxisGalerkin %.3f ms\n",
+                     l, (long long)L.n, "xyz"[L.axis], 1e3 * std::chrono::duration<double>(tk[1] - tk[0]).count(),
+                     1e3 * std::chrono::duration<double>(tk[2] - tk[1]).count());
+      }
       if (ge == hipErrorInvalidValue || (ge == hipSuccess && !ok_g)) {
         if (timing) std::fprintf(stderr, "amg_hip device setup: Galerkin product of level %d exceeds %s -> host path\n", l,
                                  ge == hipSuccess ? "the kernel's columns per coarse row" : "int32 indexing");
@@ -4279,8 +4337,9 @@ double csr_bytes(const DevCsr& M) { return 12.0 * (double)M.nnz + 4.0 * (double)
 // block cycles take their CSR kernels on such a level
 amg_hip_status ensure_axis_rows(Level& L) {
   if (!L.axis_stencil || L.P_rows.n_rows != 0) return AMG_HIP_OK;
-  HIP_TRY(upload_csr(transpose(L.P_csc), &L.P_rows));
-  HIP_TRY(upload_csr(transpose(L.R_csc), &L.R_rows));
+  HIP_TRY(L.ensure_axis_weights());  // a level built on the device: its host operators are made here
+  HIP_TRY(upload_csr(transpose(L.P()), &L.P_rows));
+  HIP_TRY(upload_csr(transpose(L.R()), &L.R_rows));
   return AMG_HIP_OK;
 }
 
@@ -5125,6 +5184,8 @@ amg_hip_status amg_hip_get_axis_weights(const amg_hip_solver* s, int32_t level, 
   const Level& L = s->lv[level];
   if (L.axis < 0)
     return fail(AMG_HIP_EINVAL, "amg_hip_get_axis_weights: the solver was not made by amg_hip_create_tensor_opdep");
+  if (L.axis_W.empty() && !s->opt.host_only) HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(L.ensure_axis_weights());
   std::memcpy(W, L.axis_W.data(), sizeof(double) * L.axis_W.size());
   return AMG_HIP_OK;
 }
@@ -5341,7 +5402,7 @@ static amg_hip_status create_tensor_dev(const std::string& who, int64_t n, const
   if (h.periodic_ctor) {  // grid, masks, levels and sides: the host constructor's one check
     AMG_TRY(periodic_args(who, n, h.dim, h.dims, (int32_t)h.periodic, n_levels, rule ? rule->masks : nullptr, o));
   } else {
-    AMG_TRY(tensor_grid_args(who, n, h.dim, h.dims, o.window, rule ? "semi" : "full"));
+    AMG_TRY(tensor_grid_args(who, n, h.dim, h.dims, o.window, rule ? (rule->opdep ? "single-axis" : "semi") : "full"));
     if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
     if (rule) {
       AMG_TRY(semi_args(who, h.dim, h.dims, n_levels, *rule));
@@ -5354,6 +5415,7 @@ static amg_hip_status create_tensor_dev(const std::string& who, int64_t n, const
   bool unsupported = true;
   amg_hip_options od = o;
   if (h.periodic_ctor && !g_periodic_device_setup) od.host_galerkin = 1;  // copy + check only
+  if (rule && rule->opdep && !g_axis_stencil) od.host_galerkin = 1;       // transfer kind 0 needs CSR(P), CSR(R): host
   amg_hip_status r = build_tensor_user_device(who, n, rowptr_dev, col_dev, val_dev, b_dev, n_levels, h, od, out,
                                               &unsupported);
   if (r != AMG_HIP_OK || !unsupported) return r;
@@ -5395,6 +5457,17 @@ amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_d
   const SemiRule rule{axis_masks, theta, min_coarse};
   return create_tensor_dev("amg_hip_create_tensor_semi_dev: ", n, rowptr_dev, col_dev, val_dev, b_dev, n_levels,
                            tensor_spec(dim, dims), &rule, opts, out);
+}
+
+amg_hip_status amg_hip_create_tensor_opdep_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                               const double* val_dev, const double* b_dev, int32_t dim,
+                                               const int64_t* dims, int32_t n_levels, const int32_t* axis_masks,
+                                               int64_t min_coarse, const amg_hip_options* opts, amg_hip_solver** out) {
+  SemiRule rule{axis_masks, 1.0, min_coarse};  // as amg_hip_create_tensor_opdep
+  rule.opdep = true;
+  rule.opdep_who = "amg_hip_create_tensor_opdep_dev: ";
+  return create_tensor_dev(rule.opdep_who, n, rowptr_dev, col_dev, val_dev, b_dev, n_levels, tensor_spec(dim, dims), &rule,
+                           opts, out);
 }
 
 amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
@@ -6221,6 +6294,7 @@ amg_hip_status amg_hip_get_transfer(const amg_hip_solver* s, int32_t level, int3
                                     int32_t* colptr, int32_t* rowind, double* val) {
   if (!s || level < 0 || level + 1 >= (int32_t)s->lv.size())
     return fail(AMG_HIP_EINVAL, "level out of range");
+  HIP_TRY(s->lv[level].ensure_axis_weights());
   const Sparse& M = which ? s->lv[level].R() : s->lv[level].P();
   if (colptr) std::memcpy(colptr, M.ptr.data(), sizeof(int32_t) * M.ptr.size());
   if (rowind) std::memcpy(rowind, M.idx.data(), sizeof(int32_t) * M.idx.size());

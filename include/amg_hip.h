@@ -522,7 +522,8 @@ amg_hip_status amg_hip_create_tensor_opdep(int64_t n, const int32_t* colptr, con
  * opts->stencil_transfers.  Process-wide, default 1, read when a solver is created.  Same bits
  * either way: an A/B switch for tests and measurements.                                          */
 void amg_hip_set_axis_stencil(int32_t on);
-/* The compact weights of `level` of a solver made by amg_hip_create_tensor_opdep, 2 (n_l - n_{l+1})
+/* The compact weights of `level` of a solver made by amg_hip_create_tensor_opdep (or _opdep_dev,
+ * which downloads them from the device at the first call), 2 (n_l - n_{l+1})
  * doubles; also on host_only solvers.  The fine points whose coordinate on the level's axis is even,
  * c = 2 q, form a grid like the level's with that axis shortened to m - floor(m / 2); the point with
  * flat index e on it (x fastest) has W[2 e] = w_lo (its coarse neighbour q - 1) and W[2 e + 1] =
@@ -724,6 +725,35 @@ amg_hip_status amg_hip_create_tensor_semi_dev(int64_t n, const int32_t* rowptr_d
                                               const int32_t* axis_masks /* n_levels - 1, host, or NULL */,
                                               double theta, int64_t min_coarse,
                                               const amg_hip_options* opts, amg_hip_solver** out);
+/* amg_hip_create_tensor_opdep for a caller's matrix in DEVICE memory (CSR, as for
+ * amg_hip_create_tensor_dev), on top of that constructor's level loop.  On every level that is not
+ * the last, K-AxisWeights makes the compact weights of amg_hip_get_axis_weights from the rows of the
+ * level's CSR arrays, straight into the array K-AxisRestrict / K-AxisProlong read (no upload), and
+ * K-AxisGalerkin forms A_{l+1} = R (A P) from CSR(A_l) and those weights with neither P, R nor A P in
+ * memory, in the summation order of the host product and with its structure (an entry for every
+ * neighbour that exists, zero weights included).  The automatic rule takes its w from
+ * K-AxisStrength.  Transfer kind 3 on every level.  The host copies of the weights and of P / R are
+ * made when amg_hip_get_axis_weights, amg_hip_get_transfer, a float or a block cycle ask for them.
+ * natural_sides and singular are honoured as on the host constructor (they do not enter the
+ * weights); amg_hip_set_mean_projection works.  The solver equals amg_hip_create_tensor_opdep's on the
+ * CSC arrays of the same A with the same options bit for bit: axes, dims, weights (-0.0 included),
+ * level matrices, and every cycle, apply, PCG, mixed and block call.
+ * Device path: true Jacobi, Chebyshev, the line smoothers, every layout, n_levels >= 2, n < 2^28.
+ * Everything else silently downloads the arrays, transposes them on the host and calls
+ * amg_hip_create_tensor_opdep: the fallbacks of amg_hip_create_tensor_dev (host_only, host_galerkin,
+ * stencil_transfers = 0, fuse_prolong, multicolour GS, the lexicographic smoothers, one level),
+ * amg_hip_set_axis_stencil(0) (kind 0 needs CSR P / R), a coarse row that reaches more coarse
+ * columns than K-AxisGalerkin's lane group holds (16 in 2-D, 32 in 3-D: 9- / 27-point levels fit),
+ * a product beyond int32 indexing.  amg_hip_setup_on_device tells the two paths apart.
+ * The argument checks are amg_hip_create_tensor_opdep's in the same words under this entry point's
+ * name, plus null arrays, all before the device is touched; then K-CsrCheck as for
+ * amg_hip_create_tensor_dev.  A row whose s_0 is zero or not finite, or whose weight is not finite,
+ * is AMG_HIP_EINVAL with the host constructor's text (level and the smallest such row).           */
+amg_hip_status amg_hip_create_tensor_opdep_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                               const double* val_dev, const double* b_dev, int32_t dim,
+                                               const int64_t* dims /* 3, host */, int32_t n_levels,
+                                               const int32_t* axis_masks /* n_levels - 1 single-axis masks, host, or NULL */,
+                                               int64_t min_coarse, const amg_hip_options* opts, amg_hip_solver** out);
 /* amg_hip_create_tensor_periodic for a caller's matrix in DEVICE memory (CSR, as for
  * amg_hip_create_tensor_dev).  The arguments are checked as by the host constructor, the arrays by
  * K-CsrCheck, first and whatever the switch says.
@@ -746,7 +776,7 @@ amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowp
                                                   const amg_hip_options* opts, amg_hip_solver** out);
 /* *on = 1: the hierarchy was built by a device-only path (amg_hip_create_poisson,
  * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor, amg_hip_create_tensor_dev,
- * amg_hip_create_tensor_semi_dev, and amg_hip_create_tensor_periodic_dev under
+ * amg_hip_create_tensor_semi_dev, amg_hip_create_tensor_opdep_dev, and amg_hip_create_tensor_periodic_dev under
  * amg_hip_set_periodic_device_setup(1), when they did not fall back),
  * 0: by the host constructor -- every other entry point and the silent fallbacks.  Also on
  * host_only solvers (0).                                                                        */

@@ -15,6 +15,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py semi [<nx> <ny> <nz> <eps_x> <eps_y> <eps_z>] PCG to 1e-8 on an axis-scaled diffusion operator: full coarsening + Jacobi, semi-coarsening + Jacobi, full coarsening + alternating lines, semi-coarsening + amg_hip_pcg_mixed (legs alternate)
        config_bench.py opdep [<nx> <ny> <nz>]                      operator-dependent interpolation (tensor_opdep) on a diffusion operator whose conductivity jumps by 10^0..10^4 between blocks of 8 nodes: ms per V-cycle with the matrix-free transfers (kind 3) against CSR transfers (kind 0), PCG to 1e-8 against full coarsening (tensor), host set-up seconds and device matrix bytes (legs alternate)
        config_bench.py opdep10 <nx> <ny> <nz> [csr]                ten cycles of one tensor_opdep hierarchy on that operator (kernel traces)
+       config_bench.py opdep-setup [<nx> <ny> <nz>]                set-up seconds of tensor_opdep on that operator assembled on the GPU, explicit masks x, y, (z,) x, ...: the host constructor and amg_hip_create_tensor_opdep_dev alternating, best of three
        config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
        config_bench.py singular [<nx> <ny> <nz>]                   PCG to 1e-8 on that operator without a Dirichlet side, one solver: mean projection (amg_hip_set_mean_projection) off and on with the consistent b and on with b + 1e-6, legs alternate; the time added per iteration next to an estimate from the tree reduction's rate in the same run
        config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
@@ -672,6 +673,81 @@ def run_opdep(dims, reps=3, rtol=1e-8, max_iters=400, cycles=10):
           "; best PCG ms: " + ", ".join(f"{k} {v * 1e3:.2f} ({iters[k]} it)" for k, v in best_p.items()), flush=True)
     for mg in legs.values():
         mg.close()
+
+
+def torch_jump(dims, block=8, contrast=4, seed=7):
+    """numpy_jump's operator assembled on the GPU: (crow, col, val, b) as torch_diffusion.  Only the table of
+    the blocks' conductivities (a few thousand numbers, numpy_jump's generator and seed) comes from the host."""
+    import numpy as np
+    import torch
+    dev = torch.device("cuda")
+    dim = len(dims)
+    n = int(np.prod(dims))
+    nb = [(m + block - 1) // block for m in dims]
+    kb = 10.0 ** np.random.default_rng(seed).integers(0, contrast + 1, size=nb[::-1]).astype(np.float64)
+    kb = torch.from_numpy(kb.ravel()).to(dev)
+    i = torch.arange(n, device=dev)
+    stride = [1, dims[0], dims[0] * dims[1]][:dim]
+    coord = [(i // stride[a]) % dims[a] for a in range(dim)]
+    blk = torch.zeros(n, dtype=torch.int64, device=dev)
+    for a in reversed(range(dim)):
+        blk = blk * nb[a] + coord[a] // block
+    knode = kb[blk]
+    w = 2 * dim + 1
+    cols = torch.zeros((n, w), dtype=torch.int64, device=dev)
+    vals = torch.zeros((n, w), dtype=torch.float64, device=dev)
+    mask = torch.zeros((n, w), dtype=torch.bool, device=dev)
+    diag = torch.zeros(n, dtype=torch.float64, device=dev)
+    for a in range(dim):
+        lo_ok, hi_ok = coord[a] > 0, coord[a] < dims[a] - 1
+        k_lo = torch.where(lo_ok, torch.roll(knode, stride[a]), knode)  # the edge takes the k of its lower endpoint;
+        k_hi = knode                                                     # a Dirichlet side the boundary node's own
+        diag = diag + k_lo + k_hi
+        s_lo, s_hi = dim - 1 - a, dim + 1 + a
+        cols[:, s_lo], vals[:, s_lo], mask[:, s_lo] = i - stride[a], -k_lo, lo_ok
+        cols[:, s_hi], vals[:, s_hi], mask[:, s_hi] = i + stride[a], -k_hi, hi_ok
+    cols[:, dim], vals[:, dim], mask[:, dim] = i, diag, True
+    crow = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    crow[1:] = torch.cumsum(mask.sum(1), 0).to(torch.int32)
+    g = torch.Generator(device=dev)
+    g.manual_seed(99)
+    b = torch.randn(n, generator=g, device=dev, dtype=torch.float64)
+    return crow, col_of(cols, mask), vals[mask].contiguous(), b
+
+
+def run_opdep_setup(dims, reps=3):
+    """Set-up seconds of the hierarchy with operator-dependent interpolation on the jump operator
+    (torch_jump, contrast 1e4, assembled on the GPU), explicit masks x, y, (z,) x, ... (cyclic_masks), true
+    Jacobi 2+2: the host constructor (Multigrid.tensor_opdep on host copies of the arrays -- the operator is
+    symmetric, its CSR arrays are its CSC arrays; the copy itself is not timed) and the device set-up
+    (Multigrid.tensor_opdep_dev on the device arrays), alternating in one process, `reps` repeats, best of
+    them; wall time around the constructor, closed by a device synchronise.  With AMG_HIP_TIMING set the
+    library writes its laps to stderr, K-AxisWeights and K-AxisGalerkin per level among them."""
+    import torch
+    crow, col, val, b = torch_jump(dims)
+    torch.cuda.synchronize()
+    h = [a.cpu().numpy() for a in (crow, col, val, b)]
+    masks = cyclic_masks(dims)
+    L = len(masks) + 1
+    tag = " x ".join(str(d) for d in dims) + " jump 1e4"
+    best = {}
+    for rep_ in range(reps):
+        for name in ("host", "device"):
+            t0 = time.perf_counter()
+            if name == "host":
+                mg = amg.Multigrid.tensor_opdep(h[0], h[1], h[2], h[3], dims, L, axis_masks=masks, **TENSOR_KW["jacobi"])
+            else:
+                mg = amg.Multigrid.tensor_opdep_dev(crow, col, val, b, dims, L, axis_masks=masks, **TENSOR_KW["jacobi"])
+            mg.sync()
+            dt = time.perf_counter() - t0
+            assert mg.setup_on_device == int(name == "device")
+            best[name] = min(best.get(name, dt), dt)
+            kinds = sorted(set(mg.level_transfer_kind(l) for l in range(L - 1)))
+            print(f"opdep-setup {tag} {L} levels, {name} rep {rep_}: {dt:.3f} s (setup_on_device {mg.setup_on_device}, "
+                  f"transfer kinds {kinds}, coarsest {mg.get_n_dofs(L - 1)} dofs)", flush=True)
+            mg.close()
+    print(f"opdep-setup {tag} {L} levels: best host {best['host']:.3f} s, best device {best['device']:.3f} s, "
+          f"ratio {best['host'] / best['device']:.1f}", flush=True)
 
 
 def run_natural(dims, reps=3, rtol=1e-8, max_iters=300):
@@ -1573,6 +1649,16 @@ elif len(sys.argv) > 1 and sys.argv[1] == "opdep":
     else:
         run_opdep((2048, 2048))
         run_opdep((128, 128, 128))
+elif len(sys.argv) > 1 and sys.argv[1] == "opdep-setup":
+    # profiles/opdep_setup.txt
+    os.environ.setdefault("AMG_HIP_TIMING", "1")
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    if len(sys.argv) > 4:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_opdep_setup(d if d[2] > 1 else d[:2])
+    else:
+        run_opdep_setup((2048, 2048))
+        run_opdep_setup((128, 128, 128))
 elif len(sys.argv) > 4 and sys.argv[1] == "opdep10":    # ten cycles of one hierarchy (kernel traces)
     d = tuple(int(x) for x in sys.argv[2:5])
     d = d if d[2] > 1 else d[:2]
