@@ -6,6 +6,7 @@ HIP kernels.  If the shared library is missing the import fails loudly; if no
 HIP device is present every compute call raises AmgHipError (status EHIP) --
 there is no CPU fallback.
 """
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -19,6 +20,10 @@ OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED, ECOMM = 0, 1, 2, 3, 4, 5
 SM_SPGS, SM_REF_JACOBI, SM_SOR, SM_JACOBI, SM_MULTICOLOR_GS, SM_CHEBYSHEV, SM_LINE_JACOBI = 0, 1, 2, 3, 4, 5, 6
 SM_LINE_ALT = 7
 LAYOUT_AUTO, LAYOUT_CSR, LAYOUT_SELL, LAYOUT_DICT = 0, 1, 2, 3
+# AMG_HIP_LEG_*: the launch forms of the cycle plan, by value (Multigrid.leg_form returns these names)
+LEG_FORMS = ("none", "plain", "pair", "duo_fine", "duo_coarse", "patch", "mc_patch", "mc_strip", "tail_head",
+             "in_tail")
+StripGeometry = collections.namedtuple("StripGeometry", "T tiles stages halo_down halo_up")
 
 _i32p = C.POINTER(C.c_int32)
 _f64p = C.POINTER(C.c_double)
@@ -210,6 +215,8 @@ _SIGS = {
     "amg_hip_patch_tile_classes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i64p]),
     "amg_hip_set_patch_seam": (None, [C.c_int32]),
     "amg_hip_patch_leg_lines": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "amg_hip_level_leg_form": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i32p]),
+    "amg_hip_strip_geometry": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "amg_hip_create_rs": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, C.c_double, C.c_int64,
                                     C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "amg_hip_slab_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SlabInfo)]),
@@ -1256,6 +1263,26 @@ class Multigrid:
         """lines of the K-Patch tiles of `level`'s down-leg (leg 0) / up-leg (leg 1); 0 = no K-Patch level.
         leg 2: of the seam launch that vcycle(n >= 2) runs on level 0; 0 = this solver runs none"""
         return int(lib().amg_hip_patch_leg_lines(self._h, int(level), int(leg)))
+
+    def leg_form(self, level):
+        """(down, up): the launch forms the cycle plan gives `level`, as names of LEG_FORMS
+        (amg_hip_level_leg_form); ValueError for a level the solver does not have"""
+        d, u = C.c_int32(0), C.c_int32(0)
+        st = lib().amg_hip_level_leg_form(self._h, int(level), C.byref(d), C.byref(u))
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return LEG_FORMS[d.value], LEG_FORMS[u.value]
+
+    def strip_geometry(self, level):
+        """StripGeometry(T, tiles, stages, halo_down, halo_up) of a K-Strip level
+        (amg_hip_strip_geometry); ValueError where the level runs in another form"""
+        v = [C.c_int32(0) for _ in range(5)]
+        st = lib().amg_hip_strip_geometry(self._h, int(level), *[C.byref(x) for x in v])
+        if st == EINVAL:
+            raise ValueError(lib().amg_hip_last_error().decode())
+        _chk(st)
+        return StripGeometry(*[int(x.value) for x in v])
 
     def patch_tile_classes(self, level, rings):
         """(one-type, column-typed, general) tile counts of `level` for the launches with `rings` halo rings

@@ -3906,6 +3906,12 @@ hipError_t launch_mc_strip(bool prolong, bool tail, StripRef A, const DictRef& D
 #undef AMG_STRIP
   });
 }
+void mc_strip_kernel_name(const DictRef& D, bool prolong, bool tail, char* buf, size_t cap) {
+  dict_dispatch_class<0>(dict_wu_class(D.words, D.wmax), [&](auto W, auto U) {
+    std::snprintf(buf, cap, "mc_strip_kernel<%d, %d, %s, %s>", (int)decltype(W)::value, (int)decltype(U)::value,
+                  (prolong && !tail) ? "true" : "false", tail ? "true" : "false");
+  });
+}
 
 void set_xcd_mapping(int on) {
   g_xcd_map = on ? 1 : 0;

@@ -390,6 +390,8 @@ struct StripRef {
 };
 int strip_window_max();
 hipError_t launch_mc_strip(bool prolong, bool tail, StripRef A, const DictRef& D, hipStream_t st);
+// the instantiation that launch runs, as a profiler prints it
+void mc_strip_kernel_name(const DictRef& D, bool prolong, bool tail, char* buf, size_t cap);
 // uh_out = uh_in + P uH for the linear interpolation pair (16-byte aligned vectors)
 hipError_t launch_linear_prolong_to(int64_t n_h, int64_t n_H, const double* uH,
                                     const double* uh_in, double* uh_out, hipStream_t st);

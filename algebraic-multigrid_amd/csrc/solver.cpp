@@ -6443,8 +6443,9 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
   const LegForm form = P.lv[0].down;  // the launch level 0 runs
   const bool mc = s->opt.smoother == AMG_HIP_SM_MULTICOLOR_GS;
   const bool mc_patch = form == LEG_MC_PATCH;
+  const bool mc_strip = form == LEG_MC_STRIP;
   // multicolour, colour kernels: the launch updates u in place; keep a copy in r
-  if (mc && !mc_patch)
+  if (mc && !mc_patch && !mc_strip)
     HIP_TRY(hipMemcpyAsync(L.r.p, L.u.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream));
   // keep u: sweep u -> tmp only (u itself is never written).  With K-Patch the launch is the
   // level's whole down-leg (2 sweeps + residual + restriction + first coarse sweep); it also
@@ -6457,7 +6458,7 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
   const bool slab = patch && s->slab.levels > 0 && s->slab.world > 1;
   // (after the launches the multicolour colour kernels' u goes back)
   auto restore = [&]() -> amg_hip_status {
-    if (mc && !mc_patch)
+    if (mc && !mc_patch && !mc_strip)
       HIP_TRY(hipMemcpyAsync(L.u.p, L.r.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream));
     return AMG_HIP_OK;
   };
@@ -6468,6 +6469,16 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
       HIP_TRY(launch_patch_rb(false, false, L.n, L.A_rows.patch_m, L.A_rows.patch_ref(), L.u.as<double>(),
                               L.f.as<double>(), nullptr, s->lv[1].n, L.tmp.as<double>(), nullptr, nullptr,
                               nullptr, plan[0].stages, (uint32_t)L.mc_ctab, s->stream));
+    } else if (mc_strip) {
+      // the level's whole down-leg, u -> tmp (down_mc_strip without r); like the K-Patch launch it
+      // rewrites f and u of level 1, which every V-cycle recomputes before use
+      Level& C = s->lv[1];
+      StripRef R = mc_strip_ref(s, 0);
+      R.x = L.u.as<double>();
+      R.u_out = L.tmp.as<double>();
+      R.fH = C.f.as<double>();
+      R.uH_zero = C.u.as<double>();
+      HIP_TRY(launch_mc_strip(false, true, R, L.A_rows.dict_ref(), s->stream));
     } else if (mc) {  // colour 0 of the forward half
       if (L.mc_dict)
         HIP_TRY(launch_dict_gs_color(L.mc_start[0], L.mc_start[1] - L.mc_start[0], L.mc_words, L.mc_wmax,
@@ -6542,6 +6553,49 @@ int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t 
   return patch_tile_lines(patch_rings(s, leg == 0 && level == 0));
 }
 
+namespace {
+int32_t leg_form_public(LegForm f) {
+  switch (f) {
+    case LEG_NONE: return AMG_HIP_LEG_NONE;
+    case LEG_PLAIN: return AMG_HIP_LEG_PLAIN;
+    case LEG_PAIR: return AMG_HIP_LEG_PAIR;
+    case LEG_DUO_FINE: return AMG_HIP_LEG_DUO_FINE;
+    case LEG_DUO_COARSE: return AMG_HIP_LEG_DUO_COARSE;
+    case LEG_PATCH: return AMG_HIP_LEG_PATCH;
+    case LEG_MC_PATCH: return AMG_HIP_LEG_MC_PATCH;
+    case LEG_MC_STRIP: return AMG_HIP_LEG_MC_STRIP;
+    case LEG_TAIL_HEAD: return AMG_HIP_LEG_TAIL_HEAD;
+    case LEG_IN_TAIL: return AMG_HIP_LEG_IN_TAIL;
+  }
+  return AMG_HIP_LEG_NONE;
+}
+}  // namespace
+
+amg_hip_status amg_hip_level_leg_form(const amg_hip_solver* s, int32_t level, int32_t* down, int32_t* up) {
+  if (!s || !down || !up || level < 0 || level >= (int32_t)s->lv.size())
+    return fail(AMG_HIP_EINVAL, "amg_hip_level_leg_form: bad argument");
+  const CyclePlan P = current_plan(s);  // host_only: every level none
+  *down = leg_form_public(P.lv[(size_t)level].down);
+  *up = leg_form_public(P.lv[(size_t)level].up);
+  return AMG_HIP_OK;
+}
+
+amg_hip_status amg_hip_strip_geometry(const amg_hip_solver* s, int32_t level, int32_t* T, int32_t* tiles,
+                                      int32_t* stages, int32_t* halo_down, int32_t* halo_up) {
+  if (!s || !T || !tiles || !stages || !halo_down || !halo_up || level < 0 || level >= (int32_t)s->lv.size())
+    return fail(AMG_HIP_EINVAL, "amg_hip_strip_geometry: bad argument");
+  // (a strip level is one on both legs)
+  if (s->opt.host_only || current_plan(s).lv[(size_t)level].up != LEG_MC_STRIP)
+    return fail(AMG_HIP_EINVAL, "amg_hip_strip_geometry: the level is no K-Strip level");
+  const StripRef R = mc_strip_ref(const_cast<amg_hip_solver*>(s), level);  // reads only
+  *T = R.T;
+  *tiles = (R.n + R.T - 1) / R.T;
+  *stages = R.nst;
+  *halo_down = (R.nst + 1) * R.hbw;  // launch_mc_strip: H = (nst + tail) hbw
+  *halo_up = R.nst * R.hbw;
+  return AMG_HIP_OK;
+}
+
 amg_hip_status amg_hip_patch_tile_classes(amg_hip_solver* s, int32_t level, int32_t rings, int64_t* out) {
   if (!s || !out || s->opt.host_only || level < 0 || level >= (int32_t)s->lv.size())
     return fail(AMG_HIP_EINVAL, "amg_hip_patch_tile_classes: bad argument");
@@ -6604,6 +6658,13 @@ amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int3
       std::snprintf(name, (size_t)name_cap, "patch_rb_kernel<%d, %d, %s, false, false>", patch_un(A.patch_un),
                     patch_kind_umask(A.patch_un, A.patch_umask), A.dict_nt ? "true" : "false");
       bytes = 25.0 * (double)L.n;
+    } else if (Q.down == LEG_MC_STRIP) {
+      // the level's whole down-leg (down_mc_strip): every colour stage of the symmetric passes, the
+      // residual and the restriction: row types + colours + x + f + out; f_H, zeroed u_H
+      const StripRef R = mc_strip_ref(const_cast<amg_hip_solver*>(s), 0);  // reads only
+      mc_strip_kernel_name(L.A_rows.dict_ref(), false, true, name, (size_t)name_cap);
+      sweeps = R.nst;
+      bytes = 26.0 * (double)L.n + 16.0 * (double)s->lv[1].n;
     } else {
       std::snprintf(name, (size_t)name_cap, "%s", L.mc_dict ? "dict_gs_color_kernel" : "sell_kernel<5>");
       const double rows = (double)(L.mc_start.size() > 1 ? L.mc_start[1] - L.mc_start[0] : L.n);

@@ -1201,7 +1201,8 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
  * written), or step 0 when the degree has no middle step (1 or 2);
  * AMG_HIP_SM_LINE_JACOBI, AMG_HIP_SM_LINE_ALT: refused (AMG_HIP_EUNSUPPORTED; a sweep is several launches);
  * AMG_HIP_SM_MULTICOLOR_GS: the first launch of the symmetric pass (K-Patch form: two colour
- * stages over the level; colour kernels: colour 0).  The level-0 solution is restored
+ * stages over the level; K-Strip form: the level's whole down-leg, which like the K-Patch launch
+ * also rewrites f and u of level 1; colour kernels: colour 0).  The level-0 solution is restored
  * afterwards.                                                                  */
 amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
                                           double* avg_ms, double* min_ms);
@@ -1209,6 +1210,28 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
  * up-leg (leg 1): 42 or 44 on a K-Patch level, 0 where the level is no K-Patch level.  leg 2: of the
  * seam launch amg_hip_vcycles(s, n >= 2) runs on level 0 (38), 0 where this solver runs none.   */
 int32_t amg_hip_patch_leg_lines(const amg_hip_solver* s, int32_t level, int32_t leg);
+/* The launch form the cycle plan gives `level` on its down-leg and its up-leg (DESIGN.md section 4,
+ * "The cycle plan"): of the cycle enqueued last, before the first one of the cycle that would run.  */
+enum {
+  AMG_HIP_LEG_NONE = 0,        /* no launch of its own (the coarsest level when r is not kept; host_only) */
+  AMG_HIP_LEG_PLAIN = 1,       /* the smoother's own launches, then the transfers                      */
+  AMG_HIP_LEG_PAIR = 2,        /* two sweeps of a small level in one launch                            */
+  AMG_HIP_LEG_DUO_FINE = 3,    /* K-Duo: the finer level of a duo                                      */
+  AMG_HIP_LEG_DUO_COARSE = 4,  /* K-Duo: the coarser level                                             */
+  AMG_HIP_LEG_PATCH = 5,       /* K-Patch: the whole leg in one launch                                 */
+  AMG_HIP_LEG_MC_PATCH = 6,    /* multicolour smoother: colour stages as patch launches                */
+  AMG_HIP_LEG_MC_STRIP = 7,    /* multicolour smoother: K-Strip, the whole leg as one strip launch     */
+  AMG_HIP_LEG_TAIL_HEAD = 8,   /* K-Tail: this level .. L-2, the solve and the way back in one launch  */
+  AMG_HIP_LEG_IN_TAIL = 9      /* a level inside that launch                                           */
+};
+/* AMG_HIP_EINVAL for a level the solver does not have; a host_only solver reports none on both legs. */
+amg_hip_status amg_hip_level_leg_form(const amg_hip_solver* s, int32_t level, int32_t* down, int32_t* up);
+/* The K-Strip launches of `level`: rows per strip T, strips (workgroups) per launch, colour stages of
+ * a leg, and the halo rows a strip loads on either side on the down-leg ((stages + 1) half-bandwidths:
+ * the residual needs one more) and on the up-leg (stages half-bandwidths).  The LDS window of a launch
+ * is T + 2 halo + 2 rows.  AMG_HIP_EINVAL where the plan runs `level` in another form.              */
+amg_hip_status amg_hip_strip_geometry(const amg_hip_solver* s, int32_t level, int32_t* T, int32_t* tiles,
+                                      int32_t* stages, int32_t* halo_down, int32_t* halo_up);
 /* Tiles of `level` by class, for the launches with `rings` halo rings (2: tiles of 44 lines, 3: 42, 5: the
  * seam launch's, 38): out[0] = tiles of one row type, out[1] = column-typed tiles, out[2] = general
  * tiles.  AMG_HIP_EINVAL where the level is no K-Patch level or has no tiles of that geometry.        */
@@ -1217,7 +1240,9 @@ amg_hip_status amg_hip_patch_tile_classes(amg_hip_solver* s, int32_t level, int3
  * namespace), the number of Jacobi sweeps over level 0 one launch of it performs, and the
  * bytes one launch has to move (what the kernel reads and writes once: SURVEY 8(d)'s CSR
  * formula for the CSR / SELL layouts; row types + f + x + out for the dictionary-coded one;
- * for the K-Patch down-leg additionally f_H, the first coarse sweep and the coarse diagonal). */
+ * for the K-Patch down-leg additionally f_H, the first coarse sweep and the coarse diagonal).
+ * On a K-Strip level 0 of the multicolour smoother the launch is mc_strip_kernel, the count is its
+ * colour stages and the bytes are row types + colours + x + f + out, f_H and the zeroed u_H.       */
 amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int32_t name_cap,
                                        int32_t* sweeps_per_launch, double* bytes_per_launch);
 

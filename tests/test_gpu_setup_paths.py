@@ -226,7 +226,9 @@ EXPECTED = {
         axes=[None, None, None, None, None],
         dirs=[None, None, None, None, None, None],
         cyclic=[None, None, None, None, None, None],
-        sweep='dict_gs_color_kernel',
+        # level 0 (2 colours, half-bandwidth 256) runs as a K-Strip level; until fine_sweep_info knew that
+        # form it named the colour kernel, which this solver never launches on level 0
+        sweep='mc_strip_kernel<1, 5, false, true>',
     ),
     'poisson-2d-256-spgs': dict(
         on_device=0,
