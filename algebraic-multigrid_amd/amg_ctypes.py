@@ -136,6 +136,17 @@ _SIGS = {
     "amg_hip_create_tensor_opdep_dev": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_int32, _i64p, C.c_int32, _i32p, C.c_int64,
                                                   C.POINTER(Options), C.POINTER(C.c_void_p)]),
+    "amg_hip_create_tensor_opdep_periodic": (C.c_int, [C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32, _i64p,
+                                                       C.c_int32, C.c_int32, _i32p, C.c_int64,
+                                                       C.POINTER(Options), C.POINTER(C.c_void_p)]),
+    "amg_hip_create_tensor_opdep_periodic_dev": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_int32, _i64p, C.c_int32, C.c_int32,
+                                                           _i32p, C.c_int64, C.POINTER(Options),
+                                                           C.POINTER(C.c_void_p)]),
+    "amg_hip_axis_restrict_per": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int32, _f64p, _f64p, _f64p,
+                                            C.c_int32]),
+    "amg_hip_axis_prolong_add_per": (C.c_int, [C.c_int32, _i64p, C.c_int32, C.c_int32, _f64p, _f64p, _f64p,
+                                               C.c_int32]),
     "amg_hip_set_axis_stencil": (None, [C.c_int32]),
     "amg_hip_get_axis_weights": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
     "amg_hip_axis_restrict": (C.c_int, [C.c_int32, _i64p, C.c_int32, _f64p, _f64p, _f64p]),
@@ -772,7 +783,7 @@ class Multigrid:
                no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
                window=False, natural_sides=0, singular=False, cyclic_lines=False, _semi=None, _periodic=None,
-               _opdep=None):
+               _opdep=None, _opdep_per=None):
         """AMG::Multigrid on a FULL-coarsening hierarchy of the grid `dims` = (nx, ny) or (nx, ny, nz),
         x fastest (amg_hip_create_tensor): every axis m -> m // 2, tensor-product linear interpolation,
         matrix-free transfer kernels unless stencil_transfers=False.  A is the caller's matrix on
@@ -804,6 +815,12 @@ class Multigrid:
                                                       d3.ctypes.data_as(_i64p), int(per), int(n_levels),
                                                       None if masks is None else _p32(masks), C.byref(o),
                                                       C.byref(h))
+        elif _opdep_per is not None:  # tensor_opdep_periodic
+            per, (masks, _, min_coarse) = _opdep_per
+            st = lib().amg_hip_create_tensor_opdep_periodic(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
+                                                            d3.ctypes.data_as(_i64p), int(per), int(n_levels),
+                                                            None if masks is None else _p32(masks),
+                                                            int(min_coarse), C.byref(o), C.byref(h))
         elif _opdep is not None:  # tensor_opdep
             masks, _, min_coarse = _opdep
             st = lib().amg_hip_create_tensor_opdep(n, _p32(colptr), _p32(rowind), _p64(val), _p64(b), dim,
@@ -833,7 +850,7 @@ class Multigrid:
                    no_fusion=False, stream=None, fast_coarse_solve=False, keep_residual=False,
                    exact_coarse_solve=False, exact_gs=False, cheb_degree=2, cheb_lower=0.3, cheb_upper=1.0,
                    window=False, host_galerkin=False, fuse_prolong=False, natural_sides=0, singular=False,
-                   cyclic_lines=False, _semi=None, _periodic=None, _opdep=None):
+                   cyclic_lines=False, _semi=None, _periodic=None, _opdep=None, _opdep_per=None):
         """Multigrid.tensor for a matrix that sits on the device, with the set-up on the device
         (amg_hip_create_tensor_dev).  A is in CSR: crow (n + 1 int32 row pointers), col (int32,
         ascending inside a row), val (float64), and b (n float64), each a contiguous 1-D torch tensor
@@ -898,6 +915,12 @@ class Multigrid:
                                                           d3.ctypes.data_as(_i64p), int(per), int(n_levels),
                                                           None if masks is None else _p32(masks), C.byref(o),
                                                           C.byref(h))
+        elif _opdep_per is not None:  # tensor_opdep_periodic_dev
+            per, (masks, _, min_coarse) = _opdep_per
+            st = lib().amg_hip_create_tensor_opdep_periodic_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
+                                                                d3.ctypes.data_as(_i64p), int(per), int(n_levels),
+                                                                None if masks is None else _p32(masks),
+                                                                int(min_coarse), C.byref(o), C.byref(h))
         elif _opdep is not None:  # tensor_opdep_dev
             masks, _, min_coarse = _opdep
             st = lib().amg_hip_create_tensor_opdep_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], dim,
@@ -953,6 +976,31 @@ class Multigrid:
         options as for Multigrid.tensor."""
         return cls.tensor(colptr, rowind, val, b, dims, n_levels,
                           _opdep=cls._semi_rule(n_levels, axis_masks, 1.0, min_coarse), **opts)
+
+    @classmethod
+    def tensor_opdep_periodic(cls, colptr, rowind, val, b, dims, n_levels, periodic_axes, axis_masks=None,
+                              min_coarse=32, **opts):
+        """Multigrid.tensor_opdep for an operator with PERIODIC axes (amg_hip_create_tensor_opdep_periodic).
+        periodic_axes: bit a = axis a wraps around (1 = x, 2 = y, 4 = z); A holds the wrap entries.  A
+        coarsened periodic axis needs an even length of at least 4 on its level; every even point of it
+        has both weights, fine point 0 taking its low one from coarse point m/2 - 1.  The automatic rule
+        (axis_masks=None) leaves out a periodic axis that is odd or shorter than 4.  natural_sides names
+        sides of the other axes only; singular=True needs all of those (none when every axis is
+        periodic).  periodic_axes=0: Multigrid.tensor_opdep's solver.  Options as for Multigrid.tensor."""
+        return cls.tensor(colptr, rowind, val, b, dims, n_levels,
+                          _opdep_per=(int(periodic_axes), cls._semi_rule(n_levels, axis_masks, 1.0, min_coarse)),
+                          **opts)
+
+    @classmethod
+    def tensor_opdep_periodic_dev(cls, crow, col, val, b, dims, n_levels, periodic_axes, axis_masks=None,
+                                  min_coarse=32, **opts):
+        """Multigrid.tensor_opdep_periodic for a CSR matrix that sits on the device
+        (amg_hip_create_tensor_opdep_periodic_dev); arguments as for Multigrid.tensor_dev.  The arrays are
+        checked on the device and the hierarchy is built by the host constructor, always:
+        setup_on_device() reports 0."""
+        return cls.tensor_dev(crow, col, val, b, dims, n_levels,
+                              _opdep_per=(int(periodic_axes), cls._semi_rule(n_levels, axis_masks, 1.0, min_coarse)),
+                              **opts)
 
     def axis_weights(self, level):
         """The compact weights of `level` of a tensor_opdep solver (amg_hip_get_axis_weights): an array of
@@ -1739,30 +1787,42 @@ def _axis_sizes(dims, axis):
     return dim, d3, axis, n_h, n_H
 
 
-def axis_restrict(dims, axis, W, r):
+def axis_restrict(dims, axis, W, r, periodic=None, vec_shift=0):
     """f_H = R r for the single-axis transfer of the fine grid `dims` with the compact weights W of
-    Multigrid.axis_weights, 2 (n_h - n_H) doubles (amg_hip_axis_restrict: K-AxisRestrict)."""
+    Multigrid.axis_weights, 2 (n_h - n_H) doubles (amg_hip_axis_restrict: K-AxisRestrict).
+    periodic (not None: amg_hip_axis_restrict_per): True = the axis wraps (even, at least 4 points; W[0]
+    of a line is w_lo of fine point 0 from the last coarse point); vec_shift=1 puts the device vectors 8
+    bytes past a 16-byte boundary."""
     dim, d3, axis, n_h, n_H = _axis_sizes(dims, axis)
     W, r = _a64(np.ravel(W)), _a64(r)
     if n_H and (r.size != n_h or W.size != 2 * (n_h - n_H)):
         raise ValueError(f"`r` / `W` must have {n_h} / {2 * (n_h - n_H)} entries, got {r.size} / {W.size}")
     out = np.empty(n_H, np.float64)
-    st = lib().amg_hip_axis_restrict(dim, d3.ctypes.data_as(_i64p), axis, _p64(W), _p64(r), _p64(out))
+    if periodic is None and not vec_shift:
+        st = lib().amg_hip_axis_restrict(dim, d3.ctypes.data_as(_i64p), axis, _p64(W), _p64(r), _p64(out))
+    else:
+        st = lib().amg_hip_axis_restrict_per(dim, d3.ctypes.data_as(_i64p), axis, int(periodic or 0), _p64(W),
+                                             _p64(r), _p64(out), int(vec_shift))
     if st == EINVAL:
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)
     return out
 
 
-def axis_prolong_add(dims, axis, W, u_H, u_h):
-    """u_h + P u_H for the same transfer (amg_hip_axis_prolong_add: K-AxisProlong); returns a new array."""
+def axis_prolong_add(dims, axis, W, u_H, u_h, periodic=None, vec_shift=0):
+    """u_h + P u_H for the same transfer (amg_hip_axis_prolong_add: K-AxisProlong); returns a new array.
+    periodic / vec_shift: as for axis_restrict (amg_hip_axis_prolong_add_per)."""
     dim, d3, axis, n_h, n_H = _axis_sizes(dims, axis)
     W, u_H = _a64(np.ravel(W)), _a64(u_H)
     u_h = np.array(u_h, dtype=np.float64, copy=True)
     if n_H and (u_h.size != n_h or u_H.size != n_H or W.size != 2 * (n_h - n_H)):
         raise ValueError(f"`u_h` / `u_H` / `W` must have {n_h} / {n_H} / {2 * (n_h - n_H)} entries, got "
                          f"{u_h.size} / {u_H.size} / {W.size}")
-    st = lib().amg_hip_axis_prolong_add(dim, d3.ctypes.data_as(_i64p), axis, _p64(W), _p64(u_H), _p64(u_h))
+    if periodic is None and not vec_shift:
+        st = lib().amg_hip_axis_prolong_add(dim, d3.ctypes.data_as(_i64p), axis, _p64(W), _p64(u_H), _p64(u_h))
+    else:
+        st = lib().amg_hip_axis_prolong_add_per(dim, d3.ctypes.data_as(_i64p), axis, int(periodic or 0), _p64(W),
+                                                _p64(u_H), _p64(u_h), int(vec_shift))
     if st == EINVAL:
         raise ValueError(lib().amg_hip_last_error().decode())
     _chk(st)

@@ -275,14 +275,16 @@ uint32_t tensor_auto_mask(int dim, const int64_t d[3], const double w[3], double
   return mask;
 }
 
-uint32_t tensor_opdep_auto_mask(int dim, const int64_t d[3], const double w[3]) {
+uint32_t tensor_opdep_auto_mask(int dim, const int64_t d[3], const double w[3], uint32_t periodic) {
   int best = -1;
-  for (int a = 0; a < dim; ++a)
-    if (d[a] >= 2 && (best < 0 || w[a] > w[best])) best = a;  // strictly larger: the lowest axis wins a tie
+  for (int a = 0; a < dim; ++a) {
+    const bool ok = ((periodic >> a) & 1u) ? (d[a] >= 4 && !(d[a] & 1)) : d[a] >= 2;
+    if (ok && (best < 0 || w[a] > w[best])) best = a;  // strictly larger: the lowest axis wins a tie
+  }
   return best < 0 ? 0u : 1u << best;
 }
 
-Sparse axis_P_from_weights(int dim, const int64_t d[3], int axis, const double* W) {
+Sparse axis_P_from_weights(int dim, const int64_t d[3], int axis, const double* W, bool periodic) {
   int64_t c[3];
   tensor_coarse_dims(dim, d, 1u << axis, c);
   const int64_t m = d[axis], mH = c[axis];
@@ -305,6 +307,10 @@ Sparse axis_P_from_weights(int dim, const int64_t d[3], int axis, const double* 
         f[axis] = 2 * H[axis];  // fine point 2 J: this column is its high neighbour
         const int64_t i0 = (f[2] * d[1] + f[1]) * d[0] + f[0];
         const int64_t e0 = (e[2] * ev[1] + e[1]) * ev[0] + e[0];  // even point q = J
+        if (periodic && 2 * H[axis] + 2 == m) {  // the seam: fine point 0 takes its low neighbour from this column
+          P.idx.push_back((int32_t)(i0 - 2 * H[axis] * stride));
+          P.val.push_back(W[2 * (e0 - H[axis] * stride) + 0]);
+        }
         P.idx.push_back((int32_t)i0);
         P.val.push_back(W[2 * e0 + 1]);
         P.idx.push_back((int32_t)(i0 + stride));
@@ -319,7 +325,7 @@ Sparse axis_P_from_weights(int dim, const int64_t d[3], int axis, const double* 
 }
 
 std::string axis_opdep_row(int64_t i, const int32_t* idx, const double* val, int32_t len, int64_t stride, int64_t m,
-                           int axis, double w[2]) {
+                           int axis, double w[2], bool periodic) {
   auto bad = [&](const char* what, double v) {
     return "row " + std::to_string(i) + ": " + what + " is " + std::to_string(v) +
            " (the entries of the row, collapsed onto axis " + std::string(1, "xyz"[axis]) + ")";
@@ -327,14 +333,18 @@ std::string axis_opdep_row(int64_t i, const int32_t* idx, const double* val, int
   const int64_t c = (i / stride) % m;
   w[0] = w[1] = 0.0;
   double sm = 0.0, s0 = 0.0, sp = 0.0;
+  // a periodic axis (even m >= 4) takes the distance mod m: the classes are m - 1, 0, 1, and every
+  // even point has both neighbours
+  const int64_t below = periodic ? m - 1 : -1;
   for (int32_t p = 0; p < len; ++p) {
-    const int64_t dc = (idx[p] / stride) % m - c;
-    if (dc == -1) sm += val[p];
+    int64_t dc = (idx[p] / stride) % m - c;
+    if (periodic && dc < 0) dc += m;
+    if (dc == below) sm += val[p];
     else if (dc == 0) s0 += val[p];
     else if (dc == 1) sp += val[p];
   }
   if (s0 == 0.0 || !std::isfinite(s0)) return bad("the diagonal sum s_0", s0);
-  if (c >= 2) {
+  if (c >= 2 || periodic) {
     w[0] = (-sm) / s0;
     if (!std::isfinite(w[0])) return bad("the weight w_lo", w[0]);
   }
@@ -346,7 +356,7 @@ std::string axis_opdep_row(int64_t i, const int32_t* idx, const double* val, int
 }
 
 std::string axis_opdep_P(const Sparse& M, int dim, const int64_t d[3], int axis, Sparse* P,
-                         std::vector<double>* W) {
+                         std::vector<double>* W, bool periodic) {
   const int64_t m = d[axis], mH = m / 2;
   const int64_t stride = axis == 0 ? 1 : (axis == 1 ? d[0] : d[0] * d[1]);
   const int64_t n = M.n_outer;
@@ -356,11 +366,12 @@ std::string axis_opdep_P(const Sparse& M, int dim, const int64_t d[3], int axis,
     if ((i / stride) % m & 1) continue;
     const int32_t p0 = M.ptr[i];
     const std::string bad =
-        axis_opdep_row(i, M.idx.data() + p0, M.val.data() + p0, M.ptr[i + 1] - p0, stride, m, axis, W->data() + 2 * e);
+        axis_opdep_row(i, M.idx.data() + p0, M.val.data() + p0, M.ptr[i + 1] - p0, stride, m, axis, W->data() + 2 * e,
+                       periodic);
     if (!bad.empty()) return bad;
     ++e;
   }
-  *P = axis_P_from_weights(dim, d, axis, W->data());
+  *P = axis_P_from_weights(dim, d, axis, W->data(), periodic);
   return "";
 }
 

@@ -77,19 +77,27 @@ uint32_t tensor_auto_mask(int dim, const int64_t dims[3], const double w[3], dou
 // m - floor(m / 2); the point with flat index e on it (x fastest) holds W[2 e] = w_lo, W[2 e + 1] =
 // w_hi, 0.0 where the neighbour does not exist.
 // Returns "" or what is wrong (s_0 or a weight that is zero-divided or not finite), naming the row.
+// periodic (amg_hip_create_tensor_opdep_periodic): the axis wraps and has an even length m >= 4 (the
+// caller checks).  The classes of the collapse are (c_col - c) mod m = m - 1, 0, 1, so the wrap entry
+// of fine point 0 goes into s_m and that of fine point m - 1 into s_p; every even point c = 2 q has
+// both neighbours, w_lo from coarse (q - 1) mod (m / 2) and w_hi from coarse q, both kept whatever
+// their value, and no slot of W stands for a missing neighbour.  The rows of a column of P ascend:
+// column m / 2 - 1 of the axis holds fine 0 (w_lo(0)), fine m - 2 (w_hi(m - 2)) and fine m - 1 (1.0).
+// periodic = false: the rule above, bit for bit.
 std::string axis_opdep_P(const Sparse& rows, int dim, const int64_t dims[3], int axis, Sparse* P,
-                         std::vector<double>* W);
+                         std::vector<double>* W, bool periodic = false);
 // The per-row part of axis_opdep_P: row i (even axis coordinate; its `len` entries idx / val in
 // ascending column order) on an axis of length m and flat stride `stride`.  w[0] = w_lo, w[1] = w_hi,
 // 0.0 where the neighbour does not exist.  Returns "" or axis_opdep_P's message for this row; the
 // device set-up (K-AxisWeights) words the row it refused with it.
 std::string axis_opdep_row(int64_t i, const int32_t* idx, const double* val, int32_t len, int64_t stride, int64_t m,
-                           int axis, double w[2]);
+                           int axis, double w[2], bool periodic = false);
 // The CSC P (and nothing else) of a compact weight array: what axis_opdep_P builds from its own W.
-Sparse axis_P_from_weights(int dim, const int64_t dims[3], int axis, const double* W);
+Sparse axis_P_from_weights(int dim, const int64_t dims[3], int axis, const double* W, bool periodic = false);
 // The automatic rule of amg_hip_create_tensor_opdep: the eligible axis (a < dim, dims[a] >= 2) with
 // the largest w[a] of tensor_axis_strength, the lowest axis on a tie; 0: no axis is eligible.
-uint32_t tensor_opdep_auto_mask(int dim, const int64_t dims[3], const double w[3]);
+// periodic (bit a = axis a): a periodic axis is eligible when its length is even and at least 4.
+uint32_t tensor_opdep_auto_mask(int dim, const int64_t dims[3], const double w[3], uint32_t periodic = 0);
 
 // multigrid.hpp:127-130
 inline int64_t coarse_dofs(int64_t n_h) { return (n_h + 1) / 2 - 1; }

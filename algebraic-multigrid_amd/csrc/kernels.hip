@@ -4380,7 +4380,12 @@ __device__ __forceinline__ void axis_load2(const double* c, bool two, double& v0
 // where the address allows (VEC: r is 16-byte aligned), as in tensor_restrict_kernel; along y / z
 // the three loads of a wave are contiguous lines.  The two weights are the second half of W's pair
 // e and the first half of pair e + stride.  uH (may be null) is zeroed in the same pass.
-template <int AXIS, bool VEC>
+// PER: the axis wraps (m even, >= 4; mE = mH = m / 2).  The third point of the last coarse point
+// H = mH - 1 is fine 0, the lowest row of its column of P, so there the sum runs
+// ((+0.0 + w_lo(0) r(0)) + w_hi(m-2) r(m-2)) + 1.0 r(m-1); its weight is the first half of the line's
+// pair 0 and its value a scalar load from the other end of the line (along y / z: of the axis, a
+// contiguous line).  Every other H keeps the order above, and the third term always exists.
+template <int AXIS, bool VEC, bool PER = false>
 __global__ __launch_bounds__(256) void axis_restrict_kernel(
     AxisGrid g, const double* __restrict__ W, const double* __restrict__ r, double* __restrict__ fH,
     double* __restrict__ uH) {
@@ -4391,7 +4396,8 @@ __global__ __launch_bounds__(256) void axis_restrict_kernel(
   const uint32_t I = t % cx, q = t / cx, J = q % cy, K = q / cy;
   if (uH) uH[t] = 0.0;
   const uint32_t H = AXIS == 0 ? I : (AXIS == 1 ? J : K);
-  const bool third = 2u * H + 2u < g.m;
+  const bool third = PER || 2u * H + 2u < g.m;
+  const bool seam = PER && 2u * H + 2u == g.m;
   int64_t a, e, sd;  // fine index of coordinate 2 H, index of that even point, stride of the axis in both
   if (AXIS == 0) {
     a = ((int64_t)K * g.ny + J) * g.nx + 2u * I;
@@ -4406,15 +4412,18 @@ __global__ __launch_bounds__(256) void axis_restrict_kernel(
     e = ((int64_t)K * g.ny + J) * g.nx + I;
     sd = (int64_t)g.nx * g.ny;
   }
+  // the third point and its even point: two steps up the axis, or H (2 H) steps down to fine 0
+  const int64_t a2 = seam ? a - (int64_t)(2u * H) * sd : a + 2 * sd;
+  const int64_t e2 = seam ? e - (int64_t)H * sd : e + sd;
   const double whi = W[2 * e + 1];
-  const double wlo = third ? W[2 * (e + sd)] : 0.0;
+  const double wlo = third ? W[2 * e2] : 0.0;
   double v0, v1, v2 = 0.0;
   if (AXIS == 0 && VEC && (a & 1) == 0) {
     const double2 p = *reinterpret_cast<const double2*>(r + a);
     v0 = p.x;
     v1 = p.y;
-    if (third) v2 = r[a + 2];
-  } else if (AXIS == 0 && VEC && third) {
+    if (third) v2 = r[a2];
+  } else if (AXIS == 0 && VEC && third && !seam) {
     v0 = r[a];
     const double2 p = *reinterpret_cast<const double2*>(r + a + 1);
     v1 = p.x;
@@ -4422,12 +4431,18 @@ __global__ __launch_bounds__(256) void axis_restrict_kernel(
   } else {
     v0 = r[a];
     v1 = r[a + sd];
-    if (third) v2 = r[a + 2 * sd];
+    if (third) v2 = r[a2];
   }
   double s = 0.0;
-  s += whi * v0;
-  s += 1.0 * v1;
-  if (third) s += wlo * v2;
+  if (seam) {
+    s += wlo * v2;
+    s += whi * v0;
+    s += 1.0 * v1;
+  } else {
+    s += whi * v0;
+    s += 1.0 * v1;
+    if (third) s += wlo * v2;
+  }
   fH[t] = s;
 }
 
@@ -4437,7 +4452,11 @@ __global__ __launch_bounds__(256) void axis_restrict_kernel(
 // (c - 1) / 2 with weight 1.0; an even one c / 2 - 1 with w_lo (c >= 2) and c / 2 with w_hi
 // (c + 1 < m), one 16-byte load of W per fine point.  Along x the lane's even point is 2p and its
 // odd one 2p + 1; along y / z both points of the pair have the lane's c and read coarse pairs.
-template <int AXIS, bool VEC>
+// PER: the axis wraps (m even, >= 4; mE = mH = m / 2), so every even c has both neighbours, the low
+// one (c / 2 - 1) mod mH.  At c = 0 that is the LAST coarse point, and the ascending order puts the
+// high term first: t = (+0.0 + w_hi(0) u_H(0)) + w_lo(0) u_H(mH - 1) -- along x a scalar load from
+// the other end of the coarse line in lane p = 0, along y / z a contiguous coarse line.
+template <int AXIS, bool VEC, bool PER = false>
 __global__ __launch_bounds__(256) void axis_prolong_add_kernel(
     AxisGrid g, const double2* __restrict__ W, const double* __restrict__ uH, double* uh) {
   const uint32_t px = (g.nx + 1u) / 2u;  // pairs per fine line
@@ -4450,11 +4469,23 @@ __global__ __launch_bounds__(256) void axis_prolong_add_kernel(
   if (AXIS == 0) {  // mE == px: the even point of the pair is point p of the line's even points
     const double2 w = W[(int64_t)row * g.mE + p];
     const double* c = uH + (int64_t)row * g.mH;
-    if (p >= 1u) t0 += w.x * c[p - 1u];
-    if (two) {  // coarse p exists iff fine 2p + 1 does
+    if (PER) {  // nx = m is even: the pair is whole and coarse p exists
       const double mid = c[p];
-      t0 += w.y * mid;
+      if (p == 0u) {
+        t0 += w.y * mid;
+        t0 += w.x * c[g.mH - 1u];
+      } else {
+        t0 += w.x * c[p - 1u];
+        t0 += w.y * mid;
+      }
       t1 += 1.0 * mid;
+    } else {
+      if (p >= 1u) t0 += w.x * c[p - 1u];
+      if (two) {  // coarse p exists iff fine 2p + 1 does
+        const double mid = c[p];
+        t0 += w.y * mid;
+        t1 += 1.0 * mid;
+      }
     }
   } else {
     const uint32_t cc = AXIS == 1 ? j : k;
@@ -4472,15 +4503,24 @@ __global__ __launch_bounds__(256) void axis_prolong_add_kernel(
       const int64_t e = base(g.mE, h);
       const double2 w0 = W[e];
       const double2 w1 = two ? W[e + 1] : make_double2(0.0, 0.0);
-      if (cc >= 2u) {
-        axis_load2<VEC>(uH + base(g.mH, h - 1u), two, m0, m1);
-        t0 += w0.x * m0;
-        if (two) t1 += w1.x * m1;
-      }
-      if (cc + 1u < g.m) {
-        axis_load2<VEC>(uH + base(g.mH, h), two, m0, m1);
+      if (PER && cc == 0u) {  // the seam line: high first, then the low neighbour on the last coarse line
+        axis_load2<VEC>(uH + base(g.mH, 0u), two, m0, m1);
         t0 += w0.y * m0;
         if (two) t1 += w1.y * m1;
+        axis_load2<VEC>(uH + base(g.mH, g.mH - 1u), two, m0, m1);
+        t0 += w0.x * m0;
+        if (two) t1 += w1.x * m1;
+      } else {
+        if (cc >= 2u) {
+          axis_load2<VEC>(uH + base(g.mH, h - 1u), two, m0, m1);
+          t0 += w0.x * m0;
+          if (two) t1 += w1.x * m1;
+        }
+        if (cc + 1u < g.m) {
+          axis_load2<VEC>(uH + base(g.mH, h), two, m0, m1);
+          t0 += w0.y * m0;
+          if (two) t1 += w1.y * m1;
+        }
       }
     }
   }
@@ -4513,12 +4553,26 @@ static bool axis_grid(int dim, const int64_t dims[3], int axis, AxisGrid* g) {
   g->mE = g->m - g->mH;
   return true;
 }
-hipError_t launch_axis_restrict(int dim, const int64_t dims[3], int axis, const double* W, const double* r,
-                                double* fH, double* uH_zero, hipStream_t st) {
+hipError_t launch_axis_restrict(int dim, const int64_t dims[3], int axis, bool periodic, const double* W,
+                                const double* r, double* fH, double* uH_zero, hipStream_t st) {
   AxisGrid g;
   if (!axis_grid(dim, dims, axis, &g) || !pair_aligned(W)) return hipErrorInvalidValue;
+  if (periodic && (g.m < 4u || (g.m & 1u))) return hipErrorInvalidValue;
   const uint32_t nH = g.nx * g.ny * g.nz / g.m * g.mH;
   const dim3 grid((nH + 255u) / 256u), block(256);
+  if (periodic) {  // the seam forms, beside the open ones below
+    if (axis == 0) {
+      if (pair_aligned(r))
+        hipLaunchKernelGGL((axis_restrict_kernel<0, true, true>), grid, block, 0, st, g, W, r, fH, uH_zero);
+      else
+        hipLaunchKernelGGL((axis_restrict_kernel<0, false, true>), grid, block, 0, st, g, W, r, fH, uH_zero);
+    } else if (axis == 1) {
+      hipLaunchKernelGGL((axis_restrict_kernel<1, false, true>), grid, block, 0, st, g, W, r, fH, uH_zero);
+    } else {
+      hipLaunchKernelGGL((axis_restrict_kernel<2, false, true>), grid, block, 0, st, g, W, r, fH, uH_zero);
+    }
+    return hipGetLastError();
+  }
   if (axis == 0) {
     if (pair_aligned(r))
       hipLaunchKernelGGL((axis_restrict_kernel<0, true>), grid, block, 0, st, g, W, r, fH, uH_zero);
@@ -4531,20 +4585,25 @@ hipError_t launch_axis_restrict(int dim, const int64_t dims[3], int axis, const 
   }
   return hipGetLastError();
 }
-hipError_t launch_axis_prolong_add(int dim, const int64_t dims[3], int axis, const double* W, const double* uH,
-                                   double* uh, hipStream_t st) {
+hipError_t launch_axis_prolong_add(int dim, const int64_t dims[3], int axis, bool periodic, const double* W,
+                                   const double* uH, double* uh, hipStream_t st) {
   AxisGrid g;
   if (!axis_grid(dim, dims, axis, &g) || !pair_aligned(W)) return hipErrorInvalidValue;
+  if (periodic && (g.m < 4u || (g.m & 1u))) return hipErrorInvalidValue;
   const uint32_t total = ((g.nx + 1u) / 2u) * g.ny * g.nz;
   const dim3 grid((total + 255u) / 256u), block(256);
   const double2* W2 = reinterpret_cast<const double2*>(W);
   const bool vec = pair_aligned(uh) && pair_aligned(uH);
-#define AMG_AXIS_PROLONG(AX)                                                                              \
-  if (vec) hipLaunchKernelGGL((axis_prolong_add_kernel<AX, true>), grid, block, 0, st, g, W2, uH, uh);   \
-  else hipLaunchKernelGGL((axis_prolong_add_kernel<AX, false>), grid, block, 0, st, g, W2, uH, uh)
-  if (axis == 0) { AMG_AXIS_PROLONG(0); }
-  else if (axis == 1) { AMG_AXIS_PROLONG(1); }
-  else { AMG_AXIS_PROLONG(2); }
+#define AMG_AXIS_PROLONG(AX, PER)                                                                              \
+  if (vec) hipLaunchKernelGGL((axis_prolong_add_kernel<AX, true, PER>), grid, block, 0, st, g, W2, uH, uh);   \
+  else hipLaunchKernelGGL((axis_prolong_add_kernel<AX, false, PER>), grid, block, 0, st, g, W2, uH, uh)
+  if (periodic) {
+    if (axis == 0) { AMG_AXIS_PROLONG(0, true); }
+    else if (axis == 1) { AMG_AXIS_PROLONG(1, true); }
+    else { AMG_AXIS_PROLONG(2, true); }
+  } else if (axis == 0) { AMG_AXIS_PROLONG(0, false); }
+  else if (axis == 1) { AMG_AXIS_PROLONG(1, false); }
+  else { AMG_AXIS_PROLONG(2, false); }
 #undef AMG_AXIS_PROLONG
   return hipGetLastError();
 }

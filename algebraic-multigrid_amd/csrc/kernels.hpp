@@ -441,12 +441,16 @@ hipError_t launch_tensor_prolong_add(int dim, const int64_t dims[3], uint32_t ma
 // W[2 e + 1] = w_hi (coarse q), 0.0 where the neighbour does not exist.  The weights are no powers
 // of two: every product is rounded, then added in the order of the CSR SpMV with R / P (from +0.0,
 // ascending column), so the bits are those of launch_csr(CSR_SPMV / CSR_SPMV_ADD) on R / P.
+// periodic: the axis wraps (host_setup.hpp: axis_opdep_P with periodic; its length even and at least
+// 4, else hipErrorInvalidValue): every even point has both weights, w_lo of fine 0 belongs to the
+// last coarse point, and the ascending order changes at the seam alone -- the last coarse point adds
+// fine 0 first, fine 0 adds its high neighbour first.  false: the open kernels, the same code as before.
 // f_H = R r, uH_zero (may be null) zero-filled in the same pass
-hipError_t launch_axis_restrict(int dim, const int64_t dims[3], int axis, const double* W, const double* r,
-                                double* fH, double* uH_zero, hipStream_t st);
+hipError_t launch_axis_restrict(int dim, const int64_t dims[3], int axis, bool periodic, const double* W,
+                                const double* r, double* fH, double* uH_zero, hipStream_t st);
 // u_h = u_h + P u_H
-hipError_t launch_axis_prolong_add(int dim, const int64_t dims[3], int axis, const double* W, const double* uH,
-                                   double* uh, hipStream_t st);
+hipError_t launch_axis_prolong_add(int dim, const int64_t dims[3], int axis, bool periodic, const double* W,
+                                   const double* uH, double* uh, hipStream_t st);
 // x[j * stride] = +0.0 for j < count (count <= 64, else hipErrorInvalidValue)
 hipError_t launch_zero_strided(double* x, int64_t stride, int count, hipStream_t st);
 hipError_t launch_add_inplace(int64_t n, const double* x, double* y, hipStream_t st);

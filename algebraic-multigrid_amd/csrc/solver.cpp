@@ -1455,7 +1455,7 @@ struct Level {
     if (lazy_linear && P_csc.ptr.empty()) P_csc = linear_P(n, n_coarse);  // interpolator.hpp:106-129
     if (tensor_stencil && P_csc.ptr.empty()) P_csc = tensor_P(tdim, dims, tmask, tsides, tper);
     if (axis >= 0 && P_csc.ptr.empty() && ensure_axis_weights() == hipSuccess)
-      P_csc = axis_P_from_weights(tdim, dims, axis, axis_W.data());
+      P_csc = axis_P_from_weights(tdim, dims, axis, axis_W.data(), axis_periodic());
     return P_csc;
   }
   const Sparse& R() const {
@@ -1483,7 +1483,9 @@ struct Level {
   // A level built on the device (amg_hip_create_tensor_opdep_dev: K-AxisWeights) has its weights in
   // axis_W_dev alone: ensure_axis_weights() downloads them on first use, P() / R() build the host
   // operators from them (axis_P_from_weights) when a getter or a CSR cycle asks.
+  // amg_hip_create_tensor_opdep_periodic: the axis may be one of tper's, and then wraps (the seam forms)
   int axis = -1;
+  bool axis_periodic() const { return axis >= 0 && ((tper >> axis) & 1u); }
   bool axis_stencil = false;
   mutable std::vector<double> axis_W;
   DevMem axis_W_dev;
@@ -2527,7 +2529,7 @@ amg_hip_status enqueue_restrict(amg_hip_solver* s, int l, bool zero_coarse_u) {
     HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(), uH, st));
     s->acct(8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
   } else if (L.axis_stencil) {                                 // the same two steps, one axis, weights of A_l
-    HIP_TRY(launch_axis_restrict(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), L.r.as<double>(),
+    HIP_TRY(launch_axis_restrict(L.tdim, L.dims, L.axis, L.axis_periodic(), L.axis_W_dev.as<double>(), L.r.as<double>(),
                                  C.f.as<double>(), uH, st));
     s->acct(8.0 * L.n + 16.0 * (L.n - C.n) + (zero_coarse_u ? 16.0 : 8.0) * C.n);
   } else {
@@ -2555,7 +2557,7 @@ amg_hip_status enqueue_prolong_add(amg_hip_solver* s, int l, double* out) {
     HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
     s->acct(8.0 * C.n + 16.0 * L.n);
   } else if (L.axis_stencil) {
-    HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_W_dev.as<double>(), C.u.as<double>(),
+    HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_periodic(), L.axis_W_dev.as<double>(), C.u.as<double>(),
                                     L.u.as<double>(), st));
     s->acct(16.0 * L.n + 16.0 * (L.n - C.n) + 8.0 * C.n);
   } else {
@@ -3036,6 +3038,9 @@ struct SemiRule {
   // theta is not used) and the weights of axis_opdep_P instead of tensor_P's
   bool opdep = false;
   const char* opdep_who = "amg_hip_create_tensor_opdep: ";  // the entry point a refused row is reported under
+  // amg_hip_create_tensor_opdep_periodic(_dev): the spec's periodic axes are checked on top of the
+  // rule, a coarsened periodic axis takes the seam form of axis_opdep_P, and the set-up runs on the host
+  bool opdep_periodic = false;
 };
 // a one-level solver's coarsest right-hand side is the caller's b, which the pinned solve must not alter
 const char* const SINGULAR_ONE_LEVEL =
@@ -3246,7 +3251,7 @@ amg_hip_status level_axis_mask(const Level& L, int l, int dim, const SemiRule* s
     if (!*last) {
       double w[3];
       AMG_TRY(strengths(w));
-      *mask = semi->opdep ? tensor_opdep_auto_mask(dim, L.dims, w) : tensor_auto_mask(dim, L.dims, w, semi->theta);
+      *mask = semi->opdep ? tensor_opdep_auto_mask(dim, L.dims, w, L.tper) : tensor_auto_mask(dim, L.dims, w, semi->theta);
       *last = *mask == 0;
     }
     if (*last) *mask = 0;
@@ -3563,7 +3568,7 @@ amg_hip_status build_solver(int64_t n, const int32_t* colptr, const int32_t* row
         L.axis_stencil = L.tensor_stencil && g_axis_stencil;
         L.tensor_stencil = false;
         for (L.axis = 0; !((L.tmask >> L.axis) & 1u); ++L.axis) {}
-        const std::string we = axis_opdep_P(A_r, h.dim, L.dims, L.axis, &L.P_csc, &L.axis_W);
+        const std::string we = axis_opdep_P(A_r, h.dim, L.dims, L.axis, &L.P_csc, &L.axis_W, L.axis_periodic());
         if (!we.empty()) return fail(AMG_HIP_EINVAL, std::string(h.semi->opdep_who) + "level " + std::to_string(l) + ": " + we);
         L.R_csc = transpose(L.P_csc);
         if (dev && L.axis_stencil) HIP_TRY(upload(L.axis_W_dev, L.axis_W.data(), L.axis_W.size()));
@@ -5177,13 +5182,49 @@ amg_hip_status amg_hip_create_tensor_opdep(int64_t n, const int32_t* colptr, con
   return build_solver(n, colptr, rowind, val, b, n_levels, &o, out, tensor_spec(dim, dims, &rule));
 }
 
+// The checks amg_hip_create_tensor_opdep_periodic adds to amg_hip_create_tensor_opdep's, in
+// amg_hip_create_tensor_periodic's order and words: the mask itself, the explicit masks on every
+// level's grid (they passed the rule's own checks already), the sides a periodic axis cannot have.
+static amg_hip_status opdep_periodic_args(const std::string& who, int32_t dim, const int64_t* dims,
+                                          int32_t periodic_axes, int32_t n_levels, const int32_t* axis_masks,
+                                          const amg_hip_options& o) {
+  const std::string pe = periodic_axes_error(dim, periodic_axes);
+  if (!pe.empty()) return fail(AMG_HIP_EINVAL, who + pe);
+  if (axis_masks) {
+    const std::string le = level_walk_error(who, dim, dims, n_levels, axis_masks, (uint32_t)periodic_axes, true);
+    if (!le.empty()) return fail(AMG_HIP_EINVAL, le);
+  }
+  const std::string se = sides_error(o, dim, (uint32_t)periodic_axes, false);
+  if (!se.empty()) return fail(AMG_HIP_EINVAL, se);
+  return AMG_HIP_OK;
+}
+
+// amg_hip_create_tensor_opdep with periodic axes: its checks under this name, then the periodic ones.
+amg_hip_status amg_hip_create_tensor_opdep_periodic(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                                    const double* val, const double* b, int32_t dim,
+                                                    const int64_t* dims, int32_t periodic_axes, int32_t n_levels,
+                                                    const int32_t* axis_masks, int64_t min_coarse,
+                                                    const amg_hip_options* opts, amg_hip_solver** out) {
+  static const std::string who = "amg_hip_create_tensor_opdep_periodic: ";
+  amg_hip_options o;
+  AMG_TRY(out_and_options(opts, out, &o));
+  AMG_TRY(tensor_grid_args(who, n, dim, dims, o.window, "single-axis"));
+  SemiRule rule{axis_masks, 1.0, min_coarse};
+  rule.opdep = true;
+  rule.opdep_who = "amg_hip_create_tensor_opdep_periodic: ";
+  rule.opdep_periodic = true;
+  AMG_TRY(semi_args(who, dim, dims, n_levels, rule));
+  AMG_TRY(opdep_periodic_args(who, dim, dims, periodic_axes, n_levels, axis_masks, o));
+  return build_solver(n, colptr, rowind, val, b, n_levels, &o, out, tensor_spec(dim, dims, &rule, periodic_axes));
+}
+
 amg_hip_status amg_hip_get_axis_weights(const amg_hip_solver* s, int32_t level, double* W) {
   if (!s || !W) return fail(AMG_HIP_EINVAL, "null argument");
   if (level < 0 || level + 1 >= (int)s->lv.size())
     return fail(AMG_HIP_EINVAL, "level out of range (the coarsest level has no transfers)");
   const Level& L = s->lv[level];
   if (L.axis < 0)
-    return fail(AMG_HIP_EINVAL, "amg_hip_get_axis_weights: the solver was not made by amg_hip_create_tensor_opdep");
+    return fail(AMG_HIP_EINVAL, "amg_hip_get_axis_weights: the solver was not made by amg_hip_create_tensor_opdep");  // or _opdep_periodic
   if (L.axis_W.empty() && !s->opt.host_only) HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(L.ensure_axis_weights());
   std::memcpy(W, L.axis_W.data(), sizeof(double) * L.axis_W.size());
@@ -5406,6 +5447,8 @@ static amg_hip_status create_tensor_dev(const std::string& who, int64_t n, const
     if (n_levels < 1) return fail(AMG_HIP_EINVAL, "`n_levels` must be at least 1");
     if (rule) {
       AMG_TRY(semi_args(who, h.dim, h.dims, n_levels, *rule));
+      if (rule->opdep_periodic)
+        AMG_TRY(opdep_periodic_args(who, h.dim, h.dims, (int32_t)h.periodic, n_levels, rule->masks, o));
     } else {  // the levels the rule allows
       const std::string e = level_walk_error(who, h.dim, h.dims, n_levels, nullptr, 0);
       if (!e.empty()) return fail(AMG_HIP_EINVAL, e);
@@ -5416,6 +5459,7 @@ static amg_hip_status create_tensor_dev(const std::string& who, int64_t n, const
   amg_hip_options od = o;
   if (h.periodic_ctor && !g_periodic_device_setup) od.host_galerkin = 1;  // copy + check only
   if (rule && rule->opdep && !g_axis_stencil) od.host_galerkin = 1;       // transfer kind 0 needs CSR(P), CSR(R): host
+  if (rule && rule->opdep_periodic) od.host_galerkin = 1;  // K-AxisWeights / K-AxisGalerkin know no seam: copy + check only
   amg_hip_status r = build_tensor_user_device(who, n, rowptr_dev, col_dev, val_dev, b_dev, n_levels, h, od, out,
                                               &unsupported);
   if (r != AMG_HIP_OK || !unsupported) return r;
@@ -5468,6 +5512,19 @@ amg_hip_status amg_hip_create_tensor_opdep_dev(int64_t n, const int32_t* rowptr_
   rule.opdep_who = "amg_hip_create_tensor_opdep_dev: ";
   return create_tensor_dev(rule.opdep_who, n, rowptr_dev, col_dev, val_dev, b_dev, n_levels, tensor_spec(dim, dims), &rule,
                            opts, out);
+}
+
+amg_hip_status amg_hip_create_tensor_opdep_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                                        const double* val_dev, const double* b_dev, int32_t dim,
+                                                        const int64_t* dims, int32_t periodic_axes, int32_t n_levels,
+                                                        const int32_t* axis_masks, int64_t min_coarse,
+                                                        const amg_hip_options* opts, amg_hip_solver** out) {
+  SemiRule rule{axis_masks, 1.0, min_coarse};  // as amg_hip_create_tensor_opdep_periodic
+  rule.opdep = true;
+  rule.opdep_who = "amg_hip_create_tensor_opdep_periodic_dev: ";
+  rule.opdep_periodic = true;
+  return create_tensor_dev(rule.opdep_who, n, rowptr_dev, col_dev, val_dev, b_dev, n_levels,
+                           tensor_spec(dim, dims, nullptr, periodic_axes), &rule, opts, out);
 }
 
 amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
@@ -6848,47 +6905,79 @@ static amg_hip_status tensor_prolong_add_host(const char* who, int32_t dim, cons
   return AMG_HIP_OK;
 }
 // the fine grid, the axis and the sizes of a stand-alone K-AxisRestrict / K-AxisProlong call
-static amg_hip_status axis_transfer_args(const char* who, int32_t dim, const int64_t* dims, int32_t axis, int64_t* n_h,
-                                         int64_t* n_H) {
+static amg_hip_status axis_transfer_args(const char* who, int32_t dim, const int64_t* dims, int32_t axis,
+                                         int32_t periodic, int32_t vec_shift, int64_t* n_h, int64_t* n_H) {
   std::string e = tensor_dims_error(dim, dims);
   if (e.empty() && (axis < 0 || axis >= dim)) e = "`axis` must be in [0, " + std::to_string(dim) + "), got " + std::to_string(axis);
   if (e.empty()) e = semi_mask_error(0, dim, dims, (int64_t)1 << axis);
+  if (e.empty() && periodic != 0 && periodic != 1) e = "`periodic` must be 0 or 1, got " + std::to_string(periodic);
+  if (e.empty() && vec_shift != 0 && vec_shift != 1) e = "`vec_shift` must be 0 or 1, got " + std::to_string(vec_shift);
+  if (e.empty() && periodic && (dims[axis] < 4 || (dims[axis] & 1)))
+    e = "axis " + std::string(1, "xyz"[axis]) + " has " + std::to_string(dims[axis]) +
+        " points; a coarsened periodic axis needs an even length of at least 4";
   if (!e.empty()) return fail(AMG_HIP_EINVAL, std::string(who) + ": " + e);
   *n_h = dims[0] * dims[1] * dims[2];
   *n_H = *n_h / dims[axis] * (dims[axis] / 2);
   return AMG_HIP_OK;
 }
-amg_hip_status amg_hip_axis_restrict(int32_t dim, const int64_t* dims, int32_t axis, const double* W, const double* r,
-                                     double* f_H) {
+// periodic / vec_shift: the _per entry points (0, 0 for the others).  A vector of `len` doubles lives
+// `vec_shift` doubles into an allocation of len + 1, so that it starts 8 bytes past a 16-byte boundary.
+static amg_hip_status axis_restrict_host(const char* who, int32_t dim, const int64_t* dims, int32_t axis,
+                                         int32_t periodic, const double* W, const double* r, double* f_H,
+                                         int32_t vec_shift) {
   int64_t n_h = 0, n_H = 0;
-  amg_hip_status st = axis_transfer_args("amg_hip_axis_restrict", dim, dims, axis, &n_h, &n_H);
+  amg_hip_status st = axis_transfer_args(who, dim, dims, axis, periodic, vec_shift, &n_h, &n_H);
   if (st != AMG_HIP_OK) return st;
   if (!W || !r || !f_H) return fail(AMG_HIP_EINVAL, "bad argument");
   if ((st = need_device()) != AMG_HIP_OK) return st;
   DevMem dw, dr, df;
   HIP_TRY(upload(dw, W, (size_t)(2 * (n_h - n_H))));
-  HIP_TRY(upload(dr, r, (size_t)n_h));
-  HIP_TRY(df.alloc(sizeof(double) * n_H));
-  HIP_TRY(launch_axis_restrict(dim, dims, axis, dw.as<double>(), dr.as<double>(), df.as<double>(), nullptr, nullptr));
+  HIP_TRY(dr.alloc(sizeof(double) * (n_h + 1)));
+  HIP_TRY(df.alloc(sizeof(double) * (n_H + 1)));
+  double* rd = dr.as<double>() + vec_shift;
+  double* fd = df.as<double>() + vec_shift;
+  HIP_TRY(hipMemcpy(rd, r, sizeof(double) * n_h, hipMemcpyHostToDevice));
+  HIP_TRY(launch_axis_restrict(dim, dims, axis, periodic != 0, dw.as<double>(), rd, fd, nullptr, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(f_H, df.p, sizeof(double) * n_H, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(f_H, fd, sizeof(double) * n_H, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
 }
-amg_hip_status amg_hip_axis_prolong_add(int32_t dim, const int64_t* dims, int32_t axis, const double* W,
-                                        const double* u_H, double* u_h) {
+static amg_hip_status axis_prolong_add_host(const char* who, int32_t dim, const int64_t* dims, int32_t axis,
+                                            int32_t periodic, const double* W, const double* u_H, double* u_h,
+                                            int32_t vec_shift) {
   int64_t n_h = 0, n_H = 0;
-  amg_hip_status st = axis_transfer_args("amg_hip_axis_prolong_add", dim, dims, axis, &n_h, &n_H);
+  amg_hip_status st = axis_transfer_args(who, dim, dims, axis, periodic, vec_shift, &n_h, &n_H);
   if (st != AMG_HIP_OK) return st;
   if (!W || !u_H || !u_h) return fail(AMG_HIP_EINVAL, "bad argument");
   if ((st = need_device()) != AMG_HIP_OK) return st;
   DevMem dw, dH, dh;
   HIP_TRY(upload(dw, W, (size_t)(2 * (n_h - n_H))));
-  HIP_TRY(upload(dH, u_H, (size_t)n_H));
-  HIP_TRY(upload(dh, u_h, (size_t)n_h));
-  HIP_TRY(launch_axis_prolong_add(dim, dims, axis, dw.as<double>(), dH.as<double>(), dh.as<double>(), nullptr));
+  HIP_TRY(dH.alloc(sizeof(double) * (n_H + 1)));
+  HIP_TRY(dh.alloc(sizeof(double) * (n_h + 1)));
+  double* Hd = dH.as<double>() + vec_shift;
+  double* hd = dh.as<double>() + vec_shift;
+  HIP_TRY(hipMemcpy(Hd, u_H, sizeof(double) * n_H, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(hd, u_h, sizeof(double) * n_h, hipMemcpyHostToDevice));
+  HIP_TRY(launch_axis_prolong_add(dim, dims, axis, periodic != 0, dw.as<double>(), Hd, hd, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(u_h, dh.p, sizeof(double) * n_h, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(u_h, hd, sizeof(double) * n_h, hipMemcpyDeviceToHost));
   return AMG_HIP_OK;
+}
+amg_hip_status amg_hip_axis_restrict(int32_t dim, const int64_t* dims, int32_t axis, const double* W, const double* r,
+                                     double* f_H) {
+  return axis_restrict_host("amg_hip_axis_restrict", dim, dims, axis, 0, W, r, f_H, 0);
+}
+amg_hip_status amg_hip_axis_prolong_add(int32_t dim, const int64_t* dims, int32_t axis, const double* W,
+                                        const double* u_H, double* u_h) {
+  return axis_prolong_add_host("amg_hip_axis_prolong_add", dim, dims, axis, 0, W, u_H, u_h, 0);
+}
+amg_hip_status amg_hip_axis_restrict_per(int32_t dim, const int64_t* dims, int32_t axis, int32_t periodic,
+                                         const double* W, const double* r, double* f_H, int32_t vec_shift) {
+  return axis_restrict_host("amg_hip_axis_restrict_per", dim, dims, axis, periodic, W, r, f_H, vec_shift);
+}
+amg_hip_status amg_hip_axis_prolong_add_per(int32_t dim, const int64_t* dims, int32_t axis, int32_t periodic,
+                                            const double* W, const double* u_H, double* u_h, int32_t vec_shift) {
+  return axis_prolong_add_host("amg_hip_axis_prolong_add_per", dim, dims, axis, periodic, W, u_H, u_h, vec_shift);
 }
 
 amg_hip_status amg_hip_tensor_prolong_add(int32_t dim, const int64_t* dims_h, const double* u_H,

@@ -208,17 +208,23 @@ class SemiTensorInterpolator : public TensorInterpolator<EleType> {
 // points (Multigrid::get_n_levels tells).  AMG::Multigrid lets the library build the hierarchy;
 // get_P / get_R hold the operators afterwards.  For coefficients that jump by orders of magnitude
 // from cell to cell, where fixed weights leave the smooth error to the Krylov method.
+// periodic_axes (bit a = axis a, default 0): the axes that wrap (amg_hip_create_tensor_opdep_periodic):
+// A holds the wrap entries, a coarsened periodic axis needs an even length of at least 4, and fine
+// point 0 of such an axis takes its low weight from the last coarse point.
 template <class EleType>
 class OpdepTensorInterpolator : public TensorInterpolator<EleType> {
   std::vector<int32_t> masks_;
   size_t min_coarse_;
+  int32_t periodic_axes_;
 
  public:
   OpdepTensorInterpolator(size_t nx, size_t ny, size_t nz = 1, std::vector<int32_t> masks = {},
-                          size_t min_coarse = 32)
-      : TensorInterpolator<EleType>(nx, ny, nz), masks_(std::move(masks)), min_coarse_(min_coarse) {}
+                          size_t min_coarse = 32, int32_t periodic_axes = 0)
+      : TensorInterpolator<EleType>(nx, ny, nz), masks_(std::move(masks)), min_coarse_(min_coarse),
+        periodic_axes_(periodic_axes) {}
   const std::vector<int32_t>& masks() const { return masks_; }
   size_t min_coarse() const { return min_coarse_; }
+  int32_t periodic_axes() const { return periodic_axes_; }
   void make_operators(size_t, size_t, size_t) override {
     throw std::logic_error("OpdepTensorInterpolator: the weights depend on the level matrix; "
                            "AMG::Multigrid builds the operators");

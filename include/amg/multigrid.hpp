@@ -158,10 +158,15 @@ class Multigrid {
           if (!opdep->masks().empty() && opdep->masks().size() + 1 != n_levels)
             throw std::invalid_argument("OpdepTensorInterpolator: " + std::to_string(opdep->masks().size()) +
                                         " axis masks for " + std::to_string(n_levels) + " levels");
-          detail::check(amg_hip_create_tensor_opdep(
-              A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(), b.data(), tp->dim(), dims,
-              (int32_t)n_levels, opdep->masks().empty() ? nullptr : opdep->masks().data(),
-              (int64_t)opdep->min_coarse(), &opt, &handle));
+          const int32_t* masks = opdep->masks().empty() ? nullptr : opdep->masks().data();
+          if (opdep->periodic_axes())  // the seam form of the weights on the axes that wrap
+            detail::check(amg_hip_create_tensor_opdep_periodic(
+                A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(), b.data(), tp->dim(), dims,
+                opdep->periodic_axes(), (int32_t)n_levels, masks, (int64_t)opdep->min_coarse(), &opt, &handle));
+          else
+            detail::check(amg_hip_create_tensor_opdep(
+                A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(), b.data(), tp->dim(), dims,
+                (int32_t)n_levels, masks, (int64_t)opdep->min_coarse(), &opt, &handle));
         } else {
           detail::check(amg_hip_create_tensor(A0.rows(), A0.outerIndexPtr(), A0.innerIndexPtr(), A0.valuePtr(),
                                               b.data(), tp->dim(), dims, (int32_t)n_levels, &opt, &handle));

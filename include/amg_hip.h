@@ -480,7 +480,8 @@ amg_hip_status amg_hip_create_tensor_semi(int64_t n, const int32_t* colptr, cons
  * cell (layered media, composites), where the fixed weights of the other tensor constructors leave
  * the smooth error to the Krylov method.  Arrays, grid, options and argument checks are those of
  * amg_hip_create_tensor_semi, all before the device is touched; opts->window = 1:
- * AMG_HIP_EUNSUPPORTED.  There is no periodic form.
+ * AMG_HIP_EUNSUPPORTED.  Periodic axes: amg_hip_create_tensor_opdep_periodic (on a matrix with wrap
+ * entries this constructor skips them -- their axis distance is m - 1 -- and P 1 != 1 along the seam).
  * axis_masks != NULL: n_levels - 1 masks of exactly one bit each (1, 2, or 4 when dim = 3);
  * `min_coarse` is ignored and the solver has exactly n_levels levels.  AMG_HIP_EINVAL with the level
  * in the message for a mask of several bits, a zero mask and a masked axis of fewer than 2 points.
@@ -518,6 +519,51 @@ amg_hip_status amg_hip_create_tensor_opdep(int64_t n, const int32_t* colptr, con
                                            const int64_t* dims /* 3 */, int32_t n_levels,
                                            const int32_t* axis_masks /* n_levels - 1 single-axis masks, or NULL */,
                                            int64_t min_coarse, const amg_hip_options* opts, amg_hip_solver** out);
+/* amg_hip_create_tensor_opdep on a grid with periodic axes (bit a of `periodic_axes` = axis a, as for
+ * amg_hip_create_tensor_periodic): unit cells of composites and layered media, where the coefficient
+ * jumps AND every axis wraps.  A has the wrap entries between the coordinates 0 and m - 1 of a
+ * periodic axis.  periodic_axes = 0 gives amg_hip_create_tensor_opdep's solver bit for bit.
+ * Weights on a level that coarsens a PERIODIC axis a of length m (even and at least 4; coarse length
+ * m / 2, coarse point J at fine coordinate 2 J + 1 as before): the entries of row i are added in
+ * ascending column order from +0.0 into s_m, s_0, s_p by (c_col - c) mod m = m - 1, 0, 1; every other
+ * distance is skipped, structural zeros are added.  EVERY even c = 2 q has both neighbours: w_lo =
+ * (-s_m) / s_0 from coarse (q - 1) mod (m / 2) and w_hi = (-s_p) / s_0 from coarse q, one negation and
+ * one division each, both kept even when they come out 0.0 or -0.0; no slot of
+ * amg_hip_get_axis_weights stands for a missing neighbour on such a level.  The rows of a column of
+ * P ascend: column m / 2 - 1 of the axis holds fine 0 (w_lo(0)), fine m - 2 (w_hi(m - 2)) and fine
+ * m - 1 (1.0) in that order, and amg_hip_get_transfer returns them so.  The refusals (s_0 zero or not
+ * finite, a weight not finite) are _tensor_opdep's.  A periodic axis that a level does not coarsen
+ * needs nothing (its wrap entries have distance 0 on the coarsened axis and go into s_0); a coarsened
+ * axis that is not periodic keeps _tensor_opdep's rule bit for bit.  R = P^T and the host Galerkin
+ * product as there: the level matrices are amg_hip_create_custom's on the P / R of
+ * amg_hip_get_transfer, bit for bit.
+ * The sums of the transfers run from +0.0 in ascending column order, which changes at the seam alone:
+ * restriction, last coarse point: f = ((+0.0 + w_lo(0) r(0)) + w_hi(m-2) r(m-2)) + 1.0 r(m-1);
+ * prolongation, fine point 0: t = (+0.0 + w_hi(0) u_H(0)) + w_lo(0) u_H(m/2 - 1).  Kind 3 (the PER
+ * forms of K-AxisRestrict / K-AxisProlong) and kind 0 give the same bits.
+ * axis_masks == NULL: _tensor_opdep's rule; an axis a < dim is eligible when it is not periodic and
+ * has at least 2 points, or is periodic with an even length of at least 4.  Explicit masks: a masked
+ * periodic axis of odd length or below 4 is AMG_HIP_EINVAL with the level in the message.
+ * Argument checks, all before the device is touched: _tensor_opdep's in its words under this name,
+ * then amg_hip_create_tensor_periodic's: periodic_axes negative or with bits at or above dim; a
+ * natural_sides bit on a periodic axis; singular = 1 unless both side bits of every non-periodic
+ * axis are set (all axes periodic with natural_sides = 0 is the fully periodic singular case, where
+ * b needs a zero mean and amg_hip_set_mean_projection helps).  opts->window = 1:
+ * AMG_HIP_EUNSUPPORTED.  opts->cyclic_lines = 1 stays AMG_HIP_EINVAL as on every constructor but
+ * _tensor_periodic: AMG_HIP_SM_LINE_ALT relaxes OPEN lines on these solvers.
+ * Everything else works as on _tensor_opdep: every smoother, every layout, host_only,
+ * stencil_transfers = 0, amg_hip_set_axis_stencil(0), amg_hip_get_axis_weights, _get_level_axes,
+ * _get_level_dims, _get_transfer, _line_directions, amg_hip_set_mean_projection;
+ * amg_hip_get_periodic_axes reports the mask.  The float and block cycles take their CSR kernels on
+ * these levels.  The coarsest operator of a periodic box has a wide band (the note at
+ * amg_hip_create_tensor_periodic): coarsen until the coarsest level is small.                      */
+amg_hip_status amg_hip_create_tensor_opdep_periodic(int64_t n, const int32_t* colptr, const int32_t* rowind,
+                                                    const double* val, const double* b, int32_t dim,
+                                                    const int64_t* dims /* 3 */, int32_t periodic_axes,
+                                                    int32_t n_levels,
+                                                    const int32_t* axis_masks /* n_levels - 1 single-axis masks, or NULL */,
+                                                    int64_t min_coarse, const amg_hip_options* opts,
+                                                    amg_hip_solver** out);
 /* 0: solvers made by amg_hip_create_tensor_opdep from now on take transfer kind 0 even with
  * opts->stencil_transfers.  Process-wide, default 1, read when a solver is created.  Same bits
  * either way: an A/B switch for tests and measurements.                                          */
@@ -527,7 +573,9 @@ void amg_hip_set_axis_stencil(int32_t on);
  * doubles; also on host_only solvers.  The fine points whose coordinate on the level's axis is even,
  * c = 2 q, form a grid like the level's with that axis shortened to m - floor(m / 2); the point with
  * flat index e on it (x fastest) has W[2 e] = w_lo (its coarse neighbour q - 1) and W[2 e + 1] =
- * w_hi (coarse q), 0.0 where the neighbour does not exist.  AMG_HIP_EINVAL on the coarsest level
+ * w_hi (coarse q), 0.0 where the neighbour does not exist (on a level of
+ * amg_hip_create_tensor_opdep_periodic that coarsens a periodic axis both always exist, and w_lo of
+ * q = 0 belongs to coarse m / 2 - 1).  AMG_HIP_EINVAL on the coarsest level
  * and for every other solver.                                                                     */
 amg_hip_status amg_hip_get_axis_weights(const amg_hip_solver* s, int32_t level, double* W);
 /* Natural boundary sides (opts->natural_sides, opts->singular; honoured by amg_hip_create_tensor,
@@ -754,6 +802,19 @@ amg_hip_status amg_hip_create_tensor_opdep_dev(int64_t n, const int32_t* rowptr_
                                                const int64_t* dims /* 3, host */, int32_t n_levels,
                                                const int32_t* axis_masks /* n_levels - 1 single-axis masks, host, or NULL */,
                                                int64_t min_coarse, const amg_hip_options* opts, amg_hip_solver** out);
+/* amg_hip_create_tensor_opdep_periodic for a caller's matrix in DEVICE memory (CSR, as for
+ * amg_hip_create_tensor_opdep_dev).  The argument checks of the host constructor in the same words
+ * under this name, plus null arrays, before the device is touched; then K-CsrCheck.  Then the arrays
+ * are downloaded, transposed on the host and given to amg_hip_create_tensor_opdep_periodic -- the
+ * silent host path, always: amg_hip_setup_on_device reports 0 and the solver is the host
+ * constructor's.  K-AxisWeights / K-AxisGalerkin with the seam are not written yet.              */
+amg_hip_status amg_hip_create_tensor_opdep_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                                        const double* val_dev, const double* b_dev, int32_t dim,
+                                                        const int64_t* dims /* 3, host */, int32_t periodic_axes,
+                                                        int32_t n_levels,
+                                                        const int32_t* axis_masks /* n_levels - 1 single-axis masks, host, or NULL */,
+                                                        int64_t min_coarse, const amg_hip_options* opts,
+                                                        amg_hip_solver** out);
 /* amg_hip_create_tensor_periodic for a caller's matrix in DEVICE memory (CSR, as for
  * amg_hip_create_tensor_dev).  The arguments are checked as by the host constructor, the arrays by
  * K-CsrCheck, first and whatever the switch says.
@@ -1337,6 +1398,19 @@ amg_hip_status amg_hip_axis_restrict(int32_t dim, const int64_t* dims_h /* 3 */,
                                      const double* r, double* f_H);
 amg_hip_status amg_hip_axis_prolong_add(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis, const double* W,
                                         const double* u_H, double* u_h);
+/* The same two transfers on an axis that wraps (periodic = 1: the PER forms of the kernels, the
+ * weights and the column order of amg_hip_create_tensor_opdep_periodic; every pair of W holds two
+ * weights, W[0] being w_lo of fine point 0 from the LAST coarse point).  Bit-identical to amg_hip_spmv
+ * with the R / P these weights stand for.  periodic = 0: the pair above, same kernels, same bits.
+ * AMG_HIP_EINVAL for periodic other than 0 / 1, and for periodic = 1 on an axis of odd length or of
+ * fewer than 4 points.  vec_shift (0 or 1, else AMG_HIP_EINVAL): the device copies of the vectors
+ * (not of W) start 8 * vec_shift bytes past a 16-byte boundary -- the load forms a caller with
+ * unaligned vectors gets; the result does not depend on it.                                       */
+amg_hip_status amg_hip_axis_restrict_per(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis, int32_t periodic,
+                                         const double* W, const double* r, double* f_H, int32_t vec_shift);
+amg_hip_status amg_hip_axis_prolong_add_per(int32_t dim, const int64_t* dims_h /* 3 */, int32_t axis,
+                                            int32_t periodic, const double* W, const double* u_H, double* u_h,
+                                            int32_t vec_shift);
 /* The same two transfers with an axis mask and the side mask of opts->natural_sides (P1N on the
  * coarsened axes): bit-identical to amg_hip_spmv with the R / P of amg_hip_get_transfer of a solver
  * made with that side mask.  The argument checks of the _axes forms, plus AMG_HIP_EINVAL for a

@@ -16,6 +16,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py opdep [<nx> <ny> <nz>]                      operator-dependent interpolation (tensor_opdep) on a diffusion operator whose conductivity jumps by 10^0..10^4 between blocks of 8 nodes: ms per V-cycle with the matrix-free transfers (kind 3) against CSR transfers (kind 0), PCG to 1e-8 against full coarsening (tensor), host set-up seconds and device matrix bytes (legs alternate)
        config_bench.py opdep10 <nx> <ny> <nz> [csr]                ten cycles of one tensor_opdep hierarchy on that operator (kernel traces)
        config_bench.py opdep-setup [<nx> <ny> <nz>]                set-up seconds of tensor_opdep on that operator assembled on the GPU, explicit masks x, y, (z,) x, ...: the host constructor and amg_hip_create_tensor_opdep_dev alternating, best of three
+       config_bench.py opdep-periodic [<nx> <ny> <nz>]             that operator with every axis periodic (wrap edges, singular, b of zero mean), explicit masks x, y, (z,) x, ...: tensor_opdep (wrap entries skipped), tensor_periodic (fixed weights) and tensor_opdep_periodic (the seam) alternating, all through the host constructors: PCG to 1e-8, ms per V-cycle, and the new solver with CSR transfers (amg_hip_set_axis_stencil(0))
        config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
        config_bench.py singular [<nx> <ny> <nz>]                   PCG to 1e-8 on that operator without a Dirichlet side, one solver: mean projection (amg_hip_set_mean_projection) off and on with the consistent b and on with b + 1e-6, legs alternate; the time added per iteration next to an estimate from the tree reduction's rate in the same run
        config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
@@ -671,6 +672,124 @@ def run_opdep(dims, reps=3, rtol=1e-8, max_iters=400, cycles=10):
                   f"{rtol:g} (relres {rel:.2e}, {'reached' if rel <= rtol else 'NOT reached: capped'})", flush=True)
     print(f"opdep {tag}: best ms/V-cycle: " + ", ".join(f"{k} {v * 1e3:.3f}" for k, v in best_c.items()) +
           "; best PCG ms: " + ", ".join(f"{k} {v * 1e3:.2f} ({iters[k]} it)" for k, v in best_p.items()), flush=True)
+    for mg in legs.values():
+        mg.close()
+
+
+def numpy_jump_periodic(dims, block=8, contrast=4, seed=7):
+    """numpy_jump's operator -- the same block conductivities from the same random stream -- with every axis
+    periodic: the m edges (i, (i + 1) mod m) per grid line, the wrap edge with the k of the block of node
+    m - 1, no face terms.  Singular (zero row sums); the right-hand side has zero mean."""
+    import numpy as np
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed)
+    n = int(np.prod(dims))
+    nb = [(m + block - 1) // block for m in dims]
+    kb = 10.0 ** rng.integers(0, contrast + 1, size=nb[::-1]).astype(np.float64)
+    idx = np.arange(n).reshape(dims[::-1])
+    knode = kb[tuple(np.meshgrid(*[np.arange(m) // block for m in dims[::-1]], indexing="ij"))].ravel()
+    diag = np.zeros(n)
+    rows, cols, vals = [np.arange(n)], [np.arange(n)], [diag]
+    for axis in range(len(dims)):
+        ax = len(dims) - 1 - axis
+        m = dims[axis]
+        lo = np.take(idx, np.arange(m), axis=ax).ravel()
+        hi = np.take(idx, (np.arange(m) + 1) % m, axis=ax).ravel()
+        k = knode[lo]
+        np.add.at(diag, lo, k)
+        np.add.at(diag, hi, k)
+        rows += [lo, hi]
+        cols += [hi, lo]
+        vals += [-k, -k]
+    A = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n)).tocsc()
+    A.sort_indices()
+    b = np.random.default_rng(99).standard_normal(n)
+    return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data, b - b.mean()
+
+
+def periodic_cyclic_masks(dims, min_coarse=32):
+    """cyclic_masks on a box whose axes are all periodic: an axis is halved while it is even with at least
+    4 points"""
+    d, masks, a, idle = list(dims), [], 0, 0
+    while idle < len(d) and d[0] * d[1] * (d[2] if len(d) == 3 else 1) > min_coarse:
+        if d[a] >= 4 and d[a] % 2 == 0:
+            masks.append(1 << a)
+            d[a] //= 2
+            idle = 0
+        else:
+            idle += 1
+        a = (a + 1) % len(d)
+    return masks
+
+
+def run_opdep_periodic(dims, reps=3, rtol=1e-8, max_iters=400, cycles=10):
+    """The fully periodic jump operator (numpy_jump_periodic, contrast 1e4, singular), true Jacobi omega 0.8
+    2+2, explicit masks x, y, (z,) x, ... (periodic_cyclic_masks), `singular`, all through the host
+    constructors.  Three legs alternate in one process, `reps` repeats: tensor_opdep (the wrap entries are
+    skipped; natural_sides on every side for `singular`), tensor_periodic (the fixed weights 1/2, 1, 1/2)
+    and tensor_opdep_periodic (the seam); a fourth solver is the new one with CSR transfers
+    (amg_hip_set_axis_stencil(0), kind 0).  Per leg: host set-up seconds apart from everything else, ms per
+    V-cycle, then amg_hip_pcg from x = 0 to `rtol`: iterations and wall ms."""
+    arrays = numpy_jump_periodic(dims)
+    dim = len(dims)
+    per, every = (1 << dim) - 1, (1 << (2 * dim)) - 1
+    masks = periodic_cyclic_masks(dims)
+    L = len(masks) + 1
+    jac = TENSOR_KW["jacobi"]
+    tag = " x ".join(str(d) for d in dims) + " periodic jump 1e4"
+
+    def seam_csr():
+        amg.set_axis_stencil(False)
+        try:
+            return amg.Multigrid.tensor_opdep_periodic(*arrays, dims, L, per, axis_masks=masks, singular=True, **jac)
+        finally:
+            amg.set_axis_stencil(True)
+    mk = {"opdep, wrap skipped": lambda: amg.Multigrid.tensor_opdep(*arrays, dims, L, axis_masks=masks,
+                                                                    natural_sides=every, singular=True, **jac),
+          "periodic, fixed weights": lambda: amg.Multigrid.tensor_periodic(*arrays, dims, L, per, axis_masks=masks,
+                                                                           singular=True, **jac),
+          "opdep with the seam": lambda: amg.Multigrid.tensor_opdep_periodic(*arrays, dims, L, per, axis_masks=masks,
+                                                                             singular=True, **jac),
+          "opdep with the seam, kind 0": seam_csr}
+    legs = {}
+    for name, make in mk.items():
+        t0 = time.perf_counter()
+        mg = make()
+        mg.sync()
+        dt = time.perf_counter() - t0
+        nl = mg.n_levels
+        kinds = sorted(set(mg.level_transfer_kind(l) for l in range(nl - 1)))
+        mg.vcycle(3)
+        mg.sync()
+        print(f"opdep-periodic {tag}, {name}: host set-up {dt:.2f} s (setup_on_device {mg.setup_on_device}), {nl} levels, "
+              f"transfer kinds {kinds}, coarsest {mg.get_n_dofs(nl - 1)} dofs ({mg.coarse_solve_kind().split(' ')[0]}), "
+              f"must-move {mg.cycle_must_move() / 1e6:.1f} MB per V-cycle", flush=True)
+        mg.zero_vec(0, "u")
+        mg.pcg(rtol=rtol, max_iters=max_iters)  # first call: work vectors, captured graphs
+        legs[name] = mg
+    cyc, pcg, iters = {k: [] for k in legs}, {k: [] for k in legs}, {}
+    for rep_ in range(reps):
+        for name, mg in legs.items():
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            mg.vcycle(cycles)
+            mg.sync()
+            dt = (time.perf_counter() - t0) / cycles
+            cyc[name].append(dt)
+            mg.zero_vec(0, "u")
+            mg.sync()
+            t0 = time.perf_counter()
+            _, it, rel = mg.pcg(rtol=rtol, max_iters=max_iters)
+            dp = time.perf_counter() - t0
+            pcg[name].append(dp)
+            iters[name] = it
+            print(f"opdep-periodic {tag}, {name} rep {rep_}: {dt * 1e3:.3f} ms/V-cycle; PCG {it} iterations, "
+                  f"{dp * 1e3:.2f} ms to {rtol:g} (relres {rel:.2e}, {'reached' if rel <= rtol else 'NOT reached: capped'})",
+                  flush=True)
+    print(f"opdep-periodic {tag}: ms/V-cycle best (worst of {reps}): " +
+          ", ".join(f"{k} {min(v) * 1e3:.3f} ({max(v) * 1e3:.3f})" for k, v in cyc.items()) +
+          "; PCG ms best: " + ", ".join(f"{k} {min(v) * 1e3:.2f} ({iters[k]} it)" for k, v in pcg.items()), flush=True)
     for mg in legs.values():
         mg.close()
 
@@ -1649,6 +1768,14 @@ elif len(sys.argv) > 1 and sys.argv[1] == "opdep":
     else:
         run_opdep((2048, 2048))
         run_opdep((128, 128, 128))
+elif len(sys.argv) > 1 and sys.argv[1] == "opdep-periodic":
+    # profiles/opdep_periodic_config_bench.txt
+    if len(sys.argv) > 4:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_opdep_periodic(d if d[2] > 1 else d[:2])
+    else:
+        run_opdep_periodic((2048, 2048))
+        run_opdep_periodic((128, 128, 128))
 elif len(sys.argv) > 1 and sys.argv[1] == "opdep-setup":
     # profiles/opdep_setup.txt
     os.environ.setdefault("AMG_HIP_TIMING", "1")
