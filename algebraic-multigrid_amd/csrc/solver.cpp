@@ -1171,24 +1171,23 @@ hipError_t line_solve_any(int, const LineRefT<float>& Y, const float* r, float* 
 }
 // A sub-sweep after its residual r = f - A u: K-LineSeam on r where the direction is cyclic (S), then
 // u += omega T^-1 r as K-LineX where the direction is the x axis (X), else as K-Line with Y and the
-// scratch y.  X and S are null where the direction has none.  dry: launch nothing.
+// scratch y.  X and S are null where the direction has none.
 template <typename T>
 hipError_t launch_line_dir(const LineRefT<T>& Y, const LineXRefT<T>* X, const SeamRefT<T>* S, int kp, T* r, T* y,
-                           T* u, T omega, bool dry, hipStream_t st) {
-  if (dry) return hipSuccess;
+                           T* u, T omega, hipStream_t st) {
   hipError_t e;
   if (S && (e = line_seam_any(kp, *S, r, st)) != hipSuccess) return e;
   return X ? linex_solve_any(kp, *X, r, u, omega, st) : line_solve_any(kp, Y, r, y, u, omega, st);
 }
 // launch_line_dir for direction d of D (AltOnDev::cyclic).  y: the scratch panel of the block cycle;
 // plain vectors (kp = 0) use the direction's own
-hipError_t launch_alt_dir(const AltOnDev& D, int d, int kp, double* r, double* y, double* u, double omega, bool dry,
+hipError_t launch_alt_dir(const AltOnDev& D, int d, int kp, double* r, double* y, double* u, double omega,
                           hipStream_t st) {
   const SeamRef S = D.seam(d);
   const LineXRef X = D.xref();
   const LineOnDev& Y = D.yz[D.yz_of(d)];
   return launch_line_dir(Y.ref(), D.along_x(d) ? &X : nullptr, D.cyclic(d) ? &S : nullptr, kp, r,
-                         kp ? y : Y.y.as<double>(), u, omega, dry, st);
+                         kp ? y : Y.y.as<double>(), u, omega, st);
 }
 // One smoothing application of a line smoother: `iters` times its nd sub-sweeps, the directions
 // ascending on the way down and descending on the way up (reverse).  sub(d) enqueues sub-sweep d.
@@ -1202,19 +1201,40 @@ amg_hip_status line_subsweeps(int64_t iters, int nd, bool reverse, F&& sub) {
 int line_dirs(int32_t smoother, const AltOnDev& D) {
   return smoother == AMG_HIP_SM_LINE_ALT ? std::max(D.n_dir, 1) : 1;
 }
+// `passes` sweeps that ping-pong u -> tmp -> u ...: sweep(i, in, out) enqueues the i-th; after an odd
+// count the result sits in tmp and copy_home() brings it to u (keeps a captured graph static)
+template <typename T, typename Sweep, typename Home>
+amg_hip_status ping_pong(int64_t passes, T* u, T* tmp, Sweep&& sweep, Home&& copy_home) {
+  for (int64_t i = 0; i < passes; ++i) {
+    AMG_TRY(sweep(i, u, tmp));
+    std::swap(u, tmp);
+  }
+  return (passes & 1) ? copy_home() : AMG_HIP_OK;
+}
+// The Chebyshev smoother: `iters` applications of the degree-k polynomial on [lo, hi], each k steps from
+// step 0, as one ping-pong.  step(alpha, beta, first, last, in, out) enqueues one step of an application.
+template <typename T, typename Step, typename Home>
+amg_hip_status cheb_steps(double lo, double hi, int iters, int k, T* u, T* tmp, Step&& step, Home&& copy_home) {
+  std::vector<double> alpha, beta;
+  cheb_coefs(lo, hi, k, &alpha, &beta);
+  return ping_pong((int64_t)iters * k, u, tmp, [&](int64_t i, T* a, T* b) {
+    const size_t j = (size_t)(i % k);
+    return step(alpha[j], beta[j], j == 0, (int)j == k - 1, a, b);
+  }, copy_home);
+}
 // sub-sweep of AMG_HIP_SM_LINE_JACOBI on plain vectors: u <- u + omega T^-1 (f - A u); r: n doubles of scratch
 hipError_t launch_line_sweep(const DevMat& A, const LineOnDev& D, double* u, const double* f, double* r,
                              double omega, hipStream_t st) {
   hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
   if (e != hipSuccess) return e;
-  return launch_line_dir<double>(D.ref(), nullptr, nullptr, 0, r, D.y.as<double>(), u, omega, false, st);
+  return launch_line_dir<double>(D.ref(), nullptr, nullptr, 0, r, D.y.as<double>(), u, omega, st);
 }
 // sub-sweep d of AMG_HIP_SM_LINE_ALT: u <- u + omega T_a^-1 (f - A u)
 hipError_t launch_alt_subsweep(const DevMat& A, const AltOnDev& D, int d, double* u, const double* f, double* r,
                                double omega, hipStream_t st) {
   hipError_t e = launch_mat(CSR_RESID, A, u, f, r, 1.0, st);
   if (e != hipSuccess) return e;
-  return launch_alt_dir(D, d, 0, r, nullptr, u, omega, false, st);
+  return launch_alt_dir(D, d, 0, r, nullptr, u, omega, st);
 }
 
 struct SpikeOnDev {  // device copy of a SpikeFactor + scratch
@@ -1367,29 +1387,34 @@ amg_hip_status upload_coarse(const Sparse& A_in, int want_fast, CoarseOnDev* C, 
 // x = A^-1 f; y: scratch of n doubles (BAND / WIDE)
 // uh_out (K-BandChain only): also uh_out = uh_in + P x, the prolongation into the level above
 // C.pin: f[n-1] is zeroed first (one more static node of a captured graph)
+// cols > 1 (the block cycle): column c's f / y / x at c * cstride; the one-wave kinds take every column in
+// one launch (one workgroup per column), K-Spike one launch per column
 hipError_t launch_coarse(const CoarseOnDev& C, double* f, double* y, double* x,
                          hipStream_t st, int64_t n_h = 0, const double* uh_in = nullptr,
-                         double* uh_out = nullptr) {
+                         double* uh_out = nullptr, int cols = 1, int64_t cstride = 0) {
   if (C.pin) {
-    const hipError_t e = launch_zero_strided(f + (C.n - 1), 0, 1, st);
+    const hipError_t e = launch_zero_strided(f + (C.n - 1), cstride, cols, st);
     if (e != hipSuccess) return e;
   }
   switch (C.kind) {
-    case COARSE_SPIKE: {
-      SpikeArgs a = C.spike->a;
-      a.f = f;
-      a.x = x;
-      return launch_spike_solve(a, st);
-    }
+    case COARSE_SPIKE:
+      for (int j = 0; j < cols; ++j) {
+        SpikeArgs a = C.spike->a;
+        a.f = f + (size_t)j * (size_t)cstride;
+        a.x = x + (size_t)j * (size_t)cstride;
+        const hipError_t e = launch_spike_solve(a, st);
+        if (e != hipSuccess) return e;
+      }
+      return hipSuccess;
     case COARSE_WIDE:
       return launch_band_wide(C.n, C.w, C.sf.as<double>(), C.sb.as<double>(), C.d.as<double>(), f,
-                              y, x, st);
+                              y, x, st, cols, cstride);
     case COARSE_CHAIN:
       return launch_band_chain(C.n, (int)C.w, C.sf.as<double>(), C.sb.as<double>(), C.d.as<double>(),
-                               f, x, st, n_h, uh_in, uh_out);
+                               f, x, st, n_h, uh_in, uh_out, cols, cstride);
     default:
       return launch_band_solve(C.n, C.m, C.sf.as<double>(), C.sb.as<double>(), C.d.as<double>(),
-                               f, y, x, st);
+                               f, y, x, st, cols, cstride);
   }
 }
 
@@ -1531,15 +1556,9 @@ struct Slab {
   int64_t lines = 0, chunk = 0, line0 = 0, line1 = 0;   // grid lines; lines per rank; owned [line0, line1)
   int halo = 0;                 // lines of level-0 u a neighbour supplies before each cycle
   std::vector<int64_t> down_lo, down_hi, up_lo, up_hi;  // lines each leg runs over, per level
-  hipGraph_t graph[3] = {nullptr, nullptr, nullptr};
-  hipGraphExec_t exec[3] = {nullptr, nullptr, nullptr};
+  CycleGraph graph[3];          // per part (CYCLE_SLAB_DOWN .. CYCLE_SLAB_UP)
   void reset_graphs() {
-    for (int i = 0; i < 3; ++i) {
-      if (exec[i]) (void)hipGraphExecDestroy(exec[i]);
-      if (graph[i]) (void)hipGraphDestroy(graph[i]);
-      exec[i] = nullptr;
-      graph[i] = nullptr;
-    }
+    for (CycleGraph& g : graph) g.reset();
   }
 };
 
@@ -1561,15 +1580,9 @@ struct Block {
   DevMem cf, cy, cx;               // coarsest level as kp contiguous columns: f, scratch, x
   DevMem px, pp, pq, pb;           // PCG panels (level-0 size)
   DevMem part, dots, act;          // 1024 x 16 partials; 6 x 16 device scalars; 16 column flags
-  hipGraph_t graph[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // per log2(kp)
-  hipGraphExec_t exec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  CycleGraph graph[5];             // per log2(kp)
   void reset_graphs() {
-    for (int i = 0; i < 5; ++i) {
-      if (exec[i]) (void)hipGraphExecDestroy(exec[i]);
-      if (graph[i]) (void)hipGraphDestroy(graph[i]);
-      exec[i] = nullptr;
-      graph[i] = nullptr;
-    }
+    for (CycleGraph& g : graph) g.reset();
   }
 };
 
@@ -1630,14 +1643,7 @@ struct F32 {
   std::vector<F32Level> lv;
   DevMem cf, cy, cx;             // coarsest system in double: f, scratch, x
   DevMem pr, pz;                 // amg_hip_pcg_mixed: r and z (doubles, level-0 size)
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  void reset_graph() {
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    exec = nullptr;
-    graph = nullptr;
-  }
+  CycleGraph graph;
 };
 
 // amg_hip_set_tail_fusion / AMG_HIP_TAIL_FUSION=1: K-Tail (deepest levels + coarsest solve in one
@@ -1750,9 +1756,7 @@ struct amg_hip_solver {
   DevMem scratch;   // 1024 doubles + 1 result
   DevMem pcg_x, pcg_p, pcg_q, pcg_b;  // PCG work vectors (allocated on first use)
   bool project_mean = false;  // amg_hip_set_mean_projection: the PCG drivers project onto the complement of the constants
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t graph_exec = nullptr;
-  bool graph_ready = false;
+  CycleGraph graph;  // the whole cycle
   double cycle_bytes = 0, fine_sweep_bytes = 0;
   // bytes the launches of one V-cycle HAVE TO move (what each kernel reads and writes once in the
   // layout it really streams), summed while the cycle is enqueued; [part] as enqueue_vcycle's
@@ -1764,40 +1768,18 @@ struct amg_hip_solver {
   // level-0 buffer it hands over in (0: tmp, 1: r), and the captured pieces -- head and seam cycle
   // per buffer, the finish
   int seam_piece = 0, seam_src = 0;
-  hipGraph_t seam_graph[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipGraphExec_t seam_exec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  void reset_seam_graphs() {
-    for (int i = 0; i < 5; ++i) {
-      if (seam_exec[i]) (void)hipGraphExecDestroy(seam_exec[i]);
-      if (seam_graph[i]) (void)hipGraphDestroy(seam_graph[i]);
-      seam_exec[i] = nullptr;
-      seam_graph[i] = nullptr;
-    }
-  }
+  CycleGraph seam_graph[5];
   Slab slab;
   Block blk;
-  // block cycle bytes, counted while it is enqueued: matrix bytes (once per launch) and bytes per
-  // row-column pair; one block cycle on k columns has to move block_mm[0] + k * block_mm[1]
-  bool block_acct = false;
-  double block_mm[2] = {0, 0};
-  void bacct(double mat, double per_col) {
-    if (!block_acct) return;
-    block_mm[0] += mat;
-    block_mm[1] += per_col;
-  }
   F32 f32;
-  // bytes of one single-precision application, counted by the dry enqueue (amg_hip_f32_must_move)
-  bool f32_acct = false;
-  double f32_mm = 0;
-  void facct(double bytes) { if (f32_acct) f32_mm += bytes; }
 
+  // every captured graph goes before the stream it was captured on (members die after this body)
   ~amg_hip_solver() {
-    f32.reset_graph();
+    f32.graph.reset();
     blk.reset_graphs();
     slab.reset_graphs();
-    reset_seam_graphs();
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    if (graph) (void)hipGraphDestroy(graph);
+    for (CycleGraph& g : seam_graph) g.reset();
+    graph.reset();
     if (stream && own_stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -2195,32 +2177,20 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
       // iters applications of the degree-k polynomial, each k steps from step 0 (phases 1 / 2 have
       // no shortcut here: u is read as it is).  The level vector ping-pongs u -> tmp -> u ...
       const DevMat& A = L.A_rows;
-      const int k = s->opt.cheb_degree;
-      std::vector<double> alpha, beta;
-      cheb_coefs(L.cheb_lo, L.cheb_hi, k, &alpha, &beta);
-      double* a = L.u.as<double>();
-      double* b = L.tmp.as<double>();
-      int64_t passes = 0;
-      for (int it = 0; it < iters; ++it) {
-        for (int j = 0; j < k; ++j) {
-          ChebStep c;
-          c.d = L.cheb_d.as<double>();
-          c.alpha = alpha[(size_t)j];
-          c.beta = beta[(size_t)j];
-          c.first = j == 0;
-          c.last = j == k - 1;
-          HIP_TRY(launch_mat_cheb(A, a, L.f.as<double>(), b, c, st));
-          // matrix, f, x, out; d written (not on the last step) and read (not on the first)
-          s->acct(mat_bytes(A) + 24.0 * L.n + (c.first ? 0.0 : 8.0 * L.n) + (c.last ? 0.0 : 8.0 * L.n));
-          std::swap(a, b);
-          ++passes;
-        }
-      }
-      if (passes & 1) {  // result sits in tmp: bring it home (keeps the graph static)
-        HIP_TRY(hipMemcpyAsync(L.u.p, L.tmp.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, st));
-        s->acct(16.0 * L.n);
-      }
-      return AMG_HIP_OK;
+      return cheb_steps(
+          L.cheb_lo, L.cheb_hi, iters, s->opt.cheb_degree, L.u.as<double>(), L.tmp.as<double>(),
+          [&](double alpha, double beta, bool first, bool last, double* a, double* b) {
+            const ChebStep c{L.cheb_d.as<double>(), alpha, beta, first, last};
+            HIP_TRY(launch_mat_cheb(A, a, L.f.as<double>(), b, c, st));
+            // matrix, f, x, out; d written (not on the last step) and read (not on the first)
+            s->acct(mat_bytes(A) + 24.0 * L.n + (first ? 0.0 : 8.0 * L.n) + (last ? 0.0 : 8.0 * L.n));
+            return AMG_HIP_OK;
+          },
+          [&] {
+            HIP_TRY(hipMemcpyAsync(L.u.p, L.tmp.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, st));
+            s->acct(16.0 * L.n);
+            return AMG_HIP_OK;
+          });
     }
     case AMG_HIP_SM_LINE_JACOBI:
     case AMG_HIP_SM_LINE_ALT: {
@@ -2904,13 +2874,6 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
   return AMG_HIP_OK;
 }
 
-amg_hip_status ensure_graph(amg_hip_solver* s) {
-  if (s->graph_ready) return AMG_HIP_OK;
-  AMG_TRY(capture_once(s->stream, [s] { return enqueue_vcycle(s); }, &s->graph, &s->graph_exec));
-  s->graph_ready = true;
-  return AMG_HIP_OK;
-}
-
 // One piece of the seam sequence (SEAM_HEAD / SEAM_CYCLE with the buffer src it hands over in, or
 // SEAM_FINISH), enqueued or replayed from its graph, captured on first use.  The piece is a mode of
 // enqueue_vcycle for the length of this call only: no vector changes its role, so a failure anywhere
@@ -2924,11 +2887,8 @@ amg_hip_status run_seam_piece(amg_hip_solver* s, int piece, int src) {
     s->seam_src = 0;
     return r;
   };
-  if (!s->opt.use_graph) return enqueue();
   const int gi = piece == SEAM_FINISH ? 4 : (piece == SEAM_HEAD ? 0 : 2) + src;
-  if (!s->seam_exec[gi]) AMG_TRY(capture_once(s->stream, enqueue, &s->seam_graph[gi], &s->seam_exec[gi]));
-  HIP_TRY(hipGraphLaunch(s->seam_exec[gi], s->stream));
-  return AMG_HIP_OK;
+  return replay_or_enqueue(s->opt.use_graph, s->seam_graph[gi], s->stream, enqueue);
 }
 
 amg_hip_status set_device(const amg_hip_solver* s) {
@@ -4425,199 +4385,193 @@ amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
   return AMG_HIP_OK;
 }
 
-// dry: count the bytes, launch nothing (amg_hip_block_must_move)
-#define BLK(expr)                 \
-  do {                            \
-    if (!dry) HIP_TRY(expr);      \
+// What a step of the block or the float cycle enqueues on, and the bytes its launches have to move.
+// launch = false is the dry run of amg_hip_block_must_move / amg_hip_f32_must_move: count, launch nothing.
+struct StepCtx {
+  hipStream_t st = nullptr;
+  bool launch = true;
+  double once = 0;     // bytes moved once per launch (the float cycle counts all of its bytes here)
+  double per_col = 0;  // bytes per column of a block panel: k columns have to move once + k * per_col
+  void count(double o, double c = 0.0) {
+    once += o;
+    per_col += c;
+  }
+};
+#define STEP_TRY(X, expr)            \
+  do {                               \
+    if ((X).launch) HIP_TRY(expr);   \
   } while (0)
 
-// K-Line on the panels (LineOnDev::solve_bytes with the factors counted once: dl, ip, cp, v, w of every
-// row; per column 40 B on an interior and 56 B on a separator row)
-void bacct_line(amg_hip_solver* s, const LineOnDev& D) {
-  const int64_t sep = D.separators();
-  s->bacct(40.0 * (double)D.n, 40.0 * (double)(D.n - sep) + 56.0 * (double)sep);
-}
-// the bytes of sub-sweep d of AMG_HIP_SM_LINE_ALT on the panels, after its residual
-void bacct_alt(amg_hip_solver* s, const AltOnDev& D, int d) {
-  if (D.cyclic(d)) {
-    // p, then den, gamma, beta of every line once; r in and the two ends of r out per column
-    const double lines = (double)(D.n / D.len[d]);
-    s->bacct(8.0 * (double)D.n + 24.0 * lines, 8.0 * (double)D.n + 16.0 * lines);
+// multigrid.hpp:263-305 as one plain launch per step on a single stream (enqueue_vcycle_body's order:
+// down-legs, coarsest solve, up-legs).  S: the steps of the block or of the float cycle.
+template <typename Steps>
+amg_hip_status walk_vcycle(int nl, Steps&& S) {
+  for (int l = 0; l + 1 < nl; ++l) {
+    AMG_TRY(S.smooth(l, false));  // :268
+    AMG_TRY(S.residual(l));       // :272-274
+    AMG_TRY(S.restriction(l));       // :278 + :281-282
   }
-  if (D.along_x(d)) s->bacct(24.0 * (double)D.n, 40.0 * (double)D.n);  // dl, ip, cp; r, y, y, u, u
-  else bacct_line(s, D.yz[D.yz_of(d)]);
-}
-
-// the smoothing of one level (enqueue_smooth's plain launches): U -> T -> U ..., home after an odd count;
-// the line smoothers update U in place (reverse: the up-leg, AMG_HIP_SM_LINE_ALT's directions descend)
-amg_hip_status enqueue_block_smooth(amg_hip_solver* s, int l, int kp, bool dry, bool reverse) {
-  Level& L = s->lv[l];
-  BlockLevel& Q = s->blk.lv[(size_t)l];
-  hipStream_t st = s->stream;
-  const double n = (double)L.n;
-  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
-    const DevCsr& A = *Q.rows;
-    const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
-    // a sub-sweep: T = F - A U, then the line solve updates U in place (Y: K-Line's scratch panel)
-    return line_subsweeps(s->opt.smoother_iters, line_dirs(s->opt.smoother, L.alt), reverse, [&](int d) {
-      BLK(launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
-                           Q.T.as<double>(), 1.0, st));
-      s->bacct(csr_bytes(A), 24.0 * n);  // matrix; u, f, r
-      HIP_TRY(alt ? launch_alt_dir(L.alt, d, kp, Q.T.as<double>(), Q.Y.as<double>(), Q.U.as<double>(), s->opt.omega,
-                                   dry, st)
-                  : launch_line_dir<double>(L.line.ref(), nullptr, nullptr, kp, Q.T.as<double>(), Q.Y.as<double>(),
-                                            Q.U.as<double>(), s->opt.omega, dry, st));
-      if (alt) bacct_alt(s, L.alt, d);
-      else bacct_line(s, L.line);
-      return AMG_HIP_OK;
-    });
-  }
-  double* a = Q.U.as<double>();
-  double* b = Q.T.as<double>();
-  int64_t passes = 0;
-  if (s->opt.smoother == AMG_HIP_SM_JACOBI) {
-    const DevCsr& A = *Q.cols;
-    for (int it = 0; it < s->opt.smoother_iters; ++it) {
-      BLK(launch_block_csr(CSR_JACOBI, kp, L.n, A.rowptr(), A.col(), A.v(), a, Q.F.as<double>(), b, s->opt.omega,
-                           st));
-      s->bacct(csr_bytes(A), 24.0 * n);  // matrix; x, f, out
-      std::swap(a, b);
-      ++passes;
-    }
-  } else {
-    const DevCsr& A = *Q.rows;
-    const int k = s->opt.cheb_degree;
-    std::vector<double> alpha, beta;
-    cheb_coefs(L.cheb_lo, L.cheb_hi, k, &alpha, &beta);
-    for (int it = 0; it < s->opt.smoother_iters; ++it) {
-      for (int j = 0; j < k; ++j) {
-        ChebStep c;
-        c.d = Q.D.as<double>();
-        c.alpha = alpha[(size_t)j];
-        c.beta = beta[(size_t)j];
-        c.first = j == 0;
-        c.last = j == k - 1;
-        BLK(launch_block_csr_cheb(kp, L.n, A.rowptr(), A.col(), A.v(), a, Q.F.as<double>(), b, c, st));
-        s->bacct(csr_bytes(A), 24.0 * n + (c.first ? 0.0 : 8.0 * n) + (c.last ? 0.0 : 8.0 * n));
-        std::swap(a, b);
-        ++passes;
-      }
-    }
-  }
-  if (passes & 1) {
-    BLK(hipMemcpyAsync(Q.U.p, Q.T.p, sizeof(double) * (size_t)L.n * (size_t)kp, hipMemcpyDeviceToDevice, st));
-    s->bacct(0.0, 16.0 * n);
+  AMG_TRY(S.coarse());            // :287-288
+  for (int l = nl - 2; l >= 0; --l) {  // :291
+    AMG_TRY(S.prolong(l));        // :294-296
+    AMG_TRY(S.smooth(l, true));   // :300
   }
   return AMG_HIP_OK;
 }
 
-// multigrid.hpp:263-305 on the block panels (enqueue_vcycle_body's order: down-legs, coarsest
-// solve, up-legs), one plain launch per step, a single stream
-amg_hip_status enqueue_block_vcycle(amg_hip_solver* s, int kp, bool dry) {
-  const int nl = (int)s->lv.size();
-  hipStream_t st = s->stream;
-  Block& B = s->blk;
-  amg_hip_status r;
-  for (int l = 0; l + 1 < nl; ++l) {
+// The steps of the block cycle on the panels of pitch kp.
+struct BlockSteps {
+  amg_hip_solver* s;
+  int kp;
+  StepCtx& X;
+
+  // K-Line on the panels (LineOnDev::solve_bytes with the factors counted once: dl, ip, cp, v, w of every
+  // row; per column 40 B on an interior and 56 B on a separator row)
+  void count_line(const LineOnDev& D) {
+    const int64_t sep = D.separators();
+    X.count(40.0 * (double)D.n, 40.0 * (double)(D.n - sep) + 56.0 * (double)sep);
+  }
+  // the bytes of sub-sweep d of AMG_HIP_SM_LINE_ALT on the panels, after its residual
+  void count_alt(const AltOnDev& D, int d) {
+    if (D.cyclic(d)) {
+      // p, then den, gamma, beta of every line once; r in and the two ends of r out per column
+      const double lines = (double)(D.n / D.len[d]);
+      X.count(8.0 * (double)D.n + 24.0 * lines, 8.0 * (double)D.n + 16.0 * lines);
+    }
+    if (D.along_x(d)) X.count(24.0 * (double)D.n, 40.0 * (double)D.n);  // dl, ip, cp; r, y, y, u, u
+    else count_line(D.yz[D.yz_of(d)]);
+  }
+
+  // the smoothing of one level (enqueue_smooth's plain launches): U -> T -> U ..., home after an odd count;
+  // the line smoothers update U in place (reverse: the up-leg, AMG_HIP_SM_LINE_ALT's directions descend)
+  amg_hip_status smooth(int l, bool reverse) {
+    Level& L = s->lv[l];
+    BlockLevel& Q = s->blk.lv[(size_t)l];
+    const double n = (double)L.n;
+    double* F = Q.F.as<double>();
+    if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
+      const DevCsr& A = *Q.rows;
+      const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
+      // a sub-sweep: T = F - A U, then the line solve updates U in place (Y: K-Line's scratch panel)
+      return line_subsweeps(s->opt.smoother_iters, line_dirs(s->opt.smoother, L.alt), reverse, [&](int d) {
+        STEP_TRY(X, launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), F,
+                                     Q.T.as<double>(), 1.0, X.st));
+        X.count(csr_bytes(A), 24.0 * n);  // matrix; u, f, r
+        STEP_TRY(X, alt ? launch_alt_dir(L.alt, d, kp, Q.T.as<double>(), Q.Y.as<double>(), Q.U.as<double>(),
+                                         s->opt.omega, X.st)
+                        : launch_line_dir<double>(L.line.ref(), nullptr, nullptr, kp, Q.T.as<double>(),
+                                                  Q.Y.as<double>(), Q.U.as<double>(), s->opt.omega, X.st));
+        if (alt) count_alt(L.alt, d);
+        else count_line(L.line);
+        return AMG_HIP_OK;
+      });
+    }
+    auto copy_home = [&] {
+      STEP_TRY(X, hipMemcpyAsync(Q.U.p, Q.T.p, sizeof(double) * (size_t)L.n * (size_t)kp, hipMemcpyDeviceToDevice,
+                                 X.st));
+      X.count(0.0, 16.0 * n);
+      return AMG_HIP_OK;
+    };
+    if (s->opt.smoother == AMG_HIP_SM_JACOBI) {
+      const DevCsr& A = *Q.cols;
+      return ping_pong(s->opt.smoother_iters, Q.U.as<double>(), Q.T.as<double>(), [&](int64_t, double* a, double* b) {
+        STEP_TRY(X, launch_block_csr(CSR_JACOBI, kp, L.n, A.rowptr(), A.col(), A.v(), a, F, b, s->opt.omega, X.st));
+        X.count(csr_bytes(A), 24.0 * n);  // matrix; x, f, out
+        return AMG_HIP_OK;
+      }, copy_home);
+    }
+    const DevCsr& A = *Q.rows;
+    return cheb_steps(L.cheb_lo, L.cheb_hi, s->opt.smoother_iters, s->opt.cheb_degree, Q.U.as<double>(),
+                      Q.T.as<double>(), [&](double alpha, double beta, bool first, bool last, double* a, double* b) {
+      const ChebStep c{Q.D.as<double>(), alpha, beta, first, last};
+      STEP_TRY(X, launch_block_csr_cheb(kp, L.n, A.rowptr(), A.col(), A.v(), a, F, b, c, X.st));
+      X.count(csr_bytes(A), 24.0 * n + (first ? 0.0 : 8.0 * n) + (last ? 0.0 : 8.0 * n));
+      return AMG_HIP_OK;
+    }, copy_home);
+  }
+
+  // R_l = F_l - A_l U_l
+  amg_hip_status residual(int l) {
+    Level& L = s->lv[l];
+    BlockLevel& Q = s->blk.lv[(size_t)l];
+    const DevCsr& A = *Q.rows;
+    STEP_TRY(X, launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
+                                 Q.R.as<double>(), 1.0, X.st));
+    X.count(csr_bytes(A), 24.0 * (double)L.n);
+    return AMG_HIP_OK;
+  }
+
+  // U_{l+1} = 0, F_{l+1} = R_l R_l
+  amg_hip_status restriction(int l) {
     Level& L = s->lv[l];
     Level& C = s->lv[l + 1];
-    BlockLevel& Q = B.lv[(size_t)l];
-    BlockLevel& QC = B.lv[(size_t)l + 1];
-    if ((r = enqueue_block_smooth(s, l, kp, dry, false)) != AMG_HIP_OK) return r;  // :268
-    const DevCsr& A = *Q.rows;                                               // :272-274
-    BLK(launch_block_csr(CSR_RESID, kp, L.n, A.rowptr(), A.col(), A.v(), Q.U.as<double>(), Q.F.as<double>(),
-                         Q.R.as<double>(), 1.0, st));
-    s->bacct(csr_bytes(A), 24.0 * (double)L.n);
-    if (L.linear && s->opt.stencil_transfers) {                              // :278 + :281-282
-      BLK(launch_block_restrict(kp, L.n, C.n, Q.R.as<double>(), QC.F.as<double>(), QC.U.as<double>(), st));
-      s->bacct(0.0, 8.0 * (double)L.n + 16.0 * (double)C.n);
+    BlockLevel& Q = s->blk.lv[(size_t)l];
+    BlockLevel& QC = s->blk.lv[(size_t)l + 1];
+    if (L.linear && s->opt.stencil_transfers) {
+      STEP_TRY(X, launch_block_restrict(kp, L.n, C.n, Q.R.as<double>(), QC.F.as<double>(), QC.U.as<double>(), X.st));
+      X.count(0.0, 8.0 * (double)L.n + 16.0 * (double)C.n);
     } else {
-      BLK(hipMemsetAsync(QC.U.p, 0, sizeof(double) * (size_t)C.n * (size_t)kp, st));
+      STEP_TRY(X, hipMemsetAsync(QC.U.p, 0, sizeof(double) * (size_t)C.n * (size_t)kp, X.st));
       const DevCsr& R = L.R_rows;
-      BLK(launch_block_csr(CSR_SPMV, kp, R.n_rows, R.rowptr(), R.col(), R.v(), Q.R.as<double>(), nullptr,
-                           QC.F.as<double>(), 1.0, st));
-      s->bacct(csr_bytes(R), 8.0 * (double)L.n + 16.0 * (double)C.n);
+      STEP_TRY(X, launch_block_csr(CSR_SPMV, kp, R.n_rows, R.rowptr(), R.col(), R.v(), Q.R.as<double>(), nullptr,
+                                   QC.F.as<double>(), 1.0, X.st));
+      X.count(csr_bytes(R), 8.0 * (double)L.n + 16.0 * (double)C.n);
     }
+    return AMG_HIP_OK;
   }
-  {  // :287-288, every column in one launch of the one-wave kinds (one workgroup per column)
-    Level& C = s->lv[(size_t)nl - 1];
-    BlockLevel& QC = B.lv[(size_t)nl - 1];
+
+  // the coarsest system on kp contiguous columns: the one-wave kinds solve every column in one launch
+  amg_hip_status coarse() {
+    Block& B = s->blk;
+    Level& C = s->lv.back();
+    BlockLevel& QC = B.lv.back();
     const CoarseOnDev& K = s->coarse;
-    double* cf = B.cf.as<double>();
-    double* cy = B.cy.as<double>();
-    double* cx = B.cx.as<double>();
-    BLK(launch_block_columns(kp, C.n, QC.F.as<double>(), cf, true, st));
-    if (K.pin)  // opt.singular: the last entry of every column's right-hand side (launch_coarse)
-      BLK(launch_zero_strided(cf + (C.n - 1), C.n, kp, st));
+    STEP_TRY(X, launch_block_columns(kp, C.n, QC.F.as<double>(), B.cf.as<double>(), true, X.st));
+    STEP_TRY(X, launch_coarse(K, B.cf.as<double>(), B.cy.as<double>(), B.cx.as<double>(), X.st, 0, nullptr, nullptr,
+                              kp, C.n));
     const double factor = 16.0 * (double)C.n * (double)std::max<int64_t>(K.w, 1);
-    switch (K.kind) {
-      case COARSE_SPIKE:
-        for (int j = 0; j < kp; ++j) {
-          SpikeArgs a = K.spike->a;
-          a.f = cf + (size_t)j * (size_t)C.n;
-          a.x = cx + (size_t)j * (size_t)C.n;
-          BLK(launch_spike_solve(a, st));
-        }
-        s->bacct(0.0, factor);
-        break;
-      case COARSE_WIDE:
-        BLK(launch_band_wide(K.n, K.w, K.sf.as<double>(), K.sb.as<double>(), K.d.as<double>(), cf, cy, cx, st, kp,
-                             C.n));
-        s->bacct(factor, 0.0);
-        break;
-      case COARSE_CHAIN:
-        BLK(launch_band_chain(K.n, (int)K.w, K.sf.as<double>(), K.sb.as<double>(), K.d.as<double>(), cf, cx, st, 0,
-                              nullptr, nullptr, kp, C.n));
-        s->bacct(factor, 0.0);
-        break;
-      default:
-        BLK(launch_band_solve(K.n, K.m, K.sf.as<double>(), K.sb.as<double>(), K.d.as<double>(), cf, cy, cx, st, kp,
-                              C.n));
-        s->bacct(factor, 0.0);
-        break;
-    }
-    BLK(launch_block_columns(kp, C.n, cx, QC.U.as<double>(), false, st));
+    if (K.kind == COARSE_SPIKE) X.count(0.0, factor);  // one launch per column
+    else X.count(factor, 0.0);
+    STEP_TRY(X, launch_block_columns(kp, C.n, B.cx.as<double>(), QC.U.as<double>(), false, X.st));
     // f and u of the solve; the two reorderings read and write each once
-    s->bacct(0.0, 24.0 * (double)C.n + 32.0 * (double)C.n);
+    X.count(0.0, 24.0 * (double)C.n + 32.0 * (double)C.n);
+    return AMG_HIP_OK;
   }
-  for (int l = nl - 2; l >= 0; --l) {                                        // :291
+
+  // U_l = U_l + P_l U_{l+1}
+  amg_hip_status prolong(int l) {
     Level& L = s->lv[l];
     Level& C = s->lv[l + 1];
-    BlockLevel& Q = B.lv[(size_t)l];
-    BlockLevel& QC = B.lv[(size_t)l + 1];
-    if (L.linear && s->opt.stencil_transfers) {                              // :294-296
-      BLK(launch_block_prolong_add(kp, L.n, C.n, QC.U.as<double>(), Q.U.as<double>(), st));
-      s->bacct(0.0, 8.0 * (double)C.n + 16.0 * (double)L.n);
+    BlockLevel& Q = s->blk.lv[(size_t)l];
+    BlockLevel& QC = s->blk.lv[(size_t)l + 1];
+    if (L.linear && s->opt.stencil_transfers) {
+      STEP_TRY(X, launch_block_prolong_add(kp, L.n, C.n, QC.U.as<double>(), Q.U.as<double>(), X.st));
+      X.count(0.0, 8.0 * (double)C.n + 16.0 * (double)L.n);
     } else {
       const DevCsr& P = L.P_rows;
-      BLK(launch_block_csr(CSR_SPMV_ADD, kp, P.n_rows, P.rowptr(), P.col(), P.v(), QC.U.as<double>(),
-                           Q.U.as<double>(), Q.U.as<double>(), 1.0, st));
-      s->bacct(csr_bytes(P), 8.0 * (double)C.n + 16.0 * (double)L.n);
+      STEP_TRY(X, launch_block_csr(CSR_SPMV_ADD, kp, P.n_rows, P.rowptr(), P.col(), P.v(), QC.U.as<double>(),
+                                   Q.U.as<double>(), Q.U.as<double>(), 1.0, X.st));
+      X.count(csr_bytes(P), 8.0 * (double)C.n + 16.0 * (double)L.n);
     }
-    if ((r = enqueue_block_smooth(s, l, kp, dry, true)) != AMG_HIP_OK) return r;  // :300
+    return AMG_HIP_OK;
   }
-  return AMG_HIP_OK;
+};
+
+// one block cycle on the panels of pitch kp
+amg_hip_status enqueue_block_vcycle(amg_hip_solver* s, int kp, StepCtx& X) {
+  return walk_vcycle((int)s->lv.size(), BlockSteps{s, kp, X});
 }
-#undef BLK
 
 int log2i(int kp) { return __builtin_ctz((unsigned)kp); }
 
 // n block cycles on the panels of level 0 (their pitch is kp): the captured graph of this kp, or
 // the same enqueue eagerly (use_graph = 0)
 amg_hip_status run_block_cycles(amg_hip_solver* s, int kp, int32_t n) {
-  Block& B = s->blk;
-  if (!s->opt.use_graph) {
-    for (int i = 0; i < n; ++i) {
-      amg_hip_status r = enqueue_block_vcycle(s, kp, false);
-      if (r != AMG_HIP_OK) return r;
-    }
-    return AMG_HIP_OK;
-  }
-  const int g = log2i(kp);
-  if (!B.exec[g])
-    AMG_TRY(capture_once(s->stream, [s, kp] { return enqueue_block_vcycle(s, kp, false); }, &B.graph[g], &B.exec[g]));
-  for (int i = 0; i < n; ++i) HIP_TRY(hipGraphLaunch(B.exec[g], s->stream));
-  return AMG_HIP_OK;
+  return replay_or_enqueue(s->opt.use_graph, s->blk.graph[log2i(kp)], s->stream,
+                           [s, kp] {
+                             StepCtx X{s->stream};
+                             return enqueue_block_vcycle(s, kp, X);
+                           }, n);
 }
 
 // out[j] (host, j < kp) = sum_i x[i, j] (y null) or x[i, j] y[i, j] over level 0's rows
@@ -4784,177 +4738,151 @@ double mat_bytes_f32(const F32Mat& M) {
   return 8.0 * (double)A.csr.nnz + 4.0 * (double)(A.csr.n_rows + 1);
 }
 
-// dry: count the bytes, launch nothing (amg_hip_f32_must_move)
-#define F32_DO(expr)              \
-  do {                            \
-    if (!dry) HIP_TRY(expr);      \
-  } while (0)
+// The steps of the float cycle, one member each: enqueue_f32_vcycle strings them together, and
+// amg_hip_f32_level_op (a test hook) runs one of them alone -- the same launches either way.
+struct F32Steps {
+  amg_hip_solver* s;
+  StepCtx& X;
 
-// One sub-sweep of a line smoother in float (launch_line_sweep / launch_alt_subsweep on the float
-// copies): r = f - A u, K-LineSeam on r where direction d is cyclic, u += omega T^-1 r.  LINE_JACOBI:
-// d = 0.  Bytes: the matrix pass; then half of the double solve's (LineOnDev::solve_bytes,
-// AltOnDev::solve_bytes).
-amg_hip_status enqueue_f32_line_subsweep(amg_hip_solver* s, int l, int d, bool dry) {
-  const Level& L = s->lv[l];
-  F32Level& Q = s->f32.lv[(size_t)l];
-  hipStream_t st = s->stream;
-  float* u = Q.u.as<float>();
-  float* r = Q.r.as<float>();
-  const float omega = (float)s->opt.omega;
-  F32_DO(launch_mat_f32(CSR_RESID, Q.rows, u, Q.f.as<float>(), r, 1.0f, nullptr, 0.0f, st));
-  s->facct(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);  // matrix; u, f in and r out
-  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI) {
-    HIP_TRY(launch_line_dir<float>(Q.line.ref(L.line), nullptr, nullptr, 0, r, Q.line.y.as<float>(), u, omega, dry,
-                                   st));
-    s->facct(0.5 * L.line.solve_bytes());
+  // One sub-sweep of a line smoother in float (launch_line_sweep / launch_alt_subsweep on the float
+  // copies): r = f - A u, K-LineSeam on r where direction d is cyclic, u += omega T^-1 r.  LINE_JACOBI:
+  // d = 0.  Bytes: the matrix pass; then half of the double solve's (LineOnDev::solve_bytes,
+  // AltOnDev::solve_bytes).
+  amg_hip_status line_subsweep(int l, int d) {
+    const Level& L = s->lv[l];
+    F32Level& Q = s->f32.lv[(size_t)l];
+    float* u = Q.u.as<float>();
+    float* r = Q.r.as<float>();
+    const float omega = (float)s->opt.omega;
+    STEP_TRY(X, launch_mat_f32(CSR_RESID, Q.rows, u, Q.f.as<float>(), r, 1.0f, nullptr, 0.0f, X.st));
+    X.count(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);  // matrix; u, f in and r out
+    if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI) {
+      STEP_TRY(X, launch_line_dir<float>(Q.line.ref(L.line), nullptr, nullptr, 0, r, Q.line.y.as<float>(), u, omega,
+                                         X.st));
+      X.count(0.5 * L.line.solve_bytes());
+      return AMG_HIP_OK;
+    }
+    const AltOnDev& D = L.alt;
+    const SeamRefT<float> S = Q.seam(D, d);
+    const LineXRefT<float> LX = Q.xref(D);
+    const int k = D.yz_of(d);
+    STEP_TRY(X, launch_line_dir(Q.yz[k].ref(D.yz[k]), D.along_x(d) ? &LX : nullptr, D.cyclic(d) ? &S : nullptr, 0, r,
+                                Q.yz[k].y.as<float>(), u, omega, X.st));
+    X.count(0.5 * D.solve_bytes(d));
     return AMG_HIP_OK;
   }
-  const AltOnDev& D = L.alt;
-  const SeamRefT<float> S = Q.seam(D, d);
-  const LineXRefT<float> X = Q.xref(D);
-  const int k = D.yz_of(d);
-  HIP_TRY(launch_line_dir(Q.yz[k].ref(D.yz[k]), D.along_x(d) ? &X : nullptr, D.cyclic(d) ? &S : nullptr, 0, r,
-                          Q.yz[k].y.as<float>(), u, omega, dry, st));
-  s->facct(0.5 * D.solve_bytes(d));
-  return AMG_HIP_OK;
-}
 
-// reverse: the way up (AMG_HIP_SM_LINE_ALT runs its directions descending there)
-amg_hip_status enqueue_f32_smooth(amg_hip_solver* s, int l, bool dry, bool reverse = false) {
-  const Level& L = s->lv[l];
-  F32Level& Q = s->f32.lv[(size_t)l];
-  hipStream_t st = s->stream;
-  const double n = (double)L.n;
-  float* a = Q.u.as<float>();
-  float* b = Q.tmp.as<float>();
-  int64_t passes = 0;
-  if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
-    // enqueue_smooth's order: u is updated in place, so nothing has to come home
-    return line_subsweeps(s->opt.smoother_iters, line_dirs(s->opt.smoother, L.alt), reverse,
-                          [&](int d) { return enqueue_f32_line_subsweep(s, l, d, dry); });
-  }
-  if (s->opt.smoother == AMG_HIP_SM_JACOBI) {
-    for (int it = 0; it < s->opt.smoother_iters; ++it) {
-      F32_DO(launch_mat_f32(CSR_JACOBI, *Q.cols, a, Q.f.as<float>(), b, (float)s->opt.omega, nullptr, 0.0f, st));
-      s->facct(mat_bytes_f32(*Q.cols) + 12.0 * n);  // matrix; x, f, out
-      std::swap(a, b);
-      ++passes;
+  // reverse: the way up (AMG_HIP_SM_LINE_ALT runs its directions descending there)
+  amg_hip_status smooth(int l, bool reverse) {
+    const Level& L = s->lv[l];
+    F32Level& Q = s->f32.lv[(size_t)l];
+    const double n = (double)L.n;
+    const float* f = Q.f.as<float>();
+    if (s->opt.smoother == AMG_HIP_SM_LINE_JACOBI || s->opt.smoother == AMG_HIP_SM_LINE_ALT) {
+      // enqueue_smooth's order: u is updated in place, so nothing has to come home
+      return line_subsweeps(s->opt.smoother_iters, line_dirs(s->opt.smoother, L.alt), reverse,
+                            [&](int d) { return line_subsweep(l, d); });
     }
-  } else {
-    const int k = s->opt.cheb_degree;
-    std::vector<double> alpha, beta;
-    cheb_coefs(L.cheb_lo, L.cheb_hi, k, &alpha, &beta);  // in double, rounded at the launch
-    for (int it = 0; it < s->opt.smoother_iters; ++it) {
-      for (int j = 0; j < k; ++j) {
-        const bool first = j == 0, last = j == k - 1;
-        F32_DO(launch_mat_f32(cheb_kernel_mode(first, last), Q.rows, a, Q.f.as<float>(), b, (float)beta[(size_t)j],
-                              Q.d.as<float>(), (float)alpha[(size_t)j], st));
-        s->facct(mat_bytes_f32(Q.rows) + 12.0 * n + (first ? 0.0 : 4.0 * n) + (last ? 0.0 : 4.0 * n));
-        std::swap(a, b);
-        ++passes;
-      }
+    auto copy_home = [&] {
+      STEP_TRY(X, hipMemcpyAsync(Q.u.p, Q.tmp.p, sizeof(float) * (size_t)L.n, hipMemcpyDeviceToDevice, X.st));
+      X.count(8.0 * n);
+      return AMG_HIP_OK;
+    };
+    if (s->opt.smoother == AMG_HIP_SM_JACOBI) {
+      return ping_pong(s->opt.smoother_iters, Q.u.as<float>(), Q.tmp.as<float>(), [&](int64_t, float* a, float* b) {
+        STEP_TRY(X, launch_mat_f32(CSR_JACOBI, *Q.cols, a, f, b, (float)s->opt.omega, nullptr, 0.0f, X.st));
+        X.count(mat_bytes_f32(*Q.cols) + 12.0 * n);  // matrix; x, f, out
+        return AMG_HIP_OK;
+      }, copy_home);
     }
+    // the coefficients in double, rounded at the launch
+    return cheb_steps(L.cheb_lo, L.cheb_hi, s->opt.smoother_iters, s->opt.cheb_degree, Q.u.as<float>(),
+                      Q.tmp.as<float>(), [&](double alpha, double beta, bool first, bool last, float* a, float* b) {
+      STEP_TRY(X, launch_mat_f32(cheb_kernel_mode(first, last), Q.rows, a, f, b, (float)beta, Q.d.as<float>(),
+                                 (float)alpha, X.st));
+      X.count(mat_bytes_f32(Q.rows) + 12.0 * n + (first ? 0.0 : 4.0 * n) + (last ? 0.0 : 4.0 * n));
+      return AMG_HIP_OK;
+    }, copy_home);
   }
-  if (passes & 1) {  // result sits in tmp: bring it home (keeps the graph static)
-    F32_DO(hipMemcpyAsync(Q.u.p, Q.tmp.p, sizeof(float) * (size_t)L.n, hipMemcpyDeviceToDevice, st));
-    s->facct(8.0 * n);
+
+  // r_l = f_l - A_l u_l (:272-274)
+  amg_hip_status residual(int l) {
+    const Level& L = s->lv[l];
+    F32Level& Q = s->f32.lv[(size_t)l];
+    STEP_TRY(X, launch_mat_f32(CSR_RESID, Q.rows, Q.u.as<float>(), Q.f.as<float>(), Q.r.as<float>(), 1.0f, nullptr,
+                               0.0f, X.st));
+    X.count(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);
+    return AMG_HIP_OK;
   }
-  return AMG_HIP_OK;
-}
 
-// The steps of the cycle, one helper each: enqueue_f32_vcycle strings them together, and
-// amg_hip_f32_level_op (a test hook) runs one of them alone -- the same launches either way.
-// r_l = f_l - A_l u_l (:272-274)
-amg_hip_status enqueue_f32_residual(amg_hip_solver* s, int l, bool dry) {
-  const Level& L = s->lv[l];
-  F32Level& Q = s->f32.lv[(size_t)l];
-  F32_DO(launch_mat_f32(CSR_RESID, Q.rows, Q.u.as<float>(), Q.f.as<float>(), Q.r.as<float>(), 1.0f, nullptr, 0.0f,
-                        s->stream));
-  s->facct(mat_bytes_f32(Q.rows) + 12.0 * (double)L.n);
-  return AMG_HIP_OK;
-}
-
-// u_{l+1} = 0, f_{l+1} = R_l r_l (:278 + :281-282)
-amg_hip_status enqueue_f32_restrict(amg_hip_solver* s, int l, bool dry) {
-  const Level& L = s->lv[l];
-  const Level& C = s->lv[l + 1];
-  F32Level& Q = s->f32.lv[(size_t)l];
-  F32Level& QC = s->f32.lv[(size_t)l + 1];
-  hipStream_t st = s->stream;
-  if (L.linear && s->opt.stencil_transfers) {
-    F32_DO(launch_linear_restrict_f32(L.n, C.n, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
-    s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
-  } else if (L.tensor_stencil) {
-    F32_DO(launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), st));
-    s->facct(4.0 * (double)L.n + 8.0 * (double)C.n);
-  } else {
-    F32_DO(launch_zero_f32(C.n, QC.u.as<float>(), st));  // as the zero guess: no memset node
-    const DevCsr& R = L.R_rows;
-    F32_DO(launch_csr_f32(CSR_SPMV, R.n_rows, R.rowptr(), R.col(), Q.rval.as<float>(), Q.r.as<float>(), nullptr,
-                          QC.f.as<float>(), 1.0f, nullptr, 0.0f, st));
-    s->facct(8.0 * (double)R.nnz + 4.0 * (double)(R.n_rows + 1) + 4.0 * (double)L.n + 8.0 * (double)C.n);
+  // u_{l+1} = 0, f_{l+1} = R_l r_l (:278 + :281-282)
+  amg_hip_status restriction(int l) {
+    const Level& L = s->lv[l];
+    const Level& C = s->lv[l + 1];
+    F32Level& Q = s->f32.lv[(size_t)l];
+    F32Level& QC = s->f32.lv[(size_t)l + 1];
+    if (L.linear && s->opt.stencil_transfers) {
+      STEP_TRY(X, launch_linear_restrict_f32(L.n, C.n, Q.r.as<float>(), QC.f.as<float>(), QC.u.as<float>(), X.st));
+      X.count(4.0 * (double)L.n + 8.0 * (double)C.n);
+    } else if (L.tensor_stencil) {
+      STEP_TRY(X, launch_tensor_restrict_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, Q.r.as<float>(),
+                                             QC.f.as<float>(), QC.u.as<float>(), X.st));
+      X.count(4.0 * (double)L.n + 8.0 * (double)C.n);
+    } else {
+      STEP_TRY(X, launch_zero_f32(C.n, QC.u.as<float>(), X.st));  // as the zero guess: no memset node
+      const DevCsr& R = L.R_rows;
+      STEP_TRY(X, launch_csr_f32(CSR_SPMV, R.n_rows, R.rowptr(), R.col(), Q.rval.as<float>(), Q.r.as<float>(), nullptr,
+                                 QC.f.as<float>(), 1.0f, nullptr, 0.0f, X.st));
+      X.count(8.0 * (double)R.nnz + 4.0 * (double)(R.n_rows + 1) + 4.0 * (double)L.n + 8.0 * (double)C.n);
+    }
+    return AMG_HIP_OK;
   }
-  return AMG_HIP_OK;
-}
 
-// :287-288 in double: widen f_L, the solver's factor, round the result
-amg_hip_status enqueue_f32_coarse(amg_hip_solver* s, bool dry) {
-  F32& F = s->f32;
-  const int nl = (int)s->lv.size();
-  const Level& C = s->lv[(size_t)nl - 1];
-  F32Level& QC = F.lv[(size_t)nl - 1];
-  hipStream_t st = s->stream;
-  F32_DO(launch_to_f64(C.n, QC.f.as<float>(), F.cf.as<double>(), st));
-  F32_DO(launch_coarse(s->coarse, F.cf.as<double>(), F.cy.as<double>(), F.cx.as<double>(), st));
-  F32_DO(launch_to_f32(C.n, F.cx.as<double>(), QC.u.as<float>(), st));
-  // the two conversions; the band of L forwards and backwards, D, f, u (enqueue_vcycle_body)
-  s->facct(24.0 * (double)C.n + 16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * (double)C.n);
-  return AMG_HIP_OK;
-}
-
-// u_l = u_l + P_l u_{l+1} (:294-296)
-amg_hip_status enqueue_f32_prolong(amg_hip_solver* s, int l, bool dry) {
-  const Level& L = s->lv[l];
-  const Level& C = s->lv[l + 1];
-  F32Level& Q = s->f32.lv[(size_t)l];
-  F32Level& QC = s->f32.lv[(size_t)l + 1];
-  hipStream_t st = s->stream;
-  if (L.linear && s->opt.stencil_transfers) {
-    F32_DO(launch_linear_prolong_add_f32(L.n, C.n, QC.u.as<float>(), Q.u.as<float>(), st));
-    s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
-  } else if (L.tensor_stencil) {
-    F32_DO(launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, QC.u.as<float>(), Q.u.as<float>(), st));
-    s->facct(4.0 * (double)C.n + 8.0 * (double)L.n);
-  } else {
-    const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
-    F32_DO(launch_csr_f32(CSR_SPMV_ADD, P.n_rows, P.rowptr(), P.col(), Q.pval.as<float>(), QC.u.as<float>(),
-                          Q.u.as<float>(), Q.u.as<float>(), 1.0f, nullptr, 0.0f, st));
-    s->facct(8.0 * (double)P.nnz + 4.0 * (double)(P.n_rows + 1) + 4.0 * (double)C.n + 8.0 * (double)L.n);
+  // :287-288 in double: widen f_L, the solver's factor, round the result
+  amg_hip_status coarse() {
+    F32& F = s->f32;
+    const Level& C = s->lv.back();
+    F32Level& QC = F.lv.back();
+    STEP_TRY(X, launch_to_f64(C.n, QC.f.as<float>(), F.cf.as<double>(), X.st));
+    STEP_TRY(X, launch_coarse(s->coarse, F.cf.as<double>(), F.cy.as<double>(), F.cx.as<double>(), X.st));
+    STEP_TRY(X, launch_to_f32(C.n, F.cx.as<double>(), QC.u.as<float>(), X.st));
+    // the two conversions; the band of L forwards and backwards, D, f, u (enqueue_vcycle_body)
+    X.count(24.0 * (double)C.n + 16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * (double)C.n);
+    return AMG_HIP_OK;
   }
-  return AMG_HIP_OK;
-}
+
+  // u_l = u_l + P_l u_{l+1} (:294-296)
+  amg_hip_status prolong(int l) {
+    const Level& L = s->lv[l];
+    const Level& C = s->lv[l + 1];
+    F32Level& Q = s->f32.lv[(size_t)l];
+    F32Level& QC = s->f32.lv[(size_t)l + 1];
+    if (L.linear && s->opt.stencil_transfers) {
+      STEP_TRY(X, launch_linear_prolong_add_f32(L.n, C.n, QC.u.as<float>(), Q.u.as<float>(), X.st));
+      X.count(4.0 * (double)C.n + 8.0 * (double)L.n);
+    } else if (L.tensor_stencil) {
+      STEP_TRY(X, launch_tensor_prolong_add_f32(L.tdim, L.dims, L.tmask, L.tsides, L.tper, QC.u.as<float>(),
+                                                Q.u.as<float>(), X.st));
+      X.count(4.0 * (double)C.n + 8.0 * (double)L.n);
+    } else {
+      const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
+      STEP_TRY(X, launch_csr_f32(CSR_SPMV_ADD, P.n_rows, P.rowptr(), P.col(), Q.pval.as<float>(), QC.u.as<float>(),
+                                 Q.u.as<float>(), Q.u.as<float>(), 1.0f, nullptr, 0.0f, X.st));
+      X.count(8.0 * (double)P.nnz + 4.0 * (double)(P.n_rows + 1) + 4.0 * (double)C.n + 8.0 * (double)L.n);
+    }
+    return AMG_HIP_OK;
+  }
+};
 
 // level 0's f holds the right-hand side, its u receives the result
-amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, bool dry) {
-  const int nl = (int)s->lv.size();
-  amg_hip_status r;
+amg_hip_status enqueue_f32_vcycle(amg_hip_solver* s, StepCtx& X) {
   // the zero guess.  A kernel, not hipMemsetAsync: a memset node of the captured graph was seen to fill
   // with stale bytes when the graph is replayed after a device-to-host copy (64 x 48 grid, 12288 bytes)
-  F32_DO(launch_zero_f32(s->lv[0].n, s->f32.lv[0].u.as<float>(), s->stream));
-  s->facct(4.0 * (double)s->lv[0].n);
-  for (int l = 0; l + 1 < nl; ++l) {
-    if ((r = enqueue_f32_smooth(s, l, dry)) != AMG_HIP_OK) return r;    // :268
-    if ((r = enqueue_f32_residual(s, l, dry)) != AMG_HIP_OK) return r;
-    if ((r = enqueue_f32_restrict(s, l, dry)) != AMG_HIP_OK) return r;
-  }
-  if ((r = enqueue_f32_coarse(s, dry)) != AMG_HIP_OK) return r;
-  for (int l = nl - 2; l >= 0; --l) {                                   // :291
-    if ((r = enqueue_f32_prolong(s, l, dry)) != AMG_HIP_OK) return r;
-    if ((r = enqueue_f32_smooth(s, l, dry, true)) != AMG_HIP_OK) return r;  // :300
-  }
-  return AMG_HIP_OK;
+  STEP_TRY(X, launch_zero_f32(s->lv[0].n, s->f32.lv[0].u.as<float>(), X.st));
+  X.count(4.0 * (double)s->lv[0].n);
+  return walk_vcycle((int)s->lv.size(), F32Steps{s, X});
 }
-#undef F32_DO
+#undef STEP_TRY
 
 // z = M32^-1 v: round v into level 0's float right-hand side, the cycle (its captured graph, or the
 // same enqueue eagerly with use_graph = 0), widen level 0's float solution into z
@@ -4962,13 +4890,10 @@ amg_hip_status f32_apply(amg_hip_solver* s, const double* v, double* z) {
   F32& F = s->f32;
   const int64_t n = s->lv[0].n;
   HIP_TRY(launch_to_f32(n, v, F.lv[0].f.as<float>(), s->stream));
-  if (!s->opt.use_graph) {
-    amg_hip_status r = enqueue_f32_vcycle(s, false);
-    if (r != AMG_HIP_OK) return r;
-  } else {
-    if (!F.exec) AMG_TRY(capture_once(s->stream, [s] { return enqueue_f32_vcycle(s, false); }, &F.graph, &F.exec));
-    HIP_TRY(hipGraphLaunch(F.exec, s->stream));
-  }
+  AMG_TRY(replay_or_enqueue(s->opt.use_graph, F.graph, s->stream, [s] {
+    StepCtx X{s->stream};
+    return enqueue_f32_vcycle(s, X);
+  }));
   HIP_TRY(launch_to_f64(n, F.lv[0].u.as<float>(), z, s->stream));
   return AMG_HIP_OK;
 }
@@ -5599,14 +5524,7 @@ amg_hip_status amg_hip_vcycles(amg_hip_solver* s, int32_t n) {
       if ((r = run_seam_piece(s, SEAM_CYCLE, src)) != AMG_HIP_OK) return r;
     return run_seam_piece(s, SEAM_FINISH, 0);
   }
-  if (s->opt.use_graph) {
-    if ((r = ensure_graph(s)) != AMG_HIP_OK) return r;
-    for (int i = 0; i < n; ++i) HIP_TRY(hipGraphLaunch(s->graph_exec, s->stream));
-  } else {
-    for (int i = 0; i < n; ++i)
-      if ((r = enqueue_vcycle(s)) != AMG_HIP_OK) return r;
-  }
-  return AMG_HIP_OK;
+  return replay_or_enqueue(s->opt.use_graph, s->graph, s->stream, [s] { return enqueue_vcycle(s); }, n);
 }
 amg_hip_status amg_hip_vcycle(amg_hip_solver* s) { return amg_hip_vcycles(s, 1); }
 
@@ -5730,14 +5648,8 @@ amg_hip_status amg_hip_slab_setup(amg_hip_solver* s, int32_t rank, int32_t world
     sb.levels = 0;  // not configured: amg_hip_slab_run refuses
     return r;
   }
-  s->reset_seam_graphs();
-  if (s->graph_ready) {  // the whole-cycle graph holds the old pointers
-    (void)hipGraphExecDestroy(s->graph_exec);
-    (void)hipGraphDestroy(s->graph);
-    s->graph_exec = nullptr;
-    s->graph = nullptr;
-    s->graph_ready = false;
-  }
+  for (CycleGraph& g : s->seam_graph) g.reset();
+  s->graph.reset();  // the whole-cycle graph holds the old pointers
   *info = pl;
   info->pitch0 = m0;
   info->gather_pitch = mk;
@@ -5754,12 +5666,8 @@ amg_hip_status amg_hip_slab_run(amg_hip_solver* s, int32_t part) {
   if (sb.levels < 1) return fail(AMG_HIP_EINVAL, "amg_hip_slab_run: amg_hip_slab_setup has not succeeded");
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
-  if (!s->opt.use_graph) return enqueue_vcycle(s, part);
-  const int gi = part - 1;
-  if (!sb.exec[gi])
-    AMG_TRY(capture_once(s->stream, [s, part] { return enqueue_vcycle(s, part); }, &sb.graph[gi], &sb.exec[gi]));
-  HIP_TRY(hipGraphLaunch(sb.exec[gi], s->stream));
-  return AMG_HIP_OK;
+  return replay_or_enqueue(s->opt.use_graph, sb.graph[part - 1], s->stream,
+                           [s, part] { return enqueue_vcycle(s, part); });
 }
 
 amg_hip_status amg_hip_window_setup(amg_hip_solver* s, const int64_t* down_lo, const int64_t* down_hi,
@@ -6187,12 +6095,9 @@ amg_hip_status amg_hip_f32_must_move(amg_hip_solver* s, double* bytes) {
   amg_hip_status r = f32_supported(s);
   if (r != AMG_HIP_OK) return r;
   if ((r = ensure_f32(s)) != AMG_HIP_OK) return r;
-  s->f32_mm = 0.0;
-  s->f32_acct = true;
-  r = enqueue_f32_vcycle(s, true);
-  s->f32_acct = false;
-  if (r != AMG_HIP_OK) return r;
-  *bytes = s->f32_mm + 24.0 * (double)s->lv[0].n;  // v -> float and float -> z: 8 + 4 bytes per row each
+  StepCtx X{s->stream, false};
+  if ((r = enqueue_f32_vcycle(s, X)) != AMG_HIP_OK) return r;
+  *bytes = X.once + 24.0 * (double)s->lv[0].n;  // v -> float and float -> z: 8 + 4 bytes per row each
   return AMG_HIP_OK;
 }
 
@@ -6252,12 +6157,14 @@ amg_hip_status amg_hip_f32_level_op(amg_hip_solver* s, int32_t level, int32_t op
   }
   amg_hip_status r = f32_hook_ready(s, level, bad);
   if (r != AMG_HIP_OK) return r;
+  StepCtx X{s->stream};
+  F32Steps S{s, X};
   switch (op) {
-    case 0: return enqueue_f32_smooth(s, level, false);
-    case 1: return enqueue_f32_residual(s, level, false);
-    case 2: return enqueue_f32_restrict(s, level, false);
-    case 3: return enqueue_f32_prolong(s, level, false);
-    default: return enqueue_f32_coarse(s, false);
+    case 0: return S.smooth(level, false);
+    case 1: return S.residual(level);
+    case 2: return S.restriction(level);
+    case 3: return S.prolong(level);
+    default: return S.coarse();
   }
 }
 
@@ -6277,7 +6184,8 @@ amg_hip_status amg_hip_f32_line_subsweep(amg_hip_solver* s, int32_t level, int32
   amg_hip_status r = f32_line_hook_ready(s, level, d < 0 || d > 2 ? "direction index out of range" : nullptr);
   if (r != AMG_HIP_OK) return r;
   if (d >= line_dirs(s->opt.smoother, s->lv[level].alt)) return fail(AMG_HIP_EINVAL, "direction index out of range");
-  return enqueue_f32_line_subsweep(s, level, d, false);
+  StepCtx X{s->stream};
+  return F32Steps{s, X}.line_subsweep(level, d);
 }
 
 amg_hip_status amg_hip_f32_line_factors(amg_hip_solver* s, int32_t level, float* dl, float* ip, float* cp) {
@@ -6578,8 +6486,7 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
       const int gi = 2;  // the seam cycle that reads tmp: captured, not run
       s->seam_piece = SEAM_CYCLE;
       s->seam_src = 0;
-      r = s->seam_exec[gi] ? AMG_HIP_OK
-                           : capture_once(s->stream, [s] { return enqueue_vcycle(s); }, &s->seam_graph[gi], &s->seam_exec[gi]);
+      r = s->seam_graph[gi].capture(s->stream, [s] { return enqueue_vcycle(s); });
       s->seam_piece = SEAM_OFF;
       if (r != AMG_HIP_OK) return r;
     }
@@ -6590,11 +6497,8 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
     // not enqueued yet: capturing the graph walks the cycle without running it
     amg_hip_status r = set_device(s);
     if (r != AMG_HIP_OK) return r;
-    if (s->opt.use_graph) {
-      if ((r = ensure_graph(s)) != AMG_HIP_OK) return r;
-    } else {
-      return fail(AMG_HIP_EINVAL, "amg_hip_cycle_must_move: run a V-cycle first");
-    }
+    if (!s->opt.use_graph) return fail(AMG_HIP_EINVAL, "amg_hip_cycle_must_move: run a V-cycle first");
+    if ((r = s->graph.capture(s->stream, [s] { return enqueue_vcycle(s); })) != AMG_HIP_OK) return r;
   }
   *bytes = s->must_move[part];
   return AMG_HIP_OK;
@@ -7847,12 +7751,9 @@ amg_hip_status amg_hip_block_must_move(amg_hip_solver* s, int32_t k, double* byt
   if (r != AMG_HIP_OK) return r;
   const int kp = block_kp(k);
   if ((r = ensure_block(s, kp)) != AMG_HIP_OK) return r;
-  s->block_mm[0] = s->block_mm[1] = 0.0;
-  s->block_acct = true;
-  r = enqueue_block_vcycle(s, kp, true);
-  s->block_acct = false;
-  if (r != AMG_HIP_OK) return r;
-  *bytes = s->block_mm[0] + (double)k * s->block_mm[1];
+  StepCtx X{s->stream, false};
+  if ((r = enqueue_block_vcycle(s, kp, X)) != AMG_HIP_OK) return r;
+  *bytes = X.once + (double)k * X.per_col;
   return AMG_HIP_OK;
 }
 

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""The launches of the double-precision V-cycle, for comparing two builds of the library.
+"""The launches of the V-cycle (double, and where the configuration says so block and float), for
+comparing two builds of the library.
 
   run one configuration (eager: use_graph=False), vcycle(1) then vcycle(3), and print cycle_must_move()
-  of parts 0 and 4 as hexadecimal floats:
+  of parts 0 and 4 as hexadecimal floats; a configuration with the "plain" switch then runs one
+  block_vcycles on 3 columns (pitch 4) and one apply_f32, and prints block_must_move(3) and
+  f32_must_move() the same way:
       AMG_HIP_LIBRARY=<lib.so> rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- \
           python3 tools/launch_sequence.py --config <name>
   list the configurations:
       python3 tools/launch_sequence.py --list
   compare the traces and the printed bytes of two builds (<dir>/<config>/t_kernel_trace.csv and
   <dir>/<config>.out of every configuration) and write the markdown report:
-      python3 tools/launch_sequence.py --compare <dir A> <dir B> > profiles/plan_launch_sequences.md
+      python3 tools/launch_sequence.py --compare <dir A> <dir B> > profiles/<name>_launch_sequences.md
 
 Only the library's existing API is used, so either build can be measured."""
 import argparse
@@ -63,7 +66,38 @@ def _configs():
         *csc(O.laplacian(64)), O.rhs(64), 4, 0.25, 50, smoother=5, use_graph=False))
     cfg["line_alt_tensor64"] = ({}, lambda: amg.Multigrid.poisson_tensor(
         64, 4, smoother=7, omega=0.8, smoother_iters=1, use_graph=False))
+    _plain_configs(amg, O, cfg, csc)
     return amg, cfg
+
+
+def _plain_configs(amg, O, cfg, csc):
+    """the configurations that also run the block and the float cycle ("plain": every switch those need):
+    between them every branch of their five steps"""
+    import test_gpu_block_lines as BL
+    import test_gpu_pcg_project as PP
+    import test_gpu_tensor_opdep as TO
+    import opdep_twin
+    plain = {"plain": 1}
+    jac = dict(smoother=amg.SM_JACOBI, omega=0.8, use_graph=False)
+    for iters in (1, 2):   # linear transfers; the copy home after an odd count
+        cfg[f"plain_jacobi{iters}_poisson33"] = (plain, lambda iters=iters: amg.Multigrid.poisson(
+            33, 4, smoother_iters=iters, **jac))
+    for name, sm in (("chebyshev", dict(smoother=5, use_graph=False)), ("jacobi", dict(smoother_iters=2, **jac))):
+        cfg[f"plain_{name}_rs64"] = (plain, lambda sm=sm: amg.Multigrid.ruge_stueben(   # CSR transfers
+            *csc(O.laplacian(64)), O.rhs(64), 4, 0.25, 50, **sm))
+    cfg["plain_line_alt_64x48"] = (plain, lambda: BL._alt_6448(amg, use_graph=False))
+    cfg["plain_cyclic_64x48"] = (plain, lambda: BL.cyclic_solver(amg, "64x48", False))
+
+    def opdep():           # axis levels through their CSR rows
+        A, b, _ = opdep_twin.case((33, 20))
+        return TO.ctor(amg, A, b, (33, 20), use_graph=False)
+    cfg["plain_opdep_33x20"] = (plain, opdep)
+    cfg["plain_singular_64x48"] = (plain, lambda: PP.make(amg, O, "64x48", use_graph=False)[0])  # the pinned solve
+    # the four coarse kinds: one-wave band (a 4 x 4 coarsest grid), K-BandChain (2 x 2), K-Spike, K-BandWide
+    cfg["plain_coarse_band"] = (plain, lambda: amg.Multigrid.poisson(129, 6, exact_coarse_solve=True, smoother_iters=2, **jac))
+    cfg["plain_coarse_chain"] = (plain, lambda: amg.Multigrid.poisson(129, 7, smoother_iters=2, **jac))
+    cfg["plain_coarse_spike"] = (plain, lambda: amg.Multigrid.poisson(129, 3, fast_coarse_solve=True, smoother_iters=2, **jac))
+    cfg["plain_coarse_wide"] = (plain, lambda: amg.Multigrid.poisson(256, 2, smoother_iters=2, **jac))
 
 
 def run(name):
@@ -73,6 +107,10 @@ def run(name):
         amg.set_patch_min_rows(switches["patch_min_rows"])
     if "tail_fusion" in switches:
         amg.set_tail_fusion(switches["tail_fusion"])
+    if "plain" in switches:
+        amg.set_block_lines(1)
+        amg.set_f32_lines(1)
+        amg.set_f32_dict(1)
     mg = make()
     try:
         mg.vcycle(1)
@@ -80,6 +118,20 @@ def run(name):
         mg.sync()
         for part in (0, 4):
             print(f"{name} cycle_must_move({part}) = {float(mg.cycle_must_move(part)).hex()}")
+        if "plain" in switches:
+            import numpy as np
+            import torch
+            n0 = mg.get_n_dofs(0)
+            rng = np.random.default_rng(3)
+            U, F = (torch.from_numpy(rng.standard_normal((n0, 3))).cuda() for _ in range(2))
+            mg.block_vcycles(U, F, n=1)
+            v = torch.from_numpy(rng.standard_normal(n0)).cuda()
+            z = torch.empty_like(v)
+            mg.apply_f32(v.data_ptr(), z.data_ptr())
+            mg.sync()
+            print(f"{name} coarse_solve_kind = {mg.coarse_solve_kind()}")
+            print(f"{name} block_must_move(3) = {float(mg.block_must_move(3)).hex()}")
+            print(f"{name} f32_must_move() = {float(mg.f32_must_move()).hex()}")
     finally:
         mg.close()
 
@@ -114,19 +166,21 @@ def compare(dir_a, dir_b):
         for d in (dir_a, dir_b):
             seqs.append(_trace(os.path.join(d, name)))
             with open(os.path.join(d, name + ".out")) as f:
-                outs.append([line.strip() for line in f if "cycle_must_move" in line])
-        same_seq, same_bytes = seqs[0] == seqs[1], outs[0] == outs[1] and len(outs[0]) == 2
+                outs.append([line.strip() for line in f if "_must_move" in line])
+        same_seq = seqs[0] == seqs[1]
+        same_bytes = outs[0] == outs[1] and len(outs[0]) == (4 if name.startswith("plain_") else 2)
         verdicts.append((name, len(seqs[0]), len(seqs[1]), same_seq, same_bytes))
         body.append(f"### {name}\n")
         for tag, seq, out in zip("AB", seqs, outs):
             ids = [table.setdefault(k, len(table)) for k in seq]
             body.append(f"{tag}: {len(seq)} launches; " + "; ".join(out) + "\n")
             body.append("```\n" + _rle(ids) + "\n```\n")
-    print("# Launch sequences of the V-cycle: parent (A) against the cycle plan (B)\n")
+    print("# Launch sequences of the V-cycle: parent (A) against this build (B)\n")
     print("`tools/launch_sequence.py`, one `rocprofv3 --kernel-trace` run per configuration and build: the solver is")
     print("created with `use_graph=False`, runs `vcycle(1)` and `vcycle(3)`, and prints `cycle_must_move()` of")
-    print("parts 0 and 4.  A list is every kernel launch of the process in dispatch order (set-up included) as")
-    print("an index into the table at the end, `k*c` for c launches of k in a row.\n")
+    print("parts 0 and 4; a `plain_*` configuration then runs one `block_vcycles` on 3 columns and one `apply_f32`")
+    print("and prints `block_must_move(3)` and `f32_must_move()`.  A list is every kernel launch of the process in")
+    print("dispatch order (set-up included) as an index into the table at the end, `k*c` for c launches of k in a row.\n")
     print("| configuration | launches A | launches B | same (kernel, grid, workgroup) list | same bytes |")
     print("|---|---|---|---|---|")
     for name, na, nb, s, b in verdicts:
