@@ -1464,7 +1464,6 @@ struct Level {
   bool symmetric = false;  //   smoother.hpp:101-117); aliases A_rows when bitwise equal
   const DevMat& A_cols() const { return symmetric ? A_rows : A_cols_own; }
   DevMem u, f, r, tmp;
-  bool march_odd = false;  // K-March traded u and tmp an odd number of times in the cycle being enqueued
   DevMem diag;             // a_ii (true-Jacobi smoother only)
   double cheb_lo = 0.0, cheb_hi = 0.0;  // Chebyshev smoother: interval of D^-1 A's spectrum
   DevMem cheb_d;           //   and its update vector d (r stays the residual: keep_residual)
@@ -1695,8 +1694,11 @@ int g_pair_duo = [] {
 int64_t g_patch_min_rows = 1000000;  // amg_hip_set_patch_min_rows (level 4 of 4096^2 has 1 048 575 rows)
 
 // The cycle plan ("The cycle plan"): which launch form every level of the
-// double-precision V-cycle takes on each leg, chosen once per enqueue by build_cycle_plan.  The
-// enqueue dispatches on it and the accessors read it; nothing else asks an eligibility predicate.
+// double-precision V-cycle takes on each leg and which of its two buffers holds its iterate when,
+// chosen once per enqueue by build_cycle_plan.  The enqueue dispatches on it and the accessors read it;
+// nothing else asks an eligibility predicate.  The buffers' roles are read from the plan (between_legs,
+// after_up, up_target, resting): no function reached from an enqueue or a level operation assigns to, or
+// swaps, a DevMem member of a Level, so a failing HIP call anywhere leaves every level as it found it.
 enum LegForm : uint8_t {
   LEG_NONE,        // no launch of its own: the coarsest level (solved, not smoothed) when r is not kept
   LEG_MC_PATCH,    // multicolour smoother, colour stages as patch launches
@@ -1724,7 +1726,10 @@ struct LevelPlan {
   bool restrict_fused = false;         // plain down-leg: residual + restriction (+ first coarse sweep) in one launch
   ProlongBy prolong = PROLONG_NONE;    // who adds P u_{l+1} to this level
   bool up_tmp = false;                 // ... and where: tmp, else u in place
-  bool march = false;                  // K-March sweeps the level (a plain leg in phase 0 that prolongs nowhere)
+  // K-March sweeps this leg in one launch (a plain leg in phase 0 that prolongs nowhere).  Between its
+  // legs the iterate of a level marched down lives in tmp for every reader and writer; the up-leg marches back
+  bool march_down = false, march_up = false;
+  bool home_copy() const { return march_down != march_up; }  // one leg only: the cycle ends with tmp -> u
   bool rests_tmp = false;              // the solution rests in tmp after the cycle, else in u
   bool writes_r = true;                // r is written when keep_residual is 0
 };
@@ -1733,7 +1738,6 @@ struct CyclePlan {
   int tail_first = -1;      // the K-Tail head, or -1
   bool seam = false;        // amg_hip_vcycles(n >= 2) runs the seam sequence
   bool zero_known = false;  // coarse pre-smoothing starts from u == 0 without reading it
-  int part = 0;
 };
 
 struct amg_hip_solver {
@@ -1759,15 +1763,11 @@ struct amg_hip_solver {
   CycleGraph graph;  // the whole cycle
   double cycle_bytes = 0, fine_sweep_bytes = 0;
   // bytes the launches of one V-cycle HAVE TO move (what each kernel reads and writes once in the
-  // layout it really streams), summed while the cycle is enqueued; [part] as enqueue_vcycle's
+  // layout it really streams), summed while the cycle is enqueued (CycleCtx); [part] as enqueue_vcycle's
   // [4]: one steady-state seam cycle (seam launch + levels 1 .. L-1; amg_hip_vcycles), [5]: its head and finish
   double must_move[6] = {0, 0, 0, 0, 0, 0};
-  int acct_part = -1;  // -1: not inside enqueue_vcycle
-  void acct(double bytes) { if (acct_part >= 0) must_move[acct_part] += bytes; }
-  // K-Patch seam (amg_hip_vcycles with n >= 2, patch_seam_ok): the piece being enqueued and the
-  // level-0 buffer it hands over in (0: tmp, 1: r), and the captured pieces -- head and seam cycle
-  // per buffer, the finish
-  int seam_piece = 0, seam_src = 0;
+  // K-Patch seam (amg_hip_vcycles with n >= 2, patch_seam_ok): the captured pieces -- head and seam
+  // cycle per level-0 buffer handed over in (0: tmp, 1: r), the finish
   CycleGraph seam_graph[5];
   Slab slab;
   Block blk;
@@ -1795,8 +1795,28 @@ double mat_bytes(const DevMat& A) {
   return (double)b;
 }
 
+// What a step of a cycle enqueues on, and the bytes its launches have to move.  launch = false is the
+// dry run of amg_hip_block_must_move / amg_hip_f32_must_move: count, launch nothing (the double cycle has none).
+struct StepCtx {
+  hipStream_t st = nullptr;
+  bool launch = true;
+  double once = 0;     // bytes moved once per launch (the double and the float cycle count all of their bytes here)
+  double per_col = 0;  // bytes per column of a block panel: k columns have to move once + k * per_col
+  void count(double o, double c = 0.0) {
+    once += o;
+    per_col += c;
+  }
+};
+// A level's iterate and its second buffer as one step sees them: u and tmp of the Level, or the two
+// the other way round where the plan says the iterate lives in tmp.
+struct LevelVecs { double *u, *tmp; };
+LevelVecs level_vecs(const Level& L, bool in_tmp) {
+  double *u = L.u.as<double>(), *t = L.tmp.as<double>();
+  return in_tmp ? LevelVecs{t, u} : LevelVecs{u, t};
+}
+
 // ---- smoother on one level --------------------------------------------------
-amg_hip_status enqueue_multicolor(amg_hip_solver* s, Level& L, hipStream_t st, bool again);
+amg_hip_status enqueue_multicolor(StepCtx& X, amg_hip_solver* s, Level& L, double* u, bool again);
 
 // full coarsening: level l (grid d) has an axis that cannot be coarsened, so level l + 1 is not possible
 std::string tensor_level_error(int l, const int64_t d[3]) {
@@ -2042,13 +2062,12 @@ static std::vector<int> duo_pairing(const amg_hip_solver* s, int tail_lt) {
   return partner;
 }
 
-// K-March: the two plain Jacobi sweeps u -> tmp -> u of a 3-D 7-point level as ONE launch u -> tmp
-// (kernels.hip: march_kernel); the level's two vectors then trade places.  A level swept this way
-// on both legs ends the cycle with them where it found them; enqueue_vcycle brings back one that was
-// swept on one leg only.  Fills the launch's arguments; the plan builder also takes the answer as the
-// level's eligibility (finish_dict): the 7-point offsets of one interior type, n a
-// multiple of the plane, and no row on a line / plane edge coupling across it.
-static bool march_fill(const amg_hip_solver* s, int l, MarchRef* R) {
+// K-March: the two plain Jacobi sweeps of a 3-D 7-point level as ONE launch from the level's iterate
+// v.u into its other buffer v.tmp (kernels.hip: march_kernel); the plan says which leg runs it and
+// where the iterate lives afterwards (LevelPlan::march_down).  Fills the launch's arguments; the plan
+// builder also takes the answer as the level's eligibility (finish_dict): the 7-point offsets of one
+// interior type, n a multiple of the plane, and no row on a line / plane edge coupling across it.
+static bool march_fill(const amg_hip_solver* s, int l, LevelVecs v, MarchRef* R) {
   const Level& L = s->lv[l];
   const DevMat& A = L.A_cols();
   if (!(s->opt.smoother == AMG_HIP_SM_JACOBI && s->opt.smoother_iters == 2 && !s->opt.no_fusion && !s->opt.window &&
@@ -2066,110 +2085,112 @@ static bool march_fill(const amg_hip_solver* s, int l, MarchRef* R) {
   R->wtab = A.dmarch.as<double>();
   R->rtype = A.drtype.as<uint8_t>();
   R->f = L.f.as<double>();
-  R->x = L.u.as<double>();
-  R->out = L.tmp.as<double>();
+  R->x = v.u;
+  R->out = v.tmp;
   R->chunk_planes = 1;
   return march_ok(*R);
 }
 // phase 3: the first sweep was already done by the fused kernel of the finer level
-// (result in tmp).  prolong_into >= 0: the last sweep also adds P u_l to that level's u.
-// reverse: the application of the up-leg (AMG_HIP_SM_LINE_ALT runs its directions in descending order).
-// march: the plan sweeps the level with K-March (only inside a whole V-cycle, which sweeps the level
-// twice: a lone smooth() must leave the vectors where a captured graph expects them).
-amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolong_into = -1,
-                              double* prolong_out = nullptr, bool reverse = false, bool march = false) {
+// (result in tmp).
+struct Sweep {
+  int phase = 0;
+  bool march = false;    // the plan sweeps this leg with K-March: v.u -> v.tmp (LevelPlan::march_down / march_up)
+  bool reverse = false;  // the application of the up-leg (AMG_HIP_SM_LINE_ALT runs its directions in descending order)
+  const double* coarse_u = nullptr;  // phase 2: u_{l+1}
+  const double* fine_u = nullptr;    // set: the last sweep also adds P u_l to level l-1, fine_out = fine_u + P u_l
+  double* fine_out = nullptr;
+};
+// One smoothing application on level l, on the iterate v.u with v.tmp as the second buffer.
+amg_hip_status enqueue_smooth(StepCtx& X, amg_hip_solver* s, int l, LevelVecs v, const Sweep& w = Sweep()) {
   Level& L = s->lv[l];
-  hipStream_t st = s->stream;
-  const int iters = s->opt.smoother_iters;
+  hipStream_t st = X.st;
+  const int iters = s->opt.smoother_iters, phase = w.phase;
   switch (s->opt.smoother) {
     case AMG_HIP_SM_SPGS:
       // forward + backward sweep: matrix, f, u in, u out each (the scan form's pre-pass also
       // writes and re-reads one number per row: + 16 n)
-      s->acct(iters * 2.0 * (mat_bytes(L.A_rows) + 24.0 * L.n + (L.scan_C > 0 ? 16.0 * L.n : 0.0)));
+      X.count(iters * 2.0 * (mat_bytes(L.A_rows) + 24.0 * L.n + (L.scan_C > 0 ? 16.0 * L.n : 0.0)));
       for (int it = 0; it < iters; ++it) {
         if (L.scan_C > 0) {  // line-scan form (kernels.hip: K-GS-scan)
           const DictRef D = L.A_rows.dict_ref();
-          HIP_TRY(launch_gs_scan(L.n, D, L.f.as<double>(), L.u.as<double>(), L.tmp.as<double>(), false, 0,
+          HIP_TRY(launch_gs_scan(L.n, D, L.f.as<double>(), v.u, v.tmp, false, 0,
                                  1.0, L.scan_C, L.scan_ring, st));
-          HIP_TRY(launch_gs_scan(L.n, D, L.f.as<double>(), L.u.as<double>(), L.tmp.as<double>(), true, 0,
+          HIP_TRY(launch_gs_scan(L.n, D, L.f.as<double>(), v.u, v.tmp, true, 0,
                                  1.0, L.scan_C, L.scan_ring, st));
           continue;
         }
-        HIP_TRY(launch_gs_lex(L.lex_fwd->d, L.f.as<double>(), L.u.as<double>(), 0, 1.0, st));
-        HIP_TRY(launch_gs_lex(L.lex_bwd->d, L.f.as<double>(), L.u.as<double>(), 0, 1.0, st));
+        HIP_TRY(launch_gs_lex(L.lex_fwd->d, L.f.as<double>(), v.u, 0, 1.0, st));
+        HIP_TRY(launch_gs_lex(L.lex_bwd->d, L.f.as<double>(), v.u, 0, 1.0, st));
       }
       return AMG_HIP_OK;
     case AMG_HIP_SM_REF_JACOBI:
     case AMG_HIP_SM_SOR: {
       const int mode = s->opt.smoother == AMG_HIP_SM_SOR ? 2 : 1;
-      s->acct(iters * (mat_bytes(L.A_rows) + 24.0 * L.n + (L.scan_C > 0 ? 16.0 * L.n : 0.0)));
+      X.count(iters * (mat_bytes(L.A_rows) + 24.0 * L.n + (L.scan_C > 0 ? 16.0 * L.n : 0.0)));
       for (int it = 0; it < iters; ++it) {
         if (L.scan_C > 0) {
-          HIP_TRY(launch_gs_scan(L.n, L.A_rows.dict_ref(), L.f.as<double>(), L.u.as<double>(),
-                                 L.tmp.as<double>(), false, mode, s->opt.omega, L.scan_C, L.scan_ring, st));
+          HIP_TRY(launch_gs_scan(L.n, L.A_rows.dict_ref(), L.f.as<double>(), v.u,
+                                 v.tmp, false, mode, s->opt.omega, L.scan_C, L.scan_ring, st));
           continue;
         }
-        HIP_TRY(launch_gs_lex(L.lex_fwd->d, L.f.as<double>(), L.u.as<double>(), mode,
+        HIP_TRY(launch_gs_lex(L.lex_fwd->d, L.f.as<double>(), v.u, mode,
                               s->opt.omega, st));
       }
       return AMG_HIP_OK;
     }
     case AMG_HIP_SM_JACOBI: {
       const DevMat& A = L.A_cols();
-      double* a = L.u.as<double>();
-      double* b = L.tmp.as<double>();
+      double* a = v.u;
+      double* b = v.tmp;
       int it = 0;
+      if (w.march) {  // both sweeps in one pass
+        MarchRef R;
+        (void)march_fill(s, l, v, &R);
+        HIP_TRY(launch_march(R, st));
+        X.count(mat_bytes(A) + 24.0 * L.n);
+        return AMG_HIP_OK;
+      }
       if (phase == 3) {
         std::swap(a, b);
         it = 1;
       } else if (phase == 1 && jacobi_fuses_zero(s)) {
         HIP_TRY(launch_jacobi_from_zero(L.n, L.diag.as<double>(), L.f.as<double>(), b,
                                         s->opt.omega, st));
-        s->acct(24.0 * L.n);  // diagonal, f, out
+        X.count(24.0 * L.n);  // diagonal, f, out
         std::swap(a, b);
         it = 1;
       } else if (phase == 2) {  // (asked for only where the plan has PROLONG_OWN_SMOOTHER)
-        Level& C = s->lv[l + 1];
+        const Level& C = s->lv[l + 1];
         HIP_TRY(launch_sell_jacobi_prolong(A.n_rows, A.idx16, A.soff.as<int64_t>(),
                                            A.scol.p, A.sval.as<double>(), a,
-                                           C.u.as<double>(), C.n, L.f.as<double>(), b,
+                                           w.coarse_u, C.n, L.f.as<double>(), b,
                                            s->opt.omega, st));
-        s->acct(mat_bytes(A) + 24.0 * L.n + 8.0 * C.n);
+        X.count(mat_bytes(A) + 24.0 * L.n + 8.0 * C.n);
         std::swap(a, b);
         it = 1;
       }
-      if (it == 0 && prolong_into < 0 && march) {  // both sweeps in one pass: u -> tmp, then trade
-        MarchRef R;
-        (void)march_fill(s, l, &R);
-        HIP_TRY(launch_march(R, st));
-        s->acct(mat_bytes(A) + 24.0 * L.n);
-        std::swap(L.u, L.tmp);
-        L.march_odd = !L.march_odd;
-        return AMG_HIP_OK;
-      }
       for (; it < iters; ++it) {
-        if (prolong_into >= 0 && it == iters - 1) {
-          Level& F = s->lv[prolong_into];
+        if (w.fine_u && it == iters - 1) {
+          const Level& F = s->lv[l - 1];
           HIP_TRY(launch_dict_jacobi_prolong(A.n_rows, A.dict_ref(), a, L.f.as<double>(), b,
-                                             s->opt.omega, F.n, F.u.as<double>(),
-                                             prolong_out ? prolong_out : F.u.as<double>(), st));
-          s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);  // sweep + u_F in, u_F + P u out
+                                             s->opt.omega, F.n, w.fine_u, w.fine_out, st));
+          X.count(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);  // sweep + u_F in, u_F + P u out
         } else {
           HIP_TRY(launch_mat(CSR_JACOBI, A, a, L.f.as<double>(), b, s->opt.omega, st));
-          s->acct(mat_bytes(A) + 24.0 * L.n);  // matrix, f, x, out
+          X.count(mat_bytes(A) + 24.0 * L.n);  // matrix, f, x, out
         }
         std::swap(a, b);
       }
       if (iters & 1) {  // result sits in tmp: bring it home (keeps the graph static)
-        HIP_TRY(hipMemcpyAsync(L.u.p, L.tmp.p, sizeof(double) * L.n,
+        HIP_TRY(hipMemcpyAsync(v.u, v.tmp, sizeof(double) * L.n,
                                hipMemcpyDeviceToDevice, st));
-        s->acct(16.0 * L.n);
+        X.count(16.0 * L.n);
       }
       return AMG_HIP_OK;
     }
     case AMG_HIP_SM_MULTICOLOR_GS:
       for (int it = 0; it < iters; ++it) {
-        amg_hip_status r = enqueue_multicolor(s, L, st, it > 0);
+        amg_hip_status r = enqueue_multicolor(X, s, L, v.u, it > 0);
         if (r != AMG_HIP_OK) return r;
       }
       return AMG_HIP_OK;
@@ -2178,17 +2199,17 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
       // no shortcut here: u is read as it is).  The level vector ping-pongs u -> tmp -> u ...
       const DevMat& A = L.A_rows;
       return cheb_steps(
-          L.cheb_lo, L.cheb_hi, iters, s->opt.cheb_degree, L.u.as<double>(), L.tmp.as<double>(),
+          L.cheb_lo, L.cheb_hi, iters, s->opt.cheb_degree, v.u, v.tmp,
           [&](double alpha, double beta, bool first, bool last, double* a, double* b) {
             const ChebStep c{L.cheb_d.as<double>(), alpha, beta, first, last};
             HIP_TRY(launch_mat_cheb(A, a, L.f.as<double>(), b, c, st));
             // matrix, f, x, out; d written (not on the last step) and read (not on the first)
-            s->acct(mat_bytes(A) + 24.0 * L.n + (first ? 0.0 : 8.0 * L.n) + (last ? 0.0 : 8.0 * L.n));
+            X.count(mat_bytes(A) + 24.0 * L.n + (first ? 0.0 : 8.0 * L.n) + (last ? 0.0 : 8.0 * L.n));
             return AMG_HIP_OK;
           },
           [&] {
-            HIP_TRY(hipMemcpyAsync(L.u.p, L.tmp.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, st));
-            s->acct(16.0 * L.n);
+            HIP_TRY(hipMemcpyAsync(v.u, v.tmp, sizeof(double) * L.n, hipMemcpyDeviceToDevice, st));
+            X.count(16.0 * L.n);
             return AMG_HIP_OK;
           });
     }
@@ -2199,13 +2220,13 @@ amg_hip_status enqueue_smooth(amg_hip_solver* s, int l, int phase = 0, int prolo
       // cycle's residual.  LINE_ALT: one sub-sweep per direction
       const DevMat& A = L.A_rows;
       const bool alt = s->opt.smoother == AMG_HIP_SM_LINE_ALT;
-      return line_subsweeps(iters, line_dirs(s->opt.smoother, L.alt), reverse, [&](int d) {
-        HIP_TRY(alt ? launch_alt_subsweep(A, L.alt, d, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
+      return line_subsweeps(iters, line_dirs(s->opt.smoother, L.alt), w.reverse, [&](int d) {
+        HIP_TRY(alt ? launch_alt_subsweep(A, L.alt, d, v.u, L.f.as<double>(), v.tmp,
                                           s->opt.omega, st)
-                    : launch_line_sweep(A, L.line, L.u.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
+                    : launch_line_sweep(A, L.line, v.u, L.f.as<double>(), v.tmp,
                                         s->opt.omega, st));
         // matrix, f, u, r; the line solve
-        s->acct(mat_bytes(A) + 24.0 * L.n + (alt ? L.alt.solve_bytes(d) : L.line.solve_bytes()));
+        X.count(mat_bytes(A) + 24.0 * L.n + (alt ? L.alt.solve_bytes(d) : L.line.solve_bytes()));
         return AMG_HIP_OK;
       });
     }
@@ -2267,15 +2288,15 @@ static StripRef mc_strip_ref(amg_hip_solver* s, int l) {
 // hand-over), the up-legs of the slab levels.
 enum { CYCLE_ALL = 0, CYCLE_SLAB_DOWN = 1, CYCLE_SLAB_TAIL = 2, CYCLE_SLAB_UP = 3 };
 
-// The ONE place that chooses launch forms: a pure host function of the solver's state (the
-// process-wide switches as they stand now included) and the part.  It walks the levels once down and
-// once up, in priority order (first match): multicolour patch, multicolour strip, K-Patch, K-Tail,
-// K-Duo, pair, plain.  Every level gets an entry whatever the part; the enqueue walks the part's range.
-CyclePlan build_cycle_plan(const amg_hip_solver* s, int part) {
+// The ONE place that chooses launch forms: a pure host function of the hierarchy and the options as set-up
+// left them (the process-wide switches as they stand now included), the part and the seam piece; it reads
+// nothing that an enqueue writes.  It walks the levels once down and once up, in priority order (first
+// match): multicolour patch, multicolour strip, K-Patch, K-Tail, K-Duo, pair, plain.  Every level gets an
+// entry whatever the part; the enqueue walks the part's range.
+CyclePlan build_cycle_plan(const amg_hip_solver* s, int part, int piece) {
   const int nl = (int)s->lv.size();
   CyclePlan P;
   P.lv.resize((size_t)nl);
-  P.part = part;
   if (s->opt.host_only) return P;  // no device cycle: nothing fused, everything rests in u
   const bool whole = part == CYCLE_ALL || part == CYCLE_SLAB_TAIL;
   const int k = s->slab.levels;
@@ -2286,11 +2307,9 @@ CyclePlan build_cycle_plan(const amg_hip_solver* s, int part) {
   const int tail_lt = whole ? tail_from(s) : -1;
   const std::vector<int> duo = whole ? duo_pairing(s, tail_lt) : std::vector<int>((size_t)nl, -1);
   // K-March only in the stand-alone whole cycle, which sweeps a level on both legs
-  const bool march_cycle = part == CYCLE_ALL && s->seam_piece == SEAM_OFF;
+  const bool march_cycle = part == CYCLE_ALL && piece == SEAM_OFF;
   for (int l = 0; l < nl; ++l) {
     LevelPlan& Q = P.lv[(size_t)l];
-    MarchRef R;
-    Q.march = march_cycle && march_fill(s, l, &R);
     Q.up_tmp = pair_up_ok(s, l);
     Q.writes_r = !(fuses_resid_restrict(s, l) || patch_level_ok(s, l) || mc_patch_ok(s, l) || mc_strip_ok(s, l) ||
                    (l == nl - 1 && l > 0));
@@ -2365,50 +2384,73 @@ CyclePlan build_cycle_plan(const amg_hip_solver* s, int part) {
       }
     }
   }
+  // K-March: the plain legs that sweep from phase 0 and prolong nowhere
+  for (int l = 0; march_cycle && l < nl; ++l) {
+    LevelPlan& Q = P.lv[(size_t)l];
+    MarchRef R;
+    if (!march_fill(s, l, level_vecs(s->lv[l], false), &R)) continue;
+    Q.march_down = Q.down == LEG_PLAIN && Q.phase == 0;
+    Q.march_up = Q.up == LEG_PLAIN && Q.prolong != PROLONG_OWN_SMOOTHER &&
+                 !(l >= 1 && P.lv[(size_t)l - 1].prolong == PROLONG_COARSER_SWEEP);
+  }
   return P;
 }
 // the plan the accessors answer from: of the cycle enqueued last, before the first one of the cycle
 // that would run
-CyclePlan current_plan(const amg_hip_solver* s) { return s->plan_kept ? s->plan : build_cycle_plan(s, CYCLE_ALL); }
-// where a level's solution rests between cycles
-DevMem& resting(amg_hip_solver* s, const CyclePlan& P, int l) {
-  return P.lv[(size_t)l].rests_tmp ? s->lv[l].tmp : s->lv[l].u;
+CyclePlan current_plan(const amg_hip_solver* s) {
+  return s->plan_kept ? s->plan : build_cycle_plan(s, CYCLE_ALL, SEAM_OFF);
+}
+// Where a level's iterate lives, by the plan.  Between cycles (the accessors, the level operations):
+LevelVecs resting(amg_hip_solver* s, const CyclePlan& P, int l) {
+  return level_vecs(s->lv[l], P.lv[(size_t)l].rests_tmp);
+}
+// ... between its two legs (before its down-leg every level has it in u) ...
+LevelVecs between_legs(amg_hip_solver* s, const CyclePlan& P, int l) {
+  return level_vecs(s->lv[l], P.lv[(size_t)l].march_down);
+}
+// ... and after its up-leg (the finer level's prolongation reads it): where it rests, or tmp until the copy home.
+// (Only K-Patch and K-Duo launches read a level that rests in tmp; under a multicolour, own-smoother or transfer
+// prolongation the plan never puts one, so those read the level's u as ever.)
+double* after_up(amg_hip_solver* s, const CyclePlan& P, int l) {
+  return level_vecs(s->lv[l], P.lv[(size_t)l].rests_tmp || P.lv[(size_t)l].home_copy()).u;
 }
 // where the prolongation INTO level l lands: a level whose two post-sweeps run as one launch reads
 // u + P u_{l+1} from tmp (its second sweep then writes u; no in-place race between the tiles),
 // every other level takes it in place
 double* up_target(amg_hip_solver* s, const CyclePlan& P, int l) {
-  return (P.lv[(size_t)l].up_tmp ? s->lv[l].tmp : s->lv[l].u).as<double>();
+  const LevelVecs v = between_legs(s, P, l);
+  return P.lv[(size_t)l].up_tmp ? v.tmp : v.u;
 }
 
 // one symmetric pass: colours 0..nc-1 then nc-1..0; a colour that directly follows itself is not
 // launched again (mc_sequence: the repeat would store the bits already there).  again: the pass
 // follows another pass of the same smoothing call (its colour 0 directly follows colour 0).
-amg_hip_status enqueue_multicolor(amg_hip_solver* s, Level& L, hipStream_t st, bool again) {
+amg_hip_status enqueue_multicolor(StepCtx& X, amg_hip_solver* s, Level& L, double* u, bool again) {
+  hipStream_t st = X.st;
   const DevMat& A = L.mc_mat;
   if (L.mc_dict && L.mc_start_dev.p && !s->opt.no_fusion) {  // small level: the whole pass in one launch
     // every row twice: code words 8 B per word and row + 4 B dof id, f, u written
-    s->acct(2.0 * ((8.0 * L.mc_words + 4.0) * L.n + 16.0 * L.n));
+    X.count(2.0 * ((8.0 * L.mc_words + 4.0) * L.n + 16.0 * L.n));
     HIP_TRY(launch_dict_gs_sweep(L.n_colors, L.mc_start_dev.as<int32_t>(), L.mc_start.back(), L.mc_words,
                                  L.mc_wmax, L.mc_codes.as<uint64_t>(), L.mc_rowid.as<int32_t>(),
                                  L.mc_doff.as<int32_t>(), L.mc_dval.as<double>(), L.mc_ntab,
-                                 L.f.as<double>(), L.u.as<double>(), st));
+                                 L.f.as<double>(), u, st));
     return AMG_HIP_OK;
   }
   // per row of a launched colour: matrix stream (dictionary: code words + 4 B dof id; SELL panels:
   // indices + values + 4 B dof id), f, u written
   const double row_bytes = (L.mc_dict ? 8.0 * L.mc_words + 4.0 : (mat_bytes(A) + 4.0 * L.n) / (double)std::max<int64_t>(L.n, 1)) + 16.0;
   auto one = [&](int c) -> hipError_t {
-    s->acct(row_bytes * (double)(L.mc_start[c + 1] - L.mc_start[c]));
+    X.count(row_bytes * (double)(L.mc_start[c + 1] - L.mc_start[c]));
     if (L.mc_dict)
       return launch_dict_gs_color(L.mc_start[c], L.mc_start[c + 1] - L.mc_start[c], L.mc_words,
                                   L.mc_wmax, L.mc_codes.as<uint64_t>(), L.mc_rowid.as<int32_t>(),
                                   L.mc_doff.as<int32_t>(), L.mc_dval.as<double>(), L.mc_ntab,
-                                  L.f.as<double>(), L.u.as<double>(), st);
+                                  L.f.as<double>(), u, st);
     return launch_sell_gs_color(A.n_rows, A.max_width, A.soff.as<int64_t>(), A.scol.as<int32_t>(),
                                 A.sval.as<double>(), L.mc_rowid.as<int32_t>(), L.mc_start[c],
                                 L.mc_start[c + 1] - L.mc_start[c], L.f.as<double>(),
-                                L.u.as<double>(), st);
+                                u, st);
   };
   const bool dedupe = !s->opt.no_fusion;
   for (int c = (again && dedupe) ? 1 : 0; c < L.n_colors; ++c) HIP_TRY(one(c));
@@ -2416,11 +2458,10 @@ amg_hip_status enqueue_multicolor(amg_hip_solver* s, Level& L, hipStream_t st, b
   return AMG_HIP_OK;
 }
 
-amg_hip_status enqueue_residual(amg_hip_solver* s, int l) {
+amg_hip_status enqueue_residual(StepCtx& X, amg_hip_solver* s, int l, const double* u) {
   Level& L = s->lv[l];
-  HIP_TRY(launch_mat(CSR_RESID, L.A_rows, L.u.as<double>(), L.f.as<double>(), L.r.as<double>(),
-                     1.0, s->stream));
-  s->acct(mat_bytes(L.A_rows) + 24.0 * L.n);  // matrix, f, u, r
+  HIP_TRY(launch_mat(CSR_RESID, L.A_rows, u, L.f.as<double>(), L.r.as<double>(), 1.0, X.st));
+  X.count(mat_bytes(L.A_rows) + 24.0 * L.n);  // matrix, f, u, r
   return AMG_HIP_OK;
 }
 
@@ -2461,81 +2502,64 @@ struct RoctxRange {
   }
 };
 
-amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part);
-amg_hip_status enqueue_vcycle(amg_hip_solver* s, int part = CYCLE_ALL) {
-  // (the pieces of the seam sequence count apart: [0] stays the stand-alone cycle)
-  const int slot = s->seam_piece == SEAM_CYCLE ? 4 : (s->seam_piece != SEAM_OFF ? 5 : part);
-  s->must_move[slot] = 0;
-  s->acct_part = slot;
-  amg_hip_status r = enqueue_vcycle_body(s, part);
-  // a level K-March swept on one leg only (the coarsest one: it has no up-leg) ends the cycle with
-  // u and tmp traded: its solution goes home so that the next cycle, or the next replay of the
-  // captured graph, finds every level where this one did
-  for (Level& L : s->lv) {
-    if (!L.march_odd) continue;
-    L.march_odd = false;
-    const hipError_t e =
-        hipMemcpyAsync(L.tmp.p, L.u.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s->stream);
-    if (e != hipSuccess && r == AMG_HIP_OK) r = fail(AMG_HIP_EHIP, std::string("K-March copy: ") + hipGetErrorString(e));
-    s->acct(16.0 * L.n);
-    std::swap(L.u, L.tmp);
-  }
-  s->acct_part = -1;
-  return r;
-}
+// What the double cycle enqueues on: the stream and the bytes its launches have to move (StepCtx, all
+// of them in `once`), the part, and the piece of the seam sequence (SEAM_*) with the level-0 buffer it
+// hands over in (0: tmp, 1: r).  Part and piece choose which levels the enqueue walks.
+struct CycleCtx : StepCtx {
+  int part = CYCLE_ALL, piece = SEAM_OFF, src = 0;
+};
 // ---- the unfused transfers: linear, tensor, axis or CSR ----------------------------------------
-// f_{l+1} = R r_l (:281-282).  zero_coarse_u: also u_{l+1} = 0 (:278) -- when the smoother starts
+// f_{l+1} = R r_l (:281-282).  uH (zero_coarse_u): also u_{l+1} = 0 there (:278) -- when the smoother starts
 // from "u == 0" without reading u, the fill itself is dead (u_{l+1} is fully overwritten before
 // anyone reads it)
-amg_hip_status enqueue_restrict(amg_hip_solver* s, int l, bool zero_coarse_u) {
+amg_hip_status enqueue_restrict(StepCtx& X, amg_hip_solver* s, int l, double* uH) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
-  hipStream_t st = s->stream;
-  double* uH = zero_coarse_u ? C.u.as<double>() : nullptr;
+  hipStream_t st = X.st;
+  const bool zero_coarse_u = uH != nullptr;
   if (L.linear && s->opt.stencil_transfers) {
     HIP_TRY(launch_linear_restrict(L.n, C.n, L.r.as<double>(), C.f.as<double>(), uH, st));
-    s->acct(8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
+    X.count(8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
   } else if (L.tensor_stencil) {                               // the same two steps, full coarsening
     HIP_TRY(launch_tensor_restrict(L.tdim, L.dims, L.tmask, L.tsides, L.tper, L.r.as<double>(), C.f.as<double>(), uH, st));
-    s->acct(8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
+    X.count(8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
   } else if (L.axis_stencil) {                                 // the same two steps, one axis, weights of A_l
     HIP_TRY(launch_axis_restrict(L.tdim, L.dims, L.axis, L.axis_periodic(), L.axis_W_dev.as<double>(), L.r.as<double>(),
                                  C.f.as<double>(), uH, st));
-    s->acct(8.0 * L.n + 16.0 * (L.n - C.n) + (zero_coarse_u ? 16.0 : 8.0) * C.n);
+    X.count(8.0 * L.n + 16.0 * (L.n - C.n) + (zero_coarse_u ? 16.0 : 8.0) * C.n);
   } else {
-    if (zero_coarse_u) HIP_TRY(hipMemsetAsync(C.u.p, 0, sizeof(double) * C.n, st));  // :278
+    if (zero_coarse_u) HIP_TRY(hipMemsetAsync(uH, 0, sizeof(double) * C.n, st));  // :278
     const DevCsr& R = L.R_rows;
     HIP_TRY(launch_csr(CSR_SPMV, R.n_rows, R.nnz, R.max_block_nnz, R.max_row_nnz,
                        R.rowptr(), R.col(), R.v(), L.r.as<double>(), nullptr,
                        C.f.as<double>(), 1.0, 0, st));
-    s->acct(12.0 * R.nnz + 4.0 * C.n + 8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
+    X.count(12.0 * R.nnz + 4.0 * C.n + 8.0 * L.n + (zero_coarse_u ? 16.0 : 8.0) * C.n);
   }
   return AMG_HIP_OK;
 }
-// out = u_l + P u_{l+1} (:294-296); out is u_l itself, or (linear transfers only) the level's tmp
-amg_hip_status enqueue_prolong_add(amg_hip_solver* s, int l, double* out) {
+// out = u + P uH (:294-296), u and uH the iterates of levels l and l+1; out is u itself, or (linear
+// transfers only) the level's other buffer
+amg_hip_status enqueue_prolong_add(StepCtx& X, amg_hip_solver* s, int l, const double* uH, double* u, double* out) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
-  hipStream_t st = s->stream;
+  hipStream_t st = X.st;
   if (L.linear && s->opt.stencil_transfers) {
-    if (out != L.u.as<double>())
-      HIP_TRY(launch_linear_prolong_to(L.n, C.n, C.u.as<double>(), L.u.as<double>(), out, st));
+    if (out != u)
+      HIP_TRY(launch_linear_prolong_to(L.n, C.n, uH, u, out, st));
     else
-      HIP_TRY(launch_linear_prolong_add(L.n, C.n, C.u.as<double>(), L.u.as<double>(), st));
-    s->acct(8.0 * C.n + 16.0 * L.n);
+      HIP_TRY(launch_linear_prolong_add(L.n, C.n, uH, u, st));
+    X.count(8.0 * C.n + 16.0 * L.n);
   } else if (L.tensor_stencil) {
-    HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, C.u.as<double>(), L.u.as<double>(), st));
-    s->acct(8.0 * C.n + 16.0 * L.n);
+    HIP_TRY(launch_tensor_prolong_add(L.tdim, L.dims, L.tmask, L.tsides, L.tper, uH, u, st));
+    X.count(8.0 * C.n + 16.0 * L.n);
   } else if (L.axis_stencil) {
-    HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_periodic(), L.axis_W_dev.as<double>(), C.u.as<double>(),
-                                    L.u.as<double>(), st));
-    s->acct(16.0 * L.n + 16.0 * (L.n - C.n) + 8.0 * C.n);
+    HIP_TRY(launch_axis_prolong_add(L.tdim, L.dims, L.axis, L.axis_periodic(), L.axis_W_dev.as<double>(), uH, u, st));
+    X.count(16.0 * L.n + 16.0 * (L.n - C.n) + 8.0 * C.n);
   } else {
     const DevCsr& P = L.P_rows;  // u_h = u_h + P u_H in one launch
     HIP_TRY(launch_csr(CSR_SPMV_ADD, P.n_rows, P.nnz, P.max_block_nnz, P.max_row_nnz,
-                       P.rowptr(), P.col(), P.v(), C.u.as<double>(), L.u.as<double>(),
-                       L.u.as<double>(), 1.0, 0, st));
-    s->acct(12.0 * P.nnz + 4.0 * L.n + 8.0 * C.n + 16.0 * L.n);
+                       P.rowptr(), P.col(), P.v(), uH, u, u, 1.0, 0, st));
+    X.count(12.0 * P.nnz + 4.0 * L.n + 8.0 * C.n + 16.0 * L.n);
   }
   return AMG_HIP_OK;
 }
@@ -2548,7 +2572,7 @@ double patch_range_frac(const Level& L, bool ranged, int64_t lo, int64_t hi) {
   return std::min(1.0, (double)(hi - lo) / lines);
 }
 // :268 (the colour stages of the symmetric passes) + :272-282
-amg_hip_status down_mc_patch(amg_hip_solver* s, int l) {
+amg_hip_status down_mc_patch(CycleCtx& X, amg_hip_solver* s, int l) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
   const DevMat& A = L.A_rows;
@@ -2559,14 +2583,14 @@ amg_hip_status down_mc_patch(amg_hip_solver* s, int l) {
     HIP_TRY(launch_patch_rb(false, M.tail, L.n, A.patch_m, A.patch_ref(), M.in, L.f.as<double>(), nullptr, C.n,
                             M.out, (M.tail && s->opt.keep_residual) ? L.r.as<double>() : nullptr,
                             M.tail ? C.f.as<double>() : nullptr, M.tail ? C.u.as<double>() : nullptr, M.stages,
-                            (uint32_t)L.mc_ctab, s->stream));
+                            (uint32_t)L.mc_ctab, X.st));
   }
   // each launch: row types + x + f + out; the last also f_H, zeroed u_H (and r when kept)
-  s->acct(nd * 25.0 * L.n + 16.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
+  X.count(nd * 25.0 * L.n + 16.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
   return AMG_HIP_OK;
 }
 // :294-296 + :300 (the colour stages of the symmetric passes)
-amg_hip_status up_mc_patch(amg_hip_solver* s, int l) {
+amg_hip_status up_mc_patch(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
   const DevMat& A = L.A_rows;
@@ -2575,14 +2599,14 @@ amg_hip_status up_mc_patch(amg_hip_solver* s, int l) {
   for (size_t q = (size_t)nd; q < plan.size(); ++q) {
     const McLaunch& M = plan[q];
     HIP_TRY(launch_patch_rb(M.prolong, false, L.n, A.patch_m, A.patch_ref(), M.in, L.f.as<double>(),
-                            M.prolong ? C.u.as<double>() : nullptr, C.n, M.out, nullptr, nullptr, nullptr,
-                            M.stages, (uint32_t)L.mc_ctab, s->stream));
+                            M.prolong ? after_up(s, P, l + 1) : nullptr, C.n, M.out, nullptr, nullptr, nullptr,
+                            M.stages, (uint32_t)L.mc_ctab, X.st));
   }
-  s->acct((double)(plan.size() - (size_t)nd) * 25.0 * L.n + 8.0 * C.n);
+  X.count((double)(plan.size() - (size_t)nd) * 25.0 * L.n + 8.0 * C.n);
   return AMG_HIP_OK;
 }
 // :268 + :272-282 of a narrow level, one launch: u -> tmp
-amg_hip_status down_mc_strip(amg_hip_solver* s, int l) {
+amg_hip_status down_mc_strip(CycleCtx& X, amg_hip_solver* s, int l) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
   StripRef R = mc_strip_ref(s, l);
@@ -2591,45 +2615,45 @@ amg_hip_status down_mc_strip(amg_hip_solver* s, int l) {
   R.r_out = s->opt.keep_residual ? L.r.as<double>() : nullptr;
   R.fH = C.f.as<double>();
   R.uH_zero = C.u.as<double>();
-  HIP_TRY(launch_mc_strip(false, true, R, L.A_rows.dict_ref(), s->stream));
+  HIP_TRY(launch_mc_strip(false, true, R, L.A_rows.dict_ref(), X.st));
   // row types + colours + x + f + out; f_H, zeroed u_H (and r when kept)
-  s->acct(26.0 * L.n + 16.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
+  X.count(26.0 * L.n + 16.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
   return AMG_HIP_OK;
 }
 // :294-296 + :300 of a narrow level, one launch: tmp + P u_H -> u
-amg_hip_status up_mc_strip(amg_hip_solver* s, int l) {
+amg_hip_status up_mc_strip(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
   StripRef R = mc_strip_ref(s, l);
   R.x = L.tmp.as<double>();
   R.u_out = L.u.as<double>();
-  R.uH = C.u.as<double>();
-  HIP_TRY(launch_mc_strip(true, false, R, L.A_rows.dict_ref(), s->stream));
-  s->acct(26.0 * L.n + 8.0 * C.n);
+  R.uH = after_up(s, P, l + 1);
+  HIP_TRY(launch_mc_strip(true, false, R, L.A_rows.dict_ref(), X.st));
+  X.count(26.0 * L.n + 8.0 * C.n);
   return AMG_HIP_OK;
 }
 // :268 (both sweeps) + :272-282 + :268 of l+1, one launch
-amg_hip_status down_patch(amg_hip_solver* s, const CyclePlan& P, int l) {
+amg_hip_status down_patch(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
   const DevMat& A = L.A_rows;
-  hipStream_t st = s->stream;
-  if (l == 0 && s->seam_piece == SEAM_CYCLE) {  // up-leg of the last cycle + this down-leg: one launch
-    HIP_TRY(launch_patch_seam(L.n, A.patch_m, A.patch_ref(5), seam_buf(s, s->seam_src), L.f.as<double>(),
-                              C.tmp.as<double>(), C.n, seam_buf(s, 1 - s->seam_src), C.f.as<double>(),
+  hipStream_t st = X.st;
+  if (l == 0 && X.piece == SEAM_CYCLE) {  // up-leg of the last cycle + this down-leg: one launch
+    HIP_TRY(launch_patch_seam(L.n, A.patch_m, A.patch_ref(5), seam_buf(s, X.src), L.f.as<double>(),
+                              C.tmp.as<double>(), C.n, seam_buf(s, 1 - X.src), C.f.as<double>(),
                               s->opt.omega, st));
-    s->acct(25.0 * L.n + 16.0 * C.n);  // row types + x + f + smoothed u; u_H, f_H
+    X.count(25.0 * L.n + 16.0 * C.n);  // row types + x + f + smoothed u; u_H, f_H
     return AMG_HIP_OK;
   }
   const Slab& sb = s->slab;
-  const bool ranged = P.part == CYCLE_SLAB_DOWN;
+  const bool ranged = X.part == CYCLE_SLAB_DOWN;
   const bool first = l == 0;  // l >= 1: the first sweep came from level l-1's kernel (in tmp) ...
   const bool xf_in = P.lv[(size_t)l].xf_in;    // ... or is formed from f here
   const bool xf_out = P.lv[(size_t)l].xf_out;  // level l+1 forms its own: f_H only
   HIP_TRY(launch_patch_down(first, L.n, A.patch_m, A.patch_ref(patch_rings(s, first)),
                             first ? L.u.as<double>() : (xf_in ? nullptr : L.tmp.as<double>()),
                             L.f.as<double>(),
-                            first ? (s->seam_piece == SEAM_HEAD ? seam_buf(s, s->seam_src) : L.tmp.as<double>())
+                            first ? (X.piece == SEAM_HEAD ? seam_buf(s, X.src) : L.tmp.as<double>())
                                   : L.u.as<double>(),
                             s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
                             C.f.as<double>(), C.diag.as<double>(), xf_out ? nullptr : C.tmp.as<double>(),
@@ -2637,30 +2661,30 @@ amg_hip_status down_patch(amg_hip_solver* s, const CyclePlan& P, int l) {
                             ranged ? sb.down_hi[l] : -1, xf_in));
   // row types + [x +] f + smoothed u; f_H [, first coarse sweep, coarse diagonal]
   // (the coarse diagonal is not read under the tiles that take it as an argument)
-  s->acct(patch_range_frac(L, ranged, ranged ? sb.down_lo[l] : 0, ranged ? sb.down_hi[l] : -1) *
+  X.count(patch_range_frac(L, ranged, ranged ? sb.down_lo[l] : 0, ranged ? sb.down_hi[l] : -1) *
           ((xf_in ? 17.0 : 25.0) * L.n + (xf_out ? 8.0 : 24.0 - 8.0 * A.patch_cfrac) * C.n +
            (s->opt.keep_residual ? 8.0 * L.n : 0.0)));
   return AMG_HIP_OK;
 }
 // :294-296 + :300 (both sweeps), one launch
-amg_hip_status up_patch(amg_hip_solver* s, const CyclePlan& P, int l) {
+amg_hip_status up_patch(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
   const DevMat& A = L.A_rows;
   const Slab& sb = s->slab;
-  const bool ranged = P.part == CYCLE_SLAB_UP;
+  const bool ranged = X.part == CYCLE_SLAB_UP;
   const bool top = l == 0;  // level 0 rests in u (its down-leg wrote tmp); coarser patch levels end in tmp
   HIP_TRY(launch_patch_up(L.n, A.patch_m, A.patch_ref(patch_rings(s, false)),
                           top ? L.tmp.as<double>() : L.u.as<double>(), L.f.as<double>(),
-                          resting(s, P, l + 1).as<double>(), C.n,
-                          top ? L.u.as<double>() : L.tmp.as<double>(), s->opt.omega, s->stream,
+                          after_up(s, P, l + 1), C.n,
+                          top ? L.u.as<double>() : L.tmp.as<double>(), s->opt.omega, X.st,
                           ranged ? sb.up_lo[l] : 0, ranged ? sb.up_hi[l] : -1));
   // row types + x + f + out; u_H
-  s->acct(patch_range_frac(L, ranged, ranged ? sb.up_lo[l] : 0, ranged ? sb.up_hi[l] : -1) * (25.0 * L.n + 8.0 * C.n));
+  X.count(patch_range_frac(L, ranged, ranged ? sb.up_lo[l] : 0, ranged ? sb.up_hi[l] : -1) * (25.0 * L.n + 8.0 * C.n));
   return AMG_HIP_OK;
 }
 // K-Tail: levels l .. L-2, the solve and the way back: ONE launch
-amg_hip_status enqueue_tail(amg_hip_solver* s, const CyclePlan& P, int l) {
+amg_hip_status enqueue_tail(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   const int nl = (int)s->lv.size();
   TailRef T;
   std::memset(&T, 0, sizeof(T));
@@ -2694,20 +2718,20 @@ amg_hip_status enqueue_tail(amg_hip_solver* s, const CyclePlan& P, int l) {
   T.diagc = C.diag.as<double>();
   Level& F = s->lv[l - 1];
   T.n_fine = (int)F.n;
-  T.uf_in = F.u.as<double>();
+  T.uf_in = between_legs(s, P, l - 1).u;
   T.uf_out = up_target(s, P, l - 1);
   T.omega = s->opt.omega;
-  HIP_TRY(launch_tail(T, s->stream));
+  HIP_TRY(launch_tail(T, X.st));
   for (int q = 0; q < T.nlev; ++q) {  // what the pair kernels of these levels would have moved
     const Level& Q = s->lv[l + q];
     const double nH = (double)s->lv[l + q + 1].n, nF = (double)s->lv[l + q - 1].n;
-    s->acct(2.0 * (mat_bytes(Q.A_rows) + 24.0 * Q.n) + 24.0 * nH + 16.0 * nF);
+    X.count(2.0 * (mat_bytes(Q.A_rows) + 24.0 * Q.n) + 24.0 * nH + 16.0 * nF);
   }
-  s->acct(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
+  X.count(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
   return AMG_HIP_OK;
 }
 // K-Duo, down: the pair launches of levels l and l+1 in one
-amg_hip_status down_duo(amg_hip_solver* s, int l) {
+amg_hip_status down_duo(CycleCtx& X, amg_hip_solver* s, int l) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
   Level& CC = s->lv[l + 2];
@@ -2718,15 +2742,15 @@ amg_hip_status down_duo(amg_hip_solver* s, int l) {
                                L.tmp.as<double>(), L.f.as<double>(), L.u.as<double>(),
                                keep ? L.r.as<double>() : nullptr, C.f.as<double>(), C.diag.as<double>(),
                                C.u.as<double>(), keep ? C.r.as<double>() : nullptr, CC.n, CC.f.as<double>(),
-                               CC.diag.as<double>(), CC.tmp.as<double>(), s->opt.omega, s->stream));
+                               CC.diag.as<double>(), CC.tmp.as<double>(), s->opt.omega, X.st));
   // what the pair launches of the two levels would have moved
-  s->acct(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (keep ? 8.0 * L.n : 0.0));
-  s->acct(mat_bytes(AC) + 24.0 * C.n + 24.0 * CC.n + (keep ? 8.0 * C.n : 0.0));
+  X.count(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (keep ? 8.0 * L.n : 0.0));
+  X.count(mat_bytes(AC) + 24.0 * C.n + 24.0 * CC.n + (keep ? 8.0 * C.n : 0.0));
   return AMG_HIP_OK;
 }
 // K-Duo, up (l: the coarser level): :300 of levels l and l-1 and the prolongations between and after
 // them in one launch; level l-1 ends in tmp
-amg_hip_status up_duo(amg_hip_solver* s, const CyclePlan& P, int l) {
+amg_hip_status up_duo(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   Level& L = s->lv[l];
   Level& F = s->lv[l - 1];
   Level& FF = s->lv[l - 2];
@@ -2734,15 +2758,15 @@ amg_hip_status up_duo(amg_hip_solver* s, const CyclePlan& P, int l) {
   const DevMat& AF = F.A_cols();
   HIP_TRY(launch_dict_duo_up(AF.n_rows, AF.dict_ref(), AF.dict_hb, A.n_rows, A.dict_ref(), A.dict_hb,
                              L.tmp.as<double>(), L.f.as<double>(), L.u.as<double>(), F.u.as<double>(),
-                             F.f.as<double>(), F.tmp.as<double>(), s->opt.omega, FF.n, FF.u.as<double>(),
-                             up_target(s, P, l - 2), s->stream));
+                             F.f.as<double>(), F.tmp.as<double>(), s->opt.omega, FF.n, between_legs(s, P, l - 2).u,
+                             up_target(s, P, l - 2), X.st));
   // what the pair launches of the two levels would have moved
-  s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
-  s->acct(mat_bytes(AF) + 24.0 * F.n + 16.0 * FF.n);
+  X.count(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
+  X.count(mat_bytes(AF) + 24.0 * F.n + 16.0 * FF.n);
   return AMG_HIP_OK;
 }
 // second pre-sweep + residual + restriction + :268 of l+1
-amg_hip_status down_pair(amg_hip_solver* s, int l) {
+amg_hip_status down_pair(CycleCtx& X, amg_hip_solver* s, int l) {
   Level& L = s->lv[l];
   Level& C = s->lv[l + 1];
   const DevMat& A = L.A_rows;
@@ -2750,63 +2774,70 @@ amg_hip_status down_pair(amg_hip_solver* s, int l) {
                                 L.f.as<double>(), L.u.as<double>(),
                                 s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
                                 C.f.as<double>(), C.diag.as<double>(), C.tmp.as<double>(),
-                                s->opt.omega, s->stream));
-  s->acct(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
+                                s->opt.omega, X.st));
+  X.count(mat_bytes(A) + 24.0 * L.n + 24.0 * C.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0));
   return AMG_HIP_OK;
 }
 // :300, both sweeps; the second prolongs into level l-1
-amg_hip_status up_pair(amg_hip_solver* s, const CyclePlan& P, int l) {
+amg_hip_status up_pair(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   Level& L = s->lv[l];
   Level& F = s->lv[l - 1];
   const DevMat& A = L.A_cols();
   HIP_TRY(launch_dict_pair_up(A.n_rows, A.dict_ref(), A.dict_hb, L.tmp.as<double>(),
                               L.f.as<double>(), L.u.as<double>(), s->opt.omega, F.n,
-                              F.u.as<double>(), up_target(s, P, l - 1), s->stream));
-  s->acct(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
+                              between_legs(s, P, l - 1).u, up_target(s, P, l - 1), X.st));
+  X.count(mat_bytes(A) + 24.0 * L.n + 16.0 * F.n);
   return AMG_HIP_OK;
 }
 // :268, then :272-282 (+ :268 of l+1 when fused)
-amg_hip_status down_plain(amg_hip_solver* s, const CyclePlan& P, int l) {
+amg_hip_status down_plain(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   const LevelPlan& Q = P.lv[(size_t)l];
-  AMG_TRY(enqueue_smooth(s, l, Q.phase, -1, nullptr, false, Q.march));  // :268
+  AMG_TRY(enqueue_smooth(X, s, l, level_vecs(s->lv[l], false), Sweep{Q.phase, Q.march_down}));  // :268
+  const double* u = between_legs(s, P, l).u;
   if (Q.restrict_fused) {                                                // :272-282 + :268 of l+1
     Level& L = s->lv[l];
     Level& C = s->lv[l + 1];
     const DevMat& A = L.A_rows;
     const bool zero_known = P.zero_known;
-    HIP_TRY(launch_dict_resid_restrict(A.n_rows, A.dict_ref(), L.u.as<double>(),
+    HIP_TRY(launch_dict_resid_restrict(A.n_rows, A.dict_ref(), u,
                                        L.f.as<double>(),
                                        s->opt.keep_residual ? L.r.as<double>() : nullptr, C.n,
                                        C.f.as<double>(),
                                        zero_known ? C.diag.as<double>() : nullptr,
                                        zero_known ? C.tmp.as<double>() : nullptr,
-                                       C.u.as<double>(), s->opt.omega, s->stream));
+                                       C.u.as<double>(), s->opt.omega, X.st));
     // matrix, u, f (r when kept); f_H and either the first coarse sweep + diagonal or the zeroed u_H
-    s->acct(mat_bytes(A) + 16.0 * L.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0) +
+    X.count(mat_bytes(A) + 16.0 * L.n + (s->opt.keep_residual ? 8.0 * L.n : 0.0) +
             (zero_known ? 24.0 : 16.0) * C.n);
     return AMG_HIP_OK;
   }
-  AMG_TRY(enqueue_residual(s, l));                                       // :272-274
-  if (l + 1 != (int)s->lv.size()) AMG_TRY(enqueue_restrict(s, l, !P.zero_known));  // :278 + :281-282
+  AMG_TRY(enqueue_residual(X, s, l, u));                                 // :272-274
+  if (l + 1 != (int)s->lv.size())                                        // :278 + :281-282
+    AMG_TRY(enqueue_restrict(X, s, l, P.zero_known ? nullptr : s->lv[l + 1].u.as<double>()));
   return AMG_HIP_OK;
 }
 // :300; the last sweep also prolongs into level l-1 when that fuses
-amg_hip_status up_plain(amg_hip_solver* s, const CyclePlan& P, int l) {
+amg_hip_status up_plain(CycleCtx& X, amg_hip_solver* s, const CyclePlan& P, int l) {
   const LevelPlan& Q = P.lv[(size_t)l];
-  const int into = (l >= 1 && P.lv[(size_t)l - 1].prolong == PROLONG_COARSER_SWEEP) ? l - 1 : -1;
-  double* out = into >= 0 ? up_target(s, P, into) : nullptr;
-  if (Q.prolong == PROLONG_OWN_SMOOTHER) return enqueue_smooth(s, l, 2, into, out);  // :294-296 inside :300
-  return enqueue_smooth(s, l, 0, into, out, true, Q.march);
+  Sweep w{Q.prolong == PROLONG_OWN_SMOOTHER ? 2 : 0, Q.march_up};  // 2: :294-296 inside :300
+  w.coarse_u = after_up(s, P, l + 1);
+  if (l >= 1 && P.lv[(size_t)l - 1].prolong == PROLONG_COARSER_SWEEP) {
+    w.fine_u = between_legs(s, P, l - 1).u;
+    w.fine_out = up_target(s, P, l - 1);
+  }
+  w.reverse = w.phase == 0;
+  return enqueue_smooth(X, s, l, between_legs(s, P, l), w);
 }
 
-// multigrid.hpp:263-305: two loops that dispatch on the plan.  The slab and window ranges (part) and
-// the seam pieces (s->seam_piece) are modes of this enqueue: they choose which levels it walks.
-amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
+// multigrid.hpp:263-305: two loops that dispatch on the plan.  The slab and window ranges (X.part) and
+// the seam pieces (X.piece) choose which levels it walks.
+amg_hip_status enqueue_vcycle_body(CycleCtx& X, amg_hip_solver* s) {
   const int nl = (int)s->lv.size();
-  hipStream_t st = s->stream;
+  hipStream_t st = X.st;
   const int k = s->slab.levels;
+  const int part = X.part;
   const bool ranged = part == CYCLE_SLAB_DOWN || part == CYCLE_SLAB_UP;
-  const CyclePlan P = build_cycle_plan(s, part);
+  const CyclePlan P = build_cycle_plan(s, part, X.piece);
   if (!ranged) {
     s->plan = P;
     s->plan_kept = true;
@@ -2815,12 +2846,12 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
     Level& L = s->lv[k];
     HIP_TRY(launch_jacobi_from_zero(L.n, L.diag.as<double>(), L.f.as<double>(), L.tmp.as<double>(),
                                     s->opt.omega, st));
-    s->acct(24.0 * L.n);
+    X.count(24.0 * L.n);
   }
   // the seam sequence (part == CYCLE_ALL): head = the cycle without the level-0 up-leg, its level-0
   // down-leg writing seam_buf(src); seam cycle = the seam launch from seam_buf(src) into the other
   // buffer, then levels 1 .. L-1 as in the cycle; finish = the level-0 up-leg alone, from tmp
-  const int piece = s->seam_piece;
+  const int piece = X.piece;
   const int down_from = part == CYCLE_SLAB_TAIL ? k : 0;
   const int down_to = part == CYCLE_SLAB_DOWN ? k : ((part == CYCLE_SLAB_UP || piece == SEAM_FINISH) ? 0 : nl);
   for (int l = down_from; l < down_to; ++l) {
@@ -2828,13 +2859,13 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
     if (form == LEG_NONE || form == LEG_IN_TAIL || form == LEG_DUO_COARSE) continue;  // no launch of its own
     RoctxRange range("down", l);
     switch (form) {
-      case LEG_MC_PATCH: AMG_TRY(down_mc_patch(s, l)); break;
-      case LEG_MC_STRIP: AMG_TRY(down_mc_strip(s, l)); break;
-      case LEG_PATCH: AMG_TRY(down_patch(s, P, l)); break;
-      case LEG_TAIL_HEAD: AMG_TRY(enqueue_tail(s, P, l)); break;
-      case LEG_DUO_FINE: AMG_TRY(down_duo(s, l)); break;
-      case LEG_PAIR: AMG_TRY(down_pair(s, l)); break;
-      default: AMG_TRY(down_plain(s, P, l)); break;
+      case LEG_MC_PATCH: AMG_TRY(down_mc_patch(X, s, l)); break;
+      case LEG_MC_STRIP: AMG_TRY(down_mc_strip(X, s, l)); break;
+      case LEG_PATCH: AMG_TRY(down_patch(X, s, P, l)); break;
+      case LEG_TAIL_HEAD: AMG_TRY(enqueue_tail(X, s, P, l)); break;
+      case LEG_DUO_FINE: AMG_TRY(down_duo(X, s, l)); break;
+      case LEG_PAIR: AMG_TRY(down_pair(X, s, l)); break;
+      default: AMG_TRY(down_plain(X, s, P, l)); break;
     }
   }
   const bool tail_done = P.tail_first >= 0 && down_to == nl;
@@ -2843,17 +2874,18 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
     if (s->opt.window)
       return fail(AMG_HIP_EINVAL, "a window solver (opt.window) runs by parts: amg_hip_window_run");
     Level& C = s->lv[nl - 1];
+    const LevelVecs vc = between_legs(s, P, nl - 1);
     const int lp = nl - 2;  // plain stencil prolongation into level L-2: one launch less when fused
     if (lp >= 0 && P.lv[(size_t)lp].prolong == PROLONG_SOLVE) {
       Level& Lp = s->lv[lp];
-      HIP_TRY(launch_coarse(s->coarse, C.f.as<double>(), C.tmp.as<double>(), C.u.as<double>(), st, Lp.n,
-                            Lp.u.as<double>(), up_target(s, P, lp)));
-      s->acct(16.0 * Lp.n);
+      HIP_TRY(launch_coarse(s->coarse, C.f.as<double>(), vc.tmp, vc.u, st, Lp.n, between_legs(s, P, lp).u,
+                            up_target(s, P, lp)));
+      X.count(16.0 * Lp.n);
     } else {
-      HIP_TRY(launch_coarse(s->coarse, C.f.as<double>(), C.tmp.as<double>(), C.u.as<double>(), st));
+      HIP_TRY(launch_coarse(s->coarse, C.f.as<double>(), vc.tmp, vc.u, st));
     }
     // banded L D L^T solve: the band of L forwards and backwards, D, f, u
-    s->acct(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
+    X.count(16.0 * (double)C.n * (double)std::max<int64_t>(s->coarse.w, 1) + 24.0 * C.n);
   }
   const int up_from = piece == SEAM_FINISH ? 0 : (part == CYCLE_SLAB_UP ? k - 1 : (part == CYCLE_SLAB_DOWN ? -1 : (tail_done ? P.tail_first - 1 : nl - 2)));
   const int up_to = part == CYCLE_SLAB_TAIL ? k : ((piece == SEAM_HEAD || piece == SEAM_CYCLE) ? 1 : 0);
@@ -2861,34 +2893,41 @@ amg_hip_status enqueue_vcycle_body(amg_hip_solver* s, int part) {
     const LevelPlan& Q = P.lv[(size_t)l];
     if (Q.up == LEG_DUO_FINE) continue;  // done by the launch of level l+1
     RoctxRange range("up", l);
-    if (Q.prolong == PROLONG_TRANSFER) AMG_TRY(enqueue_prolong_add(s, l, up_target(s, P, l)));  // :294-296
+    if (Q.prolong == PROLONG_TRANSFER)                             // :294-296
+      AMG_TRY(enqueue_prolong_add(X, s, l, after_up(s, P, l + 1), between_legs(s, P, l).u, up_target(s, P, l)));
     switch (Q.up) {
-      case LEG_MC_PATCH: AMG_TRY(up_mc_patch(s, l)); break;
-      case LEG_MC_STRIP: AMG_TRY(up_mc_strip(s, l)); break;
-      case LEG_PATCH: AMG_TRY(up_patch(s, P, l)); break;
-      case LEG_DUO_COARSE: AMG_TRY(up_duo(s, P, l)); break;
-      case LEG_PAIR: AMG_TRY(up_pair(s, P, l)); break;
-      default: AMG_TRY(up_plain(s, P, l)); break;
+      case LEG_MC_PATCH: AMG_TRY(up_mc_patch(X, s, P, l)); break;
+      case LEG_MC_STRIP: AMG_TRY(up_mc_strip(X, s, P, l)); break;
+      case LEG_PATCH: AMG_TRY(up_patch(X, s, P, l)); break;
+      case LEG_DUO_COARSE: AMG_TRY(up_duo(X, s, P, l)); break;
+      case LEG_PAIR: AMG_TRY(up_pair(X, s, P, l)); break;
+      default: AMG_TRY(up_plain(X, s, P, l)); break;
     }
+  }
+  // a level K-March swept on one leg only ends the cycle with its solution in tmp: it goes home
+  for (int l = 0; l < nl; ++l) {
+    const Level& L = s->lv[l];
+    if (!P.lv[(size_t)l].home_copy()) continue;
+    HIP_TRY(hipMemcpyAsync(L.u.p, L.tmp.p, sizeof(double) * L.n, hipMemcpyDeviceToDevice, st));
+    X.count(16.0 * L.n);
   }
   return AMG_HIP_OK;
 }
+// the cycle (or part, or seam piece) on the solver's stream; its bytes go to must_move when it is enqueued
+amg_hip_status enqueue_vcycle(amg_hip_solver* s, int part = CYCLE_ALL, int piece = SEAM_OFF, int src = 0) {
+  CycleCtx X{{s->stream}, part, piece, src};
+  const amg_hip_status r = enqueue_vcycle_body(X, s);
+  // (the pieces of the seam sequence count apart: [0] stays the stand-alone cycle)
+  s->must_move[piece == SEAM_CYCLE ? 4 : (piece != SEAM_OFF ? 5 : part)] = X.once;
+  return r;
+}
 
 // One piece of the seam sequence (SEAM_HEAD / SEAM_CYCLE with the buffer src it hands over in, or
-// SEAM_FINISH), enqueued or replayed from its graph, captured on first use.  The piece is a mode of
-// enqueue_vcycle for the length of this call only: no vector changes its role, so a failure anywhere
-// leaves the solver as a stand-alone cycle expects it.
-amg_hip_status run_seam_piece(amg_hip_solver* s, int piece, int src) {
-  auto enqueue = [s, piece, src] {
-    s->seam_piece = piece;
-    s->seam_src = src;
-    const amg_hip_status r = enqueue_vcycle(s);
-    s->seam_piece = SEAM_OFF;
-    s->seam_src = 0;
-    return r;
-  };
+// SEAM_FINISH), enqueued or replayed from its graph, captured on first use.
+amg_hip_status run_seam(amg_hip_solver* s, int piece, int src) {
   const int gi = piece == SEAM_FINISH ? 4 : (piece == SEAM_HEAD ? 0 : 2) + src;
-  return replay_or_enqueue(s->opt.use_graph, s->seam_graph[gi], s->stream, enqueue);
+  return replay_or_enqueue(s->opt.use_graph, s->seam_graph[gi], s->stream,
+                           [s, piece, src] { return enqueue_vcycle(s, CYCLE_ALL, piece, src); });
 }
 
 amg_hip_status set_device(const amg_hip_solver* s) {
@@ -4385,18 +4424,6 @@ amg_hip_status ensure_block(amg_hip_solver* s, int kp) {
   return AMG_HIP_OK;
 }
 
-// What a step of the block or the float cycle enqueues on, and the bytes its launches have to move.
-// launch = false is the dry run of amg_hip_block_must_move / amg_hip_f32_must_move: count, launch nothing.
-struct StepCtx {
-  hipStream_t st = nullptr;
-  bool launch = true;
-  double once = 0;     // bytes moved once per launch (the float cycle counts all of its bytes here)
-  double per_col = 0;  // bytes per column of a block panel: k columns have to move once + k * per_col
-  void count(double o, double c = 0.0) {
-    once += o;
-    per_col += c;
-  }
-};
 #define STEP_TRY(X, expr)            \
   do {                               \
     if ((X).launch) HIP_TRY(expr);   \
@@ -5519,10 +5546,10 @@ amg_hip_status amg_hip_vcycles(amg_hip_solver* s, int32_t n) {
     // the head starts on the buffer that makes the last seam cycle write tmp, where a stand-alone
     // cycle leaves that vector, so the finish is the cycle's own last launch.
     int src = (n - 1) & 1;
-    if ((r = run_seam_piece(s, SEAM_HEAD, src)) != AMG_HIP_OK) return r;
+    if ((r = run_seam(s, SEAM_HEAD, src)) != AMG_HIP_OK) return r;
     for (int i = 1; i < n; ++i, src ^= 1)
-      if ((r = run_seam_piece(s, SEAM_CYCLE, src)) != AMG_HIP_OK) return r;
-    return run_seam_piece(s, SEAM_FINISH, 0);
+      if ((r = run_seam(s, SEAM_CYCLE, src)) != AMG_HIP_OK) return r;
+    return run_seam(s, SEAM_FINISH, 0);
   }
   return replay_or_enqueue(s->opt.use_graph, s->graph, s->stream, [s] { return enqueue_vcycle(s); }, n);
 }
@@ -5737,31 +5764,9 @@ amg_hip_status amg_hip_get_stream(amg_hip_solver* s, void** stream) {
 static DevMem* level_vec(amg_hip_solver* s, int32_t level, int32_t which) {
   if (!s || level < 0 || level >= (int32_t)s->lv.size()) return nullptr;
   Level& L = s->lv[level];
-  if (which == 0) return &resting(s, current_plan(s), level);
+  if (which == 0) return current_plan(s).lv[(size_t)level].rests_tmp ? &L.tmp : &L.u;
   return which == 1 ? &L.f : (which == 2 ? &L.r : nullptr);
 }
-// For the length of one level operation a level that rests in tmp (this one, the coarser one) trades
-// its two buffers, so that the operation reads the solution where set_vec put it and leaves it where
-// get_vec looks for it.
-struct DuoView {
-  Level* lv[2] = {nullptr, nullptr};
-  DuoView(amg_hip_solver* s, int level) {
-    const int nl = (int)s->lv.size();
-    const CyclePlan P = current_plan(s);  // asked before any trade
-    for (int q = 0; q < 2; ++q)
-      if (level + q < nl && P.lv[(size_t)level + q].rests_tmp) {
-        lv[q] = &s->lv[level + q];
-        std::swap(lv[q]->u, lv[q]->tmp);
-      }
-  }
-  ~DuoView() {
-    for (Level* L : lv)
-      if (L) std::swap(L->u, L->tmp);
-  }
-  DuoView(const DuoView&) = delete;
-  DuoView& operator=(const DuoView&) = delete;
-};
-
 amg_hip_status amg_hip_vec_dev_ptr(amg_hip_solver* s, int32_t level, int32_t which, void** ptr, int64_t* n) {
   if (!s || !ptr || level < 0 || level >= (int32_t)s->lv.size() || which < 0 || which > 2)
     return fail(AMG_HIP_EINVAL, "bad argument");
@@ -5812,21 +5817,19 @@ amg_hip_status amg_hip_level_op(amg_hip_solver* s, int32_t level, int32_t op) {
   if (level < 0 || level >= nl) return fail(AMG_HIP_EINVAL, "level out of range");
   amg_hip_status r = set_device(s);
   if (r != AMG_HIP_OK) return r;
-  hipStream_t st = s->stream;
-  Level& L = s->lv[level];
-  const DuoView view(s, level);  // this level and the coarser one, where their solution rests in tmp
+  // on the solution where it rests (set_vec put it there, get_vec looks there); the bytes counted are dropped
+  StepCtx X{s->stream};
+  const CyclePlan P = current_plan(s);
+  const LevelVecs v = resting(s, P, level);
+  if ((op == 2 || op == 3) && level + 1 >= nl) return fail(AMG_HIP_EINVAL, "no coarser level");
   switch (op) {
-    case 0: return enqueue_smooth(s, level, 0);
-    case 1: return enqueue_residual(s, level);
-    case 2:
-      if (level + 1 >= nl) return fail(AMG_HIP_EINVAL, "no coarser level");
-      return enqueue_restrict(s, level, true);
-    case 3:
-      if (level + 1 >= nl) return fail(AMG_HIP_EINVAL, "no coarser level");
-      return enqueue_prolong_add(s, level, L.u.as<double>());
+    case 0: return enqueue_smooth(X, s, level, v);
+    case 1: return enqueue_residual(X, s, level, v.u);
+    case 2: return enqueue_restrict(X, s, level, resting(s, P, level + 1).u);
+    case 3: return enqueue_prolong_add(X, s, level, resting(s, P, level + 1).u, v.u, v.u);
     case 4:
       if (level != nl - 1) return fail(AMG_HIP_EINVAL, "the direct solve belongs to the coarsest level");
-      HIP_TRY(launch_coarse(s->coarse, L.f.as<double>(), L.tmp.as<double>(), L.u.as<double>(), st));
+      HIP_TRY(launch_coarse(s->coarse, s->lv[level].f.as<double>(), v.tmp, v.u, X.st));
       return AMG_HIP_OK;
   }
   return fail(AMG_HIP_EINVAL, "unknown level operation");
@@ -6417,8 +6420,8 @@ amg_hip_status amg_hip_profile_fine_sweep(amg_hip_solver* s, int32_t n_launches,
   // rewrites f and tmp of level 1, which every V-cycle recomputes before use.
   const bool patch = form == LEG_PATCH;
   MarchRef MR;
-  const bool march = !mc && !patch && P.lv[0].march;
-  if (march) (void)march_fill(s, 0, &MR);
+  const bool march = P.lv[0].march_down;
+  if (march) (void)march_fill(s, 0, level_vecs(L, false), &MR);
   // slab-sharded solver: this rank's launch, i.e. its own lines + halo only
   const bool slab = patch && s->slab.levels > 0 && s->slab.world > 1;
   // (after the launches the multicolour colour kernels' u goes back)
@@ -6484,10 +6487,7 @@ amg_hip_status amg_hip_cycle_must_move(amg_hip_solver* s, int32_t part, double* 
       if (r != AMG_HIP_OK) return r;
       if (!s->opt.use_graph) return fail(AMG_HIP_EINVAL, "amg_hip_cycle_must_move: run two V-cycles in one call first");
       const int gi = 2;  // the seam cycle that reads tmp: captured, not run
-      s->seam_piece = SEAM_CYCLE;
-      s->seam_src = 0;
-      r = s->seam_graph[gi].capture(s->stream, [s] { return enqueue_vcycle(s); });
-      s->seam_piece = SEAM_OFF;
+      r = s->seam_graph[gi].capture(s->stream, [s] { return enqueue_vcycle(s, CYCLE_ALL, SEAM_CYCLE, 0); });
       if (r != AMG_HIP_OK) return r;
     }
     *bytes = s->must_move[4];
@@ -6646,7 +6646,7 @@ amg_hip_status amg_hip_fine_sweep_info(const amg_hip_solver* s, char* name, int3
       const int64_t l1 = std::min<int64_t>(s->slab.lines, (s->slab.down_hi[0] + th - 1) / th * th);
       bytes *= (double)(l1 - l0) / (double)s->slab.lines;
     }
-  } else if (Q.march) {
+  } else if (Q.march_down) {
     // both sweeps of the level in one pass: row types + x + f + out
     std::snprintf(name, (size_t)name_cap, "march_kernel");
     sweeps = 2;

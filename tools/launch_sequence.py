@@ -5,7 +5,8 @@ comparing two builds of the library.
   run one configuration (eager: use_graph=False), vcycle(1) then vcycle(3), and print cycle_must_move()
   of parts 0 and 4 as hexadecimal floats; a configuration with the "plain" switch then runs one
   block_vcycles on 3 columns (pitch 4) and one apply_f32, and prints block_must_move(3) and
-  f32_must_move() the same way:
+  f32_must_move() the same way; the configuration with the "slab" switch runs parts 1, 2 and 3 of the
+  slab-cut cycle twice instead (amg_hip_slab_run) and prints cycle_must_move() of parts 1 to 3:
       AMG_HIP_LIBRARY=<lib.so> rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- \
           python3 tools/launch_sequence.py --config <name>
   list the configurations:
@@ -61,6 +62,19 @@ def _configs():
         return amg.Multigrid(*op, G.rhs_for(n), G.levels_for(n), smoother=amg.SM_JACOBI, smoother_iters=2,
                              omega=0.6, layout=amg.LAYOUT_DICT, exact_coarse_solve=True, use_graph=False)
     cfg["march64x16x3"] = ({}, march)
+
+    def march_single():   # test_march_on_a_single_level_keeps_its_buffers: the down-leg alone, then the copy home
+        op = G.box3d(64, 16, 4)
+        n = op[0].size - 1
+        return amg.Multigrid(*op, G.rhs_for(n), 1, smoother=amg.SM_JACOBI, smoother_iters=2, omega=0.6,
+                             layout=amg.LAYOUT_DICT, keep_residual=True, exact_coarse_solve=True, use_graph=False)
+    cfg["march64x16x4_single"] = ({}, march_single)
+
+    def slab():           # tests/test_gpu_slab.py::test_slab_cycle_equals_single_gpu_cycle: rank 0 of 2, every slab level
+        mg = amg.Multigrid.poisson(1024, 9, smoother=amg.SM_JACOBI, smoother_iters=2, omega=0.6, use_graph=False)
+        mg.slab_setup(0, 2, -1)
+        return mg
+    cfg["slab1024_rank0of2"] = ({"patch_min_rows": 0, "slab": 1}, slab)
     # plain path, CSR transfers (tests/test_gpu_chebyshev.py) and tensor transfers (tests/test_gpu_line_alt.py)
     cfg["chebyshev_rs64"] = ({}, lambda: amg.Multigrid.ruge_stueben(
         *csc(O.laplacian(64)), O.rhs(64), 4, 0.25, 50, smoother=5, use_graph=False))
@@ -113,10 +127,15 @@ def run(name):
         amg.set_f32_dict(1)
     mg = make()
     try:
-        mg.vcycle(1)
-        mg.vcycle(3)
+        if "slab" in switches:   # the ranged down-legs, the replicated rest, the ranged up-legs
+            for _ in range(2):
+                for part in (1, 2, 3):
+                    mg.slab_run(part)
+        else:
+            mg.vcycle(1)
+            mg.vcycle(3)
         mg.sync()
-        for part in (0, 4):
+        for part in (1, 2, 3) if "slab" in switches else (0, 4):
             print(f"{name} cycle_must_move({part}) = {float(mg.cycle_must_move(part)).hex()}")
         if "plain" in switches:
             import numpy as np
@@ -168,7 +187,7 @@ def compare(dir_a, dir_b):
             with open(os.path.join(d, name + ".out")) as f:
                 outs.append([line.strip() for line in f if "_must_move" in line])
         same_seq = seqs[0] == seqs[1]
-        same_bytes = outs[0] == outs[1] and len(outs[0]) == (4 if name.startswith("plain_") else 2)
+        same_bytes = outs[0] == outs[1] and len(outs[0]) == (4 if name.startswith("plain_") else 3 if name.startswith("slab") else 2)
         verdicts.append((name, len(seqs[0]), len(seqs[1]), same_seq, same_bytes))
         body.append(f"### {name}\n")
         for tag, seq, out in zip("AB", seqs, outs):
@@ -179,7 +198,8 @@ def compare(dir_a, dir_b):
     print("`tools/launch_sequence.py`, one `rocprofv3 --kernel-trace` run per configuration and build: the solver is")
     print("created with `use_graph=False`, runs `vcycle(1)` and `vcycle(3)`, and prints `cycle_must_move()` of")
     print("parts 0 and 4; a `plain_*` configuration then runs one `block_vcycles` on 3 columns and one `apply_f32`")
-    print("and prints `block_must_move(3)` and `f32_must_move()`.  A list is every kernel launch of the process in")
+    print("and prints `block_must_move(3)` and `f32_must_move()`; the `slab*` configuration runs `slab_run` of parts")
+    print("1, 2 and 3 twice instead and prints `cycle_must_move()` of parts 1 to 3.  A list is every kernel launch of the process in")
     print("dispatch order (set-up included) as an index into the table at the end, `k*c` for c launches of k in a row.\n")
     print("| configuration | launches A | launches B | same (kernel, grid, workgroup) list | same bytes |")
     print("|---|---|---|---|---|")
