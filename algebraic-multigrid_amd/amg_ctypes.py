@@ -503,8 +503,9 @@ def duo_tile_rows(hb_l):
 
 
 def set_periodic_device_setup(on):
-    """Multigrid.tensor_periodic_dev builds on the device (1) or through the host constructor (0, the
-    default); process-wide, read when a solver is created, the same solver bit for bit."""
+    """Multigrid.tensor_periodic_dev and Multigrid.tensor_opdep_periodic_dev build on the device (1) or
+    through the host constructor (0, the default); process-wide, read when a solver is created, the same
+    solver bit for bit."""
     lib().amg_hip_set_periodic_device_setup(int(bool(on)))
 
 
@@ -996,8 +997,10 @@ class Multigrid:
                                   min_coarse=32, **opts):
         """Multigrid.tensor_opdep_periodic for a CSR matrix that sits on the device
         (amg_hip_create_tensor_opdep_periodic_dev); arguments as for Multigrid.tensor_dev.  The arrays are
-        checked on the device and the hierarchy is built by the host constructor, always:
-        setup_on_device() reports 0."""
+        checked on the device.  After set_periodic_device_setup(1) the hierarchy is built there too
+        (K-AxisWeights / K-AxisGalerkin with the seam; smoothers, layouts and silent fallbacks of
+        Multigrid.tensor_opdep_dev) and setup_on_device reports 1 unless it fell back; by default the
+        host constructor builds it and setup_on_device reports 0.  The same solver bit for bit either way."""
         return cls.tensor_dev(crow, col, val, b, dims, n_levels,
                               _opdep_per=(int(periodic_axes), cls._semi_rule(n_levels, axis_masks, 1.0, min_coarse)),
                               **opts)

@@ -7139,6 +7139,11 @@ __device__ __forceinline__ uint32_t ax_coord(uint32_t k, const AxisSetupGrid& g)
   tg_divmod(q, g.ny, g.inv_ny, &kz, &ky);
   return g.axis == 1u ? ky : kz;
 }
+// PER: the axis wraps (axis_opdep_row with periodic; m even and >= 4, so mE = m / 2).  The classes of
+// the collapse are (c_col - c) mod m = m - 1, 0, 1 -- the wrapped distance is a select on the plain one,
+// which lies in (-m, m) -- and every even point has both neighbours: both weights are divided and
+// stored whatever their value.  PER = false is the code without the seam.
+template <bool PER>
 __global__ __launch_bounds__(256) void axis_weights_kernel(AxisSetupGrid g, uint32_t n_even,
                                                            const int32_t* __restrict__ arp,
                                                            const int32_t* __restrict__ acol,
@@ -7155,13 +7160,14 @@ __global__ __launch_bounds__(256) void axis_weights_kernel(AxisSetupGrid g, uint
                                   : (g.axis == 1u ? (z * g.ny + c) * g.nx + x : (c * g.ny + y) * g.nx + x);
   double sm = 0.0, s0 = 0.0, sp = 0.0;
   for (int32_t p = arp[i], pe = arp[i + 1]; p < pe; ++p) {
-    const int32_t dc = (int32_t)ax_coord((uint32_t)acol[p], g) - (int32_t)c;
+    const int32_t d0 = (int32_t)ax_coord((uint32_t)acol[p], g) - (int32_t)c;
+    const int32_t dc = PER && d0 < 0 ? d0 + (int32_t)g.m : d0;
     const double v = aval[p];
-    if (dc == -1) sm += v;
+    if (dc == (PER ? (int32_t)g.m - 1 : -1)) sm += v;
     else if (dc == 0) s0 += v;
     else if (dc == 1) sp += v;
   }
-  const bool has_lo = c >= 2u, has_hi = c + 1u < g.m;
+  const bool has_lo = PER || c >= 2u, has_hi = PER || c + 1u < g.m;
   const double wlo = has_lo ? (-sm) / s0 : 0.0;
   const double whi = has_hi ? (-sp) / s0 : 0.0;
   // finite: |x| < inf; a NaN fails the comparison
@@ -7188,13 +7194,21 @@ static bool axis_setup_grid(int dim, const int64_t dims[3], int axis, AxisSetupG
   *n_even = ex * ey * ez;
   return true;
 }
-hipError_t launch_axis_weights(int dim, const int64_t dims[3], int axis, const int32_t* arp, const int32_t* acol,
-                               const double* aval, double* W, int32_t* first_bad, hipStream_t st) {
+// periodic: the solver's periodic axes; the seam form runs when `axis` is one of them (even, >= 4)
+hipError_t launch_axis_weights(int dim, const int64_t dims[3], int axis, uint32_t periodic, const int32_t* arp,
+                               const int32_t* acol, const double* aval, double* W, int32_t* first_bad, hipStream_t st) {
   AxisSetupGrid g;
   uint32_t n_even = 0;
   if (!axis_setup_grid(dim, dims, axis, &g, &n_even) || (reinterpret_cast<uintptr_t>(W) & 15u)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(axis_weights_kernel, dim3((n_even + 255u) / 256u), dim3(256), 0, st, g, n_even, arp, acol, aval, W,
-                     first_bad);
+  if (periodic >= (1u << dim)) return hipErrorInvalidValue;
+  if ((periodic >> axis) & 1u) {
+    if (g.m < 4u || (g.m & 1u)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(axis_weights_kernel<true>, dim3((n_even + 255u) / 256u), dim3(256), 0, st, g, n_even, arp, acol, aval,
+                       W, first_bad);
+  } else {
+    hipLaunchKernelGGL(axis_weights_kernel<false>, dim3((n_even + 255u) / 256u), dim3(256), 0, st, g, n_even, arp, acol, aval,
+                       W, first_bad);
+  }
   return hipGetLastError();
 }
 
@@ -7215,7 +7229,18 @@ hipError_t launch_axis_weights(int dim, const int64_t dims[3], int axis, const i
 //    R(I, i) * (A P)(i, J) for i ascending, first assigned, the rest added -- spgemm_rows' order.
 //    The multiplications by 1.0 are done.
 // The count pass (FILL = false) reads neither the values nor W.
-template <int SLOTS, bool FILL>
+//
+// PER (amg_hip_create_tensor_opdep_periodic_dev): g.per() holds EVERY periodic axis of the solver,
+// whether this level coarsens it or not, for K-TensorGalerkin's reason: a wrap entry of A on an axis
+// the level leaves alone still makes a min / max box span that axis.  On a periodic axis the reachable
+// columns are offsets from the group's own coordinate (tg_cols_per), and lane s takes the s-th column
+// of the cyclic interval in ascending flat index (tg_lane_col).  On the coarsened axis, when it wraps
+// (m even, >= 4): R's last row H = m / 2 - 1 has the fine points 0, m - 2, m - 1, ascending
+// (tg_fine), with W[2 e(0)] (w_lo of fine 0), W[2 e(m - 2) + 1] (w_hi of fine m - 2) and 1.0; every
+// row of R has three points; an even ka = 2 q of P has the columns (q - 1) mod (m / 2) (w_lo) and q
+// (w_hi), distinct since m / 2 >= 2.  A coarsened axis that does not wrap keeps the rule above bit for
+// bit inside a PER launch.  PER = false is the code without any of this.
+template <int SLOTS, bool FILL, bool PER>
 __global__ __launch_bounds__(256) void axis_galerkin_kernel(
     TensorGrid g, uint32_t axis, uint32_t mE, double inv_nx, double inv_ny, const int32_t* __restrict__ arp,
     const int32_t* __restrict__ acol, const double* __restrict__ aval, const double* __restrict__ W,
@@ -7235,18 +7260,26 @@ __global__ __launch_bounds__(256) void axis_galerkin_kernel(
   const uint32_t i0 = axis == 0u ? (K * g.ny + J) * g.nx + 2u * I
                                  : (axis == 1u ? (K * g.ny + 2u * J) * g.nx + I : (2u * K * g.ny + J) * g.nx + I);
   const uint32_t e0 = axis == 0u ? (K * g.ny + J) * mE + I : (axis == 1u ? (K * mE + J) * g.nx + I : row);
-  const uint32_t nt = 2u * H + 2u < m ? 3u : 2u;  // fine rows of R's row
+  // PER: the periodic axes, and whether this coarse row is the last one of the axis when it wraps
+  const bool px = PER && (g.per() & 1u), py = PER && (g.per() & 2u), pz = PER && (g.per() & 4u);
+  const bool seam = PER && ((g.per() >> axis) & 1u) && 2u * H + 2u == m;
+  const uint32_t ib = i0 - 2u * H * stride;  // PER: the fine index with the axis coordinate 0
+  const uint32_t nt = 2u * H + 2u < m || seam ? 3u : 2u;  // fine rows of R's row
   int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
+  if (PER) hi[0] = hi[1] = hi[2] = INT32_MIN;  // offsets may be negative
   if (s < nt) {
-    const uint32_t i = i0 + s * stride;
+    const uint32_t i = PER ? ib + tg_fine(H, s, seam) * stride : i0 + s * stride;
     for (int32_t p = arp[i], e = arp[i + 1]; p < e; ++p) {
       uint32_t kx, ky, kz, q;
       tg_divmod((uint32_t)acol[p], g.nx, inv_nx, &q, &kx);
       tg_divmod(q, g.ny, inv_ny, &kz, &ky);
       int32_t l[3], h[3];
-      tg_cols(kx, g.mx, g.cx, &l[0], &h[0]);
-      tg_cols(ky, g.my, g.cy, &l[1], &h[1]);
-      tg_cols(kz, g.mz, g.cz, &l[2], &h[2]);
+      if (px) tg_cols_per(kx, g.mx, g.cx, I, &l[0], &h[0]);
+      else tg_cols(kx, g.mx, g.cx, &l[0], &h[0]);
+      if (py) tg_cols_per(ky, g.my, g.cy, J, &l[1], &h[1]);
+      else tg_cols(ky, g.my, g.cy, &l[1], &h[1]);
+      if (pz) tg_cols_per(kz, g.mz, g.cz, K, &l[2], &h[2]);
+      else tg_cols(kz, g.mz, g.cz, &l[2], &h[2]);
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         lo[a] = l[a] < lo[a] ? l[a] : lo[a];
@@ -7281,12 +7314,21 @@ __global__ __launch_bounds__(256) void axis_galerkin_kernel(
     Jc[0] = lo[0] + (int32_t)(s % bx);
     Jc[1] = lo[1] + (int32_t)((s / bx) % by);
     Jc[2] = lo[2] + (int32_t)(s / (bx * by));
+    if (px) Jc[0] = tg_lane_col((int32_t)(s % bx), lo[0], (int32_t)bx, (int32_t)I, (int32_t)g.mx);
+    if (py) Jc[1] = tg_lane_col((int32_t)((s / bx) % by), lo[1], (int32_t)by, (int32_t)J, (int32_t)g.my);
+    if (pz) Jc[2] = tg_lane_col((int32_t)(s / (bx * by)), lo[2], (int32_t)(vol / (bx * by)), (int32_t)K, (int32_t)g.mz);
     const int32_t Ja = axis == 0u ? Jc[0] : (axis == 1u ? Jc[1] : Jc[2]);
+    const bool pa = PER && ((g.per() >> axis) & 1u);  // the coarsened axis wraps
     for (uint32_t t = 0; t < nt; ++t) {
-      const uint32_t i = i0 + t * stride;
+      const uint32_t i = PER ? ib + tg_fine(H, t, seam) * stride : i0 + t * stride;
       double r = 1.0;  // R(I, i)
-      if (FILL && t == 0u) r = W[2u * e0 + 1u];
-      if (FILL && t == 2u) r = W[2u * (e0 + stride)];
+      if (PER && seam) {  // fine 0 (its w_lo), fine m - 2 (its w_hi), fine m - 1
+        if (FILL && t == 0u) r = W[2u * (e0 - H * stride)];
+        if (FILL && t == 1u) r = W[2u * e0 + 1u];
+      } else {
+        if (FILL && t == 0u) r = W[2u * e0 + 1u];
+        if (FILL && t == 2u) r = W[2u * (e0 + stride)];
+      }
       bool hit_i = false;
       double ap = 0.0;  // (A P)(i, J)
       for (int32_t p = arp[i], e = arp[i + 1]; p < e; ++p) {
@@ -7300,7 +7342,9 @@ __global__ __launch_bounds__(256) void axis_galerkin_kernel(
         for (uint32_t a = 0; a < 3u; ++a) other = other && (a == axis || (int32_t)kc[a] == Jc[a]);
         const int32_t half = (int32_t)(ka >> 1);
         const bool odd = (ka & 1u) != 0u;
-        const bool at_lo = !odd && Ja == half - 1, at_hi = !odd && Ja == half;  // Ja lies in [0, floor(m / 2))
+        // Ja lies in [0, floor(m / 2)); pa: the low neighbour of ka = 0 is the last coarse point
+        const int32_t below = pa && half == 0 ? (int32_t)(m >> 1) - 1 : half - 1;
+        const bool at_lo = !odd && Ja == below, at_hi = !odd && Ja == half;
         if (other && ((odd && Ja == half) || at_lo || at_hi)) {
           if (FILL) {
             double w = 1.0;
@@ -7336,25 +7380,38 @@ __global__ __launch_bounds__(256) void axis_galerkin_kernel(
     oval[at] = acc;
   }
 }
-hipError_t launch_axis_galerkin(bool fill, int dim, const int64_t dims[3], int axis, const int32_t* arp,
-                                const int32_t* acol, const double* aval, const double* W, int32_t* cnt,
-                                const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow, hipStream_t st) {
+// periodic: the solver's periodic axes.  As in launch_tensor_galerkin the kernel needs every one of
+// them, also those this level does not coarsen, so the seam bits are `periodic`, not `periodic & mask`.
+hipError_t launch_axis_galerkin(bool fill, int dim, const int64_t dims[3], int axis, uint32_t periodic,
+                                const int32_t* arp, const int32_t* acol, const double* aval, const double* W,
+                                int32_t* cnt, const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
+                                hipStream_t st) {
   TensorGrid g;
   AxisSetupGrid ag;
   uint32_t n_even = 0;
-  if (!axis_setup_grid(dim, dims, axis, &ag, &n_even) || !tensor_grid(dim, dims, 1u << axis, 0u, 0u, &g))
+  // tensor_grid: a coarsened periodic axis is even and >= 4
+  if (!axis_setup_grid(dim, dims, axis, &ag, &n_even) || !tensor_grid(dim, dims, 1u << axis, 0u, periodic, &g))
     return hipErrorInvalidValue;
+  g.sides = periodic << 8;
   const uint32_t nH = g.mx * g.my * g.mz;
-#define AG_LAUNCH(SLOTS, FILL)                                                                                    \
-  hipLaunchKernelGGL((axis_galerkin_kernel<SLOTS, FILL>), dim3((nH + 256u / SLOTS - 1u) / (256u / SLOTS)), dim3(256), \
+#define AG_LAUNCH(SLOTS, FILL, PER)                                                                                    \
+  hipLaunchKernelGGL((axis_galerkin_kernel<SLOTS, FILL, PER>), dim3((nH + 256u / SLOTS - 1u) / (256u / SLOTS)), dim3(256), \
                      0, st, g, (uint32_t)axis, ag.mE, ag.inv_nx, ag.inv_ny, arp, acol, aval, W, cnt, orp, ocol, oval, \
                      overflow)
-  if (dim == 3) {
-    if (fill) AG_LAUNCH(32, true);
-    else AG_LAUNCH(32, false);
+  if (periodic) {
+    if (dim == 3) {
+      if (fill) AG_LAUNCH(32, true, true);
+      else AG_LAUNCH(32, false, true);
+    } else {
+      if (fill) AG_LAUNCH(16, true, true);
+      else AG_LAUNCH(16, false, true);
+    }
+  } else if (dim == 3) {
+    if (fill) AG_LAUNCH(32, true, false);
+    else AG_LAUNCH(32, false, false);
   } else {
-    if (fill) AG_LAUNCH(16, true);
-    else AG_LAUNCH(16, false);
+    if (fill) AG_LAUNCH(16, true, false);
+    else AG_LAUNCH(16, false, false);
   }
 #undef AG_LAUNCH
   return hipGetLastError();

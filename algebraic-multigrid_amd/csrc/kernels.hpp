@@ -598,15 +598,22 @@ hipError_t launch_tensor_galerkin(bool fill, int dim, const int64_t dims[3], uin
 // `dims`, for the level that coarsens `axis` (host_setup.hpp: axis_opdep_P's weight pass, same bits,
 // -0.0 included).  W: 2 (n_l - n_{l+1}) doubles, 16-byte aligned, every one of them written.
 // *first_bad (INT32_MAX before the launch) = the smallest row axis_opdep_row refuses.  n_l < 2^28.
-hipError_t launch_axis_weights(int dim, const int64_t dims[3], int axis, const int32_t* arp, const int32_t* acol,
-                               const double* aval, double* W, int32_t* first_bad, hipStream_t st);
+// periodic: the solver's periodic axes.  When `axis` is one of them (its length even and >= 4) the
+// collapse takes the distance mod m and every even point has both weights (axis_opdep_row with
+// periodic, same bits); otherwise the kernel without the seam runs.
+hipError_t launch_axis_weights(int dim, const int64_t dims[3], int axis, uint32_t periodic, const int32_t* arp,
+                               const int32_t* acol, const double* aval, double* W, int32_t* first_bad, hipStream_t st);
 // K-AxisGalerkin (setup): A_H = R (A P) for the one-axis pair with the weights W, count pass / fill
 // pass and *overflow as for launch_tensor_galerkin.  Same entry order and bits as galerkin_csr on
 // axis_P_from_weights(W) and its transpose; the structure is geometric (an entry for every
 // neighbour that exists, zero weights included).  The count pass reads neither aval nor W.
-hipError_t launch_axis_galerkin(bool fill, int dim, const int64_t dims[3], int axis, const int32_t* arp,
-                                const int32_t* acol, const double* aval, const double* W, int32_t* cnt,
-                                const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow, hipStream_t st);
+// periodic: the solver's periodic axes, every one of them whether this level coarsens it or not (as
+// for launch_tensor_galerkin); W and P are then axis_opdep_P's with periodic on a coarsened axis that
+// wraps.  0 launches the kernel without the seam.
+hipError_t launch_axis_galerkin(bool fill, int dim, const int64_t dims[3], int axis, uint32_t periodic,
+                                const int32_t* arp, const int32_t* acol, const double* aval, const double* W,
+                                int32_t* cnt, const int32_t* orp, int32_t* ocol, double* oval, int32_t* overflow,
+                                hipStream_t st);
 // K-AxisStrength (setup): out[a] = bits of max |a_ij| over the entries of CSR(A) on the grid `dims`
 // whose column is the row's neighbour along axis a alone (host_setup.hpp: tensor_axis_strength,
 // same bits); 0.0 when there is none.  out: 3 words, initialised by the launch.

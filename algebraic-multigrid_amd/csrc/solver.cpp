@@ -218,7 +218,7 @@ hipError_t device_galerkin(const DevCsr& A, int64_t n_H, DevCsr* AH, Sparse* hos
 // kernel's lane group holds; hipErrorInvalidValue: the product is beyond int32 indexing.  Either
 // way the caller takes the host path.
 // axis >= 0 (mask = 1 << axis): the one-axis pair with the weights W on the device (K-AxisGalerkin)
-// instead of the tensor-product pair.
+// instead of the tensor-product pair; `periodic` then selects its seam form (sides: not used).
 hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3], uint32_t mask, uint32_t sides,
                                   uint32_t periodic, int64_t n_H,
                                   DevCsr* AH,
@@ -231,7 +231,7 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if ((e = total.alloc(sizeof(int64_t))) != hipSuccess) return e;
   if ((e = ovf.alloc(sizeof(int32_t))) != hipSuccess) return e;
   if ((e = hipMemset(ovf.p, 0, sizeof(int32_t))) != hipSuccess) return e;
-  e = axis >= 0 ? launch_axis_galerkin(false, dim, dims, axis, A.rowptr(), A.col(), A.v(), W, cnt.as<int32_t>(), nullptr,
+  e = axis >= 0 ? launch_axis_galerkin(false, dim, dims, axis, periodic, A.rowptr(), A.col(), A.v(), W, cnt.as<int32_t>(), nullptr,
                                        nullptr, nullptr, ovf.as<int32_t>(), nullptr)
                 : launch_tensor_galerkin(false, dim, dims, mask, sides, periodic, A.rowptr(), A.col(), A.v(), cnt.as<int32_t>(), nullptr,
                                          nullptr, nullptr, ovf.as<int32_t>(), nullptr);
@@ -248,7 +248,7 @@ hipError_t device_tensor_galerkin(const DevCsr& A, int dim, const int64_t dims[3
   if (nnz >= ((int64_t)1 << 31) - 1) return hipErrorInvalidValue;
   if ((e = AH->idx.alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
   if ((e = AH->val.alloc(sizeof(double) * std::max<int64_t>(nnz, 1))) != hipSuccess) return e;
-  e = axis >= 0 ? launch_axis_galerkin(true, dim, dims, axis, A.rowptr(), A.col(), A.v(), W, nullptr, AH->ptr.as<int32_t>(),
+  e = axis >= 0 ? launch_axis_galerkin(true, dim, dims, axis, periodic, A.rowptr(), A.col(), A.v(), W, nullptr, AH->ptr.as<int32_t>(),
                                        AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr)
                 : launch_tensor_galerkin(true, dim, dims, mask, sides, periodic, A.rowptr(), A.col(), A.v(), nullptr, AH->ptr.as<int32_t>(),
                                          AH->idx.as<int32_t>(), AH->val.as<double>(), ovf.as<int32_t>(), nullptr);
@@ -1658,8 +1658,9 @@ int g_tail_fusion = [] {
   return (e && *e == '1') ? 1 : 0;
 }();
 // amg_hip_set_periodic_device_setup / AMG_HIP_PERIODIC_DEVICE_SETUP=1: amg_hip_create_tensor_periodic_dev
-// builds on the device.  The same solver bit for bit; 0 by default only because an earlier test pins
-// amg_hip_setup_on_device == 0 for that entry point ("Periodic axes").
+// and amg_hip_create_tensor_opdep_periodic_dev build on the device.  The same solvers bit for bit; 0 by
+// default only because earlier tests pin amg_hip_setup_on_device == 0 for those entry points
+// ("Periodic axes", "Operator-dependent interpolation").
 int g_periodic_device_setup = [] {
   const char* e = std::getenv("AMG_HIP_PERIODIC_DEVICE_SETUP");
   return (e && *e == '1') ? 1 : 0;
@@ -3038,7 +3039,8 @@ struct SemiRule {
   bool opdep = false;
   const char* opdep_who = "amg_hip_create_tensor_opdep: ";  // the entry point a refused row is reported under
   // amg_hip_create_tensor_opdep_periodic(_dev): the spec's periodic axes are checked on top of the
-  // rule, a coarsened periodic axis takes the seam form of axis_opdep_P, and the set-up runs on the host
+  // rule and a coarsened periodic axis takes the seam form of axis_opdep_P; the _dev form builds on the
+  // host unless amg_hip_set_periodic_device_setup(1) is in force (K-AxisWeights / K-AxisGalerkin PER)
   bool opdep_periodic = false;
 };
 // a one-level solver's coarsest right-hand side is the caller's b, which the pinned solve must not alter
@@ -4122,8 +4124,8 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, const Hierarchy
         int32_t first_bad = none;
         HIP_TRY(hipMemcpy(stats.p, &none, sizeof(int32_t), hipMemcpyHostToDevice));
         if (timing) tk[0] = std::chrono::steady_clock::now();  // the copy above has synchronised
-        HIP_TRY(launch_axis_weights(dim, L.dims, L.axis, cur.rowptr(), cur.col(), cur.v(), L.axis_W_dev.as<double>(),
-                                    stats.as<int32_t>(), nullptr));
+        HIP_TRY(launch_axis_weights(dim, L.dims, L.axis, L.tper, cur.rowptr(), cur.col(), cur.v(),
+                                    L.axis_W_dev.as<double>(), stats.as<int32_t>(), nullptr));
         HIP_TRY(hipMemcpy(&first_bad, stats.p, sizeof(int32_t), hipMemcpyDeviceToHost));
         if (timing) tk[1] = std::chrono::steady_clock::now();
         if (first_bad != none) {  // that one row to the host, worded by the host constructor's code
@@ -4137,7 +4139,8 @@ amg_hip_status device_level_loop(amg_hip_solver* s, DevCsr& cur, const Hierarchy
           }
           const int64_t stride = L.axis == 0 ? 1 : (L.axis == 1 ? L.dims[0] : L.dims[0] * L.dims[1]);
           double w2[2];
-          std::string we = axis_opdep_row(first_bad, ci.data(), cv.data(), rp[1] - rp[0], stride, L.dims[L.axis], L.axis, w2);
+          std::string we = axis_opdep_row(first_bad, ci.data(), cv.data(), rp[1] - rp[0], stride, L.dims[L.axis], L.axis, w2,
+                                          L.axis_periodic());
           if (we.empty()) we = "row " + std::to_string(first_bad) + ": refused by K-AxisWeights";
           return fail(AMG_HIP_EINVAL, std::string(semi->opdep_who) + "level " + std::to_string(l) + ": " + we);
         }
@@ -5383,7 +5386,9 @@ static amg_hip_status build_tensor_user_device(const std::string& who, int64_t n
 // amg_hip_create_tensor_periodic_dev (h.periodic_ctor; rule: its explicit masks, or null).  With
 // amg_hip_set_periodic_device_setup(1) the periodic level loop runs on the device with the mask
 // (K-TensorGalerkin's PER form); with the default 0 its hierarchy is built on the host (the checked
-// arrays take the host constructor) and the level loop on the device is never entered.
+// arrays take the host constructor) and the level loop on the device is never entered.  The same
+// switch governs amg_hip_create_tensor_opdep_periodic_dev (rule->opdep_periodic): on, its levels take
+// the PER forms of K-AxisWeights and K-AxisGalerkin, with amg_hip_create_tensor_opdep_dev's fallbacks.
 static amg_hip_status create_tensor_dev(const std::string& who, int64_t n, const int32_t* rowptr_dev,
                                         const int32_t* col_dev, const double* val_dev, const double* b_dev,
                                         int32_t n_levels, HierarchySpec h, const SemiRule* rule,
@@ -5411,7 +5416,7 @@ static amg_hip_status create_tensor_dev(const std::string& who, int64_t n, const
   amg_hip_options od = o;
   if (h.periodic_ctor && !g_periodic_device_setup) od.host_galerkin = 1;  // copy + check only
   if (rule && rule->opdep && !g_axis_stencil) od.host_galerkin = 1;       // transfer kind 0 needs CSR(P), CSR(R): host
-  if (rule && rule->opdep_periodic) od.host_galerkin = 1;  // K-AxisWeights / K-AxisGalerkin know no seam: copy + check only
+  if (rule && rule->opdep_periodic && !g_periodic_device_setup) od.host_galerkin = 1;  // copy + check only
   amg_hip_status r = build_tensor_user_device(who, n, rowptr_dev, col_dev, val_dev, b_dev, n_levels, h, od, out,
                                               &unsupported);
   if (r != AMG_HIP_OK || !unsupported) return r;

@@ -338,10 +338,12 @@ int32_t amg_hip_duo_owned(int32_t tile, int32_t tile_rows, int32_t* out);
 /* rows of level l per tile that the K-Duo launchers use under half-bandwidth hb_l: 254 or 510 */
 int32_t amg_hip_duo_tile_rows(int32_t hb_l);
 
-/* amg_hip_create_tensor_periodic_dev builds its hierarchy on the device (K-TensorGalerkin with the
- * seam) instead of downloading to the host constructor.  Process-wide, read when a solver is created;
- * default 0 (AMG_HIP_PERIODIC_DEVICE_SETUP=1 in the environment turns it on).  The same solver bit
- * for bit either way; amg_hip_setup_on_device tells the two apart.                                 */
+/* Both periodic _dev constructors build their hierarchies on the device instead of downloading to
+ * the host constructor: amg_hip_create_tensor_periodic_dev (K-TensorGalerkin with the seam) and
+ * amg_hip_create_tensor_opdep_periodic_dev (K-AxisWeights and K-AxisGalerkin with the seam).
+ * Process-wide, read when a solver is created; default 0 (AMG_HIP_PERIODIC_DEVICE_SETUP=1 in the
+ * environment turns it on).  The same solver bit for bit either way; amg_hip_setup_on_device tells
+ * the two apart.                                                                                   */
 void amg_hip_set_periodic_device_setup(int32_t on);
 
 /* The single-precision entry points (amg_hip_apply_f32, amg_hip_pcg_mixed, amg_hip_f32_*) accept
@@ -804,10 +806,25 @@ amg_hip_status amg_hip_create_tensor_opdep_dev(int64_t n, const int32_t* rowptr_
                                                int64_t min_coarse, const amg_hip_options* opts, amg_hip_solver** out);
 /* amg_hip_create_tensor_opdep_periodic for a caller's matrix in DEVICE memory (CSR, as for
  * amg_hip_create_tensor_opdep_dev).  The argument checks of the host constructor in the same words
- * under this name, plus null arrays, before the device is touched; then K-CsrCheck.  Then the arrays
- * are downloaded, transposed on the host and given to amg_hip_create_tensor_opdep_periodic -- the
- * silent host path, always: amg_hip_setup_on_device reports 0 and the solver is the host
- * constructor's.  K-AxisWeights / K-AxisGalerkin with the seam are not written yet.              */
+ * under this name, plus null arrays, before the device is touched; then K-CsrCheck, first and
+ * whatever the switch says.
+ * With amg_hip_set_periodic_device_setup(1): amg_hip_create_tensor_opdep_dev's level loop on the
+ * device with the periodic mask.  K-AxisWeights with the seam collapses the rows of a coarsened
+ * periodic axis by the axis distance mod m (every even point has both weights, kept whatever their
+ * value), straight into the array the periodic forms of K-AxisRestrict / K-AxisProlong read;
+ * K-AxisGalerkin with the seam forms A_{l+1} with R's last row of the axis (fine points 0, m - 2,
+ * m - 1) and the wrap entries of A on every periodic axis, coarsened on the level or not.  Transfer
+ * kind 3 on every level; the automatic rule leaves out a periodic axis that is odd or shorter than 4,
+ * as on the host; natural_sides, singular and amg_hip_set_mean_projection are honoured as on the
+ * host; cyclic_lines = 1 stays refused.  Same smoothers, layouts and silent fallbacks to the host
+ * constructor as amg_hip_create_tensor_opdep_dev; amg_hip_setup_on_device reports 1 unless it fell
+ * back.  A refused row is AMG_HIP_EINVAL with the host constructor's text under this name.
+ * periodic_axes = 0 then gives amg_hip_create_tensor_opdep_dev's solver, built on the device.
+ * With the switch off (the default): the arrays are downloaded, transposed on the host and given to
+ * amg_hip_create_tensor_opdep_periodic -- the silent host path, always -- and
+ * amg_hip_setup_on_device reports 0.
+ * Either way the solver equals the host constructor's bit for bit: axes, dims, weights (-0.0
+ * included), P, R, level matrices, and every cycle, apply, PCG, mixed and block call.            */
 amg_hip_status amg_hip_create_tensor_opdep_periodic_dev(int64_t n, const int32_t* rowptr_dev, const int32_t* col_dev,
                                                         const double* val_dev, const double* b_dev, int32_t dim,
                                                         const int64_t* dims /* 3, host */, int32_t periodic_axes,
@@ -837,8 +854,9 @@ amg_hip_status amg_hip_create_tensor_periodic_dev(int64_t n, const int32_t* rowp
                                                   const amg_hip_options* opts, amg_hip_solver** out);
 /* *on = 1: the hierarchy was built by a device-only path (amg_hip_create_poisson,
  * amg_hip_create_poisson_window, amg_hip_create_poisson_tensor, amg_hip_create_tensor_dev,
- * amg_hip_create_tensor_semi_dev, amg_hip_create_tensor_opdep_dev, and amg_hip_create_tensor_periodic_dev under
- * amg_hip_set_periodic_device_setup(1), when they did not fall back),
+ * amg_hip_create_tensor_semi_dev, amg_hip_create_tensor_opdep_dev, and amg_hip_create_tensor_periodic_dev
+ * and amg_hip_create_tensor_opdep_periodic_dev under amg_hip_set_periodic_device_setup(1), when they
+ * did not fall back),
  * 0: by the host constructor -- every other entry point and the silent fallbacks.  Also on
  * host_only solvers (0).                                                                        */
 amg_hip_status amg_hip_setup_on_device(const amg_hip_solver* s, int32_t* on);

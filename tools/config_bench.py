@@ -17,6 +17,7 @@ usage: config_bench.py <dim> <n> <levels> <smoother> [cycles]     one configurat
        config_bench.py opdep10 <nx> <ny> <nz> [csr]                ten cycles of one tensor_opdep hierarchy on that operator (kernel traces)
        config_bench.py opdep-setup [<nx> <ny> <nz>]                set-up seconds of tensor_opdep on that operator assembled on the GPU, explicit masks x, y, (z,) x, ...: the host constructor and amg_hip_create_tensor_opdep_dev alternating, best of three
        config_bench.py opdep-periodic [<nx> <ny> <nz>]             that operator with every axis periodic (wrap edges, singular, b of zero mean), explicit masks x, y, (z,) x, ...: tensor_opdep (wrap entries skipped), tensor_periodic (fixed weights) and tensor_opdep_periodic (the seam) alternating, all through the host constructors: PCG to 1e-8, ms per V-cycle, and the new solver with CSR transfers (amg_hip_set_axis_stencil(0))
+       config_bench.py opdep-periodic-setup [<nx> <ny> <nz>]       set-up seconds of tensor_opdep_periodic_dev on the fully periodic jump operator assembled on the GPU, explicit masks x, y, (z,) x, ..., with set_periodic_device_setup off (host constructor) and on (device), legs alternate, best of three; next to them tensor_opdep_dev on the open-box operator of the same grid
        config_bench.py natural [<nx> <ny> <nz>]                    PCG to 1e-8 on a diffusion operator without a Dirichlet side (singular) and with Dirichlet on x-low only, through tensor_dev: natural_sides = 0 against the proper side mask (legs alternate)
        config_bench.py singular [<nx> <ny> <nz>]                   PCG to 1e-8 on that operator without a Dirichlet side, one solver: mean projection (amg_hip_set_mean_projection) off and on with the consistent b and on with b + 1e-6, legs alternate; the time added per iteration next to an estimate from the tree reduction's rate in the same run
        config_bench.py periodic [<nx> <ny> <nz>]                   PCG to 1e-8 on a diffusion operator with every axis periodic (singular): the periodic hierarchy (tensor_periodic_dev) against natural_sides on every side (tensor_dev), both built by the host constructor, legs alternate
@@ -867,6 +868,94 @@ def run_opdep_setup(dims, reps=3):
             mg.close()
     print(f"opdep-setup {tag} {L} levels: best host {best['host']:.3f} s, best device {best['device']:.3f} s, "
           f"ratio {best['host'] / best['device']:.1f}", flush=True)
+
+
+def torch_jump_periodic(dims, block=8, contrast=4, seed=7):
+    """numpy_jump_periodic's operator (every axis wraps, singular) assembled on the GPU: (crow, col, val, b) as
+    torch_jump, the columns of a row ascending; b random with zero mean.  The edge (i, (i + 1) mod m) takes the
+    k of the block of its lower endpoint i, the wrap edge that of node m - 1."""
+    import numpy as np
+    import torch
+    dev = torch.device("cuda")
+    dim = len(dims)
+    n = int(np.prod(dims))
+    nb = [(m + block - 1) // block for m in dims]
+    kb = 10.0 ** np.random.default_rng(seed).integers(0, contrast + 1, size=nb[::-1]).astype(np.float64)
+    kb = torch.from_numpy(kb.ravel()).to(dev)
+    i = torch.arange(n, device=dev)
+    stride = [1, dims[0], dims[0] * dims[1]][:dim]
+    coord = [(i // stride[a]) % dims[a] for a in range(dim)]
+    blk = torch.zeros(n, dtype=torch.int64, device=dev)
+    for a in reversed(range(dim)):
+        blk = blk * nb[a] + coord[a] // block
+    knode = kb[blk]
+    w = 2 * dim + 1
+    cols = torch.zeros((n, w), dtype=torch.int64, device=dev)
+    vals = torch.zeros((n, w), dtype=torch.float64, device=dev)
+    diag = torch.zeros(n, dtype=torch.float64, device=dev)
+    for a in range(dim):
+        span = (dims[a] - 1) * stride[a]
+        lo = torch.where(coord[a] > 0, i - stride[a], i + span)
+        hi = torch.where(coord[a] < dims[a] - 1, i + stride[a], i - span)
+        k_lo, k_hi = knode[lo], knode
+        diag = diag + k_lo + k_hi
+        cols[:, 2 * a], vals[:, 2 * a] = lo, -k_lo
+        cols[:, 2 * a + 1], vals[:, 2 * a + 1] = hi, -k_hi
+    cols[:, 2 * dim], vals[:, 2 * dim] = i, diag
+    cols, order = torch.sort(cols, dim=1)
+    vals = torch.gather(vals, 1, order)
+    crow = (torch.arange(n + 1, device=dev) * w).to(torch.int32)
+    g = torch.Generator(device=dev)
+    g.manual_seed(99)
+    b = torch.randn(n, generator=g, device=dev, dtype=torch.float64)
+    return crow, cols.reshape(-1).to(torch.int32).contiguous(), vals.reshape(-1).contiguous(), b - b.mean()
+
+
+def run_opdep_periodic_setup(dims, reps=3):
+    """Set-up seconds of Multigrid.tensor_opdep_periodic_dev on the fully periodic jump operator
+    (torch_jump_periodic, contrast 1e4, singular, assembled on the GPU), explicit masks x, y, (z,) x, ...
+    (periodic_cyclic_masks), true Jacobi 2+2, with amg_hip_set_periodic_device_setup off -- the arrays are
+    downloaded and take the host constructor -- and on -- K-AxisWeights / K-AxisGalerkin with the seam.  The
+    legs alternate in one process, `reps` repeats, best of them; wall time around the constructor, closed by
+    a device synchronise.  Next to them, in the same loop, Multigrid.tensor_opdep_dev on the open-box jump
+    operator (torch_jump) of the same grid with the same masks: the set-up without a seam.  With
+    AMG_HIP_TIMING set the library writes its laps to stderr, the two kernels per level among them."""
+    import torch
+    dim = len(dims)
+    per = (1 << dim) - 1
+    arrays = torch_jump_periodic(dims)
+    box = torch_jump(dims)
+    torch.cuda.synchronize()
+    masks = periodic_cyclic_masks(dims)
+    L = len(masks) + 1
+    jac = TENSOR_KW["jacobi"]
+    tag = " x ".join(str(d) for d in dims) + " periodic jump 1e4"
+    legs = (("switch off", 0, 0, lambda: amg.Multigrid.tensor_opdep_periodic_dev(*arrays, dims, L, per, axis_masks=masks,
+                                                                                 singular=True, **jac)),
+            ("switch on", 1, 1, lambda: amg.Multigrid.tensor_opdep_periodic_dev(*arrays, dims, L, per, axis_masks=masks,
+                                                                                singular=True, **jac)),
+            ("open box tensor_opdep_dev", 0, 1, lambda: amg.Multigrid.tensor_opdep_dev(*box, dims, L, axis_masks=masks,
+                                                                                       **jac)))
+    best = {}
+    try:
+        for rep_ in range(reps):
+            for name, on, on_device, make in legs:
+                amg.set_periodic_device_setup(on)
+                t0 = time.perf_counter()
+                mg = make()
+                mg.sync()
+                dt = time.perf_counter() - t0
+                assert mg.setup_on_device == on_device, (name, mg.setup_on_device)
+                best[name] = min(best.get(name, dt), dt)
+                kinds = sorted(set(mg.level_transfer_kind(l) for l in range(L - 1)))
+                print(f"opdep-periodic-setup {tag} {L} levels, {name} rep {rep_}: {dt:.3f} s (setup_on_device "
+                      f"{mg.setup_on_device}, transfer kinds {kinds}, coarsest {mg.get_n_dofs(L - 1)} dofs)", flush=True)
+                mg.close()
+    finally:
+        amg.set_periodic_device_setup(0)
+    off, on, box_t = best["switch off"], best["switch on"], best["open box tensor_opdep_dev"]
+    print(f"opdep-periodic-setup {tag} {L} levels: best switch off {off:.3f} s, best switch on {on:.3f} s, ratio "
+          f"{off / on:.1f}; open box tensor_opdep_dev {box_t:.3f} s, switch on / open box {on / box_t:.2f}", flush=True)
 
 
 def run_natural(dims, reps=3, rtol=1e-8, max_iters=300):
@@ -1786,6 +1875,16 @@ elif len(sys.argv) > 1 and sys.argv[1] == "opdep-setup":
     else:
         run_opdep_setup((2048, 2048))
         run_opdep_setup((128, 128, 128))
+elif len(sys.argv) > 1 and sys.argv[1] == "opdep-periodic-setup":
+    # profiles/opdep_periodic_setup.txt
+    os.environ.setdefault("AMG_HIP_TIMING", "1")
+    import torch  # noqa: F401  (before the library is loaded: INTEGRATION.md, section 2)
+    if len(sys.argv) > 4:
+        d = tuple(int(x) for x in sys.argv[2:5])
+        run_opdep_periodic_setup(d if d[2] > 1 else d[:2])
+    else:
+        run_opdep_periodic_setup((2048, 2048))
+        run_opdep_periodic_setup((128, 128, 128))
 elif len(sys.argv) > 4 and sys.argv[1] == "opdep10":    # ten cycles of one hierarchy (kernel traces)
     d = tuple(int(x) for x in sys.argv[2:5])
     d = d if d[2] > 1 else d[:2]
